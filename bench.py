@@ -361,9 +361,14 @@ def main(argv=None):
                     help="steps per launch of the render kernel (at N ranks a step is N frames, so a launch covers N x this many frames: "
                          "this many full frames' worth of paths in flight on every GPU; 1 = one step per launch)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only for rehearsals: tests/, or a 1-GPU box)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed -- the accumulator after the last timed step, the gathered image at N > 1 "
+                         "(rank 0's own rows with --no-gather) -- as DIR/accum.npy (float32, H x W x 4), for comparing two builds output for output")
     ap.add_argument("--device-map", default="", help="rehearsal aid: comma-separated HIP ordinal per local rank (e.g. 0,0 runs two ranks on one GPU; "
                                                      "RCCL needs distinct GPUs, so combine with --backend gloo --no-gather)")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # self-launch: before torch.cuda / libglrtx are touched in this process
@@ -518,6 +523,12 @@ def main(argv=None):
     st = types.SimpleNamespace(kernel_ms_total=st1.kernel_ms_total - st0.kernel_ms_total, kernel_launches=st1.kernel_launches - st0.kernel_launches,
                                launches=st1.launches - st0.launches, accumulate_ms_total=getattr(st1, "accumulate_ms_total", 0.0) - getattr(st0, "accumulate_ms_total", 0.0),
                                node_fetch_last=getattr(st1, "node_fetch_last", 0))
+    # --dump-outputs: what the timed path handed back after its last step, copied to the host now (the measurements below render into the same accumulator) and
+    # written after the result line.  Scene, seeds and launch plan depend on the arguments alone, so equal arguments give equal inputs from run to run.
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        out_img = img if img is not None else R.accum[:len(ys)]
+        dumped = {"accum": np.array(out_img.detach().cpu().numpy(), dtype=np.float32, order="C", copy=True)}  # (a copy: .cpu() of a host tensor is the tensor itself)
     del img
     if world > 1:
         td.all_reduce(same, op=td.ReduceOp.MIN)
@@ -997,6 +1008,12 @@ def main(argv=None):
             "cpu_baseline": cpu_baseline,
         }
         print(json.dumps(out), flush=True)
+        if dumped is not None:
+            dump_dir = pathlib.Path(args.dump_outputs)
+            dump_dir.mkdir(parents=True, exist_ok=True)
+            assert sum(a.nbytes for a in dumped.values()) <= 64 << 20, "--dump-outputs: more than 64 MB"
+            for name, a in dumped.items():
+                np.save(dump_dir / f"{name}.npy", a)
 
     R.close()
     if world > 1:

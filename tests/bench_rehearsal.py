@@ -143,4 +143,14 @@ if __name__ == "__main__":
                 img[3, 5, 1] += 1.0
             return img
         dist.RowGather.gather_to_root = corrupt
+
+    # Every rank here is a CPU process, but torch.distributed.barrier() first asks the HIP runtime for an accelerator (torch._C._get_accelerator), which
+    # opens the GPU in every rank on a machine that has one: eight ranks alone exceed what one GPU should have open at once.  A gloo all_reduce of a CPU
+    # scalar is the same rendezvous without touching the device.
+    import torch
+    import torch.distributed as td
+
+    def cpu_barrier(group=None, async_op=False, device_ids=None):
+        return td.all_reduce(torch.zeros(1), group=group, async_op=async_op)
+    td.barrier = cpu_barrier
     bench.main()

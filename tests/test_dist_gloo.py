@@ -191,6 +191,31 @@ def test_bench_single_rank_flow_rehearsed_on_cpu():
     assert abs(out["config"]["rays_reference_equivalent_per_frame"] * steps - rays) < 0.5
 
 
+def test_bench_dump_outputs_writes_the_accumulator_of_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: after the timed steps bench.py writes the accumulator they left (warm-up frames + timed frames, accumulated from cleared) as
+    DIR/accum.npy, float32, before the extra measurements render into it -- here against the same frames accumulated by the oracle directly."""
+    root = pathlib.Path(__file__).resolve().parents[1]
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "GLRT_REHEARSAL_OUT")}
+    env.update(OMP_NUM_THREADS="1")
+    steps, warm = 3, 2
+    r = subprocess.run([sys.executable, str(root / "tests" / "bench_rehearsal.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warm),
+                        "--steps-per-launch", "2", "--config", "rehearsal", "--backend", "gloo", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / "out")],
+                       capture_output=True, text=True, timeout=600, env=env, cwd=str(root))
+    assert r.returncode == 0, r.stderr[-3000:]
+    out = json.loads([ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")][0])
+    assert out["steps"] == steps and out["ms_per_step"] > 0
+    assert sorted(p.name for p in (tmp_path / "out").iterdir()) == ["accum.npy"]
+    got = np.load(tmp_path / "out" / "accum.npy")
+    from glrt_amd import host
+    from tests.bench_rehearsal import small_config
+    sc, pr = small_config()
+    ref = np.zeros((pr["height"], pr["width"], 4), np.float32)
+    for f in range(warm + steps):
+        pt_oracle.render(sc, dict(pr, seed=host.frame_seed(f)), accum=ref, threads=2)
+    assert got.dtype == np.float32 and got.shape == ref.shape
+    assert np.array_equal(got.view(np.uint32), ref.view(np.uint32))
+
+
 def test_launch_plan_is_balanced():
     import bench
     assert bench.launch_plan(20, 16) == [(0, 10), (10, 10)]

@@ -1,107 +1,91 @@
-"""Oracle vs the reference's own shader run live on llvmpipe (only where /root/reference and Mesa's
-swrast_dri.so exist, i.e. the build container; skipped on the GPU box)."""
+"""Oracle vs the reference's own shaders on llvmpipe, through records of what the reference made of each input (tests/golden/live/, written by
+tests/golden/make_golden_live.py from the reference's unmodified raytrace/screen shaders on Mesa llvmpipe in the build container).  Every input is
+stored with its output, so the comparison needs neither the reference checkout nor Mesa."""
 import pathlib
+import sys
 
 import numpy as np
 import pytest
 
 from conftest import assert_bit_equal
-from fuzz_scenes import CASES as FUZZ_CASES, case_scene_and_params
-from glrt_amd import scenes
-from oracle import glref, pt_oracle
+from fuzz_scenes import CASES as FUZZ_CASES
+from oracle import pt_oracle
 
-pytestmark = pytest.mark.skipif(not glref.reference_available(), reason="reference checkout / Mesa llvmpipe not present")
+sys.path.insert(0, str(pathlib.Path(__file__).resolve().parent / "golden"))
+from make_golden_live import CASES, N_SHADOW_HOSTILE, load, render_record  # noqa: E402
 
 
 @pytest.fixture(scope="module")
-def gl():
-    return glref.GLRef()
+def live():
+    """{group: {key: record}}: the recorded inputs and the reference's outputs."""
+    return {g: load(g) for g in ("configs", "fuzz", "hostile", "shadow_hostile", "screen", "screen_hostile")}
 
 
-CASES = [
-    ("c1", dict(width=96, height=64, max_depth=6, n_samples=2), {}),
-    ("c1", dict(width=64, height=64, max_depth=3, n_samples=1), dict(aperture=0.2, focal=9.0, seed=(0.91, 0.33))),
-    ("c2", dict(width=96, height=54, max_depth=8, n_samples=1, subdiv=1), dict(seed=(0.5, 0.25))),
-    ("c3", dict(width=64, height=36, max_depth=2, n=800), {}),
-    ("c4", dict(width=64, height=36, max_depth=8, n_samples=4, subdiv=1), {}),
-    ("c5", dict(width=64, height=36, max_depth=4, n=5000), dict(seed=(0.123, 0.987))),
-]
+def _screen(rec):
+    """(accumulator, [(gamma, expected bytes)]) of a resolve-pass record; a NaN gamma is the shader's default, 2.2."""
+    acc = np.concatenate([rec["rgb"], rec["count"][..., None]], -1)
+    return acc, [(2.2 if np.isnan(gm) else float(gm), out) for gm, out in zip(rec["gammas"], rec["out"])]
 
 
 @pytest.mark.parametrize("cfg,kw,over", CASES)
-def test_oracle_bit_exact_vs_live_reference(gl, cfg, kw, over):
-    sc, pr = scenes.CONFIGS[cfg](**kw)
-    pr = dict(pr, **over)
-    rgb, cnt = gl.render_reference(sc, pr)
+def test_oracle_bit_exact_vs_live_reference(live, cfg, kw, over):
+    sc, pr, rgb, cnt = render_record(live["configs"][f"case{CASES.index((cfg, kw, over))}"])
     acc, rays = pt_oracle.render(sc, pr)
     assert rays >= pr["width"] * pr["height"] * pr["n_samples"]
     assert_bit_equal(acc[..., :3], rgb, "rgb")
     assert_bit_equal(acc[..., 3], cnt, "count")
 
 
-def test_random_seeds_sweep(gl):
-    sc, pr = scenes.config_c1(48, 48, max_depth=5, n_samples=1, subdiv=1)
-    rng = np.random.default_rng(5)
-    for _ in range(6):
-        p = dict(pr, seed=tuple(float(np.float32(v)) for v in rng.uniform(0, 1, 2)))
-        rgb, cnt = gl.render_reference(sc, p)
+def test_random_seeds_sweep(live):
+    for j in range(6):
+        sc, p, rgb, cnt = render_record(live["configs"][f"seeds{j}"])
         acc, _ = pt_oracle.render(sc, p)
         assert_bit_equal(acc[..., :3], rgb, f"seed {p['seed']}")
 
 
 @pytest.mark.parametrize("case", FUZZ_CASES, ids=[f"seed{c[0]}" for c in FUZZ_CASES])
-def test_oracle_bit_exact_vs_live_reference_on_adversarial_scenes(gl, case):
+def test_oracle_bit_exact_vs_live_reference_on_adversarial_scenes(live, case):
     """The scenes of tests/test_gpu_fuzz.py (ties, degenerate and axis-aligned geometry, large distances, 1-2 triangles)
     through the reference's own shader: pins the oracle where the GPU tests rely on it."""
-    sc, pr = case_scene_and_params(case)
-    rgb, cnt = gl.render_reference(sc, pr)
+    sc, pr, rgb, cnt = render_record(live["fuzz"][f"seed{case[0]}"])
     acc, _ = pt_oracle.render(sc, pr)
     assert_bit_equal(acc[..., :3], rgb, "rgb")
     assert_bit_equal(acc[..., 3], cnt, "count")
 
 
-def test_resolve_restatement_vs_live_screen_shader(gl):
-    """The reference's screen.frag drawn into RGBA8 and read back, live, against the oracle's resolve on fresh random accumulators
+def test_resolve_restatement_vs_live_screen_shader(live):
+    """The reference's screen.frag drawn into RGBA8 and read back against the oracle's resolve on random accumulators
     (power-of-two size, several gammas) and on a rendered image."""
-    rng = np.random.default_rng(99)
-    for h, w in ((128, 256), (32, 32)):
-        rgb = (rng.random((h, w, 3), dtype=np.float32) ** 2 * 60).astype(np.float32)
-        cnt = rng.integers(1, 65, (h, w)).astype(np.float32)
-        for gamma in (2.2, 1.8, 1.0, 3.0):
-            ref = gl.render_screen(rgb, cnt, gamma)
-            got = pt_oracle.resolve(np.concatenate([rgb, cnt[..., None]], -1), gamma)
-            assert np.array_equal(got, ref), f"{h}x{w} gamma {gamma}: {int((got != ref).sum())} bytes differ"
-    sc, pr = scenes.config_c2(64, 32, max_depth=4, n_samples=8, subdiv=1)
-    acc, _ = pt_oracle.render(sc, pr)
-    assert np.array_equal(pt_oracle.resolve(acc, 2.2), gl.render_screen(acc[..., :3].copy(), acc[..., 3].copy()))
+    recs = live["screen"]
+    assert sorted(recs) == ["random128x256", "random32x32", "render"]
+    for key, rec in recs.items():
+        acc, outs = _screen(rec)
+        assert len(outs) == (1 if key == "render" else 4)
+        for gamma, ref in outs:
+            got = pt_oracle.resolve(acc, gamma)
+            assert np.array_equal(got, ref), f"{key} gamma {gamma}: {int((got != ref).sum())} bytes differ"
 
 
-def test_resolve_restatement_vs_live_screen_shader_on_hostile_accumulators(gl):
+def test_resolve_restatement_vs_live_screen_shader_on_hostile_accumulators(live):
     """Finite but hostile texels (denormals, negatives, 1e-30 .. 3e38, counts of 0 / 3e38 / fractions, values scaled by 2^-140 .. 2^119) and gammas from 1e-45
     to 3e38: llvmpipe runs the pass with denormals flushed, and so does the restatement since round 4 (counts and gammas of 3e38 showed the difference).
     Not generated: NaN / infinite texels and negative zeros -- the GL_LINEAR samplers add the neighbouring texels with weight 0, outside the restatement's domain."""
-    import sys
-    sys.path.insert(0, str(pathlib.Path(__file__).resolve().parent / "golden"))
-    from make_golden_screen_r04 import extreme_accumulator
-    acc = extreme_accumulator()
-    rng = np.random.default_rng(404)
-    for it in range(12):
-        a = acc.copy()
-        rng.shuffle(a.reshape(-1, 4))  # another arrangement of the same texels
-        gamma = float(rng.choice([2.2, 1.0, 0.45, 1e-20, 1e20, 3.0, 1e-45, 3e38, float(rng.uniform(0.1, 5))]))
-        ref = gl.render_screen(a[..., :3].copy(), a[..., 3].copy(), gamma)
-        got = pt_oracle.resolve(a, gamma)
-        assert np.array_equal(got, ref), f"arrangement {it}, gamma {gamma}: {int((got != ref).sum())} bytes differ"
+    recs = live["screen_hostile"]
+    assert len(recs) == 12
+    for key, rec in recs.items():
+        acc, outs = _screen(rec)
+        for gamma, ref in outs:
+            got = pt_oracle.resolve(acc, gamma)
+            assert np.array_equal(got, ref), f"{key}, gamma {gamma}: {int((got != ref).sum())} bytes differ"
 
 
-def test_oracle_bit_exact_vs_live_reference_on_hostile_inputs(gl):
+def test_oracle_bit_exact_vs_live_reference_on_hostile_inputs(live):
     """The inputs that round 4's device fuzzes throw at the kernels -- determinants beyond 2^126 (the reciprocal is a denormal: llvmpipe flushes it, no hit), scenes
     scaled by 1e-12 .. 1e12, seeds up to 1e20 / inf / NaN, conductors and albedos and emitters of 0 .. 1e30 / inf / NaN, vertices at infinity and NaN -- through the
-    LIVE reference: the oracle is the reference there too, so the device-against-oracle tests of the same inputs (tests/test_gpu_parity.py) mean what they say."""
-    from hostile_cases import cases
+    reference: the oracle is the reference there too, so the device-against-oracle tests of the same inputs (tests/test_gpu_parity.py) mean what they say."""
     n = 0
-    for tag, sc, p in cases():
-        rgb, cnt = gl.render_reference(sc, p)
+    for tag, rec in live["hostile"].items():
+        sc, p, rgb, cnt = render_record(rec)
         acc, _ = pt_oracle.render(sc, p)
         a = np.concatenate([rgb, cnt[..., None]], -1)
         same = (a.view(np.uint32) == acc.view(np.uint32)) | (np.isnan(a) & np.isnan(acc))
@@ -110,14 +94,12 @@ def test_oracle_bit_exact_vs_live_reference_on_hostile_inputs(gl):
     assert n >= 50
 
 
-@pytest.mark.parametrize("seed", range(32))
-def test_oracle_bit_exact_vs_live_reference_on_shadow_hostile_scenes(gl, seed):
+@pytest.mark.parametrize("seed", range(N_SHADOW_HOSTILE))
+def test_oracle_bit_exact_vs_live_reference_on_shadow_hostile_scenes(live, seed):
     """Lights flush in the faces of their ancestors' boxes, sliver light triangles, receivers that run up to the lights' edges (grazing light samples), distances
     1 .. 100, the scene translated to |coordinates| up to 1e7 (tests/fuzz_scenes.py: shadow_hostile) -- what the shadow rays' search is most sensitive to -- through
-    the LIVE reference: the oracle is the reference there, so the device tests of the same scenes (tests/test_gpu_fuzz.py) mean what they say."""
-    from fuzz_scenes import shadow_hostile
-    tag, sc, pr = shadow_hostile(seed)
-    rgb, cnt = gl.render_reference(sc, pr)
+    the reference: the oracle is the reference there, so the device tests of the same scenes (tests/test_gpu_fuzz.py) mean what they say."""
+    sc, pr, rgb, cnt = render_record(live["shadow_hostile"][f"seed{seed}"])
     acc, _ = pt_oracle.render(sc, pr)
-    assert_bit_equal(acc[..., :3], rgb, tag)
-    assert_bit_equal(acc[..., 3], cnt, tag)
+    assert_bit_equal(acc[..., :3], rgb, f"shadow_hostile seed {seed}")
+    assert_bit_equal(acc[..., 3], cnt, f"shadow_hostile seed {seed}")
