@@ -29,6 +29,8 @@
  *   glrtx_set_partition / glrtx_bind_accum / glrtx_set_stream
  *                                    no counterpart (reference is single-GPU): row-stripe sharding across
  *                                    one-process-per-GPU ranks, SURVEY.md section 8(e)
+ *   glrtx_present_*                  the screen pass and saveCurrentFrame after EVERY frame of Window::mainloop, without a sync:
+ *                                    src/core/window.cpp:157-164, src/shaders/screen.frag:15-25, window.cpp:383-414
  *   glrtx_stats / glrtx_timer_*      replaces the whole-frame Timer, src/core/timer.h:7-36, window.cpp:119-168
  *   glrtx_last_error                 replaces FatalError's stderr + abort(), src/core/common.h:88-94
  *
@@ -54,6 +56,7 @@ extern "C" {
 #define GLRTX_ESCENE (-3)   /* scene buffers inconsistent (index out of range, BVH not a tree) */
 #define GLRTX_EDEPTH (-4)   /* BVH needs more than the 64-entry traversal stack (raytrace.frag:284) */
 #define GLRTX_ENOMEM (-5)
+#define GLRTX_EBUSY (-6)    /* presentation: no free ring image for this call's frames (nothing was changed: retry after glrtx_present_release), or no image ready */
 
 #define GLRTX_ABI_VERSION 10
 
@@ -247,6 +250,48 @@ int glrtx_debug_resolve_burst(glrtx_ctx *ctx, float gamma, int reps, float *ms_p
 int glrtx_get_stats(const glrtx_ctx *ctx, glrtx_stats *out);
 int glrtx_reset_stats(glrtx_ctx *ctx);
 
+/* ---- Presentation: every frame's image, without a sync.  Replaces the second half of Window::render() -- the screen pass, screen.frag:15-25 -- and
+ * saveCurrentFrame's read-back (src/core/window.cpp:157-164, :297-317, :383-414), which the reference runs after EVERY frame of its main loop.
+ * glrtx_present_enable gives the context a ring of ring_images RGBA8 images in pinned host memory (and a device mirror of them).  From then on every
+ * frame rendered -- each glrtx_render call, each frame of glrtx_render_frames -- also produces its image: the pass that adds the frame's samples to the
+ * accumulator resolves it in the same read (launches whose render kernel accumulates by itself -- a plain single frame, a caller's stream, variants 0 / 1,
+ * the extension kernel -- are followed by the resolve kernel instead), and a copy stream of the context's own lands it in its pinned image behind that
+ * pass.  Image `frame` k is the image after the k-th frame since the last glrtx_clear / glrtx_resize: byte for byte what glrtx_resolve_rgba8(ctx, ..., gamma,
+ * flip_y) returns at that point (the owned rows, pitch width * 4).
+ * Presentation does NOT seal a fed launch (glrtx_render): a burst of render calls stays one launch, and its images are handed over when that launch's
+ * pass has run, i.e. when the launch ends -- not frame by frame inside it (the trade: full throughput against up to a launch of latency).
+ * Every frame takes a ring image when it is issued: with none free, glrtx_render / glrtx_render_frames return GLRTX_EBUSY before they change anything (no
+ * launch, no stats, no frame number), and the same call after a glrtx_present_release does what it would have done.  A call with more frames than the
+ * ring holds fails with GLRTX_EINVAL.  glrtx_hit_histogram produces no images; glrtx_resize fails with GLRTX_EINVAL while an image is acquired; images
+ * ready and not yet acquired keep their own size and frame number across glrtx_clear / glrtx_resize.
+ *   glrtx_present_enable   ring_images >= 1: (re)start presentation (gamma > 0, flip_y as in glrtx_resolve_rgba8); 0: stop -- waits for the copies in
+ *                          flight and drops the images not acquired.  Fails with GLRTX_EINVAL while an image is acquired.
+ *   glrtx_present_acquire  the oldest image not yet acquired, in frame order; wait = 0: GLRTX_EBUSY unless it is ready; wait = 1: blocks until it is
+ *                          (GLRTX_EBUSY if no frame is outstanding at all).  out->rgba stays valid, and is not rewritten, until released.
+ *   glrtx_present_release  hands an acquired image's memory back to the ring. */
+typedef struct glrtx_image {
+    const uint8_t *rgba;   /* rows x width RGBA8 texels, pinned host memory owned by the context (group: by the group) */
+    size_t pitch_bytes;
+    int32_t width, rows;   /* a context: its owned rows; a group: the full image */
+    uint64_t frame;        /* frames accumulated since the last glrtx_clear / glrtx_resize, this one included (from 1) */
+} glrtx_image;
+typedef struct glrtx_present_stats {
+    uint64_t images;       /* images produced (one per frame rendered while presentation is on); the counters run over the context's life */
+    uint64_t delivered;    /* ... of them acquired */
+    uint64_t dropped;      /* ... of them never acquired: dropped by glrtx_present_enable(ctx, 0, ...) or a re-enable */
+    uint64_t busy_returns; /* GLRTX_EBUSY returns: render calls that found no free ring image, and acquires with nothing ready */
+    int32_t ring_images;   /* 0: presentation off */
+    int32_t pending;       /* images produced and not yet acquired (ready or in flight) */
+    int32_t held;          /* images acquired and not yet released */
+    int32_t copies_last;   /* host copies of the last image (a context: 1; a group: per member one strided copy, plus one for a partial last stripe) */
+    float pass_ms_last;    /* device time of the last presenting pass (fused accumulate + resolve, or the resolve kernel), once it has completed */
+    int32_t reserved;
+} glrtx_present_stats;
+int glrtx_present_enable(glrtx_ctx *ctx, int ring_images, float gamma, int flip_y);
+int glrtx_present_acquire(glrtx_ctx *ctx, int wait, glrtx_image *out);
+int glrtx_present_release(glrtx_ctx *ctx, const glrtx_image *img);
+int glrtx_present_get_stats(const glrtx_ctx *ctx, glrtx_present_stats *out);
+
 /* HIP-event stopwatch on the stream launches go to: begin, N x render, end -> elapsed device ms. */
 int glrtx_timer_begin(glrtx_ctx *ctx);
 int glrtx_timer_end(glrtx_ctx *ctx, float *elapsed_ms_out);
@@ -296,6 +341,15 @@ int glrtx_group_get_stats(const glrtx_group *grp, glrtx_stats *out);
 /* Device-to-device copies the last gather (read_accum / resolve_rgba8) issued: one strided copy per member, on the member's own
  * stream, plus one for a partial last stripe -- at most 2 x members (diagnostic; the tests pin it). */
 int glrtx_group_gather_copies(const glrtx_group *grp);
+/* Presentation of the FULL image (see glrtx_present_enable; window.cpp:157-164 on several GPUs).  The ring's pinned images are the group's; every member
+ * resolves its own stripes into its own device images and lands them in place with one strided copy (an 8-row stripe is contiguous in the RGBA8 image; a
+ * partial last stripe takes one more) on its own copy stream -- nothing is gathered on member 0.  The members' rings move in step: a group render call
+ * returns GLRTX_EBUSY, before any member renders, when one of them has no free image.  glrtx_group_present_get_stats: member 0's counters, `copies_last`
+ * summed over the members. */
+int glrtx_group_present_enable(glrtx_group *grp, int ring_images, float gamma, int flip_y);
+int glrtx_group_present_acquire(glrtx_group *grp, int wait, glrtx_image *out);
+int glrtx_group_present_release(glrtx_group *grp, const glrtx_image *img);
+int glrtx_group_present_get_stats(const glrtx_group *grp, glrtx_present_stats *out);
 
 #ifdef __cplusplus
 }

@@ -129,6 +129,33 @@ struct glrtx_ctx {
     std::vector<int> leaf_tri;  // leaf record k of the uploaded scene -> wire triangle (glrtx_hit_histogram)
     unsigned *hit_hist_dev = nullptr;  // set only inside glrtx_hit_histogram
 
+    // Presentation (glrtx_present_enable): frame seq of the ring goes to image seq % ring -- device image (written by the presenting pass on the context's stream),
+    // then pinned host image (copied on `copy`, behind pass_done, ending with the image's event).  An image is taken for a frame only while it is FREE: released by the
+    // caller, whose acquire waited for the copy -- so neither side of an image is rewritten while anything still reads it.
+    struct Present {
+        int ring = 0;  // 0: off
+        float inv_gamma = 1.0f;
+        int flip = 1;
+        bool full = false;  // a group member: lands its stripes in place in the group's full image (the group owns the host images)
+        hipStream_t copy = nullptr;
+        hipEvent_t pass_done = nullptr, t0 = nullptr, t1 = nullptr;
+        bool timed = false;
+        DevBuf dev;            // ring x (width x owned_rows) RGBA8
+        struct Image {
+            enum { FREE, PENDING, HELD } state = FREE;
+            hipEvent_t ev = nullptr;
+            uint8_t *host = nullptr;
+            size_t host_bytes = 0;
+            uint64_t frame = 0;
+            int width = 0, rows = 0;
+        };
+        std::vector<Image> img;
+        uint64_t seq = 0, acq = 0;  // frames given an image so far / acquired so far (acq <= seq: images [acq, seq) are pending)
+        uint64_t frame = 0;         // frames accumulated since the last clear / resize
+        int copies_last = 0;
+        glrtx_present_stats st{};
+    } pres;
+
     bool count_rays = false;
     const char *last_kernel = "";  // name of the last render kernel launched (error reports)
     mutable bool counters_stale = false;          // a counting launch was issued since the device counters were last read
@@ -617,6 +644,186 @@ int feed_append(glrtx_ctx *c, const glrtx_params *p, const float *seeds_xy, int 
     return 1;
 }
 
+// ---- presentation (glrtx_ctx::Present)
+bool presenting(const glrtx_ctx *c) { return c->pres.ring > 0 && c->hit_hist_dev == nullptr; }  // (a calibration frame produces no image)
+
+size_t present_image_bytes(const glrtx_ctx *c) { return (size_t)c->width * 4 * (size_t)c->owned_rows; }
+
+// Before a render call of n frames changes anything: a free image for each of them (else GLRTX_EBUSY), device images of the current size, pinned ones too (a context's
+// own; a group's are ensured by the group).  Growing the device ring waits for everything that may still use it.
+int present_prepare(glrtx_ctx *c, int n) {
+    if (!presenting(c) || n < 1) return GLRTX_OK;
+    glrtx_ctx::Present &P = c->pres;
+    if (n > P.ring) return fail(c, GLRTX_EINVAL, "presentation: a call of %d frames needs more images than the ring holds (%d)", n, P.ring);
+    for (int k = 0; k < n; k++)
+        if (P.img[(P.seq + k) % P.ring].state != glrtx_ctx::Present::Image::FREE) {
+            P.st.busy_returns++;
+            return fail(c, GLRTX_EBUSY, "presentation: no free ring image for frame %d of this call (release an acquired image first)", k + 1);
+        }
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t bytes = present_image_bytes(c);
+    if (P.dev.bytes < bytes * (size_t)P.ring) {
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        HIP_TRY(c, hipStreamSynchronize(P.copy));
+        if (int rc = ensure(c, P.dev, bytes * (size_t)P.ring)) return rc;
+    }
+    if (!P.full)
+        for (int k = 0; k < n; k++) {
+            glrtx_ctx::Present::Image &im = P.img[(P.seq + k) % P.ring];
+            if (im.host_bytes >= bytes && im.host) continue;  // (allocated up front by glrtx_present_enable: pinning memory waits for the device; only a resize lands here)
+            if (im.host) HIP_TRY(c, hipHostFree(im.host));
+            im.host = nullptr; im.host_bytes = 0;
+            HIP_TRY(c, hipHostMalloc((void **)&im.host, std::max<size_t>(bytes, 64), hipHostMallocPortable));
+            im.host_bytes = std::max<size_t>(bytes, 64);
+        }
+    return GLRTX_OK;
+}
+
+// The device image the next frame's pass writes.
+uchar4 *present_dev_image(const glrtx_ctx *c, uint64_t seq) {
+    return (uchar4 *)((char *)c->pres.dev.p + (size_t)(seq % (uint64_t)c->pres.ring) * present_image_bytes(c));
+}
+
+// Device image -> pinned image, on the copy stream.  A context: its owned rows as they are.  A group member: its 8-row stripes in place in the full image -- ONE strided
+// copy for the whole stripes (a row of the copy is a stripe, contiguous on both sides; the destination steps by world stripes) and one more for a partial last stripe.
+// Flipped, the device image holds the owned rows in reverse: the partial stripe (the image's top rows) first, then the whole stripes in descending order -- ascending
+// destinations, so the strided copy runs forward as well.
+int present_copy(glrtx_ctx *c, const char *src, uint8_t *dst, int &copies) {
+    glrtx_ctx::Present &P = c->pres;
+    const size_t rb = (size_t)c->width * 4;
+    copies = 0;
+    if (c->owned_rows == 0) return GLRTX_OK;
+    if (!dst) return fail(c, GLRTX_EINVAL, "presentation: no host image (a group member renders through its group)");
+    if (!P.full) {
+        HIP_TRY(c, hipMemcpyAsync(dst, src, rb * (size_t)c->owned_rows, hipMemcpyDeviceToHost, P.copy));
+        copies = 1;
+        return GLRTX_OK;
+    }
+    const size_t sb = (size_t)c->stripe * rb;
+    const int whole = c->owned_rows / c->stripe, tail = c->owned_rows % c->stripe;
+    const size_t tail_at = (size_t)(whole * c->world + c->rank) * sb;  // the partial stripe's place (unflipped)
+    if (!P.flip) {
+        if (whole > 0) HIP_TRY(c, hipMemcpy2DAsync(dst + (size_t)c->rank * sb, (size_t)c->world * sb, src, sb, sb, (size_t)whole, hipMemcpyDeviceToHost, P.copy));
+        if (tail > 0) HIP_TRY(c, hipMemcpyAsync(dst + tail_at, src + (size_t)whole * sb, (size_t)tail * rb, hipMemcpyDeviceToHost, P.copy));
+    } else {
+        if (tail > 0) HIP_TRY(c, hipMemcpyAsync(dst, src, (size_t)tail * rb, hipMemcpyDeviceToHost, P.copy));
+        if (whole > 0) {
+            const int s_hi = c->rank + (whole - 1) * c->world;  // the member's highest whole stripe: the first one in the flipped image
+            const size_t at = (size_t)(c->height - (s_hi + 1) * c->stripe) * rb;
+            HIP_TRY(c, hipMemcpy2DAsync(dst + at, (size_t)c->world * sb, src + (size_t)tail * rb, sb, sb, (size_t)whole, hipMemcpyDeviceToHost, P.copy));
+        }
+    }
+    copies = (whole > 0) + (tail > 0);
+    return GLRTX_OK;
+}
+
+// n frames have been given their images on the device by a pass ordered in front of the copy stream's last wait: number them, copy them out, record their events.
+int present_issue(glrtx_ctx *c, int n) {
+    glrtx_ctx::Present &P = c->pres;
+    for (int k = 0; k < n; k++) {
+        glrtx_ctx::Present::Image &im = P.img[P.seq % P.ring];
+        int copies = 0;
+        if (int rc = present_copy(c, (const char *)present_dev_image(c, P.seq), im.host, copies)) return rc;
+        HIP_TRY(c, hipEventRecord(im.ev, P.copy));
+        im.state = glrtx_ctx::Present::Image::PENDING;
+        im.frame = ++P.frame;
+        im.width = c->width;
+        im.rows = P.full ? c->height : c->owned_rows;
+        P.copies_last = copies;
+        P.seq++;
+        P.st.images++;
+    }
+    return GLRTX_OK;
+}
+
+// Around a presenting pass on the context's stream: timing, then the copy stream is ordered behind it and its n frames are issued.
+int present_pass_begin(glrtx_ctx *c) {
+    HIP_TRY(c, hipEventRecord(c->pres.t0, c->stream));
+    return GLRTX_OK;
+}
+int present_pass_end(glrtx_ctx *c, int n) {
+    glrtx_ctx::Present &P = c->pres;
+    HIP_TRY(c, hipEventRecord(P.t1, c->stream));
+    P.timed = true;
+    HIP_TRY(c, hipEventRecord(P.pass_done, c->stream));
+    HIP_TRY(c, hipStreamWaitEvent(P.copy, P.pass_done, 0));
+    return present_issue(c, n);
+}
+
+// The image of a launch whose render kernel accumulated by itself (no planes): the resolve kernel into the frame's device image, behind the launch.
+int present_resolve(glrtx_ctx *c) {
+    if (c->owned_rows == 0) return present_issue(c, 1);
+    if (int rc = present_pass_begin(c)) return rc;
+    hipLaunchKernelGGL(resolve_kernel<kResolvePer>, resolve_grid(c->width, c->owned_rows), dim3(256), 0, c->stream, (const float4 *)c->accum,
+                       (int)(c->pitch_bytes / sizeof(float4)), c->width, c->owned_rows, present_dev_image(c, c->pres.seq), c->width, c->pres.inv_gamma, c->pres.flip);
+    HIP_TRY(c, hipGetLastError());
+    return present_pass_end(c, 1);
+}
+
+// Presentation off: nothing is appended to an open launch (its pass might write images), every pass and copy has ended, the images not acquired are dropped.
+int present_stop(glrtx_ctx *c) {
+    glrtx_ctx::Present &P = c->pres;
+    if (P.ring == 0) return GLRTX_OK;
+    for (const auto &im : P.img)
+        if (im.state == glrtx_ctx::Present::Image::HELD) return fail(c, GLRTX_EINVAL, "presentation: release the acquired images first");
+    seal_feed(c);
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipStreamSynchronize(P.copy));
+    P.st.dropped += P.seq - P.acq;
+    for (auto &im : P.img) {
+        if (im.ev) (void)hipEventDestroy(im.ev);
+        if (im.host && !P.full) (void)hipHostFree(im.host);
+    }
+    P.img.clear();
+    dev_free(P.dev);
+    P.ring = 0;
+    P.seq = P.acq = 0;
+    return GLRTX_OK;
+}
+
+// Presentation on: images of their own (group members: host images borrowed from the group, set by it).
+int present_start(glrtx_ctx *c, int ring, float gamma, int flip, bool full) {
+    if (int rc = present_stop(c)) return rc;
+    if (ring < 0 || ring > 1024) return fail(c, GLRTX_EINVAL, "glrtx_present_enable: ring_images %d (0 .. 1024)", ring);
+    if (ring == 0) return GLRTX_OK;
+    if (!(gamma > 0.f)) return fail(c, GLRTX_EINVAL, "glrtx_present_enable: gamma must be positive");
+    glrtx_ctx::Present &P = c->pres;
+    seal_feed(c);  // (a launch started before this call has a pass without images: nothing more goes into it)
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (!P.copy) {
+        HIP_TRY(c, hipStreamCreateWithFlags(&P.copy, hipStreamNonBlocking));
+        HIP_TRY(c, hipEventCreateWithFlags(&P.pass_done, hipEventDisableTiming));
+        HIP_TRY(c, hipEventCreate(&P.t0));
+        HIP_TRY(c, hipEventCreate(&P.t1));
+    }
+    P.img.assign((size_t)ring, glrtx_ctx::Present::Image{});
+    for (auto &im : P.img) HIP_TRY(c, hipEventCreateWithFlags(&im.ev, hipEventDisableTiming));
+    P.ring = ring;
+    P.inv_gamma = 1.0f / gamma;
+    P.flip = flip ? 1 : 0;
+    P.full = full;
+    P.seq = P.acq = 0;
+    P.timed = false;
+    if (c->width > 0) {  // every image of the current size now: allocating pinned memory waits for the device, so it must not happen between two frames of a burst
+        int rc = ensure(c, P.dev, present_image_bytes(c) * (size_t)ring);
+        for (auto &im : P.img) {
+            if (rc != GLRTX_OK || full) break;
+            const hipError_t e = hipHostMalloc((void **)&im.host, std::max<size_t>(present_image_bytes(c), 64), hipHostMallocPortable);
+            if (e != hipSuccess) rc = fail(c, GLRTX_ENOMEM, "glrtx_present_enable: pinned host memory: %s", hipGetErrorString(e));
+            else im.host_bytes = std::max<size_t>(present_image_bytes(c), 64);
+        }
+        if (rc != GLRTX_OK) { (void)present_stop(c); return rc; }
+    }
+    return GLRTX_OK;
+}
+
+bool present_held(const glrtx_ctx *c) {
+    for (const auto &im : c->pres.img)
+        if (im.state == glrtx_ctx::Present::Image::HELD) return true;
+    return false;
+}
+
 // Variant 2: one persistent launch; every workgroup runs the wavefront trips of the pixels it takes from the frame's tile counter.
 // n_frames > 1 ("frames in flight"): the launch covers n_frames consecutive frames that differ only in u_seed (seeds_xy);
 // the per-sample planes are added to the accumulator in frame order afterwards, so the result is bit-identical to
@@ -896,14 +1103,28 @@ int launch_wgwf(glrtx_ctx *c, const KernelArgs &a_in, const glrtx_params *p, con
         HIP_TRY(c, hipEventRecord(rec->eva, c->stream));  // (the interval evm..ev1 would include the wait for the passes queued before this one)
     }
     rec->has_eva = slot != nullptr;
+    // presenting: the pass that adds the planes also resolves every frame into its device image (fed: however many frames the launch ends up with -- each was given an
+    // image when it was appended); a launch without planes accumulated in the render kernel and is resolved behind it (below)
+    const bool pres = presenting(c);
+    const bool pres_fused = pres && (fed || w.planes);
+    if (pres_fused && (rc = present_pass_begin(c))) return rc;
     {
         const dim3 g((c->width + 63) / 64, (c->owned_rows + 3) / 4);
-        if (fed)
+        const glrtx_ctx::Present &P = c->pres;
+        const int slot0 = pres ? (int)(P.seq % (uint64_t)P.ring) : 0;
+        if (fed && pres)
+            hipLaunchKernelGGL(accumulate_present_feed_kernel, g, dim3(256), 0, c->stream, a.accum, a.pitch_f4, c->width, c->owned_rows, (const FeedDev *)slot->feed_d.p,
+                               p->n_samples, (uchar4 *)P.dev.p, (size_t)c->width * (size_t)c->owned_rows, P.ring, slot0, P.inv_gamma, P.flip);
+        else if (fed)
             hipLaunchKernelGGL(accumulate_feed_kernel, g, dim3(256), 0, c->stream, a.accum, a.pitch_f4, c->width, c->owned_rows, (const FeedDev *)slot->feed_d.p, p->n_samples);
+        else if (w.planes && pres)
+            hipLaunchKernelGGL(accumulate_present_planes_kernel, g, dim3(256), 0, c->stream, a.accum, a.pitch_f4, c->width, c->owned_rows, (const float4 *)planeBuf.p, n_frames,
+                               p->n_samples, (uchar4 *)P.dev.p, (size_t)c->width * (size_t)c->owned_rows, P.ring, slot0, P.inv_gamma, P.flip);
         else if (w.planes && n_planes > 0)
             hipLaunchKernelGGL(accumulate_planes_kernel, g, dim3(256), 0, c->stream, a.accum, a.pitch_f4, c->width, c->owned_rows, (const float4 *)planeBuf.p, n_planes);
         HIP_TRY(c, hipGetLastError());
     }
+    if (pres_fused && (rc = present_pass_end(c, n_frames))) return rc;
     if (slot) { HIP_TRY(c, hipEventRecord(slot->acc_done, c->stream)); slot->used = true; }
     HIP_TRY(c, hipEventRecord(rec->ev1, c->stream));
     rec->kernel = c->last_kernel; rec->frames = n_frames;
@@ -916,6 +1137,7 @@ int launch_wgwf(glrtx_ctx *c, const KernelArgs &a_in, const glrtx_params *p, con
         c->open.slot = slot; c->open.p = *p; c->open.frames = n_frames; c->open.cap = fed_cap; c->open.rec = rec; c->open.frame_bytes = frame_bytes;
         c->st.feed_launches++;
     } else c->open.slot = nullptr;
+    if (pres && !pres_fused) return present_resolve(c);
     return GLRTX_OK;
 }
 
@@ -1014,6 +1236,18 @@ void glrtx_destroy(glrtx_ctx *c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->own_stream) (void)hipStreamSynchronize(c->own_stream);
+    {
+        glrtx_ctx::Present &P = c->pres;
+        if (P.copy) { (void)hipStreamSynchronize(P.copy); (void)hipStreamDestroy(P.copy); }
+        for (auto &im : P.img) {
+            if (im.ev) (void)hipEventDestroy(im.ev);
+            if (im.host && !P.full) (void)hipHostFree(im.host);
+        }
+        dev_free(P.dev);
+        if (P.pass_done) (void)hipEventDestroy(P.pass_done);
+        if (P.t0) (void)hipEventDestroy(P.t0);
+        if (P.t1) (void)hipEventDestroy(P.t1);
+    }
     for (auto &sl : c->pipe) {
         if (sl.stream) { (void)hipStreamSynchronize(sl.stream); (void)hipStreamDestroy(sl.stream); }
         if (sl.render_done) (void)hipEventDestroy(sl.render_done);
@@ -1242,10 +1476,12 @@ int glrtx_local_row_to_y(const glrtx_ctx *c, int r) {
 
 int glrtx_resize(glrtx_ctx *c, int width, int height) {
     if (!c) return GLRTX_EINVAL;
+    if (present_held(c)) return fail(c, GLRTX_EINVAL, "glrtx_resize: a presented image is still acquired (glrtx_present_release it first)");
     seal_feed(c);  // (nothing is appended to an open launch across this call: glrtx_ctx::OpenFeed)
     if (width < 1 || height < 1 || width > 65536 || height > 65536) return fail(c, GLRTX_EINVAL, "glrtx_resize: bad size %dx%d", width, height);
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (c->pres.copy) HIP_TRY(c, hipStreamSynchronize(c->pres.copy));  // (the device images change their size: no copy may still read them)
     if (c->bound) {  // a caller-owned accumulator is bound: the new shape must fit it (nothing here can grow it)
         const int rows = owned_rows_of(height, c->rank, c->world, c->stripe);
         if ((size_t)width * sizeof(float4) > c->pitch_bytes || rows > c->bound_rows)
@@ -1276,6 +1512,7 @@ int glrtx_clear(glrtx_ctx *c) {
     if (!c->accum) return fail(c, GLRTX_EINVAL, "glrtx_clear: no accumulator (call glrtx_resize first)");
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipMemsetAsync(c->accum, 0, c->pitch_bytes * (size_t)c->owned_rows, c->stream));
+    c->pres.frame = 0;  // (images already produced keep their numbers)
     return GLRTX_OK;
 }
 
@@ -1332,15 +1569,18 @@ int glrtx_count_rays(glrtx_ctx *c, int enable) {
     return GLRTX_OK;
 }
 
+static int render_one(glrtx_ctx *c, const glrtx_params *p);
+
 int glrtx_render_frames(glrtx_ctx *c, const glrtx_params *p, const float *seeds_xy, int n_frames) {
     if (!c || !p) return GLRTX_EINVAL;
     if (n_frames < 0 || (n_frames > 0 && !seeds_xy)) return fail(c, GLRTX_EINVAL, "glrtx_render_frames: bad seeds/n_frames");
     if (n_frames == 0) return GLRTX_OK;
+    if (int rc = present_prepare(c, n_frames)) return rc;  // (GLRTX_EBUSY: nothing has changed)
     if (n_frames == 1 || c->variant != 2 || !wgwf_can_hold(p) || c->n_spheres > 0 || c->ext_flags != 0) {  // the megakernels have no frames-in-flight form: one launch per frame
         for (int f = 0; f < n_frames; f++) {
             glrtx_params q = *p;
             q.seed[0] = seeds_xy[2 * f]; q.seed[1] = seeds_xy[2 * f + 1];
-            if (int rc = glrtx_render(c, &q)) return rc;
+            if (int rc = render_one(c, &q)) return rc;
         }
         return GLRTX_OK;
     }
@@ -1350,7 +1590,7 @@ int glrtx_render_frames(glrtx_ctx *c, const glrtx_params *p, const float *seeds_
     // not worked around.
     if (p->n_samples >= 0 && p->max_depth >= 0 && c->have_scene && c->accum && c->owned_rows > 0 && feed_append(c, p, seeds_xy, n_frames) == 1) {
         c->last_was_render = true; c->last_p = *p;
-        return GLRTX_OK;
+        return presenting(c) ? present_issue(c, n_frames) : GLRTX_OK;  // (the launch's pass, already queued, resolves them too)
     }
     const bool may_feed = c->feed_ok && std::getenv("GLRTX_NO_FEED") == nullptr && c->pipeline && c->stream == c->own_stream;
     int most = std::min(n_frames, may_feed ? std::min(frames_cap(c, p, (int)kFedSlots), kFeedMaxFrames) : frames_cap(c, p, 1));
@@ -1363,11 +1603,11 @@ int glrtx_render_frames(glrtx_ctx *c, const glrtx_params *p, const float *seeds_
         if (n == 1) {
             glrtx_params q = *p;
             q.seed[0] = seeds_xy[2 * f0]; q.seed[1] = seeds_xy[2 * f0 + 1];
-            rc = glrtx_render(c, &q);
+            rc = render_one(c, &q);
         } else {
             c->frames_seeds = seeds_xy + 2 * (size_t)f0;
             c->frames_n = n;
-            rc = glrtx_render(c, p);
+            rc = render_one(c, p);
             c->frames_seeds = nullptr;
             c->frames_n = 1;
             if (rc == GLRTX_OK) c->st.launches += (uint64_t)(n - 1);
@@ -1379,6 +1619,12 @@ int glrtx_render_frames(glrtx_ctx *c, const glrtx_params *p, const float *seeds_
 
 int glrtx_render(glrtx_ctx *c, const glrtx_params *p) {
     if (!c || !p) return GLRTX_EINVAL;
+    if (int rc = present_prepare(c, 1)) return rc;  // (GLRTX_EBUSY: nothing has changed)
+    return render_one(c, p);
+}
+
+// glrtx_render behind the presentation check (glrtx_render_frames checks for all its frames at once)
+static int render_one(glrtx_ctx *c, const glrtx_params *p) {
     if (!c->have_scene) return fail(c, GLRTX_EINVAL, "glrtx_render: no scene uploaded");
     if (!c->accum || c->width < 1) return fail(c, GLRTX_EINVAL, "glrtx_render: no accumulator (call glrtx_resize)");
     if (p->n_samples < 0 || p->max_depth < 0) return fail(c, GLRTX_EINVAL, "glrtx_render: negative n_samples/max_depth");
@@ -1386,11 +1632,11 @@ int glrtx_render(glrtx_ctx *c, const glrtx_params *p) {
     const bool wavefront = c->variant == 2 && wgwf_can_hold(p) && c->n_spheres == 0 && c->ext_flags == 0;
     if (c->owned_rows > 0 && wavefront && c->frames_n == 1 && feed_append(c, p, p->seed, 1) == 1) {  // a launch of the same camera that is still open takes the frame itself
         c->last_was_render = true; c->last_p = *p;
-        return GLRTX_OK;
+        return presenting(c) ? present_issue(c, 1) : GLRTX_OK;
     }
     if (!wavefront) seal_feed(c);
     c->st.launches++;
-    if (c->owned_rows == 0) return GLRTX_OK;
+    if (c->owned_rows == 0) return presenting(c) ? present_issue(c, c->frames_n) : GLRTX_OK;  // (images without rows: the frame numbers stay in step)
 
     KernelArgs a;
     a.sc = c->sc;
@@ -1482,6 +1728,7 @@ int glrtx_render(glrtx_ctx *c, const glrtx_params *p) {
     c->counters_stale = c->counters_stale || c->count_rays;
     c->st.frames_last = 1;
     c->st.paths += (uint64_t)c->owned_rows * (uint64_t)c->width * (uint64_t)p->n_samples;
+    if (presenting(c)) return present_resolve(c);  // (the megakernels accumulate by themselves: the resolve kernel behind them)
     return GLRTX_OK;
 }
 
@@ -1650,6 +1897,62 @@ int glrtx_reset_stats(glrtx_ctx *c) {
     return GLRTX_OK;
 }
 
+int glrtx_present_enable(glrtx_ctx *c, int ring_images, float gamma, int flip_y) {
+    if (!c) return GLRTX_EINVAL;
+    return present_start(c, ring_images, gamma, flip_y, false);
+}
+
+int glrtx_present_acquire(glrtx_ctx *c, int wait, glrtx_image *out) {
+    if (!c || !out) return GLRTX_EINVAL;
+    glrtx_ctx::Present &P = c->pres;
+    if (P.ring == 0) return fail(c, GLRTX_EINVAL, "glrtx_present_acquire: presentation is off (glrtx_present_enable)");
+    if (P.acq == P.seq) { P.st.busy_returns++; return fail(c, GLRTX_EBUSY, "glrtx_present_acquire: no frame rendered since the last image was acquired"); }
+    glrtx_ctx::Present::Image &im = P.img[P.acq % P.ring];
+    HIP_TRY(c, hipSetDevice(c->device));
+    const hipError_t e = wait ? hipEventSynchronize(im.ev) : hipEventQuery(im.ev);
+    if (e == hipErrorNotReady) { (void)hipGetLastError(); P.st.busy_returns++; return fail(c, GLRTX_EBUSY, "glrtx_present_acquire: the next image is not ready"); }
+    if (e != hipSuccess) return fail(c, GLRTX_EDEVICE, "glrtx_present_acquire: the image's copy failed: %s", hipGetErrorString(e));
+    im.state = glrtx_ctx::Present::Image::HELD;
+    P.acq++;
+    P.st.delivered++;
+    out->rgba = im.host;
+    out->pitch_bytes = (size_t)im.width * 4;
+    out->width = im.width;
+    out->rows = im.rows;
+    out->frame = im.frame;
+    return GLRTX_OK;
+}
+
+int glrtx_present_release(glrtx_ctx *c, const glrtx_image *img) {
+    if (!c || !img) return GLRTX_EINVAL;
+    for (auto &im : c->pres.img)
+        if (im.state == glrtx_ctx::Present::Image::HELD && im.host == img->rgba) { im.state = glrtx_ctx::Present::Image::FREE; return GLRTX_OK; }
+    return fail(c, GLRTX_EINVAL, "glrtx_present_release: not an acquired image of this context");
+}
+
+int glrtx_present_get_stats(const glrtx_ctx *c, glrtx_present_stats *out) {
+    if (!c || !out) return GLRTX_EINVAL;
+    glrtx_ctx::Present &P = const_cast<glrtx_ctx *>(c)->pres;
+    if (P.timed && P.t1) {  // the last pass, once it has completed (never waits)
+        int dev_before = -1;
+        const bool have_dev = hipGetDevice(&dev_before) == hipSuccess;
+        if (hipSetDevice(c->device) == hipSuccess && hipEventQuery(P.t1) == hipSuccess) {
+            float ms = 0.f;
+            if (hipEventElapsedTime(&ms, P.t0, P.t1) == hipSuccess) P.st.pass_ms_last = ms;
+            P.timed = false;
+        }
+        (void)hipGetLastError();
+        if (have_dev && dev_before != c->device) (void)hipSetDevice(dev_before);
+    }
+    *out = P.st;
+    out->ring_images = P.ring;
+    out->pending = (int32_t)(P.seq - P.acq);
+    out->held = 0;
+    for (const auto &im : P.img) out->held += im.state == glrtx_ctx::Present::Image::HELD;
+    out->copies_last = P.copies_last;
+    return GLRTX_OK;
+}
+
 #ifdef GLRTX_TRAV_STATS
 // diagnostic build only: read and clear the traversal statistics
 int glrtx_debug_trav_stats(unsigned long long out[8]) {
@@ -1804,6 +2107,8 @@ struct glrtx_group {
     std::vector<char> peer_ok;     // per context: its device can write the root's memory directly (same device, or peer access enabled)
     int gather_copies = 0;         // copies the last gather issued (tests)
     int width = 0, height = 0;
+    std::vector<uint8_t *> pres_host;  // presentation: the full pinned images the members land their stripes in (glrtx_group_present_enable)
+    std::vector<size_t> pres_bytes;
     std::string err;
 };
 
@@ -1886,6 +2191,36 @@ int group_gather(glrtx_group *g) {
     return GLRTX_OK;
 }
 
+// Presentation, before a group render call of n frames: every member has a free image for each of them (else GLRTX_EBUSY, nothing changed), and the pinned full images
+// those frames go to hold the current size (an image is only reallocated while it is free in every member).
+int group_present_prepare(glrtx_group *g, int n) {
+    if (g->pres_host.empty() || n < 1) return GLRTX_OK;
+    for (size_t i = 0; i < g->ctx.size(); i++)
+        if (int rc = gsub(g, (int)i, present_prepare(g->ctx[i], n))) return rc;
+    glrtx_ctx::Present &P0 = g->ctx[0]->pres;
+    const size_t bytes = std::max<size_t>((size_t)g->width * 4 * (size_t)g->height, 64);
+    for (int k = 0; k < n; k++) {
+        const size_t at = (size_t)((P0.seq + k) % (uint64_t)P0.ring);
+        if (g->pres_bytes[at] >= bytes) continue;
+        if (g->pres_host[at]) GHIP_TRY(g, hipHostFree(g->pres_host[at]));
+        g->pres_host[at] = nullptr; g->pres_bytes[at] = 0;
+        GHIP_TRY(g, hipHostMalloc((void **)&g->pres_host[at], bytes, hipHostMallocPortable));
+        g->pres_bytes[at] = bytes;
+        for (glrtx_ctx *m : g->ctx) m->pres.img[at].host = g->pres_host[at];
+    }
+    return GLRTX_OK;
+}
+
+int group_present_stop(glrtx_group *g) {
+    for (size_t i = 0; i < g->ctx.size(); i++)
+        if (int rc = gsub(g, (int)i, present_stop(g->ctx[i]))) return rc;
+    for (uint8_t *h : g->pres_host)
+        if (h) (void)hipHostFree(h);
+    g->pres_host.clear();
+    g->pres_bytes.clear();
+    return GLRTX_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1934,6 +2269,10 @@ int glrtx_group_create(glrtx_group **out, const int *device_ids, int n_devices) 
 
 void glrtx_group_destroy(glrtx_group *g) {
     if (!g) return;
+    for (glrtx_ctx *c : g->ctx)  // (the members' copies land in the group's pinned images: they end first)
+        if (c->pres.copy) { (void)hipSetDevice(c->device); (void)hipStreamSynchronize(c->pres.copy); }
+    for (uint8_t *h : g->pres_host)
+        if (h) (void)hipHostFree(h);
     for (size_t i = 0; i < g->done.size(); i++) { (void)hipSetDevice(g->ctx[i]->device); (void)hipEventDestroy(g->done[i]); }
     if (!g->ctx.empty()) { (void)hipSetDevice(g->ctx[0]->device); (void)hipStreamSynchronize(g->ctx[0]->stream); dev_free(g->full); dev_free(g->full8); }
     for (glrtx_ctx *c : g->ctx) glrtx_destroy(c);
@@ -1973,6 +2312,7 @@ int glrtx_group_clear(glrtx_group *g) {
 
 int glrtx_group_render(glrtx_group *g, const glrtx_params *p) {
     if (!g) return GLRTX_EINVAL;
+    if (int rc = group_present_prepare(g, 1)) return rc;
     for (size_t i = 0; i < g->ctx.size(); i++)  // asynchronous launches: the GPUs run concurrently
         if (int rc = gsub(g, (int)i, glrtx_render(g->ctx[i], p))) return rc;
     return GLRTX_OK;
@@ -1980,6 +2320,7 @@ int glrtx_group_render(glrtx_group *g, const glrtx_params *p) {
 
 int glrtx_group_render_frames(glrtx_group *g, const glrtx_params *p, const float *seeds_xy, int n_frames) {
     if (!g) return GLRTX_EINVAL;
+    if (int rc = group_present_prepare(g, n_frames)) return rc;
     for (size_t i = 0; i < g->ctx.size(); i++)
         if (int rc = gsub(g, (int)i, glrtx_render_frames(g->ctx[i], p, seeds_xy, n_frames))) return rc;
     return GLRTX_OK;
@@ -2024,6 +2365,75 @@ int glrtx_group_resolve_rgba8(glrtx_group *g, uint8_t *dst, size_t dst_pitch_byt
 }
 
 int glrtx_group_gather_copies(const glrtx_group *g) { return g ? g->gather_copies : 0; }
+
+int glrtx_group_present_enable(glrtx_group *g, int ring_images, float gamma, int flip_y) {
+    if (!g) return GLRTX_EINVAL;
+    if (int rc = group_present_stop(g)) return rc;
+    if (ring_images == 0) return GLRTX_OK;
+    if (g->width < 1) return gfail(g, GLRTX_EINVAL, "glrtx_group_present_enable: call glrtx_group_resize first");
+    for (size_t i = 0; i < g->ctx.size(); i++)
+        if (int rc = gsub(g, (int)i, present_start(g->ctx[i], ring_images, gamma, flip_y, true))) { (void)group_present_stop(g); return rc; }
+    g->pres_host.assign((size_t)ring_images, nullptr);
+    g->pres_bytes.assign((size_t)ring_images, 0);
+    const size_t bytes = std::max<size_t>((size_t)g->width * 4 * (size_t)g->height, 64);
+    for (int k = 0; k < ring_images; k++) {  // (up front: pinning memory waits for the device)
+        if (hipHostMalloc((void **)&g->pres_host[k], bytes, hipHostMallocPortable) != hipSuccess) {
+            g->pres_host[k] = nullptr;
+            (void)group_present_stop(g);
+            return gfail(g, GLRTX_ENOMEM, "glrtx_group_present_enable: %zu bytes of pinned host memory", bytes);
+        }
+        g->pres_bytes[k] = bytes;
+        for (glrtx_ctx *m : g->ctx) m->pres.img[k].host = g->pres_host[k];
+    }
+    return GLRTX_OK;
+}
+
+int glrtx_group_present_acquire(glrtx_group *g, int wait, glrtx_image *out) {
+    if (!g || !out) return GLRTX_EINVAL;
+    if (g->pres_host.empty()) return gfail(g, GLRTX_EINVAL, "glrtx_group_present_acquire: presentation is off (glrtx_group_present_enable)");
+    glrtx_ctx::Present &P0 = g->ctx[0]->pres;
+    if (P0.acq == P0.seq) { P0.st.busy_returns++; return gfail(g, GLRTX_EBUSY, "glrtx_group_present_acquire: no frame rendered since the last image was acquired"); }
+    for (glrtx_ctx *m : g->ctx) {  // the image is there when every member's stripes are
+        glrtx_ctx::Present::Image &im = m->pres.img[m->pres.acq % m->pres.ring];
+        GHIP_TRY(g, hipSetDevice(m->device));
+        const hipError_t e = wait ? hipEventSynchronize(im.ev) : hipEventQuery(im.ev);
+        if (e == hipErrorNotReady) { (void)hipGetLastError(); P0.st.busy_returns++; return gfail(g, GLRTX_EBUSY, "glrtx_group_present_acquire: the next image is not ready"); }
+        if (e != hipSuccess) return gfail(g, GLRTX_EDEVICE, "glrtx_group_present_acquire: a member's copy failed (device %d): %s", m->device, hipGetErrorString(e));
+    }
+    const glrtx_ctx::Present::Image &im0 = P0.img[P0.acq % P0.ring];
+    out->rgba = im0.host;
+    out->pitch_bytes = (size_t)im0.width * 4;
+    out->width = im0.width;
+    out->rows = im0.rows;
+    out->frame = im0.frame;
+    for (glrtx_ctx *m : g->ctx) {
+        m->pres.img[m->pres.acq % m->pres.ring].state = glrtx_ctx::Present::Image::HELD;
+        m->pres.acq++;
+        m->pres.st.delivered++;
+    }
+    return GLRTX_OK;
+}
+
+int glrtx_group_present_release(glrtx_group *g, const glrtx_image *img) {
+    if (!g || !img) return GLRTX_EINVAL;
+    for (size_t i = 0; i < g->ctx.size(); i++)
+        if (int rc = gsub(g, (int)i, glrtx_present_release(g->ctx[i], img))) return rc;
+    return GLRTX_OK;
+}
+
+int glrtx_group_present_get_stats(const glrtx_group *g, glrtx_present_stats *out) {
+    if (!g || !out || g->ctx.empty()) return GLRTX_EINVAL;
+    int copies = 0;
+    for (size_t i = 0; i < g->ctx.size(); i++) {
+        glrtx_present_stats t{};
+        if (int rc = glrtx_present_get_stats(g->ctx[i], &t)) return rc;
+        if (i == 0) *out = t;
+        else out->pass_ms_last = std::max(out->pass_ms_last, t.pass_ms_last);  // (the members' passes run side by side)
+        copies += t.copies_last;
+    }
+    out->copies_last = copies;
+    return GLRTX_OK;
+}
 
 int glrtx_group_get_stats(const glrtx_group *g, glrtx_stats *out) {
     if (!g || !out || g->ctx.empty()) return GLRTX_EINVAL;

@@ -2622,4 +2622,58 @@ __global__ __launch_bounds__(256) void resolve_kernel(const float4 *accum, int p
 constexpr int kResolvePer = 2;
 inline dim3 resolve_grid(int width, int rows, int per = kResolvePer) { return dim3((unsigned)(((size_t)((width + 64 * per - 1) / (64 * per)) * (size_t)rows + 3) / 4)); }
 
+// ------------------------------------------------------------------------------------------ presentation (fused accumulate + resolve)
+// The presenting twins of accumulate_planes_kernel and accumulate_feed_kernel (glrtx_present_enable): the same chain of additions per pixel -- the accumulator is
+// loaded once, frame by frame, sample by sample, stored once -- and behind every frame f the pixel's screen.frag value (rs_pixel, byte-identical to resolve_kernel's)
+// goes into image slot (slot0 + f) % n_ring of the device ring, packed rows of `width` texels, row y at rows - 1 - y when flipped (within the owned rows, like
+// glrtx_resolve_rgba8).  One launch and one read of the accumulator per launch instead of a pass plus a resolve per frame.  A wave is 64 consecutive texels of a row:
+// lanes past the row's end stay in it with the texel (0, 0, 0, 1), because rs_pixel votes across the wave.
+DEV void present_store(uchar4 *ring, size_t slot_px, int n_ring, int slot0, int f, int width, int rows, int x, int y, int flip, uchar4 px) {
+    const int oy = flip ? rows - 1 - y : y;
+    ring[(size_t)((slot0 + f) % n_ring) * slot_px + (size_t)oy * width + x] = px;
+}
+__global__ __launch_bounds__(256) void accumulate_present_planes_kernel(float4 *accum, int pitch_f4, int width, int rows, const float4 *planes, int n_frames,
+                                                                        int n_samples, uchar4 *ring, size_t slot_px, int n_ring, int slot0, float inv_gamma, int flip) {
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (y >= rows) return;  // (a whole wave)
+    const bool in = x < width;
+    const size_t at = (size_t)y * pitch_f4 + x, plane = (size_t)rows * pitch_f4;
+    float4 acc = in ? accum[at] : make_float4(0.f, 0.f, 0.f, 1.f);
+    for (int f = 0; f < n_frames; f++) {
+        if (in)
+            for (int k = 0; k < n_samples; k++) {
+                const float4 v = planes[((size_t)f * n_samples + k) * plane + at];
+                acc.x = acc.x + v.x; acc.y = acc.y + v.y; acc.z = acc.z + v.z;
+                acc.w = acc.w + 1.0f;
+            }
+        const uchar4 px = rs_pixel(acc, inv_gamma);  // (every lane of the wave)
+        if (in) present_store(ring, slot_px, n_ring, slot0, f, width, rows, x, y, flip, px);
+    }
+    if (in) accum[at] = acc;
+}
+__global__ __launch_bounds__(256) void accumulate_present_feed_kernel(float4 *accum, int pitch_f4, int width, int rows, const FeedDev *fd, int n_samples,
+                                                                      uchar4 *ring, size_t slot_px, int n_ring, int slot0, float inv_gamma, int flip) {
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (y >= rows) return;  // (a whole wave)
+    const bool in = x < width;
+    const size_t at = (size_t)y * pitch_f4 + x, plane = (size_t)rows * pitch_f4;
+    const int n_frames = (int)(fd->frames_known & ~kFeedClosed);
+    float4 acc = in ? accum[at] : make_float4(0.f, 0.f, 0.f, 1.f);
+    for (int f = 0; f < n_frames; f++) {
+        if (in) {
+            const float4 *chunk = reinterpret_cast<const float4 *>(fd->chunks[f / kFeedChunkFrames]) + (size_t)(f % kFeedChunkFrames) * (size_t)n_samples * plane;
+            for (int k = 0; k < n_samples; k++) {
+                const float4 v = chunk[(size_t)k * plane + at];
+                acc.x = acc.x + v.x; acc.y = acc.y + v.y; acc.z = acc.z + v.z;
+                acc.w = acc.w + 1.0f;
+            }
+        }
+        const uchar4 px = rs_pixel(acc, inv_gamma);  // (every lane of the wave)
+        if (in) present_store(ring, slot_px, n_ring, slot0, f, width, rows, x, y, flip, px);
+    }
+    if (in) accum[at] = acc;
+}
+
 }  // namespace glrtx

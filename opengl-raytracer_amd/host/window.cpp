@@ -93,6 +93,38 @@ void Window::mainloop(const std::shared_ptr<Scene> &scene_, double fps) {
     // asynchronous, and a launch issued behind idle time runs longer -- 2 % behind 1 ms, 5 % behind 3 ms (profiles/r04_ab_launch_warmth.txt).  lastFrameMs() is the wall
     // time per frame between two such waits.
     auto t0 = std::chrono::steady_clock::now();
+    if (every) {
+        // The reference's cadence without its waits: every frame's image comes out of the ring the group presents into (glrtx_group_present_enable) -- resolved in the
+        // pass that accumulates it and copied to pinned memory on a stream of its own -- so the frames are issued back to back and stay fed launches, and this thread
+        // only waits when the ring is full.  Same PNG bytes and the same "Save:" line per frame as a sync + resolve per frame.
+        GLRTX_CHECK(glrtx_group_present_enable(grp_, kPresentRing, 2.2f, 1));
+        int images = 0;
+        auto drain = [&](int wait) {
+            glrtx_image img;
+            int rc;
+            while ((rc = glrtx_group_present_acquire(grp_, wait, &img)) == GLRTX_OK) {
+                saveImage(output_, true, img.rgba);
+                GLRTX_CHECK(glrtx_group_present_release(grp_, &img));
+                images++;
+                if (wait) break;  // (one is enough to free a ring image)
+            }
+            if (rc != GLRTX_OK && rc != GLRTX_EBUSY) GLRT_FatalError("glrtx_group_present_acquire: %s", glrtx_group_last_error(grp_));
+        };
+        // (images are taken only when the ring is full: a PNG written between two frames would let the running launch run dry, and the next frame would start a
+        //  launch of its own instead of being appended to it)
+        for (int i = 0; i < frameLimit_; i++) {
+            if (i - images >= kPresentRing) drain(1);  // (a full ring would refuse the frame with GLRTX_EBUSY: one image out first)
+            render();
+        }
+        while (images < frameLimit_) drain(1);
+        GLRTX_CHECK(glrtx_group_sync(grp_));
+        lastMs_ = frameLimit_ > 0 ? std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() / frameLimit_ : 0.0;
+        GLRTX_CHECK(glrtx_group_present_enable(grp_, 0, 2.2f, 1));
+        glrtx_stats st;
+        GLRTX_CHECK(glrtx_group_get_stats(grp_, &st));
+        GLRT_Info("Presented: %d frames, %d images, %llu render kernel launches", frameLimit_, images, (unsigned long long)st.kernel_launches);
+        return;
+    }
     int since = 0;
     for (int i = 0; i < frameLimit_; i += step) {
         const int n = frameLimit_ - i < step ? frameLimit_ - i : step;
@@ -170,6 +202,10 @@ void Window::saveCurrentFrame(const std::string &filename, bool overwrite) const
     // (with several GPUs the stripes are first gathered on the first one)
     if (glrtx_group_resolve_rgba8(grp_, bytes.data(), (size_t)width_ * 4, 2.2f, 1) != GLRTX_OK)
         GLRT_FatalError("glrtx_group_resolve_rgba8: %s", glrtx_group_last_error(grp_));
+    saveImage(filename, overwrite, bytes.data());
+}
+
+void Window::saveImage(const std::string &filename, bool overwrite, const unsigned char *bytes) const {
     std::string path = filename;
     if (!overwrite) {
         int count = 0;
@@ -177,7 +213,7 @@ void Window::saveCurrentFrame(const std::string &filename, bool overwrite) const
         const std::string base = filename.substr(0, dot), ext = dot == std::string::npos ? "" : filename.substr(dot);
         while (std::ifstream(path).good()) path = base + "_" + std::to_string(count++) + ext;
     }
-    if (!writePng(path, width_, height_, bytes.data())) GLRT_Warn("Failed to save: %s", path.c_str());
+    if (!writePng(path, width_, height_, bytes)) GLRT_Warn("Failed to save: %s", path.c_str());
     else GLRT_Info("Save: %s", path.c_str());
 }
 

@@ -48,7 +48,7 @@ public:
     // Used when no image is written between frames and render() is not overridden per frame; GLRT_FRAMES_IN_FLIGHT.
     void setFramesInFlight(int n) { framesInFlight_ = n < 1 ? 1 : n; }
     // wall-clock ms PER FRAME between the last two waits for the device, averaged over the frames issued in between (with one PNG per run: the whole run, cold first
-    // launches included; with --save-every-frame: the last frame).  The device's own time of the last launch is glrtx_stats.kernel_ms_last.
+    // launches included; with --save-every-frame: the whole run, PNG writing included).  The device's own time of the last launch is glrtx_stats.kernel_ms_last.
     double lastFrameMs() const { return lastMs_; }
     unsigned long long raysTraced() const;
 
@@ -65,6 +65,8 @@ private:
     void resizeDefault(int width, int height);
     void resetBuffer();
     void saveCurrentFrame(const std::string &filename, bool overwrite = true) const;
+    void saveImage(const std::string &filename, bool overwrite, const unsigned char *rgba) const;  // a full RGBA8 image, flipped: PNG + "Save:" line
+    static constexpr int kPresentRing = 8;  // --save-every-frame: images the loop may run ahead of the PNG writer (8.3 MB each at 1080p, pinned)
     void noteFallback();
 
     glrtx_group *grp_ = nullptr;

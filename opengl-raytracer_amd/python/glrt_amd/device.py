@@ -13,7 +13,7 @@ import numpy as np
 from .host import LIB_DIR, PKG_ROOT
 
 GLRTX_OK = 0
-GLRTX_EINVAL, GLRTX_EDEVICE, GLRTX_ESCENE, GLRTX_EDEPTH, GLRTX_ENOMEM = -1, -2, -3, -4, -5
+GLRTX_EINVAL, GLRTX_EDEVICE, GLRTX_ESCENE, GLRTX_EDEPTH, GLRTX_ENOMEM, GLRTX_EBUSY = -1, -2, -3, -4, -5, -6
 EXT_DIELECTRIC, EXT_WHITTED = 1, 2
 FALLBACK_DEPTH, FALLBACK_SAMPLES, FALLBACK_EXTENSIONS = 1, 2, 4
 
@@ -34,6 +34,27 @@ class Stats(C.Structure):
                 ("shadow_limited", C.c_int32), ("reserved2", C.c_int32), ("feed_launches", C.c_uint64), ("feed_appended", C.c_uint64)]
 
 
+class Image(C.Structure):
+    _fields_ = [("rgba", C.c_void_p), ("pitch_bytes", C.c_size_t), ("width", C.c_int32), ("rows", C.c_int32), ("frame", C.c_uint64)]
+
+
+class PresentStats(C.Structure):
+    _fields_ = [("images", C.c_uint64), ("delivered", C.c_uint64), ("dropped", C.c_uint64), ("busy_returns", C.c_uint64),
+                ("ring_images", C.c_int32), ("pending", C.c_int32), ("held", C.c_int32), ("copies_last", C.c_int32),
+                ("pass_ms_last", C.c_float), ("reserved", C.c_int32)]
+
+
+class Presented:
+    """An acquired image (glrtx_present_acquire): `frame`, and `rgba`, a (rows, width, 4) uint8 view of the pinned ring image -- zero-copy, valid until released."""
+
+    def __init__(self, img: Image):
+        self.img = img
+        self.frame = int(img.frame)
+        n = int(img.rows) * int(img.pitch_bytes)
+        buf = (C.c_uint8 * max(n, 1)).from_address(img.rgba) if img.rgba else (C.c_uint8 * 1)()
+        self.rgba = np.ctypeslib.as_array(buf)[:n].reshape(int(img.rows), int(img.width), 4)
+
+
 EXPORTS = ["glrtx_abi_version", "glrtx_create", "glrtx_destroy", "glrtx_last_error", "glrtx_upload_scene", "glrtx_build_lbvh", "glrtx_build_bvh_sah",
            "glrtx_resize", "glrtx_clear", "glrtx_set_partition", "glrtx_local_row_to_y", "glrtx_bind_accum",
            "glrtx_set_stream", "glrtx_set_variant", "glrtx_set_shadow_range_limit", "glrtx_count_rays", "glrtx_render", "glrtx_render_frames", "glrtx_sync", "glrtx_read_accum",
@@ -41,7 +62,9 @@ EXPORTS = ["glrtx_abi_version", "glrtx_create", "glrtx_destroy", "glrtx_last_err
            "glrtx_timer_begin", "glrtx_timer_end", "glrtx_upload_spheres", "glrtx_set_extensions",
            "glrtx_group_create", "glrtx_group_destroy", "glrtx_group_last_error", "glrtx_group_size", "glrtx_group_ctx",
            "glrtx_group_upload_scene", "glrtx_group_resize", "glrtx_group_clear", "glrtx_group_render", "glrtx_group_render_frames",
-           "glrtx_debug_resolve_burst", "glrtx_hit_histogram", "glrtx_group_sync", "glrtx_group_read_accum", "glrtx_group_resolve_rgba8", "glrtx_group_get_stats", "glrtx_group_gather_copies"]
+           "glrtx_debug_resolve_burst", "glrtx_hit_histogram", "glrtx_group_sync", "glrtx_group_read_accum", "glrtx_group_resolve_rgba8", "glrtx_group_get_stats", "glrtx_group_gather_copies",
+           "glrtx_present_enable", "glrtx_present_acquire", "glrtx_present_release", "glrtx_present_get_stats",
+           "glrtx_group_present_enable", "glrtx_group_present_acquire", "glrtx_group_present_release", "glrtx_group_present_get_stats"]
 
 _lib = None
 
@@ -113,6 +136,14 @@ def lib():
         L.glrtx_group_resolve_rgba8.argtypes = [vp, vp, C.c_size_t, C.c_float, C.c_int]
         L.glrtx_group_get_stats.argtypes = [vp, C.POINTER(Stats)]
         L.glrtx_group_gather_copies.argtypes = [vp]
+        L.glrtx_present_enable.argtypes = [vp, C.c_int, C.c_float, C.c_int]
+        L.glrtx_present_acquire.argtypes = [vp, C.c_int, C.POINTER(Image)]
+        L.glrtx_present_release.argtypes = [vp, C.POINTER(Image)]
+        L.glrtx_present_get_stats.argtypes = [vp, C.POINTER(PresentStats)]
+        L.glrtx_group_present_enable.argtypes = [vp, C.c_int, C.c_float, C.c_int]
+        L.glrtx_group_present_acquire.argtypes = [vp, C.c_int, C.POINTER(Image)]
+        L.glrtx_group_present_release.argtypes = [vp, C.POINTER(Image)]
+        L.glrtx_group_present_get_stats.argtypes = [vp, C.POINTER(PresentStats)]
         _lib = L
     return _lib
 
@@ -273,6 +304,27 @@ class Device:
         self._ck(self.L.glrtx_debug_resolve_burst(self.h, gamma, int(reps), C.byref(ms)))
         return float(ms.value)
 
+    def present_enable(self, ring, gamma=2.2, flip_y=True):
+        """Every frame's image into a ring of `ring` pinned RGBA8 images (glrtx_present_enable); ring = 0 turns it off (untaken images are dropped)."""
+        self._ck(self.L.glrtx_present_enable(self.h, int(ring), gamma, int(flip_y)))
+
+    def present_acquire(self, wait=True):
+        """The oldest image not yet acquired: a Presented (.frame, .rgba zero-copy view), or None when wait=False and it is not ready (GLRTX_EBUSY)."""
+        img = Image()
+        rc = self.L.glrtx_present_acquire(self.h, int(wait), C.byref(img))
+        if rc == GLRTX_EBUSY and not wait:
+            return None
+        self._ck(rc)
+        return Presented(img)
+
+    def present_release(self, img):
+        self._ck(self.L.glrtx_present_release(self.h, C.byref(img.img)))
+
+    def present_stats(self) -> PresentStats:
+        s = PresentStats()
+        self._ck(self.L.glrtx_present_get_stats(self.h, C.byref(s)))
+        return s
+
     def timer_begin(self):
         self._ck(self.L.glrtx_timer_begin(self.h))
 
@@ -361,6 +413,27 @@ class Group:
         out = np.zeros((self.hgt, self.w, 4), np.uint8)
         self._ck(self.L.glrtx_group_resolve_rgba8(self.h, out.ctypes.data, self.w * 4, gamma, int(flip_y)))
         return out
+
+    def present_enable(self, ring, gamma=2.2, flip_y=True):
+        """Every frame's image into a ring of `ring` pinned RGBA8 images (glrtx_group_present_enable: the FULL image); ring = 0 turns it off (untaken images are dropped)."""
+        self._ck(self.L.glrtx_group_present_enable(self.h, int(ring), gamma, int(flip_y)))
+
+    def present_acquire(self, wait=True):
+        """The oldest image not yet acquired: a Presented (.frame, .rgba zero-copy view), or None when wait=False and it is not ready (GLRTX_EBUSY)."""
+        img = Image()
+        rc = self.L.glrtx_group_present_acquire(self.h, int(wait), C.byref(img))
+        if rc == GLRTX_EBUSY and not wait:
+            return None
+        self._ck(rc)
+        return Presented(img)
+
+    def present_release(self, img):
+        self._ck(self.L.glrtx_group_present_release(self.h, C.byref(img.img)))
+
+    def present_stats(self) -> PresentStats:
+        s = PresentStats()
+        self._ck(self.L.glrtx_group_present_get_stats(self.h, C.byref(s)))
+        return s
 
 
 def render_image(scene, params, device_id=-1, count_rays=True):
