@@ -312,6 +312,35 @@ int glrtx_timer_end(glrtx_ctx *ctx, float *elapsed_ms_out);
 int glrtx_upload_spheres(glrtx_ctx *ctx, const float *spheres, size_t n_spheres);
 int glrtx_set_extensions(glrtx_ctx *ctx, int flags);
 
+/* ---- Participating media: the reference's volume branch (raytrace.frag:424-487, blackBody :125-142, lookups :144-152), which the
+ * reference compiles out (ENABLE_VOLUME 0, raytrace.frag:4).  Off by default; GLRTX_EXT_VOLUME (glrtx_set_extensions) switches it on,
+ * like the reference's define, and routes rendering to the persistent megakernel as the other extension flags do.  PINNED: the images
+ * are the reference shader's with the switch on and ONE edit -- densityLookup / temperatureLookup read textureLod(tex, uvw, 0.0), the
+ * trilinear magnification filter with GL_REPEAT, instead of texture(tex, uvw), whose filter GL leaves to the 2x2 pixel quad (DESIGN.md
+ * section 3, "Volumes").  Like the reference (window.cpp:271-286) only one volume exists: it applies to every media material.
+ *   glrtx_upload_volume   two nx x ny x nz grids, x fastest (the order glTexSubImage3D reads; a grid file with several channels contributes
+ *                         its first nx*ny*nz floats), copied to device memory; bbox_min / bbox_max = u_bboxMin / u_bboxMax (the scene's JSON,
+ *                         not the grid file's header); density_max = u_densityMax (the largest value of the density file over all its
+ *                         channels).  density == NULL or an empty grid (a zero dimension) removes the volume.  Kept across glrtx_upload_scene.
+ *                         GLRTX_EINVAL: NULL ctx, a negative dimension, more than 2^29 texels, a NULL temperature grid or bbox, a bbox with zero
+ *                         or non-finite extent on some axis.
+ *   Rendering with GLRTX_EXT_VOLUME set and no volume uploaded fails with GLRTX_EINVAL.  Every trial ray of the Woodcock tracking counts as a
+ *   ray (glrtx_count_rays).  Group members: glrtx_group_upload_volume, and the flag through glrtx_group_ctx. */
+#define GLRTX_EXT_VOLUME 4
+int glrtx_upload_volume(glrtx_ctx *ctx, const float *density, const float *temperature, int nx, int ny, int nz, const float bbox_min[3],
+                        const float bbox_max[3], float density_max);
+/* Debug export (no ctx; the current HIP device): the device's statements of llvmpipe's log / exp / acos, and of blackBody, evaluated on n host
+ * values.  op GLRTX_VMATH_LOG / _EXP / _ACOS: out[i] = f(in[i]); GLRTX_VMATH_BLACKBODY: out[3i..3i+2] = blackBody(100 * in[i]) (in = the
+ * temperature grid's value, as temperatureLookup() returns it).  glrtx_debug_volume_lookup: out[i] = the density lookup of the grid at
+ * pos[3i..3i+2].  Synchronous; errors are reported through glrtx_last_error(NULL). */
+#define GLRTX_VMATH_LOG 0
+#define GLRTX_VMATH_EXP 1
+#define GLRTX_VMATH_ACOS 2
+#define GLRTX_VMATH_BLACKBODY 3
+int glrtx_debug_volume_math(int op, const float *in, size_t n, float *out);
+int glrtx_debug_volume_lookup(const float *grid, int nx, int ny, int nz, const float bbox_min[3], const float bbox_max[3], const float *pos,
+                              size_t n, float *out);
+
 /* ---- Groups: the same device layer on several GPUs of one node, behind one handle and one host thread.
  * No reference counterpart (the reference is single-GPU); SURVEY.md 8(b) sketches glrtx_create(ctx**, device_ids, n) with a
  * gathering read_accum -- this is that, kept apart from the single-context calls.  Member i owns the 8-row stripes s with
@@ -330,6 +359,9 @@ int glrtx_group_size(const glrtx_group *grp);
 glrtx_ctx *glrtx_group_ctx(glrtx_group *grp, int i);
 int glrtx_group_upload_scene(glrtx_group *grp, const float *vert, size_t n_vert, const float *tri, size_t n_tri, const float *mat,
                              size_t n_mat, const float *light, size_t n_light, const float *bvh, size_t n_nodes);
+/* glrtx_upload_volume on every member (the grids are replicated, like the scene). */
+int glrtx_group_upload_volume(glrtx_group *grp, const float *density, const float *temperature, int nx, int ny, int nz, const float bbox_min[3],
+                              const float bbox_max[3], float density_max);
 int glrtx_group_resize(glrtx_group *grp, int width, int height);
 int glrtx_group_clear(glrtx_group *grp);
 int glrtx_group_render(glrtx_group *grp, const glrtx_params *params);

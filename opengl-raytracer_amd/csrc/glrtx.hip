@@ -67,6 +67,9 @@ struct glrtx_ctx {
     DevBuf forks, nrms, mats, lights, vine, accum_own, counter, rgba8, work;
     DevBuf spheres, sphereMat;  // extension kernel: analytic spheres
     int n_spheres = 0, ext_flags = 0;
+    DevBuf volDensity, volTemp;  // volume kernel (GLRTX_EXT_VOLUME): the two grids of glrtx_upload_volume
+    VolArgs vol{};
+    bool have_volume = false;
     DevBuf wfState, wfQ;      // wavefront path state (kWfStatePlanes = 6 planes of float4 x ids) + per-workgroup queues (variant 2)
     DevBuf wfSeeds, wfPlanes;       // frames in flight: per-frame seeds, per-sample planes
     // Single-frame launches that overlap (launch_wgwf): pipe_slots (<= kPipeSlots) slots used in turn, each with its own stream, path state, queues, tile
@@ -1256,7 +1259,7 @@ void glrtx_destroy(glrtx_ctx *c) {
         for (auto &ch : sl.chunks) dev_free(ch);
         if (sl.feed_h) (void)hipHostFree(sl.feed_h);
     }
-    dev_free(c->spheres); dev_free(c->sphereMat); dev_free(c->forks); dev_free(c->nrms); dev_free(c->mats); dev_free(c->lights); dev_free(c->vine);
+    dev_free(c->spheres); dev_free(c->sphereMat); dev_free(c->volDensity); dev_free(c->volTemp); dev_free(c->forks); dev_free(c->nrms); dev_free(c->mats); dev_free(c->lights); dev_free(c->vine);
     dev_free(c->accum_own); dev_free(c->counter); dev_free(c->rgba8); dev_free(c->work);
     dev_free(c->wfState); dev_free(c->wfQ); dev_free(c->wfSeeds); dev_free(c->wfPlanes);
     dev_free(c->bvhVert); dev_free(c->bvhTri); dev_free(c->bvhNodes);
@@ -1449,10 +1452,107 @@ int glrtx_upload_spheres(glrtx_ctx *c, const float *spheres, size_t n_spheres) {
 int glrtx_set_extensions(glrtx_ctx *c, int flags) {
     if (!c) return GLRTX_EINVAL;
     seal_feed(c);  // (nothing is appended to an open launch across this call: glrtx_ctx::OpenFeed)
-    if (flags & ~(GLRTX_EXT_DIELECTRIC | GLRTX_EXT_WHITTED)) return fail(c, GLRTX_EINVAL, "glrtx_set_extensions: unknown flag bits 0x%x", flags);
+    if (flags & ~(GLRTX_EXT_DIELECTRIC | GLRTX_EXT_WHITTED | GLRTX_EXT_VOLUME)) return fail(c, GLRTX_EINVAL, "glrtx_set_extensions: unknown flag bits 0x%x", flags);
     static_assert(GLRTX_EXT_DIELECTRIC == EXT_DIELECTRIC && GLRTX_EXT_WHITTED == EXT_WHITTED, "extension flag values");
     c->ext_flags = flags;
     return GLRTX_OK;
+}
+
+// Volume grids: argument checks shared by glrtx_upload_volume and the lookup export.  Returns 0 (valid), 1 (remove: no grid), or a GLRTX_E* code.
+static int check_volume(glrtx_ctx *c, const char *fn, const float *density, const float *temperature, int nx, int ny, int nz, const float *bmin,
+                        const float *bmax, bool need_temperature) {
+    if (nx < 0 || ny < 0 || nz < 0) return fail(c, GLRTX_EINVAL, "%s: negative grid dimension %d x %d x %d", fn, nx, ny, nz);
+    if (!density || nx == 0 || ny == 0 || nz == 0) return 1;
+    if ((long long)nx * ny * nz > (1ll << 29)) return fail(c, GLRTX_EINVAL, "%s: %d x %d x %d texels exceed 2^29 (32-bit texel offsets)", fn, nx, ny, nz);
+    if (need_temperature && !temperature) return fail(c, GLRTX_EINVAL, "%s: NULL temperature grid with a density grid", fn);
+    if (!bmin || !bmax) return fail(c, GLRTX_EINVAL, "%s: NULL bbox", fn);
+    for (int k = 0; k < 3; k++) {
+        const float e = bmax[k] - bmin[k];
+        if (e == 0.0f || !std::isfinite(e))
+            return fail(c, GLRTX_EINVAL, "%s: bbox has zero or non-finite extent on axis %c (%g .. %g)", fn, "xyz"[k], bmin[k], bmax[k]);
+    }
+    return 0;
+}
+static VolArgs vol_args(const float *density, const float *temperature, int nx, int ny, int nz, const float *bmin, const float *bmax, float density_max) {
+    VolArgs v{};
+    v.density = density; v.temperature = temperature;
+    v.nx = nx; v.ny = ny; v.nz = nz;
+    v.min_x = bmin[0]; v.min_y = bmin[1]; v.min_z = bmin[2];
+    v.ext_x = bmax[0] - bmin[0]; v.ext_y = bmax[1] - bmin[1]; v.ext_z = bmax[2] - bmin[2];
+    v.density_max = density_max;
+    return v;
+}
+
+int glrtx_upload_volume(glrtx_ctx *c, const float *density, const float *temperature, int nx, int ny, int nz, const float bbox_min[3],
+                        const float bbox_max[3], float density_max) {
+    if (!c) return fail(nullptr, GLRTX_EINVAL, "glrtx_upload_volume: NULL context");
+    seal_feed(c);  // (nothing is appended to an open launch across this call: glrtx_ctx::OpenFeed)
+    const int chk = check_volume(c, "glrtx_upload_volume", density, temperature, nx, ny, nz, bbox_min, bbox_max, true);
+    if (chk < 0) return chk;
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));  // (a launch in flight may still read the old grids)
+    if (chk == 1) {
+        dev_free(c->volDensity); dev_free(c->volTemp);
+        c->vol = VolArgs{};
+        c->have_volume = false;
+        return GLRTX_OK;
+    }
+    c->have_volume = false;
+    const size_t bytes = (size_t)nx * ny * nz * sizeof(float);
+    int rc;
+    if ((rc = dev_upload(c, c->volDensity, density, bytes))) return rc;
+    if ((rc = dev_upload(c, c->volTemp, temperature, bytes))) return rc;
+    c->vol = vol_args((const float *)c->volDensity.p, (const float *)c->volTemp.p, nx, ny, nz, bbox_min, bbox_max, density_max);
+    c->have_volume = true;
+    return GLRTX_OK;
+}
+
+// Debug export: one synchronous kernel on the current device, host arrays in and out.
+static int vmath_run(const char *fn, const float *in, size_t n_in, const float *grid, size_t n_grid, const VolArgs *v, float *out, size_t n_out, int op) {
+    if (n_in == 0) return GLRTX_OK;
+    if (n_in > (size_t)INT32_MAX / 4) return fail(nullptr, GLRTX_EINVAL, "%s: n = %zu too large", fn, n_in);
+    float *d_in = nullptr, *d_out = nullptr, *d_grid = nullptr;
+    int rc = GLRTX_OK;
+    hipError_t e = hipMalloc(&d_in, n_in * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc(&d_out, n_out * sizeof(float));
+    if (e == hipSuccess && grid) e = hipMalloc(&d_grid, n_grid * sizeof(float));
+    if (e == hipSuccess) e = hipMemcpy(d_in, in, n_in * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess && grid) e = hipMemcpy(d_grid, grid, n_grid * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        if (v) {
+            VolArgs va = *v;
+            va.density = d_grid; va.temperature = d_grid;
+            const int n = (int)n_out;
+            hipLaunchKernelGGL(volume_lookup_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, va, d_in, n, d_out);
+        } else {
+            const int n = (int)n_in;
+            hipLaunchKernelGGL(volume_math_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, op, d_in, n, d_out);
+        }
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(out, d_out, n_out * sizeof(float), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) rc = fail(nullptr, GLRTX_EDEVICE, "%s: %s", fn, hipGetErrorString(e));
+    if (d_in) (void)hipFree(d_in);
+    if (d_out) (void)hipFree(d_out);
+    if (d_grid) (void)hipFree(d_grid);
+    return rc;
+}
+
+int glrtx_debug_volume_math(int op, const float *in, size_t n, float *out) {
+    if (op < GLRTX_VMATH_LOG || op > GLRTX_VMATH_BLACKBODY) return fail(nullptr, GLRTX_EINVAL, "glrtx_debug_volume_math: unknown op %d", op);
+    if (n && (!in || !out)) return fail(nullptr, GLRTX_EINVAL, "glrtx_debug_volume_math: NULL buffer");
+    return vmath_run("glrtx_debug_volume_math", in, n, nullptr, 0, nullptr, out, op == GLRTX_VMATH_BLACKBODY ? 3 * n : n, op);
+}
+
+int glrtx_debug_volume_lookup(const float *grid, int nx, int ny, int nz, const float bbox_min[3], const float bbox_max[3], const float *pos,
+                              size_t n, float *out) {
+    const int chk = check_volume(nullptr, "glrtx_debug_volume_lookup", grid, nullptr, nx, ny, nz, bbox_min, bbox_max, false);
+    if (chk < 0) return chk;
+    if (chk == 1) return fail(nullptr, GLRTX_EINVAL, "glrtx_debug_volume_lookup: no grid");
+    if (n && (!pos || !out)) return fail(nullptr, GLRTX_EINVAL, "glrtx_debug_volume_lookup: NULL buffer");
+    const VolArgs v = vol_args(nullptr, nullptr, nx, ny, nz, bbox_min, bbox_max, 0.0f);
+    return vmath_run("glrtx_debug_volume_lookup", pos, 3 * n, grid, (size_t)nx * ny * nz, &v, out, n, 0);
 }
 
 int glrtx_set_partition(glrtx_ctx *c, int rank, int world, int stripe_rows) {
@@ -1628,6 +1728,7 @@ static int render_one(glrtx_ctx *c, const glrtx_params *p) {
     if (!c->have_scene) return fail(c, GLRTX_EINVAL, "glrtx_render: no scene uploaded");
     if (!c->accum || c->width < 1) return fail(c, GLRTX_EINVAL, "glrtx_render: no accumulator (call glrtx_resize)");
     if (p->n_samples < 0 || p->max_depth < 0) return fail(c, GLRTX_EINVAL, "glrtx_render: negative n_samples/max_depth");
+    if ((c->ext_flags & GLRTX_EXT_VOLUME) && !c->have_volume) return fail(c, GLRTX_EINVAL, "glrtx_render: GLRTX_EXT_VOLUME is set and no volume is uploaded (glrtx_upload_volume)");
     HIP_TRY(c, hipSetDevice(c->device));
     const bool wavefront = c->variant == 2 && wgwf_can_hold(p) && c->n_spheres == 0 && c->ext_flags == 0;
     if (c->owned_rows > 0 && wavefront && c->frames_n == 1 && feed_append(c, p, p->seed, 1) == 1) {  // a launch of the same camera that is still open takes the frame itself
@@ -1686,9 +1787,11 @@ static int render_one(glrtx_ctx *c, const glrtx_params *p) {
     if (int rc = next_launch_rec(c, rec)) return rc;
     if (variant == 1) {
         // persistent kernel: grid = what is resident at once (occupancy x CUs), capped by the work available
-        using PKernel = void (*)(const KernelArgs, unsigned *, const ExtArgs);
-        const PKernel pk = ext ? (c->count_rays ? (PKernel)pt_render_persistent<true, true> : (PKernel)pt_render_persistent<false, true>)
-                               : (c->count_rays ? (PKernel)pt_render_persistent<true, false> : (PKernel)pt_render_persistent<false, false>);
+        using PKernel = void (*)(const KernelArgs, unsigned *, const ExtArgs, const VolArgs);
+        const bool vol = (c->ext_flags & GLRTX_EXT_VOLUME) != 0;  // (render_one has checked that a volume is uploaded)
+        const PKernel pk = vol   ? (c->count_rays ? (PKernel)pt_render_persistent<true, true, true> : (PKernel)pt_render_persistent<false, true, true>)
+                           : ext ? (c->count_rays ? (PKernel)pt_render_persistent<true, true> : (PKernel)pt_render_persistent<false, true>)
+                                 : (c->count_rays ? (PKernel)pt_render_persistent<true, false> : (PKernel)pt_render_persistent<false, false>);
         ExtArgs ex{};
         ex.spheres = (const float4 *)c->spheres.p; ex.sphere_mat = (const int *)c->sphereMat.p;
         ex.n_spheres = c->n_spheres; ex.flags = c->ext_flags;
@@ -1705,8 +1808,9 @@ static int render_one(glrtx_ctx *c, const glrtx_params *p) {
         if (grid < 1) grid = 1;
         HIP_TRY(c, hipMemsetAsync(c->work.p, 0, sizeof(unsigned), c->stream));
         HIP_TRY(c, hipEventRecord(rec->ev0, c->stream));
-        c->last_kernel = ext ? "pt_render_persistent (extensions)" : "pt_render_persistent";
-        hipLaunchKernelGGL(pk, dim3(grid), dim3(kBlockThreads), lds_p, c->stream, a, (unsigned *)c->work.p, ex);
+        c->last_kernel = vol ? "pt_render_persistent (volume)" : ext ? "pt_render_persistent (extensions)" : "pt_render_persistent";
+        const VolArgs va = vol ? c->vol : VolArgs{};
+        hipLaunchKernelGGL(pk, dim3(grid), dim3(kBlockThreads), lds_p, c->stream, a, (unsigned *)c->work.p, ex, va);
     } else {
     HIP_TRY(c, hipEventRecord(rec->ev0, c->stream));
     c->last_kernel = "pt_render_kernel";
@@ -2288,6 +2392,14 @@ int glrtx_group_upload_scene(glrtx_group *g, const float *vert, size_t n_vert, c
     if (!g) return GLRTX_EINVAL;
     for (size_t i = 0; i < g->ctx.size(); i++)  // the scene is replicated: <= 27 MB even for 100k triangles
         if (int rc = gsub(g, (int)i, glrtx_upload_scene(g->ctx[i], vert, n_vert, tri, n_tri, mat, n_mat, light, n_light, bvh, n_nodes))) return rc;
+    return GLRTX_OK;
+}
+
+int glrtx_group_upload_volume(glrtx_group *g, const float *density, const float *temperature, int nx, int ny, int nz, const float bbox_min[3],
+                              const float bbox_max[3], float density_max) {
+    if (!g) return fail(nullptr, GLRTX_EINVAL, "glrtx_group_upload_volume: NULL group");
+    for (size_t i = 0; i < g->ctx.size(); i++)
+        if (int rc = gsub(g, (int)i, glrtx_upload_volume(g->ctx[i], density, temperature, nx, ny, nz, bbox_min, bbox_max, density_max))) return rc;
     return GLRTX_OK;
 }
 

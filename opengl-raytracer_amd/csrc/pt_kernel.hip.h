@@ -189,6 +189,60 @@ DEV float pt_cos(float x) {
 // The RNG argument is bounded (|t| < 92: state, seed in [0,1)), so the inf/NaN guard and the
 // [-1,1] clamp of the general routine cannot trigger differently; keep the clamp, drop nothing.
 
+// ------------------------------------------------------------------------------------------ log / exp / acos (volume transport)
+// The reference's GL implementation (Mesa llvmpipe) evaluates these with its own polynomial sequences, not with libm (DESIGN.md
+// section 3, "Volumes").  Restated operation by operation from the LLVM IR it generates for the fragment shader; the fused
+// multiply-adds are where that IR has llvm.fmuladd (the host JIT fuses them), every other operation is rounded on its own.
+// The constants are written as the float bit patterns the IR carries.
+DEV float bits_f(uint32_t u) { return __uint_as_float(u); }
+// log(x) = log2(x) * ln 2, log2 from exponent + a polynomial in y = (m - 1) / (m + 1), m the mantissa in [1, 2).
+DEV float lp_log(float x) {
+    const uint32_t b = __float_as_uint(x);
+    const float e = (float)((int)((b & 0x7f800000u) >> 23) - 127);
+    const float m = __uint_as_float((b & 0x007fffffu) | 0x3f800000u);
+    const float y = (m - 1.0f) / (m + 1.0f);
+    const float y2 = y * y, y4 = y2 * y2;
+    const float p0 = __builtin_fmaf(y4, bits_f(0x3ed03d59u), bits_f(0x3f13d321u));
+    const float p1 = __builtin_fmaf(y4, bits_f(0x3ece8316u), bits_f(0x3f7637f9u));
+    const float p2 = __builtin_fmaf(y4, p0, bits_f(0x4038aa3bu));
+    const float p3 = __builtin_fmaf(p1, y2, p2);
+    float l2 = __builtin_fmaf(y, p3, e);
+    l2 = (x >= __builtin_inff() || x != x) ? __builtin_inff() : l2;  // (uge: also NaN; the two selects below turn a NaN into NaN)
+    l2 = (x == 0.0f || x != x) ? -__builtin_inff() : l2;
+    l2 = !(x >= 0.0f) ? __uint_as_float(0x7fc00000u) : l2;
+    return l2 * bits_f(0x3f317218u);
+}
+// exp(x) = 2^i * p(f), x * log2(e) clamped to [-126.99999, 128] (the selects keep the operand order of x86 minps / maxps: a NaN passes through).
+DEV float lp_exp(float x) {
+    float t = x * bits_f(0x3fb8aa3bu);
+    t = 128.0f < t ? 128.0f : t;
+    t = bits_f(0xc2fdffffu) > t ? bits_f(0xc2fdffffu) : t;
+    const float fl = __builtin_floorf(t);
+    const float f = t - fl;
+    const float p2 = __uint_as_float((uint32_t)((int)fl + 127) << 23);
+    const float z = f * f;
+    const float a = __builtin_fmaf(z, bits_f(0x3af61905u), bits_f(0x3d64aa23u));
+    const float b = __builtin_fmaf(z, bits_f(0x3c134806u), bits_f(0x3e75ead4u));
+    const float c = __builtin_fmaf(z, a, bits_f(0x3f31727bu));
+    const float d = __builtin_fmaf(z, b, 1.0f);
+    return p2 * __builtin_fmaf(c, f, d);
+}
+// acos(x) = pi/2 - sign(x) * (pi/2 - sqrt(1 - |x|) * p(|x|)), no fused operations.
+DEV float lp_acos(float x) {
+    const float hpi = bits_f(0x3fc90fdbu);
+    const float ax = __builtin_fabsf(x);
+    const float s = __builtin_sqrtf(1.0f + -ax);
+    float p = ax * bits_f(0xbcc19a5fu);
+    p = bits_f(0x3da68d87u) + p;
+    p = ax * p;
+    p = bits_f(0xbe5bc094u) + p;
+    p = ax * p;
+    p = hpi + p;
+    const float r = hpi + -(s * p);
+    const float sg = (x == 0.0f || x != x) ? 0.0f : __uint_as_float((__float_as_uint(x) & 0x80000000u) | 0x3f800000u);
+    return hpi + -(sg * r);
+}
+
 // ------------------------------------------------------------------------------------------ rand() :104-111
 struct Rng {
     float x, y, sx, sy;
@@ -1162,7 +1216,138 @@ DEV Hit traverse_ext(const DevScene &sc, const ExtArgs &ex, const float4 *lds_sp
     return h;
 }
 
-DEV bool bounce_ext(const KernelArgs &a, const ExtArgs &ex, const float4 *lds_spheres, const float4 *lds_mats, int *stack, Rng &rng, Path &P, unsigned long long &rays) {
+// ------------------------------------------------------------------------------------------ volume branch :424-487 (opt-in)
+// The reference's participating media: Woodcock (delta) tracking through a density grid, blackbody emission from a temperature grid,
+// isotropic scattering.  The reference compiles the branch out (ENABLE_VOLUME 0, raytrace.frag:4); with the switch on, this is its
+// shader with ONE edit: densityLookup / temperatureLookup (:144-152) read textureLod(tex, uvw, 0.0) -- the magnification filter,
+// trilinear -- instead of texture(tex, uvw), whose filter depends on implicit derivatives across the 2x2 pixel quad (DESIGN.md
+// section 3, "Volumes").  Only the megakernel's extension instantiation with VOL = true runs it (glrtx_upload_volume + GLRTX_EXT_VOLUME).
+struct VolArgs {
+    const float *density;      // nx * ny * nz floats, x fastest (the order glTexSubImage3D reads)
+    const float *temperature;  // same shape
+    int nx, ny, nz;
+    float min_x, min_y, min_z;  // u_bboxMin
+    float ext_x, ext_y, ext_z;  // u_bboxMax - u_bboxMin (:145, the same subtraction the reference makes per lookup)
+    float density_max;          // u_densityMax
+};
+constexpr float VOL_SIGT = 0.16f;   // sigS.x + sigA.x = 0.1 + 0.1 * 0.6, folded by the GLSL compiler (:431-433)
+constexpr float VOL_ALBEDO = 0.625f; // sigS / sigT, folded likewise (:483)
+
+// One axis of the GL_REPEAT / GL_LINEAR texel pair: fract(s) * n - 0.5 (texel centres at (i + 0.5) / n), wrapped; w = weight of i1.
+DEV void vol_axis(float s, int n, int &i0, int &i1, float &w) {
+    const float f = s - __builtin_floorf(s);
+    const float c = f * (float)n - 0.5f;
+    const float fl = __builtin_floorf(c);
+    w = c - fl;
+    const int i = (c >= 0.0f) ? (int)fl : n - 1;  // c < 0 (the first half texel) or NaN: the last texel, then the first
+    const unsigned ic = (unsigned)i < (unsigned)n ? (unsigned)i : (unsigned)(n - 1);  // (f < 1 keeps i < n; the clamp only guards the fetch)
+    i0 = (int)ic;
+    i1 = i0 != n - 1 ? i0 + 1 : 0;
+}
+DEV float vol_lerp(float t, float a, float b) { return __builtin_fmaf(t, b - a, a); }
+// textureLod(tex, (pos - bboxMin) / (bboxMax - bboxMin), 0.0).x: eight corner loads, lerps in x, then y, then z.
+DEV float vol_lookup(const float *g, const VolArgs &v, float px, float py, float pz) {
+    int x0, x1, y0, y1, z0, z1;
+    float wx, wy, wz;
+    vol_axis((px - v.min_x) / v.ext_x, v.nx, x0, x1, wx);
+    vol_axis((py - v.min_y) / v.ext_y, v.ny, y0, y1, wy);
+    vol_axis((pz - v.min_z) / v.ext_z, v.nz, z0, z1, wz);
+    const int r00 = (z0 * v.ny + y0) * v.nx, r01 = (z0 * v.ny + y1) * v.nx;
+    const int r10 = (z1 * v.ny + y0) * v.nx, r11 = (z1 * v.ny + y1) * v.nx;
+    const float p0 = vol_lerp(wy, vol_lerp(wx, g[r00 + x0], g[r00 + x1]), vol_lerp(wx, g[r01 + x0], g[r01 + x1]));
+    const float p1 = vol_lerp(wy, vol_lerp(wx, g[r10 + x0], g[r10 + x1]), vol_lerp(wx, g[r11 + x0], g[r11 + x1]));
+    return vol_lerp(wz, p0, p1);
+}
+// blackBody(T) :125-142 for T = 100 v.  The compiler folds h*c, 2*h*c*c, l^5 and (l*k)*100 (the 100 of :477 moved next to l*k).
+DEV float vol_bb1(float v, uint32_t lk100, uint32_t l5) {
+    const float q = bits_f(0x1675e7cdu) / (bits_f(lk100) * v);
+    const float r = bits_f(0x25095070u) / (bits_f(l5) * (lp_exp(q) + -1.0f));
+    return r > 0.0f ? r : 0.0f;  // max(0.0, ...): NaN gives 0
+}
+DEV void vol_blackbody(float v, float &R, float &G, float &B) {
+    R = vol_bb1(v, 0x12857250u, 0x0bdb450bu);  // 610 nm
+    G = vol_bb1(v, 0x1270a42au, 0x0b82a8fau);  // 550 nm
+    B = vol_bb1(v, 0x1244e369u, 0x0abf9ffcu);  // 450 nm
+}
+
+// Debug export (glrtx_debug_volume_math / glrtx_debug_volume_lookup): the functions above on their own, one element per lane.
+__global__ __launch_bounds__(256) void volume_math_kernel(int op, const float *in, int n, float *out) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float x = in[i];
+    if (op == 0) out[i] = lp_log(x);
+    else if (op == 1) out[i] = lp_exp(x);
+    else if (op == 2) out[i] = lp_acos(x);
+    else vol_blackbody(x, out[3 * i], out[3 * i + 1], out[3 * i + 2]);
+}
+__global__ __launch_bounds__(256) void volume_lookup_kernel(const VolArgs v, const float *pos, int n, float *out) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    out[i] = vol_lookup(v.density, v, pos[3 * i], pos[3 * i + 1], pos[3 * i + 2]);
+}
+
+// A media surface hit from the front (:424): up to 8 trials (:436) of at most 256 Woodcock steps (:447); each trial's closest hit is the
+// megakernel's own traversal and counts as a ray.  Returns true when the depth loop ends.
+DEV bool bounce_volume(const KernelArgs &a, const ExtArgs &ex, const VolArgs &vo, const float4 *lds_spheres, int *stack, Rng &rng, Path &P, float h_t,
+                       unsigned long long &rays) {
+    const float tt = h_t + PT_EPS;  // :420
+    float ox = P.ox + tt * P.dx, oy = P.oy + tt * P.dy, oz = P.oz + tt * P.dz;
+    float dx = P.dx, dy = P.dy, dz = P.dz;
+    float bx = P.bx, by = P.by, bz = P.bz;
+    float Lx = P.Lx, Ly = P.Ly, Lz = P.Lz;
+    const float dm = vo.density_max;
+    const float rate = dm * VOL_SIGT;
+    bool ret = false;  // radiance() returns here: magenta for a trial ray that leaves the scene (:441), black for 256 steps without a decision (:460)
+    for (int k = 0; k < 8; k++) {
+        const Hit hn = traverse_ext<true>(a.sc, ex, lds_spheres, stack, ox, oy, oz, dx, dy, dz);  // spawnRay(nextOrg, vec3(0.0), nextDir)
+        rays++;
+        if (hn.tri == -1) { Lx = 1.0f; Ly = 0.0f; Lz = 1.0f; ret = true; break; }
+        float t = 0.0f;
+        bool pass = false;
+        for (int i = 0; i < 256; i++) {
+            t = t - lp_log(fmax_c(1.0f - pt_rand(rng), PT_EPS)) / rate;
+            if (t >= hn.t) { pass = true; break; }
+            const float density = vol_lookup(vo.density, vo, ox + t * dx, oy + t * dy, oz + t * dz);
+            if (density / dm > pt_rand(rng)) { pass = true; break; }  // (the rand() is drawn only when t < tHit)
+        }
+        if (!pass) { Lx = 0.0f; Ly = 0.0f; Lz = 0.0f; ret = true; break; }
+        if (t >= hn.t) {  // left the medium: continue behind its boundary (:464-467)
+            const float te = hn.t + PT_EPS;
+            ox = ox + te * dx; oy = oy + te * dy; oz = oz + te * dz;
+            break;
+        }
+        ox = ox + t * dx; oy = oy + t * dy; oz = oz + t * dz;
+        float R, G, B;
+        vol_blackbody(vol_lookup(vo.temperature, vo, ox, oy, oz), R, G, B);  // :472-473
+        Lx = Lx + (bx * R) / VOL_SIGT; Ly = Ly + (by * G) / VOL_SIGT; Lz = Lz + (bz * B) / VOL_SIGT;
+        const float theta = lp_acos(2.0f * pt_rand(rng) + -1.0f);  // :476-480
+        const float phi = PT_2PI * pt_rand(rng);
+        const float ct = pt_cos(theta), st = pt_sin(theta);
+        dx = st * pt_cos(phi); dy = st * pt_sin(phi); dz = ct;
+        bx = bx * VOL_ALBEDO; by = by * VOL_ALBEDO; bz = bz * VOL_ALBEDO;  // :483
+    }
+    P.Lx = Lx; P.Ly = Ly; P.Lz = Lz;
+    if (ret) return true;
+    const int depth = P.depth;
+    P.ox = ox; P.oy = oy; P.oz = oz; P.dx = dx; P.dy = dy; P.dz = dz;
+    P.spec = true;  // passedVolume (:486): the next surface's emission counts (shade_core)
+    P.depth = depth + 1;
+    // Russian roulette :549-555, as in shade_core
+    if (2 < depth) {
+        float pm = fmax_g(by, bz);
+        pm = fmax_g(bx, pm);
+        const float pq = fmin_c(pm, 0.95f);
+        const float rr = pt_rand(rng);
+        if (pq < rr) { P.bx = bx; P.by = by; P.bz = bz; return true; }
+        bx = fdiv(bx, pq); by = fdiv(by, pq); bz = fdiv(bz, pq);
+    }
+    P.bx = bx; P.by = by; P.bz = bz;
+    return P.depth >= a.max_depth;
+}
+
+template <bool VOL = false>
+DEV bool bounce_ext(const KernelArgs &a, const ExtArgs &ex, const float4 *lds_spheres, const float4 *lds_mats, int *stack, Rng &rng, Path &P, unsigned long long &rays,
+                    const VolArgs *vo = nullptr) {
     const Hit h = traverse_ext<true>(a.sc, ex, lds_spheres, stack, P.ox, P.oy, P.oz, P.dx, P.dy, P.dz);
     rays++;
     Surf S;
@@ -1174,6 +1359,10 @@ DEV bool bounce_ext(const KernelArgs &a, const ExtArgs &ex, const float4 *lds_sp
         const float r = rsq(dot3(qx, qy, qz, qx, qy, qz));
         S.nx = qx * r; S.ny = qy * r; S.nz = qz * r;
         S.mtrl = ex.sphere_mat[-2 - h.tri];
+    }
+    if (VOL && h.tri != -1) {
+        const int type = __float_as_int(load_mat(a.sc, lds_mats, S.mtrl).m0.w);
+        if (type == 5 && (-(P.dz * S.nz) - (P.dy * S.ny)) - (P.dx * S.nx) >= PT_EPS) return bounce_volume(a, ex, *vo, lds_spheres, stack, rng, P, h.t, rays);
     }
     Shade sh;
     shade_core<true>(a, lds_mats, rng, P, h.t, h.tri != -1, S, ex.flags, sh);
@@ -1348,6 +1537,7 @@ struct PersistKernArgs {
     KernelArgs a;
     unsigned *work_counter;
     ExtArgs ex;
+    VolArgs vol;
 };
 DEV const PersistKernArgs *persist_kernargs() {
     auto p = __builtin_amdgcn_kernarg_segment_ptr();  // constant address space
@@ -1355,12 +1545,15 @@ DEV const PersistKernArgs *persist_kernargs() {
     return (const PersistKernArgs *)p;
 }
 
-template <bool COUNT_RAYS, bool EXT = false>
-__global__ __launch_bounds__(kBlockThreads) void pt_render_persistent(const KernelArgs a_entry, unsigned *work_counter_entry, const ExtArgs ex_entry) {
+// VOL (implies EXT): the extension kernel with the volume branch (bounce_volume).
+template <bool COUNT_RAYS, bool EXT = false, bool VOL = false>
+__global__ __launch_bounds__(kBlockThreads) void pt_render_persistent(const KernelArgs a_entry, unsigned *work_counter_entry, const ExtArgs ex_entry,
+                                                                      const VolArgs vol_entry) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     float4 *lds_mats;
     int *stack;
-    (void)work_counter_entry; (void)ex_entry;
+    (void)work_counter_entry; (void)ex_entry; (void)vol_entry;
+    static_assert(!VOL || EXT, "the volume kernel is an extension kernel");
     lds_setup(a_entry, lds_raw, lds_mats, stack);
     float4 *lds_spheres = nullptr;
     if (EXT) lds_spheres = ext_stage_spheres(a_entry, ex_entry, lds_raw);
@@ -1434,7 +1627,10 @@ __global__ __launch_bounds__(kBlockThreads) void pt_render_persistent(const Kern
                 fresh = false;
             }
             bool finished = true;
-            if (a.max_depth > 0) finished = EXT ? bounce_ext(a, ka->ex, lds_spheres, lds_mats, stack, rng, P, rays) : bounce(a, lds_mats, stack, rng, P, rays);
+            if (a.max_depth > 0) {
+                if (VOL) finished = bounce_ext<true>(a, ka->ex, lds_spheres, lds_mats, stack, rng, P, rays, &ka->vol);
+                else finished = EXT ? bounce_ext(a, ka->ex, lds_spheres, lds_mats, stack, rng, P, rays) : bounce(a, lds_mats, stack, rng, P, rays);
+            }
             if (finished) {
                 acc.x = acc.x + fmin_c(P.Lx, 100.0f);  // :558, :608
                 acc.y = acc.y + fmin_c(P.Ly, 100.0f);

@@ -14,7 +14,7 @@
 using namespace glrt;
 
 static void usage(const char *exe) {
-    std::printf("usage: %s -i scene.json [-s N] [--max-depth D] [--spp N] [--frames F] [--frames-in-flight B] [--bvh sah|sah-reinsert|sah-gpu|lbvh|sah-levels-cpu|lbvh-cpu|reference] [--order-by-hits] [--out file.png] [--save-every-frame] [--device G | --gpus N | --devices a,b,..] [--extensions] [--whitted]\n"
+    std::printf("usage: %s -i scene.json [-s N] [--max-depth D] [--spp N] [--frames F] [--frames-in-flight B] [--bvh sah|sah-reinsert|sah-gpu|lbvh|sah-levels-cpu|lbvh-cpu|reference] [--order-by-hits] [--out file.png] [--save-every-frame] [--device G | --gpus N | --devices a,b,..] [--extensions] [--whitted] [--enable-volume]\n"
                 "  -i, --input             scene description (JSON; schema: SURVEY.md Appendix C)            [required]\n"
                 "  -s, --sample-per-cycle  accepted for compatibility; like the reference (main.cpp:13) it is not read\n"
                 "      --max-depth D       u_maxDepth (default 16, the reference shader's default)\n"
@@ -30,13 +30,15 @@ static void usage(const char *exe) {
                 "      --devices a,b,..    the same with an explicit device list (an ordinal may repeat)\n"
                 "      --extensions        accept what the reference does not have: shapes of type \"sphere\" (center, radius) and the material\n"
                 "                          \"dielectric\" (ior, tint); parity with the reference is not defined for such scenes\n"
-                "      --whitted           with --extensions: Whitted-style transport (direct light at diffuse surfaces, specular bounces only)\n", exe);
+                "      --whitted           with --extensions: Whitted-style transport (direct light at diffuse surfaces, specular bounces only)\n"
+                "      --enable-volume     render the participating media of \"media\" shapes: the reference's ENABLE_VOLUME switch (raytrace.frag:4);\n"
+                "                          their VOL files are read (a missing one is an error only with this flag)\n", exe);
 }
 
 int main(int argc, char **argv) {
     std::string input, out = "output.png";
     int depth = 16, spp = 1, frames = 16, device = -1, in_flight = 0;
-    bool every_frame = false, extensions = false, whitted = false, order_by_hits = false;
+    bool every_frame = false, extensions = false, whitted = false, order_by_hits = false, volume = false;
     std::vector<int> devices;
     std::string bvh;
     for (int i = 1; i < argc; i++) {
@@ -58,6 +60,7 @@ int main(int argc, char **argv) {
         else if (a == "--order-by-hits") order_by_hits = true;
         else if (a == "--extensions") extensions = true;
         else if (a == "--whitted") { extensions = true; whitted = true; }
+        else if (a == "--enable-volume") volume = true;
         else if (a == "--gpus") { const int n = std::atoi(next("--gpus")); devices.clear(); for (int k = 0; k < n; k++) devices.push_back(k); }
         else if (a == "--devices") {
             devices.clear();
@@ -81,6 +84,7 @@ int main(int argc, char **argv) {
     if (!bvh.empty()) scene->setBvhBuilder(bvh);
     scene->enableExtensions(extensions);
     scene->setWhitted(whitted);
+    scene->enableVolume(volume);
     scene->parse(input);
 
     window->mainloop(scene);

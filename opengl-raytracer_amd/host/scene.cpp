@@ -48,6 +48,10 @@ void Scene::parse(const std::string &filename) {
     if (const char *e = std::getenv("GLRT_EXTENSIONS")) extensions_ = extensions_ || std::atoi(e) != 0;
     spheres.clear();
     hasDielectric_ = false;
+    volumeSpecs_.clear();
+    hasVolume_ = false;
+    volDensity_ = VolumeGrid{};
+    volTemperature_ = VolumeGrid{};
 
     // film (scene.cpp:57-60)
     width = json["film"]["width"].int_value();
@@ -100,8 +104,30 @@ void Scene::parse(const std::string &filename) {
             else vec3(sh["emission"], m.emission);
         } else if (material == "media") {
             // The reference uploads two 3D textures here, but its shader's volume branch is compiled
-            // out (raytrace.frag:4, :424-487): the material only marks the surface as pass-through.
+            // out (raytrace.frag:4, :424-487): the material only marks the surface as pass-through -- unless enableVolume(true).
             fill3(m.type, (float)MaterialType::Media);
+            const Json &vol = sh["volume"];
+            if (vol.is_object()) {
+                VolumeSpec spec;
+                spec.density = baseDir + "/" + vol["density"].string_value();
+                spec.temperature = baseDir + "/" + vol["temperature"].string_value();
+                fill3(spec.bboxMin, 0.0f);
+                fill3(spec.bboxMax, 0.0f);
+                if (vol["bboxMin"].is_null()) GLRT_Warn("volume node does not have \"bboxMin\" key!");
+                else vec3(vol["bboxMin"], spec.bboxMin);
+                if (vol["bboxMax"].is_null()) GLRT_Warn("volume node does not have \"bboxMax\" key!");
+                else vec3(vol["bboxMax"], spec.bboxMax);
+                volumeSpecs_.push_back(spec);
+                if (volume_ && volumeSpecs_.size() == 1) {  // only volumes[0] is ever bound (window.cpp:271-286)
+                    std::string verr;
+                    if (!readVol(spec.density, volDensity_, verr)) GLRT_FatalError("Failed to load volume: %s", verr.c_str());
+                    if (!readVol(spec.temperature, volTemperature_, verr)) GLRT_FatalError("Failed to load volume: %s", verr.c_str());
+                    if (volDensity_.nx != volTemperature_.nx || volDensity_.ny != volTemperature_.ny || volDensity_.nz != volTemperature_.nz)
+                        GLRT_FatalError("volume: density (%dx%dx%d) and temperature (%dx%dx%d) grids differ in size", volDensity_.nx, volDensity_.ny,
+                                        volDensity_.nz, volTemperature_.nx, volTemperature_.ny, volTemperature_.nz);
+                    hasVolume_ = true;
+                }
+            }
         } else if (material == "dielectric" && extensions_) {
             // EXTENSION (no reference counterpart): MTRL_DIELECTRIC = 4 (raytrace.frag:32); param0 = tint, param1.x = index of refraction
             fill3(m.type, 4.0f);
@@ -342,6 +368,29 @@ struct SceneProbe {
     }
 };
 }  // namespace glrt
+
+// Volume block probe: enable = Scene::enableVolume before parse().  info = {number of volume blocks, 1 if the first block's files were loaded,
+// nx, ny, nz}; bbox = the first block's {bboxMin, bboxMax}; density_max = u_densityMax Window would upload.
+namespace glrt {
+struct SceneVolumeProbe {
+    static int run(const char *json, int enable, int info[5], float bbox[6], float *density_max) {
+        Scene sc;
+        sc.enableVolume(enable != 0);
+        sc.parse(json);
+        info[0] = (int)sc.volumeSpecs_.size();
+        info[1] = sc.hasVolume_ ? 1 : 0;
+        info[2] = sc.volDensity_.nx; info[3] = sc.volDensity_.ny; info[4] = sc.volDensity_.nz;
+        if (!sc.volumeSpecs_.empty())
+            for (int k = 0; k < 3; k++) { bbox[k] = sc.volumeSpecs_[0].bboxMin[k]; bbox[3 + k] = sc.volumeSpecs_[0].bboxMax[k]; }
+        *density_max = sc.hasVolume_ ? sc.volDensity_.maxValue() : 0.0f;
+        return 0;
+    }
+};
+}  // namespace glrt
+
+extern "C" GLRT_API int glrt_scene_volume_probe(const char *json, int enable, int info[5], float bbox[6], float *density_max) {
+    return glrt::SceneVolumeProbe::run(json, enable, info, bbox, density_max);
+}
 
 extern "C" GLRT_API int glrt_scene_probe(const char *json, const char *bvh_kind, long long counts[8], float view[16], float proj[16],
                                          float lens[2], float *vert, float *tri, float *mat, float *light, float *nodes) {

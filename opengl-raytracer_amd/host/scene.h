@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "common.h"
+#include "volume.h"
 
 namespace glrt {
 
@@ -49,6 +50,17 @@ public:
     void enableExtensions(bool on) { extensions_ = on; }
     void setWhitted(bool on) { whitted_ = on; }
     size_t numSpheres() const { return spheres.size() / 5; }
+    // Participating media (the reference's volume branch, which it compiles out: raytrace.frag:4; include/glrtx.h GLRTX_EXT_VOLUME).  parse() always keeps
+    // each "media" shape's "volume" block {density, temperature, bboxMin, bboxMax} (scene.cpp:174-214) in volumeSpecs(); with enableVolume(true) (call
+    // before parse()) it also reads the FIRST block's two VOL files -- a missing or unreadable file is then a FatalError -- and Window uploads them and
+    // sets GLRTX_EXT_VOLUME.  Off, the files are not opened and the media surfaces pass rays through unchanged, as in the reference.
+    struct VolumeSpec {
+        std::string density, temperature;  // paths, resolved against the scene file's directory
+        float bboxMin[3], bboxMax[3];      // from the JSON (u_bboxMin / u_bboxMax), not from the files
+    };
+    void enableVolume(bool on) { volume_ = on; }
+    const std::vector<VolumeSpec> &volumeSpecs() const { return volumeSpecs_; }
+    bool hasVolume() const { return hasVolume_; }
 
 private:
     void finalize();  // lights list + BVH (scene.cpp:246-256)
@@ -66,9 +78,13 @@ private:
     std::string bvhBuilder_ = "sah";
     std::vector<float> spheres;  // extension: 5 floats per sphere {cx, cy, cz, radius, material}
     bool extensions_ = false, whitted_ = false, hasDielectric_ = false;
+    std::vector<VolumeSpec> volumeSpecs_;
+    bool volume_ = false, hasVolume_ = false;
+    VolumeGrid volDensity_, volTemperature_;  // volumeSpecs_[0]'s files (only with enableVolume(true)); only the first volume is rendered (window.cpp:271-286)
 
     friend class Window;
     friend struct SceneProbe;
+    friend struct SceneVolumeProbe;
 };
 
 // OBJ triangles the way the reference's loader yields them (trimesh.cpp:113-191): three fresh

@@ -52,21 +52,30 @@ void Window::mainloop(const std::shared_ptr<Scene> &scene_, double fps) {
         scene->materials.empty() ? nullptr : &scene->materials[0].type[0], scene->materials.size(),
         scene->lights.empty() ? nullptr : &scene->lights[0].indices[0], scene->lights.size(),
         scene->nodes.empty() ? nullptr : &scene->nodes[0].bboxMin[0], scene->nodes.size()));
-    // extensions the scene asked for (Scene::enableExtensions; none in a reference scene): analytic spheres, dielectric, Whitted
-    if (!scene->spheres.empty() || scene->hasDielectric_ || scene->whitted_) {
-        const int flags = (scene->hasDielectric_ ? GLRTX_EXT_DIELECTRIC : 0) | (scene->whitted_ ? GLRTX_EXT_WHITTED : 0);
+    // the volume of the media materials (Scene::enableVolume): the reference's bindings of volumes[0] (window.cpp:271-286) -- the first nx*ny*nz floats of each
+    // file (glTexSubImage3D with GL_RED), u_densityMax = the density file's maximum, the JSON's bbox
+    if (scene->hasVolume_) {
+        const VolumeGrid &d = scene->volDensity_, &t = scene->volTemperature_;
+        const Scene::VolumeSpec &v = scene->volumeSpecs_[0];
+        GLRTX_CHECK(glrtx_group_upload_volume(grp_, d.texels(), t.texels(), d.nx, d.ny, d.nz, v.bboxMin, v.bboxMax, d.maxValue()));
+        GLRT_Info("volume: %d x %d x %d voxels, density max %g", d.nx, d.ny, d.nz, d.maxValue());
+    }
+    // extensions the scene asked for (Scene::enableExtensions; none in a reference scene): analytic spheres, dielectric, Whitted; the volume flag
+    if (!scene->spheres.empty() || scene->hasDielectric_ || scene->whitted_ || scene->hasVolume_) {
+        const int flags = (scene->hasDielectric_ ? GLRTX_EXT_DIELECTRIC : 0) | (scene->whitted_ ? GLRTX_EXT_WHITTED : 0) | (scene->hasVolume_ ? GLRTX_EXT_VOLUME : 0);
         for (int i = 0; i < glrtx_group_size(grp_); i++) {
             glrtx_ctx *c = glrtx_group_ctx(grp_, i);
             if (glrtx_upload_spheres(c, scene->spheres.empty() ? nullptr : scene->spheres.data(), scene->spheres.size() / 5) != GLRTX_OK ||
                 glrtx_set_extensions(c, flags) != GLRTX_OK)
                 GLRT_FatalError("extensions: %s", glrtx_last_error(c));
         }
-        GLRT_Info("extensions: %zu analytic spheres%s%s (not part of the reference)", scene->spheres.size() / 5,
-                  scene->hasDielectric_ ? ", dielectric" : "", scene->whitted_ ? ", Whitted termination" : "");
+        if (!scene->spheres.empty() || scene->hasDielectric_ || scene->whitted_)
+            GLRT_Info("extensions: %zu analytic spheres%s%s (not part of the reference)", scene->spheres.size() / 5,
+                      scene->hasDielectric_ ? ", dielectric" : "", scene->whitted_ ? ", Whitted termination" : "");
     }
     resize(scene->width, scene->height);
     if (const char *e = std::getenv("GLRT_BVH_ORDER")) orderByHits_ = std::string(e) == "hits";
-    if (orderByHits_ && !scene->nodes.empty() && scene->spheres.empty() && !scene->hasDielectric_ && !scene->whitted_) {
+    if (orderByHits_ && !scene->nodes.empty() && scene->spheres.empty() && !scene->hasDielectric_ && !scene->whitted_ && !scene->hasVolume_) {
         // one calibration frame on the first member's share of the rows (interleaved stripes: a fair sample of the image), counted by the render kernel itself
         glrtx_params p;
         frameParams(p);

@@ -15,6 +15,8 @@ from .host import LIB_DIR, PKG_ROOT
 GLRTX_OK = 0
 GLRTX_EINVAL, GLRTX_EDEVICE, GLRTX_ESCENE, GLRTX_EDEPTH, GLRTX_ENOMEM, GLRTX_EBUSY = -1, -2, -3, -4, -5, -6
 EXT_DIELECTRIC, EXT_WHITTED = 1, 2
+EXT_VOLUME = 4  # the reference's volume branch (ENABLE_VOLUME, raytrace.frag:4); pinned, see upload_volume
+VMATH_LOG, VMATH_EXP, VMATH_ACOS, VMATH_BLACKBODY = 0, 1, 2, 3
 FALLBACK_DEPTH, FALLBACK_SAMPLES, FALLBACK_EXTENSIONS = 1, 2, 4
 
 
@@ -64,7 +66,8 @@ EXPORTS = ["glrtx_abi_version", "glrtx_create", "glrtx_destroy", "glrtx_last_err
            "glrtx_group_upload_scene", "glrtx_group_resize", "glrtx_group_clear", "glrtx_group_render", "glrtx_group_render_frames",
            "glrtx_debug_resolve_burst", "glrtx_hit_histogram", "glrtx_group_sync", "glrtx_group_read_accum", "glrtx_group_resolve_rgba8", "glrtx_group_get_stats", "glrtx_group_gather_copies",
            "glrtx_present_enable", "glrtx_present_acquire", "glrtx_present_release", "glrtx_present_get_stats",
-           "glrtx_group_present_enable", "glrtx_group_present_acquire", "glrtx_group_present_release", "glrtx_group_present_get_stats"]
+           "glrtx_group_present_enable", "glrtx_group_present_acquire", "glrtx_group_present_release", "glrtx_group_present_get_stats",
+           "glrtx_upload_volume", "glrtx_group_upload_volume", "glrtx_debug_volume_math", "glrtx_debug_volume_lookup"]
 
 _lib = None
 
@@ -118,6 +121,10 @@ def lib():
         L.glrtx_timer_end.argtypes = [vp, C.POINTER(C.c_float)]
         L.glrtx_upload_spheres.argtypes = [vp, fp, C.c_size_t]
         L.glrtx_set_extensions.argtypes = [vp, C.c_int]
+        L.glrtx_upload_volume.argtypes = [vp, fp, fp, C.c_int, C.c_int, C.c_int, fp, fp, C.c_float]
+        L.glrtx_group_upload_volume.argtypes = [vp, fp, fp, C.c_int, C.c_int, C.c_int, fp, fp, C.c_float]
+        L.glrtx_debug_volume_math.argtypes = [C.c_int, fp, C.c_size_t, fp]
+        L.glrtx_debug_volume_lookup.argtypes = [fp, C.c_int, C.c_int, C.c_int, fp, fp, fp, C.c_size_t, fp]
         L.glrtx_group_create.argtypes = [C.POINTER(vp), C.POINTER(C.c_int), C.c_int]
         L.glrtx_group_destroy.argtypes = [vp]
         L.glrtx_group_destroy.restype = None
@@ -174,6 +181,43 @@ def make_params(p) -> Params:
     return r
 
 
+def _upload_volume(fn, h, density, temperature, bbox_min, bbox_max, density_max):
+    lo, hi = _f32(np.asarray(bbox_min).reshape(3)), _f32(np.asarray(bbox_max).reshape(3))
+    if density is None:
+        return fn(h, None, None, 0, 0, 0, _fp(lo), _fp(hi), 0.0)
+    d, t = _f32(density), _f32(temperature)
+    if d.ndim != 3 or t.shape != d.shape:
+        raise ValueError(f"upload_volume: grids must be (nz, ny, nx) and of one shape, got {d.shape} and {t.shape}")
+    nz, ny, nx = d.shape
+    dm = float(d.max()) if density_max is None else float(density_max)
+    return fn(h, _fp(d), _fp(t), nx, ny, nz, _fp(lo), _fp(hi), dm)
+
+
+def volume_math(op, x):
+    """glrtx_debug_volume_math on the current device: the kernel's log / exp / acos / blackBody (VMATH_*) of float32 array x."""
+    L = lib()
+    a = _f32(np.asarray(x).reshape(-1))
+    out = np.zeros((a.size, 3) if op == VMATH_BLACKBODY else a.size, np.float32)
+    rc = L.glrtx_debug_volume_math(int(op), _fp(a), a.size, _fp(out))
+    if rc != 0:
+        raise GlrtxError(rc, L.glrtx_last_error(None).decode())
+    return out
+
+
+def volume_lookup(grid, bbox_min, bbox_max, pos):
+    """glrtx_debug_volume_lookup on the current device: the kernel's trilinear lookup of grid (nz, ny, nx) at pos (n, 3)."""
+    L = lib()
+    g = _f32(grid)
+    p = _f32(np.asarray(pos).reshape(-1, 3))
+    lo, hi = _f32(np.asarray(bbox_min).reshape(3)), _f32(np.asarray(bbox_max).reshape(3))
+    out = np.zeros(p.shape[0], np.float32)
+    nz, ny, nx = g.shape
+    rc = L.glrtx_debug_volume_lookup(_fp(g), nx, ny, nz, _fp(lo), _fp(hi), _fp(p), p.shape[0], _fp(out))
+    if rc != 0:
+        raise GlrtxError(rc, L.glrtx_last_error(None).decode())
+    return out
+
+
 class Device:
     """One glrtx_ctx: one GPU, one row-stripe partition of the image."""
 
@@ -226,8 +270,14 @@ class Device:
         self._ck(self.L.glrtx_upload_spheres(self.h, _fp(sp), sp.shape[0]))
 
     def set_extensions(self, flags: int):
-        """EXTENSION (parity unpinned): EXT_DIELECTRIC | EXT_WHITTED."""
+        """EXT_DIELECTRIC | EXT_WHITTED (extensions, parity unpinned) | EXT_VOLUME (the reference's volume branch, pinned)."""
         self._ck(self.L.glrtx_set_extensions(self.h, int(flags)))
+
+    def upload_volume(self, density, temperature, bbox_min, bbox_max, density_max=None):
+        """The volume of the media materials (glrtx_upload_volume): density / temperature grids shaped (nz, ny, nx) -- x fastest, as
+        glTexSubImage3D reads them -- and the bbox from the scene.  density_max defaults to the density grid's maximum (the reference takes
+        the maximum over the whole file).  density None removes the volume.  Rendering needs EXT_VOLUME (set_extensions) as well."""
+        self._ck(_upload_volume(self.L.glrtx_upload_volume, self.h, density, temperature, bbox_min, bbox_max, density_max))
 
     def set_partition(self, rank, world, stripe_rows=16):
         self._ck(self.L.glrtx_set_partition(self.h, rank, world, stripe_rows))
@@ -371,6 +421,10 @@ class Group:
             rc = fn(self.L.glrtx_group_ctx(self.h, i), *args)
             if rc != 0:
                 raise GlrtxError(rc, self.L.glrtx_last_error(self.L.glrtx_group_ctx(self.h, i)).decode())
+
+    def upload_volume(self, density, temperature, bbox_min, bbox_max, density_max=None):
+        """Device.upload_volume on every member (glrtx_group_upload_volume)."""
+        self._ck(_upload_volume(self.L.glrtx_group_upload_volume, self.h, density, temperature, bbox_min, bbox_max, density_max))
 
     def upload_scene(self, scene):
         v, t, m, l, b = (_f32(scene[k]) for k in ("vert", "tri", "mat", "light", "bvh"))

@@ -37,8 +37,10 @@ def conductor(eta, kappa, alpha):
     return dict(type=MTRL_CONDUCTOR, param0=kappa, param1=eta, param2=(alpha, alpha, alpha))
 
 
-def media():
-    return dict(type=MTRL_MEDIA)
+def media(volume=None):
+    """volume (optional, for export_json_obj): the shape's "volume" block {"density": file, "temperature": file, "bboxMin": [..], "bboxMax": [..]}
+    (the reference's scene.cpp:174-214; rendered only with the volume switch, include/glrtx.h GLRTX_EXT_VOLUME)."""
+    return dict(type=MTRL_MEDIA, volume=volume) if volume is not None else dict(type=MTRL_MEDIA)
 
 
 def _mat_rows(m):
@@ -162,6 +164,87 @@ def make_params(c2w, s2c, width, height, max_depth, n_samples=1, seed=(0.137, 0.
                 height=int(height), max_depth=int(max_depth), n_samples=int(n_samples),
                 seed=(float(np.float32(seed[0])), float(np.float32(seed[1]))), aperture=float(aperture),
                 focal=float(focal))
+
+
+def box(lo, hi):
+    """Closed axis-aligned box, 12 triangles with flat OUTWARD normals: a media box is entered through a face seen from the front
+    (the volume branch, raytrace.frag:424) and its trial rays end on the inside of the opposite face."""
+    lo, hi = np.asarray(lo, np.float64), np.asarray(hi, np.float64)
+    d = hi - lo
+    X, Y, Z = np.array([d[0], 0, 0]), np.array([0, d[1], 0]), np.array([0, 0, d[2]])
+    faces = [quad(lo, Y, X), quad(lo + Z, X, Y),          # -z, +z
+             quad(lo, X, Z), quad(lo + Y, Z, X),          # -y, +y
+             quad(lo, Z, Y), quad(lo + X, Y, Z)]          # -x, +x
+    return np.concatenate([f[0] for f in faces], 0), np.concatenate([f[1] for f in faces], 0)
+
+
+# --------------------------------------------------------------------------- volumes (GLRTX_EXT_VOLUME)
+def fire_grids(n=(16, 16, 16), temperature=10.0, seed=0):
+    """A smooth blob: density and temperature fall off from a centre low in the box, with a little deterministic noise.
+    Returns (density, temperature) float32 grids shaped (nz, ny, nx), x fastest."""
+    nx, ny, nz = n
+    z, y, x = np.meshgrid((np.arange(nz) + 0.5) / nz, (np.arange(ny) + 0.5) / ny, (np.arange(nx) + 0.5) / nx, indexing="ij")
+    r2 = ((x - 0.5) / 0.35) ** 2 + ((y - 0.35) / 0.45) ** 2 + ((z - 0.5) / 0.35) ** 2
+    rng = np.random.default_rng(seed)
+    dens = np.clip(1.0 - r2, 0.0, None) * (0.8 + 0.4 * rng.random((nz, ny, nx)))
+    temp = temperature * np.clip(1.0 - 0.8 * r2, 0.0, None)
+    return dens.astype(np.float32), temp.astype(np.float32)
+
+
+def config_fire(width=1920, height=1080, max_depth=8, n_samples=1, grid=64, temperature=10.0, bvh="sah"):
+    """A media box holding a fire blob (grid^3 voxels) over a diffuse floor, a lamp above.  Returns (scene, params, volume) with
+    volume = dict(density, temperature, bbox_min, bbox_max) for Device.upload_volume."""
+    b = SceneBuilder()
+    fog = b.add_material(media())
+    grey = b.add_material(diffuse((0.7, 0.7, 0.7)))
+    lamp = b.add_material(emitter((6.0, 6.0, 6.0)))
+    lo, hi = (-1.0, 0.05, -1.0), (1.0, 2.05, 1.0)
+    b.add_mesh(*box(lo, hi), fog)
+    b.add_mesh(*quad((-6, 0, 6), (12, 0, 0), (0, 0, -12)), grey)
+    b.add_mesh(*quad((-1, 4, -1), (2, 0, 0), (0, 0, 2)), lamp)  # normal -y
+    scene = b.build(bvh)
+    dens, temp = fire_grids((grid, grid, grid), temperature)
+    c2w, s2c = camera((0, 2.2, 6), (0, 1, 0), (0, 1, 0), 40.0, width, height)
+    return scene, make_params(c2w, s2c, width, height, max_depth, n_samples), dict(density=dens, temperature=temp, bbox_min=lo, bbox_max=hi)
+
+
+def write_vol(path, grid, bbox_min=(0.0, 0.0, 0.0), bbox_max=(1.0, 1.0, 1.0)):
+    """A Mitsuba-style VOL grid file, version 3: "VOL" 3, int32 encoding 1 (float32), int32 xres yres zres channels, six float32
+    bbox values (min xyz, max xyz), then float32 data, channels fastest, then x, y, z.  grid: (nz, ny, nx) or (nz, ny, nx, channels)."""
+    g = np.asarray(grid, np.float32)
+    if g.ndim == 3:
+        g = g[..., None]
+    nz, ny, nx, nc = g.shape
+    hdr = b"VOL\x03" + np.array([1, nx, ny, nz, nc], "<i4").tobytes() + np.array([*bbox_min, *bbox_max], "<f4").tobytes()
+    with open(path, "wb") as f:
+        f.write(hdr)
+        f.write(np.ascontiguousarray(g, "<f4").tobytes())
+
+
+def read_vol(path):
+    """Inverse of write_vol: (grid (nz, ny, nx, channels) float32, bbox_min, bbox_max).  Rejects anything but version 3 float32."""
+    raw = open(path, "rb").read()
+    if len(raw) < 48 or raw[:3] != b"VOL":
+        raise ValueError(f"{path}: not a VOL file")
+    if raw[3] != 3:
+        raise ValueError(f"{path}: VOL version {raw[3]}, only 3 is supported")
+    enc, nx, ny, nz, nc = np.frombuffer(raw, "<i4", 5, 4)
+    if enc != 1:
+        raise ValueError(f"{path}: VOL encoding {enc}, only 1 (float32) is supported")
+    bb = np.frombuffer(raw, "<f4", 6, 24)
+    n = int(nx) * int(ny) * int(nz) * int(nc)
+    if nx <= 0 or ny <= 0 or nz <= 0 or nc <= 0 or len(raw) < 48 + 4 * n:
+        raise ValueError(f"{path}: VOL header {nx}x{ny}x{nz}x{nc} does not match the file size {len(raw)}")
+    g = np.frombuffer(raw, "<f4", n, 48).reshape(int(nz), int(ny), int(nx), int(nc)).astype(np.float32)
+    return g, tuple(float(v) for v in bb[:3]), tuple(float(v) for v in bb[3:])
+
+
+def volume_from_file_grid(grid):
+    """What the reference uploads from a VOL grid (scene.cpp:183-188): glTexSubImage3D with GL_RED reads the FIRST nx*ny*nz floats of
+    the data, whatever the channel count; u_densityMax is the maximum over all of it.  Returns (grid (nz, ny, nx), max)."""
+    g = np.asarray(grid, np.float32)
+    nz, ny, nx = g.shape[:3]
+    return g.reshape(-1)[: nx * ny * nz].reshape(nz, ny, nx).copy(), float(g.max())
 
 
 COPPER = dict(eta=(0.200, 0.924, 1.102), kappa=(3.912, 2.452, 2.142))
@@ -330,8 +413,12 @@ def export_json_obj(builder: SceneBuilder, directory, width, height, origin, tar
                       alpha=float(m["param2"][0]))
         elif m["type"] == MTRL_EMITTER:
             sh.update(material="emitter", emission=[float(v) for v in m["emission"]])
+        elif m["type"] == MTRL_MEDIA:
+            sh.update(material="media")
+            if m.get("volume") is not None:
+                sh["volume"] = {k: (v if isinstance(v, str) else [float(c) for c in v]) for k, v in m["volume"].items()}
         else:
-            raise ValueError("export supports diffuse / conductor / emitter shapes")
+            raise ValueError("export supports diffuse / conductor / emitter / media shapes")
         shapes.append(sh)
     cam = {"type": "perspective", "fov": fov_deg, "nearClip": near, "farClip": far,
            "lookAt": {"origin": list(origin), "target": list(target), "up": list(up)}}
