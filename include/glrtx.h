@@ -29,6 +29,8 @@
  *   glrtx_set_partition / glrtx_bind_accum / glrtx_set_stream
  *                                    no counterpart (reference is single-GPU): row-stripe sharding across
  *                                    one-process-per-GPU ranks, SURVEY.md section 8(e)
+ *   glrtx_render_adaptive            no counterpart (the reference renders every pixel of every frame): glrtx_render_frames restricted
+ *                                    to the 8x8 tiles that have not converged yet, each rendered pixel bit-identical to the full frame's
  *   glrtx_present_*                  the screen pass and saveCurrentFrame after EVERY frame of Window::mainloop, without a sync:
  *                                    src/core/window.cpp:157-164, src/shaders/screen.frag:15-25, window.cpp:383-414
  *   glrtx_stats / glrtx_timer_*      replaces the whole-frame Timer, src/core/timer.h:7-36, window.cpp:119-168
@@ -341,6 +343,39 @@ int glrtx_debug_volume_math(int op, const float *in, size_t n, float *out);
 int glrtx_debug_volume_lookup(const float *grid, int nx, int ny, int nz, const float bbox_min[3], const float bbox_max[3], const float *pos,
                               size_t n, float *out);
 
+/* ---- Adaptive sampling: spend frames only on the 8x8 tiles that have not converged (no reference counterpart; off unless called).
+ * A pixel's sample depends only on the pixel and the frame's seed (raytrace.frag:566, rand() :104-111), so rendering some pixels of a frame leaves each of them
+ * bit-identical to the full frame, and the accumulator's per-pixel count already lets pixels resolve with different sample counts (screen.frag:15-25).
+ *   glrtx_render_adaptive  at the start of the call, on the device, decides which tiles of the context's owned rows are ACTIVE; then renders n_frames frames
+ *                          with the given seeds, only the pixels of active tiles, and adds their samples to the accumulator in frame and sample order -- the
+ *                          chain of fp32 additions consecutive glrtx_render calls would form for those pixels.  Inactive tiles are not touched.  Tiles are the
+ *                          wavefront kernel's: ceil(width / 8) x ceil(owned_rows / 8) in owned-row space, row-major, partial at the right and bottom edges.
+ *                          The context gets a half buffer H (accumulator-sized, allocated on first use, zeroed by glrtx_clear / glrtx_resize): a sample is
+ *                          added to H as well whenever the pixel's count BEFORE the add is odd (H holds every second sample).  The selection is stateless:
+ *                          every call re-evaluates every tile from the accumulator and H as they stand when the call begins.  A tile is active if one of its
+ *                          in-image pixels has count < min_samples or H.w == 0, or if its error E > threshold, or E is NaN, or threshold < 0 (nothing retires:
+ *                          the call equals glrtx_render_frames bit for bit, plus H).  E is the mean over the tile's in-image pixels of
+ *                              d = (|I.r - A.r| + |I.g - A.g| + |I.b - A.b|) / sqrt(I.r + I.g + I.b + 1e-3),  I = acc.rgb / acc.w,  A = H.rgb / H.w
+ *                          (Dammertz et al.; fp32, order and summation in DESIGN.md).  Never a fed launch: an open one is sealed first.  n_frames = 0 selects only.
+ *                          Issued without a sync.  GLRTX_EINVAL, nothing changed: min_samples < 2, presentation enabled, extensions or volume on, spheres
+ *                          uploaded, variant != 2, or max_depth / n_samples beyond the wavefront kernel's path state (the megakernels have no tile list).
+ *   glrtx_adaptive_active_tiles  syncs, then reports the last selection: active and total tiles.
+ *   glrtx_read_tile_mask         syncs, then copies the last selection's mask, one byte (0 / 1) per tile, total bytes; GLRTX_EINVAL if the image has
+ *                                changed shape (resize, partition) since that selection.  glrtx_bind_accum zeroes H, like glrtx_clear.
+ *   glrtx_read_adaptive_half     syncs, then copies H (float4(rgb, count) per pixel, owned rows), like glrtx_read_accum.
+ *   glrtx_debug_adaptive_select  the selection kernels on caller arrays (width x rows float4, rows packed): the mask, E per tile (NULL: not wanted; a NaN
+ *                                is returned as 0x7FC00000), the ascending list of active tiles and its length (NULL: not wanted). */
+typedef struct glrtx_adaptive {
+    float threshold;  /* a tile retires once E <= threshold; < 0: nothing retires */
+    int min_samples;  /* every pixel of a tile needs this many samples before it may retire (>= 2) */
+} glrtx_adaptive;
+int glrtx_render_adaptive(glrtx_ctx *ctx, const glrtx_params *params, const float *seeds_xy, int n_frames, const glrtx_adaptive *cfg);
+int glrtx_adaptive_active_tiles(glrtx_ctx *ctx, int *active, int *total);
+int glrtx_read_tile_mask(glrtx_ctx *ctx, uint8_t *dst);
+int glrtx_read_adaptive_half(glrtx_ctx *ctx, float *dst_rgba, size_t dst_pitch_bytes);
+int glrtx_debug_adaptive_select(const float *accum, const float *half, int width, int rows, float threshold, int min_samples, uint8_t *mask_out,
+                                float *err_out, int *list_out, int *count_out);
+
 /* ---- Groups: the same device layer on several GPUs of one node, behind one handle and one host thread.
  * No reference counterpart (the reference is single-GPU); SURVEY.md 8(b) sketches glrtx_create(ctx**, device_ids, n) with a
  * gathering read_accum -- this is that, kept apart from the single-context calls.  Member i owns the 8-row stripes s with
@@ -367,6 +402,10 @@ int glrtx_group_clear(glrtx_group *grp);
 int glrtx_group_render(glrtx_group *grp, const glrtx_params *params);
 int glrtx_group_render_frames(glrtx_group *grp, const glrtx_params *params, const float *seeds_xy, int n_frames);
 int glrtx_group_sync(glrtx_group *grp);
+/* glrtx_render_adaptive on every member, each selecting on its own accumulator (refusals are checked on all members first); the active-tile
+ * counts are summed over the members. */
+int glrtx_group_render_adaptive(glrtx_group *grp, const glrtx_params *params, const float *seeds_xy, int n_frames, const glrtx_adaptive *cfg);
+int glrtx_group_adaptive_active_tiles(glrtx_group *grp, int *active, int *total);
 int glrtx_group_read_accum(glrtx_group *grp, float *dst_rgba, size_t dst_pitch_bytes);
 int glrtx_group_resolve_rgba8(glrtx_group *grp, uint8_t *dst, size_t dst_pitch_bytes, float gamma, int flip_y);
 int glrtx_group_get_stats(const glrtx_group *grp, glrtx_stats *out);

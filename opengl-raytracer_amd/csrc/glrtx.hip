@@ -159,6 +159,14 @@ struct glrtx_ctx {
         glrtx_present_stats st{};
     } pres;
 
+    // Adaptive sampling (glrtx_render_adaptive): the half buffer H (every second sample; accumulator-sized, allocated on first use, pitch ad_pitch x ad_rows), and what the
+    // last selection wrote -- a mask byte per tile, the ascending list of active tiles, their count in a device word -- for ad_tiles tiles.  adapt_launch: set only while
+    // glrtx_render_adaptive issues its launches (launch_wgwf then runs the ADAPT kernel, plain, on the context's stream).
+    DevBuf adHalf, adMask, adList, adCount;
+    size_t ad_pitch = 0;
+    int ad_rows = 0, ad_tiles = 0, ad_tiles_x = 0;  // (ad_tiles, ad_tiles_x: the tile grid of the last selection)
+    bool ad_selected = false, adapt_launch = false;
+
     bool count_rays = false;
     const char *last_kernel = "";  // name of the last render kernel launched (error reports)
     mutable bool counters_stale = false;          // a counting launch was issued since the device counters were last read
@@ -850,11 +858,12 @@ int launch_wgwf(glrtx_ctx *c, const KernelArgs &a_in, const glrtx_params *p, con
     const bool busy = c->last_render_done && hipEventQuery(c->last_render_done) == hipErrorNotReady;
     (void)hipGetLastError();
     const bool burst = c->last_was_render && busy && same_camera(c->last_p, *p);
-    bool fed = c->feed_ok && std::getenv("GLRTX_NO_FEED") == nullptr && c->pipeline && c->stream == c->own_stream && p->n_samples >= 1 && seeds_xy != nullptr && (n_frames > 1 || burst);
+    const bool adapt = c->adapt_launch;  // (glrtx_render_adaptive: plain, on the context's stream, always with sample planes; never fed)
+    bool fed = !adapt && c->feed_ok && std::getenv("GLRTX_NO_FEED") == nullptr && c->pipeline && c->stream == c->own_stream && p->n_samples >= 1 && seeds_xy != nullptr && (n_frames > 1 || burst);
     int fed_cap = fed ? std::min(frames_cap(c, p, (int)kFedSlots), kFeedMaxFrames) : 0;
     if (const char *v = std::getenv("GLRTX_FEED_CAP")) fed_cap = std::max(1, std::min(fed_cap, std::atoi(v)));  // (tests: launches that fill up)
     if (fed && n_frames > fed_cap) fed = false;
-    bool piped = fed || (n_frames == 1 && c->pipeline && p->n_samples >= 1 && (size_t)p->n_samples * plane_bytes <= ((size_t)1 << 30));
+    bool piped = fed || (!adapt && n_frames == 1 && c->pipeline && p->n_samples >= 1 && (size_t)p->n_samples * plane_bytes <= ((size_t)1 << 30));
     const size_t ids = total * (size_t)(fed ? fed_cap : n_frames);  // path id = frame * total + pixel
     if (ids + 1 >= (size_t)UINT32_MAX)
         return fail(c, GLRTX_EINVAL, "glrtx_render_frames: %d frames of %zu pixels exceed the 32-bit ray id space", n_frames, total);
@@ -869,13 +878,18 @@ int launch_wgwf(glrtx_ctx *c, const KernelArgs &a_in, const glrtx_params *p, con
     // config 2 -0.4 %, config 4 -1.0 % against the alternating one, the pure pair form +1.9 % (profiles/r05_state_by_position.txt).  The alternating form stays
     // compiled in (GLRTX_PAIR_FETCH=2).  Random triangle soups prefer the pair form from 10 k triangles on (-2 %; 20 k: -4.5 %, 70 k: -7 %): what decides is how
     // far apart a wave's rays are in the tree, which the record count only approximates.
-    using Kernel = void (*)(const KernelArgs, const WfArgs, unsigned *, float4 *);
+    using Kernel = void (*)(const KernelArgs, const WfArgs, unsigned *, float4 *, const int *, const unsigned *);
     const bool vine = c->sc.n_vine > 0;
     int fetch = vine ? 0 : ((size_t)c->n_fork + (size_t)c->st.n_tri >= (size_t)kPairFetchMinRecords ? 1 : 0);
     if (const char *v = std::getenv("GLRTX_PAIR_FETCH")) fetch = vine ? 0 : std::max(0, std::min(2, std::atoi(v)));
     c->st.node_fetch_last = fetch;
     const bool cr = c->count_rays;
-    const Kernel kernel = vine ? (cr ? (Kernel)pt_render_wgwf<true, true> : (Kernel)pt_render_wgwf<false, true>)
+    constexpr int A = kWgwfAdaptive;  // (the ADAPT forms of the same eight: glrtx_render_adaptive)
+    const Kernel kernel = adapt ? (vine ? (cr ? (Kernel)pt_render_wgwf<true, true, A> : (Kernel)pt_render_wgwf<false, true, A>)
+                                   : fetch == 2 ? (cr ? (Kernel)pt_render_wgwf<true, false, 2 | A> : (Kernel)pt_render_wgwf<false, false, 2 | A>)
+                                   : fetch == 1 ? (cr ? (Kernel)pt_render_wgwf<true, false, 1 | A> : (Kernel)pt_render_wgwf<false, false, 1 | A>)
+                                                : (cr ? (Kernel)pt_render_wgwf<true, false, A> : (Kernel)pt_render_wgwf<false, false, A>))
+                        : vine ? (cr ? (Kernel)pt_render_wgwf<true, true> : (Kernel)pt_render_wgwf<false, true>)
                         : fetch == 2 ? (cr ? (Kernel)pt_render_wgwf<true, false, 2> : (Kernel)pt_render_wgwf<false, false, 2>)
                         : fetch == 1 ? (cr ? (Kernel)pt_render_wgwf<true, false, 1> : (Kernel)pt_render_wgwf<false, false, 1>)
                                      : (cr ? (Kernel)pt_render_wgwf<true, false, 0> : (Kernel)pt_render_wgwf<false, false, 0>);
@@ -1042,7 +1056,7 @@ int launch_wgwf(glrtx_ctx *c, const KernelArgs &a_in, const glrtx_params *p, con
             w.seeds = (const float2 *)c->wfSeeds.p;
             w.seeds_in_lds = n_frames <= kLdsSeeds ? 1 : 0;
         }
-        if (n_frames > 1 || slot) {
+        if (n_frames > 1 || slot || adapt) {
             if ((rc = ensure(c, planeBuf, (size_t)std::max(n_planes, 1) * plane_f4 * sizeof(float4)))) return rc;
             w.planes = (float4 *)planeBuf.p;
         }
@@ -1073,6 +1087,8 @@ int launch_wgwf(glrtx_ctx *c, const KernelArgs &a_in, const glrtx_params *p, con
                   p->max_depth <= kWfDepthMax && p->n_samples <= kWfSampleMax && workPtr != nullptr;
         if (!fed && n_frames > 1) ok = ok && c->wfSeeds.bytes >= (size_t)n_frames * sizeof(float2);
         if (w.planes) ok = ok && planeBuf.bytes >= (size_t)std::max(n_planes, 1) * plane_f4 * sizeof(float4);
+        if (adapt) ok = ok && !fed && !slot && w.planes && c->ad_selected && c->ad_tiles == (int)(total >> 6) && c->adList.bytes >= (total >> 6) * sizeof(int) &&
+                      c->adMask.bytes >= (total >> 6) && c->adHalf.bytes >= (size_t)c->ad_pitch * c->owned_rows && c->ad_pitch == c->pitch_bytes;
         if (fed) ok = ok && n_frames >= 1 && n_frames <= fed_cap && fed_cap <= kFeedMaxFrames && slot->feed_d.bytes >= sizeof(FeedDev) && w.feed_host != nullptr &&
                       slot->chunks[(n_frames - 1) / kFeedChunkFrames].p != nullptr && slot->chunk_bytes == frame_bytes;
         if (!ok) return fail(c, GLRTX_EDEVICE, "internal: wgwf launch shapes inconsistent (ids %zu, max id %zu, grid %d of %zu slots (%d per CU), block_paths %d, frames %d, fed %d)", ids, max_id,
@@ -1091,9 +1107,10 @@ int launch_wgwf(glrtx_ctx *c, const KernelArgs &a_in, const glrtx_params *p, con
         HIP_TRY(c, hipGetLastError());
     }
     HIP_TRY(c, hipEventRecord(rec->ev0, rstream));
-    c->last_kernel = vine ? "pt_render_wgwf (list scan)" : "pt_render_wgwf";
+    c->last_kernel = adapt ? (vine ? "pt_render_wgwf (adaptive, list scan)" : "pt_render_wgwf (adaptive)") : vine ? "pt_render_wgwf (list scan)" : "pt_render_wgwf";
     c->counters_stale = c->counters_stale || c->count_rays;
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlockThreads), lds, rstream, a, w, workPtr, (float4 *)queueBuf.p);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlockThreads), lds, rstream, a, w, workPtr, (float4 *)queueBuf.p, adapt ? (const int *)c->adList.p : nullptr,
+                       adapt ? (const unsigned *)c->adCount.p : nullptr);
     HIP_TRY(c, hipGetLastError());
 #ifdef GLRTX_RAY_LOG
     g_dbg_last = {a, w, lds, grid, (float4 *)queueBuf.p, fetch};
@@ -1115,7 +1132,10 @@ int launch_wgwf(glrtx_ctx *c, const KernelArgs &a_in, const glrtx_params *p, con
         const dim3 g((c->width + 63) / 64, (c->owned_rows + 3) / 4);
         const glrtx_ctx::Present &P = c->pres;
         const int slot0 = pres ? (int)(P.seq % (uint64_t)P.ring) : 0;
-        if (fed && pres)
+        if (adapt)
+            hipLaunchKernelGGL(accumulate_adaptive_kernel, g, dim3(256), 0, c->stream, a.accum, (float4 *)c->adHalf.p, a.pitch_f4, c->width, c->owned_rows,
+                               (const float4 *)planeBuf.p, n_planes, (const unsigned char *)c->adMask.p, tiles8_x);
+        else if (fed && pres)
             hipLaunchKernelGGL(accumulate_present_feed_kernel, g, dim3(256), 0, c->stream, a.accum, a.pitch_f4, c->width, c->owned_rows, (const FeedDev *)slot->feed_d.p,
                                p->n_samples, (uchar4 *)P.dev.p, (size_t)c->width * (size_t)c->owned_rows, P.ring, slot0, P.inv_gamma, P.flip);
         else if (fed)
@@ -1146,6 +1166,54 @@ int launch_wgwf(glrtx_ctx *c, const KernelArgs &a_in, const glrtx_params *p, con
 
 // Whether the wavefront variant's packed path state can represent this launch (meta = depth | sample << 8 | flags << 28).
 bool wgwf_can_hold(const glrtx_params *p) { return p->max_depth <= kWfDepthMax && p->n_samples <= kWfSampleMax; }
+
+// ---- adaptive sampling (glrtx_render_adaptive)
+// The half buffer H at the accumulator's current shape, zeroed (on first adaptive use, at a clear or resize, and when the accumulator's pitch or rows have changed).
+int adapt_half_ensure(glrtx_ctx *c) {
+    const size_t bytes = c->pitch_bytes * (size_t)std::max(c->owned_rows, 1);
+    if (int rc = ensure(c, c->adHalf, bytes)) return rc;
+    HIP_TRY(c, hipMemsetAsync(c->adHalf.p, 0, bytes, c->stream));
+    c->ad_pitch = c->pitch_bytes; c->ad_rows = c->owned_rows;
+    return GLRTX_OK;
+}
+
+// Everything glrtx_render_adaptive refuses, checked before anything changes.  The megakernels have no tile list and the present ring no adaptive form.
+int adapt_check(glrtx_ctx *c, const glrtx_params *p, const float *seeds_xy, int n_frames, const glrtx_adaptive *cfg) {
+    const char *fn = "glrtx_render_adaptive";
+    if (!p || !cfg) return fail(c, GLRTX_EINVAL, "%s: NULL params or cfg", fn);
+    if (cfg->min_samples < 2) return fail(c, GLRTX_EINVAL, "%s: min_samples %d < 2 (the half buffer needs two samples)", fn, cfg->min_samples);
+    if (n_frames < 0 || (n_frames > 0 && !seeds_xy)) return fail(c, GLRTX_EINVAL, "%s: bad seeds/n_frames", fn);
+    if (!c->have_scene) return fail(c, GLRTX_EINVAL, "%s: no scene uploaded", fn);
+    if (!c->accum || c->width < 1) return fail(c, GLRTX_EINVAL, "%s: no accumulator (call glrtx_resize)", fn);
+    if (p->n_samples < 0 || p->max_depth < 0) return fail(c, GLRTX_EINVAL, "%s: negative n_samples/max_depth", fn);
+    if (c->pres.ring > 0) return fail(c, GLRTX_EINVAL, "%s: presentation is enabled (the present ring has no adaptive form)", fn);
+    if (c->ext_flags != 0) return fail(c, GLRTX_EINVAL, "%s: extensions or volume are on (only the wavefront kernel has a tile list)", fn);
+    if (c->n_spheres > 0) return fail(c, GLRTX_EINVAL, "%s: spheres are uploaded (only the wavefront kernel has a tile list)", fn);
+    if (c->variant != 2) return fail(c, GLRTX_EINVAL, "%s: variant %d (only the wavefront kernel, variant 2, has a tile list)", fn, c->variant);
+    if (!wgwf_can_hold(p)) return fail(c, GLRTX_EINVAL, "%s: max_depth %d / n_samples %d beyond the wavefront kernel's path state", fn, p->max_depth, p->n_samples);
+    return GLRTX_OK;
+}
+
+// The selection, on the context's stream behind everything issued before: mask, ascending list and count of the active tiles.
+int adapt_select(glrtx_ctx *c, const glrtx_adaptive *cfg) {
+    const int tiles8_x = (c->width + 7) / 8, tiles8_y = (c->owned_rows + 7) / 8, n_tiles = tiles8_x * tiles8_y;
+    if (c->owned_rows > 0 && (!c->adHalf.p || c->ad_pitch != c->pitch_bytes || c->ad_rows != c->owned_rows))
+        if (int rc = adapt_half_ensure(c)) return rc;
+    int rc;
+    if ((rc = ensure(c, c->adMask, (size_t)n_tiles)) || (rc = ensure(c, c->adList, (size_t)n_tiles * sizeof(int))) || (rc = ensure(c, c->adCount, sizeof(unsigned))))
+        return rc;
+    c->ad_tiles = n_tiles; c->ad_tiles_x = tiles8_x;
+    c->ad_selected = true;
+    if (n_tiles == 0) { HIP_TRY(c, hipMemsetAsync(c->adCount.p, 0, sizeof(unsigned), c->stream)); return GLRTX_OK; }
+    const int pitch_f4 = (int)(c->pitch_bytes / sizeof(float4));
+    hipLaunchKernelGGL(adaptive_select_kernel, dim3((n_tiles + 3) / 4), dim3(256), 0, c->stream, (const float4 *)c->accum, (const float4 *)c->adHalf.p, pitch_f4, c->width,
+                       c->owned_rows, tiles8_x, n_tiles, cfg->threshold, cfg->min_samples, (unsigned char *)c->adMask.p, (float *)nullptr);
+    HIP_TRY(c, hipGetLastError());
+    hipLaunchKernelGGL(adaptive_compact_kernel, dim3(1), dim3(kAdaptCompactThreads), 0, c->stream, (const unsigned char *)c->adMask.p, n_tiles, (int *)c->adList.p,
+                       (unsigned *)c->adCount.p);
+    HIP_TRY(c, hipGetLastError());
+    return GLRTX_OK;
+}
 
 }  // namespace
 
@@ -1261,6 +1329,7 @@ void glrtx_destroy(glrtx_ctx *c) {
     }
     dev_free(c->spheres); dev_free(c->sphereMat); dev_free(c->volDensity); dev_free(c->volTemp); dev_free(c->forks); dev_free(c->nrms); dev_free(c->mats); dev_free(c->lights); dev_free(c->vine);
     dev_free(c->accum_own); dev_free(c->counter); dev_free(c->rgba8); dev_free(c->work);
+    dev_free(c->adHalf); dev_free(c->adMask); dev_free(c->adList); dev_free(c->adCount);
     dev_free(c->wfState); dev_free(c->wfQ); dev_free(c->wfSeeds); dev_free(c->wfPlanes);
     dev_free(c->bvhVert); dev_free(c->bvhTri); dev_free(c->bvhNodes);
     if (c->bvhWs.p) { (void)hipFree(c->bvhWs.p); c->bvhWs.p = nullptr; c->bvhWs.bytes = 0; }
@@ -1608,10 +1677,12 @@ int glrtx_resize(glrtx_ctx *c, int width, int height) {
 
 int glrtx_clear(glrtx_ctx *c) {
     if (!c) return GLRTX_EINVAL;
+    int rc_;
     seal_feed(c);  // (nothing is appended to an open launch across this call: glrtx_ctx::OpenFeed)
     if (!c->accum) return fail(c, GLRTX_EINVAL, "glrtx_clear: no accumulator (call glrtx_resize first)");
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipMemsetAsync(c->accum, 0, c->pitch_bytes * (size_t)c->owned_rows, c->stream));
+    if (c->adHalf.p && (rc_ = adapt_half_ensure(c))) return rc_;  // (the half buffer follows the accumulator: zeroed, at the current size)
     c->pres.frame = 0;  // (images already produced keep their numbers)
     return GLRTX_OK;
 }
@@ -1635,6 +1706,7 @@ int glrtx_bind_accum(glrtx_ctx *c, void *device_ptr, size_t pitch_bytes, int cap
     c->bound_rows = capacity_rows;
     c->accum = (float4 *)device_ptr;
     c->pitch_bytes = pitch_bytes;
+    if (c->adHalf.p) return adapt_half_ensure(c);  // (another accumulator: the half buffer of the old one would be compared with unrelated samples)
     return GLRTX_OK;
 }
 
@@ -1723,6 +1795,104 @@ int glrtx_render(glrtx_ctx *c, const glrtx_params *p) {
     return render_one(c, p);
 }
 
+// Adaptive call: the selection, then n_frames frames of the active tiles only, in launches of at most what the frames-in-flight budget allows -- all of them on the
+// selection made here, at the start of the call.  Never a fed launch: an open one is sealed first, so that its frames are accumulated before these.
+int glrtx_render_adaptive(glrtx_ctx *c, const glrtx_params *p, const float *seeds_xy, int n_frames, const glrtx_adaptive *cfg) {
+    if (!c) return GLRTX_EINVAL;
+    if (int rc = adapt_check(c, p, seeds_xy, n_frames, cfg)) return rc;
+    seal_feed(c);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (int rc = adapt_select(c, cfg)) return rc;
+    if (n_frames == 0 || c->owned_rows == 0) { c->st.launches += (uint64_t)n_frames; return GLRTX_OK; }
+    const int most = std::min(n_frames, frames_cap(c, p, 1));
+    const int n_launches = (n_frames + most - 1) / most;
+    const int chunk = (n_frames + n_launches - 1) / n_launches;
+    int rc = GLRTX_OK;
+    c->adapt_launch = true;
+    for (int f0 = 0; f0 < n_frames && rc == GLRTX_OK; f0 += chunk) {
+        const int n = std::min(chunk, n_frames - f0);
+        glrtx_params q = *p;
+        q.seed[0] = seeds_xy[2 * f0]; q.seed[1] = seeds_xy[2 * f0 + 1];
+        c->frames_seeds = seeds_xy + 2 * (size_t)f0;
+        c->frames_n = n;
+        rc = render_one(c, &q);
+        c->frames_seeds = nullptr;
+        c->frames_n = 1;
+        if (rc == GLRTX_OK) c->st.launches += (uint64_t)(n - 1);
+    }
+    c->adapt_launch = false;
+    seal_feed(c);  // (the next render call starts a launch of its own)
+    return rc;
+}
+
+int glrtx_adaptive_active_tiles(glrtx_ctx *c, int *active, int *total) {
+    if (!c || !active || !total) return GLRTX_EINVAL;
+    if (!c->ad_selected) return fail(c, GLRTX_EINVAL, "glrtx_adaptive_active_tiles: no adaptive call yet");
+    if (int rc = glrtx_sync(c)) return rc;
+    unsigned n = 0;
+    HIP_TRY(c, hipMemcpy(&n, c->adCount.p, sizeof n, hipMemcpyDeviceToHost));
+    *active = (int)n;
+    *total = c->ad_tiles;
+    return GLRTX_OK;
+}
+
+int glrtx_read_tile_mask(glrtx_ctx *c, uint8_t *dst) {
+    if (!c || !dst) return GLRTX_EINVAL;
+    if (!c->ad_selected) return fail(c, GLRTX_EINVAL, "glrtx_read_tile_mask: no adaptive call yet");
+    // (the caller sizes dst by the context's CURRENT shape: a mask of another tile grid -- the image was resized or repartitioned since -- is refused, not copied)
+    if (c->ad_tiles_x != (c->width + 7) / 8 || c->ad_tiles != c->ad_tiles_x * ((c->owned_rows + 7) / 8))
+        return fail(c, GLRTX_EINVAL, "glrtx_read_tile_mask: the image changed shape since the last adaptive call (%d tiles then, %d now)", c->ad_tiles,
+                    ((c->width + 7) / 8) * ((c->owned_rows + 7) / 8));
+    if (int rc = glrtx_sync(c)) return rc;
+    if (c->ad_tiles > 0) HIP_TRY(c, hipMemcpy(dst, c->adMask.p, (size_t)c->ad_tiles, hipMemcpyDeviceToHost));
+    return GLRTX_OK;
+}
+
+int glrtx_read_adaptive_half(glrtx_ctx *c, float *dst, size_t dst_pitch_bytes) {
+    if (!c || !dst) return GLRTX_EINVAL;
+    if (!c->adHalf.p) return fail(c, GLRTX_EINVAL, "glrtx_read_adaptive_half: no half buffer (no adaptive call yet)");
+    const size_t row = (size_t)c->width * sizeof(float4);
+    if (dst_pitch_bytes < row) return fail(c, GLRTX_EINVAL, "glrtx_read_adaptive_half: dst pitch too small");
+    if (c->ad_pitch != c->pitch_bytes || c->ad_rows != c->owned_rows) return fail(c, GLRTX_EINVAL, "glrtx_read_adaptive_half: the accumulator changed shape since the last adaptive call");
+    if (int rc = glrtx_sync(c)) return rc;
+    if (c->owned_rows == 0) return GLRTX_OK;
+    HIP_TRY(c, hipMemcpy2D(dst, dst_pitch_bytes, c->adHalf.p, c->ad_pitch, row, (size_t)c->owned_rows, hipMemcpyDeviceToHost));
+    return GLRTX_OK;
+}
+
+int glrtx_debug_adaptive_select(const float *accum, const float *half, int width, int rows, float threshold, int min_samples, uint8_t *mask_out, float *err_out,
+                                int *list_out, int *count_out) {
+    const char *fn = "glrtx_debug_adaptive_select";
+    if (width < 1 || rows < 1 || width > 65536 || rows > 65536) return fail(nullptr, GLRTX_EINVAL, "%s: bad size %dx%d", fn, width, rows);
+    if (!accum || !half || !mask_out) return fail(nullptr, GLRTX_EINVAL, "%s: NULL buffer", fn);
+    const int tiles8_x = (width + 7) / 8, n_tiles = tiles8_x * ((rows + 7) / 8);
+    const size_t px_bytes = (size_t)width * rows * sizeof(float4);
+    void *d_acc = nullptr, *d_half = nullptr, *d_mask = nullptr, *d_err = nullptr, *d_list = nullptr, *d_count = nullptr;
+    hipError_t e = hipMalloc(&d_acc, px_bytes);
+    if (e == hipSuccess) e = hipMalloc(&d_half, px_bytes);
+    if (e == hipSuccess) e = hipMalloc(&d_mask, (size_t)n_tiles);
+    if (e == hipSuccess) e = hipMalloc(&d_err, (size_t)n_tiles * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc(&d_list, (size_t)n_tiles * sizeof(int));
+    if (e == hipSuccess) e = hipMalloc(&d_count, sizeof(unsigned));
+    if (e == hipSuccess) e = hipMemcpy(d_acc, accum, px_bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_half, half, px_bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(adaptive_select_kernel, dim3((n_tiles + 3) / 4), dim3(256), 0, 0, (const float4 *)d_acc, (const float4 *)d_half, width, width, rows, tiles8_x,
+                           n_tiles, threshold, min_samples, (unsigned char *)d_mask, (float *)d_err);
+        hipLaunchKernelGGL(adaptive_compact_kernel, dim3(1), dim3(kAdaptCompactThreads), 0, 0, (const unsigned char *)d_mask, n_tiles, (int *)d_list, (unsigned *)d_count);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(mask_out, d_mask, (size_t)n_tiles, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && err_out) e = hipMemcpy(err_out, d_err, (size_t)n_tiles * sizeof(float), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && list_out) e = hipMemcpy(list_out, d_list, (size_t)n_tiles * sizeof(int), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && count_out) e = hipMemcpy(count_out, d_count, sizeof(int), hipMemcpyDeviceToHost);
+    const int rc = e != hipSuccess ? fail(nullptr, GLRTX_EDEVICE, "%s: %s", fn, hipGetErrorString(e)) : GLRTX_OK;
+    for (void *q : {d_acc, d_half, d_mask, d_err, d_list, d_count})
+        if (q) (void)hipFree(q);
+    return rc;
+}
+
 // glrtx_render behind the presentation check (glrtx_render_frames checks for all its frames at once)
 static int render_one(glrtx_ctx *c, const glrtx_params *p) {
     if (!c->have_scene) return fail(c, GLRTX_EINVAL, "glrtx_render: no scene uploaded");
@@ -1731,7 +1901,7 @@ static int render_one(glrtx_ctx *c, const glrtx_params *p) {
     if ((c->ext_flags & GLRTX_EXT_VOLUME) && !c->have_volume) return fail(c, GLRTX_EINVAL, "glrtx_render: GLRTX_EXT_VOLUME is set and no volume is uploaded (glrtx_upload_volume)");
     HIP_TRY(c, hipSetDevice(c->device));
     const bool wavefront = c->variant == 2 && wgwf_can_hold(p) && c->n_spheres == 0 && c->ext_flags == 0;
-    if (c->owned_rows > 0 && wavefront && c->frames_n == 1 && feed_append(c, p, p->seed, 1) == 1) {  // a launch of the same camera that is still open takes the frame itself
+    if (c->owned_rows > 0 && wavefront && c->frames_n == 1 && !c->adapt_launch && feed_append(c, p, p->seed, 1) == 1) {  // a launch of the same camera that is still open takes the frame itself
         c->last_was_render = true; c->last_p = *p;
         return presenting(c) ? present_issue(c, 1) : GLRTX_OK;
     }
@@ -2435,6 +2605,27 @@ int glrtx_group_render_frames(glrtx_group *g, const glrtx_params *p, const float
     if (int rc = group_present_prepare(g, n_frames)) return rc;
     for (size_t i = 0; i < g->ctx.size(); i++)
         if (int rc = gsub(g, (int)i, glrtx_render_frames(g->ctx[i], p, seeds_xy, n_frames))) return rc;
+    return GLRTX_OK;
+}
+
+int glrtx_group_render_adaptive(glrtx_group *g, const glrtx_params *p, const float *seeds_xy, int n_frames, const glrtx_adaptive *cfg) {
+    if (!g) return GLRTX_EINVAL;
+    for (size_t i = 0; i < g->ctx.size(); i++)  // (every member's refusals before any member changes anything)
+        if (int rc = gsub(g, (int)i, adapt_check(g->ctx[i], p, seeds_xy, n_frames, cfg))) return rc;
+    for (size_t i = 0; i < g->ctx.size(); i++)  // each member selects on its own accumulator
+        if (int rc = gsub(g, (int)i, glrtx_render_adaptive(g->ctx[i], p, seeds_xy, n_frames, cfg))) return rc;
+    return GLRTX_OK;
+}
+
+int glrtx_group_adaptive_active_tiles(glrtx_group *g, int *active, int *total) {
+    if (!g || !active || !total) return GLRTX_EINVAL;
+    int a = 0, t = 0;
+    for (size_t i = 0; i < g->ctx.size(); i++) {
+        int ai = 0, ti = 0;
+        if (int rc = gsub(g, (int)i, glrtx_adaptive_active_tiles(g->ctx[i], &ai, &ti))) return rc;
+        a += ai; t += ti;
+    }
+    *active = a; *total = t;
     return GLRTX_OK;
 }
 

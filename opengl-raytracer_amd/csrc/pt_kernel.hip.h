@@ -2314,6 +2314,10 @@ struct WgwfKernArgs {
     WfArgs w;
     unsigned *work_counter;
     float4 *wg_queues;
+    // adaptive launches (ADAPT: glrtx_render_adaptive): the ascending list of active tiles and the device word with their count, written by adaptive_select_kernel /
+    // adaptive_compact_kernel in front of the launch.  Trailing kernel arguments, null in every other launch: behind wg_queues no offset of an existing argument moves.
+    const int *adapt_list;
+    const unsigned *adapt_count;
 };
 DEV const WgwfKernArgs *wgwf_kernargs() {
     auto p = __builtin_amdgcn_kernarg_segment_ptr();  // constant address space
@@ -2435,8 +2439,17 @@ DEV void wg_feed_topup(int kWgPaths, unsigned *ctl, int cur, unsigned *work_coun
     if (np > 0) ctl[12] = got > 0 ? 0u : ctl[12] + 1u;  // (the trip guard counts trips, not looks)
 }
 
+// kWgwfAdaptive in pt_render_wgwf's third template argument (FETCH | kWgwfAdaptive): the ADAPT form of an instantiation, for an adaptive launch
+// (glrtx_render_adaptive).  (A flag in the existing argument rather than a fourth one: the eight existing instantiations keep their names and their code.)
+// ADAPT: the launch's tile counter runs over n_active x n_frames tiles -- n_active read from the device word the selection wrote, not from the kernel arguments --
+// and counter value g is tile adapt_list[g % n_active] of frame g / n_active.  Only the top-up differs: the path ids it hands out are real ids (frame * total +
+// tile-order pixel), so everything downstream -- wf_pixel, wf_seed, wf_add_sample, WfArgs::split -- is the same code.  The adaptive list and count are trailing
+// kernel arguments (null in every other launch: behind wg_queues no offset of an existing argument moves), read through wgwf_kernargs.
+constexpr int kWgwfAdaptive = 4;
 template <bool COUNT_RAYS, bool VINE, int FETCH = 0>
-__global__ __launch_bounds__(kBlockThreads, GLRTX_WGWF_WAVES) void pt_render_wgwf(const KernelArgs a, const WfArgs w, unsigned *work_counter, float4 *wg_queues) {
+__global__ __launch_bounds__(kBlockThreads, GLRTX_WGWF_WAVES) void pt_render_wgwf(const KernelArgs a, const WfArgs w, unsigned *work_counter, float4 *wg_queues,
+                                                                                  const int * /*adapt_list*/, const unsigned * /*adapt_count*/) {
+    constexpr bool ADAPT = (FETCH & kWgwfAdaptive) != 0;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     // LDS: materials | stack | ctl[16].  The workgroup's ray/path queues live in its private slice of a
     // global buffer (L2-resident, read and written with unit stride).
@@ -2484,7 +2497,7 @@ __global__ __launch_bounds__(kBlockThreads, GLRTX_WGWF_WAVES) void pt_render_wgw
         } else if (tid_topup == 0u) {
             // 8x8-pixel tiles (64 consecutive tile-order ids each), frame-major; formed here from the kernarg segment, not once in front of the persistent
             // loop, for the same reason as gss_div below
-            const int n_tiles = wgwf_kernargs()->w.tiles_per_frame * wgwf_kernargs()->w.n_frames;
+            const int n_tiles = (ADAPT ? (int)*wgwf_kernargs()->adapt_count : wgwf_kernargs()->w.tiles_per_frame) * wgwf_kernargs()->w.n_frames;
             int want = (kWgPaths - (int)ctl[4 + cur]) >> 6;
             int base = 0, got = 0;
             // (gss_div is read from the kernarg segment HERE: taken from the by-value argument the compiler hoists the division's reciprocal and sign
@@ -2520,7 +2533,12 @@ __global__ __launch_bounds__(kBlockThreads, GLRTX_WGWF_WAVES) void pt_render_wgw
             const WgwfKernArgs *kt = wgwf_kernargs();
             const unsigned new_base = kt->w.set_base(cur, (int)blockIdx.x) + (unsigned)np;  // state index of the first new path: set `cur`, behind the live ones
             for (int k = threadIdx.x; k < got; k += kBlockThreads) {
-                const int id = tile0 * 64 + k;  // tile g = tile0 + (k >> 6) of the frame-major tile order holds ids 64 g .. 64 g + 63
+                int id = tile0 * 64 + k;  // tile g = tile0 + (k >> 6) of the frame-major tile order holds ids 64 g .. 64 g + 63
+                if (ADAPT) {  // counter value g: frame g / n_active, the (g % n_active)-th active tile (n_active > 0: this workgroup was given tiles)
+                    const int g = tile0 + (k >> 6), n_active = (int)*kt->adapt_count;
+                    const int frame = g / n_active;
+                    id = frame * kt->w.total + kt->adapt_list[g - frame * n_active] * 64 + (k & 63);
+                }
                 float4 ro = make_float4(0.f, 0.f, 0.f, __uint_as_float(WF_INVALID)), rd = ro;
                 const bool go = wf_generate_one(kt->a, kt->w, lds_cam, id, new_base + (unsigned)k, ro, rd);  // pixels outside the image leave skip markers
                 rq_w[2 * k] = ro;  // (plain stores, like every ray record: see st_stream)
@@ -2563,7 +2581,7 @@ __global__ __launch_bounds__(kBlockThreads, GLRTX_WGWF_WAVES) void pt_render_wgw
         // waves in the (memory-latency-bound) traverse phase issue ahead of waves of other workgroups that are shading:
         // their loads get going earlier (measured 1-2 %)
         __builtin_amdgcn_s_setprio(GLRTX_PRIO_TRAVERSE);
-        wg_traverse_phase<VINE, FETCH>(a, w, lds_root, stack, rq, n_rays, &ctl[1], light_bits, rays, rayQ + kWgSuspendAt);
+        wg_traverse_phase<VINE, FETCH & ~kWgwfAdaptive>(a, w, lds_root, stack, rq, n_rays, &ctl[1], light_bits, rays, rayQ + kWgSuspendAt);
         __builtin_amdgcn_s_setprio(GLRTX_PRIO_SHADE);
         PH_STAMP(pt1);
         __syncthreads();  // all hit records of this trip written
@@ -2703,6 +2721,93 @@ __global__ __launch_bounds__(256) void accumulate_feed_kernel(float4 *accum, int
         }
     }
     accum[at] = acc;
+}
+
+// ------------------------------------------------------------------------------------------ adaptive sampling (glrtx_render_adaptive)
+// The selection at the start of an adaptive call: which 8x8 tiles of the owned rows (the wavefront kernel's tiles, tiles8_x x tiles8_y, partial at the right and
+// bottom edges) are still ACTIVE.  Per pixel, the two-buffer error of Dammertz et al. between the accumulator (I = acc.rgb / acc.w) and the half buffer H (every
+// second sample, A = H.rgb / H.w):
+//     d = (|I.r - A.r| + |I.g - A.g| + |I.b - A.b|) / sqrt(I.r + I.g + I.b + kAdaptLumFloor)
+// IEEE fp32, correctly rounded, unfused, denormals flushed (the library's build flags), in exactly that order of operations.  The tile error E is the mean over the
+// tile's in-image pixels: lane k of the tile's wave holds pixel (k & 7, k >> 3) of the tile (0 outside the image), the 64 values are summed as a tree --
+// s[k] = s[k] + s[k + h] for h = 32, 16, 8, 4, 2, 1 -- and divided by the number of in-image pixels.  A tile is active if a pixel has acc.w < min_samples or
+// H.w == 0, if E > threshold or E is NaN, or if threshold < 0.  tests/adaptive_math.py states the same bit for bit.
+constexpr float kAdaptLumFloor = 1e-3f;
+constexpr int kAdaptCompactThreads = 1024;  // adaptive_compact_kernel: one workgroup
+
+// One wave per tile, four tiles per workgroup.  Writes the tile's mask byte and -- debug export only -- its E (a NaN as the canonical quiet NaN).
+__global__ __launch_bounds__(256) void adaptive_select_kernel(const float4 *accum, const float4 *half, int pitch_f4, int width, int rows, int tiles8_x, int n_tiles,
+                                                              float threshold, int min_samples, unsigned char *mask, float *tile_err) {
+    const int tile = blockIdx.x * 4 + (threadIdx.x >> 6), k = threadIdx.x & 63;
+    if (tile >= n_tiles) return;  // (wave-uniform)
+    const int x = (tile % tiles8_x) * 8 + (k & 7), y = (tile / tiles8_x) * 8 + (k >> 3);
+    const bool in = x < width && y < rows;
+    float d = 0.0f;
+    bool force = false;
+    if (in) {
+        const size_t at = (size_t)y * pitch_f4 + x;
+        const float4 c = ld_stream(&accum[at]), h = ld_stream(&half[at]);
+        force = c.w < (float)min_samples || h.w == 0.0f;
+        const float ir = c.x / c.w, ig = c.y / c.w, ib = c.z / c.w;
+        const float ar = h.x / h.w, ag = h.y / h.w, ab = h.z / h.w;
+        const float num = (__builtin_fabsf(ir - ar) + __builtin_fabsf(ig - ag)) + __builtin_fabsf(ib - ab);
+        d = num / __builtin_sqrtf(((ir + ig) + ib) + kAdaptLumFloor);
+    }
+#pragma unroll
+    for (int h = 32; h >= 1; h >>= 1) d = d + __shfl_xor(d, h, 64);  // (lane k adds lane k ^ h: lane 0 ends with the tree sum above; addition commutes)
+    const unsigned long long in_mask = __ballot(in), force_mask = __ballot(force);
+    if (k == 0) {
+        const float e = d / (float)__popcll(in_mask);
+        mask[tile] = (force_mask != 0ull || threshold < 0.0f || !(e <= threshold)) ? 1 : 0;
+        if (tile_err) tile_err[tile] = e != e ? __uint_as_float(0x7FC00000u) : e;
+    }
+}
+
+// The ascending list of active tiles and their count, by one workgroup: thread i counts the mask bytes of its chunk of consecutive tiles, an exclusive scan over the
+// threads in LDS gives every chunk its first list position, and the threads write their tiles in order.  No atomics: the list is the same on every run.
+__global__ __launch_bounds__(kAdaptCompactThreads) void adaptive_compact_kernel(const unsigned char *mask, int n_tiles, int *list, unsigned *count) {
+    __shared__ int part[kAdaptCompactThreads];
+    const int i = threadIdx.x;
+    const int chunk = (n_tiles + kAdaptCompactThreads - 1) / kAdaptCompactThreads;
+    const int t0 = min(i * chunk, n_tiles), t1 = min(t0 + chunk, n_tiles);
+    int n = 0;
+    for (int t = t0; t < t1; t++) n += mask[t] != 0;
+    part[i] = n;
+    __syncthreads();
+    for (int off = 1; off < kAdaptCompactThreads; off <<= 1) {  // inclusive scan (Hillis-Steele)
+        const int v = i >= off ? part[i - off] : 0;
+        __syncthreads();
+        part[i] += v;
+        __syncthreads();
+    }
+    int at = part[i] - n;
+    for (int t = t0; t < t1; t++)
+        if (mask[t] != 0) list[at++] = t;
+    if (i == kAdaptCompactThreads - 1) *count = (unsigned)part[i];
+}
+
+// The accumulation pass of an adaptive launch: the sample planes (frame by frame, sample by sample, as accumulate_planes_kernel) of ACTIVE tiles only -- an inactive
+// tile's planes were not written and its accumulator and H entries are not touched.  A sample also goes into the half buffer H when the pixel's count before the add
+// is odd: H holds every second sample.
+__global__ __launch_bounds__(256) void accumulate_adaptive_kernel(float4 *accum, float4 *half, int pitch_f4, int width, int rows, const float4 *planes, int n_planes,
+                                                                  const unsigned char *mask, int tiles8_x) {
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= width || y >= rows) return;
+    if (mask[(y >> 3) * tiles8_x + (x >> 3)] == 0) return;
+    const size_t at = (size_t)y * pitch_f4 + x, plane = (size_t)rows * pitch_f4;
+    float4 acc = accum[at], h = half[at];
+    for (int k = 0; k < n_planes; k++) {
+        const float4 v = planes[(size_t)k * plane + at];
+        if (((unsigned)acc.w & 1u) != 0u) {
+            h.x = h.x + v.x; h.y = h.y + v.y; h.z = h.z + v.z;
+            h.w = h.w + 1.0f;
+        }
+        acc.x = acc.x + v.x; acc.y = acc.y + v.y; acc.z = acc.z + v.z;
+        acc.w = acc.w + 1.0f;
+    }
+    accum[at] = acc;
+    half[at] = h;
 }
 
 // ------------------------------------------------------------------------------------------ resolve

@@ -14,7 +14,7 @@
 using namespace glrt;
 
 static void usage(const char *exe) {
-    std::printf("usage: %s -i scene.json [-s N] [--max-depth D] [--spp N] [--frames F] [--frames-in-flight B] [--bvh sah|sah-reinsert|sah-gpu|lbvh|sah-levels-cpu|lbvh-cpu|reference] [--order-by-hits] [--out file.png] [--save-every-frame] [--device G | --gpus N | --devices a,b,..] [--extensions] [--whitted] [--enable-volume]\n"
+    std::printf("usage: %s -i scene.json [-s N] [--max-depth D] [--spp N] [--frames F] [--frames-in-flight B] [--bvh sah|sah-reinsert|sah-gpu|lbvh|sah-levels-cpu|lbvh-cpu|reference] [--order-by-hits] [--out file.png] [--save-every-frame] [--device G | --gpus N | --devices a,b,..] [--extensions] [--whitted] [--enable-volume] [--adaptive THRESHOLD [--min-spp N]]\n"
                 "  -i, --input             scene description (JSON; schema: SURVEY.md Appendix C)            [required]\n"
                 "  -s, --sample-per-cycle  accepted for compatibility; like the reference (main.cpp:13) it is not read\n"
                 "      --max-depth D       u_maxDepth (default 16, the reference shader's default)\n"
@@ -32,13 +32,18 @@ static void usage(const char *exe) {
                 "                          \"dielectric\" (ior, tint); parity with the reference is not defined for such scenes\n"
                 "      --whitted           with --extensions: Whitted-style transport (direct light at diffuse surfaces, specular bounces only)\n"
                 "      --enable-volume     render the participating media of \"media\" shapes: the reference's ENABLE_VOLUME switch (raytrace.frag:4);\n"
-                "                          their VOL files are read (a missing one is an error only with this flag)\n", exe);
+                "                          their VOL files are read (a missing one is an error only with this flag)\n"
+                "      --adaptive T        adaptive sampling: bursts of --frames-in-flight frames on the 8x8 tiles whose error is above T only, until no tile is\n"
+                "                          active or --frames frames have been issued; an \"Adaptive:\" line per burst (not with --save-every-frame)\n"
+                "      --min-spp N         with --adaptive: samples every pixel of a tile needs before the tile may retire (default 2, at least 2)\n", exe);
 }
 
 int main(int argc, char **argv) {
     std::string input, out = "output.png";
     int depth = 16, spp = 1, frames = 16, device = -1, in_flight = 0;
-    bool every_frame = false, extensions = false, whitted = false, order_by_hits = false, volume = false;
+    bool every_frame = false, extensions = false, whitted = false, order_by_hits = false, volume = false, adaptive = false, min_spp_given = false;
+    float adapt_threshold = 0.0f;
+    int min_spp = 2;
     std::vector<int> devices;
     std::string bvh;
     for (int i = 1; i < argc; i++) {
@@ -61,6 +66,8 @@ int main(int argc, char **argv) {
         else if (a == "--extensions") extensions = true;
         else if (a == "--whitted") { extensions = true; whitted = true; }
         else if (a == "--enable-volume") volume = true;
+        else if (a == "--adaptive") { adaptive = true; adapt_threshold = (float)std::atof(next("--adaptive")); }
+        else if (a == "--min-spp") { min_spp = std::atoi(next("--min-spp")); min_spp_given = true; }
         else if (a == "--gpus") { const int n = std::atoi(next("--gpus")); devices.clear(); for (int k = 0; k < n; k++) devices.push_back(k); }
         else if (a == "--devices") {
             devices.clear();
@@ -69,6 +76,8 @@ int main(int argc, char **argv) {
         else { usage(argv[0]); return 1; }
     }
     if (input.empty()) { usage(argv[0]); return 1; }
+    if (min_spp_given && !adaptive) { std::fprintf(stderr, "--min-spp needs --adaptive\n"); return 1; }
+    if (adaptive && (every_frame || min_spp < 2)) { std::fprintf(stderr, "--adaptive: not with --save-every-frame, and --min-spp must be at least 2\n"); return 1; }
 
     auto window = std::make_unique<Window>();
     if (devices.empty()) window->setDevice(device);
@@ -79,6 +88,7 @@ int main(int argc, char **argv) {
     if (in_flight > 0) window->setFramesInFlight(in_flight);
     window->setOutput(out, every_frame);
     window->setOrderChildrenByHits(order_by_hits);
+    if (adaptive) window->setAdaptive(adapt_threshold, min_spp);
 
     auto scene = std::make_shared<Scene>();
     if (!bvh.empty()) scene->setBvhBuilder(bvh);

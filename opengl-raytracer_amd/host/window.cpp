@@ -134,6 +134,28 @@ void Window::mainloop(const std::shared_ptr<Scene> &scene_, double fps) {
         GLRT_Info("Presented: %d frames, %d images, %llu render kernel launches", frameLimit_, images, (unsigned long long)st.kernel_launches);
         return;
     }
+    if (adaptive_) {
+        // Adaptive sampling: every burst re-selects the tiles that are still active (from the accumulator as it stands) and renders its frames on those only; the
+        // count the burst was issued on is reported after it.  A burst that found no active tile rendered nothing: the run ends there.
+        glrtx_params p;
+        frameParams(p);
+        const glrtx_adaptive cfg = {adaptThreshold_, adaptMinSamples_};
+        int issued = 0;
+        while (issued < frameLimit_) {
+            const int n = frameLimit_ - issued < framesInFlight_ ? frameLimit_ - issued : framesInFlight_;
+            std::vector<float> seeds(2 * (size_t)n);
+            for (int f = 0; f < n; f++) glrt_frame_seed(frame_++, &seeds[2 * (size_t)f]);
+            GLRTX_CHECK(glrtx_group_render_adaptive(grp_, &p, seeds.data(), n, &cfg));
+            issued += n;
+            int active = 0, total = 0;
+            GLRTX_CHECK(glrtx_group_adaptive_active_tiles(grp_, &active, &total));
+            GLRT_Info("Adaptive: frame %d, active tiles %d/%d", issued, active, total);
+            if (active == 0) break;
+        }
+        lastMs_ = issued > 0 ? std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() / issued : 0.0;
+        if (!output_.empty() && frameLimit_ > 0) saveCurrentFrame(output_, true);
+        return;
+    }
     int since = 0;
     for (int i = 0; i < frameLimit_; i += step) {
         const int n = frameLimit_ - i < step ? frameLimit_ - i : step;

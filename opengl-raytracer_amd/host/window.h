@@ -47,6 +47,9 @@ public:
     // Frames issued per launch of the render kernel (glrtx_render_frames; bit-identical to one launch per frame).
     // Used when no image is written between frames and render() is not overridden per frame; GLRT_FRAMES_IN_FLIGHT.
     void setFramesInFlight(int n) { framesInFlight_ = n < 1 ? 1 : n; }
+    // Adaptive sampling (no reference counterpart; glrtx_render_adaptive): bursts of framesInFlight frames, each on the 8x8 tiles that have not converged
+    // (error above threshold, or fewer than minSamples samples), until no tile is active or the frame limit is reached; one "Adaptive:" line per burst.
+    void setAdaptive(float threshold, int minSamples) { adaptive_ = true; adaptThreshold_ = threshold; adaptMinSamples_ = minSamples; }
     // wall-clock ms PER FRAME between the last two waits for the device, averaged over the frames issued in between (with one PNG per run: the whole run, cold first
     // launches included; with --save-every-frame: the whole run, PNG writing included).  The device's own time of the last launch is glrtx_stats.kernel_ms_last.
     double lastFrameMs() const { return lastMs_; }
@@ -76,6 +79,9 @@ private:
     unsigned frame_ = 0;
     bool saveEveryFrame_ = false;
     bool orderByHits_ = false;
+    bool adaptive_ = false;
+    float adaptThreshold_ = 0.0f;
+    int adaptMinSamples_ = 2;
     bool fallbackNoted_ = false;
     std::string output_ = "output.png";
     double lastMs_ = 0.0;

@@ -36,6 +36,11 @@ class Stats(C.Structure):
                 ("shadow_limited", C.c_int32), ("reserved2", C.c_int32), ("feed_launches", C.c_uint64), ("feed_appended", C.c_uint64)]
 
 
+class Adaptive(C.Structure):
+    """glrtx_adaptive: a tile retires once its error E <= threshold (threshold < 0: nothing retires) and every pixel has min_samples (>= 2) samples."""
+    _fields_ = [("threshold", C.c_float), ("min_samples", C.c_int32)]
+
+
 class Image(C.Structure):
     _fields_ = [("rgba", C.c_void_p), ("pitch_bytes", C.c_size_t), ("width", C.c_int32), ("rows", C.c_int32), ("frame", C.c_uint64)]
 
@@ -67,7 +72,9 @@ EXPORTS = ["glrtx_abi_version", "glrtx_create", "glrtx_destroy", "glrtx_last_err
            "glrtx_debug_resolve_burst", "glrtx_hit_histogram", "glrtx_group_sync", "glrtx_group_read_accum", "glrtx_group_resolve_rgba8", "glrtx_group_get_stats", "glrtx_group_gather_copies",
            "glrtx_present_enable", "glrtx_present_acquire", "glrtx_present_release", "glrtx_present_get_stats",
            "glrtx_group_present_enable", "glrtx_group_present_acquire", "glrtx_group_present_release", "glrtx_group_present_get_stats",
-           "glrtx_upload_volume", "glrtx_group_upload_volume", "glrtx_debug_volume_math", "glrtx_debug_volume_lookup"]
+           "glrtx_upload_volume", "glrtx_group_upload_volume", "glrtx_debug_volume_math", "glrtx_debug_volume_lookup",
+           "glrtx_render_adaptive", "glrtx_adaptive_active_tiles", "glrtx_read_tile_mask", "glrtx_read_adaptive_half", "glrtx_debug_adaptive_select",
+           "glrtx_group_render_adaptive", "glrtx_group_adaptive_active_tiles"]
 
 _lib = None
 
@@ -151,6 +158,14 @@ def lib():
         L.glrtx_group_present_acquire.argtypes = [vp, C.c_int, C.POINTER(Image)]
         L.glrtx_group_present_release.argtypes = [vp, C.POINTER(Image)]
         L.glrtx_group_present_get_stats.argtypes = [vp, C.POINTER(PresentStats)]
+        ip, u8p = C.POINTER(C.c_int), C.POINTER(C.c_uint8)
+        L.glrtx_render_adaptive.argtypes = [vp, C.POINTER(Params), fp, C.c_int, C.POINTER(Adaptive)]
+        L.glrtx_adaptive_active_tiles.argtypes = [vp, ip, ip]
+        L.glrtx_read_tile_mask.argtypes = [vp, u8p]
+        L.glrtx_read_adaptive_half.argtypes = [vp, vp, C.c_size_t]
+        L.glrtx_debug_adaptive_select.argtypes = [fp, fp, C.c_int, C.c_int, C.c_float, C.c_int, u8p, fp, ip, ip]
+        L.glrtx_group_render_adaptive.argtypes = [vp, C.POINTER(Params), fp, C.c_int, C.POINTER(Adaptive)]
+        L.glrtx_group_adaptive_active_tiles.argtypes = [vp, ip, ip]
         _lib = L
     return _lib
 
@@ -216,6 +231,32 @@ def volume_lookup(grid, bbox_min, bbox_max, pos):
     if rc != 0:
         raise GlrtxError(rc, L.glrtx_last_error(None).decode())
     return out
+
+
+def adaptive_select(accum, half, threshold, min_samples):
+    """glrtx_debug_adaptive_select on the current device: the selection kernels on accum / half (rows, width, 4) float32.
+    Returns (mask (tiles_y, tiles_x) uint8, E (tiles_y, tiles_x) float32 -- NaN as 0x7FC00000 --, ascending list of active tiles)."""
+    L = lib()
+    a, h = _f32(accum), _f32(half)
+    if a.ndim != 3 or a.shape[2] != 4 or h.shape != a.shape:
+        raise ValueError(f"adaptive_select: accum and half must be (rows, width, 4) of one shape, got {a.shape} and {h.shape}")
+    rows, width = a.shape[:2]
+    ty, tx = (rows + 7) // 8, (width + 7) // 8
+    mask = np.zeros((ty, tx), np.uint8)
+    err = np.zeros((ty, tx), np.float32)
+    lst = np.zeros(ty * tx, np.int32)
+    n = C.c_int(0)
+    rc = L.glrtx_debug_adaptive_select(_fp(a), _fp(h), width, rows, float(threshold), int(min_samples), mask.ctypes.data_as(C.POINTER(C.c_uint8)), _fp(err),
+                                       lst.ctypes.data_as(C.POINTER(C.c_int)), C.byref(n))
+    if rc != 0:
+        raise GlrtxError(rc, L.glrtx_last_error(None).decode())
+    return mask, err, lst[:n.value].copy()
+
+
+def _adaptive_args(params, seeds, threshold, min_samples):
+    p = params if isinstance(params, Params) else make_params(dict(params, seed=(0.0, 0.0)) if "seed" not in params else params)
+    sd = _f32(np.asarray(seeds, np.float32).reshape(-1, 2))
+    return p, sd, Adaptive(float(threshold), int(min_samples))
 
 
 class Device:
@@ -375,6 +416,27 @@ class Device:
         self._ck(self.L.glrtx_present_get_stats(self.h, C.byref(s)))
         return s
 
+    def render_adaptive(self, params, seeds, threshold, min_samples=2):
+        """Adaptive sampling (glrtx_render_adaptive): select the active 8x8 tiles, then render len(seeds) frames of those tiles only.  threshold < 0: nothing retires."""
+        p, sd, cfg = _adaptive_args(params, seeds, threshold, min_samples)
+        self._ck(self.L.glrtx_render_adaptive(self.h, C.byref(p), _fp(sd), sd.shape[0], C.byref(cfg)))
+    def adaptive_active_tiles(self):
+        """(active, total) tiles of the last selection (syncs)."""
+        a, t = C.c_int(0), C.c_int(0)
+        self._ck(self.L.glrtx_adaptive_active_tiles(self.h, C.byref(a), C.byref(t)))
+        return int(a.value), int(t.value)
+    def tile_mask(self) -> np.ndarray:
+        """The last selection's mask, (tiles_y, tiles_x) uint8 over the owned rows (syncs)."""
+        s = self.stats()
+        out = np.zeros(((s.owned_rows + 7) // 8, (s.width + 7) // 8), np.uint8)
+        self._ck(self.L.glrtx_read_tile_mask(self.h, out.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return out
+    def read_adaptive_half(self) -> np.ndarray:
+        """The half buffer H (every second sample), (owned_rows, width, 4) float32 like read_accum."""
+        s = self.stats()
+        out = np.zeros((s.owned_rows, s.width, 4), np.float32)
+        self._ck(self.L.glrtx_read_adaptive_half(self.h, out.ctypes.data, s.width * 16))
+        return out
     def timer_begin(self):
         self._ck(self.L.glrtx_timer_begin(self.h))
 
@@ -449,6 +511,31 @@ class Group:
 
     def sync(self):
         self._ck(self.L.glrtx_group_sync(self.h))
+    def render_adaptive(self, params, seeds, threshold, min_samples=2):
+        """Device.render_adaptive on every member, each selecting on its own accumulator (glrtx_group_render_adaptive)."""
+        p, sd, cfg = _adaptive_args(params, seeds, threshold, min_samples)
+        self._ck(self.L.glrtx_group_render_adaptive(self.h, C.byref(p), _fp(sd), sd.shape[0], C.byref(cfg)))
+    def adaptive_active_tiles(self):
+        """(active, total) tiles of the last selection, summed over the members (syncs)."""
+        a, t = C.c_int(0), C.c_int(0)
+        self._ck(self.L.glrtx_group_adaptive_active_tiles(self.h, C.byref(a), C.byref(t)))
+        return int(a.value), int(t.value)
+    def _member_array(self, i, shape, dtype, fn, *args):
+        m = self.L.glrtx_group_ctx(self.h, i)
+        s = Stats()
+        self.L.glrtx_get_stats(m, C.byref(s))
+        out = np.zeros(shape(s), dtype)
+        rc = fn(m, out.ctypes.data_as(C.POINTER(C.c_uint8)) if dtype == np.uint8 else out.ctypes.data, *[a(s) for a in args])
+        if rc != 0:
+            raise GlrtxError(rc, self.L.glrtx_last_error(m).decode())
+        return out
+    def tile_mask(self):
+        """Each member's last selection mask (its own owned-row tiles): a list of (tiles_y, tiles_x) uint8."""
+        return [self._member_array(i, lambda s: ((s.owned_rows + 7) // 8, (s.width + 7) // 8), np.uint8, self.L.glrtx_read_tile_mask) for i in range(self.size())]
+    def read_adaptive_half(self):
+        """Each member's half buffer: a list of (owned_rows, width, 4) float32."""
+        return [self._member_array(i, lambda s: (s.owned_rows, s.width, 4), np.float32, self.L.glrtx_read_adaptive_half, lambda s: s.width * 16)
+                for i in range(self.size())]
 
     def stats(self) -> Stats:
         s = Stats()
