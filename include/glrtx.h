@@ -114,7 +114,9 @@ typedef struct glrtx_stats {
     /* ABI 10 */
     int32_t shadow_limited;     /* which shadow-ray search the context's launches run: 0 the reference's own closest-hit search (default: bit-exact contract), 1 the
                                    range-limited one (glrtx_set_shadow_range_limit / GLRTX_SHADOW_LIMIT=1: outside the bit-exact contract).  bench.py prints it */
-    int32_t reserved2;
+    int32_t node_layout_last;   /* (was reserved2) wavefront kernel, last launch: 1 = the compact node array (48-byte records at breadth-first positions, three loads per step,
+                                   the children located through a rank table in LDS), 0 = the 64-byte records.  The compact layout serves node_fetch_last 0 when its rank table fits
+                                   in LDS with four workgroups per CU; GLRTX_COMPACT_NODES=0/1 forces it.  Bit-identical either way */
     uint64_t feed_launches;     /* fed launches since reset_stats: launches that stayed open for the calls behind them (see glrtx_render) */
     uint64_t feed_appended;     /* frames of glrtx_render / glrtx_render_frames calls that a launch already running took by itself instead of a launch of their own */
 } glrtx_stats;
@@ -156,6 +158,15 @@ int glrtx_check_scene(const float *vert, size_t n_vert, const float *tri, size_t
 int glrtx_debug_pack_forks(const float *vert, size_t n_vert, const float *tri, size_t n_tri, const float *mat, size_t n_mat,
                            const float *light, size_t n_light, const float *bvh, size_t n_nodes, float *forks_out,
                            size_t capacity_forks, int *n_fork_out, int *root_ref_out, int *stack_entries_out);
+
+/* Host-only test hook (no device, no ctx): the compact node array the wavefront kernel walks when stats.node_layout_last is 1 -- 12 floats per position
+ * (fork {child L box min, child R box max.x} {child L box max, child R box max.y} {child R box min, child R box max.z}; leaf {v0, id} {v1 - v0, next} {v2 - v0, 0},
+ * id / next as int bit patterns: next is the position of the leaf chained behind this one, or INT32_MIN), the rank table (2 words per 32 positions: fork bits,
+ * forks at smaller positions; the fork of rank k has its children at positions 2k + 1 and 2k + 2, the root is position 0), and the 64-byte leaf records by id
+ * (16 floats each: {v0, material} {v1 - v0, next ref} {v2 - v0, -} {-}), so that a test can walk both layouts.  Any output may be NULL (counts only). */
+int glrtx_debug_pack_compact(const float *vert, size_t n_vert, const float *tri, size_t n_tri, const float *mat, size_t n_mat,
+                             const float *light, size_t n_light, const float *bvh, size_t n_nodes, float *records_out, size_t capacity_positions,
+                             int *n_positions_out, uint32_t *ranks_out, size_t capacity_words, float *leaves_out, size_t capacity_ids, int *n_ids_out);
 
 /* Linear BVH built on the device (30-bit Morton order, Karras hierarchy, bottom-up fit), returned in the wire format
  * glrtx_upload_scene takes: nodes_out = (2*n_tri-1)*9 floats, root = node 0.  Takes the place of the reference's CPU

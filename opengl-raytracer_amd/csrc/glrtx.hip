@@ -64,7 +64,7 @@ struct glrtx_ctx {
     hipEvent_t rs0 = nullptr, rs1 = nullptr;      // around the resolve kernel
     std::string err;
 
-    DevBuf forks, nrms, mats, lights, vine, accum_own, counter, rgba8, work;
+    DevBuf forks, cnodes, cranks, nrms, mats, lights, vine, accum_own, counter, rgba8, work;
     DevBuf spheres, sphereMat;  // extension kernel: analytic spheres
     int n_spheres = 0, ext_flags = 0;
     DevBuf volDensity, volTemp;  // volume kernel (GLRTX_EXT_VOLUME): the two grids of glrtx_upload_volume
@@ -288,7 +288,67 @@ struct Packed {
     int root_boxed = 0;   // the wire root is a fork: its own box (root_lo / root_hi) is tested before anything else
     int stack_need = 0;
     std::vector<int> leaf_tri;  // leaf record k (id k + 1) -> wire triangle
+    // The compact node array (pack_compact): 48-byte records at breadth-first positions, and the rank table that locates a fork's children
+    std::vector<float4> cnodes;  // 3 float4 per position
+    std::vector<uint2> cranks;   // per 32 positions {fork bits, forks in front of the group}
 };
+
+// The compact node array, beside the 64-byte one.  Positions are numbered breadth-first from the root fork (position 0); the
+// children of the fork of rank k -- k forks lie at smaller positions -- sit at positions 2k + 1 (left slot) and 2k + 2 (right slot), so a fork
+// record needs no child refs and is exactly its children's twelve box floats: three dwordx4 loads instead of four loads of 56 bytes.
+//   fork: {minL, maxR.x} {maxL, maxR.y} {minR, maxR.z}   (the step's registers: trav_asm.hip.h, GLRTX_TRAV_STEP_ASM_COMPACT)
+//   leaf: {v0, id} {v1 - v0, next} {v2 - v0, 0}          (id: the triangle id a hit carries; next: the position of the leaf chained behind it, or REF_FIN)
+// The same tree, boxes, triangle data and visiting order as the 64-byte array: a position holds the record the 64-byte ref held -- a fork, a leaf (the
+// first leaf of a chained leaf pair: the second one lives in a tail region behind the tree) or the never-hit record of an absent child.
+void pack_compact(Packed &P) {
+    P.cnodes.clear();
+    P.cranks.clear();
+    std::vector<int> ref;  // position -> ref in the 64-byte layout
+    ref.push_back(P.root_ref);
+    for (size_t q = 0; q < ref.size(); q++) {
+        const int r = ref[q];
+        if (r < 0) continue;
+        int l, rr;
+        std::memcpy(&l, &P.forks[4 * (size_t)r + 0].w, 4);
+        std::memcpy(&rr, &P.forks[4 * (size_t)r + 1].w, 4);
+        ref.push_back(l);   // 2k + 1
+        ref.push_back(rr);  // 2k + 2
+    }
+    const size_t n_main = ref.size();
+    std::vector<int> next_pos(n_main, REF_FIN);
+    for (size_t q = 0; q < ref.size(); q++) {  // chained leaves: the tail (the loop runs on over the entries it appends)
+        if (ref[q] >= 0) continue;
+        int nx;
+        std::memcpy(&nx, &P.tris[4 * (size_t)~ref[q] + 1].w, 4);
+        if (nx == REF_FIN) continue;
+        if (q >= next_pos.size()) next_pos.resize(q + 1, REF_FIN);
+        next_pos[q] = (int)ref.size();
+        ref.push_back(nx);
+    }
+    next_pos.resize(ref.size(), REF_FIN);
+    const size_t n = ref.size();
+    P.cnodes.assign(3 * n, make_float4(0.f, 0.f, 0.f, 0.f));
+    P.cranks.assign((n + 31) / 32, make_uint2(0u, 0u));
+    unsigned forks = 0;
+    for (size_t q = 0; q < n; q++) {
+        float4 *o = &P.cnodes[3 * q];
+        if (q % 32 == 0) P.cranks[q / 32].y = forks;
+        const int r = ref[q];
+        if (r >= 0) {
+            const float4 *f = &P.forks[4 * (size_t)r];
+            o[0] = make_float4(f[0].x, f[0].y, f[0].z, f[3].x);
+            o[1] = make_float4(f[1].x, f[1].y, f[1].z, f[3].y);
+            o[2] = make_float4(f[2].x, f[2].y, f[2].z, f[3].z);
+            P.cranks[q / 32].x |= 1u << (q % 32);
+            forks++;
+        } else {
+            const float4 *t = &P.tris[4 * (size_t)~r];
+            o[0] = make_float4(t[0].x, t[0].y, t[0].z, as_float(~r));
+            o[1] = make_float4(t[1].x, t[1].y, t[1].z, as_float(next_pos[q]));
+            o[2] = make_float4(t[2].x, t[2].y, t[2].z, 0.f);
+        }
+    }
+}
 
 int pack_scene(glrtx_ctx *c, std::string *err_out, Packed &P, const float *vert, size_t n_vert, const float *tri, size_t n_tri,
                const float *mat, size_t n_mat, const float *light, size_t n_light, const float *bvh, size_t n_nodes) {
@@ -574,6 +634,7 @@ int pack_scene(glrtx_ctx *c, std::string *err_out, Packed &P, const float *vert,
     P.root_ref = root_ref;
     P.stack_need = stack_need;
     P.leaf_tri.swap(leaf_tri);
+    pack_compact(P);
     return GLRTX_OK;
 }
 
@@ -883,9 +944,21 @@ int launch_wgwf(glrtx_ctx *c, const KernelArgs &a_in, const glrtx_params *p, con
     int fetch = vine ? 0 : ((size_t)c->n_fork + (size_t)c->st.n_tri >= (size_t)kPairFetchMinRecords ? 1 : 0);
     if (const char *v = std::getenv("GLRTX_PAIR_FETCH")) fetch = vine ? 0 : std::max(0, std::min(2, std::atoi(v)));
     c->st.node_fetch_last = fetch;
+    // The compact node array (pack_compact: 48-byte records, three loads per step instead of four) serves the one-record-per-lane fetch when its rank table fits in
+    // LDS beside everything else with GLRTX_WGWF_WAVES workgroups per CU still resident; GLRTX_COMPACT_NODES=0/1 overrides (1: as long as one workgroup fits).
+    const int lds_base = c->sc.lds_head_f4 * (int)sizeof(float4) + 2 * c->sc.stack_entries * kBlockThreads * (int)sizeof(int) +
+                         kWgCtlWords * (int)sizeof(unsigned) + 2 * (int)sizeof(float4) + kCamFloatsPadded * (int)sizeof(float) + kLdsSeeds * (int)sizeof(float2) +  // ctl | root box | camera block | seeds |
+                         kWgPathsMax / 8;  // light-test bits, one per path-queue position
+    const int lds_compact = lds_base + c->sc.n_crank * (int)sizeof(uint2);  // | rank table
+    bool compact = !vine && fetch == 0 && c->sc.n_crank > 0 && (size_t)lds_compact * GLRTX_WGWF_WAVES <= (size_t)160 * 1024;
+    if (const char *v = std::getenv("GLRTX_COMPACT_NODES")) compact = std::atoi(v) != 0 && !vine && fetch == 0 && c->sc.n_crank > 0 && lds_compact <= 160 * 1024;
+    c->st.node_layout_last = compact ? 1 : 0;
     const bool cr = c->count_rays;
     constexpr int A = kWgwfAdaptive;  // (the ADAPT forms of the same eight: glrtx_render_adaptive)
-    const Kernel kernel = adapt ? (vine ? (cr ? (Kernel)pt_render_wgwf<true, true, A> : (Kernel)pt_render_wgwf<false, true, A>)
+    constexpr int CP = kWgwfCompact;
+    const Kernel kernel = compact ? (adapt ? (cr ? (Kernel)pt_render_wgwf<true, false, CP | A> : (Kernel)pt_render_wgwf<false, false, CP | A>)
+                                           : (cr ? (Kernel)pt_render_wgwf<true, false, CP> : (Kernel)pt_render_wgwf<false, false, CP>))
+                        : adapt ? (vine ? (cr ? (Kernel)pt_render_wgwf<true, true, A> : (Kernel)pt_render_wgwf<false, true, A>)
                                    : fetch == 2 ? (cr ? (Kernel)pt_render_wgwf<true, false, 2 | A> : (Kernel)pt_render_wgwf<false, false, 2 | A>)
                                    : fetch == 1 ? (cr ? (Kernel)pt_render_wgwf<true, false, 1 | A> : (Kernel)pt_render_wgwf<false, false, 1 | A>)
                                                 : (cr ? (Kernel)pt_render_wgwf<true, false, A> : (Kernel)pt_render_wgwf<false, false, A>))
@@ -895,9 +968,7 @@ int launch_wgwf(glrtx_ctx *c, const KernelArgs &a_in, const glrtx_params *p, con
                                      : (cr ? (Kernel)pt_render_wgwf<true, false, 0> : (Kernel)pt_render_wgwf<false, false, 0>);
     // (north_star's "primitives staged into LDS": materials, camera block, root box and the per-lane stacks are; the top tree levels were built, measured worth
     // nothing -- profiles/r02_lds_top.json -- and removed.)
-    const int lds = c->sc.lds_head_f4 * (int)sizeof(float4) + 2 * c->sc.stack_entries * kBlockThreads * (int)sizeof(int) +
-                    kWgCtlWords * (int)sizeof(unsigned) + 2 * (int)sizeof(float4) + kCamFloatsPadded * (int)sizeof(float) + kLdsSeeds * (int)sizeof(float2) +  // ctl | root box | camera block | seeds |
-                    kWgPathsMax / 8;  // light-test bits, one per path-queue position
+    const int lds = compact ? lds_compact : lds_base;
     if (lds > 160 * 1024) return fail(c, GLRTX_EDEVICE, "wgwf kernel needs %d B of LDS (> 160 KiB)", lds);
     if (lds > 64 * 1024) HIP_TRY(c, hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     int per_cu = 0;
@@ -1327,7 +1398,7 @@ void glrtx_destroy(glrtx_ctx *c) {
         for (auto &ch : sl.chunks) dev_free(ch);
         if (sl.feed_h) (void)hipHostFree(sl.feed_h);
     }
-    dev_free(c->spheres); dev_free(c->sphereMat); dev_free(c->volDensity); dev_free(c->volTemp); dev_free(c->forks); dev_free(c->nrms); dev_free(c->mats); dev_free(c->lights); dev_free(c->vine);
+    dev_free(c->spheres); dev_free(c->sphereMat); dev_free(c->volDensity); dev_free(c->volTemp); dev_free(c->forks); dev_free(c->cnodes); dev_free(c->cranks); dev_free(c->nrms); dev_free(c->mats); dev_free(c->lights); dev_free(c->vine);
     dev_free(c->accum_own); dev_free(c->counter); dev_free(c->rgba8); dev_free(c->work);
     dev_free(c->adHalf); dev_free(c->adMask); dev_free(c->adList); dev_free(c->adCount);
     dev_free(c->wfState); dev_free(c->wfQ); dev_free(c->wfSeeds); dev_free(c->wfPlanes);
@@ -1369,6 +1440,8 @@ int glrtx_upload_scene(glrtx_ctx *c, const float *vert, size_t n_vert, const flo
     for (size_t id = 0; id < n_ids; id++) std::memcpy(&nodes[4 * (n_ids - 1 - id)], &tris[4 * id], 4 * sizeof(float4));
     std::memcpy(nodes.data() + tri_f4, forks.data(), forks.size() * sizeof(float4));
     if ((rc = dev_upload(c, c->forks, nodes.data(), nodes.size() * sizeof(float4)))) return rc;
+    if ((rc = dev_upload(c, c->cnodes, P.cnodes.data(), P.cnodes.size() * sizeof(float4)))) return rc;
+    if ((rc = dev_upload(c, c->cranks, P.cranks.data(), P.cranks.size() * sizeof(uint2)))) return rc;
     if ((rc = dev_upload(c, c->nrms, nrms.data(), nrms.size() * sizeof(float4)))) return rc;
     if ((rc = dev_upload(c, c->mats, mats.data(), mats.size() * sizeof(float4)))) return rc;
     if ((rc = dev_upload(c, c->lights, lights.data(), lights.size() * sizeof(float4)))) return rc;
@@ -1378,6 +1451,9 @@ int glrtx_upload_scene(glrtx_ctx *c, const float *vert, size_t n_vert, const flo
     sc.forks = (const float4 *)c->forks.p + tri_f4;
     sc.nodes0 = (const float4 *)c->forks.p;
     sc.node_bias = (unsigned)(tri_f4 * sizeof(float4));
+    sc.cnodes = (const float4 *)c->cnodes.p;
+    sc.cranks = (const uint2 *)c->cranks.p;
+    sc.n_crank = (int)P.cranks.size();
     sc.nrms = (const float4 *)c->nrms.p;
     sc.mats = (const float4 *)c->mats.p;
     sc.lights = (const float4 *)c->lights.p;
@@ -1435,6 +1511,23 @@ int glrtx_debug_pack_forks(const float *vert, size_t n_vert, const float *tri, s
         if (capacity_forks < nf) return pfail(nullptr, &g_create_error, GLRTX_EINVAL, "glrtx_debug_pack_forks: %zu forks, room for %zu", nf, capacity_forks);
         std::memcpy(forks_out, P.forks.data(), nf * 16 * sizeof(float));
     }
+    return GLRTX_OK;
+}
+
+// Host-only: the compact node array, its rank table and the 64-byte leaf records (include/glrtx.h), for tests that walk both layouts.
+int glrtx_debug_pack_compact(const float *vert, size_t n_vert, const float *tri, size_t n_tri, const float *mat, size_t n_mat, const float *light,
+                             size_t n_light, const float *bvh, size_t n_nodes, float *records_out, size_t capacity_positions, int *n_positions_out,
+                             uint32_t *ranks_out, size_t capacity_words, float *leaves_out, size_t capacity_ids, int *n_ids_out) {
+    Packed P;
+    if (int rc = pack_scene(nullptr, &g_create_error, P, vert, n_vert, tri, n_tri, mat, n_mat, light, n_light, bvh, n_nodes)) return rc;
+    const size_t np = P.cnodes.size() / 3, nw = 2 * P.cranks.size(), ni = P.tris.size() / 4;
+    if (n_positions_out) *n_positions_out = (int)np;
+    if (n_ids_out) *n_ids_out = (int)ni;
+    if ((records_out && capacity_positions < np) || (ranks_out && capacity_words < nw) || (leaves_out && capacity_ids < ni))
+        return pfail(nullptr, &g_create_error, GLRTX_EINVAL, "glrtx_debug_pack_compact: %zu positions, %zu rank words, %zu leaf ids: an output is too small", np, nw, ni);
+    if (records_out) std::memcpy(records_out, P.cnodes.data(), np * 12 * sizeof(float));
+    if (ranks_out) std::memcpy(ranks_out, P.cranks.data(), nw * sizeof(uint32_t));
+    if (leaves_out) std::memcpy(leaves_out, P.tris.data(), ni * 16 * sizeof(float));
     return GLRTX_OK;
 }
 

@@ -59,6 +59,10 @@ struct DevScene {
                           // signed record index and the traversal step needs no base-pointer select
     const float4 *nodes0; // first byte of that array (the all-zero record ~n_tri); record ref lies at byte ref * 64 + node_bias from
     unsigned node_bias;   // here: an unsigned 32-bit offset from a uniform base, which the load instructions take as they are
+    const float4 *cnodes; // the compact node array (glrtx.hip: pack_compact): 48-byte records {minL, maxR.x} {maxL, maxR.y} {minR, maxR.z} / {v0, id} {e1, next} {e2, 0}
+                          // at breadth-first positions; the children of the fork of rank k at positions 2k + 1, 2k + 2; the root at position 0
+    const uint2 *cranks;  // its rank table: per 32 positions {fork bits, forks at smaller positions}; staged into LDS by the kernels that walk cnodes
+    int n_crank;          // words of the rank table
     const float4 *nrms;
     const float4 *mats;
     const float4 *lights;
@@ -440,8 +444,11 @@ DEV bool trav_init(const DevScene &sc, const float4 *root, Trav &T, float ox, fl
 // What that experiment did find: written as below, every lane fetches its whole 56-byte record with FOUR load instructions
 // (dwordx4, dwordx4, dwordx3, dwordx3) issued together; the previous form -- three loads for all lanes, then one more and the
 // two refs as single dwords on the fork arm, six instructions -- was 8 % slower per frame for fewer bytes.
-template <bool CLOSEST>
-DEV bool trav_step(const DevScene &sc, int *stack, Trav &T) {
+// COMPACT: the same step on the compact node array (DevScene::cnodes; ranks: its rank table in LDS) -- the C++ statement of GLRTX_TRAV_STEP_ASM_COMPACT
+// (trav_asm.hip.h).  A ref is then a position: "is a fork" is its bit in the rank table, its children are at positions 2 rank + 1 and 2 rank + 2, and the
+// three 16-byte pieces of the record carry the right child's far corner in their spare words.  Same boxes, same triangles, same order.
+template <bool CLOSEST, bool COMPACT = false>
+DEV bool trav_step(const DevScene &sc, int *stack, Trav &T, const uint2 *ranks = nullptr) {
 #ifdef GLRTX_TRAV_STATS
     trav_stats_iter(T.cur, (const void *)(sc.forks + 4 * (ptrdiff_t)T.cur), T.stop_d == -__builtin_inff(), T.sp);
     T.iters++;
@@ -459,21 +466,36 @@ DEV bool trav_step(const DevScene &sc, int *stack, Trav &T) {
     // Fork and triangle records have the same 64-byte shape and are fetched by the SAME four loads, issued
     // before the wave splits into its fork lanes and its triangle lanes: in a mixed wave (3 of 4 iterations)
     // the two arms then cost one memory round trip, not two.
-    const bool is_fork = cur >= 0;
-    const float4 *N = reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(sc.nodes0) + ((unsigned)cur * 64u + sc.node_bias));
+    uint2 rw = make_uint2(0u, 0u);
+    if constexpr (COMPACT) rw = ranks[(unsigned)cur >> 5];
+    const bool is_fork = COMPACT ? ((rw.x >> ((unsigned)cur & 31u)) & 1u) != 0u : cur >= 0;
+    const float4 *N = COMPACT ? sc.cnodes + 3 * (size_t)(unsigned)cur
+                              : reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(sc.nodes0) + ((unsigned)cur * 64u + sc.node_bias));
     // Every lane fetches its whole record here -- dwordx4, dwordx4, dwordx3, dwordx3: FOUR load instructions issued together (the
     // compiler drops the unused C.w / D.w).  The vector-memory pipe charges per instruction and per distinct cache line, not per
     // byte: fetching the fork arm's second box and refs separately (six instructions, 20 bytes less for a triangle lane) was 8 %
     // slower per frame (profiles/r02_lds_top.json, r02_ubench_gather.json).
-    float4 A = N[0], B = N[1], C = N[2], D = N[3];
-    // Pin the fork-only words (the two refs, the second child's far corner) here, in front of the arms: without it the compiler
-    // sinks their loads into the fork arm and the fetch becomes six instructions instead of four (8 % slower per frame).
-    asm volatile("" : "+v"(A.w), "+v"(B.w), "+v"(D.x), "+v"(D.y), "+v"(D.z));
+    float4 A, B, C, D;
+    if constexpr (COMPACT) {  // three dwordx4: {minL, maxR.x} {maxL, maxR.y} {minR, maxR.z}, or {v0, id} {e1, next} {e2, 0}
+        A = N[0]; B = N[1]; C = N[2];
+        asm volatile("" : "+v"(A.w), "+v"(B.w), "+v"(C.w));
+        D = make_float4(A.w, B.w, C.w, 0.f);
+    } else {
+        A = N[0]; B = N[1]; C = N[2]; D = N[3];
+        // Pin the fork-only words (the two refs, the second child's far corner) here, in front of the arms: without it the compiler
+        // sinks their loads into the fork arm and the fetch becomes six instructions instead of four (8 % slower per frame).
+        asm volatile("" : "+v"(A.w), "+v"(B.w), "+v"(D.x), "+v"(D.y), "+v"(D.z));
+    }
     // Two separate ifs, fork arm first: its extra loads (second box, refs) must go out BEFORE the triangle arithmetic of the
     // wave's leaf lanes.  (As one if / else the compiler may place the leaf arm first -- it did once the address select was
     // gone -- and the fork lanes then wait a second round trip behind it: 5 % of the frame.)
     if (is_fork) {
-        const int l = __float_as_int(A.w), r = __float_as_int(B.w);
+        int l = __float_as_int(A.w), r = __float_as_int(B.w);
+        if constexpr (COMPACT) {
+            const unsigned rank = rw.y + (unsigned)__popc(rw.x & ((1u << ((unsigned)cur & 31u)) - 1u));
+            l = (int)(2u * rank + 1u);
+            r = l + 1;
+        }
         float t0l, t0r;
         const bool bl = box_pass(A, B, T.ox, T.oy, T.oz, T.ix, T.iy, T.iz, T.h.t, t0l);
         const bool br = box_pass(C, D, T.ox, T.oy, T.oz, T.ix, T.iy, T.iz, T.h.t, t0r);
@@ -490,7 +512,7 @@ DEV bool trav_step(const DevScene &sc, int *stack, Trav &T) {
     }
     if (!is_fork) {
         // leaf :310-331 with intersect(Ray, Triangle) :226-257; A = {v0, material}, B = v1-v0, C = v2-v0
-        const int t = ~cur;
+        const int t = COMPACT ? __float_as_int(A.w) : ~cur;
         const float tx = T.ox - A.x, ty = T.oy - A.y, tz = T.oz - A.z;
         const float px = T.dy * C.z - T.dz * C.y;
         const float py = T.dz * C.x - T.dx * C.z;
@@ -575,9 +597,11 @@ struct StepTiming { unsigned t = 0, w = 0, n = 0; };
 #define GLRTX_TS_OPERANDS
 #define GLRTX_TS_CLOBBERS
 #endif
-// FETCH: 0 one record per lane, 1 pair-cooperative, 2 the two forms in alternate steps (pair first) -- see trav_asm.hip.h and launch_wgwf (glrtx.hip)
+// FETCH: 0 one record per lane, 1 pair-cooperative, 2 the two forms in alternate steps (pair first) -- see trav_asm.hip.h and launch_wgwf (glrtx.hip);
+// kWgwfCompact | 0: one record per lane from the compact node array (DevScene::cnodes, 48-byte records; rk: the LDS byte address of its rank table)
+constexpr int kWgwfCompact = 8;
 template <int FETCH>
-DEV void trav_steps_asm(const DevScene &sc, int *stack, Trav &T GLRTX_TS_PARAM) {
+DEV void trav_steps_asm(const DevScene &sc, int *stack, Trav &T, unsigned rk GLRTX_TS_PARAM) {
     unsigned long long s_entry, s_act, s_leaf, s_bl, s_br, s_pop, s_tmp;
     const unsigned stk = (unsigned)(uintptr_t)stack;
     static_assert(kBlockThreads * 8 == 1 << 11, "trav_asm.hip.h shifts the stack index by 11: entry e of lane l at byte (e * kBlockThreads + l) * 8");
@@ -585,6 +609,23 @@ DEV void trav_steps_asm(const DevScene &sc, int *stack, Trav &T GLRTX_TS_PARAM) 
     // pair-cooperative fetch: which 16-byte pieces a lane reads of the even lane's record (0 and 2, odd lanes 1 and 3) and of the odd lane's (1 and 3, odd lanes 0 and 2)
     const unsigned par16 = (threadIdx.x & 1u) << 4;
     const unsigned bias_e = sc.node_bias + par16, bias_o = sc.node_bias + 16u - par16;
+    if constexpr ((FETCH & kWgwfCompact) != 0) {
+        static_assert((FETCH & ~kWgwfCompact) == 0, "the compact layout has the one-record-per-lane fetch only");
+        asm volatile(
+            "s_mov_b64 %[entry], exec\n\t"
+            "s_mov_b64 %[act], exec\n\t"
+            GLRTX_ASM_SET_VBASE
+            "v_bfrev_b32 v[GLRTX_VB+22], 1\n\t"
+            GLRTX_REP(GLRTX_STEPS_PER_TRIP, GLRTX_TRAV_STEP_ASM_COMPACT)
+            "99:\n\t"
+            "s_mov_b64 exec, %[entry]"
+            : [th] "+&v"(T.h.t), [tri] "+&v"(T.h.tri), [hu] "+&v"(T.h.u), [hv] "+&v"(T.h.v), [cur] "+&v"(T.cur), [sp] "+&v"(T.sp),
+              [entry] "=&s"(s_entry), [act] "=&s"(s_act), [leaf] "=&s"(s_leaf), [bl] "=&s"(s_bl), [br] "=&s"(s_br), [pop] "=&s"(s_pop), [tmp] "=&s"(s_tmp) GLRTX_TS_OPERANDS
+            : [ox] "v"(T.ox), [oy] "v"(T.oy), [oz] "v"(T.oz), [dx] "v"(T.dx), [dy] "v"(T.dy), [dz] "v"(T.dz), [ix] "v"(T.ix), [iy] "v"(T.iy), [iz] "v"(T.iz),
+              [sd] "v"(T.stop_d), [stk] "v"(stk), [cbase] "s"(sc.cnodes), [rk] "s"(rk), [eps] "s"(PT_EPS)
+            : "vcc", "scc", "memory", GLRTX_ASM_VCLOBBERS_COMPACT GLRTX_TS_CLOBBERS);
+        return;
+    }
     if (FETCH == 2) {  // pair, lane, pair, lane, ...: the pipe and the SIMDs take turns at being the busier unit (-1.3 % on the 10 k-triangle tree)
         asm volatile(
             "s_mov_b64 %[entry], exec\n\t"
@@ -2019,6 +2060,7 @@ template <bool VINE, int FETCH>
 DEV void wg_traverse_phase(const KernelArgs &a, const WfArgs &w, const float4 *root, int *stack, const float4 *rq, int n_rays,
                            unsigned *ray_head, unsigned *light_bits, unsigned long long &rays, float4 *suspend_area) {
     const int lane = threadIdx.x & 63;
+    const uint2 *ranks = reinterpret_cast<const uint2 *>(light_bits + kWgPathsMax / 32);  // the compact layout's rank table, staged behind the light-test bits (pt_render_wgwf)
     if (VINE) {  // list scan: every ray takes the same number of steps, so waves simply take 64 rays at a time
         for (;;) {
             int base = 0;
@@ -2149,7 +2191,7 @@ DEV void wg_traverse_phase(const KernelArgs &a, const WfArgs &w, const float4 *r
                         T.h.t = shadow ? shadow_limit(dist, a.sc.shadow_limited) : PT_INFTY; T.h.tri = -1; T.h.u = 0.f; T.h.v = 0.f;
                         T.stop_d = shadow ? dist : -__builtin_inff();
                         T.sp = 0;
-                        T.cur = a.sc.root_ref;
+                        T.cur = (FETCH & kWgwfCompact) ? 0 : a.sc.root_ref;  // (the compact array's root is position 0)
 #ifdef GLRTX_TRAV_STATS
                         T.iters = 0;
 #endif
@@ -2202,15 +2244,16 @@ DEV void wg_traverse_phase(const KernelArgs &a, const WfArgs &w, const float4 *r
 #endif
         if (active) {
 #if defined(GLRTX_TRAV_STATS) || defined(GLRTX_CXX_STEP)  // diagnostic / experiment builds: the C++ statement of the step
-            bool fin = trav_step<true>(a.sc, stack, T);
+            constexpr bool CP = (FETCH & kWgwfCompact) != 0;
+            bool fin = trav_step<true, CP>(a.sc, stack, T, ranks);
 #pragma unroll
             for (int k = 1; k < GLRTX_STEPS_PER_TRIP; k++)
-                if (!fin) fin = trav_step<true>(a.sc, stack, T);
+                if (!fin) fin = trav_step<true, CP>(a.sc, stack, T, ranks);
 #else
 #ifdef GLRTX_STEP_TIMING
-            trav_steps_asm<FETCH>(a.sc, stack, T, step_timing);
+            trav_steps_asm<FETCH>(a.sc, stack, T, (unsigned)(uintptr_t)ranks, step_timing);
 #else
-            trav_steps_asm<FETCH>(a.sc, stack, T);
+            trav_steps_asm<FETCH>(a.sc, stack, T, (unsigned)(uintptr_t)ranks);
 #endif
             const bool fin = T.cur == REF_FIN;
 #endif
@@ -2474,6 +2517,10 @@ __global__ __launch_bounds__(kBlockThreads, GLRTX_WGWF_WAVES) void pt_render_wgw
     float4 *rayQ = wg_queues + (size_t)blockIdx.x * kWgQueueF4;
     if (a.sc.mats_in_lds) stage_mats(a, lds_mats);
     stage_lights(a, lds_mats);
+    if (FETCH & kWgwfCompact) {  // the compact layout's rank table, last in LDS (launch_wgwf sizes it)
+        uint2 *lds_ranks = reinterpret_cast<uint2 *>(light_bits + kWgPathsMax / 32);
+        for (int i = threadIdx.x; i < a.sc.n_crank; i += kBlockThreads) lds_ranks[i] = a.sc.cranks[i];
+    }
 
     const int kWgPaths = w.block_paths;
     unsigned long long rays = 0;  // low half: reference rays, high half: those resolved without a traversal

@@ -59,9 +59,11 @@ static_assert(GLRTX_STEPS_PER_TRIP % 2 == 0, "the alternating form of the node f
 #if GLRTX_ASM_VBASE == 96
 #define GLRTX_ASM_VCLOBBERS "v96", "v97", "v98", "v99", "v100", "v101", "v102", "v103", "v104", "v105", "v106", "v107", "v108", "v109", "v110", "v111", "v112", "v113", "v114", "v115", "v116", "v117"
 #define GLRTX_ASM_VCLOBBERS_PAIR GLRTX_ASM_VCLOBBERS, "v118", "v119"
+#define GLRTX_ASM_VCLOBBERS_COMPACT GLRTX_ASM_VCLOBBERS_PAIR
 #elif GLRTX_ASM_VBASE == 72
 #define GLRTX_ASM_VCLOBBERS "v72", "v73", "v74", "v75", "v76", "v77", "v78", "v79", "v80", "v81", "v82", "v83", "v84", "v85", "v86", "v87", "v88", "v89", "v90", "v91", "v92", "v93"
 #define GLRTX_ASM_VCLOBBERS_PAIR GLRTX_ASM_VCLOBBERS, "v94", "v95"
+#define GLRTX_ASM_VCLOBBERS_COMPACT GLRTX_ASM_VCLOBBERS_PAIR
 #else
 #error "GLRTX_ASM_VBASE: add the clobber list for this base"
 #endif
@@ -252,8 +254,93 @@ static_assert(GLRTX_STEPS_PER_TRIP % 2 == 0, "the alternating form of the node f
     "v_min_f32 v[GLRTX_VB+16], v[GLRTX_VB+16], %[th]\n\t"                                                                                                                  \
     "v_cmp_ge_f32_e64 %[br], v[GLRTX_VB+16], v[GLRTX_VB+8]\n\t"
 #define GLRTX_TRAV_STEP_ASM_LANE GLRTX_TS_BEGIN GLRTX_TRAV_LANE_LOADS GLRTX_TRAV_LANE_CLASSIFY GLRTX_TRAV_LANE_FORK GLRTX_TRAV_STEP_TAIL
+// The compact layout (glrtx.hip: pack_compact; selected by launch_wgwf with one record per lane): a 48-byte record at position cur, fetched with THREE
+// dwordx4 -- fork {minL, maxR.x} {maxL, maxR.y} {minR, maxR.z} into v[GLRTX_VB+0..11], leaf {v0, id} {e1, next} {e2, 0} into the registers the leaf arm reads
+// -- and the rank word of cur from LDS (%[rk]: the staged rank table, {fork bits, forks in front} per 32 positions), read beside the loads.  Its bit says fork
+// or leaf; a fork's children are positions 2 rank + 1 (left) and 2 rank + 2 (right), formed into v[GLRTX_VB+3] / v[GLRTX_VB+7] where the 64-byte record
+// carries its refs, once the right child's far corner has been read out of them.  The arms, the stack entries, the leaf chaining and the pop are the lane
+// form's.  REF_FIN lives in v[GLRTX_VB+22] (v[GLRTX_VB+11] is loaded), v[GLRTX_VB+19] holds the rank, v[GLRTX_VB+20:21] the rank word, v[GLRTX_VB+23]
+// its LDS address.
+#ifndef GLRTX_SINGLE_WAIT
+#define GLRTX_CW2 "s_waitcnt vmcnt(2)\n\t"
+#define GLRTX_CW1 "s_waitcnt vmcnt(1)\n\t"
+#define GLRTX_CW0 "s_waitcnt vmcnt(0)\n\t"
+#else
+#define GLRTX_CW2 "s_waitcnt vmcnt(0)\n\t"
+#define GLRTX_CW1
+#define GLRTX_CW0
+#endif
+#define GLRTX_TRAV_STEP_ASM_COMPACT \
+    GLRTX_TS_BEGIN \
+    "v_lshrrev_b32 v[GLRTX_VB+23], 5, %[cur]\n\t"                                   /* the rank word of cur: LDS byte (cur >> 5) * 8 + rk */ \
+    "v_lshl_add_u32 v[GLRTX_VB+23], v[GLRTX_VB+23], 3, %[rk]\n\t" \
+    "ds_read_b64 v[GLRTX_VB+20:GLRTX_VB+21], v[GLRTX_VB+23]\n\t" \
+    "v_mul_u32_u24 v[GLRTX_VB+15], 48, %[cur]\n\t"                                  /* 48-byte records (positions < 2^24: the rank table fits in LDS) */ \
+    "global_load_dwordx4 v[GLRTX_VB+0:GLRTX_VB+3], v[GLRTX_VB+15], %[cbase]\n\t" \
+    "global_load_dwordx4 v[GLRTX_VB+4:GLRTX_VB+7], v[GLRTX_VB+15], %[cbase] offset:16\n\t" \
+    "global_load_dwordx4 v[GLRTX_VB+8:GLRTX_VB+11], v[GLRTX_VB+15], %[cbase] offset:32\n\t" \
+    "s_waitcnt lgkmcnt(0)\n\t" \
+    "v_bfe_u32 v[GLRTX_VB+19], v[GLRTX_VB+20], %[cur], 1\n\t"                       /* cur's fork bit */ \
+    "v_cmp_eq_u32_e64 %[leaf], 0, v[GLRTX_VB+19]\n\t"                               /* lanes at a triangle */ \
+    "v_bfm_b32 v[GLRTX_VB+19], %[cur], 0\n\t"                                       /* the group's positions in front of cur ... */ \
+    "v_and_b32 v[GLRTX_VB+19], v[GLRTX_VB+19], v[GLRTX_VB+20]\n\t" \
+    "v_bcnt_u32_b32 v[GLRTX_VB+19], v[GLRTX_VB+19], v[GLRTX_VB+21]\n\t"             /* ... that are forks, plus the forks of the groups in front: the rank */ \
+    "s_andn2_b64 exec, exec, %[leaf]\n\t"                                           /* ---- fork arm: exec = lanes at a fork (may be none) */ \
+    GLRTX_TS_WAIT0 GLRTX_CW2 GLRTX_TS_WAIT1 \
+    "v_sub_f32 v[GLRTX_VB+0], v[GLRTX_VB+0], %[ox]\n\t"   /* left child: (lo - o) / d as soon as the first load is in, (hi - o) / d after the second */ \
+    "v_sub_f32 v[GLRTX_VB+1], v[GLRTX_VB+1], %[oy]\n\t" \
+    "v_sub_f32 v[GLRTX_VB+2], v[GLRTX_VB+2], %[oz]\n\t" \
+    "v_mul_f32 v[GLRTX_VB+0], v[GLRTX_VB+0], %[ix]\n\t" \
+    "v_mul_f32 v[GLRTX_VB+1], v[GLRTX_VB+1], %[iy]\n\t" \
+    "v_mul_f32 v[GLRTX_VB+2], v[GLRTX_VB+2], %[iz]\n\t" \
+    GLRTX_CW1 \
+    "v_sub_f32 v[GLRTX_VB+4], v[GLRTX_VB+4], %[ox]\n\t" \
+    "v_sub_f32 v[GLRTX_VB+5], v[GLRTX_VB+5], %[oy]\n\t" \
+    "v_sub_f32 v[GLRTX_VB+6], v[GLRTX_VB+6], %[oz]\n\t" \
+    "v_mul_f32 v[GLRTX_VB+4], v[GLRTX_VB+4], %[ix]\n\t" \
+    "v_mul_f32 v[GLRTX_VB+5], v[GLRTX_VB+5], %[iy]\n\t" \
+    "v_mul_f32 v[GLRTX_VB+6], v[GLRTX_VB+6], %[iz]\n\t" \
+    "v_max_f32 v[GLRTX_VB+16], v[GLRTX_VB+4], v[GLRTX_VB+0]\n\t" \
+    "v_min_f32 v[GLRTX_VB+0], v[GLRTX_VB+4], v[GLRTX_VB+0]\n\t" \
+    "v_max_f32 v[GLRTX_VB+17], v[GLRTX_VB+5], v[GLRTX_VB+1]\n\t" \
+    "v_min_f32 v[GLRTX_VB+1], v[GLRTX_VB+5], v[GLRTX_VB+1]\n\t" \
+    "v_max_f32 v[GLRTX_VB+18], v[GLRTX_VB+6], v[GLRTX_VB+2]\n\t" \
+    "v_min_f32 v[GLRTX_VB+4], v[GLRTX_VB+6], v[GLRTX_VB+2]\n\t" \
+    "v_min3_f32 v[GLRTX_VB+16], v[GLRTX_VB+16], v[GLRTX_VB+17], v[GLRTX_VB+18]\n\t"   /* t1 */ \
+    "v_max3_f32 v[GLRTX_VB+2], v[GLRTX_VB+0], v[GLRTX_VB+1], v[GLRTX_VB+4]\n\t"       /* t0 of the left child, next to where its position goes */ \
+    "v_min_f32 v[GLRTX_VB+16], v[GLRTX_VB+16], %[th]\n\t" \
+    "v_cmp_ge_f32_e64 %[bl], v[GLRTX_VB+16], v[GLRTX_VB+2]\n\t"                     /* min(t1, tHit) >= t0 */ \
+    GLRTX_CW0 \
+    "v_sub_f32 v[GLRTX_VB+8], v[GLRTX_VB+8], %[ox]\n\t"   /* right child: lo v[GLRTX_VB+8..10], hi from the spare words v[GLRTX_VB+3], v[GLRTX_VB+7], v[GLRTX_VB+11] into v[GLRTX_VB+12..14] */ \
+    "v_sub_f32 v[GLRTX_VB+9], v[GLRTX_VB+9], %[oy]\n\t" \
+    "v_sub_f32 v[GLRTX_VB+10], v[GLRTX_VB+10], %[oz]\n\t" \
+    "v_mul_f32 v[GLRTX_VB+8], v[GLRTX_VB+8], %[ix]\n\t" \
+    "v_mul_f32 v[GLRTX_VB+9], v[GLRTX_VB+9], %[iy]\n\t" \
+    "v_mul_f32 v[GLRTX_VB+10], v[GLRTX_VB+10], %[iz]\n\t" \
+    "v_sub_f32 v[GLRTX_VB+12], v[GLRTX_VB+3], %[ox]\n\t" \
+    "v_sub_f32 v[GLRTX_VB+13], v[GLRTX_VB+7], %[oy]\n\t" \
+    "v_sub_f32 v[GLRTX_VB+14], v[GLRTX_VB+11], %[oz]\n\t" \
+    "v_mul_f32 v[GLRTX_VB+12], v[GLRTX_VB+12], %[ix]\n\t" \
+    "v_mul_f32 v[GLRTX_VB+13], v[GLRTX_VB+13], %[iy]\n\t" \
+    "v_mul_f32 v[GLRTX_VB+14], v[GLRTX_VB+14], %[iz]\n\t" \
+    "v_max_f32 v[GLRTX_VB+16], v[GLRTX_VB+12], v[GLRTX_VB+8]\n\t" \
+    "v_min_f32 v[GLRTX_VB+8], v[GLRTX_VB+12], v[GLRTX_VB+8]\n\t" \
+    "v_max_f32 v[GLRTX_VB+17], v[GLRTX_VB+13], v[GLRTX_VB+9]\n\t" \
+    "v_min_f32 v[GLRTX_VB+9], v[GLRTX_VB+13], v[GLRTX_VB+9]\n\t" \
+    "v_max_f32 v[GLRTX_VB+18], v[GLRTX_VB+14], v[GLRTX_VB+10]\n\t" \
+    "v_min_f32 v[GLRTX_VB+10], v[GLRTX_VB+14], v[GLRTX_VB+10]\n\t" \
+    "v_min3_f32 v[GLRTX_VB+16], v[GLRTX_VB+16], v[GLRTX_VB+17], v[GLRTX_VB+18]\n\t" \
+    "v_max3_f32 v[GLRTX_VB+8], v[GLRTX_VB+8], v[GLRTX_VB+9], v[GLRTX_VB+10]\n\t" \
+    "v_min_f32 v[GLRTX_VB+16], v[GLRTX_VB+16], %[th]\n\t" \
+    "v_cmp_ge_f32_e64 %[br], v[GLRTX_VB+16], v[GLRTX_VB+8]\n\t" \
+    "v_lshl_add_u32 v[GLRTX_VB+3], v[GLRTX_VB+19], 1, 1\n\t"                        /* left child: position 2 rank + 1, next to its t0 */ \
+    "v_add_u32 v[GLRTX_VB+7], 1, v[GLRTX_VB+3]\n\t"                                 /* right child: 2 rank + 2 */ \
+    GLRTX_TRAV_STEP_TAIL_X("", "v[GLRTX_VB+22]")
 // (A step without the leaf arm in every other step -- the leaf arm on twice the lanes -- was built in round 5: bit-identical, +6.25 %, profiles/r05_lane_util.txt; removed.)
-#define GLRTX_TRAV_STEP_TAIL \
+// The leaf arm and the pop, shared by every form.  TRI: the instruction that puts the triangle id into v[GLRTX_VB+3] (the 64-byte layout derives it from the
+// ref; the compact record carries it there already); FIN: the register that holds REF_FIN.
+#define GLRTX_TRAV_STEP_TAIL GLRTX_TRAV_STEP_TAIL_X("v_not_b32 v[GLRTX_VB+3], %[cur]\n\t", "v[GLRTX_VB+11]")
+#define GLRTX_TRAV_STEP_TAIL_X(TRI, FIN) \
     "v_cndmask_b32_e64 %[cur], v[GLRTX_VB+3], v[GLRTX_VB+7], %[br]\n\t"                    /* go on with the right child if it passed, else with the left */              \
     "s_or_b64 %[tmp], %[bl], %[br]\n\t"                                                                                                                \
     "s_andn2_b64 %[pop], exec, %[tmp]\n\t"                              /* fork lanes with neither child: pop */                                       \
@@ -263,7 +350,7 @@ static_assert(GLRTX_STEPS_PER_TRIP % 2 == 0, "the alternating form of the node f
     "v_add_u32 %[sp], 1, %[sp]\n\t"                                                                                                                    \
     "s_and_b64 exec, %[act], %[leaf]\n\t"                               /* ---- leaf arm: A = {v0, material} v[GLRTX_VB+0]..99, B = v1 - v0 v[GLRTX_VB+4]..102, C = v2 - v0 v[GLRTX_VB+8]..106 */ \
     "s_cbranch_scc0 21f\n\t"                                                                                                                           \
-    "v_not_b32 v[GLRTX_VB+3], %[cur]\n\t"                                         /* triangle index */                                                           \
+    TRI                                                                           /* triangle index */                                                           \
     "v_mov_b32 %[cur], v[GLRTX_VB+7]\n\t"                                       /* the triangle chained behind this one (the other leaf of a leaf pair), or REF_FIN */            \
     "v_mul_f32 v[GLRTX_VB+16], %[dy], v[GLRTX_VB+10]\n\t"                                   /* p = d x e2 */                                                               \
     "v_mul_f32 v[GLRTX_VB+19], %[dz], v[GLRTX_VB+9]\n\t"                                                                                                                  \
@@ -331,8 +418,8 @@ static_assert(GLRTX_STEPS_PER_TRIP % 2 == 0, "the alternating form of the node f
     "s_and_b64 exec, %[act], %[leaf]\n\t"                               /* every leaf lane again */                                                    \
     "v_sub_f32 v[GLRTX_VB+16], %[sd], %[th]\n\t"                                  /* shadow ray: a known occluder ends the traversal */                          \
     "v_cmp_nle_f32 vcc, %[eps], v[GLRTX_VB+16]\n\t"                              /* !(stop_d - tHit >= EPS): the ray goes on */                                 \
-    "v_cndmask_b32 %[cur], v[GLRTX_VB+11], %[cur], vcc\n\t"                      /* ... with the chained triangle if there is one; a stopped ray is finished */ \
-    "v_cmp_eq_u32_e64 %[tmp], %[cur], v[GLRTX_VB+11]\n\t"                                                                                                       \
+    "v_cndmask_b32 %[cur], " FIN ", %[cur], vcc\n\t"                      /* ... with the chained triangle if there is one; a stopped ray is finished */ \
+    "v_cmp_eq_u32_e64 %[tmp], %[cur], " FIN "\n\t"                                                                                                       \
     "s_and_b64 vcc, vcc, %[tmp]\n\t"                                   /* goes on and has nothing chained: on to the stack */                         \
     "s_or_b64 %[pop], %[pop], vcc\n\t"                                                                                                                \
     "21:\n\t"                                                                                                                                          \
@@ -340,7 +427,7 @@ static_assert(GLRTX_STEPS_PER_TRIP % 2 == 0, "the alternating form of the node f
     "s_cbranch_execz 30f\n\t"                                                                                                                          \
     "10:\n\t"                                                                                                                                          \
     "v_cmp_ne_u32 vcc, 0, %[sp]\n\t"                                                                                                                   \
-    "v_cndmask_b32 %[cur], v[GLRTX_VB+11], %[cur], vcc\n\t"                       /* empty stack: the ray is finished */                                         \
+    "v_cndmask_b32 %[cur], " FIN ", %[cur], vcc\n\t"                       /* empty stack: the ray is finished */                                         \
     "s_and_b64 exec, exec, vcc\n\t"                                                                                                                    \
     "s_cbranch_execz 30f\n\t"                                                                                                                          \
     "v_add_u32 %[sp], -1, %[sp]\n\t"                                                                                                                   \
@@ -354,7 +441,7 @@ static_assert(GLRTX_STEPS_PER_TRIP % 2 == 0, "the alternating form of the node f
     "30:\n\t"                                                                                                                                          \
     "s_mov_b64 exec, %[act]\n\t"                                                                                  \
     GLRTX_TS_END                                                                                                                       \
-    "v_cmpx_ne_u32_e64 %[act], %[cur], v[GLRTX_VB+11]\n\t"                        /* the lanes that go on */                                                     \
+    "v_cmpx_ne_u32_e64 %[act], %[cur], " FIN "\n\t"                        /* the lanes that go on */                                                     \
     "s_cbranch_execz 99f\n\t"
 
 #define GLRTX_REP1(X) X

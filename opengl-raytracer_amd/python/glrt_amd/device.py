@@ -33,7 +33,7 @@ class Stats(C.Structure):
                 ("n_mat", C.c_int32), ("n_light", C.c_int32), ("variant_last", C.c_int32), ("fallback_last", C.c_int32),
                 ("resolve_ms_last", C.c_float), ("node_fetch_last", C.c_int32), ("fallback_launches", C.c_uint64),
                 ("pipe_slots", C.c_int32), ("pipe_resident_max", C.c_int32), ("device_error_pending", C.c_int32), ("wf_state_mib", C.c_int32),
-                ("shadow_limited", C.c_int32), ("reserved2", C.c_int32), ("feed_launches", C.c_uint64), ("feed_appended", C.c_uint64)]
+                ("shadow_limited", C.c_int32), ("node_layout_last", C.c_int32), ("feed_launches", C.c_uint64), ("feed_appended", C.c_uint64)]
 
 
 class Adaptive(C.Structure):
@@ -74,7 +74,7 @@ EXPORTS = ["glrtx_abi_version", "glrtx_create", "glrtx_destroy", "glrtx_last_err
            "glrtx_group_present_enable", "glrtx_group_present_acquire", "glrtx_group_present_release", "glrtx_group_present_get_stats",
            "glrtx_upload_volume", "glrtx_group_upload_volume", "glrtx_debug_volume_math", "glrtx_debug_volume_lookup",
            "glrtx_render_adaptive", "glrtx_adaptive_active_tiles", "glrtx_read_tile_mask", "glrtx_read_adaptive_half", "glrtx_debug_adaptive_select",
-           "glrtx_group_render_adaptive", "glrtx_group_adaptive_active_tiles"]
+           "glrtx_group_render_adaptive", "glrtx_group_adaptive_active_tiles", "glrtx_debug_pack_compact"]
 
 _lib = None
 
@@ -166,6 +166,8 @@ def lib():
         L.glrtx_debug_adaptive_select.argtypes = [fp, fp, C.c_int, C.c_int, C.c_float, C.c_int, u8p, fp, ip, ip]
         L.glrtx_group_render_adaptive.argtypes = [vp, C.POINTER(Params), fp, C.c_int, C.POINTER(Adaptive)]
         L.glrtx_group_adaptive_active_tiles.argtypes = [vp, ip, ip]
+        u32p = C.POINTER(C.c_uint32)
+        L.glrtx_debug_pack_compact.argtypes = [fp, C.c_size_t] * 5 + [fp, C.c_size_t, ip, u32p, C.c_size_t, fp, C.c_size_t, ip]
         _lib = L
     return _lib
 
@@ -251,6 +253,27 @@ def adaptive_select(accum, half, threshold, min_samples):
     if rc != 0:
         raise GlrtxError(rc, L.glrtx_last_error(None).decode())
     return mask, err, lst[:n.value].copy()
+
+
+def pack_compact(scene):
+    """glrtx_debug_pack_compact (host only, no device): (records (n, 12) float32, rank table (n_words / 2, 2) uint32, 64-byte leaf records by id (n_ids, 16) float32)."""
+    L = lib()
+    arrs = [_f32(scene[k]) for k in ("vert", "tri", "mat", "light", "bvh")]
+    args = []
+    for a, w in zip(arrs, (15, 4, 18, 4, 9)):
+        args += [_fp(a), a.size // w]
+    n_pos, n_ids = C.c_int(), C.c_int()
+    rc = L.glrtx_debug_pack_compact(*args, None, 0, C.byref(n_pos), None, 0, None, 0, C.byref(n_ids))
+    if rc != 0:
+        raise GlrtxError(rc, L.glrtx_last_error(None).decode())
+    recs = np.zeros((n_pos.value, 12), np.float32)
+    ranks = np.zeros(((n_pos.value + 31) // 32, 2), np.uint32)
+    leaves = np.zeros((n_ids.value, 16), np.float32)
+    rc = L.glrtx_debug_pack_compact(*args, _fp(recs), recs.shape[0], C.byref(n_pos), ranks.ctypes.data_as(C.POINTER(C.c_uint32)), ranks.size,
+                                    _fp(leaves), leaves.shape[0], C.byref(n_ids))
+    if rc != 0:
+        raise GlrtxError(rc, L.glrtx_last_error(None).decode())
+    return recs, ranks, leaves
 
 
 def _adaptive_args(params, seeds, threshold, min_samples):

@@ -160,7 +160,8 @@ def check_pop_loop(co: pathlib.Path, ks) -> list:
 
 def check_staged_waits(co: pathlib.Path, ks) -> list:
     """The hand-written traversal step of the wavefront kernel.  Behind every node fetch (two dwordx4 + two dwordx3 loads, in either order) the waits come in
-    stages -- pair-cooperative fetch (round 4): s_waitcnt vmcnt(2) then vmcnt(0); one record per lane (rounds 2-3): vmcnt(3), (2), (1), (0) -- with no other
+    stages -- pair-cooperative fetch (round 4): s_waitcnt vmcnt(2) then vmcnt(0); one record per lane (rounds 2-3): vmcnt(3), (2), (1), (0); the compact node array
+    (three dwordx4 behind the rank word's ds_read_b64): vmcnt(2), (1), (0) -- with no other
     vector-memory instruction in between (a load or store slipped into the sequence would make the counts wait for the wrong thing).  And the DPP moves of the
     pair exchange keep gfx950's manual hazards: a DPP source register is not written by the two instructions in front of it, and no v_cmpx (a vector write
     of exec) sits in the five instructions in front of a DPP instruction (the assembler inserts no wait states into inline asm)."""
@@ -188,15 +189,20 @@ def check_staged_waits(co: pathlib.Path, ks) -> list:
         ins = body.get(k["name"], [])
         fetches = 0
         for i, s in enumerate(ins):
-            if i < 3 or not all(t.startswith("global_load_dwordx") for t in ins[i - 3:i + 1]):
-                continue
-            widths = sorted(t.split()[0][-1] for t in ins[i - 3:i + 1])
-            if widths != ["3", "3", "4", "4"] or (i + 1 < len(ins) and ins[i + 1].startswith("global_load")):
+            compact = (i >= 4 and all(t.startswith("global_load_dwordx4") for t in ins[i - 2:i + 1]) and ins[i - 3].startswith("v_mul_u32_u24")
+                       and ins[i - 4].startswith("ds_read_b64"))  # the compact layout: the rank word, then three dwordx4 of one 48-byte record
+            if not compact:
+                if i < 3 or not all(t.startswith("global_load_dwordx") for t in ins[i - 3:i + 1]):
+                    continue
+                widths = sorted(t.split()[0][-1] for t in ins[i - 3:i + 1])
+                if widths != ["3", "3", "4", "4"]:
+                    continue
+            if i + 1 < len(ins) and ins[i + 1].startswith("global_load"):
                 continue
             fetches += 1
-            pair = ins[i - 2].startswith("global_load_dwordx4")  # x4, x4, x3, x3: pair-cooperative; x4, x4, x3, x3 with one address register: per lane
+            pair = not compact and ins[i - 2].startswith("global_load_dwordx4")  # x4, x4, x3, x3: pair-cooperative; x4, x4, x3, x3 with one address register: per lane
             pair = pair and len({t.split(",")[1].strip() for t in ins[i - 3:i + 1]}) == 2  # two address registers
-            stages = [2, 0] if pair else [3, 2, 1, 0]
+            stages = [2, 1, 0] if compact else [2, 0] if pair else [3, 2, 1, 0]
             for t in ins[i + 1:i + 120]:
                 if t.startswith(("global_", "buffer_", "flat_", "scratch_")):
                     problems.append(f"{k['pretty']}: `{t}` inside the staged waits of the node fetch at instruction {i}")
@@ -212,7 +218,7 @@ def check_staged_waits(co: pathlib.Path, ks) -> list:
             else:
                 problems.append(f"{k['pretty']}: node fetch at instruction {i}: the staged waits are incomplete")
         if fetches == 0:
-            problems.append(f"{k['pretty']}: no node fetch (2 x dwordx4 + 2 x dwordx3) found")
+            problems.append(f"{k['pretty']}: no node fetch (2 x dwordx4 + 2 x dwordx3, or 3 x dwordx4 for the compact layout) found")
         for i, s in enumerate(ins):
             if "quad_perm" not in s:
                 continue
