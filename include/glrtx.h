@@ -123,7 +123,7 @@ typedef struct glrtx_stats {
 
 /* glrtx_stats.fallback_last: the wavefront kernel packs depth and sample index into one word of its path state */
 #define GLRTX_FALLBACK_DEPTH 1      /* u_maxDepth > 255 */
-#define GLRTX_FALLBACK_SAMPLES 2    /* u_nSamples >= 2^20 */
+#define GLRTX_FALLBACK_SAMPLES 2    /* u_nSamples >= 2^20 (the volume on the wavefront kernel: >= 2^16) */
 #define GLRTX_FALLBACK_EXTENSIONS 4 /* analytic spheres uploaded or extension flags set (the extension kernel is a megakernel) */
 
 int glrtx_abi_version(void);
@@ -327,7 +327,8 @@ int glrtx_set_extensions(glrtx_ctx *ctx, int flags);
 
 /* ---- Participating media: the reference's volume branch (raytrace.frag:424-487, blackBody :125-142, lookups :144-152), which the
  * reference compiles out (ENABLE_VOLUME 0, raytrace.frag:4).  Off by default; GLRTX_EXT_VOLUME (glrtx_set_extensions) switches it on,
- * like the reference's define, and routes rendering to the persistent megakernel as the other extension flags do.  PINNED: the images
+ * like the reference's define, and routes rendering to the persistent megakernel as the other extension flags do (or, with
+ * glrtx_set_volume_wavefront, to the wavefront kernel).  PINNED: the images
  * are the reference shader's with the switch on and ONE edit -- densityLookup / temperatureLookup read textureLod(tex, uvw, 0.0), the
  * trilinear magnification filter with GL_REPEAT, instead of texture(tex, uvw), whose filter GL leaves to the 2x2 pixel quad (DESIGN.md
  * section 3, "Volumes").  Like the reference (window.cpp:271-286) only one volume exists: it applies to every media material.
@@ -340,6 +341,13 @@ int glrtx_set_extensions(glrtx_ctx *ctx, int flags);
  *   Rendering with GLRTX_EXT_VOLUME set and no volume uploaded fails with GLRTX_EINVAL.  Every trial ray of the Woodcock tracking counts as a
  *   ray (glrtx_count_rays).  Group members: glrtx_group_upload_volume, and the flag through glrtx_group_ctx. */
 #define GLRTX_EXT_VOLUME 4
+/*   glrtx_set_volume_wavefront   1: volume launches run on the wavefront kernel (variant 2) instead of the persistent megakernel -- frames in flight, fed
+ *                         launches, the present ring and glrtx_render_adaptive then work with the volume on, and variant_last reports 2.  Taken when
+ *                         the volume is the only extension (no GLRTX_EXT_DIELECTRIC / WHITTED, no spheres), variant 2 is selected, u_maxDepth <= 255 and
+ *                         u_nSamples < 2^16 (beyond that: the megakernel, GLRTX_FALLBACK_SAMPLES); anything else runs as with the switch off.  The
+ *                         images and ray counts are the megakernel's, bit for bit.  Default 0; GLRTX_VOLUME_WAVEFRONT=0/1 in the environment
+ *                         overrides it at every launch.  Group members: through glrtx_group_ctx. */
+int glrtx_set_volume_wavefront(glrtx_ctx *ctx, int enable);
 int glrtx_upload_volume(glrtx_ctx *ctx, const float *density, const float *temperature, int nx, int ny, int nz, const float bbox_min[3],
                         const float bbox_max[3], float density_max);
 /* Debug export (no ctx; the current HIP device): the device's statements of llvmpipe's log / exp / acos, and of blackBody, evaluated on n host

@@ -70,6 +70,7 @@ struct glrtx_ctx {
     DevBuf volDensity, volTemp;  // volume kernel (GLRTX_EXT_VOLUME): the two grids of glrtx_upload_volume
     VolArgs vol{};
     bool have_volume = false;
+    bool vol_wavefront = false;  // glrtx_set_volume_wavefront: volume launches on the wavefront kernel's V form (GLRTX_VOLUME_WAVEFRONT=0/1 overrides it per launch)
     DevBuf wfState, wfQ;      // wavefront path state (kWfStatePlanes = 6 planes of float4 x ids) + per-workgroup queues (variant 2)
     DevBuf wfSeeds, wfPlanes;       // frames in flight: per-frame seeds, per-sample planes
     // Single-frame launches that overlap (launch_wgwf): pipe_slots (<= kPipeSlots) slots used in turn, each with its own stream, path state, queues, tile
@@ -95,6 +96,7 @@ struct glrtx_ctx {
         int frames = 0, cap = 0;  // frames published so far / the most this launch can take
         LaunchRec *rec = nullptr;
         size_t frame_bytes = 0;   // sample planes of one frame
+        bool vol = false;         // the launch is the V form (kWgwfVolume)
     } open;
     bool feed_ok = true;            // cleared when the host-coherent blocks cannot be had; GLRTX_NO_FEED=1 (read at every launch, like the other switches) turns fed launches off (A/B, tests)
     bool last_was_render = false;   // the previous call on this context was glrtx_render / glrtx_render_frames (nothing has observed the accumulator since)
@@ -674,6 +676,24 @@ void seal_feed(glrtx_ctx *c) {
     c->last_was_render = false;
 }
 
+// Volume launches on the wavefront kernel (its V form, kWgwfVolume): the switch is on (glrtx_set_volume_wavefront; GLRTX_VOLUME_WAVEFRONT=0/1, read at every
+// launch like the other switches, overrides it), the volume is the only extension, a volume is uploaded and no spheres are.
+bool vol_wavefront(const glrtx_ctx *c) {
+    bool on = c->vol_wavefront;
+    if (const char *v = std::getenv("GLRTX_VOLUME_WAVEFRONT")) on = std::atoi(v) != 0;
+    return on && c->ext_flags == GLRTX_EXT_VOLUME && c->have_volume && c->n_spheres == 0;
+}
+
+// Whether the wavefront variant's packed path state can represent this launch (meta = depth | sample << 8 | flags << 28; the V form: sample in bits 8-23).
+bool wgwf_can_hold(const glrtx_params *p, bool vol = false) { return p->max_depth <= kWfDepthMax && p->n_samples <= (vol ? kWfVolSampleMax : kWfSampleMax); }
+
+// Whether a launch of this context runs on the wavefront kernel (variant 2): no extensions, or the volume alone with the V form switched on.
+bool wgwf_routes(const glrtx_ctx *c, const glrtx_params *p) {
+    if (c->variant != 2 || c->n_spheres > 0) return false;
+    if (c->ext_flags == 0) return wgwf_can_hold(p);
+    return vol_wavefront(c) && wgwf_can_hold(p, true);
+}
+
 bool same_camera(const glrtx_params &a, const glrtx_params &b) {
     return std::memcmp(a.c2w, b.c2w, sizeof a.c2w) == 0 && std::memcmp(a.s2c, b.s2c, sizeof a.s2c) == 0 && std::memcmp(&a.aperture, &b.aperture, 4) == 0 &&
            std::memcmp(&a.focal, &b.focal, 4) == 0 && a.n_samples == b.n_samples && a.max_depth == b.max_depth;
@@ -700,7 +720,7 @@ int feed_ensure_chunks(glrtx_ctx *c, glrtx_ctx::PipeSlot &sl, int first, int n, 
 int feed_append(glrtx_ctx *c, const glrtx_params *p, const float *seeds_xy, int n) {
     glrtx_ctx::OpenFeed &o = c->open;
     if (!o.slot) return 0;
-    if (!same_camera(o.p, *p) || o.frames + n > o.cap) { o.slot = nullptr; return 0; }
+    if (!same_camera(o.p, *p) || o.frames + n > o.cap || o.vol != (c->ext_flags != 0)) { o.slot = nullptr; return 0; }
     if (feed_ensure_chunks(c, *o.slot, o.frames, n, o.cap, o.frame_bytes) != GLRTX_OK) { (void)hipGetLastError(); c->err.clear(); o.slot = nullptr; return 0; }
     FeedHost *fh = o.slot->feed_h;
     for (int i = 0; i < n; i++) fh->seeds[o.frames + i] = make_float2(seeds_xy[2 * i], seeds_xy[2 * i + 1]);
@@ -920,6 +940,7 @@ int launch_wgwf(glrtx_ctx *c, const KernelArgs &a_in, const glrtx_params *p, con
     (void)hipGetLastError();
     const bool burst = c->last_was_render && busy && same_camera(c->last_p, *p);
     const bool adapt = c->adapt_launch;  // (glrtx_render_adaptive: plain, on the context's stream, always with sample planes; never fed)
+    const bool vol = c->ext_flags != 0;  // the V form (kWgwfVolume): routed here only with the volume alone (wgwf_routes)
     bool fed = !adapt && c->feed_ok && std::getenv("GLRTX_NO_FEED") == nullptr && c->pipeline && c->stream == c->own_stream && p->n_samples >= 1 && seeds_xy != nullptr && (n_frames > 1 || burst);
     int fed_cap = fed ? std::min(frames_cap(c, p, (int)kFedSlots), kFeedMaxFrames) : 0;
     if (const char *v = std::getenv("GLRTX_FEED_CAP")) fed_cap = std::max(1, std::min(fed_cap, std::atoi(v)));  // (tests: launches that fill up)
@@ -939,10 +960,12 @@ int launch_wgwf(glrtx_ctx *c, const KernelArgs &a_in, const glrtx_params *p, con
     // config 2 -0.4 %, config 4 -1.0 % against the alternating one, the pure pair form +1.9 % (profiles/r05_state_by_position.txt).  The alternating form stays
     // compiled in (GLRTX_PAIR_FETCH=2).  Random triangle soups prefer the pair form from 10 k triangles on (-2 %; 20 k: -4.5 %, 70 k: -7 %): what decides is how
     // far apart a wave's rays are in the tree, which the record count only approximates.
-    using Kernel = void (*)(const KernelArgs, const WfArgs, unsigned *, float4 *, const int *, const unsigned *);
-    const bool vine = c->sc.n_vine > 0;
+    // The V form has one fetch form only: one record per lane on DevScene::nodes, as in the megakernels (no list scan, no pair fetch, no compact layout).
+    using Kernel = void (*)(const KernelArgs, const WfArgs, unsigned *, float4 *, const int *, const unsigned *, const VolArgs);
+    const bool vine = c->sc.n_vine > 0 && !vol;
     int fetch = vine ? 0 : ((size_t)c->n_fork + (size_t)c->st.n_tri >= (size_t)kPairFetchMinRecords ? 1 : 0);
     if (const char *v = std::getenv("GLRTX_PAIR_FETCH")) fetch = vine ? 0 : std::max(0, std::min(2, std::atoi(v)));
+    if (vol) fetch = 0;
     c->st.node_fetch_last = fetch;
     // The compact node array (pack_compact: 48-byte records, three loads per step instead of four) serves the one-record-per-lane fetch when its rank table fits in
     // LDS beside everything else with GLRTX_WGWF_WAVES workgroups per CU still resident; GLRTX_COMPACT_NODES=0/1 overrides (1: as long as one workgroup fits).
@@ -952,11 +975,15 @@ int launch_wgwf(glrtx_ctx *c, const KernelArgs &a_in, const glrtx_params *p, con
     const int lds_compact = lds_base + c->sc.n_crank * (int)sizeof(uint2);  // | rank table
     bool compact = !vine && fetch == 0 && c->sc.n_crank > 0 && (size_t)lds_compact * GLRTX_WGWF_WAVES <= (size_t)160 * 1024;
     if (const char *v = std::getenv("GLRTX_COMPACT_NODES")) compact = std::atoi(v) != 0 && !vine && fetch == 0 && c->sc.n_crank > 0 && lds_compact <= 160 * 1024;
+    if (vol) compact = false;
     c->st.node_layout_last = compact ? 1 : 0;
     const bool cr = c->count_rays;
     constexpr int A = kWgwfAdaptive;  // (the ADAPT forms of the same eight: glrtx_render_adaptive)
     constexpr int CP = kWgwfCompact;
-    const Kernel kernel = compact ? (adapt ? (cr ? (Kernel)pt_render_wgwf<true, false, CP | A> : (Kernel)pt_render_wgwf<false, false, CP | A>)
+    constexpr int V = kWgwfVolume;  // (the V form: glrtx_set_volume_wavefront)
+    const Kernel kernel = vol ? (adapt ? (cr ? (Kernel)pt_render_wgwf<true, false, V | A> : (Kernel)pt_render_wgwf<false, false, V | A>)
+                                       : (cr ? (Kernel)pt_render_wgwf<true, false, V> : (Kernel)pt_render_wgwf<false, false, V>))
+                        : compact ? (adapt ? (cr ? (Kernel)pt_render_wgwf<true, false, CP | A> : (Kernel)pt_render_wgwf<false, false, CP | A>)
                                            : (cr ? (Kernel)pt_render_wgwf<true, false, CP> : (Kernel)pt_render_wgwf<false, false, CP>))
                         : adapt ? (vine ? (cr ? (Kernel)pt_render_wgwf<true, true, A> : (Kernel)pt_render_wgwf<false, true, A>)
                                    : fetch == 2 ? (cr ? (Kernel)pt_render_wgwf<true, false, 2 | A> : (Kernel)pt_render_wgwf<false, false, 2 | A>)
@@ -1140,6 +1167,10 @@ int launch_wgwf(glrtx_ctx *c, const KernelArgs &a_in, const glrtx_params *p, con
     // trip guards (pt_render_wgwf): a path is alive for at most n_samples x (max_depth + 2) shaded trips; 64 times that (parked trips, the other paths' rounds) and a
     // constant are allowed between two tiles a workgroup is given
     w.trip_limit = (int)std::min<long long>(INT32_MAX, 64ll * std::max(p->n_samples, 1) * (p->max_depth + 2) + 64);
+    // The V form: a bounce through a medium takes up to nine shaded trips instead of one -- the media hit that queues trial 1, then trials 1 .. 8, the last of which
+    // queues the exit ray (the next bounce's path ray) -- and every such bounce ends the sample or advances the depth.  So a sample is alive for at most
+    // 9 x (max_depth + 2) shaded trips, and the bound is nine times the plain one: 64 x n_samples x 9 x (max_depth + 2) + 64.
+    if (vol) w.trip_limit = (int)std::min<long long>(INT32_MAX, 64ll * std::max(p->n_samples, 1) * 9 * (p->max_depth + 2) + 64);
     if (const char *v = std::getenv("GLRTX_TRIP_LIMIT")) w.trip_limit = std::max(1, std::atoi(v));
     w.err = c->guard_dev;
     // Shape invariants of the hand-written kernel, checked on the host before every launch (an access past one of these
@@ -1156,6 +1187,8 @@ int launch_wgwf(glrtx_ctx *c, const KernelArgs &a_in, const glrtx_params *p, con
                   block_paths <= kWgPathsMax && slice_f4 <= kWgQueueF4 && queueBuf.bytes >= (size_t)grid * kWgQueueF4 * sizeof(float4) &&
                   stateBuf.bytes >= state_bytes && w.ids == state_entries && grid >= 1 && (size_t)grid <= wg_slots &&
                   p->max_depth <= kWfDepthMax && p->n_samples <= kWfSampleMax && workPtr != nullptr;
+        if (vol) ok = ok && p->n_samples <= kWfVolSampleMax && c->ext_flags == GLRTX_EXT_VOLUME && c->have_volume && c->vol.density != nullptr &&
+                      c->vol.temperature != nullptr && c->n_spheres == 0 && !vine && fetch == 0 && !compact;
         if (!fed && n_frames > 1) ok = ok && c->wfSeeds.bytes >= (size_t)n_frames * sizeof(float2);
         if (w.planes) ok = ok && planeBuf.bytes >= (size_t)std::max(n_planes, 1) * plane_f4 * sizeof(float4);
         if (adapt) ok = ok && !fed && !slot && w.planes && c->ad_selected && c->ad_tiles == (int)(total >> 6) && c->adList.bytes >= (total >> 6) * sizeof(int) &&
@@ -1178,10 +1211,12 @@ int launch_wgwf(glrtx_ctx *c, const KernelArgs &a_in, const glrtx_params *p, con
         HIP_TRY(c, hipGetLastError());
     }
     HIP_TRY(c, hipEventRecord(rec->ev0, rstream));
-    c->last_kernel = adapt ? (vine ? "pt_render_wgwf (adaptive, list scan)" : "pt_render_wgwf (adaptive)") : vine ? "pt_render_wgwf (list scan)" : "pt_render_wgwf";
+    c->last_kernel = vol ? (adapt ? "pt_render_wgwf (volume, adaptive)" : "pt_render_wgwf (volume)")
+                   : adapt ? (vine ? "pt_render_wgwf (adaptive, list scan)" : "pt_render_wgwf (adaptive)") : vine ? "pt_render_wgwf (list scan)" : "pt_render_wgwf";
     c->counters_stale = c->counters_stale || c->count_rays;
+    const VolArgs va = vol ? c->vol : VolArgs{};
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlockThreads), lds, rstream, a, w, workPtr, (float4 *)queueBuf.p, adapt ? (const int *)c->adList.p : nullptr,
-                       adapt ? (const unsigned *)c->adCount.p : nullptr);
+                       adapt ? (const unsigned *)c->adCount.p : nullptr, va);
     HIP_TRY(c, hipGetLastError());
 #ifdef GLRTX_RAY_LOG
     g_dbg_last = {a, w, lds, grid, (float4 *)queueBuf.p, fetch};
@@ -1228,15 +1263,13 @@ int launch_wgwf(glrtx_ctx *c, const KernelArgs &a_in, const glrtx_params *p, con
     // what the next call may build on
     c->last_render_done = slot ? slot->render_done : c->state_done;  // (a plain launch runs on the context's path state: ctx_state above)
     if (fed) {
-        c->open.slot = slot; c->open.p = *p; c->open.frames = n_frames; c->open.cap = fed_cap; c->open.rec = rec; c->open.frame_bytes = frame_bytes;
+        c->open.slot = slot; c->open.p = *p; c->open.frames = n_frames; c->open.cap = fed_cap; c->open.rec = rec; c->open.frame_bytes = frame_bytes; c->open.vol = vol;
         c->st.feed_launches++;
     } else c->open.slot = nullptr;
     if (pres && !pres_fused) return present_resolve(c);
     return GLRTX_OK;
 }
 
-// Whether the wavefront variant's packed path state can represent this launch (meta = depth | sample << 8 | flags << 28).
-bool wgwf_can_hold(const glrtx_params *p) { return p->max_depth <= kWfDepthMax && p->n_samples <= kWfSampleMax; }
 
 // ---- adaptive sampling (glrtx_render_adaptive)
 // The half buffer H at the accumulator's current shape, zeroed (on first adaptive use, at a clear or resize, and when the accumulator's pitch or rows have changed).
@@ -1258,10 +1291,11 @@ int adapt_check(glrtx_ctx *c, const glrtx_params *p, const float *seeds_xy, int 
     if (!c->accum || c->width < 1) return fail(c, GLRTX_EINVAL, "%s: no accumulator (call glrtx_resize)", fn);
     if (p->n_samples < 0 || p->max_depth < 0) return fail(c, GLRTX_EINVAL, "%s: negative n_samples/max_depth", fn);
     if (c->pres.ring > 0) return fail(c, GLRTX_EINVAL, "%s: presentation is enabled (the present ring has no adaptive form)", fn);
-    if (c->ext_flags != 0) return fail(c, GLRTX_EINVAL, "%s: extensions or volume are on (only the wavefront kernel has a tile list)", fn);
+    const bool vol = vol_wavefront(c);  // the volume alone, with the V form switched on: the wavefront kernel runs it
+    if (c->ext_flags != 0 && !vol) return fail(c, GLRTX_EINVAL, "%s: extensions or volume are on (only the wavefront kernel has a tile list)", fn);
     if (c->n_spheres > 0) return fail(c, GLRTX_EINVAL, "%s: spheres are uploaded (only the wavefront kernel has a tile list)", fn);
     if (c->variant != 2) return fail(c, GLRTX_EINVAL, "%s: variant %d (only the wavefront kernel, variant 2, has a tile list)", fn, c->variant);
-    if (!wgwf_can_hold(p)) return fail(c, GLRTX_EINVAL, "%s: max_depth %d / n_samples %d beyond the wavefront kernel's path state", fn, p->max_depth, p->n_samples);
+    if (!wgwf_can_hold(p, vol)) return fail(c, GLRTX_EINVAL, "%s: max_depth %d / n_samples %d beyond the wavefront kernel's path state", fn, p->max_depth, p->n_samples);
     return GLRTX_OK;
 }
 
@@ -1827,6 +1861,13 @@ int glrtx_set_shadow_range_limit(glrtx_ctx *c, int enable) {
     return GLRTX_OK;
 }
 
+int glrtx_set_volume_wavefront(glrtx_ctx *c, int enable) {
+    if (!c) return GLRTX_EINVAL;
+    seal_feed(c);  // (nothing is appended to an open launch across this call: glrtx_ctx::OpenFeed)
+    c->vol_wavefront = enable != 0;  // read by the next launch (render_one: vol_wavefront)
+    return GLRTX_OK;
+}
+
 int glrtx_count_rays(glrtx_ctx *c, int enable) {
     if (!c) return GLRTX_EINVAL;
     seal_feed(c);  // (nothing is appended to an open launch across this call: glrtx_ctx::OpenFeed)
@@ -1841,7 +1882,7 @@ int glrtx_render_frames(glrtx_ctx *c, const glrtx_params *p, const float *seeds_
     if (n_frames < 0 || (n_frames > 0 && !seeds_xy)) return fail(c, GLRTX_EINVAL, "glrtx_render_frames: bad seeds/n_frames");
     if (n_frames == 0) return GLRTX_OK;
     if (int rc = present_prepare(c, n_frames)) return rc;  // (GLRTX_EBUSY: nothing has changed)
-    if (n_frames == 1 || c->variant != 2 || !wgwf_can_hold(p) || c->n_spheres > 0 || c->ext_flags != 0) {  // the megakernels have no frames-in-flight form: one launch per frame
+    if (n_frames == 1 || !wgwf_routes(c, p)) {  // the megakernels have no frames-in-flight form: one launch per frame
         for (int f = 0; f < n_frames; f++) {
             glrtx_params q = *p;
             q.seed[0] = seeds_xy[2 * f]; q.seed[1] = seeds_xy[2 * f + 1];
@@ -1993,7 +2034,7 @@ static int render_one(glrtx_ctx *c, const glrtx_params *p) {
     if (p->n_samples < 0 || p->max_depth < 0) return fail(c, GLRTX_EINVAL, "glrtx_render: negative n_samples/max_depth");
     if ((c->ext_flags & GLRTX_EXT_VOLUME) && !c->have_volume) return fail(c, GLRTX_EINVAL, "glrtx_render: GLRTX_EXT_VOLUME is set and no volume is uploaded (glrtx_upload_volume)");
     HIP_TRY(c, hipSetDevice(c->device));
-    const bool wavefront = c->variant == 2 && wgwf_can_hold(p) && c->n_spheres == 0 && c->ext_flags == 0;
+    const bool wavefront = wgwf_routes(c, p);
     if (c->owned_rows > 0 && wavefront && c->frames_n == 1 && !c->adapt_launch && feed_append(c, p, p->seed, 1) == 1) {  // a launch of the same camera that is still open takes the frame itself
         c->last_was_render = true; c->last_p = *p;
         return presenting(c) ? present_issue(c, 1) : GLRTX_OK;
@@ -2032,13 +2073,15 @@ static int render_one(glrtx_ctx *c, const glrtx_params *p) {
     // The wavefront variant packs depth and sample index into one word of the path state (kWfDepthMax, kWfSampleMax);
     // a launch beyond those ranges runs on the persistent megakernel instead (bit-identical, no packed state).
     // Extensions (analytic spheres, dielectric, Whitted termination) exist only in the persistent megakernel's EXT instantiation.
+    // The volume alone goes to the wavefront kernel's V form when that is switched on (glrtx_set_volume_wavefront), within its narrower sample range (kWfVolSampleMax).
     const bool ext = c->n_spheres > 0 || c->ext_flags != 0;
-    const int variant = (ext || (c->variant == 2 && !wgwf_can_hold(p))) ? 1 : c->variant;
+    const bool vol_wf = vol_wavefront(c);
+    const int variant = ((ext && !vol_wf) || (vol_wf && c->variant != 2) || (c->variant == 2 && !wgwf_can_hold(p, vol_wf))) ? 1 : c->variant;
     c->st.variant_last = variant;
     c->st.fallback_last = 0;
     if (c->variant == 2 && variant != 2) {  // not silently: the reason and a count are in the stats
-        c->st.fallback_last = (ext ? GLRTX_FALLBACK_EXTENSIONS : 0) | (p->max_depth > kWfDepthMax ? GLRTX_FALLBACK_DEPTH : 0) |
-                              (p->n_samples > kWfSampleMax ? GLRTX_FALLBACK_SAMPLES : 0);
+        c->st.fallback_last = (ext && !vol_wf ? GLRTX_FALLBACK_EXTENSIONS : 0) | (p->max_depth > kWfDepthMax ? GLRTX_FALLBACK_DEPTH : 0) |
+                              (p->n_samples > (vol_wf ? kWfVolSampleMax : kWfSampleMax) ? GLRTX_FALLBACK_SAMPLES : 0);
         c->st.fallback_launches++;
     }
     if (variant == 2) {

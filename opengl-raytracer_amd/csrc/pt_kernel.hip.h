@@ -600,6 +600,9 @@ struct StepTiming { unsigned t = 0, w = 0, n = 0; };
 // FETCH: 0 one record per lane, 1 pair-cooperative, 2 the two forms in alternate steps (pair first) -- see trav_asm.hip.h and launch_wgwf (glrtx.hip);
 // kWgwfCompact | 0: one record per lane from the compact node array (DevScene::cnodes, 48-byte records; rk: the LDS byte address of its rank table)
 constexpr int kWgwfCompact = 8;
+// kWgwfVolume: the V form of pt_render_wgwf -- the volume branch (bounce_volume) as a state machine of the shade phase, one trial ray per trip (wf_vol_trial).
+// Only with the one-record-per-lane fetch on DevScene::nodes (FETCH 0, optionally | kWgwfAdaptive); masked out wherever FETCH selects the node fetch.
+constexpr int kWgwfVolume = 16;
 template <int FETCH>
 DEV void trav_steps_asm(const DevScene &sc, int *stack, Trav &T, unsigned rk GLRTX_TS_PARAM) {
     unsigned long long s_entry, s_act, s_leaf, s_bl, s_br, s_pop, s_tmp;
@@ -1795,6 +1798,11 @@ struct WfArgs {
 constexpr int kWfStatePlanes = 2 * kWfSetPlanes;  // float4-wide planes of WfArgs::state: two sets of six
 constexpr int kWfDepthMax = 255;
 constexpr int kWfSampleMax = (1 << 20) - 1;
+// The V form (kWgwfVolume) narrows the sample index to bits 8-23 and keeps the path's volume state in bits 24-27: 0 no volume, 1..8 trial k of the Woodcock
+// loop is in flight (the hit record is that trial's closest hit), kWfVolPassed the path's ray left a medium (passedVolume, :486: the next surface's emission counts).
+constexpr int kWfVolSampleMax = (1 << 16) - 1;
+constexpr unsigned kWfVolShift = 24;
+constexpr unsigned kWfVolPassed = 9;
 constexpr unsigned WF_PENDING = 1u << 28;    // a shadow ray of the previous bounce is in flight
 constexpr unsigned WF_FINISHING = 1u << 29;  // the path has ended; only that shadow ray is awaited
 constexpr unsigned WF_RESOLVED = 1u << 30;   // the pending shadow ray's verdict is known already (bit 31) -- set when a path is deferred (below)
@@ -1908,11 +1916,72 @@ DEV bool wf_generate_one(const KernelArgs &a, const WfArgs &w, const float *cam,
     return go;
 }
 
+// The V form's trip of bounce_volume's trial loop (:436-485): h is the closest hit of trial k (1..8), traced from P.o along P.d.  The same pt_rand draws in the
+// same order and the same operations as bounce_volume.  Returns kWfVolEnd (the sample ends, P.L final), kWfVolNext (trial k + 1 from the scatter point P.o along
+// P.d) or kWfVolExit (the path goes on from P.o along P.d as an ordinary path ray with passedVolume set; depth advanced, Russian roulette played).
+// The volume's arguments are read through wgwf_vol(), a pointer into the kernarg segment the compiler cannot see through, taken anew in every step of the
+// Woodcock loop: hoisted out of it, the grid's twelve words would sit in scalar registers across the loop and push the V form into spills.
+constexpr int kWfVolEnd = 0, kWfVolNext = 1, kWfVolExit = 2;
+DEV const VolArgs *wgwf_vol();  // WgwfKernArgs::vol of the running pt_render_wgwf launch (defined below)
+// Beta and L (planes 2 and 3 at state index sidx) are fetched again behind the loop rather than carried through it: six registers less where the shade phase peaks.
+DEV int wf_vol_trial(const KernelArgs &a, const WfArgs &w, unsigned sidx, Rng &rng, Path &P, const Hit &h, unsigned k) {
+    if (h.tri < 0) { P.Lx = 1.0f; P.Ly = 0.0f; P.Lz = 1.0f; return kWfVolEnd; }  // the trial ray left the scene: magenta (:441)
+    const float ox = P.ox, oy = P.oy, oz = P.oz, dx = P.dx, dy = P.dy, dz = P.dz;
+    float t = 0.0f;
+    bool pass = false;
+    for (int i = 0; i < 256; i++) {
+        const VolArgs &vo = *wgwf_vol();
+        const float dm = vo.density_max;
+        t = t - lp_log(fmax_c(1.0f - pt_rand(rng), PT_EPS)) / (dm * VOL_SIGT);
+        if (t >= h.t) { pass = true; break; }
+        const float density = vol_lookup(vo.density, vo, ox + t * dx, oy + t * dy, oz + t * dz);
+        if (density / dm > pt_rand(rng)) { pass = true; break; }  // (the rand() is drawn only when t < tHit)
+    }
+    if (!pass) { P.Lx = 0.0f; P.Ly = 0.0f; P.Lz = 0.0f; return kWfVolEnd; }  // no decision in 256 steps: black (:460)
+    {
+        unsigned si = sidx;
+        asm volatile("" : "+v"(si));  // (opaque: the loads are not merged with the ones in front of the loop)
+        const float4 b = ld_stream(w.A(2, si)), l = ld_stream(w.A(3, si));
+        P.bx = b.x; P.by = b.y; P.bz = b.z; P.Lx = l.x; P.Ly = l.y; P.Lz = l.z;
+    }
+    if (t >= h.t) {  // left the medium: continue behind its boundary (:464-467)
+        const float te = h.t + PT_EPS;
+        P.ox = ox + te * dx; P.oy = oy + te * dy; P.oz = oz + te * dz;
+    } else {
+        P.ox = ox + t * dx; P.oy = oy + t * dy; P.oz = oz + t * dz;
+        float R, G, B;
+        const VolArgs &vo = *wgwf_vol();
+        vol_blackbody(vol_lookup(vo.temperature, vo, P.ox, P.oy, P.oz), R, G, B);  // :472-473
+        P.Lx = P.Lx + (P.bx * R) / VOL_SIGT; P.Ly = P.Ly + (P.by * G) / VOL_SIGT; P.Lz = P.Lz + (P.bz * B) / VOL_SIGT;
+        const float theta = lp_acos(2.0f * pt_rand(rng) + -1.0f);  // :476-480
+        const float phi = PT_2PI * pt_rand(rng);
+        const float ct = pt_cos(theta), st = pt_sin(theta);
+        P.dx = st * pt_cos(phi); P.dy = st * pt_sin(phi); P.dz = ct;
+        P.bx = P.bx * VOL_ALBEDO; P.by = P.by * VOL_ALBEDO; P.bz = P.bz * VOL_ALBEDO;  // :483
+        if (k < 8u) return kWfVolNext;
+        // (eight trials without a break: the loop falls through to the exit from the last scatter point, in the last direction)
+    }
+    const int depth = P.depth;
+    P.depth = depth + 1;
+    if (2 < depth) {  // Russian roulette :549-555, on the depth before the increment, as in bounce_volume
+        float pm = fmax_g(P.by, P.bz);
+        pm = fmax_g(P.bx, pm);
+        const float pq = fmin_c(pm, 0.95f);
+        const float rr = pt_rand(rng);
+        if (pq < rr) return kWfVolEnd;
+        P.bx = fdiv(P.bx, pq); P.by = fdiv(P.by, pq); P.bz = fdiv(P.bz, pq);
+    }
+    return P.depth >= a.max_depth ? kWfVolEnd : kWfVolExit;
+}
+
 // One path of the shade stage: resolve the light sample of the previous bounce, then either close the
 // sample (and start the pixel's next one) or run shade_hit() on the new hit.  Outputs which rays to
 // queue for the next trip: push_ext = the path's next ray, push_sh = this bounce's shadow ray -- and, when the path goes on (either of them, or requeue), its state
 // for the next trip, which the caller stores once it knows the path's next queue position: ray_o = plane 0 {origin, rng.x}, ray_d = plane 1 {direction, rng.y},
 // st2 / st3 = planes 2 / 3, st4 = plane 4 when has4.
+// VOL (the V form, kWgwfVolume): a media surface hit from the front queues trial 1 instead of being shaded, a trial's hit runs
+// wf_vol_trial, and a surface met after a volume is shaded with passedVolume set (meta bits 24-27, kWfVolShift).
+template <bool VOL = false>
 DEV void wf_shade_path(const KernelArgs &a, const WfArgs &w, const float4 *lds_mats, const float *cam, unsigned &id, unsigned sidx, bool light_accepted, bool &push_ext,
                        bool &push_sh, bool &requeue, float4 &ray_o, float4 &ray_d, float4 &ray_sd, float4 &st2, float4 &st3, float4 &st4, bool &has4, unsigned long long &rays) {
     const float4 s0 = ld_stream(w.A(0, sidx)), s1 = ld_stream(w.A(1, sidx)), s2 = ld_stream(w.A(2, sidx)), s3 = ld_stream(w.A(3, sidx));
@@ -1927,7 +1996,8 @@ DEV void wf_shade_path(const KernelArgs &a, const WfArgs &w, const float4 *lds_m
     const float2 sd = wf_seed(a, w, cam, (int)id);
     Rng rng = {s0.w, s1.w, sd.x, sd.y};
     const unsigned meta = __float_as_uint(s2.w);
-    unsigned sample = (meta >> 8) & 0xFFFFFu;
+    unsigned sample = (meta >> 8) & (VOL ? (unsigned)kWfVolSampleMax : 0xFFFFFu);
+    const unsigned vstate = VOL ? (meta >> kWfVolShift) & 0xFu : 0u;
     Path P;
     P.ox = s0.x; P.oy = s0.y; P.oz = s0.z; P.dx = s1.x; P.dy = s1.y; P.dz = s1.z;
     P.bx = s2.x; P.by = s2.y; P.bz = s2.z;
@@ -1944,6 +2014,18 @@ DEV void wf_shade_path(const KernelArgs &a, const WfArgs &w, const float4 *lds_m
     bool ended = (meta & WF_FINISHING) != 0u;
     Shade sh;
     sh.has_shadow = false;
+    // V form: trial k's hit (not parked: see kSuspendMax) runs the Woodcock loop here, at the top level of the function, where the fewest masks are live
+    bool vtrial = false;
+    int vtrial_next = 0;
+    if constexpr (VOL) {
+        vtrial = vstate >= 1u && vstate <= 8u && hh.x != kHitSuspended;
+        if (vtrial) {
+            Hit h;
+            h.t = hh.x; h.tri = __float_as_int(hh.y); h.u = hh.z; h.v = hh.w;
+            const int r = wf_vol_trial(a, w, sidx, rng, P, h, vstate);
+            vtrial_next = r == kWfVolNext ? (int)vstate + 1 : r == kWfVolExit ? (int)kWfVolPassed : 0;
+        }
+    }
     if (!ended) {
         if (hh.x == kHitSuspended) {
             // the path's ray is parked in a traversal lane (see kSuspendMax): nothing to shade yet.  The path stays in the queue -- its state moves to its next
@@ -1962,10 +2044,46 @@ DEV void wf_shade_path(const KernelArgs &a, const WfArgs &w, const float4 *lds_m
         Hit h;
         h.t = hh.x; h.tri = __float_as_int(hh.y); h.u = hh.z; h.v = hh.w;
         if (a.hit_hist != nullptr && h.tri >= 0) atomicAdd(&a.hit_hist[h.tri], 1u);  // (a calibration frame only: glrtx_hit_histogram)
-        shade_hit(a, lds_mats, rng, P, h, sh);
-        if (sh.untraced) rays += (1ull << 32) + 1ull;  // counted as the reference's intersect() call, not traced (Shade::untraced)
-        if (sh.ended && !sh.has_shadow) { P.Lx = sh.Lpx; P.Ly = sh.Lpy; P.Lz = sh.Lpz; }
-        ended = sh.ended && !sh.has_shadow;  // with a shadow ray in flight the sample closes next trip
+        if constexpr (VOL) {
+            // the volume branch (bounce_ext<true> / bounce_volume): at most one more ray per trip -- the next trial, or the exit ray -- and never a shadow ray
+            int vnext = -1;  // the volume state of the queued ray; -1: not a volume step
+            if (vtrial) {
+                vnext = vtrial_next;
+                if (vnext == 0) ended = true;
+            } else if (h.tri >= 0) {
+                const Surf S = surf_tri(a.sc, h);
+                const Mat M = load_mat(a.sc, lds_mats, S.mtrl);
+                const int type = __float_as_int(M.m0.w);
+                if (type == 5 && (-(P.dz * S.nz) - (P.dy * S.ny)) - (P.dx * S.nx) >= PT_EPS) {  // a media surface from the front (:424): trial 1 from x (:420)
+                    const float tt = h.t + PT_EPS;
+                    P.ox = P.ox + tt * P.dx; P.oy = P.oy + tt * P.dy; P.oz = P.oz + tt * P.dz;
+                    vnext = 1;
+                } else if (vstate == kWfVolPassed) {
+                    // passedVolume (:486, :490-494): the surface's emission counts -- added here, as shade_core<true> adds it first thing for P.spec (the depth is
+                    // at least 1 behind a volume, so shade_hit does not add it again); shade_hit then does the rest with the lighter register footprint of shade_core<false>
+                    P.Lx = P.Lx + P.bx * M.m0.x; P.Ly = P.Ly + P.by * M.m0.y; P.Lz = P.Lz + P.bz * M.m0.z;
+                }
+            }
+            if (vnext >= 0) {
+                if (!ended) {
+                    push_ext = true;
+                    ray_o = make_float4(P.ox, P.oy, P.oz, rng.x);
+                    ray_d = make_float4(P.dx, P.dy, P.dz, rng.y);
+                    st2 = make_float4(P.bx, P.by, P.bz, __uint_as_float((unsigned)P.depth | (sample << 8) | ((unsigned)vnext << kWfVolShift)));
+                    st3 = make_float4(P.Lx, P.Ly, P.Lz, s3.w);
+                    return;
+                }
+            } else {
+                shade_hit(a, lds_mats, rng, P, h, sh);
+            }
+        } else {
+            shade_hit(a, lds_mats, rng, P, h, sh);
+        }
+        if (!(VOL && ended)) {  // (V form: a trial that ended the sample has set P.L itself)
+            if (sh.untraced) rays += (1ull << 32) + 1ull;  // counted as the reference's intersect() call, not traced (Shade::untraced)
+            if (sh.ended && !sh.has_shadow) { P.Lx = sh.Lpx; P.Ly = sh.Lpy; P.Lz = sh.Lpz; }
+            ended = sh.ended && !sh.has_shadow;  // with a shadow ray in flight the sample closes next trip
+        }
     }
     if (ended) {
         // (the pixel is worked out HERE, where a sample closes, not in front of the shading: two registers less to carry through it)
@@ -2288,6 +2406,7 @@ DEV void wg_traverse_phase(const KernelArgs &a, const WfArgs &w, const float4 *r
 // lane that finished the path's shadow ray; the shadow ray pushed here carries the position its path will have in pq_next.
 // Path state: the path at queue position i is read at state index cur_base + i and -- if it goes on -- written at next_base + (its position in pq_next); the next
 // ray's record carries that index (even ray id: where the traversal lane stores the hit), and a ray parked in a traversal lane finds it behind the mark it left.
+template <bool VOL = false>
 DEV void wg_shade_phase(const KernelArgs &a, const WfArgs &w, const float4 *lds_mats, const float *cam, const unsigned *light_bits, int n_paths,
                         float4 *rq_next, unsigned *n_rays_next, unsigned *n_paths_next, unsigned cur_base, unsigned next_base, unsigned long long &rays,
                         unsigned *moved) {
@@ -2300,7 +2419,7 @@ DEV void wg_shade_phase(const KernelArgs &a, const WfArgs &w, const float4 *lds_
         float4 ro = make_float4(0.f, 0.f, 0.f, 0.f), rd = ro, rsd = ro, st2 = ro, st3 = ro, st4 = ro;
         const bool light_accepted = i < n_paths && ((light_bits[i >> 5] >> (i & 31)) & 1u) != 0u;
         if (i < n_paths)
-            wf_shade_path(a, w, lds_mats, cam, id, cur_base + (unsigned)i, light_accepted, push_ext, push_sh, requeue, ro, rd, rsd, st2, st3, st4, has4, rays);
+            wf_shade_path<VOL>(a, w, lds_mats, cam, id, cur_base + (unsigned)i, light_accepted, push_ext, push_sh, requeue, ro, rd, rsd, st2, st3, st4, has4, rays);
         const unsigned long long me = __ballot(push_ext), ms = __ballot(push_sh), mq = __ballot(requeue), mp = me | ms | mq;
         const unsigned long long mv = __ballot(id != WF_INVALID);
         unsigned br = 0, bp = 0;
@@ -2361,6 +2480,9 @@ struct WgwfKernArgs {
     // adaptive_compact_kernel in front of the launch.  Trailing kernel arguments, null in every other launch: behind wg_queues no offset of an existing argument moves.
     const int *adapt_list;
     const unsigned *adapt_count;
+    // the V form (kWgwfVolume): the launch's volume (glrtx_upload_volume).  A trailing kernel argument like the two above (zeros in every other launch), read only
+    // under `if constexpr` -- not a __device__ global: two contexts in one process (a group's members on one device) would share that.
+    VolArgs vol;
 };
 DEV const WgwfKernArgs *wgwf_kernargs() {
     auto p = __builtin_amdgcn_kernarg_segment_ptr();  // constant address space
@@ -2369,6 +2491,7 @@ DEV const WgwfKernArgs *wgwf_kernargs() {
 }
 
 DEV int wgwf_suspend_max() { return wgwf_kernargs()->w.suspend_max; }
+DEV const VolArgs *wgwf_vol() { return &wgwf_kernargs()->vol; }
 
 // Top-up of a FED launch (FeedHost / FeedDev), run by the workgroup's first wave in place of thread 0's part of pt_render_wgwf's top-up: the tiles known so far are
 // frames_known x tiles_per_frame; when few are left the wave looks at the host's word, copies the seeds and plane chunks of newly published frames into the device
@@ -2377,6 +2500,7 @@ DEV int wgwf_suspend_max() { return wgwf_kernargs()->w.suspend_max; }
 // is not lost -- the tile counter runs on into frames that may yet be published -- but kept by the workgroup as its PENDING claim (ctl[16..17]) and served, before
 // anything else is claimed, once the frames it falls into are known.  A workgroup with nothing alive and nothing to serve closes the feed -- its pending claim then lies
 // beyond the last frame and is dropped -- or, if the host was quicker, looks again.
+template <bool VOL = false>
 DEV void wg_feed_topup(int kWgPaths, unsigned *ctl, int cur, unsigned *work_counter) {
     const WgwfKernArgs *k = wgwf_kernargs();
     FeedHost *fh = k->w.feed_host;
@@ -2384,7 +2508,9 @@ DEV void wg_feed_topup(int kWgPaths, unsigned *ctl, int cur, unsigned *work_coun
     // Every atomic here is RELAXED: an acquire at agent scope invalidates the CU's vector cache -- once per trip and workgroup that would cost the traverse phase its BVH
     // lines -- and nothing needs one: the counts are read past the caches by the atomics themselves, and what a count announces lies in lines no cache has seen before
     // (FeedDev) or in host memory (read past the caches as well).  "Closed" travels in bit 31 of the same word as the count, so the two are never seen apart.
-    const int lane = threadIdx.x;
+    int lane = threadIdx.x;
+    // (the V form: an opaque copy, so that the `lane != 0` mask is formed here, not held in a scalar pair across the whole loop -- the V form has none to spare)
+    if constexpr (VOL) asm volatile("" : "+v"(lane));
     const int tpf = k->w.tiles_per_frame, gss_div = k->w.gss_div;
     const int np = (int)ctl[4 + cur];
     const bool may_take = ctl[7] == 0u && ctl[13] == 0u;
@@ -2488,11 +2614,15 @@ DEV void wg_feed_topup(int kWgPaths, unsigned *ctl, int cur, unsigned *work_coun
 // and counter value g is tile adapt_list[g % n_active] of frame g / n_active.  Only the top-up differs: the path ids it hands out are real ids (frame * total +
 // tile-order pixel), so everything downstream -- wf_pixel, wf_seed, wf_add_sample, WfArgs::split -- is the same code.  The adaptive list and count are trailing
 // kernel arguments (null in every other launch: behind wg_queues no offset of an existing argument moves), read through wgwf_kernargs.
+// kWgwfVolume likewise selects the V form (wf_shade_path<true>), alone or with kWgwfAdaptive.
 constexpr int kWgwfAdaptive = 4;
 template <bool COUNT_RAYS, bool VINE, int FETCH = 0>
 __global__ __launch_bounds__(kBlockThreads, GLRTX_WGWF_WAVES) void pt_render_wgwf(const KernelArgs a, const WfArgs w, unsigned *work_counter, float4 *wg_queues,
-                                                                                  const int * /*adapt_list*/, const unsigned * /*adapt_count*/) {
+                                                                                  const int * /*adapt_list*/, const unsigned * /*adapt_count*/, const VolArgs /*vol*/) {
     constexpr bool ADAPT = (FETCH & kWgwfAdaptive) != 0;
+    constexpr bool VOL = (FETCH & kWgwfVolume) != 0;
+    constexpr int NODE_FETCH = FETCH & ~(kWgwfAdaptive | kWgwfVolume);  // what selects the node fetch
+    static_assert(!VOL || (!VINE && NODE_FETCH == 0), "the V form has the one-record-per-lane fetch on DevScene::nodes only");
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     // LDS: materials | stack | ctl[16].  The workgroup's ray/path queues live in its private slice of a
     // global buffer (L2-resident, read and written with unit stride).
@@ -2540,7 +2670,7 @@ __global__ __launch_bounds__(kBlockThreads, GLRTX_WGWF_WAVES) void pt_render_wgw
         unsigned tid_topup = threadIdx.x;  // (an opaque copy, as below: the lane masks of these tests are then formed here, not held in scalar registers across the whole loop)
         asm volatile("" : "+v"(tid_topup));
         if (wgwf_kernargs()->w.feed_dev != nullptr) {
-            if (tid_topup < 64u) wg_feed_topup(kWgPaths, ctl, cur, work_counter);  // fed launch: the first wave (it copies what the host has published side by side)
+            if (tid_topup < 64u) wg_feed_topup<VOL>(kWgPaths, ctl, cur, work_counter);  // fed launch: the first wave (it copies what the host has published side by side)
         } else if (tid_topup == 0u) {
             // 8x8-pixel tiles (64 consecutive tile-order ids each), frame-major; formed here from the kernarg segment, not once in front of the persistent
             // loop, for the same reason as gss_div below
@@ -2628,7 +2758,7 @@ __global__ __launch_bounds__(kBlockThreads, GLRTX_WGWF_WAVES) void pt_render_wgw
         // waves in the (memory-latency-bound) traverse phase issue ahead of waves of other workgroups that are shading:
         // their loads get going earlier (measured 1-2 %)
         __builtin_amdgcn_s_setprio(GLRTX_PRIO_TRAVERSE);
-        wg_traverse_phase<VINE, FETCH & ~kWgwfAdaptive>(a, w, lds_root, stack, rq, n_rays, &ctl[1], light_bits, rays, rayQ + kWgSuspendAt);
+        wg_traverse_phase<VINE, NODE_FETCH>(a, w, lds_root, stack, rq, n_rays, &ctl[1], light_bits, rays, rayQ + kWgSuspendAt);
         __builtin_amdgcn_s_setprio(GLRTX_PRIO_SHADE);
         PH_STAMP(pt1);
         __syncthreads();  // all hit records of this trip written
@@ -2638,8 +2768,8 @@ __global__ __launch_bounds__(kBlockThreads, GLRTX_WGWF_WAVES) void pt_render_wgw
 
         // ---- shade phase: the live paths; appends go to the other queue pair
         const WgwfKernArgs *ks = wgwf_kernargs();
-        wg_shade_phase(ks->a, ks->w, lds_mats, lds_cam, light_bits, n_paths, rayQ + 2 * ((size_t)(cur ^ 1) * 2 * kWgPaths),
-                       &ctl[2 + (cur ^ 1)], &ctl[4 + (cur ^ 1)], ks->w.set_base(cur, (int)blockIdx.x), ks->w.set_base(cur ^ 1, (int)blockIdx.x), rays, &ctl[10]);
+        wg_shade_phase<VOL>(ks->a, ks->w, lds_mats, lds_cam, light_bits, n_paths, rayQ + 2 * ((size_t)(cur ^ 1) * 2 * kWgPaths),
+                            &ctl[2 + (cur ^ 1)], &ctl[4 + (cur ^ 1)], ks->w.set_base(cur, (int)blockIdx.x), ks->w.set_base(cur ^ 1, (int)blockIdx.x), rays, &ctl[10]);
         PH_STAMP(ps1);
         __syncthreads();  // everyone has read n_rays/n_paths of `cur` and finished appending
         PH_STAMP(ps2);

@@ -14,7 +14,7 @@
 using namespace glrt;
 
 static void usage(const char *exe) {
-    std::printf("usage: %s -i scene.json [-s N] [--max-depth D] [--spp N] [--frames F] [--frames-in-flight B] [--bvh sah|sah-reinsert|sah-gpu|lbvh|sah-levels-cpu|lbvh-cpu|reference] [--order-by-hits] [--out file.png] [--save-every-frame] [--device G | --gpus N | --devices a,b,..] [--extensions] [--whitted] [--enable-volume] [--adaptive THRESHOLD [--min-spp N]]\n"
+    std::printf("usage: %s -i scene.json [-s N] [--max-depth D] [--spp N] [--frames F] [--frames-in-flight B] [--bvh sah|sah-reinsert|sah-gpu|lbvh|sah-levels-cpu|lbvh-cpu|reference] [--order-by-hits] [--out file.png] [--save-every-frame] [--device G | --gpus N | --devices a,b,..] [--extensions] [--whitted] [--enable-volume] [--volume-wavefront] [--adaptive THRESHOLD [--min-spp N]]\n"
                 "  -i, --input             scene description (JSON; schema: SURVEY.md Appendix C)            [required]\n"
                 "  -s, --sample-per-cycle  accepted for compatibility; like the reference (main.cpp:13) it is not read\n"
                 "      --max-depth D       u_maxDepth (default 16, the reference shader's default)\n"
@@ -33,6 +33,8 @@ static void usage(const char *exe) {
                 "      --whitted           with --extensions: Whitted-style transport (direct light at diffuse surfaces, specular bounces only)\n"
                 "      --enable-volume     render the participating media of \"media\" shapes: the reference's ENABLE_VOLUME switch (raytrace.frag:4);\n"
                 "                          their VOL files are read (a missing one is an error only with this flag)\n"
+                "      --volume-wavefront  with --enable-volume: render the media on the wavefront kernel (frames in flight, fed launches; the same image as\n"
+                "                          the persistent megakernel, the default).  --enable-volume --adaptive T turns it on by itself\n"
                 "      --adaptive T        adaptive sampling: bursts of --frames-in-flight frames on the 8x8 tiles whose error is above T only, until no tile is\n"
                 "                          active or --frames frames have been issued; an \"Adaptive:\" line per burst (not with --save-every-frame)\n"
                 "      --min-spp N         with --adaptive: samples every pixel of a tile needs before the tile may retire (default 2, at least 2)\n", exe);
@@ -41,7 +43,7 @@ static void usage(const char *exe) {
 int main(int argc, char **argv) {
     std::string input, out = "output.png";
     int depth = 16, spp = 1, frames = 16, device = -1, in_flight = 0;
-    bool every_frame = false, extensions = false, whitted = false, order_by_hits = false, volume = false, adaptive = false, min_spp_given = false;
+    bool every_frame = false, extensions = false, whitted = false, order_by_hits = false, volume = false, adaptive = false, min_spp_given = false, volume_wavefront = false;
     float adapt_threshold = 0.0f;
     int min_spp = 2;
     std::vector<int> devices;
@@ -66,6 +68,7 @@ int main(int argc, char **argv) {
         else if (a == "--extensions") extensions = true;
         else if (a == "--whitted") { extensions = true; whitted = true; }
         else if (a == "--enable-volume") volume = true;
+        else if (a == "--volume-wavefront") volume_wavefront = true;
         else if (a == "--adaptive") { adaptive = true; adapt_threshold = (float)std::atof(next("--adaptive")); }
         else if (a == "--min-spp") { min_spp = std::atoi(next("--min-spp")); min_spp_given = true; }
         else if (a == "--gpus") { const int n = std::atoi(next("--gpus")); devices.clear(); for (int k = 0; k < n; k++) devices.push_back(k); }
@@ -89,6 +92,7 @@ int main(int argc, char **argv) {
     window->setOutput(out, every_frame);
     window->setOrderChildrenByHits(order_by_hits);
     if (adaptive) window->setAdaptive(adapt_threshold, min_spp);
+    window->setVolumeWavefront(volume_wavefront);
 
     auto scene = std::make_shared<Scene>();
     if (!bvh.empty()) scene->setBvhBuilder(bvh);

@@ -68,6 +68,9 @@ void Window::mainloop(const std::shared_ptr<Scene> &scene_, double fps) {
             if (glrtx_upload_spheres(c, scene->spheres.empty() ? nullptr : scene->spheres.data(), scene->spheres.size() / 5) != GLRTX_OK ||
                 glrtx_set_extensions(c, flags) != GLRTX_OK)
                 GLRT_FatalError("extensions: %s", glrtx_last_error(c));
+            // the volume on the wavefront kernel: asked for, or needed -- adaptive sampling has a tile list only there
+            if ((volumeWavefront_ || (adaptive_ && scene->hasVolume_)) && glrtx_set_volume_wavefront(c, 1) != GLRTX_OK)
+                GLRT_FatalError("glrtx_set_volume_wavefront: %s", glrtx_last_error(c));
         }
         if (!scene->spheres.empty() || scene->hasDielectric_ || scene->whitted_)
             GLRT_Info("extensions: %zu analytic spheres%s%s (not part of the reference)", scene->spheres.size() / 5,

@@ -50,6 +50,9 @@ public:
     // Adaptive sampling (no reference counterpart; glrtx_render_adaptive): bursts of framesInFlight frames, each on the 8x8 tiles that have not converged
     // (error above threshold, or fewer than minSamples samples), until no tile is active or the frame limit is reached; one "Adaptive:" line per burst.
     void setAdaptive(float threshold, int minSamples) { adaptive_ = true; adaptThreshold_ = threshold; adaptMinSamples_ = minSamples; }
+    // Volume scenes on the wavefront kernel (glrtx_set_volume_wavefront on every member): frames in flight, fed launches and adaptive sampling with the volume
+    // on; same images as the persistent megakernel, the default.  Adaptive sampling of a volume scene turns it on by itself.
+    void setVolumeWavefront(bool on) { volumeWavefront_ = on; }
     // wall-clock ms PER FRAME between the last two waits for the device, averaged over the frames issued in between (with one PNG per run: the whole run, cold first
     // launches included; with --save-every-frame: the whole run, PNG writing included).  The device's own time of the last launch is glrtx_stats.kernel_ms_last.
     double lastFrameMs() const { return lastMs_; }
@@ -82,6 +85,7 @@ private:
     bool adaptive_ = false;
     float adaptThreshold_ = 0.0f;
     int adaptMinSamples_ = 2;
+    bool volumeWavefront_ = false;
     bool fallbackNoted_ = false;
     std::string output_ = "output.png";
     double lastMs_ = 0.0;

@@ -74,7 +74,7 @@ EXPORTS = ["glrtx_abi_version", "glrtx_create", "glrtx_destroy", "glrtx_last_err
            "glrtx_group_present_enable", "glrtx_group_present_acquire", "glrtx_group_present_release", "glrtx_group_present_get_stats",
            "glrtx_upload_volume", "glrtx_group_upload_volume", "glrtx_debug_volume_math", "glrtx_debug_volume_lookup",
            "glrtx_render_adaptive", "glrtx_adaptive_active_tiles", "glrtx_read_tile_mask", "glrtx_read_adaptive_half", "glrtx_debug_adaptive_select",
-           "glrtx_group_render_adaptive", "glrtx_group_adaptive_active_tiles", "glrtx_debug_pack_compact"]
+           "glrtx_group_render_adaptive", "glrtx_group_adaptive_active_tiles", "glrtx_debug_pack_compact", "glrtx_set_volume_wavefront"]
 
 _lib = None
 
@@ -168,6 +168,10 @@ def lib():
         L.glrtx_group_adaptive_active_tiles.argtypes = [vp, ip, ip]
         u32p = C.POINTER(C.c_uint32)
         L.glrtx_debug_pack_compact.argtypes = [fp, C.c_size_t] * 5 + [fp, C.c_size_t, ip, u32p, C.c_size_t, fp, C.c_size_t, ip]
+        try:  # (additive to ABI 10: libraries of earlier rounds, which tools/gpu_abx.py loads, lack it)
+            L.glrtx_set_volume_wavefront.argtypes = [vp, C.c_int]
+        except AttributeError:
+            pass
         _lib = L
     return _lib
 
@@ -342,6 +346,11 @@ class Device:
         glTexSubImage3D reads them -- and the bbox from the scene.  density_max defaults to the density grid's maximum (the reference takes
         the maximum over the whole file).  density None removes the volume.  Rendering needs EXT_VOLUME (set_extensions) as well."""
         self._ck(_upload_volume(self.L.glrtx_upload_volume, self.h, density, temperature, bbox_min, bbox_max, density_max))
+
+    def set_volume_wavefront(self, enable: bool):
+        """True: volume launches (EXT_VOLUME alone) run on the wavefront kernel's V form -- frames in flight, fed launches, the present ring and
+        render_adaptive with the volume on; bit-identical to the persistent megakernel (the default).  GLRTX_VOLUME_WAVEFRONT=0/1 overrides it per launch."""
+        self._ck(self.L.glrtx_set_volume_wavefront(self.h, int(enable)))
 
     def set_partition(self, rank, world, stripe_rows=16):
         self._ck(self.L.glrtx_set_partition(self.h, rank, world, stripe_rows))
