@@ -98,6 +98,20 @@ int glrt_bvh_add_shadow_hits(uint32_t *tri_hits, size_t n_tri, const float *tri,
  * -- GLRT_HOST_EDEPTH when the optimised tree would be deeper than the 64-entry traversal stack allows: `nodes` is then left exactly as it came in.  Apply glrt_bvh_lights_first AFTER it. */
 int glrt_bvh_reinsert(float *nodes, size_t n_nodes, int max_passes, int *max_depth_out, double *cost_out);
 
+/* Refit: new boxes for a wire-format tree (9 floats per node, root = node 0) after its triangles' vertices moved; topology, child refs and leaf triangles untouched.
+ * Rule, over the nodes reachable from node 0 (the others are left as they are):
+ *   leaf              the componentwise min / max of its triangle's three vertex positions;
+ *   fork              the componentwise min / max of its present children's boxes (a fork with one child takes that child's box);
+ *   fork, no children keeps its box.
+ * Min and max are taken in a TOTAL order on float bit patterns, not with `<`: the ordered-integer key (all bits flipped when the sign is set, else the sign bit
+ * set), so -0 < +0 and NaNs lie beyond +-inf by bit pattern, and the chosen value is kept bit for bit (denormals too).  A box is then a function of the set of
+ * positions under it, whatever the association -- the device refit (glrtx_update_vertices, include/glrtx.h) folds in parallel and lands on the same bits.
+ * For trees of the builders above (coordinates inside +-1e8) refitting unchanged vertices gives back every reachable fork box numerically (==; -0 and +0 may
+ * trade places); glrt_bvh_build_chain's forks, which carry the global box by design, become tight suffix boxes.
+ * Same checks and codes as the builders: GLRT_HOST_EINVAL for NULL / empty input or a malformed tree (a child or leaf triangle out of range, a node reached
+ * twice), GLRT_HOST_EINDEX for a triangle with a vertex index out of range.  On error `nodes` is unchanged. */
+int glrt_bvh_refit(const float *vert, size_t n_vert, const float *tri, size_t n_tri, float *nodes, size_t n_nodes);
+
 void glrt_look_at(const float eye[3], const float center[3], const float up[3], float out[16]);
 void glrt_perspective(float fovy_deg, float aspect, float z_near, float z_far, float out[16]);
 void glrt_mat4_mul(const float a[16], const float b[16], float out[16]);

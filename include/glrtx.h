@@ -140,6 +140,32 @@ int glrtx_upload_scene(glrtx_ctx *ctx, const float *vert, size_t n_vert, const f
                        const float *mat, size_t n_mat, const float *light, size_t n_light, const float *bvh,
                        size_t n_nodes);
 
+/* Moving geometry without a rebuild.  New positions and normals for the uploaded scene's vertices (wire format, GLRT_VERTEX_FLOATS = 15 floats each; n_vert
+ * must be the count the scene was uploaded with); triangles, materials, lights' vertex indices and the tree's topology stay.  Every geometry-derived device
+ * buffer is rewritten on the device -- leaf and light records, normals, the fork boxes of both node layouts, the vine list, the root box -- so that the scene is
+ * byte for byte what glrtx_upload_scene(new vertices, the tree refitted by glrt_bvh_refit, include/glrt_host.h) would upload.  No host repack.
+ *   glrtx_update_vertices         host memory
+ *   glrtx_update_vertices_device  device memory on the context's device, read on the context's stream (glrtx_set_stream): the caller orders its producer
+ *                                 there, or synchronises
+ * The refit runs behind every launch of this context that may still read the scene (an open fed launch is sealed, as glrtx_upload_scene does), and the call
+ * returns when it has run (the root box is a kernel argument and is read back): every later launch sees the new scene.  The accumulator is NOT cleared
+ * (glrtx_clear is the caller's choice); adaptive state, spheres, volume and presentation are untouched.  GLRTX_EINVAL -- no scene, NULL vertices, a count
+ * other than the uploaded one -- leaves the scene unchanged. */
+int glrtx_update_vertices(glrtx_ctx *ctx, const float *vert, size_t n_vert);
+int glrtx_update_vertices_device(glrtx_ctx *ctx, const void *dev_vert, size_t n_vert);
+
+/* Test hook: a copy of one device scene buffer as the kernels read it.  which: GLRTX_SCENE_NODES (the 64-byte node array, leaf records in reverse id
+ * order then the forks), _CNODES (the compact records), _NRMS, _LIGHTS, _VINE (empty unless the tree is a vine), _ROOT (48 bytes: root box min {x, y, z, 0},
+ * max {x, y, z, 0}, then the ints root_boxed, vine_uniform, root ref, vine records).  *bytes_out (may be NULL) gets the size; dst NULL asks for the size only.
+ * Synchronises the context's stream. */
+#define GLRTX_SCENE_NODES 0
+#define GLRTX_SCENE_CNODES 1
+#define GLRTX_SCENE_NRMS 2
+#define GLRTX_SCENE_LIGHTS 3
+#define GLRTX_SCENE_VINE 4
+#define GLRTX_SCENE_ROOT 5
+int glrtx_debug_read_scene(glrtx_ctx *ctx, int which, void *dst, size_t capacity_bytes, size_t *bytes_out);
+
 /* Host-only (no device, no ctx): run the validation and repacking glrtx_upload_scene performs and
  * report the interior-node count and the traversal stack entries the BVH needs.  On failure the
  * message is available from glrtx_last_error(NULL). */
@@ -413,6 +439,8 @@ int glrtx_group_size(const glrtx_group *grp);
 glrtx_ctx *glrtx_group_ctx(glrtx_group *grp, int i);
 int glrtx_group_upload_scene(glrtx_group *grp, const float *vert, size_t n_vert, const float *tri, size_t n_tri, const float *mat,
                              size_t n_mat, const float *light, size_t n_light, const float *bvh, size_t n_nodes);
+/* glrtx_update_vertices on every member. */
+int glrtx_group_update_vertices(glrtx_group *grp, const float *vert, size_t n_vert);
 /* glrtx_upload_volume on every member (the grids are replicated, like the scene). */
 int glrtx_group_upload_volume(glrtx_group *grp, const float *density, const float *temperature, int nx, int ny, int nz, const float bbox_min[3],
                               const float bbox_max[3], float density_max);

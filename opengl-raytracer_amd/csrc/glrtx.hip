@@ -21,6 +21,7 @@
 #include "pt_kernel.hip.h"
 #include "lbvh.hip.h"
 #include "sahl.hip.h"
+#include "refit.hip.h"
 static_assert(glrtx::lbvh::kRotationPasses == GLRT_LBVH_ROTATION_PASSES, "device and CPU LBVH statements must run the same rotation sweeps");
 static_assert(glrtx::lbvh::kRebuildLeaves == GLRT_LBVH_REBUILD_LEAVES, "device and CPU LBVH statements must rebuild the same subtrees");
 
@@ -132,6 +133,15 @@ struct glrtx_ctx {
     bool state_used = false;
 
     std::vector<int> leaf_tri;  // leaf record k of the uploaded scene -> wire triangle (glrtx_hit_histogram)
+    // The refit plan (glrtx_update_vertices; refit.hip.h), kept beside the scene from its upload: the integer tables (`ints`), the wire boxes as keys with the
+    // arrival counters and the read-back words (`keys`), a staging buffer for host vertices; `a`: the kernels' arguments with every pointer set
+    struct Refit {
+        DevBuf ints, keys, vert;
+        refit::Args a{};
+        size_t n_vert = 0;
+        size_t bytes[5] = {0, 0, 0, 0, 0};  // the scene buffers' sizes as uploaded: nodes, cnodes, nrms, lights, vine (glrtx_debug_read_scene)
+        hipEvent_t slot_ev = nullptr;      // recorded on each pipe slot's stream: the refit starts behind every launch that may still read the scene
+    } rf;
     unsigned *hit_hist_dev = nullptr;  // set only inside glrtx_hit_histogram
 
     // Presentation (glrtx_present_enable): frame seq of the ring goes to image seq % ring -- device image (written by the presenting pass on the context's stream),
@@ -293,6 +303,11 @@ struct Packed {
     // The compact node array (pack_compact): 48-byte records at breadth-first positions, and the rank table that locates a fork's children
     std::vector<float4> cnodes;  // 3 float4 per position
     std::vector<uint2> cranks;   // per 32 positions {fork bits, forks in front of the group}
+    // What the refit (glrtx_update_vertices, refit.hip.h) needs beside the buffers: leaf record k -> its wire node; fork record r -> the wire forks whose boxes
+    // fill its left / right slot (-1: a leaf child or none); compact position -> its ref in the 64-byte layout; the vine's forks and leaves in list order
+    std::vector<int> leaf_wire, cpos_ref, vine_fork, vine_leaf;
+    std::vector<int2> fork_slot;
+    bool tree = false;  // a tree was packed (root_ref was not REF_ABSENT)
 };
 
 // The compact node array, beside the 64-byte one.  Positions are numbered breadth-first from the root fork (position 0); the
@@ -307,7 +322,7 @@ void pack_compact(Packed &P) {
     P.cranks.clear();
     std::vector<int> ref;  // position -> ref in the 64-byte layout
     ref.push_back(P.root_ref);
-    for (size_t q = 0; q < ref.size(); q++) {
+    for (size_t q = 0; q < ref.size(); q++) {  // (P.cpos_ref keeps the list for the refit)
         const int r = ref[q];
         if (r < 0) continue;
         int l, rr;
@@ -329,6 +344,7 @@ void pack_compact(Packed &P) {
     }
     next_pos.resize(ref.size(), REF_FIN);
     const size_t n = ref.size();
+    P.cpos_ref = ref;
     P.cnodes.assign(3 * n, make_float4(0.f, 0.f, 0.f, 0.f));
     P.cranks.assign((n + 31) / 32, make_uint2(0u, 0u));
     unsigned forks = 0;
@@ -450,6 +466,7 @@ int pack_scene(glrtx_ctx *c, std::string *err_out, Packed &P, const float *vert,
             if ((size_t)tf >= n_tri) { rc = pfail(c, err_out, GLRTX_ESCENE, "BVH leaf %d: triangle %g out of range", n, tf); return 0; }
             leaf_tri.push_back((int)tf);
             leaf_next.push_back(REF_FIN);
+            P.leaf_wire.push_back(n);
             ref_of[n] = ~(int)leaf_tri.size();  // id = record count so far (ids start at 1)
             need[n] = 0;
             return ref_of[n];
@@ -485,6 +502,7 @@ int pack_scene(glrtx_ctx *c, std::string *err_out, Packed &P, const float *vert,
                 ref_of[n] = (int)(forks.size() / 4);
                 // both children start out absent: the never-hit record (index -1) behind an infinite box (see put_box)
                 for (int k = 0; k < 4; k++) { const float e = (k & 1) ? kInf : -kInf; forks.push_back(make_float4(e, e, e, as_float(-1))); }
+                P.fork_slot.push_back(make_int2(-1, -1));
                 // forks are numbered in the order the traversal meets them (children.y first, raytrace.frag:299-307):
                 // the first-visited child's record directly follows its parent's
                 f.stage = 1;
@@ -508,6 +526,7 @@ int pack_scene(glrtx_ctx *c, std::string *err_out, Packed &P, const float *vert,
             // wire format: its own box goes here like any fork's.
             auto put_box = [&](int slot, int child) {
                 if (!is_fork(child)) return;
+                (slot ? P.fork_slot[fi].y : P.fork_slot[fi].x) = child;
                 const float *b = bvh + 9 * (size_t)child;
                 forks[4 * fi + slot].x = b[0]; forks[4 * fi + slot].y = b[1]; forks[4 * fi + slot].z = b[2];
                 forks[4 * fi + slot + 1].x = b[3]; forks[4 * fi + slot + 1].y = b[4]; forks[4 * fi + slot + 1].z = b[5];
@@ -568,7 +587,9 @@ int pack_scene(glrtx_ctx *c, std::string *err_out, Packed &P, const float *vert,
                 const float *b = bvh + 9 * (size_t)n;
                 if (std::memcmp(b, bvh, 6 * sizeof(float)) != 0) uniform = false;
                 rec(b, b + 3, ~ref_of[r]);
-                if (!is_fork(l)) { rec(all_lo, all_hi, ~ref_of[l]); break; }
+                P.vine_fork.push_back(n);
+                P.vine_leaf.push_back(r);
+                if (!is_fork(l)) { rec(all_lo, all_hi, ~ref_of[l]); P.vine_leaf.push_back(l); break; }
                 n = l;
             }
             if (is_vine && v.size() == 4 * leaf_tri.size()) {
@@ -605,6 +626,9 @@ int pack_scene(glrtx_ctx *c, std::string *err_out, Packed &P, const float *vert,
         }
         for (int f = 0; f < nf; f++) if (newid[f] < 0) { newid[f] = (int)order.size(); order.push_back(f); }
         std::vector<float4> re(forks.size());
+        std::vector<int2> slot_re(P.fork_slot.size());
+        for (int f = 0; f < nf; f++) slot_re[(size_t)newid[f]] = P.fork_slot[(size_t)f];
+        P.fork_slot.swap(slot_re);
         for (int f = 0; f < nf; f++) {
             for (int k = 0; k < 4; k++) re[4 * (size_t)newid[f] + k] = forks[4 * (size_t)f + k];
             for (int k = 0; k < 2; k++) {
@@ -615,8 +639,11 @@ int pack_scene(glrtx_ctx *c, std::string *err_out, Packed &P, const float *vert,
         forks.swap(re);
         root_ref = newid[root_ref];
     }
+    P.tree = root_ref != REF_ABSENT;
+    if (P.vine.empty()) { P.vine_fork.clear(); P.vine_leaf.clear(); }
     if (root_ref == REF_ABSENT) {  // empty scene: one childless fork, every ray misses
         forks.clear();
+        P.fork_slot.assign(1, make_int2(-1, -1));
         for (int k = 0; k < 4; k++) { const float e = (k & 1) ? kInf : -kInf; forks.push_back(make_float4(e, e, e, as_float(-1))); }
         root_ref = 0;
         stack_need = 1;  // a ray that passes the (degenerate) root box pushes the left never-hit record
@@ -646,6 +673,83 @@ int ensure(glrtx_ctx *c, DevBuf &b, size_t bytes) {
     dev_free(b);
     HIP_TRY(c, hipMalloc(&b.p, std::max<size_t>(bytes, 64)));
     b.bytes = std::max<size_t>(bytes, 64);
+    return GLRTX_OK;
+}
+
+// The refit plan of a packed scene (glrtx_ctx::Refit), uploaded next to it.  Everything in it is fixed by the topology: which vertices each leaf and light
+// record reads, the reachable wire tree (parent, children, the forks without children), where each wire box lands in the packed layouts.
+int refit_plan_upload(glrtx_ctx *c, const Packed &P, const float *tri, const float *light, size_t n_light, const float *bvh, size_t n_nodes, size_t n_vert,
+                      const size_t bytes[5]) {
+    const size_t n_wire = P.tree ? n_nodes : 0, n_leaf = P.leaf_wire.size();
+    std::vector<int> parent(n_wire, -1), extra;
+    std::vector<int2> kids(n_wire, make_int2(-1, -1));
+    if (n_wire) {  // (pack_scene has checked the tree)
+        std::vector<int> st{0};
+        while (!st.empty()) {
+            const int n = st.back();
+            st.pop_back();
+            const float *b = bvh + 9 * (size_t)n;
+            if (!(b[8] < 0.0f)) continue;
+            kids[n].x = b[6] >= 0.0f ? (int)b[6] : -1;
+            kids[n].y = b[7] >= 0.0f ? (int)b[7] : -1;
+            if (kids[n].x < 0 && kids[n].y < 0) extra.push_back(n);
+            for (int ch : {kids[n].x, kids[n].y})
+                if (ch >= 0) { parent[ch] = n; st.push_back(ch); }
+        }
+    }
+    std::vector<int> ints;
+    auto section = [&](size_t words) { while (ints.size() % 4) ints.push_back(0); const size_t at = ints.size(); ints.resize(at + words, -1); return at; };
+    const size_t o_leaf = section(4 * n_leaf);
+    for (size_t k = 0; k < n_leaf; k++) {
+        for (int j = 0; j < 3; j++) ints[o_leaf + 4 * k + j] = (int)tri[4 * (size_t)P.leaf_tri[k] + j];
+        ints[o_leaf + 4 * k + 3] = P.leaf_wire[k];
+    }
+    const size_t o_extra = section(extra.size());
+    std::copy(extra.begin(), extra.end(), ints.begin() + o_extra);
+    const size_t o_light = section(4 * n_light);
+    for (size_t l = 0; l < n_light; l++)
+        for (int j = 0; j < 3; j++) ints[o_light + 4 * l + j] = (int)light[4 * l + j];
+    const size_t o_parent = section(n_wire);
+    std::copy(parent.begin(), parent.end(), ints.begin() + o_parent);
+    const size_t o_kids = section(2 * n_wire);
+    std::memcpy(&ints[o_kids], kids.data(), n_wire * sizeof(int2));
+    const size_t o_slot = section(2 * P.fork_slot.size());
+    std::memcpy(&ints[o_slot], P.fork_slot.data(), P.fork_slot.size() * sizeof(int2));
+    const size_t o_cpos = section(P.cpos_ref.size());
+    for (size_t q = 0; q < P.cpos_ref.size(); q++) ints[o_cpos + q] = P.cpos_ref[q] >= 0 ? P.cpos_ref[q] : -1;
+    const size_t o_vf = section(P.vine_fork.size());
+    std::copy(P.vine_fork.begin(), P.vine_fork.end(), ints.begin() + o_vf);
+    const size_t o_vl = section(P.vine_leaf.size());
+    std::copy(P.vine_leaf.begin(), P.vine_leaf.end(), ints.begin() + o_vl);
+    // keys: the wire boxes (the uploaded ones: a fork without children keeps its box), the arrival counters (0), eight read-back words
+    std::vector<unsigned> keys(7 * n_wire + 8, 0u);
+    for (size_t n = 0; n < n_wire; n++)
+        for (int j = 0; j < 6; j++) {
+            unsigned u; std::memcpy(&u, &bvh[9 * n + j], 4);
+            keys[6 * n + j] = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+        }
+    glrtx_ctx::Refit &R = c->rf;
+    if (int rc = dev_upload(c, R.ints, ints.data(), ints.size() * sizeof(int))) return rc;
+    if (int rc = dev_upload(c, R.keys, keys.data(), keys.size() * sizeof(unsigned))) return rc;
+    if (!R.slot_ev) HIP_TRY(c, hipEventCreateWithFlags(&R.slot_ev, hipEventDisableTiming));
+    const int *I = (const int *)R.ints.p;
+    unsigned *K = (unsigned *)R.keys.p;
+    refit::Args &a = R.a;
+    a = refit::Args{};
+    a.leaf = (const int4 *)(I + o_leaf); a.n_leaf = (int)n_leaf;
+    a.extra = I + o_extra; a.n_extra = (int)extra.size();
+    a.light = (const int4 *)(I + o_light); a.n_light = (int)n_light;
+    a.parent = I + o_parent; a.kids = (const int2 *)(I + o_kids);
+    a.box = K; a.cnt = K + 6 * n_wire; a.out = K + 7 * n_wire;
+    a.climb = P.n_vine > 0 ? 0 : 1;
+    a.nodes = (uint4 *)c->forks.p; a.n_ids = (int)(P.tris.size() / 4);
+    a.nrms = (uint4 *)c->nrms.p; a.lights = (uint4 *)c->lights.p;
+    a.slot = (const int2 *)(I + o_slot); a.n_fork = (int)P.fork_slot.size();
+    a.cpos = I + o_cpos; a.n_cpos = (int)P.cpos_ref.size(); a.cnodes = (uint4 *)c->cnodes.p;
+    a.vine_fork = I + o_vf; a.vine_leaf = I + o_vl; a.n_vine = P.n_vine; a.vine_main = P.vine_main; a.vine = (uint4 *)c->vine.p;
+    a.root_boxed = P.tree && P.root_boxed ? 1 : 0;
+    R.n_vert = n_vert;
+    for (int k = 0; k < 5; k++) R.bytes[k] = bytes[k];
     return GLRTX_OK;
 }
 
@@ -1437,6 +1541,8 @@ void glrtx_destroy(glrtx_ctx *c) {
     dev_free(c->adHalf); dev_free(c->adMask); dev_free(c->adList); dev_free(c->adCount);
     dev_free(c->wfState); dev_free(c->wfQ); dev_free(c->wfSeeds); dev_free(c->wfPlanes);
     dev_free(c->bvhVert); dev_free(c->bvhTri); dev_free(c->bvhNodes);
+    dev_free(c->rf.ints); dev_free(c->rf.keys); dev_free(c->rf.vert);
+    if (c->rf.slot_ev) (void)hipEventDestroy(c->rf.slot_ev);
     if (c->bvhWs.p) { (void)hipFree(c->bvhWs.p); c->bvhWs.p = nullptr; c->bvhWs.bytes = 0; }
     for (auto &r : c->ring) {
         if (r.ev0) (void)hipEventDestroy(r.ev0);
@@ -1480,6 +1586,10 @@ int glrtx_upload_scene(glrtx_ctx *c, const float *vert, size_t n_vert, const flo
     if ((rc = dev_upload(c, c->mats, mats.data(), mats.size() * sizeof(float4)))) return rc;
     if ((rc = dev_upload(c, c->lights, lights.data(), lights.size() * sizeof(float4)))) return rc;
     if (!P.vine.empty() && (rc = dev_upload(c, c->vine, P.vine.data(), P.vine.size() * sizeof(float4)))) return rc;
+    c->have_scene = false;  // (until the plan is in place too)
+    const size_t scene_bytes[5] = {nodes.size() * sizeof(float4), P.cnodes.size() * sizeof(float4), nrms.size() * sizeof(float4), lights.size() * sizeof(float4),
+                                   P.vine.size() * sizeof(float4)};
+    if ((rc = refit_plan_upload(c, P, tri, light, n_light, bvh, n_nodes, n_vert, scene_bytes))) return rc;
 
     DevScene &sc = c->sc;
     sc.forks = (const float4 *)c->forks.p + tri_f4;
@@ -1513,6 +1623,90 @@ int glrtx_upload_scene(glrtx_ctx *c, const float *vert, size_t n_vert, const flo
     c->st.stack_entries = stack_need;
     c->st.lds_bytes = lds_bytes_for(sc);
     c->st.n_tri = c->n_tri; c->st.n_fork = c->n_fork; c->st.n_mat = c->n_mat; c->st.n_light = c->n_light;
+    return GLRTX_OK;
+}
+
+namespace {
+
+// The refit (refit.hip.h) from device vertices on the context's stream, behind every launch that may still read the scene; blocks until it has run and
+// the root box and vine_uniform -- kernel arguments -- are read back.  Launches issued after it are therefore ordered after it, on any stream.
+int refit_run(glrtx_ctx *c, const void *dev_vert) {
+    glrtx_ctx::Refit &R = c->rf;
+    for (auto &sl : c->pipe)
+        if (sl.stream && sl.used) {
+            HIP_TRY(c, hipEventRecord(R.slot_ev, sl.stream));
+            HIP_TRY(c, hipStreamWaitEvent(c->stream, R.slot_ev, 0));
+        }
+    refit::Args a = R.a;
+    a.vert = (const unsigned *)dev_vert;
+    const int n1 = std::max(1, a.n_leaf + a.n_extra + a.n_light);
+    hipLaunchKernelGGL(refit::k_refit_leaves, dim3((n1 + refit::kBlock - 1) / refit::kBlock), dim3(refit::kBlock), 0, c->stream, a);
+    HIP_TRY(c, hipGetLastError());
+    if (a.n_vine > 0) {
+        hipLaunchKernelGGL(refit::k_refit_vine, dim3(1), dim3(refit::kVineBlock), 0, c->stream, a);
+        HIP_TRY(c, hipGetLastError());
+    }
+    const int n3 = 2 * a.n_fork + a.n_cpos + a.n_vine + 1;
+    hipLaunchKernelGGL(refit::k_refit_scatter, dim3((n3 + refit::kBlock - 1) / refit::kBlock), dim3(refit::kBlock), 0, c->stream, a);
+    HIP_TRY(c, hipGetLastError());
+    unsigned out[8];
+    HIP_TRY(c, hipMemcpyAsync(out, a.out, sizeof out, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    float f[6];
+    std::memcpy(f, out, sizeof f);
+    c->sc.root_lo = make_float4(f[0], f[1], f[2], 0.f);
+    c->sc.root_hi = make_float4(f[3], f[4], f[5], 0.f);
+    c->sc.vine_uniform = a.n_vine > 0 && out[6] != 0u ? 1 : 0;
+    return GLRTX_OK;
+}
+
+int update_check(glrtx_ctx *c, const void *vert, size_t n_vert, const char *fn) {
+    if (!c) return GLRTX_EINVAL;
+    if (!c->have_scene) return fail(c, GLRTX_EINVAL, "%s: no scene uploaded", fn);
+    if (!vert) return fail(c, GLRTX_EINVAL, "%s: NULL vertices", fn);
+    if (n_vert != c->rf.n_vert) return fail(c, GLRTX_EINVAL, "%s: %zu vertices, the scene was uploaded with %zu", fn, n_vert, c->rf.n_vert);
+    return GLRTX_OK;
+}
+
+}  // namespace
+
+int glrtx_update_vertices(glrtx_ctx *c, const float *vert, size_t n_vert) {
+    if (int rc = update_check(c, vert, n_vert, "glrtx_update_vertices")) return rc;
+    seal_feed(c);
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t bytes = n_vert * 15 * sizeof(float);
+    if (int rc = ensure(c, c->rf.vert, bytes)) return rc;
+    HIP_TRY(c, hipMemcpyAsync(c->rf.vert.p, vert, bytes, hipMemcpyHostToDevice, c->stream));
+    return refit_run(c, c->rf.vert.p);
+}
+
+int glrtx_update_vertices_device(glrtx_ctx *c, const void *dev_vert, size_t n_vert) {
+    if (int rc = update_check(c, dev_vert, n_vert, "glrtx_update_vertices_device")) return rc;
+    seal_feed(c);
+    HIP_TRY(c, hipSetDevice(c->device));
+    return refit_run(c, dev_vert);
+}
+
+int glrtx_debug_read_scene(glrtx_ctx *c, int which, void *dst, size_t capacity_bytes, size_t *bytes_out) {
+    if (!c) return GLRTX_EINVAL;
+    if (!c->have_scene) return fail(c, GLRTX_EINVAL, "glrtx_debug_read_scene: no scene uploaded");
+    if (which < 0 || which > GLRTX_SCENE_ROOT) return fail(c, GLRTX_EINVAL, "glrtx_debug_read_scene: no buffer %d", which);
+    const void *src[5] = {c->forks.p, c->cnodes.p, c->nrms.p, c->lights.p, c->vine.p};
+    int32_t root[12];
+    size_t n = which == GLRTX_SCENE_ROOT ? sizeof root : c->rf.bytes[which];
+    if (bytes_out) *bytes_out = n;
+    if (!dst) return GLRTX_OK;
+    if (capacity_bytes < n) return fail(c, GLRTX_EINVAL, "glrtx_debug_read_scene: %zu bytes, room for %zu", n, capacity_bytes);
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (which == GLRTX_SCENE_ROOT) {
+        std::memcpy(&root[0], &c->sc.root_lo, 16);
+        std::memcpy(&root[4], &c->sc.root_hi, 16);
+        root[8] = c->sc.root_boxed; root[9] = c->sc.vine_uniform; root[10] = c->sc.root_ref; root[11] = c->rf.a.n_vine;
+        std::memcpy(dst, root, sizeof root);
+    } else if (n) {
+        HIP_TRY(c, hipMemcpy(dst, src[which], n, hipMemcpyDeviceToHost));
+    }
     return GLRTX_OK;
 }
 
@@ -2698,6 +2892,13 @@ int glrtx_group_upload_scene(glrtx_group *g, const float *vert, size_t n_vert, c
     if (!g) return GLRTX_EINVAL;
     for (size_t i = 0; i < g->ctx.size(); i++)  // the scene is replicated: <= 27 MB even for 100k triangles
         if (int rc = gsub(g, (int)i, glrtx_upload_scene(g->ctx[i], vert, n_vert, tri, n_tri, mat, n_mat, light, n_light, bvh, n_nodes))) return rc;
+    return GLRTX_OK;
+}
+
+int glrtx_group_update_vertices(glrtx_group *g, const float *vert, size_t n_vert) {
+    if (!g) return GLRTX_EINVAL;
+    for (size_t i = 0; i < g->ctx.size(); i++)
+        if (int rc = gsub(g, (int)i, glrtx_update_vertices(g->ctx[i], vert, n_vert))) return rc;
     return GLRTX_OK;
 }
 

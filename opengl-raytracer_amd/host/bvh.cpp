@@ -1327,4 +1327,76 @@ int glrt_bvh_build_reference(const float *vert, size_t n_vert, const float *tri,
     return deepest < 63 ? GLRT_HOST_OK : GLRT_HOST_EDEPTH;
 }
 
+
+// The refit rule of include/glrt_host.h, stated once (the device refit, csrc/refit.hip.h, reproduces it bit for bit).  Boxes are folded on ordered-integer keys, so a
+// box is a function of the SET of positions under it: -0 < +0, NaNs beyond +-inf by bit pattern, every bit kept (denormals included).
+namespace {
+inline uint32_t refit_key(float f) { uint32_t u; std::memcpy(&u, &f, 4); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
+inline float refit_unkey(uint32_t k) { const uint32_t u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k; float f; std::memcpy(&f, &u, 4); return f; }
+}  // namespace
+
+int glrt_bvh_refit(const float *vert, size_t n_vert, const float *tri, size_t n_tri, float *nodes, size_t n_nodes) {
+    if (!vert || !tri || !nodes || n_tri == 0 || n_nodes == 0) return GLRT_HOST_EINVAL;
+    for (size_t t = 0; t < n_tri; t++)  // (the builders' check: load_prims)
+        for (int k = 0; k < 3; k++) {
+            const float fi = tri[4 * t + k];
+            if (!(fi >= 0.f) || (size_t)fi >= n_vert) return GLRT_HOST_EINDEX;
+        }
+    std::vector<uint32_t> key(6 * n_nodes);  // the new boxes of the reachable nodes, as keys {lo xyz, hi xyz}
+    std::vector<char> seen(n_nodes, 0);
+    auto is_fork = [&](size_t n) { return nodes[9 * n + 8] < 0.0f; };
+    auto child = [&](size_t n, int k, long &out) {  // k = 0 children.x, 1 children.y; -1 absent
+        const float f = nodes[9 * n + 6 + k];
+        if (!(f >= 0.0f)) { out = -1; return true; }
+        if ((size_t)f >= n_nodes) return false;
+        out = (long)f;
+        return true;
+    };
+    struct Frame { size_t node; bool expanded; };
+    std::vector<Frame> st{{0, false}};
+    while (!st.empty()) {
+        Frame &f = st.back();
+        const size_t n = f.node;
+        uint32_t *b = &key[6 * n];
+        long kid[2] = {-1, -1};
+        if (!f.expanded) {
+            if (seen[n]) return GLRT_HOST_EINVAL;  // not a tree
+            seen[n] = 1;
+            if (!is_fork(n)) {  // leaf box: its triangle's three positions
+                const float tf = nodes[9 * n + 8];
+                if (!(tf >= 0.0f) || (size_t)tf >= n_tri) return GLRT_HOST_EINVAL;
+                for (int a = 0; a < 3; a++) { b[a] = 0xffffffffu; b[3 + a] = 0u; }
+                for (int k = 0; k < 3; k++) {
+                    const float *p = vert + GLRT_VERTEX_FLOATS * (size_t)tri[4 * (size_t)tf + k];
+                    for (int a = 0; a < 3; a++) { b[a] = std::min(b[a], refit_key(p[a])); b[3 + a] = std::max(b[3 + a], refit_key(p[a])); }
+                }
+                st.pop_back();
+                continue;
+            }
+            if (!child(n, 0, kid[0]) || !child(n, 1, kid[1])) return GLRT_HOST_EINVAL;
+            f.expanded = true;
+            for (int k = 0; k < 2; k++)
+                if (kid[k] >= 0) st.push_back({(size_t)kid[k], false});
+            continue;
+        }
+        child(n, 0, kid[0]);
+        child(n, 1, kid[1]);
+        if (kid[0] < 0 && kid[1] < 0) {  // a fork with no children keeps its box
+            for (int a = 0; a < 6; a++) b[a] = refit_key(nodes[9 * n + a]);
+        } else {  // the present children's boxes (one child: its box)
+            for (int a = 0; a < 3; a++) { b[a] = 0xffffffffu; b[3 + a] = 0u; }
+            for (int k = 0; k < 2; k++) {
+                if (kid[k] < 0) continue;
+                const uint32_t *c = &key[6 * (size_t)kid[k]];
+                for (int a = 0; a < 3; a++) { b[a] = std::min(b[a], c[a]); b[3 + a] = std::max(b[3 + a], c[3 + a]); }
+            }
+        }
+        st.pop_back();
+    }
+    for (size_t n = 0; n < n_nodes; n++)
+        if (seen[n])
+            for (int a = 0; a < 6; a++) nodes[9 * n + a] = refit_unkey(key[6 * n + a]);
+    return GLRT_HOST_OK;
+}
+
 }  // extern "C"

@@ -74,7 +74,10 @@ EXPORTS = ["glrtx_abi_version", "glrtx_create", "glrtx_destroy", "glrtx_last_err
            "glrtx_group_present_enable", "glrtx_group_present_acquire", "glrtx_group_present_release", "glrtx_group_present_get_stats",
            "glrtx_upload_volume", "glrtx_group_upload_volume", "glrtx_debug_volume_math", "glrtx_debug_volume_lookup",
            "glrtx_render_adaptive", "glrtx_adaptive_active_tiles", "glrtx_read_tile_mask", "glrtx_read_adaptive_half", "glrtx_debug_adaptive_select",
-           "glrtx_group_render_adaptive", "glrtx_group_adaptive_active_tiles", "glrtx_debug_pack_compact", "glrtx_set_volume_wavefront"]
+           "glrtx_group_render_adaptive", "glrtx_group_adaptive_active_tiles", "glrtx_debug_pack_compact", "glrtx_set_volume_wavefront",
+           "glrtx_update_vertices", "glrtx_update_vertices_device", "glrtx_group_update_vertices", "glrtx_debug_read_scene"]
+
+SCENE_BUFFERS = ("nodes", "cnodes", "nrms", "lights", "vine", "root")  # glrtx_debug_read_scene's `which`, in order (GLRTX_SCENE_*)
 
 _lib = None
 
@@ -168,6 +171,10 @@ def lib():
         L.glrtx_group_adaptive_active_tiles.argtypes = [vp, ip, ip]
         u32p = C.POINTER(C.c_uint32)
         L.glrtx_debug_pack_compact.argtypes = [fp, C.c_size_t] * 5 + [fp, C.c_size_t, ip, u32p, C.c_size_t, fp, C.c_size_t, ip]
+        L.glrtx_update_vertices.argtypes = [vp, fp, C.c_size_t]
+        L.glrtx_update_vertices_device.argtypes = [vp, vp, C.c_size_t]
+        L.glrtx_group_update_vertices.argtypes = [vp, fp, C.c_size_t]
+        L.glrtx_debug_read_scene.argtypes = [vp, C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t)]
         try:  # (additive to ABI 10: libraries of earlier rounds, which tools/gpu_abx.py loads, lack it)
             L.glrtx_set_volume_wavefront.argtypes = [vp, C.c_int]
         except AttributeError:
@@ -259,6 +266,31 @@ def adaptive_select(accum, half, threshold, min_samples):
     return mask, err, lst[:n.value].copy()
 
 
+def _host_vertices(v):
+    """A numpy vertex array for glrtx_update_vertices: float32, shape (n, 15) or flat (or the scene's (n * 5, 3) texels).  Returns (array, n)."""
+    a = np.asarray(v)
+    if a.dtype != np.float32:
+        raise TypeError(f"update_vertices: float32 vertices expected, got {a.dtype}")
+    if a.size % 15 or (a.ndim == 2 and a.shape[1] not in (3, 15)) or a.ndim > 2:
+        raise ValueError(f"update_vertices: shape {a.shape} is not (n, 15) or flat n * 15")
+    a = np.ascontiguousarray(a)
+    return a, a.size // 15
+
+
+def _device_vertices(t, device_index):
+    """A torch tensor for glrtx_update_vertices_device: contiguous float32 on the context's GPU, shape (n, 15) or flat.  Returns (pointer, n)."""
+    import torch
+    if t.dtype != torch.float32:
+        raise TypeError(f"update_vertices: float32 vertices expected, got {t.dtype}")
+    if t.device.type != "cuda" or (device_index is not None and t.device.index != device_index):
+        raise ValueError(f"update_vertices: the tensor is on {t.device}, the context on cuda:{device_index}")
+    if not t.is_contiguous():
+        raise ValueError("update_vertices: the tensor is not contiguous")
+    if not (t.dim() == 1 and t.numel() % 15 == 0) and not (t.dim() == 2 and t.shape[1] == 15):
+        raise ValueError(f"update_vertices: shape {tuple(t.shape)} is not (n, 15) or flat n * 15")
+    return t.data_ptr(), t.numel() // 15
+
+
 def pack_compact(scene):
     """glrtx_debug_pack_compact (host only, no device): (records (n, 12) float32, rank table (n_words / 2, 2) uint32, 64-byte leaf records by id (n_ids, 16) float32)."""
     L = lib()
@@ -295,6 +327,7 @@ class Device:
         rc = self.L.glrtx_create(C.byref(self.h), device_id)
         if rc != 0:
             raise GlrtxError(rc, self.L.glrtx_last_error(None).decode())
+        self.device_id = device_id
 
     def close(self):
         if self.h:
@@ -315,6 +348,28 @@ class Device:
         v, t, m, l, b = (_f32(scene[k]) for k in ("vert", "tri", "mat", "light", "bvh"))
         self._ck(self.L.glrtx_upload_scene(self.h, _fp(v), v.size // 15, _fp(t), t.size // 4, _fp(m), m.size // 18,
                                            _fp(l), l.size // 4, _fp(b), b.size // 9))
+
+    def update_vertices(self, v):
+        """New positions and normals for the uploaded scene's vertices, refitted on the device (glrtx_update_vertices): a numpy array is taken from host
+        memory, a contiguous float32 torch tensor on the context's GPU (shape (n, 15) or flat) is read on the context's stream (glrtx_update_vertices_device:
+        order its producer there with set_stream, or synchronise).  Returns when the refit has run; the accumulator is not cleared."""
+        if type(v).__module__.startswith("torch"):
+            import torch
+            idx = self.device_id if self.device_id >= 0 else torch.cuda.current_device()
+            ptr, n = _device_vertices(v, idx)
+            self._ck(self.L.glrtx_update_vertices_device(self.h, C.c_void_p(ptr), n))
+        else:
+            a, n = _host_vertices(v)
+            self._ck(self.L.glrtx_update_vertices(self.h, _fp(a), n))
+
+    def read_scene(self, which) -> np.ndarray:
+        """glrtx_debug_read_scene: one device scene buffer ("nodes", "cnodes", "nrms", "lights", "vine", "root") as raw bytes (uint8)."""
+        k = SCENE_BUFFERS.index(which)
+        n = C.c_size_t(0)
+        self._ck(self.L.glrtx_debug_read_scene(self.h, k, None, 0, C.byref(n)))
+        out = np.zeros(max(int(n.value), 1), np.uint8)
+        self._ck(self.L.glrtx_debug_read_scene(self.h, k, out.ctypes.data_as(C.c_void_p), out.size, C.byref(n)))
+        return out[:int(n.value)]
 
     def build_lbvh(self, vert, tri):
         """Linear BVH built on the GPU.  Returns (nodes (n_nodes*3, 3) float32 in the wire format, max_depth, device ms)."""
@@ -524,6 +579,11 @@ class Group:
         v, t, m, l, b = (_f32(scene[k]) for k in ("vert", "tri", "mat", "light", "bvh"))
         self._ck(self.L.glrtx_group_upload_scene(self.h, _fp(v), v.size // 15, _fp(t), t.size // 4, _fp(m), m.size // 18,
                                                  _fp(l), l.size // 4, _fp(b), b.size // 9))
+
+    def update_vertices(self, v):
+        """Device.update_vertices (host memory) on every member: glrtx_group_update_vertices."""
+        a, n = _host_vertices(v)
+        self._ck(self.L.glrtx_group_update_vertices(self.h, _fp(a), n))
 
     def resize(self, w, h):
         self._ck(self.L.glrtx_group_resize(self.h, w, h))

@@ -35,6 +35,7 @@ def lib():
         L.glrt_bvh_order_by_hits.argtypes = [fp, C.c_size_t, C.POINTER(C.c_uint32), C.c_size_t]
         L.glrt_bvh_add_shadow_hits.argtypes = [C.POINTER(C.c_uint32), C.c_size_t, fp, fp, C.c_size_t]
         L.glrt_bvh_reinsert.argtypes = [fp, C.c_size_t, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double)]
+        L.glrt_bvh_refit.argtypes = [fp, C.c_size_t, fp, C.c_size_t, fp, C.c_size_t]
         L.glrt_look_at.argtypes = [fp, fp, fp, fp]
         L.glrt_perspective.argtypes = [C.c_float, C.c_float, C.c_float, C.c_float, fp]
         L.glrt_mat4_mul.argtypes = [fp, fp, fp]
@@ -124,6 +125,17 @@ def reinsert(nodes, max_passes: int = 8):
     if rc < 0:
         raise RuntimeError(f"glrt_bvh_reinsert failed: {rc}")
     return out, depth.value, int(rc), (cost[0], cost[1])
+
+
+def refit_bvh(vert, tri, nodes):
+    """glrt_bvh_refit on a copy of `nodes`: the boxes of the tree's reachable nodes recomputed from `vert` (leaves from their triangle's positions, forks from their
+    children, in the total order on float bit patterns of include/glrt_host.h); topology untouched.  Returns nodes (nN*3, 3) float32."""
+    vert, tri = _f32(vert).reshape(-1, 15), _f32(tri).reshape(-1, 4)
+    out = _f32(nodes).reshape(-1, 3).copy()
+    rc = lib().glrt_bvh_refit(_fp(vert), vert.shape[0], _fp(tri), tri.shape[0], _fp(out), out.shape[0] // 3)
+    if rc != 0:
+        raise RuntimeError(f"glrt_bvh_refit failed: {rc}")
+    return out
 
 
 def look_at(eye, center, up) -> np.ndarray:
