@@ -112,6 +112,19 @@ int glrt_bvh_reinsert(float *nodes, size_t n_nodes, int max_passes, int *max_dep
  * twice), GLRT_HOST_EINDEX for a triangle with a vertex index out of range.  On error `nodes` is unchanged. */
 int glrt_bvh_refit(const float *vert, size_t n_vert, const float *tri, size_t n_tri, float *nodes, size_t n_nodes);
 
+/* Batched ray queries on a wire-format tree: the CPU statement of the device's glrtx_trace_rays (include/glrtx.h), with the same semantics, bit for bit.
+ * rays: n x 8 floats {ox, oy, oz, tmin, dx, dy, dz, tmax}; hits_out: n x 4 words {t (float), tri (int32: the wire triangle index, -1 on a miss), u, v}.
+ * flags: GLRT_TRACE_CLOSEST (the smallest t in (tmin, tmax); ties to the first triangle of the renderer's visiting order) or GLRT_TRACE_ANY (the first
+ * accepted hit in that order).  A hit is what the renderer's triangle test accepts (|det| >= 1e-4) with t > tmin and t below the running limit, which starts
+ * at tmax and also culls boxes; on a miss t = tmax, tri = -1, u = v = 0.  A ray with a NaN or infinite component, a zero direction or tmax <= tmin is not
+ * searched (the miss record); denormal components are read as zeros of their sign.  Runs with denormals flushed (MXCSR FTZ | DAZ, restored on return).
+ * n_nodes = 0: every ray misses.  GLRT_HOST_EINVAL: an unknown flag, NULL arrays with n > 0, a malformed tree (a child or leaf triangle out of range, a
+ * node reached twice); GLRT_HOST_EINDEX: a reachable triangle with a vertex index out of range.  n = 0 succeeds and does nothing. */
+#define GLRT_TRACE_CLOSEST 0
+#define GLRT_TRACE_ANY 1
+int glrt_trace_rays(const float *vert, size_t n_vert, const float *tri, size_t n_tri, const float *nodes, size_t n_nodes, const float *rays, size_t n,
+                    float *hits_out, int flags);
+
 void glrt_look_at(const float eye[3], const float center[3], const float up[3], float out[16]);
 void glrt_perspective(float fovy_deg, float aspect, float z_near, float z_far, float out[16]);
 void glrt_mat4_mul(const float a[16], const float b[16], float out[16]);

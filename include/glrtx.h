@@ -154,6 +154,31 @@ int glrtx_upload_scene(glrtx_ctx *ctx, const float *vert, size_t n_vert, const f
 int glrtx_update_vertices(glrtx_ctx *ctx, const float *vert, size_t n_vert);
 int glrtx_update_vertices_device(glrtx_ctx *ctx, const void *dev_vert, size_t n_vert);
 
+/* Batched ray queries against the uploaded scene: the renderer's own traversal (the same trees, node layouts and visiting order) for rays the caller hands in.
+ *   ray: 8 floats {ox, oy, oz, tmin, dx, dy, dz, tmax};  hit: 4 words {t (float), tri (int32), u (float), v (float)}.
+ * A triangle counts as hit exactly when the renderer's triangle test accepts it (raytrace.frag:226-257) with t > tmin in place of t > 1e-4, and only below the
+ * running search limit, which starts at tmax: a hit has tmin < t < tmax, and tmax also culls boxes.  The test keeps the renderer's rejection of |det| < 1e-4
+ * (det: the edge-1 dot of the direction x edge-2 cross product), so the query sees the scene exactly as the renderer does: very small triangles, and triangles
+ * seen edge-on, are never hit.  t, u, v are in the units of the direction as given (directions are not normalised); the hit point is o + t d =
+ * (1 - u - v) v0 + u v1 + v v2.  tri is the triangle's index in the uploaded wire format; on a miss tri = -1, t = tmax, u = v = 0.
+ *   GLRTX_TRACE_CLOSEST  the smallest t; among equal t the first triangle in the renderer's visiting order.  With tmin = 1e-4f, tmax = 1e8f this is bit for
+ *                        bit the hit the path tracer computes for the same ray under the same tree.
+ *   GLRTX_TRACE_ANY      the first accepted hit in that visiting order (deterministic for a given tree): visibility and shadow tests.
+ * A ray with a NaN or infinite component, a zero direction or tmax <= tmin is not searched: its answer is the miss record (t = tmax as given).  Denormal
+ * components are read as zeros of their sign, as the device's arithmetic reads them.  Only the triangles are traced: spheres (GLRTX_EXT_*) and the volume
+ * are not seen.  The result is what the CPU statement glrt_trace_rays (include/glrt_host.h) computes on the wire-format tree, bit for bit.
+ *   glrtx_trace_rays         host arrays (n x 8 floats in, n x 4 words out); returns when the hits are in hits_out
+ *   glrtx_trace_rays_device  device arrays on the context's device (16-byte aligned), read and written on the context's stream (glrtx_set_stream's, or the
+ *                            context's own): the caller orders its producer there, or synchronises.  Returns once the query is enqueued; wait with glrtx_sync
+ *                            or on that stream.
+ * Both seal an open fed launch (glrtx_render), like glrtx_update_vertices, and leave the accumulator, frame numbering, adaptive state, presentation and the
+ * ray counts of glrtx_stats untouched.  GLRTX_EINVAL, nothing changed: no scene uploaded, NULL buffers with n > 0, flags other than the two below,
+ * n >= 2^31.  n = 0 succeeds and does nothing.  Groups: query a member, glrtx_group_ctx(grp, i) -- every member holds the whole scene. */
+#define GLRTX_TRACE_CLOSEST 0
+#define GLRTX_TRACE_ANY 1
+int glrtx_trace_rays(glrtx_ctx *ctx, const float *rays, size_t n, float *hits_out, int flags);
+int glrtx_trace_rays_device(glrtx_ctx *ctx, const void *dev_rays, size_t n, void *dev_hits, int flags);
+
 /* Test hook: a copy of one device scene buffer as the kernels read it.  which: GLRTX_SCENE_NODES (the 64-byte node array, leaf records in reverse id
  * order then the forks), _CNODES (the compact records), _NRMS, _LIGHTS, _VINE (empty unless the tree is a vine), _ROOT (48 bytes: root box min {x, y, z, 0},
  * max {x, y, z, 0}, then the ints root_boxed, vine_uniform, root ref, vine records).  *bytes_out (may be NULL) gets the size; dst NULL asks for the size only.

@@ -22,6 +22,7 @@
 #include "lbvh.hip.h"
 #include "sahl.hip.h"
 #include "refit.hip.h"
+#include "query.hip.h"
 static_assert(glrtx::lbvh::kRotationPasses == GLRT_LBVH_ROTATION_PASSES, "device and CPU LBVH statements must run the same rotation sweeps");
 static_assert(glrtx::lbvh::kRebuildLeaves == GLRT_LBVH_REBUILD_LEAVES, "device and CPU LBVH statements must rebuild the same subtrees");
 
@@ -133,6 +134,9 @@ struct glrtx_ctx {
     bool state_used = false;
 
     std::vector<int> leaf_tri;  // leaf record k of the uploaded scene -> wire triangle (glrtx_hit_histogram)
+    // Ray queries (glrtx_trace_rays, query.hip.h): leaf id -> wire triangle on the device (id 0: -1), uploaded with the scene; the ray counter; the
+    // staging buffers of the host call
+    DevBuf qwire, qcounter, qrays, qhits;
     // The refit plan (glrtx_update_vertices; refit.hip.h), kept beside the scene from its upload: the integer tables (`ints`), the wire boxes as keys with the
     // arrival counters and the read-back words (`keys`), a staging buffer for host vertices; `a`: the kernels' arguments with every pointer set
     struct Refit {
@@ -1027,6 +1031,30 @@ bool present_held(const glrtx_ctx *c) {
 //   fed        -- on one of the context's pipe slots (own stream, state, queues, tile counter, plane chunks); the launch stays OPEN: later calls with the same camera
 //                 append their frames to it while it runs (feed_append).  Every multi-frame launch on the context's own stream, and a single-frame launch that
 //                 follows another one directly (a burst)
+// The node fetch the wavefront kernel's traversal uses on this scene (vine: the list scan, fetch 0): 0 one record per lane, 1 pair-cooperative, 2 the two
+// in alternate steps.  Picked by the size of the record array; GLRTX_PAIR_FETCH=0/1/2 overrides (read at every launch).  (See launch_wgwf.)
+int wgwf_fetch(const glrtx_ctx *c, bool vine) {
+    int fetch = vine ? 0 : ((size_t)c->n_fork + (size_t)c->st.n_tri >= (size_t)kPairFetchMinRecords ? 1 : 0);
+    if (const char *v = std::getenv("GLRTX_PAIR_FETCH")) fetch = vine ? 0 : std::max(0, std::min(2, std::atoi(v)));
+    return fetch;
+}
+
+// The wavefront kernel's LDS without the compact layout's rank table: materials and lights | stacks | ctl | root box | camera block | seeds | light-test bits
+int wgwf_lds_base(const glrtx_ctx *c) {
+    return c->sc.lds_head_f4 * (int)sizeof(float4) + 2 * c->sc.stack_entries * kBlockThreads * (int)sizeof(int) + kWgCtlWords * (int)sizeof(unsigned) +
+           2 * (int)sizeof(float4) + kCamFloatsPadded * (int)sizeof(float) + kLdsSeeds * (int)sizeof(float2) + kWgPathsMax / 8;
+}
+
+// Whether the wavefront kernel walks the compact node array (pack_compact: 48-byte records, three loads per step instead of four): it serves the
+// one-record-per-lane fetch when its rank table fits in LDS beside everything else with GLRTX_WGWF_WAVES workgroups per CU still resident;
+// GLRTX_COMPACT_NODES=0/1 overrides (1: as long as one workgroup fits).  The ray queries (glrtx_trace_rays) follow the same rule.
+bool wgwf_compact(const glrtx_ctx *c, bool vine, int fetch) {
+    const int lds_compact = wgwf_lds_base(c) + c->sc.n_crank * (int)sizeof(uint2);
+    bool compact = !vine && fetch == 0 && c->sc.n_crank > 0 && (size_t)lds_compact * GLRTX_WGWF_WAVES <= (size_t)160 * 1024;
+    if (const char *v = std::getenv("GLRTX_COMPACT_NODES")) compact = std::atoi(v) != 0 && !vine && fetch == 0 && c->sc.n_crank > 0 && lds_compact <= 160 * 1024;
+    return compact;
+}
+
 //   overlapped -- a single-frame launch on a pipe slot, the frame spread over all workgroup slots in one helping, slots handed over progressively (round 3): what a
 //                 caller gets that renders, resolves and saves every frame -- the reference's loop, window.cpp:121-169 -- and any single frame on a caller's stream
 //   plain      -- on the context's stream, nothing overlaps: multi-frame launches on a caller's stream (stream order is the caller's), GLRTX_NO_PIPELINE=1
@@ -1067,19 +1095,12 @@ int launch_wgwf(glrtx_ctx *c, const KernelArgs &a_in, const glrtx_params *p, con
     // The V form has one fetch form only: one record per lane on DevScene::nodes, as in the megakernels (no list scan, no pair fetch, no compact layout).
     using Kernel = void (*)(const KernelArgs, const WfArgs, unsigned *, float4 *, const int *, const unsigned *, const VolArgs);
     const bool vine = c->sc.n_vine > 0 && !vol;
-    int fetch = vine ? 0 : ((size_t)c->n_fork + (size_t)c->st.n_tri >= (size_t)kPairFetchMinRecords ? 1 : 0);
-    if (const char *v = std::getenv("GLRTX_PAIR_FETCH")) fetch = vine ? 0 : std::max(0, std::min(2, std::atoi(v)));
-    if (vol) fetch = 0;
+    int fetch = vol ? 0 : wgwf_fetch(c, vine);
     c->st.node_fetch_last = fetch;
-    // The compact node array (pack_compact: 48-byte records, three loads per step instead of four) serves the one-record-per-lane fetch when its rank table fits in
-    // LDS beside everything else with GLRTX_WGWF_WAVES workgroups per CU still resident; GLRTX_COMPACT_NODES=0/1 overrides (1: as long as one workgroup fits).
-    const int lds_base = c->sc.lds_head_f4 * (int)sizeof(float4) + 2 * c->sc.stack_entries * kBlockThreads * (int)sizeof(int) +
-                         kWgCtlWords * (int)sizeof(unsigned) + 2 * (int)sizeof(float4) + kCamFloatsPadded * (int)sizeof(float) + kLdsSeeds * (int)sizeof(float2) +  // ctl | root box | camera block | seeds |
-                         kWgPathsMax / 8;  // light-test bits, one per path-queue position
+    // The compact node array (pack_compact): wgwf_compact.
+    const int lds_base = wgwf_lds_base(c);
     const int lds_compact = lds_base + c->sc.n_crank * (int)sizeof(uint2);  // | rank table
-    bool compact = !vine && fetch == 0 && c->sc.n_crank > 0 && (size_t)lds_compact * GLRTX_WGWF_WAVES <= (size_t)160 * 1024;
-    if (const char *v = std::getenv("GLRTX_COMPACT_NODES")) compact = std::atoi(v) != 0 && !vine && fetch == 0 && c->sc.n_crank > 0 && lds_compact <= 160 * 1024;
-    if (vol) compact = false;
+    bool compact = !vol && wgwf_compact(c, vine, fetch);
     c->st.node_layout_last = compact ? 1 : 0;
     const bool cr = c->count_rays;
     constexpr int A = kWgwfAdaptive;  // (the ADAPT forms of the same eight: glrtx_render_adaptive)
@@ -1542,6 +1563,7 @@ void glrtx_destroy(glrtx_ctx *c) {
     dev_free(c->wfState); dev_free(c->wfQ); dev_free(c->wfSeeds); dev_free(c->wfPlanes);
     dev_free(c->bvhVert); dev_free(c->bvhTri); dev_free(c->bvhNodes);
     dev_free(c->rf.ints); dev_free(c->rf.keys); dev_free(c->rf.vert);
+    dev_free(c->qwire); dev_free(c->qcounter); dev_free(c->qrays); dev_free(c->qhits);
     if (c->rf.slot_ev) (void)hipEventDestroy(c->rf.slot_ev);
     if (c->bvhWs.p) { (void)hipFree(c->bvhWs.p); c->bvhWs.p = nullptr; c->bvhWs.bytes = 0; }
     for (auto &r : c->ring) {
@@ -1587,6 +1609,11 @@ int glrtx_upload_scene(glrtx_ctx *c, const float *vert, size_t n_vert, const flo
     if ((rc = dev_upload(c, c->lights, lights.data(), lights.size() * sizeof(float4)))) return rc;
     if (!P.vine.empty() && (rc = dev_upload(c, c->vine, P.vine.data(), P.vine.size() * sizeof(float4)))) return rc;
     c->have_scene = false;  // (until the plan is in place too)
+    {
+        std::vector<int> wire(P.leaf_tri.size() + 1, -1);
+        for (size_t k = 0; k < P.leaf_tri.size(); k++) wire[k + 1] = P.leaf_tri[k];
+        if ((rc = dev_upload(c, c->qwire, wire.data(), wire.size() * sizeof(int)))) return rc;
+    }
     const size_t scene_bytes[5] = {nodes.size() * sizeof(float4), P.cnodes.size() * sizeof(float4), nrms.size() * sizeof(float4), lights.size() * sizeof(float4),
                                    P.vine.size() * sizeof(float4)};
     if ((rc = refit_plan_upload(c, P, tri, light, n_light, bvh, n_nodes, n_vert, scene_bytes))) return rc;
@@ -1685,6 +1712,77 @@ int glrtx_update_vertices_device(glrtx_ctx *c, const void *dev_vert, size_t n_ve
     seal_feed(c);
     HIP_TRY(c, hipSetDevice(c->device));
     return refit_run(c, dev_vert);
+}
+
+namespace {
+
+int trace_check(glrtx_ctx *c, const void *rays, size_t n, const void *hits, int flags, const char *fn) {
+    if (!c) return GLRTX_EINVAL;
+    if (!c->have_scene) return fail(c, GLRTX_EINVAL, "%s: no scene uploaded", fn);
+    if (flags != GLRTX_TRACE_CLOSEST && flags != GLRTX_TRACE_ANY) return fail(c, GLRTX_EINVAL, "%s: unknown flags %d", fn, flags);
+    if (n >= ((size_t)1 << 31)) return fail(c, GLRTX_EINVAL, "%s: %zu rays (at most 2^31 - 1)", fn, n);
+    if (n > 0 && (!rays || !hits)) return fail(c, GLRTX_EINVAL, "%s: NULL buffer", fn);
+    return GLRTX_OK;
+}
+
+// One query launch on the context's stream (query.hip.h): the tree kernel with the node layout the wavefront kernel would walk, or the list scan on a vine.
+// A persistent grid: as many workgroups as are resident on the device at once, fewer when the batch has fewer rays.
+int trace_launch(glrtx_ctx *c, const void *rays, void *hits, size_t n, int flags) {
+    const bool vine = c->sc.n_vine > 0, any = flags == GLRTX_TRACE_ANY;
+    const int fetch = wgwf_fetch(c, vine);
+    const int lds_stack = 2 * c->sc.stack_entries * kBlockThreads * (int)sizeof(int), lds_ranks = c->sc.n_crank * (int)sizeof(uint2);
+    // the compact records where the wavefront kernel would walk them; GLRTX_COMPACT_NODES=0/1 (read at every call) forces either layout -- the query has no
+    // pair-cooperative fetch, so 1 holds whatever the size of the tree, as long as the rank table fits in LDS
+    bool compact = wgwf_compact(c, vine, fetch);
+    if (const char *v = std::getenv("GLRTX_COMPACT_NODES")) compact = std::atoi(v) != 0 && !vine && c->sc.n_crank > 0;
+    compact = compact && lds_stack + lds_ranks <= 160 * 1024;
+    using Kernel = void (*)(const query::Args);
+    const Kernel kernel = vine ? (any ? (Kernel)query::trace_vine<true> : (Kernel)query::trace_vine<false>)
+                        : compact ? (any ? (Kernel)query::trace_tree<true, true> : (Kernel)query::trace_tree<false, true>)
+                                  : (any ? (Kernel)query::trace_tree<true, false> : (Kernel)query::trace_tree<false, false>);
+    const int lds = vine ? 0 : lds_stack + (compact ? lds_ranks : 0);
+    if (lds > 64 * 1024) HIP_TRY(c, hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    int per_cu = 0;
+    HIP_TRY(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kBlockThreads, lds));
+    per_cu = std::max(per_cu, 1);
+    const size_t needed = (n + kBlockThreads - 1) / kBlockThreads;
+    const unsigned grid = (unsigned)std::max<size_t>(1, std::min<size_t>((size_t)per_cu * (size_t)c->n_cu, needed));
+    if (int rc = ensure(c, c->qcounter, sizeof(unsigned))) return rc;
+    HIP_TRY(c, hipMemsetAsync(c->qcounter.p, 0, sizeof(unsigned), c->stream));
+    query::Args a;
+    a.sc = c->sc;
+    a.rays = (const float4 *)rays;
+    a.hits = (float4 *)hits;
+    a.wire = (const int *)c->qwire.p;
+    a.counter = (unsigned *)c->qcounter.p;
+    a.n = (unsigned)n;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlockThreads), lds, c->stream, a);
+    HIP_TRY(c, hipGetLastError());
+    return GLRTX_OK;
+}
+
+}  // namespace
+
+int glrtx_trace_rays(glrtx_ctx *c, const float *rays, size_t n, float *hits_out, int flags) {
+    if (int rc = trace_check(c, rays, n, hits_out, flags, "glrtx_trace_rays")) return rc;
+    if (n == 0) return GLRTX_OK;
+    seal_feed(c);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (int rc = ensure(c, c->qrays, n * 8 * sizeof(float))) return rc;
+    if (int rc = ensure(c, c->qhits, n * 4 * sizeof(float))) return rc;
+    HIP_TRY(c, hipMemcpyAsync(c->qrays.p, rays, n * 8 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if (int rc = trace_launch(c, c->qrays.p, c->qhits.p, n, flags)) return rc;
+    HIP_TRY(c, hipMemcpyAsync(hits_out, c->qhits.p, n * 4 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return GLRTX_OK;
+}
+
+int glrtx_trace_rays_device(glrtx_ctx *c, const void *dev_rays, size_t n, void *dev_hits, int flags) {
+    if (int rc = trace_check(c, dev_rays, n, dev_hits, flags, "glrtx_trace_rays_device")) return rc;
+    if (n == 0) return GLRTX_OK;
+    seal_feed(c);
+    HIP_TRY(c, hipSetDevice(c->device));
+    return trace_launch(c, dev_rays, dev_hits, n, flags);
 }
 
 int glrtx_debug_read_scene(glrtx_ctx *c, int which, void *dst, size_t capacity_bytes, size_t *bytes_out) {

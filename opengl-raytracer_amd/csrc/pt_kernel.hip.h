@@ -447,8 +447,10 @@ DEV bool trav_init(const DevScene &sc, const float4 *root, Trav &T, float ox, fl
 // COMPACT: the same step on the compact node array (DevScene::cnodes; ranks: its rank table in LDS) -- the C++ statement of GLRTX_TRAV_STEP_ASM_COMPACT
 // (trav_asm.hip.h).  A ref is then a position: "is a fork" is its bit in the rank table, its children are at positions 2 rank + 1 and 2 rank + 2, and the
 // three 16-byte pieces of the record carry the right child's far corner in their spare words.  Same boxes, same triangles, same order.
-template <bool CLOSEST, bool COMPACT = false>
-DEV bool trav_step(const DevScene &sc, int *stack, Trav &T, const uint2 *ranks = nullptr) {
+// ANY and tmin serve the ray queries alone (query.hip.h): a hit needs t > tmin instead of t > EPS, and with ANY the ray ends at its first accepted hit.  The
+// renderer's instantiations take the defaults, which are its own constants: the same instructions as before.
+template <bool CLOSEST, bool COMPACT = false, bool ANY = false>
+DEV bool trav_step(const DevScene &sc, int *stack, Trav &T, const uint2 *ranks = nullptr, float tmin = PT_EPS) {
 #ifdef GLRTX_TRAV_STATS
     trav_stats_iter(T.cur, (const void *)(sc.forks + 4 * (ptrdiff_t)T.cur), T.stop_d == -__builtin_inff(), T.sp);
     T.iters++;
@@ -531,14 +533,14 @@ DEV bool trav_step(const DevScene &sc, int *stack, Trav &T, const uint2 *ranks =
         //  is still in the running -- most tested triangles are missed; with & and | the step was 7 % slower)
         const bool hit = !(-PT_EPS < det && det < PT_EPS) && !(u < 0.0f || 1.0f < u) &&
                          !(v < 0.0f || 1.0f < inv * (U + V)) &&  // u+v>1 is evaluated as inv*(U+V)>1
-                         !(PT_EPS >= tt);
+                         !(tmin >= tt);
         const bool closer = hit && tt < T.h.t;  // strict: among equal distances the first one visited wins (:325)
         T.h.tri = closer ? t : T.h.tri;
         if (CLOSEST) { T.h.u = closer ? u : T.h.u; T.h.v = closer ? v : T.h.v; }
         T.h.t = closer ? tt : T.h.t;  // == hit ? min(tHit, tt) : tHit (a NaN tt is never closer)
         // shadow ray: once an occluder is known the light test has failed and the traversal ends; otherwise on to the triangle chained
         // behind this one (the other leaf of a leaf pair, pack_scene) or, without one, to the stack
-        const bool stopped = T.stop_d - T.h.t >= PT_EPS;
+        const bool stopped = ANY ? closer : T.stop_d - T.h.t >= PT_EPS;
         const int next = __float_as_int(B.w);
         T.cur = stopped ? REF_FIN : next;
         need_pop = !stopped && next == REF_FIN;
@@ -684,7 +686,7 @@ DEV void trav_steps_asm(const DevScene &sc, int *stack, Trav &T, unsigned rk GLR
 // skips operations whose results nothing would have read; the ones that are executed are the same, in the same order.
 template <bool CLOSEST>
 DEV void tri_test(Hit &h, int t, float ox, float oy, float oz, float dx, float dy, float dz, float v0x, float v0y, float v0z, float e1x,
-                  float e1y, float e1z, float e2x, float e2y, float e2z) {
+                  float e1y, float e1z, float e2x, float e2y, float e2z, float tmin = PT_EPS) {
     const float tx = ox - v0x, ty = oy - v0y, tz = oz - v0z;
     const float px = dy * e2z - dz * e2y;
     const float py = dz * e2x - dx * e2z;
@@ -703,7 +705,7 @@ DEV void tri_test(Hit &h, int t, float ox, float oy, float oz, float dx, float d
     const bool ok_v = ok_u && !(v < 0.0f || 1.0f < inv * (U + V));
     if (!__any(ok_v)) return;
     const float tt = dot3(e2x, e2y, e2z, qx, qy, qz) * inv;
-    const bool hit = ok_v && !(PT_EPS >= tt);
+    const bool hit = ok_v && !(tmin >= tt);
     const bool closer = hit && tt < h.t;
     h.tri = closer ? t : h.tri;
     if (CLOSEST) { h.u = closer ? u : h.u; h.v = closer ? v : h.v; }
@@ -718,9 +720,11 @@ DEV void tri_test(Hit &h, int t, float ox, float oy, float oz, float dx, float d
 // A list whose forks all have the same box (what glrt_bvh_build_chain emits: BASELINE config 3) is scanned by the hand-written
 // loop of scan_asm.hip.h; this C++ statement serves every other vine, and as the form the assembly is checked against (-DGLRTX_SCAN_CXX).
 // Precondition: stop_d - limit < EPS (see scan_asm.hip.h).
-template <bool CLOSEST>
+// QUERY (query.hip.h): 0 the renderer; 1 a closest-hit query, 2 an any-hit query (the scan ends at the first accepted hit) -- both with a hit needing
+// t > tmin, and both on this C++ statement (the uniform list's assembly loop has the renderer's EPS built in).
+template <bool CLOSEST, int QUERY = 0>
 DEV Hit trav_scan(const DevScene &sc, float ox, float oy, float oz, float dx, float dy, float dz, bool valid,
-              float limit = PT_INFTY, float stop_d = -__builtin_inff()) {
+              float limit = PT_INFTY, float stop_d = -__builtin_inff(), float tmin = PT_EPS) {
     Hit h;
     h.t = limit; h.tri = -1; h.u = 0.f; h.v = 0.f;
     const float ix = frcp(dx), iy = frcp(dy), iz = frcp(dz);
@@ -733,6 +737,7 @@ DEV Hit trav_scan(const DevScene &sc, float ox, float oy, float oz, float dx, fl
         t1u = __builtin_fminf(__builtin_fmaxf(fx, nx), __builtin_fminf(__builtin_fmaxf(fy, ny), __builtin_fmaxf(fz, nz)));
         t0u = __builtin_fmaxf(__builtin_fminf(fx, nx), __builtin_fmaxf(__builtin_fminf(fy, ny), __builtin_fminf(fz, nz)));
 #ifndef GLRTX_SCAN_CXX
+        if constexpr (QUERY == 0) {
         if (valid) {
             unsigned groups = (unsigned)sc.vine_main >> 2;
             unsigned long long s_entry, s_alive, s_tmp;
@@ -744,6 +749,7 @@ DEV Hit trav_scan(const DevScene &sc, float ox, float oy, float oz, float dx, fl
                          : "vcc", "scc", "memory", GLRTX_ASM_VCLOBBERS, GLRTX_SCAN_SCLOBBERS);
         }
         return h;
+        }
 #endif
     }
     const int n = sc.n_vine, last_at = sc.vine_main;
@@ -764,8 +770,9 @@ DEV Hit trav_scan(const DevScene &sc, float ox, float oy, float oz, float dx, fl
             }
             alive = pass;
             if (pass) {
-                tri_test<CLOSEST>(h, __float_as_int(r[15]), ox, oy, oz, dx, dy, dz, r[3], r[7], r[8], r[9], r[10], r[11], r[12], r[13], r[14]);
+                tri_test<CLOSEST>(h, __float_as_int(r[15]), ox, oy, oz, dx, dy, dz, r[3], r[7], r[8], r[9], r[10], r[11], r[12], r[13], r[14], tmin);
                 if (stop_d - h.t >= PT_EPS) alive = false;  // shadow ray: occluded for certain (see Trav)
+                if (QUERY == 2 && h.tri >= 0) alive = false;  // any-hit query: the first accepted hit ends the scan
             }
         }
     };

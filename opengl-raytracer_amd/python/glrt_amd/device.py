@@ -75,7 +75,8 @@ EXPORTS = ["glrtx_abi_version", "glrtx_create", "glrtx_destroy", "glrtx_last_err
            "glrtx_upload_volume", "glrtx_group_upload_volume", "glrtx_debug_volume_math", "glrtx_debug_volume_lookup",
            "glrtx_render_adaptive", "glrtx_adaptive_active_tiles", "glrtx_read_tile_mask", "glrtx_read_adaptive_half", "glrtx_debug_adaptive_select",
            "glrtx_group_render_adaptive", "glrtx_group_adaptive_active_tiles", "glrtx_debug_pack_compact", "glrtx_set_volume_wavefront",
-           "glrtx_update_vertices", "glrtx_update_vertices_device", "glrtx_group_update_vertices", "glrtx_debug_read_scene"]
+           "glrtx_update_vertices", "glrtx_update_vertices_device", "glrtx_group_update_vertices", "glrtx_debug_read_scene",
+           "glrtx_trace_rays", "glrtx_trace_rays_device"]
 
 SCENE_BUFFERS = ("nodes", "cnodes", "nrms", "lights", "vine", "root")  # glrtx_debug_read_scene's `which`, in order (GLRTX_SCENE_*)
 
@@ -174,6 +175,8 @@ def lib():
         L.glrtx_update_vertices.argtypes = [vp, fp, C.c_size_t]
         L.glrtx_update_vertices_device.argtypes = [vp, vp, C.c_size_t]
         L.glrtx_group_update_vertices.argtypes = [vp, fp, C.c_size_t]
+        L.glrtx_trace_rays.argtypes = [vp, fp, C.c_size_t, fp, C.c_int]
+        L.glrtx_trace_rays_device.argtypes = [vp, vp, C.c_size_t, vp, C.c_int]
         L.glrtx_debug_read_scene.argtypes = [vp, C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t)]
         try:  # (additive to ABI 10: libraries of earlier rounds, which tools/gpu_abx.py loads, lack it)
             L.glrtx_set_volume_wavefront.argtypes = [vp, C.c_int]
@@ -361,6 +364,41 @@ class Device:
         else:
             a, n = _host_vertices(v)
             self._ck(self.L.glrtx_update_vertices(self.h, _fp(a), n))
+
+    def trace_rays(self, rays, any_hit=False, out=None):
+        """Batched ray queries against the uploaded scene (glrtx_trace_rays, include/glrtx.h).  rays: (n, 8) float32 {ox, oy, oz, tmin, dx, dy, dz, tmax}.
+        Closest hit, or with any_hit=True the first accepted hit of the renderer's visiting order.  Returns (t, tri, u, v): views of one (n, 4) buffer, tri as
+        int32 (the wire triangle index; -1 on a miss, where t = tmax and u = v = 0).
+          numpy array  -> host memory (glrtx_trace_rays); returns when the hits are there.  out: an (n, 4) float32 array, or None.
+          torch tensor -> contiguous float32 on the context's GPU, read and written on the context's stream with no host copy (glrtx_trace_rays_device),
+                          the convention of update_vertices: order the producer of `rays` there (set_stream) or synchronise, and wait on that stream
+                          (or sync()) before reading the result.  out: an (n, 4) float32 CUDA tensor, or None for a new one (allocated on torch's
+                          current stream).  Returns as soon as the query is enqueued."""
+        flags = 1 if any_hit else 0
+        if type(rays).__module__.startswith("torch"):
+            import torch
+            idx = self.device_id if self.device_id >= 0 else torch.cuda.current_device()
+            if rays.dtype != torch.float32 or rays.device.type != "cuda" or rays.device.index != idx or not rays.is_contiguous():
+                raise ValueError(f"trace_rays: a contiguous float32 tensor on cuda:{idx} expected, got {rays.dtype} on {rays.device}")
+            if rays.numel() % 8:
+                raise ValueError(f"trace_rays: shape {tuple(rays.shape)} is not (n, 8)")
+            n = rays.numel() // 8
+            if out is None:
+                out = torch.empty((n, 4), dtype=torch.float32, device=rays.device)
+            elif out.dtype != torch.float32 or out.device != rays.device or not out.is_contiguous() or out.numel() != 4 * n:
+                raise ValueError("trace_rays: out must be a contiguous (n, 4) float32 tensor on the rays' device")
+            out = out.view(n, 4)
+            self._ck(self.L.glrtx_trace_rays_device(self.h, C.c_void_p(rays.data_ptr()), n, C.c_void_p(out.data_ptr()), flags))
+            return out[:, 0], out[:, 1].view(torch.int32), out[:, 2], out[:, 3]
+        r = _f32(rays).reshape(-1, 8)
+        n = r.shape[0]
+        if out is None:
+            out = np.zeros((n, 4), np.float32)
+        elif out.dtype != np.float32 or not out.flags.c_contiguous or out.size != 4 * n:
+            raise ValueError("trace_rays: out must be a C-contiguous (n, 4) float32 array")
+        out = out.reshape(n, 4)
+        self._ck(self.L.glrtx_trace_rays(self.h, _fp(r), n, _fp(out), flags))
+        return out[:, 0], out[:, 1].view(np.int32), out[:, 2], out[:, 3]
 
     def read_scene(self, which) -> np.ndarray:
         """glrtx_debug_read_scene: one device scene buffer ("nodes", "cnodes", "nrms", "lights", "vine", "root") as raw bytes (uint8)."""

@@ -36,6 +36,7 @@ def lib():
         L.glrt_bvh_add_shadow_hits.argtypes = [C.POINTER(C.c_uint32), C.c_size_t, fp, fp, C.c_size_t]
         L.glrt_bvh_reinsert.argtypes = [fp, C.c_size_t, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double)]
         L.glrt_bvh_refit.argtypes = [fp, C.c_size_t, fp, C.c_size_t, fp, C.c_size_t]
+        L.glrt_trace_rays.argtypes = [fp, C.c_size_t, fp, C.c_size_t, fp, C.c_size_t, fp, C.c_size_t, fp, C.c_int]
         L.glrt_look_at.argtypes = [fp, fp, fp, fp]
         L.glrt_perspective.argtypes = [C.c_float, C.c_float, C.c_float, C.c_float, fp]
         L.glrt_mat4_mul.argtypes = [fp, fp, fp]
@@ -136,6 +137,23 @@ def refit_bvh(vert, tri, nodes):
     if rc != 0:
         raise RuntimeError(f"glrt_bvh_refit failed: {rc}")
     return out
+
+
+TRACE_CLOSEST, TRACE_ANY = 0, 1  # glrt_trace_rays / glrtx_trace_rays flags
+
+
+def trace_rays(vert, tri, nodes, rays, any_hit=False):
+    """glrt_trace_rays: the CPU statement of the device's ray queries on a wire-format tree (include/glrt_host.h).  rays: (n, 8) float32
+    {ox, oy, oz, tmin, dx, dy, dz, tmax}.  Returns (t, tri, u, v): views of one (n, 4) buffer, tri as int32 (the wire triangle index, -1 on a miss)."""
+    vert, tri = _f32(vert).reshape(-1, 15), _f32(tri).reshape(-1, 4)
+    nodes = _f32(nodes).reshape(-1, 9)
+    r = _f32(rays).reshape(-1, 8)
+    out = np.zeros((r.shape[0], 4), np.float32)
+    rc = lib().glrt_trace_rays(_fp(vert), vert.shape[0], _fp(tri), tri.shape[0], _fp(nodes), nodes.shape[0], _fp(r), r.shape[0], _fp(out),
+                               TRACE_ANY if any_hit else TRACE_CLOSEST)
+    if rc != 0:
+        raise RuntimeError(f"glrt_trace_rays failed: {rc}")
+    return out[:, 0], out[:, 1].view(np.int32), out[:, 2], out[:, 3]
 
 
 def look_at(eye, center, up) -> np.ndarray:

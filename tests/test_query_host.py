@@ -1,0 +1,166 @@
+"""glrt_trace_rays (include/glrt_host.h), the CPU statement of the ray queries, against a numpy brute force over all triangles, under every builder."""
+import numpy as np
+import pytest
+
+import query_rays as qr
+from fuzz_scenes import fuzz_scene
+from glrt_amd import host, scenes
+
+BUILDERS = ["sah", "sahl", "lbvh", "chain", "reference", "sah-reinsert"]
+GRAZE_MAX = 0.01  # rays on which the tree's box culling may lose a hit the brute force finds (grazing rays, flat boxes)
+
+
+def _scene(builder, seed=31, n_tri=150, **kw):
+    return fuzz_scene(seed, n_tri, builder, **kw)
+
+
+def _rays(scene, n=600):
+    c2w, s2c = scenes.camera((0.9, 0.6, 3.0), (0, 0, 0), (0, 1, 0), 45.0, 24, 16)
+    cam = qr.camera_rays(dict(c2w=c2w, s2c=s2c, width=24, height=16))
+    return np.concatenate([cam, qr.incoherent_rays(scene, n), qr.shadow_rays(scene, n // 2),
+                           qr.incoherent_rays(scene, n // 2, seed=7, tmin=0.0)])
+
+
+def _trace(scene, rays, any_hit=False):
+    return host.trace_rays(scene["vert"], scene["tri"], scene["bvh"], rays, any_hit)
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def _check_real_hits(scene, rays, res, bf):
+    hit, t, u, v = bf
+    rt, rtri, ru, rv = res
+    idx = np.nonzero(rtri >= 0)[0]
+    k = rtri[idx]
+    assert hit[idx, k].all(), "a reported hit that the triangle test rejects"
+    assert np.array_equal(_bits(rt[idx]), _bits(t[idx, k]))
+    assert np.array_equal(_bits(ru[idx]), _bits(u[idx, k]))
+    assert np.array_equal(_bits(rv[idx]), _bits(v[idx, k]))
+    miss = rtri < 0
+    assert np.array_equal(_bits(rt[miss]), _bits(rays[miss, 7])) and (ru[miss] == 0).all() and (rv[miss] == 0).all()
+
+
+@pytest.mark.parametrize("builder", BUILDERS)
+def test_closest_hit_against_brute_force(builder):
+    scene = _scene(builder)
+    rays = _rays(scene)
+    res = _trace(scene, rays)
+    bf = qr.brute_force(scene, rays)
+    _check_real_hits(scene, rays, res, bf)
+    hit, t = bf[0], bf[1]
+    tmin_bf = np.where(hit, t, np.inf).min(1)
+    any_bf = hit.any(1)
+    rt, rtri = res[0], res[1]
+    found = rtri >= 0
+    assert (rt[found] >= tmin_bf[found]).all(), "a hit closer than the closest one"
+    agree = (found == any_bf) & (~found | (rt == tmin_bf))
+    lost = ~agree
+    assert (~found[lost] | (rt[lost] > tmin_bf[lost])).all()
+    assert lost.mean() <= GRAZE_MAX, f"{lost.sum()} of {len(rays)} rays differ from the brute force"
+    assert found.sum() > len(rays) // 4  # (the ray sets do hit things)
+
+
+@pytest.mark.parametrize("builder", BUILDERS)
+def test_any_hit_against_brute_force(builder):
+    scene = _scene(builder)
+    rays = _rays(scene)
+    res = _trace(scene, rays, any_hit=True)
+    bf = qr.brute_force(scene, rays)
+    _check_real_hits(scene, rays, res, bf)
+    found, any_bf = res[1] >= 0, bf[0].any(1)
+    assert not (found & ~any_bf).any()
+    assert (any_bf & ~found).mean() <= GRAZE_MAX
+
+
+@pytest.mark.parametrize("builder", ["sah", "chain", "lbvh"])
+def test_any_hit_is_the_first_hit_of_the_visiting_order(builder):
+    """Any-hit returns a hit the closest-hit search also meets: never further than tmax, and identical to closest hit when only one triangle is hit."""
+    scene = _scene(builder, seed=33)
+    rays = _rays(scene, 300)
+    a, c = _trace(scene, rays, True), _trace(scene, rays)
+    assert np.array_equal(a[1] >= 0, c[1] >= 0)
+    assert (a[0][a[1] >= 0] >= c[0][a[1] >= 0]).all()
+    one = qr.brute_force(scene, rays)[0].sum(1) == 1
+    for x, y in zip(a, c):
+        assert np.array_equal(_bits(np.asarray(x)[one]), _bits(np.asarray(y)[one]))
+
+
+@pytest.mark.parametrize("flags", [dict(duplicates=True), dict(duplicates=True, degenerate=True), dict(degenerate=True)])
+def test_duplicates_and_degenerates_map_to_wire_indices(flags):
+    scene = fuzz_scene(35, 90, "sah", **flags)
+    rays = _rays(scene, 400)
+    res = _trace(scene, rays)
+    bf = qr.brute_force(scene, rays)
+    _check_real_hits(scene, rays, res, bf)
+    if flags.get("duplicates"):  # triangle k and k + n are the same: a tie goes to the one visited first, and both indices must occur
+        n = len(scene["tri"]) // 2
+        found = res[1][res[1] >= 0]
+        assert (found < n).any() and (found >= n).any()
+
+
+def test_tmin_zero_and_eps_from_surfaces():
+    scene = _scene("sah", seed=36)
+    r0 = qr.incoherent_rays(scene, 500, seed=3, tmin=0.0)
+    r1 = r0.copy()
+    r1[:, 3] = np.float32(1e-4)
+    for rays in (r0, r1):
+        res = _trace(scene, rays)
+        _check_real_hits(scene, rays, res, qr.brute_force(scene, rays))
+    a, b = _trace(scene, r0), _trace(scene, r1)
+    assert ((b[1] < 0) | (b[0] > np.float32(1e-4))).all()
+    assert (a[0][a[1] >= 0] <= b[0][a[1] >= 0]).all()
+
+
+def test_rays_that_need_no_search():
+    scene = _scene("sah")
+    rays = qr.special_rays()
+    for any_hit in (False, True):
+        t, tri, u, v = _trace(scene, rays, any_hit)
+        assert (tri == -1).all() and (u == 0).all() and (v == 0).all()
+        assert np.array_equal(_bits(t), _bits(rays[:, 7]))
+
+
+def test_tmax_limits_the_search():
+    scene = _scene("sah", seed=37)
+    rays = qr.incoherent_rays(scene, 400, seed=4)
+    t, tri, _, _ = _trace(scene, rays)
+    hit = tri >= 0
+    lim = rays.copy()
+    lim[hit, 7] = t[hit]  # tmax = the closest hit: that hit is excluded (t < tmax), nothing closer exists
+    t2, tri2, _, _ = _trace(scene, lim)
+    assert (tri2[hit] == -1).all() or (t2[hit & (tri2 >= 0)] < t[hit & (tri2 >= 0)]).all()
+    assert (tri2[hit] == -1).mean() > 0.95
+
+
+def test_empty_batch_and_empty_tree():
+    scene = _scene("sah")
+    t, tri, u, v = _trace(scene, np.zeros((0, 8), np.float32))
+    assert t.shape == (0,)
+    rays = _rays(scene, 50)
+    t, tri, _, _ = host.trace_rays(scene["vert"], scene["tri"], np.zeros((0, 9), np.float32), rays)
+    assert (tri == -1).all() and np.array_equal(_bits(t), _bits(rays[:, 7]))
+
+
+def test_denormal_ray_components_read_as_zero():
+    scene = _scene("sah", seed=38)
+    rays = _rays(scene, 200)
+    den = rays.copy()
+    den[:, 3] = np.float32(1e-42)  # a denormal tmin reads as +0
+    z = rays.copy()
+    z[:, 3] = np.float32(0.0)
+    for x, y in zip(_trace(scene, den), _trace(scene, z)):
+        assert np.array_equal(_bits(x), _bits(y))
+
+
+def test_matches_the_checker_at_the_renderer_limits():
+    """tmin = 1e-4, tmax = 1e8: the closest hit is the renderer's intersect() -- the checker's pt_traverse restated -- so every hit is also the brute
+    force's closest on rays without ties."""
+    scene = _scene("lbvh", seed=39)
+    rays = _rays(scene, 400)
+    rays[:, 3], rays[:, 7] = np.float32(1e-4), np.float32(1e8)
+    t, tri, _, _ = _trace(scene, rays)
+    hit, bt = qr.brute_force(scene, rays)[:2]
+    best = np.where(hit, bt, np.inf).min(1)
+    assert (t[tri >= 0] == best[tri >= 0]).all()
