@@ -125,6 +125,21 @@ int glrt_bvh_refit(const float *vert, size_t n_vert, const float *tri, size_t n_
 int glrt_trace_rays(const float *vert, size_t n_vert, const float *tri, size_t n_tri, const float *nodes, size_t n_nodes, const float *rays, size_t n,
                     float *hits_out, int flags);
 
+/* The feature pass: the CPU statement of the device's glrtx_render_features (include/glrtx.h "Denoising"), bit for bit.  Per pixel of the rows that rank
+ * `rank` of `world` owns under `stripe`-row stripes (rank 0 of 1: the whole image), in the device's local row order: the primary ray through the pixel's
+ * centre (the renderer's camera ray with both random numbers 0.5 and no thin lens; c2w / s2c: glrtx_params' matrices), its closest hit by glrt_trace_rays'
+ * walker with tmin 1e-4 and tmax 1e8, and there
+ *   out_n: {nx, ny, nz, t}   the renderer's shading normal (a NaN component stored as 0x7FC00000) and the hit distance; {0, 0, 0, 0} on a miss;
+ *   out_a: {r, g, b, id}     param0 of a diffuse material (type 2), {1, 1, 1} for every other type and on a miss; id: the material index as int32 bits, -1 on a miss.
+ * Both rows x width x 4 floats, rows packed.  mat: n_mat x GLRT_MATERIAL_FLOATS.  Errors: glrt_trace_rays', and GLRT_HOST_EINDEX for a material index out of range. */
+int glrt_render_features(const float *vert, size_t n_vert, const float *tri, size_t n_tri, const float *nodes, size_t n_nodes, const float *mat, size_t n_mat,
+                         const float *c2w, const float *s2c, int width, int height, int rank, int world, int stripe, float *out_n, float *out_a);
+/* The edge-avoiding a-trous filter: the CPU statement of the device's glrtx_denoise / glrtx_debug_denoise (include/glrtx.h "Denoising": the formulas are
+ * there), bit for bit.  accum: float4(rgb sum, count); normal_depth / albedo_id: the two feature planes; out: float4(rgb, 1); all width x rows x 4 floats, rows
+ * packed.  GLRT_HOST_EINVAL: a NULL array, a size outside 1..65536, iterations outside 1..6, a sigma that is not a positive finite number. */
+int glrt_denoise_atrous(const float *accum, const float *normal_depth, const float *albedo_id, int width, int rows, int iterations, float sigma_color,
+                        float sigma_normal, float sigma_depth, int demodulate, float *out);
+
 void glrt_look_at(const float eye[3], const float center[3], const float up[3], float out[16]);
 void glrt_perspective(float fovy_deg, float aspect, float z_near, float z_far, float out[16]);
 void glrt_mat4_mul(const float a[16], const float b[16], float out[16]);

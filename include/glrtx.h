@@ -446,6 +446,52 @@ int glrtx_read_adaptive_half(glrtx_ctx *ctx, float *dst_rgba, size_t dst_pitch_b
 int glrtx_debug_adaptive_select(const float *accum, const float *half, int width, int rows, float threshold, int min_samples, uint8_t *mask_out,
                                 float *err_out, int *list_out, int *count_out);
 
+/* ---- Denoising: feature planes and an edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) for low-sample frames (no reference counterpart; off
+ * unless called: no other call changes what it does, and nothing here ever writes the accumulator, the adaptive half buffer, the present ring or glrtx_stats.rays).
+ *   glrtx_render_features  fills two context-owned float4 planes over the owned rows (allocated on first use, released by glrtx_resize and so by a partition
+ *                          change), on the context's stream behind whatever was issued, sealing an open fed launch first:
+ *                              plane N {nx, ny, nz, t}   shading normal (the renderer's, a NaN component stored as 0x7FC00000) and distance of the closest hit;
+ *                                                        {0, 0, 0, 0} on a miss;
+ *                              plane A {r, g, b, id}     param0 of a diffuse material (type 2), {1, 1, 1} for every other type and on a miss; id: the material
+ *                                                        index as int32 bits, -1 on a miss.
+ *                          The ray of pixel (x, y) is the renderer's primary ray with both pixel random numbers 0.5 and no thin lens, whatever params->aperture
+ *                          is (only c2w and s2c are read); the search is a primary ray's (t in (1e-4, 1e8)), by the renderer's own traversal, in either node
+ *                          layout and on vines.  GLRTX_EINVAL: no scene, no size, spheres uploaded (no triangle normal to report).
+ *   glrtx_read_features    syncs, then copies the planes (owned rows, `pitch_bytes` per row in both destinations).
+ *   glrtx_denoise          filters I = acc.rgb / acc.w, guided by the feature planes AS THEY STAND (render them again after a camera move or a vertex update),
+ *                          into a context-owned float4 image D {rgb, 1}.  Issued on the context's stream without a sync; an open fed launch is sealed first.
+ *                          A pixel is DEAD when acc.w is a zero or a denormal, or when its id is INT32_MIN (reserved); dead pixels come out {0, 0, 0} and weigh 0
+ *                          as taps.  With demodulate, a = max(albedo, 1e-3) per channel (a > 1e-3 ? a : 1e-3) and c = I / a, else c = I.  Iteration i = 0 ..
+ *                          iterations - 1, for every live centre p and the 25 taps q = p + 2^i (dx, dy), dx, dy in -2..2, dy outermost (row-major):
+ *                              w(q) = (k[dy+2] k[dx+2]) * lp_exp(-((dc / sc_i + dn / sigma_normal) + min(dd, 80)))          k = {1, 4, 6, 4, 1} / 16
+ *                              dc = (dr dr + dg dg) + db db  over c_q - c_p;   dn likewise over n_q - n_p;   sc_i = sigma_color * 4^-i (a denormal: 0)
+ *                              dd = (r r) / sigma_depth,  r = (t_q - t_p) / max(t_p, 1e-6);   min(dd, 80) = dd < 80 ? dd : 80
+ *                              c'_p = (sum w(q) c_q) / max(sum w(q), 1e-20)
+ *                          over the taps that lie inside the image, are alive and carry p's id (the others are skipped, not added as zeros); both sums start at
+ *                          0 and grow in tap order; max(s, 1e-20) = s > 1e-20 ? s : 1e-20.  After the last iteration c is multiplied by a again (demodulate).
+ *                          lp_exp is the renderer's exponential (csrc/pt_kernel.hip.h).  Every fp32 operation is one correctly rounded operation, unfused,
+ *                          denormals flushed; every value stored is 0x7FC00000 when it is a NaN.  glrt_denoise_atrous (glrt_host.h) and
+ *                          tests/denoise_math.py state the same arithmetic; the three agree bit for bit.  "Inside the image" means inside the context's
+ *                          owned rows, taken as one image in local row order: a partitioned context filters its own rows only, and groups have no denoise call
+ *                          (out of scope).  GLRTX_EINVAL: iterations outside 1..6, a sigma that is not a positive finite number, no accumulator, no feature
+ *                          planes, or planes of another shape than the image now has.
+ *   glrtx_read_denoised    syncs, then copies D like glrtx_read_accum.
+ *   glrtx_resolve_denoised_rgba8  D through glrtx_resolve_rgba8's kernel (D's count word is 1, so its division changes nothing): the 8-bit image of D.
+ *   glrtx_debug_denoise    the filter on caller arrays (width x rows float4 each, rows packed) on the current HIP device, no context. */
+typedef struct glrtx_denoise_cfg {
+    int   iterations;    /* 1..6; iteration i uses tap spacing 2^i */
+    float sigma_color;   /* iteration i uses sigma_color * 4^-i */
+    float sigma_normal;
+    float sigma_depth;
+    int   demodulate;    /* 1: filter I / max(albedo, 1e-3), multiply back at the end */
+} glrtx_denoise_cfg;
+int glrtx_render_features(glrtx_ctx *ctx, const glrtx_params *params);
+int glrtx_read_features(glrtx_ctx *ctx, float *normal_depth, float *albedo_id, size_t pitch_bytes);
+int glrtx_denoise(glrtx_ctx *ctx, const glrtx_denoise_cfg *cfg);
+int glrtx_read_denoised(glrtx_ctx *ctx, float *dst_rgba, size_t dst_pitch_bytes);
+int glrtx_resolve_denoised_rgba8(glrtx_ctx *ctx, uint8_t *dst, size_t dst_pitch_bytes, float gamma, int flip_y);
+int glrtx_debug_denoise(const float *accum, const float *normal_depth, const float *albedo_id, int width, int rows, const glrtx_denoise_cfg *cfg, float *out);
+
 /* ---- Groups: the same device layer on several GPUs of one node, behind one handle and one host thread.
  * No reference counterpart (the reference is single-GPU); SURVEY.md 8(b) sketches glrtx_create(ctx**, device_ids, n) with a
  * gathering read_accum -- this is that, kept apart from the single-context calls.  Member i owns the 8-row stripes s with

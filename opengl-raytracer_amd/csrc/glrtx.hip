@@ -23,6 +23,8 @@
 #include "sahl.hip.h"
 #include "refit.hip.h"
 #include "query.hip.h"
+#include "features.hip.h"
+#include "denoise.hip.h"
 static_assert(glrtx::lbvh::kRotationPasses == GLRT_LBVH_ROTATION_PASSES, "device and CPU LBVH statements must run the same rotation sweeps");
 static_assert(glrtx::lbvh::kRebuildLeaves == GLRT_LBVH_REBUILD_LEAVES, "device and CPU LBVH statements must rebuild the same subtrees");
 
@@ -182,6 +184,12 @@ struct glrtx_ctx {
     size_t ad_pitch = 0;
     int ad_rows = 0, ad_tiles = 0, ad_tiles_x = 0;  // (ad_tiles, ad_tiles_x: the tile grid of the last selection)
     bool ad_selected = false, adapt_launch = false;
+
+    // Denoising (glrtx_render_features / glrtx_denoise): the two feature planes, the filter's two ping-pong images and its result D, all packed rows of ft_w float4 over
+    // ft_rows rows -- the shape of the owned rows when the features were rendered; allocated on first use, released by glrtx_resize (and so by a partition change)
+    DevBuf ftN, ftA, ftCounter, dnP[2], dnD;
+    int ft_w = 0, ft_rows = -1;   // (-1: no features)
+    bool dn_have = false;         // D holds a result of the current shape
 
     bool count_rays = false;
     const char *last_kernel = "";  // name of the last render kernel launched (error reports)
@@ -1396,6 +1404,54 @@ int launch_wgwf(glrtx_ctx *c, const KernelArgs &a_in, const glrtx_params *p, con
 }
 
 
+// ---- denoising (glrtx_render_features, glrtx_denoise)
+void denoise_release(glrtx_ctx *c) {
+    dev_free(c->ftN); dev_free(c->ftA); dev_free(c->ftCounter); dev_free(c->dnP[0]); dev_free(c->dnP[1]); dev_free(c->dnD);
+    c->ft_w = 0; c->ft_rows = -1; c->dn_have = false;
+}
+
+int denoise_cfg_check(glrtx_ctx *c, const glrtx_denoise_cfg *cfg, const char *fn) {
+    if (!cfg) return fail(c, GLRTX_EINVAL, "%s: NULL cfg", fn);
+    if (cfg->iterations < 1 || cfg->iterations > 6) return fail(c, GLRTX_EINVAL, "%s: iterations %d outside 1..6", fn, cfg->iterations);
+    const float sg[3] = {cfg->sigma_color, cfg->sigma_normal, cfg->sigma_depth};
+    for (float v : sg)
+        if (!(v > 0.0f) || std::isinf(v)) return fail(c, GLRTX_EINVAL, "%s: sigma %g is not a positive finite number", fn, (double)v);
+    return GLRTX_OK;
+}
+
+// The filter's passes on `stream`: accum (pitch_f4) + the two feature planes -> D, through the ping-pong images p0 / p1 (all but accum packed rows of `width`).
+int denoise_passes(glrtx_ctx *c, hipStream_t stream, const float4 *accum, int pitch_f4, const float4 *guide, const float4 *albedo, float4 *p0, float4 *p1, float4 *D,
+                   int width, int rows, const glrtx_denoise_cfg *cfg) {
+    const dim3 grid((unsigned)(((width + denoise::kTileDn - 1) / denoise::kTileDn) * ((rows + denoise::kTileDn - 1) / denoise::kTileDn)));
+    const int demod = cfg->demodulate ? 1 : 0;
+    hipLaunchKernelGGL(denoise::denoise_prep, grid, dim3(256), 0, stream, accum, pitch_f4, albedo, p0, width, rows, demod);
+    HIP_TRY(c, hipGetLastError());
+    float4 *img[2] = {p0, p1};
+    for (int it = 0; it < cfg->iterations; it++) {
+        const bool last = it == cfg->iterations - 1;
+        denoise::Args a;
+        a.src = img[it & 1]; a.guide = guide; a.albedo = albedo; a.dst = last ? D : img[(it + 1) & 1];
+        a.width = width; a.rows = rows; a.spacing = 1 << it;
+        uint32_t pw = (uint32_t)(127 - 2 * it) << 23;  // 4^-it
+        float scale;
+        std::memcpy(&scale, &pw, 4);
+        float sc = cfg->sigma_color * scale;
+        uint32_t scb;
+        std::memcpy(&scb, &sc, 4);
+        if ((scb & 0x7F800000u) == 0u) sc = 0.0f;  // (a denormal: the device would read it as zero)
+        a.sigma_color_i = sc; a.sigma_normal = cfg->sigma_normal; a.sigma_depth = cfg->sigma_depth;
+        a.demodulate = demod;
+        using Kernel = void (*)(const denoise::Args);
+        const Kernel k = it == 0 ? (last ? (Kernel)denoise::denoise_atrous<1, true> : (Kernel)denoise::denoise_atrous<1, false>)
+                       : it == 1 ? (last ? (Kernel)denoise::denoise_atrous<2, true> : (Kernel)denoise::denoise_atrous<2, false>)
+                                 : (last ? (Kernel)denoise::denoise_atrous<0, true> : (Kernel)denoise::denoise_atrous<0, false>);
+        hipLaunchKernelGGL(k, grid, dim3(256), 0, stream, a);
+        HIP_TRY(c, hipGetLastError());
+    }
+    return GLRTX_OK;
+}
+
+
 // ---- adaptive sampling (glrtx_render_adaptive)
 // The half buffer H at the accumulator's current shape, zeroed (on first adaptive use, at a clear or resize, and when the accumulator's pitch or rows have changed).
 int adapt_half_ensure(glrtx_ctx *c) {
@@ -1560,6 +1616,7 @@ void glrtx_destroy(glrtx_ctx *c) {
     dev_free(c->spheres); dev_free(c->sphereMat); dev_free(c->volDensity); dev_free(c->volTemp); dev_free(c->forks); dev_free(c->cnodes); dev_free(c->cranks); dev_free(c->nrms); dev_free(c->mats); dev_free(c->lights); dev_free(c->vine);
     dev_free(c->accum_own); dev_free(c->counter); dev_free(c->rgba8); dev_free(c->work);
     dev_free(c->adHalf); dev_free(c->adMask); dev_free(c->adList); dev_free(c->adCount);
+    denoise_release(c);
     dev_free(c->wfState); dev_free(c->wfQ); dev_free(c->wfSeeds); dev_free(c->wfPlanes);
     dev_free(c->bvhVert); dev_free(c->bvhTri); dev_free(c->bvhNodes);
     dev_free(c->rf.ints); dev_free(c->rf.keys); dev_free(c->rf.vert);
@@ -2076,6 +2133,7 @@ int glrtx_resize(glrtx_ctx *c, int width, int height) {
             return fail(c, GLRTX_EINVAL, "glrtx_resize: %dx%d (%d owned rows) does not fit the bound accumulator (%zu-byte rows, %d rows); unbind it first",
                         width, height, rows, c->pitch_bytes, c->bound_rows);
     }
+    denoise_release(c);  // (the feature planes and the filter's images have the old shape; the stream is idle)
     c->width = width; c->height = height;
     c->owned_rows = owned_rows_of(height, c->rank, c->world, c->stripe);
     c->st.width = width; c->st.height = height; c->st.owned_rows = c->owned_rows;
@@ -2315,6 +2373,151 @@ int glrtx_debug_adaptive_select(const float *accum, const float *half, int width
     if (e == hipSuccess && count_out) e = hipMemcpy(count_out, d_count, sizeof(int), hipMemcpyDeviceToHost);
     const int rc = e != hipSuccess ? fail(nullptr, GLRTX_EDEVICE, "%s: %s", fn, hipGetErrorString(e)) : GLRTX_OK;
     for (void *q : {d_acc, d_half, d_mask, d_err, d_list, d_count})
+        if (q) (void)hipFree(q);
+    return rc;
+}
+
+
+// ---- denoising
+int glrtx_render_features(glrtx_ctx *c, const glrtx_params *p) {
+    const char *fn = "glrtx_render_features";
+    if (!c) return GLRTX_EINVAL;
+    if (!p) return fail(c, GLRTX_EINVAL, "%s: NULL params", fn);
+    if (!c->have_scene) return fail(c, GLRTX_EINVAL, "%s: no scene uploaded", fn);
+    if (c->n_spheres > 0) return fail(c, GLRTX_EINVAL, "%s: spheres are uploaded (an analytic sphere has no triangle normal to report)", fn);
+    if (!c->accum || c->width < 1) return fail(c, GLRTX_EINVAL, "%s: no size (call glrtx_resize)", fn);
+    const int tiles8_x = (c->width + 7) / 8, tiles8_y = (c->owned_rows + 7) / 8;
+    if ((size_t)tiles8_x * tiles8_y >= ((size_t)1 << 25)) return fail(c, GLRTX_EINVAL, "%s: %dx%d owned pixels (at most 2^31 tile-order ids)", fn, c->width, c->owned_rows);
+    seal_feed(c);
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t bytes = (size_t)c->width * (size_t)std::max(c->owned_rows, 1) * sizeof(float4);
+    int rc;
+    if ((rc = ensure(c, c->ftN, bytes)) || (rc = ensure(c, c->ftA, bytes)) || (rc = ensure(c, c->ftCounter, sizeof(unsigned)))) return rc;
+    c->ft_w = c->width; c->ft_rows = c->owned_rows;
+    if (c->owned_rows == 0) return GLRTX_OK;
+    const bool vine = c->sc.n_vine > 0;
+    const int fetch = wgwf_fetch(c, vine);
+    const int lds_stack = 2 * c->sc.stack_entries * kBlockThreads * (int)sizeof(int), lds_ranks = c->sc.n_crank * (int)sizeof(uint2);
+    bool compact = wgwf_compact(c, vine, fetch);  // the node layout, chosen as trace_launch chooses it
+    if (const char *v = std::getenv("GLRTX_COMPACT_NODES")) compact = std::atoi(v) != 0 && !vine && c->sc.n_crank > 0;
+    compact = compact && lds_stack + lds_ranks <= 160 * 1024;
+    using Kernel = void (*)(const features::Args);
+    const Kernel kernel = vine ? (Kernel)features::features_vine : compact ? (Kernel)features::features_tree<true> : (Kernel)features::features_tree<false>;
+    const int lds = vine ? 0 : lds_stack + (compact ? lds_ranks : 0);
+    if (lds > 64 * 1024) HIP_TRY(c, hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    int per_cu = 0;
+    HIP_TRY(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kBlockThreads, lds));
+    per_cu = std::max(per_cu, 1);
+    features::Args a;
+    a.sc = c->sc;
+    std::memcpy(a.cam, p->c2w, 16 * sizeof(float));
+    std::memcpy(a.cam + 16, p->s2c, 16 * sizeof(float));
+    a.width = c->width; a.height = c->height;
+    a.owned_rows = c->owned_rows; a.rank = c->rank; a.world = c->world; a.stripe = c->stripe;
+    a.tiles8_x = tiles8_x;
+    a.n = (unsigned)(tiles8_x * tiles8_y) * 64u;
+    a.out_n = (float4 *)c->ftN.p; a.out_a = (float4 *)c->ftA.p;
+    a.counter = (unsigned *)c->ftCounter.p;
+    const size_t needed = (a.n + kBlockThreads - 1) / kBlockThreads;
+    const unsigned grid = (unsigned)std::max<size_t>(1, std::min<size_t>((size_t)per_cu * (size_t)c->n_cu, needed));
+    HIP_TRY(c, hipMemsetAsync(c->ftCounter.p, 0, sizeof(unsigned), c->stream));
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlockThreads), lds, c->stream, a);
+    HIP_TRY(c, hipGetLastError());
+    return GLRTX_OK;
+}
+
+static int denoise_shape_check(glrtx_ctx *c, const char *fn, bool need_result) {
+    if (c->ft_rows < 0 || !c->ftN.p) return fail(c, GLRTX_EINVAL, "%s: no feature planes (call glrtx_render_features first)", fn);
+    if (c->ft_w != c->width || c->ft_rows != c->owned_rows) return fail(c, GLRTX_EINVAL, "%s: the image changed shape since the features were rendered", fn);
+    if (need_result && !c->dn_have) return fail(c, GLRTX_EINVAL, "%s: no denoised image (call glrtx_denoise first)", fn);
+    return GLRTX_OK;
+}
+
+int glrtx_read_features(glrtx_ctx *c, float *normal_depth, float *albedo_id, size_t pitch_bytes) {
+    const char *fn = "glrtx_read_features";
+    if (!c || !normal_depth || !albedo_id) return GLRTX_EINVAL;
+    if (int rc = denoise_shape_check(c, fn, false)) return rc;
+    const size_t row = (size_t)c->width * sizeof(float4);
+    if (pitch_bytes < row) return fail(c, GLRTX_EINVAL, "%s: pitch too small", fn);
+    if (int rc = glrtx_sync(c)) return rc;
+    if (c->owned_rows == 0) return GLRTX_OK;
+    HIP_TRY(c, hipMemcpy2D(normal_depth, pitch_bytes, c->ftN.p, row, row, (size_t)c->owned_rows, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy2D(albedo_id, pitch_bytes, c->ftA.p, row, row, (size_t)c->owned_rows, hipMemcpyDeviceToHost));
+    return GLRTX_OK;
+}
+
+int glrtx_denoise(glrtx_ctx *c, const glrtx_denoise_cfg *cfg) {
+    const char *fn = "glrtx_denoise";
+    if (!c) return GLRTX_EINVAL;
+    if (int rc = denoise_cfg_check(c, cfg, fn)) return rc;
+    if (!c->accum || c->width < 1) return fail(c, GLRTX_EINVAL, "%s: no accumulator (call glrtx_resize)", fn);
+    if (int rc = denoise_shape_check(c, fn, false)) return rc;
+    seal_feed(c);
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t bytes = (size_t)c->width * (size_t)std::max(c->owned_rows, 1) * sizeof(float4);
+    int rc;
+    if ((rc = ensure(c, c->dnP[0], bytes)) || (rc = ensure(c, c->dnP[1], bytes)) || (rc = ensure(c, c->dnD, bytes))) return rc;
+    c->dn_have = true;
+    if (c->owned_rows == 0) return GLRTX_OK;
+    return denoise_passes(c, c->stream, c->accum, (int)(c->pitch_bytes / sizeof(float4)), (const float4 *)c->ftN.p, (const float4 *)c->ftA.p, (float4 *)c->dnP[0].p,
+                          (float4 *)c->dnP[1].p, (float4 *)c->dnD.p, c->width, c->owned_rows, cfg);
+}
+
+int glrtx_read_denoised(glrtx_ctx *c, float *dst, size_t dst_pitch_bytes) {
+    const char *fn = "glrtx_read_denoised";
+    if (!c || !dst) return GLRTX_EINVAL;
+    if (int rc = denoise_shape_check(c, fn, true)) return rc;
+    const size_t row = (size_t)c->width * sizeof(float4);
+    if (dst_pitch_bytes < row) return fail(c, GLRTX_EINVAL, "%s: dst pitch too small", fn);
+    if (int rc = glrtx_sync(c)) return rc;
+    if (c->owned_rows == 0) return GLRTX_OK;
+    HIP_TRY(c, hipMemcpy2D(dst, dst_pitch_bytes, c->dnD.p, row, row, (size_t)c->owned_rows, hipMemcpyDeviceToHost));
+    return GLRTX_OK;
+}
+
+// D through the resolve: resolve_kernel with D as its source (a mean with the count word 1: the kernel's division is exact).
+int glrtx_resolve_denoised_rgba8(glrtx_ctx *c, uint8_t *dst, size_t dst_pitch_bytes, float gamma, int flip_y) {
+    const char *fn = "glrtx_resolve_denoised_rgba8";
+    if (!c || !dst) return GLRTX_EINVAL;
+    if (int rc = denoise_shape_check(c, fn, true)) return rc;
+    if (!(gamma > 0.f)) return fail(c, GLRTX_EINVAL, "%s: gamma must be positive", fn);
+    if (dst_pitch_bytes < (size_t)c->width * 4) return fail(c, GLRTX_EINVAL, "%s: dst pitch too small", fn);
+    seal_feed(c);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (c->owned_rows == 0) return glrtx_sync(c);
+    const size_t bytes = (size_t)c->width * 4 * (size_t)c->owned_rows;
+    if (c->rgba8.bytes < bytes) {
+        dev_free(c->rgba8);
+        HIP_TRY(c, hipMalloc(&c->rgba8.p, bytes));
+        c->rgba8.bytes = bytes;
+    }
+    hipLaunchKernelGGL(resolve_kernel<kResolvePer>, resolve_grid(c->width, c->owned_rows), dim3(256), 0, c->stream, (const float4 *)c->dnD.p, c->width, c->width,
+                       c->owned_rows, (uchar4 *)c->rgba8.p, c->width, 1.0f / gamma, flip_y ? 1 : 0);
+    HIP_TRY(c, hipGetLastError());
+    if (int rc = glrtx_sync(c)) return rc;
+    HIP_TRY(c, hipMemcpy2D(dst, dst_pitch_bytes, c->rgba8.p, (size_t)c->width * 4, (size_t)c->width * 4, (size_t)c->owned_rows, hipMemcpyDeviceToHost));
+    return GLRTX_OK;
+}
+
+int glrtx_debug_denoise(const float *accum, const float *normal_depth, const float *albedo_id, int width, int rows, const glrtx_denoise_cfg *cfg, float *out) {
+    const char *fn = "glrtx_debug_denoise";
+    if (width < 1 || rows < 1 || width > 65536 || rows > 65536) return fail(nullptr, GLRTX_EINVAL, "%s: bad size %dx%d", fn, width, rows);
+    if (!accum || !normal_depth || !albedo_id || !out) return fail(nullptr, GLRTX_EINVAL, "%s: NULL buffer", fn);
+    if (int rc = denoise_cfg_check(nullptr, cfg, fn)) return rc;
+    const size_t bytes = (size_t)width * rows * sizeof(float4);
+    void *d[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // accum, guide, albedo, p0, p1, D
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < 6 && e == hipSuccess; i++) e = hipMalloc(&d[i], bytes);
+    if (e == hipSuccess) e = hipMemcpy(d[0], accum, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d[1], normal_depth, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d[2], albedo_id, bytes, hipMemcpyHostToDevice);
+    int rc = GLRTX_OK;
+    if (e == hipSuccess)
+        rc = denoise_passes(nullptr, 0, (const float4 *)d[0], width, (const float4 *)d[1], (const float4 *)d[2], (float4 *)d[3], (float4 *)d[4], (float4 *)d[5], width, rows, cfg);
+    if (e == hipSuccess && rc == GLRTX_OK) e = hipDeviceSynchronize();
+    if (e == hipSuccess && rc == GLRTX_OK) e = hipMemcpy(out, d[5], bytes, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) rc = fail(nullptr, GLRTX_EDEVICE, "%s: %s", fn, hipGetErrorString(e));
+    for (void *q : d)
         if (q) (void)hipFree(q);
     return rc;
 }

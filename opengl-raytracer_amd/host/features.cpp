@@ -1,0 +1,109 @@
+// features.cpp -- glrt_render_features (include/glrt_host.h): the CPU statement of the device's feature pass (glrtx_render_features, include/glrtx.h;
+// csrc/features.hip.h), on the wire-format scene.
+//
+// Per owned pixel: the primary ray of the pixel's centre (the renderer's camera_ray with r0 = r1 = 0.5 and no thin lens, the same expressions in the same
+// order, unfused), searched by glrt_trace_rays' walker (host/query.cpp) with tmin = 1e-4 and tmax = 1e8 -- what a primary ray of the renderer is given --,
+// then the renderer's shading normal (surf_tri: barycentric mix of the vertex normals, IEEE sqrt, IEEE reciprocal) and the hit material's albedo.
+// Compiled with -ffp-contract=off and run under MXCSR FTZ | DAZ, like host/query.cpp: the device's arithmetic, bit for bit.
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+#include <vector>
+#if defined(__SSE__)
+#include <xmmintrin.h>
+#endif
+
+#include "glrt_host.h"
+
+namespace {
+
+constexpr float kEps = 1.0e-4f;    // PT_EPS: a primary ray's tmin
+constexpr float kInfty = 1.0e8f;   // PT_INFTY: its search limit
+
+struct FlushDenormals {
+#if defined(__SSE__)
+    unsigned csr = _mm_getcsr();
+    FlushDenormals() { _mm_setcsr(csr | 0x8040u); }
+    ~FlushDenormals() { _mm_setcsr(csr); }
+#endif
+};
+
+// a NaN is stored as 0x7FC00000 on both sides (which NaN an operation yields is the one thing the two instruction sets do not share)
+inline float canon(float x) { const uint32_t q = 0x7FC00000u; float n; std::memcpy(&n, &q, 4); return x != x ? n : x; }
+inline float rsq(float x) { return 1.0f / std::sqrt(x); }
+inline float dot3(float ax, float ay, float az, float bx, float by, float bz) { return (az * bz + ay * by) + ax * bx; }
+
+// camera_ray (csrc/pt_kernel.hip.h) at the pixel centre: fcx + r0 = (x + 0.5) + 0.5, the lens offset (lox, loy) = (0, 0) kept in the expressions
+void centre_ray(const float *C, const float *S, float W, float H, int x, int y, float *ray) {
+    const float fcx = (float)x + 0.5f, fcy = (float)y + 0.5f;
+    const float nx = ((fcx + 0.5f) / W) * 2.0f + -1.0f;
+    const float ny = ((fcy + 0.5f) / H) * 2.0f + -1.0f;
+    const float tx = (S[0] * nx + S[12]) + S[4] * ny;
+    const float ty = (S[1] * nx + S[13]) + S[5] * ny;
+    const float tz = (S[2] * nx + S[14]) + S[6] * ny;
+    const float tw = (S[3] * nx + S[15]) + S[7] * ny;
+    const float cx = tx / tw, cy = ty / tw, cz = tz / tw;
+    const float rn = rsq((cz * cz + cy * cy) + cx * cx);
+    const float dx = cx * rn, dy = cy * rn, dz = cz * rn;
+    const float lox = 0.0f, loy = 0.0f;
+    const float wx = (C[0] * lox + C[12]) + C[4] * loy;
+    const float wy = (C[1] * lox + C[13]) + C[5] * loy;
+    const float wz = (C[2] * lox + C[14]) + C[6] * loy;
+    const float ww = (C[3] * lox + C[15]) + C[7] * loy;
+    const float ex = (C[0] * dx + C[4] * dy) + C[8] * dz;
+    const float ey = (C[1] * dx + C[5] * dy) + C[9] * dz;
+    const float ez = (C[2] * dx + C[6] * dy) + C[10] * dz;
+    const float re = rsq((ez * ez + ey * ey) + ex * ex);
+    ray[0] = wx / ww; ray[1] = wy / ww; ray[2] = wz / ww; ray[3] = kEps;
+    ray[4] = ex * re; ray[5] = ey * re; ray[6] = ez * re; ray[7] = kInfty;
+}
+
+}  // namespace
+
+int glrt_render_features(const float *vert, size_t n_vert, const float *tri, size_t n_tri, const float *nodes, size_t n_nodes, const float *mat, size_t n_mat,
+                         const float *c2w, const float *s2c, int width, int height, int rank, int world, int stripe, float *out_n, float *out_a) {
+    if (!c2w || !s2c || !out_n || !out_a) return GLRT_HOST_EINVAL;
+    if (width < 1 || height < 1 || width > 65536 || height > 65536 || world < 1 || rank < 0 || rank >= world || stripe < 1) return GLRT_HOST_EINVAL;
+    if (n_nodes > 0 && (!vert || !tri || !nodes || !mat)) return GLRT_HOST_EINVAL;
+    for (size_t t = 0; t < n_tri; t++) {
+        const float m = tri[4 * t + 3];
+        if (!(m >= 0.0f) || (size_t)m >= n_mat) return GLRT_HOST_EINDEX;
+    }
+    // the owned rows, in the device's order: stripe s of the image belongs to rank s % world (glrtx_local_row_to_y)
+    std::vector<int> rows;
+    for (int y = 0; y < height; y++)
+        if ((y / stripe) % world == rank) rows.push_back(y);
+    if (rows.empty()) return GLRT_HOST_OK;
+    FlushDenormals ftz;
+    const size_t n = rows.size() * (size_t)width;
+    std::vector<float> rays(8 * n), hits(4 * n);
+    for (size_t r = 0; r < rows.size(); r++)
+        for (int x = 0; x < width; x++) centre_ray(c2w, s2c, (float)width, (float)height, x, rows[r], &rays[8 * (r * width + x)]);
+    if (const int rc = glrt_trace_rays(vert, n_vert, tri, n_tri, nodes, n_nodes, rays.data(), n, hits.data(), GLRT_TRACE_CLOSEST)) return rc;
+    for (size_t i = 0; i < n; i++) {
+        const float *h = &hits[4 * i];
+        float *N = out_n + 4 * i, *A = out_a + 4 * i;
+        int32_t t;
+        std::memcpy(&t, &h[1], 4);
+        int32_t id = -1;
+        N[0] = N[1] = N[2] = N[3] = 0.0f;
+        A[0] = A[1] = A[2] = 1.0f;
+        if (t >= 0) {
+            const float *tr = tri + 4 * (size_t)t;
+            const float *n0 = vert + GLRT_VERTEX_FLOATS * (size_t)tr[0] + 3, *n1 = vert + GLRT_VERTEX_FLOATS * (size_t)tr[1] + 3,
+                        *n2 = vert + GLRT_VERTEX_FLOATS * (size_t)tr[2] + 3;
+            const float u = h[2], v = h[3];
+            const float w0 = (1.0f - u) - v;
+            const float tx = (w0 * n0[0] + u * n1[0]) + v * n2[0];
+            const float ty = (w0 * n0[1] + u * n1[1]) + v * n2[1];
+            const float tz = (w0 * n0[2] + u * n1[2]) + v * n2[2];
+            const float r = rsq(dot3(tx, ty, tz, tx, ty, tz));
+            N[0] = canon(tx * r); N[1] = canon(ty * r); N[2] = canon(tz * r); N[3] = h[0];
+            id = (int32_t)tr[3];
+            const float *m = mat + GLRT_MATERIAL_FLOATS * (size_t)id;
+            if ((int)m[0] == 2) { A[0] = m[6]; A[1] = m[7]; A[2] = m[8]; }  // a diffuse material: param0
+        }
+        std::memcpy(&A[3], &id, 4);
+    }
+    return GLRT_HOST_OK;
+}

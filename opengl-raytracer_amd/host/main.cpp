@@ -14,7 +14,7 @@
 using namespace glrt;
 
 static void usage(const char *exe) {
-    std::printf("usage: %s -i scene.json [-s N] [--max-depth D] [--spp N] [--frames F] [--frames-in-flight B] [--bvh sah|sah-reinsert|sah-gpu|lbvh|sah-levels-cpu|lbvh-cpu|reference] [--order-by-hits] [--out file.png] [--save-every-frame] [--device G | --gpus N | --devices a,b,..] [--extensions] [--whitted] [--enable-volume] [--volume-wavefront] [--adaptive THRESHOLD [--min-spp N]]\n"
+    std::printf("usage: %s -i scene.json [-s N] [--max-depth D] [--spp N] [--frames F] [--frames-in-flight B] [--bvh sah|sah-reinsert|sah-gpu|lbvh|sah-levels-cpu|lbvh-cpu|reference] [--order-by-hits] [--out file.png] [--save-every-frame] [--device G | --gpus N | --devices a,b,..] [--extensions] [--whitted] [--enable-volume] [--volume-wavefront] [--adaptive THRESHOLD [--min-spp N]] [--denoise [--denoise-iters N]]\n"
                 "  -i, --input             scene description (JSON; schema: SURVEY.md Appendix C)            [required]\n"
                 "  -s, --sample-per-cycle  accepted for compatibility; like the reference (main.cpp:13) it is not read\n"
                 "      --max-depth D       u_maxDepth (default 16, the reference shader's default)\n"
@@ -37,7 +37,10 @@ static void usage(const char *exe) {
                 "                          the persistent megakernel, the default).  --enable-volume --adaptive T turns it on by itself\n"
                 "      --adaptive T        adaptive sampling: bursts of --frames-in-flight frames on the 8x8 tiles whose error is above T only, until no tile is\n"
                 "                          active or --frames frames have been issued; an \"Adaptive:\" line per burst (not with --save-every-frame)\n"
-                "      --min-spp N         with --adaptive: samples every pixel of a tile needs before the tile may retire (default 2, at least 2)\n", exe);
+                "      --min-spp N         with --adaptive: samples every pixel of a tile needs before the tile may retire (default 2, at least 2)\n"
+                "      --denoise           write the denoised image: feature planes once before the first frame, then the edge-avoiding a-trous filter over the\n"
+                "                          accumulated mean (one device; not with --save-every-frame).  Without it the output is what it always was\n"
+                "      --denoise-iters N   with --denoise: filter iterations, 1..6 (default 5)\n", exe);
 }
 
 int main(int argc, char **argv) {
@@ -46,6 +49,8 @@ int main(int argc, char **argv) {
     bool every_frame = false, extensions = false, whitted = false, order_by_hits = false, volume = false, adaptive = false, min_spp_given = false, volume_wavefront = false;
     float adapt_threshold = 0.0f;
     int min_spp = 2;
+    bool denoise = false;
+    int denoise_iters = 0;
     std::vector<int> devices;
     std::string bvh;
     for (int i = 1; i < argc; i++) {
@@ -71,6 +76,8 @@ int main(int argc, char **argv) {
         else if (a == "--volume-wavefront") volume_wavefront = true;
         else if (a == "--adaptive") { adaptive = true; adapt_threshold = (float)std::atof(next("--adaptive")); }
         else if (a == "--min-spp") { min_spp = std::atoi(next("--min-spp")); min_spp_given = true; }
+        else if (a == "--denoise") denoise = true;
+        else if (a == "--denoise-iters") denoise_iters = std::atoi(next("--denoise-iters"));
         else if (a == "--gpus") { const int n = std::atoi(next("--gpus")); devices.clear(); for (int k = 0; k < n; k++) devices.push_back(k); }
         else if (a == "--devices") {
             devices.clear();
@@ -81,6 +88,9 @@ int main(int argc, char **argv) {
     if (input.empty()) { usage(argv[0]); return 1; }
     if (min_spp_given && !adaptive) { std::fprintf(stderr, "--min-spp needs --adaptive\n"); return 1; }
     if (adaptive && (every_frame || min_spp < 2)) { std::fprintf(stderr, "--adaptive: not with --save-every-frame, and --min-spp must be at least 2\n"); return 1; }
+
+    if (denoise_iters != 0 && (!denoise || denoise_iters < 1 || denoise_iters > 6)) { std::fprintf(stderr, "--denoise-iters needs --denoise and a value in 1..6\n"); return 1; }
+    if (denoise && (every_frame || devices.size() > 1)) { std::fprintf(stderr, "--denoise: one device, and not with --save-every-frame\n"); return 1; }
 
     auto window = std::make_unique<Window>();
     if (devices.empty()) window->setDevice(device);
@@ -93,6 +103,7 @@ int main(int argc, char **argv) {
     window->setOrderChildrenByHits(order_by_hits);
     if (adaptive) window->setAdaptive(adapt_threshold, min_spp);
     window->setVolumeWavefront(volume_wavefront);
+    if (denoise) window->setDenoise(denoise_iters);
 
     auto scene = std::make_shared<Scene>();
     if (!bvh.empty()) scene->setBvhBuilder(bvh);

@@ -104,6 +104,13 @@ void Window::mainloop(const std::shared_ptr<Scene> &scene_, double fps) {
     // Launches are issued back to back and the loop waits for the device only where it needs the pixels (a frame that is saved, the end of the run): the calls are
     // asynchronous, and a launch issued behind idle time runs longer -- 2 % behind 1 ms, 5 % behind 3 ms (profiles/r04_ab_launch_warmth.txt).  lastFrameMs() is the wall
     // time per frame between two such waits.
+    if (denoise_) {  // the feature planes of this (static) camera, once, before the first frame
+        if (glrtx_group_size(grp_) != 1 || every) GLRT_FatalError("--denoise: one device, and not with --save-every-frame (groups and the present ring have no denoised form)");
+        glrtx_params p;
+        frameParams(p);
+        glrtx_ctx *c0 = glrtx_group_ctx(grp_, 0);
+        if (glrtx_render_features(c0, &p) != GLRTX_OK) GLRT_FatalError("glrtx_render_features: %s", glrtx_last_error(c0));
+    }
     auto t0 = std::chrono::steady_clock::now();
     if (every) {
         // The reference's cadence without its waits: every frame's image comes out of the ring the group presents into (glrtx_group_present_enable) -- resolved in the
@@ -234,7 +241,12 @@ void Window::saveCurrentFrame(const std::string &filename, bool overwrite) const
     std::vector<unsigned char> bytes((size_t)width_ * height_ * 4);
     // resolve = screen.frag (rgb/count, clamp, gamma 2.2) + the vertical flip of window.cpp:391-398
     // (with several GPUs the stripes are first gathered on the first one)
-    if (glrtx_group_resolve_rgba8(grp_, bytes.data(), (size_t)width_ * 4, 2.2f, 1) != GLRTX_OK)
+    if (denoise_) {  // the filter's result through the same resolve
+        glrtx_ctx *c0 = glrtx_group_ctx(grp_, 0);
+        if (glrtx_denoise(c0, &denoiseCfg_) != GLRTX_OK || glrtx_resolve_denoised_rgba8(c0, bytes.data(), (size_t)width_ * 4, 2.2f, 1) != GLRTX_OK)
+            GLRT_FatalError("glrtx_denoise: %s", glrtx_last_error(c0));
+        GLRT_Info("Denoise: %d iterations", denoiseCfg_.iterations);
+    } else if (glrtx_group_resolve_rgba8(grp_, bytes.data(), (size_t)width_ * 4, 2.2f, 1) != GLRTX_OK)
         GLRT_FatalError("glrtx_group_resolve_rgba8: %s", glrtx_group_last_error(grp_));
     saveImage(filename, overwrite, bytes.data());
 }

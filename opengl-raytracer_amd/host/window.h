@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "common.h"
+#include "glrtx.h"
 #include "scene.h"
 
 struct glrtx_group;
@@ -53,6 +54,9 @@ public:
     // Volume scenes on the wavefront kernel (glrtx_set_volume_wavefront on every member): frames in flight, fed launches and adaptive sampling with the volume
     // on; same images as the persistent megakernel, the default.  Adaptive sampling of a volume scene turns it on by itself.
     void setVolumeWavefront(bool on) { volumeWavefront_ = on; }
+    // Denoising (no reference counterpart; glrtx_render_features / glrtx_denoise, one device only): the feature planes are rendered once before the first frame, and
+    // every image that is written is the a-trous filter's result D instead of the raw mean.  iterations < 1: the default.
+    void setDenoise(int iterations) { denoise_ = true; if (iterations >= 1) denoiseCfg_.iterations = iterations; }
     // wall-clock ms PER FRAME between the last two waits for the device, averaged over the frames issued in between (with one PNG per run: the whole run, cold first
     // launches included; with --save-every-frame: the whole run, PNG writing included).  The device's own time of the last launch is glrtx_stats.kernel_ms_last.
     double lastFrameMs() const { return lastMs_; }
@@ -86,6 +90,8 @@ private:
     float adaptThreshold_ = 0.0f;
     int adaptMinSamples_ = 2;
     bool volumeWavefront_ = false;
+    bool denoise_ = false;
+    glrtx_denoise_cfg denoiseCfg_ = {5, 100.0f, 0.1f, 0.01f, 1};  // (DESIGN.md "Denoising": the sweep behind these; glrt_amd.host.DENOISE_DEFAULTS holds the same)
     bool fallbackNoted_ = false;
     std::string output_ = "output.png";
     double lastMs_ = 0.0;

@@ -41,6 +41,10 @@ class Adaptive(C.Structure):
     _fields_ = [("threshold", C.c_float), ("min_samples", C.c_int32)]
 
 
+class DenoiseCfg(C.Structure):
+    _fields_ = [("iterations", C.c_int), ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float), ("demodulate", C.c_int)]
+
+
 class Image(C.Structure):
     _fields_ = [("rgba", C.c_void_p), ("pitch_bytes", C.c_size_t), ("width", C.c_int32), ("rows", C.c_int32), ("frame", C.c_uint64)]
 
@@ -75,6 +79,7 @@ EXPORTS = ["glrtx_abi_version", "glrtx_create", "glrtx_destroy", "glrtx_last_err
            "glrtx_upload_volume", "glrtx_group_upload_volume", "glrtx_debug_volume_math", "glrtx_debug_volume_lookup",
            "glrtx_render_adaptive", "glrtx_adaptive_active_tiles", "glrtx_read_tile_mask", "glrtx_read_adaptive_half", "glrtx_debug_adaptive_select",
            "glrtx_group_render_adaptive", "glrtx_group_adaptive_active_tiles", "glrtx_debug_pack_compact", "glrtx_set_volume_wavefront",
+           "glrtx_render_features", "glrtx_read_features", "glrtx_denoise", "glrtx_read_denoised", "glrtx_resolve_denoised_rgba8", "glrtx_debug_denoise",
            "glrtx_update_vertices", "glrtx_update_vertices_device", "glrtx_group_update_vertices", "glrtx_debug_read_scene",
            "glrtx_trace_rays", "glrtx_trace_rays_device"]
 
@@ -182,6 +187,15 @@ def lib():
             L.glrtx_set_volume_wavefront.argtypes = [vp, C.c_int]
         except AttributeError:
             pass
+        try:  # (additive to ABI 10 as well: the denoiser)
+            L.glrtx_render_features.argtypes = [vp, C.POINTER(Params)]
+            L.glrtx_read_features.argtypes = [vp, vp, vp, C.c_size_t]
+            L.glrtx_denoise.argtypes = [vp, C.POINTER(DenoiseCfg)]
+            L.glrtx_read_denoised.argtypes = [vp, vp, C.c_size_t]
+            L.glrtx_resolve_denoised_rgba8.argtypes = [vp, vp, C.c_size_t, C.c_float, C.c_int]
+            L.glrtx_debug_denoise.argtypes = [fp, fp, fp, C.c_int, C.c_int, C.POINTER(DenoiseCfg), fp]
+        except AttributeError:
+            pass
         _lib = L
     return _lib
 
@@ -267,6 +281,28 @@ def adaptive_select(accum, half, threshold, min_samples):
     if rc != 0:
         raise GlrtxError(rc, L.glrtx_last_error(None).decode())
     return mask, err, lst[:n.value].copy()
+
+
+def denoise_cfg(iterations=None, sigma_color=None, sigma_normal=None, sigma_depth=None, demodulate=None) -> DenoiseCfg:
+    """A glrtx_denoise_cfg; None takes the default (glrt_amd.host.DENOISE_DEFAULTS)."""
+    from .host import DENOISE_DEFAULTS as d
+    pick = lambda v, k: d[k] if v is None else v
+    return DenoiseCfg(int(pick(iterations, "iterations")), float(pick(sigma_color, "sigma_color")), float(pick(sigma_normal, "sigma_normal")),
+                      float(pick(sigma_depth, "sigma_depth")), int(bool(pick(demodulate, "demodulate"))))
+
+
+def debug_denoise(accum, normal_depth, albedo_id, **cfg):
+    """glrtx_debug_denoise on the current device: the filter's kernels on (rows, width, 4) float32 arrays.  Returns D, float4(rgb, 1) per pixel."""
+    L = lib()
+    a, n, al = _f32(accum), _f32(normal_depth), _f32(albedo_id)
+    if a.ndim != 3 or a.shape[2] != 4 or n.shape != a.shape or al.shape != a.shape:
+        raise ValueError(f"debug_denoise: three (rows, width, 4) arrays of one shape expected, got {a.shape}, {n.shape}, {al.shape}")
+    out = np.zeros_like(a)
+    c = denoise_cfg(**cfg)
+    rc = L.glrtx_debug_denoise(_fp(a), _fp(n), _fp(al), a.shape[1], a.shape[0], C.byref(c), _fp(out))
+    if rc != 0:
+        raise GlrtxError(rc, L.glrtx_last_error(None).decode())
+    return out
 
 
 def _host_vertices(v):
@@ -561,6 +597,31 @@ class Device:
         s = self.stats()
         out = np.zeros((s.owned_rows, s.width, 4), np.float32)
         self._ck(self.L.glrtx_read_adaptive_half(self.h, out.ctypes.data, s.width * 16))
+        return out
+    def render_features(self, params):
+        """The denoiser's feature planes for this camera (glrtx_render_features): issued on the context's stream, nothing is read back."""
+        p = make_params(params)
+        self._ck(self.L.glrtx_render_features(self.h, C.byref(p)))
+    def read_features(self):
+        """(normal_depth, albedo_id): (owned_rows, width, 4) float32 each (syncs); albedo_id[..., 3] holds the material id as int32 bits, -1 on a miss."""
+        s = self.stats()
+        n, a = np.zeros((s.owned_rows, s.width, 4), np.float32), np.zeros((s.owned_rows, s.width, 4), np.float32)
+        self._ck(self.L.glrtx_read_features(self.h, n.ctypes.data, a.ctypes.data, s.width * 16))
+        return n, a
+    def denoise(self, iterations=None, sigma_color=None, sigma_normal=None, sigma_depth=None, demodulate=None):
+        """The a-trous filter over the accumulator's mean, guided by the feature planes as they stand (glrtx_denoise); None: the default."""
+        c = denoise_cfg(iterations, sigma_color, sigma_normal, sigma_depth, demodulate)
+        self._ck(self.L.glrtx_denoise(self.h, C.byref(c)))
+    def read_denoised(self) -> np.ndarray:
+        """The denoised image D, (owned_rows, width, 4) float32 {rgb, 1} (syncs)."""
+        s = self.stats()
+        out = np.zeros((s.owned_rows, s.width, 4), np.float32)
+        self._ck(self.L.glrtx_read_denoised(self.h, out.ctypes.data, s.width * 16))
+        return out
+    def resolve_denoised_rgba8(self, gamma=2.2, flip_y=True) -> np.ndarray:
+        s = self.stats()
+        out = np.zeros((s.owned_rows, s.width, 4), np.uint8)
+        self._ck(self.L.glrtx_resolve_denoised_rgba8(self.h, out.ctypes.data, s.width * 4, gamma, int(flip_y)))
         return out
     def timer_begin(self):
         self._ck(self.L.glrtx_timer_begin(self.h))

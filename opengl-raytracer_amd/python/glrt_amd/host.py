@@ -37,6 +37,8 @@ def lib():
         L.glrt_bvh_reinsert.argtypes = [fp, C.c_size_t, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double)]
         L.glrt_bvh_refit.argtypes = [fp, C.c_size_t, fp, C.c_size_t, fp, C.c_size_t]
         L.glrt_trace_rays.argtypes = [fp, C.c_size_t, fp, C.c_size_t, fp, C.c_size_t, fp, C.c_size_t, fp, C.c_int]
+        L.glrt_render_features.argtypes = [fp, C.c_size_t, fp, C.c_size_t, fp, C.c_size_t, fp, C.c_size_t, fp, fp] + [C.c_int] * 5 + [fp, fp]
+        L.glrt_denoise_atrous.argtypes = [fp, fp, fp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int, fp]
         L.glrt_look_at.argtypes = [fp, fp, fp, fp]
         L.glrt_perspective.argtypes = [C.c_float, C.c_float, C.c_float, C.c_float, fp]
         L.glrt_mat4_mul.argtypes = [fp, fp, fp]
@@ -154,6 +156,40 @@ def trace_rays(vert, tri, nodes, rays, any_hit=False):
     if rc != 0:
         raise RuntimeError(f"glrt_trace_rays failed: {rc}")
     return out[:, 0], out[:, 1].view(np.int32), out[:, 2], out[:, 3]
+
+
+def render_features(scene, params, width=None, height=None, rank=0, world=1, stripe=16):
+    """glrt_render_features: the CPU statement of Device.render_features (include/glrt_host.h) for the rows a partition owns (default: the whole image).
+    Returns (normal_depth, albedo_id): (owned_rows, width, 4) float32 each; albedo_id[..., 3] holds the material id as int32 bits (-1: a miss)."""
+    w, h = int(width or params["width"]), int(height or params["height"])
+    vert, tri = _f32(scene["vert"]).reshape(-1, 15), _f32(scene["tri"]).reshape(-1, 4)
+    nodes, mat = _f32(scene["bvh"]).reshape(-1, 9), _f32(scene["mat"]).reshape(-1, 18)
+    c2w, s2c = _f32(params["c2w"]).reshape(16), _f32(params["s2c"]).reshape(16)
+    rows = sum(1 for y in range(h) if (y // stripe) % world == rank)
+    n, a = np.zeros((rows, w, 4), np.float32), np.zeros((rows, w, 4), np.float32)
+    rc = lib().glrt_render_features(_fp(vert), vert.shape[0], _fp(tri), tri.shape[0], _fp(nodes), nodes.shape[0], _fp(mat), mat.shape[0], _fp(c2w), _fp(s2c),
+                                    w, h, rank, world, stripe, _fp(n), _fp(a))
+    if rc != 0:
+        raise RuntimeError(f"glrt_render_features failed: {rc}")
+    return n, a
+
+
+# The denoiser's defaults (DESIGN.md "Denoising": chosen from the sweep recorded there); Device.denoise takes the same.
+DENOISE_DEFAULTS = dict(iterations=5, sigma_color=100.0, sigma_normal=0.1, sigma_depth=0.01, demodulate=True)
+
+
+def denoise_atrous(accum, normal_depth, albedo_id, iterations=DENOISE_DEFAULTS["iterations"], sigma_color=DENOISE_DEFAULTS["sigma_color"],
+                   sigma_normal=DENOISE_DEFAULTS["sigma_normal"], sigma_depth=DENOISE_DEFAULTS["sigma_depth"], demodulate=DENOISE_DEFAULTS["demodulate"]):
+    """glrt_denoise_atrous: the CPU statement of Device.denoise on (rows, width, 4) float32 arrays.  Returns D, float4(rgb, 1) per pixel."""
+    a, n, al = _f32(accum), _f32(normal_depth), _f32(albedo_id)
+    if a.ndim != 3 or a.shape[2] != 4 or n.shape != a.shape or al.shape != a.shape:
+        raise ValueError(f"denoise_atrous: three (rows, width, 4) arrays of one shape expected, got {a.shape}, {n.shape}, {al.shape}")
+    out = np.zeros_like(a)
+    rc = lib().glrt_denoise_atrous(_fp(a), _fp(n), _fp(al), a.shape[1], a.shape[0], int(iterations), float(sigma_color), float(sigma_normal),
+                                   float(sigma_depth), int(bool(demodulate)), _fp(out))
+    if rc != 0:
+        raise RuntimeError(f"glrt_denoise_atrous failed: {rc}")
+    return out
 
 
 def look_at(eye, center, up) -> np.ndarray:
