@@ -117,7 +117,7 @@ int glrt_bvh_refit(const float *vert, size_t n_vert, const float *tri, size_t n_
  * flags: GLRT_TRACE_CLOSEST (the smallest t in (tmin, tmax); ties to the first triangle of the renderer's visiting order) or GLRT_TRACE_ANY (the first
  * accepted hit in that order).  A hit is what the renderer's triangle test accepts (|det| >= 1e-4) with t > tmin and t below the running limit, which starts
  * at tmax and also culls boxes; on a miss t = tmax, tri = -1, u = v = 0.  A ray with a NaN or infinite component, a zero direction or tmax <= tmin is not
- * searched (the miss record); denormal components are read as zeros of their sign.  Runs with denormals flushed (MXCSR FTZ | DAZ, restored on return).
+ * searched (the miss record); denormal components are read as zeros of their sign (a denormal tmax is the limit 0, and is echoed as 0).  Runs with denormals flushed (MXCSR FTZ | DAZ, restored on return).
  * n_nodes = 0: every ray misses.  GLRT_HOST_EINVAL: an unknown flag, NULL arrays with n > 0, a malformed tree (a child or leaf triangle out of range, a
  * node reached twice); GLRT_HOST_EINDEX: a reachable triangle with a vertex index out of range.  n = 0 succeeds and does nothing. */
 #define GLRT_TRACE_CLOSEST 0

@@ -114,7 +114,7 @@ typedef struct glrtx_stats {
     /* ABI 10 */
     int32_t shadow_limited;     /* which shadow-ray search the context's launches run: 0 the reference's own closest-hit search (default: bit-exact contract), 1 the
                                    range-limited one (glrtx_set_shadow_range_limit / GLRTX_SHADOW_LIMIT=1: outside the bit-exact contract).  bench.py prints it */
-    int32_t node_layout_last;   /* (was reserved2) wavefront kernel, last launch: 1 = the compact node array (48-byte records at breadth-first positions, three loads per step,
+    int32_t node_layout_last;   /* (was reserved2) wavefront kernel or ray query (glrtx_trace_rays*), last launch: 1 = the compact node array (48-byte records at breadth-first positions, three loads per step,
                                    the children located through a rank table in LDS), 0 = the 64-byte records.  The compact layout serves node_fetch_last 0 when its rank table fits
                                    in LDS with four workgroups per CU; GLRTX_COMPACT_NODES=0/1 forces it.  Bit-identical either way */
     uint64_t feed_launches;     /* fed launches since reset_stats: launches that stayed open for the calls behind them (see glrtx_render) */
@@ -165,7 +165,10 @@ int glrtx_update_vertices_device(glrtx_ctx *ctx, const void *dev_vert, size_t n_
  *                        bit the hit the path tracer computes for the same ray under the same tree.
  *   GLRTX_TRACE_ANY      the first accepted hit in that visiting order (deterministic for a given tree): visibility and shadow tests.
  * A ray with a NaN or infinite component, a zero direction or tmax <= tmin is not searched: its answer is the miss record (t = tmax as given).  Denormal
- * components are read as zeros of their sign, as the device's arithmetic reads them.  Only the triangles are traced: spheres (GLRTX_EXT_*) and the volume
+ * components are read as zeros of their sign, as the device's arithmetic reads them -- tmax included: a denormal tmax is the limit 0 and comes back as 0 in
+ * the miss record, and a direction whose components are all denormal is a zero direction.  A direction with a zero component is searched like any other:
+ * 1 / 0 = +-inf in the slab test, and a slab product 0 * inf = NaN (the origin's coordinate equals a box bound on that axis) is dropped by min / max, which
+ * return their other operand -- such a ray, lying in a face plane of a box, misses that box unless the box is flat on that axis.  Only the triangles are traced: spheres (GLRTX_EXT_*) and the volume
  * are not seen.  The result is what the CPU statement glrt_trace_rays (include/glrt_host.h) computes on the wire-format tree, bit for bit.
  *   glrtx_trace_rays         host arrays (n x 8 floats in, n x 4 words out); returns when the hits are in hits_out
  *   glrtx_trace_rays_device  device arrays on the context's device (16-byte aligned), read and written on the context's stream (glrtx_set_stream's, or the

@@ -1793,6 +1793,7 @@ int trace_launch(glrtx_ctx *c, const void *rays, void *hits, size_t n, int flags
     bool compact = wgwf_compact(c, vine, fetch);
     if (const char *v = std::getenv("GLRTX_COMPACT_NODES")) compact = std::atoi(v) != 0 && !vine && c->sc.n_crank > 0;
     compact = compact && lds_stack + lds_ranks <= 160 * 1024;
+    c->st.node_layout_last = compact ? 1 : 0;  // (as the render path records it: the tests read which kernel a query ran)
     using Kernel = void (*)(const query::Args);
     const Kernel kernel = vine ? (any ? (Kernel)query::trace_vine<true> : (Kernel)query::trace_vine<false>)
                         : compact ? (any ? (Kernel)query::trace_tree<true, true> : (Kernel)query::trace_tree<false, true>)

@@ -25,21 +25,8 @@ def _trace(scene, rays, any_hit=False):
     return host.trace_rays(scene["vert"], scene["tri"], scene["bvh"], rays, any_hit)
 
 
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def _check_real_hits(scene, rays, res, bf):
-    hit, t, u, v = bf
-    rt, rtri, ru, rv = res
-    idx = np.nonzero(rtri >= 0)[0]
-    k = rtri[idx]
-    assert hit[idx, k].all(), "a reported hit that the triangle test rejects"
-    assert np.array_equal(_bits(rt[idx]), _bits(t[idx, k]))
-    assert np.array_equal(_bits(ru[idx]), _bits(u[idx, k]))
-    assert np.array_equal(_bits(rv[idx]), _bits(v[idx, k]))
-    miss = rtri < 0
-    assert np.array_equal(_bits(rt[miss]), _bits(rays[miss, 7])) and (ru[miss] == 0).all() and (rv[miss] == 0).all()
+_bits = qr.bits
+_check_real_hits = qr.check_real_hits
 
 
 @pytest.mark.parametrize("builder", BUILDERS)
