@@ -140,6 +140,16 @@ int glrt_render_features(const float *vert, size_t n_vert, const float *tri, siz
 int glrt_denoise_atrous(const float *accum, const float *normal_depth, const float *albedo_id, int width, int rows, int iterations, float sigma_color,
                         float sigma_normal, float sigma_depth, int demodulate, float *out);
 
+/* Temporal reprojection: the CPU statement of the device's glrtx_reproject / glrtx_debug_reproject (include/glrtx.h "Reprojection": the formulas are there), bit
+ * for bit.  accum / n0 / a0: the old view's accumulator float4(rgb sum, count) and feature planes; n1 / a1: the new view's planes; out: the new accumulator; all
+ * width x rows x 4 floats, rows packed.  c2w_prev / s2c_prev: the camera of the old view (inverted here with glrt_mat4_inverse's routine); c2w_cur / s2c_cur: the
+ * new view's.  carried / hit_pixels (may be NULL): pixels that carried history over, pixels of the new view with a hit.  Runs with denormals flushed (MXCSR
+ * FTZ | DAZ, restored on return).  GLRT_HOST_EINVAL: a NULL array, a size outside 1..65536, max_history < 1, a depth_tolerance that is not a positive finite
+ * number, a normal_tolerance that is not finite, a singular c2w_prev or s2c_prev. */
+int glrt_reproject(const float *accum, const float *n0, const float *a0, const float *n1, const float *a1, const float *c2w_prev, const float *s2c_prev,
+                   const float *c2w_cur, const float *s2c_cur, int width, int rows, int max_history, float depth_tolerance, float normal_tolerance, float *out,
+                   int *carried, int *hit_pixels);
+
 void glrt_look_at(const float eye[3], const float center[3], const float up[3], float out[16]);
 void glrt_perspective(float fovy_deg, float aspect, float z_near, float z_far, float out[16]);
 void glrt_mat4_mul(const float a[16], const float b[16], float out[16]);

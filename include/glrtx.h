@@ -297,7 +297,7 @@ int glrtx_sync(glrtx_ctx *ctx);
 
 /* Copy the owned rows (owned_rows x width float4) to host memory; implies a sync. */
 int glrtx_read_accum(glrtx_ctx *ctx, float *dst_rgba, size_t dst_pitch_bytes);
-/* Device address / pitch of the accumulator currently rendered into. */
+/* Device address / pitch of the accumulator currently rendered into (a successful glrtx_reproject changes the address: ask again after it). */
 int glrtx_accum_device_ptr(const glrtx_ctx *ctx, void **ptr_out, size_t *pitch_bytes_out);
 
 /* Tonemap the owned rows to RGBA8: clamp(rgb/count, 0, 1)^(1/gamma), alpha 255.  If flip_y, row 0 of
@@ -494,6 +494,62 @@ int glrtx_denoise(glrtx_ctx *ctx, const glrtx_denoise_cfg *cfg);
 int glrtx_read_denoised(glrtx_ctx *ctx, float *dst_rgba, size_t dst_pitch_bytes);
 int glrtx_resolve_denoised_rgba8(glrtx_ctx *ctx, uint8_t *dst, size_t dst_pitch_bytes, float gamma, int flip_y);
 int glrtx_debug_denoise(const float *accum, const float *normal_depth, const float *albedo_id, int width, int rows, const glrtx_denoise_cfg *cfg, float *out);
+
+/* ---- Reprojection: carry the accumulator across a camera move (the reprojection step of SVGF, Schied et al. 2017; no reference counterpart -- the reference
+ * clears and starts again at one sample, window.cpp:366-381; off unless called).  The context remembers the c2w and s2c of its last glrtx_render_features: the
+ * PREVIOUS camera, the one the accumulator and the feature planes belong to.
+ *   glrtx_reproject(cur)   on the context's stream, without a host sync (but the first call allocates).  In order: (1) seals an open fed launch and waits, on the
+ *                          device, for every pipe slot's outstanding launch, as glrtx_update_vertices does; (2) keeps the feature planes as the previous planes
+ *                          N0 / A0 by a pointer swap (a second pair is allocated on first use and released by glrtx_resize); (3) renders the planes N1 / A1 for
+ *                          `cur` exactly as glrtx_render_features(cur) does; (4) runs the reprojection kernel from the accumulator into a second, context-owned
+ *                          accumulator of the same pitch (allocated on first use, released by glrtx_resize); (5) makes that second accumulator the one rendered
+ *                          into: WHAT glrtx_accum_device_ptr RETURNS CHANGES with every successful call (the two buffers alternate) -- ask again after each one.
+ *                          The remembered camera becomes `cur`, and the planes are cur's: a following glrtx_denoise needs no glrtx_render_features.  If the adaptive
+ *                          half buffer exists it is zeroed (its every-second-sample rule has lost its meaning; H.w = 0 makes every tile active again).  The present
+ *                          ring, glrtx_stats.rays and the denoised image are not touched; the call is not a frame.
+ *                          GLRTX_EINVAL, nothing changed: NULL arguments; no feature planes, or planes of another shape than the image now has; a partitioned
+ *                          context (world > 1: the source pixel may belong to another rank; groups are out of scope, as for glrtx_denoise); a caller-bound
+ *                          accumulator (glrtx_bind_accum); everything glrtx_render_features refuses; max_history < 1; a depth_tolerance that is not a positive
+ *                          finite number; a normal_tolerance that is not finite; a previous camera whose c2w or s2c glrt_mat4_inverse (glrt_host.h) reports singular.
+ *   glrtx_reproject_last   syncs, then reports the last call's counts: pixels that carried history over, and pixels of the new view with a hit (A1.id >= 0).
+ *                          GLRTX_EINVAL before the first glrtx_reproject and after a glrtx_resize.
+ *   glrtx_debug_reproject  the kernel on caller arrays (width x rows float4 each, rows packed; accum / N0 / A0: the old view, N1 / A1: the new view's planes) on the
+ *                          current HIP device, no context.  carried / hit_pixels may be NULL.  The refusals of the cfg and of singular matrices as above; sizes
+ *                          outside 1..65536 or more than 2^31 pixels.
+ * The arithmetic (this text is the contract; glrt_reproject in glrt_host.h and tests/reproject_math.py state it again, and the three agree bit for bit).  Every fp32
+ * operation is one correctly rounded operation in the order written, unfused, denormals flushed on the way in and out; a NaN that is stored is 0x7FC00000.
+ *   On the host, once per call:  W = glrt_mat4_inverse(c2w_prev), S = glrt_mat4_inverse(s2c_prev) -- the host library's routine, compiled from the same source
+ *   (host/mat4_inverse.h); o_prev = features' centre_ray origin for the previous camera, w_k = (C[k] * 0 + C[12 + k]) + C[4 + k] * 0 for the rows k = 0..3 of
+ *   C = c2w_prev, o_prev = (w_0 / w_3, w_1 / w_3, w_2 / w_3); a denormal tolerance counts as 0.  W, S, cur's c2w and s2c are the arithmetic's matrix inputs.
+ *   Per pixel (x, y) of the new view, `width` x `rows` pixels.  "No history" means out = {0, 0, 0, 0}.  "A positive finite number": sign bit clear, exponent
+ *   field neither 0 nor 255.
+ *     No history when A1.id < 0 (a miss; the reserved id INT32_MIN is negative too) or N1.t is not a positive finite number.  Otherwise:
+ *     1  (o, d) = the feature pass's centre ray of (x, y) for cur (csrc/features.hip.h: centre_ray -- that function, not a copy).
+ *     2  P = o + t d per component (o.x + t * d.x), t = N1.t.
+ *     3  q = W (P, 1): q_k = ((W[k] * P.x + W[4 + k] * P.y) + W[8 + k] * P.z) + W[12 + k];  s = S q: s_k = ((S[k] * q.x + S[4 + k] * q.y) + S[8 + k] * q.z) + S[12 + k] * q.w
+ *        (k = 0, 1, 3).  No history unless s.w is a positive finite number.  u = ((s.x / s.w + 1) * 0.5) * width + -1, v = ((s.y / s.w + 1) * 0.5) * rows + -1:
+ *        the inverse of centre_ray's ((x + 0.5 + 0.5) / width) * 2 - 1, so an unmoved camera gives u ~ x.  No history unless -1 <= u < width and -1 <= v < rows
+ *        (outside, no tap lies in the image; a NaN fails).
+ *     4  The distance the old view should have seen: e = sqrt((dz dz + dy dy) + dx dx) over (dx, dy, dz) = P - o_prev.
+ *     5  Taps (x0 + i, y0 + j), x0 = floor(u), y0 = floor(v), i, j in {0, 1}, j outermost; fx = u - x0, fy = v - y0; the tap's weight is w = wx_i * wy_j with
+ *        wx_0 = 1 - fx, wx_1 = fx, wy likewise.  A tap COUNTS only if it lies inside the image, its accumulator count acc.w is neither a zero nor a denormal,
+ *        A0.id == A1.id, dot(N1.n, N0.n) >= normal_tolerance with the renderer's dot (az bz + ay by) + ax bx (a NaN fails), and
+ *        |N0.t - e| <= depth_tolerance * e (a NaN fails).
+ *     6  Over the taps that count, from 0, in tap order:  sw = sw + w;  sc = sc + w * acc.w;  sI = sI + w * (acc.rgb / acc.w) per channel.
+ *     7  No history unless sw > 1e-6.  r = rint(sc / sw) (to nearest, ties to even -- not floor: an unmoved camera keeps its counts whatever the last ulp of the
+ *        weights is); n = r > max_history ? max_history : r (max_history converted to float); no history unless n >= 1 (a NaN fails).
+ *        out = {(sI.r / sw) * n, (sI.g / sw) * n, (sI.b / sw) * n, n}.
+ * Out of scope: reprojection assumes STATIC geometry between the two views -- after a glrtx_update_vertices only the depth, normal and id tests protect the
+ * history; specular history is view-dependent and is carried as if it were diffuse; glrt_main has no moving camera, so the facade does not call it. */
+typedef struct glrtx_reproject_cfg {
+    int   max_history;       /* >= 1: cap on the count a pixel carries over */
+    float depth_tolerance;   /* > 0, finite: relative */
+    float normal_tolerance;  /* finite: least dot(n_new, n_old) */
+} glrtx_reproject_cfg;
+int glrtx_reproject(glrtx_ctx *ctx, const glrtx_params *cur, const glrtx_reproject_cfg *cfg);
+int glrtx_reproject_last(glrtx_ctx *ctx, int *carried, int *hit_pixels);
+int glrtx_debug_reproject(const float *accum, const float *n0, const float *a0, const float *n1, const float *a1, const float *c2w_prev, const float *s2c_prev,
+                          const float *c2w_cur, const float *s2c_cur, int width, int rows, const glrtx_reproject_cfg *cfg, float *out, int *carried, int *hit_pixels);
 
 /* ---- Groups: the same device layer on several GPUs of one node, behind one handle and one host thread.
  * No reference counterpart (the reference is single-GPU); SURVEY.md 8(b) sketches glrtx_create(ctx**, device_ids, n) with a

@@ -25,6 +25,8 @@
 #include "query.hip.h"
 #include "features.hip.h"
 #include "denoise.hip.h"
+#include "reproject.hip.h"
+#include "../host/reproject_setup.h"
 static_assert(glrtx::lbvh::kRotationPasses == GLRT_LBVH_ROTATION_PASSES, "device and CPU LBVH statements must run the same rotation sweeps");
 static_assert(glrtx::lbvh::kRebuildLeaves == GLRT_LBVH_REBUILD_LEAVES, "device and CPU LBVH statements must rebuild the same subtrees");
 
@@ -190,6 +192,12 @@ struct glrtx_ctx {
     DevBuf ftN, ftA, ftCounter, dnP[2], dnD;
     int ft_w = 0, ft_rows = -1;   // (-1: no features)
     bool dn_have = false;         // D holds a result of the current shape
+    // Reprojection (glrtx_reproject): the camera of the last glrtx_render_features (c2w[16], s2c[16]: the one the accumulator and the planes belong to), the spare
+    // pair of feature planes and the spare accumulator (own pitch x owned rows) that the next call swaps in, and its two counters; allocated on first use,
+    // released by glrtx_resize
+    float ft_cam[32] = {};
+    DevBuf ftN_spare, ftA_spare, accum_spare, rpCount;
+    bool rp_have = false;         // rpCount holds a call's counts
 
     bool count_rays = false;
     const char *last_kernel = "";  // name of the last render kernel launched (error reports)
@@ -1408,6 +1416,8 @@ int launch_wgwf(glrtx_ctx *c, const KernelArgs &a_in, const glrtx_params *p, con
 void denoise_release(glrtx_ctx *c) {
     dev_free(c->ftN); dev_free(c->ftA); dev_free(c->ftCounter); dev_free(c->dnP[0]); dev_free(c->dnP[1]); dev_free(c->dnD);
     c->ft_w = 0; c->ft_rows = -1; c->dn_have = false;
+    dev_free(c->ftN_spare); dev_free(c->ftA_spare); dev_free(c->accum_spare); dev_free(c->rpCount);  // (glrtx_reproject's spares have the old shape too)
+    c->rp_have = false;
 }
 
 int denoise_cfg_check(glrtx_ctx *c, const glrtx_denoise_cfg *cfg, const char *fn) {
@@ -2419,6 +2429,7 @@ int glrtx_render_features(glrtx_ctx *c, const glrtx_params *p) {
     a.n = (unsigned)(tiles8_x * tiles8_y) * 64u;
     a.out_n = (float4 *)c->ftN.p; a.out_a = (float4 *)c->ftA.p;
     a.counter = (unsigned *)c->ftCounter.p;
+    std::memcpy(c->ft_cam, a.cam, sizeof c->ft_cam);  // (glrtx_reproject: the camera these planes belong to)
     const size_t needed = (a.n + kBlockThreads - 1) / kBlockThreads;
     const unsigned grid = (unsigned)std::max<size_t>(1, std::min<size_t>((size_t)per_cu * (size_t)c->n_cu, needed));
     HIP_TRY(c, hipMemsetAsync(c->ftCounter.p, 0, sizeof(unsigned), c->stream));
@@ -2517,6 +2528,134 @@ int glrtx_debug_denoise(const float *accum, const float *normal_depth, const flo
         rc = denoise_passes(nullptr, 0, (const float4 *)d[0], width, (const float4 *)d[1], (const float4 *)d[2], (float4 *)d[3], (float4 *)d[4], (float4 *)d[5], width, rows, cfg);
     if (e == hipSuccess && rc == GLRTX_OK) e = hipDeviceSynchronize();
     if (e == hipSuccess && rc == GLRTX_OK) e = hipMemcpy(out, d[5], bytes, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) rc = fail(nullptr, GLRTX_EDEVICE, "%s: %s", fn, hipGetErrorString(e));
+    for (void *q : d)
+        if (q) (void)hipFree(q);
+    return rc;
+}
+
+
+// ---- reprojection (glrtx_reproject)
+static int reproject_setup_check(glrtx_ctx *c, const char *fn, const float *c2w_prev, const float *s2c_prev, const glrtx_reproject_cfg *cfg, glrt_detail::ReprojectSetup &st) {
+    switch (glrt_detail::reproject_setup(c2w_prev, s2c_prev, cfg->max_history, cfg->depth_tolerance, cfg->normal_tolerance, st)) {
+        case 0: return GLRTX_OK;
+        case 1: return fail(c, GLRTX_EINVAL, "%s: max_history %d < 1", fn, cfg->max_history);
+        case 2: return fail(c, GLRTX_EINVAL, "%s: depth_tolerance %g is not a positive finite number", fn, (double)cfg->depth_tolerance);
+        case 3: return fail(c, GLRTX_EINVAL, "%s: normal_tolerance %g is not finite", fn, (double)cfg->normal_tolerance);
+        case 4: return fail(c, GLRTX_EINVAL, "%s: the previous camera's c2w is singular", fn);
+        default: return fail(c, GLRTX_EINVAL, "%s: the previous camera's s2c is singular", fn);
+    }
+}
+
+// The kernel on `stream`: old accumulator (pitch_f4) and planes, new planes -> `out` (pitch_f4); `counts` (reproject::kCountBytes) is zeroed first.
+static hipError_t reproject_counts(const void *dev_counts, int *carried, int *hit_pixels) {
+    unsigned long long w[reproject::kCountSlots * reproject::kCountStride], sum = 0;
+    const hipError_t e = hipMemcpy(w, dev_counts, sizeof w, hipMemcpyDeviceToHost);
+    for (int i = 0; i < reproject::kCountSlots; i++) sum += w[i * reproject::kCountStride];  // (both halves stay below 2^31: no carry between them)
+    if (carried) *carried = (int)(sum & 0xFFFFFFFFull);
+    if (hit_pixels) *hit_pixels = (int)(sum >> 32);
+    return e;
+}
+
+static int reproject_pass(glrtx_ctx *c, hipStream_t stream, const glrt_detail::ReprojectSetup &st, const float *c2w_cur, const float *s2c_cur, int stripe, const float4 *acc,
+                          const float4 *n0, const float4 *a0, const float4 *n1, const float4 *a1, float4 *out, int pitch_f4, int width, int rows, void *counts) {
+    reproject::Args a{};
+    std::memcpy(a.cam.cam, c2w_cur, 16 * sizeof(float));
+    std::memcpy(a.cam.cam + 16, s2c_cur, 16 * sizeof(float));
+    a.cam.width = width; a.cam.height = rows;
+    a.cam.owned_rows = rows; a.cam.rank = 0; a.cam.world = 1; a.cam.stripe = stripe;
+    std::memcpy(a.W, st.W, sizeof a.W);
+    std::memcpy(a.S, st.S, sizeof a.S);
+    a.opx = st.o_prev[0]; a.opy = st.o_prev[1]; a.opz = st.o_prev[2];
+    a.acc = acc; a.n0 = n0; a.a0 = a0; a.n1 = n1; a.a1 = a1; a.out = out;
+    a.pitch_f4 = pitch_f4; a.width = width; a.rows = rows;
+    a.tiles_x = (width + 7) / 8;
+    a.n_tiles = a.tiles_x * ((rows + 7) / 8);
+    a.max_history = st.max_history; a.depth_tol = st.depth_tolerance; a.normal_tol = st.normal_tolerance;
+    a.counts = (unsigned long long *)counts;
+    HIP_TRY(c, hipMemsetAsync(counts, 0, reproject::kCountBytes, stream));
+    hipLaunchKernelGGL(reproject::reproject_kernel, dim3((unsigned)((a.n_tiles + 3) / 4)), dim3(256), 0, stream, a);
+    HIP_TRY(c, hipGetLastError());
+    return GLRTX_OK;
+}
+
+int glrtx_reproject(glrtx_ctx *c, const glrtx_params *cur, const glrtx_reproject_cfg *cfg) {
+    const char *fn = "glrtx_reproject";
+    if (!c) return GLRTX_EINVAL;
+    if (!cur || !cfg) return fail(c, GLRTX_EINVAL, "%s: NULL params or cfg", fn);
+    // everything glrtx_render_features refuses, before anything changes
+    if (!c->have_scene) return fail(c, GLRTX_EINVAL, "%s: no scene uploaded", fn);
+    if (c->n_spheres > 0) return fail(c, GLRTX_EINVAL, "%s: spheres are uploaded (an analytic sphere has no triangle normal to report)", fn);
+    if (!c->accum || c->width < 1) return fail(c, GLRTX_EINVAL, "%s: no size (call glrtx_resize)", fn);
+    if ((size_t)((c->width + 7) / 8) * (size_t)((c->owned_rows + 7) / 8) >= ((size_t)1 << 25))
+        return fail(c, GLRTX_EINVAL, "%s: %dx%d owned pixels (at most 2^31 tile-order ids)", fn, c->width, c->owned_rows);
+    if (c->world > 1) return fail(c, GLRTX_EINVAL, "%s: the context is partitioned (rank %d of %d): a pixel's history may lie on another rank", fn, c->rank, c->world);
+    if (c->bound) return fail(c, GLRTX_EINVAL, "%s: a caller-owned accumulator is bound (glrtx_bind_accum): the call swaps accumulators", fn);
+    if (int rc = denoise_shape_check(c, fn, false)) return rc;
+    glrt_detail::ReprojectSetup st;
+    if (int rc = reproject_setup_check(c, fn, c->ft_cam, c->ft_cam + 16, cfg, st)) return rc;
+    seal_feed(c);
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t acc_bytes = c->pitch_bytes * (size_t)std::max(c->owned_rows, 1);
+    int rc;
+    if ((rc = ensure(c, c->accum_spare, acc_bytes)) || (rc = ensure(c, c->rpCount, reproject::kCountBytes))) return rc;
+    for (auto &sl : c->pipe)  // behind every launch that may still add to the accumulator or read the scene (refit_run's rule)
+        if (sl.stream && sl.used) {
+            HIP_TRY(c, hipEventRecord(c->rf.slot_ev, sl.stream));
+            HIP_TRY(c, hipStreamWaitEvent(c->stream, c->rf.slot_ev, 0));
+        }
+    std::swap(c->ftN, c->ftN_spare);  // the planes as they stand become N0 / A0; glrtx_render_features fills (on first use: allocates) the other pair
+    std::swap(c->ftA, c->ftA_spare);
+    float cam_prev[32];
+    std::memcpy(cam_prev, c->ft_cam, sizeof cam_prev);
+    if ((rc = glrtx_render_features(c, cur))) {  // (only an allocation or a launch can fail here: the planes and their camera are put back)
+        std::swap(c->ftN, c->ftN_spare);
+        std::swap(c->ftA, c->ftA_spare);
+        std::memcpy(c->ft_cam, cam_prev, sizeof cam_prev);
+        return rc;
+    }
+    const int pitch_f4 = (int)(c->pitch_bytes / sizeof(float4));
+    if ((rc = reproject_pass(c, c->stream, st, cur->c2w, cur->s2c, c->stripe, c->accum, (const float4 *)c->ftN_spare.p, (const float4 *)c->ftA_spare.p,
+                             (const float4 *)c->ftN.p, (const float4 *)c->ftA.p, (float4 *)c->accum_spare.p, pitch_f4, c->width, c->owned_rows, c->rpCount.p)))
+        return rc;
+    std::swap(c->accum_own, c->accum_spare);  // the accumulator rendered into from here on (glrtx_accum_device_ptr changes)
+    c->accum = (float4 *)c->accum_own.p;
+    c->rp_have = true;
+    if (c->adHalf.p && (rc = adapt_half_ensure(c))) return rc;  // H held every second sample of the OLD view's pixels: zeroed, every tile is active again
+    return GLRTX_OK;
+}
+
+int glrtx_reproject_last(glrtx_ctx *c, int *carried, int *hit_pixels) {
+    const char *fn = "glrtx_reproject_last";
+    if (!c) return GLRTX_EINVAL;
+    if (!carried || !hit_pixels) return fail(c, GLRTX_EINVAL, "%s: NULL output", fn);
+    if (!c->rp_have || !c->rpCount.p) return fail(c, GLRTX_EINVAL, "%s: no reprojection yet (or the image was resized since)", fn);
+    if (int rc = glrtx_sync(c)) return rc;
+    HIP_TRY(c, reproject_counts(c->rpCount.p, carried, hit_pixels));
+    return GLRTX_OK;
+}
+
+int glrtx_debug_reproject(const float *accum, const float *n0, const float *a0, const float *n1, const float *a1, const float *c2w_prev, const float *s2c_prev,
+                          const float *c2w_cur, const float *s2c_cur, int width, int rows, const glrtx_reproject_cfg *cfg, float *out, int *carried, int *hit_pixels) {
+    const char *fn = "glrtx_debug_reproject";
+    if (width < 1 || rows < 1 || width > 65536 || rows > 65536 || (size_t)width * (size_t)rows > ((size_t)1 << 31))
+        return fail(nullptr, GLRTX_EINVAL, "%s: bad size %dx%d", fn, width, rows);
+    if (!accum || !n0 || !a0 || !n1 || !a1 || !c2w_prev || !s2c_prev || !c2w_cur || !s2c_cur || !cfg || !out) return fail(nullptr, GLRTX_EINVAL, "%s: NULL argument", fn);
+    glrt_detail::ReprojectSetup st;
+    if (int rc = reproject_setup_check(nullptr, fn, c2w_prev, s2c_prev, cfg, st)) return rc;
+    const size_t bytes = (size_t)width * rows * sizeof(float4);
+    const float *src[5] = {accum, n0, a0, n1, a1};
+    void *d[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // accum, N0, A0, N1, A1, out, counts
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < 7 && e == hipSuccess; i++) e = hipMalloc(&d[i], i == 6 ? reproject::kCountBytes : bytes);
+    for (int i = 0; i < 5 && e == hipSuccess; i++) e = hipMemcpy(d[i], src[i], bytes, hipMemcpyHostToDevice);
+    int rc = GLRTX_OK;
+    if (e == hipSuccess)
+        rc = reproject_pass(nullptr, 0, st, c2w_cur, s2c_cur, 16, (const float4 *)d[0], (const float4 *)d[1], (const float4 *)d[2], (const float4 *)d[3], (const float4 *)d[4],
+                            (float4 *)d[5], width, width, rows, d[6]);
+    if (e == hipSuccess && rc == GLRTX_OK) e = hipDeviceSynchronize();
+    if (e == hipSuccess && rc == GLRTX_OK) e = hipMemcpy(out, d[5], bytes, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && rc == GLRTX_OK) e = reproject_counts(d[6], carried, hit_pixels);
     if (e != hipSuccess) rc = fail(nullptr, GLRTX_EDEVICE, "%s: %s", fn, hipGetErrorString(e));
     for (void *q : d)
         if (q) (void)hipFree(q);

@@ -13,12 +13,13 @@
 #include <xmmintrin.h>
 #endif
 
+#include "centre_ray.h"
 #include "glrt_host.h"
 
 namespace {
 
-constexpr float kEps = 1.0e-4f;    // PT_EPS: a primary ray's tmin
-constexpr float kInfty = 1.0e8f;   // PT_INFTY: its search limit
+using glrt_detail::centre_ray;
+using glrt_detail::rsq;
 
 struct FlushDenormals {
 #if defined(__SSE__)
@@ -30,33 +31,7 @@ struct FlushDenormals {
 
 // a NaN is stored as 0x7FC00000 on both sides (which NaN an operation yields is the one thing the two instruction sets do not share)
 inline float canon(float x) { const uint32_t q = 0x7FC00000u; float n; std::memcpy(&n, &q, 4); return x != x ? n : x; }
-inline float rsq(float x) { return 1.0f / std::sqrt(x); }
 inline float dot3(float ax, float ay, float az, float bx, float by, float bz) { return (az * bz + ay * by) + ax * bx; }
-
-// camera_ray (csrc/pt_kernel.hip.h) at the pixel centre: fcx + r0 = (x + 0.5) + 0.5, the lens offset (lox, loy) = (0, 0) kept in the expressions
-void centre_ray(const float *C, const float *S, float W, float H, int x, int y, float *ray) {
-    const float fcx = (float)x + 0.5f, fcy = (float)y + 0.5f;
-    const float nx = ((fcx + 0.5f) / W) * 2.0f + -1.0f;
-    const float ny = ((fcy + 0.5f) / H) * 2.0f + -1.0f;
-    const float tx = (S[0] * nx + S[12]) + S[4] * ny;
-    const float ty = (S[1] * nx + S[13]) + S[5] * ny;
-    const float tz = (S[2] * nx + S[14]) + S[6] * ny;
-    const float tw = (S[3] * nx + S[15]) + S[7] * ny;
-    const float cx = tx / tw, cy = ty / tw, cz = tz / tw;
-    const float rn = rsq((cz * cz + cy * cy) + cx * cx);
-    const float dx = cx * rn, dy = cy * rn, dz = cz * rn;
-    const float lox = 0.0f, loy = 0.0f;
-    const float wx = (C[0] * lox + C[12]) + C[4] * loy;
-    const float wy = (C[1] * lox + C[13]) + C[5] * loy;
-    const float wz = (C[2] * lox + C[14]) + C[6] * loy;
-    const float ww = (C[3] * lox + C[15]) + C[7] * loy;
-    const float ex = (C[0] * dx + C[4] * dy) + C[8] * dz;
-    const float ey = (C[1] * dx + C[5] * dy) + C[9] * dz;
-    const float ez = (C[2] * dx + C[6] * dy) + C[10] * dz;
-    const float re = rsq((ez * ez + ey * ey) + ex * ex);
-    ray[0] = wx / ww; ray[1] = wy / ww; ray[2] = wz / ww; ray[3] = kEps;
-    ray[4] = ex * re; ray[5] = ey * re; ray[6] = ez * re; ray[7] = kInfty;
-}
 
 }  // namespace
 

@@ -45,6 +45,17 @@ class DenoiseCfg(C.Structure):
     _fields_ = [("iterations", C.c_int), ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float), ("demodulate", C.c_int)]
 
 
+class ReprojectCfg(C.Structure):
+    """glrtx_reproject_cfg; ReprojectCfg.default() holds glrt_amd.host.REPROJECT_DEFAULTS."""
+    _fields_ = [("max_history", C.c_int), ("depth_tolerance", C.c_float), ("normal_tolerance", C.c_float)]
+
+    @classmethod
+    def default(cls, max_history=None, depth_tolerance=None, normal_tolerance=None):
+        from .host import REPROJECT_DEFAULTS as d
+        pick = lambda v, k: d[k] if v is None else v
+        return cls(int(pick(max_history, "max_history")), float(pick(depth_tolerance, "depth_tolerance")), float(pick(normal_tolerance, "normal_tolerance")))
+
+
 class Image(C.Structure):
     _fields_ = [("rgba", C.c_void_p), ("pitch_bytes", C.c_size_t), ("width", C.c_int32), ("rows", C.c_int32), ("frame", C.c_uint64)]
 
@@ -81,7 +92,7 @@ EXPORTS = ["glrtx_abi_version", "glrtx_create", "glrtx_destroy", "glrtx_last_err
            "glrtx_group_render_adaptive", "glrtx_group_adaptive_active_tiles", "glrtx_debug_pack_compact", "glrtx_set_volume_wavefront",
            "glrtx_render_features", "glrtx_read_features", "glrtx_denoise", "glrtx_read_denoised", "glrtx_resolve_denoised_rgba8", "glrtx_debug_denoise",
            "glrtx_update_vertices", "glrtx_update_vertices_device", "glrtx_group_update_vertices", "glrtx_debug_read_scene",
-           "glrtx_trace_rays", "glrtx_trace_rays_device"]
+           "glrtx_trace_rays", "glrtx_trace_rays_device", "glrtx_reproject", "glrtx_reproject_last", "glrtx_debug_reproject"]
 
 SCENE_BUFFERS = ("nodes", "cnodes", "nrms", "lights", "vine", "root")  # glrtx_debug_read_scene's `which`, in order (GLRTX_SCENE_*)
 
@@ -196,6 +207,12 @@ def lib():
             L.glrtx_debug_denoise.argtypes = [fp, fp, fp, C.c_int, C.c_int, C.POINTER(DenoiseCfg), fp]
         except AttributeError:
             pass
+        try:  # (additive to ABI 10 as well: the reprojection)
+            L.glrtx_reproject.argtypes = [vp, C.POINTER(Params), C.POINTER(ReprojectCfg)]
+            L.glrtx_reproject_last.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+            L.glrtx_debug_reproject.argtypes = [fp] * 9 + [C.c_int, C.c_int, C.POINTER(ReprojectCfg), fp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        except AttributeError:
+            pass
         _lib = L
     return _lib
 
@@ -303,6 +320,24 @@ def debug_denoise(accum, normal_depth, albedo_id, **cfg):
     if rc != 0:
         raise GlrtxError(rc, L.glrtx_last_error(None).decode())
     return out
+
+
+def debug_reproject(accum, n0, a0, n1, a1, prev, cur, **cfg):
+    """glrtx_debug_reproject on the current device: the reprojection kernel on (rows, width, 4) float32 arrays (the old view's accumulator and planes, the new
+    view's planes) and the two cameras (dicts with c2w and s2c).  Returns (out, carried, hit_pixels)."""
+    L = lib()
+    arr = [_f32(v) for v in (accum, n0, a0, n1, a1)]
+    a = arr[0]
+    if a.ndim != 3 or a.shape[2] != 4 or any(v.shape != a.shape for v in arr):
+        raise ValueError(f"debug_reproject: five (rows, width, 4) arrays of one shape expected, got {[v.shape for v in arr]}")
+    mats = [_f32(np.asarray(m).reshape(16)) for m in (prev["c2w"], prev["s2c"], cur["c2w"], cur["s2c"])]
+    out = np.zeros_like(a)
+    c = ReprojectCfg.default(**cfg)
+    carried, hits = C.c_int(0), C.c_int(0)
+    rc = L.glrtx_debug_reproject(*[_fp(v) for v in arr], *[_fp(m) for m in mats], a.shape[1], a.shape[0], C.byref(c), _fp(out), C.byref(carried), C.byref(hits))
+    if rc != 0:
+        raise GlrtxError(rc, L.glrtx_last_error(None).decode())
+    return out, int(carried.value), int(hits.value)
 
 
 def _host_vertices(v):
@@ -623,6 +658,17 @@ class Device:
         out = np.zeros((s.owned_rows, s.width, 4), np.uint8)
         self._ck(self.L.glrtx_resolve_denoised_rgba8(self.h, out.ctypes.data, s.width * 4, gamma, int(flip_y)))
         return out
+    def reproject(self, params, max_history=None, depth_tolerance=None, normal_tolerance=None):
+        """Carry the accumulator from the camera of the last render_features / reproject to `params`' camera (glrtx_reproject); None: the default.  The
+        accumulator's device address changes; the feature planes are `params`' afterwards."""
+        p = make_params(params)
+        c = ReprojectCfg.default(max_history, depth_tolerance, normal_tolerance)
+        self._ck(self.L.glrtx_reproject(self.h, C.byref(p), C.byref(c)))
+    def reproject_last(self):
+        """(carried, hit_pixels) of the last reproject (syncs)."""
+        a, b = C.c_int(0), C.c_int(0)
+        self._ck(self.L.glrtx_reproject_last(self.h, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
     def timer_begin(self):
         self._ck(self.L.glrtx_timer_begin(self.h))
 

@@ -39,6 +39,7 @@ def lib():
         L.glrt_trace_rays.argtypes = [fp, C.c_size_t, fp, C.c_size_t, fp, C.c_size_t, fp, C.c_size_t, fp, C.c_int]
         L.glrt_render_features.argtypes = [fp, C.c_size_t, fp, C.c_size_t, fp, C.c_size_t, fp, C.c_size_t, fp, fp] + [C.c_int] * 5 + [fp, fp]
         L.glrt_denoise_atrous.argtypes = [fp, fp, fp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int, fp]
+        L.glrt_reproject.argtypes = [fp] * 9 + [C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, fp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.glrt_look_at.argtypes = [fp, fp, fp, fp]
         L.glrt_perspective.argtypes = [C.c_float, C.c_float, C.c_float, C.c_float, fp]
         L.glrt_mat4_mul.argtypes = [fp, fp, fp]
@@ -190,6 +191,28 @@ def denoise_atrous(accum, normal_depth, albedo_id, iterations=DENOISE_DEFAULTS["
     if rc != 0:
         raise RuntimeError(f"glrt_denoise_atrous failed: {rc}")
     return out
+
+
+# The reprojection's defaults (DESIGN.md "Reprojection": chosen from the sweep recorded there); Device.reproject takes the same.
+REPROJECT_DEFAULTS = dict(max_history=32, depth_tolerance=0.02, normal_tolerance=0.9)
+
+
+def reproject(accum, n0, a0, n1, a1, prev, cur, max_history=REPROJECT_DEFAULTS["max_history"], depth_tolerance=REPROJECT_DEFAULTS["depth_tolerance"],
+              normal_tolerance=REPROJECT_DEFAULTS["normal_tolerance"]):
+    """glrt_reproject: the CPU statement of Device.reproject on (rows, width, 4) float32 arrays.  accum, n0, a0: the old view's accumulator and feature planes;
+    n1, a1: the new view's planes; prev / cur: the two cameras (dicts with c2w and s2c).  Returns (out, carried, hit_pixels)."""
+    arr = [_f32(v) for v in (accum, n0, a0, n1, a1)]
+    a = arr[0]
+    if a.ndim != 3 or a.shape[2] != 4 or any(v.shape != a.shape for v in arr):
+        raise ValueError(f"reproject: five (rows, width, 4) arrays of one shape expected, got {[v.shape for v in arr]}")
+    mats = [_f32(m).reshape(16) for m in (prev["c2w"], prev["s2c"], cur["c2w"], cur["s2c"])]
+    out = np.zeros_like(a)
+    carried, hits = C.c_int(0), C.c_int(0)
+    rc = lib().glrt_reproject(*[_fp(v) for v in arr], *[_fp(m) for m in mats], a.shape[1], a.shape[0], int(max_history), float(depth_tolerance),
+                              float(normal_tolerance), _fp(out), C.byref(carried), C.byref(hits))
+    if rc != 0:
+        raise RuntimeError(f"glrt_reproject failed: {rc}")
+    return out, int(carried.value), int(hits.value)
 
 
 def look_at(eye, center, up) -> np.ndarray:
