@@ -134,6 +134,12 @@ int glrt_trace_rays(const float *vert, size_t n_vert, const float *tri, size_t n
  * Both rows x width x 4 floats, rows packed.  mat: n_mat x GLRT_MATERIAL_FLOATS.  Errors: glrt_trace_rays', and GLRT_HOST_EINDEX for a material index out of range. */
 int glrt_render_features(const float *vert, size_t n_vert, const float *tri, size_t n_tri, const float *nodes, size_t n_nodes, const float *mat, size_t n_mat,
                          const float *c2w, const float *s2c, int width, int height, int rank, int world, int stripe, float *out_n, float *out_a);
+/* The feature pass with the geometry plane: the CPU statement of the device's feature pass under glrtx_track_motion (include/glrtx.h "Reprojection across a
+ * geometry move").  out_n / out_a as glrt_render_features writes them, bit for bit, and
+ *   out_g: {tri, u, v, 0}    the walker's own hit: the wire triangle index as int32 bits and its barycentrics (glrt_trace_rays' words); {-1, 0, 0, 0} on a miss.
+ * GLRT_HOST_EINVAL for a NULL out_g; otherwise glrt_render_features' errors. */
+int glrt_render_features_geom(const float *vert, size_t n_vert, const float *tri, size_t n_tri, const float *nodes, size_t n_nodes, const float *mat, size_t n_mat,
+                              const float *c2w, const float *s2c, int width, int height, int rank, int world, int stripe, float *out_n, float *out_a, float *out_g);
 /* The edge-avoiding a-trous filter: the CPU statement of the device's glrtx_denoise / glrtx_debug_denoise (include/glrtx.h "Denoising": the formulas are
  * there), bit for bit.  accum: float4(rgb sum, count); normal_depth / albedo_id: the two feature planes; out: float4(rgb, 1); all width x rows x 4 floats, rows
  * packed.  GLRT_HOST_EINVAL: a NULL array, a size outside 1..65536, iterations outside 1..6, a sigma that is not a positive finite number. */
@@ -149,6 +155,14 @@ int glrt_denoise_atrous(const float *accum, const float *normal_depth, const flo
 int glrt_reproject(const float *accum, const float *n0, const float *a0, const float *n1, const float *a1, const float *c2w_prev, const float *s2c_prev,
                    const float *c2w_cur, const float *s2c_cur, int width, int rows, int max_history, float depth_tolerance, float normal_tolerance, float *out,
                    int *carried, int *hit_pixels);
+/* Reprojection across a geometry move: the CPU statement of the device's glrtx_reproject_motion / glrtx_debug_reproject_motion (include/glrtx.h "Reprojection
+ * across a geometry move": the formulas are there), bit for bit.  accum / n0 / a0: the old view; g1 / a1: the new view's geometry and albedo planes (the new
+ * view's camera enters through them alone); vert_prev (n_vert x GLRT_VERTEX_FLOATS): the vertices as they stood at the old view; tri (n_tri x 4): the wire
+ * triangles.  Everything else as glrt_reproject.  The edges p1 - p0, p2 - p0 of the previous triangles are formed with denormals kept, as the scene upload
+ * forms them; the per-pixel arithmetic runs with denormals flushed.  Errors: glrt_reproject's; GLRT_HOST_EINDEX for a triangle with a vertex index out of range. */
+int glrt_reproject_motion(const float *accum, const float *n0, const float *a0, const float *g1, const float *a1, const float *vert_prev, size_t n_vert,
+                          const float *tri, size_t n_tri, const float *c2w_prev, const float *s2c_prev, int width, int rows, int max_history,
+                          float depth_tolerance, float normal_tolerance, float *out, int *carried, int *hit_pixels);
 
 void glrt_look_at(const float eye[3], const float center[3], const float up[3], float out[16]);
 void glrt_perspective(float fovy_deg, float aspect, float z_near, float z_far, float out[16]);

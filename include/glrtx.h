@@ -540,7 +540,7 @@ int glrtx_debug_denoise(const float *accum, const float *normal_depth, const flo
  *        weights is); n = r > max_history ? max_history : r (max_history converted to float); no history unless n >= 1 (a NaN fails).
  *        out = {(sI.r / sw) * n, (sI.g / sw) * n, (sI.b / sw) * n, n}.
  * Out of scope: reprojection assumes STATIC geometry between the two views -- after a glrtx_update_vertices only the depth, normal and id tests protect the
- * history; specular history is view-dependent and is carried as if it were diffuse; glrt_main has no moving camera, so the facade does not call it. */
+ * history (glrtx_reproject_motion below is the call for moved geometry); specular history is view-dependent and is carried as if it were diffuse; glrt_main has no moving camera, so the facade does not call it. */
 typedef struct glrtx_reproject_cfg {
     int   max_history;       /* >= 1: cap on the count a pixel carries over */
     float depth_tolerance;   /* > 0, finite: relative */
@@ -550,6 +550,51 @@ int glrtx_reproject(glrtx_ctx *ctx, const glrtx_params *cur, const glrtx_reproje
 int glrtx_reproject_last(glrtx_ctx *ctx, int *carried, int *hit_pixels);
 int glrtx_debug_reproject(const float *accum, const float *n0, const float *a0, const float *n1, const float *a1, const float *c2w_prev, const float *s2c_prev,
                           const float *c2w_cur, const float *s2c_cur, int width, int rows, const glrtx_reproject_cfg *cfg, float *out, int *carried, int *hit_pixels);
+
+/* ---- Reprojection across a geometry move: the same carry-over when glrtx_update_vertices moved the surfaces between the two views (SVGF's motion vector; no
+ * reference counterpart; everything here is off unless glrtx_track_motion switched it on, and no other call changes what it does).
+ *   glrtx_track_motion(enable)  off by default.  While it is on:
+ *                          (a) every feature pass -- glrtx_render_features and the passes inside glrtx_reproject and glrtx_reproject_motion -- also writes a third
+ *                          context-owned plane G beside N and A, of the same packed layout, allocated and released as they are and double-buffered as they are
+ *                          (the reprojections swap three pairs): on a hit {tri, u, v, 0} -- the wire triangle index as int32 bits, mapped as glrtx_trace_rays
+ *                          maps it, and the traversal's own barycentrics --, on a miss {-1, 0, 0, 0}.  N and A are bit for bit what they are with tracking off.
+ *                          (b) the context keeps the PREVIOUS geometry: per wire triangle the three positions and vertex normals as they stood at the last
+ *                          feature pass.  The first glrtx_update_vertices / _device after a feature pass copies them out of the scene on the device, on the
+ *                          context's stream, before the refit; later updates before the next feature pass leave that copy alone; if nothing moved since the
+ *                          last feature pass, previous and current are the same data.  glrtx_upload_scene forgets the previous geometry (until the next feature
+ *                          pass).  glrtx_group_update_vertices goes through the members' glrtx_update_vertices.
+ *                          Switching it off syncs, forgets the previous geometry and releases G and the copy.  Switching it on makes nothing known: render the
+ *                          features before the first move.
+ *   glrtx_read_features_geom    syncs, then copies G like glrtx_read_features.  GLRTX_EINVAL while tracking is off or before a feature pass wrote a G.
+ *   glrtx_reproject_motion(cur) glrtx_reproject step for step -- the seal, the waits, the swaps, the feature pass for `cur`, the kernel into the second accumulator,
+ *                          the accumulator switch, the zeroed half buffer, the counts glrtx_reproject_last reports, the refusals -- with the arithmetic below.
+ *                          It also refuses, nothing changed, while tracking is off, before a feature pass wrote a G, and when the previous geometry is not
+ *                          known (a glrtx_upload_scene since the last feature pass).  With the camera moved as well, `cur` is the new camera: both moves are
+ *                          carried at once.
+ *   glrtx_debug_reproject_motion  the kernel on caller arrays, no context: glrtx_debug_reproject's with G1 in place of N1 (the new view's camera enters through
+ *                          the planes alone, so it is not an argument), the previous vertices (n_vert x 15 floats, wire format) and the triangles (n_tri x 4).
+ *                          Its refusals, and a triangle with a vertex index out of range.
+ * The arithmetic (the contract; glrt_reproject_motion in glrt_host.h and tests/reproject_motion_math.py state it again, and the three agree bit for bit), under
+ * the rules of "Reprojection" above: one correctly rounded fp32 operation at a time in the order written, unfused, denormals flushed in and out, a stored NaN
+ * is 0x7FC00000; W, S and o_prev as there.  Per pixel of the new view:
+ *     No history when A1.id < 0, or G1.tri < 0, or G1.tri is not below the number of triangles the previous geometry holds.  N1 is not read.  Otherwise:
+ *     2' p0, p1, p2 and n0, n1, n2: the PREVIOUS positions and vertex normals of wire triangle G1.tri; (u, v) = (G1.y, G1.z).  e1 = p1 - p0, e2 = p2 - p0 as the
+ *        scene upload forms a leaf record's edges: one IEEE subtraction each with denormals KEPT (they are flushed when the next line reads them).
+ *        P = (p0 + u * e1) + v * e2 per component.  m = the renderer's shading normal (surf_tri, csrc/pt_kernel.hip.h -- that function) of (n0, n1, n2) at
+ *        (u, v): w0 = (1 - u) - v, t = (w0 * n0 + u * n1) + v * n2 per component, m = t * (1 / sqrt((t.z t.z + t.y t.y) + t.x t.x)).
+ *     3, 4  as there, with this P.
+ *     5  as there, except that the normal test is dot(m, N0.n) >= normal_tolerance: m is what the old view should have seen at that point (the new normal
+ *        of a turned object says nothing about its old one).
+ *     6, 7  unchanged.
+ * Out of scope: changes of topology; spheres and the volume; specular history (carried as if it were diffuse); lighting that changes because geometry moved
+ * (shading near a moved object's shadow stays stale until new samples outweigh it); partitioned contexts and groups; glrt_main has no animation, so the facade
+ * calls none of this. */
+int glrtx_track_motion(glrtx_ctx *ctx, int enable);
+int glrtx_read_features_geom(glrtx_ctx *ctx, float *geom, size_t pitch_bytes);
+int glrtx_reproject_motion(glrtx_ctx *ctx, const glrtx_params *cur, const glrtx_reproject_cfg *cfg);
+int glrtx_debug_reproject_motion(const float *accum, const float *n0, const float *a0, const float *g1, const float *a1, const float *vert_prev, size_t n_vert,
+                                 const float *tri, size_t n_tri, const float *c2w_prev, const float *s2c_prev, int width, int rows, const glrtx_reproject_cfg *cfg,
+                                 float *out, int *carried, int *hit_pixels);
 
 /* ---- Groups: the same device layer on several GPUs of one node, behind one handle and one host thread.
  * No reference counterpart (the reference is single-GPU); SURVEY.md 8(b) sketches glrtx_create(ctx**, device_ids, n) with a

@@ -26,6 +26,7 @@
 #include "features.hip.h"
 #include "denoise.hip.h"
 #include "reproject.hip.h"
+#include "reproject_motion.hip.h"
 #include "../host/reproject_setup.h"
 static_assert(glrtx::lbvh::kRotationPasses == GLRT_LBVH_ROTATION_PASSES, "device and CPU LBVH statements must run the same rotation sweeps");
 static_assert(glrtx::lbvh::kRebuildLeaves == GLRT_LBVH_REBUILD_LEAVES, "device and CPU LBVH statements must rebuild the same subtrees");
@@ -198,6 +199,14 @@ struct glrtx_ctx {
     float ft_cam[32] = {};
     DevBuf ftN_spare, ftA_spare, accum_spare, rpCount;
     bool rp_have = false;         // rpCount holds a call's counts
+    // Motion tracking (glrtx_track_motion): the third feature plane G and its spare (shape and release rules of N and A), and the PREVIOUS geometry per wire
+    // triangle (motion::Args::prev_pos / prev_nrm: 3 float4 each) -- the scene as it stood at the last feature pass.  mt_geom: kMtNone, nothing is known (no
+    // feature pass since tracking was switched on or a scene was uploaded); kMtCurrent, nothing moved since that pass: the scene's own records are the previous
+    // geometry, and the next glrtx_update_vertices copies them out first; kMtSaved, that copy is what mtPos / mtNrm hold.
+    enum { kMtNone, kMtCurrent, kMtSaved };
+    bool mt_on = false, mt_g_have = false;  // mt_g_have: ftG holds the plane of the last feature pass
+    int mt_geom = kMtNone;
+    DevBuf ftG, ftG_spare, mtPos, mtNrm;
 
     bool count_rays = false;
     const char *last_kernel = "";  // name of the last render kernel launched (error reports)
@@ -1418,6 +1427,8 @@ void denoise_release(glrtx_ctx *c) {
     c->ft_w = 0; c->ft_rows = -1; c->dn_have = false;
     dev_free(c->ftN_spare); dev_free(c->ftA_spare); dev_free(c->accum_spare); dev_free(c->rpCount);  // (glrtx_reproject's spares have the old shape too)
     c->rp_have = false;
+    dev_free(c->ftG); dev_free(c->ftG_spare);
+    c->mt_g_have = false;
 }
 
 int denoise_cfg_check(glrtx_ctx *c, const glrtx_denoise_cfg *cfg, const char *fn) {
@@ -1627,6 +1638,7 @@ void glrtx_destroy(glrtx_ctx *c) {
     dev_free(c->accum_own); dev_free(c->counter); dev_free(c->rgba8); dev_free(c->work);
     dev_free(c->adHalf); dev_free(c->adMask); dev_free(c->adList); dev_free(c->adCount);
     denoise_release(c);
+    dev_free(c->mtPos); dev_free(c->mtNrm);
     dev_free(c->wfState); dev_free(c->wfQ); dev_free(c->wfSeeds); dev_free(c->wfPlanes);
     dev_free(c->bvhVert); dev_free(c->bvhTri); dev_free(c->bvhNodes);
     dev_free(c->rf.ints); dev_free(c->rf.keys); dev_free(c->rf.vert);
@@ -1714,6 +1726,8 @@ int glrtx_upload_scene(glrtx_ctx *c, const float *vert, size_t n_vert, const flo
     c->have_scene = true;
     c->leaf_tri.swap(P.leaf_tri);
     c->n_spheres = 0;  // spheres reference this scene's materials: upload them again after a new scene
+    dev_free(c->mtPos); dev_free(c->mtNrm);  // (glrtx_track_motion: the previous geometry was another scene's; the stream is idle)
+    c->mt_geom = glrtx_ctx::kMtNone;
     c->st.stack_entries = stack_need;
     c->st.lds_bytes = lds_bytes_for(sc);
     c->st.n_tri = c->n_tri; c->st.n_fork = c->n_fork; c->st.n_mat = c->n_mat; c->st.n_light = c->n_light;
@@ -1754,6 +1768,29 @@ int refit_run(glrtx_ctx *c, const void *dev_vert) {
     return GLRTX_OK;
 }
 
+// glrtx_track_motion: the scene's leaf records as they stand become the previous geometry (motion::snapshot_kernel), on the context's stream.  Only reads the
+// scene, so it needs no wait for the pipe slots; the refit that follows on the same stream is ordered behind it.
+int motion_snapshot(glrtx_ctx *c) {
+    const size_t bytes = (size_t)std::max(c->n_tri, 1) * 3 * sizeof(float4);
+    for (DevBuf *b : {&c->mtPos, &c->mtNrm})
+        if (b->bytes < bytes) {  // (triangles no leaf names are never looked up: G holds leaves' triangles only; zeroed all the same)
+            if (int rc = ensure(c, *b, bytes)) return rc;
+            HIP_TRY(c, hipMemsetAsync(b->p, 0, b->bytes, c->stream));
+        }
+    const refit::Args &r = c->rf.a;
+    motion::SnapArgs a;
+    a.nodes = r.nodes; a.nrms = r.nrms;
+    a.wire = (const int *)c->qwire.p;
+    a.n_ids = r.n_ids; a.n_leaf = r.n_leaf; a.n_tri = c->n_tri;
+    a.prev_pos = (uint4 *)c->mtPos.p; a.prev_nrm = (uint4 *)c->mtNrm.p;
+    if (a.n_leaf > 0) {
+        hipLaunchKernelGGL(motion::snapshot_kernel, dim3((unsigned)((a.n_leaf + 255) / 256)), dim3(256), 0, c->stream, a);
+        HIP_TRY(c, hipGetLastError());
+    }
+    c->mt_geom = glrtx_ctx::kMtSaved;
+    return GLRTX_OK;
+}
+
 int update_check(glrtx_ctx *c, const void *vert, size_t n_vert, const char *fn) {
     if (!c) return GLRTX_EINVAL;
     if (!c->have_scene) return fail(c, GLRTX_EINVAL, "%s: no scene uploaded", fn);
@@ -1771,6 +1808,8 @@ int glrtx_update_vertices(glrtx_ctx *c, const float *vert, size_t n_vert) {
     const size_t bytes = n_vert * 15 * sizeof(float);
     if (int rc = ensure(c, c->rf.vert, bytes)) return rc;
     HIP_TRY(c, hipMemcpyAsync(c->rf.vert.p, vert, bytes, hipMemcpyHostToDevice, c->stream));
+    if (c->mt_on && c->mt_geom == glrtx_ctx::kMtCurrent)  // the first move since the last feature pass: keep where the geometry was
+        if (int rc = motion_snapshot(c)) return rc;
     return refit_run(c, c->rf.vert.p);
 }
 
@@ -1778,6 +1817,8 @@ int glrtx_update_vertices_device(glrtx_ctx *c, const void *dev_vert, size_t n_ve
     if (int rc = update_check(c, dev_vert, n_vert, "glrtx_update_vertices_device")) return rc;
     seal_feed(c);
     HIP_TRY(c, hipSetDevice(c->device));
+    if (c->mt_on && c->mt_geom == glrtx_ctx::kMtCurrent)
+        if (int rc = motion_snapshot(c)) return rc;
     return refit_run(c, dev_vert);
 }
 
@@ -2404,8 +2445,14 @@ int glrtx_render_features(glrtx_ctx *c, const glrtx_params *p) {
     const size_t bytes = (size_t)c->width * (size_t)std::max(c->owned_rows, 1) * sizeof(float4);
     int rc;
     if ((rc = ensure(c, c->ftN, bytes)) || (rc = ensure(c, c->ftA, bytes)) || (rc = ensure(c, c->ftCounter, sizeof(unsigned)))) return rc;
+    const bool geom = c->mt_on;  // glrtx_track_motion: the *_geom kernels, which write G as well
+    if (geom && (rc = ensure(c, c->ftG, bytes))) return rc;
     c->ft_w = c->width; c->ft_rows = c->owned_rows;
-    if (c->owned_rows == 0) return GLRTX_OK;
+    const auto planes_written = [&]() {  // (glrtx_track_motion; only once nothing can fail any more) the scene as it stands is what these planes show
+        if (geom) { c->mt_g_have = true; c->mt_geom = glrtx_ctx::kMtCurrent; }
+        return GLRTX_OK;
+    };
+    if (c->owned_rows == 0) return planes_written();
     const bool vine = c->sc.n_vine > 0;
     const int fetch = wgwf_fetch(c, vine);
     const int lds_stack = 2 * c->sc.stack_entries * kBlockThreads * (int)sizeof(int), lds_ranks = c->sc.n_crank * (int)sizeof(uint2);
@@ -2413,7 +2460,11 @@ int glrtx_render_features(glrtx_ctx *c, const glrtx_params *p) {
     if (const char *v = std::getenv("GLRTX_COMPACT_NODES")) compact = std::atoi(v) != 0 && !vine && c->sc.n_crank > 0;
     compact = compact && lds_stack + lds_ranks <= 160 * 1024;
     using Kernel = void (*)(const features::Args);
-    const Kernel kernel = vine ? (Kernel)features::features_vine : compact ? (Kernel)features::features_tree<true> : (Kernel)features::features_tree<false>;
+    using KernelG = void (*)(const features::GeomArgs);
+    const Kernel kernel_n = vine ? (Kernel)features::features_vine : compact ? (Kernel)features::features_tree<true> : (Kernel)features::features_tree<false>;
+    const KernelG kernel_g = vine ? (KernelG)features::features_vine_geom
+                                  : compact ? (KernelG)features::features_tree_geom<true> : (KernelG)features::features_tree_geom<false>;
+    const void *kernel = geom ? (const void *)kernel_g : (const void *)kernel_n;
     const int lds = vine ? 0 : lds_stack + (compact ? lds_ranks : 0);
     if (lds > 64 * 1024) HIP_TRY(c, hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     int per_cu = 0;
@@ -2433,9 +2484,16 @@ int glrtx_render_features(glrtx_ctx *c, const glrtx_params *p) {
     const size_t needed = (a.n + kBlockThreads - 1) / kBlockThreads;
     const unsigned grid = (unsigned)std::max<size_t>(1, std::min<size_t>((size_t)per_cu * (size_t)c->n_cu, needed));
     HIP_TRY(c, hipMemsetAsync(c->ftCounter.p, 0, sizeof(unsigned), c->stream));
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlockThreads), lds, c->stream, a);
+    if (geom) {
+        features::GeomArgs ga;
+        static_cast<features::Args &>(ga) = a;
+        ga.out_g = (float4 *)c->ftG.p; ga.wire = (const int *)c->qwire.p;
+        hipLaunchKernelGGL(kernel_g, dim3(grid), dim3(kBlockThreads), lds, c->stream, ga);
+    } else {
+        hipLaunchKernelGGL(kernel_n, dim3(grid), dim3(kBlockThreads), lds, c->stream, a);
+    }
     HIP_TRY(c, hipGetLastError());
-    return GLRTX_OK;
+    return planes_written();
 }
 
 static int denoise_shape_check(glrtx_ctx *c, const char *fn, bool need_result) {
@@ -2579,8 +2637,29 @@ static int reproject_pass(glrtx_ctx *c, hipStream_t stream, const glrt_detail::R
     return GLRTX_OK;
 }
 
-int glrtx_reproject(glrtx_ctx *c, const glrtx_params *cur, const glrtx_reproject_cfg *cfg) {
-    const char *fn = "glrtx_reproject";
+// The motion-aware kernel (reproject_motion.hip.h) on `stream`, as reproject_pass runs the static one; prev_pos / prev_nrm: motion::Args'.
+static int reproject_motion_pass(glrtx_ctx *c, hipStream_t stream, const glrt_detail::ReprojectSetup &st, const float4 *acc, const float4 *n0, const float4 *a0,
+                                 const float4 *g1, const float4 *a1, const float4 *prev_pos, const float4 *prev_nrm, int n_tri, float4 *out, int pitch_f4, int width,
+                                 int rows, void *counts) {
+    motion::Args a{};
+    std::memcpy(a.W, st.W, sizeof a.W);
+    std::memcpy(a.S, st.S, sizeof a.S);
+    a.opx = st.o_prev[0]; a.opy = st.o_prev[1]; a.opz = st.o_prev[2];
+    a.acc = acc; a.n0 = n0; a.a0 = a0; a.g1 = g1; a.a1 = a1; a.out = out;
+    a.prev_pos = prev_pos; a.prev_nrm = prev_nrm; a.n_tri = n_tri;
+    a.pitch_f4 = pitch_f4; a.width = width; a.rows = rows;
+    a.tiles_x = (width + 7) / 8;
+    a.n_tiles = a.tiles_x * ((rows + 7) / 8);
+    a.max_history = st.max_history; a.depth_tol = st.depth_tolerance; a.normal_tol = st.normal_tolerance;
+    a.counts = (unsigned long long *)counts;
+    HIP_TRY(c, hipMemsetAsync(counts, 0, reproject::kCountBytes, stream));
+    hipLaunchKernelGGL(motion::reproject_motion_kernel, dim3((unsigned)((a.n_tiles + 3) / 4)), dim3(256), 0, stream, a);
+    HIP_TRY(c, hipGetLastError());
+    return GLRTX_OK;
+}
+
+// glrtx_reproject (motion false) and glrtx_reproject_motion (true): one sequence, two kernels.
+static int reproject_call(glrtx_ctx *c, const glrtx_params *cur, const glrtx_reproject_cfg *cfg, const char *fn, bool motion) {
     if (!c) return GLRTX_EINVAL;
     if (!cur || !cfg) return fail(c, GLRTX_EINVAL, "%s: NULL params or cfg", fn);
     // everything glrtx_render_features refuses, before anything changes
@@ -2592,6 +2671,12 @@ int glrtx_reproject(glrtx_ctx *c, const glrtx_params *cur, const glrtx_reproject
     if (c->world > 1) return fail(c, GLRTX_EINVAL, "%s: the context is partitioned (rank %d of %d): a pixel's history may lie on another rank", fn, c->rank, c->world);
     if (c->bound) return fail(c, GLRTX_EINVAL, "%s: a caller-owned accumulator is bound (glrtx_bind_accum): the call swaps accumulators", fn);
     if (int rc = denoise_shape_check(c, fn, false)) return rc;
+    if (motion) {
+        if (!c->mt_on) return fail(c, GLRTX_EINVAL, "%s: motion tracking is off (glrtx_track_motion)", fn);
+        if (!c->ftG.p || !c->mt_g_have) return fail(c, GLRTX_EINVAL, "%s: no geometry plane (call glrtx_render_features with tracking on first)", fn);
+        if (c->mt_geom == glrtx_ctx::kMtNone)
+            return fail(c, GLRTX_EINVAL, "%s: the previous geometry is not known (a scene was uploaded since the last glrtx_render_features)", fn);
+    }
     glrt_detail::ReprojectSetup st;
     if (int rc = reproject_setup_check(c, fn, c->ft_cam, c->ft_cam + 16, cfg, st)) return rc;
     seal_feed(c);
@@ -2599,6 +2684,7 @@ int glrtx_reproject(glrtx_ctx *c, const glrtx_params *cur, const glrtx_reproject
     const size_t acc_bytes = c->pitch_bytes * (size_t)std::max(c->owned_rows, 1);
     int rc;
     if ((rc = ensure(c, c->accum_spare, acc_bytes)) || (rc = ensure(c, c->rpCount, reproject::kCountBytes))) return rc;
+    if (motion && c->mt_geom == glrtx_ctx::kMtCurrent && (rc = motion_snapshot(c))) return rc;  // nothing moved since the planes: previous = current
     for (auto &sl : c->pipe)  // behind every launch that may still add to the accumulator or read the scene (refit_run's rule)
         if (sl.stream && sl.used) {
             HIP_TRY(c, hipEventRecord(c->rf.slot_ev, sl.stream));
@@ -2606,22 +2692,62 @@ int glrtx_reproject(glrtx_ctx *c, const glrtx_params *cur, const glrtx_reproject
         }
     std::swap(c->ftN, c->ftN_spare);  // the planes as they stand become N0 / A0; glrtx_render_features fills (on first use: allocates) the other pair
     std::swap(c->ftA, c->ftA_spare);
+    if (c->mt_on) std::swap(c->ftG, c->ftG_spare);  // (glrtx_track_motion: the third pair goes with them)
     float cam_prev[32];
     std::memcpy(cam_prev, c->ft_cam, sizeof cam_prev);
     if ((rc = glrtx_render_features(c, cur))) {  // (only an allocation or a launch can fail here: the planes and their camera are put back)
         std::swap(c->ftN, c->ftN_spare);
         std::swap(c->ftA, c->ftA_spare);
+        if (c->mt_on) std::swap(c->ftG, c->ftG_spare);
         std::memcpy(c->ft_cam, cam_prev, sizeof cam_prev);
         return rc;
     }
     const int pitch_f4 = (int)(c->pitch_bytes / sizeof(float4));
-    if ((rc = reproject_pass(c, c->stream, st, cur->c2w, cur->s2c, c->stripe, c->accum, (const float4 *)c->ftN_spare.p, (const float4 *)c->ftA_spare.p,
-                             (const float4 *)c->ftN.p, (const float4 *)c->ftA.p, (float4 *)c->accum_spare.p, pitch_f4, c->width, c->owned_rows, c->rpCount.p)))
-        return rc;
+    if (motion)
+        rc = reproject_motion_pass(c, c->stream, st, c->accum, (const float4 *)c->ftN_spare.p, (const float4 *)c->ftA_spare.p, (const float4 *)c->ftG.p,
+                                   (const float4 *)c->ftA.p, (const float4 *)c->mtPos.p, (const float4 *)c->mtNrm.p, c->n_tri, (float4 *)c->accum_spare.p, pitch_f4,
+                                   c->width, c->owned_rows, c->rpCount.p);
+    else
+        rc = reproject_pass(c, c->stream, st, cur->c2w, cur->s2c, c->stripe, c->accum, (const float4 *)c->ftN_spare.p, (const float4 *)c->ftA_spare.p,
+                            (const float4 *)c->ftN.p, (const float4 *)c->ftA.p, (float4 *)c->accum_spare.p, pitch_f4, c->width, c->owned_rows, c->rpCount.p);
+    if (rc) return rc;
     std::swap(c->accum_own, c->accum_spare);  // the accumulator rendered into from here on (glrtx_accum_device_ptr changes)
     c->accum = (float4 *)c->accum_own.p;
     c->rp_have = true;
     if (c->adHalf.p && (rc = adapt_half_ensure(c))) return rc;  // H held every second sample of the OLD view's pixels: zeroed, every tile is active again
+    return GLRTX_OK;
+}
+
+int glrtx_reproject(glrtx_ctx *c, const glrtx_params *cur, const glrtx_reproject_cfg *cfg) { return reproject_call(c, cur, cfg, "glrtx_reproject", false); }
+int glrtx_reproject_motion(glrtx_ctx *c, const glrtx_params *cur, const glrtx_reproject_cfg *cfg) { return reproject_call(c, cur, cfg, "glrtx_reproject_motion", true); }
+
+int glrtx_track_motion(glrtx_ctx *c, int enable) {
+    if (!c) return GLRTX_EINVAL;
+    const bool on = enable != 0;
+    if (on == c->mt_on) return GLRTX_OK;
+    if (!on) {  // forget the previous geometry and the planes: nothing may still read them
+        seal_feed(c);
+        if (int rc = glrtx_sync(c)) return rc;
+        HIP_TRY(c, hipSetDevice(c->device));
+        dev_free(c->ftG); dev_free(c->ftG_spare); dev_free(c->mtPos); dev_free(c->mtNrm);
+    }
+    c->mt_on = on;
+    c->mt_g_have = false;
+    c->mt_geom = glrtx_ctx::kMtNone;
+    return GLRTX_OK;
+}
+
+int glrtx_read_features_geom(glrtx_ctx *c, float *geom, size_t pitch_bytes) {
+    const char *fn = "glrtx_read_features_geom";
+    if (!c || !geom) return GLRTX_EINVAL;
+    if (!c->mt_on) return fail(c, GLRTX_EINVAL, "%s: motion tracking is off (glrtx_track_motion)", fn);
+    if (int rc = denoise_shape_check(c, fn, false)) return rc;
+    if (!c->ftG.p || !c->mt_g_have) return fail(c, GLRTX_EINVAL, "%s: no geometry plane (call glrtx_render_features with tracking on first)", fn);
+    const size_t row = (size_t)c->width * sizeof(float4);
+    if (pitch_bytes < row) return fail(c, GLRTX_EINVAL, "%s: pitch too small", fn);
+    if (int rc = glrtx_sync(c)) return rc;
+    if (c->owned_rows == 0) return GLRTX_OK;
+    HIP_TRY(c, hipMemcpy2D(geom, pitch_bytes, c->ftG.p, row, row, (size_t)c->owned_rows, hipMemcpyDeviceToHost));
     return GLRTX_OK;
 }
 
@@ -2653,6 +2779,51 @@ int glrtx_debug_reproject(const float *accum, const float *n0, const float *a0, 
     if (e == hipSuccess)
         rc = reproject_pass(nullptr, 0, st, c2w_cur, s2c_cur, 16, (const float4 *)d[0], (const float4 *)d[1], (const float4 *)d[2], (const float4 *)d[3], (const float4 *)d[4],
                             (float4 *)d[5], width, width, rows, d[6]);
+    if (e == hipSuccess && rc == GLRTX_OK) e = hipDeviceSynchronize();
+    if (e == hipSuccess && rc == GLRTX_OK) e = hipMemcpy(out, d[5], bytes, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && rc == GLRTX_OK) e = reproject_counts(d[6], carried, hit_pixels);
+    if (e != hipSuccess) rc = fail(nullptr, GLRTX_EDEVICE, "%s: %s", fn, hipGetErrorString(e));
+    for (void *q : d)
+        if (q) (void)hipFree(q);
+    return rc;
+}
+
+int glrtx_debug_reproject_motion(const float *accum, const float *n0, const float *a0, const float *g1, const float *a1, const float *vert_prev, size_t n_vert,
+                                 const float *tri, size_t n_tri, const float *c2w_prev, const float *s2c_prev, int width, int rows, const glrtx_reproject_cfg *cfg,
+                                 float *out, int *carried, int *hit_pixels) {
+    const char *fn = "glrtx_debug_reproject_motion";
+    if (width < 1 || rows < 1 || width > 65536 || rows > 65536 || (size_t)width * (size_t)rows > ((size_t)1 << 31))
+        return fail(nullptr, GLRTX_EINVAL, "%s: bad size %dx%d", fn, width, rows);
+    if (!accum || !n0 || !a0 || !g1 || !a1 || !c2w_prev || !s2c_prev || !cfg || !out) return fail(nullptr, GLRTX_EINVAL, "%s: NULL argument", fn);
+    if ((n_tri && (!tri || !vert_prev)) || n_tri > (size_t)INT32_MAX / 4) return fail(nullptr, GLRTX_EINVAL, "%s: NULL geometry or too many triangles", fn);
+    glrt_detail::ReprojectSetup st;
+    if (int rc = reproject_setup_check(nullptr, fn, c2w_prev, s2c_prev, cfg, st)) return rc;
+    // the previous records as pack_scene forms a triangle's: {p0} {p1 - p0} {p2 - p0}, {n0} {n1} {n2}
+    std::vector<float4> pos(3 * std::max<size_t>(n_tri, 1), make_float4(0.f, 0.f, 0.f, 0.f)), nrm(pos.size(), make_float4(0.f, 0.f, 0.f, 0.f));
+    for (size_t t = 0; t < n_tri; t++) {
+        const float *v[3];
+        for (int k = 0; k < 3; k++) {
+            const float f = tri[4 * t + k];
+            if (!(f >= 0.0f) || (size_t)f >= n_vert) return fail(nullptr, GLRTX_EINVAL, "%s: triangle %zu: vertex index %g out of range", fn, t, (double)f);
+            v[k] = vert_prev + 15 * (size_t)f;
+        }
+        pos[3 * t] = make_float4(v[0][0], v[0][1], v[0][2], 0.f);
+        pos[3 * t + 1] = make_float4(v[1][0] - v[0][0], v[1][1] - v[0][1], v[1][2] - v[0][2], 0.f);
+        pos[3 * t + 2] = make_float4(v[2][0] - v[0][0], v[2][1] - v[0][1], v[2][2] - v[0][2], 0.f);
+        for (int k = 0; k < 3; k++) nrm[3 * t + k] = make_float4(v[k][3], v[k][4], v[k][5], 0.f);
+    }
+    const size_t bytes = (size_t)width * rows * sizeof(float4), gbytes = pos.size() * sizeof(float4);
+    const float *src[5] = {accum, n0, a0, g1, a1};
+    void *d[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // accum, N0, A0, G1, A1, out, counts, positions, normals
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < 9 && e == hipSuccess; i++) e = hipMalloc(&d[i], i == 6 ? reproject::kCountBytes : i > 6 ? gbytes : bytes);
+    for (int i = 0; i < 5 && e == hipSuccess; i++) e = hipMemcpy(d[i], src[i], bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d[7], pos.data(), gbytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d[8], nrm.data(), gbytes, hipMemcpyHostToDevice);
+    int rc = GLRTX_OK;
+    if (e == hipSuccess)
+        rc = reproject_motion_pass(nullptr, 0, st, (const float4 *)d[0], (const float4 *)d[1], (const float4 *)d[2], (const float4 *)d[3], (const float4 *)d[4],
+                                   (const float4 *)d[7], (const float4 *)d[8], (int)n_tri, (float4 *)d[5], width, width, rows, d[6]);
     if (e == hipSuccess && rc == GLRTX_OK) e = hipDeviceSynchronize();
     if (e == hipSuccess && rc == GLRTX_OK) e = hipMemcpy(out, d[5], bytes, hipMemcpyDeviceToHost);
     if (e == hipSuccess && rc == GLRTX_OK) e = reproject_counts(d[6], carried, hit_pixels);

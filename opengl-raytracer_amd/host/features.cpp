@@ -1,4 +1,4 @@
-// features.cpp -- glrt_render_features (include/glrt_host.h): the CPU statement of the device's feature pass (glrtx_render_features, include/glrtx.h;
+// features.cpp -- glrt_render_features / glrt_render_features_geom (include/glrt_host.h): the CPU statement of the device's feature pass (glrtx_render_features, include/glrtx.h;
 // csrc/features.hip.h), on the wire-format scene.
 //
 // Per owned pixel: the primary ray of the pixel's centre (the renderer's camera_ray with r0 = r1 = 0.5 and no thin lens, the same expressions in the same
@@ -33,10 +33,9 @@ struct FlushDenormals {
 inline float canon(float x) { const uint32_t q = 0x7FC00000u; float n; std::memcpy(&n, &q, 4); return x != x ? n : x; }
 inline float dot3(float ax, float ay, float az, float bx, float by, float bz) { return (az * bz + ay * by) + ax * bx; }
 
-}  // namespace
-
-int glrt_render_features(const float *vert, size_t n_vert, const float *tri, size_t n_tri, const float *nodes, size_t n_nodes, const float *mat, size_t n_mat,
-                         const float *c2w, const float *s2c, int width, int height, int rank, int world, int stripe, float *out_n, float *out_a) {
+// the pass; out_g (may be NULL): the geometry plane {wire triangle as int32 bits, u, v, 0} of glrt_render_features_geom
+int render_planes(const float *vert, size_t n_vert, const float *tri, size_t n_tri, const float *nodes, size_t n_nodes, const float *mat, size_t n_mat,
+                  const float *c2w, const float *s2c, int width, int height, int rank, int world, int stripe, float *out_n, float *out_a, float *out_g) {
     if (!c2w || !s2c || !out_n || !out_a) return GLRT_HOST_EINVAL;
     if (width < 1 || height < 1 || width > 65536 || height > 65536 || world < 1 || rank < 0 || rank >= world || stripe < 1) return GLRT_HOST_EINVAL;
     if (n_nodes > 0 && (!vert || !tri || !nodes || !mat)) return GLRT_HOST_EINVAL;
@@ -79,6 +78,25 @@ int glrt_render_features(const float *vert, size_t n_vert, const float *tri, siz
             if ((int)m[0] == 2) { A[0] = m[6]; A[1] = m[7]; A[2] = m[8]; }  // a diffuse material: param0
         }
         std::memcpy(&A[3], &id, 4);
+        if (out_g) {  // the walker's own {tri, u, v}; a miss {-1, 0, 0, 0}
+            float *G = out_g + 4 * i;
+            const int32_t miss = -1;
+            std::memcpy(&G[0], t >= 0 ? &t : &miss, 4);
+            G[1] = t >= 0 ? h[2] : 0.0f; G[2] = t >= 0 ? h[3] : 0.0f; G[3] = 0.0f;
+        }
     }
     return GLRT_HOST_OK;
+}
+
+}  // namespace
+
+int glrt_render_features(const float *vert, size_t n_vert, const float *tri, size_t n_tri, const float *nodes, size_t n_nodes, const float *mat, size_t n_mat,
+                         const float *c2w, const float *s2c, int width, int height, int rank, int world, int stripe, float *out_n, float *out_a) {
+    return render_planes(vert, n_vert, tri, n_tri, nodes, n_nodes, mat, n_mat, c2w, s2c, width, height, rank, world, stripe, out_n, out_a, nullptr);
+}
+
+int glrt_render_features_geom(const float *vert, size_t n_vert, const float *tri, size_t n_tri, const float *nodes, size_t n_nodes, const float *mat, size_t n_mat,
+                              const float *c2w, const float *s2c, int width, int height, int rank, int world, int stripe, float *out_n, float *out_a, float *out_g) {
+    if (!out_g) return GLRT_HOST_EINVAL;
+    return render_planes(vert, n_vert, tri, n_tri, nodes, n_nodes, mat, n_mat, c2w, s2c, width, height, rank, world, stripe, out_n, out_a, out_g);
 }

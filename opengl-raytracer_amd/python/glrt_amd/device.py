@@ -92,7 +92,8 @@ EXPORTS = ["glrtx_abi_version", "glrtx_create", "glrtx_destroy", "glrtx_last_err
            "glrtx_group_render_adaptive", "glrtx_group_adaptive_active_tiles", "glrtx_debug_pack_compact", "glrtx_set_volume_wavefront",
            "glrtx_render_features", "glrtx_read_features", "glrtx_denoise", "glrtx_read_denoised", "glrtx_resolve_denoised_rgba8", "glrtx_debug_denoise",
            "glrtx_update_vertices", "glrtx_update_vertices_device", "glrtx_group_update_vertices", "glrtx_debug_read_scene",
-           "glrtx_trace_rays", "glrtx_trace_rays_device", "glrtx_reproject", "glrtx_reproject_last", "glrtx_debug_reproject"]
+           "glrtx_trace_rays", "glrtx_trace_rays_device", "glrtx_reproject", "glrtx_reproject_last", "glrtx_debug_reproject",
+           "glrtx_track_motion", "glrtx_read_features_geom", "glrtx_reproject_motion", "glrtx_debug_reproject_motion"]
 
 SCENE_BUFFERS = ("nodes", "cnodes", "nrms", "lights", "vine", "root")  # glrtx_debug_read_scene's `which`, in order (GLRTX_SCENE_*)
 
@@ -211,6 +212,14 @@ def lib():
             L.glrtx_reproject.argtypes = [vp, C.POINTER(Params), C.POINTER(ReprojectCfg)]
             L.glrtx_reproject_last.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
             L.glrtx_debug_reproject.argtypes = [fp] * 9 + [C.c_int, C.c_int, C.POINTER(ReprojectCfg), fp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        except AttributeError:
+            pass
+        try:  # (additive to ABI 10 as well: reprojection across a geometry move)
+            L.glrtx_track_motion.argtypes = [vp, C.c_int]
+            L.glrtx_read_features_geom.argtypes = [vp, vp, C.c_size_t]
+            L.glrtx_reproject_motion.argtypes = [vp, C.POINTER(Params), C.POINTER(ReprojectCfg)]
+            L.glrtx_debug_reproject_motion.argtypes = [fp] * 6 + [C.c_size_t, fp, C.c_size_t, fp, fp, C.c_int, C.c_int, C.POINTER(ReprojectCfg), fp,
+                                                       C.POINTER(C.c_int), C.POINTER(C.c_int)]
         except AttributeError:
             pass
         _lib = L
@@ -335,6 +344,27 @@ def debug_reproject(accum, n0, a0, n1, a1, prev, cur, **cfg):
     c = ReprojectCfg.default(**cfg)
     carried, hits = C.c_int(0), C.c_int(0)
     rc = L.glrtx_debug_reproject(*[_fp(v) for v in arr], *[_fp(m) for m in mats], a.shape[1], a.shape[0], C.byref(c), _fp(out), C.byref(carried), C.byref(hits))
+    if rc != 0:
+        raise GlrtxError(rc, L.glrtx_last_error(None).decode())
+    return out, int(carried.value), int(hits.value)
+
+
+def debug_reproject_motion(accum, n0, a0, g1, a1, vert_prev, tri, prev, **cfg):
+    """glrtx_debug_reproject_motion on the current device: the motion-aware reprojection kernel on (rows, width, 4) float32 arrays (the old view's accumulator
+    and planes, the new view's geometry and albedo planes), the vertices as they stood at the old view, the triangles, and the old view's camera (a dict with
+    c2w and s2c).  Returns (out, carried, hit_pixels)."""
+    L = lib()
+    arr = [_f32(v) for v in (accum, n0, a0, g1, a1)]
+    a = arr[0]
+    if a.ndim != 3 or a.shape[2] != 4 or any(v.shape != a.shape for v in arr):
+        raise ValueError(f"debug_reproject_motion: five (rows, width, 4) arrays of one shape expected, got {[v.shape for v in arr]}")
+    vert, tr = _f32(vert_prev).reshape(-1, 15), _f32(tri).reshape(-1, 4)
+    mats = [_f32(np.asarray(m).reshape(16)) for m in (prev["c2w"], prev["s2c"])]
+    out = np.zeros_like(a)
+    c = ReprojectCfg.default(**cfg)
+    carried, hits = C.c_int(0), C.c_int(0)
+    rc = L.glrtx_debug_reproject_motion(*[_fp(v) for v in arr], _fp(vert), vert.shape[0], _fp(tr), tr.shape[0], *[_fp(m) for m in mats], a.shape[1], a.shape[0],
+                                        C.byref(c), _fp(out), C.byref(carried), C.byref(hits))
     if rc != 0:
         raise GlrtxError(rc, L.glrtx_last_error(None).decode())
     return out, int(carried.value), int(hits.value)
@@ -669,6 +699,22 @@ class Device:
         a, b = C.c_int(0), C.c_int(0)
         self._ck(self.L.glrtx_reproject_last(self.h, C.byref(a), C.byref(b)))
         return int(a.value), int(b.value)
+    def track_motion(self, enable=True):
+        """Motion tracking on or off (glrtx_track_motion): while on, the feature passes also write the geometry plane and update_vertices keeps the geometry
+        of the last feature pass, which reproject_motion needs."""
+        self._ck(self.L.glrtx_track_motion(self.h, int(bool(enable))))
+    def read_features_geom(self) -> np.ndarray:
+        """The geometry plane G, (owned_rows, width, 4) float32 (syncs): [..., 0] the wire triangle index as int32 bits (-1: a miss), [..., 1:3] the hit's
+        barycentrics."""
+        s = self.stats()
+        g = np.zeros((s.owned_rows, s.width, 4), np.float32)
+        self._ck(self.L.glrtx_read_features_geom(self.h, g.ctypes.data, s.width * 16))
+        return g
+    def reproject_motion(self, params, max_history=None, depth_tolerance=None, normal_tolerance=None):
+        """Device.reproject for geometry that update_vertices moved since the last feature pass (glrtx_reproject_motion; needs track_motion)."""
+        p = make_params(params)
+        c = ReprojectCfg.default(max_history, depth_tolerance, normal_tolerance)
+        self._ck(self.L.glrtx_reproject_motion(self.h, C.byref(p), C.byref(c)))
     def timer_begin(self):
         self._ck(self.L.glrtx_timer_begin(self.h))
 

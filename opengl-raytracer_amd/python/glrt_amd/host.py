@@ -40,6 +40,9 @@ def lib():
         L.glrt_render_features.argtypes = [fp, C.c_size_t, fp, C.c_size_t, fp, C.c_size_t, fp, C.c_size_t, fp, fp] + [C.c_int] * 5 + [fp, fp]
         L.glrt_denoise_atrous.argtypes = [fp, fp, fp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int, fp]
         L.glrt_reproject.argtypes = [fp] * 9 + [C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, fp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.glrt_render_features_geom.argtypes = [fp, C.c_size_t, fp, C.c_size_t, fp, C.c_size_t, fp, C.c_size_t, fp, fp] + [C.c_int] * 5 + [fp, fp, fp]
+        L.glrt_reproject_motion.argtypes = [fp] * 6 + [C.c_size_t, fp, C.c_size_t, fp, fp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, fp,
+                                            C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.glrt_look_at.argtypes = [fp, fp, fp, fp]
         L.glrt_perspective.argtypes = [C.c_float, C.c_float, C.c_float, C.c_float, fp]
         L.glrt_mat4_mul.argtypes = [fp, fp, fp]
@@ -175,6 +178,22 @@ def render_features(scene, params, width=None, height=None, rank=0, world=1, str
     return n, a
 
 
+def render_features_geom(scene, params, width=None, height=None, rank=0, world=1, stripe=16):
+    """glrt_render_features_geom: render_features with the geometry plane, the CPU statement of the feature pass under Device.track_motion.  Returns
+    (normal_depth, albedo_id, geom); geom[..., 0] holds the wire triangle index as int32 bits (-1: a miss), geom[..., 1:3] the hit's barycentrics."""
+    w, h = int(width or params["width"]), int(height or params["height"])
+    vert, tri = _f32(scene["vert"]).reshape(-1, 15), _f32(scene["tri"]).reshape(-1, 4)
+    nodes, mat = _f32(scene["bvh"]).reshape(-1, 9), _f32(scene["mat"]).reshape(-1, 18)
+    c2w, s2c = _f32(params["c2w"]).reshape(16), _f32(params["s2c"]).reshape(16)
+    rows = sum(1 for y in range(h) if (y // stripe) % world == rank)
+    n, a, g = (np.zeros((rows, w, 4), np.float32) for _ in range(3))
+    rc = lib().glrt_render_features_geom(_fp(vert), vert.shape[0], _fp(tri), tri.shape[0], _fp(nodes), nodes.shape[0], _fp(mat), mat.shape[0], _fp(c2w), _fp(s2c),
+                                         w, h, rank, world, stripe, _fp(n), _fp(a), _fp(g))
+    if rc != 0:
+        raise RuntimeError(f"glrt_render_features_geom failed: {rc}")
+    return n, a, g
+
+
 # The denoiser's defaults (DESIGN.md "Denoising": chosen from the sweep recorded there); Device.denoise takes the same.
 DENOISE_DEFAULTS = dict(iterations=5, sigma_color=100.0, sigma_normal=0.1, sigma_depth=0.01, demodulate=True)
 
@@ -212,6 +231,26 @@ def reproject(accum, n0, a0, n1, a1, prev, cur, max_history=REPROJECT_DEFAULTS["
                               float(normal_tolerance), _fp(out), C.byref(carried), C.byref(hits))
     if rc != 0:
         raise RuntimeError(f"glrt_reproject failed: {rc}")
+    return out, int(carried.value), int(hits.value)
+
+
+def reproject_motion(accum, n0, a0, g1, a1, vert_prev, tri, prev, max_history=REPROJECT_DEFAULTS["max_history"],
+                     depth_tolerance=REPROJECT_DEFAULTS["depth_tolerance"], normal_tolerance=REPROJECT_DEFAULTS["normal_tolerance"]):
+    """glrt_reproject_motion: the CPU statement of Device.reproject_motion on (rows, width, 4) float32 arrays.  accum, n0, a0: the old view's accumulator and
+    feature planes; g1, a1: the new view's geometry and albedo planes; vert_prev: the vertices as they stood at the old view; tri: the scene's triangles;
+    prev: the old view's camera (a dict with c2w and s2c).  Returns (out, carried, hit_pixels)."""
+    arr = [_f32(v) for v in (accum, n0, a0, g1, a1)]
+    a = arr[0]
+    if a.ndim != 3 or a.shape[2] != 4 or any(v.shape != a.shape for v in arr):
+        raise ValueError(f"reproject_motion: five (rows, width, 4) arrays of one shape expected, got {[v.shape for v in arr]}")
+    vert, tr = _f32(vert_prev).reshape(-1, 15), _f32(tri).reshape(-1, 4)
+    mats = [_f32(m).reshape(16) for m in (prev["c2w"], prev["s2c"])]
+    out = np.zeros_like(a)
+    carried, hits = C.c_int(0), C.c_int(0)
+    rc = lib().glrt_reproject_motion(*[_fp(v) for v in arr], _fp(vert), vert.shape[0], _fp(tr), tr.shape[0], *[_fp(m) for m in mats], a.shape[1], a.shape[0],
+                                     int(max_history), float(depth_tolerance), float(normal_tolerance), _fp(out), C.byref(carried), C.byref(hits))
+    if rc != 0:
+        raise RuntimeError(f"glrt_reproject_motion failed: {rc}")
     return out, int(carried.value), int(hits.value)
 
 
