@@ -145,6 +145,19 @@ int glrt_render_features_geom(const float *vert, size_t n_vert, const float *tri
  * packed.  GLRT_HOST_EINVAL: a NULL array, a size outside 1..65536, iterations outside 1..6, a sigma that is not a positive finite number. */
 int glrt_denoise_atrous(const float *accum, const float *normal_depth, const float *albedo_id, int width, int rows, int iterations, float sigma_color,
                         float sigma_normal, float sigma_depth, int demodulate, float *out);
+/* Variance guidance: the CPU statements of glrtx_render_moments' fold, of the variance pass and of glrtx_denoise_variance / glrtx_debug_denoise_variance
+ * (include/glrtx.h "Variance guidance": the formulas are there), bit for bit (host/variance.cpp; tests/variance_math.py states them in numpy).  All images are
+ * width x rows x 4 floats, rows packed; V0 is width x rows floats.  They run with denormals flushed (MXCSR FTZ | DAZ, restored on return).
+ *   glrt_fold_moments       folds n_planes sample planes (plane k at planes + k * width * rows * 4), in order, into `moments` in place:
+ *                           l = (0.2126 r + 0.7152 g) + 0.0722 b;  M.x += l;  M.y += l * l;  M.w += 1.  n_planes = 0 changes nothing.
+ *   glrt_variance_estimate  V0 from the accumulator, M and the feature planes.
+ *   glrt_denoise_variance   the variance pass, then the filter; out: float4(rgb, 1); out_v0 (may be NULL): V0.
+ * GLRT_HOST_EINVAL: a NULL array, a size outside 1..65536, a negative n_planes, iterations outside 1..6, a sigma that is not a positive finite number. */
+int glrt_fold_moments(float *moments, const float *planes, int n_planes, int width, int rows);
+int glrt_variance_estimate(const float *accum, const float *moments, const float *normal_depth, const float *albedo_id, int width, int rows, float sigma_normal,
+                           float sigma_depth, int demodulate, float *out_v0);
+int glrt_denoise_variance(const float *accum, const float *moments, const float *normal_depth, const float *albedo_id, int width, int rows, int iterations,
+                          float sigma_lum, float sigma_normal, float sigma_depth, int demodulate, float *out, float *out_v0);
 
 /* Temporal reprojection: the CPU statement of the device's glrtx_reproject / glrtx_debug_reproject (include/glrtx.h "Reprojection": the formulas are there), bit
  * for bit.  accum / n0 / a0: the old view's accumulator float4(rgb sum, count) and feature planes; n1 / a1: the new view's planes; out: the new accumulator; all
@@ -163,6 +176,19 @@ int glrt_reproject(const float *accum, const float *n0, const float *a0, const f
 int glrt_reproject_motion(const float *accum, const float *n0, const float *a0, const float *g1, const float *a1, const float *vert_prev, size_t n_vert,
                           const float *tri, size_t n_tri, const float *c2w_prev, const float *s2c_prev, int width, int rows, int max_history,
                           float depth_tolerance, float normal_tolerance, float *out, int *carried, int *hit_pixels);
+
+/* The moments plane M through the two reprojections: the CPU statements of what glrtx_reproject / glrtx_reproject_motion write into the second M while
+ * glrtx_track_moments is on, and of glrtx_debug_reproject_moments / glrtx_debug_reproject_motion_moments (include/glrtx.h "Variance guidance": "Carrying M";
+ * host/reproject_moments.h holds the shared steps), bit for bit.  glrt_reproject / glrt_reproject_motion with two more arrays: moments (the old view's M) and
+ * moments_out (the new view's), width x rows x 4 floats each; `out`, carried and hit_pixels are what those calls give, bit for bit.  GLRT_HOST_EINVAL also for a
+ * NULL moments or moments_out. */
+int glrt_reproject_moments(const float *accum, const float *moments, const float *n0, const float *a0, const float *n1, const float *a1, const float *c2w_prev,
+                           const float *s2c_prev, const float *c2w_cur, const float *s2c_cur, int width, int rows, int max_history, float depth_tolerance,
+                           float normal_tolerance, float *out, float *moments_out, int *carried, int *hit_pixels);
+int glrt_reproject_motion_moments(const float *accum, const float *moments, const float *n0, const float *a0, const float *g1, const float *a1,
+                                  const float *vert_prev, size_t n_vert, const float *tri, size_t n_tri, const float *c2w_prev, const float *s2c_prev, int width,
+                                  int rows, int max_history, float depth_tolerance, float normal_tolerance, float *out, float *moments_out, int *carried,
+                                  int *hit_pixels);
 
 void glrt_look_at(const float eye[3], const float center[3], const float up[3], float out[16]);
 void glrt_perspective(float fovy_deg, float aspect, float z_near, float z_far, float out[16]);

@@ -495,6 +495,86 @@ int glrtx_read_denoised(glrtx_ctx *ctx, float *dst_rgba, size_t dst_pitch_bytes)
 int glrtx_resolve_denoised_rgba8(glrtx_ctx *ctx, uint8_t *dst, size_t dst_pitch_bytes, float gamma, int flip_y);
 int glrtx_debug_denoise(const float *accum, const float *normal_depth, const float *albedo_id, int width, int rows, const glrtx_denoise_cfg *cfg, float *out);
 
+/* ---- Variance guidance: per-pixel luminance moments and SVGF's variance-guided a-trous filter (Schied et al. 2017; no reference counterpart; everything here is
+ * off unless glrtx_track_moments switched it on, and while it is off no other call changes what it does or writes).  glrtx_denoise stops at colour edges with one
+ * fixed sigma_color for a pixel with 1 sample and for one with 64; here the luminance edge term is scaled by the standard deviation of each pixel's own mean, so a
+ * noisy pixel takes from its neighbours and a converged one is left alone.
+ *   lum(r, g, b) = (0.2126 r + 0.7152 g) + 0.0722 b.  The rules are those of "Denoising": every fp32 operation is one correctly rounded operation in the order
+ *   written, unfused (lp_exp carries the only fused ones), denormals flushed in and out; min / max are selects (max(x, 0) = x > 0 ? x : 0, so a NaN gives 0);
+ *   sqrt is the correctly rounded one; a NaN that is stored is 0x7FC00000.  host/variance.cpp (glrt_host.h) and tests/variance_math.py state the same arithmetic;
+ *   the three agree bit for bit.
+ *   glrtx_track_moments(enable)  off by default.  While on, the context owns a float4 plane M of the accumulator's pitch, {sum l, sum l^2, 0, count}, l = lum of one
+ *                          sample plane's rgb.  M is allocated (zeroed) on first use -- the first glrtx_render_moments or glrtx_read_moments --, zeroed by glrtx_clear
+ *                          and glrtx_bind_accum, released by glrtx_resize (and so by a partition change).  Switching tracking off syncs and releases M.
+ *                          glrtx_reproject and glrtx_reproject_motion zero the adaptive half buffer H; M they CARRY ("Carrying M" below): H's every-second-sample
+ *                          rule is a property of the old pixel grid and loses its meaning under resampling, whereas a surface point's luminance moments come
+ *                          along with its mean -- and the pixels with carried history are exactly the ones the filter should tighten on.
+ *   glrtx_render_moments   renders like glrtx_render_frames: the accumulator comes out bit for bit what glrtx_render_frames gives (the same chain of additions, in
+ *                          frame and sample order), and the same pass adds every sample to M: M.x += l; M.y += l * l; M.w += 1.  The launch shape is
+ *                          glrtx_render_adaptive's without a selection: never a fed launch (an open one is sealed first), plain launches with sample planes on the
+ *                          context's stream, in helpings of what the frames-in-flight budget allows.  n_frames = 0 only allocates M.  The adaptive half buffer is not
+ *                          touched.  GLRTX_EINVAL, nothing changed: tracking off, presentation enabled, extensions or volume on, spheres uploaded, variant != 2,
+ *                          max_depth / n_samples beyond the wavefront kernel's path state, and what glrtx_render_frames refuses.  Other rendering calls stay legal
+ *                          while tracking is on: they add samples M does not see.  M's own count says how many samples M holds; everything below uses M's count,
+ *                          never the accumulator's.
+ *   glrtx_read_moments     syncs, then copies M like glrtx_read_accum.  GLRTX_EINVAL while tracking is off.
+ *   glrtx_denoise_variance the variance pass, then the filter, into the same image D as glrtx_denoise (glrtx_read_denoised and glrtx_resolve_denoised_rgba8 serve
+ *                          it unchanged).  Issued on the context's stream without a sync.  GLRTX_EINVAL: what glrtx_denoise refuses (sigma_lum in sigma_color's
+ *                          place), tracking off, or before M exists (no first use since tracking was switched on or since a glrtx_resize).  Nothing here
+ *                          writes the accumulator, M, the adaptive half buffer, the present ring or glrtx_stats.rays.
+ *   glrtx_debug_denoise_variance  both passes on caller arrays (width x rows float4 each, rows packed) on the current HIP device, no context; v0_out (width x rows
+ *                          floats, may be NULL) receives V0.
+ * The variance pass: V0, a float per pixel -- the variance of the pixel's MEAN luminance, in the filter's colour space.  "Dead" is "Denoising"'s (acc.w a zero or a
+ * denormal, or id INT32_MIN); a dead pixel gets V0 = 0.  Per pixel: if M.w is neither a zero nor a denormal, mu1 = M.x / M.w and mu2 = M.y / M.w; otherwise
+ * mu1 = lum(acc.r / acc.w, acc.g / acc.w, acc.b / acc.w) and mu2 = mu1 * mu1.
+ *     temporal, where M.w >= 4 (a NaN fails):   v = max(mu2 - mu1 * mu1, 0) / M.w
+ *     spatial, elsewhere (every 1-spp frame):   over the 49 taps q = p + (dx, dy), dx, dy in -3..3, dy outermost, that lie inside the image, are alive and carry p's id
+ *                                               (the centre is one of them), from 0 in tap order:
+ *                                                   w = lp_exp(-(dn / sigma_normal + min(dd, 80)))        dn, dd exactly glrtx_denoise's
+ *                                                   sw = sw + w;  s1 = s1 + w * mu1_q;  s2 = s2 + w * mu2_q
+ *                                               S1 = s1 / max(sw, 1e-20), S2 = s2 / max(sw, 1e-20), v = max(S2 - S1 * S1, 0): the spread of neighbouring means already is a
+ *                                               variance of means, so there is no division by a count.
+ *     with demodulate: v = v / (la * la), la = lum(a), a = max(albedo, 1e-3) per channel as in "Denoising".      V0 = v (a NaN: 0x7FC00000).
+ * The filter: c and the dead pixels as glrtx_denoise prepares them, V = V0.  Iteration i = 0 .. iterations - 1 is glrtx_denoise's with two changes.
+ *     (1) g_p = (sum kw V_q) / (sum kw) over the 3x3 taps q = p + (dx, dy), dx, dy in -1..1, dy outermost, at unit spacing whatever i is, that lie inside the image, are
+ *         alive and carry p's id; kw = k3[dy+1] * k3[dx+1], k3 = {1, 2, 1} / 4; both sums from 0 in tap order.  sl_p = sigma_lum * sqrt(g_p) + 1e-6.  The tap weight is
+ *             w(q) = (k[dy+2] k[dx+2]) * lp_exp(-((|lum(c_q) - lum(c_p)| / sl_p + dn / sigma_normal) + min(dd, 80)))
+ *         sigma_lum does not shrink with i: the variance does that job.
+ *     (2) the variance is filtered alongside, over the same taps:  V'_p = (sum (w(q) * w(q)) * V_q) / (d * d),  d = max(sum w(q), 1e-20); a NaN is stored as 0x7FC00000,
+ *         a dead pixel gets 0.
+ *     After the last iteration c is multiplied by a again (demodulate), as there.
+ * Carrying M.  While tracking is on and M exists, glrtx_reproject and glrtx_reproject_motion also write a second M, allocated (before anything changes) and swapped
+ * as the second accumulator is, by the same kernel pass and the same taps ("Reprojection" steps 5-7; one function shared by both kernels: reproject.hip.h
+ * moments_tap / moments_out).  A tap counts for M if it counts in step 5 and its M.w is neither a zero nor a denormal.  Over those taps, from 0, in tap order:
+ *     sm = sm + w;   smc = smc + w * M.w;   s1 = s1 + w * (M.x / M.w);   s2 = s2 + w * (M.y / M.w)
+ * "No moments" means {0, 0, 0, 0}; it applies unless sm > 1e-6.  nm = rint(smc / sm), capped at max_history (nm > max_history ? max_history : nm); no moments
+ * unless nm >= 1 (a NaN fails); otherwise the new M is {(s1 / sm) * nm, (s2 / sm) * nm, 0, nm} (a NaN stored as 0x7FC00000).  A pixel with no accumulator history
+ * has no moments either.  The accumulator output of both calls and their carried / hit_pixels counts are bit for bit what they are with tracking off.
+ * glrtx_debug_reproject_moments / glrtx_debug_reproject_motion_moments are glrtx_debug_reproject / _motion with the old view's M in and the new view's M out
+ * (width x rows float4, rows packed); glrt_reproject_moments / glrt_reproject_motion_moments (glrt_host.h) and tests/variance_math.py state them again.
+ * Out of scope: groups (a partitioned context filters its own rows, as glrtx_denoise does); feeding M from fed
+ * launches, the present ring, the megakernels or the volume forms; separate direct and indirect buffers; making the adaptive selection use M. */
+typedef struct glrtx_denoise_var_cfg {
+    int   iterations;    /* 1..6; iteration i uses tap spacing 2^i */
+    float sigma_lum;     /* the luminance edge stops at sigma_lum standard deviations of the pixel's mean */
+    float sigma_normal;
+    float sigma_depth;
+    int   demodulate;    /* 1: filter I / max(albedo, 1e-3), multiply back at the end */
+} glrtx_denoise_var_cfg;
+int glrtx_track_moments(glrtx_ctx *ctx, int enable);
+int glrtx_render_moments(glrtx_ctx *ctx, const glrtx_params *params, const float *seeds_xy, int n_frames);
+int glrtx_read_moments(glrtx_ctx *ctx, float *dst_rgba, size_t dst_pitch_bytes);
+int glrtx_denoise_variance(glrtx_ctx *ctx, const glrtx_denoise_var_cfg *cfg);
+int glrtx_debug_denoise_variance(const float *accum, const float *moments, const float *normal_depth, const float *albedo_id, int width, int rows,
+                                 const glrtx_denoise_var_cfg *cfg, float *out, float *v0_out);
+struct glrtx_reproject_cfg;
+int glrtx_debug_reproject_moments(const float *accum, const float *moments, const float *n0, const float *a0, const float *n1, const float *a1, const float *c2w_prev,
+                                  const float *s2c_prev, const float *c2w_cur, const float *s2c_cur, int width, int rows, const struct glrtx_reproject_cfg *cfg,
+                                  float *out, float *moments_out, int *carried, int *hit_pixels);
+int glrtx_debug_reproject_motion_moments(const float *accum, const float *moments, const float *n0, const float *a0, const float *g1, const float *a1,
+                                         const float *vert_prev, size_t n_vert, const float *tri, size_t n_tri, const float *c2w_prev, const float *s2c_prev,
+                                         int width, int rows, const struct glrtx_reproject_cfg *cfg, float *out, float *moments_out, int *carried, int *hit_pixels);
+
 /* ---- Reprojection: carry the accumulator across a camera move (the reprojection step of SVGF, Schied et al. 2017; no reference counterpart -- the reference
  * clears and starts again at one sample, window.cpp:366-381; off unless called).  The context remembers the c2w and s2c of its last glrtx_render_features: the
  * PREVIOUS camera, the one the accumulator and the feature planes belong to.
@@ -505,7 +585,8 @@ int glrtx_debug_denoise(const float *accum, const float *normal_depth, const flo
  *                          accumulator of the same pitch (allocated on first use, released by glrtx_resize); (5) makes that second accumulator the one rendered
  *                          into: WHAT glrtx_accum_device_ptr RETURNS CHANGES with every successful call (the two buffers alternate) -- ask again after each one.
  *                          The remembered camera becomes `cur`, and the planes are cur's: a following glrtx_denoise needs no glrtx_render_features.  If the adaptive
- *                          half buffer exists it is zeroed (its every-second-sample rule has lost its meaning; H.w = 0 makes every tile active again).  The present
+ *                          half buffer exists it is zeroed (its every-second-sample rule has lost its meaning; H.w = 0 makes every tile active again);
+ *                          the moments plane M of glrtx_track_moments is carried, not zeroed ("Variance guidance").  The present
  *                          ring, glrtx_stats.rays and the denoised image are not touched; the call is not a frame.
  *                          GLRTX_EINVAL, nothing changed: NULL arguments; no feature planes, or planes of another shape than the image now has; a partitioned
  *                          context (world > 1: the source pixel may belong to another rank; groups are out of scope, as for glrtx_denoise); a caller-bound

@@ -25,6 +25,7 @@
 #include "query.hip.h"
 #include "features.hip.h"
 #include "denoise.hip.h"
+#include "variance.hip.h"
 #include "reproject.hip.h"
 #include "reproject_motion.hip.h"
 #include "../host/reproject_setup.h"
@@ -207,6 +208,15 @@ struct glrtx_ctx {
     bool mt_on = false, mt_g_have = false;  // mt_g_have: ftG holds the plane of the last feature pass
     int mt_geom = kMtNone;
     DevBuf ftG, ftG_spare, mtPos, mtNrm;
+
+    // Variance guidance (glrtx_track_moments / glrtx_render_moments / glrtx_denoise_variance): the moments plane M {sum l, sum l^2, 0, count} at the accumulator's
+    // shape (mm_pitch x mm_rows; allocated on first use while tracking is on, zeroed with the accumulator, released by glrtx_resize and by switching tracking off),
+    // and the filter's three variance planes (V0 and the ping-pong pair: packed floats of the features' shape, released with them).  moments_launch: set only while
+    // glrtx_render_moments issues its launches (launch_wgwf then runs plain, on the context's stream, with sample planes, and folds them with accumulate_moments_kernel).
+    DevBuf mmM, mmM_spare, dnV[3];  // (mmM_spare: the second M the reprojections write, of M's shape, swapped as accum_spare is)
+    size_t mm_pitch = 0;
+    int mm_rows = 0;
+    bool mm_on = false, moments_launch = false;
 
     bool count_rays = false;
     const char *last_kernel = "";  // name of the last render kernel launched (error reports)
@@ -1098,11 +1108,12 @@ int launch_wgwf(glrtx_ctx *c, const KernelArgs &a_in, const glrtx_params *p, con
     const bool burst = c->last_was_render && busy && same_camera(c->last_p, *p);
     const bool adapt = c->adapt_launch;  // (glrtx_render_adaptive: plain, on the context's stream, always with sample planes; never fed)
     const bool vol = c->ext_flags != 0;  // the V form (kWgwfVolume): routed here only with the volume alone (wgwf_routes)
-    bool fed = !adapt && c->feed_ok && std::getenv("GLRTX_NO_FEED") == nullptr && c->pipeline && c->stream == c->own_stream && p->n_samples >= 1 && seeds_xy != nullptr && (n_frames > 1 || burst);
+    const bool moments = c->moments_launch;  // (glrtx_render_moments: the same shape -- plain, with sample planes, never fed -- on the ordinary kernel)
+    bool fed = !adapt && !moments && c->feed_ok && std::getenv("GLRTX_NO_FEED") == nullptr && c->pipeline && c->stream == c->own_stream && p->n_samples >= 1 && seeds_xy != nullptr && (n_frames > 1 || burst);
     int fed_cap = fed ? std::min(frames_cap(c, p, (int)kFedSlots), kFeedMaxFrames) : 0;
     if (const char *v = std::getenv("GLRTX_FEED_CAP")) fed_cap = std::max(1, std::min(fed_cap, std::atoi(v)));  // (tests: launches that fill up)
     if (fed && n_frames > fed_cap) fed = false;
-    bool piped = fed || (!adapt && n_frames == 1 && c->pipeline && p->n_samples >= 1 && (size_t)p->n_samples * plane_bytes <= ((size_t)1 << 30));
+    bool piped = fed || (!adapt && !moments && n_frames == 1 && c->pipeline && p->n_samples >= 1 && (size_t)p->n_samples * plane_bytes <= ((size_t)1 << 30));
     const size_t ids = total * (size_t)(fed ? fed_cap : n_frames);  // path id = frame * total + pixel
     if (ids + 1 >= (size_t)UINT32_MAX)
         return fail(c, GLRTX_EINVAL, "glrtx_render_frames: %d frames of %zu pixels exceed the 32-bit ray id space", n_frames, total);
@@ -1304,7 +1315,7 @@ int launch_wgwf(glrtx_ctx *c, const KernelArgs &a_in, const glrtx_params *p, con
             w.seeds = (const float2 *)c->wfSeeds.p;
             w.seeds_in_lds = n_frames <= kLdsSeeds ? 1 : 0;
         }
-        if (n_frames > 1 || slot || adapt) {
+        if (n_frames > 1 || slot || adapt || moments) {
             if ((rc = ensure(c, planeBuf, (size_t)std::max(n_planes, 1) * plane_f4 * sizeof(float4)))) return rc;
             w.planes = (float4 *)planeBuf.p;
         }
@@ -1343,6 +1354,8 @@ int launch_wgwf(glrtx_ctx *c, const KernelArgs &a_in, const glrtx_params *p, con
         if (w.planes) ok = ok && planeBuf.bytes >= (size_t)std::max(n_planes, 1) * plane_f4 * sizeof(float4);
         if (adapt) ok = ok && !fed && !slot && w.planes && c->ad_selected && c->ad_tiles == (int)(total >> 6) && c->adList.bytes >= (total >> 6) * sizeof(int) &&
                       c->adMask.bytes >= (total >> 6) && c->adHalf.bytes >= (size_t)c->ad_pitch * c->owned_rows && c->ad_pitch == c->pitch_bytes;
+        if (moments) ok = ok && !fed && !slot && w.planes && c->mmM.p && c->mm_pitch == c->pitch_bytes && c->mm_rows == c->owned_rows &&
+                        c->mmM.bytes >= c->pitch_bytes * (size_t)c->owned_rows;
         if (fed) ok = ok && n_frames >= 1 && n_frames <= fed_cap && fed_cap <= kFeedMaxFrames && slot->feed_d.bytes >= sizeof(FeedDev) && w.feed_host != nullptr &&
                       slot->chunks[(n_frames - 1) / kFeedChunkFrames].p != nullptr && slot->chunk_bytes == frame_bytes;
         if (!ok) return fail(c, GLRTX_EDEVICE, "internal: wgwf launch shapes inconsistent (ids %zu, max id %zu, grid %d of %zu slots (%d per CU), block_paths %d, frames %d, fed %d)", ids, max_id,
@@ -1391,7 +1404,11 @@ int launch_wgwf(glrtx_ctx *c, const KernelArgs &a_in, const glrtx_params *p, con
         if (adapt)
             hipLaunchKernelGGL(accumulate_adaptive_kernel, g, dim3(256), 0, c->stream, a.accum, (float4 *)c->adHalf.p, a.pitch_f4, c->width, c->owned_rows,
                                (const float4 *)planeBuf.p, n_planes, (const unsigned char *)c->adMask.p, tiles8_x);
-        else if (fed && pres)
+        else if (moments) {
+            if (n_planes > 0)
+                hipLaunchKernelGGL(variance::accumulate_moments_kernel, g, dim3(256), 0, c->stream, a.accum, (float4 *)c->mmM.p, a.pitch_f4, c->width, c->owned_rows,
+                                   (const float4 *)planeBuf.p, n_planes);
+        } else if (fed && pres)
             hipLaunchKernelGGL(accumulate_present_feed_kernel, g, dim3(256), 0, c->stream, a.accum, a.pitch_f4, c->width, c->owned_rows, (const FeedDev *)slot->feed_d.p,
                                p->n_samples, (uchar4 *)P.dev.p, (size_t)c->width * (size_t)c->owned_rows, P.ring, slot0, P.inv_gamma, P.flip);
         else if (fed)
@@ -1429,6 +1446,7 @@ void denoise_release(glrtx_ctx *c) {
     c->rp_have = false;
     dev_free(c->ftG); dev_free(c->ftG_spare);
     c->mt_g_have = false;
+    for (DevBuf &v : c->dnV) dev_free(v);
 }
 
 int denoise_cfg_check(glrtx_ctx *c, const glrtx_denoise_cfg *cfg, const char *fn) {
@@ -1519,6 +1537,76 @@ int adapt_select(glrtx_ctx *c, const glrtx_adaptive *cfg) {
     hipLaunchKernelGGL(adaptive_compact_kernel, dim3(1), dim3(kAdaptCompactThreads), 0, c->stream, (const unsigned char *)c->adMask.p, n_tiles, (int *)c->adList.p,
                        (unsigned *)c->adCount.p);
     HIP_TRY(c, hipGetLastError());
+    return GLRTX_OK;
+}
+
+// ---- variance guidance (glrtx_track_moments, glrtx_render_moments, glrtx_denoise_variance)
+// The moments plane M at the accumulator's current shape, zeroed (on first use, at a clear and at a bind; the reprojections carry it into mmM_spare and swap).
+int moments_ensure(glrtx_ctx *c) {
+    const size_t bytes = c->pitch_bytes * (size_t)std::max(c->owned_rows, 1);
+    if (int rc = ensure(c, c->mmM, bytes)) return rc;
+    HIP_TRY(c, hipMemsetAsync(c->mmM.p, 0, bytes, c->stream));
+    c->mm_pitch = c->pitch_bytes; c->mm_rows = c->owned_rows;
+    return GLRTX_OK;
+}
+bool moments_have(const glrtx_ctx *c) { return c->mm_on && c->mmM.p && c->mm_pitch == c->pitch_bytes && c->mm_rows == c->owned_rows; }
+
+int denoise_var_cfg_check(glrtx_ctx *c, const glrtx_denoise_var_cfg *cfg, const char *fn) {
+    if (!cfg) return fail(c, GLRTX_EINVAL, "%s: NULL cfg", fn);
+    if (cfg->iterations < 1 || cfg->iterations > 6) return fail(c, GLRTX_EINVAL, "%s: iterations %d outside 1..6", fn, cfg->iterations);
+    const float sg[3] = {cfg->sigma_lum, cfg->sigma_normal, cfg->sigma_depth};
+    for (float v : sg)
+        if (!(v > 0.0f) || std::isinf(v)) return fail(c, GLRTX_EINVAL, "%s: sigma %g is not a positive finite number", fn, (double)v);
+    return GLRTX_OK;
+}
+
+// The variance pass and the variance-guided filter's passes on `stream`: accum and M (pitch_f4 each) + the two feature planes -> D, through the ping-pong images
+// p0 / p1 and the variance planes v[0] (V0), v[1], v[2] (all but accum and M packed rows of `width`).
+int denoise_var_passes(glrtx_ctx *c, hipStream_t stream, const float4 *accum, const float4 *moments, int pitch_f4, const float4 *guide, const float4 *albedo, float4 *p0,
+                       float4 *p1, float4 *D, float *const v[3], int width, int rows, const glrtx_denoise_var_cfg *cfg) {
+    const dim3 grid((unsigned)(((width + denoise::kTileDn - 1) / denoise::kTileDn) * ((rows + denoise::kTileDn - 1) / denoise::kTileDn)));
+    const int demod = cfg->demodulate ? 1 : 0;
+    variance::Args va;
+    va.accum = accum; va.moments = moments; va.guide = guide; va.albedo = albedo; va.v0 = v[0];
+    va.pitch_f4 = pitch_f4; va.width = width; va.rows = rows;
+    va.sigma_normal = cfg->sigma_normal; va.sigma_depth = cfg->sigma_depth; va.demodulate = demod;
+    hipLaunchKernelGGL(variance::variance_estimate, grid, dim3(256), 0, stream, va);
+    HIP_TRY(c, hipGetLastError());
+    hipLaunchKernelGGL(denoise::denoise_prep, grid, dim3(256), 0, stream, accum, pitch_f4, albedo, p0, width, rows, demod);
+    HIP_TRY(c, hipGetLastError());
+    float4 *img[2] = {p0, p1};
+    for (int it = 0; it < cfg->iterations; it++) {
+        const bool last = it == cfg->iterations - 1;
+        denoise::VarArgs a;
+        a.src = img[it & 1]; a.guide = guide; a.albedo = albedo; a.dst = last ? D : img[(it + 1) & 1];
+        a.vsrc = it == 0 ? v[0] : v[1 + ((it - 1) & 1)]; a.vdst = v[1 + (it & 1)];
+        a.width = width; a.rows = rows; a.spacing = 1 << it;
+        a.sigma_lum = cfg->sigma_lum; a.sigma_normal = cfg->sigma_normal; a.sigma_depth = cfg->sigma_depth;
+        a.demodulate = demod;
+        using Kernel = void (*)(const denoise::VarArgs);
+        const Kernel k = it == 0 ? (last ? (Kernel)denoise::denoise_atrous_var<1, true> : (Kernel)denoise::denoise_atrous_var<1, false>)
+                       : it == 1 ? (last ? (Kernel)denoise::denoise_atrous_var<2, true> : (Kernel)denoise::denoise_atrous_var<2, false>)
+                                 : (last ? (Kernel)denoise::denoise_atrous_var<0, true> : (Kernel)denoise::denoise_atrous_var<0, false>);
+        hipLaunchKernelGGL(k, grid, dim3(256), 0, stream, a);
+        HIP_TRY(c, hipGetLastError());
+    }
+    return GLRTX_OK;
+}
+
+// Everything glrtx_render_moments refuses, checked before anything changes: glrtx_render_adaptive's list, the volume and tracking being off.
+int moments_check(glrtx_ctx *c, const glrtx_params *p, const float *seeds_xy, int n_frames) {
+    const char *fn = "glrtx_render_moments";
+    if (!p) return fail(c, GLRTX_EINVAL, "%s: NULL params", fn);
+    if (!c->mm_on) return fail(c, GLRTX_EINVAL, "%s: moments are not tracked (glrtx_track_moments)", fn);
+    if (n_frames < 0 || (n_frames > 0 && !seeds_xy)) return fail(c, GLRTX_EINVAL, "%s: bad seeds/n_frames", fn);
+    if (!c->have_scene) return fail(c, GLRTX_EINVAL, "%s: no scene uploaded", fn);
+    if (!c->accum || c->width < 1) return fail(c, GLRTX_EINVAL, "%s: no accumulator (call glrtx_resize)", fn);
+    if (p->n_samples < 0 || p->max_depth < 0) return fail(c, GLRTX_EINVAL, "%s: negative n_samples/max_depth", fn);
+    if (c->pres.ring > 0) return fail(c, GLRTX_EINVAL, "%s: presentation is enabled (the present ring's passes do not fold moments)", fn);
+    if (c->ext_flags != 0) return fail(c, GLRTX_EINVAL, "%s: extensions or volume are on", fn);
+    if (c->n_spheres > 0) return fail(c, GLRTX_EINVAL, "%s: spheres are uploaded", fn);
+    if (c->variant != 2) return fail(c, GLRTX_EINVAL, "%s: variant %d (only the wavefront kernel, variant 2, writes sample planes)", fn, c->variant);
+    if (!wgwf_can_hold(p, false)) return fail(c, GLRTX_EINVAL, "%s: max_depth %d / n_samples %d beyond the wavefront kernel's path state", fn, p->max_depth, p->n_samples);
     return GLRTX_OK;
 }
 
@@ -1637,6 +1725,7 @@ void glrtx_destroy(glrtx_ctx *c) {
     dev_free(c->spheres); dev_free(c->sphereMat); dev_free(c->volDensity); dev_free(c->volTemp); dev_free(c->forks); dev_free(c->cnodes); dev_free(c->cranks); dev_free(c->nrms); dev_free(c->mats); dev_free(c->lights); dev_free(c->vine);
     dev_free(c->accum_own); dev_free(c->counter); dev_free(c->rgba8); dev_free(c->work);
     dev_free(c->adHalf); dev_free(c->adMask); dev_free(c->adList); dev_free(c->adCount);
+    dev_free(c->mmM); dev_free(c->mmM_spare);
     denoise_release(c);
     dev_free(c->mtPos); dev_free(c->mtNrm);
     dev_free(c->wfState); dev_free(c->wfQ); dev_free(c->wfSeeds); dev_free(c->wfPlanes);
@@ -2186,6 +2275,7 @@ int glrtx_resize(glrtx_ctx *c, int width, int height) {
                         width, height, rows, c->pitch_bytes, c->bound_rows);
     }
     denoise_release(c);  // (the feature planes and the filter's images have the old shape; the stream is idle)
+    dev_free(c->mmM); dev_free(c->mmM_spare);  // (so has the moments plane: allocated again on its next use)
     c->width = width; c->height = height;
     c->owned_rows = owned_rows_of(height, c->rank, c->world, c->stripe);
     c->st.width = width; c->st.height = height; c->st.owned_rows = c->owned_rows;
@@ -2212,6 +2302,7 @@ int glrtx_clear(glrtx_ctx *c) {
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipMemsetAsync(c->accum, 0, c->pitch_bytes * (size_t)c->owned_rows, c->stream));
     if (c->adHalf.p && (rc_ = adapt_half_ensure(c))) return rc_;  // (the half buffer follows the accumulator: zeroed, at the current size)
+    if (c->mmM.p && (rc_ = moments_ensure(c))) return rc_;        // (and so does the moments plane)
     c->pres.frame = 0;  // (images already produced keep their numbers)
     return GLRTX_OK;
 }
@@ -2235,6 +2326,7 @@ int glrtx_bind_accum(glrtx_ctx *c, void *device_ptr, size_t pitch_bytes, int cap
     c->bound_rows = capacity_rows;
     c->accum = (float4 *)device_ptr;
     c->pitch_bytes = pitch_bytes;
+    if (c->mmM.p) { if (int rc = moments_ensure(c)) return rc; }  // (another accumulator: the moments of the old one's samples say nothing about it)
     if (c->adHalf.p) return adapt_half_ensure(c);  // (another accumulator: the half buffer of the old one would be compared with unrelated samples)
     return GLRTX_OK;
 }
@@ -2592,6 +2684,114 @@ int glrtx_debug_denoise(const float *accum, const float *normal_depth, const flo
     return rc;
 }
 
+// ---- variance guidance
+int glrtx_track_moments(glrtx_ctx *c, int enable) {
+    if (!c) return GLRTX_EINVAL;
+    if (enable) { c->mm_on = true; return GLRTX_OK; }
+    if (!c->mm_on) return GLRTX_OK;
+    seal_feed(c);
+    if (int rc = glrtx_sync(c)) return rc;
+    dev_free(c->mmM); dev_free(c->mmM_spare);
+    c->mm_on = false;
+    return GLRTX_OK;
+}
+
+// glrtx_render_adaptive's launches without a selection: plain launches with sample planes on the context's stream, in helpings of what the frames-in-flight
+// budget allows, each folded by accumulate_moments_kernel into the accumulator and M.
+int glrtx_render_moments(glrtx_ctx *c, const glrtx_params *p, const float *seeds_xy, int n_frames) {
+    if (!c) return GLRTX_EINVAL;
+    if (int rc = moments_check(c, p, seeds_xy, n_frames)) return rc;
+    seal_feed(c);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (!moments_have(c))
+        if (int rc = moments_ensure(c)) return rc;
+    if (n_frames == 0 || c->owned_rows == 0) { c->st.launches += (uint64_t)n_frames; return GLRTX_OK; }
+    const int most = std::min(n_frames, frames_cap(c, p, 1));
+    const int n_launches = (n_frames + most - 1) / most;
+    const int chunk = (n_frames + n_launches - 1) / n_launches;
+    int rc = GLRTX_OK;
+    c->moments_launch = true;
+    for (int f0 = 0; f0 < n_frames && rc == GLRTX_OK; f0 += chunk) {
+        const int n = std::min(chunk, n_frames - f0);
+        glrtx_params q = *p;
+        q.seed[0] = seeds_xy[2 * f0]; q.seed[1] = seeds_xy[2 * f0 + 1];
+        c->frames_seeds = seeds_xy + 2 * (size_t)f0;
+        c->frames_n = n;
+        rc = render_one(c, &q);
+        c->frames_seeds = nullptr;
+        c->frames_n = 1;
+        if (rc == GLRTX_OK) c->st.launches += (uint64_t)(n - 1);
+    }
+    c->moments_launch = false;
+    seal_feed(c);  // (the next render call starts a launch of its own)
+    return rc;
+}
+
+int glrtx_read_moments(glrtx_ctx *c, float *dst, size_t dst_pitch_bytes) {
+    const char *fn = "glrtx_read_moments";
+    if (!c || !dst) return GLRTX_EINVAL;
+    if (!c->mm_on) return fail(c, GLRTX_EINVAL, "%s: moments are not tracked (glrtx_track_moments)", fn);
+    if (!c->accum || c->width < 1) return fail(c, GLRTX_EINVAL, "%s: no accumulator (call glrtx_resize)", fn);
+    const size_t row = (size_t)c->width * sizeof(float4);
+    if (dst_pitch_bytes < row) return fail(c, GLRTX_EINVAL, "%s: dst pitch too small", fn);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (!moments_have(c))
+        if (int rc = moments_ensure(c)) return rc;  // (first use: a plane of zeros)
+    if (int rc = glrtx_sync(c)) return rc;
+    if (c->owned_rows == 0) return GLRTX_OK;
+    HIP_TRY(c, hipMemcpy2D(dst, dst_pitch_bytes, c->mmM.p, c->mm_pitch, row, (size_t)c->owned_rows, hipMemcpyDeviceToHost));
+    return GLRTX_OK;
+}
+
+int glrtx_denoise_variance(glrtx_ctx *c, const glrtx_denoise_var_cfg *cfg) {
+    const char *fn = "glrtx_denoise_variance";
+    if (!c) return GLRTX_EINVAL;
+    if (int rc = denoise_var_cfg_check(c, cfg, fn)) return rc;
+    if (!c->accum || c->width < 1) return fail(c, GLRTX_EINVAL, "%s: no accumulator (call glrtx_resize)", fn);
+    if (!c->mm_on) return fail(c, GLRTX_EINVAL, "%s: moments are not tracked (glrtx_track_moments)", fn);
+    if (!moments_have(c)) return fail(c, GLRTX_EINVAL, "%s: no moments plane yet (call glrtx_render_moments first)", fn);
+    if (int rc = denoise_shape_check(c, fn, false)) return rc;
+    seal_feed(c);
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t px = (size_t)c->width * (size_t)std::max(c->owned_rows, 1);
+    int rc;
+    if ((rc = ensure(c, c->dnP[0], px * sizeof(float4))) || (rc = ensure(c, c->dnP[1], px * sizeof(float4))) || (rc = ensure(c, c->dnD, px * sizeof(float4)))) return rc;
+    for (DevBuf &v : c->dnV)
+        if ((rc = ensure(c, v, px * sizeof(float)))) return rc;
+    c->dn_have = true;
+    if (c->owned_rows == 0) return GLRTX_OK;
+    float *const v[3] = {(float *)c->dnV[0].p, (float *)c->dnV[1].p, (float *)c->dnV[2].p};
+    return denoise_var_passes(c, c->stream, c->accum, (const float4 *)c->mmM.p, (int)(c->pitch_bytes / sizeof(float4)), (const float4 *)c->ftN.p, (const float4 *)c->ftA.p,
+                              (float4 *)c->dnP[0].p, (float4 *)c->dnP[1].p, (float4 *)c->dnD.p, v, c->width, c->owned_rows, cfg);
+}
+
+int glrtx_debug_denoise_variance(const float *accum, const float *moments, const float *normal_depth, const float *albedo_id, int width, int rows,
+                                 const glrtx_denoise_var_cfg *cfg, float *out, float *v0_out) {
+    const char *fn = "glrtx_debug_denoise_variance";
+    if (width < 1 || rows < 1 || width > 65536 || rows > 65536) return fail(nullptr, GLRTX_EINVAL, "%s: bad size %dx%d", fn, width, rows);
+    if (!accum || !moments || !normal_depth || !albedo_id || !out) return fail(nullptr, GLRTX_EINVAL, "%s: NULL buffer", fn);
+    if (int rc = denoise_var_cfg_check(nullptr, cfg, fn)) return rc;
+    const size_t bytes = (size_t)width * rows * sizeof(float4), vbytes = (size_t)width * rows * sizeof(float);
+    void *d[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // accum, M, guide, albedo, p0, p1, D, V0, Va, Vb
+    const float *in[4] = {accum, moments, normal_depth, albedo_id};
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < 10 && e == hipSuccess; i++) e = hipMalloc(&d[i], i < 7 ? bytes : vbytes);
+    for (int i = 0; i < 4 && e == hipSuccess; i++) e = hipMemcpy(d[i], in[i], bytes, hipMemcpyHostToDevice);
+    int rc = GLRTX_OK;
+    if (e == hipSuccess) {
+        float *const v[3] = {(float *)d[7], (float *)d[8], (float *)d[9]};
+        rc = denoise_var_passes(nullptr, 0, (const float4 *)d[0], (const float4 *)d[1], width, (const float4 *)d[2], (const float4 *)d[3], (float4 *)d[4], (float4 *)d[5],
+                                (float4 *)d[6], v, width, rows, cfg);
+    }
+    if (e == hipSuccess && rc == GLRTX_OK) e = hipDeviceSynchronize();
+    if (e == hipSuccess && rc == GLRTX_OK) e = hipMemcpy(out, d[6], bytes, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && rc == GLRTX_OK && v0_out) e = hipMemcpy(v0_out, d[7], vbytes, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) rc = fail(nullptr, GLRTX_EDEVICE, "%s: %s", fn, hipGetErrorString(e));
+    for (void *q : d)
+        if (q) (void)hipFree(q);
+    return rc;
+}
+
 
 // ---- reprojection (glrtx_reproject)
 static int reproject_setup_check(glrtx_ctx *c, const char *fn, const float *c2w_prev, const float *s2c_prev, const glrtx_reproject_cfg *cfg, glrt_detail::ReprojectSetup &st) {
@@ -2616,8 +2816,10 @@ static hipError_t reproject_counts(const void *dev_counts, int *carried, int *hi
 }
 
 static int reproject_pass(glrtx_ctx *c, hipStream_t stream, const glrt_detail::ReprojectSetup &st, const float *c2w_cur, const float *s2c_cur, int stripe, const float4 *acc,
-                          const float4 *n0, const float4 *a0, const float4 *n1, const float4 *a1, float4 *out, int pitch_f4, int width, int rows, void *counts) {
+                          const float4 *n0, const float4 *a0, const float4 *n1, const float4 *a1, float4 *out, int pitch_f4, int width, int rows, void *counts,
+                          const float4 *mom = nullptr, float4 *mom_out = nullptr) {
     reproject::Args a{};
+    a.mom = mom; a.mom_out = mom_out;
     std::memcpy(a.cam.cam, c2w_cur, 16 * sizeof(float));
     std::memcpy(a.cam.cam + 16, s2c_cur, 16 * sizeof(float));
     a.cam.width = width; a.cam.height = rows;
@@ -2640,8 +2842,9 @@ static int reproject_pass(glrtx_ctx *c, hipStream_t stream, const glrt_detail::R
 // The motion-aware kernel (reproject_motion.hip.h) on `stream`, as reproject_pass runs the static one; prev_pos / prev_nrm: motion::Args'.
 static int reproject_motion_pass(glrtx_ctx *c, hipStream_t stream, const glrt_detail::ReprojectSetup &st, const float4 *acc, const float4 *n0, const float4 *a0,
                                  const float4 *g1, const float4 *a1, const float4 *prev_pos, const float4 *prev_nrm, int n_tri, float4 *out, int pitch_f4, int width,
-                                 int rows, void *counts) {
+                                 int rows, void *counts, const float4 *mom = nullptr, float4 *mom_out = nullptr) {
     motion::Args a{};
+    a.mom = mom; a.mom_out = mom_out;
     std::memcpy(a.W, st.W, sizeof a.W);
     std::memcpy(a.S, st.S, sizeof a.S);
     a.opx = st.o_prev[0]; a.opy = st.o_prev[1]; a.opz = st.o_prev[2];
@@ -2684,6 +2887,8 @@ static int reproject_call(glrtx_ctx *c, const glrtx_params *cur, const glrtx_rep
     const size_t acc_bytes = c->pitch_bytes * (size_t)std::max(c->owned_rows, 1);
     int rc;
     if ((rc = ensure(c, c->accum_spare, acc_bytes)) || (rc = ensure(c, c->rpCount, reproject::kCountBytes))) return rc;
+    const bool carry_m = moments_have(c);  // glrtx_track_moments is on and M exists: a second M is written by the same pass and swapped in as the accumulator is
+    if (carry_m && (rc = ensure(c, c->mmM_spare, acc_bytes))) return rc;
     if (motion && c->mt_geom == glrtx_ctx::kMtCurrent && (rc = motion_snapshot(c))) return rc;  // nothing moved since the planes: previous = current
     for (auto &sl : c->pipe)  // behind every launch that may still add to the accumulator or read the scene (refit_run's rule)
         if (sl.stream && sl.used) {
@@ -2706,15 +2911,17 @@ static int reproject_call(glrtx_ctx *c, const glrtx_params *cur, const glrtx_rep
     if (motion)
         rc = reproject_motion_pass(c, c->stream, st, c->accum, (const float4 *)c->ftN_spare.p, (const float4 *)c->ftA_spare.p, (const float4 *)c->ftG.p,
                                    (const float4 *)c->ftA.p, (const float4 *)c->mtPos.p, (const float4 *)c->mtNrm.p, c->n_tri, (float4 *)c->accum_spare.p, pitch_f4,
-                                   c->width, c->owned_rows, c->rpCount.p);
+                                   c->width, c->owned_rows, c->rpCount.p, carry_m ? (const float4 *)c->mmM.p : nullptr, carry_m ? (float4 *)c->mmM_spare.p : nullptr);
     else
         rc = reproject_pass(c, c->stream, st, cur->c2w, cur->s2c, c->stripe, c->accum, (const float4 *)c->ftN_spare.p, (const float4 *)c->ftA_spare.p,
-                            (const float4 *)c->ftN.p, (const float4 *)c->ftA.p, (float4 *)c->accum_spare.p, pitch_f4, c->width, c->owned_rows, c->rpCount.p);
+                            (const float4 *)c->ftN.p, (const float4 *)c->ftA.p, (float4 *)c->accum_spare.p, pitch_f4, c->width, c->owned_rows, c->rpCount.p,
+                            carry_m ? (const float4 *)c->mmM.p : nullptr, carry_m ? (float4 *)c->mmM_spare.p : nullptr);
     if (rc) return rc;
     std::swap(c->accum_own, c->accum_spare);  // the accumulator rendered into from here on (glrtx_accum_device_ptr changes)
     c->accum = (float4 *)c->accum_own.p;
     c->rp_have = true;
     if (c->adHalf.p && (rc = adapt_half_ensure(c))) return rc;  // H held every second sample of the OLD view's pixels: zeroed, every tile is active again
+    if (carry_m) std::swap(c->mmM, c->mmM_spare);  // M is CARRIED, not zeroed like H: a variance is a property of the surface point, and it came along with its mean
     return GLRTX_OK;
 }
 
@@ -2761,9 +2968,10 @@ int glrtx_reproject_last(glrtx_ctx *c, int *carried, int *hit_pixels) {
     return GLRTX_OK;
 }
 
-int glrtx_debug_reproject(const float *accum, const float *n0, const float *a0, const float *n1, const float *a1, const float *c2w_prev, const float *s2c_prev,
-                          const float *c2w_cur, const float *s2c_cur, int width, int rows, const glrtx_reproject_cfg *cfg, float *out, int *carried, int *hit_pixels) {
-    const char *fn = "glrtx_debug_reproject";
+}  // extern "C"
+static int debug_reproject_impl(const char *fn, const float *accum, const float *mom, const float *n0, const float *a0, const float *n1, const float *a1,
+                                const float *c2w_prev, const float *s2c_prev, const float *c2w_cur, const float *s2c_cur, int width, int rows,
+                                const glrtx_reproject_cfg *cfg, float *out, float *mom_out, int *carried, int *hit_pixels) {
     if (width < 1 || rows < 1 || width > 65536 || rows > 65536 || (size_t)width * (size_t)rows > ((size_t)1 << 31))
         return fail(nullptr, GLRTX_EINVAL, "%s: bad size %dx%d", fn, width, rows);
     if (!accum || !n0 || !a0 || !n1 || !a1 || !c2w_prev || !s2c_prev || !c2w_cur || !s2c_cur || !cfg || !out) return fail(nullptr, GLRTX_EINVAL, "%s: NULL argument", fn);
@@ -2771,27 +2979,42 @@ int glrtx_debug_reproject(const float *accum, const float *n0, const float *a0, 
     if (int rc = reproject_setup_check(nullptr, fn, c2w_prev, s2c_prev, cfg, st)) return rc;
     const size_t bytes = (size_t)width * rows * sizeof(float4);
     const float *src[5] = {accum, n0, a0, n1, a1};
-    void *d[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // accum, N0, A0, N1, A1, out, counts
+    void *d[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // accum, N0, A0, N1, A1, out, counts, M, M out
     hipError_t e = hipSuccess;
-    for (int i = 0; i < 7 && e == hipSuccess; i++) e = hipMalloc(&d[i], i == 6 ? reproject::kCountBytes : bytes);
+    for (int i = 0; i < (mom ? 9 : 7) && e == hipSuccess; i++) e = hipMalloc(&d[i], i == 6 ? reproject::kCountBytes : bytes);
     for (int i = 0; i < 5 && e == hipSuccess; i++) e = hipMemcpy(d[i], src[i], bytes, hipMemcpyHostToDevice);
+    if (mom && e == hipSuccess) e = hipMemcpy(d[7], mom, bytes, hipMemcpyHostToDevice);
     int rc = GLRTX_OK;
     if (e == hipSuccess)
         rc = reproject_pass(nullptr, 0, st, c2w_cur, s2c_cur, 16, (const float4 *)d[0], (const float4 *)d[1], (const float4 *)d[2], (const float4 *)d[3], (const float4 *)d[4],
-                            (float4 *)d[5], width, width, rows, d[6]);
+                            (float4 *)d[5], width, width, rows, d[6], (const float4 *)d[7], (float4 *)d[8]);
     if (e == hipSuccess && rc == GLRTX_OK) e = hipDeviceSynchronize();
     if (e == hipSuccess && rc == GLRTX_OK) e = hipMemcpy(out, d[5], bytes, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && rc == GLRTX_OK && mom) e = hipMemcpy(mom_out, d[8], bytes, hipMemcpyDeviceToHost);
     if (e == hipSuccess && rc == GLRTX_OK) e = reproject_counts(d[6], carried, hit_pixels);
     if (e != hipSuccess) rc = fail(nullptr, GLRTX_EDEVICE, "%s: %s", fn, hipGetErrorString(e));
     for (void *q : d)
         if (q) (void)hipFree(q);
     return rc;
 }
+extern "C" {
+int glrtx_debug_reproject(const float *accum, const float *n0, const float *a0, const float *n1, const float *a1, const float *c2w_prev, const float *s2c_prev,
+                          const float *c2w_cur, const float *s2c_cur, int width, int rows, const glrtx_reproject_cfg *cfg, float *out, int *carried, int *hit_pixels) {
+    return debug_reproject_impl("glrtx_debug_reproject", accum, nullptr, n0, a0, n1, a1, c2w_prev, s2c_prev, c2w_cur, s2c_cur, width, rows, cfg, out, nullptr, carried,
+                                hit_pixels);
+}
+int glrtx_debug_reproject_moments(const float *accum, const float *moments, const float *n0, const float *a0, const float *n1, const float *a1, const float *c2w_prev,
+                                  const float *s2c_prev, const float *c2w_cur, const float *s2c_cur, int width, int rows, const glrtx_reproject_cfg *cfg, float *out,
+                                  float *moments_out, int *carried, int *hit_pixels) {
+    if (!moments || !moments_out) return fail(nullptr, GLRTX_EINVAL, "glrtx_debug_reproject_moments: NULL moments");
+    return debug_reproject_impl("glrtx_debug_reproject_moments", accum, moments, n0, a0, n1, a1, c2w_prev, s2c_prev, c2w_cur, s2c_cur, width, rows, cfg, out,
+                                moments_out, carried, hit_pixels);
+}
 
-int glrtx_debug_reproject_motion(const float *accum, const float *n0, const float *a0, const float *g1, const float *a1, const float *vert_prev, size_t n_vert,
-                                 const float *tri, size_t n_tri, const float *c2w_prev, const float *s2c_prev, int width, int rows, const glrtx_reproject_cfg *cfg,
-                                 float *out, int *carried, int *hit_pixels) {
-    const char *fn = "glrtx_debug_reproject_motion";
+}  // extern "C"
+static int debug_reproject_motion_impl(const char *fn, const float *accum, const float *mom, const float *n0, const float *a0, const float *g1, const float *a1,
+                                       const float *vert_prev, size_t n_vert, const float *tri, size_t n_tri, const float *c2w_prev, const float *s2c_prev, int width,
+                                       int rows, const glrtx_reproject_cfg *cfg, float *out, float *mom_out, int *carried, int *hit_pixels) {
     if (width < 1 || rows < 1 || width > 65536 || rows > 65536 || (size_t)width * (size_t)rows > ((size_t)1 << 31))
         return fail(nullptr, GLRTX_EINVAL, "%s: bad size %dx%d", fn, width, rows);
     if (!accum || !n0 || !a0 || !g1 || !a1 || !c2w_prev || !s2c_prev || !cfg || !out) return fail(nullptr, GLRTX_EINVAL, "%s: NULL argument", fn);
@@ -2814,23 +3037,40 @@ int glrtx_debug_reproject_motion(const float *accum, const float *n0, const floa
     }
     const size_t bytes = (size_t)width * rows * sizeof(float4), gbytes = pos.size() * sizeof(float4);
     const float *src[5] = {accum, n0, a0, g1, a1};
-    void *d[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // accum, N0, A0, G1, A1, out, counts, positions, normals
+    void *d[11] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // accum, N0, A0, G1, A1, out, counts, positions, normals, M, M out
     hipError_t e = hipSuccess;
-    for (int i = 0; i < 9 && e == hipSuccess; i++) e = hipMalloc(&d[i], i == 6 ? reproject::kCountBytes : i > 6 ? gbytes : bytes);
+    for (int i = 0; i < (mom ? 11 : 9) && e == hipSuccess; i++) e = hipMalloc(&d[i], i == 6 ? reproject::kCountBytes : (i == 7 || i == 8) ? gbytes : bytes);
+    if (mom && e == hipSuccess) e = hipMemcpy(d[9], mom, bytes, hipMemcpyHostToDevice);
     for (int i = 0; i < 5 && e == hipSuccess; i++) e = hipMemcpy(d[i], src[i], bytes, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(d[7], pos.data(), gbytes, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(d[8], nrm.data(), gbytes, hipMemcpyHostToDevice);
     int rc = GLRTX_OK;
     if (e == hipSuccess)
         rc = reproject_motion_pass(nullptr, 0, st, (const float4 *)d[0], (const float4 *)d[1], (const float4 *)d[2], (const float4 *)d[3], (const float4 *)d[4],
-                                   (const float4 *)d[7], (const float4 *)d[8], (int)n_tri, (float4 *)d[5], width, width, rows, d[6]);
+                                   (const float4 *)d[7], (const float4 *)d[8], (int)n_tri, (float4 *)d[5], width, width, rows, d[6], (const float4 *)d[9],
+                                   (float4 *)d[10]);
     if (e == hipSuccess && rc == GLRTX_OK) e = hipDeviceSynchronize();
     if (e == hipSuccess && rc == GLRTX_OK) e = hipMemcpy(out, d[5], bytes, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && rc == GLRTX_OK && mom) e = hipMemcpy(mom_out, d[10], bytes, hipMemcpyDeviceToHost);
     if (e == hipSuccess && rc == GLRTX_OK) e = reproject_counts(d[6], carried, hit_pixels);
     if (e != hipSuccess) rc = fail(nullptr, GLRTX_EDEVICE, "%s: %s", fn, hipGetErrorString(e));
     for (void *q : d)
         if (q) (void)hipFree(q);
     return rc;
+}
+extern "C" {
+int glrtx_debug_reproject_motion(const float *accum, const float *n0, const float *a0, const float *g1, const float *a1, const float *vert_prev, size_t n_vert,
+                                 const float *tri, size_t n_tri, const float *c2w_prev, const float *s2c_prev, int width, int rows, const glrtx_reproject_cfg *cfg,
+                                 float *out, int *carried, int *hit_pixels) {
+    return debug_reproject_motion_impl("glrtx_debug_reproject_motion", accum, nullptr, n0, a0, g1, a1, vert_prev, n_vert, tri, n_tri, c2w_prev, s2c_prev, width, rows,
+                                       cfg, out, nullptr, carried, hit_pixels);
+}
+int glrtx_debug_reproject_motion_moments(const float *accum, const float *moments, const float *n0, const float *a0, const float *g1, const float *a1,
+                                         const float *vert_prev, size_t n_vert, const float *tri, size_t n_tri, const float *c2w_prev, const float *s2c_prev,
+                                         int width, int rows, const glrtx_reproject_cfg *cfg, float *out, float *moments_out, int *carried, int *hit_pixels) {
+    if (!moments || !moments_out) return fail(nullptr, GLRTX_EINVAL, "glrtx_debug_reproject_motion_moments: NULL moments");
+    return debug_reproject_motion_impl("glrtx_debug_reproject_motion_moments", accum, moments, n0, a0, g1, a1, vert_prev, n_vert, tri, n_tri, c2w_prev, s2c_prev,
+                                       width, rows, cfg, out, moments_out, carried, hit_pixels);
 }
 
 // glrtx_render behind the presentation check (glrtx_render_frames checks for all its frames at once)
@@ -2841,7 +3081,7 @@ static int render_one(glrtx_ctx *c, const glrtx_params *p) {
     if ((c->ext_flags & GLRTX_EXT_VOLUME) && !c->have_volume) return fail(c, GLRTX_EINVAL, "glrtx_render: GLRTX_EXT_VOLUME is set and no volume is uploaded (glrtx_upload_volume)");
     HIP_TRY(c, hipSetDevice(c->device));
     const bool wavefront = wgwf_routes(c, p);
-    if (c->owned_rows > 0 && wavefront && c->frames_n == 1 && !c->adapt_launch && feed_append(c, p, p->seed, 1) == 1) {  // a launch of the same camera that is still open takes the frame itself
+    if (c->owned_rows > 0 && wavefront && c->frames_n == 1 && !c->adapt_launch && !c->moments_launch && feed_append(c, p, p->seed, 1) == 1) {  // a launch of the same camera that is still open takes the frame itself
         c->last_was_render = true; c->last_p = *p;
         return presenting(c) ? present_issue(c, 1) : GLRTX_OK;
     }

@@ -35,18 +35,38 @@ struct Args {
     int pitch_f4, width, rows, tiles_x, n_tiles;
     float max_history, depth_tol, normal_tol;  // (max_history as a float; the tolerances with denormals flushed)
     unsigned long long *counts;  // kCountSlots words kCountStride apart: carried in the low half, hit pixels in the high half
+    const float4 *mom;        // the old view's moments plane M (pitch_f4 per row), or null: no moments are carried
+    float4 *mom_out;          // the new view's (pitch_f4 per row)
 };
 
 DEV float canon(float x) { return x != x ? __uint_as_float(0x7FC00000u) : x; }
 DEV bool tiny(float x) { return (__float_as_uint(x) & 0x7F800000u) == 0u; }  // a zero or a denormal
 DEV bool pos_finite(float x) { return (__float_as_uint(x) - 0x00800000u) < 0x7F000000u; }  // sign clear, exponent neither 0 nor 255
 
+// The moments plane through the same taps (include/glrtx.h "Variance guidance": "Carrying M"), shared with reproject_motion_kernel as centre_ray is shared with the
+// feature pass.  A tap that counts for the accumulator counts for M if M.w is neither a zero nor a denormal.
+struct MomSum { float sm, smc, s1, s2; };
+DEV void moments_tap(MomSum &s, float w, float4 M) {
+    if (tiny(M.w)) return;
+    s.sm = s.sm + w;
+    s.smc = s.smc + w * M.w;
+    s.s1 = s.s1 + w * (M.x / M.w);
+    s.s2 = s.s2 + w * (M.y / M.w);
+}
+DEV float4 moments_out(const MomSum &s, float max_history) {
+    if (!(s.sm > kMinWeight)) return make_float4(0.f, 0.f, 0.f, 0.f);
+    const float r = __builtin_rintf(s.smc / s.sm);
+    const float nm = r > max_history ? max_history : r;
+    if (!(nm >= 1.0f)) return make_float4(0.f, 0.f, 0.f, 0.f);
+    return make_float4(canon((s.s1 / s.sm) * nm), canon((s.s2 / s.sm) * nm), 0.f, nm);
+}
+
 __global__ __launch_bounds__(256) void reproject_kernel(const Args a) {
     const int tile = blockIdx.x * 4 + (threadIdx.x >> 6), k = threadIdx.x & 63;
     const int x = (tile % a.tiles_x) * 8 + (k & 7), y = (tile / a.tiles_x) * 8 + (k >> 3);
     const bool in = tile < a.n_tiles && x < a.width && y < a.rows;
     bool hit = false, carried = false;
-    float4 o4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 o4 = make_float4(0.f, 0.f, 0.f, 0.f), m4 = make_float4(0.f, 0.f, 0.f, 0.f);
     if (in) {
         const size_t p = (size_t)y * a.width + x;
         const float4 N1 = ld_stream(a.n1 + p), A1 = ld_stream(a.a1 + p);
@@ -78,6 +98,7 @@ __global__ __launch_bounds__(256) void reproject_kernel(const Args a) {
                 const float fx = u - fx0, fy = v - fy0;
                 const float wx[2] = {1.0f - fx, fx}, wy[2] = {1.0f - fy, fy};
                 float sw = 0.f, sc = 0.f, sr = 0.f, sg = 0.f, sb = 0.f;
+                MomSum ms = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                 for (int j = 0; j < 2; j++) {
 #pragma unroll
@@ -96,6 +117,7 @@ __global__ __launch_bounds__(256) void reproject_kernel(const Args a) {
                         sw = sw + w;
                         sc = sc + w * C.w;
                         sr = sr + w * (C.x / C.w); sg = sg + w * (C.y / C.w); sb = sb + w * (C.z / C.w);
+                        if (a.mom) moments_tap(ms, w, a.mom[(size_t)ty * a.pitch_f4 + tx]);
                     }
                 }
                 if (sw > kMinWeight) {
@@ -104,11 +126,13 @@ __global__ __launch_bounds__(256) void reproject_kernel(const Args a) {
                     if (n >= 1.0f) {
                         o4 = make_float4(canon((sr / sw) * n), canon((sg / sw) * n), canon((sb / sw) * n), n);
                         carried = true;
+                        if (a.mom) m4 = moments_out(ms, a.max_history);
                     }
                 }
             }
         }
         a.out[(size_t)y * a.pitch_f4 + x] = o4;
+        if (a.mom_out) a.mom_out[(size_t)y * a.pitch_f4 + x] = m4;
     }
     const unsigned long long nc = __popcll(__ballot(carried)), nh = __popcll(__ballot(hit));
     if (k == 0 && (nc | nh) != 0ull) atomicAdd(a.counts + (size_t)(blockIdx.x % kCountSlots) * kCountStride, nc | (nh << 32));

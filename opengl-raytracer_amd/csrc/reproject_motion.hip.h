@@ -32,6 +32,8 @@ struct Args {
     int pitch_f4, width, rows, tiles_x, n_tiles;
     float max_history, depth_tol, normal_tol;
     unsigned long long *counts;  // reproject::kCountSlots words
+    const float4 *mom;        // the old view's moments plane M (pitch_f4 per row), or null; mom_out: the new view's (reproject::Args')
+    float4 *mom_out;
 };
 
 __global__ __launch_bounds__(256) void reproject_motion_kernel(const Args a) {
@@ -42,7 +44,7 @@ __global__ __launch_bounds__(256) void reproject_motion_kernel(const Args a) {
     const int x = (tile % a.tiles_x) * 8 + (k & 7), y = (tile / a.tiles_x) * 8 + (k >> 3);
     const bool in = tile < a.n_tiles && x < a.width && y < a.rows;
     bool hit = false, carried = false;
-    float4 o4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 o4 = make_float4(0.f, 0.f, 0.f, 0.f), m4 = make_float4(0.f, 0.f, 0.f, 0.f);
     if (in) {
         const size_t p = (size_t)y * a.width + x;
         const float4 G1 = ld_stream(a.g1 + p), A1 = ld_stream(a.a1 + p);
@@ -79,6 +81,7 @@ __global__ __launch_bounds__(256) void reproject_motion_kernel(const Args a) {
                 const float fx = ui - fx0, fy = vi - fy0;
                 const float wx[2] = {1.0f - fx, fx}, wy[2] = {1.0f - fy, fy};
                 float sw = 0.f, sc = 0.f, sr = 0.f, sg = 0.f, sb = 0.f;
+                reproject::MomSum ms = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                 for (int j = 0; j < 2; j++) {
 #pragma unroll
@@ -97,6 +100,7 @@ __global__ __launch_bounds__(256) void reproject_motion_kernel(const Args a) {
                         sw = sw + w;
                         sc = sc + w * C.w;
                         sr = sr + w * (C.x / C.w); sg = sg + w * (C.y / C.w); sb = sb + w * (C.z / C.w);
+                        if (a.mom) reproject::moments_tap(ms, w, a.mom[(size_t)ty * a.pitch_f4 + tx]);
                     }
                 }
                 if (sw > reproject::kMinWeight) {
@@ -105,11 +109,13 @@ __global__ __launch_bounds__(256) void reproject_motion_kernel(const Args a) {
                     if (n >= 1.0f) {
                         o4 = make_float4(canon((sr / sw) * n), canon((sg / sw) * n), canon((sb / sw) * n), n);
                         carried = true;
+                        if (a.mom) m4 = reproject::moments_out(ms, a.max_history);
                     }
                 }
             }
         }
         a.out[(size_t)y * a.pitch_f4 + x] = o4;
+        if (a.mom_out) a.mom_out[(size_t)y * a.pitch_f4 + x] = m4;
     }
     const unsigned long long nc = __popcll(__ballot(carried)), nh = __popcll(__ballot(hit));
     if (k == 0 && (nc | nh) != 0ull)

@@ -1,0 +1,129 @@
+// variance.hip.h -- the moments fold and the variance pass of the variance-guided denoiser (glrtx_render_moments, glrtx_denoise_variance, include/glrtx.h
+// "Variance guidance"; the variance estimation step of SVGF, Schied et al. 2017).  The filter itself is denoise_atrous_var in denoise.hip.h.
+//
+// No reference counterpart.  The arithmetic is the header's text: host/variance.cpp and tests/variance_math.py state it again, and all three agree bit for bit
+// under denoise.hip.h's rules (one correctly rounded fp32 operation at a time in the order written, -ffp-contract=off; denormals flushed; a stored NaN is 0x7FC00000).
+//
+//   accumulate_moments_kernel  accumulate_planes_kernel with a second read-modify-write: every sample plane is added to the accumulator (the same chain of
+//       additions, so the accumulator is glrtx_render_frames') and its luminance and squared luminance to the moments plane M.  Bandwidth-bound like its twin.
+//   variance_estimate  the filter's shape: a workgroup owns a 16x16 tile, a wave an 8x8 sub-tile in tile order; tile + a 3-pixel halo (22^2 pixels) is staged in
+//       LDS as two float4 per pixel -- {mu1, mu2, id, M.w} and the feature plane's {n, t}, 15.1 KiB -- from four 16-byte loads per pixel (accumulator, M, A, N).
+//       A dead or outside pixel is staged with the reserved id, so one compare per tap applies all three exclusions.  A pixel with M.w >= 4 needs no tap at all.
+#pragma once
+#include "denoise.hip.h"
+
+namespace glrtx {
+namespace variance {
+
+using denoise::albedo_of;
+using denoise::canon;
+using denoise::kNoPixel;
+using denoise::kTileDn;
+using denoise::tiny;
+
+DEV float lum(float r, float g, float b) { return (0.2126f * r + 0.7152f * g) + 0.0722f * b; }
+DEV float max0(float x) { return x > 0.0f ? x : 0.0f; }
+
+__global__ __launch_bounds__(256) void accumulate_moments_kernel(float4 *accum, float4 *moments, int pitch_f4, int width, int rows, const float4 *planes, int n_planes) {
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= width || y >= rows) return;
+    const size_t at = (size_t)y * pitch_f4 + x, plane = (size_t)rows * pitch_f4;
+    float4 acc = accum[at], m = moments[at];
+    for (int k = 0; k < n_planes; k++) {
+        const float4 v = planes[(size_t)k * plane + at];
+        const float l = lum(v.x, v.y, v.z);
+        m.x = m.x + l; m.y = m.y + l * l; m.w = m.w + 1.0f;
+        acc.x = acc.x + v.x; acc.y = acc.y + v.y; acc.z = acc.z + v.z;
+        acc.w = acc.w + 1.0f;
+    }
+    accum[at] = acc;
+    moments[at] = m;
+}
+
+struct Args {
+    const float4 *accum;    // pitch_f4 per row
+    const float4 *moments;  // pitch_f4 per row
+    const float4 *guide;    // {n, t}, packed rows of `width`
+    const float4 *albedo;   // {rgb, id}, packed
+    float *v0;              // packed
+    int pitch_f4, width, rows;
+    float sigma_normal, sigma_depth;
+    int demodulate;
+};
+
+constexpr int kHaloVar = 3, kSideVar = kTileDn + 2 * kHaloVar;
+
+__global__ __launch_bounds__(256) void variance_estimate(const Args a) {
+    __shared__ float4 sM[kSideVar * kSideVar], sG[kSideVar * kSideVar];
+    const int tiles_x = (a.width + kTileDn - 1) / kTileDn;
+    const int tile = blockIdx.x, wv = threadIdx.x >> 6, k = threadIdx.x & 63;
+    const int x0 = (tile % tiles_x) * kTileDn, y0 = (tile / tiles_x) * kTileDn;
+    const int tx = (wv & 1) * 8 + (k & 7), ty = (wv >> 1) * 8 + (k >> 3);
+    const int x = x0 + tx, y = y0 + ty;
+    for (int i = threadIdx.x; i < kSideVar * kSideVar; i += 256) {
+        const int sy = i / kSideVar, sx = i - sy * kSideVar;
+        const int gx = x0 - kHaloVar + sx, gy = y0 - kHaloVar + sy;
+        float4 m = make_float4(0.f, 0.f, __int_as_float(kNoPixel), 0.f), g = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (gx >= 0 && gx < a.width && gy >= 0 && gy < a.rows) {
+            const size_t qa = (size_t)gy * a.pitch_f4 + gx, q = (size_t)gy * a.width + gx;
+            const float4 s = a.accum[qa], mo = a.moments[qa], al = a.albedo[q];
+            g = a.guide[q];
+            if (!tiny(s.w) && __float_as_int(al.w) != kNoPixel) {
+                m.z = al.w; m.w = mo.w;
+                if (!tiny(mo.w)) { m.x = mo.x / mo.w; m.y = mo.y / mo.w; }
+                else {
+                    const float l = lum(s.x / s.w, s.y / s.w, s.z / s.w);
+                    m.x = l; m.y = l * l;
+                }
+            }
+        }
+        sM[i] = m; sG[i] = g;
+    }
+    __syncthreads();
+    if (x >= a.width || y >= a.rows) return;
+    const int c = (ty + kHaloVar) * kSideVar + tx + kHaloVar;
+    const float4 mp = sM[c];
+    const int idp = __float_as_int(mp.z);
+    float v = 0.0f;
+    if (idp != kNoPixel) {
+        if (mp.w >= 4.0f) v = max0(mp.y - mp.x * mp.x) / mp.w;
+        else {
+            const float4 gp = sG[c];
+            const float tden = gp.w > 1.0e-6f ? gp.w : 1.0e-6f;
+            float sw = 0.0f, s1 = 0.0f, s2 = 0.0f;
+#pragma unroll
+            for (int dy = -3; dy <= 3; dy++) {
+#pragma unroll
+                for (int dx = -3; dx <= 3; dx++) {
+                    const int i = c + dy * kSideVar + dx;
+                    const float4 mq = sM[i];
+                    if (__float_as_int(mq.z) == idp) {
+                        const float4 gq = sG[i];
+                        const float nx = gq.x - gp.x, ny = gq.y - gp.y, nz = gq.z - gp.z;
+                        const float dn = (nx * nx + ny * ny) + nz * nz;
+                        const float rt = (gq.w - gp.w) / tden;
+                        const float dd = (rt * rt) / a.sigma_depth;
+                        const float w = lp_exp(-(dn / a.sigma_normal + (dd < 80.0f ? dd : 80.0f)));
+                        sw = sw + w;
+                        s1 = s1 + w * mq.x;
+                        s2 = s2 + w * mq.y;
+                    }
+                }
+            }
+            const float den = sw > 1.0e-20f ? sw : 1.0e-20f;
+            const float S1 = s1 / den, S2 = s2 / den;
+            v = max0(S2 - S1 * S1);
+        }
+        if (a.demodulate) {
+            const float4 al = a.albedo[(size_t)y * a.width + x];
+            const float la = lum(albedo_of(al.x), albedo_of(al.y), albedo_of(al.z));
+            v = v / (la * la);
+        }
+        v = canon(v);
+    }
+    a.v0[(size_t)y * a.width + x] = v;
+}
+
+}  // namespace variance
+}  // namespace glrtx

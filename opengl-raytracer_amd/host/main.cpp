@@ -14,7 +14,7 @@
 using namespace glrt;
 
 static void usage(const char *exe) {
-    std::printf("usage: %s -i scene.json [-s N] [--max-depth D] [--spp N] [--frames F] [--frames-in-flight B] [--bvh sah|sah-reinsert|sah-gpu|lbvh|sah-levels-cpu|lbvh-cpu|reference] [--order-by-hits] [--out file.png] [--save-every-frame] [--device G | --gpus N | --devices a,b,..] [--extensions] [--whitted] [--enable-volume] [--volume-wavefront] [--adaptive THRESHOLD [--min-spp N]] [--denoise [--denoise-iters N]]\n"
+    std::printf("usage: %s -i scene.json [-s N] [--max-depth D] [--spp N] [--frames F] [--frames-in-flight B] [--bvh sah|sah-reinsert|sah-gpu|lbvh|sah-levels-cpu|lbvh-cpu|reference] [--order-by-hits] [--out file.png] [--save-every-frame] [--device G | --gpus N | --devices a,b,..] [--extensions] [--whitted] [--enable-volume] [--volume-wavefront] [--adaptive THRESHOLD [--min-spp N]] [--denoise | --denoise-variance [--denoise-iters N]]\n"
                 "  -i, --input             scene description (JSON; schema: SURVEY.md Appendix C)            [required]\n"
                 "  -s, --sample-per-cycle  accepted for compatibility; like the reference (main.cpp:13) it is not read\n"
                 "      --max-depth D       u_maxDepth (default 16, the reference shader's default)\n"
@@ -40,7 +40,10 @@ static void usage(const char *exe) {
                 "      --min-spp N         with --adaptive: samples every pixel of a tile needs before the tile may retire (default 2, at least 2)\n"
                 "      --denoise           write the denoised image: feature planes once before the first frame, then the edge-avoiding a-trous filter over the\n"
                 "                          accumulated mean (one device; not with --save-every-frame).  Without it the output is what it always was\n"
-                "      --denoise-iters N   with --denoise: filter iterations, 1..6 (default 5)\n", exe);
+                "      --denoise-variance  write the variance-guided image instead: the frames are rendered with glrtx_render_moments in bursts of --frames-in-flight\n"
+                "                          (at most 1024) frames, then SVGF's filter runs over the mean (one device; not with --denoise, --adaptive,\n"
+                "                          --save-every-frame, extension or volume scenes)\n"
+                "      --denoise-iters N   with --denoise or --denoise-variance: filter iterations, 1..6 (default 5)\n", exe);
 }
 
 int main(int argc, char **argv) {
@@ -49,7 +52,7 @@ int main(int argc, char **argv) {
     bool every_frame = false, extensions = false, whitted = false, order_by_hits = false, volume = false, adaptive = false, min_spp_given = false, volume_wavefront = false;
     float adapt_threshold = 0.0f;
     int min_spp = 2;
-    bool denoise = false;
+    bool denoise = false, denoise_variance = false;
     int denoise_iters = 0;
     std::vector<int> devices;
     std::string bvh;
@@ -77,6 +80,7 @@ int main(int argc, char **argv) {
         else if (a == "--adaptive") { adaptive = true; adapt_threshold = (float)std::atof(next("--adaptive")); }
         else if (a == "--min-spp") { min_spp = std::atoi(next("--min-spp")); min_spp_given = true; }
         else if (a == "--denoise") denoise = true;
+        else if (a == "--denoise-variance") denoise_variance = true;
         else if (a == "--denoise-iters") denoise_iters = std::atoi(next("--denoise-iters"));
         else if (a == "--gpus") { const int n = std::atoi(next("--gpus")); devices.clear(); for (int k = 0; k < n; k++) devices.push_back(k); }
         else if (a == "--devices") {
@@ -89,8 +93,19 @@ int main(int argc, char **argv) {
     if (min_spp_given && !adaptive) { std::fprintf(stderr, "--min-spp needs --adaptive\n"); return 1; }
     if (adaptive && (every_frame || min_spp < 2)) { std::fprintf(stderr, "--adaptive: not with --save-every-frame, and --min-spp must be at least 2\n"); return 1; }
 
-    if (denoise_iters != 0 && (!denoise || denoise_iters < 1 || denoise_iters > 6)) { std::fprintf(stderr, "--denoise-iters needs --denoise and a value in 1..6\n"); return 1; }
+    if (denoise_iters != 0 && ((!denoise && !denoise_variance) || denoise_iters < 1 || denoise_iters > 6)) {
+        std::fprintf(stderr, "--denoise-iters needs --denoise or --denoise-variance and a value in 1..6\n");
+        return 1;
+    }
     if (denoise && (every_frame || devices.size() > 1)) { std::fprintf(stderr, "--denoise: one device, and not with --save-every-frame\n"); return 1; }
+    if (denoise_variance && (denoise || adaptive || every_frame || devices.size() > 1)) {
+        std::fprintf(stderr, "--denoise-variance: one device, and not with --denoise, --adaptive or --save-every-frame\n");
+        return 1;
+    }
+    if (denoise_variance && in_flight > 1024) {  // (a burst is one glrtx_render_moments call: as many frames as one launch's seed table takes)
+        std::fprintf(stderr, "--denoise-variance: --frames-in-flight %d is above the 1024 frames one glrtx_render_moments burst takes\n", in_flight);
+        return 1;
+    }
 
     auto window = std::make_unique<Window>();
     if (devices.empty()) window->setDevice(device);
@@ -104,6 +119,7 @@ int main(int argc, char **argv) {
     if (adaptive) window->setAdaptive(adapt_threshold, min_spp);
     window->setVolumeWavefront(volume_wavefront);
     if (denoise) window->setDenoise(denoise_iters);
+    if (denoise_variance) window->setDenoiseVariance(denoise_iters);
 
     auto scene = std::make_shared<Scene>();
     if (!bvh.empty()) scene->setBvhBuilder(bvh);

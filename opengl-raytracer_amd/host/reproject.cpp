@@ -10,6 +10,7 @@
 
 #include "centre_ray.h"
 #include "glrt_host.h"
+#include "reproject_moments.h"
 #include "reproject_setup.h"
 
 namespace {
@@ -33,9 +34,10 @@ constexpr float kMinWeight = 1.0e-6f;
 
 }  // namespace
 
-int glrt_reproject(const float *accum, const float *n0, const float *a0, const float *n1, const float *a1, const float *c2w_prev, const float *s2c_prev,
-                   const float *c2w_cur, const float *s2c_cur, int width, int rows, int max_history, float depth_tolerance, float normal_tolerance, float *out,
-                   int *carried_out, int *hit_pixels_out) {
+// glrt_reproject, and with mom / mom_out glrt_reproject_moments: the same pass, the moments riding the same taps.
+static int reproject_impl(const float *accum, const float *mom, const float *n0, const float *a0, const float *n1, const float *a1, const float *c2w_prev,
+                          const float *s2c_prev, const float *c2w_cur, const float *s2c_cur, int width, int rows, int max_history, float depth_tolerance,
+                          float normal_tolerance, float *out, float *mom_out, int *carried_out, int *hit_pixels_out) {
     if (!accum || !n0 || !a0 || !n1 || !a1 || !c2w_prev || !s2c_prev || !c2w_cur || !s2c_cur || !out) return GLRT_HOST_EINVAL;
     if (width < 1 || rows < 1 || width > 65536 || rows > 65536) return GLRT_HOST_EINVAL;
     glrt_detail::ReprojectSetup st;
@@ -49,6 +51,7 @@ int glrt_reproject(const float *accum, const float *n0, const float *a0, const f
             const size_t p = (size_t)y * width + x;
             float *o = out + 4 * p;
             o[0] = o[1] = o[2] = o[3] = 0.0f;
+            if (mom_out) { float *mo = mom_out + 4 * p; mo[0] = mo[1] = mo[2] = mo[3] = 0.0f; }
             const float *N1 = n1 + 4 * p;
             int32_t id;
             std::memcpy(&id, a1 + 4 * p + 3, 4);
@@ -77,6 +80,7 @@ int glrt_reproject(const float *accum, const float *n0, const float *a0, const f
             const float fx = u - fx0, fy = v - fy0;
             const float wx[2] = {1.0f - fx, fx}, wy[2] = {1.0f - fy, fy};
             float sw = 0.0f, sc = 0.0f, sI[3] = {0.0f, 0.0f, 0.0f};
+            glrt_detail::MomSum ms;
             for (int j = 0; j < 2; j++)
                 for (int i = 0; i < 2; i++) {
                     const int tx = x0 + i, ty = y0 + j;
@@ -92,6 +96,7 @@ int glrt_reproject(const float *accum, const float *n0, const float *a0, const f
                     sw = sw + w;
                     sc = sc + w * C[3];
                     for (int k = 0; k < 3; k++) sI[k] = sI[k] + w * (C[k] / C[3]);
+                    if (mom) glrt_detail::moments_tap(ms, w, mom + 4 * q);
                 }
             if (!(sw > kMinWeight)) continue;
             const float r = std::nearbyint(sc / sw);
@@ -100,8 +105,24 @@ int glrt_reproject(const float *accum, const float *n0, const float *a0, const f
             for (int k = 0; k < 3; k++) o[k] = canon((sI[k] / sw) * n);
             o[3] = n;
             carried++;
+            if (mom_out) glrt_detail::moments_out(ms, st.max_history, mom_out + 4 * p);
         }
     if (carried_out) *carried_out = carried;
     if (hit_pixels_out) *hit_pixels_out = hits;
     return GLRT_HOST_OK;
+}
+
+int glrt_reproject(const float *accum, const float *n0, const float *a0, const float *n1, const float *a1, const float *c2w_prev, const float *s2c_prev,
+                   const float *c2w_cur, const float *s2c_cur, int width, int rows, int max_history, float depth_tolerance, float normal_tolerance, float *out,
+                   int *carried_out, int *hit_pixels_out) {
+    return reproject_impl(accum, nullptr, n0, a0, n1, a1, c2w_prev, s2c_prev, c2w_cur, s2c_cur, width, rows, max_history, depth_tolerance, normal_tolerance, out,
+                          nullptr, carried_out, hit_pixels_out);
+}
+
+int glrt_reproject_moments(const float *accum, const float *moments, const float *n0, const float *a0, const float *n1, const float *a1, const float *c2w_prev,
+                           const float *s2c_prev, const float *c2w_cur, const float *s2c_cur, int width, int rows, int max_history, float depth_tolerance,
+                           float normal_tolerance, float *out, float *moments_out, int *carried_out, int *hit_pixels_out) {
+    if (!moments || !moments_out) return GLRT_HOST_EINVAL;
+    return reproject_impl(accum, moments, n0, a0, n1, a1, c2w_prev, s2c_prev, c2w_cur, s2c_cur, width, rows, max_history, depth_tolerance, normal_tolerance, out,
+                          moments_out, carried_out, hit_pixels_out);
 }

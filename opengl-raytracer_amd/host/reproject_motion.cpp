@@ -13,6 +13,7 @@
 
 #include "centre_ray.h"
 #include "glrt_host.h"
+#include "reproject_moments.h"
 #include "reproject_setup.h"
 
 namespace {
@@ -38,9 +39,10 @@ constexpr float kMinWeight = 1.0e-6f;
 
 }  // namespace
 
-int glrt_reproject_motion(const float *accum, const float *n0, const float *a0, const float *g1, const float *a1, const float *vert_prev, size_t n_vert,
-                          const float *tri, size_t n_tri, const float *c2w_prev, const float *s2c_prev, int width, int rows, int max_history,
-                          float depth_tolerance, float normal_tolerance, float *out, int *carried_out, int *hit_pixels_out) {
+// glrt_reproject_motion, and with mom / mom_out glrt_reproject_motion_moments: the same pass, the moments riding the same taps.
+static int reproject_motion_impl(const float *accum, const float *mom, const float *n0, const float *a0, const float *g1, const float *a1, const float *vert_prev,
+                                 size_t n_vert, const float *tri, size_t n_tri, const float *c2w_prev, const float *s2c_prev, int width, int rows, int max_history,
+                                 float depth_tolerance, float normal_tolerance, float *out, float *mom_out, int *carried_out, int *hit_pixels_out) {
     if (!accum || !n0 || !a0 || !g1 || !a1 || !c2w_prev || !s2c_prev || !out) return GLRT_HOST_EINVAL;
     if ((n_tri && (!tri || !vert_prev)) || n_tri > (size_t)INT32_MAX) return GLRT_HOST_EINVAL;
     if (width < 1 || rows < 1 || width > 65536 || rows > 65536) return GLRT_HOST_EINVAL;
@@ -84,6 +86,7 @@ int glrt_reproject_motion(const float *accum, const float *n0, const float *a0, 
             const size_t p = (size_t)y * width + x;
             float *o = out + 4 * p;
             o[0] = o[1] = o[2] = o[3] = 0.0f;
+            if (mom_out) { float *mo = mom_out + 4 * p; mo[0] = mo[1] = mo[2] = mo[3] = 0.0f; }
             const float *G1 = g1 + 4 * p;
             int32_t id, tr;
             std::memcpy(&id, a1 + 4 * p + 3, 4);
@@ -120,6 +123,7 @@ int glrt_reproject_motion(const float *accum, const float *n0, const float *a0, 
             const float fx = ui - fx0, fy = vi - fy0;
             const float wx[2] = {1.0f - fx, fx}, wy[2] = {1.0f - fy, fy};
             float sw = 0.0f, sc = 0.0f, sI[3] = {0.0f, 0.0f, 0.0f};
+            glrt_detail::MomSum ms;
             for (int j = 0; j < 2; j++)
                 for (int i = 0; i < 2; i++) {
                     const int tx0 = x0 + i, ty0 = y0 + j;
@@ -135,6 +139,7 @@ int glrt_reproject_motion(const float *accum, const float *n0, const float *a0, 
                     sw = sw + w;
                     sc = sc + w * C[3];
                     for (int k = 0; k < 3; k++) sI[k] = sI[k] + w * (C[k] / C[3]);
+                    if (mom) glrt_detail::moments_tap(ms, w, mom + 4 * q);
                 }
             if (!(sw > kMinWeight)) continue;
             const float rr = std::nearbyint(sc / sw);
@@ -143,8 +148,25 @@ int glrt_reproject_motion(const float *accum, const float *n0, const float *a0, 
             for (int k = 0; k < 3; k++) o[k] = canon((sI[k] / sw) * n);
             o[3] = n;
             carried++;
+            if (mom_out) glrt_detail::moments_out(ms, st.max_history, mom_out + 4 * p);
         }
     if (carried_out) *carried_out = carried;
     if (hit_pixels_out) *hit_pixels_out = hits;
     return GLRT_HOST_OK;
+}
+
+int glrt_reproject_motion(const float *accum, const float *n0, const float *a0, const float *g1, const float *a1, const float *vert_prev, size_t n_vert,
+                          const float *tri, size_t n_tri, const float *c2w_prev, const float *s2c_prev, int width, int rows, int max_history,
+                          float depth_tolerance, float normal_tolerance, float *out, int *carried_out, int *hit_pixels_out) {
+    return reproject_motion_impl(accum, nullptr, n0, a0, g1, a1, vert_prev, n_vert, tri, n_tri, c2w_prev, s2c_prev, width, rows, max_history, depth_tolerance,
+                                 normal_tolerance, out, nullptr, carried_out, hit_pixels_out);
+}
+
+int glrt_reproject_motion_moments(const float *accum, const float *moments, const float *n0, const float *a0, const float *g1, const float *a1,
+                                  const float *vert_prev, size_t n_vert, const float *tri, size_t n_tri, const float *c2w_prev, const float *s2c_prev, int width,
+                                  int rows, int max_history, float depth_tolerance, float normal_tolerance, float *out, float *moments_out, int *carried_out,
+                                  int *hit_pixels_out) {
+    if (!moments || !moments_out) return GLRT_HOST_EINVAL;
+    return reproject_motion_impl(accum, moments, n0, a0, g1, a1, vert_prev, n_vert, tri, n_tri, c2w_prev, s2c_prev, width, rows, max_history, depth_tolerance,
+                                 normal_tolerance, out, moments_out, carried_out, hit_pixels_out);
 }

@@ -104,8 +104,9 @@ void Window::mainloop(const std::shared_ptr<Scene> &scene_, double fps) {
     // Launches are issued back to back and the loop waits for the device only where it needs the pixels (a frame that is saved, the end of the run): the calls are
     // asynchronous, and a launch issued behind idle time runs longer -- 2 % behind 1 ms, 5 % behind 3 ms (profiles/r04_ab_launch_warmth.txt).  lastFrameMs() is the wall
     // time per frame between two such waits.
-    if (denoise_) {  // the feature planes of this (static) camera, once, before the first frame
+    if (denoise_ || denoiseVar_) {  // the feature planes of this (static) camera, once, before the first frame
         if (glrtx_group_size(grp_) != 1 || every) GLRT_FatalError("--denoise: one device, and not with --save-every-frame (groups and the present ring have no denoised form)");
+        if (denoiseVar_ && (denoise_ || adaptive_)) GLRT_FatalError("--denoise-variance: not with --denoise or --adaptive");
         glrtx_params p;
         frameParams(p);
         glrtx_ctx *c0 = glrtx_group_ctx(grp_, 0);
@@ -142,6 +143,24 @@ void Window::mainloop(const std::shared_ptr<Scene> &scene_, double fps) {
         glrtx_stats st;
         GLRTX_CHECK(glrtx_group_get_stats(grp_, &st));
         GLRT_Info("Presented: %d frames, %d images, %llu render kernel launches", frameLimit_, images, (unsigned long long)st.kernel_launches);
+        return;
+    }
+    if (denoiseVar_) {
+        // Variance guidance: the frames in bursts of framesInFlight_ through glrtx_render_moments, which folds every sample into the moments plane as well.
+        glrtx_ctx *c0 = glrtx_group_ctx(grp_, 0);
+        if (glrtx_track_moments(c0, 1) != GLRTX_OK) GLRT_FatalError("glrtx_track_moments: %s", glrtx_last_error(c0));
+        glrtx_params p;
+        frameParams(p);
+        for (int issued = 0; issued < frameLimit_;) {
+            const int n = frameLimit_ - issued < framesInFlight_ ? frameLimit_ - issued : framesInFlight_;
+            std::vector<float> seeds(2 * (size_t)n);
+            for (int f = 0; f < n; f++) glrt_frame_seed(frame_++, &seeds[2 * (size_t)f]);
+            if (glrtx_render_moments(c0, &p, seeds.data(), n) != GLRTX_OK) GLRT_FatalError("glrtx_render_moments: %s", glrtx_last_error(c0));
+            issued += n;
+        }
+        GLRTX_CHECK(glrtx_group_sync(grp_));
+        lastMs_ = frameLimit_ > 0 ? std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() / frameLimit_ : 0.0;
+        if (!output_.empty() && frameLimit_ > 0) saveCurrentFrame(output_, true);
         return;
     }
     if (adaptive_) {
@@ -246,6 +265,11 @@ void Window::saveCurrentFrame(const std::string &filename, bool overwrite) const
         if (glrtx_denoise(c0, &denoiseCfg_) != GLRTX_OK || glrtx_resolve_denoised_rgba8(c0, bytes.data(), (size_t)width_ * 4, 2.2f, 1) != GLRTX_OK)
             GLRT_FatalError("glrtx_denoise: %s", glrtx_last_error(c0));
         GLRT_Info("Denoise: %d iterations", denoiseCfg_.iterations);
+    } else if (denoiseVar_) {
+        glrtx_ctx *c0 = glrtx_group_ctx(grp_, 0);
+        if (glrtx_denoise_variance(c0, &denoiseVarCfg_) != GLRTX_OK || glrtx_resolve_denoised_rgba8(c0, bytes.data(), (size_t)width_ * 4, 2.2f, 1) != GLRTX_OK)
+            GLRT_FatalError("glrtx_denoise_variance: %s", glrtx_last_error(c0));
+        GLRT_Info("Denoise (variance-guided): %d iterations", denoiseVarCfg_.iterations);
     } else if (glrtx_group_resolve_rgba8(grp_, bytes.data(), (size_t)width_ * 4, 2.2f, 1) != GLRTX_OK)
         GLRT_FatalError("glrtx_group_resolve_rgba8: %s", glrtx_group_last_error(grp_));
     saveImage(filename, overwrite, bytes.data());

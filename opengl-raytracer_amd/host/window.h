@@ -57,6 +57,9 @@ public:
     // Denoising (no reference counterpart; glrtx_render_features / glrtx_denoise, one device only): the feature planes are rendered once before the first frame, and
     // every image that is written is the a-trous filter's result D instead of the raw mean.  iterations < 1: the default.
     void setDenoise(int iterations) { denoise_ = true; if (iterations >= 1) denoiseCfg_.iterations = iterations; }
+    // Variance-guided denoising (glrtx_track_moments / glrtx_render_moments / glrtx_denoise_variance, one device only): the frames are rendered in bursts of
+    // framesInFlight frames with the moments fold, and the saved image is the variance-guided filter's.
+    void setDenoiseVariance(int iterations) { denoiseVar_ = true; if (iterations >= 1) denoiseVarCfg_.iterations = iterations; }
     // wall-clock ms PER FRAME between the last two waits for the device, averaged over the frames issued in between (with one PNG per run: the whole run, cold first
     // launches included; with --save-every-frame: the whole run, PNG writing included).  The device's own time of the last launch is glrtx_stats.kernel_ms_last.
     double lastFrameMs() const { return lastMs_; }
@@ -90,7 +93,8 @@ private:
     float adaptThreshold_ = 0.0f;
     int adaptMinSamples_ = 2;
     bool volumeWavefront_ = false;
-    bool denoise_ = false;
+    bool denoise_ = false, denoiseVar_ = false;
+    glrtx_denoise_var_cfg denoiseVarCfg_ = {5, 4.0f, 0.1f, 0.01f, 1};  // (DESIGN.md "Variance guidance": the sweep; glrt_amd.host.DENOISE_VAR_DEFAULTS holds the same)
     glrtx_denoise_cfg denoiseCfg_ = {5, 100.0f, 0.1f, 0.01f, 1};  // (DESIGN.md "Denoising": the sweep behind these; glrt_amd.host.DENOISE_DEFAULTS holds the same)
     bool fallbackNoted_ = false;
     std::string output_ = "output.png";

@@ -45,6 +45,11 @@ class DenoiseCfg(C.Structure):
     _fields_ = [("iterations", C.c_int), ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float), ("demodulate", C.c_int)]
 
 
+class DenoiseVarCfg(C.Structure):
+    """glrtx_denoise_var_cfg (device.denoise_var_cfg fills in glrt_amd.host.DENOISE_VAR_DEFAULTS)."""
+    _fields_ = [("iterations", C.c_int), ("sigma_lum", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float), ("demodulate", C.c_int)]
+
+
 class ReprojectCfg(C.Structure):
     """glrtx_reproject_cfg; ReprojectCfg.default() holds glrt_amd.host.REPROJECT_DEFAULTS."""
     _fields_ = [("max_history", C.c_int), ("depth_tolerance", C.c_float), ("normal_tolerance", C.c_float)]
@@ -93,7 +98,9 @@ EXPORTS = ["glrtx_abi_version", "glrtx_create", "glrtx_destroy", "glrtx_last_err
            "glrtx_render_features", "glrtx_read_features", "glrtx_denoise", "glrtx_read_denoised", "glrtx_resolve_denoised_rgba8", "glrtx_debug_denoise",
            "glrtx_update_vertices", "glrtx_update_vertices_device", "glrtx_group_update_vertices", "glrtx_debug_read_scene",
            "glrtx_trace_rays", "glrtx_trace_rays_device", "glrtx_reproject", "glrtx_reproject_last", "glrtx_debug_reproject",
-           "glrtx_track_motion", "glrtx_read_features_geom", "glrtx_reproject_motion", "glrtx_debug_reproject_motion"]
+           "glrtx_track_motion", "glrtx_read_features_geom", "glrtx_reproject_motion", "glrtx_debug_reproject_motion",
+           "glrtx_track_moments", "glrtx_render_moments", "glrtx_read_moments", "glrtx_denoise_variance", "glrtx_debug_denoise_variance",
+           "glrtx_debug_reproject_moments", "glrtx_debug_reproject_motion_moments"]
 
 SCENE_BUFFERS = ("nodes", "cnodes", "nrms", "lights", "vine", "root")  # glrtx_debug_read_scene's `which`, in order (GLRTX_SCENE_*)
 
@@ -222,6 +229,17 @@ def lib():
                                                        C.POINTER(C.c_int), C.POINTER(C.c_int)]
         except AttributeError:
             pass
+        try:  # (additive to ABI 10 as well: variance guidance)
+            L.glrtx_track_moments.argtypes = [vp, C.c_int]
+            L.glrtx_render_moments.argtypes = [vp, C.POINTER(Params), fp, C.c_int]
+            L.glrtx_read_moments.argtypes = [vp, vp, C.c_size_t]
+            L.glrtx_denoise_variance.argtypes = [vp, C.POINTER(DenoiseVarCfg)]
+            L.glrtx_debug_denoise_variance.argtypes = [fp, fp, fp, fp, C.c_int, C.c_int, C.POINTER(DenoiseVarCfg), fp, fp]
+            L.glrtx_debug_reproject_moments.argtypes = [fp] * 10 + [C.c_int, C.c_int, C.POINTER(ReprojectCfg), fp, fp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+            L.glrtx_debug_reproject_motion_moments.argtypes = [fp] * 7 + [C.c_size_t, fp, C.c_size_t, fp, fp, C.c_int, C.c_int, C.POINTER(ReprojectCfg), fp, fp,
+                                                               C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        except AttributeError:
+            pass
         _lib = L
     return _lib
 
@@ -331,6 +349,31 @@ def debug_denoise(accum, normal_depth, albedo_id, **cfg):
     return out
 
 
+def denoise_var_cfg(iterations=None, sigma_lum=None, sigma_normal=None, sigma_depth=None, demodulate=None) -> DenoiseVarCfg:
+    """A glrtx_denoise_var_cfg; None takes the default (glrt_amd.host.DENOISE_VAR_DEFAULTS)."""
+    from .host import DENOISE_VAR_DEFAULTS as d
+    pick = lambda v, k: d[k] if v is None else v
+    return DenoiseVarCfg(int(pick(iterations, "iterations")), float(pick(sigma_lum, "sigma_lum")), float(pick(sigma_normal, "sigma_normal")),
+                         float(pick(sigma_depth, "sigma_depth")), int(bool(pick(demodulate, "demodulate"))))
+
+
+def debug_denoise_variance(accum, moments, normal_depth, albedo_id, return_v0=False, **cfg):
+    """glrtx_debug_denoise_variance on the current device: the variance pass and the variance-guided filter on (rows, width, 4) float32 arrays.  Returns D,
+    float4(rgb, 1) per pixel; with return_v0 (D, V0), V0 (rows, width) float32."""
+    L = lib()
+    arr = [_f32(v) for v in (accum, moments, normal_depth, albedo_id)]
+    a = arr[0]
+    if a.ndim != 3 or a.shape[2] != 4 or any(v.shape != a.shape for v in arr):
+        raise ValueError(f"debug_denoise_variance: four (rows, width, 4) arrays of one shape expected, got {[v.shape for v in arr]}")
+    out = np.zeros_like(a)
+    v0 = np.zeros(a.shape[:2], np.float32)
+    c = denoise_var_cfg(**cfg)
+    rc = L.glrtx_debug_denoise_variance(*[_fp(v) for v in arr], a.shape[1], a.shape[0], C.byref(c), _fp(out), _fp(v0) if return_v0 else None)
+    if rc != 0:
+        raise GlrtxError(rc, L.glrtx_last_error(None).decode())
+    return (out, v0) if return_v0 else out
+
+
 def debug_reproject(accum, n0, a0, n1, a1, prev, cur, **cfg):
     """glrtx_debug_reproject on the current device: the reprojection kernel on (rows, width, 4) float32 arrays (the old view's accumulator and planes, the new
     view's planes) and the two cameras (dicts with c2w and s2c).  Returns (out, carried, hit_pixels)."""
@@ -368,6 +411,45 @@ def debug_reproject_motion(accum, n0, a0, g1, a1, vert_prev, tri, prev, **cfg):
     if rc != 0:
         raise GlrtxError(rc, L.glrtx_last_error(None).decode())
     return out, int(carried.value), int(hits.value)
+
+
+def debug_reproject_moments(accum, moments, n0, a0, n1, a1, prev, cur, **cfg):
+    """glrtx_debug_reproject_moments on the current device: debug_reproject with the old view's moments plane M carried through the same taps.  Returns
+    (out, moments_out, carried, hit_pixels)."""
+    L = lib()
+    arr = [_f32(v) for v in (accum, moments, n0, a0, n1, a1)]
+    a = arr[0]
+    if a.ndim != 3 or a.shape[2] != 4 or any(v.shape != a.shape for v in arr):
+        raise ValueError(f"debug_reproject_moments: six (rows, width, 4) arrays of one shape expected, got {[v.shape for v in arr]}")
+    mats = [_f32(np.asarray(m).reshape(16)) for m in (prev["c2w"], prev["s2c"], cur["c2w"], cur["s2c"])]
+    out, mo = np.zeros_like(a), np.zeros_like(a)
+    c = ReprojectCfg.default(**cfg)
+    carried, hits = C.c_int(0), C.c_int(0)
+    rc = L.glrtx_debug_reproject_moments(*[_fp(v) for v in arr], *[_fp(m) for m in mats], a.shape[1], a.shape[0], C.byref(c), _fp(out), _fp(mo), C.byref(carried),
+                                         C.byref(hits))
+    if rc != 0:
+        raise GlrtxError(rc, L.glrtx_last_error(None).decode())
+    return out, mo, int(carried.value), int(hits.value)
+
+
+def debug_reproject_motion_moments(accum, moments, n0, a0, g1, a1, vert_prev, tri, prev, **cfg):
+    """glrtx_debug_reproject_motion_moments on the current device: debug_reproject_motion with the old view's moments plane M carried.  Returns
+    (out, moments_out, carried, hit_pixels)."""
+    L = lib()
+    arr = [_f32(v) for v in (accum, moments, n0, a0, g1, a1)]
+    a = arr[0]
+    if a.ndim != 3 or a.shape[2] != 4 or any(v.shape != a.shape for v in arr):
+        raise ValueError(f"debug_reproject_motion_moments: six (rows, width, 4) arrays of one shape expected, got {[v.shape for v in arr]}")
+    vert, tr = _f32(vert_prev).reshape(-1, 15), _f32(tri).reshape(-1, 4)
+    mats = [_f32(np.asarray(m).reshape(16)) for m in (prev["c2w"], prev["s2c"])]
+    out, mo = np.zeros_like(a), np.zeros_like(a)
+    c = ReprojectCfg.default(**cfg)
+    carried, hits = C.c_int(0), C.c_int(0)
+    rc = L.glrtx_debug_reproject_motion_moments(*[_fp(v) for v in arr], _fp(vert), vert.shape[0], _fp(tr), tr.shape[0], *[_fp(m) for m in mats], a.shape[1],
+                                                a.shape[0], C.byref(c), _fp(out), _fp(mo), C.byref(carried), C.byref(hits))
+    if rc != 0:
+        raise GlrtxError(rc, L.glrtx_last_error(None).decode())
+    return out, mo, int(carried.value), int(hits.value)
 
 
 def _host_vertices(v):
@@ -688,6 +770,25 @@ class Device:
         out = np.zeros((s.owned_rows, s.width, 4), np.uint8)
         self._ck(self.L.glrtx_resolve_denoised_rgba8(self.h, out.ctypes.data, s.width * 4, gamma, int(flip_y)))
         return out
+    def track_moments(self, enable=True):
+        """Keep the luminance moments plane M beside the accumulator (glrtx_track_moments); off by default, switching it off releases M."""
+        self._ck(self.L.glrtx_track_moments(self.h, int(bool(enable))))
+    def render_moments(self, params, seeds):
+        """render_frames that also folds every sample's luminance and squared luminance into M (glrtx_render_moments); the accumulator is render_frames'."""
+        p = params if isinstance(params, Params) else make_params(dict(params, seed=(0.0, 0.0)) if "seed" not in params else params)
+        sd = _f32(np.asarray(seeds, np.float32).reshape(-1, 2))
+        self._ck(self.L.glrtx_render_moments(self.h, C.byref(p), _fp(sd), sd.shape[0]))
+    def read_moments(self) -> np.ndarray:
+        """The moments plane M {sum l, sum l^2, 0, count}, (owned_rows, width, 4) float32 like read_accum (syncs)."""
+        s = self.stats()
+        out = np.zeros((s.owned_rows, s.width, 4), np.float32)
+        self._ck(self.L.glrtx_read_moments(self.h, out.ctypes.data, s.width * 16))
+        return out
+    def denoise_variance(self, iterations=None, sigma_lum=None, sigma_normal=None, sigma_depth=None, demodulate=None):
+        """The variance-guided a-trous filter over the accumulator's mean, steered by M and the feature planes as they stand (glrtx_denoise_variance); the result
+        is read with read_denoised / resolve_denoised_rgba8.  None: the default."""
+        c = denoise_var_cfg(iterations, sigma_lum, sigma_normal, sigma_depth, demodulate)
+        self._ck(self.L.glrtx_denoise_variance(self.h, C.byref(c)))
     def reproject(self, params, max_history=None, depth_tolerance=None, normal_tolerance=None):
         """Carry the accumulator from the camera of the last render_features / reproject to `params`' camera (glrtx_reproject); None: the default.  The
         accumulator's device address changes; the feature planes are `params`' afterwards."""

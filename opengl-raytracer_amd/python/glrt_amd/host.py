@@ -39,10 +39,16 @@ def lib():
         L.glrt_trace_rays.argtypes = [fp, C.c_size_t, fp, C.c_size_t, fp, C.c_size_t, fp, C.c_size_t, fp, C.c_int]
         L.glrt_render_features.argtypes = [fp, C.c_size_t, fp, C.c_size_t, fp, C.c_size_t, fp, C.c_size_t, fp, fp] + [C.c_int] * 5 + [fp, fp]
         L.glrt_denoise_atrous.argtypes = [fp, fp, fp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int, fp]
+        L.glrt_fold_moments.argtypes = [fp, fp, C.c_int, C.c_int, C.c_int]
+        L.glrt_variance_estimate.argtypes = [fp, fp, fp, fp, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, fp]
+        L.glrt_denoise_variance.argtypes = [fp, fp, fp, fp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int, fp, fp]
         L.glrt_reproject.argtypes = [fp] * 9 + [C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, fp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.glrt_render_features_geom.argtypes = [fp, C.c_size_t, fp, C.c_size_t, fp, C.c_size_t, fp, C.c_size_t, fp, fp] + [C.c_int] * 5 + [fp, fp, fp]
         L.glrt_reproject_motion.argtypes = [fp] * 6 + [C.c_size_t, fp, C.c_size_t, fp, fp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, fp,
                                             C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.glrt_reproject_moments.argtypes = [fp] * 10 + [C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, fp, fp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.glrt_reproject_motion_moments.argtypes = [fp] * 7 + [C.c_size_t, fp, C.c_size_t, fp, fp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, fp, fp,
+                                                    C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.glrt_look_at.argtypes = [fp, fp, fp, fp]
         L.glrt_perspective.argtypes = [C.c_float, C.c_float, C.c_float, C.c_float, fp]
         L.glrt_mat4_mul.argtypes = [fp, fp, fp]
@@ -212,6 +218,56 @@ def denoise_atrous(accum, normal_depth, albedo_id, iterations=DENOISE_DEFAULTS["
     return out
 
 
+# The variance-guided filter's defaults (DESIGN.md "Variance guidance": chosen from the sweep recorded there); Device.denoise_variance takes the same.
+DENOISE_VAR_DEFAULTS = dict(iterations=5, sigma_lum=4.0, sigma_normal=0.1, sigma_depth=0.01, demodulate=True)
+
+
+def _four_planes(name, *arrs):
+    arr = [_f32(v) for v in arrs]
+    a = arr[0]
+    if a.ndim != 3 or a.shape[2] != 4 or any(v.shape != a.shape for v in arr):
+        raise ValueError(f"{name}: (rows, width, 4) arrays of one shape expected, got {[v.shape for v in arr]}")
+    return arr
+
+
+def fold_moments(moments, planes):
+    """glrt_fold_moments: the sample planes (k, rows, width, 4), in order, folded into a copy of the moments plane M {sum l, sum l^2, 0, count}."""
+    m = _f32(moments).copy()
+    p = _f32(planes)
+    if m.ndim != 3 or m.shape[2] != 4 or p.ndim != 4 or p.shape[1:] != m.shape:
+        raise ValueError(f"fold_moments: moments (rows, width, 4) and planes (k, rows, width, 4) expected, got {m.shape} and {p.shape}")
+    rc = lib().glrt_fold_moments(_fp(m), _fp(p), p.shape[0], m.shape[1], m.shape[0])
+    if rc != 0:
+        raise RuntimeError(f"glrt_fold_moments failed: {rc}")
+    return m
+
+
+def variance_estimate(accum, moments, normal_depth, albedo_id, sigma_normal=DENOISE_VAR_DEFAULTS["sigma_normal"],
+                      sigma_depth=DENOISE_VAR_DEFAULTS["sigma_depth"], demodulate=DENOISE_VAR_DEFAULTS["demodulate"]):
+    """glrt_variance_estimate: the CPU statement of the variance pass.  Returns V0, (rows, width) float32."""
+    a, m, n, al = _four_planes("variance_estimate", accum, moments, normal_depth, albedo_id)
+    v0 = np.zeros(a.shape[:2], np.float32)
+    rc = lib().glrt_variance_estimate(_fp(a), _fp(m), _fp(n), _fp(al), a.shape[1], a.shape[0], float(sigma_normal), float(sigma_depth), int(bool(demodulate)), _fp(v0))
+    if rc != 0:
+        raise RuntimeError(f"glrt_variance_estimate failed: {rc}")
+    return v0
+
+
+def denoise_variance(accum, moments, normal_depth, albedo_id, iterations=DENOISE_VAR_DEFAULTS["iterations"], sigma_lum=DENOISE_VAR_DEFAULTS["sigma_lum"],
+                     sigma_normal=DENOISE_VAR_DEFAULTS["sigma_normal"], sigma_depth=DENOISE_VAR_DEFAULTS["sigma_depth"],
+                     demodulate=DENOISE_VAR_DEFAULTS["demodulate"], return_v0=False):
+    """glrt_denoise_variance: the CPU statement of Device.denoise_variance on (rows, width, 4) float32 arrays.  Returns D, float4(rgb, 1) per pixel (with
+    return_v0: (D, V0))."""
+    a, m, n, al = _four_planes("denoise_variance", accum, moments, normal_depth, albedo_id)
+    out = np.zeros_like(a)
+    v0 = np.zeros(a.shape[:2], np.float32) if return_v0 else None
+    rc = lib().glrt_denoise_variance(_fp(a), _fp(m), _fp(n), _fp(al), a.shape[1], a.shape[0], int(iterations), float(sigma_lum), float(sigma_normal),
+                                     float(sigma_depth), int(bool(demodulate)), _fp(out), _fp(v0) if return_v0 else None)
+    if rc != 0:
+        raise RuntimeError(f"glrt_denoise_variance failed: {rc}")
+    return (out, v0) if return_v0 else out
+
+
 # The reprojection's defaults (DESIGN.md "Reprojection": chosen from the sweep recorded there); Device.reproject takes the same.
 REPROJECT_DEFAULTS = dict(max_history=32, depth_tolerance=0.02, normal_tolerance=0.9)
 
@@ -252,6 +308,43 @@ def reproject_motion(accum, n0, a0, g1, a1, vert_prev, tri, prev, max_history=RE
     if rc != 0:
         raise RuntimeError(f"glrt_reproject_motion failed: {rc}")
     return out, int(carried.value), int(hits.value)
+
+
+def reproject_moments(accum, moments, n0, a0, n1, a1, prev, cur, max_history=REPROJECT_DEFAULTS["max_history"],
+                      depth_tolerance=REPROJECT_DEFAULTS["depth_tolerance"], normal_tolerance=REPROJECT_DEFAULTS["normal_tolerance"]):
+    """glrt_reproject_moments: reproject with the old view's moments plane M carried through the same taps (the CPU statement of Device.reproject while
+    Device.track_moments is on).  Returns (out, moments_out, carried, hit_pixels)."""
+    arr = [_f32(v) for v in (accum, moments, n0, a0, n1, a1)]
+    a = arr[0]
+    if a.ndim != 3 or a.shape[2] != 4 or any(v.shape != a.shape for v in arr):
+        raise ValueError(f"reproject_moments: six (rows, width, 4) arrays of one shape expected, got {[v.shape for v in arr]}")
+    mats = [_f32(m).reshape(16) for m in (prev["c2w"], prev["s2c"], cur["c2w"], cur["s2c"])]
+    out, mo = np.zeros_like(a), np.zeros_like(a)
+    carried, hits = C.c_int(0), C.c_int(0)
+    rc = lib().glrt_reproject_moments(*[_fp(v) for v in arr], *[_fp(m) for m in mats], a.shape[1], a.shape[0], int(max_history), float(depth_tolerance),
+                                      float(normal_tolerance), _fp(out), _fp(mo), C.byref(carried), C.byref(hits))
+    if rc != 0:
+        raise RuntimeError(f"glrt_reproject_moments failed: {rc}")
+    return out, mo, int(carried.value), int(hits.value)
+
+
+def reproject_motion_moments(accum, moments, n0, a0, g1, a1, vert_prev, tri, prev, max_history=REPROJECT_DEFAULTS["max_history"],
+                             depth_tolerance=REPROJECT_DEFAULTS["depth_tolerance"], normal_tolerance=REPROJECT_DEFAULTS["normal_tolerance"]):
+    """glrt_reproject_motion_moments: reproject_motion with the old view's moments plane M carried.  Returns (out, moments_out, carried, hit_pixels)."""
+    arr = [_f32(v) for v in (accum, moments, n0, a0, g1, a1)]
+    a = arr[0]
+    if a.ndim != 3 or a.shape[2] != 4 or any(v.shape != a.shape for v in arr):
+        raise ValueError(f"reproject_motion_moments: six (rows, width, 4) arrays of one shape expected, got {[v.shape for v in arr]}")
+    vert, tr = _f32(vert_prev).reshape(-1, 15), _f32(tri).reshape(-1, 4)
+    mats = [_f32(m).reshape(16) for m in (prev["c2w"], prev["s2c"])]
+    out, mo = np.zeros_like(a), np.zeros_like(a)
+    carried, hits = C.c_int(0), C.c_int(0)
+    rc = lib().glrt_reproject_motion_moments(*[_fp(v) for v in arr], _fp(vert), vert.shape[0], _fp(tr), tr.shape[0], *[_fp(m) for m in mats], a.shape[1],
+                                             a.shape[0], int(max_history), float(depth_tolerance), float(normal_tolerance), _fp(out), _fp(mo), C.byref(carried),
+                                             C.byref(hits))
+    if rc != 0:
+        raise RuntimeError(f"glrt_reproject_motion_moments failed: {rc}")
+    return out, mo, int(carried.value), int(hits.value)
 
 
 def look_at(eye, center, up) -> np.ndarray:
