@@ -1449,45 +1449,145 @@ void denoise_release(glrtx_ctx *c) {
     for (DevBuf &v : c->dnV) dev_free(v);
 }
 
-int denoise_cfg_check(glrtx_ctx *c, const glrtx_denoise_cfg *cfg, const char *fn) {
+// The two filters' configurations as one: glrtx_denoise_cfg and glrtx_denoise_var_cfg differ in the name of the colour term's sigma.
+struct FilterCfg { int iterations; float sigma_c, sigma_normal, sigma_depth; int demodulate; };
+FilterCfg filter_cfg(const glrtx_denoise_cfg &k) { return {k.iterations, k.sigma_color, k.sigma_normal, k.sigma_depth, k.demodulate}; }
+FilterCfg filter_cfg(const glrtx_denoise_var_cfg &k) { return {k.iterations, k.sigma_lum, k.sigma_normal, k.sigma_depth, k.demodulate}; }
+
+template <class Cfg>
+int denoise_cfg_check(glrtx_ctx *c, const Cfg *cfg, const char *fn, FilterCfg &k) {
     if (!cfg) return fail(c, GLRTX_EINVAL, "%s: NULL cfg", fn);
-    if (cfg->iterations < 1 || cfg->iterations > 6) return fail(c, GLRTX_EINVAL, "%s: iterations %d outside 1..6", fn, cfg->iterations);
-    const float sg[3] = {cfg->sigma_color, cfg->sigma_normal, cfg->sigma_depth};
+    k = filter_cfg(*cfg);
+    if (k.iterations < 1 || k.iterations > 6) return fail(c, GLRTX_EINVAL, "%s: iterations %d outside 1..6", fn, k.iterations);
+    const float sg[3] = {k.sigma_c, k.sigma_normal, k.sigma_depth};
     for (float v : sg)
         if (!(v > 0.0f) || std::isinf(v)) return fail(c, GLRTX_EINVAL, "%s: sigma %g is not a positive finite number", fn, (double)v);
     return GLRTX_OK;
 }
 
 // The filter's passes on `stream`: accum (pitch_f4) + the two feature planes -> D, through the ping-pong images p0 / p1 (all but accum packed rows of `width`).
-int denoise_passes(glrtx_ctx *c, hipStream_t stream, const float4 *accum, int pitch_f4, const float4 *guide, const float4 *albedo, float4 *p0, float4 *p1, float4 *D,
-                   int width, int rows, const glrtx_denoise_cfg *cfg) {
+// With `moments` (pitch_f4) and the variance planes v[0] (V0), v[1], v[2] (packed floats) the variance pass runs first and the iterations are the
+// variance-guided ones; without them (both null) they are the plain ones.
+int denoise_passes(glrtx_ctx *c, hipStream_t stream, const float4 *accum, const float4 *moments, int pitch_f4, const float4 *guide, const float4 *albedo, float4 *p0,
+                   float4 *p1, float4 *D, float *const *v, int width, int rows, const FilterCfg &k) {
     const dim3 grid((unsigned)(((width + denoise::kTileDn - 1) / denoise::kTileDn) * ((rows + denoise::kTileDn - 1) / denoise::kTileDn)));
-    const int demod = cfg->demodulate ? 1 : 0;
+    const int demod = k.demodulate ? 1 : 0;
+    const bool var = moments != nullptr;
+    if (var) {
+        variance::Args va;
+        va.accum = accum; va.moments = moments; va.guide = guide; va.albedo = albedo; va.v0 = v[0];
+        va.pitch_f4 = pitch_f4; va.width = width; va.rows = rows;
+        va.sigma_normal = k.sigma_normal; va.sigma_depth = k.sigma_depth; va.demodulate = demod;
+        hipLaunchKernelGGL(variance::variance_estimate, grid, dim3(256), 0, stream, va);
+        HIP_TRY(c, hipGetLastError());
+    }
     hipLaunchKernelGGL(denoise::denoise_prep, grid, dim3(256), 0, stream, accum, pitch_f4, albedo, p0, width, rows, demod);
     HIP_TRY(c, hipGetLastError());
+    using Kernel = void (*)(const denoise::Args);
+    static const Kernel kernels[2][3][2] = {  // [variance-guided][iteration 0, 1, 2 and later: S = 1, 2, 0][last]
+        {{denoise::denoise_atrous<1, false>, denoise::denoise_atrous<1, true>},
+         {denoise::denoise_atrous<2, false>, denoise::denoise_atrous<2, true>},
+         {denoise::denoise_atrous<0, false>, denoise::denoise_atrous<0, true>}},
+        {{denoise::denoise_atrous_var<1, false>, denoise::denoise_atrous_var<1, true>},
+         {denoise::denoise_atrous_var<2, false>, denoise::denoise_atrous_var<2, true>},
+         {denoise::denoise_atrous_var<0, false>, denoise::denoise_atrous_var<0, true>}}};
     float4 *img[2] = {p0, p1};
-    for (int it = 0; it < cfg->iterations; it++) {
-        const bool last = it == cfg->iterations - 1;
-        denoise::Args a;
+    for (int it = 0; it < k.iterations; it++) {
+        const bool last = it == k.iterations - 1;
+        denoise::Args a{};
         a.src = img[it & 1]; a.guide = guide; a.albedo = albedo; a.dst = last ? D : img[(it + 1) & 1];
         a.width = width; a.rows = rows; a.spacing = 1 << it;
-        uint32_t pw = (uint32_t)(127 - 2 * it) << 23;  // 4^-it
-        float scale;
-        std::memcpy(&scale, &pw, 4);
-        float sc = cfg->sigma_color * scale;
-        uint32_t scb;
-        std::memcpy(&scb, &sc, 4);
-        if ((scb & 0x7F800000u) == 0u) sc = 0.0f;  // (a denormal: the device would read it as zero)
-        a.sigma_color_i = sc; a.sigma_normal = cfg->sigma_normal; a.sigma_depth = cfg->sigma_depth;
+        if (var) {
+            a.vsrc = it == 0 ? v[0] : v[1 + ((it - 1) & 1)]; a.vdst = v[1 + (it & 1)];
+            a.sigma_c = k.sigma_c;
+        } else {
+            uint32_t pw = (uint32_t)(127 - 2 * it) << 23;  // 4^-it
+            float scale;
+            std::memcpy(&scale, &pw, 4);
+            float sc = k.sigma_c * scale;
+            uint32_t scb;
+            std::memcpy(&scb, &sc, 4);
+            if ((scb & 0x7F800000u) == 0u) sc = 0.0f;  // (a denormal: the device would read it as zero)
+            a.sigma_c = sc;
+        }
+        a.sigma_normal = k.sigma_normal; a.sigma_depth = k.sigma_depth;
         a.demodulate = demod;
-        using Kernel = void (*)(const denoise::Args);
-        const Kernel k = it == 0 ? (last ? (Kernel)denoise::denoise_atrous<1, true> : (Kernel)denoise::denoise_atrous<1, false>)
-                       : it == 1 ? (last ? (Kernel)denoise::denoise_atrous<2, true> : (Kernel)denoise::denoise_atrous<2, false>)
-                                 : (last ? (Kernel)denoise::denoise_atrous<0, true> : (Kernel)denoise::denoise_atrous<0, false>);
-        hipLaunchKernelGGL(k, grid, dim3(256), 0, stream, a);
+        hipLaunchKernelGGL(kernels[var][std::min(it, 2)][last], grid, dim3(256), 0, stream, a);
         HIP_TRY(c, hipGetLastError());
     }
     return GLRTX_OK;
+}
+
+// The debug entry points' device buffers: a handful of allocations, freed on scope exit, and the first HIP error of the sequence -- every step after it is
+// skipped, and result() reports it.
+struct DebugScratch {
+    std::vector<void *> bufs;
+    hipError_t e = hipSuccess;
+    ~DebugScratch() {
+        for (void *q : bufs) (void)hipFree(q);
+    }
+    bool ok() const { return e == hipSuccess; }
+    template <class T = float4>
+    T *alloc(size_t bytes, const void *upload = nullptr) {
+        void *q = nullptr;
+        if (ok() && (e = hipMalloc(&q, bytes)) == hipSuccess) bufs.push_back(q);
+        if (ok() && upload) e = hipMemcpy(q, upload, bytes, hipMemcpyHostToDevice);
+        return (T *)q;
+    }
+    void sync() {
+        if (ok()) e = hipDeviceSynchronize();
+    }
+    void download(void *to, const void *from, size_t bytes) {
+        if (ok() && to) e = hipMemcpy(to, from, bytes, hipMemcpyDeviceToHost);
+    }
+    int result(int rc, const char *fn) const { return ok() ? rc : fail(nullptr, GLRTX_EDEVICE, "%s: %s", fn, hipGetErrorString(e)); }
+};
+
+
+// ---- reprojection (glrtx_reproject, glrtx_reproject_motion): the launches
+// What the two kernels share (reproject::Common): the old view (accumulator of pitch_f4, planes N0 / A0), the new view's x1 (N1, or G1 for the motion kernel) and A1 -> `out` (pitch_f4); with mom /
+// mom_out the moments plane rides the same taps.  `counts`: reproject::kCountBytes.
+reproject::Common reproject_common(const glrt_detail::ReprojectSetup &st, const float4 *acc, const float4 *n0, const float4 *a0, const float4 *x1, const float4 *a1, float4 *out,
+                                   int pitch_f4, int width, int rows, void *counts, const float4 *mom, float4 *mom_out) {
+    reproject::Common a{};
+    std::memcpy(a.W, st.W, sizeof a.W);
+    std::memcpy(a.S, st.S, sizeof a.S);
+    a.opx = st.o_prev[0]; a.opy = st.o_prev[1]; a.opz = st.o_prev[2];
+    a.acc = acc; a.n0 = n0; a.a0 = a0; a.x1 = x1; a.a1 = a1; a.out = out;
+    a.pitch_f4 = pitch_f4; a.width = width; a.rows = rows;
+    a.tiles_x = (width + 7) / 8;
+    a.n_tiles = a.tiles_x * ((rows + 7) / 8);
+    a.max_history = st.max_history; a.depth_tol = st.depth_tolerance; a.normal_tol = st.normal_tolerance;
+    a.counts = (unsigned long long *)counts;
+    a.mom = mom; a.mom_out = mom_out;
+    return a;
+}
+
+// Either kernel on `stream`, its counters zeroed first.
+template <class A>
+int reproject_launch(glrtx_ctx *c, hipStream_t stream, void (*kernel)(const A), const A &a) {
+    HIP_TRY(c, hipMemsetAsync(a.c.counts, 0, reproject::kCountBytes, stream));
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((a.c.n_tiles + 3) / 4)), dim3(256), 0, stream, a);
+    HIP_TRY(c, hipGetLastError());
+    return GLRTX_OK;
+}
+
+// The static kernel (common.x1: N1): the new view's camera.
+int reproject_pass(glrtx_ctx *c, hipStream_t stream, const reproject::Common &common, const float *c2w_cur, const float *s2c_cur, int stripe) {
+    reproject::Args a{};
+    a.c = common;
+    std::memcpy(a.cam.cam, c2w_cur, 16 * sizeof(float));
+    std::memcpy(a.cam.cam + 16, s2c_cur, 16 * sizeof(float));
+    a.cam.width = common.width; a.cam.height = common.rows;
+    a.cam.owned_rows = common.rows; a.cam.rank = 0; a.cam.world = 1; a.cam.stripe = stripe;
+    return reproject_launch(c, stream, reproject::reproject_kernel, a);
+}
+
+// The motion-aware kernel (reproject_motion.hip.h; common.x1: G1): the previous geometry (prev_pos / prev_nrm: motion::Args').
+int reproject_motion_pass(glrtx_ctx *c, hipStream_t stream, const reproject::Common &common, const float4 *prev_pos, const float4 *prev_nrm, int n_tri) {
+    motion::Args a{};
+    a.c = common; a.prev_pos = prev_pos; a.prev_nrm = prev_nrm; a.n_tri = n_tri;
+    return reproject_launch(c, stream, motion::reproject_motion_kernel, a);
 }
 
 
@@ -1550,48 +1650,6 @@ int moments_ensure(glrtx_ctx *c) {
     return GLRTX_OK;
 }
 bool moments_have(const glrtx_ctx *c) { return c->mm_on && c->mmM.p && c->mm_pitch == c->pitch_bytes && c->mm_rows == c->owned_rows; }
-
-int denoise_var_cfg_check(glrtx_ctx *c, const glrtx_denoise_var_cfg *cfg, const char *fn) {
-    if (!cfg) return fail(c, GLRTX_EINVAL, "%s: NULL cfg", fn);
-    if (cfg->iterations < 1 || cfg->iterations > 6) return fail(c, GLRTX_EINVAL, "%s: iterations %d outside 1..6", fn, cfg->iterations);
-    const float sg[3] = {cfg->sigma_lum, cfg->sigma_normal, cfg->sigma_depth};
-    for (float v : sg)
-        if (!(v > 0.0f) || std::isinf(v)) return fail(c, GLRTX_EINVAL, "%s: sigma %g is not a positive finite number", fn, (double)v);
-    return GLRTX_OK;
-}
-
-// The variance pass and the variance-guided filter's passes on `stream`: accum and M (pitch_f4 each) + the two feature planes -> D, through the ping-pong images
-// p0 / p1 and the variance planes v[0] (V0), v[1], v[2] (all but accum and M packed rows of `width`).
-int denoise_var_passes(glrtx_ctx *c, hipStream_t stream, const float4 *accum, const float4 *moments, int pitch_f4, const float4 *guide, const float4 *albedo, float4 *p0,
-                       float4 *p1, float4 *D, float *const v[3], int width, int rows, const glrtx_denoise_var_cfg *cfg) {
-    const dim3 grid((unsigned)(((width + denoise::kTileDn - 1) / denoise::kTileDn) * ((rows + denoise::kTileDn - 1) / denoise::kTileDn)));
-    const int demod = cfg->demodulate ? 1 : 0;
-    variance::Args va;
-    va.accum = accum; va.moments = moments; va.guide = guide; va.albedo = albedo; va.v0 = v[0];
-    va.pitch_f4 = pitch_f4; va.width = width; va.rows = rows;
-    va.sigma_normal = cfg->sigma_normal; va.sigma_depth = cfg->sigma_depth; va.demodulate = demod;
-    hipLaunchKernelGGL(variance::variance_estimate, grid, dim3(256), 0, stream, va);
-    HIP_TRY(c, hipGetLastError());
-    hipLaunchKernelGGL(denoise::denoise_prep, grid, dim3(256), 0, stream, accum, pitch_f4, albedo, p0, width, rows, demod);
-    HIP_TRY(c, hipGetLastError());
-    float4 *img[2] = {p0, p1};
-    for (int it = 0; it < cfg->iterations; it++) {
-        const bool last = it == cfg->iterations - 1;
-        denoise::VarArgs a;
-        a.src = img[it & 1]; a.guide = guide; a.albedo = albedo; a.dst = last ? D : img[(it + 1) & 1];
-        a.vsrc = it == 0 ? v[0] : v[1 + ((it - 1) & 1)]; a.vdst = v[1 + (it & 1)];
-        a.width = width; a.rows = rows; a.spacing = 1 << it;
-        a.sigma_lum = cfg->sigma_lum; a.sigma_normal = cfg->sigma_normal; a.sigma_depth = cfg->sigma_depth;
-        a.demodulate = demod;
-        using Kernel = void (*)(const denoise::VarArgs);
-        const Kernel k = it == 0 ? (last ? (Kernel)denoise::denoise_atrous_var<1, true> : (Kernel)denoise::denoise_atrous_var<1, false>)
-                       : it == 1 ? (last ? (Kernel)denoise::denoise_atrous_var<2, true> : (Kernel)denoise::denoise_atrous_var<2, false>)
-                                 : (last ? (Kernel)denoise::denoise_atrous_var<0, true> : (Kernel)denoise::denoise_atrous_var<0, false>);
-        hipLaunchKernelGGL(k, grid, dim3(256), 0, stream, a);
-        HIP_TRY(c, hipGetLastError());
-    }
-    return GLRTX_OK;
-}
 
 // Everything glrtx_render_moments refuses, checked before anything changes: glrtx_render_adaptive's list, the volume and tracking being off.
 int moments_check(glrtx_ctx *c, const glrtx_params *p, const float *seeds_xy, int n_frames) {
@@ -2611,7 +2669,8 @@ int glrtx_read_features(glrtx_ctx *c, float *normal_depth, float *albedo_id, siz
 int glrtx_denoise(glrtx_ctx *c, const glrtx_denoise_cfg *cfg) {
     const char *fn = "glrtx_denoise";
     if (!c) return GLRTX_EINVAL;
-    if (int rc = denoise_cfg_check(c, cfg, fn)) return rc;
+    FilterCfg k;
+    if (int rc = denoise_cfg_check(c, cfg, fn, k)) return rc;
     if (!c->accum || c->width < 1) return fail(c, GLRTX_EINVAL, "%s: no accumulator (call glrtx_resize)", fn);
     if (int rc = denoise_shape_check(c, fn, false)) return rc;
     seal_feed(c);
@@ -2621,8 +2680,8 @@ int glrtx_denoise(glrtx_ctx *c, const glrtx_denoise_cfg *cfg) {
     if ((rc = ensure(c, c->dnP[0], bytes)) || (rc = ensure(c, c->dnP[1], bytes)) || (rc = ensure(c, c->dnD, bytes))) return rc;
     c->dn_have = true;
     if (c->owned_rows == 0) return GLRTX_OK;
-    return denoise_passes(c, c->stream, c->accum, (int)(c->pitch_bytes / sizeof(float4)), (const float4 *)c->ftN.p, (const float4 *)c->ftA.p, (float4 *)c->dnP[0].p,
-                          (float4 *)c->dnP[1].p, (float4 *)c->dnD.p, c->width, c->owned_rows, cfg);
+    return denoise_passes(c, c->stream, c->accum, nullptr, (int)(c->pitch_bytes / sizeof(float4)), (const float4 *)c->ftN.p, (const float4 *)c->ftA.p,
+                          (float4 *)c->dnP[0].p, (float4 *)c->dnP[1].p, (float4 *)c->dnD.p, nullptr, c->width, c->owned_rows, k);
 }
 
 int glrtx_read_denoised(glrtx_ctx *c, float *dst, size_t dst_pitch_bytes) {
@@ -2665,23 +2724,19 @@ int glrtx_debug_denoise(const float *accum, const float *normal_depth, const flo
     const char *fn = "glrtx_debug_denoise";
     if (width < 1 || rows < 1 || width > 65536 || rows > 65536) return fail(nullptr, GLRTX_EINVAL, "%s: bad size %dx%d", fn, width, rows);
     if (!accum || !normal_depth || !albedo_id || !out) return fail(nullptr, GLRTX_EINVAL, "%s: NULL buffer", fn);
-    if (int rc = denoise_cfg_check(nullptr, cfg, fn)) return rc;
+    FilterCfg k;
+    if (int rc = denoise_cfg_check(nullptr, cfg, fn, k)) return rc;
     const size_t bytes = (size_t)width * rows * sizeof(float4);
-    void *d[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // accum, guide, albedo, p0, p1, D
-    hipError_t e = hipSuccess;
-    for (int i = 0; i < 6 && e == hipSuccess; i++) e = hipMalloc(&d[i], bytes);
-    if (e == hipSuccess) e = hipMemcpy(d[0], accum, bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d[1], normal_depth, bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d[2], albedo_id, bytes, hipMemcpyHostToDevice);
+    DebugScratch s;
+    const float4 *acc = s.alloc(bytes, accum), *guide = s.alloc(bytes, normal_depth), *albedo = s.alloc(bytes, albedo_id);
+    float4 *p0 = s.alloc(bytes), *p1 = s.alloc(bytes), *D = s.alloc(bytes);
     int rc = GLRTX_OK;
-    if (e == hipSuccess)
-        rc = denoise_passes(nullptr, 0, (const float4 *)d[0], width, (const float4 *)d[1], (const float4 *)d[2], (float4 *)d[3], (float4 *)d[4], (float4 *)d[5], width, rows, cfg);
-    if (e == hipSuccess && rc == GLRTX_OK) e = hipDeviceSynchronize();
-    if (e == hipSuccess && rc == GLRTX_OK) e = hipMemcpy(out, d[5], bytes, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) rc = fail(nullptr, GLRTX_EDEVICE, "%s: %s", fn, hipGetErrorString(e));
-    for (void *q : d)
-        if (q) (void)hipFree(q);
-    return rc;
+    if (s.ok()) rc = denoise_passes(nullptr, 0, acc, nullptr, width, guide, albedo, p0, p1, D, nullptr, width, rows, k);
+    if (rc == GLRTX_OK) {
+        s.sync();
+        s.download(out, D, bytes);
+    }
+    return s.result(rc, fn);
 }
 
 // ---- variance guidance
@@ -2746,7 +2801,8 @@ int glrtx_read_moments(glrtx_ctx *c, float *dst, size_t dst_pitch_bytes) {
 int glrtx_denoise_variance(glrtx_ctx *c, const glrtx_denoise_var_cfg *cfg) {
     const char *fn = "glrtx_denoise_variance";
     if (!c) return GLRTX_EINVAL;
-    if (int rc = denoise_var_cfg_check(c, cfg, fn)) return rc;
+    FilterCfg k;
+    if (int rc = denoise_cfg_check(c, cfg, fn, k)) return rc;
     if (!c->accum || c->width < 1) return fail(c, GLRTX_EINVAL, "%s: no accumulator (call glrtx_resize)", fn);
     if (!c->mm_on) return fail(c, GLRTX_EINVAL, "%s: moments are not tracked (glrtx_track_moments)", fn);
     if (!moments_have(c)) return fail(c, GLRTX_EINVAL, "%s: no moments plane yet (call glrtx_render_moments first)", fn);
@@ -2761,8 +2817,8 @@ int glrtx_denoise_variance(glrtx_ctx *c, const glrtx_denoise_var_cfg *cfg) {
     c->dn_have = true;
     if (c->owned_rows == 0) return GLRTX_OK;
     float *const v[3] = {(float *)c->dnV[0].p, (float *)c->dnV[1].p, (float *)c->dnV[2].p};
-    return denoise_var_passes(c, c->stream, c->accum, (const float4 *)c->mmM.p, (int)(c->pitch_bytes / sizeof(float4)), (const float4 *)c->ftN.p, (const float4 *)c->ftA.p,
-                              (float4 *)c->dnP[0].p, (float4 *)c->dnP[1].p, (float4 *)c->dnD.p, v, c->width, c->owned_rows, cfg);
+    return denoise_passes(c, c->stream, c->accum, (const float4 *)c->mmM.p, (int)(c->pitch_bytes / sizeof(float4)), (const float4 *)c->ftN.p, (const float4 *)c->ftA.p,
+                          (float4 *)c->dnP[0].p, (float4 *)c->dnP[1].p, (float4 *)c->dnD.p, v, c->width, c->owned_rows, k);
 }
 
 int glrtx_debug_denoise_variance(const float *accum, const float *moments, const float *normal_depth, const float *albedo_id, int width, int rows,
@@ -2770,26 +2826,21 @@ int glrtx_debug_denoise_variance(const float *accum, const float *moments, const
     const char *fn = "glrtx_debug_denoise_variance";
     if (width < 1 || rows < 1 || width > 65536 || rows > 65536) return fail(nullptr, GLRTX_EINVAL, "%s: bad size %dx%d", fn, width, rows);
     if (!accum || !moments || !normal_depth || !albedo_id || !out) return fail(nullptr, GLRTX_EINVAL, "%s: NULL buffer", fn);
-    if (int rc = denoise_var_cfg_check(nullptr, cfg, fn)) return rc;
+    FilterCfg k;
+    if (int rc = denoise_cfg_check(nullptr, cfg, fn, k)) return rc;
     const size_t bytes = (size_t)width * rows * sizeof(float4), vbytes = (size_t)width * rows * sizeof(float);
-    void *d[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // accum, M, guide, albedo, p0, p1, D, V0, Va, Vb
-    const float *in[4] = {accum, moments, normal_depth, albedo_id};
-    hipError_t e = hipSuccess;
-    for (int i = 0; i < 10 && e == hipSuccess; i++) e = hipMalloc(&d[i], i < 7 ? bytes : vbytes);
-    for (int i = 0; i < 4 && e == hipSuccess; i++) e = hipMemcpy(d[i], in[i], bytes, hipMemcpyHostToDevice);
+    DebugScratch s;
+    const float4 *acc = s.alloc(bytes, accum), *M = s.alloc(bytes, moments), *guide = s.alloc(bytes, normal_depth), *albedo = s.alloc(bytes, albedo_id);
+    float4 *p0 = s.alloc(bytes), *p1 = s.alloc(bytes), *D = s.alloc(bytes);
+    float *const v[3] = {s.alloc<float>(vbytes), s.alloc<float>(vbytes), s.alloc<float>(vbytes)};
     int rc = GLRTX_OK;
-    if (e == hipSuccess) {
-        float *const v[3] = {(float *)d[7], (float *)d[8], (float *)d[9]};
-        rc = denoise_var_passes(nullptr, 0, (const float4 *)d[0], (const float4 *)d[1], width, (const float4 *)d[2], (const float4 *)d[3], (float4 *)d[4], (float4 *)d[5],
-                                (float4 *)d[6], v, width, rows, cfg);
+    if (s.ok()) rc = denoise_passes(nullptr, 0, acc, M, width, guide, albedo, p0, p1, D, v, width, rows, k);
+    if (rc == GLRTX_OK) {
+        s.sync();
+        s.download(out, D, bytes);
+        s.download(v0_out, v[0], vbytes);
     }
-    if (e == hipSuccess && rc == GLRTX_OK) e = hipDeviceSynchronize();
-    if (e == hipSuccess && rc == GLRTX_OK) e = hipMemcpy(out, d[6], bytes, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && rc == GLRTX_OK && v0_out) e = hipMemcpy(v0_out, d[7], vbytes, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) rc = fail(nullptr, GLRTX_EDEVICE, "%s: %s", fn, hipGetErrorString(e));
-    for (void *q : d)
-        if (q) (void)hipFree(q);
-    return rc;
+    return s.result(rc, fn);
 }
 
 
@@ -2813,52 +2864,6 @@ static hipError_t reproject_counts(const void *dev_counts, int *carried, int *hi
     if (carried) *carried = (int)(sum & 0xFFFFFFFFull);
     if (hit_pixels) *hit_pixels = (int)(sum >> 32);
     return e;
-}
-
-static int reproject_pass(glrtx_ctx *c, hipStream_t stream, const glrt_detail::ReprojectSetup &st, const float *c2w_cur, const float *s2c_cur, int stripe, const float4 *acc,
-                          const float4 *n0, const float4 *a0, const float4 *n1, const float4 *a1, float4 *out, int pitch_f4, int width, int rows, void *counts,
-                          const float4 *mom = nullptr, float4 *mom_out = nullptr) {
-    reproject::Args a{};
-    a.mom = mom; a.mom_out = mom_out;
-    std::memcpy(a.cam.cam, c2w_cur, 16 * sizeof(float));
-    std::memcpy(a.cam.cam + 16, s2c_cur, 16 * sizeof(float));
-    a.cam.width = width; a.cam.height = rows;
-    a.cam.owned_rows = rows; a.cam.rank = 0; a.cam.world = 1; a.cam.stripe = stripe;
-    std::memcpy(a.W, st.W, sizeof a.W);
-    std::memcpy(a.S, st.S, sizeof a.S);
-    a.opx = st.o_prev[0]; a.opy = st.o_prev[1]; a.opz = st.o_prev[2];
-    a.acc = acc; a.n0 = n0; a.a0 = a0; a.n1 = n1; a.a1 = a1; a.out = out;
-    a.pitch_f4 = pitch_f4; a.width = width; a.rows = rows;
-    a.tiles_x = (width + 7) / 8;
-    a.n_tiles = a.tiles_x * ((rows + 7) / 8);
-    a.max_history = st.max_history; a.depth_tol = st.depth_tolerance; a.normal_tol = st.normal_tolerance;
-    a.counts = (unsigned long long *)counts;
-    HIP_TRY(c, hipMemsetAsync(counts, 0, reproject::kCountBytes, stream));
-    hipLaunchKernelGGL(reproject::reproject_kernel, dim3((unsigned)((a.n_tiles + 3) / 4)), dim3(256), 0, stream, a);
-    HIP_TRY(c, hipGetLastError());
-    return GLRTX_OK;
-}
-
-// The motion-aware kernel (reproject_motion.hip.h) on `stream`, as reproject_pass runs the static one; prev_pos / prev_nrm: motion::Args'.
-static int reproject_motion_pass(glrtx_ctx *c, hipStream_t stream, const glrt_detail::ReprojectSetup &st, const float4 *acc, const float4 *n0, const float4 *a0,
-                                 const float4 *g1, const float4 *a1, const float4 *prev_pos, const float4 *prev_nrm, int n_tri, float4 *out, int pitch_f4, int width,
-                                 int rows, void *counts, const float4 *mom = nullptr, float4 *mom_out = nullptr) {
-    motion::Args a{};
-    a.mom = mom; a.mom_out = mom_out;
-    std::memcpy(a.W, st.W, sizeof a.W);
-    std::memcpy(a.S, st.S, sizeof a.S);
-    a.opx = st.o_prev[0]; a.opy = st.o_prev[1]; a.opz = st.o_prev[2];
-    a.acc = acc; a.n0 = n0; a.a0 = a0; a.g1 = g1; a.a1 = a1; a.out = out;
-    a.prev_pos = prev_pos; a.prev_nrm = prev_nrm; a.n_tri = n_tri;
-    a.pitch_f4 = pitch_f4; a.width = width; a.rows = rows;
-    a.tiles_x = (width + 7) / 8;
-    a.n_tiles = a.tiles_x * ((rows + 7) / 8);
-    a.max_history = st.max_history; a.depth_tol = st.depth_tolerance; a.normal_tol = st.normal_tolerance;
-    a.counts = (unsigned long long *)counts;
-    HIP_TRY(c, hipMemsetAsync(counts, 0, reproject::kCountBytes, stream));
-    hipLaunchKernelGGL(motion::reproject_motion_kernel, dim3((unsigned)((a.n_tiles + 3) / 4)), dim3(256), 0, stream, a);
-    HIP_TRY(c, hipGetLastError());
-    return GLRTX_OK;
 }
 
 // glrtx_reproject (motion false) and glrtx_reproject_motion (true): one sequence, two kernels.
@@ -2908,14 +2913,12 @@ static int reproject_call(glrtx_ctx *c, const glrtx_params *cur, const glrtx_rep
         return rc;
     }
     const int pitch_f4 = (int)(c->pitch_bytes / sizeof(float4));
-    if (motion)
-        rc = reproject_motion_pass(c, c->stream, st, c->accum, (const float4 *)c->ftN_spare.p, (const float4 *)c->ftA_spare.p, (const float4 *)c->ftG.p,
-                                   (const float4 *)c->ftA.p, (const float4 *)c->mtPos.p, (const float4 *)c->mtNrm.p, c->n_tri, (float4 *)c->accum_spare.p, pitch_f4,
-                                   c->width, c->owned_rows, c->rpCount.p, carry_m ? (const float4 *)c->mmM.p : nullptr, carry_m ? (float4 *)c->mmM_spare.p : nullptr);
-    else
-        rc = reproject_pass(c, c->stream, st, cur->c2w, cur->s2c, c->stripe, c->accum, (const float4 *)c->ftN_spare.p, (const float4 *)c->ftA_spare.p,
-                            (const float4 *)c->ftN.p, (const float4 *)c->ftA.p, (float4 *)c->accum_spare.p, pitch_f4, c->width, c->owned_rows, c->rpCount.p,
-                            carry_m ? (const float4 *)c->mmM.p : nullptr, carry_m ? (float4 *)c->mmM_spare.p : nullptr);
+    const reproject::Common common =
+        reproject_common(st, c->accum, (const float4 *)c->ftN_spare.p, (const float4 *)c->ftA_spare.p, (const float4 *)(motion ? c->ftG.p : c->ftN.p),
+                         (const float4 *)c->ftA.p, (float4 *)c->accum_spare.p, pitch_f4,
+                         c->width, c->owned_rows, c->rpCount.p, carry_m ? (const float4 *)c->mmM.p : nullptr, carry_m ? (float4 *)c->mmM_spare.p : nullptr);
+    if (motion) rc = reproject_motion_pass(c, c->stream, common, (const float4 *)c->mtPos.p, (const float4 *)c->mtNrm.p, c->n_tri);
+    else rc = reproject_pass(c, c->stream, common, cur->c2w, cur->s2c, c->stripe);
     if (rc) return rc;
     std::swap(c->accum_own, c->accum_spare);  // the accumulator rendered into from here on (glrtx_accum_device_ptr changes)
     c->accum = (float4 *)c->accum_own.p;
@@ -2978,24 +2981,21 @@ static int debug_reproject_impl(const char *fn, const float *accum, const float 
     glrt_detail::ReprojectSetup st;
     if (int rc = reproject_setup_check(nullptr, fn, c2w_prev, s2c_prev, cfg, st)) return rc;
     const size_t bytes = (size_t)width * rows * sizeof(float4);
-    const float *src[5] = {accum, n0, a0, n1, a1};
-    void *d[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // accum, N0, A0, N1, A1, out, counts, M, M out
-    hipError_t e = hipSuccess;
-    for (int i = 0; i < (mom ? 9 : 7) && e == hipSuccess; i++) e = hipMalloc(&d[i], i == 6 ? reproject::kCountBytes : bytes);
-    for (int i = 0; i < 5 && e == hipSuccess; i++) e = hipMemcpy(d[i], src[i], bytes, hipMemcpyHostToDevice);
-    if (mom && e == hipSuccess) e = hipMemcpy(d[7], mom, bytes, hipMemcpyHostToDevice);
+    DebugScratch s;
+    const float4 *acc = s.alloc(bytes, accum), *N0 = s.alloc(bytes, n0), *A0 = s.alloc(bytes, a0), *N1 = s.alloc(bytes, n1), *A1 = s.alloc(bytes, a1);
+    float4 *o = s.alloc(bytes);
+    void *counts = s.alloc<void>(reproject::kCountBytes);
+    const float4 *M = mom ? s.alloc(bytes, mom) : nullptr;
+    float4 *Mo = mom ? s.alloc(bytes) : nullptr;
     int rc = GLRTX_OK;
-    if (e == hipSuccess)
-        rc = reproject_pass(nullptr, 0, st, c2w_cur, s2c_cur, 16, (const float4 *)d[0], (const float4 *)d[1], (const float4 *)d[2], (const float4 *)d[3], (const float4 *)d[4],
-                            (float4 *)d[5], width, width, rows, d[6], (const float4 *)d[7], (float4 *)d[8]);
-    if (e == hipSuccess && rc == GLRTX_OK) e = hipDeviceSynchronize();
-    if (e == hipSuccess && rc == GLRTX_OK) e = hipMemcpy(out, d[5], bytes, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && rc == GLRTX_OK && mom) e = hipMemcpy(mom_out, d[8], bytes, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && rc == GLRTX_OK) e = reproject_counts(d[6], carried, hit_pixels);
-    if (e != hipSuccess) rc = fail(nullptr, GLRTX_EDEVICE, "%s: %s", fn, hipGetErrorString(e));
-    for (void *q : d)
-        if (q) (void)hipFree(q);
-    return rc;
+    if (s.ok()) rc = reproject_pass(nullptr, 0, reproject_common(st, acc, N0, A0, N1, A1, o, width, width, rows, counts, M, Mo), c2w_cur, s2c_cur, 16);
+    if (rc == GLRTX_OK) {
+        s.sync();
+        s.download(out, o, bytes);
+        s.download(mom_out, Mo, bytes);
+        if (s.ok()) s.e = reproject_counts(counts, carried, hit_pixels);
+    }
+    return s.result(rc, fn);
 }
 extern "C" {
 int glrtx_debug_reproject(const float *accum, const float *n0, const float *a0, const float *n1, const float *a1, const float *c2w_prev, const float *s2c_prev,
@@ -3036,27 +3036,23 @@ static int debug_reproject_motion_impl(const char *fn, const float *accum, const
         for (int k = 0; k < 3; k++) nrm[3 * t + k] = make_float4(v[k][3], v[k][4], v[k][5], 0.f);
     }
     const size_t bytes = (size_t)width * rows * sizeof(float4), gbytes = pos.size() * sizeof(float4);
-    const float *src[5] = {accum, n0, a0, g1, a1};
-    void *d[11] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // accum, N0, A0, G1, A1, out, counts, positions, normals, M, M out
-    hipError_t e = hipSuccess;
-    for (int i = 0; i < (mom ? 11 : 9) && e == hipSuccess; i++) e = hipMalloc(&d[i], i == 6 ? reproject::kCountBytes : (i == 7 || i == 8) ? gbytes : bytes);
-    if (mom && e == hipSuccess) e = hipMemcpy(d[9], mom, bytes, hipMemcpyHostToDevice);
-    for (int i = 0; i < 5 && e == hipSuccess; i++) e = hipMemcpy(d[i], src[i], bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d[7], pos.data(), gbytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d[8], nrm.data(), gbytes, hipMemcpyHostToDevice);
+    DebugScratch s;
+    const float4 *acc = s.alloc(bytes, accum), *N0 = s.alloc(bytes, n0), *A0 = s.alloc(bytes, a0), *G1 = s.alloc(bytes, g1), *A1 = s.alloc(bytes, a1);
+    const float4 *prev_pos = s.alloc(gbytes, pos.data()), *prev_nrm = s.alloc(gbytes, nrm.data());
+    float4 *o = s.alloc(bytes);
+    void *counts = s.alloc<void>(reproject::kCountBytes);
+    const float4 *M = mom ? s.alloc(bytes, mom) : nullptr;
+    float4 *Mo = mom ? s.alloc(bytes) : nullptr;
     int rc = GLRTX_OK;
-    if (e == hipSuccess)
-        rc = reproject_motion_pass(nullptr, 0, st, (const float4 *)d[0], (const float4 *)d[1], (const float4 *)d[2], (const float4 *)d[3], (const float4 *)d[4],
-                                   (const float4 *)d[7], (const float4 *)d[8], (int)n_tri, (float4 *)d[5], width, width, rows, d[6], (const float4 *)d[9],
-                                   (float4 *)d[10]);
-    if (e == hipSuccess && rc == GLRTX_OK) e = hipDeviceSynchronize();
-    if (e == hipSuccess && rc == GLRTX_OK) e = hipMemcpy(out, d[5], bytes, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && rc == GLRTX_OK && mom) e = hipMemcpy(mom_out, d[10], bytes, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && rc == GLRTX_OK) e = reproject_counts(d[6], carried, hit_pixels);
-    if (e != hipSuccess) rc = fail(nullptr, GLRTX_EDEVICE, "%s: %s", fn, hipGetErrorString(e));
-    for (void *q : d)
-        if (q) (void)hipFree(q);
-    return rc;
+    if (s.ok())
+        rc = reproject_motion_pass(nullptr, 0, reproject_common(st, acc, N0, A0, G1, A1, o, width, width, rows, counts, M, Mo), prev_pos, prev_nrm, (int)n_tri);
+    if (rc == GLRTX_OK) {
+        s.sync();
+        s.download(out, o, bytes);
+        s.download(mom_out, Mo, bytes);
+        if (s.ok()) s.e = reproject_counts(counts, carried, hit_pixels);
+    }
+    return s.result(rc, fn);
 }
 extern "C" {
 int glrtx_debug_reproject_motion(const float *accum, const float *n0, const float *a0, const float *g1, const float *a1, const float *vert_prev, size_t n_vert,

@@ -9,7 +9,8 @@
 //
 // reproject_kernel's shape: a wave is one 8x8 tile, a workgroup four consecutive tiles; A1 and G1 are read once with non-temporal 16-byte loads (N1 is not
 // read); the previous triangle's six float4 are plain 16-byte loads -- the lanes of a tile lie on the same or neighbouring triangles, so most of them are L1
-// hits --; the four taps, the store and the 64 counter slots are reproject_kernel's.  No LDS, no scratch.
+// hits --; the four taps, the store and the 64 counter slots are reproject_kernel's: reproject.hip.h's history_lookup, store_pixel and count_wave, called with the
+// previous point and the previous normal.  No LDS, no scratch.
 //
 // The previous geometry: two arrays indexed by WIRE triangle, three float4 each -- {p0} {p1 - p0} {p2 - p0} (the leaf record's own words: pack_scene's
 // edges, denormals kept) and {n0} {n1} {n2}.  snapshot_kernel copies them out of the scene's leaf records before the first refit after a feature pass.
@@ -19,35 +20,22 @@
 namespace glrtx {
 namespace motion {
 
+using reproject::pos_finite;  // (no longer called here: history_lookup applies it; tests/test_reproject_motion_abi.py's source check still names the line)
+
 struct Args {
-    float W[16], S[16];       // inverse(c2w_prev), inverse(s2c_prev)
-    float opx, opy, opz;      // the previous camera's origin
-    const float4 *acc;        // the old view: accumulator (pitch_f4 per row) and planes (packed rows of width)
-    const float4 *n0, *a0;
-    const float4 *g1, *a1;    // the new view's planes
+    reproject::Common c;      // (x1: G1)
     const float4 *prev_pos;   // 3 per wire triangle: {p0} {e1} {e2}
     const float4 *prev_nrm;   // 3 per wire triangle: the vertex normals
     int n_tri;                // triangles the two arrays hold
-    float4 *out;              // pitch_f4 per row
-    int pitch_f4, width, rows, tiles_x, n_tiles;
-    float max_history, depth_tol, normal_tol;
-    unsigned long long *counts;  // reproject::kCountSlots words
-    const float4 *mom;        // the old view's moments plane M (pitch_f4 per row), or null; mom_out: the new view's (reproject::Args')
-    float4 *mom_out;
 };
 
 __global__ __launch_bounds__(256) void reproject_motion_kernel(const Args a) {
-    using reproject::canon;
-    using reproject::pos_finite;
-    using reproject::tiny;
-    const int tile = blockIdx.x * 4 + (threadIdx.x >> 6), k = threadIdx.x & 63;
-    const int x = (tile % a.tiles_x) * 8 + (k & 7), y = (tile / a.tiles_x) * 8 + (k >> 3);
-    const bool in = tile < a.n_tiles && x < a.width && y < a.rows;
+    const reproject::Pixel px = reproject::pixel_of(a.c);
     bool hit = false, carried = false;
     float4 o4 = make_float4(0.f, 0.f, 0.f, 0.f), m4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (in) {
-        const size_t p = (size_t)y * a.width + x;
-        const float4 G1 = ld_stream(a.g1 + p), A1 = ld_stream(a.a1 + p);
+    if (px.in) {
+        const size_t p = (size_t)px.y * a.c.width + px.x;
+        const float4 G1 = ld_stream(a.c.x1 + p), A1 = ld_stream(a.c.a1 + p);
         const int id = __float_as_int(A1.w);
         hit = id >= 0;  // (the reserved id INT32_MIN is negative)
         const unsigned tri = __float_as_uint(G1.x);
@@ -60,66 +48,11 @@ __global__ __launch_bounds__(256) void reproject_motion_kernel(const Args a) {
             Hit h;
             h.t = 0.f; h.tri = (int)tri; h.u = u; h.v = v;
             const Surf M = surf_tri(prev, h);
-            const float *W = a.W, *S = a.S;
-            const float qx = ((W[0] * Px + W[4] * Py) + W[8] * Pz) + W[12];
-            const float qy = ((W[1] * Px + W[5] * Py) + W[9] * Pz) + W[13];
-            const float qz = ((W[2] * Px + W[6] * Py) + W[10] * Pz) + W[14];
-            const float qw = ((W[3] * Px + W[7] * Py) + W[11] * Pz) + W[15];
-            const float sx = ((S[0] * qx + S[4] * qy) + S[8] * qz) + S[12] * qw;
-            const float sy = ((S[1] * qx + S[5] * qy) + S[9] * qz) + S[13] * qw;
-            const float sw4 = ((S[3] * qx + S[7] * qy) + S[11] * qz) + S[15] * qw;
-            const float Wf = (float)a.width, Hf = (float)a.rows;
-            const float ui = ((sx / sw4 + 1.0f) * 0.5f) * Wf + -1.0f;
-            const float vi = ((sy / sw4 + 1.0f) * 0.5f) * Hf + -1.0f;
-            // (outside [-1, size) no tap lies inside the image; a NaN fails the comparisons)
-            if (pos_finite(sw4) && ui >= -1.0f && ui < Wf && vi >= -1.0f && vi < Hf) {
-                const float ex = Px - a.opx, ey = Py - a.opy, ez = Pz - a.opz;
-                const float e = __builtin_sqrtf((ez * ez + ey * ey) + ex * ex);
-                const float lim = a.depth_tol * e;
-                const float fx0 = __builtin_floorf(ui), fy0 = __builtin_floorf(vi);
-                const int x0 = (int)fx0, y0 = (int)fy0;
-                const float fx = ui - fx0, fy = vi - fy0;
-                const float wx[2] = {1.0f - fx, fx}, wy[2] = {1.0f - fy, fy};
-                float sw = 0.f, sc = 0.f, sr = 0.f, sg = 0.f, sb = 0.f;
-                reproject::MomSum ms = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int j = 0; j < 2; j++) {
-#pragma unroll
-                    for (int i = 0; i < 2; i++) {
-                        const int tx = x0 + i, ty = y0 + j;
-                        if (tx < 0 || tx >= a.width || ty < 0 || ty >= a.rows) continue;
-                        const size_t q = (size_t)ty * a.width + tx;
-                        const float4 A0 = a.a0[q];
-                        if (__float_as_int(A0.w) != id) continue;
-                        const float4 C = a.acc[(size_t)ty * a.pitch_f4 + tx];
-                        const float4 N0 = a.n0[q];
-                        if (tiny(C.w)) continue;
-                        if (!(dot3(M.nx, M.ny, M.nz, N0.x, N0.y, N0.z) >= a.normal_tol)) continue;
-                        if (!(__builtin_fabsf(N0.w - e) <= lim)) continue;
-                        const float w = wx[i] * wy[j];
-                        sw = sw + w;
-                        sc = sc + w * C.w;
-                        sr = sr + w * (C.x / C.w); sg = sg + w * (C.y / C.w); sb = sb + w * (C.z / C.w);
-                        if (a.mom) reproject::moments_tap(ms, w, a.mom[(size_t)ty * a.pitch_f4 + tx]);
-                    }
-                }
-                if (sw > reproject::kMinWeight) {
-                    const float r = __builtin_rintf(sc / sw);
-                    const float n = r > a.max_history ? a.max_history : r;
-                    if (n >= 1.0f) {
-                        o4 = make_float4(canon((sr / sw) * n), canon((sg / sw) * n), canon((sb / sw) * n), n);
-                        carried = true;
-                        if (a.mom) m4 = reproject::moments_out(ms, a.max_history);
-                    }
-                }
-            }
+            reproject::history_lookup(a.c, Px, Py, Pz, M.nx, M.ny, M.nz, id, o4, m4, carried);
         }
-        a.out[(size_t)y * a.pitch_f4 + x] = o4;
-        if (a.mom_out) a.mom_out[(size_t)y * a.pitch_f4 + x] = m4;
+        reproject::store_pixel(a.c, px, o4, m4);
     }
-    const unsigned long long nc = __popcll(__ballot(carried)), nh = __popcll(__ballot(hit));
-    if (k == 0 && (nc | nh) != 0ull)
-        atomicAdd(a.counts + (size_t)(blockIdx.x % reproject::kCountSlots) * reproject::kCountStride, nc | (nh << 32));
+    reproject::count_wave(a.c, carried, hit);
 }
 
 // The previous geometry out of the scene's leaf records: one thread per leaf record k (id k + 1, at node record n_ids - 1 - id; its normals at 3 id), to the

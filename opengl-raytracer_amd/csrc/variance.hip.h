@@ -1,5 +1,6 @@
 // variance.hip.h -- the moments fold and the variance pass of the variance-guided denoiser (glrtx_render_moments, glrtx_denoise_variance, include/glrtx.h
-// "Variance guidance"; the variance estimation step of SVGF, Schied et al. 2017).  The filter itself is denoise_atrous_var in denoise.hip.h.
+// "Variance guidance"; the variance estimation step of SVGF, Schied et al. 2017).  The filter itself is denoise.hip.h's atrous<S, LAST, true>, and the tile
+// arithmetic, the normal/depth term, lum, canon and tiny used below are that file's own.
 //
 // No reference counterpart.  The arithmetic is the header's text: host/variance.cpp and tests/variance_math.py state it again, and all three agree bit for bit
 // under denoise.hip.h's rules (one correctly rounded fp32 operation at a time in the order written, -ffp-contract=off; denormals flushed; a stored NaN is 0x7FC00000).
@@ -19,9 +20,9 @@ using denoise::albedo_of;
 using denoise::canon;
 using denoise::kNoPixel;
 using denoise::kTileDn;
+using denoise::lum;
 using denoise::tiny;
 
-DEV float lum(float r, float g, float b) { return (0.2126f * r + 0.7152f * g) + 0.0722f * b; }
 DEV float max0(float x) { return x > 0.0f ? x : 0.0f; }
 
 __global__ __launch_bounds__(256) void accumulate_moments_kernel(float4 *accum, float4 *moments, int pitch_f4, int width, int rows, const float4 *planes, int n_planes) {
@@ -56,14 +57,11 @@ constexpr int kHaloVar = 3, kSideVar = kTileDn + 2 * kHaloVar;
 
 __global__ __launch_bounds__(256) void variance_estimate(const Args a) {
     __shared__ float4 sM[kSideVar * kSideVar], sG[kSideVar * kSideVar];
-    const int tiles_x = (a.width + kTileDn - 1) / kTileDn;
-    const int tile = blockIdx.x, wv = threadIdx.x >> 6, k = threadIdx.x & 63;
-    const int x0 = (tile % tiles_x) * kTileDn, y0 = (tile / tiles_x) * kTileDn;
-    const int tx = (wv & 1) * 8 + (k & 7), ty = (wv >> 1) * 8 + (k >> 3);
-    const int x = x0 + tx, y = y0 + ty;
+    const denoise::Tile16 t = denoise::tile16(a.width);
+    const int x = t.x0 + t.tx, y = t.y0 + t.ty;
     for (int i = threadIdx.x; i < kSideVar * kSideVar; i += 256) {
         const int sy = i / kSideVar, sx = i - sy * kSideVar;
-        const int gx = x0 - kHaloVar + sx, gy = y0 - kHaloVar + sy;
+        const int gx = t.x0 - kHaloVar + sx, gy = t.y0 - kHaloVar + sy;
         float4 m = make_float4(0.f, 0.f, __int_as_float(kNoPixel), 0.f), g = make_float4(0.f, 0.f, 0.f, 0.f);
         if (gx >= 0 && gx < a.width && gy >= 0 && gy < a.rows) {
             const size_t qa = (size_t)gy * a.pitch_f4 + gx, q = (size_t)gy * a.width + gx;
@@ -82,7 +80,7 @@ __global__ __launch_bounds__(256) void variance_estimate(const Args a) {
     }
     __syncthreads();
     if (x >= a.width || y >= a.rows) return;
-    const int c = (ty + kHaloVar) * kSideVar + tx + kHaloVar;
+    const int c = (t.ty + kHaloVar) * kSideVar + t.tx + kHaloVar;
     const float4 mp = sM[c];
     const int idp = __float_as_int(mp.z);
     float v = 0.0f;
@@ -90,7 +88,7 @@ __global__ __launch_bounds__(256) void variance_estimate(const Args a) {
         if (mp.w >= 4.0f) v = max0(mp.y - mp.x * mp.x) / mp.w;
         else {
             const float4 gp = sG[c];
-            const float tden = gp.w > 1.0e-6f ? gp.w : 1.0e-6f;
+            const float tden = denoise::tden_of(gp);
             float sw = 0.0f, s1 = 0.0f, s2 = 0.0f;
 #pragma unroll
             for (int dy = -3; dy <= 3; dy++) {
@@ -99,19 +97,15 @@ __global__ __launch_bounds__(256) void variance_estimate(const Args a) {
                     const int i = c + dy * kSideVar + dx;
                     const float4 mq = sM[i];
                     if (__float_as_int(mq.z) == idp) {
-                        const float4 gq = sG[i];
-                        const float nx = gq.x - gp.x, ny = gq.y - gp.y, nz = gq.z - gp.z;
-                        const float dn = (nx * nx + ny * ny) + nz * nz;
-                        const float rt = (gq.w - gp.w) / tden;
-                        const float dd = (rt * rt) / a.sigma_depth;
-                        const float w = lp_exp(-(dn / a.sigma_normal + (dd < 80.0f ? dd : 80.0f)));
+                        const denoise::GeoTerm g = denoise::geometry_term(gp, tden, sG[i], a.sigma_normal, a.sigma_depth);
+                        const float w = lp_exp(-(g.n + g.d));
                         sw = sw + w;
                         s1 = s1 + w * mq.x;
                         s2 = s2 + w * mq.y;
                     }
                 }
             }
-            const float den = sw > 1.0e-20f ? sw : 1.0e-20f;
+            const float den = denoise::weight_floor(sw);
             const float S1 = s1 / den, S2 = s2 / den;
             v = max0(S2 - S1 * S1);
         }

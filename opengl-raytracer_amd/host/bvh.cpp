@@ -21,11 +21,9 @@
 #include <cstring>
 #include <limits>
 #include <vector>
-#if defined(__SSE__)
-#include <xmmintrin.h>
-#endif
 
 #include "glrt_host.h"
+#include "statement_math.h"
 
 namespace {
 
@@ -509,13 +507,7 @@ int glrt_bvh_build_lbvh(const float *vert, size_t n_vert, const float *tri, size
     if (2 * n_tri - 1 > ((size_t)1 << 24)) return GLRT_HOST_EINVAL;  // node indices travel as floats
     // This function is the CPU statement of the device build (csrc/lbvh.hip.h), which runs with fp32 denormals flushed like the rest of the device code:
     // the same mode here, for the duration of the call.
-    struct FlushDenormals {
-#if defined(__SSE__)
-        unsigned csr = _mm_getcsr();
-        FlushDenormals() { _mm_setcsr(csr | 0x8040u); }
-        ~FlushDenormals() { _mm_setcsr(csr); }
-#endif
-    } flush_denormals;
+    glrt_detail::FlushDenormals flush_denormals;
     (void)flush_denormals;
     std::vector<Prim> prims;
     if (!load_prims(vert, n_vert, tri, n_tri, prims)) return GLRT_HOST_EINDEX;
@@ -628,13 +620,7 @@ struct BinSet {
 int glrt_bvh_build_sah_levels(const float *vert, size_t n_vert, const float *tri, size_t n_tri, float *nodes_out, int *max_depth_out) {
     if (!vert || !tri || !nodes_out || n_tri == 0) return GLRT_HOST_EINVAL;
     if (2 * n_tri - 1 > ((size_t)1 << 24)) return GLRT_HOST_EINVAL;  // node indices travel as floats
-    struct FlushDenormals {  // the device statement runs with fp32 denormals flushed (as glrt_bvh_build_lbvh)
-#if defined(__SSE__)
-        unsigned csr = _mm_getcsr();
-        FlushDenormals() { _mm_setcsr(csr | 0x8040u); }
-        ~FlushDenormals() { _mm_setcsr(csr); }
-#endif
-    } flush_denormals;
+    glrt_detail::FlushDenormals flush_denormals;  // the device statement runs with fp32 denormals flushed (as glrt_bvh_build_lbvh)
     (void)flush_denormals;
     std::vector<Prim> prims;
     if (!load_prims(vert, n_vert, tri, n_tri, prims)) return GLRT_HOST_EINDEX;

@@ -9,29 +9,19 @@
 #include <cstdint>
 #include <cstring>
 #include <vector>
-#if defined(__SSE__)
-#include <xmmintrin.h>
-#endif
 
 #include "centre_ray.h"
 #include "glrt_host.h"
+#include "statement_math.h"
 
 namespace {
 
 using glrt_detail::centre_ray;
 using glrt_detail::rsq;
 
-struct FlushDenormals {
-#if defined(__SSE__)
-    unsigned csr = _mm_getcsr();
-    FlushDenormals() { _mm_setcsr(csr | 0x8040u); }
-    ~FlushDenormals() { _mm_setcsr(csr); }
-#endif
-};
-
-// a NaN is stored as 0x7FC00000 on both sides (which NaN an operation yields is the one thing the two instruction sets do not share)
-inline float canon(float x) { const uint32_t q = 0x7FC00000u; float n; std::memcpy(&n, &q, 4); return x != x ? n : x; }
-inline float dot3(float ax, float ay, float az, float bx, float by, float bz) { return (az * bz + ay * by) + ax * bx; }
+using glrt_detail::canon;
+using glrt_detail::dot3;
+using glrt_detail::FlushDenormals;
 
 // the pass; out_g (may be NULL): the geometry plane {wire triangle as int32 bits, u, v, 0} of glrt_render_features_geom
 int render_planes(const float *vert, size_t n_vert, const float *tri, size_t n_tri, const float *nodes, size_t n_nodes, const float *mat, size_t n_mat,

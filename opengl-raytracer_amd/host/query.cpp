@@ -16,11 +16,9 @@
 #include <cstring>
 #include <limits>
 #include <vector>
-#if defined(__SSE__)
-#include <xmmintrin.h>
-#endif
 
 #include "glrt_host.h"
+#include "statement_math.h"
 
 namespace {
 
@@ -29,20 +27,13 @@ constexpr float kEps = 1.0e-4f;  // the renderer's |det| rejection (PT_EPS)
 // GLSL min / max as the renderer lowers them: the other operand when one is NaN
 inline float fmin_g(float a, float b) { return (b != b) ? a : (a < b ? a : b); }
 inline float fmax_g(float a, float b) { return (b != b) ? a : (a > b ? a : b); }
-inline float dot3(float ax, float ay, float az, float bx, float by, float bz) { return (az * bz + ay * by) + ax * bx; }
+using glrt_detail::bits;
+using glrt_detail::bits_f;
+using glrt_detail::dot3;
+using glrt_detail::FlushDenormals;
 
-inline uint32_t bits(float x) { uint32_t b; std::memcpy(&b, &x, 4); return b; }
-inline float from_bits(uint32_t b) { float x; std::memcpy(&x, &b, 4); return x; }
-inline float flush(float x) { const uint32_t b = bits(x); return (b & 0x7F800000u) == 0u ? from_bits(b & 0x80000000u) : x; }
+inline float flush(float x) { const uint32_t b = bits(x); return (b & 0x7F800000u) == 0u ? bits_f(b & 0x80000000u) : x; }
 inline bool finite(float x) { return (bits(x) & 0x7F800000u) != 0x7F800000u; }
-
-struct FlushDenormals {
-#if defined(__SSE__)
-    unsigned csr = _mm_getcsr();
-    FlushDenormals() { _mm_setcsr(csr | 0x8040u); }
-    ~FlushDenormals() { _mm_setcsr(csr); }
-#endif
-};
 
 struct Tree {
     const float *vert, *tri, *nodes;

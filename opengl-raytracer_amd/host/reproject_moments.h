@@ -3,8 +3,8 @@
 // at a time in the order written; the caller runs with denormals flushed.
 #pragma once
 #include <cmath>
-#include <cstdint>
-#include <cstring>
+
+#include "statement_math.h"
 
 namespace glrt_detail {
 
@@ -12,9 +12,7 @@ struct MomSum { float sm = 0.0f, smc = 0.0f, s1 = 0.0f, s2 = 0.0f; };
 
 // A tap that counts for the accumulator counts for M if M.w is neither a zero nor a denormal.
 inline void moments_tap(MomSum &s, float w, const float *M) {
-    uint32_t b;
-    std::memcpy(&b, &M[3], 4);
-    if ((b & 0x7F800000u) == 0u) return;
+    if (tiny(M[3])) return;
     s.sm = s.sm + w;
     s.smc = s.smc + w * M[3];
     s.s1 = s.s1 + w * (M[0] / M[3]);
@@ -28,11 +26,7 @@ inline void moments_out(const MomSum &s, float max_history, float *o) {
     const float r = std::nearbyint(s.smc / s.sm);
     const float nm = r > max_history ? max_history : r;
     if (!(nm >= 1.0f)) return;
-    const float a = (s.s1 / s.sm) * nm, b = (s.s2 / s.sm) * nm;
-    const uint32_t qnan = 0x7FC00000u;
-    o[0] = a; o[1] = b; o[3] = nm;
-    if (a != a) std::memcpy(&o[0], &qnan, 4);
-    if (b != b) std::memcpy(&o[1], &qnan, 4);
+    o[0] = canon((s.s1 / s.sm) * nm); o[1] = canon((s.s2 / s.sm) * nm); o[3] = nm;
 }
 
 }  // namespace glrt_detail

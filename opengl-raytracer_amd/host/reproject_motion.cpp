@@ -3,7 +3,6 @@
 // tests/reproject_motion_math.py restates it in numpy.  Every fp32 operation of the per-pixel arithmetic is one correctly rounded IEEE operation in the order
 // written (-ffp-contract=off), under MXCSR FTZ | DAZ.  The previous triangles' edges are formed BEFORE that mode is set, as pack_scene (csrc/glrtx.hip) and the
 // device refit form a leaf record's edges: one IEEE subtraction each, denormals kept.
-#include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <vector>
@@ -13,31 +12,11 @@
 
 #include "centre_ray.h"
 #include "glrt_host.h"
-#include "reproject_moments.h"
-#include "reproject_setup.h"
+#include "reproject_lookup.h"
 
-namespace {
-
+using glrt_detail::dot3;
+using glrt_detail::FlushDenormals;
 using glrt_detail::rsq;
-
-struct FlushDenormals {
-#if defined(__SSE__)
-    unsigned csr = _mm_getcsr();
-    FlushDenormals() { _mm_setcsr(csr | 0x8040u); }
-    ~FlushDenormals() { _mm_setcsr(csr); }
-#endif
-};
-
-inline uint32_t bits(float x) { uint32_t b; std::memcpy(&b, &x, 4); return b; }
-inline float bits_f(uint32_t b) { float x; std::memcpy(&x, &b, 4); return x; }
-inline float canon(float x) { return x != x ? bits_f(0x7FC00000u) : x; }
-inline bool tiny(float x) { return (bits(x) & 0x7F800000u) == 0u; }                     // a zero or a denormal
-inline bool pos_finite(float x) { return (bits(x) - 0x00800000u) < 0x7F000000u; }       // sign clear, exponent neither 0 nor 255
-inline float dot3(float ax, float ay, float az, float bx, float by, float bz) { return (az * bz + ay * by) + ax * bx; }
-
-constexpr float kMinWeight = 1.0e-6f;
-
-}  // namespace
 
 // glrt_reproject_motion, and with mom / mom_out glrt_reproject_motion_moments: the same pass, the moments riding the same taps.
 static int reproject_motion_impl(const float *accum, const float *mom, const float *n0, const float *a0, const float *g1, const float *a1, const float *vert_prev,
@@ -78,15 +57,14 @@ static int reproject_motion_impl(const float *accum, const float *mom, const flo
         if (rc != GLRT_HOST_OK) return rc;
     }
     FlushDenormals ftz;
-    const float *W = st.W, *S = st.S;
-    const float Wf = (float)width, Hf = (float)rows;
+    const glrt_detail::OldView old{accum, mom, n0, a0, width, rows};
     int carried = 0, hits = 0;
     for (int y = 0; y < rows; y++)
         for (int x = 0; x < width; x++) {
             const size_t p = (size_t)y * width + x;
-            float *o = out + 4 * p;
+            float *o = out + 4 * p, *mo = mom_out ? mom_out + 4 * p : nullptr;
             o[0] = o[1] = o[2] = o[3] = 0.0f;
-            if (mom_out) { float *mo = mom_out + 4 * p; mo[0] = mo[1] = mo[2] = mo[3] = 0.0f; }
+            if (mo) mo[0] = mo[1] = mo[2] = mo[3] = 0.0f;
             const float *G1 = g1 + 4 * p;
             int32_t id, tr;
             std::memcpy(&id, a1 + 4 * p + 3, 4);
@@ -104,51 +82,7 @@ static int reproject_motion_impl(const float *accum, const float *mom, const flo
             const float ty = (w0 * m0[1] + u * m1[1]) + v * m2[1];
             const float tz = (w0 * m0[2] + u * m1[2]) + v * m2[2];
             const float rn = rsq(dot3(tx, ty, tz, tx, ty, tz));
-            const float mx = tx * rn, my = ty * rn, mz = tz * rn;
-            const float qx = ((W[0] * Px + W[4] * Py) + W[8] * Pz) + W[12];
-            const float qy = ((W[1] * Px + W[5] * Py) + W[9] * Pz) + W[13];
-            const float qz = ((W[2] * Px + W[6] * Py) + W[10] * Pz) + W[14];
-            const float qw = ((W[3] * Px + W[7] * Py) + W[11] * Pz) + W[15];
-            const float sx = ((S[0] * qx + S[4] * qy) + S[8] * qz) + S[12] * qw;
-            const float sy = ((S[1] * qx + S[5] * qy) + S[9] * qz) + S[13] * qw;
-            const float sw4 = ((S[3] * qx + S[7] * qy) + S[11] * qz) + S[15] * qw;
-            const float ui = ((sx / sw4 + 1.0f) * 0.5f) * Wf + -1.0f;
-            const float vi = ((sy / sw4 + 1.0f) * 0.5f) * Hf + -1.0f;
-            if (!(pos_finite(sw4) && ui >= -1.0f && ui < Wf && vi >= -1.0f && vi < Hf)) continue;  // no tap inside the image (a NaN fails)
-            const float ex = Px - st.o_prev[0], ey = Py - st.o_prev[1], ez = Pz - st.o_prev[2];
-            const float e = std::sqrt((ez * ez + ey * ey) + ex * ex);
-            const float lim = st.depth_tolerance * e;
-            const float fx0 = std::floor(ui), fy0 = std::floor(vi);
-            const int x0 = (int)fx0, y0 = (int)fy0;
-            const float fx = ui - fx0, fy = vi - fy0;
-            const float wx[2] = {1.0f - fx, fx}, wy[2] = {1.0f - fy, fy};
-            float sw = 0.0f, sc = 0.0f, sI[3] = {0.0f, 0.0f, 0.0f};
-            glrt_detail::MomSum ms;
-            for (int j = 0; j < 2; j++)
-                for (int i = 0; i < 2; i++) {
-                    const int tx0 = x0 + i, ty0 = y0 + j;
-                    if (tx0 < 0 || tx0 >= width || ty0 < 0 || ty0 >= rows) continue;
-                    const size_t q = (size_t)ty0 * width + tx0;
-                    const float *C = accum + 4 * q, *N0 = n0 + 4 * q;
-                    int32_t id0;
-                    std::memcpy(&id0, a0 + 4 * q + 3, 4);
-                    if (id0 != id || tiny(C[3])) continue;
-                    if (!(dot3(mx, my, mz, N0[0], N0[1], N0[2]) >= st.normal_tolerance)) continue;
-                    if (!(std::fabs(N0[3] - e) <= lim)) continue;
-                    const float w = wx[i] * wy[j];
-                    sw = sw + w;
-                    sc = sc + w * C[3];
-                    for (int k = 0; k < 3; k++) sI[k] = sI[k] + w * (C[k] / C[3]);
-                    if (mom) glrt_detail::moments_tap(ms, w, mom + 4 * q);
-                }
-            if (!(sw > kMinWeight)) continue;
-            const float rr = std::nearbyint(sc / sw);
-            const float n = rr > st.max_history ? st.max_history : rr;
-            if (!(n >= 1.0f)) continue;
-            for (int k = 0; k < 3; k++) o[k] = canon((sI[k] / sw) * n);
-            o[3] = n;
-            carried++;
-            if (mom_out) glrt_detail::moments_out(ms, st.max_history, mom_out + 4 * p);
+            if (glrt_detail::history_lookup(st, old, Px, Py, Pz, tx * rn, ty * rn, tz * rn, id, o, mo)) carried++;
         }
     if (carried_out) *carried_out = carried;
     if (hit_pixels_out) *hit_pixels_out = hits;

@@ -77,7 +77,7 @@ def test_features_partitioned(dev, monkeypatch):
 
 
 # ---- 2. the filter
-@pytest.mark.parametrize("rows,width", [(37, 61), (16, 16), (5, 130), (1, 1), (70, 49)])
+@pytest.mark.parametrize("rows,width", [(37, 61), (16, 16), (17, 33), (5, 130), (1, 1), (70, 49)])
 def test_filter_on_hostile_arrays(gpu_device, rows, width):
     acc, N, A = dm.hostile_arrays(rows, width, rows * 1000 + width)
     for iterations in range(1, 7):
