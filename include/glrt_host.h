@@ -190,6 +190,19 @@ int glrt_reproject_motion_moments(const float *accum, const float *moments, cons
                                   int rows, int max_history, float depth_tolerance, float normal_tolerance, float *out, float *moments_out, int *carried,
                                   int *hit_pixels);
 
+/* Tone mapping: the CPU statements of the device's glrtx_exposure_measure and of glrtx_tonemap / glrtx_resolve_tonemapped_rgba8 (include/glrtx.h "Tone mapping":
+ * the formulas are there), bit for bit (host/tonemap.cpp; tests/tonemap_math.py states them in numpy).  src: width x rows x 4 floats {rgb sum, count}, rows
+ * packed.  They run with denormals flushed (MXCSR FTZ | DAZ, restored on return).
+ *   glrt_exposure_measure   one measurement: hist_out (256 counts), counted = N, kept = K, mean_log2, target and the new E in exposure_out (each but hist_out may
+ *                           be NULL).  exposure_in: the previous E, or NULL for a first measurement (E = target).
+ *   glrt_tonemap            the curve with s = auto_exposure ? E * exposure : exposure into t_out (width x rows x 4 floats, {y, 1}), and the resolve of that
+ *                           plane -- clamp, gamma, rounding, rows flipped with flip_y -- into rgba8_out (width x rows x 4 bytes); either may be NULL.
+ * GLRT_HOST_EINVAL: a NULL src or hist_out, a size outside 1..65536, and what glrtx_tonemap_cfg's checks refuse (key, adapt, the window; op, exposure, white, gamma). */
+int glrt_exposure_measure(const float *src, int width, int rows, float key, int low_permille, int high_permille, float adapt, const float *exposure_in,
+                          uint32_t *hist_out, uint64_t *counted, uint64_t *kept, float *mean_log2, float *target, float *exposure_out);
+int glrt_tonemap(const float *src, int width, int rows, int op, int auto_exposure, float exposure, float E, float white, float gamma, int flip_y, float *t_out,
+                 uint8_t *rgba8_out);
+
 void glrt_look_at(const float eye[3], const float center[3], const float up[3], float out[16]);
 void glrt_perspective(float fovy_deg, float aspect, float z_near, float z_far, float out[16]);
 void glrt_mat4_mul(const float a[16], const float b[16], float out[16]);

@@ -677,6 +677,77 @@ int glrtx_debug_reproject_motion(const float *accum, const float *n0, const floa
                                  const float *tri, size_t n_tri, const float *c2w_prev, const float *s2c_prev, int width, int rows, const glrtx_reproject_cfg *cfg,
                                  float *out, int *carried, int *hit_pixels);
 
+/* ---- Tone mapping: a luminance histogram, an automatic exposure and a tone curve between the HDR buffers and a displayable image (no reference counterpart
+ * beyond op 0: the reference's screen.frag is clamp(mean, 0, 1) and a gamma curve; off unless called: no other call changes what it does, and nothing here ever
+ * writes the accumulator, the denoised image D, the moments, the adaptive half buffer, the present ring or the ray counts).  The SOURCE is the accumulator
+ * (source = 0) or D (source = 1; glrtx_denoise or glrtx_denoise_variance must have run at the image's current shape), over the context's owned rows taken as
+ * one image in local row order: a partitioned context measures and maps its own rows.  Every call here runs on the context's stream and seals an open fed launch
+ * first.  The context owns an exposure block in device memory (allocated by the first call here) -- the histogram and the exposure E -- and a float4 plane T
+ * (packed rows of `width`; allocated by the first glrtx_tonemap, released by glrtx_resize and so by a partition change; the exposure block survives both).
+ *   glrtx_exposure_measure   histogram and reduce, below; updates E on the device.  No host sync.
+ *   glrtx_exposure_reset     forgets E (stream-ordered): the next measurement jumps to its target, as the first one after glrtx_create does.
+ *   glrtx_read_exposure      syncs, then copies the block: the histogram, counted = N, kept = K, mean_log2, target, exposure = E of the LAST measurement, and
+ *                            the number of measurements since create / reset (0: nothing measured yet; hist and the rest are zeros, E counts as 1).
+ *   glrtx_tonemap            writes T = {y.rgb, 1}, below.  No host sync.  The kernel reads E in device memory: measure-then-map needs no host round trip.
+ *   glrtx_read_tonemapped    syncs, then copies T like glrtx_read_accum.  GLRTX_EINVAL before a glrtx_tonemap at the image's current shape.
+ *   glrtx_resolve_tonemapped_rgba8   source -> bytes in one pass (T is neither read nor written): the curve, then glrtx_resolve_rgba8's own arithmetic on {y, 1}
+ *                            with cfg's gamma and flip_y (flipped within the owned rows, as there).  Syncs and copies like glrtx_resolve_rgba8.
+ *   glrtx_debug_tonemap      all of it on caller arrays on the current HIP device, no context: src is width x rows float4, rows packed (cfg->source is not read).
+ *                            One measurement with *exposure_in as the previous E (NULL: there is none, the measurement is a first one), reported in exp_out
+ *                            (measurements = 1); then the curve with the E just measured into t_out (width x rows float4) and the fused kernel into rgba8_out
+ *                            (width x rows x 4 bytes).  exp_out, t_out and rgba8_out may each be NULL.
+ *   GLRTX_EINVAL, nothing changed (every call that takes a cfg checks all of it): a NULL cfg; op outside 0..2; source outside 0..1; exposure, key, white or gamma
+ *   that is not a positive finite number, or a white whose square is not a normal finite number; adapt outside (0, 1]; not 0 <= low_permille < high_permille
+ *   <= 1000; no accumulator; source = 1 without a denoised image of the current shape.
+ * The arithmetic (this text is the contract; glrt_exposure_measure / glrt_tonemap in glrt_host.h and tests/tonemap_math.py state it again, and the three agree
+ * bit for bit).  Every fp32 operation is one correctly rounded operation in the order written, unfused, denormals flushed on the way in and out (lp_exp and the
+ * resolve carry their own fused ones); min / max are selects as written.
+ *   Pixel value.  I = src.rgb / src.w, the IEEE quotient per channel.  A pixel is DEAD when src.w is a zero, a denormal or a NaN.
+ *   Histogram.  l = lum(I) = (0.2126 I.r + 0.7152 I.g) + 0.0722 I.b ("Variance guidance").  Not counted: dead pixels, and l that is NaN, +inf or <= 0 (after the
+ *     flush).  Otherwise k = clamp((bits(l) >> 20) - 888, 0, 255) in integer arithmetic on l's bit pattern: eight bins an octave from 2^-16 to 2^16, no
+ *     transcendental.  hist[k] is a uint32 count.
+ *   Reduce.  N = sum hist;  lo = N * low_permille / 1000 and hi = N * high_permille / 1000, floored uint64.  With c_k the exclusive prefix sum,
+ *     kept_k = max(0, min(c_k + hist[k], hi) - max(c_k, lo));  K = sum kept_k;  S = sum kept_k * (2 k + 1).
+ *     mean_log2 = (float)((double)S / (double)(16 K) - 16.0)    (IEEE double quotient and difference, one rounding to float: the mean of the kept pixels' bin centres)
+ *     target = key * lp_exp((0.0f - mean_log2) * 0x1.62e430p-1f)       lp_exp: the renderer's exponential (csrc/pt_kernel.hip.h)
+ *     With K = 0: mean_log2 = 0 and target = the previous E, or 1 if there is none.
+ *     The first measurement after glrtx_create / glrtx_exposure_reset sets E = target; later ones E = E + (target - E) * adapt.
+ *   Curve.  s = auto_exposure ? E * exposure : exposure  (E = 1 while nothing has been measured).  Per channel: x = I * s;  x = x > 0 ? x : 0 (a NaN becomes 0);
+ *     x = x < 65504 ? x : 65504;
+ *         op 0 (screen.frag's clamp)     y = x
+ *         op 1 (Reinhard extended)       y = (x * (1 + x / (white * white))) / (1 + x)
+ *         op 2 (ACES fit, Narkowicz)     y = (x * (2.51f * x + 0.03f)) / (x * (2.43f * x + 0.59f) + 0.14f)
+ *     A dead pixel gives y = {0, 0, 0}.  T = {y, 1}.
+ *   Bytes.  glrtx_resolve_tonemapped_rgba8 equals glrtx_resolve_rgba8's kernel applied to T, byte for byte (the resolve's clamp to [0, 1], gamma curve and
+ *     rounding).  It follows that op 0 with exposure = 1 and auto_exposure = 0 gives glrtx_resolve_rgba8's own bytes on any accumulator whose live pixels are
+ *     finite and whose dead pixels are zeros.
+ * Out of scope: the present ring and groups (no group call); a luminance-only curve (the curve is per channel, so saturated colours desaturate towards white);
+ * local operators. */
+typedef struct glrtx_tonemap_cfg {
+    int   op;             /* 0 = screen.frag's clamp, 1 = Reinhard extended, 2 = ACES fit (Narkowicz) */
+    int   source;         /* 0 = accumulator mean, 1 = denoised image D (glrtx_denoise / _variance must have run) */
+    int   auto_exposure;  /* 0: scale = exposure; 1: scale = E * exposure, E the context's measured exposure */
+    float exposure;       /* linear multiplier, > 0, default 1 */
+    float key;            /* default 0.18 */
+    int   low_permille, high_permille;   /* histogram window, 0 <= low < high <= 1000, default 500 / 950 */
+    float adapt;          /* (0, 1]: share of the way E moves towards its target per measurement; 1 jumps */
+    float white;          /* Reinhard white point, default 4 */
+    float gamma; int flip_y;
+} glrtx_tonemap_cfg;
+typedef struct glrtx_exposure { uint32_t hist[256]; uint64_t counted, kept; float mean_log2, target, exposure; int measurements; } glrtx_exposure;
+int glrtx_exposure_measure(glrtx_ctx *ctx, const glrtx_tonemap_cfg *cfg);
+int glrtx_exposure_reset(glrtx_ctx *ctx);
+int glrtx_read_exposure(glrtx_ctx *ctx, glrtx_exposure *out);
+int glrtx_tonemap(glrtx_ctx *ctx, const glrtx_tonemap_cfg *cfg);
+int glrtx_read_tonemapped(glrtx_ctx *ctx, float *dst_rgba, size_t dst_pitch_bytes);
+int glrtx_resolve_tonemapped_rgba8(glrtx_ctx *ctx, uint8_t *dst, size_t dst_pitch_bytes, const glrtx_tonemap_cfg *cfg);
+int glrtx_debug_tonemap(const float *src, int width, int rows, const glrtx_tonemap_cfg *cfg, const float *exposure_in, glrtx_exposure *exp_out, float *t_out,
+                        uint8_t *rgba8_out);
+/* Device time of one pass by itself, like glrtx_debug_resolve_burst: `reps` launches back to back between one pair of events after a warm-up pass, per launch.
+ * which: 0 glrtx_resolve_rgba8's kernel on the cfg's source (the yardstick, in the same run), 1 the fused tone-mapping resolve, 2 glrtx_tonemap's kernel, 3 one
+ * measurement (histogram + reduce; E moves as after that many measurements). */
+int glrtx_debug_tonemap_burst(glrtx_ctx *ctx, const glrtx_tonemap_cfg *cfg, int which, int reps, float *ms_per_launch);
+
 /* ---- Groups: the same device layer on several GPUs of one node, behind one handle and one host thread.
  * No reference counterpart (the reference is single-GPU); SURVEY.md 8(b) sketches glrtx_create(ctx**, device_ids, n) with a
  * gathering read_accum -- this is that, kept apart from the single-context calls.  Member i owns the 8-row stripes s with

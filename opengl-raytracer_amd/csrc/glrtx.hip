@@ -28,6 +28,7 @@
 #include "variance.hip.h"
 #include "reproject.hip.h"
 #include "reproject_motion.hip.h"
+#include "tonemap.hip.h"
 #include "../host/reproject_setup.h"
 static_assert(glrtx::lbvh::kRotationPasses == GLRT_LBVH_ROTATION_PASSES, "device and CPU LBVH statements must run the same rotation sweeps");
 static_assert(glrtx::lbvh::kRebuildLeaves == GLRT_LBVH_REBUILD_LEAVES, "device and CPU LBVH statements must rebuild the same subtrees");
@@ -217,6 +218,11 @@ struct glrtx_ctx {
     size_t mm_pitch = 0;
     int mm_rows = 0;
     bool mm_on = false, moments_launch = false;
+
+    // Tone mapping (glrtx_exposure_measure / glrtx_tonemap): the exposure block (tonemap::Exposure: the working histogram, then glrtx_exposure's image; allocated and
+    // zeroed on first use, kept across glrtx_resize) and the plane T (packed rows of tm_w float4 over tm_rows rows; released by glrtx_resize)
+    DevBuf tmExp, tmT;
+    int tm_w = 0, tm_rows = -1;   // (-1: no T)
 
     bool count_rays = false;
     const char *last_kernel = "";  // name of the last render kernel launched (error reports)
@@ -1668,6 +1674,76 @@ int moments_check(glrtx_ctx *c, const glrtx_params *p, const float *seeds_xy, in
     return GLRTX_OK;
 }
 
+// ---- tone mapping (glrtx_exposure_measure, glrtx_tonemap, glrtx_resolve_tonemapped_rgba8)
+static_assert(sizeof(tonemap::Exposure) == tonemap::kExposureOut + sizeof(glrtx_exposure), "tonemap::Exposure ends with glrtx_exposure's image");
+
+bool tm_positive(float v) { return v > 0.0f && !std::isinf(v); }
+
+// Everything a call that takes a glrtx_tonemap_cfg refuses about the cfg itself, checked before anything changes.
+int tonemap_cfg_check(glrtx_ctx *c, const glrtx_tonemap_cfg *k, const char *fn) {
+    if (!k) return fail(c, GLRTX_EINVAL, "%s: NULL cfg", fn);
+    if (k->op < 0 || k->op > 2) return fail(c, GLRTX_EINVAL, "%s: op %d outside 0..2", fn, k->op);
+    if (k->source < 0 || k->source > 1) return fail(c, GLRTX_EINVAL, "%s: source %d outside 0..1", fn, k->source);
+    if (!tm_positive(k->exposure)) return fail(c, GLRTX_EINVAL, "%s: exposure %g is not a positive finite number", fn, (double)k->exposure);
+    if (!tm_positive(k->key)) return fail(c, GLRTX_EINVAL, "%s: key %g is not a positive finite number", fn, (double)k->key);
+    if (!tm_positive(k->white) || !std::isnormal(k->white * k->white))
+        return fail(c, GLRTX_EINVAL, "%s: white %g is not a positive finite number with a normal square", fn, (double)k->white);
+    if (!tm_positive(k->gamma)) return fail(c, GLRTX_EINVAL, "%s: gamma %g is not a positive finite number", fn, (double)k->gamma);
+    if (!(k->adapt > 0.0f && k->adapt <= 1.0f)) return fail(c, GLRTX_EINVAL, "%s: adapt %g outside (0, 1]", fn, (double)k->adapt);
+    if (k->low_permille < 0 || k->low_permille >= k->high_permille || k->high_permille > 1000)
+        return fail(c, GLRTX_EINVAL, "%s: histogram window %d..%d is not 0 <= low < high <= 1000", fn, k->low_permille, k->high_permille);
+    return GLRTX_OK;
+}
+tonemap::Curve tonemap_curve(const glrtx_tonemap_cfg &k) { return {k.op, k.auto_exposure ? 1 : 0, k.exposure, k.white}; }
+
+// The context's exposure block, zeroed when it is first allocated (no E, an empty working histogram).
+int exposure_ensure(glrtx_ctx *c) {
+    if (c->tmExp.p) return GLRTX_OK;
+    if (int rc = ensure(c, c->tmExp, sizeof(tonemap::Exposure))) return rc;
+    HIP_TRY(c, hipMemsetAsync(c->tmExp.p, 0, sizeof(tonemap::Exposure), c->stream));
+    return GLRTX_OK;
+}
+
+// The context checks every tone-mapping call shares, and the source the cfg names.
+int tonemap_source(glrtx_ctx *c, const glrtx_tonemap_cfg *k, const char *fn, const float4 *&src, int &pitch_f4) {
+    if (int rc = tonemap_cfg_check(c, k, fn)) return rc;
+    if (!c->accum || c->width < 1) return fail(c, GLRTX_EINVAL, "%s: no accumulator (call glrtx_resize)", fn);
+    if (k->source == 1) {
+        if (!c->dn_have || !c->dnD.p || c->ft_w != c->width || c->ft_rows != c->owned_rows)
+            return fail(c, GLRTX_EINVAL, "%s: source = 1 without a denoised image of the current shape (call glrtx_denoise or glrtx_denoise_variance first)", fn);
+        src = (const float4 *)c->dnD.p; pitch_f4 = c->width;
+    } else {
+        src = c->accum; pitch_f4 = (int)(c->pitch_bytes / sizeof(float4));
+    }
+    return GLRTX_OK;
+}
+
+// One measurement on `stream`: the histogram into st->work, then the reduce.
+int exposure_passes(glrtx_ctx *c, hipStream_t stream, const float4 *src, int pitch_f4, int width, int rows, tonemap::Exposure *st, const glrtx_tonemap_cfg &k) {
+    if (rows > 0) {
+        hipLaunchKernelGGL(tonemap::exposure_histogram, tonemap::histogram_grid(width, rows), dim3(256), 0, stream, src, pitch_f4, width, rows, st);
+        HIP_TRY(c, hipGetLastError());
+    }
+    const tonemap::ReduceArgs ra{st, k.key, k.adapt, k.low_permille, k.high_permille};
+    hipLaunchKernelGGL(tonemap::exposure_reduce, dim3(1), dim3(256), 0, stream, ra);
+    HIP_TRY(c, hipGetLastError());
+    return GLRTX_OK;
+}
+int tonemap_plane_pass(glrtx_ctx *c, hipStream_t stream, const float4 *src, int pitch_f4, int width, int rows, float4 *T, const tonemap::Exposure *st,
+                       const glrtx_tonemap_cfg &k) {
+    hipLaunchKernelGGL(tonemap::tonemap_plane, dim3((unsigned)((width + 63) / 64), (unsigned)((rows + 3) / 4)), dim3(256), 0, stream, src, pitch_f4, width, rows, T,
+                       tonemap_curve(k), st);
+    HIP_TRY(c, hipGetLastError());
+    return GLRTX_OK;
+}
+int tonemap_resolve_pass(glrtx_ctx *c, hipStream_t stream, const float4 *src, int pitch_f4, int width, int rows, uchar4 *out, const tonemap::Exposure *st,
+                         const glrtx_tonemap_cfg &k) {
+    hipLaunchKernelGGL(tonemap::tonemap_resolve<kResolvePer>, resolve_grid(width, rows), dim3(256), 0, stream, src, pitch_f4, width, rows, out, width, 1.0f / k.gamma,
+                       k.flip_y ? 1 : 0, tonemap_curve(k), st);
+    HIP_TRY(c, hipGetLastError());
+    return GLRTX_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1784,6 +1860,7 @@ void glrtx_destroy(glrtx_ctx *c) {
     dev_free(c->accum_own); dev_free(c->counter); dev_free(c->rgba8); dev_free(c->work);
     dev_free(c->adHalf); dev_free(c->adMask); dev_free(c->adList); dev_free(c->adCount);
     dev_free(c->mmM); dev_free(c->mmM_spare);
+    dev_free(c->tmExp); dev_free(c->tmT);
     denoise_release(c);
     dev_free(c->mtPos); dev_free(c->mtNrm);
     dev_free(c->wfState); dev_free(c->wfQ); dev_free(c->wfSeeds); dev_free(c->wfPlanes);
@@ -2334,6 +2411,7 @@ int glrtx_resize(glrtx_ctx *c, int width, int height) {
     }
     denoise_release(c);  // (the feature planes and the filter's images have the old shape; the stream is idle)
     dev_free(c->mmM); dev_free(c->mmM_spare);  // (so has the moments plane: allocated again on its next use)
+    dev_free(c->tmT); c->tm_w = 0; c->tm_rows = -1;  // (and the tone-mapped plane; the exposure block has no shape and stays)
     c->width = width; c->height = height;
     c->owned_rows = owned_rows_of(height, c->rank, c->world, c->stripe);
     c->st.width = width; c->st.height = height; c->st.owned_rows = c->owned_rows;
@@ -2841,6 +2919,153 @@ int glrtx_debug_denoise_variance(const float *accum, const float *moments, const
         s.download(v0_out, v[0], vbytes);
     }
     return s.result(rc, fn);
+}
+
+// ---- tone mapping
+int glrtx_exposure_measure(glrtx_ctx *c, const glrtx_tonemap_cfg *cfg) {
+    const char *fn = "glrtx_exposure_measure";
+    if (!c) return GLRTX_EINVAL;
+    const float4 *src = nullptr;
+    int pitch_f4 = 0;
+    if (int rc = tonemap_source(c, cfg, fn, src, pitch_f4)) return rc;
+    seal_feed(c);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (int rc = exposure_ensure(c)) return rc;
+    return exposure_passes(c, c->stream, src, pitch_f4, c->width, c->owned_rows, (tonemap::Exposure *)c->tmExp.p, *cfg);
+}
+
+int glrtx_exposure_reset(glrtx_ctx *c) {
+    if (!c) return GLRTX_EINVAL;
+    seal_feed(c);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (c->tmExp.p) HIP_TRY(c, hipMemsetAsync(c->tmExp.p, 0, sizeof(tonemap::Exposure), c->stream));
+    return GLRTX_OK;
+}
+
+int glrtx_read_exposure(glrtx_ctx *c, glrtx_exposure *out) {
+    if (!c || !out) return GLRTX_EINVAL;
+    seal_feed(c);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (int rc = exposure_ensure(c)) return rc;
+    if (int rc = glrtx_sync(c)) return rc;
+    HIP_TRY(c, hipMemcpy(out, (const char *)c->tmExp.p + tonemap::kExposureOut, sizeof *out, hipMemcpyDeviceToHost));
+    return GLRTX_OK;
+}
+
+int glrtx_tonemap(glrtx_ctx *c, const glrtx_tonemap_cfg *cfg) {
+    const char *fn = "glrtx_tonemap";
+    if (!c) return GLRTX_EINVAL;
+    const float4 *src = nullptr;
+    int pitch_f4 = 0;
+    if (int rc = tonemap_source(c, cfg, fn, src, pitch_f4)) return rc;
+    seal_feed(c);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (int rc = exposure_ensure(c)) return rc;
+    if (int rc = ensure(c, c->tmT, (size_t)c->width * (size_t)std::max(c->owned_rows, 1) * sizeof(float4))) return rc;
+    c->tm_w = c->width; c->tm_rows = c->owned_rows;
+    if (c->owned_rows == 0) return GLRTX_OK;
+    return tonemap_plane_pass(c, c->stream, src, pitch_f4, c->width, c->owned_rows, (float4 *)c->tmT.p, (const tonemap::Exposure *)c->tmExp.p, *cfg);
+}
+
+int glrtx_read_tonemapped(glrtx_ctx *c, float *dst, size_t dst_pitch_bytes) {
+    const char *fn = "glrtx_read_tonemapped";
+    if (!c || !dst) return GLRTX_EINVAL;
+    if (!c->tmT.p || c->tm_w != c->width || c->tm_rows != c->owned_rows) return fail(c, GLRTX_EINVAL, "%s: no tone-mapped plane (call glrtx_tonemap first)", fn);
+    const size_t row = (size_t)c->width * sizeof(float4);
+    if (dst_pitch_bytes < row) return fail(c, GLRTX_EINVAL, "%s: dst pitch too small", fn);
+    if (int rc = glrtx_sync(c)) return rc;
+    if (c->owned_rows == 0) return GLRTX_OK;
+    HIP_TRY(c, hipMemcpy2D(dst, dst_pitch_bytes, c->tmT.p, row, row, (size_t)c->owned_rows, hipMemcpyDeviceToHost));
+    return GLRTX_OK;
+}
+
+// Source -> bytes in one pass: the curve in front of the resolve's own arithmetic (tonemap_resolve); T is not touched.
+int glrtx_resolve_tonemapped_rgba8(glrtx_ctx *c, uint8_t *dst, size_t dst_pitch_bytes, const glrtx_tonemap_cfg *cfg) {
+    const char *fn = "glrtx_resolve_tonemapped_rgba8";
+    if (!c || !dst) return GLRTX_EINVAL;
+    const float4 *src = nullptr;
+    int pitch_f4 = 0;
+    if (int rc = tonemap_source(c, cfg, fn, src, pitch_f4)) return rc;
+    if (dst_pitch_bytes < (size_t)c->width * 4) return fail(c, GLRTX_EINVAL, "%s: dst pitch too small", fn);
+    seal_feed(c);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (int rc = exposure_ensure(c)) return rc;
+    if (c->owned_rows == 0) return glrtx_sync(c);
+    if (int rc = ensure(c, c->rgba8, (size_t)c->width * 4 * (size_t)c->owned_rows)) return rc;
+    if (int rc = tonemap_resolve_pass(c, c->stream, src, pitch_f4, c->width, c->owned_rows, (uchar4 *)c->rgba8.p, (const tonemap::Exposure *)c->tmExp.p, *cfg)) return rc;
+    if (int rc = glrtx_sync(c)) return rc;
+    HIP_TRY(c, hipMemcpy2D(dst, dst_pitch_bytes, c->rgba8.p, (size_t)c->width * 4, (size_t)c->width * 4, (size_t)c->owned_rows, hipMemcpyDeviceToHost));
+    return GLRTX_OK;
+}
+
+int glrtx_debug_tonemap(const float *src, int width, int rows, const glrtx_tonemap_cfg *cfg, const float *exposure_in, glrtx_exposure *exp_out, float *t_out,
+                        uint8_t *rgba8_out) {
+    const char *fn = "glrtx_debug_tonemap";
+    if (width < 1 || rows < 1 || width > 65536 || rows > 65536) return fail(nullptr, GLRTX_EINVAL, "%s: bad size %dx%d", fn, width, rows);
+    if (!src) return fail(nullptr, GLRTX_EINVAL, "%s: NULL buffer", fn);
+    if (int rc = tonemap_cfg_check(nullptr, cfg, fn)) return rc;
+    const size_t px = (size_t)width * rows;
+    tonemap::Exposure init{};
+    if (exposure_in) { init.exposure = *exposure_in; init.measurements = 1; }
+    DebugScratch s;
+    const float4 *in = s.alloc(px * sizeof(float4), src);
+    tonemap::Exposure *st = s.alloc<tonemap::Exposure>(sizeof init, &init);
+    float4 *T = s.alloc(px * sizeof(float4));
+    uchar4 *bytes = s.alloc<uchar4>(px * 4);
+    int rc = GLRTX_OK;
+    if (s.ok()) rc = exposure_passes(nullptr, 0, in, width, width, rows, st, *cfg);
+    if (s.ok() && rc == GLRTX_OK) rc = tonemap_plane_pass(nullptr, 0, in, width, width, rows, T, st, *cfg);
+    if (s.ok() && rc == GLRTX_OK) rc = tonemap_resolve_pass(nullptr, 0, in, width, width, rows, bytes, st, *cfg);
+    if (rc == GLRTX_OK) {
+        s.sync();
+        if (exp_out) {
+            s.download(exp_out, (const char *)st + tonemap::kExposureOut, sizeof *exp_out);
+            if (s.ok() && exposure_in) exp_out->measurements = 1;  // (one measurement, whatever stood before it)
+        }
+        s.download(t_out, T, px * sizeof(float4));
+        s.download(rgba8_out, bytes, px * 4);
+    }
+    return s.result(rc, fn);
+}
+
+// Device time of one tone-mapping pass by itself, as glrtx_debug_resolve_burst measures the resolve: `reps` launches back to back between one pair of events, after
+// a warm-up pass.  which: 0 the plain resolve kernel on the cfg's source (the yardstick beside it), 1 tonemap_resolve, 2 tonemap_plane, 3 a measurement (histogram
+// + reduce).  3 moves E like `reps` measurements; nothing else the context owns changes but T (2) and the byte image.
+int glrtx_debug_tonemap_burst(glrtx_ctx *c, const glrtx_tonemap_cfg *cfg, int which, int reps, float *ms_per_launch) {
+    const char *fn = "glrtx_debug_tonemap_burst";
+    if (!c || !ms_per_launch || reps < 1 || which < 0 || which > 3) return GLRTX_EINVAL;
+    const float4 *src = nullptr;
+    int pitch_f4 = 0;
+    if (int rc = tonemap_source(c, cfg, fn, src, pitch_f4)) return rc;
+    if (c->owned_rows == 0) return fail(c, GLRTX_EINVAL, "%s: no rows", fn);
+    seal_feed(c);
+    HIP_TRY(c, hipSetDevice(c->device));
+    int rc;
+    if ((rc = exposure_ensure(c)) || (rc = ensure(c, c->rgba8, (size_t)c->width * 4 * (size_t)c->owned_rows))) return rc;
+    if (which == 2) {
+        if ((rc = ensure(c, c->tmT, (size_t)c->width * (size_t)c->owned_rows * sizeof(float4)))) return rc;
+        c->tm_w = c->width; c->tm_rows = c->owned_rows;
+    }
+    tonemap::Exposure *st = (tonemap::Exposure *)c->tmExp.p;
+    for (int pass = 0; pass < 2; pass++) {  // (the first pass warms the device up)
+        HIP_TRY(c, hipEventRecord(c->rs0, c->stream));
+        for (int i = 0; i < reps && rc == GLRTX_OK; i++) {
+            if (which == 0)
+                hipLaunchKernelGGL(resolve_kernel<kResolvePer>, resolve_grid(c->width, c->owned_rows), dim3(256), 0, c->stream, src, pitch_f4, c->width, c->owned_rows,
+                                   (uchar4 *)c->rgba8.p, c->width, 1.0f / cfg->gamma, cfg->flip_y ? 1 : 0);
+            else if (which == 1) rc = tonemap_resolve_pass(c, c->stream, src, pitch_f4, c->width, c->owned_rows, (uchar4 *)c->rgba8.p, st, *cfg);
+            else if (which == 2) rc = tonemap_plane_pass(c, c->stream, src, pitch_f4, c->width, c->owned_rows, (float4 *)c->tmT.p, st, *cfg);
+            else rc = exposure_passes(c, c->stream, src, pitch_f4, c->width, c->owned_rows, st, *cfg);
+        }
+        if (rc) return rc;
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipEventRecord(c->rs1, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    float ms = 0.f;
+    HIP_TRY(c, hipEventElapsedTime(&ms, c->rs0, c->rs1));
+    *ms_per_launch = ms / (float)reps;
+    return GLRTX_OK;
 }
 
 

@@ -1,6 +1,7 @@
 // main.cpp -- headless render-loop entry point with the shape of the reference's main
 // (src/main.cpp:9-31): parse arguments -> Window() -> Scene::parse(-i file) -> Window::mainloop().
 // Extra flags drive what the reference hard-codes or leaves to the shader defaults.
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -14,7 +15,7 @@
 using namespace glrt;
 
 static void usage(const char *exe) {
-    std::printf("usage: %s -i scene.json [-s N] [--max-depth D] [--spp N] [--frames F] [--frames-in-flight B] [--bvh sah|sah-reinsert|sah-gpu|lbvh|sah-levels-cpu|lbvh-cpu|reference] [--order-by-hits] [--out file.png] [--save-every-frame] [--device G | --gpus N | --devices a,b,..] [--extensions] [--whitted] [--enable-volume] [--volume-wavefront] [--adaptive THRESHOLD [--min-spp N]] [--denoise | --denoise-variance [--denoise-iters N]]\n"
+    std::printf("usage: %s -i scene.json [-s N] [--max-depth D] [--spp N] [--frames F] [--frames-in-flight B] [--bvh sah|sah-reinsert|sah-gpu|lbvh|sah-levels-cpu|lbvh-cpu|reference] [--order-by-hits] [--out file.png] [--save-every-frame] [--device G | --gpus N | --devices a,b,..] [--extensions] [--whitted] [--enable-volume] [--volume-wavefront] [--adaptive THRESHOLD [--min-spp N]] [--denoise | --denoise-variance [--denoise-iters N]] [--tonemap clamp|reinhard|aces [--exposure X] [--auto-exposure]]\n"
                 "  -i, --input             scene description (JSON; schema: SURVEY.md Appendix C)            [required]\n"
                 "  -s, --sample-per-cycle  accepted for compatibility; like the reference (main.cpp:13) it is not read\n"
                 "      --max-depth D       u_maxDepth (default 16, the reference shader's default)\n"
@@ -43,7 +44,12 @@ static void usage(const char *exe) {
                 "      --denoise-variance  write the variance-guided image instead: the frames are rendered with glrtx_render_moments in bursts of --frames-in-flight\n"
                 "                          (at most 1024) frames, then SVGF's filter runs over the mean (one device; not with --denoise, --adaptive,\n"
                 "                          --save-every-frame, extension or volume scenes)\n"
-                "      --denoise-iters N   with --denoise or --denoise-variance: filter iterations, 1..6 (default 5)\n", exe);
+                "      --denoise-iters N   with --denoise or --denoise-variance: filter iterations, 1..6 (default 5)\n"
+                "      --tonemap OP        write the image through a tone curve: clamp (the plain resolve's), reinhard (extended, white point 4) or aces (Narkowicz's fit);\n"
+                "                          the denoised image with --denoise / --denoise-variance (one device; not with --save-every-frame).  Without it the output is\n"
+                "                          what it always was\n"
+                "      --exposure X        with --tonemap: linear multiplier in front of the curve (default 1)\n"
+                "      --auto-exposure     with --tonemap: multiply by the exposure measured from the image's luminance histogram as well (key 0.18)\n", exe);
 }
 
 int main(int argc, char **argv) {
@@ -54,6 +60,9 @@ int main(int argc, char **argv) {
     int min_spp = 2;
     bool denoise = false, denoise_variance = false;
     int denoise_iters = 0;
+    int tonemap_op = -1;
+    float exposure = 1.0f;
+    bool exposure_given = false, auto_exposure = false;
     std::vector<int> devices;
     std::string bvh;
     for (int i = 1; i < argc; i++) {
@@ -82,6 +91,13 @@ int main(int argc, char **argv) {
         else if (a == "--denoise") denoise = true;
         else if (a == "--denoise-variance") denoise_variance = true;
         else if (a == "--denoise-iters") denoise_iters = std::atoi(next("--denoise-iters"));
+        else if (a == "--tonemap") {
+            const std::string op = next("--tonemap");
+            tonemap_op = op == "clamp" ? 0 : (op == "reinhard" ? 1 : (op == "aces" ? 2 : -2));
+            if (tonemap_op < 0) { std::fprintf(stderr, "--tonemap: clamp, reinhard or aces\n"); return 1; }
+        }
+        else if (a == "--exposure") { exposure = (float)std::atof(next("--exposure")); exposure_given = true; }
+        else if (a == "--auto-exposure") auto_exposure = true;
         else if (a == "--gpus") { const int n = std::atoi(next("--gpus")); devices.clear(); for (int k = 0; k < n; k++) devices.push_back(k); }
         else if (a == "--devices") {
             devices.clear();
@@ -106,6 +122,11 @@ int main(int argc, char **argv) {
         std::fprintf(stderr, "--denoise-variance: --frames-in-flight %d is above the 1024 frames one glrtx_render_moments burst takes\n", in_flight);
         return 1;
     }
+    if ((exposure_given || auto_exposure) && tonemap_op < 0) { std::fprintf(stderr, "--exposure and --auto-exposure need --tonemap\n"); return 1; }
+    if (tonemap_op >= 0 && (every_frame || devices.size() > 1 || !(exposure > 0.0f) || std::isinf(exposure))) {
+        std::fprintf(stderr, "--tonemap: one device, not with --save-every-frame, and --exposure must be a positive finite number\n");
+        return 1;
+    }
 
     auto window = std::make_unique<Window>();
     if (devices.empty()) window->setDevice(device);
@@ -120,6 +141,7 @@ int main(int argc, char **argv) {
     window->setVolumeWavefront(volume_wavefront);
     if (denoise) window->setDenoise(denoise_iters);
     if (denoise_variance) window->setDenoiseVariance(denoise_iters);
+    if (tonemap_op >= 0) window->setTonemap(tonemap_op, exposure, auto_exposure);
 
     auto scene = std::make_shared<Scene>();
     if (!bvh.empty()) scene->setBvhBuilder(bvh);

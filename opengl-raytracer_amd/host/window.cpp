@@ -104,6 +104,7 @@ void Window::mainloop(const std::shared_ptr<Scene> &scene_, double fps) {
     // Launches are issued back to back and the loop waits for the device only where it needs the pixels (a frame that is saved, the end of the run): the calls are
     // asynchronous, and a launch issued behind idle time runs longer -- 2 % behind 1 ms, 5 % behind 3 ms (profiles/r04_ab_launch_warmth.txt).  lastFrameMs() is the wall
     // time per frame between two such waits.
+    if (tonemap_ && (glrtx_group_size(grp_) != 1 || every)) GLRT_FatalError("--tonemap: one device, and not with --save-every-frame (groups and the present ring have no tone-mapped form)");
     if (denoise_ || denoiseVar_) {  // the feature planes of this (static) camera, once, before the first frame
         if (glrtx_group_size(grp_) != 1 || every) GLRT_FatalError("--denoise: one device, and not with --save-every-frame (groups and the present ring have no denoised form)");
         if (denoiseVar_ && (denoise_ || adaptive_)) GLRT_FatalError("--denoise-variance: not with --denoise or --adaptive");
@@ -258,6 +259,25 @@ void Window::resetBuffer() { GLRTX_CHECK(glrtx_group_resize(grp_, width_, height
 
 void Window::saveCurrentFrame(const std::string &filename, bool overwrite) const {
     std::vector<unsigned char> bytes((size_t)width_ * height_ * 4);
+    if (tonemap_) {  // --tonemap: the denoised image if one was asked for, else the accumulator, through the exposure and the tone curve (one device: checked in mainloop)
+        glrtx_ctx *c0 = glrtx_group_ctx(grp_, 0);
+        glrtx_tonemap_cfg cfg = tonemapCfg_;
+        cfg.source = (denoise_ || denoiseVar_) ? 1 : 0;
+        if (denoise_ && glrtx_denoise(c0, &denoiseCfg_) != GLRTX_OK) GLRT_FatalError("glrtx_denoise: %s", glrtx_last_error(c0));
+        if (denoiseVar_ && glrtx_denoise_variance(c0, &denoiseVarCfg_) != GLRTX_OK) GLRT_FatalError("glrtx_denoise_variance: %s", glrtx_last_error(c0));
+        if (cfg.auto_exposure && glrtx_exposure_measure(c0, &cfg) != GLRTX_OK) GLRT_FatalError("glrtx_exposure_measure: %s", glrtx_last_error(c0));
+        if (glrtx_resolve_tonemapped_rgba8(c0, bytes.data(), (size_t)width_ * 4, &cfg) != GLRTX_OK)
+            GLRT_FatalError("glrtx_resolve_tonemapped_rgba8: %s", glrtx_last_error(c0));
+        if (cfg.auto_exposure) {
+            glrtx_exposure e;
+            if (glrtx_read_exposure(c0, &e) != GLRTX_OK) GLRT_FatalError("glrtx_read_exposure: %s", glrtx_last_error(c0));
+            GLRT_Info("Tonemap: op %d, exposure %g x measured %g (mean log2 luminance %g over %llu of %llu pixels)", cfg.op, (double)cfg.exposure, (double)e.exposure,
+                      (double)e.mean_log2, (unsigned long long)e.kept, (unsigned long long)e.counted);
+        } else
+            GLRT_Info("Tonemap: op %d, exposure %g", cfg.op, (double)cfg.exposure);
+        saveImage(filename, overwrite, bytes.data());
+        return;
+    }
     // resolve = screen.frag (rgb/count, clamp, gamma 2.2) + the vertical flip of window.cpp:391-398
     // (with several GPUs the stripes are first gathered on the first one)
     if (denoise_) {  // the filter's result through the same resolve

@@ -59,6 +59,9 @@ public:
     void setDenoise(int iterations) { denoise_ = true; if (iterations >= 1) denoiseCfg_.iterations = iterations; }
     // Variance-guided denoising (glrtx_track_moments / glrtx_render_moments / glrtx_denoise_variance, one device only): the frames are rendered in bursts of
     // framesInFlight frames with the moments fold, and the saved image is the variance-guided filter's.
+    // Tone mapping of the saved image (glrtx_exposure_measure / glrtx_resolve_tonemapped_rgba8, one device only): op 0 clamp, 1 Reinhard, 2 ACES; the source is the
+    // denoised image when a denoiser is on.  Without it the saved image is the plain resolve's, byte for byte.
+    void setTonemap(int op, float exposure, bool autoExposure) { tonemap_ = true; tonemapCfg_.op = op; tonemapCfg_.exposure = exposure; tonemapCfg_.auto_exposure = autoExposure ? 1 : 0; }
     void setDenoiseVariance(int iterations) { denoiseVar_ = true; if (iterations >= 1) denoiseVarCfg_.iterations = iterations; }
     // wall-clock ms PER FRAME between the last two waits for the device, averaged over the frames issued in between (with one PNG per run: the whole run, cold first
     // launches included; with --save-every-frame: the whole run, PNG writing included).  The device's own time of the last launch is glrtx_stats.kernel_ms_last.
@@ -94,6 +97,8 @@ private:
     int adaptMinSamples_ = 2;
     bool volumeWavefront_ = false;
     bool denoise_ = false, denoiseVar_ = false;
+    bool tonemap_ = false;
+    glrtx_tonemap_cfg tonemapCfg_ = {0, 0, 0, 1.0f, 0.18f, 500, 950, 1.0f, 4.0f, 2.2f, 1};  // (glrt_amd.host.TONEMAP_DEFAULTS holds the same)
     glrtx_denoise_var_cfg denoiseVarCfg_ = {5, 4.0f, 0.1f, 0.01f, 1};  // (DESIGN.md "Variance guidance": the sweep; glrt_amd.host.DENOISE_VAR_DEFAULTS holds the same)
     glrtx_denoise_cfg denoiseCfg_ = {5, 100.0f, 0.1f, 0.01f, 1};  // (DESIGN.md "Denoising": the sweep behind these; glrt_amd.host.DENOISE_DEFAULTS holds the same)
     bool fallbackNoted_ = false;

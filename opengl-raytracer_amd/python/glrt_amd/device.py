@@ -61,6 +61,40 @@ class ReprojectCfg(C.Structure):
         return cls(int(pick(max_history, "max_history")), float(pick(depth_tolerance, "depth_tolerance")), float(pick(normal_tolerance, "normal_tolerance")))
 
 
+class TonemapCfg(C.Structure):
+    """glrtx_tonemap_cfg (include/glrtx.h "Tone mapping"); TonemapCfg.default(**fields) holds glrt_amd.host.TONEMAP_DEFAULTS.  op: 0 clamp, 1 Reinhard, 2 ACES
+    (or one of TONEMAP_OPS' names)."""
+    _fields_ = [("op", C.c_int), ("source", C.c_int), ("auto_exposure", C.c_int), ("exposure", C.c_float), ("key", C.c_float), ("low_permille", C.c_int),
+                ("high_permille", C.c_int), ("adapt", C.c_float), ("white", C.c_float), ("gamma", C.c_float), ("flip_y", C.c_int)]
+
+    @classmethod
+    def default(cls, **fields):
+        from .host import TONEMAP_DEFAULTS, TONEMAP_OPS
+        d = dict(TONEMAP_DEFAULTS)
+        unknown = set(fields) - set(d)
+        if unknown:
+            raise TypeError(f"TonemapCfg: unknown field(s) {sorted(unknown)}")
+        d.update({k: v for k, v in fields.items() if v is not None})
+        if isinstance(d["op"], str):
+            d["op"] = TONEMAP_OPS[d["op"]]
+        c = cls()
+        for name, ctype in cls._fields_:
+            setattr(c, name, float(d[name]) if ctype is C.c_float else int(d[name]))
+        return c
+
+
+class Exposure(C.Structure):
+    """glrtx_exposure: the last measurement's histogram, N, K, mean_log2, target, E, and the number of measurements since create / reset."""
+    _fields_ = [("hist", C.c_uint32 * 256), ("counted", C.c_uint64), ("kept", C.c_uint64), ("mean_log2", C.c_float), ("target", C.c_float),
+                ("exposure", C.c_float), ("measurements", C.c_int)]
+
+
+def _tonemap_cfg(cfg, fields) -> TonemapCfg:
+    if cfg is not None and fields:
+        raise TypeError("give a TonemapCfg or its fields, not both")
+    return cfg if cfg is not None else TonemapCfg.default(**fields)
+
+
 class Image(C.Structure):
     _fields_ = [("rgba", C.c_void_p), ("pitch_bytes", C.c_size_t), ("width", C.c_int32), ("rows", C.c_int32), ("frame", C.c_uint64)]
 
@@ -100,7 +134,9 @@ EXPORTS = ["glrtx_abi_version", "glrtx_create", "glrtx_destroy", "glrtx_last_err
            "glrtx_trace_rays", "glrtx_trace_rays_device", "glrtx_reproject", "glrtx_reproject_last", "glrtx_debug_reproject",
            "glrtx_track_motion", "glrtx_read_features_geom", "glrtx_reproject_motion", "glrtx_debug_reproject_motion",
            "glrtx_track_moments", "glrtx_render_moments", "glrtx_read_moments", "glrtx_denoise_variance", "glrtx_debug_denoise_variance",
-           "glrtx_debug_reproject_moments", "glrtx_debug_reproject_motion_moments"]
+           "glrtx_debug_reproject_moments", "glrtx_debug_reproject_motion_moments",
+           "glrtx_exposure_measure", "glrtx_exposure_reset", "glrtx_read_exposure", "glrtx_tonemap", "glrtx_read_tonemapped", "glrtx_resolve_tonemapped_rgba8",
+           "glrtx_debug_tonemap", "glrtx_debug_tonemap_burst"]
 
 SCENE_BUFFERS = ("nodes", "cnodes", "nrms", "lights", "vine", "root")  # glrtx_debug_read_scene's `which`, in order (GLRTX_SCENE_*)
 
@@ -240,6 +276,18 @@ def lib():
                                                                C.POINTER(C.c_int), C.POINTER(C.c_int)]
         except AttributeError:
             pass
+        try:  # (additive to ABI 10 as well: tone mapping)
+            tc = C.POINTER(TonemapCfg)
+            L.glrtx_exposure_measure.argtypes = [vp, tc]
+            L.glrtx_exposure_reset.argtypes = [vp]
+            L.glrtx_read_exposure.argtypes = [vp, C.POINTER(Exposure)]
+            L.glrtx_tonemap.argtypes = [vp, tc]
+            L.glrtx_read_tonemapped.argtypes = [vp, vp, C.c_size_t]
+            L.glrtx_resolve_tonemapped_rgba8.argtypes = [vp, vp, C.c_size_t, tc]
+            L.glrtx_debug_tonemap.argtypes = [fp, C.c_int, C.c_int, tc, fp, C.POINTER(Exposure), fp, C.POINTER(C.c_uint8)]
+            L.glrtx_debug_tonemap_burst.argtypes = [vp, tc, C.c_int, C.c_int, C.POINTER(C.c_float)]
+        except AttributeError:
+            pass
         _lib = L
     return _lib
 
@@ -372,6 +420,23 @@ def debug_denoise_variance(accum, moments, normal_depth, albedo_id, return_v0=Fa
     if rc != 0:
         raise GlrtxError(rc, L.glrtx_last_error(None).decode())
     return (out, v0) if return_v0 else out
+
+
+def debug_tonemap(src, exposure_in=None, cfg=None, **fields):
+    """glrtx_debug_tonemap on the current device: one exposure measurement (exposure_in: the previous E, None for a first one), the curve and the fused resolve
+    on a (rows, width, 4) float32 array.  Returns (Exposure, T (rows, width, 4) float32, bytes (rows, width, 4) uint8)."""
+    L = lib()
+    a = _f32(src)
+    if a.ndim != 3 or a.shape[2] != 4:
+        raise ValueError(f"debug_tonemap: a (rows, width, 4) array expected, got {a.shape}")
+    c = _tonemap_cfg(cfg, fields)
+    e, t, b = Exposure(), np.zeros_like(a), np.zeros(a.shape, np.uint8)
+    prev = None if exposure_in is None else C.c_float(float(exposure_in))
+    rc = L.glrtx_debug_tonemap(_fp(a), a.shape[1], a.shape[0], C.byref(c), None if prev is None else C.byref(prev), C.byref(e), _fp(t),
+                               b.ctypes.data_as(C.POINTER(C.c_uint8)))
+    if rc != 0:
+        raise GlrtxError(rc, L.glrtx_last_error(None).decode())
+    return e, t, b
 
 
 def debug_reproject(accum, n0, a0, n1, a1, prev, cur, **cfg):
@@ -816,6 +881,39 @@ class Device:
         p = make_params(params)
         c = ReprojectCfg.default(max_history, depth_tolerance, normal_tolerance)
         self._ck(self.L.glrtx_reproject_motion(self.h, C.byref(p), C.byref(c)))
+    def exposure_measure(self, cfg=None, **fields):
+        """One exposure measurement of the cfg's source (glrtx_exposure_measure): histogram and reduce on the context's stream, E updated on the device; no sync.
+        cfg: a TonemapCfg, or its fields as keywords (None: glrt_amd.host.TONEMAP_DEFAULTS)."""
+        self._ck(self.L.glrtx_exposure_measure(self.h, C.byref(_tonemap_cfg(cfg, fields))))
+    def exposure_reset(self):
+        """Forget E (glrtx_exposure_reset): the next measurement jumps to its target."""
+        self._ck(self.L.glrtx_exposure_reset(self.h))
+    def read_exposure(self) -> Exposure:
+        """The last measurement (syncs): an Exposure; measurements == 0 before the first one."""
+        e = Exposure()
+        self._ck(self.L.glrtx_read_exposure(self.h, C.byref(e)))
+        return e
+    def tonemap(self, cfg=None, **fields):
+        """The tone curve over the cfg's source into the context's plane T (glrtx_tonemap); no sync."""
+        self._ck(self.L.glrtx_tonemap(self.h, C.byref(_tonemap_cfg(cfg, fields))))
+    def read_tonemapped(self) -> np.ndarray:
+        """The plane T, (owned_rows, width, 4) float32 {y.rgb, 1} (syncs)."""
+        s = self.stats()
+        out = np.zeros((s.owned_rows, s.width, 4), np.float32)
+        self._ck(self.L.glrtx_read_tonemapped(self.h, out.ctypes.data, s.width * 16))
+        return out
+    def resolve_tonemapped_rgba8(self, cfg=None, **fields) -> np.ndarray:
+        """The cfg's source through the curve and the resolve in one pass (glrtx_resolve_tonemapped_rgba8): (owned_rows, width, 4) uint8."""
+        s = self.stats()
+        out = np.zeros((s.owned_rows, s.width, 4), np.uint8)
+        self._ck(self.L.glrtx_resolve_tonemapped_rgba8(self.h, out.ctypes.data, s.width * 4, C.byref(_tonemap_cfg(cfg, fields))))
+        return out
+    def tonemap_burst_ms(self, which, reps=20, cfg=None, **fields) -> float:
+        """Device time of one launch of a tone-mapping pass from `reps` launches back to back (glrtx_debug_tonemap_burst).  which: 0 the plain resolve kernel,
+        1 the fused tone-mapping resolve, 2 the plane kernel, 3 a measurement."""
+        ms = C.c_float(0)
+        self._ck(self.L.glrtx_debug_tonemap_burst(self.h, C.byref(_tonemap_cfg(cfg, fields)), int(which), int(reps), C.byref(ms)))
+        return float(ms.value)
     def timer_begin(self):
         self._ck(self.L.glrtx_timer_begin(self.h))
 

@@ -49,6 +49,9 @@ def lib():
         L.glrt_reproject_moments.argtypes = [fp] * 10 + [C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, fp, fp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.glrt_reproject_motion_moments.argtypes = [fp] * 7 + [C.c_size_t, fp, C.c_size_t, fp, fp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, fp, fp,
                                                     C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        u32p, u64p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
+        L.glrt_exposure_measure.argtypes = [fp, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_float, fp, u32p, u64p, u64p, fp, fp, fp]
+        L.glrt_tonemap.argtypes = [fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, fp, C.POINTER(C.c_uint8)]
         L.glrt_look_at.argtypes = [fp, fp, fp, fp]
         L.glrt_perspective.argtypes = [C.c_float, C.c_float, C.c_float, C.c_float, fp]
         L.glrt_mat4_mul.argtypes = [fp, fp, fp]
@@ -269,6 +272,45 @@ def denoise_variance(accum, moments, normal_depth, albedo_id, iterations=DENOISE
 
 
 # The reprojection's defaults (DESIGN.md "Reprojection": chosen from the sweep recorded there); Device.reproject takes the same.
+# glrtx_tonemap_cfg's defaults (include/glrtx.h "Tone mapping") and the names of its ops
+TONEMAP_DEFAULTS = dict(op=0, source=0, auto_exposure=0, exposure=1.0, key=0.18, low_permille=500, high_permille=950, adapt=1.0, white=4.0, gamma=2.2, flip_y=1)
+TONEMAP_OPS = dict(clamp=0, reinhard=1, aces=2)
+
+
+def exposure_measure(src, exposure_in=None, key=TONEMAP_DEFAULTS["key"], low_permille=TONEMAP_DEFAULTS["low_permille"],
+                     high_permille=TONEMAP_DEFAULTS["high_permille"], adapt=TONEMAP_DEFAULTS["adapt"]):
+    """glrt_exposure_measure: the CPU statement of one exposure measurement on a (rows, width, 4) float32 array; exposure_in: the previous E, None for a first
+    measurement.  Returns a dict: hist (256 uint32), counted, kept, mean_log2, target, exposure (float32)."""
+    a = _f32(src)
+    if a.ndim != 3 or a.shape[2] != 4:
+        raise ValueError(f"exposure_measure: a (rows, width, 4) array expected, got {a.shape}")
+    hist = np.zeros(256, np.uint32)
+    n, k = C.c_uint64(0), C.c_uint64(0)
+    f = np.zeros(3, np.float32)
+    prev = None if exposure_in is None else np.array([exposure_in], np.float32)
+    rc = lib().glrt_exposure_measure(_fp(a), a.shape[1], a.shape[0], float(key), int(low_permille), int(high_permille), float(adapt),
+                                     None if prev is None else _fp(prev), hist.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(n), C.byref(k),
+                                     _fp(f[0:1]), _fp(f[1:2]), _fp(f[2:3]))
+    if rc != 0:
+        raise RuntimeError(f"glrt_exposure_measure failed: {rc}")
+    return dict(hist=hist, counted=int(n.value), kept=int(k.value), mean_log2=f[0], target=f[1], exposure=f[2])
+
+
+def tonemap(src, op=TONEMAP_DEFAULTS["op"], auto_exposure=TONEMAP_DEFAULTS["auto_exposure"], exposure=TONEMAP_DEFAULTS["exposure"], E=1.0,
+            white=TONEMAP_DEFAULTS["white"], gamma=TONEMAP_DEFAULTS["gamma"], flip_y=TONEMAP_DEFAULTS["flip_y"]):
+    """glrt_tonemap: the CPU statement of the tone curve and of the resolve behind it on a (rows, width, 4) float32 array; E: the measured exposure (read when
+    auto_exposure).  Returns (T (rows, width, 4) float32 {y, 1}, bytes (rows, width, 4) uint8)."""
+    a = _f32(src)
+    if a.ndim != 3 or a.shape[2] != 4:
+        raise ValueError(f"tonemap: a (rows, width, 4) array expected, got {a.shape}")
+    t, b = np.zeros_like(a), np.zeros(a.shape, np.uint8)
+    rc = lib().glrt_tonemap(_fp(a), a.shape[1], a.shape[0], TONEMAP_OPS.get(op, op) if isinstance(op, str) else int(op), int(bool(auto_exposure)), float(exposure),
+                            float(E), float(white), float(gamma), int(bool(flip_y)), _fp(t), b.ctypes.data_as(C.POINTER(C.c_uint8)))
+    if rc != 0:
+        raise RuntimeError(f"glrt_tonemap failed: {rc}")
+    return t, b
+
+
 REPROJECT_DEFAULTS = dict(max_history=32, depth_tolerance=0.02, normal_tolerance=0.9)
 
 
