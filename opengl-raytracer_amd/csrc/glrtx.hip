@@ -19,6 +19,7 @@
 
 #include "glrt_host.h"
 #include "pt_kernel.hip.h"
+#include "accumulate.hip.h"
 #include "lbvh.hip.h"
 #include "sahl.hip.h"
 #include "refit.hip.h"
@@ -122,8 +123,6 @@ struct glrtx_ctx {
     DevScene sc{};
     bool have_scene = false;
     int n_tri = 0, n_fork = 0, n_mat = 0, n_light = 0;
-    const float *frames_seeds = nullptr;  // set only inside glrtx_render_frames
-    int frames_n = 1;
     int budget_share = 1;     // contexts of one group on this device: each takes 1 / budget_share of the frames-in-flight memory budget
 
     int width = 0, height = 0;
@@ -153,7 +152,6 @@ struct glrtx_ctx {
         size_t bytes[5] = {0, 0, 0, 0, 0};  // the scene buffers' sizes as uploaded: nodes, cnodes, nrms, lights, vine (glrtx_debug_read_scene)
         hipEvent_t slot_ev = nullptr;      // recorded on each pipe slot's stream: the refit starts behind every launch that may still read the scene
     } rf;
-    unsigned *hit_hist_dev = nullptr;  // set only inside glrtx_hit_histogram
 
     // Presentation (glrtx_present_enable): frame seq of the ring goes to image seq % ring -- device image (written by the presenting pass on the context's stream),
     // then pinned host image (copied on `copy`, behind pass_done, ending with the image's event).  An image is taken for a frame only while it is FREE: released by the
@@ -183,12 +181,11 @@ struct glrtx_ctx {
     } pres;
 
     // Adaptive sampling (glrtx_render_adaptive): the half buffer H (every second sample; accumulator-sized, allocated on first use, pitch ad_pitch x ad_rows), and what the
-    // last selection wrote -- a mask byte per tile, the ascending list of active tiles, their count in a device word -- for ad_tiles tiles.  adapt_launch: set only while
-    // glrtx_render_adaptive issues its launches (launch_wgwf then runs the ADAPT kernel, plain, on the context's stream).
+    // last selection wrote -- a mask byte per tile, the ascending list of active tiles, their count in a device word -- for ad_tiles tiles.
     DevBuf adHalf, adMask, adList, adCount;
     size_t ad_pitch = 0;
     int ad_rows = 0, ad_tiles = 0, ad_tiles_x = 0;  // (ad_tiles, ad_tiles_x: the tile grid of the last selection)
-    bool ad_selected = false, adapt_launch = false;
+    bool ad_selected = false;
 
     // Denoising (glrtx_render_features / glrtx_denoise): the two feature planes, the filter's two ping-pong images and its result D, all packed rows of ft_w float4 over
     // ft_rows rows -- the shape of the owned rows when the features were rendered; allocated on first use, released by glrtx_resize (and so by a partition change)
@@ -212,12 +209,11 @@ struct glrtx_ctx {
 
     // Variance guidance (glrtx_track_moments / glrtx_render_moments / glrtx_denoise_variance): the moments plane M {sum l, sum l^2, 0, count} at the accumulator's
     // shape (mm_pitch x mm_rows; allocated on first use while tracking is on, zeroed with the accumulator, released by glrtx_resize and by switching tracking off),
-    // and the filter's three variance planes (V0 and the ping-pong pair: packed floats of the features' shape, released with them).  moments_launch: set only while
-    // glrtx_render_moments issues its launches (launch_wgwf then runs plain, on the context's stream, with sample planes, and folds them with accumulate_moments_kernel).
+    // and the filter's three variance planes (V0 and the ping-pong pair: packed floats of the features' shape, released with them).
     DevBuf mmM, mmM_spare, dnV[3];  // (mmM_spare: the second M the reprojections write, of M's shape, swapped as accum_spare is)
     size_t mm_pitch = 0;
     int mm_rows = 0;
-    bool mm_on = false, moments_launch = false;
+    bool mm_on = false;
 
     // Tone mapping (glrtx_exposure_measure / glrtx_tonemap): the exposure block (tonemap::Exposure: the working histogram, then glrtx_exposure's image; allocated and
     // zeroed on first use, kept across glrtx_resize) and the plane T (packed rows of tm_w float4 over tm_rows rows; released by glrtx_resize)
@@ -262,6 +258,15 @@ int dev_upload(glrtx_ctx *c, DevBuf &b, const void *src, size_t bytes) {
 void dev_free(DevBuf &b) {
     if (b.p) (void)hipFree(b.p);
     b.p = nullptr; b.bytes = 0;
+}
+
+// diagnostic builds only: read and clear a device symbol (the traversal statistics, the step timing, the phase clocks)
+template <class Sym>
+int take_symbol(const Sym &sym, void *out) {
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(sym), sizeof(Sym)) != hipSuccess) return GLRTX_EDEVICE;
+    static const Sym zero{};
+    if (hipMemcpyToSymbol(HIP_SYMBOL(sym), &zero, sizeof(Sym)) != hipSuccess) return GLRTX_EDEVICE;
+    return GLRTX_OK;
 }
 
 int owned_rows_of(int height, int rank, int world, int stripe) {
@@ -807,12 +812,15 @@ DevBuf g_dbg_log_rays, g_dbg_log_trips;
 // to be free on the device, so that the launch shapes, and with them the timing, do not depend on what else runs there (path state does not count: it is addressed by
 // workgroup and queue position, 0.8 GB whatever the frames in flight), and by the 31-bit path ids (frame * pixels + pixel).  GLRTX_FRAMES_BUDGET_MB overrides the default (tests).
 // `slots`: the budget is shared by that many launches that may be in flight at once (fed launches: kFedSlots).
+size_t frames_budget(const glrtx_ctx *c) {  // (this context's share of it)
+    size_t budget = (size_t)kFramesBudgetGiB << 30;
+    if (const char *v = std::getenv("GLRTX_FRAMES_BUDGET_MB")) budget = (size_t)std::max(1, std::atoi(v)) << 20;
+    return budget / (size_t)std::max(c->budget_share, 1);
+}
 int frames_cap(const glrtx_ctx *c, const glrtx_params *p, int slots) {
     const size_t px = (size_t)((c->width + 7) / 8) * (size_t)((c->owned_rows + 7) / 8) * 64;
     const size_t per_frame = (size_t)std::max(p->n_samples, 1) * c->pitch_bytes * (size_t)std::max(c->owned_rows, 1);
-    size_t budget = (size_t)kFramesBudgetGiB << 30;
-    if (const char *v = std::getenv("GLRTX_FRAMES_BUDGET_MB")) budget = (size_t)std::max(1, std::atoi(v)) << 20;
-    budget /= (size_t)std::max(c->budget_share, 1) * (size_t)std::max(slots, 1);
+    const size_t budget = frames_budget(c) / (size_t)std::max(slots, 1);
     const size_t id_cap = (((size_t)1 << 31) - 2) / std::max<size_t>(px, 1);  // path ids (frame * pixels + pixel) stay below 2^31
     return (int)std::max<size_t>(1, std::min<size_t>(id_cap, budget / std::max<size_t>(per_frame, 1)));
 }
@@ -886,7 +894,7 @@ int feed_append(glrtx_ctx *c, const glrtx_params *p, const float *seeds_xy, int 
 }
 
 // ---- presentation (glrtx_ctx::Present)
-bool presenting(const glrtx_ctx *c) { return c->pres.ring > 0 && c->hit_hist_dev == nullptr; }  // (a calibration frame produces no image)
+bool presenting(const glrtx_ctx *c) { return c->pres.ring > 0; }
 
 size_t present_image_bytes(const glrtx_ctx *c) { return (size_t)c->width * 4 * (size_t)c->owned_rows; }
 
@@ -1065,15 +1073,25 @@ bool present_held(const glrtx_ctx *c) {
     return false;
 }
 
-// Variant 2: one persistent launch; every workgroup runs the wavefront trips of the pixels it takes from the frame's tile counter.
-// n_frames > 1 ("frames in flight"): the launch covers n_frames consecutive frames that differ only in u_seed (seeds_xy);
-// the per-sample planes are added to the accumulator in frame order afterwards, so the result is bit-identical to
-// n_frames separate launches.  Three forms (chosen here):
-//   fed        -- on one of the context's pipe slots (own stream, state, queues, tile counter, plane chunks); the launch stays OPEN: later calls with the same camera
-//                 append their frames to it while it runs (feed_append).  Every multi-frame launch on the context's own stream, and a single-frame launch that
-//                 follows another one directly (a burst)
+// ---- a render launch (variant 2).  What one launch is asked for.  The entry points make it and pass it through render_one into launch_wgwf: nothing about a launch travels through the context.
+struct RenderReq {
+    // Ordinary: glrtx_render / glrtx_render_frames.
+    // Adaptive (glrtx_render_adaptive): the ADAPT kernel over the selection's active tiles -- plain, on the context's stream, always with sample planes, never fed.
+    // Moments (glrtx_render_moments): the same shape -- plain, with sample planes, never fed -- on the ordinary kernel; the pass folds the planes into M as well.
+    // Calibration (glrtx_hit_histogram): one plain single-frame launch on the context's stream that counts closest hits per leaf record into `hit_hist` while it shades
+    //     into `scratch` instead of the accumulator: no pipe slot, no ray counting, no presentation step.
+    enum Kind { Ordinary, Adaptive, Moments, Calibration } kind = Ordinary;
+    const float *seeds = nullptr;  // {x, y} per frame; a single frame's seed is the parameters' own
+    int n_frames = 1;
+    unsigned *hit_hist = nullptr; float4 *scratch = nullptr;  // Calibration
+    bool calibration() const { return kind == Calibration; }
+    bool count_rays(const glrtx_ctx *c) const { return c->count_rays && !calibration(); }
+    bool presents(const glrtx_ctx *c) const { return presenting(c) && !calibration(); }
+    float4 *accum(const glrtx_ctx *c) const { return calibration() ? scratch : c->accum; }
+};
+
 // The node fetch the wavefront kernel's traversal uses on this scene (vine: the list scan, fetch 0): 0 one record per lane, 1 pair-cooperative, 2 the two
-// in alternate steps.  Picked by the size of the record array; GLRTX_PAIR_FETCH=0/1/2 overrides (read at every launch).  (See launch_wgwf.)
+// in alternate steps.  Picked by the size of the record array; GLRTX_PAIR_FETCH=0/1/2 overrides (read at every launch).  (See wgwf_kernel.)
 int wgwf_fetch(const glrtx_ctx *c, bool vine) {
     int fetch = vine ? 0 : ((size_t)c->n_fork + (size_t)c->st.n_tri >= (size_t)kPairFetchMinRecords ? 1 : 0);
     if (const char *v = std::getenv("GLRTX_PAIR_FETCH")) fetch = vine ? 0 : std::max(0, std::min(2, std::atoi(v)));
@@ -1096,126 +1114,154 @@ bool wgwf_compact(const glrtx_ctx *c, bool vine, int fetch) {
     return compact;
 }
 
+// Variant 2: one persistent launch; every workgroup runs the wavefront trips of the pixels it takes from the frame's tile counter.
+// n_frames > 1 ("frames in flight"): the launch covers n_frames consecutive frames that differ only in u_seed (seeds_xy);
+// the per-sample planes are added to the accumulator in frame order afterwards (accumulate.hip.h), so the result is bit-identical to
+// n_frames separate launches.  launch_wgwf is the steps below, in order; what they work out about the launch is gathered here.
+using WgwfFn = void (*)(const KernelArgs, const WfArgs, unsigned *, float4 *, const int *, const unsigned *, const VolArgs);
+struct WgwfLaunch {
+    const glrtx_params *p;
+    RenderReq req;
+    const float *seeds_xy;  // n_frames seeds
+    KernelArgs a;
+    // sizes: 8x8 tiles per row, pixels of the whole tiles (path id = frame * total + pixel), one sample plane, one frame's planes
+    int n_frames, n_planes, tiles8_x;
+    size_t total, plane_f4, plane_bytes, frame_bytes;
+    struct Form { bool busy, fed, piped; int fed_cap; } f;  // (wgwf_form)
+    size_t ids;
+    struct Kernel { WgwfFn fn; const char *name; bool vol, vine, compact, adapt; int fetch, lds, per_cu; size_t wg_slots; } k;  // (wgwf_kernel)
+    glrtx_ctx::PipeSlot *slot;  // (wgwf_pipe_slot; null: plain)
+    int pipe_busy, block_paths, grid;
+    bool ctx_state;  // (wgwf_args) the buffers the kernel runs on, its stream, its arguments
+    DevBuf *stateBuf, *queueBuf, *planeBuf;
+    unsigned *workPtr;
+    hipStream_t rstream;
+    size_t state_entries, state_bytes;
+    WfArgs w;
+};
+
+// ---- which form.  Three:
+//   fed        -- on one of the context's pipe slots (own stream, state, queues, tile counter, plane chunks); the launch stays OPEN: later calls with the same camera
+//                 append their frames to it while it runs (feed_append).  Every multi-frame launch on the context's own stream, and a single-frame launch that
+//                 follows another one directly (a burst)
 //   overlapped -- a single-frame launch on a pipe slot, the frame spread over all workgroup slots in one helping, slots handed over progressively (round 3): what a
 //                 caller gets that renders, resolves and saves every frame -- the reference's loop, window.cpp:121-169 -- and any single frame on a caller's stream
-//   plain      -- on the context's stream, nothing overlaps: multi-frame launches on a caller's stream (stream order is the caller's), GLRTX_NO_PIPELINE=1
-int launch_wgwf(glrtx_ctx *c, const KernelArgs &a_in, const glrtx_params *p, const float *seeds_xy, int n_frames) {
-    KernelArgs a = a_in;
-    const int tiles8_x = (c->width + 7) / 8, tiles8_y = (c->owned_rows + 7) / 8;
-    const size_t total = (size_t)tiles8_x * tiles8_y * 64;
-    if (total * 2 >= (size_t)INT32_MAX) return fail(c, GLRTX_EINVAL, "image too large for the wgwf variant");
-    const size_t plane_bytes = (size_t)a.pitch_f4 * (size_t)c->owned_rows * sizeof(float4);
-    const size_t frame_bytes = (size_t)std::max(p->n_samples, 1) * plane_bytes;
-    int rc;
-    // ---- which form
+//   plain      -- on the context's stream, nothing overlaps: multi-frame launches on a caller's stream (stream order is the caller's), GLRTX_NO_PIPELINE=1, and every
+//                 launch that is not an ordinary one (RenderReq)
+WgwfLaunch::Form wgwf_form(glrtx_ctx *c, const WgwfLaunch &L) {
+    const glrtx_params *p = L.p;
+    WgwfLaunch::Form f{};
     // (busy: the context's last render kernel -- a slot's, or one on the context's stream -- has not ended yet)
-    const bool busy = c->last_render_done && hipEventQuery(c->last_render_done) == hipErrorNotReady;
+    f.busy = c->last_render_done && hipEventQuery(c->last_render_done) == hipErrorNotReady;
     (void)hipGetLastError();
-    const bool burst = c->last_was_render && busy && same_camera(c->last_p, *p);
-    const bool adapt = c->adapt_launch;  // (glrtx_render_adaptive: plain, on the context's stream, always with sample planes; never fed)
-    const bool vol = c->ext_flags != 0;  // the V form (kWgwfVolume): routed here only with the volume alone (wgwf_routes)
-    const bool moments = c->moments_launch;  // (glrtx_render_moments: the same shape -- plain, with sample planes, never fed -- on the ordinary kernel)
-    bool fed = !adapt && !moments && c->feed_ok && std::getenv("GLRTX_NO_FEED") == nullptr && c->pipeline && c->stream == c->own_stream && p->n_samples >= 1 && seeds_xy != nullptr && (n_frames > 1 || burst);
-    int fed_cap = fed ? std::min(frames_cap(c, p, (int)kFedSlots), kFeedMaxFrames) : 0;
-    if (const char *v = std::getenv("GLRTX_FEED_CAP")) fed_cap = std::max(1, std::min(fed_cap, std::atoi(v)));  // (tests: launches that fill up)
-    if (fed && n_frames > fed_cap) fed = false;
-    bool piped = fed || (!adapt && !moments && n_frames == 1 && c->pipeline && p->n_samples >= 1 && (size_t)p->n_samples * plane_bytes <= ((size_t)1 << 30));
-    const size_t ids = total * (size_t)(fed ? fed_cap : n_frames);  // path id = frame * total + pixel
-    if (ids + 1 >= (size_t)UINT32_MAX)
-        return fail(c, GLRTX_EINVAL, "glrtx_render_frames: %d frames of %zu pixels exceed the 32-bit ray id space", n_frames, total);
+    const bool burst = c->last_was_render && f.busy && same_camera(c->last_p, *p);
+    const bool ordinary = L.req.kind == RenderReq::Ordinary;
+    f.fed = ordinary && c->feed_ok && std::getenv("GLRTX_NO_FEED") == nullptr && c->pipeline && c->stream == c->own_stream && p->n_samples >= 1 && L.seeds_xy != nullptr &&
+            (L.n_frames > 1 || burst);
+    f.fed_cap = f.fed ? std::min(frames_cap(c, p, (int)kFedSlots), kFeedMaxFrames) : 0;
+    if (const char *v = std::getenv("GLRTX_FEED_CAP")) f.fed_cap = std::max(1, std::min(f.fed_cap, std::atoi(v)));  // (tests: launches that fill up)
+    if (f.fed && L.n_frames > f.fed_cap) f.fed = false;
+    f.piped = f.fed || (ordinary && L.n_frames == 1 && c->pipeline && p->n_samples >= 1 && (size_t)p->n_samples * L.plane_bytes <= ((size_t)1 << 30));
+    return f;
+}
 
-    // ---- the kernel and how many of its workgroups fit the device.  Eight instantiations: ray counting on/off x (list scan of a vine (brute-force) tree | tree traversal
-    // with one record per lane | with the pair-cooperative node fetch | with the two in alternate steps).  The pair fetch trades 25 vector-ALU instructions per step for a
-    // third less time in the CU's vector-memory pipe (trav_asm.hip.h): it pays where a wave's lanes are spread over many records -- large trees, incoherent rays: config 5
-    // (100 k triangles) -9 % per frame -- and costs ~1 % where they share the top of a small tree (headline, 10 k triangles: the step is paced by instruction issue there),
-    // profiles/r04_ab_pair_fetch.txt.  Picked by the size of the record array; GLRTX_PAIR_FETCH=0/1 overrides.  All forms are bit-identical (same IEEE operations on the same record).
-    // On small trees the two forms in alternate steps (FETCH 2: the pipe is the busier unit in one step, the SIMDs in the next) beat both by 1.0 .. 1.3 % in round 4.
-    // Since the path state is read and written by queue position (WfArgs::state) the pipe has a fifth less to do and the plain form wins there: headline -0.7 %,
-    // config 2 -0.4 %, config 4 -1.0 % against the alternating one, the pure pair form +1.9 % (profiles/r05_state_by_position.txt).  The alternating form stays
-    // compiled in (GLRTX_PAIR_FETCH=2).  Random triangle soups prefer the pair form from 10 k triangles on (-2 %; 20 k: -4.5 %, 70 k: -7 %): what decides is how
-    // far apart a wave's rays are in the tree, which the record count only approximates.
-    // The V form has one fetch form only: one record per lane on DevScene::nodes, as in the megakernels (no list scan, no pair fetch, no compact layout).
-    using Kernel = void (*)(const KernelArgs, const WfArgs, unsigned *, float4 *, const int *, const unsigned *, const VolArgs);
-    const bool vine = c->sc.n_vine > 0 && !vol;
-    int fetch = vol ? 0 : wgwf_fetch(c, vine);
-    c->st.node_fetch_last = fetch;
-    // The compact node array (pack_compact): wgwf_compact.
-    const int lds_base = wgwf_lds_base(c);
-    const int lds_compact = lds_base + c->sc.n_crank * (int)sizeof(uint2);  // | rank table
-    bool compact = !vol && wgwf_compact(c, vine, fetch);
-    c->st.node_layout_last = compact ? 1 : 0;
-    const bool cr = c->count_rays;
-    constexpr int A = kWgwfAdaptive;  // (the ADAPT forms of the same eight: glrtx_render_adaptive)
-    constexpr int CP = kWgwfCompact;
-    constexpr int V = kWgwfVolume;  // (the V form: glrtx_set_volume_wavefront)
-    const Kernel kernel = vol ? (adapt ? (cr ? (Kernel)pt_render_wgwf<true, false, V | A> : (Kernel)pt_render_wgwf<false, false, V | A>)
-                                       : (cr ? (Kernel)pt_render_wgwf<true, false, V> : (Kernel)pt_render_wgwf<false, false, V>))
-                        : compact ? (adapt ? (cr ? (Kernel)pt_render_wgwf<true, false, CP | A> : (Kernel)pt_render_wgwf<false, false, CP | A>)
-                                           : (cr ? (Kernel)pt_render_wgwf<true, false, CP> : (Kernel)pt_render_wgwf<false, false, CP>))
-                        : adapt ? (vine ? (cr ? (Kernel)pt_render_wgwf<true, true, A> : (Kernel)pt_render_wgwf<false, true, A>)
-                                   : fetch == 2 ? (cr ? (Kernel)pt_render_wgwf<true, false, 2 | A> : (Kernel)pt_render_wgwf<false, false, 2 | A>)
-                                   : fetch == 1 ? (cr ? (Kernel)pt_render_wgwf<true, false, 1 | A> : (Kernel)pt_render_wgwf<false, false, 1 | A>)
-                                                : (cr ? (Kernel)pt_render_wgwf<true, false, A> : (Kernel)pt_render_wgwf<false, false, A>))
-                        : vine ? (cr ? (Kernel)pt_render_wgwf<true, true> : (Kernel)pt_render_wgwf<false, true>)
-                        : fetch == 2 ? (cr ? (Kernel)pt_render_wgwf<true, false, 2> : (Kernel)pt_render_wgwf<false, false, 2>)
-                        : fetch == 1 ? (cr ? (Kernel)pt_render_wgwf<true, false, 1> : (Kernel)pt_render_wgwf<false, false, 1>)
-                                     : (cr ? (Kernel)pt_render_wgwf<true, false, 0> : (Kernel)pt_render_wgwf<false, false, 0>);
+// ---- the kernel and how many of its workgroups fit the device.  Eight instantiations: ray counting on/off x (list scan of a vine (brute-force) tree | tree traversal
+// with one record per lane | with the pair-cooperative node fetch | with the two in alternate steps).  The pair fetch trades 25 vector-ALU instructions per step for a
+// third less time in the CU's vector-memory pipe (trav_asm.hip.h): it pays where a wave's lanes are spread over many records -- large trees, incoherent rays: config 5
+// (100 k triangles) -9 % per frame -- and costs ~1 % where they share the top of a small tree (headline, 10 k triangles: the step is paced by instruction issue there),
+// profiles/r04_ab_pair_fetch.txt.  Picked by the size of the record array; GLRTX_PAIR_FETCH=0/1 overrides.  All forms are bit-identical (same IEEE operations on the same record).
+// On small trees the two forms in alternate steps (FETCH 2: the pipe is the busier unit in one step, the SIMDs in the next) beat both by 1.0 .. 1.3 % in round 4.
+// Since the path state is read and written by queue position (WfArgs::state) the pipe has a fifth less to do and the plain form wins there: headline -0.7 %,
+// config 2 -0.4 %, config 4 -1.0 % against the alternating one, the pure pair form +1.9 % (profiles/r05_state_by_position.txt).  The alternating form stays
+// compiled in (GLRTX_PAIR_FETCH=2).  Random triangle soups prefer the pair form from 10 k triangles on (-2 %; 20 k: -4.5 %, 70 k: -7 %): what decides is how
+// far apart a wave's rays are in the tree, which the record count only approximates.
+// The compact node array (pack_compact) has its own four: wgwf_compact.
+// The V form (kWgwfVolume: glrtx_set_volume_wavefront; routed here only with the volume alone, wgwf_routes) has one fetch form only: one record per lane on
+// DevScene::nodes, as in the megakernels (no list scan, no pair fetch, no compact layout).
+// Each of the six has its ADAPT twin (kWgwfAdaptive: glrtx_render_adaptive): 24 instantiations, one table.
+enum WgwfTrav { kTravVine, kTravFetch0, kTravFetch1, kTravFetch2, kTravCompact, kTravVolume, kTravForms };
+#define GLRTX_WGWF_ROW(VINE, FLAGS) {{pt_render_wgwf<false, VINE, FLAGS>, pt_render_wgwf<true, VINE, FLAGS>}, \
+                                     {pt_render_wgwf<false, VINE, (FLAGS) | kWgwfAdaptive>, pt_render_wgwf<true, VINE, (FLAGS) | kWgwfAdaptive>}}
+constexpr WgwfFn kWgwfKernels[kTravForms][2][2] = {  // [traversal][adaptive][count_rays]
+    GLRTX_WGWF_ROW(true, 0), GLRTX_WGWF_ROW(false, 0), GLRTX_WGWF_ROW(false, 1), GLRTX_WGWF_ROW(false, 2), GLRTX_WGWF_ROW(false, kWgwfCompact), GLRTX_WGWF_ROW(false, kWgwfVolume)};
+#undef GLRTX_WGWF_ROW
+constexpr const char *kWgwfNames[3][2] = {  // [list scan | tree | volume][adaptive] (error reports)
+    {"pt_render_wgwf (list scan)", "pt_render_wgwf (adaptive, list scan)"}, {"pt_render_wgwf", "pt_render_wgwf (adaptive)"}, {"pt_render_wgwf (volume)", "pt_render_wgwf (volume, adaptive)"}};
+
+int wgwf_kernel(glrtx_ctx *c, WgwfLaunch &L) {
+    WgwfLaunch::Kernel &k = L.k;
+    k.vol = c->ext_flags != 0;
+    k.adapt = L.req.kind == RenderReq::Adaptive;
+    k.vine = c->sc.n_vine > 0 && !k.vol;
+    k.fetch = k.vol ? 0 : wgwf_fetch(c, k.vine);
+    c->st.node_fetch_last = k.fetch;
+    k.compact = !k.vol && wgwf_compact(c, k.vine, k.fetch);
+    c->st.node_layout_last = k.compact ? 1 : 0;
+    const int trav = k.vol ? kTravVolume : k.compact ? kTravCompact : k.vine ? kTravVine : kTravFetch0 + k.fetch;
+    k.fn = kWgwfKernels[trav][k.adapt][L.req.count_rays(c)];
+    k.name = kWgwfNames[k.vol ? 2 : k.vine ? 0 : 1][k.adapt];
     // (north_star's "primitives staged into LDS": materials, camera block, root box and the per-lane stacks are; the top tree levels were built, measured worth
     // nothing -- profiles/r02_lds_top.json -- and removed.)
-    const int lds = compact ? lds_compact : lds_base;
-    if (lds > 160 * 1024) return fail(c, GLRTX_EDEVICE, "wgwf kernel needs %d B of LDS (> 160 KiB)", lds);
-    if (lds > 64 * 1024) HIP_TRY(c, hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    int per_cu = 0;
-    HIP_TRY(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kBlockThreads, lds));
+    k.lds = wgwf_lds_base(c) + (k.compact ? c->sc.n_crank * (int)sizeof(uint2) : 0);  // | rank table
+    if (k.lds > 160 * 1024) return fail(c, GLRTX_EDEVICE, "wgwf kernel needs %d B of LDS (> 160 KiB)", k.lds);
+    if (k.lds > 64 * 1024) HIP_TRY(c, hipFuncSetAttribute((const void *)k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, k.lds));
+    k.per_cu = 0;
+    HIP_TRY(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&k.per_cu, k.fn, kBlockThreads, k.lds));
     // (launch_bounds' second argument is a minimum, not a cap: an instantiation with little LDS may be reported with more workgroups per CU than the buffers below are
     //  sized for -- ADVICE round 5)
-    per_cu = std::max(1, std::min(per_cu, GLRTX_WGWF_WAVES));
-    if (const char *v = std::getenv("GLRTX_WGS_PER_CU")) per_cu = std::max(1, std::min(per_cu, std::atoi(v)));  // occupancy experiments
-    const size_t wg_slots = (size_t)c->n_cu * (size_t)per_cu;
-    const size_t queue_bytes_max = wg_slots * kWgQueueF4 * sizeof(float4);
+    k.per_cu = std::max(1, std::min(k.per_cu, GLRTX_WGWF_WAVES));
+    if (const char *v = std::getenv("GLRTX_WGS_PER_CU")) k.per_cu = std::max(1, std::min(k.per_cu, std::atoi(v)));  // occupancy experiments
+    k.wg_slots = (size_t)c->n_cu * (size_t)k.per_cu;
+    return GLRTX_OK;
+}
 
-    // ---- a pipe slot (fed and overlapped launches).  A slot owns path state, per-workgroup queues and sample planes of its own (~0.8 GB at 1080p for an overlapped
-    // single frame, 1.4 GB + planes for a fed launch): the slots are charged to the same memory budget as the frames in flight (kFramesBudgetGiB, split between the members
-    // of a group that share this GPU), a slot whose buffers cannot be allocated is given up -- the launch then runs plain on the context's stream instead of failing -- and
-    // among the slots in use the next one whose previous launch has completed is taken (round robin only when none has), so that a launch never queues behind a busy slot
-    // while an idle one exists.
-    // Shapes.  plain / fed: every workgroup keeps up to kWgPathsMax paths alive, less when the launch is short (below; a fed launch is sized as if it were to take
-    // 16 frames: it may).  overlapped, issued while the context's last launch is still rendering: the frame in ONE helping per workgroup, spread over all the slots (the smallest power of two that holds
-    // work / resident paths: 2048 at 1080p; with 1024 the workgroups come back for a second helping, 1.31 instead of 1.24 ms per frame, with 4096 half of them get
-    // nothing, 1.67), every launch has the full grid and takes its tiles without guided self-scheduling, so its workgroups do not finish together -- one that finds the
-    // tile counter exhausted and its paths dead leaves, and a workgroup of the next launch (queued on another stream) takes the slot (profiles/r03_ab_pipeline.txt).
-    auto shape = [&](bool overlapped, bool is_fed, int share, bool device_busy, int &block_paths, int &grid) {
-        const int resident = std::max(1, per_cu / std::max(share, 1)) * c->n_cu;
-        const size_t work = total * (size_t)(is_fed ? std::max(n_frames, std::min(16, fed_cap)) : n_frames);
-        block_paths = kWgPathsMax;
-        if (overlapped && device_busy) { block_paths = 256; while (block_paths < kWgPathsMax && (size_t)resident * block_paths < work) block_paths *= 2; }
-        else {
-            // A launch ends with a tail in which its last paths run out -- about one path item's lifetime, and an item is a pixel's n_samples samples in sequence
-            // (their random numbers are one chain) -- and nothing overlaps that tail when the launch is alone on the device (plain, fed, or a single frame issued
-            // to an idle device).  Fewer paths per workgroup mean more, shorter helpings and a shorter tail, but slower trips: the most paths that still give the
-            // launch two helpings per workgroup (several frames of one sample per pixel) or four (more samples: longer items; a single frame: its tail is as long
-            // as the rest of it).  Lone launches, profiles/r06_launch_shapes.txt: 1080p 1 spp, one frame 2.4 -> 1.67 ms (config 2: 2.1 -> 1.39, config 3: 17.0 -> 11.4,
-            // config 5: 4.6 -> 3.1); 16 spp, one frame 39 -> 24 ms, four frames 19.4 -> 18.5; config 4 (4K, 16 spp), one frame 51 -> 39 ms.
-            const size_t tenths = (p->n_samples > 1 || (n_frames == 1 && !is_fed)) ? 39 : 19;
-            while (block_paths > 512 && work * 10 < tenths * (size_t)resident * block_paths) block_paths /= 2;
-            while (block_paths > 256 && work < (size_t)resident * block_paths) block_paths /= 2;  // (small images: every workgroup of the grid has a full helping)
-        }
-        if (const char *v = std::getenv("GLRTX_BLOCK_PATHS")) { const int x = std::atoi(v); if (x >= 256 && x <= kWgPathsMax && (x & (x - 1)) == 0) block_paths = x; }
-        grid = std::max(1, (int)std::min<size_t>((size_t)resident, (work + block_paths - 1) / block_paths));
-    };
-    glrtx_ctx::PipeSlot *slot = nullptr;
-    int pipe_busy = 0, block_paths = 0, grid = 0;
-    if (piped) {
-        shape(!fed, fed, 1, busy, block_paths, grid);
+// ---- the launch's shape.  plain / fed: every workgroup keeps up to kWgPathsMax paths alive, less when the launch is short (below; a fed launch is sized as if it were to take
+// 16 frames: it may).  overlapped, issued while the context's last launch is still rendering: the frame in ONE helping per workgroup, spread over all the slots (the smallest power of two that holds
+// work / resident paths: 2048 at 1080p; with 1024 the workgroups come back for a second helping, 1.31 instead of 1.24 ms per frame, with 4096 half of them get
+// nothing, 1.67), every launch has the full grid and takes its tiles without guided self-scheduling, so its workgroups do not finish together -- one that finds the
+// tile counter exhausted and its paths dead leaves, and a workgroup of the next launch (queued on another stream) takes the slot (profiles/r03_ab_pipeline.txt).
+void wgwf_shape(const glrtx_ctx *c, const WgwfLaunch &L, bool overlapped, bool is_fed, int share, bool device_busy, int &block_paths, int &grid) {
+    const int n_frames = L.n_frames, fed_cap = L.f.fed_cap, n_samples = L.p->n_samples;
+    const size_t total = L.total;
+    const int resident = std::max(1, L.k.per_cu / std::max(share, 1)) * c->n_cu;
+    const size_t work = total * (size_t)(is_fed ? std::max(n_frames, std::min(16, fed_cap)) : n_frames);
+    block_paths = kWgPathsMax;
+    if (overlapped && device_busy) { block_paths = 256; while (block_paths < kWgPathsMax && (size_t)resident * block_paths < work) block_paths *= 2; }
+    else {
+        // A launch ends with a tail in which its last paths run out -- about one path item's lifetime, and an item is a pixel's n_samples samples in sequence
+        // (their random numbers are one chain) -- and nothing overlaps that tail when the launch is alone on the device (plain, fed, or a single frame issued
+        // to an idle device).  Fewer paths per workgroup mean more, shorter helpings and a shorter tail, but slower trips: the most paths that still give the
+        // launch two helpings per workgroup (several frames of one sample per pixel) or four (more samples: longer items; a single frame: its tail is as long
+        // as the rest of it).  Lone launches, profiles/r06_launch_shapes.txt: 1080p 1 spp, one frame 2.4 -> 1.67 ms (config 2: 2.1 -> 1.39, config 3: 17.0 -> 11.4,
+        // config 5: 4.6 -> 3.1); 16 spp, one frame 39 -> 24 ms, four frames 19.4 -> 18.5; config 4 (4K, 16 spp), one frame 51 -> 39 ms.
+        const size_t tenths = (n_samples > 1 || (n_frames == 1 && !is_fed)) ? 39 : 19;
+        while (block_paths > 512 && work * 10 < tenths * (size_t)resident * block_paths) block_paths /= 2;
+        while (block_paths > 256 && work < (size_t)resident * block_paths) block_paths /= 2;  // (small images: every workgroup of the grid has a full helping)
+    }
+    if (const char *v = std::getenv("GLRTX_BLOCK_PATHS")) { const int x = std::atoi(v); if (x >= 256 && x <= kWgPathsMax && (x & (x - 1)) == 0) block_paths = x; }
+    grid = std::max(1, (int)std::min<size_t>((size_t)resident, (work + block_paths - 1) / block_paths));
+}
+
+// ---- a pipe slot (fed and overlapped launches).  A slot owns path state, per-workgroup queues and sample planes of its own (~0.8 GB at 1080p for an overlapped
+// single frame, 1.4 GB + planes for a fed launch): the slots are charged to the same memory budget as the frames in flight (kFramesBudgetGiB, split between the members
+// of a group that share this GPU), a slot whose buffers cannot be allocated is given up -- the launch then runs plain on the context's stream instead of failing -- and
+// among the slots in use the next one whose previous launch has completed is taken (round robin only when none has), so that a launch never queues behind a busy slot
+// while an idle one exists.  Leaves L.slot (null: the launch runs plain) and the launch's shape.
+int wgwf_pipe_slot(glrtx_ctx *c, WgwfLaunch &L) {
+    WgwfLaunch::Form &f = L.f;
+    const int n_frames = L.n_frames;
+    const size_t frame_bytes = L.frame_bytes;
+    glrtx_ctx::PipeSlot *&slot = L.slot = nullptr;
+    int &pipe_busy = L.pipe_busy = 0, &block_paths = L.block_paths = 0, &grid = L.grid = 0;
+    if (f.piped) {
+        const bool fed = f.fed, busy = f.busy;
+        wgwf_shape(c, L, !fed, fed, 1, busy, block_paths, grid);
         // (an overlapped slot's path state holds either of a single frame's two shapes -- issued to an idle or to a busy device: growing it later would free memory, and
         //  freeing waits for the device)
         size_t slot_state_entries = (size_t)grid * block_paths;
-        if (!fed) { int b2 = 0, g2 = 0; shape(true, false, 1, !busy, b2, g2); slot_state_entries = std::max(slot_state_entries, (size_t)g2 * b2); }
+        if (!fed) { int b2 = 0, g2 = 0; wgwf_shape(c, L, true, false, 1, !busy, b2, g2); slot_state_entries = std::max(slot_state_entries, (size_t)g2 * b2); }
         const size_t per_slot = (fed ? 0 : (size_t)kWfStatePlanes * slot_state_entries * sizeof(float4)) + (size_t)grid * kWgQueueF4 * sizeof(float4) + (fed ? 0 : frame_bytes);
-        size_t budget = (size_t)kFramesBudgetGiB << 30;
-        if (const char *v = std::getenv("GLRTX_FRAMES_BUDGET_MB")) budget = (size_t)std::max(1, std::atoi(v)) << 20;
-        budget /= (size_t)std::max(c->budget_share, 1);
-        unsigned allowed = (unsigned)std::min<size_t>(c->pipe_slots, budget / std::max<size_t>(per_slot, 1));
+        unsigned allowed = (unsigned)std::min<size_t>(c->pipe_slots, frames_budget(c) / std::max<size_t>(per_slot, 1));
         if (fed) allowed = std::min(allowed, kFedSlots);
         c->st.pipe_slots = (int32_t)allowed;
         if (allowed >= 1) {
@@ -1230,7 +1276,7 @@ int launch_wgwf(glrtx_ctx *c, const KernelArgs &a_in, const glrtx_params *p, con
             for (unsigned k = 0; k < kPipeSlots; k++)
                 if (k != pick && c->pipe[k].used && hipEventQuery(c->pipe[k].render_done) == hipErrorNotReady) pipe_busy++;
             (void)hipGetLastError();
-            if (c->pipe_share > 1 && pipe_busy > 0 && !fed) shape(true, false, c->pipe_share, busy, block_paths, grid);  // (GLRTX_PIPE_SHARE: the round-3 form, A/B only)
+            if (c->pipe_share > 1 && pipe_busy > 0 && !fed) wgwf_shape(c, L, true, false, c->pipe_share, busy, block_paths, grid);  // (GLRTX_PIPE_SHARE: the round-3 form, A/B only)
             // the slot's buffers, before anything depends on them.  A fed launch's plane chunks hold a given number of bytes per frame: another size starts afresh
             // (the slot's last launch is waited for first: freeing memory waits for the device anyway)
             bool ok = true;
@@ -1245,7 +1291,7 @@ int launch_wgwf(glrtx_ctx *c, const KernelArgs &a_in, const glrtx_params *p, con
             }
             if (!fed) ok = ok && ensure(c, slot->state, (size_t)kWfStatePlanes * slot_state_entries * sizeof(float4)) == GLRTX_OK;
             ok = ok && ensure(c, slot->queues, (size_t)grid * kWgQueueF4 * sizeof(float4)) == GLRTX_OK;
-            if (fed) ok = ok && ensure(c, slot->feed_d, sizeof(FeedDev)) == GLRTX_OK && feed_ensure_chunks(c, *slot, 0, n_frames, fed_cap, frame_bytes) == GLRTX_OK;
+            if (fed) ok = ok && ensure(c, slot->feed_d, sizeof(FeedDev)) == GLRTX_OK && feed_ensure_chunks(c, *slot, 0, n_frames, f.fed_cap, frame_bytes) == GLRTX_OK;
             else ok = ok && ensure(c, slot->planes, frame_bytes) == GLRTX_OK;
             if (!ok) {
                 (void)hipGetLastError();
@@ -1269,65 +1315,73 @@ int launch_wgwf(glrtx_ctx *c, const KernelArgs &a_in, const glrtx_params *p, con
                 pipe_busy = 0;
             }
         }
-        if (!slot) { piped = false; fed = false; }
+        if (!slot) { f.piped = false; f.fed = false; }
     }
     if (!slot) {
-        if (n_frames > frames_cap(c, p, 1)) return fail(c, GLRTX_ENOMEM, "glrtx_render_frames: %d frames exceed the frames-in-flight memory budget", n_frames);
-        shape(false, false, 1, busy, block_paths, grid);
+        if (n_frames > frames_cap(c, L.p, 1)) return fail(c, GLRTX_ENOMEM, "glrtx_render_frames: %d frames exceed the frames-in-flight memory budget", n_frames);
+        wgwf_shape(c, L, false, false, 1, f.busy, block_paths, grid);
     }
     if (slot) c->st.pipe_resident_max = std::max<int32_t>(c->st.pipe_resident_max, pipe_busy + 1);
+    return GLRTX_OK;
+}
+
+// ---- the buffers the kernel runs on, and its arguments
+int wgwf_args(glrtx_ctx *c, WgwfLaunch &L) {
+    const glrtx_params *p = L.p;
+    glrtx_ctx::PipeSlot *const slot = L.slot;
+    const bool fed = L.f.fed, adapt = L.k.adapt, moments = L.req.kind == RenderReq::Moments;
+    const int n_frames = L.n_frames, grid = L.grid;
+    int rc;
     // A fed launch runs on its slot's stream and queues but on the CONTEXT's path state, like a plain launch: the same launch is 0.8 % faster there than on a slot's state
     // buffer (same-context A/B, two boxes, profiles/r06_ab_feed_cadence.txt -- where a 0.8-GB buffer lands physically decides what its stream of stores costs:
-    // profiles/r04_context_regimes.txt).  Launches that share that buffer run one after the other (state_done below): fed launches end all their workgroups together,
+    // profiles/r04_context_regimes.txt).  Launches that share that buffer run one after the other (state_done in wgwf_issue): fed launches end all their workgroups together,
     // so there was nothing for them to overlap with anyway.
-    const bool ctx_state = !slot || fed;
-    DevBuf &stateBuf = ctx_state ? c->wfState : slot->state;
-    DevBuf &queueBuf = slot ? slot->queues : c->wfQ;
-    DevBuf &planeBuf = slot ? slot->planes : c->wfPlanes;
-    unsigned *const workPtr = (unsigned *)(slot ? slot->work.p : c->work.p);
-    const hipStream_t rstream = slot ? slot->stream : c->stream;  // the render kernel's stream
+    L.ctx_state = !slot || fed;
+    L.stateBuf = L.ctx_state ? &c->wfState : &slot->state;
+    L.queueBuf = slot ? &slot->queues : &c->wfQ;
+    L.planeBuf = slot ? &slot->planes : &c->wfPlanes;
+    L.workPtr = (unsigned *)(slot ? slot->work.p : c->work.p);
+    L.rstream = slot ? slot->stream : c->stream;  // the render kernel's stream
     // path state: two sets of six planes, an entry per workgroup of THIS launch and path-queue position (WfArgs::state): 0.8 GB for a full grid with kWgPathsMax paths
     // each, kilobytes for a small image (it used to be sized for the largest launch the device can hold, whatever the launch)
-    const size_t state_entries = (size_t)grid * (size_t)block_paths;
-    const size_t state_bytes = (size_t)kWfStatePlanes * state_entries * sizeof(float4);
-    if ((rc = ensure(c, stateBuf, state_bytes))) return rc;
-    if ((rc = ensure(c, queueBuf, (size_t)grid * kWgQueueF4 * sizeof(float4)))) return rc;  // per-workgroup queues
-    WfArgs w;
+    L.state_entries = (size_t)grid * (size_t)L.block_paths;
+    L.state_bytes = (size_t)kWfStatePlanes * L.state_entries * sizeof(float4);
+    if ((rc = ensure(c, *L.stateBuf, L.state_bytes))) return rc;
+    if ((rc = ensure(c, *L.queueBuf, (size_t)grid * kWgQueueF4 * sizeof(float4)))) return rc;  // per-workgroup queues
+    WfArgs &w = L.w;
     std::memset(&w, 0, sizeof w);
-    w.state = (float4 *)stateBuf.p;
-    w.ids = state_entries;  // (the plane stride)
-    c->st.wf_state_mib = (int32_t)((state_bytes + ((size_t)1 << 20) - 1) >> 20);
-    w.total = (int)total;
-    w.tiles8_x = tiles8_x;
+    w.state = (float4 *)L.stateBuf->p;
+    w.ids = L.state_entries;  // (the plane stride)
+    c->st.wf_state_mib = (int32_t)((L.state_bytes + ((size_t)1 << 20) - 1) >> 20);
+    w.total = (int)L.total;
+    w.tiles8_x = L.tiles8_x;
     w.refill_min = kRefillMin;
     if (const char *v = std::getenv("GLRTX_REFILL_MIN")) w.refill_min = std::max(1, std::min(64, std::atoi(v)));
-    w.n_frames = fed ? std::max(fed_cap, 2) : n_frames;  // (fed: the most frames the launch can take -- and > 1, so that path ids are split into frame and pixel)
-    w.tiles_per_frame = (int)(total >> 6);
-    const size_t plane_f4 = (size_t)a.pitch_f4 * (size_t)c->owned_rows;
-    const int n_planes = n_frames * p->n_samples;
+    w.n_frames = fed ? std::max(L.f.fed_cap, 2) : n_frames;  // (fed: the most frames the launch can take -- and > 1, so that path ids are split into frame and pixel)
+    w.tiles_per_frame = (int)(L.total >> 6);
     if (fed) {
         FeedHost *fh = slot->feed_h;
-        for (int i = 0; i < n_frames; i++) fh->seeds[i] = make_float2(seeds_xy[2 * i], seeds_xy[2 * i + 1]);
+        for (int i = 0; i < n_frames; i++) fh->seeds[i] = make_float2(L.seeds_xy[2 * i], L.seeds_xy[2 * i + 1]);
         __atomic_store_n(&fh->frames_pub, (unsigned)n_frames, __ATOMIC_RELEASE);
         w.feed_host = slot->feed_h_dev;
         w.feed_dev = (FeedDev *)slot->feed_d.p;
-        w.feed_plane_f4 = plane_f4;
+        w.feed_plane_f4 = L.plane_f4;
         w.feed_margin = 64 * 4 * grid;  // where guided self-scheduling starts to taper the helpings (gss_div x 64 tiles)
         if (const char *v = std::getenv("GLRTX_FEED_MARGIN")) w.feed_margin = std::max(0, std::atoi(v));
     } else {
         if (n_frames > 1) {
             if ((rc = ensure(c, c->wfSeeds, (size_t)n_frames * sizeof(float2)))) return rc;
-            HIP_TRY(c, hipMemcpyAsync(c->wfSeeds.p, seeds_xy, (size_t)n_frames * sizeof(float2), hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(c, hipMemcpyAsync(c->wfSeeds.p, L.seeds_xy, (size_t)n_frames * sizeof(float2), hipMemcpyHostToDevice, c->stream));
             w.seeds = (const float2 *)c->wfSeeds.p;
             w.seeds_in_lds = n_frames <= kLdsSeeds ? 1 : 0;
         }
         if (n_frames > 1 || slot || adapt || moments) {
-            if ((rc = ensure(c, planeBuf, (size_t)std::max(n_planes, 1) * plane_f4 * sizeof(float4)))) return rc;
-            w.planes = (float4 *)planeBuf.p;
+            if ((rc = ensure(c, *L.planeBuf, (size_t)std::max(L.n_planes, 1) * L.plane_f4 * sizeof(float4)))) return rc;
+            w.planes = (float4 *)L.planeBuf->p;
         }
     }
-    w.block_paths = block_paths;
-    w.gss_div = (slot && !fed) ? 0 : 4 * grid;  // (overlapped single-frame launches: no guided self-scheduling, see `shape` above)
+    w.block_paths = L.block_paths;
+    w.gss_div = (slot && !fed) ? 0 : 4 * grid;  // (overlapped single-frame launches: no guided self-scheduling, see wgwf_shape)
     if (const char *v = std::getenv("GLRTX_GSS_DIV")) w.gss_div = std::max(0, std::atoi(v));
     w.suspend_max = kSuspendMax;
     if (const char *v = std::getenv("GLRTX_SUSPEND_MAX")) w.suspend_max = std::max(0, std::min(64, std::atoi(v)));
@@ -1337,61 +1391,84 @@ int launch_wgwf(glrtx_ctx *c, const KernelArgs &a_in, const glrtx_params *p, con
     // The V form: a bounce through a medium takes up to nine shaded trips instead of one -- the media hit that queues trial 1, then trials 1 .. 8, the last of which
     // queues the exit ray (the next bounce's path ray) -- and every such bounce ends the sample or advances the depth.  So a sample is alive for at most
     // 9 x (max_depth + 2) shaded trips, and the bound is nine times the plain one: 64 x n_samples x 9 x (max_depth + 2) + 64.
-    if (vol) w.trip_limit = (int)std::min<long long>(INT32_MAX, 64ll * std::max(p->n_samples, 1) * 9 * (p->max_depth + 2) + 64);
+    if (L.k.vol) w.trip_limit = (int)std::min<long long>(INT32_MAX, 64ll * std::max(p->n_samples, 1) * 9 * (p->max_depth + 2) + 64);
     if (const char *v = std::getenv("GLRTX_TRIP_LIMIT")) w.trip_limit = std::max(1, std::atoi(v));
     w.err = c->guard_dev;
-    // Shape invariants of the hand-written kernel, checked on the host before every launch (an access past one of these
-    // buffers is a GPU memory fault, not an error code): every path id the launch can form indexes inside the state arrays;
-    // every workgroup of the grid has its own queue slice; a slice holds both halves of the double-buffered ray queue
-    // (2 rays per live path: the next ray and the shadow ray) and of the path-id queue; every (frame, sample) has its plane.
-    {
-        const size_t max_id = ids - 1;
-        const size_t max_sidx = (size_t)kWfSetPlanes * state_entries + (size_t)grid * block_paths - 1;  // the highest state index a ray record can carry (set 1)
-        const size_t slice_f4 = 2 * (size_t)2 * 2 * block_paths /* ray records */ + (2 * (size_t)block_paths * sizeof(unsigned) + 15) / 16 /* path ids [2] */;
-        static_assert(kWgSuspendAt + (size_t)kSuspendF4 * kBlockThreads == kWgQueueF4, "the suspend area closes a workgroup's slice");
-        bool ok = slice_f4 <= kWgSuspendAt && max_id < (size_t)WF_INVALID && 2 * max_sidx + 1 < (size_t)WF_INVALID && (size_t)grid * block_paths <= state_entries &&
-                  (size_t)kWfStatePlanes * state_entries * sizeof(float4) < ((size_t)1 << 32) && (block_paths & (block_paths - 1)) == 0 && block_paths >= 256 &&
-                  block_paths <= kWgPathsMax && slice_f4 <= kWgQueueF4 && queueBuf.bytes >= (size_t)grid * kWgQueueF4 * sizeof(float4) &&
-                  stateBuf.bytes >= state_bytes && w.ids == state_entries && grid >= 1 && (size_t)grid <= wg_slots &&
-                  p->max_depth <= kWfDepthMax && p->n_samples <= kWfSampleMax && workPtr != nullptr;
-        if (vol) ok = ok && p->n_samples <= kWfVolSampleMax && c->ext_flags == GLRTX_EXT_VOLUME && c->have_volume && c->vol.density != nullptr &&
-                      c->vol.temperature != nullptr && c->n_spheres == 0 && !vine && fetch == 0 && !compact;
-        if (!fed && n_frames > 1) ok = ok && c->wfSeeds.bytes >= (size_t)n_frames * sizeof(float2);
-        if (w.planes) ok = ok && planeBuf.bytes >= (size_t)std::max(n_planes, 1) * plane_f4 * sizeof(float4);
-        if (adapt) ok = ok && !fed && !slot && w.planes && c->ad_selected && c->ad_tiles == (int)(total >> 6) && c->adList.bytes >= (total >> 6) * sizeof(int) &&
-                      c->adMask.bytes >= (total >> 6) && c->adHalf.bytes >= (size_t)c->ad_pitch * c->owned_rows && c->ad_pitch == c->pitch_bytes;
-        if (moments) ok = ok && !fed && !slot && w.planes && c->mmM.p && c->mm_pitch == c->pitch_bytes && c->mm_rows == c->owned_rows &&
-                        c->mmM.bytes >= c->pitch_bytes * (size_t)c->owned_rows;
-        if (fed) ok = ok && n_frames >= 1 && n_frames <= fed_cap && fed_cap <= kFeedMaxFrames && slot->feed_d.bytes >= sizeof(FeedDev) && w.feed_host != nullptr &&
-                      slot->chunks[(n_frames - 1) / kFeedChunkFrames].p != nullptr && slot->chunk_bytes == frame_bytes;
-        if (!ok) return fail(c, GLRTX_EDEVICE, "internal: wgwf launch shapes inconsistent (ids %zu, max id %zu, grid %d of %zu slots (%d per CU), block_paths %d, frames %d, fed %d)", ids, max_id,
-                             grid, wg_slots, per_cu, block_paths, n_frames, (int)fed);
-        (void)queue_bytes_max;
-    }
+    return GLRTX_OK;
+}
+
+// ---- shape invariants of the hand-written kernel, checked on the host before every launch (an access past one of these
+// buffers is a GPU memory fault, not an error code): every path id the launch can form indexes inside the state arrays;
+// every workgroup of the grid has its own queue slice; a slice holds both halves of the double-buffered ray queue
+// (2 rays per live path: the next ray and the shadow ray) and of the path-id queue; every (frame, sample) has its plane.
+int wgwf_check(glrtx_ctx *c, const WgwfLaunch &L) {
+    const glrtx_params *p = L.p;
+    const glrtx_ctx::PipeSlot *const slot = L.slot;
+    const WfArgs &w = L.w;
+    const bool fed = L.f.fed, moments = L.req.kind == RenderReq::Moments;
+    const int n_frames = L.n_frames, grid = L.grid, block_paths = L.block_paths, fed_cap = L.f.fed_cap;
+    const size_t state_entries = L.state_entries, total = L.total, max_id = L.ids - 1;
+    const size_t max_sidx = (size_t)kWfSetPlanes * state_entries + (size_t)grid * block_paths - 1;  // the highest state index a ray record can carry (set 1)
+    const size_t slice_f4 = 2 * (size_t)2 * 2 * block_paths /* ray records */ + (2 * (size_t)block_paths * sizeof(unsigned) + 15) / 16 /* path ids [2] */;
+    static_assert(kWgSuspendAt + (size_t)kSuspendF4 * kBlockThreads == kWgQueueF4, "the suspend area closes a workgroup's slice");
+    bool ok = slice_f4 <= kWgSuspendAt && max_id < (size_t)WF_INVALID && 2 * max_sidx + 1 < (size_t)WF_INVALID && (size_t)grid * block_paths <= state_entries &&
+              (size_t)kWfStatePlanes * state_entries * sizeof(float4) < ((size_t)1 << 32) && (block_paths & (block_paths - 1)) == 0 && block_paths >= 256 &&
+              block_paths <= kWgPathsMax && slice_f4 <= kWgQueueF4 && L.queueBuf->bytes >= (size_t)grid * kWgQueueF4 * sizeof(float4) &&
+              L.stateBuf->bytes >= L.state_bytes && w.ids == state_entries && grid >= 1 && (size_t)grid <= L.k.wg_slots &&
+              p->max_depth <= kWfDepthMax && p->n_samples <= kWfSampleMax && L.workPtr != nullptr;
+    if (L.k.vol) ok = ok && p->n_samples <= kWfVolSampleMax && c->ext_flags == GLRTX_EXT_VOLUME && c->have_volume && c->vol.density != nullptr &&
+                      c->vol.temperature != nullptr && c->n_spheres == 0 && !L.k.vine && L.k.fetch == 0 && !L.k.compact;
+    if (!fed && n_frames > 1) ok = ok && c->wfSeeds.bytes >= (size_t)n_frames * sizeof(float2);
+    if (w.planes) ok = ok && L.planeBuf->bytes >= (size_t)std::max(L.n_planes, 1) * L.plane_f4 * sizeof(float4);
+    if (L.k.adapt) ok = ok && !fed && !slot && w.planes && c->ad_selected && c->ad_tiles == (int)(total >> 6) && c->adList.bytes >= (total >> 6) * sizeof(int) &&
+                        c->adMask.bytes >= (total >> 6) && c->adHalf.bytes >= (size_t)c->ad_pitch * c->owned_rows && c->ad_pitch == c->pitch_bytes;
+    if (moments) ok = ok && !fed && !slot && w.planes && c->mmM.p && c->mm_pitch == c->pitch_bytes && c->mm_rows == c->owned_rows &&
+                      c->mmM.bytes >= c->pitch_bytes * (size_t)c->owned_rows;
+    if (fed) ok = ok && n_frames >= 1 && n_frames <= fed_cap && fed_cap <= kFeedMaxFrames && slot->feed_d.bytes >= sizeof(FeedDev) && w.feed_host != nullptr &&
+                  slot->chunks[(n_frames - 1) / kFeedChunkFrames].p != nullptr && slot->chunk_bytes == L.frame_bytes;
+    if (!ok) return fail(c, GLRTX_EDEVICE, "internal: wgwf launch shapes inconsistent (ids %zu, max id %zu, grid %d of %zu slots (%d per CU), block_paths %d, frames %d, fed %d)", L.ids, max_id,
+                         grid, L.k.wg_slots, L.k.per_cu, block_paths, n_frames, (int)fed);
+    return GLRTX_OK;
+}
+
+// The accumulation pass of one (source, sink) pair on the context's stream (accumulate.hip.h).
+template <class Src, class Sink>
+void accumulate_launch(glrtx_ctx *c, const accumulate::Image &im, const Src &src, const Sink &sink) {
+    hipLaunchKernelGGL(accumulate::entry(src, sink), dim3((im.width + 63) / 64, (im.rows + 3) / 4), dim3(256), 0, c->stream, im, src, sink);
+}
+
+// ---- issue: the render kernel on its stream, the accumulation pass (and the images) on the context's, the events that order and time them
+int wgwf_issue(glrtx_ctx *c, const WgwfLaunch &L) {
+    const glrtx_params *p = L.p;
+    glrtx_ctx::PipeSlot *const slot = L.slot;
+    const WfArgs &w = L.w;
+    const bool fed = L.f.fed, adapt = L.k.adapt, vol = L.k.vol;
+    const int n_frames = L.n_frames, n_planes = L.n_planes;
+    const hipStream_t rstream = L.rstream;
     glrtx_ctx::LaunchRec *rec = nullptr;
+    int rc;
     if ((rc = next_launch_rec(c, rec))) return rc;
     // a slot's render kernel overwrites the planes its previous plane-accumulation pass (two launches ago, on the context's stream) reads
     if (slot && slot->used) HIP_TRY(c, hipStreamWaitEvent(rstream, slot->acc_done, 0));
     // ... and a kernel on the context's path state starts behind the last one that used it (another stream's, possibly)
-    if (ctx_state && c->state_used) HIP_TRY(c, hipStreamWaitEvent(rstream, c->state_done, 0));
-    HIP_TRY(c, hipMemsetAsync(workPtr, 0, sizeof(unsigned), rstream));
+    if (L.ctx_state && c->state_used) HIP_TRY(c, hipStreamWaitEvent(rstream, c->state_done, 0));
+    HIP_TRY(c, hipMemsetAsync(L.workPtr, 0, sizeof(unsigned), rstream));
     if (fed) {  // the device mirror starts with the frames published so far (kernel boundary: visible to every workgroup of the render kernel)
         hipLaunchKernelGGL(feed_prefill_kernel, dim3(1), dim3(64), 0, rstream, (FeedDev *)slot->feed_d.p, (const FeedHost *)slot->feed_h_dev, n_frames);
         HIP_TRY(c, hipGetLastError());
     }
     HIP_TRY(c, hipEventRecord(rec->ev0, rstream));
-    c->last_kernel = vol ? (adapt ? "pt_render_wgwf (volume, adaptive)" : "pt_render_wgwf (volume)")
-                   : adapt ? (vine ? "pt_render_wgwf (adaptive, list scan)" : "pt_render_wgwf (adaptive)") : vine ? "pt_render_wgwf (list scan)" : "pt_render_wgwf";
-    c->counters_stale = c->counters_stale || c->count_rays;
+    c->last_kernel = L.k.name;
+    c->counters_stale = c->counters_stale || L.req.count_rays(c);
     const VolArgs va = vol ? c->vol : VolArgs{};
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlockThreads), lds, rstream, a, w, workPtr, (float4 *)queueBuf.p, adapt ? (const int *)c->adList.p : nullptr,
+    hipLaunchKernelGGL(L.k.fn, dim3(L.grid), dim3(kBlockThreads), L.k.lds, rstream, L.a, w, L.workPtr, (float4 *)L.queueBuf->p, adapt ? (const int *)c->adList.p : nullptr,
                        adapt ? (const unsigned *)c->adCount.p : nullptr, va);
     HIP_TRY(c, hipGetLastError());
 #ifdef GLRTX_RAY_LOG
-    g_dbg_last = {a, w, lds, grid, (float4 *)queueBuf.p, fetch};
+    g_dbg_last = {L.a, w, L.k.lds, L.grid, (float4 *)L.queueBuf->p, L.k.fetch};
 #endif
     HIP_TRY(c, hipEventRecord(rec->evm, rstream));
-    if (ctx_state) { HIP_TRY(c, hipEventRecord(c->state_done, rstream)); c->state_used = true; }
+    if (L.ctx_state) { HIP_TRY(c, hipEventRecord(c->state_done, rstream)); c->state_used = true; }
     if (slot) {  // the context's stream -- where the caller's own work, the resolve pass and the next accumulation are ordered -- takes over
         HIP_TRY(c, hipEventRecord(slot->render_done, rstream));
         HIP_TRY(c, hipStreamWaitEvent(c->stream, slot->render_done, 0));
@@ -1400,30 +1477,22 @@ int launch_wgwf(glrtx_ctx *c, const KernelArgs &a_in, const glrtx_params *p, con
     rec->has_eva = slot != nullptr;
     // presenting: the pass that adds the planes also resolves every frame into its device image (fed: however many frames the launch ends up with -- each was given an
     // image when it was appended); a launch without planes accumulated in the render kernel and is resolved behind it (below)
-    const bool pres = presenting(c);
+    const bool pres = L.req.presents(c);
     const bool pres_fused = pres && (fed || w.planes);
     if (pres_fused && (rc = present_pass_begin(c))) return rc;
     {
-        const dim3 g((c->width + 63) / 64, (c->owned_rows + 3) / 4);
+        // the source follows the form, the sink the request
+        const accumulate::Image im{L.a.accum, L.a.pitch_f4, c->width, c->owned_rows};
+        const accumulate::Planes flat{(const float4 *)L.planeBuf->p, n_frames, p->n_samples};
+        const accumulate::Fed feed{fed ? (const FeedDev *)slot->feed_d.p : nullptr, p->n_samples};
         const glrtx_ctx::Present &P = c->pres;
-        const int slot0 = pres ? (int)(P.seq % (uint64_t)P.ring) : 0;
-        if (adapt)
-            hipLaunchKernelGGL(accumulate_adaptive_kernel, g, dim3(256), 0, c->stream, a.accum, (float4 *)c->adHalf.p, a.pitch_f4, c->width, c->owned_rows,
-                               (const float4 *)planeBuf.p, n_planes, (const unsigned char *)c->adMask.p, tiles8_x);
-        else if (moments) {
-            if (n_planes > 0)
-                hipLaunchKernelGGL(variance::accumulate_moments_kernel, g, dim3(256), 0, c->stream, a.accum, (float4 *)c->mmM.p, a.pitch_f4, c->width, c->owned_rows,
-                                   (const float4 *)planeBuf.p, n_planes);
-        } else if (fed && pres)
-            hipLaunchKernelGGL(accumulate_present_feed_kernel, g, dim3(256), 0, c->stream, a.accum, a.pitch_f4, c->width, c->owned_rows, (const FeedDev *)slot->feed_d.p,
-                               p->n_samples, (uchar4 *)P.dev.p, (size_t)c->width * (size_t)c->owned_rows, P.ring, slot0, P.inv_gamma, P.flip);
-        else if (fed)
-            hipLaunchKernelGGL(accumulate_feed_kernel, g, dim3(256), 0, c->stream, a.accum, a.pitch_f4, c->width, c->owned_rows, (const FeedDev *)slot->feed_d.p, p->n_samples);
-        else if (w.planes && pres)
-            hipLaunchKernelGGL(accumulate_present_planes_kernel, g, dim3(256), 0, c->stream, a.accum, a.pitch_f4, c->width, c->owned_rows, (const float4 *)planeBuf.p, n_frames,
-                               p->n_samples, (uchar4 *)P.dev.p, (size_t)c->width * (size_t)c->owned_rows, P.ring, slot0, P.inv_gamma, P.flip);
-        else if (w.planes && n_planes > 0)
-            hipLaunchKernelGGL(accumulate_planes_kernel, g, dim3(256), 0, c->stream, a.accum, a.pitch_f4, c->width, c->owned_rows, (const float4 *)planeBuf.p, n_planes);
+        const accumulate::Present ring{(uchar4 *)P.dev.p, (size_t)c->width * (size_t)c->owned_rows, P.ring, pres ? (int)(P.seq % (uint64_t)P.ring) : 0, P.inv_gamma, P.flip};
+        if (adapt) accumulate_launch(c, im, flat, accumulate::Half{(float4 *)c->adHalf.p, (const unsigned char *)c->adMask.p, L.tiles8_x});
+        else if (L.req.kind == RenderReq::Moments) { if (n_planes > 0) accumulate_launch(c, im, flat, accumulate::Moments{(float4 *)c->mmM.p}); }
+        else if (fed && pres) accumulate_launch(c, im, feed, ring);
+        else if (fed) accumulate_launch(c, im, feed, accumulate::None{});
+        else if (w.planes && pres) accumulate_launch(c, im, flat, ring);
+        else if (w.planes && n_planes > 0) accumulate_launch(c, im, flat, accumulate::None{});
         HIP_TRY(c, hipGetLastError());
     }
     if (pres_fused && (rc = present_pass_end(c, n_frames))) return rc;
@@ -1434,13 +1503,34 @@ int launch_wgwf(glrtx_ctx *c, const KernelArgs &a_in, const glrtx_params *p, con
     c->st.frames_last = n_frames;
     c->st.paths += (uint64_t)c->owned_rows * (uint64_t)c->width * (uint64_t)p->n_samples * (uint64_t)n_frames;
     // what the next call may build on
-    c->last_render_done = slot ? slot->render_done : c->state_done;  // (a plain launch runs on the context's path state: ctx_state above)
+    c->last_render_done = slot ? slot->render_done : c->state_done;  // (a plain launch runs on the context's path state: ctx_state)
     if (fed) {
-        c->open.slot = slot; c->open.p = *p; c->open.frames = n_frames; c->open.cap = fed_cap; c->open.rec = rec; c->open.frame_bytes = frame_bytes; c->open.vol = vol;
+        c->open.slot = slot; c->open.p = *p; c->open.frames = n_frames; c->open.cap = L.f.fed_cap; c->open.rec = rec; c->open.frame_bytes = L.frame_bytes; c->open.vol = vol;
         c->st.feed_launches++;
     } else c->open.slot = nullptr;
     if (pres && !pres_fused) return present_resolve(c);
     return GLRTX_OK;
+}
+
+int launch_wgwf(glrtx_ctx *c, const KernelArgs &a, const glrtx_params *p, const RenderReq &req) {
+    WgwfLaunch L{};
+    L.p = p; L.req = req; L.a = a; L.n_frames = req.n_frames;
+    L.seeds_xy = req.n_frames == 1 ? p->seed : req.seeds;
+    L.tiles8_x = (c->width + 7) / 8;
+    L.total = (size_t)L.tiles8_x * ((c->owned_rows + 7) / 8) * 64;
+    if (L.total * 2 >= (size_t)INT32_MAX) return fail(c, GLRTX_EINVAL, "image too large for the wgwf variant");
+    L.plane_f4 = (size_t)a.pitch_f4 * (size_t)c->owned_rows;
+    L.plane_bytes = L.plane_f4 * sizeof(float4);
+    L.frame_bytes = (size_t)std::max(p->n_samples, 1) * L.plane_bytes;
+    L.n_planes = L.n_frames * p->n_samples;
+    L.f = wgwf_form(c, L);
+    L.ids = L.total * (size_t)(L.f.fed ? L.f.fed_cap : L.n_frames);  // path id = frame * total + pixel
+    if (L.ids + 1 >= (size_t)UINT32_MAX) return fail(c, GLRTX_EINVAL, "glrtx_render_frames: %d frames of %zu pixels exceed the 32-bit ray id space", L.n_frames, L.total);
+    if (int rc = wgwf_kernel(c, L)) return rc;
+    if (int rc = wgwf_pipe_slot(c, L)) return rc;
+    if (int rc = wgwf_args(c, L)) return rc;
+    if (int rc = wgwf_check(c, L)) return rc;
+    return wgwf_issue(c, L);
 }
 
 
@@ -2505,21 +2595,30 @@ int glrtx_count_rays(glrtx_ctx *c, int enable) {
     return GLRTX_OK;
 }
 
-static int render_one(glrtx_ctx *c, const glrtx_params *p);
+
+static int render_one(glrtx_ctx *c, const glrtx_params *p, const RenderReq &req);
+
+// n_frames frames (seeds_xy) of one kind as launches of at most `most` frames, of equal size -- 16 frames under a limit of 14 are 8 + 8, not 14 + 2 -- in order.  A
+// helping's parameters carry its first frame's seed (a single-frame helping renders with it); every frame counts as a launch in the statistics.
+static int render_helpings(glrtx_ctx *c, const glrtx_params *p, const float *seeds_xy, int n_frames, int most, RenderReq::Kind kind) {
+    const int n_launches = (n_frames + most - 1) / most;
+    const int chunk = (n_frames + n_launches - 1) / n_launches;
+    for (int f0 = 0; f0 < n_frames; f0 += chunk) {
+        glrtx_params q = *p;
+        q.seed[0] = seeds_xy[2 * f0]; q.seed[1] = seeds_xy[2 * f0 + 1];
+        const RenderReq req{kind, seeds_xy + 2 * (size_t)f0, std::min(chunk, n_frames - f0)};
+        if (int rc = render_one(c, &q, req)) return rc;
+        c->st.launches += (uint64_t)(req.n_frames - 1);  // (render_one has counted one)
+    }
+    return GLRTX_OK;
+}
 
 int glrtx_render_frames(glrtx_ctx *c, const glrtx_params *p, const float *seeds_xy, int n_frames) {
     if (!c || !p) return GLRTX_EINVAL;
     if (n_frames < 0 || (n_frames > 0 && !seeds_xy)) return fail(c, GLRTX_EINVAL, "glrtx_render_frames: bad seeds/n_frames");
     if (n_frames == 0) return GLRTX_OK;
     if (int rc = present_prepare(c, n_frames)) return rc;  // (GLRTX_EBUSY: nothing has changed)
-    if (n_frames == 1 || !wgwf_routes(c, p)) {  // the megakernels have no frames-in-flight form: one launch per frame
-        for (int f = 0; f < n_frames; f++) {
-            glrtx_params q = *p;
-            q.seed[0] = seeds_xy[2 * f]; q.seed[1] = seeds_xy[2 * f + 1];
-            if (int rc = render_one(c, &q)) return rc;
-        }
-        return GLRTX_OK;
-    }
+    if (n_frames == 1 || !wgwf_routes(c, p)) return render_helpings(c, p, seeds_xy, n_frames, 1, RenderReq::Ordinary);  // the megakernels have no frames-in-flight form: one launch per frame
     HIP_TRY(c, hipSetDevice(c->device));
     // A launch of the same camera that is still open takes the frames itself (feed_append); otherwise they are issued as launches of at most `most` frames -- what the
     // frames-in-flight memory budget allows (frames_cap) -- of equal size, in order; each of them stays open for the next call.  An allocation that fails is reported,
@@ -2531,32 +2630,13 @@ int glrtx_render_frames(glrtx_ctx *c, const glrtx_params *p, const float *seeds_
     const bool may_feed = c->feed_ok && std::getenv("GLRTX_NO_FEED") == nullptr && c->pipeline && c->stream == c->own_stream;
     int most = std::min(n_frames, may_feed ? std::min(frames_cap(c, p, (int)kFedSlots), kFeedMaxFrames) : frames_cap(c, p, 1));
     if (const char *v = std::getenv("GLRTX_FEED_CAP")) { if (may_feed) most = std::max(1, std::min(most, std::atoi(v))); }
-    const int n_launches = (n_frames + most - 1) / most;
-    const int chunk = (n_frames + n_launches - 1) / n_launches;  // equal helpings: 16 frames under a limit of 14 are 8 + 8, not 14 + 2
-    for (int f0 = 0; f0 < n_frames; f0 += chunk) {
-        const int n = std::min(chunk, n_frames - f0);
-        int rc;
-        if (n == 1) {
-            glrtx_params q = *p;
-            q.seed[0] = seeds_xy[2 * f0]; q.seed[1] = seeds_xy[2 * f0 + 1];
-            rc = render_one(c, &q);
-        } else {
-            c->frames_seeds = seeds_xy + 2 * (size_t)f0;
-            c->frames_n = n;
-            rc = render_one(c, p);
-            c->frames_seeds = nullptr;
-            c->frames_n = 1;
-            if (rc == GLRTX_OK) c->st.launches += (uint64_t)(n - 1);
-        }
-        if (rc != GLRTX_OK) return rc;
-    }
-    return GLRTX_OK;
+    return render_helpings(c, p, seeds_xy, n_frames, most, RenderReq::Ordinary);
 }
 
 int glrtx_render(glrtx_ctx *c, const glrtx_params *p) {
     if (!c || !p) return GLRTX_EINVAL;
     if (int rc = present_prepare(c, 1)) return rc;  // (GLRTX_EBUSY: nothing has changed)
-    return render_one(c, p);
+    return render_one(c, p, RenderReq{});
 }
 
 // Adaptive call: the selection, then n_frames frames of the active tiles only, in launches of at most what the frames-in-flight budget allows -- all of them on the
@@ -2568,23 +2648,7 @@ int glrtx_render_adaptive(glrtx_ctx *c, const glrtx_params *p, const float *seed
     HIP_TRY(c, hipSetDevice(c->device));
     if (int rc = adapt_select(c, cfg)) return rc;
     if (n_frames == 0 || c->owned_rows == 0) { c->st.launches += (uint64_t)n_frames; return GLRTX_OK; }
-    const int most = std::min(n_frames, frames_cap(c, p, 1));
-    const int n_launches = (n_frames + most - 1) / most;
-    const int chunk = (n_frames + n_launches - 1) / n_launches;
-    int rc = GLRTX_OK;
-    c->adapt_launch = true;
-    for (int f0 = 0; f0 < n_frames && rc == GLRTX_OK; f0 += chunk) {
-        const int n = std::min(chunk, n_frames - f0);
-        glrtx_params q = *p;
-        q.seed[0] = seeds_xy[2 * f0]; q.seed[1] = seeds_xy[2 * f0 + 1];
-        c->frames_seeds = seeds_xy + 2 * (size_t)f0;
-        c->frames_n = n;
-        rc = render_one(c, &q);
-        c->frames_seeds = nullptr;
-        c->frames_n = 1;
-        if (rc == GLRTX_OK) c->st.launches += (uint64_t)(n - 1);
-    }
-    c->adapt_launch = false;
+    const int rc = render_helpings(c, p, seeds_xy, n_frames, std::min(n_frames, frames_cap(c, p, 1)), RenderReq::Adaptive);
     seal_feed(c);  // (the next render call starts a launch of its own)
     return rc;
 }
@@ -2839,23 +2903,7 @@ int glrtx_render_moments(glrtx_ctx *c, const glrtx_params *p, const float *seeds
     if (!moments_have(c))
         if (int rc = moments_ensure(c)) return rc;
     if (n_frames == 0 || c->owned_rows == 0) { c->st.launches += (uint64_t)n_frames; return GLRTX_OK; }
-    const int most = std::min(n_frames, frames_cap(c, p, 1));
-    const int n_launches = (n_frames + most - 1) / most;
-    const int chunk = (n_frames + n_launches - 1) / n_launches;
-    int rc = GLRTX_OK;
-    c->moments_launch = true;
-    for (int f0 = 0; f0 < n_frames && rc == GLRTX_OK; f0 += chunk) {
-        const int n = std::min(chunk, n_frames - f0);
-        glrtx_params q = *p;
-        q.seed[0] = seeds_xy[2 * f0]; q.seed[1] = seeds_xy[2 * f0 + 1];
-        c->frames_seeds = seeds_xy + 2 * (size_t)f0;
-        c->frames_n = n;
-        rc = render_one(c, &q);
-        c->frames_seeds = nullptr;
-        c->frames_n = 1;
-        if (rc == GLRTX_OK) c->st.launches += (uint64_t)(n - 1);
-    }
-    c->moments_launch = false;
+    const int rc = render_helpings(c, p, seeds_xy, n_frames, std::min(n_frames, frames_cap(c, p, 1)), RenderReq::Moments);
     seal_feed(c);  // (the next render call starts a launch of its own)
     return rc;
 }
@@ -3295,20 +3343,20 @@ int glrtx_debug_reproject_motion_moments(const float *accum, const float *moment
 }
 
 // glrtx_render behind the presentation check (glrtx_render_frames checks for all its frames at once)
-static int render_one(glrtx_ctx *c, const glrtx_params *p) {
+static int render_one(glrtx_ctx *c, const glrtx_params *p, const RenderReq &req) {
     if (!c->have_scene) return fail(c, GLRTX_EINVAL, "glrtx_render: no scene uploaded");
     if (!c->accum || c->width < 1) return fail(c, GLRTX_EINVAL, "glrtx_render: no accumulator (call glrtx_resize)");
     if (p->n_samples < 0 || p->max_depth < 0) return fail(c, GLRTX_EINVAL, "glrtx_render: negative n_samples/max_depth");
     if ((c->ext_flags & GLRTX_EXT_VOLUME) && !c->have_volume) return fail(c, GLRTX_EINVAL, "glrtx_render: GLRTX_EXT_VOLUME is set and no volume is uploaded (glrtx_upload_volume)");
     HIP_TRY(c, hipSetDevice(c->device));
     const bool wavefront = wgwf_routes(c, p);
-    if (c->owned_rows > 0 && wavefront && c->frames_n == 1 && !c->adapt_launch && !c->moments_launch && feed_append(c, p, p->seed, 1) == 1) {  // a launch of the same camera that is still open takes the frame itself
+    if (c->owned_rows > 0 && wavefront && req.kind == RenderReq::Ordinary && req.n_frames == 1 && feed_append(c, p, p->seed, 1) == 1) {  // a launch of the same camera that is still open takes the frame itself
         c->last_was_render = true; c->last_p = *p;
         return presenting(c) ? present_issue(c, 1) : GLRTX_OK;
     }
     if (!wavefront) seal_feed(c);
     c->st.launches++;
-    if (c->owned_rows == 0) return presenting(c) ? present_issue(c, c->frames_n) : GLRTX_OK;  // (images without rows: the frame numbers stay in step)
+    if (c->owned_rows == 0) return req.presents(c) ? present_issue(c, req.n_frames) : GLRTX_OK;  // (images without rows: the frame numbers stay in step)
 
     KernelArgs a;
     a.sc = c->sc;
@@ -3321,10 +3369,10 @@ static int render_one(glrtx_ctx *c, const glrtx_params *p) {
     a.width = c->width; a.height = c->height;
     a.owned_rows = c->owned_rows;
     a.rank = c->rank; a.world = c->world; a.stripe = c->stripe;
-    a.accum = c->accum;
+    a.accum = req.accum(c);
     a.pitch_f4 = (int)(c->pitch_bytes / sizeof(float4));
     a.ray_counter = (unsigned long long *)c->counter.p;
-    a.hit_hist = c->hit_hist_dev;  // (null outside glrtx_hit_histogram)
+    a.hit_hist = req.hit_hist;  // (null outside glrtx_hit_histogram)
     a.tiles_x = (c->width + kTile - 1) / kTile;
     const int tiles_y = (c->owned_rows + kTile - 1) / kTile;
     a.n_tiles = a.tiles_x * tiles_y;
@@ -3352,7 +3400,7 @@ static int render_one(glrtx_ctx *c, const glrtx_params *p) {
         c->st.fallback_launches++;
     }
     if (variant == 2) {
-        const int rc = launch_wgwf(c, a, p, c->frames_n == 1 ? p->seed : c->frames_seeds, c->frames_n);
+        const int rc = launch_wgwf(c, a, p, req);
         if (rc == GLRTX_OK) { c->last_was_render = true; c->last_p = *p; } else seal_feed(c);
         return rc;
     }
@@ -3361,10 +3409,13 @@ static int render_one(glrtx_ctx *c, const glrtx_params *p) {
     if (variant == 1) {
         // persistent kernel: grid = what is resident at once (occupancy x CUs), capped by the work available
         using PKernel = void (*)(const KernelArgs, unsigned *, const ExtArgs, const VolArgs);
+        static constexpr PKernel kPersistent[3][2] = {  // [plain | extensions | volume][count_rays]
+            {pt_render_persistent<false, false>, pt_render_persistent<true, false>}, {pt_render_persistent<false, true>, pt_render_persistent<true, true>},
+            {pt_render_persistent<false, true, true>, pt_render_persistent<true, true, true>}};
+        static constexpr const char *kPersistentNames[3] = {"pt_render_persistent", "pt_render_persistent (extensions)", "pt_render_persistent (volume)"};
         const bool vol = (c->ext_flags & GLRTX_EXT_VOLUME) != 0;  // (render_one has checked that a volume is uploaded)
-        const PKernel pk = vol   ? (c->count_rays ? (PKernel)pt_render_persistent<true, true, true> : (PKernel)pt_render_persistent<false, true, true>)
-                           : ext ? (c->count_rays ? (PKernel)pt_render_persistent<true, true> : (PKernel)pt_render_persistent<false, true>)
-                                 : (c->count_rays ? (PKernel)pt_render_persistent<true, false> : (PKernel)pt_render_persistent<false, false>);
+        const int which = vol ? 2 : ext ? 1 : 0;
+        const PKernel pk = kPersistent[which][c->count_rays];
         ExtArgs ex{};
         ex.spheres = (const float4 *)c->spheres.p; ex.sphere_mat = (const int *)c->sphereMat.p;
         ex.n_spheres = c->n_spheres; ex.flags = c->ext_flags;
@@ -3381,21 +3432,16 @@ static int render_one(glrtx_ctx *c, const glrtx_params *p) {
         if (grid < 1) grid = 1;
         HIP_TRY(c, hipMemsetAsync(c->work.p, 0, sizeof(unsigned), c->stream));
         HIP_TRY(c, hipEventRecord(rec->ev0, c->stream));
-        c->last_kernel = vol ? "pt_render_persistent (volume)" : ext ? "pt_render_persistent (extensions)" : "pt_render_persistent";
+        c->last_kernel = kPersistentNames[which];
         const VolArgs va = vol ? c->vol : VolArgs{};
         hipLaunchKernelGGL(pk, dim3(grid), dim3(kBlockThreads), lds_p, c->stream, a, (unsigned *)c->work.p, ex, va);
     } else {
-    HIP_TRY(c, hipEventRecord(rec->ev0, c->stream));
-    c->last_kernel = "pt_render_kernel";
-    if (c->count_rays) {
-        if (lds > 64 * 1024)
-            HIP_TRY(c, hipFuncSetAttribute((const void *)pt_render_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        hipLaunchKernelGGL(pt_render_kernel<true>, dim3(a.n_tiles), dim3(kBlockThreads), lds, c->stream, a);
-    } else {
-        if (lds > 64 * 1024)
-            HIP_TRY(c, hipFuncSetAttribute((const void *)pt_render_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        hipLaunchKernelGGL(pt_render_kernel<false>, dim3(a.n_tiles), dim3(kBlockThreads), lds, c->stream, a);
-    }
+        static constexpr void (*kTileKernel[2])(const KernelArgs) = {pt_render_kernel<false>, pt_render_kernel<true>};  // [count_rays]
+        const auto tk = kTileKernel[c->count_rays];
+        HIP_TRY(c, hipEventRecord(rec->ev0, c->stream));
+        c->last_kernel = "pt_render_kernel";
+        if (lds > 64 * 1024) HIP_TRY(c, hipFuncSetAttribute((const void *)tk, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        hipLaunchKernelGGL(tk, dim3(a.n_tiles), dim3(kBlockThreads), lds, c->stream, a);
     }
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipEventRecord(rec->evm, c->stream));
@@ -3440,6 +3486,16 @@ int glrtx_accum_device_ptr(const glrtx_ctx *c, void **ptr_out, size_t *pitch_out
     return GLRTX_OK;
 }
 
+// resolve_kernel's instantiation for a call and its grid: kResolvePer pixels per lane; GLRTX_RESOLVE_PER=1/2/4 overrides (A/B; read at every call)
+using ResolveFn = void (*)(const float4 *, int, int, int, uchar4 *, int, float, int);
+struct ResolvePick { ResolveFn fn; dim3 grid; };
+static ResolvePick resolve_pick(const glrtx_ctx *c) {
+    int per = kResolvePer;
+    if (const char *v = std::getenv("GLRTX_RESOLVE_PER")) per = std::atoi(v);
+    per = per == 1 || per == 4 ? per : 2;
+    return {per == 1 ? resolve_kernel<1> : (per == 4 ? resolve_kernel<4> : resolve_kernel<2>), resolve_grid(c->width, c->owned_rows, per)};
+}
+
 int glrtx_resolve_rgba8(glrtx_ctx *c, uint8_t *dst, size_t dst_pitch_bytes, float gamma, int flip_y) {
     if (!c || !dst) return GLRTX_EINVAL;
     seal_feed(c);  // (nothing is appended to an open launch across this call: glrtx_ctx::OpenFeed)
@@ -3454,13 +3510,9 @@ int glrtx_resolve_rgba8(glrtx_ctx *c, uint8_t *dst, size_t dst_pitch_bytes, floa
         HIP_TRY(c, hipMalloc(&c->rgba8.p, bytes));
         c->rgba8.bytes = bytes;
     }
-    int per = kResolvePer;
-    if (const char *v = std::getenv("GLRTX_RESOLVE_PER")) per = std::atoi(v);  // (A/B: pixels per lane)
-    per = per == 1 || per == 4 ? per : 2;
-    const dim3 grid = resolve_grid(c->width, c->owned_rows, per);
+    const ResolvePick rk = resolve_pick(c);
     HIP_TRY(c, hipEventRecord(c->rs0, c->stream));
-    const auto rk = per == 1 ? resolve_kernel<1> : (per == 4 ? resolve_kernel<4> : resolve_kernel<2>);
-    hipLaunchKernelGGL(rk, grid, dim3(256), 0, c->stream, (const float4 *)c->accum, (int)(c->pitch_bytes / sizeof(float4)),
+    hipLaunchKernelGGL(rk.fn, rk.grid, dim3(256), 0, c->stream, (const float4 *)c->accum, (int)(c->pitch_bytes / sizeof(float4)),
                        c->width, c->owned_rows, (uchar4 *)c->rgba8.p, c->width, 1.0f / gamma, flip_y ? 1 : 0);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipEventRecord(c->rs1, c->stream));
@@ -3479,15 +3531,11 @@ int glrtx_debug_resolve_burst(glrtx_ctx *c, float gamma, int reps, float *ms_per
     if (!c->accum || c->owned_rows == 0) return fail(c, GLRTX_EINVAL, "glrtx_debug_resolve_burst: no accumulator");
     HIP_TRY(c, hipSetDevice(c->device));
     if (int rc = ensure(c, c->rgba8, (size_t)c->width * 4 * (size_t)c->owned_rows)) return rc;
-    int per = kResolvePer;
-    if (const char *v = std::getenv("GLRTX_RESOLVE_PER")) per = std::atoi(v);
-    per = per == 1 || per == 4 ? per : 2;
-    const dim3 grid = resolve_grid(c->width, c->owned_rows, per);
-    const auto rk = per == 1 ? resolve_kernel<1> : (per == 4 ? resolve_kernel<4> : resolve_kernel<2>);
+    const ResolvePick rk = resolve_pick(c);
     for (int pass = 0; pass < 2; pass++) {  // (the first pass warms the device up)
         HIP_TRY(c, hipEventRecord(c->rs0, c->stream));
         for (int i = 0; i < reps; i++)
-            hipLaunchKernelGGL(rk, grid, dim3(256), 0, c->stream, (const float4 *)c->accum, (int)(c->pitch_bytes / sizeof(float4)), c->width, c->owned_rows,
+            hipLaunchKernelGGL(rk.fn, rk.grid, dim3(256), 0, c->stream, (const float4 *)c->accum, (int)(c->pitch_bytes / sizeof(float4)), c->width, c->owned_rows,
                                (uchar4 *)c->rgba8.p, c->width, 1.0f / gamma, 1);
         HIP_TRY(c, hipGetLastError());
         HIP_TRY(c, hipEventRecord(c->rs1, c->stream));
@@ -3516,17 +3564,13 @@ int glrtx_hit_histogram(glrtx_ctx *c, const glrtx_params *p, uint32_t *hist_out,
     const size_t n_rec = c->leaf_tri.size() + 1;
     DevBuf hist, scratch;
     int rc = GLRTX_OK;
-    float4 *const accum_was = c->accum;
-    const bool pipeline_was = c->pipeline, count_was = c->count_rays;
     const glrtx_stats st_was = c->st;
     if ((rc = ensure(c, hist, n_rec * sizeof(unsigned))) == GLRTX_OK && (rc = ensure(c, scratch, c->pitch_bytes * (size_t)c->owned_rows)) == GLRTX_OK) {
         hipError_t e = hipMemsetAsync(hist.p, 0, n_rec * sizeof(unsigned), c->stream);
         if (e == hipSuccess) e = hipMemsetAsync(scratch.p, 0, c->pitch_bytes * (size_t)c->owned_rows, c->stream);
         if (e != hipSuccess) rc = fail(c, GLRTX_EDEVICE, "glrtx_hit_histogram: %s", hipGetErrorString(e));
         if (rc == GLRTX_OK) {
-            c->accum = (float4 *)scratch.p; c->pipeline = false; c->count_rays = false; c->hit_hist_dev = (unsigned *)hist.p;  // one plain launch on the context's stream
-            rc = glrtx_render(c, p);
-            c->hit_hist_dev = nullptr; c->accum = accum_was; c->pipeline = pipeline_was; c->count_rays = count_was;
+            rc = render_one(c, p, RenderReq{RenderReq::Calibration, nullptr, 1, (unsigned *)hist.p, (float4 *)scratch.p});
             seal_feed(c);
             if (rc == GLRTX_OK) rc = glrtx_sync(c);
         }
@@ -3540,7 +3584,6 @@ int glrtx_hit_histogram(glrtx_ctx *c, const glrtx_params *p, uint32_t *hist_out,
         }
     }
     dev_free(hist); dev_free(scratch);
-    const double kms = c->st.kernel_ms_total; (void)kms;
     c->st = st_was;  // (the calibration frame is not part of the caller's statistics)
     return rc;
 }
@@ -3631,31 +3674,10 @@ int glrtx_present_get_stats(const glrtx_ctx *c, glrtx_present_stats *out) {
 }
 
 #ifdef GLRTX_TRAV_STATS
-// diagnostic build only: read and clear the traversal statistics
-int glrtx_debug_trav_stats(unsigned long long out[8]) {
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_trav_stats), 8 * sizeof(unsigned long long)) != hipSuccess) return GLRTX_EDEVICE;
-    unsigned long long z[8] = {0};
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_trav_stats), z, sizeof z) != hipSuccess) return GLRTX_EDEVICE;
-    return GLRTX_OK;
-}
-int glrtx_debug_trav_trips(unsigned long long out[4]) {
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_trav_trips), 4 * sizeof(unsigned long long)) != hipSuccess) return GLRTX_EDEVICE;
-    unsigned long long z[4] = {0};
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_trav_trips), z, sizeof z) != hipSuccess) return GLRTX_EDEVICE;
-    return GLRTX_OK;
-}
-int glrtx_debug_trav_sp_hist(unsigned long long out[16]) {
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_trav_sp_hist), 16 * sizeof(unsigned long long)) != hipSuccess) return GLRTX_EDEVICE;
-    unsigned long long z[16] = {0};
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_trav_sp_hist), z, sizeof z) != hipSuccess) return GLRTX_EDEVICE;
-    return GLRTX_OK;
-}
-int glrtx_debug_trav_hist(unsigned long long out[16]) {
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_trav_hist), 16 * sizeof(unsigned long long)) != hipSuccess) return GLRTX_EDEVICE;
-    unsigned long long z[16] = {0};
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_trav_hist), z, sizeof z) != hipSuccess) return GLRTX_EDEVICE;
-    return GLRTX_OK;
-}
+int glrtx_debug_trav_stats(unsigned long long out[8]) { return take_symbol(g_trav_stats, out); }
+int glrtx_debug_trav_trips(unsigned long long out[4]) { return take_symbol(g_trav_trips, out); }
+int glrtx_debug_trav_sp_hist(unsigned long long out[16]) { return take_symbol(g_trav_sp_hist, out); }
+int glrtx_debug_trav_hist(unsigned long long out[16]) { return take_symbol(g_trav_hist, out); }
 #endif
 
 #ifdef GLRTX_RAY_LOG
@@ -3728,27 +3750,12 @@ int glrtx_debug_ray_log_replay(glrtx_ctx *c, int reps, double out[4]) {
 #endif
 
 #ifdef GLRTX_STEP_TIMING
-int glrtx_debug_step_timing(unsigned long long out[4]) {
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_step_timing), 4 * sizeof(unsigned long long)) != hipSuccess) return GLRTX_EDEVICE;
-    unsigned long long z[4] = {0};
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_step_timing), z, sizeof z) != hipSuccess) return GLRTX_EDEVICE;
-    return GLRTX_OK;
-}
+int glrtx_debug_step_timing(unsigned long long out[4]) { return take_symbol(g_step_timing, out); }
 #endif
 
 #ifdef GLRTX_PHASE_STATS
-int glrtx_debug_trip_log(unsigned out[16 * 64 * 4]) {
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_trip_log), 16 * 64 * 16) != hipSuccess) return GLRTX_EDEVICE;
-    static unsigned z[16 * 64 * 4];
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_trip_log), z, sizeof z) != hipSuccess) return GLRTX_EDEVICE;
-    return GLRTX_OK;
-}
-int glrtx_debug_phase_cycles(unsigned long long out[8]) {
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_phase_cycles), 8 * sizeof(unsigned long long)) != hipSuccess) return GLRTX_EDEVICE;
-    unsigned long long z[8] = {0};
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_phase_cycles), z, sizeof z) != hipSuccess) return GLRTX_EDEVICE;
-    return GLRTX_OK;
-}
+int glrtx_debug_trip_log(unsigned out[16 * 64 * 4]) { return take_symbol(g_trip_log, out); }
+int glrtx_debug_phase_cycles(unsigned long long out[8]) { return take_symbol(g_phase_cycles, out); }
 #endif
 
 int glrtx_timer_begin(glrtx_ctx *c) {

@@ -2860,52 +2860,7 @@ __global__ __launch_bounds__(kBlockThreads, GLRTX_WGWF_WAVES) void pt_replay_tra
 #endif
 
 // ------------------------------------------------------------------------------------------ frames in flight
-// Adds the sample planes of one glrtx_render_frames launch to the accumulator, plane by plane in frame (and sample)
-// order: per pixel the same chain of float additions that consecutive single-frame launches perform.
-// Bandwidth-bound: 16 B per plane and pixel in, one 16-B read-modify-write of the accumulator.
-__global__ __launch_bounds__(256) void accumulate_planes_kernel(float4 *accum, int pitch_f4, int width, int rows, const float4 *planes,
-                                                                int n_planes) {
-    const int x = blockIdx.x * 64 + (threadIdx.x & 63);
-    const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (x >= width || y >= rows) return;
-    const size_t at = (size_t)y * pitch_f4 + x, plane = (size_t)rows * pitch_f4;
-    float4 acc = accum[at];
-    for (int k = 0; k < n_planes; k++) {
-        const float4 v = planes[(size_t)k * plane + at];
-        acc.x = acc.x + v.x; acc.y = acc.y + v.y; acc.z = acc.z + v.z;
-        acc.w = acc.w + 1.0f;
-    }
-    accum[at] = acc;
-}
-
-// In front of a fed launch's render kernel, on its stream: the frames the launch starts with go into the device mirror by ONE wave (left to the render kernel, every
-// workgroup would fetch them across PCIe in its first top-up: a thousand times the same reads).
-__global__ __launch_bounds__(64) void feed_prefill_kernel(FeedDev *fd, const FeedHost *fh, int n_frames) {
-    const int lane = threadIdx.x;
-    for (int f = lane; f < n_frames; f += 64) fd->seeds[f] = (unsigned long long)__float_as_uint(fh->seeds[f].x) | ((unsigned long long)__float_as_uint(fh->seeds[f].y) << 32);
-    for (int c = lane; c <= (n_frames - 1) / kFeedChunkFrames; c += 64) fd->chunks[c] = (unsigned long long)fh->chunks[c];
-    if (lane == 0) fd->frames_known = (unsigned)n_frames;
-}
-
-// The same pass behind a FED launch: the frames are however many the launch ended up taking (FeedDev::frames_known, final once the render kernel has ended) and their
-// planes lie in chunks of kFeedChunkFrames frames.  Same order of additions: frame by frame, sample by sample.
-__global__ __launch_bounds__(256) void accumulate_feed_kernel(float4 *accum, int pitch_f4, int width, int rows, const FeedDev *fd, int n_samples) {
-    const int x = blockIdx.x * 64 + (threadIdx.x & 63);
-    const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (x >= width || y >= rows) return;
-    const size_t at = (size_t)y * pitch_f4 + x, plane = (size_t)rows * pitch_f4;
-    const int n_frames = (int)(fd->frames_known & ~kFeedClosed);
-    float4 acc = accum[at];
-    for (int f = 0; f < n_frames; f++) {
-        const float4 *chunk = reinterpret_cast<const float4 *>(fd->chunks[f / kFeedChunkFrames]) + (size_t)(f % kFeedChunkFrames) * (size_t)n_samples * plane;
-        for (int k = 0; k < n_samples; k++) {
-            const float4 v = chunk[(size_t)k * plane + at];
-            acc.x = acc.x + v.x; acc.y = acc.y + v.y; acc.z = acc.z + v.z;
-            acc.w = acc.w + 1.0f;
-        }
-    }
-    accum[at] = acc;
-}
+// The pass that adds a launch's sample planes to the accumulator (plain, fed, adaptive, with the moments plane, presenting) and feed_prefill_kernel: accumulate.hip.h.
 
 // ------------------------------------------------------------------------------------------ adaptive sampling (glrtx_render_adaptive)
 // The selection at the start of an adaptive call: which 8x8 tiles of the owned rows (the wavefront kernel's tiles, tiles8_x x tiles8_y, partial at the right and
@@ -2970,29 +2925,7 @@ __global__ __launch_bounds__(kAdaptCompactThreads) void adaptive_compact_kernel(
     if (i == kAdaptCompactThreads - 1) *count = (unsigned)part[i];
 }
 
-// The accumulation pass of an adaptive launch: the sample planes (frame by frame, sample by sample, as accumulate_planes_kernel) of ACTIVE tiles only -- an inactive
-// tile's planes were not written and its accumulator and H entries are not touched.  A sample also goes into the half buffer H when the pixel's count before the add
-// is odd: H holds every second sample.
-__global__ __launch_bounds__(256) void accumulate_adaptive_kernel(float4 *accum, float4 *half, int pitch_f4, int width, int rows, const float4 *planes, int n_planes,
-                                                                  const unsigned char *mask, int tiles8_x) {
-    const int x = blockIdx.x * 64 + (threadIdx.x & 63);
-    const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (x >= width || y >= rows) return;
-    if (mask[(y >> 3) * tiles8_x + (x >> 3)] == 0) return;
-    const size_t at = (size_t)y * pitch_f4 + x, plane = (size_t)rows * pitch_f4;
-    float4 acc = accum[at], h = half[at];
-    for (int k = 0; k < n_planes; k++) {
-        const float4 v = planes[(size_t)k * plane + at];
-        if (((unsigned)acc.w & 1u) != 0u) {
-            h.x = h.x + v.x; h.y = h.y + v.y; h.z = h.z + v.z;
-            h.w = h.w + 1.0f;
-        }
-        acc.x = acc.x + v.x; acc.y = acc.y + v.y; acc.z = acc.z + v.z;
-        acc.w = acc.w + 1.0f;
-    }
-    accum[at] = acc;
-    half[at] = h;
-}
+// (The accumulation pass of an adaptive launch -- active tiles only, every second sample into H: accumulate.hip.h, the Half sink.)
 
 // ------------------------------------------------------------------------------------------ resolve
 // screen.frag:15-25 (rgb / count, clamp, pow(., 1 / u_gamma)) + the RGBA8 colour buffer it is drawn into and
@@ -3107,58 +3040,6 @@ __global__ __launch_bounds__(256) void resolve_kernel(const float4 *accum, int p
 constexpr int kResolvePer = 2;
 inline dim3 resolve_grid(int width, int rows, int per = kResolvePer) { return dim3((unsigned)(((size_t)((width + 64 * per - 1) / (64 * per)) * (size_t)rows + 3) / 4)); }
 
-// ------------------------------------------------------------------------------------------ presentation (fused accumulate + resolve)
-// The presenting twins of accumulate_planes_kernel and accumulate_feed_kernel (glrtx_present_enable): the same chain of additions per pixel -- the accumulator is
-// loaded once, frame by frame, sample by sample, stored once -- and behind every frame f the pixel's screen.frag value (rs_pixel, byte-identical to resolve_kernel's)
-// goes into image slot (slot0 + f) % n_ring of the device ring, packed rows of `width` texels, row y at rows - 1 - y when flipped (within the owned rows, like
-// glrtx_resolve_rgba8).  One launch and one read of the accumulator per launch instead of a pass plus a resolve per frame.  A wave is 64 consecutive texels of a row:
-// lanes past the row's end stay in it with the texel (0, 0, 0, 1), because rs_pixel votes across the wave.
-DEV void present_store(uchar4 *ring, size_t slot_px, int n_ring, int slot0, int f, int width, int rows, int x, int y, int flip, uchar4 px) {
-    const int oy = flip ? rows - 1 - y : y;
-    ring[(size_t)((slot0 + f) % n_ring) * slot_px + (size_t)oy * width + x] = px;
-}
-__global__ __launch_bounds__(256) void accumulate_present_planes_kernel(float4 *accum, int pitch_f4, int width, int rows, const float4 *planes, int n_frames,
-                                                                        int n_samples, uchar4 *ring, size_t slot_px, int n_ring, int slot0, float inv_gamma, int flip) {
-    const int x = blockIdx.x * 64 + (threadIdx.x & 63);
-    const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (y >= rows) return;  // (a whole wave)
-    const bool in = x < width;
-    const size_t at = (size_t)y * pitch_f4 + x, plane = (size_t)rows * pitch_f4;
-    float4 acc = in ? accum[at] : make_float4(0.f, 0.f, 0.f, 1.f);
-    for (int f = 0; f < n_frames; f++) {
-        if (in)
-            for (int k = 0; k < n_samples; k++) {
-                const float4 v = planes[((size_t)f * n_samples + k) * plane + at];
-                acc.x = acc.x + v.x; acc.y = acc.y + v.y; acc.z = acc.z + v.z;
-                acc.w = acc.w + 1.0f;
-            }
-        const uchar4 px = rs_pixel(acc, inv_gamma);  // (every lane of the wave)
-        if (in) present_store(ring, slot_px, n_ring, slot0, f, width, rows, x, y, flip, px);
-    }
-    if (in) accum[at] = acc;
-}
-__global__ __launch_bounds__(256) void accumulate_present_feed_kernel(float4 *accum, int pitch_f4, int width, int rows, const FeedDev *fd, int n_samples,
-                                                                      uchar4 *ring, size_t slot_px, int n_ring, int slot0, float inv_gamma, int flip) {
-    const int x = blockIdx.x * 64 + (threadIdx.x & 63);
-    const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (y >= rows) return;  // (a whole wave)
-    const bool in = x < width;
-    const size_t at = (size_t)y * pitch_f4 + x, plane = (size_t)rows * pitch_f4;
-    const int n_frames = (int)(fd->frames_known & ~kFeedClosed);
-    float4 acc = in ? accum[at] : make_float4(0.f, 0.f, 0.f, 1.f);
-    for (int f = 0; f < n_frames; f++) {
-        if (in) {
-            const float4 *chunk = reinterpret_cast<const float4 *>(fd->chunks[f / kFeedChunkFrames]) + (size_t)(f % kFeedChunkFrames) * (size_t)n_samples * plane;
-            for (int k = 0; k < n_samples; k++) {
-                const float4 v = chunk[(size_t)k * plane + at];
-                acc.x = acc.x + v.x; acc.y = acc.y + v.y; acc.z = acc.z + v.z;
-                acc.w = acc.w + 1.0f;
-            }
-        }
-        const uchar4 px = rs_pixel(acc, inv_gamma);  // (every lane of the wave)
-        if (in) present_store(ring, slot_px, n_ring, slot0, f, width, rows, x, y, flip, px);
-    }
-    if (in) accum[at] = acc;
-}
+// (Presentation, glrtx_present_enable: the pass that accumulates and stores an image behind every frame is accumulate.hip.h's Present sink.)
 
 }  // namespace glrtx

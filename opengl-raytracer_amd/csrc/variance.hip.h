@@ -5,8 +5,8 @@
 // No reference counterpart.  The arithmetic is the header's text: host/variance.cpp and tests/variance_math.py state it again, and all three agree bit for bit
 // under denoise.hip.h's rules (one correctly rounded fp32 operation at a time in the order written, -ffp-contract=off; denormals flushed; a stored NaN is 0x7FC00000).
 //
-//   accumulate_moments_kernel  accumulate_planes_kernel with a second read-modify-write: every sample plane is added to the accumulator (the same chain of
-//       additions, so the accumulator is glrtx_render_frames') and its luminance and squared luminance to the moments plane M.  Bandwidth-bound like its twin.
+//   accumulate_moments_kernel  lives in accumulate.hip.h (the one accumulation pass, its Moments sink; still in this namespace): every sample plane is added to the
+//       accumulator (the same chain of additions, so the accumulator is glrtx_render_frames') and its luminance and squared luminance to the moments plane M.
 //   variance_estimate  the filter's shape: a workgroup owns a 16x16 tile, a wave an 8x8 sub-tile in tile order; tile + a 3-pixel halo (22^2 pixels) is staged in
 //       LDS as two float4 per pixel -- {mu1, mu2, id, M.w} and the feature plane's {n, t}, 15.1 KiB -- from four 16-byte loads per pixel (accumulator, M, A, N).
 //       A dead or outside pixel is staged with the reserved id, so one compare per tap applies all three exclusions.  A pixel with M.w >= 4 needs no tap at all.
@@ -24,23 +24,6 @@ using denoise::lum;
 using denoise::tiny;
 
 DEV float max0(float x) { return x > 0.0f ? x : 0.0f; }
-
-__global__ __launch_bounds__(256) void accumulate_moments_kernel(float4 *accum, float4 *moments, int pitch_f4, int width, int rows, const float4 *planes, int n_planes) {
-    const int x = blockIdx.x * 64 + (threadIdx.x & 63);
-    const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (x >= width || y >= rows) return;
-    const size_t at = (size_t)y * pitch_f4 + x, plane = (size_t)rows * pitch_f4;
-    float4 acc = accum[at], m = moments[at];
-    for (int k = 0; k < n_planes; k++) {
-        const float4 v = planes[(size_t)k * plane + at];
-        const float l = lum(v.x, v.y, v.z);
-        m.x = m.x + l; m.y = m.y + l * l; m.w = m.w + 1.0f;
-        acc.x = acc.x + v.x; acc.y = acc.y + v.y; acc.z = acc.z + v.z;
-        acc.w = acc.w + 1.0f;
-    }
-    accum[at] = acc;
-    moments[at] = m;
-}
 
 struct Args {
     const float4 *accum;    // pitch_f4 per row
