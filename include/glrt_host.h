@@ -203,6 +203,13 @@ int glrt_exposure_measure(const float *src, int width, int rows, float key, int 
 int glrt_tonemap(const float *src, int width, int rows, int op, int auto_exposure, float exposure, float E, float white, float gamma, int flip_y, float *t_out,
                  uint8_t *rgba8_out);
 
+/* Bloom: the CPU statement of the device's glrtx_bloom / glrtx_debug_bloom (include/glrtx.h "Bloom": the formulas are there), bit for bit (host/bloom.cpp;
+ * tests/bloom_math.py states them in numpy).  src: width x rows x 4 floats {rgb sum, count}, rows packed; threshold, strength and levels are glrtx_bloom_cfg's
+ * (its source has no meaning here).  d_out: the planes D_1 .. D_levels back to back, 4 floats a texel {rgb, 0} (the sum of w_k * h_k texels, w_{k+1} =
+ * (w_k + 1) >> 1); b_out: width x rows x 4 floats {x + strength * glow, 1}; either may be NULL.  Runs with denormals flushed (MXCSR FTZ | DAZ, restored on return).
+ * GLRT_HOST_EINVAL: a NULL src, a size outside 1..65536, levels outside 1..8, a threshold that is not finite and >= 0, a strength outside [0, 1e4]. */
+int glrt_bloom(const float *src, int width, int rows, float threshold, float strength, int levels, float *d_out, float *b_out);
+
 void glrt_look_at(const float eye[3], const float center[3], const float up[3], float out[16]);
 void glrt_perspective(float fovy_deg, float aspect, float z_near, float z_far, float out[16]);
 void glrt_mat4_mul(const float a[16], const float b[16], float out[16]);

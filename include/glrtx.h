@@ -748,6 +748,54 @@ int glrtx_debug_tonemap(const float *src, int width, int rows, const glrtx_tonem
  * measurement (histogram + reduce; E moves as after that many measurements). */
 int glrtx_debug_tonemap_burst(glrtx_ctx *ctx, const glrtx_tonemap_cfg *cfg, int which, int reps, float *ms_per_launch);
 
+/* ---- Bloom: a glow around over-bright pixels, added to the linear HDR image in front of the tone curve (no reference counterpart; off unless called: no other
+ * call changes what it does, and nothing here ever writes the accumulator, the denoised image D, the plane T but through glrtx_tonemap_bloomed, the moments, the
+ * exposure block, the adaptive half buffer, the present ring or the ray counts).  The SOURCE is the accumulator (source = 0) or D (source = 1), as in "Tone
+ * mapping".  Every call here runs on the context's stream and seals an open fed launch first.  The context owns the plane B (float4, packed rows of `width`, in
+ * the accumulator's {rgb, w} form with w = 1) and the pyramid D_1 .. D_levels; the first glrtx_bloom allocates them, glrtx_resize releases them.
+ *   glrtx_bloom                    fills B, below: 2 * levels kernel launches.  No host sync.
+ *   glrtx_read_bloomed             syncs, then copies B like glrtx_read_tonemapped.  GLRTX_EINVAL before a glrtx_bloom at the image's current shape.
+ *   glrtx_tonemap_bloomed          glrtx_tonemap with B as its source: writes T.  cfg->source is not read.  GLRTX_EINVAL before a glrtx_bloom at the current shape.
+ *   glrtx_resolve_bloomed_rgba8    glrtx_resolve_tonemapped_rgba8 with B as its source.  cfg->source is not read.  GLRTX_EINVAL before a glrtx_bloom likewise.
+ *                                  The exposure E is still measured by glrtx_exposure_measure on the unbloomed source; the curve reads it as it always does.
+ *   glrtx_debug_bloom              the kernels on caller arrays on the current HIP device, no context: src is width x rows float4, rows packed (cfg->source is
+ *                                  not read).  d_out receives D_1 .. D_levels packed back to back as float4 with w = 0 (the sum of w_k * h_k texels), copied before
+ *                                  the up chain runs; b_out receives B.  Either may be NULL.
+ *   glrtx_debug_bloom_burst        device time of one glrtx_bloom from `reps` of them back to back between one pair of events after a warm-up pass.
+ *   GLRTX_EINVAL, nothing changed: a NULL argument; source outside 0..1; a threshold that is not finite and >= 0; a strength that is not in [0, 1e4] (a NaN
+ *   among them); levels outside 1..8; no accumulator; source = 1 without a denoised image of the current shape; a partitioned context (world > 1: a seam per
+ *   stripe would be wrong); glrtx_debug_bloom's sizes outside 1..65536.  Groups: no call.
+ * The arithmetic (this text is the contract; glrt_bloom in glrt_host.h and tests/bloom_math.py state it again, and the three agree bit for bit).  Every fp32
+ * operation is one correctly rounded operation in the order written, unfused, denormals flushed on the way in and out, as in "Tone mapping"; selects are as written.
+ *   Pixel value.  I = src.rgb / src.w.  A pixel is DEAD as in "Tone mapping" (src.w a zero, a denormal or a NaN): x = {0, 0, 0}.  Otherwise per channel
+ *     x = I > 0 ? I : 0 (a NaN becomes 0);  x = x < 65504 ? x : 65504.
+ *   Bright pass.  l = lum(x) ("Variance guidance");  n = l - threshold;  n = n > 0 ? n : 0;  m = l > 1e-4f ? l : 1e-4f;  g = n / m (the IEEE quotient);
+ *     D_0 = x * g per channel.  From here on every value is finite and >= 0.
+ *   Down chain, k = 0 .. levels - 1.  Level 0 has the image's size w_0 x h_0 (owned rows);  w_{k+1} = (w_k + 1) >> 1, likewise h.
+ *     c5(a, b, c, d, e) = ((a + e) + 4 * (b + d)) + 6 * c.  Clamp to edge: X(i) = clamp(2x + i, 0, w_k - 1), Y(j) = clamp(2y + j, 0, h_k - 1).
+ *     r_j = c5(D_k(X(-2), Y(j)), D_k(X(-1), Y(j)), D_k(X(0), Y(j)), D_k(X(1), Y(j)), D_k(X(2), Y(j)))  for j = -2 .. 2
+ *     D_{k+1}(x, y) = c5(r_-2, r_-1, r_0, r_1, r_2) * 0x1p-8f        (Burt and Adelson's binomial kernel, horizontal first; every weight is dyadic)
+ *   Up chain.  up(C, w, h) of a wc x hc plane C:  near = x >> 1;  far = (x & 1) ? near + 1 : near - 1, both clamped to [0, wc - 1];
+ *     hz(x, cy) = 0.75f * C(near, cy) + 0.25f * C(far, cy);  vertically the same rule on hz:  up(x, y) = 0.75f * hz(x, near_y) + 0.25f * hz(x, far_y).
+ *     U_levels = D_levels;  for k = levels - 1 down to 1:  U_k = D_k + up(U_{k+1}, w_k, h_k);  glow = up(U_1, w_0, h_0) * (1.0f / (float)levels).
+ *   B = {x + strength * glow, 1}.
+ *   It follows that (1) a uniform image {0.5, 0.5, 0.5, 1} with threshold 0, strength 1 and levels 1, 2, 4 or 8 gives B.rgb == 1.0f at every pixel of every
+ *   size, bit for bit; (2) when no pixel's luminance exceeds the threshold, and whenever strength is 0, B.rgb is x, bit for bit; (3) B is finite for every input.
+ * The defaults -- threshold 1, strength 0.25, five levels -- are conventional values, not tuned on anything.
+ * Out of scope: the present ring, groups and partitioned contexts; lens dirt, anamorphic streaks, a soft knee; measuring the exposure on B. */
+typedef struct glrtx_bloom_cfg {
+    int   source;     /* 0 = accumulator mean, 1 = denoised image D (as glrtx_tonemap_cfg.source) */
+    float threshold;  /* luminance above which a pixel glows; finite, >= 0; default 1 */
+    float strength;   /* finite, 0 <= strength <= 1e4; default 0.25 */
+    int   levels;     /* 1..8; default 5 */
+} glrtx_bloom_cfg;
+int glrtx_bloom(glrtx_ctx *ctx, const glrtx_bloom_cfg *cfg);
+int glrtx_read_bloomed(glrtx_ctx *ctx, float *dst_rgba, size_t dst_pitch_bytes);
+int glrtx_tonemap_bloomed(glrtx_ctx *ctx, const glrtx_tonemap_cfg *cfg);
+int glrtx_resolve_bloomed_rgba8(glrtx_ctx *ctx, uint8_t *dst, size_t dst_pitch_bytes, const glrtx_tonemap_cfg *cfg);
+int glrtx_debug_bloom(const float *src, int width, int rows, const glrtx_bloom_cfg *cfg, float *d_out, float *b_out);
+int glrtx_debug_bloom_burst(glrtx_ctx *ctx, const glrtx_bloom_cfg *cfg, int reps, float *ms_per_call);
+
 /* ---- Groups: the same device layer on several GPUs of one node, behind one handle and one host thread.
  * No reference counterpart (the reference is single-GPU); SURVEY.md 8(b) sketches glrtx_create(ctx**, device_ids, n) with a
  * gathering read_accum -- this is that, kept apart from the single-context calls.  Member i owns the 8-row stripes s with

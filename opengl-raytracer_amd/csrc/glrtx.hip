@@ -30,6 +30,7 @@
 #include "reproject.hip.h"
 #include "reproject_motion.hip.h"
 #include "tonemap.hip.h"
+#include "bloom.hip.h"
 #include "../host/reproject_setup.h"
 static_assert(glrtx::lbvh::kRotationPasses == GLRT_LBVH_ROTATION_PASSES, "device and CPU LBVH statements must run the same rotation sweeps");
 static_assert(glrtx::lbvh::kRebuildLeaves == GLRT_LBVH_REBUILD_LEAVES, "device and CPU LBVH statements must rebuild the same subtrees");
@@ -219,6 +220,10 @@ struct glrtx_ctx {
     // zeroed on first use, kept across glrtx_resize) and the plane T (packed rows of tm_w float4 over tm_rows rows; released by glrtx_resize)
     DevBuf tmExp, tmT;
     int tm_w = 0, tm_rows = -1;   // (-1: no T)
+
+    // Bloom (glrtx_bloom): the plane B (packed rows of bl_w float4 over bl_rows rows) and the pyramid D_1 .. D_8 behind it; both released by glrtx_resize
+    DevBuf blB, blPyr;
+    int bl_w = 0, bl_rows = -1;   // (-1: no B)
 
     bool count_rays = false;
     const char *last_kernel = "";  // name of the last render kernel launched (error reports)
@@ -1834,6 +1839,80 @@ int tonemap_resolve_pass(glrtx_ctx *c, hipStream_t stream, const float4 *src, in
     return GLRTX_OK;
 }
 
+// ---- bloom (glrtx_bloom, glrtx_debug_bloom)
+// The sizes of the levels 0 .. levels and where D_k (k >= 1) starts in the packed pyramid, in float4.
+struct BloomLevels {
+    int n, w[9], h[9];
+    size_t at[10];  // at[k]: D_k's first texel; at[n + 1]: the pyramid's size
+};
+BloomLevels bloom_levels(int width, int rows, int levels) {
+    BloomLevels L{};
+    L.n = levels; L.w[0] = width; L.h[0] = rows;
+    L.at[0] = L.at[1] = 0;
+    for (int k = 1; k <= levels; k++) {
+        L.w[k] = (L.w[k - 1] + 1) >> 1; L.h[k] = (L.h[k - 1] + 1) >> 1;
+        L.at[k + 1] = L.at[k] + (size_t)L.w[k] * (size_t)L.h[k];
+    }
+    return L;
+}
+
+// Everything a call that takes a glrtx_bloom_cfg refuses about the cfg itself, checked before anything changes.
+int bloom_cfg_check(glrtx_ctx *c, const glrtx_bloom_cfg *k, const char *fn) {
+    if (!k) return fail(c, GLRTX_EINVAL, "%s: NULL cfg", fn);
+    if (k->source < 0 || k->source > 1) return fail(c, GLRTX_EINVAL, "%s: source %d outside 0..1", fn, k->source);
+    if (!(k->threshold >= 0.0f) || std::isinf(k->threshold)) return fail(c, GLRTX_EINVAL, "%s: threshold %g is not a finite number >= 0", fn, (double)k->threshold);
+    if (!(k->strength >= 0.0f && k->strength <= 1.0e4f)) return fail(c, GLRTX_EINVAL, "%s: strength %g outside [0, 1e4]", fn, (double)k->strength);
+    if (k->levels < 1 || k->levels > 8) return fail(c, GLRTX_EINVAL, "%s: levels %d outside 1..8", fn, k->levels);
+    return GLRTX_OK;
+}
+
+// The context checks every call that takes a glrtx_bloom_cfg shares, and the source the cfg names.
+int bloom_source(glrtx_ctx *c, const glrtx_bloom_cfg *k, const char *fn, const float4 *&src, int &pitch_f4) {
+    if (int rc = bloom_cfg_check(c, k, fn)) return rc;
+    if (!c->accum || c->width < 1 || c->owned_rows < 1) return fail(c, GLRTX_EINVAL, "%s: no accumulator (call glrtx_resize)", fn);
+    if (c->world > 1) return fail(c, GLRTX_EINVAL, "%s: the context is partitioned (rank %d of %d): the glow would stop at every stripe's seam", fn, c->rank, c->world);
+    if (k->source == 1) {
+        if (!c->dn_have || !c->dnD.p || c->ft_w != c->width || c->ft_rows != c->owned_rows)
+            return fail(c, GLRTX_EINVAL, "%s: source = 1 without a denoised image of the current shape (call glrtx_denoise or glrtx_denoise_variance first)", fn);
+        src = (const float4 *)c->dnD.p; pitch_f4 = c->width;
+    } else {
+        src = c->accum; pitch_f4 = (int)(c->pitch_bytes / sizeof(float4));
+    }
+    return GLRTX_OK;
+}
+
+// The down chain on `stream`: the source through the bright pass to D_1, then D_1 .. D_levels into the packed pyramid.
+int bloom_down_passes(glrtx_ctx *c, hipStream_t stream, const float4 *src, int pitch_f4, const BloomLevels &L, float4 *pyr, const glrtx_bloom_cfg &k) {
+    hipLaunchKernelGGL(bloom::bloom_down<true>, bloom::down_grid(L.w[1], L.h[1]), dim3(256), 0, stream, src, pitch_f4, L.w[0], L.h[0], pyr + L.at[1], L.w[1], L.h[1],
+                       k.threshold);
+    HIP_TRY(c, hipGetLastError());
+    for (int j = 1; j < L.n; j++) {
+        hipLaunchKernelGGL(bloom::bloom_down<false>, bloom::down_grid(L.w[j + 1], L.h[j + 1]), dim3(256), 0, stream, (const float4 *)(pyr + L.at[j]), L.w[j], L.w[j],
+                           L.h[j], pyr + L.at[j + 1], L.w[j + 1], L.h[j + 1], 0.0f);
+        HIP_TRY(c, hipGetLastError());
+    }
+    return GLRTX_OK;
+}
+// The up chain: U_k over D_k for k = levels - 1 .. 1, then B from U_1 and the source.
+int bloom_up_passes(glrtx_ctx *c, hipStream_t stream, const float4 *src, int pitch_f4, const BloomLevels &L, float4 *pyr, float4 *B, const glrtx_bloom_cfg &k) {
+    for (int j = L.n - 1; j >= 1; j--) {
+        hipLaunchKernelGGL(bloom::bloom_up<false>, bloom::up_grid(L.w[j], L.h[j]), dim3(256), 0, stream, (const float4 *)(pyr + L.at[j + 1]), L.w[j + 1], L.h[j + 1],
+                           pyr + L.at[j], L.w[j], L.h[j], (const float4 *)nullptr, 0, (float4 *)nullptr, 0.0f, 0.0f);
+        HIP_TRY(c, hipGetLastError());
+    }
+    hipLaunchKernelGGL(bloom::bloom_up<true>, bloom::up_grid(L.w[0], L.h[0]), dim3(256), 0, stream, (const float4 *)(pyr + L.at[1]), L.w[1], L.h[1], (float4 *)nullptr,
+                       L.w[0], L.h[0], src, pitch_f4, B, k.strength, 1.0f / (float)k.levels);
+    HIP_TRY(c, hipGetLastError());
+    return GLRTX_OK;
+}
+// B's and the pyramid's allocations (the pyramid always at its eight-level size: a shape has one)
+int bloom_ensure(glrtx_ctx *c) {
+    const size_t px = (size_t)c->width * (size_t)c->owned_rows;
+    if (int rc = ensure(c, c->blB, px * sizeof(float4))) return rc;
+    return ensure(c, c->blPyr, bloom_levels(c->width, c->owned_rows, 8).at[9] * sizeof(float4));
+}
+bool bloom_have(const glrtx_ctx *c) { return c->blB.p && c->bl_w == c->width && c->bl_rows == c->owned_rows; }
+
 }  // namespace
 
 extern "C" {
@@ -1951,6 +2030,7 @@ void glrtx_destroy(glrtx_ctx *c) {
     dev_free(c->adHalf); dev_free(c->adMask); dev_free(c->adList); dev_free(c->adCount);
     dev_free(c->mmM); dev_free(c->mmM_spare);
     dev_free(c->tmExp); dev_free(c->tmT);
+    dev_free(c->blB); dev_free(c->blPyr);
     denoise_release(c);
     dev_free(c->mtPos); dev_free(c->mtNrm);
     dev_free(c->wfState); dev_free(c->wfQ); dev_free(c->wfSeeds); dev_free(c->wfPlanes);
@@ -2502,6 +2582,7 @@ int glrtx_resize(glrtx_ctx *c, int width, int height) {
     denoise_release(c);  // (the feature planes and the filter's images have the old shape; the stream is idle)
     dev_free(c->mmM); dev_free(c->mmM_spare);  // (so has the moments plane: allocated again on its next use)
     dev_free(c->tmT); c->tm_w = 0; c->tm_rows = -1;  // (and the tone-mapped plane; the exposure block has no shape and stays)
+    dev_free(c->blB); dev_free(c->blPyr); c->bl_w = 0; c->bl_rows = -1;  // (and the bloomed plane with its pyramid)
     c->width = width; c->height = height;
     c->owned_rows = owned_rows_of(height, c->rank, c->world, c->stripe);
     c->st.width = width; c->st.height = height; c->st.owned_rows = c->owned_rows;
@@ -3116,6 +3197,125 @@ int glrtx_debug_tonemap_burst(glrtx_ctx *c, const glrtx_tonemap_cfg *cfg, int wh
     return GLRTX_OK;
 }
 
+
+// ---- bloom
+int glrtx_bloom(glrtx_ctx *c, const glrtx_bloom_cfg *cfg) {
+    const char *fn = "glrtx_bloom";
+    if (!c) return GLRTX_EINVAL;
+    const float4 *src = nullptr;
+    int pitch_f4 = 0;
+    if (int rc = bloom_source(c, cfg, fn, src, pitch_f4)) return rc;
+    seal_feed(c);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (int rc = bloom_ensure(c)) return rc;
+    c->bl_w = c->width; c->bl_rows = c->owned_rows;
+    const BloomLevels L = bloom_levels(c->width, c->owned_rows, cfg->levels);
+    if (int rc = bloom_down_passes(c, c->stream, src, pitch_f4, L, (float4 *)c->blPyr.p, *cfg)) return rc;
+    return bloom_up_passes(c, c->stream, src, pitch_f4, L, (float4 *)c->blPyr.p, (float4 *)c->blB.p, *cfg);
+}
+
+int glrtx_read_bloomed(glrtx_ctx *c, float *dst, size_t dst_pitch_bytes) {
+    const char *fn = "glrtx_read_bloomed";
+    if (!c || !dst) return GLRTX_EINVAL;
+    if (!bloom_have(c)) return fail(c, GLRTX_EINVAL, "%s: no bloomed plane (call glrtx_bloom first)", fn);
+    const size_t row = (size_t)c->width * sizeof(float4);
+    if (dst_pitch_bytes < row) return fail(c, GLRTX_EINVAL, "%s: dst pitch too small", fn);
+    if (int rc = glrtx_sync(c)) return rc;
+    HIP_TRY(c, hipMemcpy2D(dst, dst_pitch_bytes, c->blB.p, row, row, (size_t)c->owned_rows, hipMemcpyDeviceToHost));
+    return GLRTX_OK;
+}
+
+// glrtx_tonemap with B as its source: tonemap_plane, B -> T.
+int glrtx_tonemap_bloomed(glrtx_ctx *c, const glrtx_tonemap_cfg *cfg) {
+    const char *fn = "glrtx_tonemap_bloomed";
+    if (!c) return GLRTX_EINVAL;
+    if (!cfg) return fail(c, GLRTX_EINVAL, "%s: NULL cfg", fn);
+    glrtx_tonemap_cfg k = *cfg;
+    k.source = 0;  // (not read: the source is B)
+    if (int rc = tonemap_cfg_check(c, &k, fn)) return rc;
+    if (!bloom_have(c)) return fail(c, GLRTX_EINVAL, "%s: no bloomed plane (call glrtx_bloom first)", fn);
+    seal_feed(c);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (int rc = exposure_ensure(c)) return rc;
+    if (int rc = ensure(c, c->tmT, (size_t)c->width * (size_t)c->owned_rows * sizeof(float4))) return rc;
+    c->tm_w = c->width; c->tm_rows = c->owned_rows;
+    return tonemap_plane_pass(c, c->stream, (const float4 *)c->blB.p, c->width, c->width, c->owned_rows, (float4 *)c->tmT.p, (const tonemap::Exposure *)c->tmExp.p, k);
+}
+
+// glrtx_resolve_tonemapped_rgba8 with B as its source: tonemap_resolve, B -> bytes.
+int glrtx_resolve_bloomed_rgba8(glrtx_ctx *c, uint8_t *dst, size_t dst_pitch_bytes, const glrtx_tonemap_cfg *cfg) {
+    const char *fn = "glrtx_resolve_bloomed_rgba8";
+    if (!c || !dst) return GLRTX_EINVAL;
+    if (!cfg) return fail(c, GLRTX_EINVAL, "%s: NULL cfg", fn);
+    glrtx_tonemap_cfg k = *cfg;
+    k.source = 0;  // (not read: the source is B)
+    if (int rc = tonemap_cfg_check(c, &k, fn)) return rc;
+    if (!bloom_have(c)) return fail(c, GLRTX_EINVAL, "%s: no bloomed plane (call glrtx_bloom first)", fn);
+    if (dst_pitch_bytes < (size_t)c->width * 4) return fail(c, GLRTX_EINVAL, "%s: dst pitch too small", fn);
+    seal_feed(c);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (int rc = exposure_ensure(c)) return rc;
+    if (int rc = ensure(c, c->rgba8, (size_t)c->width * 4 * (size_t)c->owned_rows)) return rc;
+    if (int rc = tonemap_resolve_pass(c, c->stream, (const float4 *)c->blB.p, c->width, c->width, c->owned_rows, (uchar4 *)c->rgba8.p,
+                                      (const tonemap::Exposure *)c->tmExp.p, k)) return rc;
+    if (int rc = glrtx_sync(c)) return rc;
+    HIP_TRY(c, hipMemcpy2D(dst, dst_pitch_bytes, c->rgba8.p, (size_t)c->width * 4, (size_t)c->width * 4, (size_t)c->owned_rows, hipMemcpyDeviceToHost));
+    return GLRTX_OK;
+}
+
+int glrtx_debug_bloom(const float *src, int width, int rows, const glrtx_bloom_cfg *cfg, float *d_out, float *b_out) {
+    const char *fn = "glrtx_debug_bloom";
+    if (width < 1 || rows < 1 || width > 65536 || rows > 65536) return fail(nullptr, GLRTX_EINVAL, "%s: bad size %dx%d", fn, width, rows);
+    if (!src) return fail(nullptr, GLRTX_EINVAL, "%s: NULL buffer", fn);
+    if (int rc = bloom_cfg_check(nullptr, cfg, fn)) return rc;
+    const size_t px = (size_t)width * rows;
+    const BloomLevels L = bloom_levels(width, rows, cfg->levels);
+    const size_t pyr_bytes = L.at[L.n + 1] * sizeof(float4);
+    DebugScratch s;
+    const float4 *in = s.alloc(px * sizeof(float4), src);
+    float4 *pyr = s.alloc(pyr_bytes);
+    float4 *B = s.alloc(px * sizeof(float4));
+    int rc = GLRTX_OK;
+    if (s.ok()) rc = bloom_down_passes(nullptr, 0, in, width, L, pyr, *cfg);
+    if (rc == GLRTX_OK) {
+        s.sync();
+        s.download(d_out, pyr, pyr_bytes);  // (D_1 .. D_levels, before the up chain turns them into U_k)
+    }
+    if (s.ok() && rc == GLRTX_OK) rc = bloom_up_passes(nullptr, 0, in, width, L, pyr, B, *cfg);
+    if (rc == GLRTX_OK) {
+        s.sync();
+        s.download(b_out, B, px * sizeof(float4));
+    }
+    return s.result(rc, fn);
+}
+
+// Device time of one glrtx_bloom (2 * levels launches) by itself, as glrtx_debug_tonemap_burst measures its passes: `reps` calls' launches back to back between
+// one pair of events, after a warm-up pass.  Leaves B as glrtx_bloom does.
+int glrtx_debug_bloom_burst(glrtx_ctx *c, const glrtx_bloom_cfg *cfg, int reps, float *ms_per_call) {
+    const char *fn = "glrtx_debug_bloom_burst";
+    if (!c || !ms_per_call || reps < 1) return GLRTX_EINVAL;
+    const float4 *src = nullptr;
+    int pitch_f4 = 0;
+    if (int rc = bloom_source(c, cfg, fn, src, pitch_f4)) return rc;
+    seal_feed(c);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (int rc = bloom_ensure(c)) return rc;
+    c->bl_w = c->width; c->bl_rows = c->owned_rows;
+    const BloomLevels L = bloom_levels(c->width, c->owned_rows, cfg->levels);
+    for (int pass = 0; pass < 2; pass++) {  // (the first pass warms the device up)
+        HIP_TRY(c, hipEventRecord(c->rs0, c->stream));
+        for (int i = 0; i < reps; i++) {
+            if (int rc = bloom_down_passes(c, c->stream, src, pitch_f4, L, (float4 *)c->blPyr.p, *cfg)) return rc;
+            if (int rc = bloom_up_passes(c, c->stream, src, pitch_f4, L, (float4 *)c->blPyr.p, (float4 *)c->blB.p, *cfg)) return rc;
+        }
+        HIP_TRY(c, hipEventRecord(c->rs1, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    float ms = 0.f;
+    HIP_TRY(c, hipEventElapsedTime(&ms, c->rs0, c->rs1));
+    *ms_per_call = ms / (float)reps;
+    return GLRTX_OK;
+}
 
 // ---- reprojection (glrtx_reproject)
 static int reproject_setup_check(glrtx_ctx *c, const char *fn, const float *c2w_prev, const float *s2c_prev, const glrtx_reproject_cfg *cfg, glrt_detail::ReprojectSetup &st) {

@@ -15,7 +15,7 @@
 using namespace glrt;
 
 static void usage(const char *exe) {
-    std::printf("usage: %s -i scene.json [-s N] [--max-depth D] [--spp N] [--frames F] [--frames-in-flight B] [--bvh sah|sah-reinsert|sah-gpu|lbvh|sah-levels-cpu|lbvh-cpu|reference] [--order-by-hits] [--out file.png] [--save-every-frame] [--device G | --gpus N | --devices a,b,..] [--extensions] [--whitted] [--enable-volume] [--volume-wavefront] [--adaptive THRESHOLD [--min-spp N]] [--denoise | --denoise-variance [--denoise-iters N]] [--tonemap clamp|reinhard|aces [--exposure X] [--auto-exposure]]\n"
+    std::printf("usage: %s -i scene.json [-s N] [--max-depth D] [--spp N] [--frames F] [--frames-in-flight B] [--bvh sah|sah-reinsert|sah-gpu|lbvh|sah-levels-cpu|lbvh-cpu|reference] [--order-by-hits] [--out file.png] [--save-every-frame] [--device G | --gpus N | --devices a,b,..] [--extensions] [--whitted] [--enable-volume] [--volume-wavefront] [--adaptive THRESHOLD [--min-spp N]] [--denoise | --denoise-variance [--denoise-iters N]] [--tonemap clamp|reinhard|aces [--exposure X] [--auto-exposure]] [--bloom [--bloom-threshold T] [--bloom-strength S] [--bloom-levels N]]\n"
                 "  -i, --input             scene description (JSON; schema: SURVEY.md Appendix C)            [required]\n"
                 "  -s, --sample-per-cycle  accepted for compatibility; like the reference (main.cpp:13) it is not read\n"
                 "      --max-depth D       u_maxDepth (default 16, the reference shader's default)\n"
@@ -49,7 +49,12 @@ static void usage(const char *exe) {
                 "                          the denoised image with --denoise / --denoise-variance (one device; not with --save-every-frame).  Without it the output is\n"
                 "                          what it always was\n"
                 "      --exposure X        with --tonemap: linear multiplier in front of the curve (default 1)\n"
-                "      --auto-exposure     with --tonemap: multiply by the exposure measured from the image's luminance histogram as well (key 0.18)\n", exe);
+                "      --auto-exposure     with --tonemap: multiply by the exposure measured from the image's luminance histogram as well (key 0.18)\n"
+                "      --bloom             add a glow around over-bright pixels to the linear image in front of the curve (an image pyramid: glrtx_bloom); after\n"
+                "                          --denoise* if given; without --tonemap the curve is clamp (one device; not with --save-every-frame)\n"
+                "      --bloom-threshold T with --bloom: luminance above which a pixel glows, >= 0 (default 1)\n"
+                "      --bloom-strength S  with --bloom: weight of the glow, 0..1e4 (default 0.25)\n"
+                "      --bloom-levels N    with --bloom: pyramid levels, 1..8 (default 5)\n", exe);
 }
 
 int main(int argc, char **argv) {
@@ -63,6 +68,9 @@ int main(int argc, char **argv) {
     int tonemap_op = -1;
     float exposure = 1.0f;
     bool exposure_given = false, auto_exposure = false;
+    bool bloom = false, bloom_opt = false;
+    float bloom_threshold = 1.0f, bloom_strength = 0.25f;
+    int bloom_levels = 5;
     std::vector<int> devices;
     std::string bvh;
     for (int i = 1; i < argc; i++) {
@@ -98,6 +106,10 @@ int main(int argc, char **argv) {
         }
         else if (a == "--exposure") { exposure = (float)std::atof(next("--exposure")); exposure_given = true; }
         else if (a == "--auto-exposure") auto_exposure = true;
+        else if (a == "--bloom") bloom = true;
+        else if (a == "--bloom-threshold") { bloom_threshold = (float)std::atof(next("--bloom-threshold")); bloom_opt = true; }
+        else if (a == "--bloom-strength") { bloom_strength = (float)std::atof(next("--bloom-strength")); bloom_opt = true; }
+        else if (a == "--bloom-levels") { bloom_levels = std::atoi(next("--bloom-levels")); bloom_opt = true; }
         else if (a == "--gpus") { const int n = std::atoi(next("--gpus")); devices.clear(); for (int k = 0; k < n; k++) devices.push_back(k); }
         else if (a == "--devices") {
             devices.clear();
@@ -122,6 +134,12 @@ int main(int argc, char **argv) {
         std::fprintf(stderr, "--denoise-variance: --frames-in-flight %d is above the 1024 frames one glrtx_render_moments burst takes\n", in_flight);
         return 1;
     }
+    if (bloom_opt && !bloom) { std::fprintf(stderr, "--bloom-threshold, --bloom-strength and --bloom-levels need --bloom\n"); return 1; }
+    if (bloom && (every_frame || devices.size() > 1 || !(bloom_threshold >= 0.0f) || std::isinf(bloom_threshold) || !(bloom_strength >= 0.0f && bloom_strength <= 1.0e4f) ||
+                  bloom_levels < 1 || bloom_levels > 8)) {
+        std::fprintf(stderr, "--bloom: one device, not with --save-every-frame; --bloom-threshold finite and >= 0, --bloom-strength in 0..1e4, --bloom-levels in 1..8\n");
+        return 1;
+    }
     if ((exposure_given || auto_exposure) && tonemap_op < 0) { std::fprintf(stderr, "--exposure and --auto-exposure need --tonemap\n"); return 1; }
     if (tonemap_op >= 0 && (every_frame || devices.size() > 1 || !(exposure > 0.0f) || std::isinf(exposure))) {
         std::fprintf(stderr, "--tonemap: one device, not with --save-every-frame, and --exposure must be a positive finite number\n");
@@ -142,6 +160,7 @@ int main(int argc, char **argv) {
     if (denoise) window->setDenoise(denoise_iters);
     if (denoise_variance) window->setDenoiseVariance(denoise_iters);
     if (tonemap_op >= 0) window->setTonemap(tonemap_op, exposure, auto_exposure);
+    if (bloom) window->setBloom(bloom_threshold, bloom_strength, bloom_levels);
 
     auto scene = std::make_shared<Scene>();
     if (!bvh.empty()) scene->setBvhBuilder(bvh);

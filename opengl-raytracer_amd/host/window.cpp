@@ -104,6 +104,7 @@ void Window::mainloop(const std::shared_ptr<Scene> &scene_, double fps) {
     // Launches are issued back to back and the loop waits for the device only where it needs the pixels (a frame that is saved, the end of the run): the calls are
     // asynchronous, and a launch issued behind idle time runs longer -- 2 % behind 1 ms, 5 % behind 3 ms (profiles/r04_ab_launch_warmth.txt).  lastFrameMs() is the wall
     // time per frame between two such waits.
+    if (bloom_ && (glrtx_group_size(grp_) != 1 || every)) GLRT_FatalError("--bloom: one device, and not with --save-every-frame (groups and the present ring have no bloomed form)");
     if (tonemap_ && (glrtx_group_size(grp_) != 1 || every)) GLRT_FatalError("--tonemap: one device, and not with --save-every-frame (groups and the present ring have no tone-mapped form)");
     if (denoise_ || denoiseVar_) {  // the feature planes of this (static) camera, once, before the first frame
         if (glrtx_group_size(grp_) != 1 || every) GLRT_FatalError("--denoise: one device, and not with --save-every-frame (groups and the present ring have no denoised form)");
@@ -259,14 +260,20 @@ void Window::resetBuffer() { GLRTX_CHECK(glrtx_group_resize(grp_, width_, height
 
 void Window::saveCurrentFrame(const std::string &filename, bool overwrite) const {
     std::vector<unsigned char> bytes((size_t)width_ * height_ * 4);
-    if (tonemap_) {  // --tonemap: the denoised image if one was asked for, else the accumulator, through the exposure and the tone curve (one device: checked in mainloop)
+    if (tonemap_ || bloom_) {  // --tonemap / --bloom: the denoised image if one was asked for, else the accumulator, through the exposure and the tone curve (one device: checked in mainloop)
         glrtx_ctx *c0 = glrtx_group_ctx(grp_, 0);
         glrtx_tonemap_cfg cfg = tonemapCfg_;
         cfg.source = (denoise_ || denoiseVar_) ? 1 : 0;
         if (denoise_ && glrtx_denoise(c0, &denoiseCfg_) != GLRTX_OK) GLRT_FatalError("glrtx_denoise: %s", glrtx_last_error(c0));
         if (denoiseVar_ && glrtx_denoise_variance(c0, &denoiseVarCfg_) != GLRTX_OK) GLRT_FatalError("glrtx_denoise_variance: %s", glrtx_last_error(c0));
         if (cfg.auto_exposure && glrtx_exposure_measure(c0, &cfg) != GLRTX_OK) GLRT_FatalError("glrtx_exposure_measure: %s", glrtx_last_error(c0));
-        if (glrtx_resolve_tonemapped_rgba8(c0, bytes.data(), (size_t)width_ * 4, &cfg) != GLRTX_OK)
+        if (bloom_) {  // the glow on the linear image, then the curve (op 0 at exposure 1 without --tonemap) over B; the exposure was measured on the unbloomed source
+            glrtx_bloom_cfg bc = bloomCfg_;
+            bc.source = cfg.source;
+            if (glrtx_bloom(c0, &bc) != GLRTX_OK) GLRT_FatalError("glrtx_bloom: %s", glrtx_last_error(c0));
+            if (glrtx_resolve_bloomed_rgba8(c0, bytes.data(), (size_t)width_ * 4, &cfg) != GLRTX_OK) GLRT_FatalError("glrtx_resolve_bloomed_rgba8: %s", glrtx_last_error(c0));
+            GLRT_Info("Bloom: threshold %g, strength %g, %d levels", (double)bc.threshold, (double)bc.strength, bc.levels);
+        } else if (glrtx_resolve_tonemapped_rgba8(c0, bytes.data(), (size_t)width_ * 4, &cfg) != GLRTX_OK)
             GLRT_FatalError("glrtx_resolve_tonemapped_rgba8: %s", glrtx_last_error(c0));
         if (cfg.auto_exposure) {
             glrtx_exposure e;

@@ -62,6 +62,9 @@ public:
     // Tone mapping of the saved image (glrtx_exposure_measure / glrtx_resolve_tonemapped_rgba8, one device only): op 0 clamp, 1 Reinhard, 2 ACES; the source is the
     // denoised image when a denoiser is on.  Without it the saved image is the plain resolve's, byte for byte.
     void setTonemap(int op, float exposure, bool autoExposure) { tonemap_ = true; tonemapCfg_.op = op; tonemapCfg_.exposure = exposure; tonemapCfg_.auto_exposure = autoExposure ? 1 : 0; }
+    // Bloom in front of the curve (glrtx_bloom / glrtx_resolve_bloomed_rgba8, one device only): the saved image is B -- the denoised image when a denoiser is on,
+    // else the accumulator, plus the glow -- through the tone curve (clamp at exposure 1 without setTonemap).  Without it the saved image is what it was.
+    void setBloom(float threshold, float strength, int levels) { bloom_ = true; bloomCfg_.threshold = threshold; bloomCfg_.strength = strength; bloomCfg_.levels = levels; }
     void setDenoiseVariance(int iterations) { denoiseVar_ = true; if (iterations >= 1) denoiseVarCfg_.iterations = iterations; }
     // wall-clock ms PER FRAME between the last two waits for the device, averaged over the frames issued in between (with one PNG per run: the whole run, cold first
     // launches included; with --save-every-frame: the whole run, PNG writing included).  The device's own time of the last launch is glrtx_stats.kernel_ms_last.
@@ -98,6 +101,8 @@ private:
     bool volumeWavefront_ = false;
     bool denoise_ = false, denoiseVar_ = false;
     bool tonemap_ = false;
+    bool bloom_ = false;
+    glrtx_bloom_cfg bloomCfg_ = {0, 1.0f, 0.25f, 5};  // (glrt_amd.host.BLOOM_DEFAULTS holds the same)
     glrtx_tonemap_cfg tonemapCfg_ = {0, 0, 0, 1.0f, 0.18f, 500, 950, 1.0f, 4.0f, 2.2f, 1};  // (glrt_amd.host.TONEMAP_DEFAULTS holds the same)
     glrtx_denoise_var_cfg denoiseVarCfg_ = {5, 4.0f, 0.1f, 0.01f, 1};  // (DESIGN.md "Variance guidance": the sweep; glrt_amd.host.DENOISE_VAR_DEFAULTS holds the same)
     glrtx_denoise_cfg denoiseCfg_ = {5, 100.0f, 0.1f, 0.01f, 1};  // (DESIGN.md "Denoising": the sweep behind these; glrt_amd.host.DENOISE_DEFAULTS holds the same)

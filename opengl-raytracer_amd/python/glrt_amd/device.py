@@ -95,6 +95,30 @@ def _tonemap_cfg(cfg, fields) -> TonemapCfg:
     return cfg if cfg is not None else TonemapCfg.default(**fields)
 
 
+class BloomCfg(C.Structure):
+    """glrtx_bloom_cfg (include/glrtx.h "Bloom"); BloomCfg.default(**fields) holds glrt_amd.host.BLOOM_DEFAULTS."""
+    _fields_ = [("source", C.c_int), ("threshold", C.c_float), ("strength", C.c_float), ("levels", C.c_int)]
+
+    @classmethod
+    def default(cls, **fields):
+        from .host import BLOOM_DEFAULTS
+        d = dict(BLOOM_DEFAULTS)
+        unknown = set(fields) - set(d)
+        if unknown:
+            raise TypeError(f"BloomCfg: unknown field(s) {sorted(unknown)}")
+        d.update({k: v for k, v in fields.items() if v is not None})
+        c = cls()
+        for name, ctype in cls._fields_:
+            setattr(c, name, float(d[name]) if ctype is C.c_float else int(d[name]))
+        return c
+
+
+def _bloom_cfg(cfg, fields) -> BloomCfg:
+    if cfg is not None and fields:
+        raise TypeError("give a BloomCfg or its fields, not both")
+    return cfg if cfg is not None else BloomCfg.default(**fields)
+
+
 class Image(C.Structure):
     _fields_ = [("rgba", C.c_void_p), ("pitch_bytes", C.c_size_t), ("width", C.c_int32), ("rows", C.c_int32), ("frame", C.c_uint64)]
 
@@ -136,7 +160,8 @@ EXPORTS = ["glrtx_abi_version", "glrtx_create", "glrtx_destroy", "glrtx_last_err
            "glrtx_track_moments", "glrtx_render_moments", "glrtx_read_moments", "glrtx_denoise_variance", "glrtx_debug_denoise_variance",
            "glrtx_debug_reproject_moments", "glrtx_debug_reproject_motion_moments",
            "glrtx_exposure_measure", "glrtx_exposure_reset", "glrtx_read_exposure", "glrtx_tonemap", "glrtx_read_tonemapped", "glrtx_resolve_tonemapped_rgba8",
-           "glrtx_debug_tonemap", "glrtx_debug_tonemap_burst"]
+           "glrtx_debug_tonemap", "glrtx_debug_tonemap_burst",
+           "glrtx_bloom", "glrtx_read_bloomed", "glrtx_tonemap_bloomed", "glrtx_resolve_bloomed_rgba8", "glrtx_debug_bloom", "glrtx_debug_bloom_burst"]
 
 SCENE_BUFFERS = ("nodes", "cnodes", "nrms", "lights", "vine", "root")  # glrtx_debug_read_scene's `which`, in order (GLRTX_SCENE_*)
 
@@ -288,6 +313,16 @@ def lib():
             L.glrtx_debug_tonemap_burst.argtypes = [vp, tc, C.c_int, C.c_int, C.POINTER(C.c_float)]
         except AttributeError:
             pass
+        try:  # (additive to ABI 10 as well: bloom)
+            tc, bc = C.POINTER(TonemapCfg), C.POINTER(BloomCfg)
+            L.glrtx_bloom.argtypes = [vp, bc]
+            L.glrtx_read_bloomed.argtypes = [vp, vp, C.c_size_t]
+            L.glrtx_tonemap_bloomed.argtypes = [vp, tc]
+            L.glrtx_resolve_bloomed_rgba8.argtypes = [vp, vp, C.c_size_t, tc]
+            L.glrtx_debug_bloom.argtypes = [fp, C.c_int, C.c_int, bc, fp, fp]
+            L.glrtx_debug_bloom_burst.argtypes = [vp, bc, C.c_int, C.POINTER(C.c_float)]
+        except AttributeError:
+            pass
         _lib = L
     return _lib
 
@@ -437,6 +472,22 @@ def debug_tonemap(src, exposure_in=None, cfg=None, **fields):
     if rc != 0:
         raise GlrtxError(rc, L.glrtx_last_error(None).decode())
     return e, t, b
+
+
+def debug_bloom(src, cfg=None, **fields):
+    """glrtx_debug_bloom on the current device: the bloom kernels on a (rows, width, 4) float32 array.  Returns (d, B): d the planes D_1 .. D_levels packed back
+    to back, (n, 4) float32 with w = 0, as they stand before the up chain; B (rows, width, 4) float32."""
+    from .host import bloom_texels
+    L = lib()
+    a = _f32(src)
+    if a.ndim != 3 or a.shape[2] != 4:
+        raise ValueError(f"debug_bloom: a (rows, width, 4) array expected, got {a.shape}")
+    c = _bloom_cfg(cfg, fields)
+    d, b = np.zeros((bloom_texels(a.shape[1], a.shape[0], min(max(c.levels, 1), 8)), 4), np.float32), np.zeros_like(a)
+    rc = L.glrtx_debug_bloom(_fp(a), a.shape[1], a.shape[0], C.byref(c), _fp(d), _fp(b))
+    if rc != 0:
+        raise GlrtxError(rc, L.glrtx_last_error(None).decode())
+    return d, b
 
 
 def debug_reproject(accum, n0, a0, n1, a1, prev, cur, **cfg):
@@ -913,6 +964,30 @@ class Device:
         1 the fused tone-mapping resolve, 2 the plane kernel, 3 a measurement."""
         ms = C.c_float(0)
         self._ck(self.L.glrtx_debug_tonemap_burst(self.h, C.byref(_tonemap_cfg(cfg, fields)), int(which), int(reps), C.byref(ms)))
+        return float(ms.value)
+    def bloom(self, cfg=None, **fields):
+        """The glow of the cfg's source into the context's plane B (glrtx_bloom): 2 * levels launches on the context's stream; no sync.  cfg: a BloomCfg, or its
+        fields as keywords (None: glrt_amd.host.BLOOM_DEFAULTS)."""
+        self._ck(self.L.glrtx_bloom(self.h, C.byref(_bloom_cfg(cfg, fields))))
+    def read_bloomed(self) -> np.ndarray:
+        """The plane B, (owned_rows, width, 4) float32 {x + strength * glow, 1} (syncs)."""
+        s = self.stats()
+        out = np.zeros((s.owned_rows, s.width, 4), np.float32)
+        self._ck(self.L.glrtx_read_bloomed(self.h, out.ctypes.data, s.width * 16))
+        return out
+    def tonemap_bloomed(self, cfg=None, **fields):
+        """The tone curve over B into the context's plane T (glrtx_tonemap_bloomed; the cfg's source is not read); no sync."""
+        self._ck(self.L.glrtx_tonemap_bloomed(self.h, C.byref(_tonemap_cfg(cfg, fields))))
+    def resolve_bloomed_rgba8(self, cfg=None, **fields) -> np.ndarray:
+        """B through the curve and the resolve in one pass (glrtx_resolve_bloomed_rgba8; the cfg's source is not read): (owned_rows, width, 4) uint8."""
+        s = self.stats()
+        out = np.zeros((s.owned_rows, s.width, 4), np.uint8)
+        self._ck(self.L.glrtx_resolve_bloomed_rgba8(self.h, out.ctypes.data, s.width * 4, C.byref(_tonemap_cfg(cfg, fields))))
+        return out
+    def bloom_burst_ms(self, reps=20, cfg=None, **fields) -> float:
+        """Device time of one glrtx_bloom from `reps` of them back to back (glrtx_debug_bloom_burst)."""
+        ms = C.c_float(0)
+        self._ck(self.L.glrtx_debug_bloom_burst(self.h, C.byref(_bloom_cfg(cfg, fields)), int(reps), C.byref(ms)))
         return float(ms.value)
     def timer_begin(self):
         self._ck(self.L.glrtx_timer_begin(self.h))

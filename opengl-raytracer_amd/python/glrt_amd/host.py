@@ -52,6 +52,7 @@ def lib():
         u32p, u64p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
         L.glrt_exposure_measure.argtypes = [fp, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_float, fp, u32p, u64p, u64p, fp, fp, fp]
         L.glrt_tonemap.argtypes = [fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, fp, C.POINTER(C.c_uint8)]
+        L.glrt_bloom.argtypes = [fp, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, fp, fp]
         L.glrt_look_at.argtypes = [fp, fp, fp, fp]
         L.glrt_perspective.argtypes = [C.c_float, C.c_float, C.c_float, C.c_float, fp]
         L.glrt_mat4_mul.argtypes = [fp, fp, fp]
@@ -309,6 +310,34 @@ def tonemap(src, op=TONEMAP_DEFAULTS["op"], auto_exposure=TONEMAP_DEFAULTS["auto
     if rc != 0:
         raise RuntimeError(f"glrt_tonemap failed: {rc}")
     return t, b
+
+
+# glrtx_bloom_cfg's defaults (include/glrtx.h "Bloom": conventional values, not tuned on anything)
+BLOOM_DEFAULTS = dict(source=0, threshold=1.0, strength=0.25, levels=5)
+
+
+def bloom_texels(width, rows, levels):
+    """The number of texels in the packed pyramid D_1 .. D_levels of a width x rows image: w_{k+1} = (w_k + 1) >> 1."""
+    n, w, h = 0, int(width), int(rows)
+    for _ in range(int(levels)):
+        w, h = (w + 1) >> 1, (h + 1) >> 1
+        n += w * h
+    return n
+
+
+def bloom(src, threshold=BLOOM_DEFAULTS["threshold"], strength=BLOOM_DEFAULTS["strength"], levels=BLOOM_DEFAULTS["levels"]):
+    """glrt_bloom: the CPU statement of the bloom pass on a (rows, width, 4) float32 array.  Returns (d, B): d the planes D_1 .. D_levels packed back to back,
+    (n, 4) float32 with w = 0; B (rows, width, 4) float32 {x + strength * glow, 1}."""
+    a = _f32(src)
+    if a.ndim != 3 or a.shape[2] != 4:
+        raise ValueError(f"bloom: a (rows, width, 4) array expected, got {a.shape}")
+    if not 1 <= int(levels) <= 8:
+        raise RuntimeError(f"glrt_bloom failed: levels {levels} outside 1..8")
+    d, b = np.zeros((bloom_texels(a.shape[1], a.shape[0], levels), 4), np.float32), np.zeros_like(a)
+    rc = lib().glrt_bloom(_fp(a), a.shape[1], a.shape[0], float(threshold), float(strength), int(levels), _fp(d), _fp(b))
+    if rc != 0:
+        raise RuntimeError(f"glrt_bloom failed: {rc}")
+    return d, b
 
 
 REPROJECT_DEFAULTS = dict(max_history=32, depth_tolerance=0.02, normal_tolerance=0.9)
