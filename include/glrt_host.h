@@ -158,6 +158,11 @@ int glrt_variance_estimate(const float *accum, const float *moments, const float
                            float sigma_depth, int demodulate, float *out_v0);
 int glrt_denoise_variance(const float *accum, const float *moments, const float *normal_depth, const float *albedo_id, int width, int rows, int iterations,
                           float sigma_lum, float sigma_normal, float sigma_depth, int demodulate, float *out, float *out_v0);
+/* The selection of glrtx_render_adaptive_moments / glrtx_debug_adaptive_select_moments (include/glrtx.h "Adaptive sampling by variance": the formulas are
+ * there), bit for bit (host/variance.cpp; tests/adaptive_moments_math.py states it in numpy).  moments: width x rows x 4 floats, rows packed; mask_out: a byte
+ * (0 / 1) per 8x8 tile, ceil(width / 8) x ceil(rows / 8), row-major; err_out (may be NULL): E per tile, a NaN as 0x7FC00000.  Runs with denormals flushed.
+ * GLRT_HOST_EINVAL: a NULL moments or mask_out, a size outside 1..65536. */
+int glrt_adaptive_select_moments(const float *moments, int width, int rows, float threshold, int min_samples, uint8_t *mask_out, float *err_out);
 
 /* Temporal reprojection: the CPU statement of the device's glrtx_reproject / glrtx_debug_reproject (include/glrtx.h "Reprojection": the formulas are there), bit
  * for bit.  accum / n0 / a0: the old view's accumulator float4(rgb sum, count) and feature planes; n1 / a1: the new view's planes; out: the new accumulator; all

@@ -553,7 +553,8 @@ int glrtx_debug_denoise(const float *accum, const float *normal_depth, const flo
  * glrtx_debug_reproject_moments / glrtx_debug_reproject_motion_moments are glrtx_debug_reproject / _motion with the old view's M in and the new view's M out
  * (width x rows float4, rows packed); glrt_reproject_moments / glrt_reproject_motion_moments (glrt_host.h) and tests/variance_math.py state them again.
  * Out of scope: groups (a partitioned context filters its own rows, as glrtx_denoise does); feeding M from fed
- * launches, the present ring, the megakernels or the volume forms; separate direct and indirect buffers; making the adaptive selection use M. */
+ * launches, the present ring, the megakernels or the volume forms; separate direct and indirect buffers.  (The adaptive selection made from M: "Adaptive
+ * sampling by variance" below.) */
 typedef struct glrtx_denoise_var_cfg {
     int   iterations;    /* 1..6; iteration i uses tap spacing 2^i */
     float sigma_lum;     /* the luminance edge stops at sigma_lum standard deviations of the pixel's mean */
@@ -574,6 +575,49 @@ int glrtx_debug_reproject_moments(const float *accum, const float *moments, cons
 int glrtx_debug_reproject_motion_moments(const float *accum, const float *moments, const float *n0, const float *a0, const float *g1, const float *a1,
                                          const float *vert_prev, size_t n_vert, const float *tri, size_t n_tri, const float *c2w_prev, const float *s2c_prev,
                                          int width, int rows, const struct glrtx_reproject_cfg *cfg, float *out, float *moments_out, int *carried, int *hit_pixels);
+
+/* ---- Adaptive sampling by variance: glrtx_render_adaptive with the selection made from the moments plane M (no reference counterpart; off unless called: no
+ * other call changes what it does or writes).  glrtx_render_adaptive estimates a tile's error from the half buffer H, and both reprojections zero H ("H.w = 0 makes
+ * every tile active again"): after every camera or geometry move it renders the whole frame again.  M is carried by both reprojections ("Carrying M"), and it is
+ * the direct estimate of what the two-buffer trick approximates: the variance of each pixel's mean.  With the selection made from M a call after a move spends its
+ * frames on the disoccluded tiles -- no moments, therefore active -- and on the tiles that are still noisy, and the samples it adds feed the variance that
+ * glrtx_denoise_variance reads afterwards.
+ *   glrtx_render_adaptive_moments  is glrtx_render_adaptive step for step -- the selection at the start of the call, on the device; then n_frames frames of the
+ *                          active tiles only, by the same kernel over the same tile list, plain launches with sample planes on the context's stream in helpings of
+ *                          what the frames-in-flight budget allows, never fed, an open fed launch sealed first; issued without a sync -- with three differences.
+ *                          (1) The selection reads M only, as M stands when the call begins (M gets its zeroed first-use allocation if needed, as in
+ *                          glrtx_render_moments).  It neither reads nor allocates H.  It writes the context's one mask, list and count: glrtx_adaptive_active_tiles
+ *                          and glrtx_read_tile_mask report this selection as they report glrtx_render_adaptive's, whichever came last.
+ *                          (2) The accumulation pass adds each sample of an active tile's pixel to the accumulator and folds it into M exactly as
+ *                          glrtx_render_moments does: M.x += l; M.y += l * l; M.w += 1, then acc.rgb += v.rgb; acc.w += 1, in frame and sample order.  Inactive
+ *                          tiles are not touched in either buffer.
+ *                          (3) H is not touched at all: not created, not read, not written.
+ *                          The rules are those of "Variance guidance" (one correctly rounded fp32 operation at a time in the order written, unfused, denormals
+ *                          flushed in and out, the correctly rounded sqrt, selects as written).  Per in-image pixel of an 8x8 tile:
+ *                              force = !(M.w >= (float)min_samples)                    (a zero, a denormal, a negative or a NaN count forces)
+ *                              mu1 = M.x / M.w;   mu2 = M.y / M.w
+ *                              v = mu2 - mu1 * mu1;   v = v > 0 ? v : 0;   v = v / M.w   (glrtx_denoise_variance's temporal branch, without demodulation)
+ *                              d = sqrt(v) / sqrt(mu1 + 1e-3)
+ *                          d is 0 outside the image.  E is the tile's mean of d: lane k of the tile's wave holds pixel (k & 7, k >> 3), the 64 values are summed
+ *                          as a tree -- s[k] = s[k] + s[k ^ h] for h = 32, 16, 8, 4, 2, 1 -- and s[0] is divided by the number of in-image pixels.  A tile is active
+ *                          if one of its in-image pixels forces, if threshold < 0 (nothing retires: the accumulator and M come out bit for bit
+ *                          glrtx_render_moments's), or if !(E <= threshold) (a NaN E keeps the tile active).
+ *                          THRESHOLDS OF THE TWO FORMS ARE NOT INTERCHANGEABLE.  Here d is a standard error of the mean luminance over the root of that luminance;
+ *                          in glrtx_render_adaptive it is a sum of three channel differences between two half-images over sqrt(r + g + b).  The same number means
+ *                          different image quality in the two calls.
+ *                          n_frames = 0 selects only.  min_samples >= 2 as there: one sample has no variance.  GLRTX_EINVAL, nothing changed: everything
+ *                          glrtx_render_adaptive refuses and everything glrtx_render_moments refuses -- NULL params or cfg, min_samples < 2, bad seeds / n_frames,
+ *                          tracking off, no scene, no accumulator, presentation enabled, extensions or volume on (the V form too: M is not fed by the volume
+ *                          forms), spheres uploaded, variant != 2, max_depth / n_samples beyond the wavefront kernel's path state.  A partitioned context selects
+ *                          and renders on its owned rows, as in glrtx_render_moments; there is no group call (groups are out of scope for M).
+ *   glrtx_debug_adaptive_select_moments  the selection kernels on a caller array (width x rows float4, rows packed) on the current HIP device, no context: the mask, E
+ *                          per tile (NULL: not wanted; a NaN is returned as 0x7FC00000), the ascending list of active tiles and its length (NULL: not wanted).
+ * glrt_adaptive_select_moments (glrt_host.h) and tests/adaptive_moments_math.py state the selection again; the three agree bit for bit.
+ * Out of scope: group calls and the present ring; a per-tile sample budget beyond the on/off decision; selecting by glrtx_denoise_variance's filtered variance; the
+ * volume forms; feeding M from fed launches. */
+int glrtx_render_adaptive_moments(glrtx_ctx *ctx, const glrtx_params *params, const float *seeds_xy, int n_frames, const glrtx_adaptive *cfg);
+int glrtx_debug_adaptive_select_moments(const float *moments, int width, int rows, float threshold, int min_samples, uint8_t *mask_out, float *err_out, int *list_out,
+                                        int *count_out);
 
 /* ---- Reprojection: carry the accumulator across a camera move (the reprojection step of SVGF, Schied et al. 2017; no reference counterpart -- the reference
  * clears and starts again at one sample, window.cpp:366-381; off unless called).  The context remembers the c2w and s2c of its last glrtx_render_features: the

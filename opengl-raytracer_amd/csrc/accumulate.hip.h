@@ -2,7 +2,7 @@
 //
 // Per pixel the pass is one chain of float additions -- acc.xyz += v.xyz; acc.w += 1 -- over the launch's planes, frame by frame, sample by sample: the chain that
 // consecutive single-frame launches perform inside the render kernel.  Every bit-exactness guarantee of the library rests on that chain, so it is written in one
-// template (pass) and the six kernels are entry points over it.  They differ in two things only:
+// template (pass) and the seven kernels are entry points over it.  They differ in two things only:
 //   the SOURCE  Planes -- one flat array [frame][sample][rows][pitch_f4] (plain and overlapped launches);
 //               Fed -- a fed launch's chunks of kFeedChunkFrames frames behind FeedDev, however many frames the launch ended up taking (FeedDev::frames_known, final
 //               once the render kernel has ended);
@@ -10,10 +10,11 @@
 //               Half (glrtx_render_adaptive) -- ACTIVE tiles only: an inactive tile's planes were not written, its accumulator and H entries are not touched; a sample
 //               also goes into the half buffer H when the pixel's count BEFORE the add is odd: H holds every second sample (tests/adaptive_math.py);
 //               Moments (glrtx_render_moments) -- the sample's luminance and its square go into the moments plane M {sum l, sum l^2, 0, count} (tests/variance_math.py);
+//               MomentsMasked (glrtx_render_adaptive_moments) -- Moments on ACTIVE tiles only: an inactive tile's accumulator and M entries are not touched;
 //               Present (glrtx_present_enable) -- behind every frame f the pixel's screen.frag value (rs_pixel, byte-identical to resolve_kernel's) goes into image
 //               (slot0 + f) % n_ring of the device ring, packed rows of `width` texels, row y at rows - 1 - y when flipped (within the owned rows, like
 //               glrtx_resolve_rgba8): one launch and one read of the accumulator instead of a pass plus a resolve per frame.
-// Bandwidth-bound: 16 B per plane and pixel in, one 16-B read-modify-write of the accumulator (Half, Moments: two), 4 B per frame and pixel out (Present).
+// Bandwidth-bound: 16 B per plane and pixel in, one 16-B read-modify-write of the accumulator (Half, Moments, MomentsMasked: two), 4 B per frame and pixel out (Present).
 #pragma once
 #include <type_traits>
 
@@ -41,6 +42,7 @@ struct Fed {
 struct None {};
 struct Half { float4 *half; const unsigned char *mask; int tiles8_x; };  // H and the selection's mask byte per 8x8 tile
 struct Moments { float4 *moments; };                                     // M, of the accumulator's pitch
+struct MomentsMasked { float4 *moments; const unsigned char *mask; int tiles8_x; };  // M and the selection's mask byte per 8x8 tile
 struct Present { uchar4 *ring; size_t slot_px; int n_ring, slot0; float inv_gamma; int flip; };
 
 // One lane per pixel, a wave is 64 consecutive pixels of a row, four rows per workgroup: a grid of (width + 63) / 64 x (rows + 3) / 4.
@@ -50,13 +52,14 @@ struct Present { uchar4 *ring; size_t slot_px; int n_ring, slot0; float inv_gamm
 // A flat source's frames are contiguous, so a sink without a per-frame step takes them as one run of n_frames * n_samples planes: one loop for the compiler to unroll.
 template <class Src, class Sink>
 DEV void pass(const Image im, const Src src, const Sink sink) {
-    constexpr bool kHalf = std::is_same_v<Sink, Half>, kMoments = std::is_same_v<Sink, Moments>, kPresent = std::is_same_v<Sink, Present>;
+    constexpr bool kHalf = std::is_same_v<Sink, Half>, kMasked = std::is_same_v<Sink, MomentsMasked>, kMoments = std::is_same_v<Sink, Moments> || kMasked,
+                   kPresent = std::is_same_v<Sink, Present>;
     const int x = blockIdx.x * 64 + (threadIdx.x & 63);
     const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (y >= im.rows) return;  // (a whole wave)
     if (!kPresent && x >= im.width) return;
     const bool in = kPresent ? x < im.width : true;
-    if constexpr (kHalf)
+    if constexpr (kHalf || kMasked)
         if (sink.mask[(y >> 3) * sink.tiles8_x + (x >> 3)] == 0) return;
     const size_t at = (size_t)y * im.pitch_f4 + x, plane = (size_t)im.rows * im.pitch_f4;
     int runs = src.frames(), len = src.n_samples;
@@ -103,12 +106,14 @@ __global__ __launch_bounds__(256) void accumulate_adaptive_kernel(const accumula
 __global__ __launch_bounds__(256) void accumulate_present_planes_kernel(const accumulate::Image im, const accumulate::Planes src, const accumulate::Present sink) { accumulate::pass(im, src, sink); }
 __global__ __launch_bounds__(256) void accumulate_present_feed_kernel(const accumulate::Image im, const accumulate::Fed src, const accumulate::Present sink) { accumulate::pass(im, src, sink); }
 namespace variance { __global__ __launch_bounds__(256) void accumulate_moments_kernel(const accumulate::Image im, const accumulate::Planes src, const accumulate::Moments sink) { accumulate::pass(im, src, sink); } }
+namespace adaptive_moments { __global__ __launch_bounds__(256) void accumulate_kernel(const accumulate::Image im, const accumulate::Planes src, const accumulate::MomentsMasked sink) { accumulate::pass(im, src, sink); } }
 
 namespace accumulate {
 inline auto entry(Planes, None) { return accumulate_planes_kernel; }
 inline auto entry(Fed, None) { return accumulate_feed_kernel; }
 inline auto entry(Planes, Half) { return accumulate_adaptive_kernel; }
 inline auto entry(Planes, Moments) { return variance::accumulate_moments_kernel; }
+inline auto entry(Planes, MomentsMasked) { return adaptive_moments::accumulate_kernel; }
 inline auto entry(Planes, Present) { return accumulate_present_planes_kernel; }
 inline auto entry(Fed, Present) { return accumulate_present_feed_kernel; }
 }  // namespace accumulate

@@ -1085,7 +1085,10 @@ struct RenderReq {
     // Moments (glrtx_render_moments): the same shape -- plain, with sample planes, never fed -- on the ordinary kernel; the pass folds the planes into M as well.
     // Calibration (glrtx_hit_histogram): one plain single-frame launch on the context's stream that counts closest hits per leaf record into `hit_hist` while it shades
     //     into `scratch` instead of the accumulator: no pipe slot, no ray counting, no presentation step.
-    enum Kind { Ordinary, Adaptive, Moments, Calibration } kind = Ordinary;
+    // AdaptiveMoments (glrtx_render_adaptive_moments): Adaptive's launch on the selection made from M; the pass folds the active tiles' planes into M, not into H.
+    enum Kind { Ordinary, Adaptive, Moments, Calibration, AdaptiveMoments } kind = Ordinary;
+    bool adaptive() const { return kind == Adaptive || kind == AdaptiveMoments; }
+    bool folds_moments() const { return kind == Moments || kind == AdaptiveMoments; }
     const float *seeds = nullptr;  // {x, y} per frame; a single frame's seed is the parameters' own
     int n_frames = 1;
     unsigned *hit_hist = nullptr; float4 *scratch = nullptr;  // Calibration
@@ -1183,7 +1186,7 @@ WgwfLaunch::Form wgwf_form(glrtx_ctx *c, const WgwfLaunch &L) {
 // The compact node array (pack_compact) has its own four: wgwf_compact.
 // The V form (kWgwfVolume: glrtx_set_volume_wavefront; routed here only with the volume alone, wgwf_routes) has one fetch form only: one record per lane on
 // DevScene::nodes, as in the megakernels (no list scan, no pair fetch, no compact layout).
-// Each of the six has its ADAPT twin (kWgwfAdaptive: glrtx_render_adaptive): 24 instantiations, one table.
+// Each of the six has its ADAPT twin (kWgwfAdaptive: glrtx_render_adaptive, glrtx_render_adaptive_moments): 24 instantiations, one table.
 enum WgwfTrav { kTravVine, kTravFetch0, kTravFetch1, kTravFetch2, kTravCompact, kTravVolume, kTravForms };
 #define GLRTX_WGWF_ROW(VINE, FLAGS) {{pt_render_wgwf<false, VINE, FLAGS>, pt_render_wgwf<true, VINE, FLAGS>}, \
                                      {pt_render_wgwf<false, VINE, (FLAGS) | kWgwfAdaptive>, pt_render_wgwf<true, VINE, (FLAGS) | kWgwfAdaptive>}}
@@ -1196,7 +1199,7 @@ constexpr const char *kWgwfNames[3][2] = {  // [list scan | tree | volume][adapt
 int wgwf_kernel(glrtx_ctx *c, WgwfLaunch &L) {
     WgwfLaunch::Kernel &k = L.k;
     k.vol = c->ext_flags != 0;
-    k.adapt = L.req.kind == RenderReq::Adaptive;
+    k.adapt = L.req.adaptive();
     k.vine = c->sc.n_vine > 0 && !k.vol;
     k.fetch = k.vol ? 0 : wgwf_fetch(c, k.vine);
     c->st.node_fetch_last = k.fetch;
@@ -1410,7 +1413,7 @@ int wgwf_check(glrtx_ctx *c, const WgwfLaunch &L) {
     const glrtx_params *p = L.p;
     const glrtx_ctx::PipeSlot *const slot = L.slot;
     const WfArgs &w = L.w;
-    const bool fed = L.f.fed, moments = L.req.kind == RenderReq::Moments;
+    const bool fed = L.f.fed, moments = L.req.folds_moments();
     const int n_frames = L.n_frames, grid = L.grid, block_paths = L.block_paths, fed_cap = L.f.fed_cap;
     const size_t state_entries = L.state_entries, total = L.total, max_id = L.ids - 1;
     const size_t max_sidx = (size_t)kWfSetPlanes * state_entries + (size_t)grid * block_paths - 1;  // the highest state index a ray record can carry (set 1)
@@ -1426,7 +1429,8 @@ int wgwf_check(glrtx_ctx *c, const WgwfLaunch &L) {
     if (!fed && n_frames > 1) ok = ok && c->wfSeeds.bytes >= (size_t)n_frames * sizeof(float2);
     if (w.planes) ok = ok && L.planeBuf->bytes >= (size_t)std::max(L.n_planes, 1) * L.plane_f4 * sizeof(float4);
     if (L.k.adapt) ok = ok && !fed && !slot && w.planes && c->ad_selected && c->ad_tiles == (int)(total >> 6) && c->adList.bytes >= (total >> 6) * sizeof(int) &&
-                        c->adMask.bytes >= (total >> 6) && c->adHalf.bytes >= (size_t)c->ad_pitch * c->owned_rows && c->ad_pitch == c->pitch_bytes;
+                        c->adMask.bytes >= (total >> 6);
+    if (L.req.kind == RenderReq::Adaptive) ok = ok && c->adHalf.bytes >= (size_t)c->ad_pitch * c->owned_rows && c->ad_pitch == c->pitch_bytes;
     if (moments) ok = ok && !fed && !slot && w.planes && c->mmM.p && c->mm_pitch == c->pitch_bytes && c->mm_rows == c->owned_rows &&
                       c->mmM.bytes >= c->pitch_bytes * (size_t)c->owned_rows;
     if (fed) ok = ok && n_frames >= 1 && n_frames <= fed_cap && fed_cap <= kFeedMaxFrames && slot->feed_d.bytes >= sizeof(FeedDev) && w.feed_host != nullptr &&
@@ -1492,7 +1496,9 @@ int wgwf_issue(glrtx_ctx *c, const WgwfLaunch &L) {
         const accumulate::Fed feed{fed ? (const FeedDev *)slot->feed_d.p : nullptr, p->n_samples};
         const glrtx_ctx::Present &P = c->pres;
         const accumulate::Present ring{(uchar4 *)P.dev.p, (size_t)c->width * (size_t)c->owned_rows, P.ring, pres ? (int)(P.seq % (uint64_t)P.ring) : 0, P.inv_gamma, P.flip};
-        if (adapt) accumulate_launch(c, im, flat, accumulate::Half{(float4 *)c->adHalf.p, (const unsigned char *)c->adMask.p, L.tiles8_x});
+        if (L.req.kind == RenderReq::AdaptiveMoments) {
+            if (n_planes > 0) accumulate_launch(c, im, flat, accumulate::MomentsMasked{(float4 *)c->mmM.p, (const unsigned char *)c->adMask.p, L.tiles8_x});
+        } else if (adapt) accumulate_launch(c, im, flat, accumulate::Half{(float4 *)c->adHalf.p, (const unsigned char *)c->adMask.p, L.tiles8_x});
         else if (L.req.kind == RenderReq::Moments) { if (n_planes > 0) accumulate_launch(c, im, flat, accumulate::Moments{(float4 *)c->mmM.p}); }
         else if (fed && pres) accumulate_launch(c, im, feed, ring);
         else if (fed) accumulate_launch(c, im, feed, accumulate::None{});
@@ -1720,10 +1726,11 @@ int adapt_check(glrtx_ctx *c, const glrtx_params *p, const float *seeds_xy, int 
     return GLRTX_OK;
 }
 
-// The selection, on the context's stream behind everything issued before: mask, ascending list and count of the active tiles.
-int adapt_select(glrtx_ctx *c, const glrtx_adaptive *cfg) {
+// The selection, on the context's stream behind everything issued before: mask, ascending list and count of the active tiles.  from_moments
+// (glrtx_render_adaptive_moments): from M, which the caller has made sure of, by adaptive_moments::select_kernel; H is neither read nor allocated.
+int adapt_select(glrtx_ctx *c, const glrtx_adaptive *cfg, bool from_moments) {
     const int tiles8_x = (c->width + 7) / 8, tiles8_y = (c->owned_rows + 7) / 8, n_tiles = tiles8_x * tiles8_y;
-    if (c->owned_rows > 0 && (!c->adHalf.p || c->ad_pitch != c->pitch_bytes || c->ad_rows != c->owned_rows))
+    if (!from_moments && c->owned_rows > 0 && (!c->adHalf.p || c->ad_pitch != c->pitch_bytes || c->ad_rows != c->owned_rows))
         if (int rc = adapt_half_ensure(c)) return rc;
     int rc;
     if ((rc = ensure(c, c->adMask, (size_t)n_tiles)) || (rc = ensure(c, c->adList, (size_t)n_tiles * sizeof(int))) || (rc = ensure(c, c->adCount, sizeof(unsigned))))
@@ -1732,8 +1739,12 @@ int adapt_select(glrtx_ctx *c, const glrtx_adaptive *cfg) {
     c->ad_selected = true;
     if (n_tiles == 0) { HIP_TRY(c, hipMemsetAsync(c->adCount.p, 0, sizeof(unsigned), c->stream)); return GLRTX_OK; }
     const int pitch_f4 = (int)(c->pitch_bytes / sizeof(float4));
-    hipLaunchKernelGGL(adaptive_select_kernel, dim3((n_tiles + 3) / 4), dim3(256), 0, c->stream, (const float4 *)c->accum, (const float4 *)c->adHalf.p, pitch_f4, c->width,
-                       c->owned_rows, tiles8_x, n_tiles, cfg->threshold, cfg->min_samples, (unsigned char *)c->adMask.p, (float *)nullptr);
+    if (from_moments)
+        hipLaunchKernelGGL(adaptive_moments::select_kernel, dim3((n_tiles + 3) / 4), dim3(256), 0, c->stream, (const float4 *)c->mmM.p, pitch_f4, c->width,
+                           c->owned_rows, tiles8_x, n_tiles, cfg->threshold, cfg->min_samples, (unsigned char *)c->adMask.p, (float *)nullptr);
+    else
+        hipLaunchKernelGGL(adaptive_select_kernel, dim3((n_tiles + 3) / 4), dim3(256), 0, c->stream, (const float4 *)c->accum, (const float4 *)c->adHalf.p, pitch_f4, c->width,
+                           c->owned_rows, tiles8_x, n_tiles, cfg->threshold, cfg->min_samples, (unsigned char *)c->adMask.p, (float *)nullptr);
     HIP_TRY(c, hipGetLastError());
     hipLaunchKernelGGL(adaptive_compact_kernel, dim3(1), dim3(kAdaptCompactThreads), 0, c->stream, (const unsigned char *)c->adMask.p, n_tiles, (int *)c->adList.p,
                        (unsigned *)c->adCount.p);
@@ -1753,8 +1764,7 @@ int moments_ensure(glrtx_ctx *c) {
 bool moments_have(const glrtx_ctx *c) { return c->mm_on && c->mmM.p && c->mm_pitch == c->pitch_bytes && c->mm_rows == c->owned_rows; }
 
 // Everything glrtx_render_moments refuses, checked before anything changes: glrtx_render_adaptive's list, the volume and tracking being off.
-int moments_check(glrtx_ctx *c, const glrtx_params *p, const float *seeds_xy, int n_frames) {
-    const char *fn = "glrtx_render_moments";
+int moments_check(glrtx_ctx *c, const glrtx_params *p, const float *seeds_xy, int n_frames, const char *fn = "glrtx_render_moments") {
     if (!p) return fail(c, GLRTX_EINVAL, "%s: NULL params", fn);
     if (!c->mm_on) return fail(c, GLRTX_EINVAL, "%s: moments are not tracked (glrtx_track_moments)", fn);
     if (n_frames < 0 || (n_frames > 0 && !seeds_xy)) return fail(c, GLRTX_EINVAL, "%s: bad seeds/n_frames", fn);
@@ -1767,6 +1777,15 @@ int moments_check(glrtx_ctx *c, const glrtx_params *p, const float *seeds_xy, in
     if (c->variant != 2) return fail(c, GLRTX_EINVAL, "%s: variant %d (only the wavefront kernel, variant 2, writes sample planes)", fn, c->variant);
     if (!wgwf_can_hold(p, false)) return fail(c, GLRTX_EINVAL, "%s: max_depth %d / n_samples %d beyond the wavefront kernel's path state", fn, p->max_depth, p->n_samples);
     return GLRTX_OK;
+}
+
+// Everything glrtx_render_adaptive_moments refuses, checked before anything changes: glrtx_render_adaptive's list and glrtx_render_moments's (which holds all of the
+// former's but the configuration, and the volume forms besides).
+int adapt_moments_check(glrtx_ctx *c, const glrtx_params *p, const float *seeds_xy, int n_frames, const glrtx_adaptive *cfg) {
+    const char *fn = "glrtx_render_adaptive_moments";
+    if (!p || !cfg) return fail(c, GLRTX_EINVAL, "%s: NULL params or cfg", fn);
+    if (cfg->min_samples < 2) return fail(c, GLRTX_EINVAL, "%s: min_samples %d < 2 (one sample has no variance)", fn, cfg->min_samples);
+    return moments_check(c, p, seeds_xy, n_frames, fn);
 }
 
 // ---- tone mapping (glrtx_exposure_measure, glrtx_tonemap, glrtx_resolve_tonemapped_rgba8)
@@ -2727,7 +2746,7 @@ int glrtx_render_adaptive(glrtx_ctx *c, const glrtx_params *p, const float *seed
     if (int rc = adapt_check(c, p, seeds_xy, n_frames, cfg)) return rc;
     seal_feed(c);
     HIP_TRY(c, hipSetDevice(c->device));
-    if (int rc = adapt_select(c, cfg)) return rc;
+    if (int rc = adapt_select(c, cfg, false)) return rc;
     if (n_frames == 0 || c->owned_rows == 0) { c->st.launches += (uint64_t)n_frames; return GLRTX_OK; }
     const int rc = render_helpings(c, p, seeds_xy, n_frames, std::min(n_frames, frames_cap(c, p, 1)), RenderReq::Adaptive);
     seal_feed(c);  // (the next render call starts a launch of its own)
@@ -2986,6 +3005,52 @@ int glrtx_render_moments(glrtx_ctx *c, const glrtx_params *p, const float *seeds
     if (n_frames == 0 || c->owned_rows == 0) { c->st.launches += (uint64_t)n_frames; return GLRTX_OK; }
     const int rc = render_helpings(c, p, seeds_xy, n_frames, std::min(n_frames, frames_cap(c, p, 1)), RenderReq::Moments);
     seal_feed(c);  // (the next render call starts a launch of its own)
+    return rc;
+}
+
+// glrtx_render_adaptive with the selection made from M and the active tiles' samples folded into M: H is neither read, allocated nor written.
+int glrtx_render_adaptive_moments(glrtx_ctx *c, const glrtx_params *p, const float *seeds_xy, int n_frames, const glrtx_adaptive *cfg) {
+    if (!c) return GLRTX_EINVAL;
+    if (int rc = adapt_moments_check(c, p, seeds_xy, n_frames, cfg)) return rc;
+    seal_feed(c);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (!moments_have(c))
+        if (int rc = moments_ensure(c)) return rc;
+    if (int rc = adapt_select(c, cfg, true)) return rc;
+    if (n_frames == 0 || c->owned_rows == 0) { c->st.launches += (uint64_t)n_frames; return GLRTX_OK; }
+    const int rc = render_helpings(c, p, seeds_xy, n_frames, std::min(n_frames, frames_cap(c, p, 1)), RenderReq::AdaptiveMoments);
+    seal_feed(c);  // (the next render call starts a launch of its own)
+    return rc;
+}
+
+int glrtx_debug_adaptive_select_moments(const float *moments, int width, int rows, float threshold, int min_samples, uint8_t *mask_out, float *err_out, int *list_out,
+                                        int *count_out) {
+    const char *fn = "glrtx_debug_adaptive_select_moments";
+    if (width < 1 || rows < 1 || width > 65536 || rows > 65536) return fail(nullptr, GLRTX_EINVAL, "%s: bad size %dx%d", fn, width, rows);
+    if (!moments || !mask_out) return fail(nullptr, GLRTX_EINVAL, "%s: NULL buffer", fn);
+    const int tiles8_x = (width + 7) / 8, n_tiles = tiles8_x * ((rows + 7) / 8);
+    const size_t px_bytes = (size_t)width * rows * sizeof(float4);
+    void *d_m = nullptr, *d_mask = nullptr, *d_err = nullptr, *d_list = nullptr, *d_count = nullptr;
+    hipError_t e = hipMalloc(&d_m, px_bytes);
+    if (e == hipSuccess) e = hipMalloc(&d_mask, (size_t)n_tiles);
+    if (e == hipSuccess) e = hipMalloc(&d_err, (size_t)n_tiles * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc(&d_list, (size_t)n_tiles * sizeof(int));
+    if (e == hipSuccess) e = hipMalloc(&d_count, sizeof(unsigned));
+    if (e == hipSuccess) e = hipMemcpy(d_m, moments, px_bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(adaptive_moments::select_kernel, dim3((n_tiles + 3) / 4), dim3(256), 0, 0, (const float4 *)d_m, width, width, rows, tiles8_x, n_tiles,
+                           threshold, min_samples, (unsigned char *)d_mask, (float *)d_err);
+        hipLaunchKernelGGL(adaptive_compact_kernel, dim3(1), dim3(kAdaptCompactThreads), 0, 0, (const unsigned char *)d_mask, n_tiles, (int *)d_list, (unsigned *)d_count);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(mask_out, d_mask, (size_t)n_tiles, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && err_out) e = hipMemcpy(err_out, d_err, (size_t)n_tiles * sizeof(float), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && list_out) e = hipMemcpy(list_out, d_list, (size_t)n_tiles * sizeof(int), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && count_out) e = hipMemcpy(count_out, d_count, sizeof(int), hipMemcpyDeviceToHost);
+    const int rc = e != hipSuccess ? fail(nullptr, GLRTX_EDEVICE, "%s: %s", fn, hipGetErrorString(e)) : GLRTX_OK;
+    for (void *q : {d_m, d_mask, d_err, d_list, d_count})
+        if (q) (void)hipFree(q);
     return rc;
 }
 

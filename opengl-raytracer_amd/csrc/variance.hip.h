@@ -10,6 +10,8 @@
 //   variance_estimate  the filter's shape: a workgroup owns a 16x16 tile, a wave an 8x8 sub-tile in tile order; tile + a 3-pixel halo (22^2 pixels) is staged in
 //       LDS as two float4 per pixel -- {mu1, mu2, id, M.w} and the feature plane's {n, t}, 15.1 KiB -- from four 16-byte loads per pixel (accumulator, M, A, N).
 //       A dead or outside pixel is staged with the reserved id, so one compare per tap applies all three exclusions.  A pixel with M.w >= 4 needs no tap at all.
+//   adaptive_moments::select_kernel  the selection of glrtx_render_adaptive_moments (include/glrtx.h "Adaptive sampling by variance"): adaptive_select_kernel's layout
+//       -- one wave per 8x8 tile, four tiles per workgroup, the same tree sum -- over M alone: one streaming 16-byte load per pixel where the H form takes two.
 #pragma once
 #include "denoise.hip.h"
 
@@ -103,4 +105,42 @@ __global__ __launch_bounds__(256) void variance_estimate(const Args a) {
 }
 
 }  // namespace variance
+
+// (A namespace of its own: the kernels of the variance pass proper are counted by name.)
+namespace adaptive_moments {
+
+using variance::max0;
+
+// The selection at the start of glrtx_render_adaptive_moments: which 8x8 tiles of the owned rows are still ACTIVE, from the moments plane as it stands.  Per pixel
+// the temporal branch of the variance pass above, without demodulation, as a standard error of the mean luminance over the root of that mean:
+//     force = !(M.w >= min_samples);   mu1 = M.x / M.w;   mu2 = M.y / M.w;   v = max(mu2 - mu1 * mu1, 0) / M.w;   d = sqrt(v) / sqrt(mu1 + kAdaptLumFloor)
+// Lane k of the tile's wave holds pixel (k & 7, k >> 3) (0 outside the image); E is adaptive_select_kernel's tree sum over the in-image count.  A tile is active if a
+// pixel forces, if threshold < 0 or if !(E <= threshold).  Writes the tile's mask byte and -- debug export only -- its E (a NaN as the canonical quiet NaN).
+// host/variance.cpp (glrt_adaptive_select_moments) and tests/adaptive_moments_math.py state the same bit for bit.
+__global__ __launch_bounds__(256) void select_kernel(const float4 *moments, int pitch_f4, int width, int rows, int tiles8_x, int n_tiles, float threshold, int min_samples,
+                                                     unsigned char *mask, float *tile_err) {
+    const int tile = blockIdx.x * 4 + (threadIdx.x >> 6), k = threadIdx.x & 63;
+    if (tile >= n_tiles) return;  // (wave-uniform)
+    const int x = (tile % tiles8_x) * 8 + (k & 7), y = (tile / tiles8_x) * 8 + (k >> 3);
+    const bool in = x < width && y < rows;
+    float d = 0.0f;
+    bool force = false;
+    if (in) {
+        const float4 m = ld_stream(&moments[(size_t)y * pitch_f4 + x]);
+        force = !(m.w >= (float)min_samples);
+        const float mu1 = m.x / m.w, mu2 = m.y / m.w;
+        const float v = max0(mu2 - mu1 * mu1) / m.w;
+        d = __builtin_sqrtf(v) / __builtin_sqrtf(mu1 + kAdaptLumFloor);
+    }
+#pragma unroll
+    for (int h = 32; h >= 1; h >>= 1) d = d + __shfl_xor(d, h, 64);  // (lane k adds lane k ^ h: lane 0 ends with the tree sum; addition commutes)
+    const unsigned long long in_mask = __ballot(in), force_mask = __ballot(force);
+    if (k == 0) {
+        const float e = d / (float)__popcll(in_mask);
+        mask[tile] = (force_mask != 0ull || threshold < 0.0f || !(e <= threshold)) ? 1 : 0;
+        if (tile_err) tile_err[tile] = e != e ? __uint_as_float(0x7FC00000u) : e;
+    }
+}
+
+}  // namespace adaptive_moments
 }  // namespace glrtx

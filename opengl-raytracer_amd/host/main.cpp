@@ -15,7 +15,7 @@
 using namespace glrt;
 
 static void usage(const char *exe) {
-    std::printf("usage: %s -i scene.json [-s N] [--max-depth D] [--spp N] [--frames F] [--frames-in-flight B] [--bvh sah|sah-reinsert|sah-gpu|lbvh|sah-levels-cpu|lbvh-cpu|reference] [--order-by-hits] [--out file.png] [--save-every-frame] [--device G | --gpus N | --devices a,b,..] [--extensions] [--whitted] [--enable-volume] [--volume-wavefront] [--adaptive THRESHOLD [--min-spp N]] [--denoise | --denoise-variance [--denoise-iters N]] [--tonemap clamp|reinhard|aces [--exposure X] [--auto-exposure]] [--bloom [--bloom-threshold T] [--bloom-strength S] [--bloom-levels N]]\n"
+    std::printf("usage: %s -i scene.json [-s N] [--max-depth D] [--spp N] [--frames F] [--frames-in-flight B] [--bvh sah|sah-reinsert|sah-gpu|lbvh|sah-levels-cpu|lbvh-cpu|reference] [--order-by-hits] [--out file.png] [--save-every-frame] [--device G | --gpus N | --devices a,b,..] [--extensions] [--whitted] [--enable-volume] [--volume-wavefront] [--adaptive THRESHOLD | --adaptive-variance THRESHOLD [--min-spp N]] [--denoise | --denoise-variance [--denoise-iters N]] [--tonemap clamp|reinhard|aces [--exposure X] [--auto-exposure]] [--bloom [--bloom-threshold T] [--bloom-strength S] [--bloom-levels N]]\n"
                 "  -i, --input             scene description (JSON; schema: SURVEY.md Appendix C)            [required]\n"
                 "  -s, --sample-per-cycle  accepted for compatibility; like the reference (main.cpp:13) it is not read\n"
                 "      --max-depth D       u_maxDepth (default 16, the reference shader's default)\n"
@@ -38,7 +38,10 @@ static void usage(const char *exe) {
                 "                          the persistent megakernel, the default).  --enable-volume --adaptive T turns it on by itself\n"
                 "      --adaptive T        adaptive sampling: bursts of --frames-in-flight frames on the 8x8 tiles whose error is above T only, until no tile is\n"
                 "                          active or --frames frames have been issued; an \"Adaptive:\" line per burst (not with --save-every-frame)\n"
-                "      --min-spp N         with --adaptive: samples every pixel of a tile needs before the tile may retire (default 2, at least 2)\n"
+                "      --adaptive-variance T  the same bursts with the tiles selected by the variance of their pixels' mean luminance (the moments plane that\n"
+                "                          --denoise-variance filters by): a tile retires once its mean standard error over the root of its luminance is at most T --\n"
+                "                          not --adaptive's T.  One device; not with --adaptive or --save-every-frame; composes with --denoise-variance, --bloom, --tonemap\n"
+                "      --min-spp N         with --adaptive or --adaptive-variance: samples every pixel of a tile needs before the tile may retire (default 2, at least 2)\n"
                 "      --denoise           write the denoised image: feature planes once before the first frame, then the edge-avoiding a-trous filter over the\n"
                 "                          accumulated mean (one device; not with --save-every-frame).  Without it the output is what it always was\n"
                 "      --denoise-variance  write the variance-guided image instead: the frames are rendered with glrtx_render_moments in bursts of --frames-in-flight\n"
@@ -60,7 +63,7 @@ static void usage(const char *exe) {
 int main(int argc, char **argv) {
     std::string input, out = "output.png";
     int depth = 16, spp = 1, frames = 16, device = -1, in_flight = 0;
-    bool every_frame = false, extensions = false, whitted = false, order_by_hits = false, volume = false, adaptive = false, min_spp_given = false, volume_wavefront = false;
+    bool every_frame = false, extensions = false, whitted = false, order_by_hits = false, volume = false, adaptive = false, adaptive_variance = false, min_spp_given = false, volume_wavefront = false;
     float adapt_threshold = 0.0f;
     int min_spp = 2;
     bool denoise = false, denoise_variance = false;
@@ -95,6 +98,7 @@ int main(int argc, char **argv) {
         else if (a == "--enable-volume") volume = true;
         else if (a == "--volume-wavefront") volume_wavefront = true;
         else if (a == "--adaptive") { adaptive = true; adapt_threshold = (float)std::atof(next("--adaptive")); }
+        else if (a == "--adaptive-variance") { adaptive_variance = true; adapt_threshold = (float)std::atof(next("--adaptive-variance")); }
         else if (a == "--min-spp") { min_spp = std::atoi(next("--min-spp")); min_spp_given = true; }
         else if (a == "--denoise") denoise = true;
         else if (a == "--denoise-variance") denoise_variance = true;
@@ -118,7 +122,11 @@ int main(int argc, char **argv) {
         else { usage(argv[0]); return 1; }
     }
     if (input.empty()) { usage(argv[0]); return 1; }
-    if (min_spp_given && !adaptive) { std::fprintf(stderr, "--min-spp needs --adaptive\n"); return 1; }
+    if (min_spp_given && !adaptive && !adaptive_variance) { std::fprintf(stderr, "--min-spp needs --adaptive or --adaptive-variance\n"); return 1; }
+    if (adaptive_variance && (adaptive || every_frame || devices.size() > 1 || min_spp < 2)) {
+        std::fprintf(stderr, "--adaptive-variance: one device, not with --adaptive or --save-every-frame, and --min-spp must be at least 2\n");
+        return 1;
+    }
     if (adaptive && (every_frame || min_spp < 2)) { std::fprintf(stderr, "--adaptive: not with --save-every-frame, and --min-spp must be at least 2\n"); return 1; }
 
     if (denoise_iters != 0 && ((!denoise && !denoise_variance) || denoise_iters < 1 || denoise_iters > 6)) {
@@ -156,6 +164,7 @@ int main(int argc, char **argv) {
     window->setOutput(out, every_frame);
     window->setOrderChildrenByHits(order_by_hits);
     if (adaptive) window->setAdaptive(adapt_threshold, min_spp);
+    if (adaptive_variance) window->setAdaptiveVariance(adapt_threshold, min_spp);
     window->setVolumeWavefront(volume_wavefront);
     if (denoise) window->setDenoise(denoise_iters);
     if (denoise_variance) window->setDenoiseVariance(denoise_iters);

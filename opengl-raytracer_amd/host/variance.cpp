@@ -1,5 +1,6 @@
-// variance.cpp -- glrt_fold_moments and glrt_variance_estimate (include/glrt_host.h): the CPU statements of the device's moments fold and variance pass
-// (glrtx_render_moments, glrtx_denoise_variance, include/glrtx.h "Variance guidance"; csrc/variance.hip.h).  The variance-guided filter that reads V0 is
+// variance.cpp -- glrt_fold_moments, glrt_variance_estimate and glrt_adaptive_select_moments (include/glrt_host.h): the CPU statements of the device's moments fold,
+// variance pass and selection from M (glrtx_render_moments, glrtx_denoise_variance, glrtx_render_adaptive_moments, include/glrtx.h "Variance guidance" and
+// "Adaptive sampling by variance"; csrc/variance.hip.h).  The variance-guided filter that reads V0 is
 // host/denoise.cpp's.  The contract is the text in include/glrtx.h; tests/variance_math.py restates it in numpy.  Every fp32 operation below is one correctly
 // rounded IEEE operation in the order written (-ffp-contract=off; the only fused operations are lp_exp's own fmaf calls), under MXCSR FTZ | DAZ.
 #include <cmath>
@@ -15,6 +16,8 @@ namespace {
 using namespace glrt_detail;
 
 inline float max0(float x) { return x > 0.0f ? x : 0.0f; }
+
+constexpr float kAdaptLumFloor = 1.0e-3f;  // csrc/pt_kernel.hip.h: kAdaptLumFloor
 
 bool sigma_ok(float v) { return v > 0.0f && !std::isinf(v); }
 
@@ -100,5 +103,35 @@ int glrt_variance_estimate(const float *accum, const float *moments, const float
     std::vector<int32_t> id;
     ids_of(accum, albedo_id, (size_t)width * rows, id);
     estimate(accum, moments, normal_depth, albedo_id, id, width, rows, sigma_normal, sigma_depth, demodulate, out_v0);
+    return GLRT_HOST_OK;
+}
+
+int glrt_adaptive_select_moments(const float *moments, int width, int rows, float threshold, int min_samples, uint8_t *mask_out, float *err_out) {
+    if (!moments || !mask_out || width < 1 || rows < 1 || width > 65536 || rows > 65536) return GLRT_HOST_EINVAL;
+    FlushDenormals ftz;
+    const int tiles_x = (width + 7) / 8, tiles_y = (rows + 7) / 8;
+    for (int ty = 0; ty < tiles_y; ty++)
+        for (int tx = 0; tx < tiles_x; tx++) {
+            float s[64];
+            int n_in = 0;
+            bool force = false;
+            for (int k = 0; k < 64; k++) {  // lane k of the tile's wave: pixel (k & 7, k >> 3)
+                const int x = tx * 8 + (k & 7), y = ty * 8 + (k >> 3);
+                s[k] = 0.0f;
+                if (x >= width || y >= rows) continue;
+                n_in++;
+                const float *m = moments + 4 * ((size_t)y * width + x);
+                if (!(m[3] >= (float)min_samples)) force = true;
+                const float mu1 = m[0] / m[3], mu2 = m[1] / m[3];
+                const float v = max0(mu2 - mu1 * mu1) / m[3];
+                s[k] = std::sqrt(v) / std::sqrt(mu1 + kAdaptLumFloor);
+            }
+            for (int h = 32; h >= 1; h >>= 1)
+                for (int k = 0; k < h; k++) s[k] = s[k] + s[k ^ h];
+            const float e = s[0] / (float)n_in;
+            const size_t t = (size_t)ty * tiles_x + tx;
+            mask_out[t] = (force || threshold < 0.0f || !(e <= threshold)) ? 1 : 0;
+            if (err_out) err_out[t] = canon(e);
+        }
     return GLRT_HOST_OK;
 }

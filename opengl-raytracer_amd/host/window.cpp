@@ -147,6 +147,30 @@ void Window::mainloop(const std::shared_ptr<Scene> &scene_, double fps) {
         GLRT_Info("Presented: %d frames, %d images, %llu render kernel launches", frameLimit_, images, (unsigned long long)st.kernel_launches);
         return;
     }
+    if (adaptiveVar_) {
+        // Adaptive sampling by variance: --adaptive's bursts with every selection made from the moments plane, which the bursts themselves feed.
+        if (glrtx_group_size(grp_) != 1 || adaptive_) GLRT_FatalError("--adaptive-variance: one device, and not with --adaptive (groups have no moments plane)");
+        glrtx_ctx *c0 = glrtx_group_ctx(grp_, 0);
+        if (glrtx_track_moments(c0, 1) != GLRTX_OK) GLRT_FatalError("glrtx_track_moments: %s", glrtx_last_error(c0));
+        glrtx_params p;
+        frameParams(p);
+        const glrtx_adaptive cfg = {adaptThreshold_, adaptMinSamples_};
+        int issued = 0;
+        while (issued < frameLimit_) {
+            const int n = frameLimit_ - issued < framesInFlight_ ? frameLimit_ - issued : framesInFlight_;
+            std::vector<float> seeds(2 * (size_t)n);
+            for (int f = 0; f < n; f++) glrt_frame_seed(frame_++, &seeds[2 * (size_t)f]);
+            if (glrtx_render_adaptive_moments(c0, &p, seeds.data(), n, &cfg) != GLRTX_OK) GLRT_FatalError("glrtx_render_adaptive_moments: %s", glrtx_last_error(c0));
+            issued += n;
+            int active = 0, total = 0;
+            if (glrtx_adaptive_active_tiles(c0, &active, &total) != GLRTX_OK) GLRT_FatalError("glrtx_adaptive_active_tiles: %s", glrtx_last_error(c0));
+            GLRT_Info("Adaptive: frame %d, active tiles %d/%d", issued, active, total);
+            if (active == 0) break;
+        }
+        lastMs_ = issued > 0 ? std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() / issued : 0.0;
+        if (!output_.empty() && frameLimit_ > 0) saveCurrentFrame(output_, true);
+        return;
+    }
     if (denoiseVar_) {
         // Variance guidance: the frames in bursts of framesInFlight_ through glrtx_render_moments, which folds every sample into the moments plane as well.
         glrtx_ctx *c0 = glrtx_group_ctx(grp_, 0);

@@ -51,6 +51,9 @@ public:
     // Adaptive sampling (no reference counterpart; glrtx_render_adaptive): bursts of framesInFlight frames, each on the 8x8 tiles that have not converged
     // (error above threshold, or fewer than minSamples samples), until no tile is active or the frame limit is reached; one "Adaptive:" line per burst.
     void setAdaptive(float threshold, int minSamples) { adaptive_ = true; adaptThreshold_ = threshold; adaptMinSamples_ = minSamples; }
+    // The same bursts with the selection made from the luminance moments (glrtx_render_adaptive_moments; tracking is switched on): one device; composes with
+    // setDenoiseVariance, whose filter reads the variance the bursts fed.  Its thresholds are not setAdaptive's.
+    void setAdaptiveVariance(float threshold, int minSamples) { adaptiveVar_ = true; adaptThreshold_ = threshold; adaptMinSamples_ = minSamples; }
     // Volume scenes on the wavefront kernel (glrtx_set_volume_wavefront on every member): frames in flight, fed launches and adaptive sampling with the volume
     // on; same images as the persistent megakernel, the default.  Adaptive sampling of a volume scene turns it on by itself.
     void setVolumeWavefront(bool on) { volumeWavefront_ = on; }
@@ -95,7 +98,7 @@ private:
     unsigned frame_ = 0;
     bool saveEveryFrame_ = false;
     bool orderByHits_ = false;
-    bool adaptive_ = false;
+    bool adaptive_ = false, adaptiveVar_ = false;
     float adaptThreshold_ = 0.0f;
     int adaptMinSamples_ = 2;
     bool volumeWavefront_ = false;

@@ -158,7 +158,7 @@ EXPORTS = ["glrtx_abi_version", "glrtx_create", "glrtx_destroy", "glrtx_last_err
            "glrtx_trace_rays", "glrtx_trace_rays_device", "glrtx_reproject", "glrtx_reproject_last", "glrtx_debug_reproject",
            "glrtx_track_motion", "glrtx_read_features_geom", "glrtx_reproject_motion", "glrtx_debug_reproject_motion",
            "glrtx_track_moments", "glrtx_render_moments", "glrtx_read_moments", "glrtx_denoise_variance", "glrtx_debug_denoise_variance",
-           "glrtx_debug_reproject_moments", "glrtx_debug_reproject_motion_moments",
+           "glrtx_debug_reproject_moments", "glrtx_debug_reproject_motion_moments", "glrtx_render_adaptive_moments", "glrtx_debug_adaptive_select_moments",
            "glrtx_exposure_measure", "glrtx_exposure_reset", "glrtx_read_exposure", "glrtx_tonemap", "glrtx_read_tonemapped", "glrtx_resolve_tonemapped_rgba8",
            "glrtx_debug_tonemap", "glrtx_debug_tonemap_burst",
            "glrtx_bloom", "glrtx_read_bloomed", "glrtx_tonemap_bloomed", "glrtx_resolve_bloomed_rgba8", "glrtx_debug_bloom", "glrtx_debug_bloom_burst"]
@@ -301,6 +301,11 @@ def lib():
                                                                C.POINTER(C.c_int), C.POINTER(C.c_int)]
         except AttributeError:
             pass
+        try:  # (additive to ABI 10 as well: the adaptive selection from M)
+            L.glrtx_render_adaptive_moments.argtypes = [vp, C.POINTER(Params), fp, C.c_int, C.POINTER(Adaptive)]
+            L.glrtx_debug_adaptive_select_moments.argtypes = [fp, C.c_int, C.c_int, C.c_float, C.c_int, u8p, fp, ip, ip]
+        except AttributeError:
+            pass
         try:  # (additive to ABI 10 as well: tone mapping)
             tc = C.POINTER(TonemapCfg)
             L.glrtx_exposure_measure.argtypes = [vp, tc]
@@ -405,6 +410,26 @@ def adaptive_select(accum, half, threshold, min_samples):
     n = C.c_int(0)
     rc = L.glrtx_debug_adaptive_select(_fp(a), _fp(h), width, rows, float(threshold), int(min_samples), mask.ctypes.data_as(C.POINTER(C.c_uint8)), _fp(err),
                                        lst.ctypes.data_as(C.POINTER(C.c_int)), C.byref(n))
+    if rc != 0:
+        raise GlrtxError(rc, L.glrtx_last_error(None).decode())
+    return mask, err, lst[:n.value].copy()
+
+
+def adaptive_select_moments(moments, threshold, min_samples):
+    """glrtx_debug_adaptive_select_moments on the current device: the selection kernels of render_adaptive_moments on a moments plane (rows, width, 4) float32.
+    Returns (mask (tiles_y, tiles_x) uint8, E (tiles_y, tiles_x) float32 -- NaN as 0x7FC00000 --, ascending list of active tiles)."""
+    L = lib()
+    m = _f32(moments)
+    if m.ndim != 3 or m.shape[2] != 4:
+        raise ValueError(f"adaptive_select_moments: moments must be (rows, width, 4), got {m.shape}")
+    rows, width = m.shape[:2]
+    ty, tx = (rows + 7) // 8, (width + 7) // 8
+    mask = np.zeros((ty, tx), np.uint8)
+    err = np.zeros((ty, tx), np.float32)
+    lst = np.zeros(ty * tx, np.int32)
+    n = C.c_int(0)
+    rc = L.glrtx_debug_adaptive_select_moments(_fp(m), width, rows, float(threshold), int(min_samples), mask.ctypes.data_as(C.POINTER(C.c_uint8)), _fp(err),
+                                               lst.ctypes.data_as(C.POINTER(C.c_int)), C.byref(n))
     if rc != 0:
         raise GlrtxError(rc, L.glrtx_last_error(None).decode())
     return mask, err, lst[:n.value].copy()
@@ -844,6 +869,14 @@ class Device:
         """Adaptive sampling (glrtx_render_adaptive): select the active 8x8 tiles, then render len(seeds) frames of those tiles only.  threshold < 0: nothing retires."""
         p, sd, cfg = _adaptive_args(params, seeds, threshold, min_samples)
         self._ck(self.L.glrtx_render_adaptive(self.h, C.byref(p), _fp(sd), sd.shape[0], C.byref(cfg)))
+    def render_adaptive_moments(self, params, seeds, cfg, min_samples=2):
+        """render_adaptive with the selection made from the moments plane M and the active tiles' samples folded into M (glrtx_render_adaptive_moments; needs
+        track_moments).  cfg: an Adaptive, or the threshold (then min_samples applies).  Its thresholds are not render_adaptive's: here a tile's error is the
+        mean standard error of its pixels' mean luminance over the root of that luminance.  The half buffer is neither read nor written."""
+        if isinstance(cfg, Adaptive):
+            cfg, min_samples = cfg.threshold, cfg.min_samples
+        p, sd, k = _adaptive_args(params, seeds, cfg, min_samples)
+        self._ck(self.L.glrtx_render_adaptive_moments(self.h, C.byref(p), _fp(sd), sd.shape[0], C.byref(k)))
     def adaptive_active_tiles(self):
         """(active, total) tiles of the last selection (syncs)."""
         a, t = C.c_int(0), C.c_int(0)

@@ -42,6 +42,7 @@ def lib():
         L.glrt_fold_moments.argtypes = [fp, fp, C.c_int, C.c_int, C.c_int]
         L.glrt_variance_estimate.argtypes = [fp, fp, fp, fp, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, fp]
         L.glrt_denoise_variance.argtypes = [fp, fp, fp, fp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int, fp, fp]
+        L.glrt_adaptive_select_moments.argtypes = [fp, C.c_int, C.c_int, C.c_float, C.c_int, C.POINTER(C.c_uint8), fp]
         L.glrt_reproject.argtypes = [fp] * 9 + [C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, fp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.glrt_render_features_geom.argtypes = [fp, C.c_size_t, fp, C.c_size_t, fp, C.c_size_t, fp, C.c_size_t, fp, fp] + [C.c_int] * 5 + [fp, fp, fp]
         L.glrt_reproject_motion.argtypes = [fp] * 6 + [C.c_size_t, fp, C.c_size_t, fp, fp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, fp,
@@ -255,6 +256,21 @@ def variance_estimate(accum, moments, normal_depth, albedo_id, sigma_normal=DENO
     if rc != 0:
         raise RuntimeError(f"glrt_variance_estimate failed: {rc}")
     return v0
+
+
+def adaptive_select_moments(moments, threshold, min_samples):
+    """glrt_adaptive_select_moments: the CPU statement of Device.render_adaptive_moments' selection on a moments plane (rows, width, 4) float32.
+    Returns (mask (tiles_y, tiles_x) uint8, E (tiles_y, tiles_x) float32, a NaN as 0x7FC00000)."""
+    m = _f32(moments)
+    if m.ndim != 3 or m.shape[2] != 4:
+        raise ValueError(f"adaptive_select_moments: moments must be (rows, width, 4), got {m.shape}")
+    rows, width = m.shape[:2]
+    mask = np.zeros(((rows + 7) // 8, (width + 7) // 8), np.uint8)
+    err = np.zeros(mask.shape, np.float32)
+    rc = lib().glrt_adaptive_select_moments(_fp(m), width, rows, float(threshold), int(min_samples), mask.ctypes.data_as(C.POINTER(C.c_uint8)), _fp(err))
+    if rc != 0:
+        raise RuntimeError(f"glrt_adaptive_select_moments failed: {rc}")
+    return mask, err
 
 
 def denoise_variance(accum, moments, normal_depth, albedo_id, iterations=DENOISE_VAR_DEFAULTS["iterations"], sigma_lum=DENOISE_VAR_DEFAULTS["sigma_lum"],
