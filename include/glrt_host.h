@@ -164,6 +164,18 @@ int glrt_denoise_variance(const float *accum, const float *moments, const float 
  * GLRT_HOST_EINVAL: a NULL moments or mask_out, a size outside 1..65536. */
 int glrt_adaptive_select_moments(const float *moments, int width, int rows, float threshold, int min_samples, uint8_t *mask_out, float *err_out);
 
+/* Firefly re-weighting: the CPU statements of glrtx_render_cascades' fold and of glrtx_reweight / glrtx_debug_reweight (include/glrtx.h "Firefly
+ * re-weighting": the formulas are there), bit for bit (host/reweight.cpp; tests/reweight_math.py states them in numpy).  cascades: the six planes C_0 .. C_5
+ * back to back, each width x rows x 4 floats {sum w r, sum w g, sum w b, count}, rows packed.  They run with denormals flushed (MXCSR FTZ | DAZ, restored on return).
+ *   glrt_fold_cascades  folds n_planes sample planes (plane k at planes + k * width * rows * 4), in order, into `cascades` in place and -- like the device's
+ *                       pass, after the cascades' own update -- into `accum` (width x rows x 4 floats {rgb sum, count}; may be NULL).  n_planes = 0 changes nothing.
+ *   glrt_reweight       the resolve: out, width x rows x 4 floats {rgb, 1}; a NaN is stored as 0x7FC00000.
+ * GLRT_HOST_EINVAL: a NULL array, a size outside 1..65536, a negative n_planes, a start outside 2^-20 .. 2^20 (a NaN included), a kappa that is not a positive
+ * finite number. */
+#define GLRT_CASCADES 6
+int glrt_fold_cascades(float *cascades, float *accum, const float *planes, int n_planes, int width, int rows, float start);
+int glrt_reweight(const float *cascades, int width, int rows, float kappa, float *out);
+
 /* Temporal reprojection: the CPU statement of the device's glrtx_reproject / glrtx_debug_reproject (include/glrtx.h "Reprojection": the formulas are there), bit
  * for bit.  accum / n0 / a0: the old view's accumulator float4(rgb sum, count) and feature planes; n1 / a1: the new view's planes; out: the new accumulator; all
  * width x rows x 4 floats, rows packed.  c2w_prev / s2c_prev: the camera of the old view (inverted here with glrt_mat4_inverse's routine); c2w_cur / s2c_cur: the

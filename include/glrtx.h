@@ -840,6 +840,74 @@ int glrtx_resolve_bloomed_rgba8(glrtx_ctx *ctx, uint8_t *dst, size_t dst_pitch_b
 int glrtx_debug_bloom(const float *src, int width, int rows, const glrtx_bloom_cfg *cfg, float *d_out, float *b_out);
 int glrtx_debug_bloom_burst(glrtx_ctx *ctx, const glrtx_bloom_cfg *cfg, int reps, float *ms_per_call);
 
+/* ---- Firefly re-weighting: luminance cascades beside the accumulator and a resolve that keeps a brightness level only as far as the neighbourhood expects it
+ * (Zirr, Hanika and Dachsbacher, "Re-weighting Firefly Samples for Improved Finite-Sample Monte Carlo Estimates", CGF 37(6), 2018; no reference counterpart;
+ * everything here is off unless called: with tracking off no other call changes what it does or writes).  Meant for the image accumulated for a second or two
+ * -- tens to hundreds of samples per pixel -- where no spatial filter is wanted and the remaining error is a few dozen lone samples.
+ *   glrtx_track_cascades           enable != 0: keep the cascade planes C with bounds b_k = start * 8^k.  C is allocated, zeroed, on first use; zeroed by glrtx_clear
+ *                                  and glrtx_bind_accum; released by glrtx_resize; enabling again with another start zeroes it (the bins were the old bounds').
+ *                                  enable = 0 syncs and releases C (start is not read).  glrtx_reproject and glrtx_reproject_motion ZERO C if it exists: the bins
+ *                                  belong to the old pixel grid (H's rule, not M's).
+ *   glrtx_render_cascades          glrtx_render_moments with the other sink: plain launches with sample planes on the context's stream, in helpings, never fed; each
+ *                                  is folded by one pass into the accumulator -- bit for bit glrtx_render_frames' -- and into C.  n_frames = 0 only allocates.
+ *                                  Feeds C only: with glrtx_track_moments on as well, each render call feeds its own plane.
+ *   glrtx_read_cascades            syncs, then copies the six planes back to back, owned rows each, rows dst_pitch_bytes apart (plane k at k * owned_rows rows).
+ *   glrtx_reweight                 the resolve, below, into the image D {rgb, 1} -- the one glrtx_denoise writes: glrtx_read_denoised, glrtx_resolve_denoised_rgba8
+ *                                  and source = 1 of the tone-mapping and bloom calls serve it unchanged.  Needs no feature planes.  On the context's stream, no
+ *                                  host sync; seals an open fed launch.
+ *   glrtx_debug_fold_cascades      the pass kernel on packed caller arrays on the current HIP device, no context: accum (width x rows float4), cascades (six such
+ *                                  planes back to back), frames (n_frames planes, one sample each) -> accum_out, cascades_out (either may be NULL).
+ *   glrtx_debug_reweight           the resolve kernel on caller arrays likewise: cascades -> out (width x rows float4).
+ *   glrtx_debug_reweight_burst     device time of one resolve from `reps` launches back to back between one pair of events after a warm-up pass.
+ *   GLRTX_EINVAL, nothing changed: a NULL argument; a start that is not within 2^-20 .. 2^20 (a NaN among them); a kappa that is not a positive finite number;
+ *   glrtx_render_cascades: everything glrtx_render_moments refuses, with cascade tracking in the place of moments tracking; glrtx_read_cascades, glrtx_reweight:
+ *   tracking off, no accumulator; glrtx_reweight also: C not yet allocated at the current shape, a partitioned context (world > 1: a seam per stripe); the debug
+ *   calls' sizes outside 1..65536, n_frames < 0.  Groups: no call.
+ * The arithmetic (this text is the contract; glrt_fold_cascades / glrt_reweight in glrt_host.h and tests/reweight_math.py state it again, and the three agree bit
+ * for bit).  The rules are those of "Variance guidance": every fp32 operation is one correctly rounded operation in the order written, unfused; denormals are
+ * flushed in and out; selects are as written; lum(r, g, b) = (0.2126 r + 0.7152 g) + 0.0722 b.
+ *   Cascade planes.  Six float4 planes C_0 .. C_5 of the accumulator's pitch, {sum w r, sum w g, sum w b, count}.  b_k = start * 8^k: start is scaled by powers of
+ *     two, so every b_k is exact.
+ *   Fold, per sample v, before the accumulator's own add.  With l = lum(v):
+ *     j = 0;  for k = 1 .. 4: if (l >= b_k) j = k                        (a NaN leaves j = 0)
+ *     lower = b_j;  upper = b_{j+1}
+ *     if (!(l > lower))     { wl = 1; wu = 0; jc = j }                   (l <= start, negatives, NaN)
+ *     else if (l >= upper)  { wl = 0; wu = 1; jc = 5 }                   (only j = 4: at or beyond the top bound, +inf)
+ *     else { q = lower / l;  wl = (q - 0.125f) / 0.875f;  wl = wl > 0 ? wl : 0;  wl = wl < 1 ? wl : 1;  wu = 1.0f - wl;  jc = j }
+ *     C_j.rgb += wl * v.rgb  (three products, three adds; always performed, also with wl = 0);  C_{j+1}.rgb += wu * v.rgb;  C_jc.w += 1.0f
+ *     No other plane is touched by that sample.  The split is Zirr et al.'s, linear in 1 / l: a sample contributes exactly 1 to sum_k lum(C_k) / b_k.  The count
+ *     word is this library's addition (the paper estimates counts from lum(C_k) / b_k; the fourth word is free and holds the exact integer): sum_k C_k.w is the
+ *     number of samples folded, exactly, and while every sample has l <= start, C_0 is the accumulator's own chain (1 * v = v).
+ *   Resolve, per pixel p, into D {rgb, 1}:
+ *     T_5 = C_5.w;  T_k = T_{k+1} + C_k.w for k = 4 .. 0                  (samples at level k or brighter)
+ *     n = T_0(p).  DEAD when n is a zero, a denormal or a NaN: D = {0, 0, 0, 1}.
+ *     for j = 1 .. 5:  s = 0;  over the 3x3 taps q = p + (dx, dy), dy outermost, inside the image (the owned rows as one image):  s = s + T_{j-1}(q)
+ *                      s = s - 1.0f;  s = s > 0 ? s : 0;  r_j = s / kappa;  r_j = r_j < 1 ? r_j : 1
+ *     per channel:     a = C_0.c(p);  for j = 1 .. 5:  a = a + r_j * C_j.c(p);      D.c = a / n      (a NaN is stored as 0x7FC00000)
+ *     Cascade 0 always counts in full.  A brighter level counts as far as the 3x3 neighbourhood holds kappa samples at that level's lower neighbour or brighter,
+ *     other than one: a lone sample supports nothing.  Being dimmer than the surroundings is never a firefly, hence "or brighter" and not the paper's j - 1 .. j + 1
+ *     window; the ramp to kappa replaces the paper's global / local pair.  With 1 spp an interior pixel's neighbourhood holds 8 other samples, so kappa <= 8
+ *     passes a uniformly bright region unchanged at 1 spp.
+ *   It follows that (1) when every folded sample had l <= start and C and the accumulator were cleared together, D.rgb == acc.rgb / acc.w, bit for bit; (2) a
+ *   5x5 image of eight samples {0.5, 0.5, 0.5} per pixel plus a ninth that is {5000, 5000, 5000} at the centre and {0.5, ...} elsewhere, start 1, kappa 4: the
+ *   centre's counts are [8, 0, 0, 0, 1, 0], the centre resolves to 4.0f / 9.0f exactly and every other pixel to 0.5f; (3) D is finite whenever C is finite with
+ *   integer counts (and the six colours' sum does not overflow).
+ * The estimate is consistent: as samples build up every level becomes supported and D converges to the mean; it never exceeds the mean of non-negative samples.
+ * Out of scope: carrying C through the reprojections; feeding C and M in one pass; adaptive launches, fed launches, the present ring, the megakernels and the
+ * volume forms; groups and partitioned resolves; re-weighting in front of the denoisers (they read the accumulator); the paper's local-reliability term; more or
+ * fewer than six cascades, a base other than 8. */
+typedef struct glrtx_reweight_cfg {
+    float kappa;  /* samples a 3x3 neighbourhood must hold besides one for a level to count in full; finite, > 0; default 4 */
+} glrtx_reweight_cfg;
+int glrtx_track_cascades(glrtx_ctx *ctx, int enable, float start);
+int glrtx_render_cascades(glrtx_ctx *ctx, const glrtx_params *params, const float *seeds_xy, int n_frames);
+int glrtx_read_cascades(glrtx_ctx *ctx, float *dst, size_t dst_pitch_bytes);
+int glrtx_reweight(glrtx_ctx *ctx, const glrtx_reweight_cfg *cfg);
+int glrtx_debug_fold_cascades(const float *accum, const float *cascades, const float *frames, int n_frames, int width, int rows, float start, float *accum_out,
+                              float *cascades_out);
+int glrtx_debug_reweight(const float *cascades, int width, int rows, const glrtx_reweight_cfg *cfg, float *out);
+int glrtx_debug_reweight_burst(glrtx_ctx *ctx, const glrtx_reweight_cfg *cfg, int reps, float *ms_per_launch);
+
 /* ---- Groups: the same device layer on several GPUs of one node, behind one handle and one host thread.
  * No reference counterpart (the reference is single-GPU); SURVEY.md 8(b) sketches glrtx_create(ctx**, device_ids, n) with a
  * gathering read_accum -- this is that, kept apart from the single-context calls.  Member i owns the 8-row stripes s with

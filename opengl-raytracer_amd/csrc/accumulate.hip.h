@@ -2,7 +2,7 @@
 //
 // Per pixel the pass is one chain of float additions -- acc.xyz += v.xyz; acc.w += 1 -- over the launch's planes, frame by frame, sample by sample: the chain that
 // consecutive single-frame launches perform inside the render kernel.  Every bit-exactness guarantee of the library rests on that chain, so it is written in one
-// template (pass) and the seven kernels are entry points over it.  They differ in two things only:
+// template (pass) and the eight kernels are entry points over it.  They differ in two things only:
 //   the SOURCE  Planes -- one flat array [frame][sample][rows][pitch_f4] (plain and overlapped launches);
 //               Fed -- a fed launch's chunks of kFeedChunkFrames frames behind FeedDev, however many frames the launch ended up taking (FeedDev::frames_known, final
 //               once the render kernel has ended);
@@ -11,14 +11,18 @@
 //               also goes into the half buffer H when the pixel's count BEFORE the add is odd: H holds every second sample (tests/adaptive_math.py);
 //               Moments (glrtx_render_moments) -- the sample's luminance and its square go into the moments plane M {sum l, sum l^2, 0, count} (tests/variance_math.py);
 //               MomentsMasked (glrtx_render_adaptive_moments) -- Moments on ACTIVE tiles only: an inactive tile's accumulator and M entries are not touched;
+//               Cascades (glrtx_render_cascades) -- the sample is split by luminance over the six cascade planes C_0 .. C_5 {sum w rgb, count} (reweight.hip.h: fold;
+//               tests/reweight_math.py); the six float4 are loaded before the sample loop and stored after it;
 //               Present (glrtx_present_enable) -- behind every frame f the pixel's screen.frag value (rs_pixel, byte-identical to resolve_kernel's) goes into image
 //               (slot0 + f) % n_ring of the device ring, packed rows of `width` texels, row y at rows - 1 - y when flipped (within the owned rows, like
 //               glrtx_resolve_rgba8): one launch and one read of the accumulator instead of a pass plus a resolve per frame.
-// Bandwidth-bound: 16 B per plane and pixel in, one 16-B read-modify-write of the accumulator (Half, Moments, MomentsMasked: two), 4 B per frame and pixel out (Present).
+// Bandwidth-bound: 16 B per plane and pixel in, one 16-B read-modify-write of the accumulator (Half, Moments, MomentsMasked: two; Cascades: seven), 4 B per frame and
+// pixel out (Present).
 #pragma once
 #include <type_traits>
 
 #include "denoise.hip.h"  // (pt_kernel.hip.h: FeedDev, rs_pixel; lum)
+#include "reweight.hip.h"
 
 namespace glrtx {
 namespace accumulate {
@@ -43,6 +47,7 @@ struct None {};
 struct Half { float4 *half; const unsigned char *mask; int tiles8_x; };  // H and the selection's mask byte per 8x8 tile
 struct Moments { float4 *moments; };                                     // M, of the accumulator's pitch
 struct MomentsMasked { float4 *moments; const unsigned char *mask; int tiles8_x; };  // M and the selection's mask byte per 8x8 tile
+struct Cascades { float4 *c; size_t plane; float start; };                           // C_0 .. C_5, `plane` float4 apart, of the accumulator's pitch
 struct Present { uchar4 *ring; size_t slot_px; int n_ring, slot0; float inv_gamma; int flip; };
 
 // One lane per pixel, a wave is 64 consecutive pixels of a row, four rows per workgroup: a grid of (width + 63) / 64 x (rows + 3) / 4.
@@ -53,7 +58,7 @@ struct Present { uchar4 *ring; size_t slot_px; int n_ring, slot0; float inv_gamm
 template <class Src, class Sink>
 DEV void pass(const Image im, const Src src, const Sink sink) {
     constexpr bool kHalf = std::is_same_v<Sink, Half>, kMasked = std::is_same_v<Sink, MomentsMasked>, kMoments = std::is_same_v<Sink, Moments> || kMasked,
-                   kPresent = std::is_same_v<Sink, Present>;
+                   kPresent = std::is_same_v<Sink, Present>, kCascades = std::is_same_v<Sink, Cascades>;
     const int x = blockIdx.x * 64 + (threadIdx.x & 63);
     const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (y >= im.rows) return;  // (a whole wave)
@@ -68,6 +73,13 @@ DEV void pass(const Image im, const Src src, const Sink sink) {
     float4 side = make_float4(0.f, 0.f, 0.f, 0.f);  // H or M
     if constexpr (kHalf) side = sink.half[at];
     if constexpr (kMoments) side = sink.moments[at];
+    [[maybe_unused]] float4 cas[kCascades ? reweight::kCascades : 1];
+    [[maybe_unused]] reweight::Bounds bounds;
+    if constexpr (kCascades) {
+        bounds = reweight::bounds_of(sink.start);
+#pragma unroll
+        for (int k = 0; k < reweight::kCascades; k++) cas[k] = sink.c[(size_t)k * sink.plane + at];
+    }
     for (int f = 0; f < runs; f++) {
         if (in) {
             const float4 *p = src.frame(f, plane) + at;
@@ -82,6 +94,7 @@ DEV void pass(const Image im, const Src src, const Sink sink) {
                     const float l = denoise::lum(v.x, v.y, v.z);
                     side.x = side.x + l; side.y = side.y + l * l; side.w = side.w + 1.0f;
                 }
+                if constexpr (kCascades) reweight::fold(cas, bounds, v);
                 acc.x = acc.x + v.x; acc.y = acc.y + v.y; acc.z = acc.z + v.z;
                 acc.w = acc.w + 1.0f;
             }
@@ -95,6 +108,10 @@ DEV void pass(const Image im, const Src src, const Sink sink) {
     if (in) im.accum[at] = acc;
     if constexpr (kHalf) sink.half[at] = side;
     if constexpr (kMoments) sink.moments[at] = side;
+    if constexpr (kCascades) {
+#pragma unroll
+        for (int k = 0; k < reweight::kCascades; k++) sink.c[(size_t)k * sink.plane + at] = cas[k];
+    }
 }
 
 }  // namespace accumulate
@@ -107,6 +124,7 @@ __global__ __launch_bounds__(256) void accumulate_present_planes_kernel(const ac
 __global__ __launch_bounds__(256) void accumulate_present_feed_kernel(const accumulate::Image im, const accumulate::Fed src, const accumulate::Present sink) { accumulate::pass(im, src, sink); }
 namespace variance { __global__ __launch_bounds__(256) void accumulate_moments_kernel(const accumulate::Image im, const accumulate::Planes src, const accumulate::Moments sink) { accumulate::pass(im, src, sink); } }
 namespace adaptive_moments { __global__ __launch_bounds__(256) void accumulate_kernel(const accumulate::Image im, const accumulate::Planes src, const accumulate::MomentsMasked sink) { accumulate::pass(im, src, sink); } }
+namespace reweight { __global__ __launch_bounds__(256) void accumulate_cascades_kernel(const accumulate::Image im, const accumulate::Planes src, const accumulate::Cascades sink) { accumulate::pass(im, src, sink); } }
 
 namespace accumulate {
 inline auto entry(Planes, None) { return accumulate_planes_kernel; }
@@ -114,6 +132,7 @@ inline auto entry(Fed, None) { return accumulate_feed_kernel; }
 inline auto entry(Planes, Half) { return accumulate_adaptive_kernel; }
 inline auto entry(Planes, Moments) { return variance::accumulate_moments_kernel; }
 inline auto entry(Planes, MomentsMasked) { return adaptive_moments::accumulate_kernel; }
+inline auto entry(Planes, Cascades) { return reweight::accumulate_cascades_kernel; }
 inline auto entry(Planes, Present) { return accumulate_present_planes_kernel; }
 inline auto entry(Fed, Present) { return accumulate_present_feed_kernel; }
 }  // namespace accumulate

@@ -192,7 +192,8 @@ struct glrtx_ctx {
     // ft_rows rows -- the shape of the owned rows when the features were rendered; allocated on first use, released by glrtx_resize (and so by a partition change)
     DevBuf ftN, ftA, ftCounter, dnP[2], dnD;
     int ft_w = 0, ft_rows = -1;   // (-1: no features)
-    bool dn_have = false;         // D holds a result of the current shape
+    bool dn_have = false;         // D holds a result ...
+    int dn_w = 0, dn_rows = -1;   // ... of this shape: recorded where D is written (glrtx_denoise, glrtx_denoise_variance, glrtx_reweight -- which needs no feature planes)
     // Reprojection (glrtx_reproject): the camera of the last glrtx_render_features (c2w[16], s2c[16]: the one the accumulator and the planes belong to), the spare
     // pair of feature planes and the spare accumulator (own pitch x owned rows) that the next call swaps in, and its two counters; allocated on first use,
     // released by glrtx_resize
@@ -215,6 +216,15 @@ struct glrtx_ctx {
     size_t mm_pitch = 0;
     int mm_rows = 0;
     bool mm_on = false;
+
+    // Firefly re-weighting (glrtx_track_cascades / glrtx_render_cascades / glrtx_reweight): the six cascade planes C_0 .. C_5 back to back, each of the accumulator's
+    // shape (rw_pitch x rw_rows; allocated on first use while tracking is on, zeroed with the accumulator and by the reprojections, released by glrtx_resize and by
+    // switching tracking off), and the bounds' start.
+    DevBuf rwC;
+    size_t rw_pitch = 0;
+    int rw_rows = 0;
+    bool rw_on = false;
+    float rw_start = 1.0f;
 
     // Tone mapping (glrtx_exposure_measure / glrtx_tonemap): the exposure block (tonemap::Exposure: the working histogram, then glrtx_exposure's image; allocated and
     // zeroed on first use, kept across glrtx_resize) and the plane T (packed rows of tm_w float4 over tm_rows rows; released by glrtx_resize)
@@ -1086,7 +1096,8 @@ struct RenderReq {
     // Calibration (glrtx_hit_histogram): one plain single-frame launch on the context's stream that counts closest hits per leaf record into `hit_hist` while it shades
     //     into `scratch` instead of the accumulator: no pipe slot, no ray counting, no presentation step.
     // AdaptiveMoments (glrtx_render_adaptive_moments): Adaptive's launch on the selection made from M; the pass folds the active tiles' planes into M, not into H.
-    enum Kind { Ordinary, Adaptive, Moments, Calibration, AdaptiveMoments } kind = Ordinary;
+    // Cascades (glrtx_render_cascades): Moments' launch; the pass folds the planes into the cascade planes C instead of M.
+    enum Kind { Ordinary, Adaptive, Moments, Calibration, AdaptiveMoments, Cascades } kind = Ordinary;
     bool adaptive() const { return kind == Adaptive || kind == AdaptiveMoments; }
     bool folds_moments() const { return kind == Moments || kind == AdaptiveMoments; }
     const float *seeds = nullptr;  // {x, y} per frame; a single frame's seed is the parameters' own
@@ -1337,7 +1348,7 @@ int wgwf_pipe_slot(glrtx_ctx *c, WgwfLaunch &L) {
 int wgwf_args(glrtx_ctx *c, WgwfLaunch &L) {
     const glrtx_params *p = L.p;
     glrtx_ctx::PipeSlot *const slot = L.slot;
-    const bool fed = L.f.fed, adapt = L.k.adapt, moments = L.req.kind == RenderReq::Moments;
+    const bool fed = L.f.fed, adapt = L.k.adapt, moments = L.req.kind == RenderReq::Moments || L.req.kind == RenderReq::Cascades;
     const int n_frames = L.n_frames, grid = L.grid;
     int rc;
     // A fed launch runs on its slot's stream and queues but on the CONTEXT's path state, like a plain launch: the same launch is 0.8 % faster there than on a slot's state
@@ -1433,6 +1444,8 @@ int wgwf_check(glrtx_ctx *c, const WgwfLaunch &L) {
     if (L.req.kind == RenderReq::Adaptive) ok = ok && c->adHalf.bytes >= (size_t)c->ad_pitch * c->owned_rows && c->ad_pitch == c->pitch_bytes;
     if (moments) ok = ok && !fed && !slot && w.planes && c->mmM.p && c->mm_pitch == c->pitch_bytes && c->mm_rows == c->owned_rows &&
                       c->mmM.bytes >= c->pitch_bytes * (size_t)c->owned_rows;
+    if (L.req.kind == RenderReq::Cascades) ok = ok && !fed && !slot && w.planes && c->rwC.p && c->rw_pitch == c->pitch_bytes && c->rw_rows == c->owned_rows &&
+                                                 c->rwC.bytes >= (size_t)reweight::kCascades * c->pitch_bytes * (size_t)c->owned_rows;
     if (fed) ok = ok && n_frames >= 1 && n_frames <= fed_cap && fed_cap <= kFeedMaxFrames && slot->feed_d.bytes >= sizeof(FeedDev) && w.feed_host != nullptr &&
                   slot->chunks[(n_frames - 1) / kFeedChunkFrames].p != nullptr && slot->chunk_bytes == L.frame_bytes;
     if (!ok) return fail(c, GLRTX_EDEVICE, "internal: wgwf launch shapes inconsistent (ids %zu, max id %zu, grid %d of %zu slots (%d per CU), block_paths %d, frames %d, fed %d)", L.ids, max_id,
@@ -1500,6 +1513,9 @@ int wgwf_issue(glrtx_ctx *c, const WgwfLaunch &L) {
             if (n_planes > 0) accumulate_launch(c, im, flat, accumulate::MomentsMasked{(float4 *)c->mmM.p, (const unsigned char *)c->adMask.p, L.tiles8_x});
         } else if (adapt) accumulate_launch(c, im, flat, accumulate::Half{(float4 *)c->adHalf.p, (const unsigned char *)c->adMask.p, L.tiles8_x});
         else if (L.req.kind == RenderReq::Moments) { if (n_planes > 0) accumulate_launch(c, im, flat, accumulate::Moments{(float4 *)c->mmM.p}); }
+        else if (L.req.kind == RenderReq::Cascades) {
+            if (n_planes > 0) accumulate_launch(c, im, flat, accumulate::Cascades{(float4 *)c->rwC.p, (size_t)L.a.pitch_f4 * (size_t)c->owned_rows, c->rw_start});
+        }
         else if (fed && pres) accumulate_launch(c, im, feed, ring);
         else if (fed) accumulate_launch(c, im, feed, accumulate::None{});
         else if (w.planes && pres) accumulate_launch(c, im, flat, ring);
@@ -1548,7 +1564,7 @@ int launch_wgwf(glrtx_ctx *c, const KernelArgs &a, const glrtx_params *p, const 
 // ---- denoising (glrtx_render_features, glrtx_denoise)
 void denoise_release(glrtx_ctx *c) {
     dev_free(c->ftN); dev_free(c->ftA); dev_free(c->ftCounter); dev_free(c->dnP[0]); dev_free(c->dnP[1]); dev_free(c->dnD);
-    c->ft_w = 0; c->ft_rows = -1; c->dn_have = false;
+    c->ft_w = 0; c->ft_rows = -1; c->dn_have = false; c->dn_w = 0; c->dn_rows = -1;
     dev_free(c->ftN_spare); dev_free(c->ftA_spare); dev_free(c->accum_spare); dev_free(c->rpCount);  // (glrtx_reproject's spares have the old shape too)
     c->rp_have = false;
     dev_free(c->ftG); dev_free(c->ftG_spare);
@@ -1763,20 +1779,25 @@ int moments_ensure(glrtx_ctx *c) {
 }
 bool moments_have(const glrtx_ctx *c) { return c->mm_on && c->mmM.p && c->mm_pitch == c->pitch_bytes && c->mm_rows == c->owned_rows; }
 
-// Everything glrtx_render_moments refuses, checked before anything changes: glrtx_render_adaptive's list, the volume and tracking being off.
-int moments_check(glrtx_ctx *c, const glrtx_params *p, const float *seeds_xy, int n_frames, const char *fn = "glrtx_render_moments") {
+// Everything a render call that folds its planes into a side plane refuses (glrtx_render_moments, glrtx_render_cascades), checked before anything changes:
+// glrtx_render_adaptive's list, the volume and the plane's tracking being off (`tracked`; `untracked` says so).
+int side_plane_check(glrtx_ctx *c, const glrtx_params *p, const float *seeds_xy, int n_frames, const char *fn, bool tracked, const char *untracked) {
     if (!p) return fail(c, GLRTX_EINVAL, "%s: NULL params", fn);
-    if (!c->mm_on) return fail(c, GLRTX_EINVAL, "%s: moments are not tracked (glrtx_track_moments)", fn);
+    if (!tracked) return fail(c, GLRTX_EINVAL, "%s: %s", fn, untracked);
     if (n_frames < 0 || (n_frames > 0 && !seeds_xy)) return fail(c, GLRTX_EINVAL, "%s: bad seeds/n_frames", fn);
     if (!c->have_scene) return fail(c, GLRTX_EINVAL, "%s: no scene uploaded", fn);
     if (!c->accum || c->width < 1) return fail(c, GLRTX_EINVAL, "%s: no accumulator (call glrtx_resize)", fn);
     if (p->n_samples < 0 || p->max_depth < 0) return fail(c, GLRTX_EINVAL, "%s: negative n_samples/max_depth", fn);
-    if (c->pres.ring > 0) return fail(c, GLRTX_EINVAL, "%s: presentation is enabled (the present ring's passes do not fold moments)", fn);
+    if (c->pres.ring > 0) return fail(c, GLRTX_EINVAL, "%s: presentation is enabled (the present ring's passes fold neither moments nor cascades)", fn);
     if (c->ext_flags != 0) return fail(c, GLRTX_EINVAL, "%s: extensions or volume are on", fn);
     if (c->n_spheres > 0) return fail(c, GLRTX_EINVAL, "%s: spheres are uploaded", fn);
     if (c->variant != 2) return fail(c, GLRTX_EINVAL, "%s: variant %d (only the wavefront kernel, variant 2, writes sample planes)", fn, c->variant);
     if (!wgwf_can_hold(p, false)) return fail(c, GLRTX_EINVAL, "%s: max_depth %d / n_samples %d beyond the wavefront kernel's path state", fn, p->max_depth, p->n_samples);
     return GLRTX_OK;
+}
+
+int moments_check(glrtx_ctx *c, const glrtx_params *p, const float *seeds_xy, int n_frames, const char *fn = "glrtx_render_moments") {
+    return side_plane_check(c, p, seeds_xy, n_frames, fn, c->mm_on, "moments are not tracked (glrtx_track_moments)");
 }
 
 // Everything glrtx_render_adaptive_moments refuses, checked before anything changes: glrtx_render_adaptive's list and glrtx_render_moments's (which holds all of the
@@ -1787,6 +1808,36 @@ int adapt_moments_check(glrtx_ctx *c, const glrtx_params *p, const float *seeds_
     if (cfg->min_samples < 2) return fail(c, GLRTX_EINVAL, "%s: min_samples %d < 2 (one sample has no variance)", fn, cfg->min_samples);
     return moments_check(c, p, seeds_xy, n_frames, fn);
 }
+
+// ---- firefly re-weighting (glrtx_track_cascades, glrtx_render_cascades, glrtx_reweight)
+// The cascade planes C at the accumulator's current shape, zeroed (on first use, at a clear, at a bind, at a reprojection, at another start).
+int cascades_ensure(glrtx_ctx *c) {
+    const size_t bytes = (size_t)reweight::kCascades * c->pitch_bytes * (size_t)std::max(c->owned_rows, 1);
+    if (int rc = ensure(c, c->rwC, bytes)) return rc;
+    HIP_TRY(c, hipMemsetAsync(c->rwC.p, 0, bytes, c->stream));
+    c->rw_pitch = c->pitch_bytes; c->rw_rows = c->owned_rows;
+    return GLRTX_OK;
+}
+bool cascades_have(const glrtx_ctx *c) { return c->rw_on && c->rwC.p && c->rw_pitch == c->pitch_bytes && c->rw_rows == c->owned_rows; }
+bool cascade_start_ok(float s) { return s >= 0x1p-20f && s <= 0x1p20f; }  // (a NaN fails both)
+
+int reweight_cfg_check(glrtx_ctx *c, const glrtx_reweight_cfg *k, const char *fn) {
+    if (!k) return fail(c, GLRTX_EINVAL, "%s: NULL cfg", fn);
+    if (!(k->kappa > 0.0f) || std::isinf(k->kappa)) return fail(c, GLRTX_EINVAL, "%s: kappa %g is not a positive finite number", fn, (double)k->kappa);
+    return GLRTX_OK;
+}
+
+// The resolve on `stream`: the six planes (pitch_f4, `plane` float4 apart) -> D (packed rows of `width`).
+int reweight_pass(glrtx_ctx *c, hipStream_t stream, const float4 *C, size_t plane, int pitch_f4, int width, int rows, float4 *D, const glrtx_reweight_cfg &k) {
+    const reweight::Args a{C, plane, D, pitch_f4, width, rows, k.kappa};
+    hipLaunchKernelGGL(reweight::reweight_kernel, reweight::reweight_grid(width, rows), dim3(256), 0, stream, a);
+    HIP_TRY(c, hipGetLastError());
+    return GLRTX_OK;
+}
+
+// D holds a result of the image's current shape.  (For every sequence of calls without glrtx_reweight this is what the feature planes' shape used to say: D is
+// written only at the current shape -- by the filters, whose feature planes have it -- and glrtx_resize, the only call that changes the shape, drops D.)
+bool denoised_have(const glrtx_ctx *c) { return c->dn_have && c->dnD.p && c->dn_w == c->width && c->dn_rows == c->owned_rows; }
 
 // ---- tone mapping (glrtx_exposure_measure, glrtx_tonemap, glrtx_resolve_tonemapped_rgba8)
 static_assert(sizeof(tonemap::Exposure) == tonemap::kExposureOut + sizeof(glrtx_exposure), "tonemap::Exposure ends with glrtx_exposure's image");
@@ -1823,7 +1874,7 @@ int tonemap_source(glrtx_ctx *c, const glrtx_tonemap_cfg *k, const char *fn, con
     if (int rc = tonemap_cfg_check(c, k, fn)) return rc;
     if (!c->accum || c->width < 1) return fail(c, GLRTX_EINVAL, "%s: no accumulator (call glrtx_resize)", fn);
     if (k->source == 1) {
-        if (!c->dn_have || !c->dnD.p || c->ft_w != c->width || c->ft_rows != c->owned_rows)
+        if (!denoised_have(c))
             return fail(c, GLRTX_EINVAL, "%s: source = 1 without a denoised image of the current shape (call glrtx_denoise or glrtx_denoise_variance first)", fn);
         src = (const float4 *)c->dnD.p; pitch_f4 = c->width;
     } else {
@@ -1891,7 +1942,7 @@ int bloom_source(glrtx_ctx *c, const glrtx_bloom_cfg *k, const char *fn, const f
     if (!c->accum || c->width < 1 || c->owned_rows < 1) return fail(c, GLRTX_EINVAL, "%s: no accumulator (call glrtx_resize)", fn);
     if (c->world > 1) return fail(c, GLRTX_EINVAL, "%s: the context is partitioned (rank %d of %d): the glow would stop at every stripe's seam", fn, c->rank, c->world);
     if (k->source == 1) {
-        if (!c->dn_have || !c->dnD.p || c->ft_w != c->width || c->ft_rows != c->owned_rows)
+        if (!denoised_have(c))
             return fail(c, GLRTX_EINVAL, "%s: source = 1 without a denoised image of the current shape (call glrtx_denoise or glrtx_denoise_variance first)", fn);
         src = (const float4 *)c->dnD.p; pitch_f4 = c->width;
     } else {
@@ -2048,6 +2099,7 @@ void glrtx_destroy(glrtx_ctx *c) {
     dev_free(c->accum_own); dev_free(c->counter); dev_free(c->rgba8); dev_free(c->work);
     dev_free(c->adHalf); dev_free(c->adMask); dev_free(c->adList); dev_free(c->adCount);
     dev_free(c->mmM); dev_free(c->mmM_spare);
+    dev_free(c->rwC);
     dev_free(c->tmExp); dev_free(c->tmT);
     dev_free(c->blB); dev_free(c->blPyr);
     denoise_release(c);
@@ -2600,6 +2652,7 @@ int glrtx_resize(glrtx_ctx *c, int width, int height) {
     }
     denoise_release(c);  // (the feature planes and the filter's images have the old shape; the stream is idle)
     dev_free(c->mmM); dev_free(c->mmM_spare);  // (so has the moments plane: allocated again on its next use)
+    dev_free(c->rwC);  // (and the cascade planes)
     dev_free(c->tmT); c->tm_w = 0; c->tm_rows = -1;  // (and the tone-mapped plane; the exposure block has no shape and stays)
     dev_free(c->blB); dev_free(c->blPyr); c->bl_w = 0; c->bl_rows = -1;  // (and the bloomed plane with its pyramid)
     c->width = width; c->height = height;
@@ -2629,6 +2682,7 @@ int glrtx_clear(glrtx_ctx *c) {
     HIP_TRY(c, hipMemsetAsync(c->accum, 0, c->pitch_bytes * (size_t)c->owned_rows, c->stream));
     if (c->adHalf.p && (rc_ = adapt_half_ensure(c))) return rc_;  // (the half buffer follows the accumulator: zeroed, at the current size)
     if (c->mmM.p && (rc_ = moments_ensure(c))) return rc_;        // (and so does the moments plane)
+    if (c->rwC.p && (rc_ = cascades_ensure(c))) return rc_;       // (and so do the cascade planes)
     c->pres.frame = 0;  // (images already produced keep their numbers)
     return GLRTX_OK;
 }
@@ -2653,6 +2707,7 @@ int glrtx_bind_accum(glrtx_ctx *c, void *device_ptr, size_t pitch_bytes, int cap
     c->accum = (float4 *)device_ptr;
     c->pitch_bytes = pitch_bytes;
     if (c->mmM.p) { if (int rc = moments_ensure(c)) return rc; }  // (another accumulator: the moments of the old one's samples say nothing about it)
+    if (c->rwC.p) { if (int rc = cascades_ensure(c)) return rc; } // (and neither do its cascades)
     if (c->adHalf.p) return adapt_half_ensure(c);  // (another accumulator: the half buffer of the old one would be compared with unrelated samples)
     return GLRTX_OK;
 }
@@ -2889,6 +2944,7 @@ int glrtx_render_features(glrtx_ctx *c, const glrtx_params *p) {
 }
 
 static int denoise_shape_check(glrtx_ctx *c, const char *fn, bool need_result) {
+    if (need_result && denoised_have(c)) return GLRTX_OK;  // (glrtx_reweight writes D without feature planes; otherwise the refusals below are what they were)
     if (c->ft_rows < 0 || !c->ftN.p) return fail(c, GLRTX_EINVAL, "%s: no feature planes (call glrtx_render_features first)", fn);
     if (c->ft_w != c->width || c->ft_rows != c->owned_rows) return fail(c, GLRTX_EINVAL, "%s: the image changed shape since the features were rendered", fn);
     if (need_result && !c->dn_have) return fail(c, GLRTX_EINVAL, "%s: no denoised image (call glrtx_denoise first)", fn);
@@ -2920,7 +2976,7 @@ int glrtx_denoise(glrtx_ctx *c, const glrtx_denoise_cfg *cfg) {
     const size_t bytes = (size_t)c->width * (size_t)std::max(c->owned_rows, 1) * sizeof(float4);
     int rc;
     if ((rc = ensure(c, c->dnP[0], bytes)) || (rc = ensure(c, c->dnP[1], bytes)) || (rc = ensure(c, c->dnD, bytes))) return rc;
-    c->dn_have = true;
+    c->dn_have = true; c->dn_w = c->width; c->dn_rows = c->owned_rows;
     if (c->owned_rows == 0) return GLRTX_OK;
     return denoise_passes(c, c->stream, c->accum, nullptr, (int)(c->pitch_bytes / sizeof(float4)), (const float4 *)c->ftN.p, (const float4 *)c->ftA.p,
                           (float4 *)c->dnP[0].p, (float4 *)c->dnP[1].p, (float4 *)c->dnD.p, nullptr, c->width, c->owned_rows, k);
@@ -3086,7 +3142,7 @@ int glrtx_denoise_variance(glrtx_ctx *c, const glrtx_denoise_var_cfg *cfg) {
     if ((rc = ensure(c, c->dnP[0], px * sizeof(float4))) || (rc = ensure(c, c->dnP[1], px * sizeof(float4))) || (rc = ensure(c, c->dnD, px * sizeof(float4)))) return rc;
     for (DevBuf &v : c->dnV)
         if ((rc = ensure(c, v, px * sizeof(float)))) return rc;
-    c->dn_have = true;
+    c->dn_have = true; c->dn_w = c->width; c->dn_rows = c->owned_rows;
     if (c->owned_rows == 0) return GLRTX_OK;
     float *const v[3] = {(float *)c->dnV[0].p, (float *)c->dnV[1].p, (float *)c->dnV[2].p};
     return denoise_passes(c, c->stream, c->accum, (const float4 *)c->mmM.p, (int)(c->pitch_bytes / sizeof(float4)), (const float4 *)c->ftN.p, (const float4 *)c->ftA.p,
@@ -3113,6 +3169,152 @@ int glrtx_debug_denoise_variance(const float *accum, const float *moments, const
         s.download(v0_out, v[0], vbytes);
     }
     return s.result(rc, fn);
+}
+
+// ---- firefly re-weighting
+int glrtx_track_cascades(glrtx_ctx *c, int enable, float start) {
+    const char *fn = "glrtx_track_cascades";
+    if (!c) return GLRTX_EINVAL;
+    if (enable) {
+        if (!cascade_start_ok(start)) return fail(c, GLRTX_EINVAL, "%s: start %g is not within 2^-20 .. 2^20", fn, (double)start);
+        if (c->rw_on && c->rwC.p && start != c->rw_start) {  // the bins were the old bounds'
+            seal_feed(c);
+            HIP_TRY(c, hipSetDevice(c->device));
+            if (int rc = cascades_ensure(c)) return rc;
+        }
+        c->rw_on = true; c->rw_start = start;
+        return GLRTX_OK;
+    }
+    if (!c->rw_on) return GLRTX_OK;
+    seal_feed(c);
+    if (int rc = glrtx_sync(c)) return rc;
+    dev_free(c->rwC);
+    c->rw_on = false;
+    return GLRTX_OK;
+}
+
+// glrtx_render_moments with the other sink: plain launches with sample planes on the context's stream, each folded by accumulate_cascades_kernel into the
+// accumulator and C.
+int glrtx_render_cascades(glrtx_ctx *c, const glrtx_params *p, const float *seeds_xy, int n_frames) {
+    const char *fn = "glrtx_render_cascades";
+    if (!c) return GLRTX_EINVAL;
+    if (int rc = side_plane_check(c, p, seeds_xy, n_frames, fn, c->rw_on, "cascades are not tracked (glrtx_track_cascades)")) return rc;
+    seal_feed(c);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (!cascades_have(c))
+        if (int rc = cascades_ensure(c)) return rc;
+    if (n_frames == 0 || c->owned_rows == 0) { c->st.launches += (uint64_t)n_frames; return GLRTX_OK; }
+    const int rc = render_helpings(c, p, seeds_xy, n_frames, std::min(n_frames, frames_cap(c, p, 1)), RenderReq::Cascades);
+    seal_feed(c);  // (the next render call starts a launch of its own)
+    return rc;
+}
+
+int glrtx_read_cascades(glrtx_ctx *c, float *dst, size_t dst_pitch_bytes) {
+    const char *fn = "glrtx_read_cascades";
+    if (!c || !dst) return GLRTX_EINVAL;
+    if (!c->rw_on) return fail(c, GLRTX_EINVAL, "%s: cascades are not tracked (glrtx_track_cascades)", fn);
+    if (!c->accum || c->width < 1) return fail(c, GLRTX_EINVAL, "%s: no accumulator (call glrtx_resize)", fn);
+    const size_t row = (size_t)c->width * sizeof(float4);
+    if (dst_pitch_bytes < row) return fail(c, GLRTX_EINVAL, "%s: dst pitch too small", fn);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (!cascades_have(c))
+        if (int rc = cascades_ensure(c)) return rc;  // (first use: planes of zeros)
+    if (int rc = glrtx_sync(c)) return rc;
+    if (c->owned_rows == 0) return GLRTX_OK;
+    const size_t plane = c->rw_pitch * (size_t)c->owned_rows;
+    for (int k = 0; k < reweight::kCascades; k++)
+        HIP_TRY(c, hipMemcpy2D((char *)dst + (size_t)k * (size_t)c->owned_rows * dst_pitch_bytes, dst_pitch_bytes, (const char *)c->rwC.p + (size_t)k * plane,
+                               c->rw_pitch, row, (size_t)c->owned_rows, hipMemcpyDeviceToHost));
+    return GLRTX_OK;
+}
+
+// Everything glrtx_reweight refuses, checked before anything changes.
+static int reweight_check(glrtx_ctx *c, const glrtx_reweight_cfg *cfg, const char *fn) {
+    if (int rc = reweight_cfg_check(c, cfg, fn)) return rc;
+    if (!c->rw_on) return fail(c, GLRTX_EINVAL, "%s: cascades are not tracked (glrtx_track_cascades)", fn);
+    if (!c->accum || c->width < 1) return fail(c, GLRTX_EINVAL, "%s: no accumulator (call glrtx_resize)", fn);
+    if (!cascades_have(c)) return fail(c, GLRTX_EINVAL, "%s: no cascade planes yet (call glrtx_render_cascades first)", fn);
+    if (c->world > 1) return fail(c, GLRTX_EINVAL, "%s: the context is partitioned (rank %d of %d): the neighbourhood would stop at every stripe's seam", fn, c->rank, c->world);
+    return GLRTX_OK;
+}
+
+int glrtx_reweight(glrtx_ctx *c, const glrtx_reweight_cfg *cfg) {
+    const char *fn = "glrtx_reweight";
+    if (!c) return GLRTX_EINVAL;
+    if (int rc = reweight_check(c, cfg, fn)) return rc;
+    seal_feed(c);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (int rc = ensure(c, c->dnD, (size_t)c->width * (size_t)std::max(c->owned_rows, 1) * sizeof(float4))) return rc;
+    c->dn_have = true; c->dn_w = c->width; c->dn_rows = c->owned_rows;
+    if (c->owned_rows == 0) return GLRTX_OK;
+    const int pitch_f4 = (int)(c->pitch_bytes / sizeof(float4));
+    return reweight_pass(c, c->stream, (const float4 *)c->rwC.p, (size_t)pitch_f4 * (size_t)c->owned_rows, pitch_f4, c->width, c->owned_rows, (float4 *)c->dnD.p, *cfg);
+}
+
+int glrtx_debug_fold_cascades(const float *accum, const float *cascades, const float *frames, int n_frames, int width, int rows, float start, float *accum_out,
+                              float *cascades_out) {
+    const char *fn = "glrtx_debug_fold_cascades";
+    if (width < 1 || rows < 1 || width > 65536 || rows > 65536) return fail(nullptr, GLRTX_EINVAL, "%s: bad size %dx%d", fn, width, rows);
+    if (!accum || !cascades || n_frames < 0 || (n_frames > 0 && !frames)) return fail(nullptr, GLRTX_EINVAL, "%s: NULL buffer or negative n_frames", fn);
+    if (!cascade_start_ok(start)) return fail(nullptr, GLRTX_EINVAL, "%s: start %g is not within 2^-20 .. 2^20", fn, (double)start);
+    const size_t plane = (size_t)width * rows, bytes = plane * sizeof(float4);
+    DebugScratch s;
+    float4 *acc = s.alloc(bytes, accum), *C = s.alloc(reweight::kCascades * bytes, cascades);
+    const float4 *F = s.alloc(std::max<size_t>((size_t)n_frames, 1) * bytes, n_frames > 0 ? frames : nullptr);
+    if (s.ok() && n_frames > 0) {
+        const accumulate::Image im{acc, width, width, rows};
+        hipLaunchKernelGGL(reweight::accumulate_cascades_kernel, dim3((width + 63) / 64, (rows + 3) / 4), dim3(256), 0, 0, im, accumulate::Planes{F, n_frames, 1},
+                           accumulate::Cascades{C, plane, start});
+        s.e = hipGetLastError();
+    }
+    s.sync();
+    s.download(accum_out, acc, bytes);
+    s.download(cascades_out, C, reweight::kCascades * bytes);
+    return s.result(GLRTX_OK, fn);
+}
+
+int glrtx_debug_reweight(const float *cascades, int width, int rows, const glrtx_reweight_cfg *cfg, float *out) {
+    const char *fn = "glrtx_debug_reweight";
+    if (width < 1 || rows < 1 || width > 65536 || rows > 65536) return fail(nullptr, GLRTX_EINVAL, "%s: bad size %dx%d", fn, width, rows);
+    if (!cascades || !out) return fail(nullptr, GLRTX_EINVAL, "%s: NULL buffer", fn);
+    if (int rc = reweight_cfg_check(nullptr, cfg, fn)) return rc;
+    const size_t plane = (size_t)width * rows, bytes = plane * sizeof(float4);
+    DebugScratch s;
+    const float4 *C = s.alloc(reweight::kCascades * bytes, cascades);
+    float4 *D = s.alloc(bytes);
+    int rc = GLRTX_OK;
+    if (s.ok()) rc = reweight_pass(nullptr, 0, C, plane, width, width, rows, D, *cfg);
+    if (rc == GLRTX_OK) {
+        s.sync();
+        s.download(out, D, bytes);
+    }
+    return s.result(rc, fn);
+}
+
+// Device time of one resolve by itself, as glrtx_debug_tonemap_burst measures its passes.  Writes D as glrtx_reweight does.
+int glrtx_debug_reweight_burst(glrtx_ctx *c, const glrtx_reweight_cfg *cfg, int reps, float *ms_per_launch) {
+    const char *fn = "glrtx_debug_reweight_burst";
+    if (!c || !ms_per_launch || reps < 1) return GLRTX_EINVAL;
+    if (int rc = reweight_check(c, cfg, fn)) return rc;
+    if (c->owned_rows == 0) return fail(c, GLRTX_EINVAL, "%s: no rows", fn);
+    seal_feed(c);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (int rc = ensure(c, c->dnD, (size_t)c->width * (size_t)c->owned_rows * sizeof(float4))) return rc;
+    c->dn_have = true; c->dn_w = c->width; c->dn_rows = c->owned_rows;
+    const int pitch_f4 = (int)(c->pitch_bytes / sizeof(float4));
+    for (int pass = 0; pass < 2; pass++) {  // (the first pass warms the device up)
+        HIP_TRY(c, hipEventRecord(c->rs0, c->stream));
+        for (int i = 0; i < reps; i++)
+            if (int rc = reweight_pass(c, c->stream, (const float4 *)c->rwC.p, (size_t)pitch_f4 * (size_t)c->owned_rows, pitch_f4, c->width, c->owned_rows,
+                                       (float4 *)c->dnD.p, *cfg))
+                return rc;
+        HIP_TRY(c, hipEventRecord(c->rs1, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    float ms = 0.f;
+    HIP_TRY(c, hipEventElapsedTime(&ms, c->rs0, c->rs1));
+    *ms_per_launch = ms / (float)reps;
+    return GLRTX_OK;
 }
 
 // ---- tone mapping
@@ -3462,6 +3664,7 @@ static int reproject_call(glrtx_ctx *c, const glrtx_params *cur, const glrtx_rep
     c->accum = (float4 *)c->accum_own.p;
     c->rp_have = true;
     if (c->adHalf.p && (rc = adapt_half_ensure(c))) return rc;  // H held every second sample of the OLD view's pixels: zeroed, every tile is active again
+    if (c->rwC.p && (rc = cascades_ensure(c))) return rc;  // C held the OLD pixel grid's bins: zeroed like H (carrying it is out of scope)
     if (carry_m) std::swap(c->mmM, c->mmM_spare);  // M is CARRIED, not zeroed like H: a variance is a property of the surface point, and it came along with its mean
     return GLRTX_OK;
 }

@@ -15,7 +15,7 @@
 using namespace glrt;
 
 static void usage(const char *exe) {
-    std::printf("usage: %s -i scene.json [-s N] [--max-depth D] [--spp N] [--frames F] [--frames-in-flight B] [--bvh sah|sah-reinsert|sah-gpu|lbvh|sah-levels-cpu|lbvh-cpu|reference] [--order-by-hits] [--out file.png] [--save-every-frame] [--device G | --gpus N | --devices a,b,..] [--extensions] [--whitted] [--enable-volume] [--volume-wavefront] [--adaptive THRESHOLD | --adaptive-variance THRESHOLD [--min-spp N]] [--denoise | --denoise-variance [--denoise-iters N]] [--tonemap clamp|reinhard|aces [--exposure X] [--auto-exposure]] [--bloom [--bloom-threshold T] [--bloom-strength S] [--bloom-levels N]]\n"
+    std::printf("usage: %s -i scene.json [-s N] [--max-depth D] [--spp N] [--frames F] [--frames-in-flight B] [--bvh sah|sah-reinsert|sah-gpu|lbvh|sah-levels-cpu|lbvh-cpu|reference] [--order-by-hits] [--out file.png] [--save-every-frame] [--device G | --gpus N | --devices a,b,..] [--extensions] [--whitted] [--enable-volume] [--volume-wavefront] [--adaptive THRESHOLD | --adaptive-variance THRESHOLD [--min-spp N]] [--denoise | --denoise-variance [--denoise-iters N]] [--tonemap clamp|reinhard|aces [--exposure X] [--auto-exposure]] [--bloom [--bloom-threshold T] [--bloom-strength S] [--bloom-levels N]] [--reweight [--reweight-kappa K] [--reweight-start S]]\n"
                 "  -i, --input             scene description (JSON; schema: SURVEY.md Appendix C)            [required]\n"
                 "  -s, --sample-per-cycle  accepted for compatibility; like the reference (main.cpp:13) it is not read\n"
                 "      --max-depth D       u_maxDepth (default 16, the reference shader's default)\n"
@@ -57,7 +57,13 @@ static void usage(const char *exe) {
                 "                          --denoise* if given; without --tonemap the curve is clamp (one device; not with --save-every-frame)\n"
                 "      --bloom-threshold T with --bloom: luminance above which a pixel glows, >= 0 (default 1)\n"
                 "      --bloom-strength S  with --bloom: weight of the glow, 0..1e4 (default 0.25)\n"
-                "      --bloom-levels N    with --bloom: pyramid levels, 1..8 (default 5)\n", exe);
+                "      --bloom-levels N    with --bloom: pyramid levels, 1..8 (default 5)\n"
+                "      --reweight          write the firefly re-weighted image: the frames are rendered with glrtx_render_cascades in bursts of --frames-in-flight (at\n"
+                "                          most 1024) frames, every sample binned by luminance, and a brightness level counts only as far as the 3x3 neighbourhood\n"
+                "                          expects it; goes through --bloom / --tonemap as a denoised image does (one device; not with --denoise, --denoise-variance,\n"
+                "                          --adaptive, --adaptive-variance, --enable-volume or --save-every-frame)\n"
+                "      --reweight-kappa K  with --reweight: samples the neighbourhood must hold besides one for a level to count in full, > 0 (default 4)\n"
+                "      --reweight-start S  with --reweight: luminance bound of the first cascade, 2^-20 .. 2^20 (default 1); the others are S * 8^k\n", exe);
 }
 
 int main(int argc, char **argv) {
@@ -72,6 +78,8 @@ int main(int argc, char **argv) {
     float exposure = 1.0f;
     bool exposure_given = false, auto_exposure = false;
     bool bloom = false, bloom_opt = false;
+    bool reweight = false, reweight_opt = false;
+    float reweight_kappa = 4.0f, reweight_start = 1.0f;
     float bloom_threshold = 1.0f, bloom_strength = 0.25f;
     int bloom_levels = 5;
     std::vector<int> devices;
@@ -111,6 +119,9 @@ int main(int argc, char **argv) {
         else if (a == "--exposure") { exposure = (float)std::atof(next("--exposure")); exposure_given = true; }
         else if (a == "--auto-exposure") auto_exposure = true;
         else if (a == "--bloom") bloom = true;
+        else if (a == "--reweight") reweight = true;
+        else if (a == "--reweight-kappa") { reweight_kappa = (float)std::atof(next("--reweight-kappa")); reweight_opt = true; }
+        else if (a == "--reweight-start") { reweight_start = (float)std::atof(next("--reweight-start")); reweight_opt = true; }
         else if (a == "--bloom-threshold") { bloom_threshold = (float)std::atof(next("--bloom-threshold")); bloom_opt = true; }
         else if (a == "--bloom-strength") { bloom_strength = (float)std::atof(next("--bloom-strength")); bloom_opt = true; }
         else if (a == "--bloom-levels") { bloom_levels = std::atoi(next("--bloom-levels")); bloom_opt = true; }
@@ -142,6 +153,19 @@ int main(int argc, char **argv) {
         std::fprintf(stderr, "--denoise-variance: --frames-in-flight %d is above the 1024 frames one glrtx_render_moments burst takes\n", in_flight);
         return 1;
     }
+    if (reweight_opt && !reweight) { std::fprintf(stderr, "--reweight-kappa and --reweight-start need --reweight\n"); return 1; }
+    if (reweight && (denoise || denoise_variance || adaptive || adaptive_variance || volume || every_frame || devices.size() > 1)) {
+        std::fprintf(stderr, "--reweight: one device, and not with --denoise, --denoise-variance, --adaptive, --adaptive-variance, --enable-volume or --save-every-frame\n");
+        return 1;
+    }
+    if (reweight && (!(reweight_kappa > 0.0f) || std::isinf(reweight_kappa) || !(reweight_start >= 0x1p-20f && reweight_start <= 0x1p20f))) {
+        std::fprintf(stderr, "--reweight: --reweight-kappa must be a positive finite number and --reweight-start within 2^-20 .. 2^20\n");
+        return 1;
+    }
+    if (reweight && in_flight > 1024) {  // (a burst is one glrtx_render_cascades call, as --denoise-variance's is one glrtx_render_moments call)
+        std::fprintf(stderr, "--reweight: --frames-in-flight %d is above the 1024 frames one glrtx_render_cascades burst takes\n", in_flight);
+        return 1;
+    }
     if (bloom_opt && !bloom) { std::fprintf(stderr, "--bloom-threshold, --bloom-strength and --bloom-levels need --bloom\n"); return 1; }
     if (bloom && (every_frame || devices.size() > 1 || !(bloom_threshold >= 0.0f) || std::isinf(bloom_threshold) || !(bloom_strength >= 0.0f && bloom_strength <= 1.0e4f) ||
                   bloom_levels < 1 || bloom_levels > 8)) {
@@ -170,6 +194,7 @@ int main(int argc, char **argv) {
     if (denoise_variance) window->setDenoiseVariance(denoise_iters);
     if (tonemap_op >= 0) window->setTonemap(tonemap_op, exposure, auto_exposure);
     if (bloom) window->setBloom(bloom_threshold, bloom_strength, bloom_levels);
+    if (reweight) window->setReweight(reweight_kappa, reweight_start);
 
     auto scene = std::make_shared<Scene>();
     if (!bvh.empty()) scene->setBvhBuilder(bvh);

@@ -189,6 +189,25 @@ void Window::mainloop(const std::shared_ptr<Scene> &scene_, double fps) {
         if (!output_.empty() && frameLimit_ > 0) saveCurrentFrame(output_, true);
         return;
     }
+    if (reweight_) {
+        // Firefly re-weighting: the frames in bursts of framesInFlight_ through glrtx_render_cascades, which splits every sample over the cascade planes as well.
+        if (glrtx_group_size(grp_) != 1 || denoise_ || denoiseVar_ || adaptive_) GLRT_FatalError("--reweight: one device, and not with --denoise, --denoise-variance or --adaptive*");
+        glrtx_ctx *c0 = glrtx_group_ctx(grp_, 0);
+        if (glrtx_track_cascades(c0, 1, reweightStart_) != GLRTX_OK) GLRT_FatalError("glrtx_track_cascades: %s", glrtx_last_error(c0));
+        glrtx_params p;
+        frameParams(p);
+        for (int issued = 0; issued < frameLimit_;) {
+            const int n = frameLimit_ - issued < framesInFlight_ ? frameLimit_ - issued : framesInFlight_;
+            std::vector<float> seeds(2 * (size_t)n);
+            for (int f = 0; f < n; f++) glrt_frame_seed(frame_++, &seeds[2 * (size_t)f]);
+            if (glrtx_render_cascades(c0, &p, seeds.data(), n) != GLRTX_OK) GLRT_FatalError("glrtx_render_cascades: %s", glrtx_last_error(c0));
+            issued += n;
+        }
+        GLRTX_CHECK(glrtx_group_sync(grp_));
+        lastMs_ = frameLimit_ > 0 ? std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() / frameLimit_ : 0.0;
+        if (!output_.empty() && frameLimit_ > 0) saveCurrentFrame(output_, true);
+        return;
+    }
     if (adaptive_) {
         // Adaptive sampling: every burst re-selects the tiles that are still active (from the accumulator as it stands) and renders its frames on those only; the
         // count the burst was issued on is reported after it.  A burst that found no active tile rendered nothing: the run ends there.
@@ -287,7 +306,11 @@ void Window::saveCurrentFrame(const std::string &filename, bool overwrite) const
     if (tonemap_ || bloom_) {  // --tonemap / --bloom: the denoised image if one was asked for, else the accumulator, through the exposure and the tone curve (one device: checked in mainloop)
         glrtx_ctx *c0 = glrtx_group_ctx(grp_, 0);
         glrtx_tonemap_cfg cfg = tonemapCfg_;
-        cfg.source = (denoise_ || denoiseVar_) ? 1 : 0;
+        cfg.source = (denoise_ || denoiseVar_ || reweight_) ? 1 : 0;
+        if (reweight_) {
+            if (glrtx_reweight(c0, &reweightCfg_) != GLRTX_OK) GLRT_FatalError("glrtx_reweight: %s", glrtx_last_error(c0));
+            GLRT_Info("Reweight: kappa %g, start %g", (double)reweightCfg_.kappa, (double)reweightStart_);
+        }
         if (denoise_ && glrtx_denoise(c0, &denoiseCfg_) != GLRTX_OK) GLRT_FatalError("glrtx_denoise: %s", glrtx_last_error(c0));
         if (denoiseVar_ && glrtx_denoise_variance(c0, &denoiseVarCfg_) != GLRTX_OK) GLRT_FatalError("glrtx_denoise_variance: %s", glrtx_last_error(c0));
         if (cfg.auto_exposure && glrtx_exposure_measure(c0, &cfg) != GLRTX_OK) GLRT_FatalError("glrtx_exposure_measure: %s", glrtx_last_error(c0));
@@ -321,6 +344,11 @@ void Window::saveCurrentFrame(const std::string &filename, bool overwrite) const
         if (glrtx_denoise_variance(c0, &denoiseVarCfg_) != GLRTX_OK || glrtx_resolve_denoised_rgba8(c0, bytes.data(), (size_t)width_ * 4, 2.2f, 1) != GLRTX_OK)
             GLRT_FatalError("glrtx_denoise_variance: %s", glrtx_last_error(c0));
         GLRT_Info("Denoise (variance-guided): %d iterations", denoiseVarCfg_.iterations);
+    } else if (reweight_) {  // the re-weighted image through the same resolve
+        glrtx_ctx *c0 = glrtx_group_ctx(grp_, 0);
+        if (glrtx_reweight(c0, &reweightCfg_) != GLRTX_OK || glrtx_resolve_denoised_rgba8(c0, bytes.data(), (size_t)width_ * 4, 2.2f, 1) != GLRTX_OK)
+            GLRT_FatalError("glrtx_reweight: %s", glrtx_last_error(c0));
+        GLRT_Info("Reweight: kappa %g, start %g", (double)reweightCfg_.kappa, (double)reweightStart_);
     } else if (glrtx_group_resolve_rgba8(grp_, bytes.data(), (size_t)width_ * 4, 2.2f, 1) != GLRTX_OK)
         GLRT_FatalError("glrtx_group_resolve_rgba8: %s", glrtx_group_last_error(grp_));
     saveImage(filename, overwrite, bytes.data());

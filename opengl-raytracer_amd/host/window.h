@@ -68,6 +68,9 @@ public:
     // Bloom in front of the curve (glrtx_bloom / glrtx_resolve_bloomed_rgba8, one device only): the saved image is B -- the denoised image when a denoiser is on,
     // else the accumulator, plus the glow -- through the tone curve (clamp at exposure 1 without setTonemap).  Without it the saved image is what it was.
     void setBloom(float threshold, float strength, int levels) { bloom_ = true; bloomCfg_.threshold = threshold; bloomCfg_.strength = strength; bloomCfg_.levels = levels; }
+    // Firefly re-weighting (glrtx_track_cascades / glrtx_render_cascades / glrtx_reweight, one device only): the frames are rendered in bursts of framesInFlight
+    // frames with the cascade fold, and the saved image is the re-weighted one (through setBloom / setTonemap as a denoised image would go).
+    void setReweight(float kappa, float start) { reweight_ = true; reweightCfg_.kappa = kappa; reweightStart_ = start; }
     void setDenoiseVariance(int iterations) { denoiseVar_ = true; if (iterations >= 1) denoiseVarCfg_.iterations = iterations; }
     // wall-clock ms PER FRAME between the last two waits for the device, averaged over the frames issued in between (with one PNG per run: the whole run, cold first
     // launches included; with --save-every-frame: the whole run, PNG writing included).  The device's own time of the last launch is glrtx_stats.kernel_ms_last.
@@ -103,6 +106,9 @@ private:
     int adaptMinSamples_ = 2;
     bool volumeWavefront_ = false;
     bool denoise_ = false, denoiseVar_ = false;
+    bool reweight_ = false;
+    glrtx_reweight_cfg reweightCfg_ = {4.0f};  // (glrt_amd.host.REWEIGHT_DEFAULTS holds the same)
+    float reweightStart_ = 1.0f;
     bool tonemap_ = false;
     bool bloom_ = false;
     glrtx_bloom_cfg bloomCfg_ = {0, 1.0f, 0.25f, 5};  // (glrt_amd.host.BLOOM_DEFAULTS holds the same)

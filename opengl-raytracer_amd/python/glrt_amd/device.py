@@ -119,6 +119,16 @@ def _bloom_cfg(cfg, fields) -> BloomCfg:
     return cfg if cfg is not None else BloomCfg.default(**fields)
 
 
+class ReweightCfg(C.Structure):
+    """glrtx_reweight_cfg (include/glrtx.h "Firefly re-weighting"); reweight_cfg() holds glrt_amd.host.REWEIGHT_DEFAULTS."""
+    _fields_ = [("kappa", C.c_float)]
+
+
+def reweight_cfg(kappa=None) -> ReweightCfg:
+    from .host import REWEIGHT_DEFAULTS
+    return ReweightCfg(float(REWEIGHT_DEFAULTS["kappa"] if kappa is None else kappa))
+
+
 class Image(C.Structure):
     _fields_ = [("rgba", C.c_void_p), ("pitch_bytes", C.c_size_t), ("width", C.c_int32), ("rows", C.c_int32), ("frame", C.c_uint64)]
 
@@ -161,7 +171,9 @@ EXPORTS = ["glrtx_abi_version", "glrtx_create", "glrtx_destroy", "glrtx_last_err
            "glrtx_debug_reproject_moments", "glrtx_debug_reproject_motion_moments", "glrtx_render_adaptive_moments", "glrtx_debug_adaptive_select_moments",
            "glrtx_exposure_measure", "glrtx_exposure_reset", "glrtx_read_exposure", "glrtx_tonemap", "glrtx_read_tonemapped", "glrtx_resolve_tonemapped_rgba8",
            "glrtx_debug_tonemap", "glrtx_debug_tonemap_burst",
-           "glrtx_bloom", "glrtx_read_bloomed", "glrtx_tonemap_bloomed", "glrtx_resolve_bloomed_rgba8", "glrtx_debug_bloom", "glrtx_debug_bloom_burst"]
+           "glrtx_bloom", "glrtx_read_bloomed", "glrtx_tonemap_bloomed", "glrtx_resolve_bloomed_rgba8", "glrtx_debug_bloom", "glrtx_debug_bloom_burst",
+           "glrtx_track_cascades", "glrtx_render_cascades", "glrtx_read_cascades", "glrtx_reweight", "glrtx_debug_fold_cascades", "glrtx_debug_reweight",
+           "glrtx_debug_reweight_burst"]
 
 SCENE_BUFFERS = ("nodes", "cnodes", "nrms", "lights", "vine", "root")  # glrtx_debug_read_scene's `which`, in order (GLRTX_SCENE_*)
 
@@ -326,6 +338,17 @@ def lib():
             L.glrtx_resolve_bloomed_rgba8.argtypes = [vp, vp, C.c_size_t, tc]
             L.glrtx_debug_bloom.argtypes = [fp, C.c_int, C.c_int, bc, fp, fp]
             L.glrtx_debug_bloom_burst.argtypes = [vp, bc, C.c_int, C.POINTER(C.c_float)]
+        except AttributeError:
+            pass
+        try:  # (additive to ABI 10 as well: firefly re-weighting)
+            rc = C.POINTER(ReweightCfg)
+            L.glrtx_track_cascades.argtypes = [vp, C.c_int, C.c_float]
+            L.glrtx_render_cascades.argtypes = [vp, C.POINTER(Params), fp, C.c_int]
+            L.glrtx_read_cascades.argtypes = [vp, vp, C.c_size_t]
+            L.glrtx_reweight.argtypes = [vp, rc]
+            L.glrtx_debug_fold_cascades.argtypes = [fp, fp, fp, C.c_int, C.c_int, C.c_int, C.c_float, fp, fp]
+            L.glrtx_debug_reweight.argtypes = [fp, C.c_int, C.c_int, rc, fp]
+            L.glrtx_debug_reweight_burst.argtypes = [vp, rc, C.c_int, C.POINTER(C.c_float)]
         except AttributeError:
             pass
         _lib = L
@@ -513,6 +536,36 @@ def debug_bloom(src, cfg=None, **fields):
     if rc != 0:
         raise GlrtxError(rc, L.glrtx_last_error(None).decode())
     return d, b
+
+
+def debug_fold_cascades(accum, cascades, frames, start=None):
+    """glrtx_debug_fold_cascades on the current device: the accumulation pass with the cascade sink on packed arrays -- accum (rows, width, 4), cascades
+    (6, rows, width, 4), frames (n, rows, width, 4), one sample each.  Returns (accum_out, cascades_out)."""
+    from .host import REWEIGHT_DEFAULTS
+    L = lib()
+    a, c, f = _f32(accum), _f32(cascades), _f32(frames)
+    if a.ndim != 3 or a.shape[2] != 4 or c.shape != (6,) + a.shape or f.ndim != 4 or f.shape[1:] != a.shape:
+        raise ValueError(f"debug_fold_cascades: (rows, width, 4), (6, rows, width, 4) and (n, rows, width, 4) expected, got {a.shape}, {c.shape}, {f.shape}")
+    ao, co = np.zeros_like(a), np.zeros_like(c)
+    rc = L.glrtx_debug_fold_cascades(_fp(a), _fp(c), _fp(f) if f.shape[0] else None, f.shape[0], a.shape[1], a.shape[0],
+                                     float(REWEIGHT_DEFAULTS["start"] if start is None else start), _fp(ao), _fp(co))
+    if rc != 0:
+        raise GlrtxError(rc, L.glrtx_last_error(None).decode())
+    return ao, co
+
+
+def debug_reweight(cascades, cfg=None, kappa=None):
+    """glrtx_debug_reweight on the current device: the resolve kernel on cascade planes (6, rows, width, 4).  Returns D (rows, width, 4) float32."""
+    L = lib()
+    c = _f32(cascades)
+    if c.ndim != 4 or c.shape[0] != 6 or c.shape[3] != 4:
+        raise ValueError(f"debug_reweight: cascades must be (6, rows, width, 4), got {c.shape}")
+    k = cfg if cfg is not None else reweight_cfg(kappa)
+    out = np.zeros(c.shape[1:], np.float32)
+    rc = L.glrtx_debug_reweight(_fp(c), c.shape[2], c.shape[1], C.byref(k), _fp(out))
+    if rc != 0:
+        raise GlrtxError(rc, L.glrtx_last_error(None).decode())
+    return out
 
 
 def debug_reproject(accum, n0, a0, n1, a1, prev, cur, **cfg):
@@ -938,6 +991,32 @@ class Device:
         is read with read_denoised / resolve_denoised_rgba8.  None: the default."""
         c = denoise_var_cfg(iterations, sigma_lum, sigma_normal, sigma_depth, demodulate)
         self._ck(self.L.glrtx_denoise_variance(self.h, C.byref(c)))
+    def track_cascades(self, enable=True, start=None):
+        """Keep the six luminance cascade planes C beside the accumulator, with bounds start * 8^k (glrtx_track_cascades); off by default, switching it off
+        releases C, another start zeroes it."""
+        from .host import REWEIGHT_DEFAULTS
+        self._ck(self.L.glrtx_track_cascades(self.h, int(bool(enable)), float(REWEIGHT_DEFAULTS["start"] if start is None else start)))
+    def render_cascades(self, params, seeds):
+        """render_frames that also splits every sample by luminance over the cascade planes C (glrtx_render_cascades); the accumulator is render_frames'."""
+        p = params if isinstance(params, Params) else make_params(dict(params, seed=(0.0, 0.0)) if "seed" not in params else params)
+        sd = _f32(np.asarray(seeds, np.float32).reshape(-1, 2))
+        self._ck(self.L.glrtx_render_cascades(self.h, C.byref(p), _fp(sd), sd.shape[0]))
+    def read_cascades(self) -> np.ndarray:
+        """The cascade planes C {sum w r, sum w g, sum w b, count}, (6, owned_rows, width, 4) float32 (syncs)."""
+        s = self.stats()
+        out = np.zeros((6, s.owned_rows, s.width, 4), np.float32)
+        self._ck(self.L.glrtx_read_cascades(self.h, out.ctypes.data, s.width * 16))
+        return out
+    def reweight(self, cfg=None, kappa=None):
+        """The firefly re-weighting resolve of C into the image D (glrtx_reweight); the result is read with read_denoised / resolve_denoised_rgba8 and is
+        source = 1 of the tone-mapping and bloom calls.  None: the default."""
+        k = cfg if cfg is not None else reweight_cfg(kappa)
+        self._ck(self.L.glrtx_reweight(self.h, C.byref(k)))
+    def reweight_burst_ms(self, reps=20, cfg=None, kappa=None) -> float:
+        k = cfg if cfg is not None else reweight_cfg(kappa)
+        ms = C.c_float()
+        self._ck(self.L.glrtx_debug_reweight_burst(self.h, C.byref(k), int(reps), C.byref(ms)))
+        return float(ms.value)
     def reproject(self, params, max_history=None, depth_tolerance=None, normal_tolerance=None):
         """Carry the accumulator from the camera of the last render_features / reproject to `params`' camera (glrtx_reproject); None: the default.  The
         accumulator's device address changes; the feature planes are `params`' afterwards."""

@@ -54,6 +54,8 @@ def lib():
         L.glrt_exposure_measure.argtypes = [fp, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_float, fp, u32p, u64p, u64p, fp, fp, fp]
         L.glrt_tonemap.argtypes = [fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, fp, C.POINTER(C.c_uint8)]
         L.glrt_bloom.argtypes = [fp, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, fp, fp]
+        L.glrt_fold_cascades.argtypes = [fp, fp, fp, C.c_int, C.c_int, C.c_int, C.c_float]
+        L.glrt_reweight.argtypes = [fp, C.c_int, C.c_int, C.c_float, fp]
         L.glrt_look_at.argtypes = [fp, fp, fp, fp]
         L.glrt_perspective.argtypes = [C.c_float, C.c_float, C.c_float, C.c_float, fp]
         L.glrt_mat4_mul.argtypes = [fp, fp, fp]
@@ -354,6 +356,39 @@ def bloom(src, threshold=BLOOM_DEFAULTS["threshold"], strength=BLOOM_DEFAULTS["s
     if rc != 0:
         raise RuntimeError(f"glrt_bloom failed: {rc}")
     return d, b
+
+
+REWEIGHT_DEFAULTS = dict(kappa=4.0, start=1.0)
+
+
+def fold_cascades(cascades, planes, accum=None, start=REWEIGHT_DEFAULTS["start"]):
+    """glrt_fold_cascades: the sample planes (k, rows, width, 4), in order, folded into a copy of the cascade planes C (6, rows, width, 4) {sum w rgb, count}
+    (None: zeros) and, with `accum` (rows, width, 4), into a copy of that accumulator as the device's pass does.  Returns C, or (C, accumulator) with `accum`."""
+    p = _f32(planes)
+    if p.ndim != 4 or p.shape[3] != 4:
+        raise ValueError(f"fold_cascades: planes (k, rows, width, 4) expected, got {p.shape}")
+    c = np.zeros((6,) + p.shape[1:], np.float32) if cascades is None else _f32(cascades).copy()
+    if c.shape != (6,) + p.shape[1:]:
+        raise ValueError(f"fold_cascades: cascades (6, rows, width, 4) matching the planes expected, got {c.shape} and {p.shape}")
+    a = None if accum is None else _f32(accum).copy()
+    if a is not None and a.shape != p.shape[1:]:
+        raise ValueError(f"fold_cascades: accum (rows, width, 4) matching the planes expected, got {a.shape}")
+    rc = lib().glrt_fold_cascades(_fp(c), None if a is None else _fp(a), _fp(p), p.shape[0], p.shape[2], p.shape[1], float(start))
+    if rc != 0:
+        raise RuntimeError(f"glrt_fold_cascades failed: {rc}")
+    return c if a is None else (c, a)
+
+
+def reweight(cascades, kappa=REWEIGHT_DEFAULTS["kappa"]):
+    """glrt_reweight: the CPU statement of Device.reweight on cascade planes (6, rows, width, 4).  Returns D (rows, width, 4) float32 {rgb, 1}."""
+    c = _f32(cascades)
+    if c.ndim != 4 or c.shape[0] != 6 or c.shape[3] != 4:
+        raise ValueError(f"reweight: cascades must be (6, rows, width, 4), got {c.shape}")
+    out = np.empty(c.shape[1:], np.float32)
+    rc = lib().glrt_reweight(_fp(c), c.shape[2], c.shape[1], float(kappa), _fp(out))
+    if rc != 0:
+        raise RuntimeError(f"glrt_reweight failed: {rc}")
+    return out
 
 
 REPROJECT_DEFAULTS = dict(max_history=32, depth_tolerance=0.02, normal_tolerance=0.9)
