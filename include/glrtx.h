@@ -712,8 +712,8 @@ int glrtx_debug_reproject(const float *accum, const float *n0, const float *a0, 
  *        of a turned object says nothing about its old one).
  *     6, 7  unchanged.
  * Out of scope: changes of topology; spheres and the volume; specular history (carried as if it were diffuse); lighting that changes because geometry moved
- * (shading near a moved object's shadow stays stale until new samples outweigh it); partitioned contexts and groups; glrt_main has no animation, so the facade
- * calls none of this. */
+ * (shading near a moved object's shadow stays stale until new samples outweigh it); partitioned contexts and groups.  The facade calls this from
+ * glrt_main --animate --carry-history ("Posing" below; host/window.h: setAnimation). */
 int glrtx_track_motion(glrtx_ctx *ctx, int enable);
 int glrtx_read_features_geom(glrtx_ctx *ctx, float *geom, size_t pitch_bytes);
 int glrtx_reproject_motion(glrtx_ctx *ctx, const glrtx_params *cur, const glrtx_reproject_cfg *cfg);
@@ -907,6 +907,53 @@ int glrtx_debug_fold_cascades(const float *accum, const float *cascades, const f
                               float *cascades_out);
 int glrtx_debug_reweight(const float *cascades, int width, int rows, const glrtx_reweight_cfg *cfg, float *out);
 int glrtx_debug_reweight_burst(glrtx_ctx *ctx, const glrtx_reweight_cfg *cfg, int reps, float *ms_per_launch);
+
+/* ---- Posing: rigid objects and linear-blend skinning on the device, in front of the refit (no reference counterpart; off unless called: no other call's
+ * behaviour changes).  "Object 3 turned by this matrix" without the host touching a vertex: the rest pose stays on the device, a pose is a few matrices, and
+ * one pass (csrc/skin.hip.h) writes the posed vertices where glrtx_update_vertices would have copied them.  A rigid object is the one-bone case.
+ *
+ * A RIG belongs to the uploaded scene.  It holds
+ *   - the rest pose: n_vert wire vertices of GLRT_VERTEX_FLOATS = 15 floats each {pos, normal, uv, tangent, binormal};
+ *   - per vertex four bone indices int32 b[4] and four weights float w[4];
+ *   - a bone count n_bones, between 1 and 65536.
+ * A POSE is n_bones matrices of 12 floats, row-major 3x4: m[i][0..2] is the linear part, m[i][3] the translation.
+ *
+ * Arithmetic.  Every operation is a single fp32 operation, correctly rounded and unfused.  Denormals count as zeros of their sign into and out of every
+ * operation (the library's flags; tests/adaptive_math.py: _op, ftz).  A NaN that is stored is 0x7FC00000.  dot(a, v) is (a2 v.z + a1 v.y) + a0 v.x, the
+ * project's order.  Per vertex:
+ *   Blend     B[i][j] = ((w0 M_b0[i][j] + w1 M_b1[i][j]) + w2 M_b2[i][j]) + w3 M_b3[i][j], all twelve entries.  All four terms are always formed, so the
+ *             operation sequence does not depend on the data.
+ *   Position  pos'[i] = dot(B[i][0..2], pos) + B[i][3].
+ *   Cofactor matrix.  With L = B[:, 0..2], each entry of C is two rounded products and one subtraction:
+ *               C00 = L11 L22 - L12 L21    C01 = L12 L20 - L10 L22    C02 = L10 L21 - L11 L20
+ *               C10 = L21 L02 - L22 L01    C11 = L22 L00 - L20 L02    C12 = L20 L01 - L21 L00
+ *               C20 = L01 L12 - L02 L11    C21 = L02 L10 - L00 L12    C22 = L00 L11 - L01 L10
+ *             (rows 1 and 2 are row 0 with the row indices advanced cyclically).  C equals det(L) L^-T: it turns a normal the way the transformed triangle's
+ *             own cross product turns -- (L a) x (L b) = C (a x b) --, reflections included, so a posed normal stays on the side of the posed face it was on.
+ *   Normal    v[i] = dot(C[i], normal);  s = dot(v, v);  l = sqrt(s) (IEEE);  normal' = l > 0 ? v / l : v, three IEEE quotients.
+ *   Tangent and binormal  tangent'[i] = dot(L[i], tangent), binormal' likewise.  Neither is normalised; the renderer reads neither.
+ *   uv        its three words are moved as integers.
+ * It follows that a vertex with w = {1, 0, 0, 0} and finite matrices gets B == M_b0 up to the sign of a zero, and that the identity pose returns positions,
+ * tangents and binormals unchanged (up to the sign of a zero; denormals as zeros).  Normals come back renormalised, which can differ from the input in the last
+ * place.  The CPU statement is glrt_skin_vertices (include/glrt_host.h), bit for bit.
+ *
+ *   glrtx_upload_rig  keeps the rest pose and the rig on the device.  GLRTX_EINVAL, nothing changed: no scene, n_vert other than the scene's, a NULL pointer,
+ *                     n_bones outside 1..65536, a bone index outside [0, n_bones), a non-finite weight.  glrtx_upload_scene forgets the rig;
+ *                     glrtx_update_vertices / _device keep it: the rest pose is the rig's own copy, not the scene's vertices.
+ *   glrtx_pose        uploads the matrices (n_bones x 48 bytes), runs the skinning kernel into the context's vertex buffer and then takes exactly
+ *                     glrtx_update_vertices_device's path: an open fed launch is sealed, the motion snapshot is taken if glrtx_track_motion asks for one, the
+ *                     refit runs behind every launch that may still read the scene, and the call returns when it has run.  Afterwards every device scene buffer
+ *                     is byte for byte what glrtx_update_vertices(ctx, glrt_skin_vertices(...)) leaves.  GLRTX_EINVAL, nothing changed: no rig, a bone count
+ *                     other than the rig's, a NULL pointer, a non-finite matrix entry (the entries are checked on the host before anything is issued).
+ *   glrtx_debug_skin  the kernel alone on host arrays on the current HIP device, no context: vert_out gets n_vert wire vertices.  Refuses what glrt_skin_vertices
+ *                     refuses (weights and matrices are not checked: the hook takes whatever the kernel can be handed).
+ *   glrtx_debug_skin_burst  device time of the kernel by itself from `reps` launches back to back between one pair of events after a warm-up pass (the rig with
+ *                     the last pose's matrices into the vertex buffer, which holds exactly that already).  GLRTX_EINVAL before a first glrtx_pose.
+ * Groups: no call.  Pose a member through glrtx_group_ctx(grp, i).  glrtx_pose blocks as glrtx_update_vertices does, for the same read-back words. */
+int glrtx_upload_rig(glrtx_ctx *ctx, const float *rest_vert, size_t n_vert, const int32_t *bones4, const float *weights4, int n_bones);
+int glrtx_pose(glrtx_ctx *ctx, const float *matrices, int n_bones);
+int glrtx_debug_skin(const float *rest, size_t n_vert, const int32_t *bones4, const float *weights4, const float *matrices, int n_bones, float *vert_out);
+int glrtx_debug_skin_burst(glrtx_ctx *ctx, int reps, float *ms_per_launch);
 
 /* ---- Groups: the same device layer on several GPUs of one node, behind one handle and one host thread.
  * No reference counterpart (the reference is single-GPU); SURVEY.md 8(b) sketches glrtx_create(ctx**, device_ids, n) with a

@@ -23,6 +23,7 @@
 #include "lbvh.hip.h"
 #include "sahl.hip.h"
 #include "refit.hip.h"
+#include "skin.hip.h"
 #include "query.hip.h"
 #include "features.hip.h"
 #include "denoise.hip.h"
@@ -153,6 +154,12 @@ struct glrtx_ctx {
         size_t bytes[5] = {0, 0, 0, 0, 0};  // the scene buffers' sizes as uploaded: nodes, cnodes, nrms, lights, vine (glrtx_debug_read_scene)
         hipEvent_t slot_ev = nullptr;      // recorded on each pipe slot's stream: the refit starts behind every launch that may still read the scene
     } rf;
+    // The rig (glrtx_upload_rig; skin.hip.h), the scene's until the next glrtx_upload_scene: the rest pose, the {bones, weights} records and the pose matrices of
+    // the last glrtx_pose.  n_bones == 0: no rig.
+    struct Rig {
+        DevBuf rest, rig, pose;
+        int n_bones = 0;
+    } sk;
 
     // Presentation (glrtx_present_enable): frame seq of the ring goes to image seq % ring -- device image (written by the presenting pass on the context's stream),
     // then pinned host image (copied on `copy`, behind pass_done, ending with the image's event).  An image is taken for a frame only while it is FREE: released by the
@@ -2107,6 +2114,7 @@ void glrtx_destroy(glrtx_ctx *c) {
     dev_free(c->wfState); dev_free(c->wfQ); dev_free(c->wfSeeds); dev_free(c->wfPlanes);
     dev_free(c->bvhVert); dev_free(c->bvhTri); dev_free(c->bvhNodes);
     dev_free(c->rf.ints); dev_free(c->rf.keys); dev_free(c->rf.vert);
+    dev_free(c->sk.rest); dev_free(c->sk.rig); dev_free(c->sk.pose);
     dev_free(c->qwire); dev_free(c->qcounter); dev_free(c->qrays); dev_free(c->qhits);
     if (c->rf.slot_ev) (void)hipEventDestroy(c->rf.slot_ev);
     if (c->bvhWs.p) { (void)hipFree(c->bvhWs.p); c->bvhWs.p = nullptr; c->bvhWs.bytes = 0; }
@@ -2193,6 +2201,8 @@ int glrtx_upload_scene(glrtx_ctx *c, const float *vert, size_t n_vert, const flo
     c->n_spheres = 0;  // spheres reference this scene's materials: upload them again after a new scene
     dev_free(c->mtPos); dev_free(c->mtNrm);  // (glrtx_track_motion: the previous geometry was another scene's; the stream is idle)
     c->mt_geom = glrtx_ctx::kMtNone;
+    dev_free(c->sk.rest); dev_free(c->sk.rig); dev_free(c->sk.pose);  // (glrtx_upload_rig: the rig was another scene's)
+    c->sk.n_bones = 0;
     c->st.stack_entries = stack_need;
     c->st.lds_bytes = lds_bytes_for(sc);
     c->st.n_tri = c->n_tri; c->st.n_fork = c->n_fork; c->st.n_mat = c->n_mat; c->st.n_light = c->n_light;
@@ -2285,6 +2295,123 @@ int glrtx_update_vertices_device(glrtx_ctx *c, const void *dev_vert, size_t n_ve
     if (c->mt_on && c->mt_geom == glrtx_ctx::kMtCurrent)
         if (int rc = motion_snapshot(c)) return rc;
     return refit_run(c, dev_vert);
+}
+
+namespace {
+
+// ---- posing (glrtx_upload_rig, glrtx_pose, glrtx_debug_skin; skin.hip.h)
+bool all_finite(const float *v, size_t n) {
+    for (size_t k = 0; k < n; k++)
+        if (!std::isfinite(v[k])) return false;
+    return true;
+}
+
+// What the rig calls refuse alike; weights are the context call's to check (the debug hook takes any).
+int rig_check(glrtx_ctx *c, const void *rest, size_t n_vert, const int32_t *bones4, const float *weights4, int n_bones, const char *fn) {
+    if (n_bones < 1 || n_bones > GLRT_MAX_BONES) return fail(c, GLRTX_EINVAL, "%s: %d bones (1 .. %d)", fn, n_bones, GLRT_MAX_BONES);
+    if (n_vert >= ((size_t)1 << 31)) return fail(c, GLRTX_EINVAL, "%s: %zu vertices (at most 2^31 - 1)", fn, n_vert);
+    if (n_vert > 0 && (!rest || !bones4 || !weights4)) return fail(c, GLRTX_EINVAL, "%s: NULL buffer", fn);
+    for (size_t k = 0; k < 4 * n_vert; k++)
+        if (bones4[k] < 0 || bones4[k] >= n_bones) return fail(c, GLRTX_EINVAL, "%s: vertex %zu names bone %d of %d", fn, k / 4, (int)bones4[k], n_bones);
+    return GLRTX_OK;
+}
+
+// The kernel's rig records: {b0, b1, b2, b3} {w0, w1, w2, w3} a vertex, 32 bytes
+void rig_records(std::vector<uint4> &r, size_t n_vert, const int32_t *bones4, const float *weights4) {
+    r.resize(2 * n_vert);
+    for (size_t i = 0; i < n_vert; i++) {
+        std::memcpy(&r[2 * i], bones4 + 4 * i, sizeof(uint4));
+        std::memcpy(&r[2 * i + 1], weights4 + 4 * i, sizeof(uint4));
+    }
+}
+
+void skin_launch(const skin::Args &a, hipStream_t stream) {
+    if (a.n_vert == 0) return;
+    hipLaunchKernelGGL(skin::skin_kernel, dim3((unsigned)((a.n_vert + skin::kBlock - 1) / skin::kBlock)), dim3(skin::kBlock), 0, stream, a);
+}
+
+}  // namespace
+
+int glrtx_upload_rig(glrtx_ctx *c, const float *rest_vert, size_t n_vert, const int32_t *bones4, const float *weights4, int n_bones) {
+    const char *fn = "glrtx_upload_rig";
+    if (int rc = update_check(c, rest_vert, n_vert, fn)) return rc;
+    if (int rc = rig_check(c, rest_vert, n_vert, bones4, weights4, n_bones, fn)) return rc;
+    if (!all_finite(weights4, 4 * n_vert)) return fail(c, GLRTX_EINVAL, "%s: a weight is not finite", fn);
+    std::vector<uint4> rig;
+    rig_records(rig, n_vert, bones4, weights4);
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));  // (a glrtx_pose's kernel has run: glrtx_pose blocks; this orders the frees behind anything else on the stream)
+    c->sk.n_bones = 0;  // (until all three buffers are in place)
+    if (int rc = dev_upload(c, c->sk.rest, rest_vert, n_vert * skin::kVertexWords * sizeof(float))) return rc;
+    if (int rc = dev_upload(c, c->sk.rig, rig.data(), rig.size() * sizeof(uint4))) return rc;
+    if (int rc = ensure(c, c->sk.pose, (size_t)n_bones * 12 * sizeof(float))) return rc;
+    c->sk.n_bones = n_bones;
+    return GLRTX_OK;
+}
+
+int glrtx_pose(glrtx_ctx *c, const float *matrices, int n_bones) {
+    const char *fn = "glrtx_pose";
+    if (!c) return GLRTX_EINVAL;
+    if (!c->have_scene || c->sk.n_bones == 0) return fail(c, GLRTX_EINVAL, "%s: no rig uploaded (glrtx_upload_rig)", fn);
+    if (n_bones != c->sk.n_bones) return fail(c, GLRTX_EINVAL, "%s: %d matrices, the rig has %d bones", fn, n_bones, c->sk.n_bones);
+    if (!matrices) return fail(c, GLRTX_EINVAL, "%s: NULL matrices", fn);
+    if (!all_finite(matrices, (size_t)n_bones * 12)) return fail(c, GLRTX_EINVAL, "%s: a matrix entry is not finite", fn);
+    seal_feed(c);
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t n_vert = c->rf.n_vert;
+    if (int rc = ensure(c, c->rf.vert, n_vert * skin::kVertexWords * sizeof(float))) return rc;
+    HIP_TRY(c, hipMemcpyAsync(c->sk.pose.p, matrices, (size_t)n_bones * 12 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    skin_launch(skin::Args{(const unsigned *)c->sk.rest.p, (const uint4 *)c->sk.rig.p, (const float4 *)c->sk.pose.p, (unsigned *)c->rf.vert.p, n_vert}, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    if (c->mt_on && c->mt_geom == glrtx_ctx::kMtCurrent)  // (glrtx_update_vertices_device's path from here)
+        if (int rc = motion_snapshot(c)) return rc;
+    return refit_run(c, c->rf.vert.p);
+}
+
+int glrtx_debug_skin(const float *rest, size_t n_vert, const int32_t *bones4, const float *weights4, const float *matrices, int n_bones, float *vert_out) {
+    const char *fn = "glrtx_debug_skin";
+    if (int rc = rig_check(nullptr, rest, n_vert, bones4, weights4, n_bones, fn)) return rc;
+    if (!matrices || (n_vert > 0 && !vert_out)) return fail(nullptr, GLRTX_EINVAL, "%s: NULL buffer", fn);
+    if (n_vert == 0) return GLRTX_OK;
+    std::vector<uint4> rig;
+    rig_records(rig, n_vert, bones4, weights4);
+    const size_t bytes = n_vert * skin::kVertexWords * sizeof(float);
+    DebugScratch s;
+    const unsigned *R = s.alloc<unsigned>(bytes, rest);
+    const uint4 *G = s.alloc<uint4>(rig.size() * sizeof(uint4), rig.data());
+    const float4 *P = s.alloc<float4>((size_t)n_bones * 12 * sizeof(float), matrices);
+    unsigned *O = s.alloc<unsigned>(bytes);
+    if (s.ok()) {
+        skin_launch(skin::Args{R, G, P, O, n_vert}, 0);
+        s.e = hipGetLastError();
+    }
+    s.sync();
+    s.download(vert_out, O, bytes);
+    return s.result(GLRTX_OK, fn);
+}
+
+// Device time of the skinning kernel by itself, as glrtx_debug_reweight_burst measures its pass: the rig with the matrices of the last glrtx_pose, into the
+// context's vertex buffer -- which holds exactly that already, so nothing changes.
+int glrtx_debug_skin_burst(glrtx_ctx *c, int reps, float *ms_per_launch) {
+    const char *fn = "glrtx_debug_skin_burst";
+    if (!c || !ms_per_launch || reps < 1) return GLRTX_EINVAL;
+    const size_t n_vert = c->rf.n_vert;
+    if (!c->have_scene || c->sk.n_bones == 0 || c->rf.vert.bytes < n_vert * skin::kVertexWords * sizeof(float))
+        return fail(c, GLRTX_EINVAL, "%s: no rig uploaded, or no glrtx_pose yet", fn);
+    seal_feed(c);
+    HIP_TRY(c, hipSetDevice(c->device));
+    const skin::Args a{(const unsigned *)c->sk.rest.p, (const uint4 *)c->sk.rig.p, (const float4 *)c->sk.pose.p, (unsigned *)c->rf.vert.p, n_vert};
+    for (int pass = 0; pass < 2; pass++) {  // (the first pass warms the device up)
+        HIP_TRY(c, hipEventRecord(c->rs0, c->stream));
+        for (int i = 0; i < reps; i++) skin_launch(a, c->stream);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipEventRecord(c->rs1, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    float ms = 0.f;
+    HIP_TRY(c, hipEventElapsedTime(&ms, c->rs0, c->rs1));
+    *ms_per_launch = ms / (float)reps;
+    return GLRTX_OK;
 }
 
 namespace {

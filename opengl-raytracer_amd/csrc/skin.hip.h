@@ -1,0 +1,92 @@
+// skin.hip.h -- posing: linear-blend skinning of the uploaded scene's vertices (glrtx_upload_rig, glrtx_pose, glrtx_debug_skin, include/glrtx.h "Posing").  A
+// rigid object is the one-bone case {obj, 0, 0, 0} / {1, 0, 0, 0}.  The pass runs in front of the refit (refit.hip.h): rest pose + rig + pose matrices -> wire
+// vertices in the context's vertex buffer, which the refit then reads exactly as it reads uploaded ones.
+//
+// No reference counterpart.  The arithmetic is the header's text: host/skin.cpp (glrt_skin_vertices) and tests/skin_math.py state it again, and all three agree
+// bit for bit under denoise.hip.h's rules (one correctly rounded fp32 operation at a time in the order written, -ffp-contract=off; denormals flushed; a stored
+// NaN is 0x7FC00000).  All four blend terms are formed whatever the weights are, so the operation sequence does not depend on the data.
+//
+//   skin_kernel  one thread per vertex, 256-thread workgroups.  Per vertex: the 60-byte rest record as 15 dword loads (a record is 60 bytes, so a lane's record is
+//       not 16-byte aligned; the 64 records of a wave are 3840 contiguous bytes, so every cache line a wave touches is used whole), the 32-byte rig record {b[4],
+//       w[4]} as two 16-byte loads, 4 x 48 bytes of matrices as twelve 16-byte loads (a pose is a few kilobytes: cache-resident), 15 dword stores.  152 bytes of
+//       compulsory traffic per vertex.  No LDS, no atomics, no scratch.
+#pragma once
+#include "denoise.hip.h"
+
+namespace glrtx {
+namespace skin {
+
+constexpr int kBlock = 256;
+constexpr int kVertexWords = 15;  // GLRT_VERTEX_FLOATS: pos, normal, uv, tangent, binormal
+
+struct Args {
+    const unsigned *rest;  // n_vert x 15 words: the rest pose, wire format
+    const uint4 *rig;      // n_vert x 2: {b0, b1, b2, b3} (int32, each within [0, n_bones): checked on the host before the upload), {w0, w1, w2, w3} (float)
+    const float4 *pose;    // n_bones x 3: the rows of the 3x4 matrices
+    unsigned *out;         // n_vert x 15 words
+    size_t n_vert;
+};
+
+// the project's order (pt_kernel.hip.h: dot): (a2 v.z + a1 v.y) + a0 v.x
+DEV float dot3(float a0, float a1, float a2, float vx, float vy, float vz) { return (a2 * vz + a1 * vy) + a0 * vx; }
+DEV float blend(float w0, float w1, float w2, float w3, float m0, float m1, float m2, float m3) { return ((w0 * m0 + w1 * m1) + w2 * m2) + w3 * m3; }
+DEV float4 blend_row(const float4 w, const float4 m0, const float4 m1, const float4 m2, const float4 m3) {
+    return make_float4(blend(w.x, w.y, w.z, w.w, m0.x, m1.x, m2.x, m3.x), blend(w.x, w.y, w.z, w.w, m0.y, m1.y, m2.y, m3.y),
+                       blend(w.x, w.y, w.z, w.w, m0.z, m1.z, m2.z, m3.z), blend(w.x, w.y, w.z, w.w, m0.w, m1.w, m2.w, m3.w));
+}
+DEV unsigned word(float x) { return __float_as_uint(denoise::canon(x)); }
+
+__global__ __launch_bounds__(kBlock) void skin_kernel(const Args a) {
+    const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= a.n_vert) return;
+    const unsigned *r = a.rest + kVertexWords * i;
+    unsigned in[kVertexWords];
+#pragma unroll
+    for (int k = 0; k < kVertexWords; k++) in[k] = r[k];
+    const uint4 b = a.rig[2 * i];
+    const uint4 wu = a.rig[2 * i + 1];
+    const float4 w = make_float4(__uint_as_float(wu.x), __uint_as_float(wu.y), __uint_as_float(wu.z), __uint_as_float(wu.w));
+    const float4 *m0 = a.pose + 3 * (size_t)b.x, *m1 = a.pose + 3 * (size_t)b.y, *m2 = a.pose + 3 * (size_t)b.z, *m3 = a.pose + 3 * (size_t)b.w;
+    // Blend: B = ((w0 M_b0 + w1 M_b1) + w2 M_b2) + w3 M_b3, all twelve entries; B0 .. B2 are B's rows {L[i][0], L[i][1], L[i][2], translation}
+    const float4 B0 = blend_row(w, m0[0], m1[0], m2[0], m3[0]);
+    const float4 B1 = blend_row(w, m0[1], m1[1], m2[1], m3[1]);
+    const float4 B2 = blend_row(w, m0[2], m1[2], m2[2], m3[2]);
+
+    const float px = __uint_as_float(in[0]), py = __uint_as_float(in[1]), pz = __uint_as_float(in[2]);
+    const float nx = __uint_as_float(in[3]), ny = __uint_as_float(in[4]), nz = __uint_as_float(in[5]);
+    const float tx = __uint_as_float(in[9]), ty = __uint_as_float(in[10]), tz = __uint_as_float(in[11]);
+    const float bx = __uint_as_float(in[12]), by = __uint_as_float(in[13]), bz = __uint_as_float(in[14]);
+
+    unsigned o[kVertexWords];
+    // Position
+    o[0] = word(dot3(B0.x, B0.y, B0.z, px, py, pz) + B0.w);
+    o[1] = word(dot3(B1.x, B1.y, B1.z, px, py, pz) + B1.w);
+    o[2] = word(dot3(B2.x, B2.y, B2.z, px, py, pz) + B2.w);
+    // Cofactor matrix of L (det L^-T): two rounded products and one subtraction an entry
+    const float c00 = B1.y * B2.z - B1.z * B2.y, c01 = B1.z * B2.x - B1.x * B2.z, c02 = B1.x * B2.y - B1.y * B2.x;
+    const float c10 = B2.y * B0.z - B2.z * B0.y, c11 = B2.z * B0.x - B2.x * B0.z, c12 = B2.x * B0.y - B2.y * B0.x;
+    const float c20 = B0.y * B1.z - B0.z * B1.y, c21 = B0.z * B1.x - B0.x * B1.z, c22 = B0.x * B1.y - B0.y * B1.x;
+    // Normal
+    const float vx = dot3(c00, c01, c02, nx, ny, nz), vy = dot3(c10, c11, c12, nx, ny, nz), vz = dot3(c20, c21, c22, nx, ny, nz);
+    const float s = dot3(vx, vy, vz, vx, vy, vz);
+    const float l = __builtin_sqrtf(s);
+    const bool unit = l > 0.0f;
+    o[3] = word(unit ? vx / l : vx);
+    o[4] = word(unit ? vy / l : vy);
+    o[5] = word(unit ? vz / l : vz);
+    // uv: moved as integers
+    o[6] = in[6]; o[7] = in[7]; o[8] = in[8];
+    // Tangent and binormal: L times the vector, not normalised
+    o[9] = word(dot3(B0.x, B0.y, B0.z, tx, ty, tz));
+    o[10] = word(dot3(B1.x, B1.y, B1.z, tx, ty, tz));
+    o[11] = word(dot3(B2.x, B2.y, B2.z, tx, ty, tz));
+    o[12] = word(dot3(B0.x, B0.y, B0.z, bx, by, bz));
+    o[13] = word(dot3(B1.x, B1.y, B1.z, bx, by, bz));
+    o[14] = word(dot3(B2.x, B2.y, B2.z, bx, by, bz));
+    unsigned *d = a.out + kVertexWords * i;
+#pragma unroll
+    for (int k = 0; k < kVertexWords; k++) d[k] = o[k];
+}
+
+}  // namespace skin
+}  // namespace glrtx

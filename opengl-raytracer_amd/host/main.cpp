@@ -15,7 +15,7 @@
 using namespace glrt;
 
 static void usage(const char *exe) {
-    std::printf("usage: %s -i scene.json [-s N] [--max-depth D] [--spp N] [--frames F] [--frames-in-flight B] [--bvh sah|sah-reinsert|sah-gpu|lbvh|sah-levels-cpu|lbvh-cpu|reference] [--order-by-hits] [--out file.png] [--save-every-frame] [--device G | --gpus N | --devices a,b,..] [--extensions] [--whitted] [--enable-volume] [--volume-wavefront] [--adaptive THRESHOLD | --adaptive-variance THRESHOLD [--min-spp N]] [--denoise | --denoise-variance [--denoise-iters N]] [--tonemap clamp|reinhard|aces [--exposure X] [--auto-exposure]] [--bloom [--bloom-threshold T] [--bloom-strength S] [--bloom-levels N]] [--reweight [--reweight-kappa K] [--reweight-start S]]\n"
+    std::printf("usage: %s -i scene.json [-s N] [--max-depth D] [--spp N] [--frames F] [--frames-in-flight B] [--bvh sah|sah-reinsert|sah-gpu|lbvh|sah-levels-cpu|lbvh-cpu|reference] [--order-by-hits] [--out file.png] [--save-every-frame] [--device G | --gpus N | --devices a,b,..] [--extensions] [--whitted] [--enable-volume] [--volume-wavefront] [--adaptive THRESHOLD | --adaptive-variance THRESHOLD [--min-spp N]] [--denoise | --denoise-variance [--denoise-iters N]] [--tonemap clamp|reinhard|aces [--exposure X] [--auto-exposure]] [--bloom [--bloom-threshold T] [--bloom-strength S] [--bloom-levels N]] [--reweight [--reweight-kappa K] [--reweight-start S]] [--animate FILE [--carry-history]]\n"
                 "  -i, --input             scene description (JSON; schema: SURVEY.md Appendix C)            [required]\n"
                 "  -s, --sample-per-cycle  accepted for compatibility; like the reference (main.cpp:13) it is not read\n"
                 "      --max-depth D       u_maxDepth (default 16, the reference shader's default)\n"
@@ -63,7 +63,14 @@ static void usage(const char *exe) {
                 "                          expects it; goes through --bloom / --tonemap as a denoised image does (one device; not with --denoise, --denoise-variance,\n"
                 "                          --adaptive, --adaptive-variance, --enable-volume or --save-every-frame)\n"
                 "      --reweight-kappa K  with --reweight: samples the neighbourhood must hold besides one for a level to count in full, > 0 (default 4)\n"
-                "      --reweight-start S  with --reweight: luminance bound of the first cascade, 2^-20 .. 2^20 (default 1); the others are S * 8^k\n", exe);
+                "      --reweight-start S  with --reweight: luminance bound of the first cascade, 2^-20 .. 2^20 (default 1); the others are S * 8^k\n"
+                "      --animate FILE      pose the scene's shapes on the device step by step (glrtx_pose): FILE is JSON, {\"steps\": [{\"matrices\": [[shape, m0, ..., m11], ...],\n"
+                "                          \"camera\": {...}}, ...]} -- shape: index into the scene file's \"scene\" array, m: row-major 3x4, unlisted shapes keep the identity,\n"
+                "                          \"camera\" optional with the scene file's keys.  Every step renders --frames frames and writes <out stem>_<step, 4 digits>.<ext> as a\n"
+                "                          still run would under the same --denoise* / --bloom / --tonemap (one device; not with --adaptive*, --reweight, --enable-volume,\n"
+                "                          --extensions or --save-every-frame)\n"
+                "      --carry-history     with --animate: keep the accumulator across the steps by motion-aware reprojection (glrtx_reproject_motion) instead of clearing\n"
+                "                          it; moments are tracked, so --denoise-variance composes (not with --denoise)\n", exe);
 }
 
 int main(int argc, char **argv) {
@@ -83,7 +90,8 @@ int main(int argc, char **argv) {
     float bloom_threshold = 1.0f, bloom_strength = 0.25f;
     int bloom_levels = 5;
     std::vector<int> devices;
-    std::string bvh;
+    std::string bvh, animate;
+    bool carry_history = false;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         auto next = [&](const char *name) -> const char * {
@@ -120,6 +128,8 @@ int main(int argc, char **argv) {
         else if (a == "--auto-exposure") auto_exposure = true;
         else if (a == "--bloom") bloom = true;
         else if (a == "--reweight") reweight = true;
+        else if (a == "--animate") animate = next("--animate");
+        else if (a == "--carry-history") carry_history = true;
         else if (a == "--reweight-kappa") { reweight_kappa = (float)std::atof(next("--reweight-kappa")); reweight_opt = true; }
         else if (a == "--reweight-start") { reweight_start = (float)std::atof(next("--reweight-start")); reweight_opt = true; }
         else if (a == "--bloom-threshold") { bloom_threshold = (float)std::atof(next("--bloom-threshold")); bloom_opt = true; }
@@ -166,6 +176,16 @@ int main(int argc, char **argv) {
         std::fprintf(stderr, "--reweight: --frames-in-flight %d is above the 1024 frames one glrtx_render_cascades burst takes\n", in_flight);
         return 1;
     }
+    if (carry_history && animate.empty()) { std::fprintf(stderr, "--carry-history needs --animate\n"); return 1; }
+    if (!animate.empty() && (devices.size() > 1 || adaptive || adaptive_variance || reweight || volume || extensions || every_frame)) {
+        std::fprintf(stderr, "--animate: one device, and not with --adaptive, --adaptive-variance, --reweight, --enable-volume, --extensions or --save-every-frame\n");
+        return 1;
+    }
+    if (carry_history && denoise) { std::fprintf(stderr, "--carry-history: not with --denoise (the fixed-sigma filter has no moments; use --denoise-variance)\n"); return 1; }
+    if (!animate.empty() && (denoise_variance || carry_history) && in_flight > 1024) {
+        std::fprintf(stderr, "--animate: --frames-in-flight %d is above the 1024 frames one glrtx_render_moments burst takes\n", in_flight);
+        return 1;
+    }
     if (bloom_opt && !bloom) { std::fprintf(stderr, "--bloom-threshold, --bloom-strength and --bloom-levels need --bloom\n"); return 1; }
     if (bloom && (every_frame || devices.size() > 1 || !(bloom_threshold >= 0.0f) || std::isinf(bloom_threshold) || !(bloom_strength >= 0.0f && bloom_strength <= 1.0e4f) ||
                   bloom_levels < 1 || bloom_levels > 8)) {
@@ -195,6 +215,7 @@ int main(int argc, char **argv) {
     if (tonemap_op >= 0) window->setTonemap(tonemap_op, exposure, auto_exposure);
     if (bloom) window->setBloom(bloom_threshold, bloom_strength, bloom_levels);
     if (reweight) window->setReweight(reweight_kappa, reweight_start);
+    if (!animate.empty()) window->setAnimation(animate, carry_history);
 
     auto scene = std::make_shared<Scene>();
     if (!bvh.empty()) scene->setBvhBuilder(bvh);

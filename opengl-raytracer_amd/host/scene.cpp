@@ -61,28 +61,15 @@ void Scene::parse(const std::string &filename) {
     // camera (scene.cpp:62-114)
     const std::string type = json["camera"]["type"].string_value();
     GLRT_Info("Camera type: %s", type.c_str());
-    if (type == "perspective") {
-        const Json &cam = json["camera"];
-        apertureRadius = (float)cam["apertureRadius"].number_value();  // absent -> 0
-        focalLength = (float)cam["focalLength"].number_value();        // absent -> 0 (scene.cpp:71-74)
-        if (cam["lookAt"].is_null()) GLRT_FatalError("perspective camera node does not have \"lookAt\" key!");
-        float origin[3], target[3], up[3];
-        vec3(cam["lookAt"]["origin"], origin);
-        vec3(cam["lookAt"]["target"], target);
-        vec3(cam["lookAt"]["up"], up);
-        glrt_look_at(origin, target, up, viewM);
-        if (cam["fov"].is_null()) GLRT_FatalError("perspective camera node does not have \"fov\" key!");
-        if (cam["nearClip"].is_null()) GLRT_FatalError("perspective camera node does not have \"nearClip\" key!");
-        if (cam["farClip"].is_null()) GLRT_FatalError("perspective camera node does not have \"farClip\" key!");
-        glrt_perspective((float)cam["fov"].number_value(), (float)width / (float)height,
-                         (float)cam["nearClip"].number_value(), (float)cam["farClip"].number_value(), projM);
-    }
+    if (type == "perspective") readPerspective(json["camera"], viewM, projM, apertureRadius, focalLength);
 
     // shapes (scene.cpp:116-250)
     vertices.clear(); triangles.clear(); lights.clear(); materials.clear(); nodes.clear();
+    shapeFirstVertex_.clear(); animation_.clear();
     const auto &shapes = json["scene"].array_items();
     for (size_t i = 0; i < shapes.size(); i++) {
         const Json &sh = shapes[i];
+        shapeFirstVertex_.push_back(vertices.size());
         const std::string material = sh["material"].string_value();
         Material m;
         std::memset(&m, 0, sizeof m);
@@ -171,12 +158,67 @@ void Scene::parse(const std::string &filename) {
     GLRT_Info("#BVH node: %d", (int)nodes.size());
 }
 
+void Scene::readPerspective(const Json &cam, float view[16], float proj[16], float &aperture, float &focal) const {
+    aperture = (float)cam["apertureRadius"].number_value();  // absent -> 0
+    focal = (float)cam["focalLength"].number_value();        // absent -> 0 (scene.cpp:71-74)
+    if (cam["lookAt"].is_null()) GLRT_FatalError("perspective camera node does not have \"lookAt\" key!");
+    float origin[3], target[3], up[3];
+    vec3(cam["lookAt"]["origin"], origin);
+    vec3(cam["lookAt"]["target"], target);
+    vec3(cam["lookAt"]["up"], up);
+    glrt_look_at(origin, target, up, view);
+    if (cam["fov"].is_null()) GLRT_FatalError("perspective camera node does not have \"fov\" key!");
+    if (cam["nearClip"].is_null()) GLRT_FatalError("perspective camera node does not have \"nearClip\" key!");
+    if (cam["farClip"].is_null()) GLRT_FatalError("perspective camera node does not have \"farClip\" key!");
+    glrt_perspective((float)cam["fov"].number_value(), (float)width / (float)height,
+                     (float)cam["nearClip"].number_value(), (float)cam["farClip"].number_value(), proj);
+}
+
+void Scene::parseAnimation(const std::string &filename) {
+    std::ifstream reader(filename.c_str(), std::ios::in);
+    if (reader.fail()) GLRT_FatalError("Failed to open file: %s", filename.c_str());
+    std::stringstream ss;
+    ss << reader.rdbuf();
+    std::string err;
+    const Json json = Json::parse(ss.str(), err);
+    if (!err.empty()) GLRT_FatalError("animation: %s", err.c_str());
+    if (!json["steps"].is_array()) GLRT_FatalError("animation: no \"steps\" array");
+    const size_t n_shapes = shapeFirstVertex_.size();
+    animation_.clear();
+    const auto &steps = json["steps"].array_items();
+    for (size_t s = 0; s < steps.size(); s++) {
+        AnimationStep st;
+        st.matrices.assign(12 * n_shapes, 0.0f);
+        for (size_t b = 0; b < n_shapes; b++) st.matrices[12 * b] = st.matrices[12 * b + 5] = st.matrices[12 * b + 10] = 1.0f;
+        for (const Json &entry : steps[s]["matrices"].array_items()) {
+            const auto &v = entry.array_items();
+            bool numbers = true;
+            for (const Json &x : v) numbers = numbers && x.is_number();
+            if (v.size() != 13 || !numbers)
+                GLRT_FatalError("animation step %zu: a matrix entry is a shape index and 12 numbers, this one has %zu", s, v.empty() ? (size_t)0 : v.size() - 1);
+            const double shape = v[0].number_value();
+            if (!(shape >= 0.0 && shape < (double)n_shapes) || shape != std::floor(shape))
+                GLRT_FatalError("animation step %zu: shape index %g is out of range (the scene has %zu shapes)", s, shape, n_shapes);
+            for (size_t k = 0; k < 12; k++) st.matrices[12 * (size_t)shape + k] = (float)v[k + 1].number_value();
+        }
+        const Json &cam = steps[s]["camera"];
+        if (!cam.is_null()) {
+            if (cam["type"].string_value() != "perspective") GLRT_FatalError("animation step %zu: camera type \"%s\" (perspective)", s, cam["type"].string_value().c_str());
+            st.hasCamera = true;
+            readPerspective(cam, st.viewM, st.projM, st.apertureRadius, st.focalLength);
+        }
+        animation_.push_back(std::move(st));
+    }
+    GLRT_Info("Animation: %zu steps, %zu shapes", animation_.size(), n_shapes);
+}
+
 void Scene::setBuffers(int w, int h, const float view[16], const float proj[16], float aperture, float focal,
                        std::vector<Vertex> v, std::vector<Triangle> t, std::vector<Material> m, std::vector<BVHNode> n) {
     width = w; height = h; apertureRadius = aperture; focalLength = focal;
     std::memcpy(viewM, view, sizeof viewM);
     std::memcpy(projM, proj, sizeof projM);
     vertices = std::move(v); triangles = std::move(t); materials = std::move(m); nodes = std::move(n);
+    shapeFirstVertex_.clear(); animation_.clear();
     finalize();
 }
 
@@ -387,6 +429,38 @@ struct SceneVolumeProbe {
     }
 };
 }  // namespace glrt
+
+// Animation probe: parse the scene, then the animation file.  counts = {steps, shapes}; first_vertex (shapes + 1 values: the last is the vertex count), matrices
+// (steps x shapes x 12), has_camera (steps) and cameras (steps x 34: view, proj, aperture, focal length; zeros without a camera) may each be NULL.
+namespace glrt {
+struct SceneAnimationProbe {
+    static int run(const char *json, const char *animation, long long counts[2], long long *first_vertex, float *matrices, int *has_camera, float *cameras) {
+        Scene sc;
+        sc.parse(json);
+        sc.parseAnimation(animation);
+        const size_t n_shapes = sc.numShapes(), n_steps = sc.animation_.size();
+        counts[0] = (long long)n_steps; counts[1] = (long long)n_shapes;
+        if (first_vertex)
+            for (size_t i = 0; i <= n_shapes; i++) first_vertex[i] = (long long)sc.shapeFirstVertex(i);
+        for (size_t s = 0; s < n_steps; s++) {
+            const Scene::AnimationStep &st = sc.animation_[s];
+            if (matrices && n_shapes) std::memcpy(matrices + s * 12 * n_shapes, st.matrices.data(), 12 * n_shapes * sizeof(float));
+            if (has_camera) has_camera[s] = st.hasCamera ? 1 : 0;
+            if (cameras) {
+                float *c = cameras + 34 * s;
+                std::memset(c, 0, 34 * sizeof(float));
+                if (st.hasCamera) { std::memcpy(c, st.viewM, 64); std::memcpy(c + 16, st.projM, 64); c[32] = st.apertureRadius; c[33] = st.focalLength; }
+            }
+        }
+        return 0;
+    }
+};
+}  // namespace glrt
+
+extern "C" GLRT_API int glrt_scene_animation_probe(const char *json, const char *animation, long long counts[2], long long *first_vertex, float *matrices,
+                                                   int *has_camera, float *cameras) {
+    return glrt::SceneAnimationProbe::run(json, animation, counts, first_vertex, matrices, has_camera, cameras);
+}
 
 extern "C" GLRT_API int glrt_scene_volume_probe(const char *json, int enable, int info[5], float bbox[6], float *density_max) {
     return glrt::SceneVolumeProbe::run(json, enable, info, bbox, density_max);

@@ -12,6 +12,8 @@
 
 namespace glrt {
 
+class Json;
+
 // Wire-format records, byte-identical to the reference's (scene.h:16-35, trimesh.h:15-25, bvh.h:84-100).
 struct Vertex { float pos[3], normal[3], uv[3], tangent[3], binormal[3]; };
 struct Triangle { float indices[4]; };  // i, j, k, materialId
@@ -62,8 +64,27 @@ public:
     const std::vector<VolumeSpec> &volumeSpecs() const { return volumeSpecs_; }
     bool hasVolume() const { return hasVolume_; }
 
+    // Animation (no reference counterpart; glrt_main --animate, Window::setAnimation): call after parse().  FILE is JSON,
+    //     {"steps": [ {"matrices": [[shape, m0, ..., m11], ...], "camera": { ... }}, ... ]}
+    // shape: an index into the scene file's "scene" array; m0 .. m11: that shape's pose matrix, row-major 3x4 (include/glrtx.h "Posing").  Shapes a step does not
+    // list get the identity.  "camera" is optional and has the keys of the scene file's own "camera" block (it goes through the same code); without it the scene
+    // file's camera holds for that step.  Numbers are parsed as doubles and cast to float.  A shape index out of range and an entry that is not 13 numbers are
+    // FatalErrors.  Bone i of the rig Window uploads is shape i: loadObj yields three fresh vertices per triangle, so shapes never share a vertex.
+    struct AnimationStep {
+        std::vector<float> matrices;  // numShapes() x 12
+        bool hasCamera = false;
+        float viewM[16], projM[16], apertureRadius = 0.0f, focalLength = 0.0f;  // (with hasCamera)
+    };
+    void parseAnimation(const std::string &filename);
+    const std::vector<AnimationStep> &animation() const { return animation_; }
+    size_t numShapes() const { return shapeFirstVertex_.size(); }
+    // the first vertex of entry i of the JSON "scene" array (an entry without geometry owns none: its range is empty); i == numShapes(): the vertex count
+    size_t shapeFirstVertex(size_t i) const { return i < shapeFirstVertex_.size() ? shapeFirstVertex_[i] : vertices.size(); }
+
 private:
     void finalize();  // lights list + BVH (scene.cpp:246-256)
+    // a "camera" block of type "perspective" (scene.cpp:62-114) into the four camera fields given; the scene file's and an animation step's alike
+    void readPerspective(const Json &cam, float view[16], float proj[16], float &aperture, float &focal) const;
 
     int width = 0, height = 0;
     float apertureRadius = 0.0f, focalLength = 1.0f;
@@ -80,11 +101,14 @@ private:
     bool extensions_ = false, whitted_ = false, hasDielectric_ = false;
     std::vector<VolumeSpec> volumeSpecs_;
     bool volume_ = false, hasVolume_ = false;
+    std::vector<size_t> shapeFirstVertex_;  // per entry of the JSON "scene" array (parse() only: setBuffers knows no shapes)
+    std::vector<AnimationStep> animation_;
     VolumeGrid volDensity_, volTemperature_;  // volumeSpecs_[0]'s files (only with enableVolume(true)); only the first volume is rendered (window.cpp:271-286)
 
     friend class Window;
     friend struct SceneProbe;
     friend struct SceneVolumeProbe;
+    friend struct SceneAnimationProbe;
 };
 
 // OBJ triangles the way the reference's loader yields them (trimesh.cpp:113-191): three fresh

@@ -5,6 +5,7 @@
 
 #include <chrono>
 #include <cstdint>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
@@ -106,6 +107,10 @@ void Window::mainloop(const std::shared_ptr<Scene> &scene_, double fps) {
     // time per frame between two such waits.
     if (bloom_ && (glrtx_group_size(grp_) != 1 || every)) GLRT_FatalError("--bloom: one device, and not with --save-every-frame (groups and the present ring have no bloomed form)");
     if (tonemap_ && (glrtx_group_size(grp_) != 1 || every)) GLRT_FatalError("--tonemap: one device, and not with --save-every-frame (groups and the present ring have no tone-mapped form)");
+    if (!animationFile_.empty()) {
+        animate();
+        return;
+    }
     if (denoise_ || denoiseVar_) {  // the feature planes of this (static) camera, once, before the first frame
         if (glrtx_group_size(grp_) != 1 || every) GLRT_FatalError("--denoise: one device, and not with --save-every-frame (groups and the present ring have no denoised form)");
         if (denoiseVar_ && (denoise_ || adaptive_)) GLRT_FatalError("--denoise-variance: not with --denoise or --adaptive");
@@ -245,6 +250,85 @@ void Window::mainloop(const std::shared_ptr<Scene> &scene_, double fps) {
         }
     }
     if (!every && !output_.empty() && frameLimit_ > 0) saveCurrentFrame(output_, true);
+}
+
+// --animate: the steps of the animation file, posed on the device (window.h: setAnimation has the call sequence).
+void Window::animate() {
+    if (glrtx_group_size(grp_) != 1) GLRT_FatalError("--animate: one device (groups have no pose call)");
+    if (saveEveryFrame_) GLRT_FatalError("--animate: not with --save-every-frame (a step writes one image)");
+    if (adaptive_ || adaptiveVar_) GLRT_FatalError("--animate: not with --adaptive or --adaptive-variance");
+    if (reweight_) GLRT_FatalError("--animate: not with --reweight");
+    if (scene->hasVolume_ || scene->volume_) GLRT_FatalError("--animate: not with --enable-volume (the volume does not move)");
+    if (scene->extensions_ || !scene->spheres.empty() || scene->hasDielectric_ || scene->whitted_) GLRT_FatalError("--animate: not with --extensions (spheres do not move)");
+    if (carryHistory_ && denoise_) GLRT_FatalError("--carry-history: not with --denoise (the fixed-sigma filter has no moments; use --denoise-variance)");
+    if (denoise_ && denoiseVar_) GLRT_FatalError("--denoise-variance: not with --denoise");
+    scene->parseAnimation(animationFile_);
+    const std::vector<Scene::AnimationStep> &steps = scene->animation();
+    const size_t n_vert = scene->vertices.size(), n_shapes = scene->numShapes();
+    if (n_vert == 0 || n_shapes == 0 || n_shapes > 65536) GLRT_FatalError("--animate: the scene needs geometry and 1 .. 65536 shapes (it has %zu)", n_shapes);
+    glrtx_ctx *c0 = glrtx_group_ctx(grp_, 0);
+    {  // the rig: the scene's vertices are the rest pose, vertex v follows the shape it came from alone
+        std::vector<int32_t> bones(4 * n_vert, 0);
+        std::vector<float> weights(4 * n_vert, 0.0f);
+        for (size_t i = 0; i < n_shapes; i++)
+            for (size_t v = scene->shapeFirstVertex(i); v < scene->shapeFirstVertex(i + 1); v++) { bones[4 * v] = (int32_t)i; weights[4 * v] = 1.0f; }
+        if (glrtx_upload_rig(c0, &scene->vertices[0].pos[0], n_vert, bones.data(), weights.data(), (int)n_shapes) != GLRTX_OK)
+            GLRT_FatalError("glrtx_upload_rig: %s", glrtx_last_error(c0));
+    }
+    float view0[16], proj0[16];
+    std::memcpy(view0, scene->viewM, sizeof view0);
+    std::memcpy(proj0, scene->projM, sizeof proj0);
+    const float aperture0 = scene->apertureRadius, focal0 = scene->focalLength;
+    const bool moments = carryHistory_ || denoiseVar_;
+    const glrtx_reproject_cfg carry = {32, 0.02f, 0.9f};  // (glrt_amd.host.REPROJECT_DEFAULTS holds the same)
+    const size_t dot = output_.find_last_of('.'), slash = output_.find_last_of("/\\");
+    const bool has_ext = dot != std::string::npos && (slash == std::string::npos || dot > slash);
+    const std::string stem = has_ext ? output_.substr(0, dot) : output_, ext = has_ext ? output_.substr(dot) : "";
+    for (size_t s = 0; s < steps.size(); s++) {
+        const Scene::AnimationStep &st = steps[s];
+        std::memcpy(scene->viewM, st.hasCamera ? st.viewM : view0, sizeof view0);
+        std::memcpy(scene->projM, st.hasCamera ? st.projM : proj0, sizeof proj0);
+        scene->apertureRadius = st.hasCamera ? st.apertureRadius : aperture0;
+        scene->focalLength = st.hasCamera ? st.focalLength : focal0;
+        auto t0 = std::chrono::steady_clock::now();
+        if (glrtx_pose(c0, st.matrices.data(), (int)n_shapes) != GLRTX_OK) GLRT_FatalError("glrtx_pose: %s", glrtx_last_error(c0));
+        glrtx_params p;
+        frameParams(p);
+        if (carryHistory_) {
+            if (s == 0) {
+                if (glrtx_track_motion(c0, 1) != GLRTX_OK) GLRT_FatalError("glrtx_track_motion: %s", glrtx_last_error(c0));
+                if (glrtx_track_moments(c0, 1) != GLRTX_OK) GLRT_FatalError("glrtx_track_moments: %s", glrtx_last_error(c0));
+                if (glrtx_render_features(c0, &p) != GLRTX_OK) GLRT_FatalError("glrtx_render_features: %s", glrtx_last_error(c0));
+            } else {
+                if (glrtx_reproject_motion(c0, &p, &carry) != GLRTX_OK) GLRT_FatalError("glrtx_reproject_motion: %s", glrtx_last_error(c0));
+                int carried = 0, hits = 0;
+                if (glrtx_reproject_last(c0, &carried, &hits) != GLRTX_OK) GLRT_FatalError("glrtx_reproject_last: %s", glrtx_last_error(c0));
+                GLRT_Info("Animate: step %zu carries history at %d of %d hit pixels", s, carried, hits);
+            }
+        } else {
+            GLRTX_CHECK(glrtx_group_clear(grp_));
+            if ((denoise_ || denoiseVar_) && glrtx_render_features(c0, &p) != GLRTX_OK) GLRT_FatalError("glrtx_render_features: %s", glrtx_last_error(c0));
+            if (denoiseVar_ && s == 0 && glrtx_track_moments(c0, 1) != GLRTX_OK) GLRT_FatalError("glrtx_track_moments: %s", glrtx_last_error(c0));
+        }
+        for (int issued = 0; issued < frameLimit_;) {
+            const int n = frameLimit_ - issued < framesInFlight_ ? frameLimit_ - issued : framesInFlight_;
+            if (moments) {
+                std::vector<float> seeds(2 * (size_t)n);
+                for (int f = 0; f < n; f++) glrt_frame_seed(frame_++, &seeds[2 * (size_t)f]);
+                if (glrtx_render_moments(c0, &p, seeds.data(), n) != GLRTX_OK) GLRT_FatalError("glrtx_render_moments: %s", glrtx_last_error(c0));
+            } else if (n == 1) render();
+            else renderFrames(n);
+            issued += n;
+        }
+        GLRTX_CHECK(glrtx_group_sync(grp_));
+        lastMs_ = frameLimit_ > 0 ? std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() / frameLimit_ : 0.0;
+        char num[16];
+        std::snprintf(num, sizeof num, "_%04zu", s);
+        if (!output_.empty()) saveCurrentFrame(stem + num + ext, true);
+    }
+    std::memcpy(scene->viewM, view0, sizeof view0);
+    std::memcpy(scene->projM, proj0, sizeof proj0);
+    scene->apertureRadius = aperture0; scene->focalLength = focal0;
 }
 
 void Window::initialize() {

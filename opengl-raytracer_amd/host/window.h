@@ -72,6 +72,14 @@ public:
     // frames with the cascade fold, and the saved image is the re-weighted one (through setBloom / setTonemap as a denoised image would go).
     void setReweight(float kappa, float start) { reweight_ = true; reweightCfg_.kappa = kappa; reweightStart_ = start; }
     void setDenoiseVariance(int iterations) { denoiseVar_ = true; if (iterations >= 1) denoiseVarCfg_.iterations = iterations; }
+    // Animation (no reference counterpart; glrtx_upload_rig / glrtx_pose, one device only): the steps of `file` (Scene::parseAnimation has the format) are posed on
+    // the device one after the other -- bone i is shape i of the scene file --, each rendered with the frame limit's frames and written to <stem>_<step, four
+    // digits>.<ext> exactly as a still run writes its image under the same denoise / bloom / tonemap settings.  The frame counter behind the seeds runs on across
+    // the steps.  Step s issues: glrtx_pose; then, with carryHistory, at s = 0 glrtx_track_motion(1), glrtx_track_moments(1) and glrtx_render_features, from
+    // s = 1 on glrtx_reproject_motion with the default configuration -- without it glrtx_clear and the feature pass a still run's denoiser would make --; then the
+    // frames in bursts of framesInFlight (through glrtx_render_moments when moments are tracked: carryHistory or setDenoiseVariance); then the image.
+    // Not with several devices, setAdaptive*, setReweight, extension or volume scenes, one image per frame, or carryHistory with setDenoise (no moments).
+    void setAnimation(const std::string &file, bool carryHistory) { animationFile_ = file; carryHistory_ = carryHistory; }
     // wall-clock ms PER FRAME between the last two waits for the device, averaged over the frames issued in between (with one PNG per run: the whole run, cold first
     // launches included; with --save-every-frame: the whole run, PNG writing included).  The device's own time of the last launch is glrtx_stats.kernel_ms_last.
     double lastFrameMs() const { return lastMs_; }
@@ -93,6 +101,7 @@ private:
     void saveImage(const std::string &filename, bool overwrite, const unsigned char *rgba) const;  // a full RGBA8 image, flipped: PNG + "Save:" line
     static constexpr int kPresentRing = 8;  // --save-every-frame: images the loop may run ahead of the PNG writer (8.3 MB each at 1080p, pinned)
     void noteFallback();
+    void animate();
 
     glrtx_group *grp_ = nullptr;
     std::vector<int> devices_ = {-1};  // -1: the current HIP device
@@ -116,6 +125,8 @@ private:
     glrtx_denoise_var_cfg denoiseVarCfg_ = {5, 4.0f, 0.1f, 0.01f, 1};  // (DESIGN.md "Variance guidance": the sweep; glrt_amd.host.DENOISE_VAR_DEFAULTS holds the same)
     glrtx_denoise_cfg denoiseCfg_ = {5, 100.0f, 0.1f, 0.01f, 1};  // (DESIGN.md "Denoising": the sweep behind these; glrt_amd.host.DENOISE_DEFAULTS holds the same)
     bool fallbackNoted_ = false;
+    std::string animationFile_;
+    bool carryHistory_ = false;
     std::string output_ = "output.png";
     double lastMs_ = 0.0;
     std::shared_ptr<Scene> scene = nullptr;

@@ -173,7 +173,7 @@ EXPORTS = ["glrtx_abi_version", "glrtx_create", "glrtx_destroy", "glrtx_last_err
            "glrtx_debug_tonemap", "glrtx_debug_tonemap_burst",
            "glrtx_bloom", "glrtx_read_bloomed", "glrtx_tonemap_bloomed", "glrtx_resolve_bloomed_rgba8", "glrtx_debug_bloom", "glrtx_debug_bloom_burst",
            "glrtx_track_cascades", "glrtx_render_cascades", "glrtx_read_cascades", "glrtx_reweight", "glrtx_debug_fold_cascades", "glrtx_debug_reweight",
-           "glrtx_debug_reweight_burst"]
+           "glrtx_debug_reweight_burst", "glrtx_upload_rig", "glrtx_pose", "glrtx_debug_skin", "glrtx_debug_skin_burst"]
 
 SCENE_BUFFERS = ("nodes", "cnodes", "nrms", "lights", "vine", "root")  # glrtx_debug_read_scene's `which`, in order (GLRTX_SCENE_*)
 
@@ -349,6 +349,14 @@ def lib():
             L.glrtx_debug_fold_cascades.argtypes = [fp, fp, fp, C.c_int, C.c_int, C.c_int, C.c_float, fp, fp]
             L.glrtx_debug_reweight.argtypes = [fp, C.c_int, C.c_int, rc, fp]
             L.glrtx_debug_reweight_burst.argtypes = [vp, rc, C.c_int, C.POINTER(C.c_float)]
+        except AttributeError:
+            pass
+        try:  # (additive to ABI 10 as well: posing)
+            i32p = C.POINTER(C.c_int32)
+            L.glrtx_upload_rig.argtypes = [vp, fp, C.c_size_t, i32p, fp, C.c_int]
+            L.glrtx_pose.argtypes = [vp, fp, C.c_int]
+            L.glrtx_debug_skin.argtypes = [fp, C.c_size_t, i32p, fp, fp, C.c_int, fp]
+            L.glrtx_debug_skin_burst.argtypes = [vp, C.c_int, C.POINTER(C.c_float)]
         except AttributeError:
             pass
         _lib = L
@@ -646,6 +654,19 @@ def debug_reproject_motion_moments(accum, moments, n0, a0, g1, a1, vert_prev, tr
     return out, mo, int(carried.value), int(hits.value)
 
 
+def debug_skin(rest, bones, weights, matrices):
+    """glrtx_debug_skin on the current device: the skinning kernel alone on a rig's arrays -- rest (n, 15) float32, bones (n, 4) int32, weights (n, 4) float32,
+    matrices (n_bones, 12) float32.  Returns the posed vertices (n, 15) float32."""
+    from .host import rig_arrays
+    L = lib()
+    r, b, w, m = rig_arrays("debug_skin", rest, bones, weights, matrices)
+    out = np.zeros_like(r)
+    rc = L.glrtx_debug_skin(_fp(r), r.shape[0], b.ctypes.data_as(C.POINTER(C.c_int32)), _fp(w), _fp(m), m.shape[0], _fp(out))
+    if rc != 0:
+        raise GlrtxError(rc, L.glrtx_last_error(None).decode())
+    return out
+
+
 def _host_vertices(v):
     """A numpy vertex array for glrtx_update_vertices: float32, shape (n, 15) or flat (or the scene's (n * 5, 3) texels).  Returns (array, n)."""
     a = np.asarray(v)
@@ -741,6 +762,27 @@ class Device:
         else:
             a, n = _host_vertices(v)
             self._ck(self.L.glrtx_update_vertices(self.h, _fp(a), n))
+
+    def upload_rig(self, rest, bones, weights, n_bones):
+        """glrtx_upload_rig: the rest pose (n, 15) float32 (or the scene's vertex texels), four bone indices (n, 4) int32 and four weights (n, 4) float32 a
+        vertex, kept on the device for pose().  glrt_amd.rig.rigid gives the bones and weights of rigid objects."""
+        from .host import rig_arrays
+        r, b, w = rig_arrays("upload_rig", rest, bones, weights)
+        self._ck(self.L.glrtx_upload_rig(self.h, _fp(r), r.shape[0], b.ctypes.data_as(C.POINTER(C.c_int32)), _fp(w), int(n_bones)))
+
+    def pose(self, matrices):
+        """glrtx_pose: matrices (n_bones, 12) float32, row-major 3x4 -- skins the rest pose on the device and refits, as update_vertices of the skinned
+        vertices would.  Returns when the refit has run; the accumulator is not cleared."""
+        m = _f32(matrices)
+        if m.size % 12:
+            raise ValueError(f"pose: matrices must be (n_bones, 12) or (n_bones, 3, 4), got {m.shape}")
+        self._ck(self.L.glrtx_pose(self.h, _fp(m), m.size // 12))
+
+    def skin_burst_ms(self, reps=20) -> float:
+        """glrtx_debug_skin_burst: device ms of one launch of the skinning kernel (the rig with the last pose's matrices), from `reps` launches back to back."""
+        ms = C.c_float(0)
+        self._ck(self.L.glrtx_debug_skin_burst(self.h, int(reps), C.byref(ms)))
+        return float(ms.value)
 
     def trace_rays(self, rays, any_hit=False, out=None):
         """Batched ray queries against the uploaded scene (glrtx_trace_rays, include/glrtx.h).  rays: (n, 8) float32 {ox, oy, oz, tmin, dx, dy, dz, tmax}.

@@ -56,6 +56,7 @@ def lib():
         L.glrt_bloom.argtypes = [fp, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, fp, fp]
         L.glrt_fold_cascades.argtypes = [fp, fp, fp, C.c_int, C.c_int, C.c_int, C.c_float]
         L.glrt_reweight.argtypes = [fp, C.c_int, C.c_int, C.c_float, fp]
+        L.glrt_skin_vertices.argtypes = [fp, C.c_size_t, C.POINTER(C.c_int32), fp, fp, C.c_int, fp]
         L.glrt_look_at.argtypes = [fp, fp, fp, fp]
         L.glrt_perspective.argtypes = [C.c_float, C.c_float, C.c_float, C.c_float, fp]
         L.glrt_mat4_mul.argtypes = [fp, fp, fp]
@@ -388,6 +389,32 @@ def reweight(cascades, kappa=REWEIGHT_DEFAULTS["kappa"]):
     rc = lib().glrt_reweight(_fp(c), c.shape[2], c.shape[1], float(kappa), _fp(out))
     if rc != 0:
         raise RuntimeError(f"glrt_reweight failed: {rc}")
+    return out
+
+
+def rig_arrays(name, rest, bones, weights, matrices=None):
+    """The arrays of a rig as the C calls take them: rest (n, 15) float32, bones (n, 4) int32, weights (n, 4) float32 and, if given, matrices (n_bones, 12)
+    float32 (also accepted as (n_bones, 3, 4)).  Bits are kept: float32 input is not converted."""
+    r = _f32(rest).reshape(-1, 15)
+    b = np.ascontiguousarray(bones, dtype=np.int32).reshape(-1, 4)
+    w = _f32(weights).reshape(-1, 4)
+    if not (r.shape[0] == b.shape[0] == w.shape[0]):
+        raise ValueError(f"{name}: {r.shape[0]} vertices, {b.shape[0]} bone records, {w.shape[0]} weight records")
+    if matrices is None:
+        return r, b, w
+    m = _f32(matrices)
+    if m.size % 12 or m.size == 0:
+        raise ValueError(f"{name}: matrices must be (n_bones, 12) or (n_bones, 3, 4), got {m.shape}")
+    return r, b, w, m.reshape(-1, 12)
+
+
+def skin_vertices(rest, bones, weights, matrices):
+    """glrt_skin_vertices: the CPU statement of Device.pose / device.debug_skin (include/glrtx.h "Posing").  Returns the posed vertices (n, 15) float32."""
+    r, b, w, m = rig_arrays("skin_vertices", rest, bones, weights, matrices)
+    out = np.zeros_like(r)
+    rc = lib().glrt_skin_vertices(_fp(r), r.shape[0], b.ctypes.data_as(C.POINTER(C.c_int32)), _fp(w), _fp(m), m.shape[0], _fp(out))
+    if rc != 0:
+        raise RuntimeError(f"glrt_skin_vertices failed: {rc}")
     return out
 
 

@@ -1,0 +1,23 @@
+"""Rigs for Device.upload_rig / host.skin_vertices (include/glrtx.h "Posing"): four bone indices and four weights a vertex."""
+from __future__ import annotations
+
+import numpy as np
+
+IDENTITY = np.array([1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0], np.float32)  # one pose matrix: row-major 3x4
+
+
+def rigid(object_of_vertex):
+    """Rigid objects: vertex i follows bone object_of_vertex[i] alone.  Returns (bones (n, 4) int32 {obj, 0, 0, 0}, weights (n, 4) float32 {1, 0, 0, 0})."""
+    obj = np.asarray(object_of_vertex)
+    if obj.ndim != 1 or not np.issubdtype(obj.dtype, np.integer):
+        raise ValueError(f"rigid: one integer object index a vertex expected, got {obj.dtype} {obj.shape}")
+    bones = np.zeros((obj.size, 4), np.int32)
+    bones[:, 0] = obj
+    weights = np.zeros((obj.size, 4), np.float32)
+    weights[:, 0] = 1.0
+    return bones, weights
+
+
+def identity_pose(n_bones):
+    """n_bones identity matrices (n_bones, 12) float32."""
+    return np.tile(IDENTITY, (int(n_bones), 1))
