@@ -55,6 +55,23 @@ struct DevBuf {
     size_t bytes = 0;
 };
 
+// An image plane a context owns beside its accumulator, and the shape of the image it was last written at: the accumulator's own (accum_shape: H, M, C) or packed rows
+// of float4 (packed_shape: N / A / G, D, T, B).  Whoever writes a plane stamps it; a reader asks whether it is current; glrtx_resize and a tracking switched off drop it.
+struct Shape {
+    int width = 0;
+    size_t pitch = 0;  // bytes from row to row
+    int rows = -1;     // (-1: never stamped)
+    bool operator==(const Shape &o) const { return width == o.width && pitch == o.pitch && rows == o.rows; }
+};
+struct Plane {
+    DevBuf buf;
+    Shape at;
+    void stamp(const Shape &s) { at = s; }
+    bool stamped() const { return at.rows >= 0; }
+    bool current(const Shape &s) const { return buf.p && at == s; }
+    void drop();
+};
+
 }  // namespace
 
 struct glrtx_ctx {
@@ -188,19 +205,18 @@ struct glrtx_ctx {
         glrtx_present_stats st{};
     } pres;
 
-    // Adaptive sampling (glrtx_render_adaptive): the half buffer H (every second sample; accumulator-sized, allocated on first use, pitch ad_pitch x ad_rows), and what the
+    // Adaptive sampling (glrtx_render_adaptive): the half buffer H (every second sample; of the accumulator's shape, allocated on first use), and what the
     // last selection wrote -- a mask byte per tile, the ascending list of active tiles, their count in a device word -- for ad_tiles tiles.
-    DevBuf adHalf, adMask, adList, adCount;
-    size_t ad_pitch = 0;
-    int ad_rows = 0, ad_tiles = 0, ad_tiles_x = 0;  // (ad_tiles, ad_tiles_x: the tile grid of the last selection)
+    Plane adHalf;
+    DevBuf adMask, adList, adCount;
+    int ad_tiles = 0, ad_tiles_x = 0;  // (the tile grid of the last selection)
     bool ad_selected = false;
 
-    // Denoising (glrtx_render_features / glrtx_denoise): the two feature planes, the filter's two ping-pong images and its result D, all packed rows of ft_w float4 over
-    // ft_rows rows -- the shape of the owned rows when the features were rendered; allocated on first use, released by glrtx_resize (and so by a partition change)
-    DevBuf ftN, ftA, ftCounter, dnP[2], dnD;
-    int ft_w = 0, ft_rows = -1;   // (-1: no features)
-    bool dn_have = false;         // D holds a result ...
-    int dn_w = 0, dn_rows = -1;   // ... of this shape: recorded where D is written (glrtx_denoise, glrtx_denoise_variance, glrtx_reweight -- which needs no feature planes)
+    // Denoising (glrtx_render_features / glrtx_denoise): the two feature planes, the filter's two ping-pong images and its result D, all packed rows of float4 --
+    // ftN's stamp is the shape of the owned rows when the features were rendered (A and G share it); allocated on first use, released by glrtx_resize (and so by a
+    // partition change).  D is stamped where it is written (glrtx_denoise, glrtx_denoise_variance, glrtx_reweight -- which needs no feature planes).
+    Plane ftN, dnD;
+    DevBuf ftA, ftCounter, dnP[2];
     // Reprojection (glrtx_reproject): the camera of the last glrtx_render_features (c2w[16], s2c[16]: the one the accumulator and the planes belong to), the spare
     // pair of feature planes and the spare accumulator (own pitch x owned rows) that the next call swaps in, and its two counters; allocated on first use,
     // released by glrtx_resize
@@ -217,30 +233,27 @@ struct glrtx_ctx {
     DevBuf ftG, ftG_spare, mtPos, mtNrm;
 
     // Variance guidance (glrtx_track_moments / glrtx_render_moments / glrtx_denoise_variance): the moments plane M {sum l, sum l^2, 0, count} at the accumulator's
-    // shape (mm_pitch x mm_rows; allocated on first use while tracking is on, zeroed with the accumulator, released by glrtx_resize and by switching tracking off),
+    // shape (allocated on first use while tracking is on, zeroed with the accumulator, released by glrtx_resize and by switching tracking off),
     // and the filter's three variance planes (V0 and the ping-pong pair: packed floats of the features' shape, released with them).
-    DevBuf mmM, mmM_spare, dnV[3];  // (mmM_spare: the second M the reprojections write, of M's shape, swapped as accum_spare is)
-    size_t mm_pitch = 0;
-    int mm_rows = 0;
+    Plane mmM;
+    DevBuf mmM_spare, dnV[3];  // (mmM_spare: the second M the reprojections write, of M's shape, swapped as accum_spare is)
     bool mm_on = false;
 
     // Firefly re-weighting (glrtx_track_cascades / glrtx_render_cascades / glrtx_reweight): the six cascade planes C_0 .. C_5 back to back, each of the accumulator's
-    // shape (rw_pitch x rw_rows; allocated on first use while tracking is on, zeroed with the accumulator and by the reprojections, released by glrtx_resize and by
+    // shape (allocated on first use while tracking is on, zeroed with the accumulator and by the reprojections, released by glrtx_resize and by
     // switching tracking off), and the bounds' start.
-    DevBuf rwC;
-    size_t rw_pitch = 0;
-    int rw_rows = 0;
+    Plane rwC;
     bool rw_on = false;
     float rw_start = 1.0f;
 
     // Tone mapping (glrtx_exposure_measure / glrtx_tonemap): the exposure block (tonemap::Exposure: the working histogram, then glrtx_exposure's image; allocated and
-    // zeroed on first use, kept across glrtx_resize) and the plane T (packed rows of tm_w float4 over tm_rows rows; released by glrtx_resize)
-    DevBuf tmExp, tmT;
-    int tm_w = 0, tm_rows = -1;   // (-1: no T)
+    // zeroed on first use, kept across glrtx_resize) and the plane T (packed rows of float4; released by glrtx_resize)
+    DevBuf tmExp;
+    Plane tmT;
 
-    // Bloom (glrtx_bloom): the plane B (packed rows of bl_w float4 over bl_rows rows) and the pyramid D_1 .. D_8 behind it; both released by glrtx_resize
-    DevBuf blB, blPyr;
-    int bl_w = 0, bl_rows = -1;   // (-1: no B)
+    // Bloom (glrtx_bloom): the plane B (packed rows of float4) and the pyramid D_1 .. D_8 behind it; both released by glrtx_resize
+    Plane blB;
+    DevBuf blPyr;
 
     bool count_rays = false;
     const char *last_kernel = "";  // name of the last render kernel launched (error reports)
@@ -281,6 +294,10 @@ void dev_free(DevBuf &b) {
     if (b.p) (void)hipFree(b.p);
     b.p = nullptr; b.bytes = 0;
 }
+
+void Plane::drop() { dev_free(buf); at = Shape{}; }
+Shape accum_shape(const glrtx_ctx *c) { return {c->width, c->pitch_bytes, c->owned_rows}; }
+Shape packed_shape(const glrtx_ctx *c) { return {c->width, (size_t)c->width * sizeof(float4), c->owned_rows}; }
 
 // diagnostic builds only: read and clear a device symbol (the traversal statistics, the step timing, the phase clocks)
 template <class Sym>
@@ -745,6 +762,65 @@ int ensure(glrtx_ctx *c, DevBuf &b, size_t bytes) {
     dev_free(b);
     HIP_TRY(c, hipMalloc(&b.p, std::max<size_t>(bytes, 64)));
     b.bytes = std::max<size_t>(bytes, 64);
+    return GLRTX_OK;
+}
+
+// `n_planes` planes of the accumulator's current shape back to back in P, zeroed on the context's stream: H, M and C on first use, at a clear, a bind or a
+// reprojection -- whenever the accumulator they sit beside starts again or changes shape.
+int plane_zero(glrtx_ctx *c, Plane &P, int n_planes = 1) {
+    const size_t bytes = (size_t)n_planes * c->pitch_bytes * (size_t)std::max(c->owned_rows, 1);
+    if (int rc = ensure(c, P.buf, bytes)) return rc;
+    HIP_TRY(c, hipMemsetAsync(P.buf.p, 0, bytes, c->stream));
+    P.stamp(accum_shape(c));
+    return GLRTX_OK;
+}
+
+// P about to be written at the image's current shape, as packed rows of float4 (N, D, T, B): room for it, and its stamp.
+int plane_packed(glrtx_ctx *c, Plane &P) {
+    if (int rc = ensure(c, P.buf, (size_t)c->width * (size_t)std::max(c->owned_rows, 1) * sizeof(float4))) return rc;
+    P.stamp(packed_shape(c));
+    return GLRTX_OK;
+}
+
+// The tail of every read-back: behind everything issued, the owned rows of `n_planes` planes that lie back to back at `src` (rows src_pitch apart) into the caller's
+// rows (dst_pitch apart, the planes back to back as well).  The caller has refused a dst_pitch below a row.
+int read_back(glrtx_ctx *c, const void *src, size_t src_pitch, void *dst, size_t dst_pitch, int n_planes = 1) {
+    if (int rc = glrtx_sync(c)) return rc;
+    const size_t rows = (size_t)c->owned_rows;
+    for (int k = 0; k < n_planes && rows > 0; k++)
+        HIP_TRY(c, hipMemcpy2D((char *)dst + (size_t)k * rows * dst_pitch, dst_pitch, (const char *)src + (size_t)k * rows * src_pitch, src_pitch,
+                               (size_t)c->width * sizeof(float4), rows, hipMemcpyDeviceToHost));
+    return GLRTX_OK;
+}
+
+// The tail of every resolve to bytes: the context's byte image at the current shape, `launch` (the pass that fills it, on the context's stream), then the rows to the
+// caller.  A member that owns no rows only waits.
+template <class Launch>
+int resolve_to_caller(glrtx_ctx *c, uint8_t *dst, size_t dst_pitch, Launch &&launch) {
+    if (c->owned_rows == 0) return glrtx_sync(c);
+    const size_t row = (size_t)c->width * 4;
+    if (int rc = ensure(c, c->rgba8, row * (size_t)c->owned_rows)) return rc;
+    if (int rc = launch((uchar4 *)c->rgba8.p)) return rc;
+    if (int rc = glrtx_sync(c)) return rc;
+    HIP_TRY(c, hipMemcpy2D(dst, dst_pitch, c->rgba8.p, row, row, (size_t)c->owned_rows, hipMemcpyDeviceToHost));
+    return GLRTX_OK;
+}
+
+// Device time of `launches` (one call's worth, on the context's stream) by itself: `reps` of them back to back between one pair of events, after a pass that
+// warms the device up.  A single launch between two events carries the command processor's latency on both sides, which says nothing about the kernel.
+template <class Launches>
+int burst_time(glrtx_ctx *c, int reps, float *ms_per_rep, Launches &&launches) {
+    for (int pass = 0; pass < 2; pass++) {
+        HIP_TRY(c, hipEventRecord(c->rs0, c->stream));
+        for (int i = 0; i < reps; i++)
+            if (int rc = launches()) return rc;
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipEventRecord(c->rs1, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    float ms = 0.f;
+    HIP_TRY(c, hipEventElapsedTime(&ms, c->rs0, c->rs1));
+    *ms_per_rep = ms / (float)reps;
     return GLRTX_OK;
 }
 
@@ -1448,11 +1524,11 @@ int wgwf_check(glrtx_ctx *c, const WgwfLaunch &L) {
     if (w.planes) ok = ok && L.planeBuf->bytes >= (size_t)std::max(L.n_planes, 1) * L.plane_f4 * sizeof(float4);
     if (L.k.adapt) ok = ok && !fed && !slot && w.planes && c->ad_selected && c->ad_tiles == (int)(total >> 6) && c->adList.bytes >= (total >> 6) * sizeof(int) &&
                         c->adMask.bytes >= (total >> 6);
-    if (L.req.kind == RenderReq::Adaptive) ok = ok && c->adHalf.bytes >= (size_t)c->ad_pitch * c->owned_rows && c->ad_pitch == c->pitch_bytes;
-    if (moments) ok = ok && !fed && !slot && w.planes && c->mmM.p && c->mm_pitch == c->pitch_bytes && c->mm_rows == c->owned_rows &&
-                      c->mmM.bytes >= c->pitch_bytes * (size_t)c->owned_rows;
-    if (L.req.kind == RenderReq::Cascades) ok = ok && !fed && !slot && w.planes && c->rwC.p && c->rw_pitch == c->pitch_bytes && c->rw_rows == c->owned_rows &&
-                                                 c->rwC.bytes >= (size_t)reweight::kCascades * c->pitch_bytes * (size_t)c->owned_rows;
+    const size_t acc_bytes = c->pitch_bytes * (size_t)c->owned_rows;
+    if (L.req.kind == RenderReq::Adaptive) ok = ok && c->adHalf.current(accum_shape(c)) && c->adHalf.buf.bytes >= acc_bytes;
+    if (moments) ok = ok && !fed && !slot && w.planes && c->mmM.current(accum_shape(c)) && c->mmM.buf.bytes >= acc_bytes;
+    if (L.req.kind == RenderReq::Cascades) ok = ok && !fed && !slot && w.planes && c->rwC.current(accum_shape(c)) &&
+                                                 c->rwC.buf.bytes >= (size_t)reweight::kCascades * acc_bytes;
     if (fed) ok = ok && n_frames >= 1 && n_frames <= fed_cap && fed_cap <= kFeedMaxFrames && slot->feed_d.bytes >= sizeof(FeedDev) && w.feed_host != nullptr &&
                   slot->chunks[(n_frames - 1) / kFeedChunkFrames].p != nullptr && slot->chunk_bytes == L.frame_bytes;
     if (!ok) return fail(c, GLRTX_EDEVICE, "internal: wgwf launch shapes inconsistent (ids %zu, max id %zu, grid %d of %zu slots (%d per CU), block_paths %d, frames %d, fed %d)", L.ids, max_id,
@@ -1517,11 +1593,11 @@ int wgwf_issue(glrtx_ctx *c, const WgwfLaunch &L) {
         const glrtx_ctx::Present &P = c->pres;
         const accumulate::Present ring{(uchar4 *)P.dev.p, (size_t)c->width * (size_t)c->owned_rows, P.ring, pres ? (int)(P.seq % (uint64_t)P.ring) : 0, P.inv_gamma, P.flip};
         if (L.req.kind == RenderReq::AdaptiveMoments) {
-            if (n_planes > 0) accumulate_launch(c, im, flat, accumulate::MomentsMasked{(float4 *)c->mmM.p, (const unsigned char *)c->adMask.p, L.tiles8_x});
-        } else if (adapt) accumulate_launch(c, im, flat, accumulate::Half{(float4 *)c->adHalf.p, (const unsigned char *)c->adMask.p, L.tiles8_x});
-        else if (L.req.kind == RenderReq::Moments) { if (n_planes > 0) accumulate_launch(c, im, flat, accumulate::Moments{(float4 *)c->mmM.p}); }
+            if (n_planes > 0) accumulate_launch(c, im, flat, accumulate::MomentsMasked{(float4 *)c->mmM.buf.p, (const unsigned char *)c->adMask.p, L.tiles8_x});
+        } else if (adapt) accumulate_launch(c, im, flat, accumulate::Half{(float4 *)c->adHalf.buf.p, (const unsigned char *)c->adMask.p, L.tiles8_x});
+        else if (L.req.kind == RenderReq::Moments) { if (n_planes > 0) accumulate_launch(c, im, flat, accumulate::Moments{(float4 *)c->mmM.buf.p}); }
         else if (L.req.kind == RenderReq::Cascades) {
-            if (n_planes > 0) accumulate_launch(c, im, flat, accumulate::Cascades{(float4 *)c->rwC.p, (size_t)L.a.pitch_f4 * (size_t)c->owned_rows, c->rw_start});
+            if (n_planes > 0) accumulate_launch(c, im, flat, accumulate::Cascades{(float4 *)c->rwC.buf.p, (size_t)L.a.pitch_f4 * (size_t)c->owned_rows, c->rw_start});
         }
         else if (fed && pres) accumulate_launch(c, im, feed, ring);
         else if (fed) accumulate_launch(c, im, feed, accumulate::None{});
@@ -1570,8 +1646,7 @@ int launch_wgwf(glrtx_ctx *c, const KernelArgs &a, const glrtx_params *p, const 
 
 // ---- denoising (glrtx_render_features, glrtx_denoise)
 void denoise_release(glrtx_ctx *c) {
-    dev_free(c->ftN); dev_free(c->ftA); dev_free(c->ftCounter); dev_free(c->dnP[0]); dev_free(c->dnP[1]); dev_free(c->dnD);
-    c->ft_w = 0; c->ft_rows = -1; c->dn_have = false; c->dn_w = 0; c->dn_rows = -1;
+    c->ftN.drop(); dev_free(c->ftA); dev_free(c->ftCounter); dev_free(c->dnP[0]); dev_free(c->dnP[1]); c->dnD.drop();
     dev_free(c->ftN_spare); dev_free(c->ftA_spare); dev_free(c->accum_spare); dev_free(c->rpCount);  // (glrtx_reproject's spares have the old shape too)
     c->rp_have = false;
     dev_free(c->ftG); dev_free(c->ftG_spare);
@@ -1722,15 +1797,6 @@ int reproject_motion_pass(glrtx_ctx *c, hipStream_t stream, const reproject::Com
 
 
 // ---- adaptive sampling (glrtx_render_adaptive)
-// The half buffer H at the accumulator's current shape, zeroed (on first adaptive use, at a clear or resize, and when the accumulator's pitch or rows have changed).
-int adapt_half_ensure(glrtx_ctx *c) {
-    const size_t bytes = c->pitch_bytes * (size_t)std::max(c->owned_rows, 1);
-    if (int rc = ensure(c, c->adHalf, bytes)) return rc;
-    HIP_TRY(c, hipMemsetAsync(c->adHalf.p, 0, bytes, c->stream));
-    c->ad_pitch = c->pitch_bytes; c->ad_rows = c->owned_rows;
-    return GLRTX_OK;
-}
-
 // Everything glrtx_render_adaptive refuses, checked before anything changes.  The megakernels have no tile list and the present ring no adaptive form.
 int adapt_check(glrtx_ctx *c, const glrtx_params *p, const float *seeds_xy, int n_frames, const glrtx_adaptive *cfg) {
     const char *fn = "glrtx_render_adaptive";
@@ -1753,8 +1819,8 @@ int adapt_check(glrtx_ctx *c, const glrtx_params *p, const float *seeds_xy, int 
 // (glrtx_render_adaptive_moments): from M, which the caller has made sure of, by adaptive_moments::select_kernel; H is neither read nor allocated.
 int adapt_select(glrtx_ctx *c, const glrtx_adaptive *cfg, bool from_moments) {
     const int tiles8_x = (c->width + 7) / 8, tiles8_y = (c->owned_rows + 7) / 8, n_tiles = tiles8_x * tiles8_y;
-    if (!from_moments && c->owned_rows > 0 && (!c->adHalf.p || c->ad_pitch != c->pitch_bytes || c->ad_rows != c->owned_rows))
-        if (int rc = adapt_half_ensure(c)) return rc;
+    if (!from_moments && c->owned_rows > 0 && !c->adHalf.current(accum_shape(c)))
+        if (int rc = plane_zero(c, c->adHalf)) return rc;  // (first adaptive use, or the accumulator's pitch or rows have changed)
     int rc;
     if ((rc = ensure(c, c->adMask, (size_t)n_tiles)) || (rc = ensure(c, c->adList, (size_t)n_tiles * sizeof(int))) || (rc = ensure(c, c->adCount, sizeof(unsigned))))
         return rc;
@@ -1763,10 +1829,10 @@ int adapt_select(glrtx_ctx *c, const glrtx_adaptive *cfg, bool from_moments) {
     if (n_tiles == 0) { HIP_TRY(c, hipMemsetAsync(c->adCount.p, 0, sizeof(unsigned), c->stream)); return GLRTX_OK; }
     const int pitch_f4 = (int)(c->pitch_bytes / sizeof(float4));
     if (from_moments)
-        hipLaunchKernelGGL(adaptive_moments::select_kernel, dim3((n_tiles + 3) / 4), dim3(256), 0, c->stream, (const float4 *)c->mmM.p, pitch_f4, c->width,
+        hipLaunchKernelGGL(adaptive_moments::select_kernel, dim3((n_tiles + 3) / 4), dim3(256), 0, c->stream, (const float4 *)c->mmM.buf.p, pitch_f4, c->width,
                            c->owned_rows, tiles8_x, n_tiles, cfg->threshold, cfg->min_samples, (unsigned char *)c->adMask.p, (float *)nullptr);
     else
-        hipLaunchKernelGGL(adaptive_select_kernel, dim3((n_tiles + 3) / 4), dim3(256), 0, c->stream, (const float4 *)c->accum, (const float4 *)c->adHalf.p, pitch_f4, c->width,
+        hipLaunchKernelGGL(adaptive_select_kernel, dim3((n_tiles + 3) / 4), dim3(256), 0, c->stream, (const float4 *)c->accum, (const float4 *)c->adHalf.buf.p, pitch_f4, c->width,
                            c->owned_rows, tiles8_x, n_tiles, cfg->threshold, cfg->min_samples, (unsigned char *)c->adMask.p, (float *)nullptr);
     HIP_TRY(c, hipGetLastError());
     hipLaunchKernelGGL(adaptive_compact_kernel, dim3(1), dim3(kAdaptCompactThreads), 0, c->stream, (const unsigned char *)c->adMask.p, n_tiles, (int *)c->adList.p,
@@ -1776,16 +1842,6 @@ int adapt_select(glrtx_ctx *c, const glrtx_adaptive *cfg, bool from_moments) {
 }
 
 // ---- variance guidance (glrtx_track_moments, glrtx_render_moments, glrtx_denoise_variance)
-// The moments plane M at the accumulator's current shape, zeroed (on first use, at a clear and at a bind; the reprojections carry it into mmM_spare and swap).
-int moments_ensure(glrtx_ctx *c) {
-    const size_t bytes = c->pitch_bytes * (size_t)std::max(c->owned_rows, 1);
-    if (int rc = ensure(c, c->mmM, bytes)) return rc;
-    HIP_TRY(c, hipMemsetAsync(c->mmM.p, 0, bytes, c->stream));
-    c->mm_pitch = c->pitch_bytes; c->mm_rows = c->owned_rows;
-    return GLRTX_OK;
-}
-bool moments_have(const glrtx_ctx *c) { return c->mm_on && c->mmM.p && c->mm_pitch == c->pitch_bytes && c->mm_rows == c->owned_rows; }
-
 // Everything a render call that folds its planes into a side plane refuses (glrtx_render_moments, glrtx_render_cascades), checked before anything changes:
 // glrtx_render_adaptive's list, the volume and the plane's tracking being off (`tracked`; `untracked` says so).
 int side_plane_check(glrtx_ctx *c, const glrtx_params *p, const float *seeds_xy, int n_frames, const char *fn, bool tracked, const char *untracked) {
@@ -1817,15 +1873,6 @@ int adapt_moments_check(glrtx_ctx *c, const glrtx_params *p, const float *seeds_
 }
 
 // ---- firefly re-weighting (glrtx_track_cascades, glrtx_render_cascades, glrtx_reweight)
-// The cascade planes C at the accumulator's current shape, zeroed (on first use, at a clear, at a bind, at a reprojection, at another start).
-int cascades_ensure(glrtx_ctx *c) {
-    const size_t bytes = (size_t)reweight::kCascades * c->pitch_bytes * (size_t)std::max(c->owned_rows, 1);
-    if (int rc = ensure(c, c->rwC, bytes)) return rc;
-    HIP_TRY(c, hipMemsetAsync(c->rwC.p, 0, bytes, c->stream));
-    c->rw_pitch = c->pitch_bytes; c->rw_rows = c->owned_rows;
-    return GLRTX_OK;
-}
-bool cascades_have(const glrtx_ctx *c) { return c->rw_on && c->rwC.p && c->rw_pitch == c->pitch_bytes && c->rw_rows == c->owned_rows; }
 bool cascade_start_ok(float s) { return s >= 0x1p-20f && s <= 0x1p20f; }  // (a NaN fails both)
 
 int reweight_cfg_check(glrtx_ctx *c, const glrtx_reweight_cfg *k, const char *fn) {
@@ -1841,10 +1888,6 @@ int reweight_pass(glrtx_ctx *c, hipStream_t stream, const float4 *C, size_t plan
     HIP_TRY(c, hipGetLastError());
     return GLRTX_OK;
 }
-
-// D holds a result of the image's current shape.  (For every sequence of calls without glrtx_reweight this is what the feature planes' shape used to say: D is
-// written only at the current shape -- by the filters, whose feature planes have it -- and glrtx_resize, the only call that changes the shape, drops D.)
-bool denoised_have(const glrtx_ctx *c) { return c->dn_have && c->dnD.p && c->dn_w == c->width && c->dn_rows == c->owned_rows; }
 
 // ---- tone mapping (glrtx_exposure_measure, glrtx_tonemap, glrtx_resolve_tonemapped_rgba8)
 static_assert(sizeof(tonemap::Exposure) == tonemap::kExposureOut + sizeof(glrtx_exposure), "tonemap::Exposure ends with glrtx_exposure's image");
@@ -1876,17 +1919,32 @@ int exposure_ensure(glrtx_ctx *c) {
     return GLRTX_OK;
 }
 
+// The HDR image a tone-mapping or bloom cfg names: 0 the accumulator, 1 the image D -- of the current shape, or the call is refused.
+int hdr_source(glrtx_ctx *c, int source, const char *fn, const float4 *&src, int &pitch_f4) {
+    if (source == 1) {
+        if (!c->dnD.current(packed_shape(c)))
+            return fail(c, GLRTX_EINVAL, "%s: source = 1 without a denoised image of the current shape (call glrtx_denoise or glrtx_denoise_variance first)", fn);
+        src = (const float4 *)c->dnD.buf.p; pitch_f4 = c->width;
+    } else {
+        src = c->accum; pitch_f4 = (int)(c->pitch_bytes / sizeof(float4));
+    }
+    return GLRTX_OK;
+}
+
 // The context checks every tone-mapping call shares, and the source the cfg names.
 int tonemap_source(glrtx_ctx *c, const glrtx_tonemap_cfg *k, const char *fn, const float4 *&src, int &pitch_f4) {
     if (int rc = tonemap_cfg_check(c, k, fn)) return rc;
     if (!c->accum || c->width < 1) return fail(c, GLRTX_EINVAL, "%s: no accumulator (call glrtx_resize)", fn);
-    if (k->source == 1) {
-        if (!denoised_have(c))
-            return fail(c, GLRTX_EINVAL, "%s: source = 1 without a denoised image of the current shape (call glrtx_denoise or glrtx_denoise_variance first)", fn);
-        src = (const float4 *)c->dnD.p; pitch_f4 = c->width;
-    } else {
-        src = c->accum; pitch_f4 = (int)(c->pitch_bytes / sizeof(float4));
-    }
+    return hdr_source(c, k->source, fn, src, pitch_f4);
+}
+
+// What the two tone-mapping calls that read B share: the cfg with its source unread, and B of the current shape.
+int tonemap_bloomed_cfg(glrtx_ctx *c, const glrtx_tonemap_cfg *cfg, const char *fn, glrtx_tonemap_cfg &k) {
+    if (!cfg) return fail(c, GLRTX_EINVAL, "%s: NULL cfg", fn);
+    k = *cfg;
+    k.source = 0;  // (not read: the source is B)
+    if (int rc = tonemap_cfg_check(c, &k, fn)) return rc;
+    if (!c->blB.current(packed_shape(c))) return fail(c, GLRTX_EINVAL, "%s: no bloomed plane (call glrtx_bloom first)", fn);
     return GLRTX_OK;
 }
 
@@ -1948,14 +2006,7 @@ int bloom_source(glrtx_ctx *c, const glrtx_bloom_cfg *k, const char *fn, const f
     if (int rc = bloom_cfg_check(c, k, fn)) return rc;
     if (!c->accum || c->width < 1 || c->owned_rows < 1) return fail(c, GLRTX_EINVAL, "%s: no accumulator (call glrtx_resize)", fn);
     if (c->world > 1) return fail(c, GLRTX_EINVAL, "%s: the context is partitioned (rank %d of %d): the glow would stop at every stripe's seam", fn, c->rank, c->world);
-    if (k->source == 1) {
-        if (!denoised_have(c))
-            return fail(c, GLRTX_EINVAL, "%s: source = 1 without a denoised image of the current shape (call glrtx_denoise or glrtx_denoise_variance first)", fn);
-        src = (const float4 *)c->dnD.p; pitch_f4 = c->width;
-    } else {
-        src = c->accum; pitch_f4 = (int)(c->pitch_bytes / sizeof(float4));
-    }
-    return GLRTX_OK;
+    return hdr_source(c, k->source, fn, src, pitch_f4);
 }
 
 // The down chain on `stream`: the source through the bright pass to D_1, then D_1 .. D_levels into the packed pyramid.
@@ -1982,13 +2033,11 @@ int bloom_up_passes(glrtx_ctx *c, hipStream_t stream, const float4 *src, int pit
     HIP_TRY(c, hipGetLastError());
     return GLRTX_OK;
 }
-// B's and the pyramid's allocations (the pyramid always at its eight-level size: a shape has one)
+// B's and the pyramid's allocations (the pyramid always at its eight-level size: a shape has one); B is about to be written
 int bloom_ensure(glrtx_ctx *c) {
-    const size_t px = (size_t)c->width * (size_t)c->owned_rows;
-    if (int rc = ensure(c, c->blB, px * sizeof(float4))) return rc;
-    return ensure(c, c->blPyr, bloom_levels(c->width, c->owned_rows, 8).at[9] * sizeof(float4));
+    if (int rc = ensure(c, c->blPyr, bloom_levels(c->width, c->owned_rows, 8).at[9] * sizeof(float4))) return rc;
+    return plane_packed(c, c->blB);
 }
-bool bloom_have(const glrtx_ctx *c) { return c->blB.p && c->bl_w == c->width && c->bl_rows == c->owned_rows; }
 
 }  // namespace
 
@@ -2104,11 +2153,11 @@ void glrtx_destroy(glrtx_ctx *c) {
     }
     dev_free(c->spheres); dev_free(c->sphereMat); dev_free(c->volDensity); dev_free(c->volTemp); dev_free(c->forks); dev_free(c->cnodes); dev_free(c->cranks); dev_free(c->nrms); dev_free(c->mats); dev_free(c->lights); dev_free(c->vine);
     dev_free(c->accum_own); dev_free(c->counter); dev_free(c->rgba8); dev_free(c->work);
-    dev_free(c->adHalf); dev_free(c->adMask); dev_free(c->adList); dev_free(c->adCount);
-    dev_free(c->mmM); dev_free(c->mmM_spare);
-    dev_free(c->rwC);
-    dev_free(c->tmExp); dev_free(c->tmT);
-    dev_free(c->blB); dev_free(c->blPyr);
+    c->adHalf.drop(); dev_free(c->adMask); dev_free(c->adList); dev_free(c->adCount);
+    c->mmM.drop(); dev_free(c->mmM_spare);
+    c->rwC.drop();
+    dev_free(c->tmExp); c->tmT.drop();
+    c->blB.drop(); dev_free(c->blPyr);
     denoise_release(c);
     dev_free(c->mtPos); dev_free(c->mtNrm);
     dev_free(c->wfState); dev_free(c->wfQ); dev_free(c->wfSeeds); dev_free(c->wfPlanes);
@@ -2401,17 +2450,7 @@ int glrtx_debug_skin_burst(glrtx_ctx *c, int reps, float *ms_per_launch) {
     seal_feed(c);
     HIP_TRY(c, hipSetDevice(c->device));
     const skin::Args a{(const unsigned *)c->sk.rest.p, (const uint4 *)c->sk.rig.p, (const float4 *)c->sk.pose.p, (unsigned *)c->rf.vert.p, n_vert};
-    for (int pass = 0; pass < 2; pass++) {  // (the first pass warms the device up)
-        HIP_TRY(c, hipEventRecord(c->rs0, c->stream));
-        for (int i = 0; i < reps; i++) skin_launch(a, c->stream);
-        HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, hipEventRecord(c->rs1, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-    }
-    float ms = 0.f;
-    HIP_TRY(c, hipEventElapsedTime(&ms, c->rs0, c->rs1));
-    *ms_per_launch = ms / (float)reps;
-    return GLRTX_OK;
+    return burst_time(c, reps, ms_per_launch, [&] { skin_launch(a, c->stream); return GLRTX_OK; });
 }
 
 namespace {
@@ -2700,14 +2739,11 @@ int glrtx_upload_volume(glrtx_ctx *c, const float *density, const float *tempera
 static int vmath_run(const char *fn, const float *in, size_t n_in, const float *grid, size_t n_grid, const VolArgs *v, float *out, size_t n_out, int op) {
     if (n_in == 0) return GLRTX_OK;
     if (n_in > (size_t)INT32_MAX / 4) return fail(nullptr, GLRTX_EINVAL, "%s: n = %zu too large", fn, n_in);
-    float *d_in = nullptr, *d_out = nullptr, *d_grid = nullptr;
-    int rc = GLRTX_OK;
-    hipError_t e = hipMalloc(&d_in, n_in * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(&d_out, n_out * sizeof(float));
-    if (e == hipSuccess && grid) e = hipMalloc(&d_grid, n_grid * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(d_in, in, n_in * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess && grid) e = hipMemcpy(d_grid, grid, n_grid * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
+    DebugScratch s;
+    const float *d_in = s.alloc<float>(n_in * sizeof(float), in);
+    float *d_out = s.alloc<float>(n_out * sizeof(float));
+    const float *d_grid = grid ? s.alloc<float>(n_grid * sizeof(float), grid) : nullptr;
+    if (s.ok()) {
         if (v) {
             VolArgs va = *v;
             va.density = d_grid; va.temperature = d_grid;
@@ -2717,15 +2753,11 @@ static int vmath_run(const char *fn, const float *in, size_t n_in, const float *
             const int n = (int)n_in;
             hipLaunchKernelGGL(volume_math_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, op, d_in, n, d_out);
         }
-        e = hipGetLastError();
+        s.e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy(out, d_out, n_out * sizeof(float), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) rc = fail(nullptr, GLRTX_EDEVICE, "%s: %s", fn, hipGetErrorString(e));
-    if (d_in) (void)hipFree(d_in);
-    if (d_out) (void)hipFree(d_out);
-    if (d_grid) (void)hipFree(d_grid);
-    return rc;
+    s.sync();
+    s.download(out, d_out, n_out * sizeof(float));
+    return s.result(GLRTX_OK, fn);
 }
 
 int glrtx_debug_volume_math(int op, const float *in, size_t n, float *out) {
@@ -2778,10 +2810,10 @@ int glrtx_resize(glrtx_ctx *c, int width, int height) {
                         width, height, rows, c->pitch_bytes, c->bound_rows);
     }
     denoise_release(c);  // (the feature planes and the filter's images have the old shape; the stream is idle)
-    dev_free(c->mmM); dev_free(c->mmM_spare);  // (so has the moments plane: allocated again on its next use)
-    dev_free(c->rwC);  // (and the cascade planes)
-    dev_free(c->tmT); c->tm_w = 0; c->tm_rows = -1;  // (and the tone-mapped plane; the exposure block has no shape and stays)
-    dev_free(c->blB); dev_free(c->blPyr); c->bl_w = 0; c->bl_rows = -1;  // (and the bloomed plane with its pyramid)
+    c->mmM.drop(); dev_free(c->mmM_spare);  // (so has the moments plane: allocated again on its next use)
+    c->rwC.drop();  // (and the cascade planes)
+    c->tmT.drop();  // (and the tone-mapped plane; the exposure block has no shape and stays)
+    c->blB.drop(); dev_free(c->blPyr);  // (and the bloomed plane with its pyramid)
     c->width = width; c->height = height;
     c->owned_rows = owned_rows_of(height, c->rank, c->world, c->stripe);
     c->st.width = width; c->st.height = height; c->st.owned_rows = c->owned_rows;
@@ -2807,9 +2839,9 @@ int glrtx_clear(glrtx_ctx *c) {
     if (!c->accum) return fail(c, GLRTX_EINVAL, "glrtx_clear: no accumulator (call glrtx_resize first)");
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipMemsetAsync(c->accum, 0, c->pitch_bytes * (size_t)c->owned_rows, c->stream));
-    if (c->adHalf.p && (rc_ = adapt_half_ensure(c))) return rc_;  // (the half buffer follows the accumulator: zeroed, at the current size)
-    if (c->mmM.p && (rc_ = moments_ensure(c))) return rc_;        // (and so does the moments plane)
-    if (c->rwC.p && (rc_ = cascades_ensure(c))) return rc_;       // (and so do the cascade planes)
+    if (c->adHalf.buf.p && (rc_ = plane_zero(c, c->adHalf))) return rc_;  // (the half buffer follows the accumulator: zeroed, at the current size)
+    if (c->mmM.buf.p && (rc_ = plane_zero(c, c->mmM))) return rc_;        // (and so does the moments plane)
+    if (c->rwC.buf.p && (rc_ = plane_zero(c, c->rwC, reweight::kCascades))) return rc_;  // (and so do the cascade planes)
     c->pres.frame = 0;  // (images already produced keep their numbers)
     return GLRTX_OK;
 }
@@ -2833,9 +2865,9 @@ int glrtx_bind_accum(glrtx_ctx *c, void *device_ptr, size_t pitch_bytes, int cap
     c->bound_rows = capacity_rows;
     c->accum = (float4 *)device_ptr;
     c->pitch_bytes = pitch_bytes;
-    if (c->mmM.p) { if (int rc = moments_ensure(c)) return rc; }  // (another accumulator: the moments of the old one's samples say nothing about it)
-    if (c->rwC.p) { if (int rc = cascades_ensure(c)) return rc; } // (and neither do its cascades)
-    if (c->adHalf.p) return adapt_half_ensure(c);  // (another accumulator: the half buffer of the old one would be compared with unrelated samples)
+    if (c->mmM.buf.p) { if (int rc = plane_zero(c, c->mmM)) return rc; }  // (another accumulator: the moments of the old one's samples say nothing about it)
+    if (c->rwC.buf.p) { if (int rc = plane_zero(c, c->rwC, reweight::kCascades)) return rc; }  // (and neither do its cascades)
+    if (c->adHalf.buf.p) return plane_zero(c, c->adHalf);  // (another accumulator: the half buffer of the old one would be compared with unrelated samples)
     return GLRTX_OK;
 }
 
@@ -2921,18 +2953,28 @@ int glrtx_render(glrtx_ctx *c, const glrtx_params *p) {
     return render_one(c, p, RenderReq{});
 }
 
-// Adaptive call: the selection, then n_frames frames of the active tiles only, in launches of at most what the frames-in-flight budget allows -- all of them on the
-// selection made here, at the start of the call.  Never a fed launch: an open one is sealed first, so that its frames are accumulated before these.
+// What the four render calls with a side plane share once their refusals are past: the plane they fold into at the accumulator's shape (`plane`; a plane of zeros on
+// first use; none for H, which the selection itself makes sure of), the selection (`select`: its cfg, or none), then n_frames frames of `kind` in launches of at most
+// what the frames-in-flight budget allows -- all of them on the selection made here, at the start of the call.  Never a fed launch: an open one is sealed first, so
+// that its frames are accumulated before these.
+static int render_side(glrtx_ctx *c, const glrtx_params *p, const float *seeds_xy, int n_frames, RenderReq::Kind kind, Plane *plane, const glrtx_adaptive *select) {
+    seal_feed(c);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (plane && !plane->current(accum_shape(c)))
+        if (int rc = plane_zero(c, *plane, kind == RenderReq::Cascades ? reweight::kCascades : 1)) return rc;
+    if (select)
+        if (int rc = adapt_select(c, select, kind == RenderReq::AdaptiveMoments)) return rc;
+    if (n_frames == 0 || c->owned_rows == 0) { c->st.launches += (uint64_t)n_frames; return GLRTX_OK; }
+    const int rc = render_helpings(c, p, seeds_xy, n_frames, std::min(n_frames, frames_cap(c, p, 1)), kind);
+    seal_feed(c);  // (the next render call starts a launch of its own)
+    return rc;
+}
+
+// Adaptive call: the selection from H, then n_frames frames of the active tiles only.
 int glrtx_render_adaptive(glrtx_ctx *c, const glrtx_params *p, const float *seeds_xy, int n_frames, const glrtx_adaptive *cfg) {
     if (!c) return GLRTX_EINVAL;
     if (int rc = adapt_check(c, p, seeds_xy, n_frames, cfg)) return rc;
-    seal_feed(c);
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (int rc = adapt_select(c, cfg, false)) return rc;
-    if (n_frames == 0 || c->owned_rows == 0) { c->st.launches += (uint64_t)n_frames; return GLRTX_OK; }
-    const int rc = render_helpings(c, p, seeds_xy, n_frames, std::min(n_frames, frames_cap(c, p, 1)), RenderReq::Adaptive);
-    seal_feed(c);  // (the next render call starts a launch of its own)
-    return rc;
+    return render_side(c, p, seeds_xy, n_frames, RenderReq::Adaptive, nullptr, cfg);
 }
 
 int glrtx_adaptive_active_tiles(glrtx_ctx *c, int *active, int *total) {
@@ -2960,47 +3002,59 @@ int glrtx_read_tile_mask(glrtx_ctx *c, uint8_t *dst) {
 
 int glrtx_read_adaptive_half(glrtx_ctx *c, float *dst, size_t dst_pitch_bytes) {
     if (!c || !dst) return GLRTX_EINVAL;
-    if (!c->adHalf.p) return fail(c, GLRTX_EINVAL, "glrtx_read_adaptive_half: no half buffer (no adaptive call yet)");
-    const size_t row = (size_t)c->width * sizeof(float4);
-    if (dst_pitch_bytes < row) return fail(c, GLRTX_EINVAL, "glrtx_read_adaptive_half: dst pitch too small");
-    if (c->ad_pitch != c->pitch_bytes || c->ad_rows != c->owned_rows) return fail(c, GLRTX_EINVAL, "glrtx_read_adaptive_half: the accumulator changed shape since the last adaptive call");
-    if (int rc = glrtx_sync(c)) return rc;
-    if (c->owned_rows == 0) return GLRTX_OK;
-    HIP_TRY(c, hipMemcpy2D(dst, dst_pitch_bytes, c->adHalf.p, c->ad_pitch, row, (size_t)c->owned_rows, hipMemcpyDeviceToHost));
-    return GLRTX_OK;
+    if (!c->adHalf.buf.p) return fail(c, GLRTX_EINVAL, "glrtx_read_adaptive_half: no half buffer (no adaptive call yet)");
+    if (dst_pitch_bytes < (size_t)c->width * sizeof(float4)) return fail(c, GLRTX_EINVAL, "glrtx_read_adaptive_half: dst pitch too small");
+    if (!c->adHalf.current(accum_shape(c))) return fail(c, GLRTX_EINVAL, "glrtx_read_adaptive_half: the accumulator changed shape since the last adaptive call");
+    return read_back(c, c->adHalf.buf.p, c->pitch_bytes, dst, dst_pitch_bytes);
 }
+
+}  // extern "C"
+// The two debug selections: `in` (the accumulator and H, or M) on the device, `select` (the one launch they differ in: input planes, mask, errors), the compaction,
+// and the results back.
+template <class Select>
+static int debug_select(const char *fn, std::initializer_list<const float *> in, int width, int rows, uint8_t *mask_out, float *err_out, int *list_out, int *count_out,
+                        Select &&select) {
+    if (width < 1 || rows < 1 || width > 65536 || rows > 65536) return fail(nullptr, GLRTX_EINVAL, "%s: bad size %dx%d", fn, width, rows);
+    if (!mask_out || std::find(in.begin(), in.end(), nullptr) != in.end()) return fail(nullptr, GLRTX_EINVAL, "%s: NULL buffer", fn);
+    const int tiles8_x = (width + 7) / 8, n_tiles = tiles8_x * ((rows + 7) / 8);
+    DebugScratch s;
+    const float4 *d_in[2] = {nullptr, nullptr};
+    int n_in = 0;
+    for (const float *a : in) d_in[n_in++] = s.alloc((size_t)width * rows * sizeof(float4), a);
+    unsigned char *d_mask = s.alloc<unsigned char>((size_t)n_tiles);
+    float *d_err = s.alloc<float>((size_t)n_tiles * sizeof(float));
+    int *d_list = s.alloc<int>((size_t)n_tiles * sizeof(int));
+    unsigned *d_count = s.alloc<unsigned>(sizeof(unsigned));
+    if (s.ok()) {
+        select(d_in, tiles8_x, n_tiles, d_mask, d_err);
+        hipLaunchKernelGGL(adaptive_compact_kernel, dim3(1), dim3(kAdaptCompactThreads), 0, 0, (const unsigned char *)d_mask, n_tiles, d_list, d_count);
+        s.e = hipGetLastError();
+    }
+    s.sync();
+    s.download(mask_out, d_mask, (size_t)n_tiles);
+    s.download(err_out, d_err, (size_t)n_tiles * sizeof(float));
+    s.download(list_out, d_list, (size_t)n_tiles * sizeof(int));
+    s.download(count_out, d_count, sizeof(int));
+    return s.result(GLRTX_OK, fn);
+}
+extern "C" {
 
 int glrtx_debug_adaptive_select(const float *accum, const float *half, int width, int rows, float threshold, int min_samples, uint8_t *mask_out, float *err_out,
                                 int *list_out, int *count_out) {
-    const char *fn = "glrtx_debug_adaptive_select";
-    if (width < 1 || rows < 1 || width > 65536 || rows > 65536) return fail(nullptr, GLRTX_EINVAL, "%s: bad size %dx%d", fn, width, rows);
-    if (!accum || !half || !mask_out) return fail(nullptr, GLRTX_EINVAL, "%s: NULL buffer", fn);
-    const int tiles8_x = (width + 7) / 8, n_tiles = tiles8_x * ((rows + 7) / 8);
-    const size_t px_bytes = (size_t)width * rows * sizeof(float4);
-    void *d_acc = nullptr, *d_half = nullptr, *d_mask = nullptr, *d_err = nullptr, *d_list = nullptr, *d_count = nullptr;
-    hipError_t e = hipMalloc(&d_acc, px_bytes);
-    if (e == hipSuccess) e = hipMalloc(&d_half, px_bytes);
-    if (e == hipSuccess) e = hipMalloc(&d_mask, (size_t)n_tiles);
-    if (e == hipSuccess) e = hipMalloc(&d_err, (size_t)n_tiles * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(&d_list, (size_t)n_tiles * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc(&d_count, sizeof(unsigned));
-    if (e == hipSuccess) e = hipMemcpy(d_acc, accum, px_bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_half, half, px_bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(adaptive_select_kernel, dim3((n_tiles + 3) / 4), dim3(256), 0, 0, (const float4 *)d_acc, (const float4 *)d_half, width, width, rows, tiles8_x,
-                           n_tiles, threshold, min_samples, (unsigned char *)d_mask, (float *)d_err);
-        hipLaunchKernelGGL(adaptive_compact_kernel, dim3(1), dim3(kAdaptCompactThreads), 0, 0, (const unsigned char *)d_mask, n_tiles, (int *)d_list, (unsigned *)d_count);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy(mask_out, d_mask, (size_t)n_tiles, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && err_out) e = hipMemcpy(err_out, d_err, (size_t)n_tiles * sizeof(float), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && list_out) e = hipMemcpy(list_out, d_list, (size_t)n_tiles * sizeof(int), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && count_out) e = hipMemcpy(count_out, d_count, sizeof(int), hipMemcpyDeviceToHost);
-    const int rc = e != hipSuccess ? fail(nullptr, GLRTX_EDEVICE, "%s: %s", fn, hipGetErrorString(e)) : GLRTX_OK;
-    for (void *q : {d_acc, d_half, d_mask, d_err, d_list, d_count})
-        if (q) (void)hipFree(q);
-    return rc;
+    return debug_select("glrtx_debug_adaptive_select", {accum, half}, width, rows, mask_out, err_out, list_out, count_out,
+                        [&](const float4 *const *in, int tiles8_x, int n_tiles, unsigned char *mask, float *err) {
+                            hipLaunchKernelGGL(adaptive_select_kernel, dim3((n_tiles + 3) / 4), dim3(256), 0, 0, in[0], in[1], width, width, rows, tiles8_x, n_tiles,
+                                               threshold, min_samples, mask, err);
+                        });
+}
+
+int glrtx_debug_adaptive_select_moments(const float *moments, int width, int rows, float threshold, int min_samples, uint8_t *mask_out, float *err_out, int *list_out,
+                                        int *count_out) {
+    return debug_select("glrtx_debug_adaptive_select_moments", {moments}, width, rows, mask_out, err_out, list_out, count_out,
+                        [&](const float4 *const *in, int tiles8_x, int n_tiles, unsigned char *mask, float *err) {
+                            hipLaunchKernelGGL(adaptive_moments::select_kernel, dim3((n_tiles + 3) / 4), dim3(256), 0, 0, in[0], width, width, rows, tiles8_x, n_tiles,
+                                               threshold, min_samples, mask, err);
+                        });
 }
 
 
@@ -3018,10 +3072,9 @@ int glrtx_render_features(glrtx_ctx *c, const glrtx_params *p) {
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t bytes = (size_t)c->width * (size_t)std::max(c->owned_rows, 1) * sizeof(float4);
     int rc;
-    if ((rc = ensure(c, c->ftN, bytes)) || (rc = ensure(c, c->ftA, bytes)) || (rc = ensure(c, c->ftCounter, sizeof(unsigned)))) return rc;
+    if ((rc = ensure(c, c->ftA, bytes)) || (rc = ensure(c, c->ftCounter, sizeof(unsigned)))) return rc;
     const bool geom = c->mt_on;  // glrtx_track_motion: the *_geom kernels, which write G as well
-    if (geom && (rc = ensure(c, c->ftG, bytes))) return rc;
-    c->ft_w = c->width; c->ft_rows = c->owned_rows;
+    if ((geom && (rc = ensure(c, c->ftG, bytes))) || (rc = plane_packed(c, c->ftN))) return rc;
     const auto planes_written = [&]() {  // (glrtx_track_motion; only once nothing can fail any more) the scene as it stands is what these planes show
         if (geom) { c->mt_g_have = true; c->mt_geom = glrtx_ctx::kMtCurrent; }
         return GLRTX_OK;
@@ -3052,7 +3105,7 @@ int glrtx_render_features(glrtx_ctx *c, const glrtx_params *p) {
     a.owned_rows = c->owned_rows; a.rank = c->rank; a.world = c->world; a.stripe = c->stripe;
     a.tiles8_x = tiles8_x;
     a.n = (unsigned)(tiles8_x * tiles8_y) * 64u;
-    a.out_n = (float4 *)c->ftN.p; a.out_a = (float4 *)c->ftA.p;
+    a.out_n = (float4 *)c->ftN.buf.p; a.out_a = (float4 *)c->ftA.p;
     a.counter = (unsigned *)c->ftCounter.p;
     std::memcpy(c->ft_cam, a.cam, sizeof c->ft_cam);  // (glrtx_reproject: the camera these planes belong to)
     const size_t needed = (a.n + kBlockThreads - 1) / kBlockThreads;
@@ -3071,10 +3124,10 @@ int glrtx_render_features(glrtx_ctx *c, const glrtx_params *p) {
 }
 
 static int denoise_shape_check(glrtx_ctx *c, const char *fn, bool need_result) {
-    if (need_result && denoised_have(c)) return GLRTX_OK;  // (glrtx_reweight writes D without feature planes; otherwise the refusals below are what they were)
-    if (c->ft_rows < 0 || !c->ftN.p) return fail(c, GLRTX_EINVAL, "%s: no feature planes (call glrtx_render_features first)", fn);
-    if (c->ft_w != c->width || c->ft_rows != c->owned_rows) return fail(c, GLRTX_EINVAL, "%s: the image changed shape since the features were rendered", fn);
-    if (need_result && !c->dn_have) return fail(c, GLRTX_EINVAL, "%s: no denoised image (call glrtx_denoise first)", fn);
+    if (need_result && c->dnD.current(packed_shape(c))) return GLRTX_OK;  // (glrtx_reweight writes D without feature planes; otherwise the refusals below are what they were)
+    if (!c->ftN.stamped() || !c->ftN.buf.p) return fail(c, GLRTX_EINVAL, "%s: no feature planes (call glrtx_render_features first)", fn);
+    if (!c->ftN.current(packed_shape(c))) return fail(c, GLRTX_EINVAL, "%s: the image changed shape since the features were rendered", fn);
+    if (need_result && !c->dnD.stamped()) return fail(c, GLRTX_EINVAL, "%s: no denoised image (call glrtx_denoise first)", fn);
     return GLRTX_OK;
 }
 
@@ -3084,11 +3137,8 @@ int glrtx_read_features(glrtx_ctx *c, float *normal_depth, float *albedo_id, siz
     if (int rc = denoise_shape_check(c, fn, false)) return rc;
     const size_t row = (size_t)c->width * sizeof(float4);
     if (pitch_bytes < row) return fail(c, GLRTX_EINVAL, "%s: pitch too small", fn);
-    if (int rc = glrtx_sync(c)) return rc;
-    if (c->owned_rows == 0) return GLRTX_OK;
-    HIP_TRY(c, hipMemcpy2D(normal_depth, pitch_bytes, c->ftN.p, row, row, (size_t)c->owned_rows, hipMemcpyDeviceToHost));
-    HIP_TRY(c, hipMemcpy2D(albedo_id, pitch_bytes, c->ftA.p, row, row, (size_t)c->owned_rows, hipMemcpyDeviceToHost));
-    return GLRTX_OK;
+    if (int rc = read_back(c, c->ftN.buf.p, row, normal_depth, pitch_bytes)) return rc;
+    return read_back(c, c->ftA.p, row, albedo_id, pitch_bytes);
 }
 
 int glrtx_denoise(glrtx_ctx *c, const glrtx_denoise_cfg *cfg) {
@@ -3102,11 +3152,10 @@ int glrtx_denoise(glrtx_ctx *c, const glrtx_denoise_cfg *cfg) {
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t bytes = (size_t)c->width * (size_t)std::max(c->owned_rows, 1) * sizeof(float4);
     int rc;
-    if ((rc = ensure(c, c->dnP[0], bytes)) || (rc = ensure(c, c->dnP[1], bytes)) || (rc = ensure(c, c->dnD, bytes))) return rc;
-    c->dn_have = true; c->dn_w = c->width; c->dn_rows = c->owned_rows;
+    if ((rc = ensure(c, c->dnP[0], bytes)) || (rc = ensure(c, c->dnP[1], bytes)) || (rc = plane_packed(c, c->dnD))) return rc;
     if (c->owned_rows == 0) return GLRTX_OK;
-    return denoise_passes(c, c->stream, c->accum, nullptr, (int)(c->pitch_bytes / sizeof(float4)), (const float4 *)c->ftN.p, (const float4 *)c->ftA.p,
-                          (float4 *)c->dnP[0].p, (float4 *)c->dnP[1].p, (float4 *)c->dnD.p, nullptr, c->width, c->owned_rows, k);
+    return denoise_passes(c, c->stream, c->accum, nullptr, (int)(c->pitch_bytes / sizeof(float4)), (const float4 *)c->ftN.buf.p, (const float4 *)c->ftA.p,
+                          (float4 *)c->dnP[0].p, (float4 *)c->dnP[1].p, (float4 *)c->dnD.buf.p, nullptr, c->width, c->owned_rows, k);
 }
 
 int glrtx_read_denoised(glrtx_ctx *c, float *dst, size_t dst_pitch_bytes) {
@@ -3115,10 +3164,7 @@ int glrtx_read_denoised(glrtx_ctx *c, float *dst, size_t dst_pitch_bytes) {
     if (int rc = denoise_shape_check(c, fn, true)) return rc;
     const size_t row = (size_t)c->width * sizeof(float4);
     if (dst_pitch_bytes < row) return fail(c, GLRTX_EINVAL, "%s: dst pitch too small", fn);
-    if (int rc = glrtx_sync(c)) return rc;
-    if (c->owned_rows == 0) return GLRTX_OK;
-    HIP_TRY(c, hipMemcpy2D(dst, dst_pitch_bytes, c->dnD.p, row, row, (size_t)c->owned_rows, hipMemcpyDeviceToHost));
-    return GLRTX_OK;
+    return read_back(c, c->dnD.buf.p, row, dst, dst_pitch_bytes);
 }
 
 // D through the resolve: resolve_kernel with D as its source (a mean with the count word 1: the kernel's division is exact).
@@ -3130,19 +3176,12 @@ int glrtx_resolve_denoised_rgba8(glrtx_ctx *c, uint8_t *dst, size_t dst_pitch_by
     if (dst_pitch_bytes < (size_t)c->width * 4) return fail(c, GLRTX_EINVAL, "%s: dst pitch too small", fn);
     seal_feed(c);
     HIP_TRY(c, hipSetDevice(c->device));
-    if (c->owned_rows == 0) return glrtx_sync(c);
-    const size_t bytes = (size_t)c->width * 4 * (size_t)c->owned_rows;
-    if (c->rgba8.bytes < bytes) {
-        dev_free(c->rgba8);
-        HIP_TRY(c, hipMalloc(&c->rgba8.p, bytes));
-        c->rgba8.bytes = bytes;
-    }
-    hipLaunchKernelGGL(resolve_kernel<kResolvePer>, resolve_grid(c->width, c->owned_rows), dim3(256), 0, c->stream, (const float4 *)c->dnD.p, c->width, c->width,
-                       c->owned_rows, (uchar4 *)c->rgba8.p, c->width, 1.0f / gamma, flip_y ? 1 : 0);
-    HIP_TRY(c, hipGetLastError());
-    if (int rc = glrtx_sync(c)) return rc;
-    HIP_TRY(c, hipMemcpy2D(dst, dst_pitch_bytes, c->rgba8.p, (size_t)c->width * 4, (size_t)c->width * 4, (size_t)c->owned_rows, hipMemcpyDeviceToHost));
-    return GLRTX_OK;
+    return resolve_to_caller(c, dst, dst_pitch_bytes, [&](uchar4 *out) {
+        hipLaunchKernelGGL(resolve_kernel<kResolvePer>, resolve_grid(c->width, c->owned_rows), dim3(256), 0, c->stream, (const float4 *)c->dnD.buf.p, c->width, c->width,
+                           c->owned_rows, out, c->width, 1.0f / gamma, flip_y ? 1 : 0);
+        HIP_TRY(c, hipGetLastError());
+        return GLRTX_OK;
+    });
 }
 
 int glrtx_debug_denoise(const float *accum, const float *normal_depth, const float *albedo_id, int width, int rows, const glrtx_denoise_cfg *cfg, float *out) {
@@ -3171,70 +3210,24 @@ int glrtx_track_moments(glrtx_ctx *c, int enable) {
     if (!c->mm_on) return GLRTX_OK;
     seal_feed(c);
     if (int rc = glrtx_sync(c)) return rc;
-    dev_free(c->mmM); dev_free(c->mmM_spare);
+    c->mmM.drop(); dev_free(c->mmM_spare);
     c->mm_on = false;
     return GLRTX_OK;
 }
 
-// glrtx_render_adaptive's launches without a selection: plain launches with sample planes on the context's stream, in helpings of what the frames-in-flight
-// budget allows, each folded by accumulate_moments_kernel into the accumulator and M.
+// glrtx_render_adaptive's launches without a selection: plain launches with sample planes on the context's stream, each folded by accumulate_moments_kernel into
+// the accumulator and M.
 int glrtx_render_moments(glrtx_ctx *c, const glrtx_params *p, const float *seeds_xy, int n_frames) {
     if (!c) return GLRTX_EINVAL;
     if (int rc = moments_check(c, p, seeds_xy, n_frames)) return rc;
-    seal_feed(c);
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (!moments_have(c))
-        if (int rc = moments_ensure(c)) return rc;
-    if (n_frames == 0 || c->owned_rows == 0) { c->st.launches += (uint64_t)n_frames; return GLRTX_OK; }
-    const int rc = render_helpings(c, p, seeds_xy, n_frames, std::min(n_frames, frames_cap(c, p, 1)), RenderReq::Moments);
-    seal_feed(c);  // (the next render call starts a launch of its own)
-    return rc;
+    return render_side(c, p, seeds_xy, n_frames, RenderReq::Moments, &c->mmM, nullptr);
 }
 
 // glrtx_render_adaptive with the selection made from M and the active tiles' samples folded into M: H is neither read, allocated nor written.
 int glrtx_render_adaptive_moments(glrtx_ctx *c, const glrtx_params *p, const float *seeds_xy, int n_frames, const glrtx_adaptive *cfg) {
     if (!c) return GLRTX_EINVAL;
     if (int rc = adapt_moments_check(c, p, seeds_xy, n_frames, cfg)) return rc;
-    seal_feed(c);
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (!moments_have(c))
-        if (int rc = moments_ensure(c)) return rc;
-    if (int rc = adapt_select(c, cfg, true)) return rc;
-    if (n_frames == 0 || c->owned_rows == 0) { c->st.launches += (uint64_t)n_frames; return GLRTX_OK; }
-    const int rc = render_helpings(c, p, seeds_xy, n_frames, std::min(n_frames, frames_cap(c, p, 1)), RenderReq::AdaptiveMoments);
-    seal_feed(c);  // (the next render call starts a launch of its own)
-    return rc;
-}
-
-int glrtx_debug_adaptive_select_moments(const float *moments, int width, int rows, float threshold, int min_samples, uint8_t *mask_out, float *err_out, int *list_out,
-                                        int *count_out) {
-    const char *fn = "glrtx_debug_adaptive_select_moments";
-    if (width < 1 || rows < 1 || width > 65536 || rows > 65536) return fail(nullptr, GLRTX_EINVAL, "%s: bad size %dx%d", fn, width, rows);
-    if (!moments || !mask_out) return fail(nullptr, GLRTX_EINVAL, "%s: NULL buffer", fn);
-    const int tiles8_x = (width + 7) / 8, n_tiles = tiles8_x * ((rows + 7) / 8);
-    const size_t px_bytes = (size_t)width * rows * sizeof(float4);
-    void *d_m = nullptr, *d_mask = nullptr, *d_err = nullptr, *d_list = nullptr, *d_count = nullptr;
-    hipError_t e = hipMalloc(&d_m, px_bytes);
-    if (e == hipSuccess) e = hipMalloc(&d_mask, (size_t)n_tiles);
-    if (e == hipSuccess) e = hipMalloc(&d_err, (size_t)n_tiles * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(&d_list, (size_t)n_tiles * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc(&d_count, sizeof(unsigned));
-    if (e == hipSuccess) e = hipMemcpy(d_m, moments, px_bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(adaptive_moments::select_kernel, dim3((n_tiles + 3) / 4), dim3(256), 0, 0, (const float4 *)d_m, width, width, rows, tiles8_x, n_tiles,
-                           threshold, min_samples, (unsigned char *)d_mask, (float *)d_err);
-        hipLaunchKernelGGL(adaptive_compact_kernel, dim3(1), dim3(kAdaptCompactThreads), 0, 0, (const unsigned char *)d_mask, n_tiles, (int *)d_list, (unsigned *)d_count);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy(mask_out, d_mask, (size_t)n_tiles, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && err_out) e = hipMemcpy(err_out, d_err, (size_t)n_tiles * sizeof(float), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && list_out) e = hipMemcpy(list_out, d_list, (size_t)n_tiles * sizeof(int), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && count_out) e = hipMemcpy(count_out, d_count, sizeof(int), hipMemcpyDeviceToHost);
-    const int rc = e != hipSuccess ? fail(nullptr, GLRTX_EDEVICE, "%s: %s", fn, hipGetErrorString(e)) : GLRTX_OK;
-    for (void *q : {d_m, d_mask, d_err, d_list, d_count})
-        if (q) (void)hipFree(q);
-    return rc;
+    return render_side(c, p, seeds_xy, n_frames, RenderReq::AdaptiveMoments, &c->mmM, cfg);
 }
 
 int glrtx_read_moments(glrtx_ctx *c, float *dst, size_t dst_pitch_bytes) {
@@ -3242,15 +3235,11 @@ int glrtx_read_moments(glrtx_ctx *c, float *dst, size_t dst_pitch_bytes) {
     if (!c || !dst) return GLRTX_EINVAL;
     if (!c->mm_on) return fail(c, GLRTX_EINVAL, "%s: moments are not tracked (glrtx_track_moments)", fn);
     if (!c->accum || c->width < 1) return fail(c, GLRTX_EINVAL, "%s: no accumulator (call glrtx_resize)", fn);
-    const size_t row = (size_t)c->width * sizeof(float4);
-    if (dst_pitch_bytes < row) return fail(c, GLRTX_EINVAL, "%s: dst pitch too small", fn);
+    if (dst_pitch_bytes < (size_t)c->width * sizeof(float4)) return fail(c, GLRTX_EINVAL, "%s: dst pitch too small", fn);
     HIP_TRY(c, hipSetDevice(c->device));
-    if (!moments_have(c))
-        if (int rc = moments_ensure(c)) return rc;  // (first use: a plane of zeros)
-    if (int rc = glrtx_sync(c)) return rc;
-    if (c->owned_rows == 0) return GLRTX_OK;
-    HIP_TRY(c, hipMemcpy2D(dst, dst_pitch_bytes, c->mmM.p, c->mm_pitch, row, (size_t)c->owned_rows, hipMemcpyDeviceToHost));
-    return GLRTX_OK;
+    if (!c->mmM.current(accum_shape(c)))
+        if (int rc = plane_zero(c, c->mmM)) return rc;  // (first use: a plane of zeros)
+    return read_back(c, c->mmM.buf.p, c->pitch_bytes, dst, dst_pitch_bytes);
 }
 
 int glrtx_denoise_variance(glrtx_ctx *c, const glrtx_denoise_var_cfg *cfg) {
@@ -3260,20 +3249,20 @@ int glrtx_denoise_variance(glrtx_ctx *c, const glrtx_denoise_var_cfg *cfg) {
     if (int rc = denoise_cfg_check(c, cfg, fn, k)) return rc;
     if (!c->accum || c->width < 1) return fail(c, GLRTX_EINVAL, "%s: no accumulator (call glrtx_resize)", fn);
     if (!c->mm_on) return fail(c, GLRTX_EINVAL, "%s: moments are not tracked (glrtx_track_moments)", fn);
-    if (!moments_have(c)) return fail(c, GLRTX_EINVAL, "%s: no moments plane yet (call glrtx_render_moments first)", fn);
+    if (!c->mmM.current(accum_shape(c))) return fail(c, GLRTX_EINVAL, "%s: no moments plane yet (call glrtx_render_moments first)", fn);
     if (int rc = denoise_shape_check(c, fn, false)) return rc;
     seal_feed(c);
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t px = (size_t)c->width * (size_t)std::max(c->owned_rows, 1);
     int rc;
-    if ((rc = ensure(c, c->dnP[0], px * sizeof(float4))) || (rc = ensure(c, c->dnP[1], px * sizeof(float4))) || (rc = ensure(c, c->dnD, px * sizeof(float4)))) return rc;
+    if ((rc = ensure(c, c->dnP[0], px * sizeof(float4))) || (rc = ensure(c, c->dnP[1], px * sizeof(float4)))) return rc;
     for (DevBuf &v : c->dnV)
         if ((rc = ensure(c, v, px * sizeof(float)))) return rc;
-    c->dn_have = true; c->dn_w = c->width; c->dn_rows = c->owned_rows;
+    if ((rc = plane_packed(c, c->dnD))) return rc;
     if (c->owned_rows == 0) return GLRTX_OK;
     float *const v[3] = {(float *)c->dnV[0].p, (float *)c->dnV[1].p, (float *)c->dnV[2].p};
-    return denoise_passes(c, c->stream, c->accum, (const float4 *)c->mmM.p, (int)(c->pitch_bytes / sizeof(float4)), (const float4 *)c->ftN.p, (const float4 *)c->ftA.p,
-                          (float4 *)c->dnP[0].p, (float4 *)c->dnP[1].p, (float4 *)c->dnD.p, v, c->width, c->owned_rows, k);
+    return denoise_passes(c, c->stream, c->accum, (const float4 *)c->mmM.buf.p, (int)(c->pitch_bytes / sizeof(float4)), (const float4 *)c->ftN.buf.p, (const float4 *)c->ftA.p,
+                          (float4 *)c->dnP[0].p, (float4 *)c->dnP[1].p, (float4 *)c->dnD.buf.p, v, c->width, c->owned_rows, k);
 }
 
 int glrtx_debug_denoise_variance(const float *accum, const float *moments, const float *normal_depth, const float *albedo_id, int width, int rows,
@@ -3304,10 +3293,10 @@ int glrtx_track_cascades(glrtx_ctx *c, int enable, float start) {
     if (!c) return GLRTX_EINVAL;
     if (enable) {
         if (!cascade_start_ok(start)) return fail(c, GLRTX_EINVAL, "%s: start %g is not within 2^-20 .. 2^20", fn, (double)start);
-        if (c->rw_on && c->rwC.p && start != c->rw_start) {  // the bins were the old bounds'
+        if (c->rw_on && c->rwC.buf.p && start != c->rw_start) {  // the bins were the old bounds'
             seal_feed(c);
             HIP_TRY(c, hipSetDevice(c->device));
-            if (int rc = cascades_ensure(c)) return rc;
+            if (int rc = plane_zero(c, c->rwC, reweight::kCascades)) return rc;
         }
         c->rw_on = true; c->rw_start = start;
         return GLRTX_OK;
@@ -3315,7 +3304,7 @@ int glrtx_track_cascades(glrtx_ctx *c, int enable, float start) {
     if (!c->rw_on) return GLRTX_OK;
     seal_feed(c);
     if (int rc = glrtx_sync(c)) return rc;
-    dev_free(c->rwC);
+    c->rwC.drop();
     c->rw_on = false;
     return GLRTX_OK;
 }
@@ -3326,14 +3315,7 @@ int glrtx_render_cascades(glrtx_ctx *c, const glrtx_params *p, const float *seed
     const char *fn = "glrtx_render_cascades";
     if (!c) return GLRTX_EINVAL;
     if (int rc = side_plane_check(c, p, seeds_xy, n_frames, fn, c->rw_on, "cascades are not tracked (glrtx_track_cascades)")) return rc;
-    seal_feed(c);
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (!cascades_have(c))
-        if (int rc = cascades_ensure(c)) return rc;
-    if (n_frames == 0 || c->owned_rows == 0) { c->st.launches += (uint64_t)n_frames; return GLRTX_OK; }
-    const int rc = render_helpings(c, p, seeds_xy, n_frames, std::min(n_frames, frames_cap(c, p, 1)), RenderReq::Cascades);
-    seal_feed(c);  // (the next render call starts a launch of its own)
-    return rc;
+    return render_side(c, p, seeds_xy, n_frames, RenderReq::Cascades, &c->rwC, nullptr);
 }
 
 int glrtx_read_cascades(glrtx_ctx *c, float *dst, size_t dst_pitch_bytes) {
@@ -3341,18 +3323,11 @@ int glrtx_read_cascades(glrtx_ctx *c, float *dst, size_t dst_pitch_bytes) {
     if (!c || !dst) return GLRTX_EINVAL;
     if (!c->rw_on) return fail(c, GLRTX_EINVAL, "%s: cascades are not tracked (glrtx_track_cascades)", fn);
     if (!c->accum || c->width < 1) return fail(c, GLRTX_EINVAL, "%s: no accumulator (call glrtx_resize)", fn);
-    const size_t row = (size_t)c->width * sizeof(float4);
-    if (dst_pitch_bytes < row) return fail(c, GLRTX_EINVAL, "%s: dst pitch too small", fn);
+    if (dst_pitch_bytes < (size_t)c->width * sizeof(float4)) return fail(c, GLRTX_EINVAL, "%s: dst pitch too small", fn);
     HIP_TRY(c, hipSetDevice(c->device));
-    if (!cascades_have(c))
-        if (int rc = cascades_ensure(c)) return rc;  // (first use: planes of zeros)
-    if (int rc = glrtx_sync(c)) return rc;
-    if (c->owned_rows == 0) return GLRTX_OK;
-    const size_t plane = c->rw_pitch * (size_t)c->owned_rows;
-    for (int k = 0; k < reweight::kCascades; k++)
-        HIP_TRY(c, hipMemcpy2D((char *)dst + (size_t)k * (size_t)c->owned_rows * dst_pitch_bytes, dst_pitch_bytes, (const char *)c->rwC.p + (size_t)k * plane,
-                               c->rw_pitch, row, (size_t)c->owned_rows, hipMemcpyDeviceToHost));
-    return GLRTX_OK;
+    if (!c->rwC.current(accum_shape(c)))
+        if (int rc = plane_zero(c, c->rwC, reweight::kCascades)) return rc;  // (first use: planes of zeros)
+    return read_back(c, c->rwC.buf.p, c->pitch_bytes, dst, dst_pitch_bytes, reweight::kCascades);
 }
 
 // Everything glrtx_reweight refuses, checked before anything changes.
@@ -3360,7 +3335,7 @@ static int reweight_check(glrtx_ctx *c, const glrtx_reweight_cfg *cfg, const cha
     if (int rc = reweight_cfg_check(c, cfg, fn)) return rc;
     if (!c->rw_on) return fail(c, GLRTX_EINVAL, "%s: cascades are not tracked (glrtx_track_cascades)", fn);
     if (!c->accum || c->width < 1) return fail(c, GLRTX_EINVAL, "%s: no accumulator (call glrtx_resize)", fn);
-    if (!cascades_have(c)) return fail(c, GLRTX_EINVAL, "%s: no cascade planes yet (call glrtx_render_cascades first)", fn);
+    if (!c->rwC.current(accum_shape(c))) return fail(c, GLRTX_EINVAL, "%s: no cascade planes yet (call glrtx_render_cascades first)", fn);
     if (c->world > 1) return fail(c, GLRTX_EINVAL, "%s: the context is partitioned (rank %d of %d): the neighbourhood would stop at every stripe's seam", fn, c->rank, c->world);
     return GLRTX_OK;
 }
@@ -3371,11 +3346,10 @@ int glrtx_reweight(glrtx_ctx *c, const glrtx_reweight_cfg *cfg) {
     if (int rc = reweight_check(c, cfg, fn)) return rc;
     seal_feed(c);
     HIP_TRY(c, hipSetDevice(c->device));
-    if (int rc = ensure(c, c->dnD, (size_t)c->width * (size_t)std::max(c->owned_rows, 1) * sizeof(float4))) return rc;
-    c->dn_have = true; c->dn_w = c->width; c->dn_rows = c->owned_rows;
+    if (int rc = plane_packed(c, c->dnD)) return rc;
     if (c->owned_rows == 0) return GLRTX_OK;
     const int pitch_f4 = (int)(c->pitch_bytes / sizeof(float4));
-    return reweight_pass(c, c->stream, (const float4 *)c->rwC.p, (size_t)pitch_f4 * (size_t)c->owned_rows, pitch_f4, c->width, c->owned_rows, (float4 *)c->dnD.p, *cfg);
+    return reweight_pass(c, c->stream, (const float4 *)c->rwC.buf.p, (size_t)pitch_f4 * (size_t)c->owned_rows, pitch_f4, c->width, c->owned_rows, (float4 *)c->dnD.buf.p, *cfg);
 }
 
 int glrtx_debug_fold_cascades(const float *accum, const float *cascades, const float *frames, int n_frames, int width, int rows, float start, float *accum_out,
@@ -3426,22 +3400,12 @@ int glrtx_debug_reweight_burst(glrtx_ctx *c, const glrtx_reweight_cfg *cfg, int 
     if (c->owned_rows == 0) return fail(c, GLRTX_EINVAL, "%s: no rows", fn);
     seal_feed(c);
     HIP_TRY(c, hipSetDevice(c->device));
-    if (int rc = ensure(c, c->dnD, (size_t)c->width * (size_t)c->owned_rows * sizeof(float4))) return rc;
-    c->dn_have = true; c->dn_w = c->width; c->dn_rows = c->owned_rows;
+    if (int rc = plane_packed(c, c->dnD)) return rc;
     const int pitch_f4 = (int)(c->pitch_bytes / sizeof(float4));
-    for (int pass = 0; pass < 2; pass++) {  // (the first pass warms the device up)
-        HIP_TRY(c, hipEventRecord(c->rs0, c->stream));
-        for (int i = 0; i < reps; i++)
-            if (int rc = reweight_pass(c, c->stream, (const float4 *)c->rwC.p, (size_t)pitch_f4 * (size_t)c->owned_rows, pitch_f4, c->width, c->owned_rows,
-                                       (float4 *)c->dnD.p, *cfg))
-                return rc;
-        HIP_TRY(c, hipEventRecord(c->rs1, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-    }
-    float ms = 0.f;
-    HIP_TRY(c, hipEventElapsedTime(&ms, c->rs0, c->rs1));
-    *ms_per_launch = ms / (float)reps;
-    return GLRTX_OK;
+    return burst_time(c, reps, ms_per_launch, [&] {
+        return reweight_pass(c, c->stream, (const float4 *)c->rwC.buf.p, (size_t)pitch_f4 * (size_t)c->owned_rows, pitch_f4, c->width, c->owned_rows,
+                             (float4 *)c->dnD.buf.p, *cfg);
+    });
 }
 
 // ---- tone mapping
@@ -3484,22 +3448,18 @@ int glrtx_tonemap(glrtx_ctx *c, const glrtx_tonemap_cfg *cfg) {
     seal_feed(c);
     HIP_TRY(c, hipSetDevice(c->device));
     if (int rc = exposure_ensure(c)) return rc;
-    if (int rc = ensure(c, c->tmT, (size_t)c->width * (size_t)std::max(c->owned_rows, 1) * sizeof(float4))) return rc;
-    c->tm_w = c->width; c->tm_rows = c->owned_rows;
+    if (int rc = plane_packed(c, c->tmT)) return rc;
     if (c->owned_rows == 0) return GLRTX_OK;
-    return tonemap_plane_pass(c, c->stream, src, pitch_f4, c->width, c->owned_rows, (float4 *)c->tmT.p, (const tonemap::Exposure *)c->tmExp.p, *cfg);
+    return tonemap_plane_pass(c, c->stream, src, pitch_f4, c->width, c->owned_rows, (float4 *)c->tmT.buf.p, (const tonemap::Exposure *)c->tmExp.p, *cfg);
 }
 
 int glrtx_read_tonemapped(glrtx_ctx *c, float *dst, size_t dst_pitch_bytes) {
     const char *fn = "glrtx_read_tonemapped";
     if (!c || !dst) return GLRTX_EINVAL;
-    if (!c->tmT.p || c->tm_w != c->width || c->tm_rows != c->owned_rows) return fail(c, GLRTX_EINVAL, "%s: no tone-mapped plane (call glrtx_tonemap first)", fn);
+    if (!c->tmT.current(packed_shape(c))) return fail(c, GLRTX_EINVAL, "%s: no tone-mapped plane (call glrtx_tonemap first)", fn);
     const size_t row = (size_t)c->width * sizeof(float4);
     if (dst_pitch_bytes < row) return fail(c, GLRTX_EINVAL, "%s: dst pitch too small", fn);
-    if (int rc = glrtx_sync(c)) return rc;
-    if (c->owned_rows == 0) return GLRTX_OK;
-    HIP_TRY(c, hipMemcpy2D(dst, dst_pitch_bytes, c->tmT.p, row, row, (size_t)c->owned_rows, hipMemcpyDeviceToHost));
-    return GLRTX_OK;
+    return read_back(c, c->tmT.buf.p, row, dst, dst_pitch_bytes);
 }
 
 // Source -> bytes in one pass: the curve in front of the resolve's own arithmetic (tonemap_resolve); T is not touched.
@@ -3513,12 +3473,9 @@ int glrtx_resolve_tonemapped_rgba8(glrtx_ctx *c, uint8_t *dst, size_t dst_pitch_
     seal_feed(c);
     HIP_TRY(c, hipSetDevice(c->device));
     if (int rc = exposure_ensure(c)) return rc;
-    if (c->owned_rows == 0) return glrtx_sync(c);
-    if (int rc = ensure(c, c->rgba8, (size_t)c->width * 4 * (size_t)c->owned_rows)) return rc;
-    if (int rc = tonemap_resolve_pass(c, c->stream, src, pitch_f4, c->width, c->owned_rows, (uchar4 *)c->rgba8.p, (const tonemap::Exposure *)c->tmExp.p, *cfg)) return rc;
-    if (int rc = glrtx_sync(c)) return rc;
-    HIP_TRY(c, hipMemcpy2D(dst, dst_pitch_bytes, c->rgba8.p, (size_t)c->width * 4, (size_t)c->width * 4, (size_t)c->owned_rows, hipMemcpyDeviceToHost));
-    return GLRTX_OK;
+    return resolve_to_caller(c, dst, dst_pitch_bytes, [&](uchar4 *out) {
+        return tonemap_resolve_pass(c, c->stream, src, pitch_f4, c->width, c->owned_rows, out, (const tonemap::Exposure *)c->tmExp.p, *cfg);
+    });
 }
 
 int glrtx_debug_tonemap(const float *src, int width, int rows, const glrtx_tonemap_cfg *cfg, const float *exposure_in, glrtx_exposure *exp_out, float *t_out,
@@ -3565,30 +3522,16 @@ int glrtx_debug_tonemap_burst(glrtx_ctx *c, const glrtx_tonemap_cfg *cfg, int wh
     HIP_TRY(c, hipSetDevice(c->device));
     int rc;
     if ((rc = exposure_ensure(c)) || (rc = ensure(c, c->rgba8, (size_t)c->width * 4 * (size_t)c->owned_rows))) return rc;
-    if (which == 2) {
-        if ((rc = ensure(c, c->tmT, (size_t)c->width * (size_t)c->owned_rows * sizeof(float4)))) return rc;
-        c->tm_w = c->width; c->tm_rows = c->owned_rows;
-    }
+    if (which == 2 && (rc = plane_packed(c, c->tmT))) return rc;
     tonemap::Exposure *st = (tonemap::Exposure *)c->tmExp.p;
-    for (int pass = 0; pass < 2; pass++) {  // (the first pass warms the device up)
-        HIP_TRY(c, hipEventRecord(c->rs0, c->stream));
-        for (int i = 0; i < reps && rc == GLRTX_OK; i++) {
-            if (which == 0)
-                hipLaunchKernelGGL(resolve_kernel<kResolvePer>, resolve_grid(c->width, c->owned_rows), dim3(256), 0, c->stream, src, pitch_f4, c->width, c->owned_rows,
-                                   (uchar4 *)c->rgba8.p, c->width, 1.0f / cfg->gamma, cfg->flip_y ? 1 : 0);
-            else if (which == 1) rc = tonemap_resolve_pass(c, c->stream, src, pitch_f4, c->width, c->owned_rows, (uchar4 *)c->rgba8.p, st, *cfg);
-            else if (which == 2) rc = tonemap_plane_pass(c, c->stream, src, pitch_f4, c->width, c->owned_rows, (float4 *)c->tmT.p, st, *cfg);
-            else rc = exposure_passes(c, c->stream, src, pitch_f4, c->width, c->owned_rows, st, *cfg);
-        }
-        if (rc) return rc;
-        HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, hipEventRecord(c->rs1, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-    }
-    float ms = 0.f;
-    HIP_TRY(c, hipEventElapsedTime(&ms, c->rs0, c->rs1));
-    *ms_per_launch = ms / (float)reps;
-    return GLRTX_OK;
+    return burst_time(c, reps, ms_per_launch, [&] {
+        if (which == 1) return tonemap_resolve_pass(c, c->stream, src, pitch_f4, c->width, c->owned_rows, (uchar4 *)c->rgba8.p, st, *cfg);
+        if (which == 2) return tonemap_plane_pass(c, c->stream, src, pitch_f4, c->width, c->owned_rows, (float4 *)c->tmT.buf.p, st, *cfg);
+        if (which == 3) return exposure_passes(c, c->stream, src, pitch_f4, c->width, c->owned_rows, st, *cfg);
+        hipLaunchKernelGGL(resolve_kernel<kResolvePer>, resolve_grid(c->width, c->owned_rows), dim3(256), 0, c->stream, src, pitch_f4, c->width, c->owned_rows,
+                           (uchar4 *)c->rgba8.p, c->width, 1.0f / cfg->gamma, cfg->flip_y ? 1 : 0);
+        return GLRTX_OK;
+    });
 }
 
 
@@ -3602,59 +3545,46 @@ int glrtx_bloom(glrtx_ctx *c, const glrtx_bloom_cfg *cfg) {
     seal_feed(c);
     HIP_TRY(c, hipSetDevice(c->device));
     if (int rc = bloom_ensure(c)) return rc;
-    c->bl_w = c->width; c->bl_rows = c->owned_rows;
     const BloomLevels L = bloom_levels(c->width, c->owned_rows, cfg->levels);
     if (int rc = bloom_down_passes(c, c->stream, src, pitch_f4, L, (float4 *)c->blPyr.p, *cfg)) return rc;
-    return bloom_up_passes(c, c->stream, src, pitch_f4, L, (float4 *)c->blPyr.p, (float4 *)c->blB.p, *cfg);
+    return bloom_up_passes(c, c->stream, src, pitch_f4, L, (float4 *)c->blPyr.p, (float4 *)c->blB.buf.p, *cfg);
 }
 
 int glrtx_read_bloomed(glrtx_ctx *c, float *dst, size_t dst_pitch_bytes) {
     const char *fn = "glrtx_read_bloomed";
     if (!c || !dst) return GLRTX_EINVAL;
-    if (!bloom_have(c)) return fail(c, GLRTX_EINVAL, "%s: no bloomed plane (call glrtx_bloom first)", fn);
+    if (!c->blB.current(packed_shape(c))) return fail(c, GLRTX_EINVAL, "%s: no bloomed plane (call glrtx_bloom first)", fn);
     const size_t row = (size_t)c->width * sizeof(float4);
     if (dst_pitch_bytes < row) return fail(c, GLRTX_EINVAL, "%s: dst pitch too small", fn);
-    if (int rc = glrtx_sync(c)) return rc;
-    HIP_TRY(c, hipMemcpy2D(dst, dst_pitch_bytes, c->blB.p, row, row, (size_t)c->owned_rows, hipMemcpyDeviceToHost));
-    return GLRTX_OK;
+    return read_back(c, c->blB.buf.p, row, dst, dst_pitch_bytes);
 }
 
 // glrtx_tonemap with B as its source: tonemap_plane, B -> T.
 int glrtx_tonemap_bloomed(glrtx_ctx *c, const glrtx_tonemap_cfg *cfg) {
     const char *fn = "glrtx_tonemap_bloomed";
     if (!c) return GLRTX_EINVAL;
-    if (!cfg) return fail(c, GLRTX_EINVAL, "%s: NULL cfg", fn);
-    glrtx_tonemap_cfg k = *cfg;
-    k.source = 0;  // (not read: the source is B)
-    if (int rc = tonemap_cfg_check(c, &k, fn)) return rc;
-    if (!bloom_have(c)) return fail(c, GLRTX_EINVAL, "%s: no bloomed plane (call glrtx_bloom first)", fn);
+    glrtx_tonemap_cfg k;
+    if (int rc = tonemap_bloomed_cfg(c, cfg, fn, k)) return rc;
     seal_feed(c);
     HIP_TRY(c, hipSetDevice(c->device));
     if (int rc = exposure_ensure(c)) return rc;
-    if (int rc = ensure(c, c->tmT, (size_t)c->width * (size_t)c->owned_rows * sizeof(float4))) return rc;
-    c->tm_w = c->width; c->tm_rows = c->owned_rows;
-    return tonemap_plane_pass(c, c->stream, (const float4 *)c->blB.p, c->width, c->width, c->owned_rows, (float4 *)c->tmT.p, (const tonemap::Exposure *)c->tmExp.p, k);
+    if (int rc = plane_packed(c, c->tmT)) return rc;
+    return tonemap_plane_pass(c, c->stream, (const float4 *)c->blB.buf.p, c->width, c->width, c->owned_rows, (float4 *)c->tmT.buf.p, (const tonemap::Exposure *)c->tmExp.p, k);
 }
 
 // glrtx_resolve_tonemapped_rgba8 with B as its source: tonemap_resolve, B -> bytes.
 int glrtx_resolve_bloomed_rgba8(glrtx_ctx *c, uint8_t *dst, size_t dst_pitch_bytes, const glrtx_tonemap_cfg *cfg) {
     const char *fn = "glrtx_resolve_bloomed_rgba8";
     if (!c || !dst) return GLRTX_EINVAL;
-    if (!cfg) return fail(c, GLRTX_EINVAL, "%s: NULL cfg", fn);
-    glrtx_tonemap_cfg k = *cfg;
-    k.source = 0;  // (not read: the source is B)
-    if (int rc = tonemap_cfg_check(c, &k, fn)) return rc;
-    if (!bloom_have(c)) return fail(c, GLRTX_EINVAL, "%s: no bloomed plane (call glrtx_bloom first)", fn);
+    glrtx_tonemap_cfg k;
+    if (int rc = tonemap_bloomed_cfg(c, cfg, fn, k)) return rc;
     if (dst_pitch_bytes < (size_t)c->width * 4) return fail(c, GLRTX_EINVAL, "%s: dst pitch too small", fn);
     seal_feed(c);
     HIP_TRY(c, hipSetDevice(c->device));
     if (int rc = exposure_ensure(c)) return rc;
-    if (int rc = ensure(c, c->rgba8, (size_t)c->width * 4 * (size_t)c->owned_rows)) return rc;
-    if (int rc = tonemap_resolve_pass(c, c->stream, (const float4 *)c->blB.p, c->width, c->width, c->owned_rows, (uchar4 *)c->rgba8.p,
-                                      (const tonemap::Exposure *)c->tmExp.p, k)) return rc;
-    if (int rc = glrtx_sync(c)) return rc;
-    HIP_TRY(c, hipMemcpy2D(dst, dst_pitch_bytes, c->rgba8.p, (size_t)c->width * 4, (size_t)c->width * 4, (size_t)c->owned_rows, hipMemcpyDeviceToHost));
-    return GLRTX_OK;
+    return resolve_to_caller(c, dst, dst_pitch_bytes, [&](uchar4 *out) {
+        return tonemap_resolve_pass(c, c->stream, (const float4 *)c->blB.buf.p, c->width, c->width, c->owned_rows, out, (const tonemap::Exposure *)c->tmExp.p, k);
+    });
 }
 
 int glrtx_debug_bloom(const float *src, int width, int rows, const glrtx_bloom_cfg *cfg, float *d_out, float *b_out) {
@@ -3694,21 +3624,11 @@ int glrtx_debug_bloom_burst(glrtx_ctx *c, const glrtx_bloom_cfg *cfg, int reps, 
     seal_feed(c);
     HIP_TRY(c, hipSetDevice(c->device));
     if (int rc = bloom_ensure(c)) return rc;
-    c->bl_w = c->width; c->bl_rows = c->owned_rows;
     const BloomLevels L = bloom_levels(c->width, c->owned_rows, cfg->levels);
-    for (int pass = 0; pass < 2; pass++) {  // (the first pass warms the device up)
-        HIP_TRY(c, hipEventRecord(c->rs0, c->stream));
-        for (int i = 0; i < reps; i++) {
-            if (int rc = bloom_down_passes(c, c->stream, src, pitch_f4, L, (float4 *)c->blPyr.p, *cfg)) return rc;
-            if (int rc = bloom_up_passes(c, c->stream, src, pitch_f4, L, (float4 *)c->blPyr.p, (float4 *)c->blB.p, *cfg)) return rc;
-        }
-        HIP_TRY(c, hipEventRecord(c->rs1, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-    }
-    float ms = 0.f;
-    HIP_TRY(c, hipEventElapsedTime(&ms, c->rs0, c->rs1));
-    *ms_per_call = ms / (float)reps;
-    return GLRTX_OK;
+    return burst_time(c, reps, ms_per_call, [&] {
+        if (int rc = bloom_down_passes(c, c->stream, src, pitch_f4, L, (float4 *)c->blPyr.p, *cfg)) return rc;
+        return bloom_up_passes(c, c->stream, src, pitch_f4, L, (float4 *)c->blPyr.p, (float4 *)c->blB.buf.p, *cfg);
+    });
 }
 
 // ---- reprojection (glrtx_reproject)
@@ -3759,7 +3679,7 @@ static int reproject_call(glrtx_ctx *c, const glrtx_params *cur, const glrtx_rep
     const size_t acc_bytes = c->pitch_bytes * (size_t)std::max(c->owned_rows, 1);
     int rc;
     if ((rc = ensure(c, c->accum_spare, acc_bytes)) || (rc = ensure(c, c->rpCount, reproject::kCountBytes))) return rc;
-    const bool carry_m = moments_have(c);  // glrtx_track_moments is on and M exists: a second M is written by the same pass and swapped in as the accumulator is
+    const bool carry_m = c->mmM.current(accum_shape(c));  // glrtx_track_moments is on and M exists: a second M is written by the same pass and swapped in as the accumulator is
     if (carry_m && (rc = ensure(c, c->mmM_spare, acc_bytes))) return rc;
     if (motion && c->mt_geom == glrtx_ctx::kMtCurrent && (rc = motion_snapshot(c))) return rc;  // nothing moved since the planes: previous = current
     for (auto &sl : c->pipe)  // behind every launch that may still add to the accumulator or read the scene (refit_run's rule)
@@ -3767,13 +3687,13 @@ static int reproject_call(glrtx_ctx *c, const glrtx_params *cur, const glrtx_rep
             HIP_TRY(c, hipEventRecord(c->rf.slot_ev, sl.stream));
             HIP_TRY(c, hipStreamWaitEvent(c->stream, c->rf.slot_ev, 0));
         }
-    std::swap(c->ftN, c->ftN_spare);  // the planes as they stand become N0 / A0; glrtx_render_features fills (on first use: allocates) the other pair
+    std::swap(c->ftN.buf, c->ftN_spare);  // the planes as they stand become N0 / A0; glrtx_render_features fills (on first use: allocates) the other pair
     std::swap(c->ftA, c->ftA_spare);
     if (c->mt_on) std::swap(c->ftG, c->ftG_spare);  // (glrtx_track_motion: the third pair goes with them)
     float cam_prev[32];
     std::memcpy(cam_prev, c->ft_cam, sizeof cam_prev);
     if ((rc = glrtx_render_features(c, cur))) {  // (only an allocation or a launch can fail here: the planes and their camera are put back)
-        std::swap(c->ftN, c->ftN_spare);
+        std::swap(c->ftN.buf, c->ftN_spare);
         std::swap(c->ftA, c->ftA_spare);
         if (c->mt_on) std::swap(c->ftG, c->ftG_spare);
         std::memcpy(c->ft_cam, cam_prev, sizeof cam_prev);
@@ -3781,18 +3701,18 @@ static int reproject_call(glrtx_ctx *c, const glrtx_params *cur, const glrtx_rep
     }
     const int pitch_f4 = (int)(c->pitch_bytes / sizeof(float4));
     const reproject::Common common =
-        reproject_common(st, c->accum, (const float4 *)c->ftN_spare.p, (const float4 *)c->ftA_spare.p, (const float4 *)(motion ? c->ftG.p : c->ftN.p),
+        reproject_common(st, c->accum, (const float4 *)c->ftN_spare.p, (const float4 *)c->ftA_spare.p, (const float4 *)(motion ? c->ftG.p : c->ftN.buf.p),
                          (const float4 *)c->ftA.p, (float4 *)c->accum_spare.p, pitch_f4,
-                         c->width, c->owned_rows, c->rpCount.p, carry_m ? (const float4 *)c->mmM.p : nullptr, carry_m ? (float4 *)c->mmM_spare.p : nullptr);
+                         c->width, c->owned_rows, c->rpCount.p, carry_m ? (const float4 *)c->mmM.buf.p : nullptr, carry_m ? (float4 *)c->mmM_spare.p : nullptr);
     if (motion) rc = reproject_motion_pass(c, c->stream, common, (const float4 *)c->mtPos.p, (const float4 *)c->mtNrm.p, c->n_tri);
     else rc = reproject_pass(c, c->stream, common, cur->c2w, cur->s2c, c->stripe);
     if (rc) return rc;
     std::swap(c->accum_own, c->accum_spare);  // the accumulator rendered into from here on (glrtx_accum_device_ptr changes)
     c->accum = (float4 *)c->accum_own.p;
     c->rp_have = true;
-    if (c->adHalf.p && (rc = adapt_half_ensure(c))) return rc;  // H held every second sample of the OLD view's pixels: zeroed, every tile is active again
-    if (c->rwC.p && (rc = cascades_ensure(c))) return rc;  // C held the OLD pixel grid's bins: zeroed like H (carrying it is out of scope)
-    if (carry_m) std::swap(c->mmM, c->mmM_spare);  // M is CARRIED, not zeroed like H: a variance is a property of the surface point, and it came along with its mean
+    if (c->adHalf.buf.p && (rc = plane_zero(c, c->adHalf))) return rc;  // H held every second sample of the OLD view's pixels: zeroed, every tile is active again
+    if (c->rwC.buf.p && (rc = plane_zero(c, c->rwC, reweight::kCascades))) return rc;  // C held the OLD pixel grid's bins: zeroed like H (carrying it is out of scope)
+    if (carry_m) std::swap(c->mmM.buf, c->mmM_spare);  // M is CARRIED, not zeroed like H: a variance is a property of the surface point, and it came along with its mean
     return GLRTX_OK;
 }
 
@@ -3823,10 +3743,7 @@ int glrtx_read_features_geom(glrtx_ctx *c, float *geom, size_t pitch_bytes) {
     if (!c->ftG.p || !c->mt_g_have) return fail(c, GLRTX_EINVAL, "%s: no geometry plane (call glrtx_render_features with tracking on first)", fn);
     const size_t row = (size_t)c->width * sizeof(float4);
     if (pitch_bytes < row) return fail(c, GLRTX_EINVAL, "%s: pitch too small", fn);
-    if (int rc = glrtx_sync(c)) return rc;
-    if (c->owned_rows == 0) return GLRTX_OK;
-    HIP_TRY(c, hipMemcpy2D(geom, pitch_bytes, c->ftG.p, row, row, (size_t)c->owned_rows, hipMemcpyDeviceToHost));
-    return GLRTX_OK;
+    return read_back(c, c->ftG.p, row, geom, pitch_bytes);
 }
 
 int glrtx_reproject_last(glrtx_ctx *c, int *carried, int *hit_pixels) {
@@ -4065,12 +3982,8 @@ int glrtx_read_accum(glrtx_ctx *c, float *dst, size_t dst_pitch_bytes) {
     if (!c || !dst) return GLRTX_EINVAL;
     seal_feed(c);  // (nothing is appended to an open launch across this call: glrtx_ctx::OpenFeed)
     if (!c->accum) return fail(c, GLRTX_EINVAL, "glrtx_read_accum: no accumulator");
-    const size_t row = (size_t)c->width * sizeof(float4);
-    if (dst_pitch_bytes < row) return fail(c, GLRTX_EINVAL, "glrtx_read_accum: dst pitch too small");
-    if (int rc = glrtx_sync(c)) return rc;
-    if (c->owned_rows == 0) return GLRTX_OK;
-    HIP_TRY(c, hipMemcpy2D(dst, dst_pitch_bytes, c->accum, c->pitch_bytes, row, (size_t)c->owned_rows, hipMemcpyDeviceToHost));
-    return GLRTX_OK;
+    if (dst_pitch_bytes < (size_t)c->width * sizeof(float4)) return fail(c, GLRTX_EINVAL, "glrtx_read_accum: dst pitch too small");
+    return read_back(c, c->accum, c->pitch_bytes, dst, dst_pitch_bytes);
 }
 
 int glrtx_accum_device_ptr(const glrtx_ctx *c, void **ptr_out, size_t *pitch_out) {
@@ -4098,24 +4011,17 @@ int glrtx_resolve_rgba8(glrtx_ctx *c, uint8_t *dst, size_t dst_pitch_bytes, floa
     if (!(gamma > 0.f)) return fail(c, GLRTX_EINVAL, "glrtx_resolve_rgba8: gamma must be positive");
     if (dst_pitch_bytes < (size_t)c->width * 4) return fail(c, GLRTX_EINVAL, "glrtx_resolve_rgba8: dst pitch too small");
     HIP_TRY(c, hipSetDevice(c->device));
-    if (c->owned_rows == 0) return glrtx_sync(c);
-    const size_t bytes = (size_t)c->width * 4 * (size_t)c->owned_rows;
-    if (c->rgba8.bytes < bytes) {
-        dev_free(c->rgba8);
-        HIP_TRY(c, hipMalloc(&c->rgba8.p, bytes));
-        c->rgba8.bytes = bytes;
-    }
-    const ResolvePick rk = resolve_pick(c);
-    HIP_TRY(c, hipEventRecord(c->rs0, c->stream));
-    hipLaunchKernelGGL(rk.fn, rk.grid, dim3(256), 0, c->stream, (const float4 *)c->accum, (int)(c->pitch_bytes / sizeof(float4)),
-                       c->width, c->owned_rows, (uchar4 *)c->rgba8.p, c->width, 1.0f / gamma, flip_y ? 1 : 0);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipEventRecord(c->rs1, c->stream));
-    if (int rc = glrtx_sync(c)) return rc;
-    HIP_TRY(c, hipEventElapsedTime(&c->st.resolve_ms_last, c->rs0, c->rs1));
-    HIP_TRY(c, hipMemcpy2D(dst, dst_pitch_bytes, c->rgba8.p, (size_t)c->width * 4, (size_t)c->width * 4, (size_t)c->owned_rows,
-                           hipMemcpyDeviceToHost));
-    return GLRTX_OK;
+    const int rc = resolve_to_caller(c, dst, dst_pitch_bytes, [&](uchar4 *out) {
+        const ResolvePick rk = resolve_pick(c);
+        HIP_TRY(c, hipEventRecord(c->rs0, c->stream));
+        hipLaunchKernelGGL(rk.fn, rk.grid, dim3(256), 0, c->stream, (const float4 *)c->accum, (int)(c->pitch_bytes / sizeof(float4)),
+                           c->width, c->owned_rows, out, c->width, 1.0f / gamma, flip_y ? 1 : 0);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipEventRecord(c->rs1, c->stream));
+        return GLRTX_OK;
+    });
+    if (rc == GLRTX_OK && c->owned_rows > 0) HIP_TRY(c, hipEventElapsedTime(&c->st.resolve_ms_last, c->rs0, c->rs1));  // (the copy's sync has seen rs1)
+    return rc;
 }
 
 // Device time of the resolve kernel by itself: `reps` launches back to back between one pair of events, per launch.  A single launch between two events (what
@@ -4127,19 +4033,11 @@ int glrtx_debug_resolve_burst(glrtx_ctx *c, float gamma, int reps, float *ms_per
     HIP_TRY(c, hipSetDevice(c->device));
     if (int rc = ensure(c, c->rgba8, (size_t)c->width * 4 * (size_t)c->owned_rows)) return rc;
     const ResolvePick rk = resolve_pick(c);
-    for (int pass = 0; pass < 2; pass++) {  // (the first pass warms the device up)
-        HIP_TRY(c, hipEventRecord(c->rs0, c->stream));
-        for (int i = 0; i < reps; i++)
-            hipLaunchKernelGGL(rk.fn, rk.grid, dim3(256), 0, c->stream, (const float4 *)c->accum, (int)(c->pitch_bytes / sizeof(float4)), c->width, c->owned_rows,
-                               (uchar4 *)c->rgba8.p, c->width, 1.0f / gamma, 1);
-        HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, hipEventRecord(c->rs1, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-    }
-    float ms = 0.f;
-    HIP_TRY(c, hipEventElapsedTime(&ms, c->rs0, c->rs1));
-    *ms_per_launch = ms / (float)reps;
-    return GLRTX_OK;
+    return burst_time(c, reps, ms_per_launch, [&] {
+        hipLaunchKernelGGL(rk.fn, rk.grid, dim3(256), 0, c->stream, (const float4 *)c->accum, (int)(c->pitch_bytes / sizeof(float4)), c->width, c->owned_rows,
+                           (uchar4 *)c->rgba8.p, c->width, 1.0f / gamma, 1);
+        return GLRTX_OK;
+    });
 }
 
 // Profile of a calibration frame: how often every triangle of the uploaded scene is the CLOSEST hit of a path ray (camera rays and bounces), counted by the render

@@ -719,6 +719,19 @@ def _adaptive_args(params, seeds, threshold, min_samples):
     return p, sd, Adaptive(float(threshold), int(min_samples))
 
 
+def _read_image(L, ctx, fn, *args, dtype=np.float32, planes=(), split=False):
+    """What a read-back or a resolve of the context `ctx` returns: zeros of planes + (owned_rows, width, 4) of `dtype`, filled by fn(ctx, address, packed row
+    pitch, *args) -- with `split`, by fn(ctx, one address per plane, pitch, *args)."""
+    s = Stats()
+    rc = L.glrtx_get_stats(ctx, C.byref(s))
+    out = np.zeros(tuple(planes) + (s.owned_rows, s.width, 4), dtype)
+    dst = [a.ctypes.data for a in out] if split else [out.ctypes.data]
+    rc = rc or fn(ctx, *dst, s.width * 4 * out.itemsize, *args)
+    if rc != 0:
+        raise GlrtxError(rc, L.glrtx_last_error(ctx).decode())
+    return out
+
+
 class Device:
     """One glrtx_ctx: one GPU, one row-stripe partition of the image."""
 
@@ -915,16 +928,10 @@ class Device:
         return np.array([self.L.glrtx_local_row_to_y(self.h, r) for r in range(n)], np.int64)
 
     def read_accum(self) -> np.ndarray:
-        s = self.stats()
-        out = np.zeros((s.owned_rows, s.width, 4), np.float32)
-        self._ck(self.L.glrtx_read_accum(self.h, out.ctypes.data, s.width * 16))
-        return out
+        return _read_image(self.L, self.h, self.L.glrtx_read_accum)
 
     def resolve_rgba8(self, gamma=2.2, flip_y=True) -> np.ndarray:
-        s = self.stats()
-        out = np.zeros((s.owned_rows, s.width, 4), np.uint8)
-        self._ck(self.L.glrtx_resolve_rgba8(self.h, out.ctypes.data, s.width * 4, gamma, int(flip_y)))
-        return out
+        return _read_image(self.L, self.h, self.L.glrtx_resolve_rgba8, gamma, int(flip_y), dtype=np.uint8)
 
     def hit_histogram(self, params, n_tri) -> np.ndarray:
         """Closest hits per triangle of the uploaded scene in ONE calibration frame of `params` (glrtx_hit_histogram): input of host.order_by_hits."""
@@ -985,19 +992,14 @@ class Device:
         return out
     def read_adaptive_half(self) -> np.ndarray:
         """The half buffer H (every second sample), (owned_rows, width, 4) float32 like read_accum."""
-        s = self.stats()
-        out = np.zeros((s.owned_rows, s.width, 4), np.float32)
-        self._ck(self.L.glrtx_read_adaptive_half(self.h, out.ctypes.data, s.width * 16))
-        return out
+        return _read_image(self.L, self.h, self.L.glrtx_read_adaptive_half)
     def render_features(self, params):
         """The denoiser's feature planes for this camera (glrtx_render_features): issued on the context's stream, nothing is read back."""
         p = make_params(params)
         self._ck(self.L.glrtx_render_features(self.h, C.byref(p)))
     def read_features(self):
         """(normal_depth, albedo_id): (owned_rows, width, 4) float32 each (syncs); albedo_id[..., 3] holds the material id as int32 bits, -1 on a miss."""
-        s = self.stats()
-        n, a = np.zeros((s.owned_rows, s.width, 4), np.float32), np.zeros((s.owned_rows, s.width, 4), np.float32)
-        self._ck(self.L.glrtx_read_features(self.h, n.ctypes.data, a.ctypes.data, s.width * 16))
+        n, a = _read_image(self.L, self.h, self.L.glrtx_read_features, planes=(2,), split=True)
         return n, a
     def denoise(self, iterations=None, sigma_color=None, sigma_normal=None, sigma_depth=None, demodulate=None):
         """The a-trous filter over the accumulator's mean, guided by the feature planes as they stand (glrtx_denoise); None: the default."""
@@ -1005,15 +1007,9 @@ class Device:
         self._ck(self.L.glrtx_denoise(self.h, C.byref(c)))
     def read_denoised(self) -> np.ndarray:
         """The denoised image D, (owned_rows, width, 4) float32 {rgb, 1} (syncs)."""
-        s = self.stats()
-        out = np.zeros((s.owned_rows, s.width, 4), np.float32)
-        self._ck(self.L.glrtx_read_denoised(self.h, out.ctypes.data, s.width * 16))
-        return out
+        return _read_image(self.L, self.h, self.L.glrtx_read_denoised)
     def resolve_denoised_rgba8(self, gamma=2.2, flip_y=True) -> np.ndarray:
-        s = self.stats()
-        out = np.zeros((s.owned_rows, s.width, 4), np.uint8)
-        self._ck(self.L.glrtx_resolve_denoised_rgba8(self.h, out.ctypes.data, s.width * 4, gamma, int(flip_y)))
-        return out
+        return _read_image(self.L, self.h, self.L.glrtx_resolve_denoised_rgba8, gamma, int(flip_y), dtype=np.uint8)
     def track_moments(self, enable=True):
         """Keep the luminance moments plane M beside the accumulator (glrtx_track_moments); off by default, switching it off releases M."""
         self._ck(self.L.glrtx_track_moments(self.h, int(bool(enable))))
@@ -1024,10 +1020,7 @@ class Device:
         self._ck(self.L.glrtx_render_moments(self.h, C.byref(p), _fp(sd), sd.shape[0]))
     def read_moments(self) -> np.ndarray:
         """The moments plane M {sum l, sum l^2, 0, count}, (owned_rows, width, 4) float32 like read_accum (syncs)."""
-        s = self.stats()
-        out = np.zeros((s.owned_rows, s.width, 4), np.float32)
-        self._ck(self.L.glrtx_read_moments(self.h, out.ctypes.data, s.width * 16))
-        return out
+        return _read_image(self.L, self.h, self.L.glrtx_read_moments)
     def denoise_variance(self, iterations=None, sigma_lum=None, sigma_normal=None, sigma_depth=None, demodulate=None):
         """The variance-guided a-trous filter over the accumulator's mean, steered by M and the feature planes as they stand (glrtx_denoise_variance); the result
         is read with read_denoised / resolve_denoised_rgba8.  None: the default."""
@@ -1045,10 +1038,7 @@ class Device:
         self._ck(self.L.glrtx_render_cascades(self.h, C.byref(p), _fp(sd), sd.shape[0]))
     def read_cascades(self) -> np.ndarray:
         """The cascade planes C {sum w r, sum w g, sum w b, count}, (6, owned_rows, width, 4) float32 (syncs)."""
-        s = self.stats()
-        out = np.zeros((6, s.owned_rows, s.width, 4), np.float32)
-        self._ck(self.L.glrtx_read_cascades(self.h, out.ctypes.data, s.width * 16))
-        return out
+        return _read_image(self.L, self.h, self.L.glrtx_read_cascades, planes=(6,))
     def reweight(self, cfg=None, kappa=None):
         """The firefly re-weighting resolve of C into the image D (glrtx_reweight); the result is read with read_denoised / resolve_denoised_rgba8 and is
         source = 1 of the tone-mapping and bloom calls.  None: the default."""
@@ -1077,10 +1067,7 @@ class Device:
     def read_features_geom(self) -> np.ndarray:
         """The geometry plane G, (owned_rows, width, 4) float32 (syncs): [..., 0] the wire triangle index as int32 bits (-1: a miss), [..., 1:3] the hit's
         barycentrics."""
-        s = self.stats()
-        g = np.zeros((s.owned_rows, s.width, 4), np.float32)
-        self._ck(self.L.glrtx_read_features_geom(self.h, g.ctypes.data, s.width * 16))
-        return g
+        return _read_image(self.L, self.h, self.L.glrtx_read_features_geom)
     def reproject_motion(self, params, max_history=None, depth_tolerance=None, normal_tolerance=None):
         """Device.reproject for geometry that update_vertices moved since the last feature pass (glrtx_reproject_motion; needs track_motion)."""
         p = make_params(params)
@@ -1103,16 +1090,10 @@ class Device:
         self._ck(self.L.glrtx_tonemap(self.h, C.byref(_tonemap_cfg(cfg, fields))))
     def read_tonemapped(self) -> np.ndarray:
         """The plane T, (owned_rows, width, 4) float32 {y.rgb, 1} (syncs)."""
-        s = self.stats()
-        out = np.zeros((s.owned_rows, s.width, 4), np.float32)
-        self._ck(self.L.glrtx_read_tonemapped(self.h, out.ctypes.data, s.width * 16))
-        return out
+        return _read_image(self.L, self.h, self.L.glrtx_read_tonemapped)
     def resolve_tonemapped_rgba8(self, cfg=None, **fields) -> np.ndarray:
         """The cfg's source through the curve and the resolve in one pass (glrtx_resolve_tonemapped_rgba8): (owned_rows, width, 4) uint8."""
-        s = self.stats()
-        out = np.zeros((s.owned_rows, s.width, 4), np.uint8)
-        self._ck(self.L.glrtx_resolve_tonemapped_rgba8(self.h, out.ctypes.data, s.width * 4, C.byref(_tonemap_cfg(cfg, fields))))
-        return out
+        return _read_image(self.L, self.h, self.L.glrtx_resolve_tonemapped_rgba8, C.byref(_tonemap_cfg(cfg, fields)), dtype=np.uint8)
     def tonemap_burst_ms(self, which, reps=20, cfg=None, **fields) -> float:
         """Device time of one launch of a tone-mapping pass from `reps` launches back to back (glrtx_debug_tonemap_burst).  which: 0 the plain resolve kernel,
         1 the fused tone-mapping resolve, 2 the plane kernel, 3 a measurement."""
@@ -1125,19 +1106,13 @@ class Device:
         self._ck(self.L.glrtx_bloom(self.h, C.byref(_bloom_cfg(cfg, fields))))
     def read_bloomed(self) -> np.ndarray:
         """The plane B, (owned_rows, width, 4) float32 {x + strength * glow, 1} (syncs)."""
-        s = self.stats()
-        out = np.zeros((s.owned_rows, s.width, 4), np.float32)
-        self._ck(self.L.glrtx_read_bloomed(self.h, out.ctypes.data, s.width * 16))
-        return out
+        return _read_image(self.L, self.h, self.L.glrtx_read_bloomed)
     def tonemap_bloomed(self, cfg=None, **fields):
         """The tone curve over B into the context's plane T (glrtx_tonemap_bloomed; the cfg's source is not read); no sync."""
         self._ck(self.L.glrtx_tonemap_bloomed(self.h, C.byref(_tonemap_cfg(cfg, fields))))
     def resolve_bloomed_rgba8(self, cfg=None, **fields) -> np.ndarray:
         """B through the curve and the resolve in one pass (glrtx_resolve_bloomed_rgba8; the cfg's source is not read): (owned_rows, width, 4) uint8."""
-        s = self.stats()
-        out = np.zeros((s.owned_rows, s.width, 4), np.uint8)
-        self._ck(self.L.glrtx_resolve_bloomed_rgba8(self.h, out.ctypes.data, s.width * 4, C.byref(_tonemap_cfg(cfg, fields))))
-        return out
+        return _read_image(self.L, self.h, self.L.glrtx_resolve_bloomed_rgba8, C.byref(_tonemap_cfg(cfg, fields)), dtype=np.uint8)
     def bloom_burst_ms(self, reps=20, cfg=None, **fields) -> float:
         """Device time of one glrtx_bloom from `reps` of them back to back (glrtx_debug_bloom_burst)."""
         ms = C.c_float(0)
@@ -1231,22 +1206,21 @@ class Group:
         a, t = C.c_int(0), C.c_int(0)
         self._ck(self.L.glrtx_group_adaptive_active_tiles(self.h, C.byref(a), C.byref(t)))
         return int(a.value), int(t.value)
-    def _member_array(self, i, shape, dtype, fn, *args):
-        m = self.L.glrtx_group_ctx(self.h, i)
-        s = Stats()
-        self.L.glrtx_get_stats(m, C.byref(s))
-        out = np.zeros(shape(s), dtype)
-        rc = fn(m, out.ctypes.data_as(C.POINTER(C.c_uint8)) if dtype == np.uint8 else out.ctypes.data, *[a(s) for a in args])
-        if rc != 0:
-            raise GlrtxError(rc, self.L.glrtx_last_error(m).decode())
-        return out
     def tile_mask(self):
         """Each member's last selection mask (its own owned-row tiles): a list of (tiles_y, tiles_x) uint8."""
-        return [self._member_array(i, lambda s: ((s.owned_rows + 7) // 8, (s.width + 7) // 8), np.uint8, self.L.glrtx_read_tile_mask) for i in range(self.size())]
+        out = []
+        for i in range(self.size()):
+            m = self.L.glrtx_group_ctx(self.h, i)
+            s = Stats()
+            self.L.glrtx_get_stats(m, C.byref(s))
+            out.append(np.zeros(((s.owned_rows + 7) // 8, (s.width + 7) // 8), np.uint8))
+            rc = self.L.glrtx_read_tile_mask(m, out[-1].ctypes.data_as(C.POINTER(C.c_uint8)))
+            if rc != 0:
+                raise GlrtxError(rc, self.L.glrtx_last_error(m).decode())
+        return out
     def read_adaptive_half(self):
         """Each member's half buffer: a list of (owned_rows, width, 4) float32."""
-        return [self._member_array(i, lambda s: (s.owned_rows, s.width, 4), np.float32, self.L.glrtx_read_adaptive_half, lambda s: s.width * 16)
-                for i in range(self.size())]
+        return [_read_image(self.L, self.L.glrtx_group_ctx(self.h, i), self.L.glrtx_read_adaptive_half) for i in range(self.size())]
 
     def stats(self) -> Stats:
         s = Stats()
