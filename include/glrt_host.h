@@ -236,6 +236,19 @@ int glrt_bloom(const float *src, int width, int rows, float threshold, float str
 int glrt_skin_vertices(const float *rest_vert, size_t n_vert, const int32_t *bones4, const float *weights4, const float *matrices, int n_bones,
                        float *vert_out);
 
+/* Deforming: the CPU statement of the device's deform pass (glrtx_pose_morph / glrtx_pose_dualquat / glrtx_debug_deform, include/glrtx.h "Deforming": the
+ * arithmetic is there), bit for bit (host/deform.cpp; tests/deform_math.py states it in numpy).  The rig is glrt_skin_vertices'; bone_data: mode 0, n_bones x 12
+ * floats (matrices); mode 1, n_bones x 8 floats {r.x, r.y, r.z, r.w, d.x, d.y, d.z, d.w} (dual quaternions); deltas: n_targets x n_vert x 6 floats {dpos,
+ * dnormal}, target-major; morph_weights: n_targets floats.  A target whose weight is a zero or a denormal is not read.  Runs with denormals flushed (MXCSR FTZ |
+ * DAZ, restored on return).  Bone weights, bone data and deltas are NOT checked for finiteness.  GLRT_HOST_EINVAL: what glrt_skin_vertices refuses, a mode other
+ * than 0 and 1, n_targets outside 0..GLRT_MAX_MORPH_TARGETS, NULL deltas or morph_weights with n_targets > 0, a morph weight that is not finite. */
+#define GLRT_MAX_MORPH_TARGETS 64
+int glrt_deform_vertices(const float *rest_vert, size_t n_vert, const int32_t *bones4, const float *weights4, const float *bone_data, int n_bones, int mode,
+                         const float *deltas, const float *morph_weights, int n_targets, float *vert_out);
+/* The dual quaternion {r.x, r.y, r.z, r.w, d.x, d.y, d.z, d.w} of a rigid 3x4 matrix (row-major; the rotation is taken as orthonormal): computed in double and
+ * rounded once, with the sign that makes r.w >= 0.  d = 1/2 (t, 0) * r. */
+void glrt_dualquat_from_matrix(const float m[12], float dq[8]);
+
 void glrt_look_at(const float eye[3], const float center[3], const float up[3], float out[16]);
 void glrt_perspective(float fovy_deg, float aspect, float z_near, float z_far, float out[16]);
 void glrt_mat4_mul(const float a[16], const float b[16], float out[16]);

@@ -955,6 +955,59 @@ int glrtx_pose(glrtx_ctx *ctx, const float *matrices, int n_bones);
 int glrtx_debug_skin(const float *rest, size_t n_vert, const int32_t *bones4, const float *weights4, const float *matrices, int n_bones, float *vert_out);
 int glrtx_debug_skin_burst(glrtx_ctx *ctx, int reps, float *ms_per_launch);
 
+/* ---- Deforming: morph targets and dual-quaternion skinning on the device, in the same place as Posing (no reference counterpart; off unless called: no other
+ * call's behaviour changes).  Two things bones of matrices cannot say: a shape that is no bone's -- a face, a cloth or fluid cache, an OBJ sequence: blend
+ * shapes --, and a twist that keeps its volume (linear blending takes a joint turned by 180 degrees between two bones to radius 0 at its mid ring).  One pass
+ * (csrc/skin.hip.h: deform_kernel) in front of the refit does both; everything behind it sees a vertex update, as after glrtx_pose.
+ *
+ * Arithmetic.  The rules are Posing's: one correctly rounded fp32 operation at a time, unfused, in the order written; denormals are zeros of their sign into
+ * and out of every operation; a stored NaN is 0x7FC00000; dot(a, v) = (a2 v.z + a1 v.y) + a0 v.x; blend(w, m) = ((w0 m0 + w1 m1) + w2 m2) + w3 m3.
+ *
+ * MORPH TARGETS.  A rig may carry n_targets <= GLRTX_MAX_MORPH_TARGETS = 64 targets.  Each target is n_vert x 6 floats {dpos, dnormal}, target-major, dense.
+ * A pose carries n_targets weights; they are checked finite on the host (a non-finite weight is GLRTX_EINVAL and nothing is issued).
+ *   Active    a target is active iff |w| >= 2^-126 (non-zero after the flush).  Inactive targets are not read at all: a NaN or Inf delta under a zero weight
+ *             changes nothing (the case a careless 0 * delta gets wrong).
+ *   Morph     per vertex, over the active targets in ascending index:  p[i] = p[i] + w_k * dpos_k[i]  and  n[i] = n[i] + w_k * dnormal_k[i]  -- a rounded
+ *             product, then a rounded sum --, starting from the rest position and normal.
+ * Morphing runs before skinning (glTF's order): the morphed p, n and the rest tangent, binormal and uv then go through the skinning stage.  With no active
+ * target the result is Posing's, bit for bit.
+ *
+ * DUAL-QUATERNION POSE.  n_bones x 8 floats {r.x, r.y, r.z, r.w, d.x, d.y, d.z, d.w}; w is the scalar part; d = 1/2 (t, 0) * r for a rotation r and a
+ * translation t.  The values are checked finite, not checked for unit length.  dot4(a, b) = ((a.w b.w + a.z b.z) + a.y b.y) + a.x b.x.  Per vertex:
+ *   Sign      s0 = w0;  for k = 1..3: h = dot4(r_b0, r_bk), s_k = h < 0 ? -w_k : w_k.  The negation flips the sign bit; a NaN h keeps w_k.
+ *   Blend     R[j] = blend(s, r_b.[j]) and D[j] = blend(s, d_b.[j]): eight blends, all terms always formed.
+ *   Normalise l = sqrt(dot4(R, R));  each of the eight entries becomes l > 0 ? x / l : x, IEEE quotients.
+ *   Rotation  the nine products xx, yy, zz, xy, xz, yz, wx, wy, wz of R's x, y, z, w;
+ *               L00 = 1 - 2 (yy + zz)    L01 = 2 (xy - wz)        L02 = 2 (xz + wy)
+ *               L10 = 2 (xy + wz)        L11 = 1 - 2 (xx + zz)    L12 = 2 (yz - wx)
+ *               L20 = 2 (xz - wy)        L21 = 2 (yz + wx)        L22 = 1 - 2 (xx + yy)
+ *   Translation  t.x = 2 (((R.w D.x - D.w R.x) + R.y D.z) - R.z D.y);  t.y and t.z follow with x -> y -> z advanced cyclically.
+ * From there the vertex is Posing's with B = [L | t]: position, the normal through the cofactor matrix and the l > 0 normalisation, tangent and binormal, uv
+ * as words -- the text is Posing's.  Negating all eight floats of a bone changes nothing unless an h is exactly 0.  The CPU statement is glrt_deform_vertices
+ * (include/glrt_host.h), bit for bit; glrt_dualquat_from_matrix there makes a bone's eight floats from a rigid 3x4 matrix.
+ *
+ *   glrtx_upload_morph_targets  keeps the deltas on the device in the layout they come in.  Needs a rig with that n_vert; n_targets == 0 drops the targets.
+ *                     GLRTX_EINVAL, nothing changed: no rig, another n_vert, n_targets outside 0..64, NULL deltas.  glrtx_upload_rig and glrtx_upload_scene
+ *                     forget the targets; glrtx_update_vertices / _device keep them.  Deltas are not checked, as rest vertices are not.
+ *   glrtx_pose_morph  glrtx_pose with morph weights: matrices as there.  glrtx_pose_dualquat: the same with a dual-quaternion pose.  n_targets must be the
+ *                     rig's; 0 with a NULL pointer is allowed when the rig has none.  Both take exactly glrtx_pose's path behind the kernel: the seal, the
+ *                     motion snapshot, the refit and the same blocking read-back; afterwards every device scene buffer is byte for byte what
+ *                     glrtx_update_vertices(ctx, glrt_deform_vertices(...)) leaves.  GLRTX_EINVAL, every device buffer untouched: no rig, a bone or target
+ *                     count other than the rig's, a NULL pointer, a non-finite pose entry or morph weight.
+ *   glrtx_debug_deform  the kernel alone on host arrays on the current HIP device, no context.  mode 0: bone_data is n_bones x 12 (matrices), 1: n_bones x 8
+ *                     (dual quaternions).  Refuses what glrt_deform_vertices refuses (bone weights, bone data and deltas are not checked; morph weights are,
+ *                     because the host decides from them which targets the kernel reads).
+ *   glrtx_debug_deform_burst  device time of the kernel by itself, as glrtx_debug_skin_burst: the last glrtx_pose_morph / glrtx_pose_dualquat launch again.
+ *                     GLRTX_EINVAL before a first one.
+ * Groups: no call. */
+#define GLRTX_MAX_MORPH_TARGETS 64
+int glrtx_upload_morph_targets(glrtx_ctx *ctx, const float *deltas, int n_targets, size_t n_vert);
+int glrtx_pose_morph(glrtx_ctx *ctx, const float *matrices, int n_bones, const float *morph_weights, int n_targets);
+int glrtx_pose_dualquat(glrtx_ctx *ctx, const float *dualquats, int n_bones, const float *morph_weights, int n_targets);
+int glrtx_debug_deform(const float *rest, size_t n_vert, const int32_t *bones4, const float *weights4, const float *bone_data, int n_bones, int mode,
+                       const float *deltas, const float *morph_weights, int n_targets, float *vert_out);
+int glrtx_debug_deform_burst(glrtx_ctx *ctx, int reps, float *ms_per_launch);
+
 /* ---- Groups: the same device layer on several GPUs of one node, behind one handle and one host thread.
  * No reference counterpart (the reference is single-GPU); SURVEY.md 8(b) sketches glrtx_create(ctx**, device_ids, n) with a
  * gathering read_accum -- this is that, kept apart from the single-context calls.  Member i owns the 8-row stripes s with

@@ -173,9 +173,12 @@ struct glrtx_ctx {
     } rf;
     // The rig (glrtx_upload_rig; skin.hip.h), the scene's until the next glrtx_upload_scene: the rest pose, the {bones, weights} records and the pose matrices of
     // the last glrtx_pose.  n_bones == 0: no rig.
+    // Deforming (glrtx_upload_morph_targets, glrtx_pose_morph, glrtx_pose_dualquat): the rig's morph targets as uploaded (n_targets x n_vert x 24 bytes; n_targets
+    // == 0: none), the dual quaternions of the last glrtx_pose_dualquat, and the arguments of the last deform launch for the timing hook (mode -1: none yet).
     struct Rig {
-        DevBuf rest, rig, pose;
-        int n_bones = 0;
+        DevBuf rest, rig, pose, dq, morph;
+        int n_bones = 0, n_targets = 0, deform_mode = -1;
+        skin::DeformArgs deform{};
     } sk;
 
     // Presentation (glrtx_present_enable): frame seq of the ring goes to image seq % ring -- device image (written by the presenting pass on the context's stream),
@@ -2163,7 +2166,7 @@ void glrtx_destroy(glrtx_ctx *c) {
     dev_free(c->wfState); dev_free(c->wfQ); dev_free(c->wfSeeds); dev_free(c->wfPlanes);
     dev_free(c->bvhVert); dev_free(c->bvhTri); dev_free(c->bvhNodes);
     dev_free(c->rf.ints); dev_free(c->rf.keys); dev_free(c->rf.vert);
-    dev_free(c->sk.rest); dev_free(c->sk.rig); dev_free(c->sk.pose);
+    dev_free(c->sk.rest); dev_free(c->sk.rig); dev_free(c->sk.pose); dev_free(c->sk.dq); dev_free(c->sk.morph);
     dev_free(c->qwire); dev_free(c->qcounter); dev_free(c->qrays); dev_free(c->qhits);
     if (c->rf.slot_ev) (void)hipEventDestroy(c->rf.slot_ev);
     if (c->bvhWs.p) { (void)hipFree(c->bvhWs.p); c->bvhWs.p = nullptr; c->bvhWs.bytes = 0; }
@@ -2251,6 +2254,8 @@ int glrtx_upload_scene(glrtx_ctx *c, const float *vert, size_t n_vert, const flo
     dev_free(c->mtPos); dev_free(c->mtNrm);  // (glrtx_track_motion: the previous geometry was another scene's; the stream is idle)
     c->mt_geom = glrtx_ctx::kMtNone;
     dev_free(c->sk.rest); dev_free(c->sk.rig); dev_free(c->sk.pose);  // (glrtx_upload_rig: the rig was another scene's)
+    dev_free(c->sk.dq); dev_free(c->sk.morph);
+    c->sk.n_targets = 0; c->sk.deform_mode = -1;
     c->sk.n_bones = 0;
     c->st.stack_entries = stack_need;
     c->st.lds_bytes = lds_bytes_for(sc);
@@ -2391,6 +2396,8 @@ int glrtx_upload_rig(glrtx_ctx *c, const float *rest_vert, size_t n_vert, const 
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));  // (a glrtx_pose's kernel has run: glrtx_pose blocks; this orders the frees behind anything else on the stream)
     c->sk.n_bones = 0;  // (until all three buffers are in place)
+    dev_free(c->sk.morph);  // the morph targets were the previous rig's (glrtx_upload_morph_targets)
+    c->sk.n_targets = 0; c->sk.deform_mode = -1;
     if (int rc = dev_upload(c, c->sk.rest, rest_vert, n_vert * skin::kVertexWords * sizeof(float))) return rc;
     if (int rc = dev_upload(c, c->sk.rig, rig.data(), rig.size() * sizeof(uint4))) return rc;
     if (int rc = ensure(c, c->sk.pose, (size_t)n_bones * 12 * sizeof(float))) return rc;
@@ -2451,6 +2458,135 @@ int glrtx_debug_skin_burst(glrtx_ctx *c, int reps, float *ms_per_launch) {
     HIP_TRY(c, hipSetDevice(c->device));
     const skin::Args a{(const unsigned *)c->sk.rest.p, (const uint4 *)c->sk.rig.p, (const float4 *)c->sk.pose.p, (unsigned *)c->rf.vert.p, n_vert};
     return burst_time(c, reps, ms_per_launch, [&] { skin_launch(a, c->stream); return GLRTX_OK; });
+}
+
+namespace {
+
+// ---- deforming (glrtx_upload_morph_targets, glrtx_pose_morph, glrtx_pose_dualquat, glrtx_debug_deform; skin.hip.h: deform_kernel)
+static_assert(skin::kMaxTargets == GLRTX_MAX_MORPH_TARGETS, "skin.hip.h and glrtx.h disagree");
+
+// The kernel's list of active targets: those whose weight is not a zero after the flush, in ascending index
+void morph_list(skin::Morph &m, const float *weights, int n_targets) {
+    m.n_active = 0;
+    for (int k = 0; k < n_targets; k++)
+        if (std::fabs(weights[k]) >= 1.17549435e-38f) {  // 2^-126
+            m.index[m.n_active] = (unsigned)k;
+            m.weight[m.n_active++] = weights[k];
+        }
+}
+
+// What the pose calls and the debug hook refuse alike about the morph weights
+int morph_check(glrtx_ctx *c, const float *morph_weights, int n_targets, const char *fn) {
+    if (n_targets < 0 || n_targets > GLRTX_MAX_MORPH_TARGETS) return fail(c, GLRTX_EINVAL, "%s: %d morph targets (0 .. %d)", fn, n_targets, GLRTX_MAX_MORPH_TARGETS);
+    if (n_targets > 0 && !morph_weights) return fail(c, GLRTX_EINVAL, "%s: NULL morph weights", fn);
+    if (!all_finite(morph_weights, (size_t)n_targets)) return fail(c, GLRTX_EINVAL, "%s: a morph weight is not finite", fn);
+    return GLRTX_OK;
+}
+
+void deform_launch(const skin::DeformArgs &a, int mode, hipStream_t stream) {
+    if (a.n_vert == 0) return;
+    const dim3 grid((unsigned)((a.n_vert + skin::kBlock - 1) / skin::kBlock)), block(skin::kBlock);
+    if (mode) hipLaunchKernelGGL(skin::deform_kernel<true>, grid, block, 0, stream, a);
+    else hipLaunchKernelGGL(skin::deform_kernel<false>, grid, block, 0, stream, a);
+}
+
+// glrtx_pose_morph (mode 0: n_bones x 12 floats) and glrtx_pose_dualquat (mode 1: n_bones x 8 floats): glrtx_pose with the deform kernel in the skinning kernel's place
+int deform_pose(glrtx_ctx *c, const float *bone_data, int n_bones, const float *morph_weights, int n_targets, int mode, const char *fn) {
+    if (!c) return GLRTX_EINVAL;
+    if (!c->have_scene || c->sk.n_bones == 0) return fail(c, GLRTX_EINVAL, "%s: no rig uploaded (glrtx_upload_rig)", fn);
+    if (n_bones != c->sk.n_bones) return fail(c, GLRTX_EINVAL, "%s: %d bones, the rig has %d", fn, n_bones, c->sk.n_bones);
+    if (n_targets != c->sk.n_targets) return fail(c, GLRTX_EINVAL, "%s: %d morph weights, the rig has %d targets", fn, n_targets, c->sk.n_targets);
+    if (!bone_data) return fail(c, GLRTX_EINVAL, "%s: NULL pose", fn);
+    if (int rc = morph_check(c, morph_weights, n_targets, fn)) return rc;
+    const size_t pose_bytes = (size_t)n_bones * (mode ? 8 : 12) * sizeof(float);
+    if (!all_finite(bone_data, pose_bytes / sizeof(float))) return fail(c, GLRTX_EINVAL, "%s: a pose entry is not finite", fn);
+    seal_feed(c);
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t n_vert = c->rf.n_vert;
+    if (int rc = ensure(c, c->rf.vert, n_vert * skin::kVertexWords * sizeof(float))) return rc;
+    DevBuf &pose = mode ? c->sk.dq : c->sk.pose;
+    if (int rc = ensure(c, pose, pose_bytes)) return rc;
+    HIP_TRY(c, hipMemcpyAsync(pose.p, bone_data, pose_bytes, hipMemcpyHostToDevice, c->stream));
+    skin::DeformArgs &a = c->sk.deform;
+    a = skin::DeformArgs{(const unsigned *)c->sk.rest.p, (const uint4 *)c->sk.rig.p, (const float4 *)pose.p, (unsigned *)c->rf.vert.p, n_vert,
+                         (const float2 *)c->sk.morph.p, {}};
+    morph_list(a.morph, morph_weights, n_targets);
+    c->sk.deform_mode = mode;
+    deform_launch(a, mode, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    if (c->mt_on && c->mt_geom == glrtx_ctx::kMtCurrent)  // (glrtx_pose's path from here)
+        if (int rc = motion_snapshot(c)) return rc;
+    return refit_run(c, c->rf.vert.p);
+}
+
+}  // namespace
+
+int glrtx_upload_morph_targets(glrtx_ctx *c, const float *deltas, int n_targets, size_t n_vert) {
+    const char *fn = "glrtx_upload_morph_targets";
+    if (!c) return GLRTX_EINVAL;
+    if (!c->have_scene || c->sk.n_bones == 0) return fail(c, GLRTX_EINVAL, "%s: no rig uploaded (glrtx_upload_rig)", fn);
+    if (n_vert != c->rf.n_vert) return fail(c, GLRTX_EINVAL, "%s: %zu vertices, the rig has %zu", fn, n_vert, c->rf.n_vert);
+    if (n_targets < 0 || n_targets > GLRTX_MAX_MORPH_TARGETS) return fail(c, GLRTX_EINVAL, "%s: %d morph targets (0 .. %d)", fn, n_targets, GLRTX_MAX_MORPH_TARGETS);
+    if (n_targets > 0 && n_vert > 0 && !deltas) return fail(c, GLRTX_EINVAL, "%s: NULL deltas", fn);
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));  // (as glrtx_upload_rig: the free is ordered behind anything on the stream)
+    c->sk.n_targets = 0; c->sk.deform_mode = -1;
+    if (n_targets == 0) {
+        dev_free(c->sk.morph);
+        return GLRTX_OK;
+    }
+    if (int rc = dev_upload(c, c->sk.morph, deltas, (size_t)n_targets * n_vert * skin::kDeltaWords * sizeof(float))) return rc;
+    c->sk.n_targets = n_targets;
+    return GLRTX_OK;
+}
+
+int glrtx_pose_morph(glrtx_ctx *c, const float *matrices, int n_bones, const float *morph_weights, int n_targets) {
+    return deform_pose(c, matrices, n_bones, morph_weights, n_targets, 0, "glrtx_pose_morph");
+}
+
+int glrtx_pose_dualquat(glrtx_ctx *c, const float *dualquats, int n_bones, const float *morph_weights, int n_targets) {
+    return deform_pose(c, dualquats, n_bones, morph_weights, n_targets, 1, "glrtx_pose_dualquat");
+}
+
+int glrtx_debug_deform(const float *rest, size_t n_vert, const int32_t *bones4, const float *weights4, const float *bone_data, int n_bones, int mode,
+                       const float *deltas, const float *morph_weights, int n_targets, float *vert_out) {
+    const char *fn = "glrtx_debug_deform";
+    if (int rc = rig_check(nullptr, rest, n_vert, bones4, weights4, n_bones, fn)) return rc;
+    if (mode != 0 && mode != 1) return fail(nullptr, GLRTX_EINVAL, "%s: mode %d (0: matrices, 1: dual quaternions)", fn, mode);
+    if (int rc = morph_check(nullptr, morph_weights, n_targets, fn)) return rc;
+    if (!bone_data || (n_vert > 0 && (!vert_out || (n_targets > 0 && !deltas)))) return fail(nullptr, GLRTX_EINVAL, "%s: NULL buffer", fn);
+    if (n_vert == 0) return GLRTX_OK;
+    std::vector<uint4> rig;
+    rig_records(rig, n_vert, bones4, weights4);
+    const size_t bytes = n_vert * skin::kVertexWords * sizeof(float);
+    DebugScratch s;
+    skin::DeformArgs a{};
+    a.rest = s.alloc<unsigned>(bytes, rest);
+    a.rig = s.alloc<uint4>(rig.size() * sizeof(uint4), rig.data());
+    a.pose = s.alloc<float4>((size_t)n_bones * (mode ? 8 : 12) * sizeof(float), bone_data);
+    a.out = s.alloc<unsigned>(bytes);
+    a.n_vert = n_vert;
+    if (n_targets > 0) a.deltas = s.alloc<float2>((size_t)n_targets * n_vert * skin::kDeltaWords * sizeof(float), deltas);
+    morph_list(a.morph, morph_weights, n_targets);
+    if (s.ok()) {
+        deform_launch(a, mode, 0);
+        s.e = hipGetLastError();
+    }
+    s.sync();
+    s.download(vert_out, a.out, bytes);
+    return s.result(GLRTX_OK, fn);
+}
+
+// Device time of the deform kernel by itself, as glrtx_debug_skin_burst: the last glrtx_pose_morph / glrtx_pose_dualquat launch again, into the context's vertex
+// buffer -- which holds exactly that already, unless another call has written it since.
+int glrtx_debug_deform_burst(glrtx_ctx *c, int reps, float *ms_per_launch) {
+    const char *fn = "glrtx_debug_deform_burst";
+    if (!c || !ms_per_launch || reps < 1) return GLRTX_EINVAL;
+    if (!c->have_scene || c->sk.n_bones == 0 || c->sk.deform_mode < 0)
+        return fail(c, GLRTX_EINVAL, "%s: no rig uploaded, or no glrtx_pose_morph / glrtx_pose_dualquat yet", fn);
+    seal_feed(c);
+    HIP_TRY(c, hipSetDevice(c->device));
+    return burst_time(c, reps, ms_per_launch, [&] { deform_launch(c->sk.deform, c->sk.deform_mode, c->stream); return GLRTX_OK; });
 }
 
 namespace {

@@ -10,6 +10,18 @@
 //       not 16-byte aligned; the 64 records of a wave are 3840 contiguous bytes, so every cache line a wave touches is used whole), the 32-byte rig record {b[4],
 //       w[4]} as two 16-byte loads, 4 x 48 bytes of matrices as twelve 16-byte loads (a pose is a few kilobytes: cache-resident), 15 dword stores.  152 bytes of
 //       compulsory traffic per vertex.  No LDS, no atomics, no scratch.
+//
+// Deforming (glrtx_upload_morph_targets, glrtx_pose_morph, glrtx_pose_dualquat, glrtx_debug_deform; include/glrtx.h "Deforming"): morph targets in front of the
+// skinning stage, and dual quaternions as a second way to state a bone.  host/deform.cpp (glrt_deform_vertices) and tests/deform_math.py state it again.
+//
+//   deform_kernel<DQ>  skin_kernel's shape: one thread per vertex, 256-thread workgroups, no LDS, no atomics, no scratch.  The active morph targets arrive
+//       compacted by the host in the kernel's arguments -- a count, and an index and a weight per target --, so the loop's trip count, the weights and each
+//       target's base address are scalar (s_load from the argument segment, scalar address arithmetic); only the deltas are per-lane loads.  The deltas keep the
+//       layout they are uploaded in, target-major and dense, 24 bytes {dpos, dnormal} a vertex: a lane reads its record as three 8-byte loads (24 i is 8-byte
+//       aligned), a wave's 64 records are 1536 contiguous bytes, and a target that is not active is never touched because no byte of it lies between the bytes
+//       of one that is.  DQ = false: bones are skin_kernel's 48-byte matrices, 152 + 24 active bytes a vertex.  DQ = true: a bone is 32 bytes {r, d}, two
+//       16-byte loads a bone and lane, 136 + 24 active bytes a vertex; sign, blend, normalise, and the 3x4 matrix [L | t] of the blended dual quaternion.  Both
+//       end in the same tail (transform_store), which is skin_kernel's arithmetic from B on.
 #pragma once
 #include "denoise.hip.h"
 
@@ -86,6 +98,115 @@ __global__ __launch_bounds__(kBlock) void skin_kernel(const Args a) {
     unsigned *d = a.out + kVertexWords * i;
 #pragma unroll
     for (int k = 0; k < kVertexWords; k++) d[k] = o[k];
+}
+
+// ---- Deforming
+constexpr int kMaxTargets = 64;  // GLRTX_MAX_MORPH_TARGETS
+constexpr int kDeltaWords = 6;   // {dpos, dnormal}
+
+// The active targets of one pose, compacted by the host (a target is active iff its weight is not a zero after the flush): wave-uniform
+struct Morph {
+    int n_active;
+    unsigned index[kMaxTargets];
+    float weight[kMaxTargets];
+};
+
+struct DeformArgs {
+    const unsigned *rest;  // as Args
+    const uint4 *rig;
+    const float4 *pose;    // DQ = false: n_bones x 3 matrix rows; DQ = true: n_bones x 2 {r.x, r.y, r.z, r.w} {d.x, d.y, d.z, d.w}
+    unsigned *out;
+    size_t n_vert;
+    const float2 *deltas;  // n_targets x n_vert x 3: {dpos.x, dpos.y} {dpos.z, dnormal.x} {dnormal.y, dnormal.z}; never read when n_active == 0
+    Morph morph;
+};
+
+DEV float dot4(const float4 a, const float4 b) { return ((a.w * b.w + a.z * b.z) + a.y * b.y) + a.x * b.x; }
+DEV float4 quot4(const float4 a, float l, bool unit) { return make_float4(unit ? a.x / l : a.x, unit ? a.y / l : a.y, unit ? a.z / l : a.z, unit ? a.w / l : a.w); }
+
+// Posing from B on: position, the normal through the cofactor matrix, tangent and binormal, uv as words.  p, n: the (morphed) position and normal; `in`: the
+// rest record, for uv, tangent and binormal.
+DEV void transform_store(const float4 B0, const float4 B1, const float4 B2, const unsigned (&in)[kVertexWords], float px, float py, float pz, float nx, float ny,
+                         float nz, unsigned *d) {
+    const float tx = __uint_as_float(in[9]), ty = __uint_as_float(in[10]), tz = __uint_as_float(in[11]);
+    const float bx = __uint_as_float(in[12]), by = __uint_as_float(in[13]), bz = __uint_as_float(in[14]);
+    unsigned o[kVertexWords];
+    o[0] = word(dot3(B0.x, B0.y, B0.z, px, py, pz) + B0.w);
+    o[1] = word(dot3(B1.x, B1.y, B1.z, px, py, pz) + B1.w);
+    o[2] = word(dot3(B2.x, B2.y, B2.z, px, py, pz) + B2.w);
+    const float c00 = B1.y * B2.z - B1.z * B2.y, c01 = B1.z * B2.x - B1.x * B2.z, c02 = B1.x * B2.y - B1.y * B2.x;
+    const float c10 = B2.y * B0.z - B2.z * B0.y, c11 = B2.z * B0.x - B2.x * B0.z, c12 = B2.x * B0.y - B2.y * B0.x;
+    const float c20 = B0.y * B1.z - B0.z * B1.y, c21 = B0.z * B1.x - B0.x * B1.z, c22 = B0.x * B1.y - B0.y * B1.x;
+    const float vx = dot3(c00, c01, c02, nx, ny, nz), vy = dot3(c10, c11, c12, nx, ny, nz), vz = dot3(c20, c21, c22, nx, ny, nz);
+    const float s = dot3(vx, vy, vz, vx, vy, vz);
+    const float l = __builtin_sqrtf(s);
+    const bool unit = l > 0.0f;
+    o[3] = word(unit ? vx / l : vx);
+    o[4] = word(unit ? vy / l : vy);
+    o[5] = word(unit ? vz / l : vz);
+    o[6] = in[6]; o[7] = in[7]; o[8] = in[8];
+    o[9] = word(dot3(B0.x, B0.y, B0.z, tx, ty, tz));
+    o[10] = word(dot3(B1.x, B1.y, B1.z, tx, ty, tz));
+    o[11] = word(dot3(B2.x, B2.y, B2.z, tx, ty, tz));
+    o[12] = word(dot3(B0.x, B0.y, B0.z, bx, by, bz));
+    o[13] = word(dot3(B1.x, B1.y, B1.z, bx, by, bz));
+    o[14] = word(dot3(B2.x, B2.y, B2.z, bx, by, bz));
+#pragma unroll
+    for (int k = 0; k < kVertexWords; k++) d[k] = o[k];
+}
+
+template <bool DQ>
+__global__ __launch_bounds__(kBlock) void deform_kernel(const DeformArgs a) {
+    const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= a.n_vert) return;
+    const unsigned *r = a.rest + kVertexWords * i;
+    unsigned in[kVertexWords];
+#pragma unroll
+    for (int k = 0; k < kVertexWords; k++) in[k] = r[k];
+    const uint4 b = a.rig[2 * i];
+    const uint4 wu = a.rig[2 * i + 1];
+    const float4 w = make_float4(__uint_as_float(wu.x), __uint_as_float(wu.y), __uint_as_float(wu.z), __uint_as_float(wu.w));
+
+    // Morph: over the active targets in ascending index, a rounded product and a rounded sum a component
+    float px = __uint_as_float(in[0]), py = __uint_as_float(in[1]), pz = __uint_as_float(in[2]);
+    float nx = __uint_as_float(in[3]), ny = __uint_as_float(in[4]), nz = __uint_as_float(in[5]);
+    for (int k = 0; k < a.morph.n_active; k++) {
+        const float wk = a.morph.weight[k];
+        const float2 *d = (a.deltas + 3 * (size_t)a.morph.index[k] * a.n_vert) + 3 * i;  // (the target's base is scalar)
+        const float2 d0 = d[0], d1 = d[1], d2 = d[2];
+        px = px + wk * d0.x; py = py + wk * d0.y; pz = pz + wk * d1.x;
+        nx = nx + wk * d1.y; ny = ny + wk * d2.x; nz = nz + wk * d2.y;
+    }
+
+    float4 B0, B1, B2;
+    if (DQ) {
+        const float4 *q0 = a.pose + 2 * (size_t)b.x, *q1 = a.pose + 2 * (size_t)b.y, *q2 = a.pose + 2 * (size_t)b.z, *q3 = a.pose + 2 * (size_t)b.w;
+        const float4 r0 = q0[0], r1 = q1[0], r2 = q2[0], r3 = q3[0];
+        // Sign: a bone whose rotation lies in the other hemisphere from bone 0's enters with its weight negated (a NaN h keeps the weight)
+        const float4 s = make_float4(w.x, dot4(r0, r1) < 0.0f ? -w.y : w.y, dot4(r0, r2) < 0.0f ? -w.z : w.z, dot4(r0, r3) < 0.0f ? -w.w : w.w);
+        float4 R = blend_row(s, r0, r1, r2, r3);
+        float4 D = blend_row(s, q0[1], q1[1], q2[1], q3[1]);
+        // Normalise
+        const float l = __builtin_sqrtf(dot4(R, R));
+        const bool unit = l > 0.0f;
+        R = quot4(R, l, unit);
+        D = quot4(D, l, unit);
+        // Rotation
+        const float xx = R.x * R.x, yy = R.y * R.y, zz = R.z * R.z, xy = R.x * R.y, xz = R.x * R.z, yz = R.y * R.z, wx = R.w * R.x, wy = R.w * R.y, wz = R.w * R.z;
+        B0.x = 1.0f - 2.0f * (yy + zz); B0.y = 2.0f * (xy - wz); B0.z = 2.0f * (xz + wy);
+        B1.x = 2.0f * (xy + wz); B1.y = 1.0f - 2.0f * (xx + zz); B1.z = 2.0f * (yz - wx);
+        B2.x = 2.0f * (xz - wy); B2.y = 2.0f * (yz + wx); B2.z = 1.0f - 2.0f * (xx + yy);
+        // Translation
+        B0.w = 2.0f * (((R.w * D.x - D.w * R.x) + R.y * D.z) - R.z * D.y);
+        B1.w = 2.0f * (((R.w * D.y - D.w * R.y) + R.z * D.x) - R.x * D.z);
+        B2.w = 2.0f * (((R.w * D.z - D.w * R.z) + R.x * D.y) - R.y * D.x);
+    } else {
+        const float4 *m0 = a.pose + 3 * (size_t)b.x, *m1 = a.pose + 3 * (size_t)b.y, *m2 = a.pose + 3 * (size_t)b.z, *m3 = a.pose + 3 * (size_t)b.w;
+        B0 = blend_row(w, m0[0], m1[0], m2[0], m3[0]);
+        B1 = blend_row(w, m0[1], m1[1], m2[1], m3[1]);
+        B2 = blend_row(w, m0[2], m1[2], m2[2], m3[2]);
+    }
+    transform_store(B0, B1, B2, in, px, py, pz, nx, ny, nz, a.out + kVertexWords * i);
 }
 
 }  // namespace skin

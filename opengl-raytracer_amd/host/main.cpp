@@ -68,7 +68,8 @@ static void usage(const char *exe) {
                 "                          \"camera\": {...}}, ...]} -- shape: index into the scene file's \"scene\" array, m: row-major 3x4, unlisted shapes keep the identity,\n"
                 "                          \"camera\" optional with the scene file's keys.  Every step renders --frames frames and writes <out stem>_<step, 4 digits>.<ext> as a\n"
                 "                          still run would under the same --denoise* / --bloom / --tonemap (one device; not with --adaptive*, --reweight, --enable-volume,\n"
-                "                          --extensions or --save-every-frame)\n"
+                "                          --extensions or --save-every-frame).  Morph targets: a top-level \"targets\": [{\"shape\": i, \"file\": \"x.obj\"}, ...] and per step\n"
+                "                          \"weights\": [[target, w], ...] blend the shapes' vertices towards the targets' before the pose (glrtx_pose_morph)\n"
                 "      --carry-history     with --animate: keep the accumulator across the steps by motion-aware reprojection (glrtx_reproject_motion) instead of clearing\n"
                 "                          it; moments are tracked, so --denoise-variance composes (not with --denoise)\n", exe);
 }

@@ -65,7 +65,7 @@ void Scene::parse(const std::string &filename) {
 
     // shapes (scene.cpp:116-250)
     vertices.clear(); triangles.clear(); lights.clear(); materials.clear(); nodes.clear();
-    shapeFirstVertex_.clear(); animation_.clear();
+    shapeFirstVertex_.clear(); animation_.clear(); morphShape_.clear(); morphDeltas_.clear();
     const auto &shapes = json["scene"].array_items();
     for (size_t i = 0; i < shapes.size(); i++) {
         const Json &sh = shapes[i];
@@ -184,7 +184,36 @@ void Scene::parseAnimation(const std::string &filename) {
     if (!err.empty()) GLRT_FatalError("animation: %s", err.c_str());
     if (!json["steps"].is_array()) GLRT_FatalError("animation: no \"steps\" array");
     const size_t n_shapes = shapeFirstVertex_.size();
-    animation_.clear();
+    animation_.clear(); morphShape_.clear(); morphDeltas_.clear();
+    auto index_of = [](const Json &x, size_t n) { const double v = x.number_value(); return x.is_number() && v >= 0.0 && v < (double)n && v == std::floor(v); };
+    if (!json["targets"].is_null()) {  // morph targets: one OBJ a target, the deltas of its shape's vertices
+        if (!json["targets"].is_array()) GLRT_FatalError("animation: \"targets\" is not an array");
+        const auto &targets = json["targets"].array_items();
+        if (targets.size() > 64) GLRT_FatalError("animation: %zu morph targets (at most 64)", targets.size());
+        const size_t slash = filename.find_last_of("/\\");
+        const std::string dir = slash == std::string::npos ? "." : filename.substr(0, slash);
+        morphDeltas_.assign(targets.size() * vertices.size() * 6, 0.0f);
+        for (size_t t = 0; t < targets.size(); t++) {
+            if (!index_of(targets[t]["shape"], n_shapes))
+                GLRT_FatalError("animation target %zu: shape index %g is out of range (the scene has %zu shapes)", t, targets[t]["shape"].number_value(), n_shapes);
+            const size_t shape = (size_t)targets[t]["shape"].number_value();
+            const std::string file = dir + "/" + targets[t]["file"].string_value();
+            std::vector<Vertex> mesh;
+            std::string oerr;
+            if (!loadObj(file, mesh, oerr)) GLRT_FatalError("animation target %zu: failed to load *.obj file: %s (%s)", t, file.c_str(), oerr.c_str());
+            const size_t first = shapeFirstVertex(shape), count = shapeFirstVertex(shape + 1) - first;
+            if (mesh.size() != count)
+                GLRT_FatalError("animation target %zu: %s has %zu vertices, shape %zu has %zu", t, file.c_str(), mesh.size(), shape, count);
+            float *d = morphDeltas_.data() + (t * vertices.size() + first) * 6;
+            for (size_t v = 0; v < count; v++)
+                for (int k = 0; k < 3; k++) {
+                    d[6 * v + k] = mesh[v].pos[k] - vertices[first + v].pos[k];
+                    d[6 * v + 3 + k] = mesh[v].normal[k] - vertices[first + v].normal[k];
+                }
+            morphShape_.push_back(shape);
+        }
+    }
+    const size_t n_targets = morphShape_.size();
     const auto &steps = json["steps"].array_items();
     for (size_t s = 0; s < steps.size(); s++) {
         AnimationStep st;
@@ -201,6 +230,14 @@ void Scene::parseAnimation(const std::string &filename) {
                 GLRT_FatalError("animation step %zu: shape index %g is out of range (the scene has %zu shapes)", s, shape, n_shapes);
             for (size_t k = 0; k < 12; k++) st.matrices[12 * (size_t)shape + k] = (float)v[k + 1].number_value();
         }
+        st.weights.assign(n_targets, 0.0f);
+        for (const Json &entry : steps[s]["weights"].array_items()) {
+            const auto &v = entry.array_items();
+            if (v.size() != 2 || !v[1].is_number()) GLRT_FatalError("animation step %zu: a weight entry is a target index and a number", s);
+            if (!index_of(v[0], n_targets))
+                GLRT_FatalError("animation step %zu: target index %g is out of range (the file has %zu targets)", s, v[0].number_value(), n_targets);
+            st.weights[(size_t)v[0].number_value()] = (float)v[1].number_value();
+        }
         const Json &cam = steps[s]["camera"];
         if (!cam.is_null()) {
             if (cam["type"].string_value() != "perspective") GLRT_FatalError("animation step %zu: camera type \"%s\" (perspective)", s, cam["type"].string_value().c_str());
@@ -210,6 +247,7 @@ void Scene::parseAnimation(const std::string &filename) {
         animation_.push_back(std::move(st));
     }
     GLRT_Info("Animation: %zu steps, %zu shapes", animation_.size(), n_shapes);
+    if (n_targets) GLRT_Info("Animation: %zu morph targets", n_targets);
 }
 
 void Scene::setBuffers(int w, int h, const float view[16], const float proj[16], float aperture, float focal,
@@ -218,7 +256,7 @@ void Scene::setBuffers(int w, int h, const float view[16], const float proj[16],
     std::memcpy(viewM, view, sizeof viewM);
     std::memcpy(projM, proj, sizeof projM);
     vertices = std::move(v); triangles = std::move(t); materials = std::move(m); nodes = std::move(n);
-    shapeFirstVertex_.clear(); animation_.clear();
+    shapeFirstVertex_.clear(); animation_.clear(); morphShape_.clear(); morphDeltas_.clear();
     finalize();
 }
 
@@ -456,6 +494,30 @@ struct SceneAnimationProbe {
     }
 };
 }  // namespace glrt
+
+// Morph probe: parse the scene, then the animation file.  counts = {steps, targets, vertices}; target_shape (targets), deltas (targets x vertices x 6) and weights
+// (steps x targets) may each be NULL.
+namespace glrt {
+struct SceneMorphProbe {
+    static int run(const char *json, const char *animation, long long counts[3], int *target_shape, float *deltas, float *weights) {
+        Scene sc;
+        sc.parse(json);
+        sc.parseAnimation(animation);
+        const size_t n_steps = sc.animation_.size(), n_targets = sc.numMorphTargets();
+        counts[0] = (long long)n_steps; counts[1] = (long long)n_targets; counts[2] = (long long)sc.vertices.size();
+        if (target_shape)
+            for (size_t t = 0; t < n_targets; t++) target_shape[t] = (int)sc.morphShape_[t];
+        if (deltas && !sc.morphDeltas_.empty()) std::memcpy(deltas, sc.morphDeltas_.data(), sc.morphDeltas_.size() * sizeof(float));
+        if (weights && n_targets)
+            for (size_t s = 0; s < n_steps; s++) std::memcpy(weights + s * n_targets, sc.animation_[s].weights.data(), n_targets * sizeof(float));
+        return 0;
+    }
+};
+}  // namespace glrt
+
+extern "C" GLRT_API int glrt_scene_morph_probe(const char *json, const char *animation, long long counts[3], int *target_shape, float *deltas, float *weights) {
+    return glrt::SceneMorphProbe::run(json, animation, counts, target_shape, deltas, weights);
+}
 
 extern "C" GLRT_API int glrt_scene_animation_probe(const char *json, const char *animation, long long counts[2], long long *first_vertex, float *matrices,
                                                    int *has_camera, float *cameras) {

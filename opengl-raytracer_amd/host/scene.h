@@ -70,14 +70,23 @@ public:
     // list get the identity.  "camera" is optional and has the keys of the scene file's own "camera" block (it goes through the same code); without it the scene
     // file's camera holds for that step.  Numbers are parsed as doubles and cast to float.  A shape index out of range and an entry that is not 13 numbers are
     // FatalErrors.  Bone i of the rig Window uploads is shape i: loadObj yields three fresh vertices per triangle, so shapes never share a vertex.
+    //
+    // Morph targets (include/glrtx.h "Deforming").  The file may carry a top-level "targets": [{"shape": i, "file": "x.obj"}, ...] (at most 64; the path is
+    // resolved against the animation file's directory) and each step "weights": [[target, w], ...]; targets a step does not list get 0.  A target OBJ goes
+    // through loadObj and must give shape i's vertex count (otherwise a FatalError names both counts); its delta is target - rest for position and normal, one
+    // float subtraction each, and zero outside the shape.  A file without "targets" is what it was.
     struct AnimationStep {
         std::vector<float> matrices;  // numShapes() x 12
+        std::vector<float> weights;   // numMorphTargets()
         bool hasCamera = false;
         float viewM[16], projM[16], apertureRadius = 0.0f, focalLength = 0.0f;  // (with hasCamera)
     };
     void parseAnimation(const std::string &filename);
     const std::vector<AnimationStep> &animation() const { return animation_; }
     size_t numShapes() const { return shapeFirstVertex_.size(); }
+    size_t numMorphTargets() const { return morphShape_.size(); }
+    // the targets' deltas as glrtx_upload_morph_targets takes them: numMorphTargets() x vertex count x 6 floats {dpos, dnormal}
+    const std::vector<float> &morphDeltas() const { return morphDeltas_; }
     // the first vertex of entry i of the JSON "scene" array (an entry without geometry owns none: its range is empty); i == numShapes(): the vertex count
     size_t shapeFirstVertex(size_t i) const { return i < shapeFirstVertex_.size() ? shapeFirstVertex_[i] : vertices.size(); }
 
@@ -103,12 +112,15 @@ private:
     bool volume_ = false, hasVolume_ = false;
     std::vector<size_t> shapeFirstVertex_;  // per entry of the JSON "scene" array (parse() only: setBuffers knows no shapes)
     std::vector<AnimationStep> animation_;
+    std::vector<size_t> morphShape_;   // per morph target of the animation file: its shape
+    std::vector<float> morphDeltas_;
     VolumeGrid volDensity_, volTemperature_;  // volumeSpecs_[0]'s files (only with enableVolume(true)); only the first volume is rendered (window.cpp:271-286)
 
     friend class Window;
     friend struct SceneProbe;
     friend struct SceneVolumeProbe;
     friend struct SceneAnimationProbe;
+    friend struct SceneMorphProbe;
 };
 
 // OBJ triangles the way the reference's loader yields them (trimesh.cpp:113-191): three fresh

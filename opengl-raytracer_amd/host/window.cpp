@@ -275,6 +275,9 @@ void Window::animate() {
         if (glrtx_upload_rig(c0, &scene->vertices[0].pos[0], n_vert, bones.data(), weights.data(), (int)n_shapes) != GLRTX_OK)
             GLRT_FatalError("glrtx_upload_rig: %s", glrtx_last_error(c0));
     }
+    const int n_targets = (int)scene->numMorphTargets();  // the file's morph targets go up after the rig; with them a step is a glrtx_pose_morph
+    if (n_targets > 0 && glrtx_upload_morph_targets(c0, scene->morphDeltas().data(), n_targets, n_vert) != GLRTX_OK)
+        GLRT_FatalError("glrtx_upload_morph_targets: %s", glrtx_last_error(c0));
     float view0[16], proj0[16];
     std::memcpy(view0, scene->viewM, sizeof view0);
     std::memcpy(proj0, scene->projM, sizeof proj0);
@@ -291,7 +294,10 @@ void Window::animate() {
         scene->apertureRadius = st.hasCamera ? st.apertureRadius : aperture0;
         scene->focalLength = st.hasCamera ? st.focalLength : focal0;
         auto t0 = std::chrono::steady_clock::now();
-        if (glrtx_pose(c0, st.matrices.data(), (int)n_shapes) != GLRTX_OK) GLRT_FatalError("glrtx_pose: %s", glrtx_last_error(c0));
+        if (n_targets > 0) {
+            if (glrtx_pose_morph(c0, st.matrices.data(), (int)n_shapes, st.weights.data(), n_targets) != GLRTX_OK)
+                GLRT_FatalError("glrtx_pose_morph: %s", glrtx_last_error(c0));
+        } else if (glrtx_pose(c0, st.matrices.data(), (int)n_shapes) != GLRTX_OK) GLRT_FatalError("glrtx_pose: %s", glrtx_last_error(c0));
         glrtx_params p;
         frameParams(p);
         if (carryHistory_) {

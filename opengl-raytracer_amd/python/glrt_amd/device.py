@@ -173,7 +173,8 @@ EXPORTS = ["glrtx_abi_version", "glrtx_create", "glrtx_destroy", "glrtx_last_err
            "glrtx_debug_tonemap", "glrtx_debug_tonemap_burst",
            "glrtx_bloom", "glrtx_read_bloomed", "glrtx_tonemap_bloomed", "glrtx_resolve_bloomed_rgba8", "glrtx_debug_bloom", "glrtx_debug_bloom_burst",
            "glrtx_track_cascades", "glrtx_render_cascades", "glrtx_read_cascades", "glrtx_reweight", "glrtx_debug_fold_cascades", "glrtx_debug_reweight",
-           "glrtx_debug_reweight_burst", "glrtx_upload_rig", "glrtx_pose", "glrtx_debug_skin", "glrtx_debug_skin_burst"]
+           "glrtx_debug_reweight_burst", "glrtx_upload_rig", "glrtx_pose", "glrtx_debug_skin", "glrtx_debug_skin_burst",
+           "glrtx_upload_morph_targets", "glrtx_pose_morph", "glrtx_pose_dualquat", "glrtx_debug_deform", "glrtx_debug_deform_burst"]
 
 SCENE_BUFFERS = ("nodes", "cnodes", "nrms", "lights", "vine", "root")  # glrtx_debug_read_scene's `which`, in order (GLRTX_SCENE_*)
 
@@ -357,6 +358,11 @@ def lib():
             L.glrtx_pose.argtypes = [vp, fp, C.c_int]
             L.glrtx_debug_skin.argtypes = [fp, C.c_size_t, i32p, fp, fp, C.c_int, fp]
             L.glrtx_debug_skin_burst.argtypes = [vp, C.c_int, C.POINTER(C.c_float)]
+            L.glrtx_upload_morph_targets.argtypes = [vp, fp, C.c_int, C.c_size_t]
+            L.glrtx_pose_morph.argtypes = [vp, fp, C.c_int, fp, C.c_int]
+            L.glrtx_pose_dualquat.argtypes = [vp, fp, C.c_int, fp, C.c_int]
+            L.glrtx_debug_deform.argtypes = [fp, C.c_size_t, i32p, fp, fp, C.c_int, C.c_int, fp, fp, C.c_int, fp]
+            L.glrtx_debug_deform_burst.argtypes = [vp, C.c_int, C.POINTER(C.c_float)]
         except AttributeError:
             pass
         _lib = L
@@ -667,6 +673,20 @@ def debug_skin(rest, bones, weights, matrices):
     return out
 
 
+def debug_deform(rest, bones, weights, bone_data, mode=0, deltas=None, morph_weights=None):
+    """glrtx_debug_deform on the current device: the deform kernel alone -- the rig of debug_skin; bone_data (n_bones, 12) matrices (mode 0) or (n_bones, 8) dual
+    quaternions (mode 1); deltas (n_targets, n, 6) float32 and morph_weights (n_targets,) float32, or neither.  Returns the deformed vertices (n, 15) float32."""
+    from .host import deform_arrays
+    L = lib()
+    r, b, w, m, d, mw = deform_arrays("debug_deform", rest, bones, weights, bone_data, mode, deltas, morph_weights)
+    out = np.zeros_like(r)
+    rc = L.glrtx_debug_deform(_fp(r), r.shape[0], b.ctypes.data_as(C.POINTER(C.c_int32)), _fp(w), _fp(m), m.shape[0], int(mode),
+                              _fp(d) if mw.size else None, _fp(mw) if mw.size else None, mw.size, _fp(out))
+    if rc != 0:
+        raise GlrtxError(rc, L.glrtx_last_error(None).decode())
+    return out
+
+
 def _host_vertices(v):
     """A numpy vertex array for glrtx_update_vertices: float32, shape (n, 15) or flat (or the scene's (n * 5, 3) texels).  Returns (array, n)."""
     a = np.asarray(v)
@@ -742,6 +762,7 @@ class Device:
         if rc != 0:
             raise GlrtxError(rc, self.L.glrtx_last_error(None).decode())
         self.device_id = device_id
+        self._rig_vertices = 0  # of the last upload_rig (upload_morph_targets names it when it drops the targets)
 
     def close(self):
         if self.h:
@@ -782,6 +803,7 @@ class Device:
         from .host import rig_arrays
         r, b, w = rig_arrays("upload_rig", rest, bones, weights)
         self._ck(self.L.glrtx_upload_rig(self.h, _fp(r), r.shape[0], b.ctypes.data_as(C.POINTER(C.c_int32)), _fp(w), int(n_bones)))
+        self._rig_vertices = r.shape[0]
 
     def pose(self, matrices):
         """glrtx_pose: matrices (n_bones, 12) float32, row-major 3x4 -- skins the rest pose on the device and refits, as update_vertices of the skinned
@@ -790,6 +812,43 @@ class Device:
         if m.size % 12:
             raise ValueError(f"pose: matrices must be (n_bones, 12) or (n_bones, 3, 4), got {m.shape}")
         self._ck(self.L.glrtx_pose(self.h, _fp(m), m.size // 12))
+
+    def upload_morph_targets(self, deltas):
+        """glrtx_upload_morph_targets: deltas (n_targets, n_vert, 6) float32 {dpos, dnormal} for the uploaded rig; None or an empty array drops the targets."""
+        d = np.zeros((0, 0, 6), np.float32) if deltas is None else _f32(deltas)
+        if d.ndim != 3 or d.shape[2] != 6:
+            raise ValueError(f"upload_morph_targets: deltas must be (n_targets, n_vert, 6), got {d.shape}")
+        if d.shape[0] == 0:  # dropping: the call still names the rig's vertex count
+            self._ck(self.L.glrtx_upload_morph_targets(self.h, None, 0, self._rig_vertices))
+        else:
+            self._ck(self.L.glrtx_upload_morph_targets(self.h, _fp(d), d.shape[0], d.shape[1]))
+
+    @staticmethod
+    def _morph_weights(w):
+        mw = np.zeros(0, np.float32) if w is None else _f32(w).reshape(-1)
+        return (_fp(mw) if mw.size else None), mw.size, mw
+
+    def pose_morph(self, matrices, morph_weights=None):
+        """glrtx_pose_morph: pose() with one weight a morph target of the rig (None: the rig has none)."""
+        m = _f32(matrices)
+        if m.size % 12:
+            raise ValueError(f"pose_morph: matrices must be (n_bones, 12) or (n_bones, 3, 4), got {m.shape}")
+        p, n, keep = self._morph_weights(morph_weights)
+        self._ck(self.L.glrtx_pose_morph(self.h, _fp(m), m.size // 12, p, n))
+
+    def pose_dualquat(self, dualquats, morph_weights=None):
+        """glrtx_pose_dualquat: dualquats (n_bones, 8) float32 {r.xyzw, d.xyzw} (glrt_amd.rig.dualquat), and the morph weights as for pose_morph."""
+        q = _f32(dualquats)
+        if q.size % 8:
+            raise ValueError(f"pose_dualquat: dual quaternions must be (n_bones, 8), got {q.shape}")
+        p, n, keep = self._morph_weights(morph_weights)
+        self._ck(self.L.glrtx_pose_dualquat(self.h, _fp(q), q.size // 8, p, n))
+
+    def deform_burst_ms(self, reps=20) -> float:
+        """glrtx_debug_deform_burst: device ms of one launch of the deform kernel (the last pose_morph / pose_dualquat again), from `reps` back to back."""
+        ms = C.c_float(0)
+        self._ck(self.L.glrtx_debug_deform_burst(self.h, int(reps), C.byref(ms)))
+        return float(ms.value)
 
     def skin_burst_ms(self, reps=20) -> float:
         """glrtx_debug_skin_burst: device ms of one launch of the skinning kernel (the rig with the last pose's matrices), from `reps` launches back to back."""

@@ -57,6 +57,9 @@ def lib():
         L.glrt_fold_cascades.argtypes = [fp, fp, fp, C.c_int, C.c_int, C.c_int, C.c_float]
         L.glrt_reweight.argtypes = [fp, C.c_int, C.c_int, C.c_float, fp]
         L.glrt_skin_vertices.argtypes = [fp, C.c_size_t, C.POINTER(C.c_int32), fp, fp, C.c_int, fp]
+        L.glrt_deform_vertices.argtypes = [fp, C.c_size_t, C.POINTER(C.c_int32), fp, fp, C.c_int, C.c_int, fp, fp, C.c_int, fp]
+        L.glrt_dualquat_from_matrix.argtypes = [fp, fp]
+        L.glrt_dualquat_from_matrix.restype = None
         L.glrt_look_at.argtypes = [fp, fp, fp, fp]
         L.glrt_perspective.argtypes = [C.c_float, C.c_float, C.c_float, C.c_float, fp]
         L.glrt_mat4_mul.argtypes = [fp, fp, fp]
@@ -415,6 +418,41 @@ def skin_vertices(rest, bones, weights, matrices):
     rc = lib().glrt_skin_vertices(_fp(r), r.shape[0], b.ctypes.data_as(C.POINTER(C.c_int32)), _fp(w), _fp(m), m.shape[0], _fp(out))
     if rc != 0:
         raise RuntimeError(f"glrt_skin_vertices failed: {rc}")
+    return out
+
+
+def deform_arrays(name, rest, bones, weights, bone_data, mode, deltas, morph_weights):
+    """rig_arrays plus the bone data of `mode` -- (n_bones, 12) matrices or (n_bones, 8) dual quaternions --, the deltas (n_targets, n, 6) and the morph weights
+    (n_targets,), both empty when there are no targets.  Bits are kept."""
+    r, b, w = rig_arrays(name, rest, bones, weights)
+    per = 8 if mode else 12
+    m = _f32(bone_data)
+    if m.size % per or m.size == 0:
+        raise ValueError(f"{name}: mode {mode} takes (n_bones, {per}) bone data, got {m.shape}")
+    mw = np.zeros(0, np.float32) if morph_weights is None else _f32(morph_weights).reshape(-1)
+    d = np.zeros((0, r.shape[0], 6), np.float32) if deltas is None else _f32(deltas)
+    if d.shape != (mw.size, r.shape[0], 6):
+        raise ValueError(f"{name}: deltas {d.shape}, expected ({mw.size}, {r.shape[0]}, 6) for {mw.size} morph weights")
+    return r, b, w, m.reshape(-1, per), d, mw
+
+
+def deform_vertices(rest, bones, weights, bone_data, mode=0, deltas=None, morph_weights=None):
+    """glrt_deform_vertices: the CPU statement of Device.pose_morph / Device.pose_dualquat / device.debug_deform (include/glrtx.h "Deforming").  mode 0: bone_data
+    is (n_bones, 12) matrices; mode 1: (n_bones, 8) dual quaternions.  Returns the deformed vertices (n, 15) float32."""
+    r, b, w, m, d, mw = deform_arrays("deform_vertices", rest, bones, weights, bone_data, mode, deltas, morph_weights)
+    out = np.zeros_like(r)
+    rc = lib().glrt_deform_vertices(_fp(r), r.shape[0], b.ctypes.data_as(C.POINTER(C.c_int32)), _fp(w), _fp(m), m.shape[0], int(mode),
+                                    _fp(d) if mw.size else None, _fp(mw) if mw.size else None, mw.size, _fp(out))
+    if rc != 0:
+        raise RuntimeError(f"glrt_deform_vertices failed: {rc}")
+    return out
+
+
+def dualquat_from_matrix(m):
+    """glrt_dualquat_from_matrix: the eight floats {r.xyzw, d.xyzw} of one rigid 3x4 matrix (12 floats, row-major)."""
+    a = _f32(m).reshape(12)
+    out = np.zeros(8, np.float32)
+    lib().glrt_dualquat_from_matrix(_fp(a), _fp(out))
     return out
 
 

@@ -1,4 +1,5 @@
-"""Rigs for Device.upload_rig / host.skin_vertices (include/glrtx.h "Posing"): four bone indices and four weights a vertex."""
+"""Rigs for Device.upload_rig / host.skin_vertices (include/glrtx.h "Posing"): four bone indices and four weights a vertex; and dual-quaternion poses for
+Device.pose_dualquat / host.deform_vertices (include/glrtx.h "Deforming")."""
 from __future__ import annotations
 
 import numpy as np
@@ -21,3 +22,21 @@ def rigid(object_of_vertex):
 def identity_pose(n_bones):
     """n_bones identity matrices (n_bones, 12) float32."""
     return np.tile(IDENTITY, (int(n_bones), 1))
+
+
+IDENTITY_DUALQUAT = np.array([0, 0, 0, 1, 0, 0, 0, 0], np.float32)  # {r.x, r.y, r.z, r.w, d.x, d.y, d.z, d.w}
+
+
+def dualquat(matrices):
+    """The dual-quaternion pose (n_bones, 8) float32 of rigid 3x4 matrices (n_bones, 12) or (n_bones, 3, 4): glrt_dualquat_from_matrix a bone (the rotation is
+    taken as orthonormal, r.w >= 0)."""
+    from .host import dualquat_from_matrix
+    m = np.ascontiguousarray(matrices, np.float32)
+    if m.size % 12 or m.size == 0:
+        raise ValueError(f"dualquat: matrices must be (n_bones, 12) or (n_bones, 3, 4), got {m.shape}")
+    return np.stack([dualquat_from_matrix(row) for row in m.reshape(-1, 12)])
+
+
+def identity_dualquats(n_bones):
+    """n_bones identity dual quaternions (n_bones, 8) float32."""
+    return np.tile(IDENTITY_DUALQUAT, (int(n_bones), 1))
