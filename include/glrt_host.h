@@ -245,6 +245,18 @@ int glrt_skin_vertices(const float *rest_vert, size_t n_vert, const int32_t *bon
 #define GLRT_MAX_MORPH_TARGETS 64
 int glrt_deform_vertices(const float *rest_vert, size_t n_vert, const int32_t *bones4, const float *weights4, const float *bone_data, int n_bones, int mode,
                          const float *deltas, const float *morph_weights, int n_targets, float *vert_out);
+/* Sparse targets (include/glrtx.h "Deforming", SPARSE TARGETS: the wire form and the rules are there).  glrt_deform_vertices_sparse is glrt_deform_vertices over
+ * a sparse set -- offsets[n_targets + 1], vertex[nnz], deltas[nnz x 6], n_targets <= GLRT_MAX_SPARSE_MORPH_TARGETS --, bit for bit the device's
+ * deform_sparse_kernel; it runs under FTZ | DAZ and validates exactly as glrtx_upload_morph_targets_sparse does.  GLRT_HOST_EINVAL: what glrt_deform_vertices
+ * refuses about the rig, the mode and the morph weights, n_targets outside 0..1024, a NULL array with entries to read (n_targets == 0 needs no array; nnz == 0
+ * needs no vertex and no deltas), offsets[0] != 0, decreasing offsets, nnz >= 2^31, an index >= n_vert, indices not strictly ascending inside a target.
+ * glrt_morph_sparsify makes a sparse set from dense deltas (n_targets x n_vert x 6, n_targets <= 1024 here): entry (k, v) is kept iff some component of its six
+ * floats has a non-zero exponent field (a normal number, an Inf or a NaN).  It always fills offsets[n_targets + 1]; with vertex_out == NULL it only counts, so a
+ * caller calls it twice: once for offsets[n_targets] = nnz, once with vertex_out[nnz] and deltas_out[nnz x 6]. */
+#define GLRT_MAX_SPARSE_MORPH_TARGETS 1024
+int glrt_deform_vertices_sparse(const float *rest_vert, size_t n_vert, const int32_t *bones4, const float *weights4, const float *bone_data, int n_bones, int mode,
+                                const uint64_t *offsets, const uint32_t *vertex, const float *deltas, const float *morph_weights, int n_targets, float *vert_out);
+int glrt_morph_sparsify(const float *dense_deltas, int n_targets, size_t n_vert, uint64_t *offsets, uint32_t *vertex_out, float *deltas_out);
 /* The dual quaternion {r.x, r.y, r.z, r.w, d.x, d.y, d.z, d.w} of a rigid 3x4 matrix (row-major; the rotation is taken as orthonormal): computed in double and
  * rounded once, with the sign that makes r.w >= 0.  d = 1/2 (t, 0) * r. */
 void glrt_dualquat_from_matrix(const float m[12], float dq[8]);

@@ -958,7 +958,7 @@ int glrtx_debug_skin_burst(glrtx_ctx *ctx, int reps, float *ms_per_launch);
 /* ---- Deforming: morph targets and dual-quaternion skinning on the device, in the same place as Posing (no reference counterpart; off unless called: no other
  * call's behaviour changes).  Two things bones of matrices cannot say: a shape that is no bone's -- a face, a cloth or fluid cache, an OBJ sequence: blend
  * shapes --, and a twist that keeps its volume (linear blending takes a joint turned by 180 degrees between two bones to radius 0 at its mid ring).  One pass
- * (csrc/skin.hip.h: deform_kernel) in front of the refit does both; everything behind it sees a vertex update, as after glrtx_pose.
+ * (csrc/skin.hip.h: deform_kernel, deform_sparse_kernel) in front of the refit does both; everything behind it sees a vertex update, as after glrtx_pose.
  *
  * Arithmetic.  The rules are Posing's: one correctly rounded fp32 operation at a time, unfused, in the order written; denormals are zeros of their sign into
  * and out of every operation; a stored NaN is 0x7FC00000; dot(a, v) = (a2 v.z + a1 v.y) + a0 v.x; blend(w, m) = ((w0 m0 + w1 m1) + w2 m2) + w3 m3.
@@ -997,16 +997,53 @@ int glrtx_debug_skin_burst(glrtx_ctx *ctx, int reps, float *ms_per_launch);
  *   glrtx_debug_deform  the kernel alone on host arrays on the current HIP device, no context.  mode 0: bone_data is n_bones x 12 (matrices), 1: n_bones x 8
  *                     (dual quaternions).  Refuses what glrt_deform_vertices refuses (bone weights, bone data and deltas are not checked; morph weights are,
  *                     because the host decides from them which targets the kernel reads).
- *   glrtx_debug_deform_burst  device time of the kernel by itself, as glrtx_debug_skin_burst: the last glrtx_pose_morph / glrtx_pose_dualquat launch again.
- *                     GLRTX_EINVAL before a first one.
+ *   glrtx_debug_deform_burst  device time of the kernel by itself, as glrtx_debug_skin_burst: the last glrtx_pose_morph / glrtx_pose_dualquat launch again,
+ *                     whichever kernel that was (dense or sparse).  GLRTX_EINVAL before a first one.
+ *
+ * SPARSE TARGETS.  A rig carries EITHER a dense set (above, <= GLRTX_MAX_MORPH_TARGETS = 64 targets) OR a sparse set of n_targets <=
+ * GLRTX_MAX_SPARSE_MORPH_TARGETS = 1024 targets, each of which lists only the vertices it moves.  The set is handed in by target, as glTF's sparse accessors do:
+ *   offsets[n_targets + 1]  uint64, offsets[0] = 0, non-decreasing; nnz = offsets[n_targets] < 2^31; target k's entries are [offsets[k], offsets[k + 1])
+ *   vertex[nnz]             uint32, strictly ascending inside a target, each < n_vert
+ *   deltas[nnz x 6]         float {dpos, dnormal}, not checked (as dense deltas are not)
+ * The rules are the dense form's, in Posing's arithmetic:
+ *   Active    as above: a target is active iff |w| >= 2^-126.
+ *   Morph     per vertex, over the entries that list this vertex and belong to an active target, in ascending target index:  p = p + w_k * dpos  and
+ *             n = n + w_k * dnormal  -- a rounded product, then a rounded sum --, starting from the rest position and normal.  A vertex that no active target
+ *             lists keeps its rest p and n untouched: no + 0 is formed.
+ *   Inactive entries  an entry of an inactive target never enters the arithmetic: a NaN or Inf under a zero weight changes nothing.  It MAY BE LOADED -- the one
+ *             place this wording is weaker than the dense form's "not read at all": the entries of a vertex lie side by side whatever target they belong to.
+ *   Then the skinning stage, matrices or dual quaternions, unchanged.  With no active target the result is Posing's, bit for bit.
+ * Two relations to the dense form:
+ *   1. A sparse set in which every target lists every vertex performs the dense form's operation sequence: it equals the dense form bit for bit on any data.
+ *   2. Dropping an entry whose six floats are all zeros after the flush (exponent field 0) changes the result at most in the sign of a zero, and changes
+ *      nothing at all when no rest position or normal component is a negative zero or a negative denormal (precondition).  A rounded sum is -0 only if both
+ *      operands are -0, so under the precondition p never becomes -0 and p + (+-0) = p.  Without it the two forms are NOT equal: -0 + (+0) is +0.
+ * The CPU statement is glrt_deform_vertices_sparse (include/glrt_host.h), bit for bit; glrt_morph_sparsify there drops exactly the entries of relation 2.
+ *
+ *   glrtx_upload_morph_targets_sparse  transposes the set on the host into a vertex-major inverted index -- row[n_vert + 1] and 32-byte entries {target, dpos}
+ *                     {dnormal, 0}, ascending by target inside a row -- and keeps that on the device: 4 (n_vert + 1) + 32 nnz bytes.  Needs a rig with that
+ *                     n_vert.  GLRTX_EINVAL, nothing changed: no scene or no rig, another n_vert, n_targets outside 0..1024, a NULL array with entries to read
+ *                     (nnz == 0 with NULL vertex and deltas is a valid set; n_targets == 0 needs no array), offsets[0] != 0 or decreasing offsets, nnz >=
+ *                     2^31, an index >= n_vert, indices not strictly ascending inside a target; the message names the target and the entry.  Uploading either
+ *                     kind of set replaces the other; n_targets == 0 through either call drops whatever is there; glrtx_upload_rig and glrtx_upload_scene
+ *                     forget the set; glrtx_update_vertices / _device keep it.
+ *   glrtx_pose_morph, glrtx_pose_dualquat  work with whichever set the rig holds: n_targets up to 1024 with a sparse set, and the rig's count as before.  The
+ *                     weight table (n_targets floats, +0 for an inactive target) goes up per pose beside the bone data.  With no active weight, or nnz == 0,
+ *                     the dense kernel runs with no active target and reads no entry at all.
+ *   glrtx_debug_deform_sparse  the sparse kernel alone on host arrays on the current HIP device, no context.  Refuses what glrt_deform_vertices_sparse refuses,
+ *                     before it touches a device.
  * Groups: no call. */
 #define GLRTX_MAX_MORPH_TARGETS 64
+#define GLRTX_MAX_SPARSE_MORPH_TARGETS 1024
 int glrtx_upload_morph_targets(glrtx_ctx *ctx, const float *deltas, int n_targets, size_t n_vert);
 int glrtx_pose_morph(glrtx_ctx *ctx, const float *matrices, int n_bones, const float *morph_weights, int n_targets);
 int glrtx_pose_dualquat(glrtx_ctx *ctx, const float *dualquats, int n_bones, const float *morph_weights, int n_targets);
 int glrtx_debug_deform(const float *rest, size_t n_vert, const int32_t *bones4, const float *weights4, const float *bone_data, int n_bones, int mode,
                        const float *deltas, const float *morph_weights, int n_targets, float *vert_out);
 int glrtx_debug_deform_burst(glrtx_ctx *ctx, int reps, float *ms_per_launch);
+int glrtx_upload_morph_targets_sparse(glrtx_ctx *ctx, const uint64_t *offsets, const uint32_t *vertex, const float *deltas, int n_targets, size_t n_vert);
+int glrtx_debug_deform_sparse(const float *rest, size_t n_vert, const int32_t *bones4, const float *weights4, const float *bone_data, int n_bones, int mode,
+                              const uint64_t *offsets, const uint32_t *vertex, const float *deltas, const float *morph_weights, int n_targets, float *vert_out);
 
 /* ---- Groups: the same device layer on several GPUs of one node, behind one handle and one host thread.
  * No reference counterpart (the reference is single-GPU); SURVEY.md 8(b) sketches glrtx_create(ctx**, device_ids, n) with a

@@ -33,6 +33,7 @@
 #include "tonemap.hip.h"
 #include "bloom.hip.h"
 #include "../host/reproject_setup.h"
+#include "../host/morph_sparse.h"
 static_assert(glrtx::lbvh::kRotationPasses == GLRT_LBVH_ROTATION_PASSES, "device and CPU LBVH statements must run the same rotation sweeps");
 static_assert(glrtx::lbvh::kRebuildLeaves == GLRT_LBVH_REBUILD_LEAVES, "device and CPU LBVH statements must rebuild the same subtrees");
 
@@ -175,10 +176,16 @@ struct glrtx_ctx {
     // the last glrtx_pose.  n_bones == 0: no rig.
     // Deforming (glrtx_upload_morph_targets, glrtx_pose_morph, glrtx_pose_dualquat): the rig's morph targets as uploaded (n_targets x n_vert x 24 bytes; n_targets
     // == 0: none), the dual quaternions of the last glrtx_pose_dualquat, and the arguments of the last deform launch for the timing hook (mode -1: none yet).
+    // A rig holds a dense set (morph) or a sparse one (glrtx_upload_morph_targets_sparse: the inverted index srow / sent of nnz entries, and the weight table
+    // swt of the last pose, whose host copy is wtab), never both; last_sparse: the last deform launch was deform_sparse_kernel with the arguments in sdeform.
     struct Rig {
-        DevBuf rest, rig, pose, dq, morph;
+        DevBuf rest, rig, pose, dq, morph, srow, sent, swt;
         int n_bones = 0, n_targets = 0, deform_mode = -1;
+        bool sparse = false, last_sparse = false;
+        size_t nnz = 0;
         skin::DeformArgs deform{};
+        skin::SparseArgs sdeform{};
+        std::vector<float> wtab;
     } sk;
 
     // Presentation (glrtx_present_enable): frame seq of the ring goes to image seq % ring -- device image (written by the presenting pass on the context's stream),
@@ -299,6 +306,15 @@ void dev_free(DevBuf &b) {
 }
 
 void Plane::drop() { dev_free(buf); at = Shape{}; }
+
+// The rig's morph targets, dense or sparse, are forgotten (the stream is idle: every caller has synchronised it or runs behind a blocking call)
+void morph_drop(glrtx_ctx *c) {
+    dev_free(c->sk.morph); dev_free(c->sk.srow); dev_free(c->sk.sent);
+    c->sk.n_targets = 0; c->sk.deform_mode = -1;
+    c->sk.sparse = c->sk.last_sparse = false;
+    c->sk.nnz = 0;
+}
+
 Shape accum_shape(const glrtx_ctx *c) { return {c->width, c->pitch_bytes, c->owned_rows}; }
 Shape packed_shape(const glrtx_ctx *c) { return {c->width, (size_t)c->width * sizeof(float4), c->owned_rows}; }
 
@@ -2167,6 +2183,7 @@ void glrtx_destroy(glrtx_ctx *c) {
     dev_free(c->bvhVert); dev_free(c->bvhTri); dev_free(c->bvhNodes);
     dev_free(c->rf.ints); dev_free(c->rf.keys); dev_free(c->rf.vert);
     dev_free(c->sk.rest); dev_free(c->sk.rig); dev_free(c->sk.pose); dev_free(c->sk.dq); dev_free(c->sk.morph);
+    dev_free(c->sk.srow); dev_free(c->sk.sent); dev_free(c->sk.swt);
     dev_free(c->qwire); dev_free(c->qcounter); dev_free(c->qrays); dev_free(c->qhits);
     if (c->rf.slot_ev) (void)hipEventDestroy(c->rf.slot_ev);
     if (c->bvhWs.p) { (void)hipFree(c->bvhWs.p); c->bvhWs.p = nullptr; c->bvhWs.bytes = 0; }
@@ -2254,8 +2271,8 @@ int glrtx_upload_scene(glrtx_ctx *c, const float *vert, size_t n_vert, const flo
     dev_free(c->mtPos); dev_free(c->mtNrm);  // (glrtx_track_motion: the previous geometry was another scene's; the stream is idle)
     c->mt_geom = glrtx_ctx::kMtNone;
     dev_free(c->sk.rest); dev_free(c->sk.rig); dev_free(c->sk.pose);  // (glrtx_upload_rig: the rig was another scene's)
-    dev_free(c->sk.dq); dev_free(c->sk.morph);
-    c->sk.n_targets = 0; c->sk.deform_mode = -1;
+    dev_free(c->sk.dq);
+    morph_drop(c);
     c->sk.n_bones = 0;
     c->st.stack_entries = stack_need;
     c->st.lds_bytes = lds_bytes_for(sc);
@@ -2396,8 +2413,7 @@ int glrtx_upload_rig(glrtx_ctx *c, const float *rest_vert, size_t n_vert, const 
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));  // (a glrtx_pose's kernel has run: glrtx_pose blocks; this orders the frees behind anything else on the stream)
     c->sk.n_bones = 0;  // (until all three buffers are in place)
-    dev_free(c->sk.morph);  // the morph targets were the previous rig's (glrtx_upload_morph_targets)
-    c->sk.n_targets = 0; c->sk.deform_mode = -1;
+    morph_drop(c);  // the morph targets were the previous rig's (glrtx_upload_morph_targets, glrtx_upload_morph_targets_sparse)
     if (int rc = dev_upload(c, c->sk.rest, rest_vert, n_vert * skin::kVertexWords * sizeof(float))) return rc;
     if (int rc = dev_upload(c, c->sk.rig, rig.data(), rig.size() * sizeof(uint4))) return rc;
     if (int rc = ensure(c, c->sk.pose, (size_t)n_bones * 12 * sizeof(float))) return rc;
@@ -2476,8 +2492,8 @@ void morph_list(skin::Morph &m, const float *weights, int n_targets) {
 }
 
 // What the pose calls and the debug hook refuse alike about the morph weights
-int morph_check(glrtx_ctx *c, const float *morph_weights, int n_targets, const char *fn) {
-    if (n_targets < 0 || n_targets > GLRTX_MAX_MORPH_TARGETS) return fail(c, GLRTX_EINVAL, "%s: %d morph targets (0 .. %d)", fn, n_targets, GLRTX_MAX_MORPH_TARGETS);
+int morph_check(glrtx_ctx *c, const float *morph_weights, int n_targets, const char *fn, int cap = GLRTX_MAX_MORPH_TARGETS) {
+    if (n_targets < 0 || n_targets > cap) return fail(c, GLRTX_EINVAL, "%s: %d morph targets (0 .. %d)", fn, n_targets, cap);
     if (n_targets > 0 && !morph_weights) return fail(c, GLRTX_EINVAL, "%s: NULL morph weights", fn);
     if (!all_finite(morph_weights, (size_t)n_targets)) return fail(c, GLRTX_EINVAL, "%s: a morph weight is not finite", fn);
     return GLRTX_OK;
@@ -2490,6 +2506,57 @@ void deform_launch(const skin::DeformArgs &a, int mode, hipStream_t stream) {
     else hipLaunchKernelGGL(skin::deform_kernel<false>, grid, block, 0, stream, a);
 }
 
+// ---- sparse targets (glrtx_upload_morph_targets_sparse, glrtx_debug_deform_sparse; skin.hip.h: deform_sparse_kernel)
+static_assert(skin::kMaxSparseTargets == GLRTX_MAX_SPARSE_MORPH_TARGETS && glrt_detail::kMaxSparseTargets == GLRTX_MAX_SPARSE_MORPH_TARGETS,
+              "skin.hip.h, host/morph_sparse.h and glrtx.h disagree");
+
+void deform_sparse_launch(const skin::SparseArgs &a, int mode, hipStream_t stream) {
+    if (a.n_vert == 0) return;
+    const dim3 grid((unsigned)((a.n_vert + skin::kBlock - 1) / skin::kBlock)), block(skin::kBlock);
+    if (mode) hipLaunchKernelGGL(skin::deform_sparse_kernel<true>, grid, block, 0, stream, a);
+    else hipLaunchKernelGGL(skin::deform_sparse_kernel<false>, grid, block, 0, stream, a);
+}
+
+// What the upload, the debug hook and the CPU statement refuse alike about a set in its wire form (host/morph_sparse.h)
+int sparse_check(glrtx_ctx *c, const uint64_t *offsets, const uint32_t *vertex, const float *deltas, int n_targets, size_t n_vert, const char *fn) {
+    glrt_detail::SparseFault f;
+    if (glrt_detail::morph_sparse_check(offsets, vertex, deltas, n_targets, n_vert, f)) return GLRTX_OK;
+    char why[256];
+    glrt_detail::morph_sparse_message(f, n_targets, why, sizeof why);
+    return fail(c, GLRTX_EINVAL, "%s: %s", fn, why);
+}
+
+// The vertex-major inverted index of a checked set: row[n_vert + 1], and the entries in row order.  A stable counting sort over the target-major input: the
+// targets are walked in ascending index, so the entries of a row come out ascending by target.
+void sparse_index(const uint64_t *offsets, const uint32_t *vertex, const float *deltas, int n_targets, size_t n_vert, std::vector<unsigned> &row,
+                  std::vector<float4> &entry) {
+    const size_t nnz = n_targets > 0 ? (size_t)offsets[n_targets] : 0;
+    row.assign(n_vert + 1, 0u);
+    for (size_t e = 0; e < nnz; e++) row[(size_t)vertex[e] + 1]++;
+    for (size_t i = 0; i < n_vert; i++) row[i + 1] += row[i];
+    entry.resize(2 * nnz);
+    std::vector<unsigned> at(row.begin(), row.end() - 1);
+    for (int k = 0; k < n_targets; k++)
+        for (uint64_t e = offsets[k]; e < offsets[k + 1]; e++) {
+            const float *d = deltas + 6 * e;
+            float4 *q = entry.data() + 2 * (size_t)at[vertex[e]]++;
+            q[0] = make_float4(__builtin_bit_cast(float, (unsigned)k), d[0], d[1], d[2]);
+            q[1] = make_float4(d[3], d[4], d[5], 0.0f);
+        }
+}
+
+// The pose's weight table: the weight of an active target, exact +0 of an inactive one.  Returns the number of active targets.
+int sparse_weights(std::vector<float> &tab, const float *weights, int n_targets) {
+    tab.assign((size_t)n_targets, 0.0f);
+    int n_active = 0;
+    for (int k = 0; k < n_targets; k++)
+        if (std::fabs(weights[k]) >= 1.17549435e-38f) {  // 2^-126
+            tab[(size_t)k] = weights[k];
+            n_active++;
+        }
+    return n_active;
+}
+
 // glrtx_pose_morph (mode 0: n_bones x 12 floats) and glrtx_pose_dualquat (mode 1: n_bones x 8 floats): glrtx_pose with the deform kernel in the skinning kernel's place
 int deform_pose(glrtx_ctx *c, const float *bone_data, int n_bones, const float *morph_weights, int n_targets, int mode, const char *fn) {
     if (!c) return GLRTX_EINVAL;
@@ -2497,7 +2564,7 @@ int deform_pose(glrtx_ctx *c, const float *bone_data, int n_bones, const float *
     if (n_bones != c->sk.n_bones) return fail(c, GLRTX_EINVAL, "%s: %d bones, the rig has %d", fn, n_bones, c->sk.n_bones);
     if (n_targets != c->sk.n_targets) return fail(c, GLRTX_EINVAL, "%s: %d morph weights, the rig has %d targets", fn, n_targets, c->sk.n_targets);
     if (!bone_data) return fail(c, GLRTX_EINVAL, "%s: NULL pose", fn);
-    if (int rc = morph_check(c, morph_weights, n_targets, fn)) return rc;
+    if (int rc = morph_check(c, morph_weights, n_targets, fn, c->sk.sparse ? GLRTX_MAX_SPARSE_MORPH_TARGETS : GLRTX_MAX_MORPH_TARGETS)) return rc;
     const size_t pose_bytes = (size_t)n_bones * (mode ? 8 : 12) * sizeof(float);
     if (!all_finite(bone_data, pose_bytes / sizeof(float))) return fail(c, GLRTX_EINVAL, "%s: a pose entry is not finite", fn);
     seal_feed(c);
@@ -2507,12 +2574,24 @@ int deform_pose(glrtx_ctx *c, const float *bone_data, int n_bones, const float *
     DevBuf &pose = mode ? c->sk.dq : c->sk.pose;
     if (int rc = ensure(c, pose, pose_bytes)) return rc;
     HIP_TRY(c, hipMemcpyAsync(pose.p, bone_data, pose_bytes, hipMemcpyHostToDevice, c->stream));
-    skin::DeformArgs &a = c->sk.deform;
-    a = skin::DeformArgs{(const unsigned *)c->sk.rest.p, (const uint4 *)c->sk.rig.p, (const float4 *)pose.p, (unsigned *)c->rf.vert.p, n_vert,
-                         (const float2 *)c->sk.morph.p, {}};
-    morph_list(a.morph, morph_weights, n_targets);
+    // A sparse set with an active weight and an entry goes through deform_sparse_kernel; without either there is nothing to add, and deform_kernel with no
+    // active target reads no delta at all: Posing's bits
+    const bool sparse = c->sk.sparse && c->sk.nnz > 0 && sparse_weights(c->sk.wtab, morph_weights, n_targets) > 0;
+    if (sparse) {
+        if (int rc = ensure(c, c->sk.swt, (size_t)n_targets * sizeof(float))) return rc;
+        HIP_TRY(c, hipMemcpyAsync(c->sk.swt.p, c->sk.wtab.data(), (size_t)n_targets * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        c->sk.sdeform = skin::SparseArgs{(const unsigned *)c->sk.rest.p, (const uint4 *)c->sk.rig.p, (const float4 *)pose.p, (unsigned *)c->rf.vert.p, n_vert,
+                                         (const unsigned *)c->sk.srow.p, (const float4 *)c->sk.sent.p, (const float *)c->sk.swt.p, n_targets};
+        deform_sparse_launch(c->sk.sdeform, mode, c->stream);
+    } else {
+        skin::DeformArgs &a = c->sk.deform;
+        a = skin::DeformArgs{(const unsigned *)c->sk.rest.p, (const uint4 *)c->sk.rig.p, (const float4 *)pose.p, (unsigned *)c->rf.vert.p, n_vert,
+                             (const float2 *)c->sk.morph.p, {}};
+        if (!c->sk.sparse) morph_list(a.morph, morph_weights, n_targets);
+        deform_launch(a, mode, c->stream);
+    }
     c->sk.deform_mode = mode;
-    deform_launch(a, mode, c->stream);
+    c->sk.last_sparse = sparse;
     HIP_TRY(c, hipGetLastError());
     if (c->mt_on && c->mt_geom == glrtx_ctx::kMtCurrent)  // (glrtx_pose's path from here)
         if (int rc = motion_snapshot(c)) return rc;
@@ -2530,13 +2609,31 @@ int glrtx_upload_morph_targets(glrtx_ctx *c, const float *deltas, int n_targets,
     if (n_targets > 0 && n_vert > 0 && !deltas) return fail(c, GLRTX_EINVAL, "%s: NULL deltas", fn);
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));  // (as glrtx_upload_rig: the free is ordered behind anything on the stream)
-    c->sk.n_targets = 0; c->sk.deform_mode = -1;
-    if (n_targets == 0) {
-        dev_free(c->sk.morph);
-        return GLRTX_OK;
-    }
+    morph_drop(c);  // (either kind of set: an upload replaces whatever the rig holds)
+    if (n_targets == 0) return GLRTX_OK;
     if (int rc = dev_upload(c, c->sk.morph, deltas, (size_t)n_targets * n_vert * skin::kDeltaWords * sizeof(float))) return rc;
     c->sk.n_targets = n_targets;
+    return GLRTX_OK;
+}
+
+int glrtx_upload_morph_targets_sparse(glrtx_ctx *c, const uint64_t *offsets, const uint32_t *vertex, const float *deltas, int n_targets, size_t n_vert) {
+    const char *fn = "glrtx_upload_morph_targets_sparse";
+    if (!c) return GLRTX_EINVAL;
+    if (!c->have_scene || c->sk.n_bones == 0) return fail(c, GLRTX_EINVAL, "%s: no rig uploaded (glrtx_upload_rig)", fn);
+    if (n_vert != c->rf.n_vert) return fail(c, GLRTX_EINVAL, "%s: %zu vertices, the rig has %zu", fn, n_vert, c->rf.n_vert);
+    if (int rc = sparse_check(c, offsets, vertex, deltas, n_targets, n_vert, fn)) return rc;
+    std::vector<unsigned> row;
+    std::vector<float4> entry;
+    if (n_targets > 0) sparse_index(offsets, vertex, deltas, n_targets, n_vert, row, entry);
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));  // (as glrtx_upload_rig: the frees are ordered behind anything on the stream)
+    morph_drop(c);
+    if (n_targets == 0) return GLRTX_OK;
+    if (int rc = dev_upload(c, c->sk.srow, row.data(), row.size() * sizeof(unsigned))) return rc;
+    if (int rc = dev_upload(c, c->sk.sent, entry.data(), entry.size() * sizeof(float4))) return rc;
+    c->sk.n_targets = n_targets;
+    c->sk.sparse = true;
+    c->sk.nnz = entry.size() / 2;
     return GLRTX_OK;
 }
 
@@ -2577,6 +2674,43 @@ int glrtx_debug_deform(const float *rest, size_t n_vert, const int32_t *bones4, 
     return s.result(GLRTX_OK, fn);
 }
 
+int glrtx_debug_deform_sparse(const float *rest, size_t n_vert, const int32_t *bones4, const float *weights4, const float *bone_data, int n_bones, int mode,
+                              const uint64_t *offsets, const uint32_t *vertex, const float *deltas, const float *morph_weights, int n_targets, float *vert_out) {
+    const char *fn = "glrtx_debug_deform_sparse";
+    if (int rc = rig_check(nullptr, rest, n_vert, bones4, weights4, n_bones, fn)) return rc;
+    if (mode != 0 && mode != 1) return fail(nullptr, GLRTX_EINVAL, "%s: mode %d (0: matrices, 1: dual quaternions)", fn, mode);
+    if (int rc = sparse_check(nullptr, offsets, vertex, deltas, n_targets, n_vert, fn)) return rc;
+    if (int rc = morph_check(nullptr, morph_weights, n_targets, fn, GLRTX_MAX_SPARSE_MORPH_TARGETS)) return rc;
+    if (!bone_data || (n_vert > 0 && !vert_out)) return fail(nullptr, GLRTX_EINVAL, "%s: NULL buffer", fn);
+    if (n_vert == 0) return GLRTX_OK;
+    std::vector<uint4> rig;
+    rig_records(rig, n_vert, bones4, weights4);
+    std::vector<unsigned> row;
+    std::vector<float4> entry;
+    std::vector<float> tab;
+    sparse_index(offsets, vertex, deltas, n_targets, n_vert, row, entry);
+    sparse_weights(tab, morph_weights, n_targets);
+    const size_t bytes = n_vert * skin::kVertexWords * sizeof(float);
+    DebugScratch s;
+    skin::SparseArgs a{};
+    a.rest = s.alloc<unsigned>(bytes, rest);
+    a.rig = s.alloc<uint4>(rig.size() * sizeof(uint4), rig.data());
+    a.pose = s.alloc<float4>((size_t)n_bones * (mode ? 8 : 12) * sizeof(float), bone_data);
+    a.out = s.alloc<unsigned>(bytes);
+    a.n_vert = n_vert;
+    a.row = s.alloc<unsigned>(row.size() * sizeof(unsigned), row.data());
+    a.entry = s.alloc<float4>(std::max<size_t>(entry.size(), 2) * sizeof(float4), entry.empty() ? nullptr : entry.data());  // (the hook always runs the sparse kernel)
+    a.weight = s.alloc<float>(std::max<size_t>(tab.size(), 1) * sizeof(float), tab.empty() ? nullptr : tab.data());
+    a.n_targets = n_targets;
+    if (s.ok()) {
+        deform_sparse_launch(a, mode, 0);
+        s.e = hipGetLastError();
+    }
+    s.sync();
+    s.download(vert_out, a.out, bytes);
+    return s.result(GLRTX_OK, fn);
+}
+
 // Device time of the deform kernel by itself, as glrtx_debug_skin_burst: the last glrtx_pose_morph / glrtx_pose_dualquat launch again, into the context's vertex
 // buffer -- which holds exactly that already, unless another call has written it since.
 int glrtx_debug_deform_burst(glrtx_ctx *c, int reps, float *ms_per_launch) {
@@ -2586,7 +2720,11 @@ int glrtx_debug_deform_burst(glrtx_ctx *c, int reps, float *ms_per_launch) {
         return fail(c, GLRTX_EINVAL, "%s: no rig uploaded, or no glrtx_pose_morph / glrtx_pose_dualquat yet", fn);
     seal_feed(c);
     HIP_TRY(c, hipSetDevice(c->device));
-    return burst_time(c, reps, ms_per_launch, [&] { deform_launch(c->sk.deform, c->sk.deform_mode, c->stream); return GLRTX_OK; });
+    return burst_time(c, reps, ms_per_launch, [&] {
+        if (c->sk.last_sparse) deform_sparse_launch(c->sk.sdeform, c->sk.deform_mode, c->stream);  // (whichever kernel the last pose ran)
+        else deform_launch(c->sk.deform, c->sk.deform_mode, c->stream);
+        return GLRTX_OK;
+    });
 }
 
 namespace {

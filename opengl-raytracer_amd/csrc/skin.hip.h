@@ -22,6 +22,19 @@
 //       of one that is.  DQ = false: bones are skin_kernel's 48-byte matrices, 152 + 24 active bytes a vertex.  DQ = true: a bone is 32 bytes {r, d}, two
 //       16-byte loads a bone and lane, 136 + 24 active bytes a vertex; sign, blend, normalise, and the 3x4 matrix [L | t] of the blended dual quaternion.  Both
 //       end in the same tail (transform_store), which is skin_kernel's arithmetic from B on.
+//
+// Sparse targets (glrtx_upload_morph_targets_sparse; include/glrtx.h "Deforming", SPARSE TARGETS): a target lists only the vertices it moves, up to 1024 a rig.
+// host/deform.cpp (glrt_deform_vertices_sparse) and tests/deform_sparse_math.py state it again.
+//
+//   deform_sparse_kernel<DQ>  deform_kernel's shape: one thread per vertex, 256-thread workgroups, no atomics, no scratch.  The set arrives as a vertex-major
+//       inverted index built on the host: row[n_vert + 1], and the entries in row order, ascending by target inside a row -- each destination sums its own
+//       list in a fixed order (a gather), so nothing is shared between lanes and the result is reproducible bit for bit.  An entry is 32 bytes {target, dpos}
+//       {dnormal, 0}, two 16-byte loads; a lane reads row[i] and row[i + 1] (a wave: 260 contiguous bytes) and walks its row, a lane-dependent trip count.  The
+//       pose's weight table (n_targets floats, exact +0 for an inactive target) is staged once a workgroup in LDS, 4 KB, and looked up per lane by the
+//       entry's target; an entry under a zero weight is skipped without touching p or n.  One barrier behind the staging: the body is guarded by i < n_vert and
+//       NO thread returns in front of the barrier.  The blend and the dual-quaternion block are deform_kernel's text repeated (the existing kernels are not
+//       edited: moving a loop into a shared body has renumbered a kernel here before); the tail is transform_store, shared.  152 + 4 bytes a vertex plus 32 an
+//       entry (DQ: 136 + 4).
 #pragma once
 #include "denoise.hip.h"
 
@@ -207,6 +220,77 @@ __global__ __launch_bounds__(kBlock) void deform_kernel(const DeformArgs a) {
         B2 = blend_row(w, m0[2], m1[2], m2[2], m3[2]);
     }
     transform_store(B0, B1, B2, in, px, py, pz, nx, ny, nz, a.out + kVertexWords * i);
+}
+
+// ---- Sparse targets
+constexpr int kMaxSparseTargets = 1024;  // GLRTX_MAX_SPARSE_MORPH_TARGETS
+
+struct SparseArgs {
+    const unsigned *rest;  // as Args
+    const uint4 *rig;
+    const float4 *pose;    // as DeformArgs
+    unsigned *out;
+    size_t n_vert;
+    const unsigned *row;   // n_vert + 1: vertex i's entries are [row[i], row[i + 1])
+    const float4 *entry;   // nnz x 2: {target (as bits), dpos.x, dpos.y, dpos.z} {dnormal.x, dnormal.y, dnormal.z, 0}, ascending by target inside a row
+    const float *weight;   // n_targets: the pose's weights, +0 for an inactive target
+    int n_targets;         // <= kMaxSparseTargets; every entry's target is below it (the host built the index)
+};
+
+template <bool DQ>
+__global__ __launch_bounds__(kBlock) void deform_sparse_kernel(const SparseArgs a) {
+    __shared__ float wt[kMaxSparseTargets];
+    for (int k = threadIdx.x; k < a.n_targets; k += kBlock) wt[k] = a.weight[k];
+    __syncthreads();  // every thread of the workgroup arrives: nothing returns above this line
+    const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i < a.n_vert) {
+        const unsigned *r = a.rest + kVertexWords * i;
+        unsigned in[kVertexWords];
+#pragma unroll
+        for (int k = 0; k < kVertexWords; k++) in[k] = r[k];
+        const uint4 b = a.rig[2 * i];
+        const uint4 wu = a.rig[2 * i + 1];
+        const float4 w = make_float4(__uint_as_float(wu.x), __uint_as_float(wu.y), __uint_as_float(wu.z), __uint_as_float(wu.w));
+
+        // Morph: the vertex's own entries in ascending target index, a rounded product and a rounded sum a component; an entry of an inactive target is skipped
+        float px = __uint_as_float(in[0]), py = __uint_as_float(in[1]), pz = __uint_as_float(in[2]);
+        float nx = __uint_as_float(in[3]), ny = __uint_as_float(in[4]), nz = __uint_as_float(in[5]);
+        const unsigned e1 = a.row[i + 1];
+        for (unsigned e = a.row[i]; e < e1; e++) {
+            const float4 d0 = a.entry[2 * (size_t)e], d1 = a.entry[2 * (size_t)e + 1];
+            const float wk = wt[__float_as_uint(d0.x)];
+            if (wk != 0.0f) {
+                px = px + wk * d0.y; py = py + wk * d0.z; pz = pz + wk * d0.w;
+                nx = nx + wk * d1.x; ny = ny + wk * d1.y; nz = nz + wk * d1.z;
+            }
+        }
+
+        float4 B0, B1, B2;
+        if (DQ) {
+            const float4 *q0 = a.pose + 2 * (size_t)b.x, *q1 = a.pose + 2 * (size_t)b.y, *q2 = a.pose + 2 * (size_t)b.z, *q3 = a.pose + 2 * (size_t)b.w;
+            const float4 r0 = q0[0], r1 = q1[0], r2 = q2[0], r3 = q3[0];
+            const float4 s = make_float4(w.x, dot4(r0, r1) < 0.0f ? -w.y : w.y, dot4(r0, r2) < 0.0f ? -w.z : w.z, dot4(r0, r3) < 0.0f ? -w.w : w.w);
+            float4 R = blend_row(s, r0, r1, r2, r3);
+            float4 D = blend_row(s, q0[1], q1[1], q2[1], q3[1]);
+            const float l = __builtin_sqrtf(dot4(R, R));
+            const bool unit = l > 0.0f;
+            R = quot4(R, l, unit);
+            D = quot4(D, l, unit);
+            const float xx = R.x * R.x, yy = R.y * R.y, zz = R.z * R.z, xy = R.x * R.y, xz = R.x * R.z, yz = R.y * R.z, wx = R.w * R.x, wy = R.w * R.y, wz = R.w * R.z;
+            B0.x = 1.0f - 2.0f * (yy + zz); B0.y = 2.0f * (xy - wz); B0.z = 2.0f * (xz + wy);
+            B1.x = 2.0f * (xy + wz); B1.y = 1.0f - 2.0f * (xx + zz); B1.z = 2.0f * (yz - wx);
+            B2.x = 2.0f * (xz - wy); B2.y = 2.0f * (yz + wx); B2.z = 1.0f - 2.0f * (xx + yy);
+            B0.w = 2.0f * (((R.w * D.x - D.w * R.x) + R.y * D.z) - R.z * D.y);
+            B1.w = 2.0f * (((R.w * D.y - D.w * R.y) + R.z * D.x) - R.x * D.z);
+            B2.w = 2.0f * (((R.w * D.z - D.w * R.z) + R.x * D.y) - R.y * D.x);
+        } else {
+            const float4 *m0 = a.pose + 3 * (size_t)b.x, *m1 = a.pose + 3 * (size_t)b.y, *m2 = a.pose + 3 * (size_t)b.z, *m3 = a.pose + 3 * (size_t)b.w;
+            B0 = blend_row(w, m0[0], m1[0], m2[0], m3[0]);
+            B1 = blend_row(w, m0[1], m1[1], m2[1], m3[1]);
+            B2 = blend_row(w, m0[2], m1[2], m2[2], m3[2]);
+        }
+        transform_store(B0, B1, B2, in, px, py, pz, nx, ny, nz, a.out + kVertexWords * i);
+    }
 }
 
 }  // namespace skin

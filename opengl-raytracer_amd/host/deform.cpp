@@ -1,11 +1,15 @@
 // deform.cpp -- glrt_deform_vertices (include/glrt_host.h): the CPU statement of the device's deform pass (glrtx_pose_morph, glrtx_pose_dualquat,
-// glrtx_debug_deform, include/glrtx.h "Deforming"; csrc/skin.hip.h: deform_kernel), and glrt_dualquat_from_matrix.  The contract is the text in include/glrtx.h;
+// glrtx_debug_deform, include/glrtx.h "Deforming"; csrc/skin.hip.h: deform_kernel), and glrt_dualquat_from_matrix.  glrt_deform_vertices_sparse is the same
+// statement over a sparse set (csrc/skin.hip.h: deform_sparse_kernel; tests/deform_sparse_math.py), glrt_morph_sparsify makes one from dense deltas.  The contract is the text in include/glrtx.h;
 // tests/deform_math.py restates it in numpy.  Every fp32 operation of the statement is one correctly rounded IEEE operation in the order written
 // (-ffp-contract=off), under MXCSR FTZ | DAZ.  From B = [L | t] on the vertex is Posing's, as host/skin.cpp states it.
 #include <cmath>
 #include <cstring>
 
+#include <vector>
+
 #include "glrt_host.h"
+#include "morph_sparse.h"
 #include "statement_math.h"
 
 namespace {
@@ -39,6 +43,41 @@ void dualquat_matrix(const float *w, const float *const q[4], float B[3][4]) {
     }
 }
 
+// The skinning stage of one vertex: B from matrices or dual quaternions, then Posing from B on (host/skin.cpp).  p, n: the (morphed) position and normal.
+void skin_stage(const float *in, const int32_t *b, const float *w, const float *bone_data, int stride, int mode, const float p[3], const float n[3], float *o) {
+    const float *const m[4] = {bone_data + stride * (size_t)b[0], bone_data + stride * (size_t)b[1], bone_data + stride * (size_t)b[2],
+                               bone_data + stride * (size_t)b[3]};
+    float B[3][4];
+    if (mode) dualquat_matrix(w, m, B);
+    else
+        for (int r = 0; r < 3; r++)
+            for (int c = 0; c < 4; c++) B[r][c] = blend(w, m, 4 * r + c);
+    // Posing from B on (host/skin.cpp)
+    const float *t = in + 9, *bn = in + 12;
+    float pos[3], v[3], tg[3], bi[3];
+    for (int r = 0; r < 3; r++) {
+        pos[r] = dot3(B[r][0], B[r][1], B[r][2], p[0], p[1], p[2]) + B[r][3];
+        tg[r] = dot3(B[r][0], B[r][1], B[r][2], t[0], t[1], t[2]);
+        bi[r] = dot3(B[r][0], B[r][1], B[r][2], bn[0], bn[1], bn[2]);
+    }
+    for (int r = 0; r < 3; r++) {
+        const float *x = B[(r + 1) % 3], *y = B[(r + 2) % 3];
+        const float c0 = x[1] * y[2] - x[2] * y[1], c1 = x[2] * y[0] - x[0] * y[2], c2 = x[0] * y[1] - x[1] * y[0];
+        v[r] = dot3(c0, c1, c2, n[0], n[1], n[2]);
+    }
+    const float s = dot3(v[0], v[1], v[2], v[0], v[1], v[2]);
+    const float l = std::sqrt(s);
+    const bool unit = l > 0.0f;
+    std::memcpy(o + 6, in + 6, 3 * sizeof(float));  // uv: moved as integers
+    for (int r = 0; r < 3; r++) {
+        const float nr = unit ? v[r] / l : v[r];
+        o[r] = canon(pos[r]);
+        o[3 + r] = canon(nr);
+        o[9 + r] = canon(tg[r]);
+        o[12 + r] = canon(bi[r]);
+    }
+}
+
 }  // namespace
 
 int glrt_deform_vertices(const float *rest_vert, size_t n_vert, const int32_t *bones4, const float *weights4, const float *bone_data, int n_bones, int mode,
@@ -69,38 +108,59 @@ int glrt_deform_vertices(const float *rest_vert, size_t n_vert, const int32_t *b
                 n[r] = n[r] + wk * d[3 + r];
             }
         }
-        const float *const m[4] = {bone_data + stride * (size_t)b[0], bone_data + stride * (size_t)b[1], bone_data + stride * (size_t)b[2],
-                                   bone_data + stride * (size_t)b[3]};
-        float B[3][4];
-        if (mode) dualquat_matrix(w, m, B);
-        else
-            for (int r = 0; r < 3; r++)
-                for (int c = 0; c < 4; c++) B[r][c] = blend(w, m, 4 * r + c);
-        // Posing from B on (host/skin.cpp)
-        float *o = vert_out + kV * i;
-        const float *t = in + 9, *bn = in + 12;
-        float pos[3], v[3], tg[3], bi[3];
-        for (int r = 0; r < 3; r++) {
-            pos[r] = dot3(B[r][0], B[r][1], B[r][2], p[0], p[1], p[2]) + B[r][3];
-            tg[r] = dot3(B[r][0], B[r][1], B[r][2], t[0], t[1], t[2]);
-            bi[r] = dot3(B[r][0], B[r][1], B[r][2], bn[0], bn[1], bn[2]);
+        skin_stage(in, b, w, bone_data, stride, mode, p, n, vert_out + kV * i);
+    }
+    return GLRT_HOST_OK;
+}
+
+int glrt_deform_vertices_sparse(const float *rest_vert, size_t n_vert, const int32_t *bones4, const float *weights4, const float *bone_data, int n_bones, int mode,
+                                const uint64_t *offsets, const uint32_t *vertex, const float *deltas, const float *morph_weights, int n_targets, float *vert_out) {
+    if (n_bones < 1 || n_bones > GLRT_MAX_BONES || !bone_data || (n_vert > 0 && (!rest_vert || !bones4 || !weights4 || !vert_out))) return GLRT_HOST_EINVAL;
+    if (mode != 0 && mode != 1) return GLRT_HOST_EINVAL;
+    SparseFault fault;
+    if (!morph_sparse_check(offsets, vertex, deltas, n_targets, n_vert, fault)) return GLRT_HOST_EINVAL;
+    if (n_targets > 0 && !morph_weights) return GLRT_HOST_EINVAL;
+    for (int k = 0; k < n_targets; k++)
+        if (!std::isfinite(morph_weights[k])) return GLRT_HOST_EINVAL;
+    for (size_t k = 0; k < 4 * n_vert; k++)
+        if (bones4[k] < 0 || bones4[k] >= n_bones) return GLRT_HOST_EINVAL;
+    FlushDenormals ftz;
+    // Morph: the targets in ascending index, each active one's entries onto the vertices they list -- per vertex that is the entries that list it, in ascending
+    // target index.  A vertex no active target lists keeps the rest words.
+    std::vector<float> pn(6 * n_vert);
+    for (size_t i = 0; i < n_vert; i++) std::memcpy(&pn[6 * i], rest_vert + kV * i, 6 * sizeof(float));
+    for (int k = 0; k < n_targets; k++) {
+        const float wk = morph_weights[k];
+        if (tiny(wk)) continue;  // inactive: its entries never enter the arithmetic
+        for (uint64_t e = offsets[k]; e < offsets[k + 1]; e++) {
+            float *q = &pn[6 * (size_t)vertex[e]];
+            const float *d = deltas + 6 * e;
+            for (int r = 0; r < 6; r++) q[r] = q[r] + wk * d[r];
         }
-        for (int r = 0; r < 3; r++) {
-            const float *x = B[(r + 1) % 3], *y = B[(r + 2) % 3];
-            const float c0 = x[1] * y[2] - x[2] * y[1], c1 = x[2] * y[0] - x[0] * y[2], c2 = x[0] * y[1] - x[1] * y[0];
-            v[r] = dot3(c0, c1, c2, n[0], n[1], n[2]);
+    }
+    const int stride = mode ? 8 : 12;
+    for (size_t i = 0; i < n_vert; i++)
+        skin_stage(rest_vert + kV * i, bones4 + 4 * i, weights4 + 4 * i, bone_data, stride, mode, &pn[6 * i], &pn[6 * i + 3], vert_out + kV * i);
+    return GLRT_HOST_OK;
+}
+
+int glrt_morph_sparsify(const float *dense_deltas, int n_targets, size_t n_vert, uint64_t *offsets, uint32_t *vertex_out, float *deltas_out) {
+    if (n_targets < 0 || n_targets > GLRT_MAX_SPARSE_MORPH_TARGETS || !offsets || n_vert >= ((size_t)1 << 32)) return GLRT_HOST_EINVAL;
+    if (n_targets > 0 && n_vert > 0 && !dense_deltas) return GLRT_HOST_EINVAL;
+    if (vertex_out && !deltas_out) return GLRT_HOST_EINVAL;
+    uint64_t nnz = 0;
+    offsets[0] = 0;
+    for (int k = 0; k < n_targets; k++) {
+        for (size_t i = 0; i < n_vert; i++) {
+            const float *d = dense_deltas + ((size_t)k * n_vert + i) * 6;
+            if (!morph_entry_kept(d)) continue;
+            if (vertex_out) {
+                vertex_out[nnz] = (uint32_t)i;
+                std::memcpy(deltas_out + 6 * nnz, d, 6 * sizeof(float));
+            }
+            nnz++;
         }
-        const float s = dot3(v[0], v[1], v[2], v[0], v[1], v[2]);
-        const float l = std::sqrt(s);
-        const bool unit = l > 0.0f;
-        std::memcpy(o + 6, in + 6, 3 * sizeof(float));  // uv: moved as integers
-        for (int r = 0; r < 3; r++) {
-            const float nr = unit ? v[r] / l : v[r];
-            o[r] = canon(pos[r]);
-            o[3 + r] = canon(nr);
-            o[9 + r] = canon(tg[r]);
-            o[12 + r] = canon(bi[r]);
-        }
+        offsets[k + 1] = nnz;
     }
     return GLRT_HOST_OK;
 }

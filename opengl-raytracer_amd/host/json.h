@@ -31,6 +31,7 @@ public:
     bool is_object() const { return type_ == OBJECT; }
     double number_value() const { return type_ == NUMBER ? num_ : 0.0; }
     int int_value() const { return (int)number_value(); }
+    bool is_bool() const { return type_ == BOOL; }
     bool bool_value() const { return type_ == BOOL && num_ != 0.0; }
     const std::string &string_value() const { static const std::string e; return type_ == STRING ? str_ : e; }
     const std::vector<Json> &array_items() const { static const std::vector<Json> e; return type_ == ARRAY ? *arr_ : e; }

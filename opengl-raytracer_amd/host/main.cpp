@@ -69,7 +69,9 @@ static void usage(const char *exe) {
                 "                          \"camera\" optional with the scene file's keys.  Every step renders --frames frames and writes <out stem>_<step, 4 digits>.<ext> as a\n"
                 "                          still run would under the same --denoise* / --bloom / --tonemap (one device; not with --adaptive*, --reweight, --enable-volume,\n"
                 "                          --extensions or --save-every-frame).  Morph targets: a top-level \"targets\": [{\"shape\": i, \"file\": \"x.obj\"}, ...] and per step\n"
-                "                          \"weights\": [[target, w], ...] blend the shapes' vertices towards the targets' before the pose (glrtx_pose_morph)\n"
+                "                          \"weights\": [[target, w], ...] blend the shapes' vertices towards the targets' before the pose (glrtx_pose_morph), at most 64\n"
+                "                          targets; with a top-level \"sparse_targets\": true at most 1024, each kept as the list of the vertices it moves\n"
+                "                          (glrtx_upload_morph_targets_sparse)\n"
                 "      --carry-history     with --animate: keep the accumulator across the steps by motion-aware reprojection (glrtx_reproject_motion) instead of clearing\n"
                 "                          it; moments are tracked, so --denoise-variance composes (not with --denoise)\n", exe);
 }

@@ -13,6 +13,7 @@
 #include "glrt_host.h"
 #include "glrtx.h"
 #include "json.h"
+#include "morph_sparse.h"
 
 namespace glrt {
 
@@ -66,6 +67,7 @@ void Scene::parse(const std::string &filename) {
     // shapes (scene.cpp:116-250)
     vertices.clear(); triangles.clear(); lights.clear(); materials.clear(); nodes.clear();
     shapeFirstVertex_.clear(); animation_.clear(); morphShape_.clear(); morphDeltas_.clear();
+    morphSparse_ = false; morphOffsets_.clear(); morphVertex_.clear(); morphSparseDeltas_.clear();
     const auto &shapes = json["scene"].array_items();
     for (size_t i = 0; i < shapes.size(); i++) {
         const Json &sh = shapes[i];
@@ -185,14 +187,20 @@ void Scene::parseAnimation(const std::string &filename) {
     if (!json["steps"].is_array()) GLRT_FatalError("animation: no \"steps\" array");
     const size_t n_shapes = shapeFirstVertex_.size();
     animation_.clear(); morphShape_.clear(); morphDeltas_.clear();
+    morphSparse_ = false; morphOffsets_.clear(); morphVertex_.clear(); morphSparseDeltas_.clear();
+    if (!json["sparse_targets"].is_null() && !json["sparse_targets"].is_bool()) GLRT_FatalError("animation: \"sparse_targets\" is not true or false");
+    morphSparse_ = json["sparse_targets"].bool_value();
     auto index_of = [](const Json &x, size_t n) { const double v = x.number_value(); return x.is_number() && v >= 0.0 && v < (double)n && v == std::floor(v); };
     if (!json["targets"].is_null()) {  // morph targets: one OBJ a target, the deltas of its shape's vertices
         if (!json["targets"].is_array()) GLRT_FatalError("animation: \"targets\" is not an array");
         const auto &targets = json["targets"].array_items();
-        if (targets.size() > 64) GLRT_FatalError("animation: %zu morph targets (at most 64)", targets.size());
+        if (morphSparse_ && targets.size() > GLRT_MAX_SPARSE_MORPH_TARGETS)
+            GLRT_FatalError("animation: %zu sparse morph targets (at most %d)", targets.size(), GLRT_MAX_SPARSE_MORPH_TARGETS);
+        if (!morphSparse_ && targets.size() > 64) GLRT_FatalError("animation: %zu morph targets (at most 64)", targets.size());
         const size_t slash = filename.find_last_of("/\\");
         const std::string dir = slash == std::string::npos ? "." : filename.substr(0, slash);
-        morphDeltas_.assign(targets.size() * vertices.size() * 6, 0.0f);
+        if (morphSparse_) morphOffsets_.assign(1, 0);  // (the dense targets x vertices x 6 array is never allocated)
+        else morphDeltas_.assign(targets.size() * vertices.size() * 6, 0.0f);
         for (size_t t = 0; t < targets.size(); t++) {
             if (!index_of(targets[t]["shape"], n_shapes))
                 GLRT_FatalError("animation target %zu: shape index %g is out of range (the scene has %zu shapes)", t, targets[t]["shape"].number_value(), n_shapes);
@@ -204,6 +212,21 @@ void Scene::parseAnimation(const std::string &filename) {
             const size_t first = shapeFirstVertex(shape), count = shapeFirstVertex(shape + 1) - first;
             if (mesh.size() != count)
                 GLRT_FatalError("animation target %zu: %s has %zu vertices, shape %zu has %zu", t, file.c_str(), mesh.size(), shape, count);
+            if (morphSparse_) {  // the index directly: a vertex of the shape gets an entry iff its delta passes glrt_morph_sparsify's rule
+                for (size_t v = 0; v < count; v++) {
+                    float d[6];
+                    for (int k = 0; k < 3; k++) {
+                        d[k] = mesh[v].pos[k] - vertices[first + v].pos[k];
+                        d[3 + k] = mesh[v].normal[k] - vertices[first + v].normal[k];
+                    }
+                    if (!glrt_detail::morph_entry_kept(d)) continue;
+                    morphVertex_.push_back((uint32_t)(first + v));
+                    morphSparseDeltas_.insert(morphSparseDeltas_.end(), d, d + 6);
+                }
+                morphOffsets_.push_back((uint64_t)morphVertex_.size());
+                morphShape_.push_back(shape);
+                continue;
+            }
             float *d = morphDeltas_.data() + (t * vertices.size() + first) * 6;
             for (size_t v = 0; v < count; v++)
                 for (int k = 0; k < 3; k++) {
@@ -247,7 +270,8 @@ void Scene::parseAnimation(const std::string &filename) {
         animation_.push_back(std::move(st));
     }
     GLRT_Info("Animation: %zu steps, %zu shapes", animation_.size(), n_shapes);
-    if (n_targets) GLRT_Info("Animation: %zu morph targets", n_targets);
+    if (n_targets && morphSparse_) GLRT_Info("Animation: %zu sparse morph targets, %zu entries", n_targets, morphVertex_.size());
+    else if (n_targets) GLRT_Info("Animation: %zu morph targets", n_targets);
 }
 
 void Scene::setBuffers(int w, int h, const float view[16], const float proj[16], float aperture, float focal,
@@ -257,6 +281,7 @@ void Scene::setBuffers(int w, int h, const float view[16], const float proj[16],
     std::memcpy(projM, proj, sizeof projM);
     vertices = std::move(v); triangles = std::move(t); materials = std::move(m); nodes = std::move(n);
     shapeFirstVertex_.clear(); animation_.clear(); morphShape_.clear(); morphDeltas_.clear();
+    morphSparse_ = false; morphOffsets_.clear(); morphVertex_.clear(); morphSparseDeltas_.clear();
     finalize();
 }
 
@@ -514,6 +539,34 @@ struct SceneMorphProbe {
     }
 };
 }  // namespace glrt
+
+// Sparse morph probe: as the morph probe for a file with "sparse_targets": true.  counts = {steps, targets, vertices, entries, sparse (0 / 1)}; target_shape
+// (targets), offsets (targets + 1), vertex (entries), deltas (entries x 6) and weights (steps x targets) may each be NULL.
+namespace glrt {
+struct SceneMorphSparseProbe {
+    static int run(const char *json, const char *animation, long long counts[5], int *target_shape, uint64_t *offsets, uint32_t *vertex, float *deltas, float *weights) {
+        Scene sc;
+        sc.parse(json);
+        sc.parseAnimation(animation);
+        const size_t n_steps = sc.animation_.size(), n_targets = sc.numMorphTargets(), nnz = sc.morphVertex_.size();
+        counts[0] = (long long)n_steps; counts[1] = (long long)n_targets; counts[2] = (long long)sc.vertices.size();
+        counts[3] = (long long)nnz; counts[4] = sc.morphSparse_ ? 1 : 0;
+        if (target_shape)
+            for (size_t t = 0; t < n_targets; t++) target_shape[t] = (int)sc.morphShape_[t];
+        if (offsets && !sc.morphOffsets_.empty()) std::memcpy(offsets, sc.morphOffsets_.data(), sc.morphOffsets_.size() * sizeof(uint64_t));
+        if (vertex && nnz) std::memcpy(vertex, sc.morphVertex_.data(), nnz * sizeof(uint32_t));
+        if (deltas && nnz) std::memcpy(deltas, sc.morphSparseDeltas_.data(), nnz * 6 * sizeof(float));
+        if (weights && n_targets)
+            for (size_t s = 0; s < n_steps; s++) std::memcpy(weights + s * n_targets, sc.animation_[s].weights.data(), n_targets * sizeof(float));
+        return 0;
+    }
+};
+}  // namespace glrt
+
+extern "C" GLRT_API int glrt_scene_morph_sparse_probe(const char *json, const char *animation, long long counts[5], int *target_shape, uint64_t *offsets,
+                                                      uint32_t *vertex, float *deltas, float *weights) {
+    return glrt::SceneMorphSparseProbe::run(json, animation, counts, target_shape, offsets, vertex, deltas, weights);
+}
 
 extern "C" GLRT_API int glrt_scene_morph_probe(const char *json, const char *animation, long long counts[3], int *target_shape, float *deltas, float *weights) {
     return glrt::SceneMorphProbe::run(json, animation, counts, target_shape, deltas, weights);

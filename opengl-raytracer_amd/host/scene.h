@@ -4,6 +4,7 @@
 // TextureBuffer objects (scene.h:63-67) this class holds the flat host buffers in the identical
 // byte layout and hands them to glrtx_upload_scene (include/glrtx.h).
 #pragma once
+#include <cstdint>
 #include <string>
 #include <vector>
 
@@ -75,6 +76,11 @@ public:
     // resolved against the animation file's directory) and each step "weights": [[target, w], ...]; targets a step does not list get 0.  A target OBJ goes
     // through loadObj and must give shape i's vertex count (otherwise a FatalError names both counts); its delta is target - rest for position and normal, one
     // float subtraction each, and zero outside the shape.  A file without "targets" is what it was.
+    //
+    // Sparse targets (include/glrtx.h "Deforming", SPARSE TARGETS).  With a top-level "sparse_targets": true the limit is 1024 targets instead of 64 and the
+    // parser builds the sparse set directly from each target OBJ: a vertex of the shape gets an entry iff its delta passes glrt_morph_sparsify's rule (some
+    // component with a non-zero exponent field); the dense targets x vertices x 6 array is never allocated and morphDeltas() stays empty.  Window uploads the
+    // set with glrtx_upload_morph_targets_sparse.  A file without the key parses, uploads and renders as before.
     struct AnimationStep {
         std::vector<float> matrices;  // numShapes() x 12
         std::vector<float> weights;   // numMorphTargets()
@@ -87,6 +93,11 @@ public:
     size_t numMorphTargets() const { return morphShape_.size(); }
     // the targets' deltas as glrtx_upload_morph_targets takes them: numMorphTargets() x vertex count x 6 floats {dpos, dnormal}
     const std::vector<float> &morphDeltas() const { return morphDeltas_; }
+    // with "sparse_targets": true, the set as glrtx_upload_morph_targets_sparse takes it: offsets (numMorphTargets() + 1), vertex and deltas (6 floats an entry)
+    bool morphSparse() const { return morphSparse_; }
+    const std::vector<uint64_t> &morphOffsets() const { return morphOffsets_; }
+    const std::vector<uint32_t> &morphVertex() const { return morphVertex_; }
+    const std::vector<float> &morphSparseDeltas() const { return morphSparseDeltas_; }
     // the first vertex of entry i of the JSON "scene" array (an entry without geometry owns none: its range is empty); i == numShapes(): the vertex count
     size_t shapeFirstVertex(size_t i) const { return i < shapeFirstVertex_.size() ? shapeFirstVertex_[i] : vertices.size(); }
 
@@ -114,6 +125,10 @@ private:
     std::vector<AnimationStep> animation_;
     std::vector<size_t> morphShape_;   // per morph target of the animation file: its shape
     std::vector<float> morphDeltas_;
+    bool morphSparse_ = false;  // "sparse_targets": true -- the three arrays below in morphDeltas_' place
+    std::vector<uint64_t> morphOffsets_;
+    std::vector<uint32_t> morphVertex_;
+    std::vector<float> morphSparseDeltas_;
     VolumeGrid volDensity_, volTemperature_;  // volumeSpecs_[0]'s files (only with enableVolume(true)); only the first volume is rendered (window.cpp:271-286)
 
     friend class Window;
@@ -121,6 +136,7 @@ private:
     friend struct SceneVolumeProbe;
     friend struct SceneAnimationProbe;
     friend struct SceneMorphProbe;
+    friend struct SceneMorphSparseProbe;
 };
 
 // OBJ triangles the way the reference's loader yields them (trimesh.cpp:113-191): three fresh

@@ -276,7 +276,11 @@ void Window::animate() {
             GLRT_FatalError("glrtx_upload_rig: %s", glrtx_last_error(c0));
     }
     const int n_targets = (int)scene->numMorphTargets();  // the file's morph targets go up after the rig; with them a step is a glrtx_pose_morph
-    if (n_targets > 0 && glrtx_upload_morph_targets(c0, scene->morphDeltas().data(), n_targets, n_vert) != GLRTX_OK)
+    if (n_targets > 0 && scene->morphSparse()) {  // ("sparse_targets": true: the parser's index, never a dense array)
+        if (glrtx_upload_morph_targets_sparse(c0, scene->morphOffsets().data(), scene->morphVertex().data(), scene->morphSparseDeltas().data(), n_targets, n_vert) !=
+            GLRTX_OK)
+            GLRT_FatalError("glrtx_upload_morph_targets_sparse: %s", glrtx_last_error(c0));
+    } else if (n_targets > 0 && glrtx_upload_morph_targets(c0, scene->morphDeltas().data(), n_targets, n_vert) != GLRTX_OK)
         GLRT_FatalError("glrtx_upload_morph_targets: %s", glrtx_last_error(c0));
     float view0[16], proj0[16];
     std::memcpy(view0, scene->viewM, sizeof view0);

@@ -79,7 +79,8 @@ public:
     // s = 1 on glrtx_reproject_motion with the default configuration -- without it glrtx_clear and the feature pass a still run's denoiser would make --; then the
     // frames in bursts of framesInFlight (through glrtx_render_moments when moments are tracked: carryHistory or setDenoiseVariance); then the image.
     // Not with several devices, setAdaptive*, setReweight, extension or volume scenes, one image per frame, or carryHistory with setDenoise (no moments).
-    // A file with morph targets: glrtx_upload_morph_targets once after glrtx_upload_rig, and every step's pose is glrtx_pose_morph with the step's weights.
+    // A file with morph targets: glrtx_upload_morph_targets once after glrtx_upload_rig -- glrtx_upload_morph_targets_sparse for a file with "sparse_targets":
+    // true --, and every step's pose is glrtx_pose_morph with the step's weights.
     void setAnimation(const std::string &file, bool carryHistory) { animationFile_ = file; carryHistory_ = carryHistory; }
     // wall-clock ms PER FRAME between the last two waits for the device, averaged over the frames issued in between (with one PNG per run: the whole run, cold first
     // launches included; with --save-every-frame: the whole run, PNG writing included).  The device's own time of the last launch is glrtx_stats.kernel_ms_last.

@@ -174,7 +174,8 @@ EXPORTS = ["glrtx_abi_version", "glrtx_create", "glrtx_destroy", "glrtx_last_err
            "glrtx_bloom", "glrtx_read_bloomed", "glrtx_tonemap_bloomed", "glrtx_resolve_bloomed_rgba8", "glrtx_debug_bloom", "glrtx_debug_bloom_burst",
            "glrtx_track_cascades", "glrtx_render_cascades", "glrtx_read_cascades", "glrtx_reweight", "glrtx_debug_fold_cascades", "glrtx_debug_reweight",
            "glrtx_debug_reweight_burst", "glrtx_upload_rig", "glrtx_pose", "glrtx_debug_skin", "glrtx_debug_skin_burst",
-           "glrtx_upload_morph_targets", "glrtx_pose_morph", "glrtx_pose_dualquat", "glrtx_debug_deform", "glrtx_debug_deform_burst"]
+           "glrtx_upload_morph_targets", "glrtx_pose_morph", "glrtx_pose_dualquat", "glrtx_debug_deform", "glrtx_debug_deform_burst",
+           "glrtx_upload_morph_targets_sparse", "glrtx_debug_deform_sparse"]
 
 SCENE_BUFFERS = ("nodes", "cnodes", "nrms", "lights", "vine", "root")  # glrtx_debug_read_scene's `which`, in order (GLRTX_SCENE_*)
 
@@ -363,6 +364,9 @@ def lib():
             L.glrtx_pose_dualquat.argtypes = [vp, fp, C.c_int, fp, C.c_int]
             L.glrtx_debug_deform.argtypes = [fp, C.c_size_t, i32p, fp, fp, C.c_int, C.c_int, fp, fp, C.c_int, fp]
             L.glrtx_debug_deform_burst.argtypes = [vp, C.c_int, C.POINTER(C.c_float)]
+            u32p, u64p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
+            L.glrtx_upload_morph_targets_sparse.argtypes = [vp, u64p, u32p, fp, C.c_int, C.c_size_t]
+            L.glrtx_debug_deform_sparse.argtypes = [fp, C.c_size_t, i32p, fp, fp, C.c_int, C.c_int, u64p, u32p, fp, fp, C.c_int, fp]
         except AttributeError:
             pass
         _lib = L
@@ -687,6 +691,25 @@ def debug_deform(rest, bones, weights, bone_data, mode=0, deltas=None, morph_wei
     return out
 
 
+def debug_deform_sparse(rest, bones, weights, bone_data, mode=0, offsets=None, vertex=None, deltas=None, morph_weights=None):
+    """glrtx_debug_deform_sparse on the current device: the sparse deform kernel alone -- the rig and bone data of debug_deform; the set as offsets
+    (n_targets + 1,) uint64, vertex (nnz,) uint32, deltas (nnz, 6) float32; morph_weights (n_targets,) float32.  Returns the deformed vertices (n, 15) float32."""
+    from .host import deform_arrays, sparse_arrays, sparse_pointers
+    L = lib()
+    r, b, w, m, _, _ = deform_arrays("debug_deform_sparse", rest, bones, weights, bone_data, mode, None, None)
+    o, v, d = sparse_arrays("debug_deform_sparse", offsets, vertex, deltas)
+    mw = np.zeros(0, np.float32) if morph_weights is None else _f32(morph_weights).reshape(-1)
+    if mw.size != o.size - 1:
+        raise ValueError(f"debug_deform_sparse: {mw.size} morph weights for {o.size - 1} targets")
+    out = np.zeros_like(r)
+    po, pv, pd = sparse_pointers(o, v, d)
+    rc = L.glrtx_debug_deform_sparse(_fp(r), r.shape[0], b.ctypes.data_as(C.POINTER(C.c_int32)), _fp(w), _fp(m), m.shape[0], int(mode), po, pv, pd,
+                                     _fp(mw) if mw.size else None, mw.size, _fp(out))
+    if rc != 0:
+        raise GlrtxError(rc, L.glrtx_last_error(None).decode())
+    return out
+
+
 def _host_vertices(v):
     """A numpy vertex array for glrtx_update_vertices: float32, shape (n, 15) or flat (or the scene's (n * 5, 3) texels).  Returns (array, n)."""
     a = np.asarray(v)
@@ -822,6 +845,15 @@ class Device:
             self._ck(self.L.glrtx_upload_morph_targets(self.h, None, 0, self._rig_vertices))
         else:
             self._ck(self.L.glrtx_upload_morph_targets(self.h, _fp(d), d.shape[0], d.shape[1]))
+
+    def upload_morph_targets_sparse(self, offsets, vertex=None, deltas=None, n_vert=None):
+        """glrtx_upload_morph_targets_sparse: a sparse set for the uploaded rig -- offsets (n_targets + 1,) uint64, vertex (nnz,) uint32, deltas (nnz, 6) float32
+        {dpos, dnormal} (glrt_amd.host.morph_sparsify makes the three from dense deltas).  offsets None, or a single 0, drops whatever set the rig holds.
+        n_vert: the vertex count the set was made for (the rig's, unless given)."""
+        from .host import sparse_arrays, sparse_pointers
+        o, v, d = sparse_arrays("upload_morph_targets_sparse", offsets, vertex, deltas)
+        po, pv, pd = sparse_pointers(o, v, d)
+        self._ck(self.L.glrtx_upload_morph_targets_sparse(self.h, po, pv, pd, o.size - 1, self._rig_vertices if n_vert is None else int(n_vert)))
 
     @staticmethod
     def _morph_weights(w):

@@ -58,6 +58,8 @@ def lib():
         L.glrt_reweight.argtypes = [fp, C.c_int, C.c_int, C.c_float, fp]
         L.glrt_skin_vertices.argtypes = [fp, C.c_size_t, C.POINTER(C.c_int32), fp, fp, C.c_int, fp]
         L.glrt_deform_vertices.argtypes = [fp, C.c_size_t, C.POINTER(C.c_int32), fp, fp, C.c_int, C.c_int, fp, fp, C.c_int, fp]
+        L.glrt_deform_vertices_sparse.argtypes = [fp, C.c_size_t, C.POINTER(C.c_int32), fp, fp, C.c_int, C.c_int, u64p, u32p, fp, fp, C.c_int, fp]
+        L.glrt_morph_sparsify.argtypes = [fp, C.c_int, C.c_size_t, u64p, u32p, fp]
         L.glrt_dualquat_from_matrix.argtypes = [fp, fp]
         L.glrt_dualquat_from_matrix.restype = None
         L.glrt_look_at.argtypes = [fp, fp, fp, fp]
@@ -446,6 +448,63 @@ def deform_vertices(rest, bones, weights, bone_data, mode=0, deltas=None, morph_
     if rc != 0:
         raise RuntimeError(f"glrt_deform_vertices failed: {rc}")
     return out
+
+
+def sparse_arrays(name, offsets, vertex, deltas):
+    """A sparse morph-target set as the C calls take it: offsets (n_targets + 1,) uint64, vertex (nnz,) uint32, deltas (nnz, 6) float32; None for all three is
+    the set of no targets.  Only the shapes are looked at here: what the set holds is the library's to check.  Bits are kept."""
+    if offsets is None:
+        return np.zeros(1, np.uint64), np.zeros(0, np.uint32), np.zeros((0, 6), np.float32)
+    o = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
+    v = np.zeros(0, np.uint32) if vertex is None else np.ascontiguousarray(vertex, dtype=np.uint32).reshape(-1)
+    d = np.zeros((0, 6), np.float32) if deltas is None else _f32(deltas).reshape(-1, 6)
+    if o.size < 1 or v.size != d.shape[0]:
+        raise ValueError(f"{name}: {o.size} offsets, {v.size} vertex indices, {d.shape[0]} delta records")
+    return o, v, d
+
+
+def sparse_pointers(o, v, d):
+    """The three ctypes pointers of sparse_arrays' result; an empty vertex or deltas array goes in as NULL."""
+    return (o.ctypes.data_as(C.POINTER(C.c_uint64)), v.ctypes.data_as(C.POINTER(C.c_uint32)) if v.size else None, _fp(d) if d.size else None)
+
+
+def deform_vertices_sparse(rest, bones, weights, bone_data, mode=0, offsets=None, vertex=None, deltas=None, morph_weights=None):
+    """glrt_deform_vertices_sparse: the CPU statement of Device.pose_morph / Device.pose_dualquat on a rig with a sparse set and of device.debug_deform_sparse
+    (include/glrtx.h "Deforming", SPARSE TARGETS).  offsets (n_targets + 1,), vertex (nnz,), deltas (nnz, 6), morph_weights (n_targets,).  Returns (n, 15)."""
+    r, b, w, m, _, _ = deform_arrays("deform_vertices_sparse", rest, bones, weights, bone_data, mode, None, None)
+    o, v, d = sparse_arrays("deform_vertices_sparse", offsets, vertex, deltas)
+    mw = np.zeros(0, np.float32) if morph_weights is None else _f32(morph_weights).reshape(-1)
+    if mw.size != o.size - 1:
+        raise ValueError(f"deform_vertices_sparse: {mw.size} morph weights for {o.size - 1} targets")
+    out = np.zeros_like(r)
+    po, pv, pd = sparse_pointers(o, v, d)
+    rc = lib().glrt_deform_vertices_sparse(_fp(r), r.shape[0], b.ctypes.data_as(C.POINTER(C.c_int32)), _fp(w), _fp(m), m.shape[0], int(mode), po, pv, pd,
+                                           _fp(mw) if mw.size else None, mw.size, _fp(out))
+    if rc != 0:
+        raise RuntimeError(f"glrt_deform_vertices_sparse failed: {rc}")
+    return out
+
+
+def morph_sparsify(deltas):
+    """glrt_morph_sparsify: dense deltas (n_targets, n_vert, 6) float32 -> (offsets (n_targets + 1,) uint64, vertex (nnz,) uint32, deltas (nnz, 6) float32), the
+    entries with a component whose exponent field is not 0.  The counting call first, then the filling call."""
+    d = _f32(deltas)
+    if d.ndim != 3 or d.shape[2] != 6:
+        raise ValueError(f"morph_sparsify: deltas must be (n_targets, n_vert, 6), got {d.shape}")
+    L = lib()
+    o = np.zeros(d.shape[0] + 1, np.uint64)
+    po = o.ctypes.data_as(C.POINTER(C.c_uint64))
+    src = _fp(d) if d.size else None
+    rc = L.glrt_morph_sparsify(src, d.shape[0], d.shape[1], po, None, None)
+    if rc != 0:
+        raise RuntimeError(f"glrt_morph_sparsify failed: {rc}")
+    nnz = int(o[-1])
+    v, out = np.zeros(nnz, np.uint32), np.zeros((nnz, 6), np.float32)
+    if nnz:
+        rc = L.glrt_morph_sparsify(src, d.shape[0], d.shape[1], po, v.ctypes.data_as(C.POINTER(C.c_uint32)), _fp(out))
+        if rc != 0 or int(o[-1]) != nnz:
+            raise RuntimeError(f"glrt_morph_sparsify failed: {rc} ({int(o[-1])} entries after {nnz} counted)")
+    return o, v, out
 
 
 def dualquat_from_matrix(m):
