@@ -261,6 +261,26 @@ int glrt_morph_sparsify(const float *dense_deltas, int n_targets, size_t n_vert,
  * rounded once, with the sign that makes r.w >= 0.  d = 1/2 (t, 0) * r. */
 void glrt_dualquat_from_matrix(const float m[12], float dq[8]);
 
+/* Rebuilding normals: the CPU statements of the device's normal rebuild (glrtx_update_positions / glrtx_set_pose_normals / glrtx_debug_rebuild_normals,
+ * include/glrtx.h "Rebuilding normals": the weld rule, the orientation rule and the arithmetic are there), bit for bit (host/normals.cpp, host/normal_topology.h;
+ * tests/normals_math.py states them in numpy).  rest_vert / vert_inout: n_vert wire vertices of GLRT_VERTEX_FLOATS floats; tri: n_tri x 4 floats {i0, i1, i2,
+ * material} as glrt_bvh_build_* take them.  The arithmetic runs with denormals flushed (MXCSR FTZ | DAZ, restored on return).
+ *   glrt_normal_topology        class_of_vertex_out[n_vert]: the weld class of every vertex, ids ascending with each class's smallest member (so the map is a
+ *                               function of the input alone); flip_out[n_tri]: 1 for a triangle wound against its rest normals, else 0; n_classes_out may be
+ *                               NULL.  flags: 0, or GLRT_NORMALS_WELD_POSITIONS to weld by position alone.
+ *   glrt_rebuild_normals        rebuilds the normal words of vert_inout in place from its position words; every other word is left as it is.  class_of_vertex may
+ *                               be any map with ids below n_vert (the rows of ids no vertex carries are empty); flip is n_tri bytes, zero or not.
+ *   glrt_positions_to_vertices  vert_out = the rest records with their three position words replaced by pos (n_vert x 3 floats), moved as integers (vert_out may
+ *                               not overlap the inputs).
+ * GLRT_HOST_EINVAL: a NULL pointer with something to read or write, n_vert or n_tri >= 2^31, a corner index that is not an integer in [0, n_vert), an unknown
+ * flag, a class id >= n_vert. */
+#define GLRT_NORMALS_WELD_POSITIONS 1u
+#define GLRT_NORMAL_CHUNK 256u
+int glrt_normal_topology(const float *rest_vert, size_t n_vert, const float *tri, size_t n_tri, unsigned flags, uint32_t *class_of_vertex_out, uint8_t *flip_out,
+                         size_t *n_classes_out);
+int glrt_rebuild_normals(float *vert_inout, size_t n_vert, const float *tri, size_t n_tri, const uint32_t *class_of_vertex, const uint8_t *flip);
+int glrt_positions_to_vertices(const float *rest_vert, const float *pos, size_t n_vert, float *vert_out);
+
 void glrt_look_at(const float eye[3], const float center[3], const float up[3], float out[16]);
 void glrt_perspective(float fovy_deg, float aspect, float z_near, float z_far, float out[16]);
 void glrt_mat4_mul(const float a[16], const float b[16], float out[16]);

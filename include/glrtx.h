@@ -1045,6 +1045,76 @@ int glrtx_upload_morph_targets_sparse(glrtx_ctx *ctx, const uint64_t *offsets, c
 int glrtx_debug_deform_sparse(const float *rest, size_t n_vert, const int32_t *bones4, const float *weights4, const float *bone_data, int n_bones, int mode,
                               const uint64_t *offsets, const uint32_t *vertex, const float *deltas, const float *morph_weights, int n_targets, float *vert_out);
 
+/* ---- Rebuilding normals: shading normals rebuilt on the device from the moved surface (no reference counterpart; off unless called: no other call's behaviour
+ * changes).  A bone carries its normals exactly (Posing's cofactor matrix).  A morph target does not: its normal is n + sum w dnormal, only as good as the deltas
+ * the file carried, and glTF targets very often carry none.  A simulation or a cache gives positions and nothing else.  Three passes (csrc/normals.hip.h) make
+ * area-weighted smooth normals from the triangles as they stand; they serve a position-only vertex update and an opt-in stage between the deform kernels and
+ * the refit.
+ *
+ * Arithmetic.  The rules are Posing's: one correctly rounded fp32 operation at a time, unfused, in the order written; denormals are zeros of their sign into
+ * and out of every operation; a stored NaN is 0x7FC00000; dot(a, b) = (a.z b.z + a.y b.y) + a.x b.x.
+ *
+ * TOPOLOGY.  Built on the host, once, from the rest vertices (n_vert x 15 floats, wire format) and the wire triangles (n_tri x 4 floats {i0, i1, i2,
+ * material}, as glrtx_upload_scene takes them).
+ *   Weld classes  two vertices are the same smooth vertex iff the six words of their rest position and rest normal are equal as 32-bit patterns; +0 and -0
+ *             differ.  This welds the unindexed three-vertices-a-triangle meshes of the facade's OBJ reader and of scenes.SceneBuilder, and keeps a box's
+ *             corners apart, because their normals differ.  With the flag GLRTX_NORMALS_WELD_POSITIONS = 1 only the three position words are compared: for
+ *             meshes that carry no normals worth keeping.  Class ids ascend with each class's smallest member.
+ *   Face list     a class's list holds the triangles with at least one corner in the class, each once, in ascending triangle index.
+ *   Orientation   triangle t is FLIPPED iff, in the rest pose, dot(f, m) < 0, where f is its face vector (below) and m = (n0 + n1) + n2 per component over its
+ *             corners' rest normals in corner order.  A NaN or a zero does not flip.  With this, rebuilt normals keep the side the authored normals were on,
+ *             whatever the winding.
+ *
+ * REBUILD.  In place on n_vert wire vertices.  Positions are only read; normal words are the only ones written; no word is both read and written.
+ *   Face vector   of triangle t with corners i0, i1, i2:  e1 = p[i1] - p[i0]  and  e2 = p[i2] - p[i0]  per component;
+ *               f.x = e1.y e2.z - e1.z e2.y    f.y = e1.z e2.x - e1.x e2.z    f.z = e1.x e2.y - e1.y e2.x
+ *             -- two rounded products and one subtraction a component.  If t is flipped, the three sign bits are inverted.  The vector is not normalised: the
+ *             sum is area-weighted.
+ *   Sum           of a class, over its face list in order, in chunks of GLRTX_NORMAL_CHUNK = 256 entries.  Inside a chunk  c = f_first, then c = c + f_next
+ *             per component; across chunks  s = c_0, then s = s + c_k  in chunk order.  A list of up to 256 faces is a plain sequential sum.  The chunk rule
+ *             is part of the contract so that a later kernel may hand a long list's chunks to separate waves without changing a bit; today every class is
+ *             summed on one lane, in that order.  An empty list has s = 0.
+ *   Normal        l = sqrt(dot(s, s)).  If l == 0 the normal words in place are KEPT: an empty list, a degenerate or exactly cancelling neighbourhood, a vertex
+ *             that no triangle names.  Otherwise n = s / l, three IEEE quotients; a NaN goes through as the canonical NaN; l = +Inf gives zeros or NaN.  Every
+ *             member of the class receives the same three words.
+ * Tangents and binormals are not touched: the renderer reads neither, and they keep their rest or posed words.  The CPU statements are glrt_normal_topology
+ * and glrt_rebuild_normals (include/glrt_host.h), bit for bit; glrt_positions_to_vertices there makes the records of a position-only update.
+ *
+ *   glrtx_upload_normal_topology  builds the topology (glrt_normal_topology's routine) and keeps on the device a copy of rest_vert (60 n_vert bytes) and the
+ *                     index: 16-byte triangle records {i0, i1, i2, flip}, a class id a vertex, the face lists as rows -- 16 n_tri + 4 n_vert +
+ *                     4 (n_classes + 1) + 4 entries bytes, entries being the summed length of the face lists (at most 3 n_tri) -- and 16 (n_tri + n_classes)
+ *                     bytes of scratch for a rebuild.  GLRTX_EINVAL, nothing changed: no scene, n_vert other than the scene's, a NULL pointer, a corner index
+ *                     that is not an integer in [0, n_vert), n_tri >= 2^31, an unknown flag (or face lists of 2^32 entries or more).  glrtx_upload_scene
+ *                     forgets the topology and the switch below; glrtx_upload_rig, glrtx_update_vertices / _device and the morph uploads keep both; a second
+ *                     upload replaces the topology and keeps the switch.
+ *   glrtx_update_positions, glrtx_update_positions_device  pos: n_vert x 3 floats, in host memory or on the context's GPU (read on the context's stream, as
+ *                     glrtx_update_vertices_device reads its vertices).  One kernel writes each vertex's record into the context's vertex buffer -- the new
+ *                     position words, moved as integers, and the other twelve words from the topology's rest copy --, the rebuild runs on that buffer, and the
+ *                     call then takes exactly glrtx_update_vertices_device's path: the seal, the motion snapshot when glrtx_track_motion asks for one, the
+ *                     refit, the blocking read-back.  Afterwards every device scene buffer is byte for byte what glrtx_update_vertices(ctx, V) leaves, V being
+ *                     glrt_rebuild_normals applied to glrt_positions_to_vertices(rest, pos).  GLRTX_EINVAL, every buffer untouched: no topology, another
+ *                     n_vert, a NULL pointer.  The positions are not checked, as vertices are not.
+ *   glrtx_set_pose_normals  off by default.  While on, glrtx_pose, glrtx_pose_morph and glrtx_pose_dualquat run the rebuild on the vertex buffer between their
+ *                     deform kernel and the refit, with dense and with sparse sets.  The result is then what glrtx_update_vertices leaves for: the CPU pose or
+ *                     deform statement, followed by glrt_rebuild_normals with the topology of the RIG's rest pose (the caller passes that rest pose to both
+ *                     uploads).  A class with l == 0 keeps its posed normal.  Enabling without a topology is GLRTX_EINVAL.  While off, nothing about a pose
+ *                     changes, with or without a topology.
+ *   glrtx_debug_rebuild_normals  the three passes alone on host arrays on the current HIP device, no context, with a caller-made class map (any ids below
+ *                     n_vert) and flip bytes (zero or not), so that tests can hand in classes no weld would make.  vert_out gets the n_vert wire vertices.
+ *                     Refuses what glrt_rebuild_normals refuses: a class id >= n_vert, a corner out of range, a NULL pointer.
+ *   glrtx_debug_normals_burst  device time of the rebuild by itself, as glrtx_debug_skin_burst: the three passes on the context's vertex buffer.  GLRTX_EINVAL
+ *                     without a topology or before anything has filled the vertex buffer.
+ * Groups: no call.  Pose or update a member through glrtx_group_ctx(grp, i).  Spheres, the volume and partitioned contexts are not involved. */
+#define GLRTX_NORMALS_WELD_POSITIONS 1u
+#define GLRTX_NORMAL_CHUNK 256u
+int glrtx_upload_normal_topology(glrtx_ctx *ctx, const float *rest_vert, size_t n_vert, const float *tri, size_t n_tri, unsigned flags);
+int glrtx_update_positions(glrtx_ctx *ctx, const float *pos, size_t n_vert);
+int glrtx_update_positions_device(glrtx_ctx *ctx, const void *dev_pos, size_t n_vert);
+int glrtx_set_pose_normals(glrtx_ctx *ctx, int enable);
+int glrtx_debug_rebuild_normals(const float *vert_in, size_t n_vert, const float *tri, size_t n_tri, const uint32_t *class_of_vertex, const uint8_t *flip,
+                                float *vert_out);
+int glrtx_debug_normals_burst(glrtx_ctx *ctx, int reps, float *ms_per_launch);
+
 /* ---- Groups: the same device layer on several GPUs of one node, behind one handle and one host thread.
  * No reference counterpart (the reference is single-GPU); SURVEY.md 8(b) sketches glrtx_create(ctx**, device_ids, n) with a
  * gathering read_accum -- this is that, kept apart from the single-context calls.  Member i owns the 8-row stripes s with

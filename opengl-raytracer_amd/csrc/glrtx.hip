@@ -24,6 +24,7 @@
 #include "sahl.hip.h"
 #include "refit.hip.h"
 #include "skin.hip.h"
+#include "normals.hip.h"
 #include "query.hip.h"
 #include "features.hip.h"
 #include "denoise.hip.h"
@@ -34,6 +35,7 @@
 #include "bloom.hip.h"
 #include "../host/reproject_setup.h"
 #include "../host/morph_sparse.h"
+#include "../host/normal_topology.h"
 static_assert(glrtx::lbvh::kRotationPasses == GLRT_LBVH_ROTATION_PASSES, "device and CPU LBVH statements must run the same rotation sweeps");
 static_assert(glrtx::lbvh::kRebuildLeaves == GLRT_LBVH_REBUILD_LEAVES, "device and CPU LBVH statements must rebuild the same subtrees");
 
@@ -187,6 +189,14 @@ struct glrtx_ctx {
         skin::SparseArgs sdeform{};
         std::vector<float> wtab;
     } sk;
+    // Rebuilding normals (glrtx_upload_normal_topology; normals.hip.h), the scene's until the next glrtx_upload_scene: the topology's own copy of the rest
+    // vertices, the index (tri, cls, row, face), the two scratch arrays of a rebuild (fvec, cnrm) and a staging buffer for host positions.  have: a topology is
+    // uploaded; pose_on: glrtx_set_pose_normals.  `a`: the kernels' arguments but for the vertex buffer, which a call sets.
+    struct Normals {
+        DevBuf rest, tri, cls, row, face, fvec, cnrm, pos;
+        bool have = false, pose_on = false;
+        normals::Args a{};
+    } nm;
 
     // Presentation (glrtx_present_enable): frame seq of the ring goes to image seq % ring -- device image (written by the presenting pass on the context's stream),
     // then pinned host image (copied on `copy`, behind pass_done, ending with the image's event).  An image is taken for a frame only while it is FREE: released by the
@@ -306,6 +316,13 @@ void dev_free(DevBuf &b) {
 }
 
 void Plane::drop() { dev_free(buf); at = Shape{}; }
+
+// The normal topology and the pose switch are forgotten (the stream is idle, as for morph_drop)
+void normals_drop(glrtx_ctx *c) {
+    for (DevBuf *b : {&c->nm.rest, &c->nm.tri, &c->nm.cls, &c->nm.row, &c->nm.face, &c->nm.fvec, &c->nm.cnrm, &c->nm.pos}) dev_free(*b);
+    c->nm.have = c->nm.pose_on = false;
+    c->nm.a = normals::Args{};
+}
 
 // The rig's morph targets, dense or sparse, are forgotten (the stream is idle: every caller has synchronised it or runs behind a blocking call)
 void morph_drop(glrtx_ctx *c) {
@@ -2184,6 +2201,7 @@ void glrtx_destroy(glrtx_ctx *c) {
     dev_free(c->rf.ints); dev_free(c->rf.keys); dev_free(c->rf.vert);
     dev_free(c->sk.rest); dev_free(c->sk.rig); dev_free(c->sk.pose); dev_free(c->sk.dq); dev_free(c->sk.morph);
     dev_free(c->sk.srow); dev_free(c->sk.sent); dev_free(c->sk.swt);
+    normals_drop(c);
     dev_free(c->qwire); dev_free(c->qcounter); dev_free(c->qrays); dev_free(c->qhits);
     if (c->rf.slot_ev) (void)hipEventDestroy(c->rf.slot_ev);
     if (c->bvhWs.p) { (void)hipFree(c->bvhWs.p); c->bvhWs.p = nullptr; c->bvhWs.bytes = 0; }
@@ -2274,6 +2292,7 @@ int glrtx_upload_scene(glrtx_ctx *c, const float *vert, size_t n_vert, const flo
     dev_free(c->sk.dq);
     morph_drop(c);
     c->sk.n_bones = 0;
+    normals_drop(c);  // (glrtx_upload_normal_topology, glrtx_set_pose_normals: the topology was another scene's)
     c->st.stack_entries = stack_need;
     c->st.lds_bytes = lds_bytes_for(sc);
     c->st.n_tri = c->n_tri; c->st.n_fork = c->n_fork; c->st.n_mat = c->n_mat; c->st.n_light = c->n_light;
@@ -2345,7 +2364,171 @@ int update_check(glrtx_ctx *c, const void *vert, size_t n_vert, const char *fn) 
     return GLRTX_OK;
 }
 
+// ---- rebuilding normals (glrtx_upload_normal_topology, glrtx_update_positions, glrtx_set_pose_normals, glrtx_debug_rebuild_normals; normals.hip.h)
+static_assert(normals::kChunk == GLRTX_NORMAL_CHUNK && glrt_detail::kNormalChunk == GLRTX_NORMAL_CHUNK &&
+                  glrt_detail::kNormalsWeldPositions == GLRTX_NORMALS_WELD_POSITIONS,
+              "normals.hip.h, host/normal_topology.h and glrtx.h disagree");
+
+// The rebuild in place on a.vert: face vectors, class sums, the members' normal words
+void normals_launch(const normals::Args &a, hipStream_t stream) {
+    const auto grid = [](unsigned n) { return dim3((n + normals::kBlock - 1) / normals::kBlock); };
+    if (a.n_vert == 0) return;
+    if (a.n_tri > 0) hipLaunchKernelGGL(normals::face_kernel, grid(a.n_tri), dim3(normals::kBlock), 0, stream, a);
+    hipLaunchKernelGGL(normals::class_kernel, grid(a.n_classes), dim3(normals::kBlock), 0, stream, a);
+    hipLaunchKernelGGL(normals::vertex_kernel, grid(a.n_vert), dim3(normals::kBlock), 0, stream, a);
+}
+
+// The context's rebuild on its vertex buffer (which the caller has just written on the stream)
+void normals_run(glrtx_ctx *c) {
+    normals::Args a = c->nm.a;
+    a.vert = (unsigned *)c->rf.vert.p;
+    normals_launch(a, c->stream);
+}
+
+// The index of a checked mesh as the kernels read it: 16-byte triangle records {i0, i1, i2, flip as a sign mask}, and the face lists as 32-bit rows.  Returns
+// false when the lists hold 2^32 entries or more.
+bool normals_index(const float *tri, size_t n_tri, const uint32_t *cls, const uint8_t *flip, size_t n_vert, std::vector<uint4> &rec, std::vector<unsigned> &row,
+                   std::vector<uint32_t> &face) {
+    std::vector<uint64_t> row64;
+    glrt_detail::normal_face_lists(tri, n_tri, cls, n_vert, row64, face);
+    if (row64.back() >= ((uint64_t)1 << 32)) return false;
+    row.assign(row64.begin(), row64.end());
+    rec.resize(n_tri);
+    for (size_t t = 0; t < n_tri; t++)
+        rec[t] = make_uint4((unsigned)tri[4 * t], (unsigned)tri[4 * t + 1], (unsigned)tri[4 * t + 2], flip[t] ? 0x80000000u : 0u);
+    return true;
+}
+
+int normals_fault(glrtx_ctx *c, const glrt_detail::NormalFault &f, size_t n_vert, const char *fn) {
+    char why[256];
+    glrt_detail::normal_fault_message(f, n_vert, why, sizeof why);
+    return fail(c, GLRTX_EINVAL, "%s: %s", fn, why);
+}
+
+// glrtx_update_positions / _device behind their checks: the records from `dev_pos` and the rest copy, the rebuild, then glrtx_update_vertices_device's path
+int positions_run(glrtx_ctx *c, const void *dev_pos) {
+    const size_t n_vert = c->rf.n_vert;
+    if (n_vert > 0) {
+        hipLaunchKernelGGL(normals::positions_kernel, dim3((unsigned)((n_vert + normals::kBlock - 1) / normals::kBlock)), dim3(normals::kBlock), 0, c->stream,
+                           (const unsigned *)c->nm.rest.p, (const unsigned *)dev_pos, (unsigned *)c->rf.vert.p, (unsigned)n_vert);
+        normals_run(c);
+    }
+    HIP_TRY(c, hipGetLastError());
+    if (c->mt_on && c->mt_geom == glrtx_ctx::kMtCurrent)
+        if (int rc = motion_snapshot(c)) return rc;
+    return refit_run(c, c->rf.vert.p);
+}
+
+int positions_check(glrtx_ctx *c, const void *pos, size_t n_vert, const char *fn) {
+    if (int rc = update_check(c, pos, n_vert, fn)) return rc;
+    if (!c->nm.have) return fail(c, GLRTX_EINVAL, "%s: no normal topology uploaded (glrtx_upload_normal_topology)", fn);
+    return GLRTX_OK;
+}
+
 }  // namespace
+
+int glrtx_upload_normal_topology(glrtx_ctx *c, const float *rest_vert, size_t n_vert, const float *tri, size_t n_tri, unsigned flags) {
+    const char *fn = "glrtx_upload_normal_topology";
+    if (int rc = update_check(c, rest_vert, n_vert, fn)) return rc;
+    if (flags & ~GLRTX_NORMALS_WELD_POSITIONS) return fail(c, GLRTX_EINVAL, "%s: unknown flag bits 0x%x", fn, flags & ~GLRTX_NORMALS_WELD_POSITIONS);
+    if (!tri) return fail(c, GLRTX_EINVAL, "%s: NULL triangles", fn);
+    glrt_detail::NormalFault f;
+    if (!glrt_detail::normal_mesh_check(tri, n_tri, n_vert, f)) return normals_fault(c, f, n_vert, fn);
+    std::vector<uint32_t> cls(n_vert), face;
+    std::vector<uint8_t> flip(n_tri);
+    const size_t n_classes = glrt_detail::normal_weld(rest_vert, n_vert, flags, cls.data());
+    glrt_detail::normal_flips(rest_vert, tri, n_tri, flip.data());
+    std::vector<uint4> rec;
+    std::vector<unsigned> row;
+    if (!normals_index(tri, n_tri, cls.data(), flip.data(), n_vert, rec, row, face)) return fail(c, GLRTX_EINVAL, "%s: the face lists hold 2^32 entries or more", fn);
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));  // (as glrtx_upload_rig: the frees are ordered behind anything on the stream)
+    const bool pose_on = c->nm.have && c->nm.pose_on;  // (a topology that replaces one keeps the switch)
+    c->nm.have = c->nm.pose_on = false;  // (until every buffer is in place)
+    glrtx_ctx::Normals &N = c->nm;
+    if (int rc = dev_upload(c, N.rest, rest_vert, n_vert * normals::kVertexWords * sizeof(float))) return rc;
+    if (int rc = dev_upload(c, N.tri, rec.data(), rec.size() * sizeof(uint4))) return rc;
+    if (int rc = dev_upload(c, N.cls, cls.data(), cls.size() * sizeof(uint32_t))) return rc;
+    if (int rc = dev_upload(c, N.row, row.data(), row.size() * sizeof(unsigned))) return rc;
+    if (int rc = dev_upload(c, N.face, face.data(), face.size() * sizeof(uint32_t))) return rc;
+    if (int rc = ensure(c, N.fvec, n_tri * sizeof(float4))) return rc;
+    if (int rc = ensure(c, N.cnrm, n_classes * sizeof(float4))) return rc;
+    N.a = normals::Args{(const uint4 *)N.tri.p, (const unsigned *)N.cls.p, (const unsigned *)N.row.p, (const unsigned *)N.face.p, nullptr, (float4 *)N.fvec.p,
+                        (float4 *)N.cnrm.p, (unsigned)n_vert, (unsigned)n_tri, (unsigned)n_classes};
+    N.have = true;
+    N.pose_on = pose_on;
+    return GLRTX_OK;
+}
+
+int glrtx_update_positions(glrtx_ctx *c, const float *pos, size_t n_vert) {
+    if (int rc = positions_check(c, pos, n_vert, "glrtx_update_positions")) return rc;
+    seal_feed(c);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (int rc = ensure(c, c->rf.vert, n_vert * normals::kVertexWords * sizeof(float))) return rc;
+    if (int rc = ensure(c, c->nm.pos, n_vert * 3 * sizeof(float))) return rc;
+    HIP_TRY(c, hipMemcpyAsync(c->nm.pos.p, pos, n_vert * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    return positions_run(c, c->nm.pos.p);
+}
+
+int glrtx_update_positions_device(glrtx_ctx *c, const void *dev_pos, size_t n_vert) {
+    if (int rc = positions_check(c, dev_pos, n_vert, "glrtx_update_positions_device")) return rc;
+    seal_feed(c);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (int rc = ensure(c, c->rf.vert, n_vert * normals::kVertexWords * sizeof(float))) return rc;
+    return positions_run(c, dev_pos);
+}
+
+int glrtx_set_pose_normals(glrtx_ctx *c, int enable) {
+    if (!c) return GLRTX_EINVAL;
+    if (enable && (!c->have_scene || !c->nm.have))
+        return fail(c, GLRTX_EINVAL, "glrtx_set_pose_normals: no normal topology uploaded (glrtx_upload_normal_topology)");
+    c->nm.pose_on = enable != 0;
+    return GLRTX_OK;
+}
+
+int glrtx_debug_rebuild_normals(const float *vert_in, size_t n_vert, const float *tri, size_t n_tri, const uint32_t *class_of_vertex, const uint8_t *flip,
+                                float *vert_out) {
+    const char *fn = "glrtx_debug_rebuild_normals";
+    if ((n_vert > 0 && (!vert_in || !class_of_vertex || !vert_out)) || (n_tri > 0 && !flip)) return fail(nullptr, GLRTX_EINVAL, "%s: NULL buffer", fn);
+    glrt_detail::NormalFault f;
+    if (!glrt_detail::normal_mesh_check(tri, n_tri, n_vert, f) || !glrt_detail::normal_class_check(class_of_vertex, n_vert, f))
+        return normals_fault(nullptr, f, n_vert, fn);
+    if (n_vert == 0) return GLRTX_OK;
+    std::vector<uint4> rec;
+    std::vector<unsigned> row;
+    std::vector<uint32_t> face;
+    if (!normals_index(tri, n_tri, class_of_vertex, flip, n_vert, rec, row, face)) return fail(nullptr, GLRTX_EINVAL, "%s: the face lists hold 2^32 entries or more", fn);
+    const size_t bytes = n_vert * normals::kVertexWords * sizeof(float);
+    DebugScratch s;
+    normals::Args a{};
+    a.tri = s.alloc<uint4>(std::max<size_t>(rec.size(), 1) * sizeof(uint4), rec.empty() ? nullptr : rec.data());
+    a.cls = s.alloc<unsigned>(n_vert * sizeof(unsigned), class_of_vertex);
+    a.row = s.alloc<unsigned>(row.size() * sizeof(unsigned), row.data());
+    a.face = s.alloc<unsigned>(std::max<size_t>(face.size(), 1) * sizeof(unsigned), face.empty() ? nullptr : face.data());
+    a.vert = s.alloc<unsigned>(bytes, vert_in);
+    a.fvec = s.alloc<float4>(std::max<size_t>(n_tri, 1) * sizeof(float4));
+    a.cnrm = s.alloc<float4>((row.size() - 1) * sizeof(float4));
+    a.n_vert = (unsigned)n_vert; a.n_tri = (unsigned)n_tri; a.n_classes = (unsigned)(row.size() - 1);
+    if (s.ok()) {
+        normals_launch(a, 0);
+        s.e = hipGetLastError();
+    }
+    s.sync();
+    s.download(vert_out, a.vert, bytes);
+    return s.result(GLRTX_OK, fn);
+}
+
+// Device time of the rebuild by itself, as glrtx_debug_skin_burst: the three passes on the context's vertex buffer, whose normal words then hold the rebuilt
+// normals of the positions that are there (after a glrtx_update_positions or a pose under glrtx_set_pose_normals: exactly what they hold already).
+int glrtx_debug_normals_burst(glrtx_ctx *c, int reps, float *ms_per_launch) {
+    const char *fn = "glrtx_debug_normals_burst";
+    if (!c || !ms_per_launch || reps < 1) return GLRTX_EINVAL;
+    if (!c->have_scene || !c->nm.have || c->rf.vert.bytes < c->rf.n_vert * normals::kVertexWords * sizeof(float))
+        return fail(c, GLRTX_EINVAL, "%s: no normal topology uploaded, or no vertices in the vertex buffer yet", fn);
+    seal_feed(c);
+    HIP_TRY(c, hipSetDevice(c->device));
+    return burst_time(c, reps, ms_per_launch, [&] { normals_run(c); return GLRTX_OK; });
+}
 
 int glrtx_update_vertices(glrtx_ctx *c, const float *vert, size_t n_vert) {
     if (int rc = update_check(c, vert, n_vert, "glrtx_update_vertices")) return rc;
@@ -2434,6 +2617,7 @@ int glrtx_pose(glrtx_ctx *c, const float *matrices, int n_bones) {
     if (int rc = ensure(c, c->rf.vert, n_vert * skin::kVertexWords * sizeof(float))) return rc;
     HIP_TRY(c, hipMemcpyAsync(c->sk.pose.p, matrices, (size_t)n_bones * 12 * sizeof(float), hipMemcpyHostToDevice, c->stream));
     skin_launch(skin::Args{(const unsigned *)c->sk.rest.p, (const uint4 *)c->sk.rig.p, (const float4 *)c->sk.pose.p, (unsigned *)c->rf.vert.p, n_vert}, c->stream);
+    if (c->nm.pose_on) normals_run(c);  // (glrtx_set_pose_normals: the rebuild between the kernel and the refit)
     HIP_TRY(c, hipGetLastError());
     if (c->mt_on && c->mt_geom == glrtx_ctx::kMtCurrent)  // (glrtx_update_vertices_device's path from here)
         if (int rc = motion_snapshot(c)) return rc;
@@ -2592,6 +2776,7 @@ int deform_pose(glrtx_ctx *c, const float *bone_data, int n_bones, const float *
     }
     c->sk.deform_mode = mode;
     c->sk.last_sparse = sparse;
+    if (c->nm.pose_on) normals_run(c);  // (glrtx_set_pose_normals)
     HIP_TRY(c, hipGetLastError());
     if (c->mt_on && c->mt_geom == glrtx_ctx::kMtCurrent)  // (glrtx_pose's path from here)
         if (int rc = motion_snapshot(c)) return rc;

@@ -71,7 +71,9 @@ static void usage(const char *exe) {
                 "                          --extensions or --save-every-frame).  Morph targets: a top-level \"targets\": [{\"shape\": i, \"file\": \"x.obj\"}, ...] and per step\n"
                 "                          \"weights\": [[target, w], ...] blend the shapes' vertices towards the targets' before the pose (glrtx_pose_morph), at most 64\n"
                 "                          targets; with a top-level \"sparse_targets\": true at most 1024, each kept as the list of the vertices it moves\n"
-                "                          (glrtx_upload_morph_targets_sparse)\n"
+                "                          (glrtx_upload_morph_targets_sparse); a top-level \"rebuild_normals\": true rebuilds every step's shading normals\n"
+                "                          from its moved faces (glrtx_set_pose_normals), welded by position and normal or, with \"weld\": \"positions\", by\n"
+                "                          position alone\n"
                 "      --carry-history     with --animate: keep the accumulator across the steps by motion-aware reprojection (glrtx_reproject_motion) instead of clearing\n"
                 "                          it; moments are tracked, so --denoise-variance composes (not with --denoise)\n", exe);
 }

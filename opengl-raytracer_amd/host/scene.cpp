@@ -190,6 +190,15 @@ void Scene::parseAnimation(const std::string &filename) {
     morphSparse_ = false; morphOffsets_.clear(); morphVertex_.clear(); morphSparseDeltas_.clear();
     if (!json["sparse_targets"].is_null() && !json["sparse_targets"].is_bool()) GLRT_FatalError("animation: \"sparse_targets\" is not true or false");
     morphSparse_ = json["sparse_targets"].bool_value();
+    if (!json["rebuild_normals"].is_null() && !json["rebuild_normals"].is_bool()) GLRT_FatalError("animation: \"rebuild_normals\" is not true or false");
+    rebuildNormals_ = json["rebuild_normals"].bool_value();
+    normalFlags_ = 0;
+    if (!json["weld"].is_null()) {
+        const std::string weld = json["weld"].string_value();
+        if (!json["weld"].is_string() || (weld != "positions" && weld != "normals"))
+            GLRT_FatalError("animation: \"weld\" is not \"positions\" or \"normals\"");
+        if (weld == "positions") normalFlags_ = GLRT_NORMALS_WELD_POSITIONS;
+    }
     auto index_of = [](const Json &x, size_t n) { const double v = x.number_value(); return x.is_number() && v >= 0.0 && v < (double)n && v == std::floor(v); };
     if (!json["targets"].is_null()) {  // morph targets: one OBJ a target, the deltas of its shape's vertices
         if (!json["targets"].is_array()) GLRT_FatalError("animation: \"targets\" is not an array");
@@ -272,6 +281,7 @@ void Scene::parseAnimation(const std::string &filename) {
     GLRT_Info("Animation: %zu steps, %zu shapes", animation_.size(), n_shapes);
     if (n_targets && morphSparse_) GLRT_Info("Animation: %zu sparse morph targets, %zu entries", n_targets, morphVertex_.size());
     else if (n_targets) GLRT_Info("Animation: %zu morph targets", n_targets);
+    if (rebuildNormals_) GLRT_Info("Animation: normals rebuilt from the moved faces, welded by %s", normalFlags_ ? "position" : "position and normal");
 }
 
 void Scene::setBuffers(int w, int h, const float view[16], const float proj[16], float aperture, float focal,
@@ -562,6 +572,22 @@ struct SceneMorphSparseProbe {
     }
 };
 }  // namespace glrt
+
+// Normals probe: what an animation file says about rebuilding normals.  out = {rebuild_normals (0 / 1), the topology flags}.
+namespace glrt {
+struct SceneNormalsProbe {
+    static int run(const char *json, const char *animation, int out[2]) {
+        Scene sc;
+        sc.parse(json);
+        sc.parseAnimation(animation);
+        out[0] = sc.rebuildNormals_ ? 1 : 0;
+        out[1] = (int)sc.normalFlags_;
+        return 0;
+    }
+};
+}  // namespace glrt
+
+extern "C" GLRT_API int glrt_scene_normals_probe(const char *json, const char *animation, int out[2]) { return glrt::SceneNormalsProbe::run(json, animation, out); }
 
 extern "C" GLRT_API int glrt_scene_morph_sparse_probe(const char *json, const char *animation, long long counts[5], int *target_shape, uint64_t *offsets,
                                                       uint32_t *vertex, float *deltas, float *weights) {

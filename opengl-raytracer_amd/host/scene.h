@@ -81,6 +81,11 @@ public:
     // parser builds the sparse set directly from each target OBJ: a vertex of the shape gets an entry iff its delta passes glrt_morph_sparsify's rule (some
     // component with a non-zero exponent field); the dense targets x vertices x 6 array is never allocated and morphDeltas() stays empty.  Window uploads the
     // set with glrtx_upload_morph_targets_sparse.  A file without the key parses, uploads and renders as before.
+    //
+    // Rebuilding normals (include/glrtx.h "Rebuilding normals").  With a top-level "rebuild_normals": true Window uploads the normal topology of the scene's
+    // vertices beside the rig and sets glrtx_set_pose_normals before the first step: every step's normals are rebuilt from its moved faces.  An optional
+    // "weld": "positions" welds by position alone (GLRTX_NORMALS_WELD_POSITIONS); "weld": "normals" is the default's name.  Anything but true or false, and any
+    // other "weld", is a FatalError naming the key.  A file without the keys renders as before.
     struct AnimationStep {
         std::vector<float> matrices;  // numShapes() x 12
         std::vector<float> weights;   // numMorphTargets()
@@ -98,6 +103,9 @@ public:
     const std::vector<uint64_t> &morphOffsets() const { return morphOffsets_; }
     const std::vector<uint32_t> &morphVertex() const { return morphVertex_; }
     const std::vector<float> &morphSparseDeltas() const { return morphSparseDeltas_; }
+    // "rebuild_normals": true, and the flags "weld" asks glrtx_upload_normal_topology for
+    bool rebuildNormals() const { return rebuildNormals_; }
+    unsigned normalTopologyFlags() const { return normalFlags_; }
     // the first vertex of entry i of the JSON "scene" array (an entry without geometry owns none: its range is empty); i == numShapes(): the vertex count
     size_t shapeFirstVertex(size_t i) const { return i < shapeFirstVertex_.size() ? shapeFirstVertex_[i] : vertices.size(); }
 
@@ -129,6 +137,8 @@ private:
     std::vector<uint64_t> morphOffsets_;
     std::vector<uint32_t> morphVertex_;
     std::vector<float> morphSparseDeltas_;
+    bool rebuildNormals_ = false;  // "rebuild_normals": true
+    unsigned normalFlags_ = 0;     // "weld": "positions" -> GLRTX_NORMALS_WELD_POSITIONS
     VolumeGrid volDensity_, volTemperature_;  // volumeSpecs_[0]'s files (only with enableVolume(true)); only the first volume is rendered (window.cpp:271-286)
 
     friend class Window;
@@ -137,6 +147,7 @@ private:
     friend struct SceneAnimationProbe;
     friend struct SceneMorphProbe;
     friend struct SceneMorphSparseProbe;
+    friend struct SceneNormalsProbe;
 };
 
 // OBJ triangles the way the reference's loader yields them (trimesh.cpp:113-191): three fresh

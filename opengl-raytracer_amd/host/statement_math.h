@@ -1,5 +1,6 @@
 // statement_math.h -- what the CPU statements of the device's passes share (host/query.cpp, features.cpp, denoise.cpp, variance.cpp, reproject.cpp,
-// reproject_motion.cpp, tonemap.cpp, bloom.cpp, reweight.cpp, and the device-build statements in bvh.cpp): the denormal mode they run under and the small fp32 helpers they are written in.  Internal
+// reproject_motion.cpp, tonemap.cpp, bloom.cpp, reweight.cpp, normals.cpp, and the device-build statements in bvh.cpp; normal_topology.h, which the device
+// library compiles as well, takes FlushDenormals and dot3 from here): the denormal mode they run under and the small fp32 helpers they are written in.  Internal
 // to the host library; the kernels (csrc/) state the same helpers in their own source and share none of this.  Every operation is one correctly rounded IEEE
 // operation in the order written (the callers are compiled with -ffp-contract=off; lp_exp's fmaf calls are the only fused ones).
 #pragma once

@@ -282,6 +282,12 @@ void Window::animate() {
             GLRT_FatalError("glrtx_upload_morph_targets_sparse: %s", glrtx_last_error(c0));
     } else if (n_targets > 0 && glrtx_upload_morph_targets(c0, scene->morphDeltas().data(), n_targets, n_vert) != GLRTX_OK)
         GLRT_FatalError("glrtx_upload_morph_targets: %s", glrtx_last_error(c0));
+    if (scene->rebuildNormals()) {  // ("rebuild_normals": true: the topology of the rest pose beside the rig, and the switch before the first step)
+        if (glrtx_upload_normal_topology(c0, &scene->vertices[0].pos[0], n_vert, &scene->triangles[0].indices[0], scene->triangles.size(),
+                                         scene->normalTopologyFlags()) != GLRTX_OK)
+            GLRT_FatalError("glrtx_upload_normal_topology: %s", glrtx_last_error(c0));
+        if (glrtx_set_pose_normals(c0, 1) != GLRTX_OK) GLRT_FatalError("glrtx_set_pose_normals: %s", glrtx_last_error(c0));
+    }
     float view0[16], proj0[16];
     std::memcpy(view0, scene->viewM, sizeof view0);
     std::memcpy(proj0, scene->projM, sizeof proj0);

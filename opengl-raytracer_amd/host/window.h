@@ -80,7 +80,8 @@ public:
     // frames in bursts of framesInFlight (through glrtx_render_moments when moments are tracked: carryHistory or setDenoiseVariance); then the image.
     // Not with several devices, setAdaptive*, setReweight, extension or volume scenes, one image per frame, or carryHistory with setDenoise (no moments).
     // A file with morph targets: glrtx_upload_morph_targets once after glrtx_upload_rig -- glrtx_upload_morph_targets_sparse for a file with "sparse_targets":
-    // true --, and every step's pose is glrtx_pose_morph with the step's weights.
+    // true --, and every step's pose is glrtx_pose_morph with the step's weights.  A file with "rebuild_normals": true: glrtx_upload_normal_topology of the
+    // scene's vertices and triangles after them, then glrtx_set_pose_normals(1), so that every step's pose rebuilds the normals in front of its refit.
     void setAnimation(const std::string &file, bool carryHistory) { animationFile_ = file; carryHistory_ = carryHistory; }
     // wall-clock ms PER FRAME between the last two waits for the device, averaged over the frames issued in between (with one PNG per run: the whole run, cold first
     // launches included; with --save-every-frame: the whole run, PNG writing included).  The device's own time of the last launch is glrtx_stats.kernel_ms_last.

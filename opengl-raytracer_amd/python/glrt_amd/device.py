@@ -175,7 +175,9 @@ EXPORTS = ["glrtx_abi_version", "glrtx_create", "glrtx_destroy", "glrtx_last_err
            "glrtx_track_cascades", "glrtx_render_cascades", "glrtx_read_cascades", "glrtx_reweight", "glrtx_debug_fold_cascades", "glrtx_debug_reweight",
            "glrtx_debug_reweight_burst", "glrtx_upload_rig", "glrtx_pose", "glrtx_debug_skin", "glrtx_debug_skin_burst",
            "glrtx_upload_morph_targets", "glrtx_pose_morph", "glrtx_pose_dualquat", "glrtx_debug_deform", "glrtx_debug_deform_burst",
-           "glrtx_upload_morph_targets_sparse", "glrtx_debug_deform_sparse"]
+           "glrtx_upload_morph_targets_sparse", "glrtx_debug_deform_sparse",
+           "glrtx_upload_normal_topology", "glrtx_update_positions", "glrtx_update_positions_device", "glrtx_set_pose_normals",
+           "glrtx_debug_rebuild_normals", "glrtx_debug_normals_burst"]
 
 SCENE_BUFFERS = ("nodes", "cnodes", "nrms", "lights", "vine", "root")  # glrtx_debug_read_scene's `which`, in order (GLRTX_SCENE_*)
 
@@ -367,6 +369,16 @@ def lib():
             u32p, u64p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
             L.glrtx_upload_morph_targets_sparse.argtypes = [vp, u64p, u32p, fp, C.c_int, C.c_size_t]
             L.glrtx_debug_deform_sparse.argtypes = [fp, C.c_size_t, i32p, fp, fp, C.c_int, C.c_int, u64p, u32p, fp, fp, C.c_int, fp]
+        except AttributeError:
+            pass
+        try:  # (additive to ABI 10 as well: rebuilding normals)
+            u8p = C.POINTER(C.c_uint8)
+            L.glrtx_upload_normal_topology.argtypes = [vp, fp, C.c_size_t, fp, C.c_size_t, C.c_uint]
+            L.glrtx_update_positions.argtypes = [vp, fp, C.c_size_t]
+            L.glrtx_update_positions_device.argtypes = [vp, vp, C.c_size_t]
+            L.glrtx_set_pose_normals.argtypes = [vp, C.c_int]
+            L.glrtx_debug_rebuild_normals.argtypes = [fp, C.c_size_t, fp, C.c_size_t, C.POINTER(C.c_uint32), u8p, fp]
+            L.glrtx_debug_normals_burst.argtypes = [vp, C.c_int, C.POINTER(C.c_float)]
         except AttributeError:
             pass
         _lib = L
@@ -710,6 +722,20 @@ def debug_deform_sparse(rest, bones, weights, bone_data, mode=0, offsets=None, v
     return out
 
 
+def debug_rebuild_normals(vert, tri, class_of_vertex, flip):
+    """glrtx_debug_rebuild_normals on the current device: the rebuild's three passes alone -- vert (n, 15) float32, tri (n_tri, 4) float32, a class id a vertex
+    (n,) uint32 (any ids below n) and a flip byte a triangle (n_tri,) uint8.  Returns the vertices (n, 15) float32 with their normal words rebuilt."""
+    from .host import _ptr, normals_arrays
+    L = lib()
+    v, t, c, f = normals_arrays("debug_rebuild_normals", vert, tri, class_of_vertex, flip)
+    out = np.zeros_like(v)
+    rc = L.glrtx_debug_rebuild_normals(_ptr(v, C.c_float), v.shape[0], _ptr(t, C.c_float), t.shape[0], _ptr(c, C.c_uint32), _ptr(f, C.c_uint8),
+                                       _ptr(out, C.c_float))
+    if rc != 0:
+        raise GlrtxError(rc, L.glrtx_last_error(None).decode())
+    return out
+
+
 def _host_vertices(v):
     """A numpy vertex array for glrtx_update_vertices: float32, shape (n, 15) or flat (or the scene's (n * 5, 3) texels).  Returns (array, n)."""
     a = np.asarray(v)
@@ -819,6 +845,49 @@ class Device:
         else:
             a, n = _host_vertices(v)
             self._ck(self.L.glrtx_update_vertices(self.h, _fp(a), n))
+
+    def upload_normal_topology(self, rest, tri, flags=0):
+        """glrtx_upload_normal_topology: the weld classes, orientation and face lists of the rest vertices (n, 15) float32 (or the scene's vertex texels) and the
+        wire triangles (n_tri, 4) float32, kept on the device with a copy of the rest vertices for update_positions() and set_pose_normals().  flags: 0, or
+        host.NORMALS_WELD_POSITIONS to weld by position alone."""
+        r = _f32(rest).reshape(-1, 15)
+        t = _f32(tri).reshape(-1, 4)
+        self._ck(self.L.glrtx_upload_normal_topology(self.h, _fp(r), r.shape[0], _fp(t), t.shape[0], int(flags)))
+
+    def update_positions(self, p):
+        """New positions alone for the uploaded scene's vertices; the normals are rebuilt on the device and the tree refitted (glrtx_update_positions): a numpy
+        array (n, 3) or flat is taken from host memory, a contiguous float32 torch tensor on the context's GPU is read on the context's stream
+        (glrtx_update_positions_device), as update_vertices does.  Needs upload_normal_topology.  Returns when the refit has run."""
+        if type(p).__module__.startswith("torch"):
+            import torch
+            idx = self.device_id if self.device_id >= 0 else torch.cuda.current_device()
+            if p.dtype != torch.float32:
+                raise TypeError(f"update_positions: float32 positions expected, got {p.dtype}")
+            if p.device.type != "cuda" or p.device.index != idx:
+                raise ValueError(f"update_positions: the tensor is on {p.device}, the context on cuda:{idx}")
+            if not p.is_contiguous():
+                raise ValueError("update_positions: the tensor is not contiguous")
+            if not (p.dim() == 1 and p.numel() % 3 == 0) and not (p.dim() == 2 and p.shape[1] == 3):
+                raise ValueError(f"update_positions: shape {tuple(p.shape)} is not (n, 3) or flat n * 3")
+            self._ck(self.L.glrtx_update_positions_device(self.h, C.c_void_p(p.data_ptr()), p.numel() // 3))
+        else:
+            a = np.asarray(p)
+            if a.dtype != np.float32:
+                raise TypeError(f"update_positions: float32 positions expected, got {a.dtype}")
+            if a.size % 3 or a.ndim > 2 or (a.ndim == 2 and a.shape[1] != 3):
+                raise ValueError(f"update_positions: shape {a.shape} is not (n, 3) or flat n * 3")
+            a = np.ascontiguousarray(a)
+            self._ck(self.L.glrtx_update_positions(self.h, _fp(a), a.size // 3))
+
+    def set_pose_normals(self, enable=True):
+        """glrtx_set_pose_normals: while on, pose / pose_morph / pose_dualquat rebuild the normals between their kernel and the refit."""
+        self._ck(self.L.glrtx_set_pose_normals(self.h, 1 if enable else 0))
+
+    def normals_burst_ms(self, reps=20) -> float:
+        """glrtx_debug_normals_burst: device ms of one rebuild (its three passes on the vertex buffer), from `reps` back to back."""
+        ms = C.c_float(0)
+        self._ck(self.L.glrtx_debug_normals_burst(self.h, int(reps), C.byref(ms)))
+        return float(ms.value)
 
     def upload_rig(self, rest, bones, weights, n_bones):
         """glrtx_upload_rig: the rest pose (n, 15) float32 (or the scene's vertex texels), four bone indices (n, 4) int32 and four weights (n, 4) float32 a

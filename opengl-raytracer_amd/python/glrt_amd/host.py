@@ -61,6 +61,10 @@ def lib():
         L.glrt_deform_vertices_sparse.argtypes = [fp, C.c_size_t, C.POINTER(C.c_int32), fp, fp, C.c_int, C.c_int, u64p, u32p, fp, fp, C.c_int, fp]
         L.glrt_morph_sparsify.argtypes = [fp, C.c_int, C.c_size_t, u64p, u32p, fp]
         L.glrt_dualquat_from_matrix.argtypes = [fp, fp]
+        u8p = C.POINTER(C.c_uint8)
+        L.glrt_normal_topology.argtypes = [fp, C.c_size_t, fp, C.c_size_t, C.c_uint, u32p, u8p, C.POINTER(C.c_size_t)]
+        L.glrt_rebuild_normals.argtypes = [fp, C.c_size_t, fp, C.c_size_t, u32p, u8p]
+        L.glrt_positions_to_vertices.argtypes = [fp, fp, C.c_size_t, fp]
         L.glrt_dualquat_from_matrix.restype = None
         L.glrt_look_at.argtypes = [fp, fp, fp, fp]
         L.glrt_perspective.argtypes = [C.c_float, C.c_float, C.c_float, C.c_float, fp]
@@ -512,6 +516,63 @@ def dualquat_from_matrix(m):
     a = _f32(m).reshape(12)
     out = np.zeros(8, np.float32)
     lib().glrt_dualquat_from_matrix(_fp(a), _fp(out))
+    return out
+
+
+NORMALS_WELD_POSITIONS = 1  # GLRT_NORMALS_WELD_POSITIONS
+NORMAL_CHUNK = 256  # GLRT_NORMAL_CHUNK
+
+
+def normals_arrays(name, vert, tri, class_of_vertex=None, flip=None):
+    """The arrays of a normal rebuild as the C calls take them: vert (n, 15) float32, tri (n_tri, 4) float32 and, if given, the class map (n,) uint32 and the
+    flip bytes (n_tri,) uint8.  Only the shapes are looked at here.  Bits are kept: float32 input is not converted."""
+    v = _f32(vert).reshape(-1, 15)
+    t = _f32(tri).reshape(-1, 4)
+    if class_of_vertex is None:
+        return v, t
+    c = np.ascontiguousarray(class_of_vertex, dtype=np.uint32).reshape(-1)
+    f = np.ascontiguousarray(flip, dtype=np.uint8).reshape(-1)
+    if c.size != v.shape[0] or f.size != t.shape[0]:
+        raise ValueError(f"{name}: {v.shape[0]} vertices with {c.size} class ids, {t.shape[0]} triangles with {f.size} flip bytes")
+    return v, t, c, f
+
+
+def _ptr(a, ctype):
+    return a.ctypes.data_as(C.POINTER(ctype)) if a.size else None
+
+
+def normal_topology(rest, tri, flags=0):
+    """glrt_normal_topology (include/glrtx.h "Rebuilding normals", TOPOLOGY): the weld classes of the rest vertices (n, 15) and the orientation of the wire
+    triangles (n_tri, 4).  Returns (class_of_vertex (n,) uint32, flip (n_tri,) uint8, n_classes)."""
+    v, t = normals_arrays("normal_topology", rest, tri)
+    c, f, n = np.zeros(v.shape[0], np.uint32), np.zeros(t.shape[0], np.uint8), C.c_size_t(0)
+    rc = lib().glrt_normal_topology(_ptr(v, C.c_float), v.shape[0], _ptr(t, C.c_float), t.shape[0], int(flags), _ptr(c, C.c_uint32), _ptr(f, C.c_uint8), C.byref(n))
+    if rc != 0:
+        raise RuntimeError(f"glrt_normal_topology failed: {rc}")
+    return c, f, int(n.value)
+
+
+def rebuild_normals(vert, tri, class_of_vertex, flip):
+    """glrt_rebuild_normals: the CPU statement of Device.update_positions, of a pose under Device.set_pose_normals and of device.debug_rebuild_normals
+    (include/glrtx.h "Rebuilding normals", REBUILD).  Returns a copy of vert (n, 15) float32 with its normal words rebuilt from its position words."""
+    v, t, c, f = normals_arrays("rebuild_normals", vert, tri, class_of_vertex, flip)
+    out = v.copy()
+    rc = lib().glrt_rebuild_normals(_ptr(out, C.c_float), out.shape[0], _ptr(t, C.c_float), t.shape[0], _ptr(c, C.c_uint32), _ptr(f, C.c_uint8))
+    if rc != 0:
+        raise RuntimeError(f"glrt_rebuild_normals failed: {rc}")
+    return out
+
+
+def positions_to_vertices(rest, pos):
+    """glrt_positions_to_vertices: the rest records (n, 15) with their position words replaced by pos (n, 3), moved as integers."""
+    r = _f32(rest).reshape(-1, 15)
+    p = _f32(pos).reshape(-1, 3)
+    if p.shape[0] != r.shape[0]:
+        raise ValueError(f"positions_to_vertices: {r.shape[0]} vertices, {p.shape[0]} positions")
+    out = np.zeros_like(r)
+    rc = lib().glrt_positions_to_vertices(_ptr(r, C.c_float), _ptr(p, C.c_float), r.shape[0], _ptr(out, C.c_float))
+    if rc != 0:
+        raise RuntimeError(f"glrt_positions_to_vertices failed: {rc}")
     return out
 
 
