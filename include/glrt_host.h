@@ -281,6 +281,33 @@ int glrt_normal_topology(const float *rest_vert, size_t n_vert, const float *tri
 int glrt_rebuild_normals(float *vert_inout, size_t n_vert, const float *tri, size_t n_tri, const uint32_t *class_of_vertex, const uint8_t *flip);
 int glrt_positions_to_vertices(const float *rest_vert, const float *pos, size_t n_vert, float *vert_out);
 
+/* Textures: the CPU statements of the device's texture lookup (glrtx_upload_textures / glrtx_debug_texture_lookup, include/glrtx.h "Textures": the set, the
+ * formats, the coordinate and filter rules are there), bit for bit (host/texture.cpp; tests/texture_math.py states them in numpy).  glrt_texture is
+ * glrtx_texture's layout and the GLRT_TEX_* values are the GLRTX_TEX_* ones.  The arithmetic runs with denormals flushed (MXCSR FTZ | DAZ, restored on return).
+ *   glrt_texture_lookup   rgb_out[3i..3i+2] = the lookup in texture which[i] at (st[2i], st[2i+1]).
+ *   glrt_srgb_table       the 256 floats GLRT_TEX_RGBA8_SRGB decodes a byte with.
+ *   glrt_texture_albedo   what plane A of the feature pass holds (rgb) for hit records as plane G stores them (hits: n x {wire triangle as int32 bits, u, v, 0}),
+ *                         on the wire-format scene with material m bound to texture material_texture[m] (-1: none): the lookup at the interpolated
+ *                         coordinates for a bound diffuse material, param0 for an unbound diffuse one, {1, 1, 1} otherwise and on a miss.
+ * GLRT_HOST_EINVAL: a NULL pointer with something to read or write, or a set glrtx_upload_textures refuses.  GLRT_HOST_EINDEX: a texture, triangle, vertex or
+ * material index out of range, or a binding on a material that is not diffuse. */
+#define GLRT_TEX_RGBA32F 0
+#define GLRT_TEX_RGBA8_UNORM 1
+#define GLRT_TEX_RGBA8_SRGB 2
+#define GLRT_TEX_REPEAT 0
+#define GLRT_TEX_CLAMP 1
+#define GLRT_TEX_NEAREST 0
+#define GLRT_TEX_BILINEAR 1
+typedef struct glrt_texture {
+    uint64_t offset;
+    int32_t width, height, format, wrap_s, wrap_t, filter;
+} glrt_texture;
+int glrt_texture_lookup(const glrt_texture *tex, size_t n_tex, const void *texels, size_t texel_bytes, const int32_t *which, const float *st, size_t n,
+                        float *rgb_out);
+const float *glrt_srgb_table(void);
+int glrt_texture_albedo(const float *vert, size_t n_vert, const float *tri, size_t n_tri, const float *mat, size_t n_mat, const glrt_texture *tex, size_t n_tex,
+                        const void *texels, size_t texel_bytes, const int32_t *material_texture, const float *hits, size_t n, float *rgb_out);
+
 void glrt_look_at(const float eye[3], const float center[3], const float up[3], float out[16]);
 void glrt_perspective(float fovy_deg, float aspect, float z_near, float z_far, float out[16]);
 void glrt_mat4_mul(const float a[16], const float b[16], float out[16]);

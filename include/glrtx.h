@@ -1115,6 +1115,68 @@ int glrtx_debug_rebuild_normals(const float *vert_in, size_t n_vert, const float
                                 float *vert_out);
 int glrtx_debug_normals_burst(glrtx_ctx *ctx, int reps, float *ms_per_launch);
 
+/* ---- Textures: a diffuse material's albedo looked up in an image at the hit's texture coordinates (no reference counterpart -- the reference's Vertex carries
+ * uv and its Material ends in texIds, and nothing reads either; off unless called: no other call's behaviour changes).  gfx950 has no image-sampling path: a
+ * lookup is address arithmetic and up to four gathers (csrc/texture.hip.h).  Only the extension megakernel shades with textures: while a set is bound, launches
+ * run on the persistent megakernel exactly as with analytic spheres uploaded (variant_last 1, GLRTX_FALLBACK_EXTENSIONS).  PINNED through the reference all the
+ * same: a texture whose texels are constant over each triangle renders, bit for bit, the image of the same geometry with one diffuse material a triangle.
+ *
+ * Arithmetic.  Every operation is one correctly rounded fp32 operation in the order written, unfused; denormals are zeros of their sign into and out of every
+ * operation.  Three statements agree bit for bit: tex_lookup (csrc/texture.hip.h), glrt_texture_lookup (include/glrt_host.h), tests/texture_math.py.
+ *
+ * SET.  n_tex <= GLRTX_TEX_MAX = 4096 descriptors over one texel blob.  A descriptor: the byte offset of its first texel in the blob (a multiple of 16), width
+ * and height in 1 .. GLRTX_TEX_MAX_DIM = 16384, a format, a wrap mode per axis, a filter.  Texels run row-major, x fastest; row 0 is t = 0.  No mip levels: a path
+ * tracer without ray differentials has no footprint to choose one by (the volume lookups read textureLod(.., 0) for the same reason).
+ * FORMATS.  GLRTX_TEX_RGBA32F: four floats a texel.  GLRTX_TEX_RGBA8_UNORM: four bytes, a channel is (float)b / 255.0f (one IEEE quotient).
+ *   GLRTX_TEX_RGBA8_SRGB: four bytes, a channel is entry b of a table of 256 floats -- the piecewise sRGB formula (b / 255 <= 0.04045 ? c / 12.92 :
+ *   ((c + 0.055) / 1.055) ^ 2.4) evaluated in float64 and rounded once to fp32; the table is stated as constants on each side (glrt_srgb_table), there is no
+ *   pow at run time.  Alpha is never read.
+ * COORDINATES.  A non-finite s or t is 0.  Per axis with N texels and coordinate s:
+ *   GLRTX_TEX_REPEAT  x = s - floor(s).       GLRTX_TEX_CLAMP  x = s > 0 ? s : 0, then x = x < 1 ? x : 1.       a = x * (float)N.
+ *   GLRTX_TEX_NEAREST   i = (int)floor(a); under repeat i >= N becomes i - N, under clamp i > N - 1 becomes N - 1.
+ *   GLRTX_TEX_BILINEAR  b = a - 0.5, fl = floor(b), f = b - fl, i0 = (int)fl, i1 = i0 + 1; each index: under repeat i < 0 becomes i + N and i >= N becomes
+ *                       i - N; under clamp i < 0 becomes 0 and i > N - 1 becomes N - 1.
+ * FILTER (bilinear), per channel, with txy the decoded texel at column ix, row iy:  c0 = t00 + fx * (t10 - t00),  c1 = t01 + fx * (t11 - t01),
+ *   c = c0 + fy * (c1 - c0).  Four equal texels give that texel's words exactly (d = 0, f * 0 = 0, t + 0 = t for the finite texels a texture should hold).
+ *   Nearest returns the decoded texel.
+ * AT A HIT of a triangle with vertices 0, 1, 2 in wire order and barycentrics (u, v):  w0 = (1 - u) - v,  s = (w0 * s0 + u * s1) + v * s2, t likewise -- the
+ *   order surf_tri mixes the normals in.  (s, t) = words 6 and 7 of a wire vertex (uv.x, uv.y); uv.z is ignored.
+ * SHADING.  A diffuse (type 2) material bound to texture k takes its albedo from the lookup wherever the reference reads param0: the BSDF value is albedo / PI
+ *   (the division the material staging performs), the light sample's f is the albedo itself.  The texture REPLACES param0, it does not multiply it.  Analytic
+ *   spheres have no coordinates: a sphere with a bound material shades with param0.
+ *
+ *   glrtx_upload_textures  copies descriptors and blob to the device and binds material m to texture material_texture[m] (-1: untextured).  The per-triangle
+ *                     table of the three corners' (s, t) is built in this call from the vertices glrtx_upload_scene was given, and is FROZEN from then on:
+ *                     glrtx_update_vertices*, glrtx_pose* and glrtx_update_positions* move geometry, not the mapping (their uv words are carried along and
+ *                     not read again).  n_tex = 0 unbinds: the context renders as before.  glrtx_upload_scene drops the set, as it drops spheres.
+ *                     GLRTX_EINVAL, everything unchanged, the offender named in the message: no scene uploaded; n_mat other than the scene's material count;
+ *                     a texture index out of range; a binding on a material that is not diffuse; a descriptor with a zero or oversized dimension, an unknown
+ *                     format, wrap or filter, or a misaligned offset; a texture whose last texel lies past texel_bytes; more than 2^31 - 1 texels in total;
+ *                     more than GLRTX_TEX_MAX textures; a NULL pointer.
+ *   While a set is bound these refuse with GLRTX_EINVAL and a message that says "textures are bound": glrtx_render_adaptive*, glrtx_render_moments,
+ *                     glrtx_render_cascades and glrtx_hit_histogram (the wavefront kernel's calls).  The present ring works as it does with spheres.
+ *   Feature pass      with a set bound, plane A of glrtx_render_features carries the looked-up albedo of a textured diffuse hit (the material id is unchanged),
+ *                     so `demodulate` keeps texture detail out of both denoisers' filters.  glrt_texture_albedo (include/glrt_host.h) states it on plane G.
+ *   glrtx_debug_texture_lookup  tex_lookup on caller arrays on the current HIP device, no context: rgb_out[3i..] = lookup(which[i], st[2i], st[2i + 1]).
+ *                     Refuses what glrtx_upload_textures refuses of a set, and a `which` out of range.  Errors through glrtx_last_error(NULL).
+ * Groups: no call; a member is reached through glrtx_group_ctx(grp, i). */
+#define GLRTX_TEX_MAX 4096
+#define GLRTX_TEX_MAX_DIM 16384
+enum glrtx_tex_format { GLRTX_TEX_RGBA32F = 0, GLRTX_TEX_RGBA8_UNORM = 1, GLRTX_TEX_RGBA8_SRGB = 2 };
+enum glrtx_tex_wrap { GLRTX_TEX_REPEAT = 0, GLRTX_TEX_CLAMP = 1 };
+enum glrtx_tex_filter { GLRTX_TEX_NEAREST = 0, GLRTX_TEX_BILINEAR = 1 };
+typedef struct glrtx_texture {
+    uint64_t offset;        /* bytes from the start of the blob; a multiple of 16 */
+    int32_t width, height;  /* 1 .. GLRTX_TEX_MAX_DIM */
+    int32_t format;         /* glrtx_tex_format */
+    int32_t wrap_s, wrap_t; /* glrtx_tex_wrap */
+    int32_t filter;         /* glrtx_tex_filter */
+} glrtx_texture;
+int glrtx_upload_textures(glrtx_ctx *ctx, const glrtx_texture *tex, size_t n_tex, const void *texels, size_t texel_bytes, const int32_t *material_texture,
+                          size_t n_mat);
+int glrtx_debug_texture_lookup(const glrtx_texture *tex, size_t n_tex, const void *texels, size_t texel_bytes, const int32_t *which, const float *st, size_t n,
+                               float *rgb_out);
+
 /* ---- Groups: the same device layer on several GPUs of one node, behind one handle and one host thread.
  * No reference counterpart (the reference is single-GPU); SURVEY.md 8(b) sketches glrtx_create(ctx**, device_ids, n) with a
  * gathering read_accum -- this is that, kept apart from the single-context calls.  Member i owns the 8-row stripes s with

@@ -13,6 +13,9 @@
 // Under glrtx_track_motion the *_geom kernels write a third plane  G {wire triangle as int32 bits, u, v, 0}, a miss {-1, 0, 0, 0}: the traversal's own hit, the
 // triangle mapped through the ray queries' table (query::store_hit's).  They take GeomArgs, whose store() adds the plane, and run the same loops; the kernels without it
 // keep their names and their instructions.
+// With a texture set bound (glrtx_upload_textures) the *_tex kernels run instead: TexArgs / TexGeomArgs add the set, and their store() puts the albedo tex_lookup
+// finds at the hit's coordinates into A for a diffuse material bound to a texture -- what the extension kernel shades with.  The material id is unchanged.  They
+// are further instantiations of the same loops, launched only while a set is bound; the kernels above keep their names and their instructions.
 #pragma once
 #include "query.hip.h"
 
@@ -101,6 +104,32 @@ DEV void store(const GeomArgs &q, unsigned id, const Hit &h) {
     float4 G = make_float4(__int_as_float(-1), 0.f, 0.f, 0.f);
     if (h.tri >= 0) G = make_float4(__int_as_float(q.wire[h.tri]), h.u, h.v, 0.f);
     q.out_g[(size_t)lrow * q.width + lx] = G;
+}
+
+// With textures: the planes as above, then A's rgb again for a hit whose material is bound (host/texture.cpp: glrt_texture_albedo states it on plane G)
+DEV void store_albedo(const Args &q, const TexSet &ts, unsigned id, const Hit &h) {
+    int lx, lrow;
+    if (h.tri < 0 || !pixel_of(q, id, lx, lrow)) return;
+    const int mtrl = __float_as_int(q.sc.nrms[3 * h.tri].w);
+    const int k = ts.mat_tex[mtrl];
+    if (k < 0) return;
+    const float2 st = tex_hit_st(ts, h.tri, h.u, h.v);
+    const float3 c = tex_lookup(ts, k, st.x, st.y);
+    q.out_a[(size_t)lrow * q.width + lx] = make_float4(c.x, c.y, c.z, __int_as_float(mtrl));
+}
+struct TexArgs : Args {
+    TexSet tex;
+};
+struct TexGeomArgs : GeomArgs {
+    TexSet tex;
+};
+DEV void store(const TexArgs &q, unsigned id, const Hit &h) {
+    store(static_cast<const Args &>(q), id, h);
+    store_albedo(q, q.tex, id, h);
+}
+DEV void store(const TexGeomArgs &q, unsigned id, const Hit &h) {
+    store(static_cast<const GeomArgs &>(q), id, h);
+    store_albedo(q, q.tex, id, h);
 }
 
 // Trees: query::trace_tree's loop with the ray made here.
@@ -286,6 +315,10 @@ DEV void tree_body(const A &q) {
 }
 template <bool COMPACT>
 __global__ __launch_bounds__(kBlockThreads) void features_tree_geom(const GeomArgs q) { tree_body<COMPACT>(q); }
+template <bool COMPACT>
+__global__ __launch_bounds__(kBlockThreads) void features_tree_tex(const TexArgs q) { tree_body<COMPACT>(q); }
+template <bool COMPACT>
+__global__ __launch_bounds__(kBlockThreads) void features_tree_geom_tex(const TexGeomArgs q) { tree_body<COMPACT>(q); }
 
 // Vines: the list scan, a wave 64 ids (one tile) at a time.
 template <class A>
@@ -305,6 +338,8 @@ DEV void vine_body(const A &q) {
 }
 __global__ __launch_bounds__(kBlockThreads) void features_vine(const Args q) { vine_body(q); }
 __global__ __launch_bounds__(kBlockThreads) void features_vine_geom(const GeomArgs q) { vine_body(q); }
+__global__ __launch_bounds__(kBlockThreads) void features_vine_tex(const TexArgs q) { vine_body(q); }
+__global__ __launch_bounds__(kBlockThreads) void features_vine_geom_tex(const TexGeomArgs q) { vine_body(q); }
 
 }  // namespace features
 }  // namespace glrtx

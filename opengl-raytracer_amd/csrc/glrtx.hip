@@ -36,6 +36,7 @@
 #include "../host/reproject_setup.h"
 #include "../host/morph_sparse.h"
 #include "../host/normal_topology.h"
+#include "../host/texture_set.h"
 static_assert(glrtx::lbvh::kRotationPasses == GLRT_LBVH_ROTATION_PASSES, "device and CPU LBVH statements must run the same rotation sweeps");
 static_assert(glrtx::lbvh::kRebuildLeaves == GLRT_LBVH_REBUILD_LEAVES, "device and CPU LBVH statements must rebuild the same subtrees");
 
@@ -99,6 +100,12 @@ struct glrtx_ctx {
     DevBuf forks, cnodes, cranks, nrms, mats, lights, vine, accum_own, counter, rgba8, work;
     DevBuf spheres, sphereMat;  // extension kernel: analytic spheres
     int n_spheres = 0, ext_flags = 0;
+    // Textures (glrtx_upload_textures; texture.hip.h), the scene's until the next glrtx_upload_scene: descriptors, the texel blob, the per-triangle coordinate
+    // table and the per-material binding on the device; n_tex == 0: no set bound.  scene_st: the table's source -- six floats {s, t} x 3 a device triangle
+    // (record 0 the never-hit one), taken from the vertices glrtx_upload_scene was given.
+    DevBuf texDesc, texTexels, texSt, texBind;
+    int n_tex = 0;
+    std::vector<float> scene_st;
     DevBuf volDensity, volTemp;  // volume kernel (GLRTX_EXT_VOLUME): the two grids of glrtx_upload_volume
     VolArgs vol{};
     bool have_volume = false;
@@ -967,12 +974,18 @@ void seal_feed(glrtx_ctx *c) {
     c->last_was_render = false;
 }
 
+// The bound texture set as the kernels take it (n_tex > 0)
+static_assert(sizeof(TexDesc) == sizeof(glrtx_texture) && sizeof(glrtx_texture) == sizeof(glrt_detail::TexRecord), "one descriptor layout on the wire, the host and the device");
+TexSet tex_set(const glrtx_ctx *c) {
+    return TexSet{(const TexDesc *)c->texDesc.p, (const unsigned char *)c->texTexels.p, (const float2 *)c->texSt.p, (const int *)c->texBind.p, c->n_tex};
+}
+
 // Volume launches on the wavefront kernel (its V form, kWgwfVolume): the switch is on (glrtx_set_volume_wavefront; GLRTX_VOLUME_WAVEFRONT=0/1, read at every
 // launch like the other switches, overrides it), the volume is the only extension, a volume is uploaded and no spheres are.
 bool vol_wavefront(const glrtx_ctx *c) {
     bool on = c->vol_wavefront;
     if (const char *v = std::getenv("GLRTX_VOLUME_WAVEFRONT")) on = std::atoi(v) != 0;
-    return on && c->ext_flags == GLRTX_EXT_VOLUME && c->have_volume && c->n_spheres == 0;
+    return on && c->ext_flags == GLRTX_EXT_VOLUME && c->have_volume && c->n_spheres == 0 && c->n_tex == 0;  // (textures are shaded by the megakernel only)
 }
 
 // Whether the wavefront variant's packed path state can represent this launch (meta = depth | sample << 8 | flags << 28; the V form: sample in bits 8-23).
@@ -980,7 +993,7 @@ bool wgwf_can_hold(const glrtx_params *p, bool vol = false) { return p->max_dept
 
 // Whether a launch of this context runs on the wavefront kernel (variant 2): no extensions, or the volume alone with the V form switched on.
 bool wgwf_routes(const glrtx_ctx *c, const glrtx_params *p) {
-    if (c->variant != 2 || c->n_spheres > 0) return false;
+    if (c->variant != 2 || c->n_spheres > 0 || c->n_tex > 0) return false;
     if (c->ext_flags == 0) return wgwf_can_hold(p);
     return vol_wavefront(c) && wgwf_can_hold(p, true);
 }
@@ -1846,6 +1859,7 @@ int adapt_check(glrtx_ctx *c, const glrtx_params *p, const float *seeds_xy, int 
     const bool vol = vol_wavefront(c);  // the volume alone, with the V form switched on: the wavefront kernel runs it
     if (c->ext_flags != 0 && !vol) return fail(c, GLRTX_EINVAL, "%s: extensions or volume are on (only the wavefront kernel has a tile list)", fn);
     if (c->n_spheres > 0) return fail(c, GLRTX_EINVAL, "%s: spheres are uploaded (only the wavefront kernel has a tile list)", fn);
+    if (c->n_tex > 0) return fail(c, GLRTX_EINVAL, "%s: textures are bound (only the wavefront kernel has a tile list)", fn);
     if (c->variant != 2) return fail(c, GLRTX_EINVAL, "%s: variant %d (only the wavefront kernel, variant 2, has a tile list)", fn, c->variant);
     if (!wgwf_can_hold(p, vol)) return fail(c, GLRTX_EINVAL, "%s: max_depth %d / n_samples %d beyond the wavefront kernel's path state", fn, p->max_depth, p->n_samples);
     return GLRTX_OK;
@@ -1890,6 +1904,7 @@ int side_plane_check(glrtx_ctx *c, const glrtx_params *p, const float *seeds_xy,
     if (c->pres.ring > 0) return fail(c, GLRTX_EINVAL, "%s: presentation is enabled (the present ring's passes fold neither moments nor cascades)", fn);
     if (c->ext_flags != 0) return fail(c, GLRTX_EINVAL, "%s: extensions or volume are on", fn);
     if (c->n_spheres > 0) return fail(c, GLRTX_EINVAL, "%s: spheres are uploaded", fn);
+    if (c->n_tex > 0) return fail(c, GLRTX_EINVAL, "%s: textures are bound (the megakernel that shades them writes no sample planes)", fn);
     if (c->variant != 2) return fail(c, GLRTX_EINVAL, "%s: variant %d (only the wavefront kernel, variant 2, writes sample planes)", fn, c->variant);
     if (!wgwf_can_hold(p, false)) return fail(c, GLRTX_EINVAL, "%s: max_depth %d / n_samples %d beyond the wavefront kernel's path state", fn, p->max_depth, p->n_samples);
     return GLRTX_OK;
@@ -2187,6 +2202,7 @@ void glrtx_destroy(glrtx_ctx *c) {
         for (auto &ch : sl.chunks) dev_free(ch);
         if (sl.feed_h) (void)hipHostFree(sl.feed_h);
     }
+    dev_free(c->texDesc); dev_free(c->texTexels); dev_free(c->texSt); dev_free(c->texBind);
     dev_free(c->spheres); dev_free(c->sphereMat); dev_free(c->volDensity); dev_free(c->volTemp); dev_free(c->forks); dev_free(c->cnodes); dev_free(c->cranks); dev_free(c->nrms); dev_free(c->mats); dev_free(c->lights); dev_free(c->vine);
     dev_free(c->accum_own); dev_free(c->counter); dev_free(c->rgba8); dev_free(c->work);
     c->adHalf.drop(); dev_free(c->adMask); dev_free(c->adList); dev_free(c->adCount);
@@ -2286,6 +2302,13 @@ int glrtx_upload_scene(glrtx_ctx *c, const float *vert, size_t n_vert, const flo
     c->have_scene = true;
     c->leaf_tri.swap(P.leaf_tri);
     c->n_spheres = 0;  // spheres reference this scene's materials: upload them again after a new scene
+    c->n_tex = 0;      // ... and so does a texture set's binding (glrtx_upload_textures)
+    c->scene_st.assign(6 * (c->leaf_tri.size() + 1), 0.0f);  // the corners' (s, t) of every device triangle: words 6 and 7 of a wire vertex
+    for (size_t k = 0; k < c->leaf_tri.size(); k++)
+        for (int j = 0; j < 3; j++) {
+            const float *v = vert + 15 * (size_t)tri[4 * (size_t)c->leaf_tri[k] + j];
+            c->scene_st[6 * (k + 1) + 2 * j] = v[6]; c->scene_st[6 * (k + 1) + 2 * j + 1] = v[7];
+        }
     dev_free(c->mtPos); dev_free(c->mtNrm);  // (glrtx_track_motion: the previous geometry was another scene's; the stream is idle)
     c->mt_geom = glrtx_ctx::kMtNone;
     dev_free(c->sk.rest); dev_free(c->sk.rig); dev_free(c->sk.pose);  // (glrtx_upload_rig: the rig was another scene's)
@@ -3136,6 +3159,78 @@ int glrtx_upload_spheres(glrtx_ctx *c, const float *spheres, size_t n_spheres) {
     return GLRTX_OK;
 }
 
+int glrtx_upload_textures(glrtx_ctx *c, const glrtx_texture *tex, size_t n_tex, const void *texels, size_t texel_bytes, const int32_t *material_texture,
+                          size_t n_mat) {
+    const char *fn = "glrtx_upload_textures";
+    if (!c) return GLRTX_EINVAL;
+    seal_feed(c);  // (nothing is appended to an open launch across this call: glrtx_ctx::OpenFeed)
+    if (!c->have_scene) return fail(c, GLRTX_EINVAL, "%s: no scene uploaded", fn);
+    if (n_tex == 0) {  // unbind: the next launch is routed as before (the buffers stay until the context goes)
+        HIP_TRY(c, hipSetDevice(c->device));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        c->n_tex = 0;
+        return GLRTX_OK;
+    }
+    if (n_mat != (size_t)c->n_mat) return fail(c, GLRTX_EINVAL, "%s: %zu bindings, the scene has %d materials", fn, n_mat, c->n_mat);
+    if (!material_texture) return fail(c, GLRTX_EINVAL, "%s: NULL material_texture", fn);
+    const std::string bad = glrt_detail::texture_set_error(reinterpret_cast<const glrt_detail::TexRecord *>(tex), n_tex, texels, texel_bytes);
+    if (!bad.empty()) return fail(c, GLRTX_EINVAL, "%s: %s", fn, bad.c_str());
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));  // (also behind every launch that reads the materials or a set bound before)
+    std::vector<float4> m0(3 * n_mat);
+    HIP_TRY(c, hipMemcpy(m0.data(), c->mats.p, m0.size() * sizeof(float4), hipMemcpyDeviceToHost));
+    for (size_t m = 0; m < n_mat; m++) {
+        const int32_t k = material_texture[m];
+        if (k < -1 || (k >= 0 && (size_t)k >= n_tex)) return fail(c, GLRTX_EINVAL, "%s: material %zu is bound to texture %d of %zu", fn, m, k, n_tex);
+        int type;
+        std::memcpy(&type, &m0[3 * m].w, 4);
+        if (k >= 0 && type != 2) return fail(c, GLRTX_EINVAL, "%s: material %zu is bound to texture %d and is not diffuse (type %d)", fn, m, k, type);
+    }
+    // used bytes of the blob only: the last texel of the texture that reaches furthest
+    size_t used = 0;
+    for (size_t k = 0; k < n_tex; k++)
+        used = std::max(used, (size_t)tex[k].offset + (size_t)tex[k].width * (size_t)tex[k].height * glrt_detail::tex_texel_bytes(tex[k].format));
+    // fresh buffers first, the context's own replaced only once all four are filled: a failure leaves the bound set as it was
+    DevBuf d, t, st, b;
+    int rc;
+    if ((rc = dev_upload(c, d, tex, n_tex * sizeof(glrtx_texture))) || (rc = dev_upload(c, t, texels, used)) ||
+        (rc = dev_upload(c, st, c->scene_st.data(), c->scene_st.size() * sizeof(float))) || (rc = dev_upload(c, b, material_texture, n_mat * sizeof(int32_t)))) {
+        dev_free(d); dev_free(t); dev_free(st); dev_free(b);
+        return rc;
+    }
+    dev_free(c->texDesc); dev_free(c->texTexels); dev_free(c->texSt); dev_free(c->texBind);
+    c->texDesc = d; c->texTexels = t; c->texSt = st; c->texBind = b;
+    c->n_tex = (int)n_tex;
+    return GLRTX_OK;
+}
+
+int glrtx_debug_texture_lookup(const glrtx_texture *tex, size_t n_tex, const void *texels, size_t texel_bytes, const int32_t *which, const float *st, size_t n,
+                               float *rgb_out) {
+    const char *fn = "glrtx_debug_texture_lookup";
+    if (n_tex == 0 || (n && (!which || !st || !rgb_out))) return fail(nullptr, GLRTX_EINVAL, "%s: NULL buffer or no texture", fn);
+    if (n > (size_t)INT32_MAX / 4) return fail(nullptr, GLRTX_EINVAL, "%s: too many lookups", fn);
+    const std::string bad = glrt_detail::texture_set_error(reinterpret_cast<const glrt_detail::TexRecord *>(tex), n_tex, texels, texel_bytes);
+    if (!bad.empty()) return fail(nullptr, GLRTX_EINVAL, "%s: %s", fn, bad.c_str());
+    for (size_t i = 0; i < n; i++)
+        if (which[i] < 0 || (size_t)which[i] >= n_tex) return fail(nullptr, GLRTX_EINVAL, "%s: lookup %zu names texture %d of %zu", fn, i, which[i], n_tex);
+    if (n == 0) return GLRTX_OK;
+    DebugScratch s;
+    TexSet ts{};
+    ts.desc = s.alloc<TexDesc>(n_tex * sizeof(glrtx_texture), tex);
+    ts.texels = s.alloc<unsigned char>(texel_bytes, texels);
+    ts.n_tex = (int)n_tex;
+    const int *d_which = s.alloc<int>(n * sizeof(int), which);
+    const float *d_st = s.alloc<float>(2 * n * sizeof(float), st);
+    float *d_out = s.alloc<float>(3 * n * sizeof(float));
+    if (s.ok()) {
+        hipLaunchKernelGGL(tex_lookup_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, ts, d_which, d_st, (unsigned)n, d_out);
+        s.e = hipGetLastError();
+    }
+    s.sync();
+    s.download(rgb_out, d_out, 3 * n * sizeof(float));
+    return s.result(GLRTX_OK, fn);
+}
+
 int glrtx_set_extensions(glrtx_ctx *c, int flags) {
     if (!c) return GLRTX_EINVAL;
     seal_feed(c);  // (nothing is appended to an open launch across this call: glrtx_ctx::OpenFeed)
@@ -3550,7 +3645,14 @@ int glrtx_render_features(glrtx_ctx *c, const glrtx_params *p) {
     const Kernel kernel_n = vine ? (Kernel)features::features_vine : compact ? (Kernel)features::features_tree<true> : (Kernel)features::features_tree<false>;
     const KernelG kernel_g = vine ? (KernelG)features::features_vine_geom
                                   : compact ? (KernelG)features::features_tree_geom<true> : (KernelG)features::features_tree_geom<false>;
-    const void *kernel = geom ? (const void *)kernel_g : (const void *)kernel_n;
+    // with a texture set bound: the textured instantiations, whose plane A carries the looked-up albedo (the ones above are launched as ever without a set)
+    using KernelT = void (*)(const features::TexArgs);
+    using KernelGT = void (*)(const features::TexGeomArgs);
+    const bool tex = c->n_tex > 0;
+    const KernelT kernel_t = vine ? (KernelT)features::features_vine_tex : compact ? (KernelT)features::features_tree_tex<true> : (KernelT)features::features_tree_tex<false>;
+    const KernelGT kernel_gt = vine ? (KernelGT)features::features_vine_geom_tex
+                                    : compact ? (KernelGT)features::features_tree_geom_tex<true> : (KernelGT)features::features_tree_geom_tex<false>;
+    const void *kernel = tex ? (geom ? (const void *)kernel_gt : (const void *)kernel_t) : geom ? (const void *)kernel_g : (const void *)kernel_n;
     const int lds = vine ? 0 : lds_stack + (compact ? lds_ranks : 0);
     if (lds > 64 * 1024) HIP_TRY(c, hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     int per_cu = 0;
@@ -3570,7 +3672,18 @@ int glrtx_render_features(glrtx_ctx *c, const glrtx_params *p) {
     const size_t needed = (a.n + kBlockThreads - 1) / kBlockThreads;
     const unsigned grid = (unsigned)std::max<size_t>(1, std::min<size_t>((size_t)per_cu * (size_t)c->n_cu, needed));
     HIP_TRY(c, hipMemsetAsync(c->ftCounter.p, 0, sizeof(unsigned), c->stream));
-    if (geom) {
+    if (tex && geom) {
+        features::TexGeomArgs ga;
+        static_cast<features::Args &>(ga) = a;
+        ga.out_g = (float4 *)c->ftG.p; ga.wire = (const int *)c->qwire.p;
+        ga.tex = tex_set(c);
+        hipLaunchKernelGGL(kernel_gt, dim3(grid), dim3(kBlockThreads), lds, c->stream, ga);
+    } else if (tex) {
+        features::TexArgs ta;
+        static_cast<features::Args &>(ta) = a;
+        ta.tex = tex_set(c);
+        hipLaunchKernelGGL(kernel_t, dim3(grid), dim3(kBlockThreads), lds, c->stream, ta);
+    } else if (geom) {
         features::GeomArgs ga;
         static_cast<features::Args &>(ga) = a;
         ga.out_g = (float4 *)c->ftG.p; ga.wire = (const int *)c->qwire.p;
@@ -4360,7 +4473,8 @@ static int render_one(glrtx_ctx *c, const glrtx_params *p, const RenderReq &req)
     // a launch beyond those ranges runs on the persistent megakernel instead (bit-identical, no packed state).
     // Extensions (analytic spheres, dielectric, Whitted termination) exist only in the persistent megakernel's EXT instantiation.
     // The volume alone goes to the wavefront kernel's V form when that is switched on (glrtx_set_volume_wavefront), within its narrower sample range (kWfVolSampleMax).
-    const bool ext = c->n_spheres > 0 || c->ext_flags != 0;
+    const bool tex = c->n_tex > 0;  // a bound texture set: the extension megakernel's textured instantiations (pt_render_persistent_tex)
+    const bool ext = c->n_spheres > 0 || c->ext_flags != 0 || tex;
     const bool vol_wf = vol_wavefront(c);
     const int variant = ((ext && !vol_wf) || (vol_wf && c->variant != 2) || (c->variant == 2 && !wgwf_can_hold(p, vol_wf))) ? 1 : c->variant;
     c->st.variant_last = variant;
@@ -4384,10 +4498,14 @@ static int render_one(glrtx_ctx *c, const glrtx_params *p, const RenderReq &req)
             {pt_render_persistent<false, false>, pt_render_persistent<true, false>}, {pt_render_persistent<false, true>, pt_render_persistent<true, true>},
             {pt_render_persistent<false, true, true>, pt_render_persistent<true, true, true>}};
         static constexpr const char *kPersistentNames[3] = {"pt_render_persistent", "pt_render_persistent (extensions)", "pt_render_persistent (volume)"};
+        static constexpr PKernel kPersistentTex[2][2] = {{pt_render_persistent_tex<false, false>, pt_render_persistent_tex<true, false>},  // [extensions | volume][count_rays]
+                                                         {pt_render_persistent_tex<false, true>, pt_render_persistent_tex<true, true>}};
+        static constexpr const char *kPersistentTexNames[2] = {"pt_render_persistent (extensions, textures)", "pt_render_persistent (volume, textures)"};
         const bool vol = (c->ext_flags & GLRTX_EXT_VOLUME) != 0;  // (render_one has checked that a volume is uploaded)
         const int which = vol ? 2 : ext ? 1 : 0;
-        const PKernel pk = kPersistent[which][c->count_rays];
+        const PKernel pk = tex ? kPersistentTex[vol][c->count_rays] : kPersistent[which][c->count_rays];
         ExtArgs ex{};
+        if (tex) ex.tex = tex_set(c);
         ex.spheres = (const float4 *)c->spheres.p; ex.sphere_mat = (const int *)c->sphereMat.p;
         ex.n_spheres = c->n_spheres; ex.flags = c->ext_flags;
         const int lds_p = lds + (ext ? c->n_spheres * (int)sizeof(float4) : 0);  // extension kernel: the spheres are staged behind the stacks
@@ -4403,7 +4521,7 @@ static int render_one(glrtx_ctx *c, const glrtx_params *p, const RenderReq &req)
         if (grid < 1) grid = 1;
         HIP_TRY(c, hipMemsetAsync(c->work.p, 0, sizeof(unsigned), c->stream));
         HIP_TRY(c, hipEventRecord(rec->ev0, c->stream));
-        c->last_kernel = kPersistentNames[which];
+        c->last_kernel = tex ? kPersistentTexNames[vol] : kPersistentNames[which];
         const VolArgs va = vol ? c->vol : VolArgs{};
         hipLaunchKernelGGL(pk, dim3(grid), dim3(kBlockThreads), lds_p, c->stream, a, (unsigned *)c->work.p, ex, va);
     } else {
@@ -4510,6 +4628,7 @@ int glrtx_hit_histogram(glrtx_ctx *c, const glrtx_params *p, uint32_t *hist_out,
     if (!c->have_scene) return fail(c, GLRTX_EINVAL, "glrtx_hit_histogram: no scene uploaded");
     if (!c->accum || c->width < 1 || c->owned_rows < 1) return fail(c, GLRTX_EINVAL, "glrtx_hit_histogram: no image size (call glrtx_resize)");
     if (n_tri != (size_t)c->n_tri) return fail(c, GLRTX_EINVAL, "glrtx_hit_histogram: the scene has %d triangles, room for %zu", c->n_tri, n_tri);
+    if (c->n_tex > 0) return fail(c, GLRTX_EINVAL, "glrtx_hit_histogram: textures are bound (wavefront kernel only)");
     if (c->variant != 2 || !wgwf_can_hold(p) || c->n_spheres > 0 || c->ext_flags != 0) return fail(c, GLRTX_EINVAL, "glrtx_hit_histogram: wavefront kernel only");
     HIP_TRY(c, hipSetDevice(c->device));
     if (int rc = glrtx_sync(c)) return rc;

@@ -37,6 +37,7 @@
 
 #include "trav_asm.hip.h"
 #include "scan_asm.hip.h"
+#include "texture.hip.h"
 
 namespace glrtx {
 
@@ -907,8 +908,12 @@ DEV Surf surf_tri(const DevScene &sc, const Hit &h) {
 constexpr int EXT_DIELECTRIC = 1;  // materials of type MTRL_DIELECTRIC (raytrace.frag:32, never branched on there: black) reflect / refract
 constexpr int EXT_WHITTED = 2;     // Whitted-style: a diffuse surface gathers its direct light and the path ends there; only specular bounces continue
 
-template <bool EXT>
-DEV void shade_core(const KernelArgs &a, const float4 *lds_mats, Rng &rng, Path &P, float h_t, bool h_hit, const Surf &S, int ext_flags, Shade &out) {
+// TEX (implies EXT; include/glrtx.h "Textures"): `textured` says that the hit's diffuse material is bound to a texture and (ar, ag, ab) is the albedo looked up at the
+// hit, which then stands wherever the reference reads param0 (:514 with its 1 / PI, :372 without).
+template <bool EXT, bool TEX = false>
+DEV void shade_core(const KernelArgs &a, const float4 *lds_mats, Rng &rng, Path &P, float h_t, bool h_hit, const Surf &S, int ext_flags, Shade &out,
+                    bool textured = false, float ar = 0.f, float ag = 0.f, float ab = 0.f) {
+    static_assert(!TEX || EXT, "textures are shaded by the extension kernel");
     const DevScene &sc = a.sc;
     float ox = P.ox, oy = P.oy, oz = P.oz, dx = P.dx, dy = P.dy, dz = P.dz;
     float bx = P.bx, by = P.by, bz = P.bz;
@@ -998,7 +1003,8 @@ DEV void shade_core(const KernelArgs &a, const float4 *lds_mats, Rng &rng, Path 
                 wlx = pt_cos(r1) * r2s;
                 wly = pt_sin(r1) * r2s;
                 wlz = __builtin_sqrtf(1.0f - rb);
-                if (sc.mats_in_lds) { fx = M.m2.x; fy = M.m2.y; fz = M.m2.z; }  // albedo / PI, formed when the materials were staged (stage_mats)
+                if (TEX && textured) { fx = div_pi(ar); fy = div_pi(ag); fz = div_pi(ab); }  // (div_pi(x) = x / PI: the words the staging would form)
+                else if (sc.mats_in_lds) { fx = M.m2.x; fy = M.m2.y; fz = M.m2.z; }  // albedo / PI, formed when the materials were staged (stage_mats)
                 else { fx = div_pi(M.m1.x); fy = div_pi(M.m1.y); fz = div_pi(M.m1.z); }
                 pdf = div_pi(wlz);
             } else if (type == 3) {
@@ -1105,6 +1111,7 @@ DEV void shade_core(const KernelArgs &a, const float4 *lds_mats, Rng &rng, Path 
                     float gx = 0.f, gy = 0.f, gz = 0.f;
                     if (type == 2) {
                         gx = M.m1.x; gy = M.m1.y; gz = M.m1.z;  // albedo without 1/PI :372
+                        if (TEX && textured) { gx = ar; gy = ag; gz = ab; }
                     } else if (type == 3) {
                         const float ax = M.m1.w, ay = M.m2.w;
                         const float cosI = fmax_c((-(dirz * nz) - (diry * ny)) - (dirx * nx), 0.0f);
@@ -1234,6 +1241,7 @@ struct ExtArgs {
     const int *sphere_mat;  // material id per sphere
     int n_spheres;
     int flags;              // EXT_*
+    TexSet tex;             // the bound texture set (texture.hip.h); read only by the TEX instantiations, launched only while a set is bound
 };
 constexpr int kMaxSpheres = 1024;
 
@@ -1396,7 +1404,7 @@ DEV bool bounce_volume(const KernelArgs &a, const ExtArgs &ex, const VolArgs &vo
     return P.depth >= a.max_depth;
 }
 
-template <bool VOL = false>
+template <bool VOL = false, bool TEX = false>
 DEV bool bounce_ext(const KernelArgs &a, const ExtArgs &ex, const float4 *lds_spheres, const float4 *lds_mats, int *stack, Rng &rng, Path &P, unsigned long long &rays,
                     const VolArgs *vo = nullptr) {
     const Hit h = traverse_ext<true>(a.sc, ex, lds_spheres, stack, P.ox, P.oy, P.oz, P.dx, P.dy, P.dz);
@@ -1416,7 +1424,22 @@ DEV bool bounce_ext(const KernelArgs &a, const ExtArgs &ex, const float4 *lds_sp
         if (type == 5 && (-(P.dz * S.nz) - (P.dy * S.ny)) - (P.dx * S.nx) >= PT_EPS) return bounce_volume(a, ex, *vo, lds_spheres, stack, rng, P, h.t, rays);
     }
     Shade sh;
-    shade_core<true>(a, lds_mats, rng, P, h.t, h.tri != -1, S, ex.flags, sh);
+    if (TEX) {
+        // a triangle whose material is bound to a texture (only diffuse materials can be: glrtx_upload_textures): the albedo at the hit's coordinates
+        bool textured = false;
+        float3 alb = make_float3(0.f, 0.f, 0.f);
+        if (h.tri >= 0) {
+            const int k = ex.tex.mat_tex[S.mtrl];
+            if (k >= 0) {
+                const float2 st = tex_hit_st(ex.tex, h.tri, h.u, h.v);
+                alb = tex_lookup(ex.tex, k, st.x, st.y);
+                textured = true;
+            }
+        }
+        shade_core<true, true>(a, lds_mats, rng, P, h.t, h.tri != -1, S, ex.flags, sh, textured, alb.x, alb.y, alb.z);
+    } else {
+        shade_core<true>(a, lds_mats, rng, P, h.t, h.tri != -1, S, ex.flags, sh);
+    }
     bool ok = false;
     if (sh.has_shadow) {
         const Hit s = traverse_ext<false>(a.sc, ex, lds_spheres, stack, P.ox, P.oy, P.oz, sh.sdx, sh.sdy, sh.sdz, shadow_limit(sh.dist, a.sc.shadow_limited), sh.dist);
@@ -1681,6 +1704,111 @@ __global__ __launch_bounds__(kBlockThreads) void pt_render_persistent(const Kern
             if (a.max_depth > 0) {
                 if (VOL) finished = bounce_ext<true>(a, ka->ex, lds_spheres, lds_mats, stack, rng, P, rays, &ka->vol);
                 else finished = EXT ? bounce_ext(a, ka->ex, lds_spheres, lds_mats, stack, rng, P, rays) : bounce(a, lds_mats, stack, rng, P, rays);
+            }
+            if (finished) {
+                acc.x = acc.x + fmin_c(P.Lx, 100.0f);  // :558, :608
+                acc.y = acc.y + fmin_c(P.Ly, 100.0f);
+                acc.z = acc.z + fmin_c(P.Lz, 100.0f);
+                acc.w = acc.w + 1.0f;
+                sample++;
+                if (sample >= a.n_samples) {
+                    a.accum[px_off] = acc;
+                    alive = false;
+                } else {
+                    fresh = true;
+                }
+            }
+        }
+    }
+    flush_rays<COUNT_RAYS>(persist_kernargs()->a, rays);
+}
+
+// The extension kernel with textured albedo (include/glrtx.h "Textures"): bounce_ext<VOL, true> looks the albedo up, everything else is pt_render_persistent<*, true, VOL>.
+// Launched only while a texture set is bound.  The loop is written out a second time on purpose: called from a body shared by both kernels, the compiler allocated
+// the registers of every pt_render_persistent instantiation differently (the same operations, another schedule), and the kernels without textures are to keep
+// their instructions.  Keep the two in step.
+template <bool COUNT_RAYS, bool VOL>
+__global__ __launch_bounds__(kBlockThreads) void pt_render_persistent_tex(const KernelArgs a_entry, unsigned *work_counter_entry, const ExtArgs ex_entry,
+                                                                          const VolArgs vol_entry) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+    float4 *lds_mats;
+    int *stack;
+    (void)work_counter_entry; (void)ex_entry; (void)vol_entry;
+    lds_setup(a_entry, lds_raw, lds_mats, stack);
+    float4 *lds_spheres = ext_stage_spheres(a_entry, ex_entry, lds_raw);
+    const KernelArgs &a = persist_kernargs()->a;  // (re-taken inside the loop)
+
+    const int lane = threadIdx.x & 63;
+    const unsigned long long lt_mask = (1ull << lane) - 1ull;
+    const int tiles8_x = (a.width + 7) >> 3, tiles8_y = (a.owned_rows + 7) >> 3;
+    const int total = tiles8_x * tiles8_y * 64;
+
+    // wave-uniform work state
+    int chunk_next = 0, chunk_end = 0;
+    bool exhausted = false;
+    // per-lane state
+    bool alive = false, fresh = false;
+    int px_off = 0, sample = 0;
+    float fcx = 0.f, fcy = 0.f;
+    Rng rng = {0.f, 0.f, a.seed_x, a.seed_y};
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    Path P;
+    path_begin(P, 0.f, 0.f, 0.f, 0.f, 0.f, 1.f);
+    unsigned long long rays = 0;  // low half: reference rays, high half: those resolved without a traversal
+
+    for (;;) {
+        const PersistKernArgs *ka = persist_kernargs();
+        const KernelArgs &a = ka->a;
+        unsigned *const work_counter = ka->work_counter;
+        // ---- regeneration: idle lanes take the next pixels of the wave's chunk
+        unsigned long long idle = __ballot(!alive);
+        while (idle != 0ull && !exhausted) {
+            if (chunk_next >= chunk_end) {
+                int base = 0;
+                if (lane == 0) base = (int)atomicAdd(work_counter, (unsigned)kChunk);
+                base = __builtin_amdgcn_readfirstlane(base);
+                if (base >= total) { exhausted = true; break; }
+                chunk_next = base;
+                chunk_end = base + kChunk < total ? base + kChunk : total;
+            }
+            const int n = __popcll(idle);
+            const int avail = chunk_end - chunk_next;
+            const int take = n < avail ? n : avail;
+            const int rank = __popcll(idle & lt_mask);
+            if (!alive && rank < take) {
+                const int id = chunk_next + rank;
+                const int t = id >> 6, w = id & 63;
+                const int lx = (t % tiles8_x) * 8 + (w & 7);
+                const int lrow = (t / tiles8_x) * 8 + (w >> 3);
+                if (lx < a.width && lrow < a.owned_rows && a.n_samples > 0) {
+                    const int gy = local_row_to_y(a, lrow);
+                    fcx = (float)lx + 0.5f; fcy = (float)gy + 0.5f;  // gl_FragCoord.xy
+                    rng.x = fcx / (float)a.width; rng.y = fcy / (float)a.height;  // :567
+                    px_off = lrow * a.pitch_f4 + lx;
+                    acc = a.accum[px_off];  // previous (L, count) (:570-572)
+                    sample = 0;
+                    alive = true; fresh = true;
+                }
+            }
+            chunk_next += take;
+            // still-idle lanes (chunk ran short, or the pixel drawn lies outside the image) go round again;
+            // every round consumes at least one id, so the loop ends when the image is exhausted
+            idle = __ballot(!alive);
+        }
+        if (!__any(alive)) {
+            if (exhausted) break;
+            continue;
+        }
+        // ---- one step for every live lane: (new sample ->) one bounce
+        if (alive) {
+            if (fresh) {
+                camera_ray(a, a.cam, rng, fcx, fcy, P);
+                fresh = false;
+            }
+            bool finished = true;
+            if (a.max_depth > 0) {
+                if (VOL) finished = bounce_ext<true, true>(a, ka->ex, lds_spheres, lds_mats, stack, rng, P, rays, &ka->vol);
+                else finished = bounce_ext<false, true>(a, ka->ex, lds_spheres, lds_mats, stack, rng, P, rays);
             }
             if (finished) {
                 acc.x = acc.x + fmin_c(P.Lx, 100.0f);  // :558, :608

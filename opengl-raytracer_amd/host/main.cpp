@@ -30,7 +30,8 @@ static void usage(const char *exe) {
                 "      --gpus N            render on HIP devices 0..N-1: interleaved 8-row stripes, gathered when the image is written\n"
                 "      --devices a,b,..    the same with an explicit device list (an ordinal may repeat)\n"
                 "      --extensions        accept what the reference does not have: shapes of type \"sphere\" (center, radius) and the material\n"
-                "                          \"dielectric\" (ior, tint); parity with the reference is not defined for such scenes\n"
+                "                          \"dielectric\" (ior, tint), and a diffuse shape's \"texture\": {\"file\": x.ppm | x.pfm, \"filter\", \"wrap\", \"srgb\"}\n"
+                "                          (looked up at the OBJ's vt coordinates); parity with the reference is not defined for such scenes\n"
                 "      --whitted           with --extensions: Whitted-style transport (direct light at diffuse surfaces, specular bounces only)\n"
                 "      --enable-volume     render the participating media of \"media\" shapes: the reference's ENABLE_VOLUME switch (raytrace.frag:4);\n"
                 "                          their VOL files are read (a missing one is an error only with this flag)\n"

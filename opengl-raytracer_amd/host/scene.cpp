@@ -48,6 +48,7 @@ void Scene::parse(const std::string &filename) {
     const std::string baseDir = dirOf(filename);
     if (const char *e = std::getenv("GLRT_EXTENSIONS")) extensions_ = extensions_ || std::atoi(e) != 0;
     spheres.clear();
+    textures_.clear();
     hasDielectric_ = false;
     volumeSpecs_.clear();
     hasVolume_ = false;
@@ -79,6 +80,39 @@ void Scene::parse(const std::string &filename) {
             fill3(m.type, (float)MaterialType::Diffuse);
             if (sh["reflectance"].is_null()) { GLRT_Warn("diffuse node does not have \"reflectance\" key!"); fill3(m.param0, 0.5f); }
             else vec3(sh["reflectance"], m.param0);
+            if (extensions_ && !sh["texture"].is_null()) {  // EXTENSION (scene.h: TextureSpec); off, the key is one the parser does not know
+                const Json &tx = sh["texture"];
+                if (!tx.is_object()) GLRT_FatalError("shape %zu: \"texture\" is not an object", i);
+                TextureSpec spec;
+                spec.material = materials.size();
+                if (!tx["file"].is_string() || tx["file"].string_value().empty()) GLRT_FatalError("shape %zu: \"texture\" has no \"file\" string", i);
+                spec.file = baseDir + "/" + tx["file"].string_value();
+                spec.filter = GLRTX_TEX_BILINEAR;
+                if (!tx["filter"].is_null()) {
+                    const std::string v = tx["filter"].is_string() ? tx["filter"].string_value() : std::string();
+                    if (v == "bilinear") spec.filter = GLRTX_TEX_BILINEAR;
+                    else if (v == "nearest") spec.filter = GLRTX_TEX_NEAREST;
+                    else GLRT_FatalError("shape %zu: texture \"filter\" is not \"bilinear\" or \"nearest\"", i);
+                }
+                spec.wrap = GLRTX_TEX_REPEAT;
+                if (!tx["wrap"].is_null()) {
+                    const std::string v = tx["wrap"].is_string() ? tx["wrap"].string_value() : std::string();
+                    if (v == "repeat") spec.wrap = GLRTX_TEX_REPEAT;
+                    else if (v == "clamp") spec.wrap = GLRTX_TEX_CLAMP;
+                    else GLRT_FatalError("shape %zu: texture \"wrap\" is not \"repeat\" or \"clamp\"", i);
+                }
+                bool srgb = true;
+                if (!tx["srgb"].is_null()) {
+                    if (!tx["srgb"].is_bool()) GLRT_FatalError("shape %zu: texture \"srgb\" is not true or false", i);
+                    srgb = tx["srgb"].bool_value();
+                }
+                std::string terr;
+                if (!readTextureFile(spec.file, spec.image, terr)) GLRT_FatalError("shape %zu: texture \"file\": %s", i, terr.c_str());
+                spec.format = spec.image.isFloat ? GLRTX_TEX_RGBA32F : srgb ? GLRTX_TEX_RGBA8_SRGB : GLRTX_TEX_RGBA8_UNORM;
+                GLRT_Info("texture: %s, %d x %d, %s", spec.file.c_str(), spec.image.width, spec.image.height,
+                          spec.image.isFloat ? "float" : srgb ? "8-bit sRGB" : "8-bit linear");
+                textures_.push_back(std::move(spec));
+            }
         } else if (material == "conductor") {
             fill3(m.type, (float)MaterialType::Conductor);
             if (sh["kappa"].is_null()) { GLRT_Warn("conductor node does not have \"kappa\" key!"); fill3(m.param0, 1.0f); }
@@ -586,6 +620,35 @@ struct SceneNormalsProbe {
     }
 };
 }  // namespace glrt
+
+// Texture probe: parse with extensions on or off.  counts = {textures, materials}; per texture info[7k..] = {material, width, height, format, wrap, filter, texel
+// bytes}; texels (may be NULL): the textures' texels one after the other, at most texel_cap bytes.
+namespace glrt {
+struct SceneTextureProbe {
+    static int run(const char *json, int extensions, long long counts[2], int *info, unsigned char *texels, size_t texel_cap) {
+        Scene sc;
+        sc.enableExtensions(extensions != 0);
+        sc.parse(json);
+        counts[0] = (long long)sc.textures_.size();
+        counts[1] = (long long)sc.materials.size();
+        size_t at = 0;
+        for (size_t k = 0; k < sc.textures_.size(); k++) {
+            const Scene::TextureSpec &t = sc.textures_[k];
+            if (info) {
+                const int row[7] = {(int)t.material, t.image.width, t.image.height, t.format, t.wrap, t.filter, (int)t.image.texels.size()};
+                std::memcpy(info + 7 * k, row, sizeof row);
+            }
+            if (texels && at + t.image.texels.size() <= texel_cap) std::memcpy(texels + at, t.image.texels.data(), t.image.texels.size());
+            at += t.image.texels.size();
+        }
+        return 0;
+    }
+};
+}  // namespace glrt
+
+extern "C" GLRT_API int glrt_scene_texture_probe(const char *json, int extensions, long long counts[2], int *info, unsigned char *texels, size_t texel_cap) {
+    return glrt::SceneTextureProbe::run(json, extensions, counts, info, texels, texel_cap);
+}
 
 extern "C" GLRT_API int glrt_scene_normals_probe(const char *json, const char *animation, int out[2]) { return glrt::SceneNormalsProbe::run(json, animation, out); }
 

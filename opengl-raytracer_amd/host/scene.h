@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "common.h"
+#include "texture_file.h"
 #include "volume.h"
 
 namespace glrt {
@@ -53,6 +54,21 @@ public:
     void enableExtensions(bool on) { extensions_ = on; }
     void setWhitted(bool on) { whitted_ = on; }
     size_t numSpheres() const { return spheres.size() / 5; }
+    // Textures (include/glrtx.h "Textures"; no reference counterpart).  With extensions on, a "diffuse" shape may carry
+    //     "texture": {"file": "x.ppm" | "x.pfm", "filter": "bilinear" | "nearest", "wrap": "repeat" | "clamp", "srgb": true | false}
+    // "file" is required and resolved against the scene file's directory: a binary PPM (P6, 8-bit) or a PFM (float, linear), read by texture_file.h with
+    // row 0 at t = 0 (the top row of a PPM is t = 1, OBJ's convention).  "filter" defaults to "bilinear", "wrap" to "repeat" (both axes), "srgb" to true; it
+    // selects GLRTX_TEX_RGBA8_SRGB or _UNORM for a PPM and says nothing about a PFM.  The texture replaces "reflectance" as the shape's albedo, looked up at
+    // the OBJ's vt coordinates.  An unreadable file and a value other than those above are FatalErrors that name the key.  Window uploads the set after the
+    // scene (glrtx_upload_textures).  With extensions off the key is ignored, as the reference ignores keys it does not know; a file without it parses and
+    // renders as before.
+    struct TextureSpec {
+        size_t material;  // the shape's material
+        std::string file;
+        int format, wrap, filter;  // GLRTX_TEX_*
+        TextureImage image;
+    };
+    const std::vector<TextureSpec> &textureSpecs() const { return textures_; }
     // Participating media (the reference's volume branch, which it compiles out: raytrace.frag:4; include/glrtx.h GLRTX_EXT_VOLUME).  parse() always keeps
     // each "media" shape's "volume" block {density, temperature, bboxMin, bboxMax} (scene.cpp:174-214) in volumeSpecs(); with enableVolume(true) (call
     // before parse()) it also reads the FIRST block's two VOL files -- a missing or unreadable file is then a FatalError -- and Window uploads them and
@@ -126,6 +142,7 @@ private:
     int bvhDepth_ = 0;
     std::string bvhBuilder_ = "sah";
     std::vector<float> spheres;  // extension: 5 floats per sphere {cx, cy, cz, radius, material}
+    std::vector<TextureSpec> textures_;  // extension: one per textured diffuse shape, in shape order
     bool extensions_ = false, whitted_ = false, hasDielectric_ = false;
     std::vector<VolumeSpec> volumeSpecs_;
     bool volume_ = false, hasVolume_ = false;
@@ -148,6 +165,7 @@ private:
     friend struct SceneMorphProbe;
     friend struct SceneMorphSparseProbe;
     friend struct SceneNormalsProbe;
+    friend struct SceneTextureProbe;
 };
 
 // OBJ triangles the way the reference's loader yields them (trimesh.cpp:113-191): three fresh

@@ -41,6 +41,26 @@ unsigned long long Window::raysTraced() const {
     return st.rays;
 }
 
+// The scene's textures (Scene::TextureSpec; extensions only) as one set on every member, after the scene: launches then run on the extension megakernel
+void Window::uploadTextures() {
+    if (scene->textures_.empty()) return;
+    std::vector<glrtx_texture> desc;
+    std::vector<unsigned char> blob;
+    std::vector<int32_t> bind(scene->materials.size(), -1);
+    for (const Scene::TextureSpec &t : scene->textures_) {
+        blob.resize((blob.size() + 15) / 16 * 16, 0);
+        desc.push_back(glrtx_texture{(uint64_t)blob.size(), t.image.width, t.image.height, t.format, t.wrap, t.wrap, t.filter});
+        blob.insert(blob.end(), t.image.texels.begin(), t.image.texels.end());
+        bind[t.material] = (int32_t)desc.size() - 1;
+    }
+    for (int i = 0; i < glrtx_group_size(grp_); i++) {
+        glrtx_ctx *c = glrtx_group_ctx(grp_, i);
+        if (glrtx_upload_textures(c, desc.data(), desc.size(), blob.data(), blob.size(), bind.data(), bind.size()) != GLRTX_OK)
+            GLRT_FatalError("glrtx_upload_textures: %s", glrtx_last_error(c));
+    }
+    GLRT_Info("textures: %zu, %zu texel bytes (not part of the reference)", desc.size(), blob.size());
+}
+
 void Window::mainloop(const std::shared_ptr<Scene> &scene_, double fps) {
     (void)fps;  // the reference's default fps = -1 renders every iteration (window.cpp:126); so do we
     scene = scene_;
@@ -77,9 +97,10 @@ void Window::mainloop(const std::shared_ptr<Scene> &scene_, double fps) {
             GLRT_Info("extensions: %zu analytic spheres%s%s (not part of the reference)", scene->spheres.size() / 5,
                       scene->hasDielectric_ ? ", dielectric" : "", scene->whitted_ ? ", Whitted termination" : "");
     }
+    uploadTextures();
     resize(scene->width, scene->height);
     if (const char *e = std::getenv("GLRT_BVH_ORDER")) orderByHits_ = std::string(e) == "hits";
-    if (orderByHits_ && !scene->nodes.empty() && scene->spheres.empty() && !scene->hasDielectric_ && !scene->whitted_ && !scene->hasVolume_) {
+    if (orderByHits_ && !scene->nodes.empty() && scene->textures_.empty() && scene->spheres.empty() && !scene->hasDielectric_ && !scene->whitted_ && !scene->hasVolume_) {
         // one calibration frame on the first member's share of the rows (interleaved stripes: a fair sample of the image), counted by the render kernel itself
         glrtx_params p;
         frameParams(p);

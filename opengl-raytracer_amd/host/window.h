@@ -98,6 +98,7 @@ protected:
 
 private:
     void frameParams(struct ::glrtx_params &p) const;
+    void uploadTextures();  // the scene's texture set on every member (glrtx_upload_textures)
     void resizeDefault(int width, int height);
     void resetBuffer();
     void saveCurrentFrame(const std::string &filename, bool overwrite = true) const;

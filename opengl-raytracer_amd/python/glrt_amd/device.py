@@ -177,7 +177,7 @@ EXPORTS = ["glrtx_abi_version", "glrtx_create", "glrtx_destroy", "glrtx_last_err
            "glrtx_upload_morph_targets", "glrtx_pose_morph", "glrtx_pose_dualquat", "glrtx_debug_deform", "glrtx_debug_deform_burst",
            "glrtx_upload_morph_targets_sparse", "glrtx_debug_deform_sparse",
            "glrtx_upload_normal_topology", "glrtx_update_positions", "glrtx_update_positions_device", "glrtx_set_pose_normals",
-           "glrtx_debug_rebuild_normals", "glrtx_debug_normals_burst"]
+           "glrtx_debug_rebuild_normals", "glrtx_debug_normals_burst", "glrtx_upload_textures", "glrtx_debug_texture_lookup"]
 
 SCENE_BUFFERS = ("nodes", "cnodes", "nrms", "lights", "vine", "root")  # glrtx_debug_read_scene's `which`, in order (GLRTX_SCENE_*)
 
@@ -381,6 +381,12 @@ def lib():
             L.glrtx_debug_normals_burst.argtypes = [vp, C.c_int, C.POINTER(C.c_float)]
         except AttributeError:
             pass
+        try:  # (additive to ABI 10 as well: textures)
+            i32p = C.POINTER(C.c_int32)
+            L.glrtx_upload_textures.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, i32p, C.c_size_t]
+            L.glrtx_debug_texture_lookup.argtypes = [vp, C.c_size_t, vp, C.c_size_t, i32p, fp, C.c_size_t, fp]
+        except AttributeError:
+            pass
         _lib = L
     return _lib
 
@@ -443,6 +449,22 @@ def volume_lookup(grid, bbox_min, bbox_max, pos):
     out = np.zeros(p.shape[0], np.float32)
     nz, ny, nx = g.shape
     rc = L.glrtx_debug_volume_lookup(_fp(g), nx, ny, nz, _fp(lo), _fp(hi), _fp(p), p.shape[0], _fp(out))
+    if rc != 0:
+        raise GlrtxError(rc, L.glrtx_last_error(None).decode())
+    return out
+
+
+def debug_texture_lookup(textures, which, st):
+    """glrtx_debug_texture_lookup on the current device: the kernels' tex_lookup (include/glrtx.h "Textures").  Arguments and result as host.texture_lookup's."""
+    from .host import pack_textures
+    L = lib()
+    desc, blob = pack_textures(textures)
+    w = np.ascontiguousarray(which, dtype=np.int32).reshape(-1)
+    c = _f32(st).reshape(-1, 2)
+    if c.shape[0] != w.size:
+        raise ValueError(f"debug_texture_lookup: {w.size} texture indices, {c.shape[0]} coordinates")
+    out = np.zeros((w.size, 3), np.float32)
+    rc = L.glrtx_debug_texture_lookup(desc.ctypes.data, desc.size, blob.ctypes.data, blob.size, w.ctypes.data_as(C.POINTER(C.c_int32)), _fp(c), w.size, _fp(out))
     if rc != 0:
         raise GlrtxError(rc, L.glrtx_last_error(None).decode())
     return out
@@ -1021,6 +1043,15 @@ class Device:
         """EXTENSION (parity unpinned): (n, 5) rows [cx, cy, cz, radius, material]; None or empty removes them."""
         sp = _f32(np.zeros((0, 5)) if spheres is None else np.asarray(spheres, np.float32).reshape(-1, 5))
         self._ck(self.L.glrtx_upload_spheres(self.h, _fp(sp), sp.shape[0]))
+
+    def upload_textures(self, textures, material_texture):
+        """Bind a texture set (glrtx_upload_textures; include/glrtx.h "Textures"): textures as host.pack_textures takes them -- a list of (array, format, wrap,
+        filter) --, material_texture one texture index a material of the uploaded scene (-1: untextured; only diffuse materials can be bound).  Launches then run
+        on the extension megakernel.  None or an empty list unbinds.  The triangles' texture coordinates are those of the uploaded scene's vertices, frozen."""
+        from .host import pack_textures
+        desc, blob = pack_textures(textures or [])
+        b = np.ascontiguousarray([] if material_texture is None else material_texture, dtype=np.int32).reshape(-1)
+        self._ck(self.L.glrtx_upload_textures(self.h, desc.ctypes.data, desc.size, blob.ctypes.data, blob.size, b.ctypes.data_as(C.POINTER(C.c_int32)), b.size))
 
     def set_extensions(self, flags: int):
         """EXT_DIELECTRIC | EXT_WHITTED (extensions, parity unpinned) | EXT_VOLUME (the reference's volume branch, pinned)."""

@@ -66,6 +66,11 @@ def lib():
         L.glrt_rebuild_normals.argtypes = [fp, C.c_size_t, fp, C.c_size_t, u32p, u8p]
         L.glrt_positions_to_vertices.argtypes = [fp, fp, C.c_size_t, fp]
         L.glrt_dualquat_from_matrix.restype = None
+        i32p = C.POINTER(C.c_int32)
+        L.glrt_texture_lookup.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, i32p, fp, C.c_size_t, fp]
+        L.glrt_srgb_table.restype = fp
+        L.glrt_srgb_table.argtypes = []
+        L.glrt_texture_albedo.argtypes = [fp, C.c_size_t, fp, C.c_size_t, fp, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, i32p, fp, C.c_size_t, fp]
         L.glrt_look_at.argtypes = [fp, fp, fp, fp]
         L.glrt_perspective.argtypes = [C.c_float, C.c_float, C.c_float, C.c_float, fp]
         L.glrt_mat4_mul.argtypes = [fp, fp, fp]
@@ -574,6 +579,80 @@ def positions_to_vertices(rest, pos):
     if rc != 0:
         raise RuntimeError(f"glrt_positions_to_vertices failed: {rc}")
     return out
+
+
+# Textures (include/glrtx.h "Textures"): GLRT_TEX_* / GLRTX_TEX_*
+TEX_RGBA32F, TEX_RGBA8_UNORM, TEX_RGBA8_SRGB = 0, 1, 2
+TEX_REPEAT, TEX_CLAMP = 0, 1
+TEX_NEAREST, TEX_BILINEAR = 0, 1
+TEX_FORMATS = dict(rgba32f=TEX_RGBA32F, rgba8_unorm=TEX_RGBA8_UNORM, rgba8_srgb=TEX_RGBA8_SRGB)
+TEX_WRAPS = dict(repeat=TEX_REPEAT, clamp=TEX_CLAMP)
+TEX_FILTERS = dict(nearest=TEX_NEAREST, bilinear=TEX_BILINEAR)
+TEXTURE_DTYPE = np.dtype([("offset", "<u8"), ("width", "<i4"), ("height", "<i4"), ("format", "<i4"), ("wrap_s", "<i4"), ("wrap_t", "<i4"), ("filter", "<i4")])  # glrtx_texture
+
+
+def pack_textures(textures):
+    """A texture set as the C calls take it.  textures: a list of (array, format, wrap, filter) -- array (height, width, 3 or 4), row 0 at t = 0, float32 for
+    rgba32f and uint8 for the 8-bit formats (three channels get an alpha of 1 / 255, which nothing reads); format, wrap and filter are TEX_* numbers or their
+    names, wrap may be a pair (wrap_s, wrap_t).  A pair (descriptors, blob) already packed passes through.  Returns (descriptors (n,) TEXTURE_DTYPE, blob uint8)."""
+    if isinstance(textures, tuple) and len(textures) == 2 and getattr(textures[0], "dtype", None) == TEXTURE_DTYPE:
+        return np.ascontiguousarray(textures[0]), np.ascontiguousarray(textures[1], dtype=np.uint8).reshape(-1)
+    code = lambda v, names: names[v] if isinstance(v, str) else int(v)
+    desc = np.zeros(len(textures), TEXTURE_DTYPE)
+    parts, at = [], 0
+    for k, (arr, fmt, wrap, filt) in enumerate(textures):
+        fmt = code(fmt, TEX_FORMATS)
+        ws, wt = wrap if isinstance(wrap, (tuple, list)) else (wrap, wrap)
+        a = np.asarray(arr)
+        if a.ndim != 3 or a.shape[2] not in (3, 4):
+            raise ValueError(f"pack_textures: texture {k} must be (height, width, 3 or 4), got {a.shape}")
+        a = np.ascontiguousarray(a, dtype=np.float32 if fmt == TEX_RGBA32F else np.uint8)
+        if a.shape[2] == 3:
+            a = np.concatenate([a, np.full(a.shape[:2] + (1,), 1.0 if fmt == TEX_RGBA32F else 255, a.dtype)], axis=2)
+        raw = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
+        desc[k] = (at, a.shape[1], a.shape[0], fmt, code(ws, TEX_WRAPS), code(wt, TEX_WRAPS), code(filt, TEX_FILTERS))
+        pad = (-raw.size) % 16
+        parts += [raw, np.zeros(pad, np.uint8)]
+        at += raw.size + pad
+    return desc, (np.concatenate(parts) if parts else np.zeros(0, np.uint8))
+
+
+def srgb_table():
+    """glrt_srgb_table: the 256 floats TEX_RGBA8_SRGB decodes a byte with."""
+    return np.ctypeslib.as_array(lib().glrt_srgb_table(), shape=(256,)).copy()
+
+
+def texture_lookup(textures, which, st):
+    """glrt_texture_lookup: the CPU statement of the device's texture lookup (include/glrtx.h "Textures").  textures as pack_textures takes them; which (n,) texture
+    indices; st (n, 2).  Returns rgb (n, 3) float32."""
+    desc, blob = pack_textures(textures)
+    w = np.ascontiguousarray(which, dtype=np.int32).reshape(-1)
+    c = _f32(st).reshape(-1, 2)
+    if c.shape[0] != w.size:
+        raise ValueError(f"texture_lookup: {w.size} texture indices, {c.shape[0]} coordinates")
+    out = np.zeros((w.size, 3), np.float32)
+    rc = lib().glrt_texture_lookup(desc.ctypes.data, desc.size, blob.ctypes.data, blob.size, _ptr(w, C.c_int32), _ptr(c, C.c_float), w.size, _ptr(out, C.c_float))
+    if rc != 0:
+        raise RuntimeError(f"glrt_texture_lookup failed: {rc}")
+    return out
+
+
+def texture_albedo(scene, textures, material_texture, hits):
+    """glrt_texture_albedo: what plane A of the feature pass holds for hit records as plane G stores them (hits (..., 4): wire triangle as int32 bits, u, v, 0) on
+    `scene` (vert / tri / mat) with material m bound to texture material_texture[m] (-1: none).  Returns rgb (..., 3) float32."""
+    desc, blob = pack_textures(textures)
+    v, t, m = _f32(scene["vert"]).reshape(-1, 15), _f32(scene["tri"]).reshape(-1, 4), _f32(scene["mat"]).reshape(-1, 18)
+    b = np.ascontiguousarray(material_texture, dtype=np.int32).reshape(-1)
+    if b.size != m.shape[0]:
+        raise ValueError(f"texture_albedo: {m.shape[0]} materials, {b.size} bindings")
+    h = _f32(hits)
+    flat = h.reshape(-1, 4)
+    out = np.zeros((flat.shape[0], 3), np.float32)
+    rc = lib().glrt_texture_albedo(_ptr(v, C.c_float), v.shape[0], _ptr(t, C.c_float), t.shape[0], _ptr(m, C.c_float), m.shape[0], desc.ctypes.data, desc.size,
+                                   blob.ctypes.data, blob.size, _ptr(b, C.c_int32), _ptr(flat, C.c_float), flat.shape[0], _ptr(out, C.c_float))
+    if rc != 0:
+        raise RuntimeError(f"glrt_texture_albedo failed: {rc}")
+    return out.reshape(h.shape[:-1] + (3,))
 
 
 REPROJECT_DEFAULTS = dict(max_history=32, depth_tolerance=0.02, normal_tolerance=0.9)

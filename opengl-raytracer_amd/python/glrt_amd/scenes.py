@@ -28,8 +28,10 @@ def emitter(emission):
     return dict(type=MTRL_EMITTER, emission=emission)
 
 
-def diffuse(reflectance):
-    return dict(type=MTRL_DIFFUSE, param0=reflectance)
+def diffuse(reflectance, texture=None):
+    """texture (optional, for export_json_obj): the shape's "texture" block {"file": name, "filter": .., "wrap": .., "srgb": ..} (host/scene.h; read only with
+    extensions on).  The buffers SceneBuilder makes do not change with it: a texture set is bound with Device.upload_textures."""
+    return dict(type=MTRL_DIFFUSE, param0=reflectance, texture=texture) if texture is not None else dict(type=MTRL_DIFFUSE, param0=reflectance)
 
 
 def conductor(eta, kappa, alpha):
@@ -108,14 +110,17 @@ class SceneBuilder:
     def __init__(self):
         self.materials = []
         self._pos, self._nrm, self._mid = [], [], []
+        self._uv = []  # per add_mesh: None, or (nT, 3, 2) texture coordinates
 
     def add_material(self, m) -> int:
         self.materials.append(m)
         return len(self.materials) - 1
 
-    def add_mesh(self, pos, nrm, material_id):
+    def add_mesh(self, pos, nrm, material_id, uv=None):
+        """uv (optional): (nT, 3, 2) texture coordinates (s, t), written into the vertices' uv row (uv.z stays 0); without it the row is zeros, as before."""
         pos = np.asarray(pos, np.float32).reshape(-1, 3, 3)
         nrm = np.asarray(nrm, np.float32).reshape(-1, 3, 3)
+        self._uv.append(None if uv is None else np.asarray(uv, np.float32).reshape(pos.shape[0], 3, 2))
         mid = np.broadcast_to(np.asarray(material_id, np.float32), (pos.shape[0],))
         self._pos.append(pos)
         self._nrm.append(nrm)
@@ -129,6 +134,9 @@ class SceneBuilder:
         vert = np.zeros((n_tri * 3, 5, 3), np.float32)
         vert[:, 0] = pos.reshape(-1, 3)
         vert[:, 1] = nrm.reshape(-1, 3)
+        if any(u is not None for u in self._uv):
+            uv = np.concatenate([np.zeros((p.shape[0], 3, 2), np.float32) if u is None else u for p, u in zip(self._pos, self._uv)], 0)
+            vert[:, 2, :2] = uv.reshape(-1, 2)
         vert = vert.reshape(-1, 3)
         idx = np.arange(n_tri * 3, dtype=np.float32).reshape(n_tri, 3)
         tri = np.concatenate([idx, mid[:, None]], 1).astype(np.float32)
@@ -239,6 +247,25 @@ def read_vol(path):
     return g, tuple(float(v) for v in bb[:3]), tuple(float(v) for v in bb[3:])
 
 
+def write_ppm(path, rgb):
+    """A binary PPM (P6, 8-bit) of rgb (height, width, 3) uint8 whose ROW 0 IS t = 0: the file's rows run from the top of the picture down, so they are
+    written last row first (the top row of a PPM is t = 1, OBJ's convention)."""
+    a = np.ascontiguousarray(rgb, np.uint8)
+    assert a.ndim == 3 and a.shape[2] == 3
+    with open(path, "wb") as f:
+        f.write(b"P6\n%d %d\n255\n" % (a.shape[1], a.shape[0]))
+        f.write(a[::-1].tobytes())
+
+
+def write_pfm(path, rgb):
+    """A little-endian PFM ("PF", scale -1) of rgb (height, width, 3) float32 whose row 0 is t = 0: a PFM's rows run from the bottom up, as the array's do."""
+    a = np.ascontiguousarray(rgb, "<f4")
+    assert a.ndim == 3 and a.shape[2] == 3
+    with open(path, "wb") as f:
+        f.write(b"PF\n%d %d\n-1.0\n" % (a.shape[1], a.shape[0]))
+        f.write(a.tobytes())
+
+
 def volume_from_file_grid(grid):
     """What the reference uploads from a VOL grid (scene.cpp:183-188): glTexSubImage3D with GL_RED reads the FIRST nx*ny*nz floats of
     the data, whatever the channel count; u_densityMax is the maximum over all of it.  Returns (grid (nz, ny, nx), max)."""
@@ -296,6 +323,46 @@ def config_spheres(width=256, height=256, max_depth=4, n_samples=1, subdiv=None,
     scene = b.build(bvh)
     c2w, s2c = camera((0, 3, 9), (0, 1, 0), (0, 1, 0), 40.0, width, height)
     return scene, make_params(c2w, s2c, width, height, max_depth, n_samples), spheres
+
+
+def config_textured_wall(n=6, width=64, height=48, max_depth=4, n_samples=2, albedo=None, per_cell=False, uv=None, seed=1, bvh="sah", texture=None):
+    """A vertical wall of n x n cells (two triangles each) facing the camera behind an icosphere(1) conductor, over a grey floor and under c1's lamp: the scene
+    textures are pinned on (include/glrtx.h "Textures").  A wall, not a floor: the reference's light-sampling acceptance rule leaves a surface
+    parallel to the lamp nearly dark, and a dark surface shows no albedo.
+      per_cell False  the wall has ONE diffuse material (param0 0.5 grey, which a bound texture replaces) and texture coordinates: `uv` (2 n n, 3, 2), by
+                      default each cell's centre ((i + 0.5) / n, (j + 0.5) / n) at all three corners of its triangles -- cell (column i, row j) then reads
+                      texel [j, i] of an n x n texture, or the block [2j : 2j + 2, 2i : 2i + 2] of a 2n x 2n one at the block's centre;
+      per_cell True   no coordinates, and one diffuse material a cell with param0 = albedo[j, i]: what a texture constant over each cell must render as.
+    The two forms have the same triangles in the same order, so the same tree.  albedo: (n, n, 3) float32, random in [0.1, 0.9] from `seed` by default.
+    texture: the "texture" block export_json_obj writes for the wall's shape (scenes.diffuse).  Its materials follow its shapes' order, as Scene::parse numbers them.
+    Returns (scene, params, wall) with wall = dict(n, albedo, material (the wall's id, or the first cell's), tri (its triangle range), vert (its vertex range),
+    builder (the SceneBuilder, for export_json_obj), camera (export_json_obj's origin, target, up, fov))."""
+    rng = np.random.default_rng(seed)
+    alb = np.asarray(rng.uniform(0.1, 0.9, (n, n, 3)) if albedo is None else albedo, np.float32).reshape(n, n, 3)
+    b = SceneBuilder()
+    grey = b.add_material(diffuse((0.7, 0.7, 0.7)))
+    cu = b.add_material(conductor(COPPER["eta"], COPPER["kappa"], 0.2))
+    lamp = b.add_material(emitter((10.0, 10.0, 10.0)))
+    b.add_mesh(*quad((-10, 0, 10), (20, 0, 0), (0, 0, -20)), grey)
+    b.add_mesh(*icosphere(1, 1.0, (0.0, 1.0, 0.0)), cu)
+    b.add_mesh(*quad((-1, 5, -1), (2, 0, 0), (0, 0, 2)), lamp)
+    first_tri = sum(p.shape[0] for p in b._pos)
+    x0, y0, z0, w, h = -5.0, 0.0, -2.0, 10.0, 6.0
+    pos, nrm, mid, st = [], [], [], []
+    wall = len(b.materials) if per_cell else b.add_material(diffuse((0.5, 0.5, 0.5), texture))
+    for j in range(n):
+        for i in range(n):
+            p, q = quad((x0 + w * i / n, y0 + h * j / n, z0), (w / n, 0, 0), (0, h / n, 0))  # normal +z, towards the camera
+            pos.append(p); nrm.append(q)
+            mid += [b.add_material(diffuse(tuple(float(c) for c in alb[j, i]))) if per_cell else wall] * 2
+            st.append(np.broadcast_to(np.array([(i + 0.5) / n, (j + 0.5) / n], np.float32), (2, 3, 2)))
+    coords = None if per_cell else (np.concatenate(st, 0) if uv is None else uv)
+    b.add_mesh(np.concatenate(pos, 0), np.concatenate(nrm, 0), np.asarray(mid, np.float32), uv=coords)
+    scene = b.build(bvh)
+    c2w, s2c = camera((0, 3, 9), (0, 1, 0), (0, 1, 0), 40.0, width, height)
+    info = dict(n=n, albedo=alb, material=wall, tri=range(first_tri, first_tri + 2 * n * n), vert=range(3 * first_tri, 3 * (first_tri + 2 * n * n)), builder=b,
+                camera=((0, 3, 9), (0, 1, 0), (0, 1, 0), 40.0))
+    return scene, make_params(c2w, s2c, width, height, max_depth, n_samples), info
 
 
 def _eight_spheres(b: SceneBuilder, subdiv: int):
@@ -393,7 +460,7 @@ def export_json_obj(builder: SceneBuilder, directory, width, height, origin, tar
     d = pathlib.Path(directory)
     d.mkdir(parents=True, exist_ok=True)
     shapes = []
-    for k, (pos, nrm, mid) in enumerate(zip(builder._pos, builder._nrm, builder._mid)):
+    for k, (pos, nrm, mid, uv) in enumerate(zip(builder._pos, builder._nrm, builder._mid, builder._uv)):
         assert np.all(mid == mid[0]), "one material per shape (scene.cpp:124-219)"
         m = builder.materials[int(mid[0])]
         lines = []
@@ -401,13 +468,18 @@ def export_json_obj(builder: SceneBuilder, directory, width, height, origin, tar
             lines.append("v %.9g %.9g %.9g" % tuple(p))
         for n in nrm.reshape(-1, 3):
             lines.append("vn %.9g %.9g %.9g" % tuple(n))
+        if uv is not None:  # (a mesh added with texture coordinates: vt lines and v/vt/vn corners)
+            for c in uv.reshape(-1, 2):
+                lines.append("vt %.9g %.9g" % tuple(c))
         for t in range(pos.shape[0]):
             a = 3 * t + 1
-            lines.append(f"f {a}//{a} {a + 1}//{a + 1} {a + 2}//{a + 2}")
+            lines.append(f"f {a}/{a}/{a} {a + 1}/{a + 1}/{a + 1} {a + 2}/{a + 2}/{a + 2}" if uv is not None else f"f {a}//{a} {a + 1}//{a + 1} {a + 2}//{a + 2}")
         (d / f"shape{k}.obj").write_text("\n".join(lines) + "\n")
         sh = {"type": "obj", "filename": f"shape{k}.obj"}
         if m["type"] == MTRL_DIFFUSE:
             sh.update(material="diffuse", reflectance=[float(v) for v in m["param0"]])
+            if m.get("texture") is not None:
+                sh["texture"] = dict(m["texture"]) if isinstance(m["texture"], dict) else m["texture"]
         elif m["type"] == MTRL_CONDUCTOR:
             sh.update(material="conductor", kappa=[float(v) for v in m["param0"]], eta=[float(v) for v in m["param1"]],
                       alpha=float(m["param2"][0]))
