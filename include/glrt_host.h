@@ -228,7 +228,7 @@ int glrt_tonemap(const float *src, int width, int rows, int op, int auto_exposur
 int glrt_bloom(const float *src, int width, int rows, float threshold, float strength, int levels, float *d_out, float *b_out);
 
 /* Posing: the CPU statement of the device's skinning pass (glrtx_pose / glrtx_debug_skin, include/glrtx.h "Posing": the arithmetic is there), bit for bit
- * (host/skin.cpp; tests/skin_math.py states it in numpy).  rest_vert: n_vert wire vertices of GLRT_VERTEX_FLOATS floats; bones4 / weights4: four bone indices and
+ * (host/deform.cpp; tests/skin_math.py states it in numpy).  rest_vert: n_vert wire vertices of GLRT_VERTEX_FLOATS floats; bones4 / weights4: four bone indices and
  * four weights a vertex; matrices: n_bones x 12 floats, row-major 3x4; vert_out: n_vert wire vertices (may not overlap the inputs).  Runs with denormals flushed
  * (MXCSR FTZ | DAZ, restored on return).  Weights and matrices are NOT checked for finiteness here: the statement covers whatever the kernel can be handed.
  * GLRT_HOST_EINVAL: a NULL pointer (with n_vert > 0; matrices always), n_bones outside 1..GLRT_MAX_BONES, a bone index outside [0, n_bones). */

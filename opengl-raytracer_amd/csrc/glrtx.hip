@@ -184,16 +184,36 @@ struct glrtx_ctx {
     // The rig (glrtx_upload_rig; skin.hip.h), the scene's until the next glrtx_upload_scene: the rest pose, the {bones, weights} records and the pose matrices of
     // the last glrtx_pose.  n_bones == 0: no rig.
     // Deforming (glrtx_upload_morph_targets, glrtx_pose_morph, glrtx_pose_dualquat): the rig's morph targets as uploaded (n_targets x n_vert x 24 bytes; n_targets
-    // == 0: none), the dual quaternions of the last glrtx_pose_dualquat, and the arguments of the last deform launch for the timing hook (mode -1: none yet).
+    // == 0: none) and the dual quaternions of the last glrtx_pose_dualquat.
     // A rig holds a dense set (morph) or a sparse one (glrtx_upload_morph_targets_sparse: the inverted index srow / sent of nnz entries, and the weight table
-    // swt of the last pose, whose host copy is wtab), never both; last_sparse: the last deform launch was deform_sparse_kernel with the arguments in sdeform.
+    // swt of the last pose, whose host copy is wtab), never both.
+    // One pose launch (pose_launch): which kernel of skin.hip.h, its mode (0: matrices, 1: dual quaternions; the skinning kernel has mode 0 only) and that kernel's
+    // arguments.  The three argument structs begin alike -- rest, rig, pose, out, n_vert -- so n_vert is read through any of them; the constructor sets those
+    // five and leaves the deform kernels' own (the targets) zero: no active target, no entry.
+    struct PoseLaunch {
+        enum Kernel { kNone, kSkin, kDeform, kSparse } kernel = kNone;
+        int mode = 0;
+        union {
+            skin::Args skin;
+            skin::DeformArgs deform{};
+            skin::SparseArgs sparse;
+        };
+        PoseLaunch() = default;
+        PoseLaunch(Kernel k, int m, const void *rest, const void *rig, const void *pose, void *out, size_t n_vert) : kernel(k), mode(m) {
+            const skin::Args a{(const unsigned *)rest, (const uint4 *)rig, (const float4 *)pose, (unsigned *)out, n_vert};
+            if (k == kSkin) skin = a;
+            else if (k == kDeform) deform = skin::DeformArgs{a.rest, a.rig, a.pose, a.out, a.n_vert, nullptr, {}};
+            else sparse = skin::SparseArgs{a.rest, a.rig, a.pose, a.out, a.n_vert, nullptr, nullptr, nullptr, 0};
+        }
+    };
+    // last: the launch of the last glrtx_pose_morph / glrtx_pose_dualquat, for glrtx_debug_deform_burst (kNone: none since the rig or its targets were
+    // uploaded; a glrtx_pose leaves it as it is).
     struct Rig {
         DevBuf rest, rig, pose, dq, morph, srow, sent, swt;
-        int n_bones = 0, n_targets = 0, deform_mode = -1;
-        bool sparse = false, last_sparse = false;
+        int n_bones = 0, n_targets = 0;
+        bool sparse = false;
         size_t nnz = 0;
-        skin::DeformArgs deform{};
-        skin::SparseArgs sdeform{};
+        PoseLaunch last;
         std::vector<float> wtab;
     } sk;
     // Rebuilding normals (glrtx_upload_normal_topology; normals.hip.h), the scene's until the next glrtx_upload_scene: the topology's own copy of the rest
@@ -334,9 +354,10 @@ void normals_drop(glrtx_ctx *c) {
 // The rig's morph targets, dense or sparse, are forgotten (the stream is idle: every caller has synchronised it or runs behind a blocking call)
 void morph_drop(glrtx_ctx *c) {
     dev_free(c->sk.morph); dev_free(c->sk.srow); dev_free(c->sk.sent);
-    c->sk.n_targets = 0; c->sk.deform_mode = -1;
-    c->sk.sparse = c->sk.last_sparse = false;
+    c->sk.n_targets = 0;
+    c->sk.sparse = false;
     c->sk.nnz = 0;
+    c->sk.last = glrtx_ctx::PoseLaunch{};
 }
 
 Shape accum_shape(const glrtx_ctx *c) { return {c->width, c->pitch_bytes, c->owned_rows}; }
@@ -2428,18 +2449,32 @@ int normals_fault(glrtx_ctx *c, const glrt_detail::NormalFault &f, size_t n_vert
     return fail(c, GLRTX_EINVAL, "%s: %s", fn, why);
 }
 
-// glrtx_update_positions / _device behind their checks: the records from `dev_pos` and the rest copy, the rebuild, then glrtx_update_vertices_device's path
-int positions_run(glrtx_ctx *c, const void *dev_pos) {
-    const size_t n_vert = c->rf.n_vert;
-    if (n_vert > 0) {
-        hipLaunchKernelGGL(normals::positions_kernel, dim3((unsigned)((n_vert + normals::kBlock - 1) / normals::kBlock)), dim3(normals::kBlock), 0, c->stream,
-                           (const unsigned *)c->nm.rest.p, (const unsigned *)dev_pos, (unsigned *)c->rf.vert.p, (unsigned)n_vert);
-        normals_run(c);
-    }
+// ---- a geometry move (DESIGN.md "A geometry move"): the call's checks, move_begin, the new vertices written on the context's stream, move_commit
+// Nothing more goes into an open launch; with own_buffer the context's vertex buffer is there to be written (a caller's device vertices need none).
+// (static, as the other new helpers below: an unnamed namespace inside this file's extern "C" block does not keep a name out of the dynamic symbol table)
+static int move_begin(glrtx_ctx *c, bool own_buffer) {
+    seal_feed(c);
+    HIP_TRY(c, hipSetDevice(c->device));
+    return own_buffer ? ensure(c, c->rf.vert, c->rf.n_vert * normals::kVertexWords * sizeof(float)) : GLRTX_OK;
+}
+
+// The vertices at dev_vert become the scene's: the rebuild in the context's buffer if asked for, the previous geometry kept if this is the first move since the
+// last feature pass (glrtx_track_motion), then the refit
+static int move_commit(glrtx_ctx *c, const void *dev_vert, bool rebuild_normals) {
+    if (rebuild_normals) normals_run(c);
     HIP_TRY(c, hipGetLastError());
     if (c->mt_on && c->mt_geom == glrtx_ctx::kMtCurrent)
         if (int rc = motion_snapshot(c)) return rc;
-    return refit_run(c, c->rf.vert.p);
+    return refit_run(c, dev_vert);
+}
+
+// glrtx_update_positions / _device between begin and commit: the records from `dev_pos` and the topology's rest copy
+int positions_run(glrtx_ctx *c, const void *dev_pos) {
+    const size_t n_vert = c->rf.n_vert;
+    if (n_vert > 0)
+        hipLaunchKernelGGL(normals::positions_kernel, dim3((unsigned)((n_vert + normals::kBlock - 1) / normals::kBlock)), dim3(normals::kBlock), 0, c->stream,
+                           (const unsigned *)c->nm.rest.p, (const unsigned *)dev_pos, (unsigned *)c->rf.vert.p, (unsigned)n_vert);
+    return move_commit(c, c->rf.vert.p, true);
 }
 
 int positions_check(glrtx_ctx *c, const void *pos, size_t n_vert, const char *fn) {
@@ -2485,9 +2520,7 @@ int glrtx_upload_normal_topology(glrtx_ctx *c, const float *rest_vert, size_t n_
 
 int glrtx_update_positions(glrtx_ctx *c, const float *pos, size_t n_vert) {
     if (int rc = positions_check(c, pos, n_vert, "glrtx_update_positions")) return rc;
-    seal_feed(c);
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (int rc = ensure(c, c->rf.vert, n_vert * normals::kVertexWords * sizeof(float))) return rc;
+    if (int rc = move_begin(c, true)) return rc;
     if (int rc = ensure(c, c->nm.pos, n_vert * 3 * sizeof(float))) return rc;
     HIP_TRY(c, hipMemcpyAsync(c->nm.pos.p, pos, n_vert * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
     return positions_run(c, c->nm.pos.p);
@@ -2495,9 +2528,7 @@ int glrtx_update_positions(glrtx_ctx *c, const float *pos, size_t n_vert) {
 
 int glrtx_update_positions_device(glrtx_ctx *c, const void *dev_pos, size_t n_vert) {
     if (int rc = positions_check(c, dev_pos, n_vert, "glrtx_update_positions_device")) return rc;
-    seal_feed(c);
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (int rc = ensure(c, c->rf.vert, n_vert * normals::kVertexWords * sizeof(float))) return rc;
+    if (int rc = move_begin(c, true)) return rc;
     return positions_run(c, dev_pos);
 }
 
@@ -2555,23 +2586,15 @@ int glrtx_debug_normals_burst(glrtx_ctx *c, int reps, float *ms_per_launch) {
 
 int glrtx_update_vertices(glrtx_ctx *c, const float *vert, size_t n_vert) {
     if (int rc = update_check(c, vert, n_vert, "glrtx_update_vertices")) return rc;
-    seal_feed(c);
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t bytes = n_vert * 15 * sizeof(float);
-    if (int rc = ensure(c, c->rf.vert, bytes)) return rc;
-    HIP_TRY(c, hipMemcpyAsync(c->rf.vert.p, vert, bytes, hipMemcpyHostToDevice, c->stream));
-    if (c->mt_on && c->mt_geom == glrtx_ctx::kMtCurrent)  // the first move since the last feature pass: keep where the geometry was
-        if (int rc = motion_snapshot(c)) return rc;
-    return refit_run(c, c->rf.vert.p);
+    if (int rc = move_begin(c, true)) return rc;
+    HIP_TRY(c, hipMemcpyAsync(c->rf.vert.p, vert, n_vert * 15 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    return move_commit(c, c->rf.vert.p, false);
 }
 
 int glrtx_update_vertices_device(glrtx_ctx *c, const void *dev_vert, size_t n_vert) {
     if (int rc = update_check(c, dev_vert, n_vert, "glrtx_update_vertices_device")) return rc;
-    seal_feed(c);
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (c->mt_on && c->mt_geom == glrtx_ctx::kMtCurrent)
-        if (int rc = motion_snapshot(c)) return rc;
-    return refit_run(c, dev_vert);
+    if (int rc = move_begin(c, false)) return rc;  // (the caller's buffer is read where it is: the context's stays unallocated)
+    return move_commit(c, dev_vert, false);
 }
 
 namespace {
@@ -2602,11 +2625,6 @@ void rig_records(std::vector<uint4> &r, size_t n_vert, const int32_t *bones4, co
     }
 }
 
-void skin_launch(const skin::Args &a, hipStream_t stream) {
-    if (a.n_vert == 0) return;
-    hipLaunchKernelGGL(skin::skin_kernel, dim3((unsigned)((a.n_vert + skin::kBlock - 1) / skin::kBlock)), dim3(skin::kBlock), 0, stream, a);
-}
-
 }  // namespace
 
 int glrtx_upload_rig(glrtx_ctx *c, const float *rest_vert, size_t n_vert, const int32_t *bones4, const float *weights4, int n_bones) {
@@ -2627,62 +2645,6 @@ int glrtx_upload_rig(glrtx_ctx *c, const float *rest_vert, size_t n_vert, const 
     return GLRTX_OK;
 }
 
-int glrtx_pose(glrtx_ctx *c, const float *matrices, int n_bones) {
-    const char *fn = "glrtx_pose";
-    if (!c) return GLRTX_EINVAL;
-    if (!c->have_scene || c->sk.n_bones == 0) return fail(c, GLRTX_EINVAL, "%s: no rig uploaded (glrtx_upload_rig)", fn);
-    if (n_bones != c->sk.n_bones) return fail(c, GLRTX_EINVAL, "%s: %d matrices, the rig has %d bones", fn, n_bones, c->sk.n_bones);
-    if (!matrices) return fail(c, GLRTX_EINVAL, "%s: NULL matrices", fn);
-    if (!all_finite(matrices, (size_t)n_bones * 12)) return fail(c, GLRTX_EINVAL, "%s: a matrix entry is not finite", fn);
-    seal_feed(c);
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t n_vert = c->rf.n_vert;
-    if (int rc = ensure(c, c->rf.vert, n_vert * skin::kVertexWords * sizeof(float))) return rc;
-    HIP_TRY(c, hipMemcpyAsync(c->sk.pose.p, matrices, (size_t)n_bones * 12 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    skin_launch(skin::Args{(const unsigned *)c->sk.rest.p, (const uint4 *)c->sk.rig.p, (const float4 *)c->sk.pose.p, (unsigned *)c->rf.vert.p, n_vert}, c->stream);
-    if (c->nm.pose_on) normals_run(c);  // (glrtx_set_pose_normals: the rebuild between the kernel and the refit)
-    HIP_TRY(c, hipGetLastError());
-    if (c->mt_on && c->mt_geom == glrtx_ctx::kMtCurrent)  // (glrtx_update_vertices_device's path from here)
-        if (int rc = motion_snapshot(c)) return rc;
-    return refit_run(c, c->rf.vert.p);
-}
-
-int glrtx_debug_skin(const float *rest, size_t n_vert, const int32_t *bones4, const float *weights4, const float *matrices, int n_bones, float *vert_out) {
-    const char *fn = "glrtx_debug_skin";
-    if (int rc = rig_check(nullptr, rest, n_vert, bones4, weights4, n_bones, fn)) return rc;
-    if (!matrices || (n_vert > 0 && !vert_out)) return fail(nullptr, GLRTX_EINVAL, "%s: NULL buffer", fn);
-    if (n_vert == 0) return GLRTX_OK;
-    std::vector<uint4> rig;
-    rig_records(rig, n_vert, bones4, weights4);
-    const size_t bytes = n_vert * skin::kVertexWords * sizeof(float);
-    DebugScratch s;
-    const unsigned *R = s.alloc<unsigned>(bytes, rest);
-    const uint4 *G = s.alloc<uint4>(rig.size() * sizeof(uint4), rig.data());
-    const float4 *P = s.alloc<float4>((size_t)n_bones * 12 * sizeof(float), matrices);
-    unsigned *O = s.alloc<unsigned>(bytes);
-    if (s.ok()) {
-        skin_launch(skin::Args{R, G, P, O, n_vert}, 0);
-        s.e = hipGetLastError();
-    }
-    s.sync();
-    s.download(vert_out, O, bytes);
-    return s.result(GLRTX_OK, fn);
-}
-
-// Device time of the skinning kernel by itself, as glrtx_debug_reweight_burst measures its pass: the rig with the matrices of the last glrtx_pose, into the
-// context's vertex buffer -- which holds exactly that already, so nothing changes.
-int glrtx_debug_skin_burst(glrtx_ctx *c, int reps, float *ms_per_launch) {
-    const char *fn = "glrtx_debug_skin_burst";
-    if (!c || !ms_per_launch || reps < 1) return GLRTX_EINVAL;
-    const size_t n_vert = c->rf.n_vert;
-    if (!c->have_scene || c->sk.n_bones == 0 || c->rf.vert.bytes < n_vert * skin::kVertexWords * sizeof(float))
-        return fail(c, GLRTX_EINVAL, "%s: no rig uploaded, or no glrtx_pose yet", fn);
-    seal_feed(c);
-    HIP_TRY(c, hipSetDevice(c->device));
-    const skin::Args a{(const unsigned *)c->sk.rest.p, (const uint4 *)c->sk.rig.p, (const float4 *)c->sk.pose.p, (unsigned *)c->rf.vert.p, n_vert};
-    return burst_time(c, reps, ms_per_launch, [&] { skin_launch(a, c->stream); return GLRTX_OK; });
-}
-
 namespace {
 
 // ---- deforming (glrtx_upload_morph_targets, glrtx_pose_morph, glrtx_pose_dualquat, glrtx_debug_deform; skin.hip.h: deform_kernel)
@@ -2692,7 +2654,7 @@ static_assert(skin::kMaxTargets == GLRTX_MAX_MORPH_TARGETS, "skin.hip.h and glrt
 void morph_list(skin::Morph &m, const float *weights, int n_targets) {
     m.n_active = 0;
     for (int k = 0; k < n_targets; k++)
-        if (std::fabs(weights[k]) >= 1.17549435e-38f) {  // 2^-126
+        if (!glrt_detail::tiny(weights[k])) {
             m.index[m.n_active] = (unsigned)k;
             m.weight[m.n_active++] = weights[k];
         }
@@ -2706,23 +2668,9 @@ int morph_check(glrtx_ctx *c, const float *morph_weights, int n_targets, const c
     return GLRTX_OK;
 }
 
-void deform_launch(const skin::DeformArgs &a, int mode, hipStream_t stream) {
-    if (a.n_vert == 0) return;
-    const dim3 grid((unsigned)((a.n_vert + skin::kBlock - 1) / skin::kBlock)), block(skin::kBlock);
-    if (mode) hipLaunchKernelGGL(skin::deform_kernel<true>, grid, block, 0, stream, a);
-    else hipLaunchKernelGGL(skin::deform_kernel<false>, grid, block, 0, stream, a);
-}
-
 // ---- sparse targets (glrtx_upload_morph_targets_sparse, glrtx_debug_deform_sparse; skin.hip.h: deform_sparse_kernel)
 static_assert(skin::kMaxSparseTargets == GLRTX_MAX_SPARSE_MORPH_TARGETS && glrt_detail::kMaxSparseTargets == GLRTX_MAX_SPARSE_MORPH_TARGETS,
               "skin.hip.h, host/morph_sparse.h and glrtx.h disagree");
-
-void deform_sparse_launch(const skin::SparseArgs &a, int mode, hipStream_t stream) {
-    if (a.n_vert == 0) return;
-    const dim3 grid((unsigned)((a.n_vert + skin::kBlock - 1) / skin::kBlock)), block(skin::kBlock);
-    if (mode) hipLaunchKernelGGL(skin::deform_sparse_kernel<true>, grid, block, 0, stream, a);
-    else hipLaunchKernelGGL(skin::deform_sparse_kernel<false>, grid, block, 0, stream, a);
-}
 
 // What the upload, the debug hook and the CPU statement refuse alike about a set in its wire form (host/morph_sparse.h)
 int sparse_check(glrtx_ctx *c, const uint64_t *offsets, const uint32_t *vertex, const float *deltas, int n_targets, size_t n_vert, const char *fn) {
@@ -2757,54 +2705,95 @@ int sparse_weights(std::vector<float> &tab, const float *weights, int n_targets)
     tab.assign((size_t)n_targets, 0.0f);
     int n_active = 0;
     for (int k = 0; k < n_targets; k++)
-        if (std::fabs(weights[k]) >= 1.17549435e-38f) {  // 2^-126
+        if (!glrt_detail::tiny(weights[k])) {
             tab[(size_t)k] = weights[k];
             n_active++;
         }
     return n_active;
 }
 
-// glrtx_pose_morph (mode 0: n_bones x 12 floats) and glrtx_pose_dualquat (mode 1: n_bones x 8 floats): glrtx_pose with the deform kernel in the skinning kernel's place
-int deform_pose(glrtx_ctx *c, const float *bone_data, int n_bones, const float *morph_weights, int n_targets, int mode, const char *fn) {
+using PoseLaunch = glrtx_ctx::PoseLaunch;
+
+static void pose_launch(const PoseLaunch &L, hipStream_t stream) {
+    if (L.kernel == PoseLaunch::kNone || L.skin.n_vert == 0) return;
+    const dim3 grid((unsigned)((L.skin.n_vert + skin::kBlock - 1) / skin::kBlock)), block(skin::kBlock);
+    if (L.kernel == PoseLaunch::kSkin) hipLaunchKernelGGL(skin::skin_kernel, grid, block, 0, stream, L.skin);
+    else if (L.kernel == PoseLaunch::kDeform && L.mode) hipLaunchKernelGGL(skin::deform_kernel<true>, grid, block, 0, stream, L.deform);
+    else if (L.kernel == PoseLaunch::kDeform) hipLaunchKernelGGL(skin::deform_kernel<false>, grid, block, 0, stream, L.deform);
+    else if (L.mode) hipLaunchKernelGGL(skin::deform_sparse_kernel<true>, grid, block, 0, stream, L.sparse);
+    else hipLaunchKernelGGL(skin::deform_sparse_kernel<false>, grid, block, 0, stream, L.sparse);
+}
+
+// What the pose calls refuse alike; the bone count and the pose data each refuses in its own words
+static int pose_check(glrtx_ctx *c, const char *fn) {
     if (!c) return GLRTX_EINVAL;
     if (!c->have_scene || c->sk.n_bones == 0) return fail(c, GLRTX_EINVAL, "%s: no rig uploaded (glrtx_upload_rig)", fn);
-    if (n_bones != c->sk.n_bones) return fail(c, GLRTX_EINVAL, "%s: %d bones, the rig has %d", fn, n_bones, c->sk.n_bones);
-    if (n_targets != c->sk.n_targets) return fail(c, GLRTX_EINVAL, "%s: %d morph weights, the rig has %d targets", fn, n_targets, c->sk.n_targets);
-    if (!bone_data) return fail(c, GLRTX_EINVAL, "%s: NULL pose", fn);
-    if (int rc = morph_check(c, morph_weights, n_targets, fn, c->sk.sparse ? GLRTX_MAX_SPARSE_MORPH_TARGETS : GLRTX_MAX_MORPH_TARGETS)) return rc;
-    const size_t pose_bytes = (size_t)n_bones * (mode ? 8 : 12) * sizeof(float);
-    if (!all_finite(bone_data, pose_bytes / sizeof(float))) return fail(c, GLRTX_EINVAL, "%s: a pose entry is not finite", fn);
-    seal_feed(c);
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t n_vert = c->rf.n_vert;
-    if (int rc = ensure(c, c->rf.vert, n_vert * skin::kVertexWords * sizeof(float))) return rc;
-    DevBuf &pose = mode ? c->sk.dq : c->sk.pose;
+    return GLRTX_OK;
+}
+
+// A pose call behind its checks, as a geometry move: the pose data (mode 0: 12 floats a bone, mode 1: 8) into its buffer, the kernel into the context's vertex
+// buffer.  kSkin is glrtx_pose; kDeform asks for the deform kernels, the dense or the sparse one as the rig's set and the weights decide.
+static int pose_move(glrtx_ctx *c, PoseLaunch::Kernel kernel, int mode, const float *bone_data, const float *morph_weights, int n_targets) {
+    if (int rc = move_begin(c, true)) return rc;
+    glrtx_ctx::Rig &K = c->sk;
+    const size_t pose_bytes = (size_t)K.n_bones * (mode ? 8 : 12) * sizeof(float);
+    DevBuf &pose = mode ? K.dq : K.pose;
     if (int rc = ensure(c, pose, pose_bytes)) return rc;
     HIP_TRY(c, hipMemcpyAsync(pose.p, bone_data, pose_bytes, hipMemcpyHostToDevice, c->stream));
     // A sparse set with an active weight and an entry goes through deform_sparse_kernel; without either there is nothing to add, and deform_kernel with no
     // active target reads no delta at all: Posing's bits
-    const bool sparse = c->sk.sparse && c->sk.nnz > 0 && sparse_weights(c->sk.wtab, morph_weights, n_targets) > 0;
-    if (sparse) {
-        if (int rc = ensure(c, c->sk.swt, (size_t)n_targets * sizeof(float))) return rc;
-        HIP_TRY(c, hipMemcpyAsync(c->sk.swt.p, c->sk.wtab.data(), (size_t)n_targets * sizeof(float), hipMemcpyHostToDevice, c->stream));
-        c->sk.sdeform = skin::SparseArgs{(const unsigned *)c->sk.rest.p, (const uint4 *)c->sk.rig.p, (const float4 *)pose.p, (unsigned *)c->rf.vert.p, n_vert,
-                                         (const unsigned *)c->sk.srow.p, (const float4 *)c->sk.sent.p, (const float *)c->sk.swt.p, n_targets};
-        deform_sparse_launch(c->sk.sdeform, mode, c->stream);
-    } else {
-        skin::DeformArgs &a = c->sk.deform;
-        a = skin::DeformArgs{(const unsigned *)c->sk.rest.p, (const uint4 *)c->sk.rig.p, (const float4 *)pose.p, (unsigned *)c->rf.vert.p, n_vert,
-                             (const float2 *)c->sk.morph.p, {}};
-        if (!c->sk.sparse) morph_list(a.morph, morph_weights, n_targets);
-        deform_launch(a, mode, c->stream);
+    if (kernel == PoseLaunch::kDeform && K.sparse && K.nnz > 0 && sparse_weights(K.wtab, morph_weights, n_targets) > 0) kernel = PoseLaunch::kSparse;
+    PoseLaunch L(kernel, mode, K.rest.p, K.rig.p, pose.p, c->rf.vert.p, c->rf.n_vert);
+    if (kernel == PoseLaunch::kSparse) {
+        if (int rc = ensure(c, K.swt, (size_t)n_targets * sizeof(float))) return rc;
+        HIP_TRY(c, hipMemcpyAsync(K.swt.p, K.wtab.data(), (size_t)n_targets * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        L.sparse.row = (const unsigned *)K.srow.p; L.sparse.entry = (const float4 *)K.sent.p; L.sparse.weight = (const float *)K.swt.p;
+        L.sparse.n_targets = n_targets;
+    } else if (kernel == PoseLaunch::kDeform) {
+        L.deform.deltas = (const float2 *)K.morph.p;
+        if (!K.sparse) morph_list(L.deform.morph, morph_weights, n_targets);
     }
-    c->sk.deform_mode = mode;
-    c->sk.last_sparse = sparse;
-    if (c->nm.pose_on) normals_run(c);  // (glrtx_set_pose_normals)
-    HIP_TRY(c, hipGetLastError());
-    if (c->mt_on && c->mt_geom == glrtx_ctx::kMtCurrent)  // (glrtx_pose's path from here)
-        if (int rc = motion_snapshot(c)) return rc;
-    return refit_run(c, c->rf.vert.p);
+    pose_launch(L, c->stream);
+    if (kernel != PoseLaunch::kSkin) K.last = L;  // (a glrtx_pose leaves the record: glrtx_debug_deform_burst goes on replaying the last deform launch)
+    return move_commit(c, c->rf.vert.p, c->nm.pose_on);  // (glrtx_set_pose_normals: the rebuild between the kernel and the refit)
 }
+
+// glrtx_pose_morph (mode 0: n_bones x 12 floats) and glrtx_pose_dualquat (mode 1: n_bones x 8 floats)
+int deform_pose(glrtx_ctx *c, const float *bone_data, int n_bones, const float *morph_weights, int n_targets, int mode, const char *fn) {
+    if (int rc = pose_check(c, fn)) return rc;
+    if (n_bones != c->sk.n_bones) return fail(c, GLRTX_EINVAL, "%s: %d bones, the rig has %d", fn, n_bones, c->sk.n_bones);
+    if (n_targets != c->sk.n_targets) return fail(c, GLRTX_EINVAL, "%s: %d morph weights, the rig has %d targets", fn, n_targets, c->sk.n_targets);
+    if (!bone_data) return fail(c, GLRTX_EINVAL, "%s: NULL pose", fn);
+    if (int rc = morph_check(c, morph_weights, n_targets, fn, c->sk.sparse ? GLRTX_MAX_SPARSE_MORPH_TARGETS : GLRTX_MAX_MORPH_TARGETS)) return rc;
+    if (!all_finite(bone_data, (size_t)n_bones * (mode ? 8 : 12))) return fail(c, GLRTX_EINVAL, "%s: a pose entry is not finite", fn);
+    return pose_move(c, PoseLaunch::kDeform, mode, bone_data, morph_weights, n_targets);
+}
+
+// What the three pose hooks share: the rest vertices, the rig records, the pose data and the output in scratch, as one launch L; a hook adds its own
+// buffers to both, then run(): the launch on the null stream, the result read back
+struct PoseScratch : DebugScratch {
+    size_t bytes;
+    PoseLaunch L;
+    PoseScratch(PoseLaunch::Kernel kernel, int mode, const float *rest, size_t n_vert, const int32_t *bones4, const float *weights4, const float *bone_data,
+                int n_bones)
+        : bytes(n_vert * skin::kVertexWords * sizeof(float)) {
+        std::vector<uint4> rig;
+        rig_records(rig, n_vert, bones4, weights4);
+        const unsigned *R = alloc<unsigned>(bytes, rest);
+        const uint4 *G = alloc<uint4>(rig.size() * sizeof(uint4), rig.data());
+        const float4 *P = alloc<float4>((size_t)n_bones * (mode ? 8 : 12) * sizeof(float), bone_data);
+        L = PoseLaunch(kernel, mode, R, G, P, alloc<unsigned>(bytes), n_vert);
+    }
+    int run(float *vert_out, const char *fn) {
+        if (ok()) {
+            pose_launch(L, 0);
+            e = hipGetLastError();
+        }
+        sync();
+        download(vert_out, L.skin.out, bytes);
+        return result(GLRTX_OK, fn);
+    }
+};
 
 }  // namespace
 
@@ -2845,12 +2834,29 @@ int glrtx_upload_morph_targets_sparse(glrtx_ctx *c, const uint64_t *offsets, con
     return GLRTX_OK;
 }
 
+int glrtx_pose(glrtx_ctx *c, const float *matrices, int n_bones) {
+    const char *fn = "glrtx_pose";
+    if (int rc = pose_check(c, fn)) return rc;
+    if (n_bones != c->sk.n_bones) return fail(c, GLRTX_EINVAL, "%s: %d matrices, the rig has %d bones", fn, n_bones, c->sk.n_bones);
+    if (!matrices) return fail(c, GLRTX_EINVAL, "%s: NULL matrices", fn);
+    if (!all_finite(matrices, (size_t)n_bones * 12)) return fail(c, GLRTX_EINVAL, "%s: a matrix entry is not finite", fn);
+    return pose_move(c, PoseLaunch::kSkin, 0, matrices, nullptr, 0);
+}
+
 int glrtx_pose_morph(glrtx_ctx *c, const float *matrices, int n_bones, const float *morph_weights, int n_targets) {
     return deform_pose(c, matrices, n_bones, morph_weights, n_targets, 0, "glrtx_pose_morph");
 }
 
 int glrtx_pose_dualquat(glrtx_ctx *c, const float *dualquats, int n_bones, const float *morph_weights, int n_targets) {
     return deform_pose(c, dualquats, n_bones, morph_weights, n_targets, 1, "glrtx_pose_dualquat");
+}
+
+int glrtx_debug_skin(const float *rest, size_t n_vert, const int32_t *bones4, const float *weights4, const float *matrices, int n_bones, float *vert_out) {
+    const char *fn = "glrtx_debug_skin";
+    if (int rc = rig_check(nullptr, rest, n_vert, bones4, weights4, n_bones, fn)) return rc;
+    if (!matrices || (n_vert > 0 && !vert_out)) return fail(nullptr, GLRTX_EINVAL, "%s: NULL buffer", fn);
+    if (n_vert == 0) return GLRTX_OK;
+    return PoseScratch(PoseLaunch::kSkin, 0, rest, n_vert, bones4, weights4, matrices, n_bones).run(vert_out, fn);
 }
 
 int glrtx_debug_deform(const float *rest, size_t n_vert, const int32_t *bones4, const float *weights4, const float *bone_data, int n_bones, int mode,
@@ -2861,25 +2867,10 @@ int glrtx_debug_deform(const float *rest, size_t n_vert, const int32_t *bones4, 
     if (int rc = morph_check(nullptr, morph_weights, n_targets, fn)) return rc;
     if (!bone_data || (n_vert > 0 && (!vert_out || (n_targets > 0 && !deltas)))) return fail(nullptr, GLRTX_EINVAL, "%s: NULL buffer", fn);
     if (n_vert == 0) return GLRTX_OK;
-    std::vector<uint4> rig;
-    rig_records(rig, n_vert, bones4, weights4);
-    const size_t bytes = n_vert * skin::kVertexWords * sizeof(float);
-    DebugScratch s;
-    skin::DeformArgs a{};
-    a.rest = s.alloc<unsigned>(bytes, rest);
-    a.rig = s.alloc<uint4>(rig.size() * sizeof(uint4), rig.data());
-    a.pose = s.alloc<float4>((size_t)n_bones * (mode ? 8 : 12) * sizeof(float), bone_data);
-    a.out = s.alloc<unsigned>(bytes);
-    a.n_vert = n_vert;
-    if (n_targets > 0) a.deltas = s.alloc<float2>((size_t)n_targets * n_vert * skin::kDeltaWords * sizeof(float), deltas);
-    morph_list(a.morph, morph_weights, n_targets);
-    if (s.ok()) {
-        deform_launch(a, mode, 0);
-        s.e = hipGetLastError();
-    }
-    s.sync();
-    s.download(vert_out, a.out, bytes);
-    return s.result(GLRTX_OK, fn);
+    PoseScratch s(PoseLaunch::kDeform, mode, rest, n_vert, bones4, weights4, bone_data, n_bones);
+    if (n_targets > 0) s.L.deform.deltas = s.alloc<float2>((size_t)n_targets * n_vert * skin::kDeltaWords * sizeof(float), deltas);
+    morph_list(s.L.deform.morph, morph_weights, n_targets);
+    return s.run(vert_out, fn);
 }
 
 int glrtx_debug_deform_sparse(const float *rest, size_t n_vert, const int32_t *bones4, const float *weights4, const float *bone_data, int n_bones, int mode,
@@ -2891,48 +2882,44 @@ int glrtx_debug_deform_sparse(const float *rest, size_t n_vert, const int32_t *b
     if (int rc = morph_check(nullptr, morph_weights, n_targets, fn, GLRTX_MAX_SPARSE_MORPH_TARGETS)) return rc;
     if (!bone_data || (n_vert > 0 && !vert_out)) return fail(nullptr, GLRTX_EINVAL, "%s: NULL buffer", fn);
     if (n_vert == 0) return GLRTX_OK;
-    std::vector<uint4> rig;
-    rig_records(rig, n_vert, bones4, weights4);
     std::vector<unsigned> row;
     std::vector<float4> entry;
     std::vector<float> tab;
     sparse_index(offsets, vertex, deltas, n_targets, n_vert, row, entry);
     sparse_weights(tab, morph_weights, n_targets);
-    const size_t bytes = n_vert * skin::kVertexWords * sizeof(float);
-    DebugScratch s;
-    skin::SparseArgs a{};
-    a.rest = s.alloc<unsigned>(bytes, rest);
-    a.rig = s.alloc<uint4>(rig.size() * sizeof(uint4), rig.data());
-    a.pose = s.alloc<float4>((size_t)n_bones * (mode ? 8 : 12) * sizeof(float), bone_data);
-    a.out = s.alloc<unsigned>(bytes);
-    a.n_vert = n_vert;
+    PoseScratch s(PoseLaunch::kSparse, mode, rest, n_vert, bones4, weights4, bone_data, n_bones);
+    skin::SparseArgs &a = s.L.sparse;
     a.row = s.alloc<unsigned>(row.size() * sizeof(unsigned), row.data());
     a.entry = s.alloc<float4>(std::max<size_t>(entry.size(), 2) * sizeof(float4), entry.empty() ? nullptr : entry.data());  // (the hook always runs the sparse kernel)
     a.weight = s.alloc<float>(std::max<size_t>(tab.size(), 1) * sizeof(float), tab.empty() ? nullptr : tab.data());
     a.n_targets = n_targets;
-    if (s.ok()) {
-        deform_sparse_launch(a, mode, 0);
-        s.e = hipGetLastError();
-    }
-    s.sync();
-    s.download(vert_out, a.out, bytes);
-    return s.result(GLRTX_OK, fn);
+    return s.run(vert_out, fn);
 }
 
-// Device time of the deform kernel by itself, as glrtx_debug_skin_burst: the last glrtx_pose_morph / glrtx_pose_dualquat launch again, into the context's vertex
-// buffer -- which holds exactly that already, unless another call has written it since.
+// Device time of the skinning kernel by itself, as glrtx_debug_reweight_burst measures its pass: the rig with the matrices of the last glrtx_pose, into the
+// context's vertex buffer -- which holds exactly that already, so nothing changes.
+int glrtx_debug_skin_burst(glrtx_ctx *c, int reps, float *ms_per_launch) {
+    const char *fn = "glrtx_debug_skin_burst";
+    if (!c || !ms_per_launch || reps < 1) return GLRTX_EINVAL;
+    const size_t n_vert = c->rf.n_vert;
+    if (!c->have_scene || c->sk.n_bones == 0 || c->rf.vert.bytes < n_vert * skin::kVertexWords * sizeof(float))
+        return fail(c, GLRTX_EINVAL, "%s: no rig uploaded, or no glrtx_pose yet", fn);
+    seal_feed(c);
+    HIP_TRY(c, hipSetDevice(c->device));
+    const PoseLaunch L(PoseLaunch::kSkin, 0, c->sk.rest.p, c->sk.rig.p, c->sk.pose.p, c->rf.vert.p, n_vert);
+    return burst_time(c, reps, ms_per_launch, [&] { pose_launch(L, c->stream); return GLRTX_OK; });
+}
+
+// Device time of the deform kernel by itself, as glrtx_debug_skin_burst: the last glrtx_pose_morph / glrtx_pose_dualquat launch again (whichever kernel it
+// ran), into the context's vertex buffer -- which holds exactly that already, unless another call has written it since.
 int glrtx_debug_deform_burst(glrtx_ctx *c, int reps, float *ms_per_launch) {
     const char *fn = "glrtx_debug_deform_burst";
     if (!c || !ms_per_launch || reps < 1) return GLRTX_EINVAL;
-    if (!c->have_scene || c->sk.n_bones == 0 || c->sk.deform_mode < 0)
+    if (!c->have_scene || c->sk.n_bones == 0 || c->sk.last.kernel == PoseLaunch::kNone)
         return fail(c, GLRTX_EINVAL, "%s: no rig uploaded, or no glrtx_pose_morph / glrtx_pose_dualquat yet", fn);
     seal_feed(c);
     HIP_TRY(c, hipSetDevice(c->device));
-    return burst_time(c, reps, ms_per_launch, [&] {
-        if (c->sk.last_sparse) deform_sparse_launch(c->sk.sdeform, c->sk.deform_mode, c->stream);  // (whichever kernel the last pose ran)
-        else deform_launch(c->sk.deform, c->sk.deform_mode, c->stream);
-        return GLRTX_OK;
-    });
+    return burst_time(c, reps, ms_per_launch, [&] { pose_launch(c->sk.last, c->stream); return GLRTX_OK; });
 }
 
 namespace {

@@ -2,7 +2,7 @@
 // rigid object is the one-bone case {obj, 0, 0, 0} / {1, 0, 0, 0}.  The pass runs in front of the refit (refit.hip.h): rest pose + rig + pose matrices -> wire
 // vertices in the context's vertex buffer, which the refit then reads exactly as it reads uploaded ones.
 //
-// No reference counterpart.  The arithmetic is the header's text: host/skin.cpp (glrt_skin_vertices) and tests/skin_math.py state it again, and all three agree
+// No reference counterpart.  The arithmetic is the header's text: host/deform.cpp (glrt_skin_vertices) and tests/skin_math.py state it again, and all three agree
 // bit for bit under denoise.hip.h's rules (one correctly rounded fp32 operation at a time in the order written, -ffp-contract=off; denormals flushed; a stored
 // NaN is 0x7FC00000).  All four blend terms are formed whatever the weights are, so the operation sequence does not depend on the data.
 //

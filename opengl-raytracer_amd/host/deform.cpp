@@ -1,8 +1,9 @@
-// deform.cpp -- glrt_deform_vertices (include/glrt_host.h): the CPU statement of the device's deform pass (glrtx_pose_morph, glrtx_pose_dualquat,
-// glrtx_debug_deform, include/glrtx.h "Deforming"; csrc/skin.hip.h: deform_kernel), and glrt_dualquat_from_matrix.  glrt_deform_vertices_sparse is the same
-// statement over a sparse set (csrc/skin.hip.h: deform_sparse_kernel; tests/deform_sparse_math.py), glrt_morph_sparsify makes one from dense deltas.  The contract is the text in include/glrtx.h;
-// tests/deform_math.py restates it in numpy.  Every fp32 operation of the statement is one correctly rounded IEEE operation in the order written
-// (-ffp-contract=off), under MXCSR FTZ | DAZ.  From B = [L | t] on the vertex is Posing's, as host/skin.cpp states it.
+// deform.cpp -- the CPU statements of the device's pose kernels (include/glrt_host.h; csrc/skin.hip.h), and glrt_dualquat_from_matrix.  glrt_skin_vertices
+// states the skinning pass (glrtx_pose, glrtx_debug_skin, include/glrtx.h "Posing": skin_kernel), glrt_deform_vertices the deform pass (glrtx_pose_morph,
+// glrtx_pose_dualquat, glrtx_debug_deform, "Deforming": deform_kernel), glrt_deform_vertices_sparse the same over a sparse set (deform_sparse_kernel);
+// glrt_morph_sparsify makes a sparse set from dense deltas.  The contract is the text in include/glrtx.h; tests/skin_math.py, tests/deform_math.py and
+// tests/deform_sparse_math.py restate it in numpy.  Every fp32 operation of the statements is one correctly rounded IEEE operation in the order written
+// (-ffp-contract=off), under MXCSR FTZ | DAZ.  The three share skin_stage: from B = [L | t] on, a vertex is Posing's whichever call made B.
 #include <cmath>
 #include <cstring>
 
@@ -43,7 +44,7 @@ void dualquat_matrix(const float *w, const float *const q[4], float B[3][4]) {
     }
 }
 
-// The skinning stage of one vertex: B from matrices or dual quaternions, then Posing from B on (host/skin.cpp).  p, n: the (morphed) position and normal.
+// The skinning stage of one vertex: B from matrices or dual quaternions, then Posing from B on.  p, n: the (morphed) position and normal.
 void skin_stage(const float *in, const int32_t *b, const float *w, const float *bone_data, int stride, int mode, const float p[3], const float n[3], float *o) {
     const float *const m[4] = {bone_data + stride * (size_t)b[0], bone_data + stride * (size_t)b[1], bone_data + stride * (size_t)b[2],
                                bone_data + stride * (size_t)b[3]};
@@ -52,7 +53,6 @@ void skin_stage(const float *in, const int32_t *b, const float *w, const float *
     else
         for (int r = 0; r < 3; r++)
             for (int c = 0; c < 4; c++) B[r][c] = blend(w, m, 4 * r + c);
-    // Posing from B on (host/skin.cpp)
     const float *t = in + 9, *bn = in + 12;
     float pos[3], v[3], tg[3], bi[3];
     for (int r = 0; r < 3; r++) {
@@ -78,17 +78,34 @@ void skin_stage(const float *in, const int32_t *b, const float *w, const float *
     }
 }
 
+// What the three statements refuse alike: the bone count, a missing buffer, a vertex that names a bone outside the rig
+bool rig_ok(const float *rest_vert, size_t n_vert, const int32_t *bones4, const float *weights4, const float *bone_data, int n_bones, const float *vert_out) {
+    if (n_bones < 1 || n_bones > GLRT_MAX_BONES || !bone_data || (n_vert > 0 && (!rest_vert || !bones4 || !weights4 || !vert_out))) return false;
+    for (size_t k = 0; k < 4 * n_vert; k++)
+        if (bones4[k] < 0 || bones4[k] >= n_bones) return false;
+    return true;
+}
+
 }  // namespace
+
+int glrt_skin_vertices(const float *rest_vert, size_t n_vert, const int32_t *bones4, const float *weights4, const float *matrices, int n_bones,
+                       float *vert_out) {
+    if (!rig_ok(rest_vert, n_vert, bones4, weights4, matrices, n_bones, vert_out)) return GLRT_HOST_EINVAL;
+    FlushDenormals ftz;
+    for (size_t i = 0; i < n_vert; i++) {
+        const float *in = rest_vert + kV * i;
+        skin_stage(in, bones4 + 4 * i, weights4 + 4 * i, matrices, 12, 0, in, in + 3, vert_out + kV * i);
+    }
+    return GLRT_HOST_OK;
+}
 
 int glrt_deform_vertices(const float *rest_vert, size_t n_vert, const int32_t *bones4, const float *weights4, const float *bone_data, int n_bones, int mode,
                          const float *deltas, const float *morph_weights, int n_targets, float *vert_out) {
-    if (n_bones < 1 || n_bones > GLRT_MAX_BONES || !bone_data || (n_vert > 0 && (!rest_vert || !bones4 || !weights4 || !vert_out))) return GLRT_HOST_EINVAL;
+    if (!rig_ok(rest_vert, n_vert, bones4, weights4, bone_data, n_bones, vert_out)) return GLRT_HOST_EINVAL;
     if ((mode != 0 && mode != 1) || n_targets < 0 || n_targets > GLRT_MAX_MORPH_TARGETS) return GLRT_HOST_EINVAL;
     if (n_targets > 0 && (!morph_weights || (n_vert > 0 && !deltas))) return GLRT_HOST_EINVAL;
     for (int k = 0; k < n_targets; k++)
         if (!std::isfinite(morph_weights[k])) return GLRT_HOST_EINVAL;
-    for (size_t k = 0; k < 4 * n_vert; k++)
-        if (bones4[k] < 0 || bones4[k] >= n_bones) return GLRT_HOST_EINVAL;
     // the active targets: a weight that is not a zero after the flush
     int active[GLRT_MAX_MORPH_TARGETS], n_active = 0;
     for (int k = 0; k < n_targets; k++)
@@ -115,15 +132,13 @@ int glrt_deform_vertices(const float *rest_vert, size_t n_vert, const int32_t *b
 
 int glrt_deform_vertices_sparse(const float *rest_vert, size_t n_vert, const int32_t *bones4, const float *weights4, const float *bone_data, int n_bones, int mode,
                                 const uint64_t *offsets, const uint32_t *vertex, const float *deltas, const float *morph_weights, int n_targets, float *vert_out) {
-    if (n_bones < 1 || n_bones > GLRT_MAX_BONES || !bone_data || (n_vert > 0 && (!rest_vert || !bones4 || !weights4 || !vert_out))) return GLRT_HOST_EINVAL;
+    if (!rig_ok(rest_vert, n_vert, bones4, weights4, bone_data, n_bones, vert_out)) return GLRT_HOST_EINVAL;
     if (mode != 0 && mode != 1) return GLRT_HOST_EINVAL;
     SparseFault fault;
     if (!morph_sparse_check(offsets, vertex, deltas, n_targets, n_vert, fault)) return GLRT_HOST_EINVAL;
     if (n_targets > 0 && !morph_weights) return GLRT_HOST_EINVAL;
     for (int k = 0; k < n_targets; k++)
         if (!std::isfinite(morph_weights[k])) return GLRT_HOST_EINVAL;
-    for (size_t k = 0; k < 4 * n_vert; k++)
-        if (bones4[k] < 0 || bones4[k] >= n_bones) return GLRT_HOST_EINVAL;
     FlushDenormals ftz;
     // Morph: the targets in ascending index, each active one's entries onto the vertices they list -- per vertex that is the entries that list it, in ascending
     // target index.  A vertex no active target lists keeps the rest words.

@@ -758,29 +758,41 @@ def debug_rebuild_normals(vert, tri, class_of_vertex, flip):
     return out
 
 
-def _host_vertices(v):
-    """A numpy vertex array for glrtx_update_vertices: float32, shape (n, 15) or flat (or the scene's (n * 5, 3) texels).  Returns (array, n)."""
+def _host_vertices(v, width=15, fn="update_vertices", what="vertices"):
+    """A numpy array of rows for an update call: float32, shape (n, width) or flat -- 15 words a vertex for glrtx_update_vertices (or the scene's (n * 5, 3)
+    texels), 3 a position for glrtx_update_positions.  Returns (array, n)."""
     a = np.asarray(v)
     if a.dtype != np.float32:
-        raise TypeError(f"update_vertices: float32 vertices expected, got {a.dtype}")
-    if a.size % 15 or (a.ndim == 2 and a.shape[1] not in (3, 15)) or a.ndim > 2:
-        raise ValueError(f"update_vertices: shape {a.shape} is not (n, 15) or flat n * 15")
+        raise TypeError(f"{fn}: float32 {what} expected, got {a.dtype}")
+    if a.size % width or (a.ndim == 2 and a.shape[1] not in (3, width)) or a.ndim > 2:
+        raise ValueError(f"{fn}: shape {a.shape} is not (n, {width}) or flat n * {width}")
     a = np.ascontiguousarray(a)
-    return a, a.size // 15
+    return a, a.size // width
 
 
-def _device_vertices(t, device_index):
-    """A torch tensor for glrtx_update_vertices_device: contiguous float32 on the context's GPU, shape (n, 15) or flat.  Returns (pointer, n)."""
+def _device_vertices(t, device_index, width=15, fn="update_vertices", what="vertices"):
+    """A torch tensor of rows for the _device form of an update call: contiguous float32 on the context's GPU, shape (n, width) or flat.  Returns (pointer, n)."""
     import torch
     if t.dtype != torch.float32:
-        raise TypeError(f"update_vertices: float32 vertices expected, got {t.dtype}")
+        raise TypeError(f"{fn}: float32 {what} expected, got {t.dtype}")
     if t.device.type != "cuda" or (device_index is not None and t.device.index != device_index):
-        raise ValueError(f"update_vertices: the tensor is on {t.device}, the context on cuda:{device_index}")
+        raise ValueError(f"{fn}: the tensor is on {t.device}, the context on cuda:{device_index}")
     if not t.is_contiguous():
-        raise ValueError("update_vertices: the tensor is not contiguous")
-    if not (t.dim() == 1 and t.numel() % 15 == 0) and not (t.dim() == 2 and t.shape[1] == 15):
-        raise ValueError(f"update_vertices: shape {tuple(t.shape)} is not (n, 15) or flat n * 15")
-    return t.data_ptr(), t.numel() // 15
+        raise ValueError(f"{fn}: the tensor is not contiguous")
+    if not (t.dim() == 1 and t.numel() % width == 0) and not (t.dim() == 2 and t.shape[1] == width):
+        raise ValueError(f"{fn}: shape {tuple(t.shape)} is not (n, {width}) or flat n * {width}")
+    return t.data_ptr(), t.numel() // width
+
+
+def _bone_data(fn, what, data, per, shapes):
+    """The bone data of a pose call: float32 with `per` words a bone.  Returns (array, n_bones)."""
+    m = _f32(data)
+    if m.size % per:
+        raise ValueError(f"{fn}: {what} must be {shapes}, got {m.shape}")
+    return m, m.size // per
+
+
+_MATRIX_SHAPES = "(n_bones, 12) or (n_bones, 3, 4)"
 
 
 def pack_compact(scene):
@@ -855,18 +867,22 @@ class Device:
         self._ck(self.L.glrtx_upload_scene(self.h, _fp(v), v.size // 15, _fp(t), t.size // 4, _fp(m), m.size // 18,
                                            _fp(l), l.size // 4, _fp(b), b.size // 9))
 
+    def _update(self, v, width, fn, what, host_call, device_call):
+        """update_vertices / update_positions: a numpy array goes through `host_call`, a torch tensor through `device_call`."""
+        if type(v).__module__.startswith("torch"):
+            import torch
+            idx = self.device_id if self.device_id >= 0 else torch.cuda.current_device()
+            ptr, n = _device_vertices(v, idx, width, fn, what)
+            self._ck(device_call(self.h, C.c_void_p(ptr), n))
+        else:
+            a, n = _host_vertices(v, width, fn, what)
+            self._ck(host_call(self.h, _fp(a), n))
+
     def update_vertices(self, v):
         """New positions and normals for the uploaded scene's vertices, refitted on the device (glrtx_update_vertices): a numpy array is taken from host
         memory, a contiguous float32 torch tensor on the context's GPU (shape (n, 15) or flat) is read on the context's stream (glrtx_update_vertices_device:
         order its producer there with set_stream, or synchronise).  Returns when the refit has run; the accumulator is not cleared."""
-        if type(v).__module__.startswith("torch"):
-            import torch
-            idx = self.device_id if self.device_id >= 0 else torch.cuda.current_device()
-            ptr, n = _device_vertices(v, idx)
-            self._ck(self.L.glrtx_update_vertices_device(self.h, C.c_void_p(ptr), n))
-        else:
-            a, n = _host_vertices(v)
-            self._ck(self.L.glrtx_update_vertices(self.h, _fp(a), n))
+        self._update(v, 15, "update_vertices", "vertices", self.L.glrtx_update_vertices, self.L.glrtx_update_vertices_device)
 
     def upload_normal_topology(self, rest, tri, flags=0):
         """glrtx_upload_normal_topology: the weld classes, orientation and face lists of the rest vertices (n, 15) float32 (or the scene's vertex texels) and the
@@ -880,26 +896,7 @@ class Device:
         """New positions alone for the uploaded scene's vertices; the normals are rebuilt on the device and the tree refitted (glrtx_update_positions): a numpy
         array (n, 3) or flat is taken from host memory, a contiguous float32 torch tensor on the context's GPU is read on the context's stream
         (glrtx_update_positions_device), as update_vertices does.  Needs upload_normal_topology.  Returns when the refit has run."""
-        if type(p).__module__.startswith("torch"):
-            import torch
-            idx = self.device_id if self.device_id >= 0 else torch.cuda.current_device()
-            if p.dtype != torch.float32:
-                raise TypeError(f"update_positions: float32 positions expected, got {p.dtype}")
-            if p.device.type != "cuda" or p.device.index != idx:
-                raise ValueError(f"update_positions: the tensor is on {p.device}, the context on cuda:{idx}")
-            if not p.is_contiguous():
-                raise ValueError("update_positions: the tensor is not contiguous")
-            if not (p.dim() == 1 and p.numel() % 3 == 0) and not (p.dim() == 2 and p.shape[1] == 3):
-                raise ValueError(f"update_positions: shape {tuple(p.shape)} is not (n, 3) or flat n * 3")
-            self._ck(self.L.glrtx_update_positions_device(self.h, C.c_void_p(p.data_ptr()), p.numel() // 3))
-        else:
-            a = np.asarray(p)
-            if a.dtype != np.float32:
-                raise TypeError(f"update_positions: float32 positions expected, got {a.dtype}")
-            if a.size % 3 or a.ndim > 2 or (a.ndim == 2 and a.shape[1] != 3):
-                raise ValueError(f"update_positions: shape {a.shape} is not (n, 3) or flat n * 3")
-            a = np.ascontiguousarray(a)
-            self._ck(self.L.glrtx_update_positions(self.h, _fp(a), a.size // 3))
+        self._update(p, 3, "update_positions", "positions", self.L.glrtx_update_positions, self.L.glrtx_update_positions_device)
 
     def set_pose_normals(self, enable=True):
         """glrtx_set_pose_normals: while on, pose / pose_morph / pose_dualquat rebuild the normals between their kernel and the refit."""
@@ -922,10 +919,8 @@ class Device:
     def pose(self, matrices):
         """glrtx_pose: matrices (n_bones, 12) float32, row-major 3x4 -- skins the rest pose on the device and refits, as update_vertices of the skinned
         vertices would.  Returns when the refit has run; the accumulator is not cleared."""
-        m = _f32(matrices)
-        if m.size % 12:
-            raise ValueError(f"pose: matrices must be (n_bones, 12) or (n_bones, 3, 4), got {m.shape}")
-        self._ck(self.L.glrtx_pose(self.h, _fp(m), m.size // 12))
+        m, n_bones = _bone_data("pose", "matrices", matrices, 12, _MATRIX_SHAPES)
+        self._ck(self.L.glrtx_pose(self.h, _fp(m), n_bones))
 
     def upload_morph_targets(self, deltas):
         """glrtx_upload_morph_targets: deltas (n_targets, n_vert, 6) float32 {dpos, dnormal} for the uploaded rig; None or an empty array drops the targets."""
@@ -953,19 +948,15 @@ class Device:
 
     def pose_morph(self, matrices, morph_weights=None):
         """glrtx_pose_morph: pose() with one weight a morph target of the rig (None: the rig has none)."""
-        m = _f32(matrices)
-        if m.size % 12:
-            raise ValueError(f"pose_morph: matrices must be (n_bones, 12) or (n_bones, 3, 4), got {m.shape}")
+        m, n_bones = _bone_data("pose_morph", "matrices", matrices, 12, _MATRIX_SHAPES)
         p, n, keep = self._morph_weights(morph_weights)
-        self._ck(self.L.glrtx_pose_morph(self.h, _fp(m), m.size // 12, p, n))
+        self._ck(self.L.glrtx_pose_morph(self.h, _fp(m), n_bones, p, n))
 
     def pose_dualquat(self, dualquats, morph_weights=None):
         """glrtx_pose_dualquat: dualquats (n_bones, 8) float32 {r.xyzw, d.xyzw} (glrt_amd.rig.dualquat), and the morph weights as for pose_morph."""
-        q = _f32(dualquats)
-        if q.size % 8:
-            raise ValueError(f"pose_dualquat: dual quaternions must be (n_bones, 8), got {q.shape}")
+        q, n_bones = _bone_data("pose_dualquat", "dual quaternions", dualquats, 8, "(n_bones, 8)")
         p, n, keep = self._morph_weights(morph_weights)
-        self._ck(self.L.glrtx_pose_dualquat(self.h, _fp(q), q.size // 8, p, n))
+        self._ck(self.L.glrtx_pose_dualquat(self.h, _fp(q), n_bones, p, n))
 
     def deform_burst_ms(self, reps=20) -> float:
         """glrtx_debug_deform_burst: device ms of one launch of the deform kernel (the last pose_morph / pose_dualquat again), from `reps` back to back."""

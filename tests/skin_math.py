@@ -1,4 +1,4 @@
-"""numpy statement of the skinning pass (include/glrtx.h "Posing"; csrc/skin.hip.h: skin_kernel; host/skin.cpp: glrt_skin_vertices), and the hostile rigs the
+"""numpy statement of the skinning pass (include/glrtx.h "Posing"; csrc/skin.hip.h: skin_kernel; host/deform.cpp: glrt_skin_vertices), and the hostile rigs the
 tests pose.
 
 Every operation is one IEEE float32 operation, correctly rounded, in the contract's order, with denormals read and written as zeros of their sign
