@@ -308,6 +308,26 @@ const float *glrt_srgb_table(void);
 int glrt_texture_albedo(const float *vert, size_t n_vert, const float *tri, size_t n_tri, const float *mat, size_t n_mat, const glrt_texture *tex, size_t n_tex,
                         const void *texels, size_t texel_bytes, const int32_t *material_texture, const float *hits, size_t n, float *rgb_out);
 
+/* Environment: the CPU statements of the device's environment lighting (glrtx_upload_environment / glrtx_debug_env_*, include/glrtx.h "Environment": the
+ * octahedral mapping, its inverse, the solid-angle factor, the importance grid and the sampling rule are there), bit for bit (host/environment.cpp;
+ * tests/env_math.py states them in numpy).  glrt_env_cfg is glrtx_env_cfg's layout.  The arithmetic runs with denormals flushed (MXCSR FTZ | DAZ, restored).
+ *   glrt_env_weights       weights_out[j * G + i] = the weight of cell (row j, column i) of the G x G importance grid, in the device's summation order;
+ *                          *grid_out = G (cfg.grid, or min(N, 256) for 0).  weights_out holds 1024 * 1024 floats at most.
+ *   glrt_env_alias         the five tables of a G x G grid of weights (Vose's method in float64, thresholds rounded once to fp32): row_q / row_alias [G],
+ *                          col_q / col_alias / cell_p [G * G].
+ *   glrt_env_sample        out[8i..] = {direction, pdf, Le.rgb, 0} of the six uniforms u[6i..], with p_env = cfg.light_pick.
+ *   glrt_env_eval          out[4i..] = {Le.rgb, pdf} of the direction dir[3i..].
+ *   glrt_env_from_latlong  resamples a lat-long image (height rows of width RGB float triples; +y is up, the top row is +y, the centre column is -z, +x lies
+ *                          to its right) into an n x n octahedral RGBA32F map (alpha 1): evaluated at the texel centres with bilinear taps in float64, the
+ *                          columns wrapping, the rows clamped.  Not a device statement: it prepares an input.
+ * GLRT_HOST_EINVAL: a NULL pointer with something to read or write, or a map or configuration glrtx_upload_environment refuses. */
+typedef struct glrt_env_cfg { int32_t mode; int32_t grid; float light_pick; float scale[3]; float rotation[9]; } glrt_env_cfg;
+int glrt_env_weights(const glrt_texture *map, const void *texels, size_t texel_bytes, const glrt_env_cfg *cfg, float *weights_out, int32_t *grid_out);
+int glrt_env_alias(const float *weights, int32_t grid, float *row_q, int32_t *row_alias, float *col_q, int32_t *col_alias, float *cell_p);
+int glrt_env_sample(const glrt_texture *map, const void *texels, size_t texel_bytes, const glrt_env_cfg *cfg, const float *u, size_t n, float *out);
+int glrt_env_eval(const glrt_texture *map, const void *texels, size_t texel_bytes, const glrt_env_cfg *cfg, const float *dir, size_t n, float *out);
+int glrt_env_from_latlong(const float *rgb, int32_t width, int32_t height, int32_t n, float *rgba_out);
+
 void glrt_look_at(const float eye[3], const float center[3], const float up[3], float out[16]);
 void glrt_perspective(float fovy_deg, float aspect, float z_near, float z_far, float out[16]);
 void glrt_mat4_mul(const float a[16], const float b[16], float out[16]);

@@ -1177,6 +1177,78 @@ int glrtx_upload_textures(glrtx_ctx *ctx, const glrtx_texture *tex, size_t n_tex
 int glrtx_debug_texture_lookup(const glrtx_texture *tex, size_t n_tex, const void *texels, size_t texel_bytes, const int32_t *which, const float *st, size_t n,
                                float *rgb_out);
 
+/* ---- Environment: light from an HDR map where a ray leaves the scene (no reference counterpart -- the reference's misses return black; PARITY UNPINNED; off
+ * unless called: no other call's behaviour changes).  One image, SQUARE, N x N with N in 2 .. GLRTX_TEX_MAX_DIM, described by a glrtx_texture (offset 0): any of
+ * the three formats, nearest or bilinear, wrap GLRTX_TEX_CLAMP on both axes.  The layout is OCTAHEDRAL with +y as the fold axis, not lat-long: direction ->
+ * (s, t) is three absolute values, one quotient and a few selects on a shading path that is bound by instruction issue; lat-long needs atan2 and acos, which
+ * have no bit-exact statement here.  While an environment is bound, launches run on the persistent megakernel exactly as with analytic spheres uploaded
+ * (variant_last 1, GLRTX_FALLBACK_EXTENSIONS), in kernels of their own (pt_render_persistent_env); textures, spheres, GLRTX_EXT_DIELECTRIC and
+ * GLRTX_EXT_WHITTED combine with it, GLRTX_EXT_VOLUME does not.
+ *
+ * Arithmetic.  Every operation is one correctly rounded fp32 operation in the order written, unfused; denormals are zeros of their sign into and out of every
+ * operation.  Three statements agree bit for bit: csrc/environment.hip.h, glrt_env_* (include/glrt_host.h), tests/env_math.py.
+ *
+ * DIRECTION TO (s, t).  d is the ray direction as the path carries it (not normalised along a path); R = rotation, row-major 3 x 3.
+ *   e = R d, each row (R0 * dx + R1 * dy) + R2 * dz.   l = (|ex| + |ey|) + |ez|.   l zero or not finite: the radiance is 0.
+ *   px = ex / l, pz = ez / l.   For ey < 0 (a -0 does not fold):  px' = (1 - |pz|) * sgn(px),  pz' = (1 - |px|) * sgn(pz),  sgn(0) = sgn(-0) = +1.
+ *   s = px * 0.5 + 0.5,  t = pz * 0.5 + 0.5.   The L1 norm of the unit direction, for the pdf: py = ey / l, n1 = 1 / sqrt((pz * pz + py * py) + px * px), from the
+ *   quotients before the fold.   So +y is the centre of the square, -y its four corners, +x the middle of the right edge, +z of the top edge.
+ * RADIANCE.  Le = scale * lookup(map, s, t), per channel; the lookup is the one of "Textures", as it is.  Bilinear filtering across the fold seams is NOT
+ *   corrected: at the square's edge a lookup reads what clamp gives it, not the texel on the other side of the fold.
+ * INVERSE.  u = s * 2 - 1,  v = t * 2 - 1,  y = (1 - |u|) - |v|.   For y < 0:  x = (1 - |v|) * sgn(u),  z = (1 - |u|) * sgn(v);  else x = u, z = v.
+ *   r = 1 / sqrt((z * z + y * y) + x * x),  q = (x, y, z) * r,  direction = R^T q, each component (R0c * qx + R1c * qy) + R2c * qz.
+ * SOLID ANGLE.  dOmega = 4 n1^3 ds dt with n1 = r * ((|x| + |y|) + |z|), the L1 norm of the unit direction (an octahedron face lies at distance 1 / sqrt(3)
+ *   from the origin, which gives dOmega = du dv / |p|^3); J = 4 * ((n1 * n1) * n1).  The integral over the square is 4 pi.
+ *
+ * ESTIMATORS (glrtx_env_cfg::mode).  The reference estimates direct light by next-event estimation without MIS and counts emission met by a path only at
+ *   depth 0; the extension kernel also counts it behind a specular bounce.  Both modes keep that design and converge to the same image.
+ *   GLRTX_ENV_ESCAPE   wherever a path's ray misses, L += beta * Le(d), at every depth.  No extra random number, no extra ray: with a map of zeros, or scale
+ *                      0, image and ray count are those without a map, bit for bit.
+ *   GLRTX_ENV_SAMPLED  the environment is one more light of sampleDirect.  At a miss Le is added only at depth 0 or behind a specular bounce (the emitter rule).
+ *                      Light pick: rl = rand() as before; rl < p_env takes the environment, else lid = (int)(((rl - p_env) / (1 - p_env)) * nLights), clamped
+ *                      as before, and the triangle light's pdf is multiplied by (1 - p_env).  p_env = light_pick, forced to 1 for a scene without lights; with
+ *                      light_pick = 0 both expressions are the reference's exactly and so are the random stream and the image wherever no primary ray misses.
+ *                      The environment branch draws six more numbers u0 .. u5: row cj = cell(u0), cj = u1 < row_q[cj] ? cj : row_alias[cj]; column
+ *                      ci = cell(u2), k = cj * G + ci, ci = u3 < col_q[k] ? ci : col_alias[k]  (cell(u) = (int)(u * G) kept in 0 .. G - 1);
+ *                      s = (ci + u4) / G, t = (cj + u5) / G; the direction w by INVERSE; Le by RADIANCE at that (s, t);
+ *                      pdf = ((cell_p[cj * G + ci] * (G * G)) / J) * p_env;  the sample contributes Le * f * (n . w) / pdf when n . w > 0 and pdf > 0, with f
+ *                      the BSDF VALUE (diffuse: albedo / PI, textured albedo included; conductor: the block the light sample evaluates) -- not the
+ *                      reference's albedo without 1 / PI, which stays with the triangle lights, where it is pinned.  The shadow ray has no far end: the
+ *                      sample is accepted when the ray hits nothing, spheres included.  It counts as one ray.
+ *   WHY SAMPLED FOR A SUN.  The accumulation clamps each sample at 100.  In escape mode a path that finds a 50 000-nit sun is clamped: a bias.  In sampled
+ *                      mode a sample is Le f cos / pdf, bounded by the irradiance, and stays under the clamp.
+ * IMPORTANCE GRID.  G x G cells over the square; G = cfg.grid (1 .. 1024; 0: min(N, 256)).  The weight of cell (row j, column i) is the sum of
+ *   max(lum(scale * texel), 0) * J at the texel centres ((x + 0.5) / N, (y + 0.5) / N) over the texels x in max(i * N / G - 1, 0) .. min(ceil((i + 1) * N / G),
+ *   N - 1) (integer quotients) and y likewise from j: the texels that overlap the cell, WIDENED by one on every side -- a bilinear lookup inside the cell reads
+ *   no texel outside that block, so the radiance is never positive where the pdf is zero.  lum(r, g, b) = (0.2126 r + 0.7152 g) + 0.0722 b.  A weight that is
+ *   not finite counts as 0.  Order of the sum (env_weights_kernel, one wave a cell): partial sum k of 64 adds the block's texels k, k + 64, .. (row-major in
+ *   the block) in that order from 0; then p[k] += p[k + h] for h = 32, 16, .. 1.  The tables are built on the host from those weights: Vose's alias method in
+ *   float64 in a stated order (host/env_tables.h), thresholds rounded once to fp32; a row table over the rows' sums, one column table a row,
+ *   cell_p = (float)(w / total).  An all-zero grid is legal: sampled mode then never contributes, and the miss rule still applies.
+ *
+ *   glrtx_upload_environment   copies the map and builds the tables; map == NULL unbinds (the context renders as before, variant_last back to what it was).  The
+ *                     map does not depend on the scene and is KEPT across glrtx_upload_scene, as the volume is.
+ *   glrtx_set_environment_cfg  changes the configuration of the bound environment: mode, light_pick and rotation freely (the weights do not depend on them); scale or grid rebuild the tables.
+ *                     Both: GLRTX_EINVAL, everything unchanged, the offender named in the message, for a NULL context or configuration; a map that is not square
+ *                     or smaller than 2 x 2; a wrap other than clamp; anything glrtx_upload_textures refuses of a descriptor; a mode other than 0 or 1; grid
+ *                     outside 0 .. 1024; light_pick outside [0, 1] or NaN; a scale or rotation entry that is not finite, or a negative scale;
+ *                     glrtx_set_environment_cfg with no environment bound.
+ *   While an environment is bound these refuse with GLRTX_EINVAL and a message that says "an environment is bound": rendering with GLRTX_EXT_VOLUME set (the volume
+ *                     branch has its own escape path), glrtx_render_adaptive*, glrtx_render_moments, glrtx_render_cascades and glrtx_hit_histogram (the
+ *                     wavefront kernel's calls).  The present ring works as it does with spheres.  The feature pass is unchanged: a miss pixel keeps what it has.
+ *   glrtx_debug_env_weights / _sample / _eval   the device statements on caller arrays on the current HIP device, no context.  weights_out: G * G floats,
+ *                     *grid_out = G.  sample: out[8i..] = {direction, pdf, Le.rgb, 0} of the six uniforms u[6i..], with p_env = cfg.light_pick.  eval:
+ *                     out[4i..] = {Le.rgb, pdf} of the direction dir[3i..].  They refuse what glrtx_upload_environment refuses.  Errors through glrtx_last_error(NULL).
+ * NOT BUILT: seam-correct filtering, MIS between the two estimators, an environment beside the volume or under the wavefront kernel, the background in the
+ *   feature planes and denoisers.  Groups: no call; a member is reached through glrtx_group_ctx(grp, i). */
+enum glrtx_env_mode { GLRTX_ENV_ESCAPE = 0, GLRTX_ENV_SAMPLED = 1 };
+typedef struct glrtx_env_cfg { int32_t mode; int32_t grid; float light_pick; float scale[3]; float rotation[9]; } glrtx_env_cfg;
+int glrtx_upload_environment(glrtx_ctx *ctx, const glrtx_texture *map, const void *texels, size_t texel_bytes, const glrtx_env_cfg *cfg);
+int glrtx_set_environment_cfg(glrtx_ctx *ctx, const glrtx_env_cfg *cfg);
+int glrtx_debug_env_weights(const glrtx_texture *map, const void *texels, size_t texel_bytes, const glrtx_env_cfg *cfg, float *weights_out, int32_t *grid_out);
+int glrtx_debug_env_sample(const glrtx_texture *map, const void *texels, size_t texel_bytes, const glrtx_env_cfg *cfg, const float *u, size_t n, float *out);
+int glrtx_debug_env_eval(const glrtx_texture *map, const void *texels, size_t texel_bytes, const glrtx_env_cfg *cfg, const float *dir, size_t n, float *out);
+
 /* ---- Groups: the same device layer on several GPUs of one node, behind one handle and one host thread.
  * No reference counterpart (the reference is single-GPU); SURVEY.md 8(b) sketches glrtx_create(ctx**, device_ids, n) with a
  * gathering read_accum -- this is that, kept apart from the single-context calls.  Member i owns the 8-row stripes s with

@@ -37,6 +37,7 @@
 #include "../host/morph_sparse.h"
 #include "../host/normal_topology.h"
 #include "../host/texture_set.h"
+#include "../host/env_tables.h"
 static_assert(glrtx::lbvh::kRotationPasses == GLRT_LBVH_ROTATION_PASSES, "device and CPU LBVH statements must run the same rotation sweeps");
 static_assert(glrtx::lbvh::kRebuildLeaves == GLRT_LBVH_REBUILD_LEAVES, "device and CPU LBVH statements must rebuild the same subtrees");
 
@@ -106,6 +107,12 @@ struct glrtx_ctx {
     DevBuf texDesc, texTexels, texSt, texBind;
     int n_tex = 0;
     std::vector<float> scene_st;
+    // Environment (glrtx_upload_environment; environment.hip.h), kept across glrtx_upload_scene: the map's texels, the importance grid's five tables, and what the
+    // kernels take of it (env: its pointers are these buffers'; p_env is set at every launch).  env_cfg / env_desc: what it was made from.
+    DevBuf envTexels, envRowQ, envRowAlias, envColQ, envColAlias, envCellP;
+    EnvArgs env{};
+    glrtx_env_cfg env_cfg{};
+    bool have_env = false;
     DevBuf volDensity, volTemp;  // volume kernel (GLRTX_EXT_VOLUME): the two grids of glrtx_upload_volume
     VolArgs vol{};
     bool have_volume = false;
@@ -1006,7 +1013,7 @@ TexSet tex_set(const glrtx_ctx *c) {
 bool vol_wavefront(const glrtx_ctx *c) {
     bool on = c->vol_wavefront;
     if (const char *v = std::getenv("GLRTX_VOLUME_WAVEFRONT")) on = std::atoi(v) != 0;
-    return on && c->ext_flags == GLRTX_EXT_VOLUME && c->have_volume && c->n_spheres == 0 && c->n_tex == 0;  // (textures are shaded by the megakernel only)
+    return on && c->ext_flags == GLRTX_EXT_VOLUME && c->have_volume && c->n_spheres == 0 && c->n_tex == 0 && !c->have_env;  // (textures and the environment are shaded by the megakernel only)
 }
 
 // Whether the wavefront variant's packed path state can represent this launch (meta = depth | sample << 8 | flags << 28; the V form: sample in bits 8-23).
@@ -1014,7 +1021,7 @@ bool wgwf_can_hold(const glrtx_params *p, bool vol = false) { return p->max_dept
 
 // Whether a launch of this context runs on the wavefront kernel (variant 2): no extensions, or the volume alone with the V form switched on.
 bool wgwf_routes(const glrtx_ctx *c, const glrtx_params *p) {
-    if (c->variant != 2 || c->n_spheres > 0 || c->n_tex > 0) return false;
+    if (c->variant != 2 || c->n_spheres > 0 || c->n_tex > 0 || c->have_env) return false;
     if (c->ext_flags == 0) return wgwf_can_hold(p);
     return vol_wavefront(c) && wgwf_can_hold(p, true);
 }
@@ -1881,6 +1888,7 @@ int adapt_check(glrtx_ctx *c, const glrtx_params *p, const float *seeds_xy, int 
     if (c->ext_flags != 0 && !vol) return fail(c, GLRTX_EINVAL, "%s: extensions or volume are on (only the wavefront kernel has a tile list)", fn);
     if (c->n_spheres > 0) return fail(c, GLRTX_EINVAL, "%s: spheres are uploaded (only the wavefront kernel has a tile list)", fn);
     if (c->n_tex > 0) return fail(c, GLRTX_EINVAL, "%s: textures are bound (only the wavefront kernel has a tile list)", fn);
+    if (c->have_env) return fail(c, GLRTX_EINVAL, "%s: an environment is bound (only the wavefront kernel has a tile list)", fn);
     if (c->variant != 2) return fail(c, GLRTX_EINVAL, "%s: variant %d (only the wavefront kernel, variant 2, has a tile list)", fn, c->variant);
     if (!wgwf_can_hold(p, vol)) return fail(c, GLRTX_EINVAL, "%s: max_depth %d / n_samples %d beyond the wavefront kernel's path state", fn, p->max_depth, p->n_samples);
     return GLRTX_OK;
@@ -1926,6 +1934,7 @@ int side_plane_check(glrtx_ctx *c, const glrtx_params *p, const float *seeds_xy,
     if (c->ext_flags != 0) return fail(c, GLRTX_EINVAL, "%s: extensions or volume are on", fn);
     if (c->n_spheres > 0) return fail(c, GLRTX_EINVAL, "%s: spheres are uploaded", fn);
     if (c->n_tex > 0) return fail(c, GLRTX_EINVAL, "%s: textures are bound (the megakernel that shades them writes no sample planes)", fn);
+    if (c->have_env) return fail(c, GLRTX_EINVAL, "%s: an environment is bound (the megakernel that shades it writes no sample planes)", fn);
     if (c->variant != 2) return fail(c, GLRTX_EINVAL, "%s: variant %d (only the wavefront kernel, variant 2, writes sample planes)", fn, c->variant);
     if (!wgwf_can_hold(p, false)) return fail(c, GLRTX_EINVAL, "%s: max_depth %d / n_samples %d beyond the wavefront kernel's path state", fn, p->max_depth, p->n_samples);
     return GLRTX_OK;
@@ -2224,6 +2233,7 @@ void glrtx_destroy(glrtx_ctx *c) {
         if (sl.feed_h) (void)hipHostFree(sl.feed_h);
     }
     dev_free(c->texDesc); dev_free(c->texTexels); dev_free(c->texSt); dev_free(c->texBind);
+    for (DevBuf *b : {&c->envTexels, &c->envRowQ, &c->envRowAlias, &c->envColQ, &c->envColAlias, &c->envCellP}) dev_free(*b);
     dev_free(c->spheres); dev_free(c->sphereMat); dev_free(c->volDensity); dev_free(c->volTemp); dev_free(c->forks); dev_free(c->cnodes); dev_free(c->cranks); dev_free(c->nrms); dev_free(c->mats); dev_free(c->lights); dev_free(c->vine);
     dev_free(c->accum_own); dev_free(c->counter); dev_free(c->rgba8); dev_free(c->work);
     c->adHalf.drop(); dev_free(c->adMask); dev_free(c->adList); dev_free(c->adCount);
@@ -3216,6 +3226,184 @@ int glrtx_debug_texture_lookup(const glrtx_texture *tex, size_t n_tex, const voi
     s.sync();
     s.download(rgb_out, d_out, 3 * n * sizeof(float));
     return s.result(GLRTX_OK, fn);
+}
+
+}  // extern "C"
+
+// ---- environment (glrtx_upload_environment, glrtx_set_environment_cfg, glrtx_debug_env_*; environment.hip.h)
+namespace {
+static_assert(sizeof(glrtx_env_cfg) == sizeof(glrt_detail::EnvCfg), "one environment configuration on the wire, the host and the device");
+static_assert(GLRTX_ENV_ESCAPE == ENV_ESCAPE && GLRTX_ENV_SAMPLED == ENV_SAMPLED && glrt_detail::kEnvGridMax == kEnvGridMax, "environment constants");
+
+// An environment on the device: the map's texels, the five tables, and the kernels' view of them
+struct EnvDevice {
+    DevBuf texels, row_q, row_alias, col_q, col_alias, cell_p;
+    EnvArgs args{};
+    void free_all() {
+        for (DevBuf *b : {&texels, &row_q, &row_alias, &col_q, &col_alias, &cell_p}) dev_free(*b);
+    }
+};
+
+// The configuration's part of EnvArgs, and the tables of the map at ed.texels: the weights kernel on `st`, Vose's method on the host, five uploads.
+// weights_out (optional): the G * G cell weights.  The texels must be on the device already; on failure the caller frees ed.
+int env_configure(glrtx_ctx *c, hipStream_t st, EnvDevice &ed, const glrtx_texture &map, const glrtx_env_cfg &cfg, float *weights_out) {
+    EnvArgs &ea = ed.args;
+    std::memcpy(&ea.desc, &map, sizeof ea.desc);
+    ea.desc.offset = 0;
+    ea.texels = (const unsigned char *)ed.texels.p;
+    std::memcpy(ea.R, cfg.rotation, sizeof ea.R);
+    std::memcpy(ea.scale, cfg.scale, sizeof ea.scale);
+    ea.mode = cfg.mode;
+    ea.p_env = cfg.light_pick;
+    const int G = glrt_detail::env_grid(cfg.grid, map.width);
+    ea.G = G;
+    const size_t cells = (size_t)G * (size_t)G;
+    DevBuf w;
+    if (int rc = ensure(c, w, cells * sizeof(float))) return rc;
+    hipLaunchKernelGGL(env_weights_kernel, dim3((unsigned)G, (unsigned)G), dim3(kEnvWeightThreads), 0, st, ea, (float *)w.p);
+    std::vector<float> weights(cells);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = hipMemcpy(weights.data(), w.p, cells * sizeof(float), hipMemcpyDeviceToHost);
+    dev_free(w);
+    if (e != hipSuccess) return fail(c, GLRTX_EDEVICE, "env_weights_kernel: %s", hipGetErrorString(e));
+    if (weights_out) std::memcpy(weights_out, weights.data(), cells * sizeof(float));
+    const glrt_detail::EnvTables t = glrt_detail::env_tables(weights.data(), G);
+    int rc;
+    if ((rc = dev_upload(c, ed.row_q, t.row_q.data(), (size_t)G * sizeof(float))) || (rc = dev_upload(c, ed.row_alias, t.row_alias.data(), (size_t)G * sizeof(int32_t))) ||
+        (rc = dev_upload(c, ed.col_q, t.col_q.data(), cells * sizeof(float))) || (rc = dev_upload(c, ed.col_alias, t.col_alias.data(), cells * sizeof(int32_t))) ||
+        (rc = dev_upload(c, ed.cell_p, t.cell_p.data(), cells * sizeof(float))))
+        return rc;
+    ea.row_q = (const float *)ed.row_q.p; ea.row_alias = (const int *)ed.row_alias.p;
+    ea.col_q = (const float *)ed.col_q.p; ea.col_alias = (const int *)ed.col_alias.p;
+    ea.cell_p = (const float *)ed.cell_p.p;
+    return GLRTX_OK;
+}
+
+size_t env_map_bytes(const glrtx_texture &map) { return (size_t)map.width * (size_t)map.height * glrt_detail::tex_texel_bytes(map.format); }
+
+// What the three debug hooks share: the refusals, the map and its tables on the current device
+int env_debug_setup(const char *fn, EnvDevice &ed, const glrtx_texture *map, const void *texels, size_t texel_bytes, const glrtx_env_cfg *cfg, float *weights_out) {
+    const std::string bad = glrt_detail::env_error(reinterpret_cast<const glrt_detail::TexRecord *>(map), texels, texel_bytes, reinterpret_cast<const glrt_detail::EnvCfg *>(cfg));
+    if (!bad.empty()) return fail(nullptr, GLRTX_EINVAL, "%s: %s", fn, bad.c_str());
+    if (int rc = dev_upload(nullptr, ed.texels, (const unsigned char *)texels + map->offset, env_map_bytes(*map))) return rc;
+    return env_configure(nullptr, nullptr, ed, *map, *cfg, weights_out);
+}
+
+// The bound environment replaced by ed (the stream is idle)
+void env_adopt(glrtx_ctx *c, EnvDevice &ed, const glrtx_env_cfg &cfg, bool keep_texels) {
+    if (!keep_texels) { dev_free(c->envTexels); c->envTexels = ed.texels; }
+    dev_free(c->envRowQ); dev_free(c->envRowAlias); dev_free(c->envColQ); dev_free(c->envColAlias); dev_free(c->envCellP);
+    c->envRowQ = ed.row_q; c->envRowAlias = ed.row_alias; c->envColQ = ed.col_q; c->envColAlias = ed.col_alias; c->envCellP = ed.cell_p;
+    c->env = ed.args;
+    c->env_cfg = cfg;
+    c->have_env = true;
+}
+}  // namespace
+
+extern "C" {
+int glrtx_upload_environment(glrtx_ctx *c, const glrtx_texture *map, const void *texels, size_t texel_bytes, const glrtx_env_cfg *cfg) {
+    const char *fn = "glrtx_upload_environment";
+    if (!c) return fail(nullptr, GLRTX_EINVAL, "%s: NULL context", fn);
+    seal_feed(c);  // (nothing is appended to an open launch across this call: glrtx_ctx::OpenFeed)
+    if (!map) {  // unbind: the next launch is routed as before (the buffers stay until the context goes or another map comes)
+        HIP_TRY(c, hipSetDevice(c->device));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        c->have_env = false;
+        return GLRTX_OK;
+    }
+    const std::string bad = glrt_detail::env_error(reinterpret_cast<const glrt_detail::TexRecord *>(map), texels, texel_bytes, reinterpret_cast<const glrt_detail::EnvCfg *>(cfg));
+    if (!bad.empty()) return fail(c, GLRTX_EINVAL, "%s: %s", fn, bad.c_str());
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));  // (also behind every launch that reads an environment bound before)
+    // fresh buffers first, the context's own replaced only once all are filled: a failure leaves the bound environment as it was
+    EnvDevice ed;
+    int rc = dev_upload(c, ed.texels, (const unsigned char *)texels + map->offset, env_map_bytes(*map));
+    if (!rc) rc = env_configure(c, c->stream, ed, *map, *cfg, nullptr);
+    if (rc) { ed.free_all(); return rc; }
+    env_adopt(c, ed, *cfg, false);
+    return GLRTX_OK;
+}
+
+int glrtx_set_environment_cfg(glrtx_ctx *c, const glrtx_env_cfg *cfg) {
+    const char *fn = "glrtx_set_environment_cfg";
+    if (!c) return fail(nullptr, GLRTX_EINVAL, "%s: NULL context", fn);
+    seal_feed(c);  // (nothing is appended to an open launch across this call: glrtx_ctx::OpenFeed)
+    const std::string bad = glrt_detail::env_error(nullptr, nullptr, 0, reinterpret_cast<const glrt_detail::EnvCfg *>(cfg), false);
+    if (!bad.empty()) return fail(c, GLRTX_EINVAL, "%s: %s", fn, bad.c_str());
+    if (!c->have_env) return fail(c, GLRTX_EINVAL, "%s: no environment is bound (glrtx_upload_environment)", fn);
+    const glrtx_env_cfg &old = c->env_cfg;
+    const bool rebuild = std::memcmp(old.scale, cfg->scale, sizeof old.scale) != 0 || glrt_detail::env_grid(old.grid, c->env.desc.width) != glrt_detail::env_grid(cfg->grid, c->env.desc.width);
+    if (!rebuild) {  // mode, light_pick, rotation: kernel arguments of the next launch
+        c->env.mode = cfg->mode;
+        std::memcpy(c->env.R, cfg->rotation, sizeof c->env.R);
+        c->env_cfg = *cfg;
+        return GLRTX_OK;
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    EnvDevice ed;
+    ed.texels = c->envTexels;  // (borrowed: the map stays)
+    glrtx_texture map;
+    std::memcpy(&map, &c->env.desc, sizeof map);
+    const int rc = env_configure(c, c->stream, ed, map, *cfg, nullptr);
+    if (rc) { ed.texels = DevBuf{}; ed.free_all(); return rc; }
+    env_adopt(c, ed, *cfg, true);
+    return GLRTX_OK;
+}
+
+int glrtx_debug_env_weights(const glrtx_texture *map, const void *texels, size_t texel_bytes, const glrtx_env_cfg *cfg, float *weights_out, int32_t *grid_out) {
+    const char *fn = "glrtx_debug_env_weights";
+    if (!weights_out || !grid_out) return fail(nullptr, GLRTX_EINVAL, "%s: NULL output", fn);
+    EnvDevice ed;
+    const int rc = env_debug_setup(fn, ed, map, texels, texel_bytes, cfg, weights_out);
+    if (!rc) *grid_out = ed.args.G;
+    ed.free_all();
+    return rc;
+}
+
+int glrtx_debug_env_sample(const glrtx_texture *map, const void *texels, size_t texel_bytes, const glrtx_env_cfg *cfg, const float *u, size_t n, float *out) {
+    const char *fn = "glrtx_debug_env_sample";
+    if (n && (!u || !out)) return fail(nullptr, GLRTX_EINVAL, "%s: NULL buffer", fn);
+    if (n > (size_t)INT32_MAX / 8) return fail(nullptr, GLRTX_EINVAL, "%s: too many samples", fn);
+    EnvDevice ed;
+    int rc = env_debug_setup(fn, ed, map, texels, texel_bytes, cfg, nullptr);
+    if (!rc && n) {
+        DebugScratch s;
+        const float *d_u = s.alloc<float>(6 * n * sizeof(float), u);
+        float *d_out = s.alloc<float>(8 * n * sizeof(float));
+        if (s.ok()) {
+            hipLaunchKernelGGL(env_sample_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, ed.args, d_u, (unsigned)n, d_out);
+            s.e = hipGetLastError();
+        }
+        s.sync();
+        s.download(out, d_out, 8 * n * sizeof(float));
+        rc = s.result(GLRTX_OK, fn);
+    }
+    ed.free_all();
+    return rc;
+}
+
+int glrtx_debug_env_eval(const glrtx_texture *map, const void *texels, size_t texel_bytes, const glrtx_env_cfg *cfg, const float *dir, size_t n, float *out) {
+    const char *fn = "glrtx_debug_env_eval";
+    if (n && (!dir || !out)) return fail(nullptr, GLRTX_EINVAL, "%s: NULL buffer", fn);
+    if (n > (size_t)INT32_MAX / 4) return fail(nullptr, GLRTX_EINVAL, "%s: too many directions", fn);
+    EnvDevice ed;
+    int rc = env_debug_setup(fn, ed, map, texels, texel_bytes, cfg, nullptr);
+    if (!rc && n) {
+        DebugScratch s;
+        const float *d_dir = s.alloc<float>(3 * n * sizeof(float), dir);
+        float *d_out = s.alloc<float>(4 * n * sizeof(float));
+        if (s.ok()) {
+            hipLaunchKernelGGL(env_eval_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, ed.args, d_dir, (unsigned)n, d_out);
+            s.e = hipGetLastError();
+        }
+        s.sync();
+        s.download(out, d_out, 4 * n * sizeof(float));
+        rc = s.result(GLRTX_OK, fn);
+    }
+    ed.free_all();
+    return rc;
 }
 
 int glrtx_set_extensions(glrtx_ctx *c, int flags) {
@@ -4419,6 +4607,8 @@ static int render_one(glrtx_ctx *c, const glrtx_params *p, const RenderReq &req)
     if (!c->accum || c->width < 1) return fail(c, GLRTX_EINVAL, "glrtx_render: no accumulator (call glrtx_resize)");
     if (p->n_samples < 0 || p->max_depth < 0) return fail(c, GLRTX_EINVAL, "glrtx_render: negative n_samples/max_depth");
     if ((c->ext_flags & GLRTX_EXT_VOLUME) && !c->have_volume) return fail(c, GLRTX_EINVAL, "glrtx_render: GLRTX_EXT_VOLUME is set and no volume is uploaded (glrtx_upload_volume)");
+    if ((c->ext_flags & GLRTX_EXT_VOLUME) && c->have_env)
+        return fail(c, GLRTX_EINVAL, "glrtx_render: GLRTX_EXT_VOLUME is set and an environment is bound (the volume branch has its own escape path)");
     HIP_TRY(c, hipSetDevice(c->device));
     const bool wavefront = wgwf_routes(c, p);
     if (c->owned_rows > 0 && wavefront && req.kind == RenderReq::Ordinary && req.n_frames == 1 && feed_append(c, p, p->seed, 1) == 1) {  // a launch of the same camera that is still open takes the frame itself
@@ -4461,7 +4651,8 @@ static int render_one(glrtx_ctx *c, const glrtx_params *p, const RenderReq &req)
     // Extensions (analytic spheres, dielectric, Whitted termination) exist only in the persistent megakernel's EXT instantiation.
     // The volume alone goes to the wavefront kernel's V form when that is switched on (glrtx_set_volume_wavefront), within its narrower sample range (kWfVolSampleMax).
     const bool tex = c->n_tex > 0;  // a bound texture set: the extension megakernel's textured instantiations (pt_render_persistent_tex)
-    const bool ext = c->n_spheres > 0 || c->ext_flags != 0 || tex;
+    const bool envb = c->have_env;  // a bound environment: the extension megakernel's environment instantiations (pt_render_persistent_env)
+    const bool ext = c->n_spheres > 0 || c->ext_flags != 0 || tex || envb;
     const bool vol_wf = vol_wavefront(c);
     const int variant = ((ext && !vol_wf) || (vol_wf && c->variant != 2) || (c->variant == 2 && !wgwf_can_hold(p, vol_wf))) ? 1 : c->variant;
     c->st.variant_last = variant;
@@ -4490,16 +4681,22 @@ static int render_one(glrtx_ctx *c, const glrtx_params *p, const RenderReq &req)
         static constexpr const char *kPersistentTexNames[2] = {"pt_render_persistent (extensions, textures)", "pt_render_persistent (volume, textures)"};
         const bool vol = (c->ext_flags & GLRTX_EXT_VOLUME) != 0;  // (render_one has checked that a volume is uploaded)
         const int which = vol ? 2 : ext ? 1 : 0;
-        const PKernel pk = tex ? kPersistentTex[vol][c->count_rays] : kPersistent[which][c->count_rays];
+        using EKernel = void (*)(const KernelArgs, unsigned *, const ExtArgs, const EnvArgs);
+        static constexpr EKernel kPersistentEnv[2][2] = {{pt_render_persistent_env<false, false>, pt_render_persistent_env<true, false>},  // [textures][count_rays]
+                                                         {pt_render_persistent_env<false, true>, pt_render_persistent_env<true, true>}};
+        static constexpr const char *kPersistentEnvNames[2] = {"pt_render_persistent (extensions, environment)", "pt_render_persistent (extensions, environment, textures)"};
+        const EKernel ek = kPersistentEnv[tex][c->count_rays];
+        const PKernel pk = envb ? (PKernel) nullptr : tex ? kPersistentTex[vol][c->count_rays] : kPersistent[which][c->count_rays];
+        const void *kfn = envb ? (const void *)ek : (const void *)pk;
         ExtArgs ex{};
         if (tex) ex.tex = tex_set(c);
         ex.spheres = (const float4 *)c->spheres.p; ex.sphere_mat = (const int *)c->sphereMat.p;
         ex.n_spheres = c->n_spheres; ex.flags = c->ext_flags;
         const int lds_p = lds + (ext ? c->n_spheres * (int)sizeof(float4) : 0);  // extension kernel: the spheres are staged behind the stacks
         if (lds_p > 160 * 1024) return fail(c, GLRTX_EDEVICE, "render kernel needs %d B of LDS (> 160 KiB)", lds_p);
-        if (lds_p > 64 * 1024) HIP_TRY(c, hipFuncSetAttribute((const void *)pk, hipFuncAttributeMaxDynamicSharedMemorySize, lds_p));
+        if (lds_p > 64 * 1024) HIP_TRY(c, hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_p));
         int per_cu = 0;
-        HIP_TRY(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, pk, kBlockThreads, lds_p));
+        HIP_TRY(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kfn, kBlockThreads, lds_p));
         if (per_cu < 1) per_cu = 1;
         const int tiles8 = ((c->width + 7) / 8) * ((c->owned_rows + 7) / 8);
         const int n_chunks = (tiles8 * 64 + kChunk - 1) / kChunk;
@@ -4508,9 +4705,15 @@ static int render_one(glrtx_ctx *c, const glrtx_params *p, const RenderReq &req)
         if (grid < 1) grid = 1;
         HIP_TRY(c, hipMemsetAsync(c->work.p, 0, sizeof(unsigned), c->stream));
         HIP_TRY(c, hipEventRecord(rec->ev0, c->stream));
-        c->last_kernel = tex ? kPersistentTexNames[vol] : kPersistentNames[which];
+        c->last_kernel = envb ? kPersistentEnvNames[tex] : tex ? kPersistentTexNames[vol] : kPersistentNames[which];
         const VolArgs va = vol ? c->vol : VolArgs{};
-        hipLaunchKernelGGL(pk, dim3(grid), dim3(kBlockThreads), lds_p, c->stream, a, (unsigned *)c->work.p, ex, va);
+        if (envb) {
+            EnvArgs ea = c->env;
+            ea.p_env = c->sc.n_light == 0 ? 1.0f : c->env_cfg.light_pick;  // a scene without lights: the environment is the only light to pick
+            hipLaunchKernelGGL(ek, dim3(grid), dim3(kBlockThreads), lds_p, c->stream, a, (unsigned *)c->work.p, ex, ea);
+        } else {
+            hipLaunchKernelGGL(pk, dim3(grid), dim3(kBlockThreads), lds_p, c->stream, a, (unsigned *)c->work.p, ex, va);
+        }
     } else {
         static constexpr void (*kTileKernel[2])(const KernelArgs) = {pt_render_kernel<false>, pt_render_kernel<true>};  // [count_rays]
         const auto tk = kTileKernel[c->count_rays];
@@ -4616,6 +4819,7 @@ int glrtx_hit_histogram(glrtx_ctx *c, const glrtx_params *p, uint32_t *hist_out,
     if (!c->accum || c->width < 1 || c->owned_rows < 1) return fail(c, GLRTX_EINVAL, "glrtx_hit_histogram: no image size (call glrtx_resize)");
     if (n_tri != (size_t)c->n_tri) return fail(c, GLRTX_EINVAL, "glrtx_hit_histogram: the scene has %d triangles, room for %zu", c->n_tri, n_tri);
     if (c->n_tex > 0) return fail(c, GLRTX_EINVAL, "glrtx_hit_histogram: textures are bound (wavefront kernel only)");
+    if (c->have_env) return fail(c, GLRTX_EINVAL, "glrtx_hit_histogram: an environment is bound (wavefront kernel only)");
     if (c->variant != 2 || !wgwf_can_hold(p) || c->n_spheres > 0 || c->ext_flags != 0) return fail(c, GLRTX_EINVAL, "glrtx_hit_histogram: wavefront kernel only");
     HIP_TRY(c, hipSetDevice(c->device));
     if (int rc = glrtx_sync(c)) return rc;

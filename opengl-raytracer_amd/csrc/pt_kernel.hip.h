@@ -38,6 +38,7 @@
 #include "trav_asm.hip.h"
 #include "scan_asm.hip.h"
 #include "texture.hip.h"
+#include "environment.hip.h"
 
 namespace glrtx {
 
@@ -880,6 +881,7 @@ struct Shade {
     float Lfx, Lfy, Lfz;  // L with it rejected
     bool untraced;        // the reference traces a shadow ray here, but both outcomes give the same L bit for bit (no
                           // contribution: a cosine <= 0, or one too small to register): counted as a ray, not traced
+    bool env_shadow;      // environment instantiations only: the shadow ray has no far end -- the sample is accepted when the ray hits NOTHING
 };
 
 // Surface at a hit: shading normal and material.  surf_tri() is the reference's (:254 and the triangle's material id);
@@ -910,10 +912,14 @@ constexpr int EXT_WHITTED = 2;     // Whitted-style: a diffuse surface gathers i
 
 // TEX (implies EXT; include/glrtx.h "Textures"): `textured` says that the hit's diffuse material is bound to a texture and (ar, ag, ab) is the albedo looked up at the
 // hit, which then stands wherever the reference reads param0 (:514 with its 1 / PI, :372 without).
-template <bool EXT, bool TEX = false>
+// ENV (implies EXT; include/glrtx.h "Environment"): *env is the bound environment.  A miss adds beta * Le(d) -- at every depth in escape mode, under the emitter
+// rule (:490) in sampled mode --, and in sampled mode the environment is one more light of sampleDirect, picked with probability env->p_env.
+template <bool EXT, bool TEX = false, bool ENV = false>
 DEV void shade_core(const KernelArgs &a, const float4 *lds_mats, Rng &rng, Path &P, float h_t, bool h_hit, const Surf &S, int ext_flags, Shade &out,
-                    bool textured = false, float ar = 0.f, float ag = 0.f, float ab = 0.f) {
+                    bool textured = false, float ar = 0.f, float ag = 0.f, float ab = 0.f, const EnvArgs *env = nullptr) {
     static_assert(!TEX || EXT, "textures are shaded by the extension kernel");
+    static_assert(!ENV || EXT, "the environment is shaded by the extension kernel");
+    bool env_shadow = false;
     const DevScene &sc = a.sc;
     float ox = P.ox, oy = P.oy, oz = P.oz, dx = P.dx, dy = P.dy, dz = P.dz;
     float bx = P.bx, by = P.by, bz = P.bz;
@@ -928,6 +934,10 @@ DEV void shade_core(const KernelArgs &a, const float4 *lds_mats, Rng &rng, Path 
 
     bool spec_out = false, stop_after = false;
     do {
+        if (ENV && !h_hit && (env->mode == ENV_ESCAPE || depth == 0 || P.spec)) {  // the ray leaves the scene: L += beta * Le(d)
+            const float3 le = env_radiance(*env, dx, dy, dz);
+            Lx = Lx + bx * le.x; Ly = Ly + by * le.y; Lz = Lz + bz * le.z;
+        }
         if (!h_hit) break;  // miss: nothing is added and the loop ends (:497-499)
         const float nx = S.nx, ny = S.ny, nz = S.nz;
         const Mat M = load_mat(sc, lds_mats, S.mtrl);
@@ -1077,7 +1087,47 @@ DEV void shade_core(const KernelArgs &a, const float4 *lds_mats, Rng &rng, Path 
             {
                 const float rl = pt_rand(rng);
                 int lid = (int)(rl * nLf);
+                const bool env_on = ENV && env->mode == ENV_SAMPLED;
+                if (env_on) lid = (int)(((rl - env->p_env) / (1.0f - env->p_env)) * nLf);  // (p_env = 0: (rl - 0) / 1 = rl)
                 lid = (sc.n_light - 1 < lid) ? sc.n_light - 1 : lid;
+                if (env_on && rl < env->p_env) {
+                    // ---- the environment as the light: a cell of the importance grid, a direction inside it, Le f max(n . w, 0) / pdf with f the BSDF value itself
+                    const float e0 = pt_rand(rng), e1 = pt_rand(rng), e2 = pt_rand(rng), e3 = pt_rand(rng), e4 = pt_rand(rng), e5 = pt_rand(rng);
+                    float dirx, diry, dirz, epdf;
+                    const float3 le = env_sample(*env, e0, e1, e2, e3, e4, e5, dirx, diry, dirz, epdf);
+                    has_shadow = true;
+                    env_shadow = true;
+                    sdx = dirx; sdy = diry; sdz = dirz;
+                    sdist = PT_INFTY;
+                    float gx = fx, gy = fy, gz = fz;  // diffuse: albedo / PI (textured albedo included)
+                    if (type == 3) {
+                        const float ax = M.m1.w, ay = M.m2.w;
+                        const float cosI = fmax_c((-(dirz * nz) - (diry * ny)) - (dirx * nx), 0.0f);
+                        const float c2 = cosI * cosI, s2 = 1.0f - c2;
+                        const float Fx = fresnel1(c2, s2, cosI, M.m2.x, M.m1.x);
+                        const float Fy = fresnel1(c2, s2, cosI, M.m2.y, M.m1.y);
+                        const float Fz = fresnel1(c2, s2, cosI, M.m2.z, M.m1.z);
+                        const float ilx = (uz * dirz - nuy * diry) + ux * dirx;
+                        const float ily = (vz * dirz + vy * diry) + vx * dirx;
+                        const float ilz = (dirz * nz + diry * ny) + dirx * nx;
+                        const float hx = ilx + wox, hy = ily + woy, hz = ilz + woz;
+                        const float rh = rsq((hz * hz + hy * hy) + hx * hx);
+                        const float D = ggx(hx * rh, hy * rh, hz * rh, ax, ay);
+                        const float wisx = ilx * ax, wisy = ily * ay;
+                        const float len_wi = __builtin_sqrtf((ilz * ilz + wisy * wisy) + wisx * wisx);
+                        const float wosx = wox * ax, wosy = woy * ay;
+                        const float len_wo = __builtin_sqrtf((woz * woz + wosy * wosy) + wosx * wosx);
+                        const float den = 2.0f * (__builtin_fabsf(woz) * len_wi + __builtin_fabsf(ilz) * len_wo);
+                        const float brdf = fdiv(D, den);
+                        gx = Fx * brdf; gy = Fy * brdf; gz = Fz * brdf;
+                    }
+                    const float dot0 = (dirz * nz + diry * ny) + dirx * nx;
+                    if (0.0f < dot0 && 0.0f < epdf) {
+                        cx = fdiv((le.x * gx) * dot0, epdf);
+                        cy = fdiv((le.y * gy) * dot0, epdf);
+                        cz = fdiv((le.z * gz) * dot0, epdf);
+                    }
+                } else {  // ---- a triangle light, :343-401 (left at its indentation: these lines are the reference's, unchanged)
                 const float ua0 = pt_rand(rng);
                 const float ub0 = pt_rand(rng);
                 const bool flip = 1.0f < ua0 + ub0;
@@ -1144,12 +1194,14 @@ DEV void shade_core(const KernelArgs &a, const float4 *lds_mats, Rng &rng, Path 
                         const float kz = e1x * e2y - e1y * e2x;
                         const float G = fdiv(dot0 * dot1, dd);  // dist*dist is folded to dd
                         const float area = 0.5f * __builtin_sqrtf((kz * kz + ky * ky) + kx * kx);
-                        const float lpdf = frcp(area * nLf);
+                        float lpdf = frcp(area * nLf);
+                        if (env_on) lpdf = lpdf * (1.0f - env->p_env);  // (p_env = 0: x * 1 = x)
                         cx = fdiv((LM.m0.x * gx) * G, lpdf);
                         cy = fdiv((LM.m0.y * gy) * G, lpdf);
                         cz = fdiv((LM.m0.z * gz) * G, lpdf);
                     }
                 }
+                }  // (a triangle light)
             }
             // :539 L += beta * sampleDirect(): both outcomes of the acceptance test
             px_ = bx * cx; py_ = by * cy; pz_ = bz * cz;
@@ -1187,6 +1239,7 @@ DEV void shade_core(const KernelArgs &a, const float4 *lds_mats, Rng &rng, Path 
     out.ended = done || P.depth >= a.max_depth;
     out.has_shadow = has_shadow;
     out.untraced = false;
+    if (ENV) out.env_shadow = env_shadow;
     out.sdx = sdx; out.sdy = sdy; out.sdz = sdz; out.dist = sdist;
     if (has_shadow) {
         out.Lpx = Lx + px_; out.Lpy = Ly + py_; out.Lpz = Lz + pz_;
@@ -1404,9 +1457,10 @@ DEV bool bounce_volume(const KernelArgs &a, const ExtArgs &ex, const VolArgs &vo
     return P.depth >= a.max_depth;
 }
 
-template <bool VOL = false, bool TEX = false>
+template <bool VOL = false, bool TEX = false, bool ENV = false>
 DEV bool bounce_ext(const KernelArgs &a, const ExtArgs &ex, const float4 *lds_spheres, const float4 *lds_mats, int *stack, Rng &rng, Path &P, unsigned long long &rays,
-                    const VolArgs *vo = nullptr) {
+                    const VolArgs *vo = nullptr, const EnvArgs *env = nullptr) {
+    static_assert(!(ENV && VOL), "the volume branch has its own escape path: no environment beside it");
     const Hit h = traverse_ext<true>(a.sc, ex, lds_spheres, stack, P.ox, P.oy, P.oz, P.dx, P.dy, P.dz);
     rays++;
     Surf S;
@@ -1436,12 +1490,18 @@ DEV bool bounce_ext(const KernelArgs &a, const ExtArgs &ex, const float4 *lds_sp
                 textured = true;
             }
         }
-        shade_core<true, true>(a, lds_mats, rng, P, h.t, h.tri != -1, S, ex.flags, sh, textured, alb.x, alb.y, alb.z);
+        shade_core<true, true, ENV>(a, lds_mats, rng, P, h.t, h.tri != -1, S, ex.flags, sh, textured, alb.x, alb.y, alb.z, env);
+    } else if (ENV) {
+        shade_core<true, false, true>(a, lds_mats, rng, P, h.t, h.tri != -1, S, ex.flags, sh, false, 0.f, 0.f, 0.f, env);
     } else {
         shade_core<true>(a, lds_mats, rng, P, h.t, h.tri != -1, S, ex.flags, sh);
     }
     bool ok = false;
-    if (sh.has_shadow) {
+    if (ENV && sh.has_shadow && sh.env_shadow) {  // towards the environment: any hit at all (spheres included) occludes -- the inverse of nee_accepted
+        const Hit s = traverse_ext<false>(a.sc, ex, lds_spheres, stack, P.ox, P.oy, P.oz, sh.sdx, sh.sdy, sh.sdz, PT_INFTY, PT_INFTY);
+        rays++;
+        ok = s.tri == -1;
+    } else if (sh.has_shadow) {
         const Hit s = traverse_ext<false>(a.sc, ex, lds_spheres, stack, P.ox, P.oy, P.oz, sh.sdx, sh.sdy, sh.sdz, shadow_limit(sh.dist, a.sc.shadow_limited), sh.dist);
         rays++;
         ok = nee_accepted(sh.dist, s.t, s.tri != -1);
@@ -1826,6 +1886,119 @@ __global__ __launch_bounds__(kBlockThreads) void pt_render_persistent_tex(const 
         }
     }
     flush_rays<COUNT_RAYS>(persist_kernargs()->a, rays);
+}
+
+// The extension kernel with an environment bound (include/glrtx.h "Environment"): bounce_ext<false, TEX, true> adds the environment's radiance where a ray leaves
+// the scene and, in sampled mode, draws it as a light; everything else is pt_render_persistent<*, true>.  Launched only while an environment is bound; the
+// environment's arguments take the place of the volume's in the kernarg block (the two do not combine).  The loop is written out once more for the reason
+// pt_render_persistent_tex gives: the existing instantiations are to keep their instructions.  Keep the three in step.
+struct PersistEnvKernArgs {
+    KernelArgs a;
+    unsigned *work_counter;
+    ExtArgs ex;
+    EnvArgs env;
+};
+DEV const PersistEnvKernArgs *persist_env_kernargs() {
+    auto p = __builtin_amdgcn_kernarg_segment_ptr();  // constant address space
+    asm volatile("" : "+s"(p));  // opaque: loads through it stay behind this point
+    return (const PersistEnvKernArgs *)p;
+}
+template <bool COUNT_RAYS, bool TEX>
+__global__ __launch_bounds__(kBlockThreads) void pt_render_persistent_env(const KernelArgs a_entry, unsigned *work_counter_entry, const ExtArgs ex_entry,
+                                                                          const EnvArgs env_entry) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+    float4 *lds_mats;
+    int *stack;
+    (void)work_counter_entry; (void)ex_entry; (void)env_entry;
+    lds_setup(a_entry, lds_raw, lds_mats, stack);
+    float4 *lds_spheres = ext_stage_spheres(a_entry, ex_entry, lds_raw);
+    const KernelArgs &a = persist_env_kernargs()->a;  // (re-taken inside the loop)
+
+    const int lane = threadIdx.x & 63;
+    const unsigned long long lt_mask = (1ull << lane) - 1ull;
+    const int tiles8_x = (a.width + 7) >> 3, tiles8_y = (a.owned_rows + 7) >> 3;
+    const int total = tiles8_x * tiles8_y * 64;
+
+    // wave-uniform work state
+    int chunk_next = 0, chunk_end = 0;
+    bool exhausted = false;
+    // per-lane state
+    bool alive = false, fresh = false;
+    int px_off = 0, sample = 0;
+    float fcx = 0.f, fcy = 0.f;
+    Rng rng = {0.f, 0.f, a.seed_x, a.seed_y};
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    Path P;
+    path_begin(P, 0.f, 0.f, 0.f, 0.f, 0.f, 1.f);
+    unsigned long long rays = 0;  // low half: reference rays, high half: those resolved without a traversal
+
+    for (;;) {
+        const PersistEnvKernArgs *ka = persist_env_kernargs();
+        const KernelArgs &a = ka->a;
+        unsigned *const work_counter = ka->work_counter;
+        // ---- regeneration: idle lanes take the next pixels of the wave's chunk
+        unsigned long long idle = __ballot(!alive);
+        while (idle != 0ull && !exhausted) {
+            if (chunk_next >= chunk_end) {
+                int base = 0;
+                if (lane == 0) base = (int)atomicAdd(work_counter, (unsigned)kChunk);
+                base = __builtin_amdgcn_readfirstlane(base);
+                if (base >= total) { exhausted = true; break; }
+                chunk_next = base;
+                chunk_end = base + kChunk < total ? base + kChunk : total;
+            }
+            const int n = __popcll(idle);
+            const int avail = chunk_end - chunk_next;
+            const int take = n < avail ? n : avail;
+            const int rank = __popcll(idle & lt_mask);
+            if (!alive && rank < take) {
+                const int id = chunk_next + rank;
+                const int t = id >> 6, w = id & 63;
+                const int lx = (t % tiles8_x) * 8 + (w & 7);
+                const int lrow = (t / tiles8_x) * 8 + (w >> 3);
+                if (lx < a.width && lrow < a.owned_rows && a.n_samples > 0) {
+                    const int gy = local_row_to_y(a, lrow);
+                    fcx = (float)lx + 0.5f; fcy = (float)gy + 0.5f;  // gl_FragCoord.xy
+                    rng.x = fcx / (float)a.width; rng.y = fcy / (float)a.height;  // :567
+                    px_off = lrow * a.pitch_f4 + lx;
+                    acc = a.accum[px_off];  // previous (L, count) (:570-572)
+                    sample = 0;
+                    alive = true; fresh = true;
+                }
+            }
+            chunk_next += take;
+            // still-idle lanes (chunk ran short, or the pixel drawn lies outside the image) go round again;
+            // every round consumes at least one id, so the loop ends when the image is exhausted
+            idle = __ballot(!alive);
+        }
+        if (!__any(alive)) {
+            if (exhausted) break;
+            continue;
+        }
+        // ---- one step for every live lane: (new sample ->) one bounce
+        if (alive) {
+            if (fresh) {
+                camera_ray(a, a.cam, rng, fcx, fcy, P);
+                fresh = false;
+            }
+            bool finished = true;
+            if (a.max_depth > 0) finished = bounce_ext<false, TEX, true>(a, ka->ex, lds_spheres, lds_mats, stack, rng, P, rays, nullptr, &ka->env);
+            if (finished) {
+                acc.x = acc.x + fmin_c(P.Lx, 100.0f);  // :558, :608
+                acc.y = acc.y + fmin_c(P.Ly, 100.0f);
+                acc.z = acc.z + fmin_c(P.Lz, 100.0f);
+                acc.w = acc.w + 1.0f;
+                sample++;
+                if (sample >= a.n_samples) {
+                    a.accum[px_off] = acc;
+                    alive = false;
+                } else {
+                    fresh = true;
+                }
+            }
+        }
+    }
+    flush_rays<COUNT_RAYS>(persist_env_kernargs()->a, rays);
 }
 
 // ------------------------------------------------------------------------------------------ wavefront formulation

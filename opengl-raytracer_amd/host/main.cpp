@@ -32,6 +32,9 @@ static void usage(const char *exe) {
                 "      --extensions        accept what the reference does not have: shapes of type \"sphere\" (center, radius) and the material\n"
                 "                          \"dielectric\" (ior, tint), and a diffuse shape's \"texture\": {\"file\": x.ppm | x.pfm, \"filter\", \"wrap\", \"srgb\"}\n"
                 "                          (looked up at the OBJ's vt coordinates); parity with the reference is not defined for such scenes\n"
+                "                          and the top-level \"environment\": {\"file\": x.pfm | x.ppm, \"layout\": \"latlong\" | \"octahedral\", \"size\", \"mode\", \"scale\",\n"
+                "                          \"rotate_y\", \"light_pick\", \"filter\", \"srgb\"} (light from an HDR map where a ray leaves the scene; not with --enable-volume)\n"
+                "      --env-mode M        with --extensions: \"escape\" or \"sampled\", overrides the \"environment\" block's \"mode\"\n"
                 "      --whitted           with --extensions: Whitted-style transport (direct light at diffuse surfaces, specular bounces only)\n"
                 "      --enable-volume     render the participating media of \"media\" shapes: the reference's ENABLE_VOLUME switch (raytrace.frag:4);\n"
                 "                          their VOL files are read (a missing one is an error only with this flag)\n"
@@ -82,6 +85,7 @@ static void usage(const char *exe) {
 int main(int argc, char **argv) {
     std::string input, out = "output.png";
     int depth = 16, spp = 1, frames = 16, device = -1, in_flight = 0;
+    int env_mode = -1;  // --env-mode: GLRTX_ENV_*, -1 the scene file's
     bool every_frame = false, extensions = false, whitted = false, order_by_hits = false, volume = false, adaptive = false, adaptive_variance = false, min_spp_given = false, volume_wavefront = false;
     float adapt_threshold = 0.0f;
     int min_spp = 2;
@@ -117,6 +121,11 @@ int main(int argc, char **argv) {
         else if (a == "--order-by-hits") order_by_hits = true;
         else if (a == "--extensions") extensions = true;
         else if (a == "--whitted") { extensions = true; whitted = true; }
+        else if (a == "--env-mode") {
+            const std::string m = next("--env-mode");
+            if (m != "escape" && m != "sampled") { std::fprintf(stderr, "--env-mode is \"escape\" or \"sampled\"\n"); return 1; }
+            env_mode = m == "sampled" ? 1 : 0;
+        }
         else if (a == "--enable-volume") volume = true;
         else if (a == "--volume-wavefront") volume_wavefront = true;
         else if (a == "--adaptive") { adaptive = true; adapt_threshold = (float)std::atof(next("--adaptive")); }
@@ -227,6 +236,7 @@ int main(int argc, char **argv) {
     if (!bvh.empty()) scene->setBvhBuilder(bvh);
     scene->enableExtensions(extensions);
     scene->setWhitted(whitted);
+    scene->setEnvMode(env_mode);
     scene->enableVolume(volume);
     scene->parse(input);
 

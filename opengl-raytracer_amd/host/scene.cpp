@@ -49,6 +49,7 @@ void Scene::parse(const std::string &filename) {
     if (const char *e = std::getenv("GLRT_EXTENSIONS")) extensions_ = extensions_ || std::atoi(e) != 0;
     spheres.clear();
     textures_.clear();
+    environment_ = EnvironmentSpec{};
     hasDielectric_ = false;
     volumeSpecs_.clear();
     hasVolume_ = false;
@@ -59,6 +60,74 @@ void Scene::parse(const std::string &filename) {
     width = json["film"]["width"].int_value();
     height = json["film"]["height"].int_value();
     GLRT_Info("window: %d x %d", width, height);
+
+    if (extensions_ && !json["environment"].is_null()) {  // EXTENSION (scene.h: EnvironmentSpec); off, the key is one the parser does not know
+        const Json &ev = json["environment"];
+        if (!ev.is_object()) GLRT_FatalError("\"environment\" is not an object");
+        if (volume_) GLRT_FatalError("\"environment\" and --enable-volume do not combine: the volume branch has its own escape path");
+        EnvironmentSpec &spec = environment_;
+        if (!ev["file"].is_string() || ev["file"].string_value().empty()) GLRT_FatalError("\"environment\" has no \"file\" string");
+        spec.file = baseDir + "/" + ev["file"].string_value();
+        const auto word = [&](const char *key, const char *a, const char *b, bool first_default) {
+            if (ev[key].is_null()) return first_default;
+            const std::string v = ev[key].is_string() ? ev[key].string_value() : std::string();
+            if (v != a && v != b) GLRT_FatalError("environment \"%s\" is not \"%s\" or \"%s\"", key, a, b);
+            return v == a;
+        };
+        spec.latlong = word("layout", "latlong", "octahedral", true);
+        spec.mode = word("mode", "escape", "sampled", true) ? GLRTX_ENV_ESCAPE : GLRTX_ENV_SAMPLED;
+        if (envModeOverride_ >= 0) spec.mode = envModeOverride_;
+        spec.filter = word("filter", "bilinear", "nearest", true) ? GLRTX_TEX_BILINEAR : GLRTX_TEX_NEAREST;
+        bool srgb = true;
+        if (!ev["srgb"].is_null()) {
+            if (!ev["srgb"].is_bool()) GLRT_FatalError("environment \"srgb\" is not true or false");
+            srgb = ev["srgb"].bool_value();
+        }
+        if (!ev["scale"].is_null()) {
+            if (ev["scale"].is_number()) fill3(spec.scale, (float)ev["scale"].number_value());
+            else if (ev["scale"].is_array() && ev["scale"].array_items().size() == 3) vec3(ev["scale"], spec.scale);
+            else GLRT_FatalError("environment \"scale\" is not a number or [r, g, b]");
+        }
+        const auto number = [&](const char *key, float def) {
+            if (ev[key].is_null()) return def;
+            if (!ev[key].is_number()) GLRT_FatalError("environment \"%s\" is not a number", key);
+            return (float)ev[key].number_value();
+        };
+        spec.rotateY = number("rotate_y", 0.0f);
+        spec.lightPick = number("light_pick", 0.5f);
+        const int size = (int)number("size", 512.0f);
+        TextureImage img;
+        std::string terr;
+        if (!readTextureFile(spec.file, img, terr)) GLRT_FatalError("environment \"file\": %s", terr.c_str());
+        if (spec.latlong) {
+            if (size < 2 || size > GLRTX_TEX_MAX_DIM) GLRT_FatalError("environment \"size\" %d lies outside 2 .. %d", size, GLRTX_TEX_MAX_DIM);
+            // the picture as float RGB rows from the TOP down (row 0 of the image is the bottom row); a PPM's bytes through the format's own decode
+            const size_t n = (size_t)img.width * (size_t)img.height;
+            std::vector<float> rgb(3 * n);
+            const float *table = glrt_srgb_table();
+            for (int y = 0; y < img.height; y++)
+                for (int x = 0; x < img.width; x++) {
+                    const size_t src = (size_t)(img.height - 1 - y) * img.width + x, dst = (size_t)y * img.width + x;
+                    for (int c = 0; c < 3; c++) {
+                        if (img.isFloat) std::memcpy(&rgb[3 * dst + c], &img.texels[16 * src + 4 * c], 4);
+                        else { const unsigned b = img.texels[4 * src + c]; rgb[3 * dst + c] = srgb ? table[b] : (float)b / 255.0f; }
+                    }
+                }
+            spec.size = size;
+            spec.format = GLRTX_TEX_RGBA32F;
+            spec.texels.resize((size_t)size * size * 16);
+            if (glrt_env_from_latlong(rgb.data(), img.width, img.height, size, reinterpret_cast<float *>(spec.texels.data())) != GLRT_HOST_OK)
+                GLRT_FatalError("environment: resampling %s failed", spec.file.c_str());
+        } else {
+            if (img.width != img.height || img.width < 2) GLRT_FatalError("environment \"file\": an octahedral map is square, 2 texels a side at least (%d x %d)", img.width, img.height);
+            spec.size = img.width;
+            spec.format = img.isFloat ? GLRTX_TEX_RGBA32F : srgb ? GLRTX_TEX_RGBA8_SRGB : GLRTX_TEX_RGBA8_UNORM;
+            spec.texels = std::move(img.texels);
+        }
+        spec.present = true;
+        GLRT_Info("environment: %s, %s, %d x %d octahedral, %s mode (not part of the reference)", spec.file.c_str(), spec.latlong ? "lat-long" : "octahedral",
+                  spec.size, spec.size, spec.mode == GLRTX_ENV_SAMPLED ? "sampled" : "escape");
+    }
 
     // camera (scene.cpp:62-114)
     const std::string type = json["camera"]["type"].string_value();
@@ -648,6 +717,31 @@ struct SceneTextureProbe {
 
 extern "C" GLRT_API int glrt_scene_texture_probe(const char *json, int extensions, long long counts[2], int *info, unsigned char *texels, size_t texel_cap) {
     return glrt::SceneTextureProbe::run(json, extensions, counts, info, texels, texel_cap);
+}
+
+// Environment probe: parse with extensions on or off and an optional mode override (-1: none).  info = {present, mode, size, format, filter, latlong, texel
+// bytes}; values = {scale[3], rotate_y, light_pick}; texels (may be NULL): the octahedral map, at most texel_cap bytes.
+namespace glrt {
+struct SceneEnvironmentProbe {
+    static int run(const char *json, int extensions, int mode_override, int info[7], float values[5], unsigned char *texels, size_t texel_cap) {
+        Scene sc;
+        sc.enableExtensions(extensions != 0);
+        sc.setEnvMode(mode_override);
+        sc.parse(json);
+        const Scene::EnvironmentSpec &e = sc.environment_;
+        const int row[7] = {e.present ? 1 : 0, e.mode, e.size, e.format, e.filter, e.latlong ? 1 : 0, (int)e.texels.size()};
+        std::memcpy(info, row, sizeof row);
+        const float v[5] = {e.scale[0], e.scale[1], e.scale[2], e.rotateY, e.lightPick};
+        std::memcpy(values, v, sizeof v);
+        if (texels && e.texels.size() <= texel_cap) std::memcpy(texels, e.texels.data(), e.texels.size());
+        return 0;
+    }
+};
+}  // namespace glrt
+
+extern "C" GLRT_API int glrt_scene_environment_probe(const char *json, int extensions, int mode_override, int info[7], float values[5], unsigned char *texels,
+                                                     size_t texel_cap) {
+    return glrt::SceneEnvironmentProbe::run(json, extensions, mode_override, info, values, texels, texel_cap);
 }
 
 extern "C" GLRT_API int glrt_scene_normals_probe(const char *json, const char *animation, int out[2]) { return glrt::SceneNormalsProbe::run(json, animation, out); }

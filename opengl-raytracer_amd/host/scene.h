@@ -69,6 +69,28 @@ public:
         TextureImage image;
     };
     const std::vector<TextureSpec> &textureSpecs() const { return textures_; }
+    // Environment (include/glrtx.h "Environment"; no reference counterpart).  With extensions on, the scene file may carry the top-level key
+    //     "environment": {"file": "x.pfm" | "x.ppm", "layout": "latlong" | "octahedral", "size": N, "mode": "escape" | "sampled", "scale": x | [r, g, b],
+    //                     "rotate_y": degrees, "light_pick": p, "filter": "bilinear" | "nearest", "srgb": true | false}
+    // "file" is required and read as a texture's is (texture_file.h: row 0 is the bottom row of the picture).  "layout" defaults to "latlong": the picture --
+    // +y up, its top row +y, its centre column -z -- is resampled into a size x size octahedral float map (glrt_env_from_latlong; "size" defaults to 512, 2 ..
+    // 16384).  "octahedral": the file IS the map (square; row 0 at t = 0; "size" is not read) in the file's own format.  "mode" defaults to "escape", "scale"
+    // to 1, "rotate_y" to 0 (a positive angle turns the map so that what it holds along +z is seen along +x after a quarter turn), "light_pick" to 0.5,
+    // "filter" to "bilinear", "srgb" to true (a PPM's bytes; a PFM is linear).  A value other than those above and an unreadable file are FatalErrors that
+    // name the key.  Window uploads it after the scene (glrtx_upload_environment).  glrt_main --env-mode overrides "mode" (setEnvMode, before parse()).
+    // With extensions off the key is ignored, as the reference ignores keys it does not know.  Together with enableVolume(true) it is a FatalError: the volume
+    // branch has its own escape path.
+    struct EnvironmentSpec {
+        bool present = false;
+        std::string file;
+        bool latlong = true;
+        int size = 0, format = 0, filter = 1, mode = 0;  // the map's side; GLRTX_TEX_*; GLRTX_ENV_*
+        float scale[3] = {1.0f, 1.0f, 1.0f};
+        float rotateY = 0.0f, lightPick = 0.5f;
+        std::vector<unsigned char> texels;  // the octahedral map, row 0 at t = 0
+    };
+    const EnvironmentSpec &environmentSpec() const { return environment_; }
+    void setEnvMode(int mode) { envModeOverride_ = mode; }  // GLRTX_ENV_*; -1: the file's
     // Participating media (the reference's volume branch, which it compiles out: raytrace.frag:4; include/glrtx.h GLRTX_EXT_VOLUME).  parse() always keeps
     // each "media" shape's "volume" block {density, temperature, bboxMin, bboxMax} (scene.cpp:174-214) in volumeSpecs(); with enableVolume(true) (call
     // before parse()) it also reads the FIRST block's two VOL files -- a missing or unreadable file is then a FatalError -- and Window uploads them and
@@ -143,6 +165,8 @@ private:
     std::string bvhBuilder_ = "sah";
     std::vector<float> spheres;  // extension: 5 floats per sphere {cx, cy, cz, radius, material}
     std::vector<TextureSpec> textures_;  // extension: one per textured diffuse shape, in shape order
+    EnvironmentSpec environment_;        // extension: the scene file's "environment" block
+    int envModeOverride_ = -1;
     bool extensions_ = false, whitted_ = false, hasDielectric_ = false;
     std::vector<VolumeSpec> volumeSpecs_;
     bool volume_ = false, hasVolume_ = false;
@@ -166,6 +190,7 @@ private:
     friend struct SceneMorphSparseProbe;
     friend struct SceneNormalsProbe;
     friend struct SceneTextureProbe;
+    friend struct SceneEnvironmentProbe;
 };
 
 // OBJ triangles the way the reference's loader yields them (trimesh.cpp:113-191): three fresh

@@ -8,6 +8,7 @@
 #include "glrt_host.h"
 #include "statement_math.h"
 #include "texture_set.h"
+#include "texture_statement.h"
 
 namespace {
 
@@ -113,6 +114,10 @@ void lookup(const TexRecord &d, const unsigned char *texels, float s, float t, f
 }
 
 }  // namespace
+
+// (texture_statement.h: the same statement for host/environment.cpp)
+void glrt_detail::texture_lookup_one(const TexRecord &d, const unsigned char *texels, float s, float t, float rgb[3]) { lookup(d, texels, s, t, rgb); }
+void glrt_detail::texture_texel_one(const TexRecord &d, const unsigned char *texels, int ix, int iy, float rgb[3]) { texel(d, texels, ix, iy, rgb); }
 
 const float *glrt_srgb_table(void) {
     static float table[256];

@@ -4,6 +4,7 @@
 #include "window.h"
 
 #include <chrono>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -61,6 +62,30 @@ void Window::uploadTextures() {
     GLRT_Info("textures: %zu, %zu texel bytes (not part of the reference)", desc.size(), blob.size());
 }
 
+// The scene's environment (Scene::EnvironmentSpec; extensions only) on every member, after the scene: launches then run on the extension megakernel
+void Window::uploadEnvironment() {
+    const Scene::EnvironmentSpec &e = scene->environment_;
+    if (!e.present) return;
+    const glrtx_texture map{0, e.size, e.size, e.format, GLRTX_TEX_CLAMP, GLRTX_TEX_CLAMP, e.filter};
+    glrtx_env_cfg cfg{};
+    cfg.mode = e.mode;
+    cfg.grid = 0;
+    cfg.light_pick = e.lightPick;
+    std::memcpy(cfg.scale, e.scale, sizeof cfg.scale);
+    // a turn about +y; quarter turns exactly (the same words as glrt_amd.host.env_cfg(rotate_y=..))
+    const double a = (double)e.rotateY * 3.14159265358979323846 / 180.0;
+    float cs = (float)std::cos(a), sn = (float)std::sin(a);
+    if (std::fmod((double)e.rotateY, 90.0) == 0.0) { cs = (float)std::round(std::cos(a)); sn = (float)std::round(std::sin(a)); }
+    const float R[9] = {cs, 0.0f, 0.0f - sn, 0.0f, 1.0f, 0.0f, sn, 0.0f, cs};
+    std::memcpy(cfg.rotation, R, sizeof R);
+    for (int i = 0; i < glrtx_group_size(grp_); i++) {
+        glrtx_ctx *c = glrtx_group_ctx(grp_, i);
+        if (glrtx_upload_environment(c, &map, e.texels.data(), e.texels.size(), &cfg) != GLRTX_OK)
+            GLRT_FatalError("glrtx_upload_environment: %s", glrtx_last_error(c));
+    }
+    GLRT_Info("environment: %d x %d texels, %s mode (not part of the reference)", e.size, e.size, e.mode == GLRTX_ENV_SAMPLED ? "sampled" : "escape");
+}
+
 void Window::mainloop(const std::shared_ptr<Scene> &scene_, double fps) {
     (void)fps;  // the reference's default fps = -1 renders every iteration (window.cpp:126); so do we
     scene = scene_;
@@ -98,9 +123,10 @@ void Window::mainloop(const std::shared_ptr<Scene> &scene_, double fps) {
                       scene->hasDielectric_ ? ", dielectric" : "", scene->whitted_ ? ", Whitted termination" : "");
     }
     uploadTextures();
+    uploadEnvironment();
     resize(scene->width, scene->height);
     if (const char *e = std::getenv("GLRT_BVH_ORDER")) orderByHits_ = std::string(e) == "hits";
-    if (orderByHits_ && !scene->nodes.empty() && scene->textures_.empty() && scene->spheres.empty() && !scene->hasDielectric_ && !scene->whitted_ && !scene->hasVolume_) {
+    if (orderByHits_ && !scene->nodes.empty() && scene->textures_.empty() && !scene->environment_.present && scene->spheres.empty() && !scene->hasDielectric_ && !scene->whitted_ && !scene->hasVolume_) {
         // one calibration frame on the first member's share of the rows (interleaved stripes: a fair sample of the image), counted by the render kernel itself
         glrtx_params p;
         frameParams(p);

@@ -99,6 +99,7 @@ protected:
 private:
     void frameParams(struct ::glrtx_params &p) const;
     void uploadTextures();  // the scene's texture set on every member (glrtx_upload_textures)
+    void uploadEnvironment();  // the scene's environment on every member (glrtx_upload_environment)
     void resizeDefault(int width, int height);
     void resetBuffer();
     void saveCurrentFrame(const std::string &filename, bool overwrite = true) const;

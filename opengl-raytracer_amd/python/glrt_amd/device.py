@@ -10,7 +10,7 @@ import ctypes as C
 
 import numpy as np
 
-from .host import LIB_DIR, PKG_ROOT
+from .host import LIB_DIR, PKG_ROOT, EnvCfg, ENV_ESCAPE, ENV_SAMPLED  # noqa: F401  (device.EnvCfg is glrtx_env_cfg)
 
 GLRTX_OK = 0
 GLRTX_EINVAL, GLRTX_EDEVICE, GLRTX_ESCENE, GLRTX_EDEPTH, GLRTX_ENOMEM, GLRTX_EBUSY = -1, -2, -3, -4, -5, -6
@@ -177,7 +177,8 @@ EXPORTS = ["glrtx_abi_version", "glrtx_create", "glrtx_destroy", "glrtx_last_err
            "glrtx_upload_morph_targets", "glrtx_pose_morph", "glrtx_pose_dualquat", "glrtx_debug_deform", "glrtx_debug_deform_burst",
            "glrtx_upload_morph_targets_sparse", "glrtx_debug_deform_sparse",
            "glrtx_upload_normal_topology", "glrtx_update_positions", "glrtx_update_positions_device", "glrtx_set_pose_normals",
-           "glrtx_debug_rebuild_normals", "glrtx_debug_normals_burst", "glrtx_upload_textures", "glrtx_debug_texture_lookup"]
+           "glrtx_debug_rebuild_normals", "glrtx_debug_normals_burst", "glrtx_upload_textures", "glrtx_debug_texture_lookup",
+           "glrtx_upload_environment", "glrtx_set_environment_cfg", "glrtx_debug_env_weights", "glrtx_debug_env_sample", "glrtx_debug_env_eval"]
 
 SCENE_BUFFERS = ("nodes", "cnodes", "nrms", "lights", "vine", "root")  # glrtx_debug_read_scene's `which`, in order (GLRTX_SCENE_*)
 
@@ -387,6 +388,14 @@ def lib():
             L.glrtx_debug_texture_lookup.argtypes = [vp, C.c_size_t, vp, C.c_size_t, i32p, fp, C.c_size_t, fp]
         except AttributeError:
             pass
+        try:  # (additive to ABI 10 as well: the environment)
+            L.glrtx_upload_environment.argtypes = [vp, vp, vp, C.c_size_t, vp]
+            L.glrtx_set_environment_cfg.argtypes = [vp, vp]
+            L.glrtx_debug_env_weights.argtypes = [vp, vp, C.c_size_t, vp, fp, C.POINTER(C.c_int32)]
+            L.glrtx_debug_env_sample.argtypes = [vp, vp, C.c_size_t, vp, fp, C.c_size_t, fp]
+            L.glrtx_debug_env_eval.argtypes = [vp, vp, C.c_size_t, vp, fp, C.c_size_t, fp]
+        except AttributeError:
+            pass
         _lib = L
     return _lib
 
@@ -467,6 +476,41 @@ def debug_texture_lookup(textures, which, st):
     rc = L.glrtx_debug_texture_lookup(desc.ctypes.data, desc.size, blob.ctypes.data, blob.size, w.ctypes.data_as(C.POINTER(C.c_int32)), _fp(c), w.size, _fp(out))
     if rc != 0:
         raise GlrtxError(rc, L.glrtx_last_error(None).decode())
+    return out
+
+
+def _debug_env(name, env_map, cfg, *rest):
+    from .host import pack_environment
+    L = lib()
+    desc, blob = pack_environment(env_map)
+    rc = getattr(L, name)(desc.ctypes.data, blob.ctypes.data, blob.size, C.addressof(cfg) if cfg is not None else None, *rest)
+    if rc != 0:
+        raise GlrtxError(rc, L.glrtx_last_error(None).decode())
+
+
+def debug_env_weights(env_map, cfg):
+    """glrtx_debug_env_weights on the current device: env_weights_kernel (include/glrtx.h "Environment").  Arguments and result as host.env_weights's."""
+    from .host import pack_environment
+    desc, _ = pack_environment(env_map)
+    g = int(cfg.grid) if cfg is not None and 0 < int(cfg.grid) <= 1024 else min(int(desc["width"][0]), 256)
+    out, grid = np.zeros(max(g, 1) ** 2, np.float32), C.c_int32(0)
+    _debug_env("glrtx_debug_env_weights", env_map, cfg, _fp(out), C.byref(grid))
+    return out.reshape(grid.value, grid.value)
+
+
+def debug_env_sample(env_map, cfg, u):
+    """glrtx_debug_env_sample on the current device: the kernels' env_sample.  Arguments and result as host.env_sample's."""
+    q = _f32(u).reshape(-1, 6)
+    out = np.zeros((q.shape[0], 8), np.float32)
+    _debug_env("glrtx_debug_env_sample", env_map, cfg, _fp(q), q.shape[0], _fp(out))
+    return out
+
+
+def debug_env_eval(env_map, cfg, dirs):
+    """glrtx_debug_env_eval on the current device: the kernels' env_eval.  Arguments and result as host.env_eval's."""
+    d = _f32(dirs).reshape(-1, 3)
+    out = np.zeros((d.shape[0], 4), np.float32)
+    _debug_env("glrtx_debug_env_eval", env_map, cfg, _fp(d), d.shape[0], _fp(out))
     return out
 
 
@@ -1043,6 +1087,22 @@ class Device:
         desc, blob = pack_textures(textures or [])
         b = np.ascontiguousarray([] if material_texture is None else material_texture, dtype=np.int32).reshape(-1)
         self._ck(self.L.glrtx_upload_textures(self.h, desc.ctypes.data, desc.size, blob.ctypes.data, blob.size, b.ctypes.data_as(C.POINTER(C.c_int32)), b.size))
+
+    def upload_environment(self, env_map, cfg=None):
+        """Bind an environment (glrtx_upload_environment; include/glrtx.h "Environment"): env_map as host.pack_environment takes it -- (array (N, N, 3 or 4),
+        format, filter), an octahedral map with +y at the centre --, cfg a device.EnvCfg (host.env_cfg builds one; default: escape mode, scale 1, no rotation).
+        Launches then run on the extension megakernel.  env_map None unbinds.  The map is kept across upload_scene."""
+        from .host import env_cfg, pack_environment
+        if env_map is None:
+            self._ck(self.L.glrtx_upload_environment(self.h, None, None, 0, None))
+            return
+        cfg = env_cfg() if cfg is None else cfg
+        desc, blob = pack_environment(env_map)
+        self._ck(self.L.glrtx_upload_environment(self.h, desc.ctypes.data, blob.ctypes.data, blob.size, C.addressof(cfg)))
+
+    def set_environment_cfg(self, cfg):
+        """glrtx_set_environment_cfg: mode, light_pick and rotation take effect at the next launch; a new scale or grid rebuilds the sampling tables."""
+        self._ck(self.L.glrtx_set_environment_cfg(self.h, C.addressof(cfg) if cfg is not None else None))
 
     def set_extensions(self, flags: int):
         """EXT_DIELECTRIC | EXT_WHITTED (extensions, parity unpinned) | EXT_VOLUME (the reference's volume branch, pinned)."""

@@ -71,6 +71,12 @@ def lib():
         L.glrt_srgb_table.restype = fp
         L.glrt_srgb_table.argtypes = []
         L.glrt_texture_albedo.argtypes = [fp, C.c_size_t, fp, C.c_size_t, fp, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, i32p, fp, C.c_size_t, fp]
+        vp = C.c_void_p
+        L.glrt_env_weights.argtypes = [vp, vp, C.c_size_t, vp, fp, i32p]
+        L.glrt_env_alias.argtypes = [fp, C.c_int32, fp, i32p, fp, i32p, fp]
+        L.glrt_env_sample.argtypes = [vp, vp, C.c_size_t, vp, fp, C.c_size_t, fp]
+        L.glrt_env_eval.argtypes = [vp, vp, C.c_size_t, vp, fp, C.c_size_t, fp]
+        L.glrt_env_from_latlong.argtypes = [fp, C.c_int32, C.c_int32, C.c_int32, fp]
         L.glrt_look_at.argtypes = [fp, fp, fp, fp]
         L.glrt_perspective.argtypes = [C.c_float, C.c_float, C.c_float, C.c_float, fp]
         L.glrt_mat4_mul.argtypes = [fp, fp, fp]
@@ -742,6 +748,102 @@ def look_at(eye, center, up) -> np.ndarray:
 def perspective(fovy_deg, aspect, z_near, z_far) -> np.ndarray:
     out = np.zeros(16, np.float32)
     lib().glrt_perspective(fovy_deg, aspect, z_near, z_far, _fp(out))
+    return out
+
+
+# Environment (include/glrtx.h "Environment"): GLRTX_ENV_*
+ENV_ESCAPE, ENV_SAMPLED = 0, 1
+ENV_MODES = dict(escape=ENV_ESCAPE, sampled=ENV_SAMPLED)
+
+
+class EnvCfg(C.Structure):  # glrtx_env_cfg == glrt_env_cfg
+    _fields_ = [("mode", C.c_int32), ("grid", C.c_int32), ("light_pick", C.c_float), ("scale", C.c_float * 3), ("rotation", C.c_float * 9)]
+
+
+def env_cfg(mode=ENV_ESCAPE, grid=0, light_pick=0.5, scale=1.0, rotation=None, rotate_y=None) -> EnvCfg:
+    """A glrtx_env_cfg.  mode: ENV_* or its name; scale: a number or an RGB triple; rotation: a row-major 3 x 3 (map space = rotation * world), default the
+    identity; rotate_y (degrees) instead: the map turned about +y, so that what lay along +z lies along +x after a quarter turn."""
+    c = EnvCfg()
+    c.mode = ENV_MODES[mode] if isinstance(mode, str) else int(mode)
+    c.grid = int(grid)
+    c.light_pick = float(light_pick)
+    c.scale[:] = [float(v) for v in np.broadcast_to(np.asarray(scale, np.float32), (3,))]
+    if rotation is None:
+        a = np.deg2rad(0.0 if rotate_y is None else float(rotate_y))
+        cs, sn = np.float32(np.cos(a)), np.float32(np.sin(a))
+        if rotate_y is not None and float(rotate_y) % 90.0 == 0.0:  # quarter turns exactly
+            cs, sn = np.float32(round(float(np.cos(a)))), np.float32(round(float(np.sin(a))))
+        rotation = [cs, 0.0, 0.0 - sn, 0.0, 1.0, 0.0, sn, 0.0, cs]  # (0 - 0 = +0: no turn is the identity's words)
+    c.rotation[:] = [float(v) for v in np.asarray(rotation, np.float32).reshape(9)]
+    return c
+
+
+def pack_environment(env_map):
+    """An environment map as the C calls take it.  env_map: (array, format, filter) -- array (N, N, 3 or 4) as pack_textures takes a texture, row 0 at t = 0
+    (the -z edge of the octahedral square), clamp on both axes.  A pair (descriptors, blob) already packed passes through."""
+    if isinstance(env_map, tuple) and len(env_map) == 2 and getattr(env_map[0], "dtype", None) == TEXTURE_DTYPE:
+        return pack_textures(env_map)
+    arr, fmt, filt = env_map
+    return pack_textures([(arr, fmt, TEX_CLAMP, filt)])
+
+
+def _env_call(name, env_map, cfg, *rest):
+    desc, blob = pack_environment(env_map)
+    rc = getattr(lib(), name)(desc.ctypes.data, blob.ctypes.data, blob.size, C.addressof(cfg) if cfg is not None else None, *rest)
+    if rc != 0:
+        raise RuntimeError(f"{name} failed: {rc}")
+
+
+def env_weights(env_map, cfg):
+    """glrt_env_weights: the importance grid's cell weights, (G, G) float32 with row j (the t axis) first, in the device's summation order."""
+    desc, _ = pack_environment(env_map)
+    g = int(cfg.grid) if cfg is not None and 0 < int(cfg.grid) <= 1024 else min(int(desc["width"][0]), 256)
+    out, grid = np.zeros(max(g, 1) ** 2, np.float32), C.c_int32(0)
+    _env_call("glrt_env_weights", env_map, cfg, _ptr(out, C.c_float), C.byref(grid))
+    return out.reshape(grid.value, grid.value)
+
+
+def env_alias(weights):
+    """glrt_env_alias: the sampling tables of a (G, G) grid of weights.  Returns dict(row_q (G,), row_alias (G,), col_q (G, G), col_alias (G, G), cell_p (G, G))."""
+    w = _f32(weights)
+    if w.ndim != 2 or w.shape[0] != w.shape[1]:
+        raise ValueError(f"env_alias: weights must be (G, G), got {w.shape}")
+    g = w.shape[0]
+    t = dict(row_q=np.zeros(g, np.float32), row_alias=np.zeros(g, np.int32), col_q=np.zeros((g, g), np.float32), col_alias=np.zeros((g, g), np.int32),
+             cell_p=np.zeros((g, g), np.float32))
+    rc = lib().glrt_env_alias(_ptr(w, C.c_float), g, _ptr(t["row_q"], C.c_float), _ptr(t["row_alias"], C.c_int32), _ptr(t["col_q"], C.c_float),
+                              _ptr(t["col_alias"], C.c_int32), _ptr(t["cell_p"], C.c_float))
+    if rc != 0:
+        raise RuntimeError(f"glrt_env_alias failed: {rc}")
+    return t
+
+
+def env_sample(env_map, cfg, u):
+    """glrt_env_sample: six uniforms a row of u (n, 6) -> (n, 8) float32 rows {direction, pdf, Le.rgb, 0}; the pdf carries p_env = cfg.light_pick."""
+    q = _f32(u).reshape(-1, 6)
+    out = np.zeros((q.shape[0], 8), np.float32)
+    _env_call("glrt_env_sample", env_map, cfg, _ptr(q, C.c_float), q.shape[0], _ptr(out, C.c_float))
+    return out
+
+
+def env_eval(env_map, cfg, dirs):
+    """glrt_env_eval: directions (n, 3), not normalised -> (n, 4) float32 rows {Le.rgb, pdf}."""
+    d = _f32(dirs).reshape(-1, 3)
+    out = np.zeros((d.shape[0], 4), np.float32)
+    _env_call("glrt_env_eval", env_map, cfg, _ptr(d, C.c_float), d.shape[0], _ptr(out, C.c_float))
+    return out
+
+
+def env_from_latlong(image, n):
+    """glrt_env_from_latlong: a lat-long image (height, width, 3) -- +y up, the top row +y, the centre column -z -- resampled into an (n, n, 4) float32
+    octahedral map (alpha 1)."""
+    a = _f32(np.asarray(image)[..., :3])
+    if a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError(f"env_from_latlong: image must be (height, width, 3 or 4), got {np.asarray(image).shape}")
+    out = np.zeros((int(n), int(n), 4), np.float32)
+    rc = lib().glrt_env_from_latlong(_ptr(a, C.c_float), a.shape[1], a.shape[0], int(n), _ptr(out, C.c_float))
+    if rc != 0:
+        raise RuntimeError(f"glrt_env_from_latlong failed: {rc}")
     return out
 
 

@@ -365,6 +365,64 @@ def config_textured_wall(n=6, width=64, height=48, max_depth=4, n_samples=2, alb
     return scene, make_params(c2w, s2c, width, height, max_depth, n_samples), info
 
 
+# --------------------------------------------------------------------------- environment lighting (include/glrtx.h "Environment"; PARITY UNPINNED)
+ENV_QUAD_ALBEDO = (0.5, 0.25, 0.75)
+
+
+def config_env_quad(width=64, height=48, max_depth=2, n_samples=16):
+    """One large diffuse quad (ENV_QUAD_ALBEDO) facing +y that fills the view of a camera looking straight down, and no lights: under a constant environment E
+    every pixel is albedo * E (the furnace), under any environment its mean is (albedo / pi) * the cosine-weighted integral of the upper hemisphere."""
+    b = SceneBuilder()
+    b.add_mesh(*quad((-50, 0, 50), (100, 0, 0), (0, 0, -100)), b.add_material(diffuse(ENV_QUAD_ALBEDO)))
+    scene = b.build()
+    c2w, s2c = camera((0, 5, 0), (0, 0, 0), (0, 0, -1), 40.0, width, height)
+    return scene, make_params(c2w, s2c, width, height, max_depth, n_samples)
+
+
+def config_env_sky(direction, up=None, width=64, height=48, fov_deg=10.0, max_depth=1, n_samples=1):
+    """Nothing in view: a camera at the origin looking along `direction` with a narrow field of view, and a single far-away triangle behind it (a scene needs
+    one).  Every pixel shows the environment."""
+    d = np.asarray(direction, np.float64)
+    d = d / np.linalg.norm(d)
+    if up is None:
+        up = (0.0, 0.0, -1.0) if abs(d[1]) > 0.9 else (0.0, 1.0, 0.0)
+    b = SceneBuilder()
+    grey = b.add_material(diffuse((0.5, 0.5, 0.5)))
+    c = -1000.0 * d
+    e1 = np.cross(d, np.asarray(up, np.float64))
+    e1 /= np.linalg.norm(e1)
+    e2 = np.cross(d, e1)
+    pos = np.array([[c, c + e1, c + e2]], np.float32)
+    b.add_mesh(pos, np.broadcast_to(d.astype(np.float32), (1, 3, 3)), grey)
+    scene = b.build()
+    c2w, s2c = camera((0, 0, 0), tuple(d), up, fov_deg, width, height, near=0.1, far=100.0)
+    return scene, make_params(c2w, s2c, width, height, max_depth, n_samples)
+
+
+def config_env_box(width=64, height=48, max_depth=4, n_samples=2):
+    """A closed room with a lamp under its ceiling, a conductor ball and the camera inside: no ray leaves it, whatever environment is bound."""
+    b = SceneBuilder()
+    grey = b.add_material(diffuse((0.7, 0.7, 0.7)))
+    red = b.add_material(diffuse((0.8, 0.3, 0.3)))
+    cu = b.add_material(conductor(COPPER["eta"], COPPER["kappa"], 0.2))
+    lamp = b.add_material(emitter((10.0, 10.0, 10.0)))
+    pos, nrm = box((-4, 0, -4), (4, 6, 10))
+    b.add_mesh(pos, -nrm, grey)  # the walls face inward
+    b.add_mesh(*icosphere(1, 1.0, (-1.5, 1.0, 0.0)), red)
+    b.add_mesh(*icosphere(1, 1.0, (1.5, 1.0, 0.0)), cu)
+    b.add_mesh(*quad((-1, 5, -1), (2, 0, 0), (0, 0, 2)), lamp)
+    scene = b.build()
+    c2w, s2c = camera((0, 3, 9), (0, 1, 0), (0, 1, 0), 40.0, width, height)
+    return scene, make_params(c2w, s2c, width, height, max_depth, n_samples)
+
+
+def env_octant_map():
+    """A 4 x 4 float map with sixteen distinct colours (nearest filtering): the four inner texels are the upper octants, the four corners the lower ones, and an
+    edge texel is shared by the upper and the lower octant of its quadrant.  Returns (4, 4, 3) float32, texel [y, x]."""
+    k = np.arange(16, dtype=np.float32).reshape(4, 4)
+    return np.stack([0.125 + k / 16.0, 1.0 - k / 32.0, 0.25 + (k % 4) / 8.0], -1).astype(np.float32)
+
+
 def _eight_spheres(b: SceneBuilder, subdiv: int):
     xs = (-3.3, -1.1, 1.1, 3.3)
     albedos = ((0.75, 0.75, 0.75), (0.8, 0.3, 0.3), (0.3, 0.7, 0.35), (0.3, 0.4, 0.8))
