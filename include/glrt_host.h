@@ -328,6 +328,20 @@ int glrt_env_sample(const glrt_texture *map, const void *texels, size_t texel_by
 int glrt_env_eval(const glrt_texture *map, const void *texels, size_t texel_bytes, const glrt_env_cfg *cfg, const float *dir, size_t n, float *out);
 int glrt_env_from_latlong(const float *rgb, int32_t width, int32_t height, int32_t n, float *rgba_out);
 
+/* Material maps: the CPU statements of the device's tangent-space normal rule and roughness rule (glrtx_bind_material_maps / glrtx_debug_map_normal,
+ * include/glrtx.h "Material maps": decode, frame, perturbation and the cases that keep the normal are there), bit for bit (host/maps.cpp; tests/maps_math.py
+ * states them in numpy).  glrt_material_map is glrtx_material_map's layout.  The arithmetic runs with denormals flushed (MXCSR FTZ | DAZ, restored on return).
+ *   glrt_map_decode   m_out[3i..] = rgb[3i..] * 2 + -1: a looked-up texel as the tangent-space vector.
+ *   glrt_map_normal   normal_out[3i..] = n' of record i: GLRT_MAP_RECORD_FLOATS floats {n, e1, e2, (s0, t0), (s1, t1), (s2, t2), m}, m decoded.
+ *   glrt_map_alpha    alpha_out[2i..] = (ax, ay) of the roughness texel rgb[3i..]: channels r and g, floored at GLRT_MAP_ALPHA_MIN.
+ * GLRT_HOST_EINVAL: a NULL pointer with something to read or write. */
+#define GLRT_MAP_ALPHA_MIN 1e-3f
+#define GLRT_MAP_RECORD_FLOATS 18
+typedef struct glrt_material_map { int32_t normal, roughness; float normal_scale; int32_t reserved; } glrt_material_map;
+int glrt_map_decode(const float *rgb, size_t n, float *m_out);
+int glrt_map_normal(const float *records, size_t n, float scale, float *normal_out);
+int glrt_map_alpha(const float *rgb, size_t n, float *alpha_out);
+
 void glrt_look_at(const float eye[3], const float center[3], const float up[3], float out[16]);
 void glrt_perspective(float fovy_deg, float aspect, float z_near, float z_far, float out[16]);
 void glrt_mat4_mul(const float a[16], const float b[16], float out[16]);

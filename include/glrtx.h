@@ -1249,6 +1249,55 @@ int glrtx_debug_env_weights(const glrtx_texture *map, const void *texels, size_t
 int glrtx_debug_env_sample(const glrtx_texture *map, const void *texels, size_t texel_bytes, const glrtx_env_cfg *cfg, const float *u, size_t n, float *out);
 int glrtx_debug_env_eval(const glrtx_texture *map, const void *texels, size_t texel_bytes, const glrtx_env_cfg *cfg, const float *dir, size_t n, float *out);
 
+/* ---- Material maps: a tangent-space normal map on a diffuse or conductor material, a roughness map on a conductor (no reference counterpart; off unless
+ * called: with no maps bound every launch runs the kernels it ran before).  The maps are textures of the set glrtx_upload_textures bound -- that set may bind no
+ * albedo at all (all -1) --, looked up by "Textures"' rule at the hit's (s, t).  Shaded by MAPS instantiations of the extension megakernel's textured kernels
+ * (pt_render_persistent_tex, pt_render_persistent_env), launched only while maps are bound.  PINNED through the reference all the same: a flat normal map and a
+ * constant roughness map of the material's own alphas render the unmapped image bit for bit, and a roughness map that is constant over each cell renders the
+ * image of one conductor material a cell.
+ *
+ * Arithmetic.  Every operation is one correctly rounded fp32 operation in the order written, unfused; denormals are zeros of their sign into and out of every
+ * operation.  Dots are (x x' + y y') + z z'.  rsq(x) = 1 / sqrt(x), IEEE sqrt then IEEE reciprocal (surf_tri's).  Three statements agree bit for bit:
+ * csrc/maps.hip.h, glrt_map_normal / glrt_map_alpha (include/glrt_host.h), tests/maps_math.py.
+ *
+ * INPUTS at a triangle hit.  n: the shading normal surf_tri returns.  e1 = v1 - v0, e2 = v2 - v0: the leaf record's words, in the wire's corner order, as the
+ *   refit rewrote them after the last move -- a posed or updated mesh carries its frame along.  (s0, t0), (s1, t1), (s2, t2): the corners' coordinates, FROZEN
+ *   when the set was uploaded.  c: the lookup of the bound map at the hit's (s, t).
+ * DECODE.   m = c * 2 + -1 per channel, for every format.
+ * FRAME.    ds1 = s1 - s0, ds2 = s2 - s0, dt1 = t1 - t0, dt2 = t2 - t0;  det = ds1 * dt2 - ds2 * dt1;
+ *   Tr = e1 * dt2 - e2 * dt1,  Br = e2 * ds1 - e1 * ds2, per component; for det < 0 the sign bits of both are inverted.
+ *   k = dot(n, Tr),  Tp = Tr - k * n,  l2 = dot(Tp, Tp),  T = Tp * rsq(l2);
+ *   C = cross(n, T) = (ny Tz - nz Ty, nz Tx - nx Tz, nx Ty - ny Tx);  B = C, with its sign bits inverted iff dot(C, Br) < 0.
+ *   TANGENTS ARE PER TRIANGLE AND ARE NOT INTERPOLATED: the wire's tangent / binormal words are not read.
+ * PERTURBATION.  a = m.x * scale, b = m.y * scale;  p = (a * T + b * B) + m.z * n per component;  q = dot(p, p);  n' = p * rsq(q).
+ * KEPT.     n is kept, word for word, when det is zero or not finite; when l2 or q is not a finite positive number; when a and b are both zero (either
+ *   sign).  The last rule is part of the contract: an RGBA32F map of (0.5, 0.5, 1.0) renders the unmapped image bit for bit.
+ * WHERE.    n' stands wherever the reference reads the shading normal: the local frame, woz, the spawn offset, the cosine of the light sample, the
+ *   environment branch.
+ * ROUGHNESS.  On a conductor (type 3) bound to a roughness map: ax = c.r > GLRTX_MAP_ALPHA_MIN ? c.r : GLRTX_MAP_ALPHA_MIN, ay likewise from c.g (a NaN gives
+ *   the floor).  They REPLACE alpha.x / alpha.y at the three places the shading reads them: the BSDF sample, the triangle-light evaluation and the
+ *   environment-light evaluation.  Channel b and alpha are not read.
+ * Analytic spheres have no coordinates and shade unmapped, as with albedo.
+ *
+ *   glrtx_bind_material_maps  binds record m to material m: texture indices of the bound set (-1: none) and the normal map's scale.  maps == NULL or
+ *                     n_mat == 0 unbinds.  glrtx_upload_textures and glrtx_upload_scene DROP the maps: a new set invalidates the indices.
+ *                     GLRTX_EINVAL, everything unchanged, the offender named in the message: no texture set is bound; n_mat other than the scene's material
+ *                     count; an index outside -1 .. n_tex - 1; a normal map on a material that is neither diffuse nor conductor; a roughness map on a
+ *                     material that is not a conductor; a map whose texture has format GLRTX_TEX_RGBA8_SRGB; a scale that is not finite; reserved non-zero.
+ *   The wavefront kernel's calls keep refusing with "textures are bound".  glrtx_upload_textures' own refusals are unchanged, the conductor binding included:
+ *                     that is why this is a second call.
+ *   Feature pass      with maps bound, plane N of glrtx_render_features carries n' of the primary hit, so the denoisers' normal edge-stop and the
+ *                     reprojections' normal test see the detail the image shows.  Albedo, material id, distance and plane G are unchanged.
+ *   glrtx_debug_map_normal  the rule on caller arrays on the current HIP device, no context: record i is GLRTX_MAP_RECORD_FLOATS floats {n, e1, e2, (s0, t0),
+ *                     (s1, t1), (s2, t2), m} with m the DECODED texel; normal_out[3i..] = n'.  Errors through glrtx_last_error(NULL).
+ * NOT BUILT: emission maps (next-event estimation samples light triangles from a table that carries no coordinates), interpolated per-vertex tangents, maps
+ *   on spheres and on the dielectric, mip levels, height / parallax maps.  Groups: no call; a member is reached through glrtx_group_ctx(grp, i). */
+#define GLRTX_MAP_ALPHA_MIN 1e-3f
+#define GLRTX_MAP_RECORD_FLOATS 18
+typedef struct glrtx_material_map { int32_t normal, roughness; float normal_scale; int32_t reserved; } glrtx_material_map; /* 16 bytes; -1: none; reserved 0 */
+int glrtx_bind_material_maps(glrtx_ctx *ctx, const glrtx_material_map *maps, size_t n_mat);
+int glrtx_debug_map_normal(const float *records, size_t n, float scale, float *normal_out);
+
 /* ---- Groups: the same device layer on several GPUs of one node, behind one handle and one host thread.
  * No reference counterpart (the reference is single-GPU); SURVEY.md 8(b) sketches glrtx_create(ctx**, device_ids, n) with a
  * gathering read_accum -- this is that, kept apart from the single-context calls.  Member i owns the 8-row stripes s with

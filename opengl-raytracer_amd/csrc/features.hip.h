@@ -16,6 +16,8 @@
 // With a texture set bound (glrtx_upload_textures) the *_tex kernels run instead: TexArgs / TexGeomArgs add the set, and their store() puts the albedo tex_lookup
 // finds at the hit's coordinates into A for a diffuse material bound to a texture -- what the extension kernel shades with.  The material id is unchanged.  They
 // are further instantiations of the same loops, launched only while a set is bound; the kernels above keep their names and their instructions.
+// With material maps bound as well (glrtx_bind_material_maps) the *_maps kernels run: MapArgs / MapGeomArgs are the textured arguments, and their store() puts
+// the mapped normal n' (maps.hip.h) into N for a hit whose material is bound to a normal map.  Launched only while maps are bound.
 #pragma once
 #include "query.hip.h"
 
@@ -130,6 +132,28 @@ DEV void store(const TexArgs &q, unsigned id, const Hit &h) {
 DEV void store(const TexGeomArgs &q, unsigned id, const Hit &h) {
     store(static_cast<const GeomArgs &>(q), id, h);
     store_albedo(q, q.tex, id, h);
+}
+
+// With material maps bound on top of the set (glrtx_bind_material_maps): the planes as above, then N's normal again for a hit whose material is bound to a
+// normal map -- n' of maps.hip.h, what the extension kernel shades the primary hit with.  t, A, the material id and G are unchanged.
+DEV void store_mapped_normal(const Args &q, const TexSet &ts, unsigned id, const Hit &h) {
+    int lx, lrow;
+    if (h.tri < 0 || !pixel_of(q, id, lx, lrow)) return;
+    const MapRec mr = ts.maps[__float_as_int(q.sc.nrms[3 * h.tri].w)];
+    if (mr.normal < 0) return;
+    const Surf S = surf_tri(q.sc, h);
+    const float3 n = map_hit_normal(ts, q.sc.forks, mr.normal, mr.scale, h.tri, tex_hit_st(ts, h.tri, h.u, h.v), make_float3(S.nx, S.ny, S.nz));
+    q.out_n[(size_t)lrow * q.width + lx] = make_float4(canon(n.x), canon(n.y), canon(n.z), h.t);
+}
+struct MapArgs : TexArgs {};
+struct MapGeomArgs : TexGeomArgs {};
+DEV void store(const MapArgs &q, unsigned id, const Hit &h) {
+    store(static_cast<const TexArgs &>(q), id, h);
+    store_mapped_normal(q, q.tex, id, h);
+}
+DEV void store(const MapGeomArgs &q, unsigned id, const Hit &h) {
+    store(static_cast<const TexGeomArgs &>(q), id, h);
+    store_mapped_normal(q, q.tex, id, h);
 }
 
 // Trees: query::trace_tree's loop with the ray made here.
@@ -319,6 +343,10 @@ template <bool COMPACT>
 __global__ __launch_bounds__(kBlockThreads) void features_tree_tex(const TexArgs q) { tree_body<COMPACT>(q); }
 template <bool COMPACT>
 __global__ __launch_bounds__(kBlockThreads) void features_tree_geom_tex(const TexGeomArgs q) { tree_body<COMPACT>(q); }
+template <bool COMPACT>
+__global__ __launch_bounds__(kBlockThreads) void features_tree_maps(const MapArgs q) { tree_body<COMPACT>(q); }
+template <bool COMPACT>
+__global__ __launch_bounds__(kBlockThreads) void features_tree_geom_maps(const MapGeomArgs q) { tree_body<COMPACT>(q); }
 
 // Vines: the list scan, a wave 64 ids (one tile) at a time.
 template <class A>
@@ -340,6 +368,8 @@ __global__ __launch_bounds__(kBlockThreads) void features_vine(const Args q) { v
 __global__ __launch_bounds__(kBlockThreads) void features_vine_geom(const GeomArgs q) { vine_body(q); }
 __global__ __launch_bounds__(kBlockThreads) void features_vine_tex(const TexArgs q) { vine_body(q); }
 __global__ __launch_bounds__(kBlockThreads) void features_vine_geom_tex(const TexGeomArgs q) { vine_body(q); }
+__global__ __launch_bounds__(kBlockThreads) void features_vine_maps(const MapArgs q) { vine_body(q); }
+__global__ __launch_bounds__(kBlockThreads) void features_vine_geom_maps(const MapGeomArgs q) { vine_body(q); }
 
 }  // namespace features
 }  // namespace glrtx

@@ -107,6 +107,11 @@ struct glrtx_ctx {
     DevBuf texDesc, texTexels, texSt, texBind;
     int n_tex = 0;
     std::vector<float> scene_st;
+    // Material maps (glrtx_bind_material_maps; maps.hip.h), the set's until the next glrtx_upload_textures or glrtx_upload_scene: one MapRec a material on the
+    // device; have_maps: the MAPS instantiations are launched.  tex_format: the bound set's formats (a map may not be sRGB).
+    DevBuf texMaps;
+    bool have_maps = false;
+    std::vector<int> tex_format;
     // Environment (glrtx_upload_environment; environment.hip.h), kept across glrtx_upload_scene: the map's texels, the importance grid's five tables, and what the
     // kernels take of it (env: its pointers are these buffers'; p_env is set at every launch).  env_cfg / env_desc: what it was made from.
     DevBuf envTexels, envRowQ, envRowAlias, envColQ, envColAlias, envCellP;
@@ -1005,7 +1010,8 @@ void seal_feed(glrtx_ctx *c) {
 // The bound texture set as the kernels take it (n_tex > 0)
 static_assert(sizeof(TexDesc) == sizeof(glrtx_texture) && sizeof(glrtx_texture) == sizeof(glrt_detail::TexRecord), "one descriptor layout on the wire, the host and the device");
 TexSet tex_set(const glrtx_ctx *c) {
-    return TexSet{(const TexDesc *)c->texDesc.p, (const unsigned char *)c->texTexels.p, (const float2 *)c->texSt.p, (const int *)c->texBind.p, c->n_tex};
+    return TexSet{(const TexDesc *)c->texDesc.p, (const unsigned char *)c->texTexels.p, (const float2 *)c->texSt.p, (const int *)c->texBind.p, c->n_tex,
+                  c->have_maps ? (const MapRec *)c->texMaps.p : nullptr};
 }
 
 // Volume launches on the wavefront kernel (its V form, kWgwfVolume): the switch is on (glrtx_set_volume_wavefront; GLRTX_VOLUME_WAVEFRONT=0/1, read at every
@@ -2232,7 +2238,7 @@ void glrtx_destroy(glrtx_ctx *c) {
         for (auto &ch : sl.chunks) dev_free(ch);
         if (sl.feed_h) (void)hipHostFree(sl.feed_h);
     }
-    dev_free(c->texDesc); dev_free(c->texTexels); dev_free(c->texSt); dev_free(c->texBind);
+    dev_free(c->texDesc); dev_free(c->texTexels); dev_free(c->texSt); dev_free(c->texBind); dev_free(c->texMaps);
     for (DevBuf *b : {&c->envTexels, &c->envRowQ, &c->envRowAlias, &c->envColQ, &c->envColAlias, &c->envCellP}) dev_free(*b);
     dev_free(c->spheres); dev_free(c->sphereMat); dev_free(c->volDensity); dev_free(c->volTemp); dev_free(c->forks); dev_free(c->cnodes); dev_free(c->cranks); dev_free(c->nrms); dev_free(c->mats); dev_free(c->lights); dev_free(c->vine);
     dev_free(c->accum_own); dev_free(c->counter); dev_free(c->rgba8); dev_free(c->work);
@@ -2334,6 +2340,7 @@ int glrtx_upload_scene(glrtx_ctx *c, const float *vert, size_t n_vert, const flo
     c->leaf_tri.swap(P.leaf_tri);
     c->n_spheres = 0;  // spheres reference this scene's materials: upload them again after a new scene
     c->n_tex = 0;      // ... and so does a texture set's binding (glrtx_upload_textures)
+    c->have_maps = false;  // ... and the material maps bound on top of it (glrtx_bind_material_maps)
     c->scene_st.assign(6 * (c->leaf_tri.size() + 1), 0.0f);  // the corners' (s, t) of every device triangle: words 6 and 7 of a wire vertex
     for (size_t k = 0; k < c->leaf_tri.size(); k++)
         for (int j = 0; j < 3; j++) {
@@ -3166,6 +3173,7 @@ int glrtx_upload_textures(glrtx_ctx *c, const glrtx_texture *tex, size_t n_tex, 
         HIP_TRY(c, hipSetDevice(c->device));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         c->n_tex = 0;
+        c->have_maps = false;
         return GLRTX_OK;
     }
     if (n_mat != (size_t)c->n_mat) return fail(c, GLRTX_EINVAL, "%s: %zu bindings, the scene has %d materials", fn, n_mat, c->n_mat);
@@ -3196,6 +3204,9 @@ int glrtx_upload_textures(glrtx_ctx *c, const glrtx_texture *tex, size_t n_tex, 
         return rc;
     }
     dev_free(c->texDesc); dev_free(c->texTexels); dev_free(c->texSt); dev_free(c->texBind);
+    c->have_maps = false;  // (glrtx_bind_material_maps: a new set invalidates the indices)
+    c->tex_format.resize(n_tex);
+    for (size_t k = 0; k < n_tex; k++) c->tex_format[k] = tex[k].format;
     c->texDesc = d; c->texTexels = t; c->texSt = st; c->texBind = b;
     c->n_tex = (int)n_tex;
     return GLRTX_OK;
@@ -3225,6 +3236,68 @@ int glrtx_debug_texture_lookup(const glrtx_texture *tex, size_t n_tex, const voi
     }
     s.sync();
     s.download(rgb_out, d_out, 3 * n * sizeof(float));
+    return s.result(GLRTX_OK, fn);
+}
+
+// ---- material maps (include/glrtx.h "Material maps"; maps.hip.h)
+static_assert(sizeof(glrtx_material_map) == sizeof(MapRec) && sizeof(MapRec) == 16, "one map record on the wire and the device");
+static_assert(GLRTX_MAP_ALPHA_MIN == MAP_ALPHA_MIN && GLRTX_MAP_RECORD_FLOATS == kMapRecordFloats, "material map constants");
+
+int glrtx_bind_material_maps(glrtx_ctx *c, const glrtx_material_map *maps, size_t n_mat) {
+    const char *fn = "glrtx_bind_material_maps";
+    if (!c) return GLRTX_EINVAL;
+    seal_feed(c);  // (nothing is appended to an open launch across this call: glrtx_ctx::OpenFeed)
+    if (!maps || n_mat == 0) {  // unbind: the next launch runs the textured kernels as before (the buffer stays until the context goes)
+        HIP_TRY(c, hipSetDevice(c->device));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        c->have_maps = false;
+        return GLRTX_OK;
+    }
+    if (!c->have_scene || c->n_tex == 0) return fail(c, GLRTX_EINVAL, "%s: no texture set is bound (call glrtx_upload_textures first)", fn);
+    if (n_mat != (size_t)c->n_mat) return fail(c, GLRTX_EINVAL, "%s: %zu records, the scene has %d materials", fn, n_mat, c->n_mat);
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));  // (also behind every launch that reads the materials or the maps bound before)
+    std::vector<float4> m0(3 * n_mat);
+    HIP_TRY(c, hipMemcpy(m0.data(), c->mats.p, m0.size() * sizeof(float4), hipMemcpyDeviceToHost));
+    for (size_t m = 0; m < n_mat; m++) {
+        const glrtx_material_map &r = maps[m];
+        int type;
+        std::memcpy(&type, &m0[3 * m].w, 4);
+        for (int which = 0; which < 2; which++) {
+            const int32_t k = which ? r.roughness : r.normal;
+            const char *what = which ? "roughness" : "normal";
+            if (k < -1 || k >= c->n_tex) return fail(c, GLRTX_EINVAL, "%s: material %zu: %s map %d of %d textures", fn, m, what, k, c->n_tex);
+            if (k >= 0 && c->tex_format[(size_t)k] == GLRTX_TEX_RGBA8_SRGB)
+                return fail(c, GLRTX_EINVAL, "%s: material %zu: %s map %d has format GLRTX_TEX_RGBA8_SRGB (a map holds vectors, not colours)", fn, m, what, k);
+        }
+        if (r.normal >= 0 && type != 2 && type != 3)
+            return fail(c, GLRTX_EINVAL, "%s: material %zu has a normal map and is neither diffuse nor conductor (type %d)", fn, m, type);
+        if (r.roughness >= 0 && type != 3) return fail(c, GLRTX_EINVAL, "%s: material %zu has a roughness map and is not a conductor (type %d)", fn, m, type);
+        if (!std::isfinite(r.normal_scale)) return fail(c, GLRTX_EINVAL, "%s: material %zu: normal_scale is not finite", fn, m);
+        if (r.reserved != 0) return fail(c, GLRTX_EINVAL, "%s: material %zu: reserved is %d, not 0", fn, m, r.reserved);
+    }
+    DevBuf b;  // a fresh buffer first: a failure leaves the bound maps as they were
+    if (int rc = dev_upload(c, b, maps, n_mat * sizeof(glrtx_material_map))) { dev_free(b); return rc; }
+    dev_free(c->texMaps);
+    c->texMaps = b;
+    c->have_maps = true;
+    return GLRTX_OK;
+}
+
+int glrtx_debug_map_normal(const float *records, size_t n, float scale, float *normal_out) {
+    const char *fn = "glrtx_debug_map_normal";
+    if (n && (!records || !normal_out)) return fail(nullptr, GLRTX_EINVAL, "%s: NULL buffer", fn);
+    if (n > (size_t)INT32_MAX / kMapRecordFloats) return fail(nullptr, GLRTX_EINVAL, "%s: too many records", fn);
+    if (n == 0) return GLRTX_OK;
+    DebugScratch s;
+    const float *d_rec = s.alloc<float>(kMapRecordFloats * n * sizeof(float), records);
+    float *d_out = s.alloc<float>(3 * n * sizeof(float));
+    if (s.ok()) {
+        hipLaunchKernelGGL(map_normal_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, d_rec, (unsigned)n, scale, d_out);
+        s.e = hipGetLastError();
+    }
+    s.sync();
+    s.download(normal_out, d_out, 3 * n * sizeof(float));
     return s.result(GLRTX_OK, fn);
 }
 
@@ -3827,7 +3900,17 @@ int glrtx_render_features(glrtx_ctx *c, const glrtx_params *p) {
     const KernelT kernel_t = vine ? (KernelT)features::features_vine_tex : compact ? (KernelT)features::features_tree_tex<true> : (KernelT)features::features_tree_tex<false>;
     const KernelGT kernel_gt = vine ? (KernelGT)features::features_vine_geom_tex
                                     : compact ? (KernelGT)features::features_tree_geom_tex<true> : (KernelGT)features::features_tree_geom_tex<false>;
-    const void *kernel = tex ? (geom ? (const void *)kernel_gt : (const void *)kernel_t) : geom ? (const void *)kernel_g : (const void *)kernel_n;
+    // with material maps bound on top of the set: the *_maps instantiations, whose plane N carries the mapped normal
+    using KernelM = void (*)(const features::MapArgs);
+    using KernelGM = void (*)(const features::MapGeomArgs);
+    const bool maps = tex && c->have_maps;
+    const KernelM kernel_m = vine ? (KernelM)features::features_vine_maps : compact ? (KernelM)features::features_tree_maps<true> : (KernelM)features::features_tree_maps<false>;
+    const KernelGM kernel_gm = vine ? (KernelGM)features::features_vine_geom_maps
+                                    : compact ? (KernelGM)features::features_tree_geom_maps<true> : (KernelGM)features::features_tree_geom_maps<false>;
+    const void *kernel = maps  ? (geom ? (const void *)kernel_gm : (const void *)kernel_m)
+                         : tex ? (geom ? (const void *)kernel_gt : (const void *)kernel_t)
+                         : geom ? (const void *)kernel_g
+                                : (const void *)kernel_n;
     const int lds = vine ? 0 : lds_stack + (compact ? lds_ranks : 0);
     if (lds > 64 * 1024) HIP_TRY(c, hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     int per_cu = 0;
@@ -3847,7 +3930,18 @@ int glrtx_render_features(glrtx_ctx *c, const glrtx_params *p) {
     const size_t needed = (a.n + kBlockThreads - 1) / kBlockThreads;
     const unsigned grid = (unsigned)std::max<size_t>(1, std::min<size_t>((size_t)per_cu * (size_t)c->n_cu, needed));
     HIP_TRY(c, hipMemsetAsync(c->ftCounter.p, 0, sizeof(unsigned), c->stream));
-    if (tex && geom) {
+    if (maps && geom) {
+        features::MapGeomArgs ga;
+        static_cast<features::Args &>(ga) = a;
+        ga.out_g = (float4 *)c->ftG.p; ga.wire = (const int *)c->qwire.p;
+        ga.tex = tex_set(c);
+        hipLaunchKernelGGL(kernel_gm, dim3(grid), dim3(kBlockThreads), lds, c->stream, ga);
+    } else if (maps) {
+        features::MapArgs ta;
+        static_cast<features::Args &>(ta) = a;
+        ta.tex = tex_set(c);
+        hipLaunchKernelGGL(kernel_m, dim3(grid), dim3(kBlockThreads), lds, c->stream, ta);
+    } else if (tex && geom) {
         features::TexGeomArgs ga;
         static_cast<features::Args &>(ga) = a;
         ga.out_g = (float4 *)c->ftG.p; ga.wire = (const int *)c->qwire.p;
@@ -4685,8 +4779,13 @@ static int render_one(glrtx_ctx *c, const glrtx_params *p, const RenderReq &req)
         static constexpr EKernel kPersistentEnv[2][2] = {{pt_render_persistent_env<false, false>, pt_render_persistent_env<true, false>},  // [textures][count_rays]
                                                          {pt_render_persistent_env<false, true>, pt_render_persistent_env<true, true>}};
         static constexpr const char *kPersistentEnvNames[2] = {"pt_render_persistent (extensions, environment)", "pt_render_persistent (extensions, environment, textures)"};
-        const EKernel ek = kPersistentEnv[tex][c->count_rays];
-        const PKernel pk = envb ? (PKernel) nullptr : tex ? kPersistentTex[vol][c->count_rays] : kPersistent[which][c->count_rays];
+        // material maps bound on top of the set (glrtx_bind_material_maps): the MAPS instantiations; without them the kernels above are launched as ever
+        static constexpr PKernel kPersistentMaps[2][2] = {{pt_render_persistent_tex<false, false, true>, pt_render_persistent_tex<true, false, true>},  // [extensions | volume][count_rays]
+                                                          {pt_render_persistent_tex<false, true, true>, pt_render_persistent_tex<true, true, true>}};
+        static constexpr EKernel kPersistentEnvMaps[2] = {pt_render_persistent_env<false, true, true>, pt_render_persistent_env<true, true, true>};  // [count_rays]
+        const bool maps = tex && c->have_maps;
+        const EKernel ek = maps ? kPersistentEnvMaps[c->count_rays] : kPersistentEnv[tex][c->count_rays];
+        const PKernel pk = envb ? (PKernel) nullptr : maps ? kPersistentMaps[vol][c->count_rays] : tex ? kPersistentTex[vol][c->count_rays] : kPersistent[which][c->count_rays];
         const void *kfn = envb ? (const void *)ek : (const void *)pk;
         ExtArgs ex{};
         if (tex) ex.tex = tex_set(c);
@@ -4705,7 +4804,9 @@ static int render_one(glrtx_ctx *c, const glrtx_params *p, const RenderReq &req)
         if (grid < 1) grid = 1;
         HIP_TRY(c, hipMemsetAsync(c->work.p, 0, sizeof(unsigned), c->stream));
         HIP_TRY(c, hipEventRecord(rec->ev0, c->stream));
-        c->last_kernel = envb ? kPersistentEnvNames[tex] : tex ? kPersistentTexNames[vol] : kPersistentNames[which];
+        static constexpr const char *kPersistentMapsNames[3] = {"pt_render_persistent (extensions, textures, maps)", "pt_render_persistent (volume, textures, maps)",
+                                                                "pt_render_persistent (extensions, environment, textures, maps)"};
+        c->last_kernel = maps ? kPersistentMapsNames[envb ? 2 : vol] : envb ? kPersistentEnvNames[tex] : tex ? kPersistentTexNames[vol] : kPersistentNames[which];
         const VolArgs va = vol ? c->vol : VolArgs{};
         if (envb) {
             EnvArgs ea = c->env;

@@ -38,6 +38,7 @@
 #include "trav_asm.hip.h"
 #include "scan_asm.hip.h"
 #include "texture.hip.h"
+#include "maps.hip.h"
 #include "environment.hip.h"
 
 namespace glrtx {
@@ -914,10 +915,14 @@ constexpr int EXT_WHITTED = 2;     // Whitted-style: a diffuse surface gathers i
 // hit, which then stands wherever the reference reads param0 (:514 with its 1 / PI, :372 without).
 // ENV (implies EXT; include/glrtx.h "Environment"): *env is the bound environment.  A miss adds beta * Le(d) -- at every depth in escape mode, under the emitter
 // rule (:490) in sampled mode --, and in sampled mode the environment is one more light of sampleDirect, picked with probability env->p_env.
-template <bool EXT, bool TEX = false, bool ENV = false>
+// MAPS (implies TEX; include/glrtx.h "Material maps"): S carries the mapped normal n' already (bounce_ext), which then stands wherever the reference reads the
+// shading normal; `rough` says that the hit's conductor is bound to a roughness map and (rax, ray) REPLACE alpha.x / alpha.y at the three places they are read.
+template <bool EXT, bool TEX = false, bool ENV = false, bool MAPS = false>
 DEV void shade_core(const KernelArgs &a, const float4 *lds_mats, Rng &rng, Path &P, float h_t, bool h_hit, const Surf &S, int ext_flags, Shade &out,
-                    bool textured = false, float ar = 0.f, float ag = 0.f, float ab = 0.f, const EnvArgs *env = nullptr) {
+                    bool textured = false, float ar = 0.f, float ag = 0.f, float ab = 0.f, const EnvArgs *env = nullptr, bool rough = false, float rax = 0.f,
+                    float ray = 0.f) {
     static_assert(!TEX || EXT, "textures are shaded by the extension kernel");
+    static_assert(!MAPS || TEX, "material maps are looked up in the bound texture set");
     static_assert(!ENV || EXT, "the environment is shaded by the extension kernel");
     bool env_shadow = false;
     const DevScene &sc = a.sc;
@@ -1019,7 +1024,8 @@ DEV void shade_core(const KernelArgs &a, const float4 *lds_mats, Rng &rng, Path 
                 pdf = div_pi(wlz);
             } else if (type == 3) {
                 // conductor :520-532; param0 = kappa, param1 = eta
-                const float ax = M.m1.w, ay = M.m2.w;
+                float ax = M.m1.w, ay = M.m2.w;
+                if (MAPS && rough) { ax = rax; ay = ray; }
                 const float u0 = pt_rand(rng);
                 const float u1 = pt_rand(rng);
                 // sampleGGXVNDF :195-214
@@ -1101,7 +1107,8 @@ DEV void shade_core(const KernelArgs &a, const float4 *lds_mats, Rng &rng, Path 
                     sdist = PT_INFTY;
                     float gx = fx, gy = fy, gz = fz;  // diffuse: albedo / PI (textured albedo included)
                     if (type == 3) {
-                        const float ax = M.m1.w, ay = M.m2.w;
+                        float ax = M.m1.w, ay = M.m2.w;
+                        if (MAPS && rough) { ax = rax; ay = ray; }
                         const float cosI = fmax_c((-(dirz * nz) - (diry * ny)) - (dirx * nx), 0.0f);
                         const float c2 = cosI * cosI, s2 = 1.0f - c2;
                         const float Fx = fresnel1(c2, s2, cosI, M.m2.x, M.m1.x);
@@ -1163,7 +1170,8 @@ DEV void shade_core(const KernelArgs &a, const float4 *lds_mats, Rng &rng, Path 
                         gx = M.m1.x; gy = M.m1.y; gz = M.m1.z;  // albedo without 1/PI :372
                         if (TEX && textured) { gx = ar; gy = ag; gz = ab; }
                     } else if (type == 3) {
-                        const float ax = M.m1.w, ay = M.m2.w;
+                        float ax = M.m1.w, ay = M.m2.w;
+                        if (MAPS && rough) { ax = rax; ay = ray; }
                         const float cosI = fmax_c((-(dirz * nz) - (diry * ny)) - (dirx * nx), 0.0f);
                         const float c2 = cosI * cosI, s2 = 1.0f - c2;
                         const float Fx = fresnel1(c2, s2, cosI, M.m2.x, M.m1.x);
@@ -1457,7 +1465,7 @@ DEV bool bounce_volume(const KernelArgs &a, const ExtArgs &ex, const VolArgs &vo
     return P.depth >= a.max_depth;
 }
 
-template <bool VOL = false, bool TEX = false, bool ENV = false>
+template <bool VOL = false, bool TEX = false, bool ENV = false, bool MAPS = false>
 DEV bool bounce_ext(const KernelArgs &a, const ExtArgs &ex, const float4 *lds_spheres, const float4 *lds_mats, int *stack, Rng &rng, Path &P, unsigned long long &rays,
                     const VolArgs *vo = nullptr, const EnvArgs *env = nullptr) {
     static_assert(!(ENV && VOL), "the volume branch has its own escape path: no environment beside it");
@@ -1490,7 +1498,29 @@ DEV bool bounce_ext(const KernelArgs &a, const ExtArgs &ex, const float4 *lds_sp
                 textured = true;
             }
         }
-        shade_core<true, true, ENV>(a, lds_mats, rng, P, h.t, h.tri != -1, S, ex.flags, sh, textured, alb.x, alb.y, alb.z, env);
+        if (MAPS) {
+            // a triangle whose material is bound to a map (glrtx_bind_material_maps): n' takes the place of surf_tri's normal, a conductor's alphas come from the
+            // roughness texel.  The test is wave-uniform wherever a wave's hits lie on one material; spheres have no coordinates and shade unmapped.
+            bool rough = false;
+            float2 al = make_float2(0.f, 0.f);
+            if (h.tri >= 0) {
+                const MapRec mr = ex.tex.maps[S.mtrl];
+                if ((mr.normal & mr.roughness) != -1) {
+                    const float2 st = tex_hit_st(ex.tex, h.tri, h.u, h.v);
+                    if (mr.normal >= 0) {
+                        const float3 n = map_hit_normal(ex.tex, a.sc.forks, mr.normal, mr.scale, h.tri, st, make_float3(S.nx, S.ny, S.nz));
+                        S.nx = n.x; S.ny = n.y; S.nz = n.z;
+                    }
+                    if (mr.roughness >= 0) {
+                        al = map_alpha(tex_lookup(ex.tex, mr.roughness, st.x, st.y));
+                        rough = true;
+                    }
+                }
+            }
+            shade_core<true, true, ENV, true>(a, lds_mats, rng, P, h.t, h.tri != -1, S, ex.flags, sh, textured, alb.x, alb.y, alb.z, env, rough, al.x, al.y);
+        } else {
+            shade_core<true, true, ENV>(a, lds_mats, rng, P, h.t, h.tri != -1, S, ex.flags, sh, textured, alb.x, alb.y, alb.z, env);
+        }
     } else if (ENV) {
         shade_core<true, false, true>(a, lds_mats, rng, P, h.t, h.tri != -1, S, ex.flags, sh, false, 0.f, 0.f, 0.f, env);
     } else {
@@ -1787,7 +1817,8 @@ __global__ __launch_bounds__(kBlockThreads) void pt_render_persistent(const Kern
 // Launched only while a texture set is bound.  The loop is written out a second time on purpose: called from a body shared by both kernels, the compiler allocated
 // the registers of every pt_render_persistent instantiation differently (the same operations, another schedule), and the kernels without textures are to keep
 // their instructions.  Keep the two in step.
-template <bool COUNT_RAYS, bool VOL>
+// MAPS: with material maps bound on top of the set (include/glrtx.h "Material maps"), bounce_ext<VOL, true, false, true>; instantiations of their own, launched only then.
+template <bool COUNT_RAYS, bool VOL, bool MAPS = false>
 __global__ __launch_bounds__(kBlockThreads) void pt_render_persistent_tex(const KernelArgs a_entry, unsigned *work_counter_entry, const ExtArgs ex_entry,
                                                                           const VolArgs vol_entry) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
@@ -1867,8 +1898,8 @@ __global__ __launch_bounds__(kBlockThreads) void pt_render_persistent_tex(const 
             }
             bool finished = true;
             if (a.max_depth > 0) {
-                if (VOL) finished = bounce_ext<true, true>(a, ka->ex, lds_spheres, lds_mats, stack, rng, P, rays, &ka->vol);
-                else finished = bounce_ext<false, true>(a, ka->ex, lds_spheres, lds_mats, stack, rng, P, rays);
+                if (VOL) finished = bounce_ext<true, true, false, MAPS>(a, ka->ex, lds_spheres, lds_mats, stack, rng, P, rays, &ka->vol);
+                else finished = bounce_ext<false, true, false, MAPS>(a, ka->ex, lds_spheres, lds_mats, stack, rng, P, rays);
             }
             if (finished) {
                 acc.x = acc.x + fmin_c(P.Lx, 100.0f);  // :558, :608
@@ -1903,7 +1934,7 @@ DEV const PersistEnvKernArgs *persist_env_kernargs() {
     asm volatile("" : "+s"(p));  // opaque: loads through it stay behind this point
     return (const PersistEnvKernArgs *)p;
 }
-template <bool COUNT_RAYS, bool TEX>
+template <bool COUNT_RAYS, bool TEX, bool MAPS = false>  // (MAPS: as pt_render_persistent_tex's; needs TEX)
 __global__ __launch_bounds__(kBlockThreads) void pt_render_persistent_env(const KernelArgs a_entry, unsigned *work_counter_entry, const ExtArgs ex_entry,
                                                                           const EnvArgs env_entry) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
@@ -1982,7 +2013,7 @@ __global__ __launch_bounds__(kBlockThreads) void pt_render_persistent_env(const 
                 fresh = false;
             }
             bool finished = true;
-            if (a.max_depth > 0) finished = bounce_ext<false, TEX, true>(a, ka->ex, lds_spheres, lds_mats, stack, rng, P, rays, nullptr, &ka->env);
+            if (a.max_depth > 0) finished = bounce_ext<false, TEX, true, MAPS>(a, ka->ex, lds_spheres, lds_mats, stack, rng, P, rays, nullptr, &ka->env);
             if (finished) {
                 acc.x = acc.x + fmin_c(P.Lx, 100.0f);  // :558, :608
                 acc.y = acc.y + fmin_c(P.Ly, 100.0f);

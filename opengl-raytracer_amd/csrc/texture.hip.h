@@ -26,13 +26,16 @@ constexpr int TEX_REPEAT = 0, TEX_CLAMP = 1;
 constexpr int TEX_NEAREST = 0, TEX_BILINEAR = 1;
 
 // A bound set.  tri_st: three {s, t} a device triangle (the index surf_tri reads nrms with; triangle 0 is the never-hit record), frozen when the set was
-// uploaded.  mat_tex: texture index a material, -1 untextured.
+// uploaded.  mat_tex: texture index a material, -1 untextured.  maps: the material maps bound on top of the set (glrtx_bind_material_maps; maps.hip.h), one record
+// a material, or null; only the MAPS instantiations read it, and they are launched only while maps are bound.
+struct MapRec;
 struct TexSet {
     const TexDesc *desc;
     const unsigned char *texels;
     const float2 *tri_st;
     const int *mat_tex;
     int n_tex;
+    const MapRec *maps;
 };
 
 // sRGB byte -> linear: the piecewise formula in float64, rounded once to fp32 (bit patterns; tests/test_texture_host.py recomputes them)

@@ -49,6 +49,7 @@ void Scene::parse(const std::string &filename) {
     if (const char *e = std::getenv("GLRT_EXTENSIONS")) extensions_ = extensions_ || std::atoi(e) != 0;
     spheres.clear();
     textures_.clear();
+    maps_.clear();
     environment_ = EnvironmentSpec{};
     hasDielectric_ = false;
     volumeSpecs_.clear();
@@ -230,6 +231,48 @@ void Scene::parse(const std::string &filename) {
             hasDielectric_ = true;
         } else {
             GLRT_FatalError("Unsupported material: %s", material.c_str());
+        }
+        if (extensions_) {  // EXTENSION (scene.h: MapSpec); off, the keys are ones the parser does not know
+            for (const char *key : {"normal_map", "roughness_map"}) {
+                const Json &mp = sh[key];
+                if (mp.is_null()) continue;
+                const bool rough = key[0] == 'r';
+                if (!mp.is_object()) GLRT_FatalError("shape %zu: \"%s\" is not an object", i, key);
+                if (rough ? material != "conductor" : (material != "diffuse" && material != "conductor"))
+                    GLRT_FatalError("shape %zu: \"%s\" on a %s shape (%s)", i, key, material.c_str(), rough ? "a conductor takes one" : "a diffuse or conductor shape takes one");
+                MapSpec spec;
+                spec.material = materials.size();
+                spec.roughness = rough;
+                if (!mp["file"].is_string() || mp["file"].string_value().empty()) GLRT_FatalError("shape %zu: \"%s\" has no \"file\" string", i, key);
+                spec.file = baseDir + "/" + mp["file"].string_value();
+                spec.filter = GLRTX_TEX_BILINEAR;
+                if (!mp["filter"].is_null()) {
+                    const std::string v = mp["filter"].is_string() ? mp["filter"].string_value() : std::string();
+                    if (v == "bilinear") spec.filter = GLRTX_TEX_BILINEAR;
+                    else if (v == "nearest") spec.filter = GLRTX_TEX_NEAREST;
+                    else GLRT_FatalError("shape %zu: %s \"filter\" is not \"bilinear\" or \"nearest\"", i, key);
+                }
+                spec.wrap = GLRTX_TEX_REPEAT;
+                if (!mp["wrap"].is_null()) {
+                    const std::string v = mp["wrap"].is_string() ? mp["wrap"].string_value() : std::string();
+                    if (v == "repeat") spec.wrap = GLRTX_TEX_REPEAT;
+                    else if (v == "clamp") spec.wrap = GLRTX_TEX_CLAMP;
+                    else GLRT_FatalError("shape %zu: %s \"wrap\" is not \"repeat\" or \"clamp\"", i, key);
+                }
+                if (!mp["srgb"].is_null() && !(mp["srgb"].is_bool() && !mp["srgb"].bool_value()))
+                    GLRT_FatalError("shape %zu: %s \"srgb\": a map holds vectors, not colours (an sRGB map is refused)", i, key);
+                spec.scale = 1.0f;
+                if (!mp["scale"].is_null()) {
+                    if (rough) GLRT_FatalError("shape %zu: roughness_map has no \"scale\"", i);
+                    spec.scale = mp["scale"].is_number() ? (float)mp["scale"].number_value() : NAN;
+                    if (!std::isfinite(spec.scale)) GLRT_FatalError("shape %zu: normal_map \"scale\" is not a finite number", i);
+                }
+                std::string terr;
+                if (!readTextureFile(spec.file, spec.image, terr)) GLRT_FatalError("shape %zu: %s \"file\": %s", i, key, terr.c_str());
+                spec.format = spec.image.isFloat ? GLRTX_TEX_RGBA32F : GLRTX_TEX_RGBA8_UNORM;
+                GLRT_Info("%s: %s, %d x %d, %s", key, spec.file.c_str(), spec.image.width, spec.image.height, spec.image.isFloat ? "float" : "8-bit linear");
+                maps_.push_back(std::move(spec));
+            }
         }
         materials.push_back(m);
 
@@ -717,6 +760,29 @@ struct SceneTextureProbe {
 
 extern "C" GLRT_API int glrt_scene_texture_probe(const char *json, int extensions, long long counts[2], int *info, unsigned char *texels, size_t texel_cap) {
     return glrt::SceneTextureProbe::run(json, extensions, counts, info, texels, texel_cap);
+}
+
+// Material-map probe: parse with extensions on or off.  Returns the number of maps; per map info[7k..] = {material, roughness (0 / 1), width, height, format,
+// wrap, filter} and scale[k].
+namespace glrt {
+struct SceneMapProbe {
+    static int run(const char *json, int extensions, int *info, float *scale, int cap) {
+        Scene sc;
+        sc.enableExtensions(extensions != 0);
+        sc.parse(json);
+        for (size_t k = 0; k < sc.maps_.size() && (int)k < cap; k++) {
+            const Scene::MapSpec &t = sc.maps_[k];
+            const int row[7] = {(int)t.material, t.roughness ? 1 : 0, t.image.width, t.image.height, t.format, t.wrap, t.filter};
+            if (info) std::memcpy(info + 7 * k, row, sizeof row);
+            if (scale) scale[k] = t.scale;
+        }
+        return (int)sc.maps_.size();
+    }
+};
+}  // namespace glrt
+
+extern "C" GLRT_API int glrt_scene_map_probe(const char *json, int extensions, int *info, float *scale, int cap) {
+    return glrt::SceneMapProbe::run(json, extensions, info, scale, cap);
 }
 
 // Environment probe: parse with extensions on or off and an optional mode override (-1: none).  info = {present, mode, size, format, filter, latlong, texel

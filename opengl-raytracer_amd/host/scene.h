@@ -69,6 +69,22 @@ public:
         TextureImage image;
     };
     const std::vector<TextureSpec> &textureSpecs() const { return textures_; }
+    // Material maps (include/glrtx.h "Material maps"; no reference counterpart).  With extensions on, a "diffuse" or "conductor" shape may carry
+    //     "normal_map": {"file": "x.pfm" | "x.ppm", "filter": .., "wrap": .., "scale": x}      and a "conductor" shape
+    //     "roughness_map": {"file": "x.pfm" | "x.ppm", "filter": .., "wrap": ..}
+    // "file", "filter" and "wrap" as in "texture".  A PPM is read as GLRTX_TEX_RGBA8_UNORM: a map holds vectors, not colours, and "srgb": true is a
+    // FatalError.  "scale" (normal maps; default 1) is the normal map's scale and must be finite.  Both are looked up at the OBJ's vt coordinates.  A map on a
+    // shape of another material and a value other than those above are FatalErrors that name the key.  Window uploads the maps' images behind the textures in
+    // the one set and binds them (glrtx_bind_material_maps).  With extensions off the keys are ignored, as "texture" is.
+    struct MapSpec {
+        size_t material;  // the shape's material
+        bool roughness;   // false: a normal map
+        std::string file;
+        int format, wrap, filter;  // GLRTX_TEX_*
+        float scale;
+        TextureImage image;
+    };
+    const std::vector<MapSpec> &mapSpecs() const { return maps_; }
     // Environment (include/glrtx.h "Environment"; no reference counterpart).  With extensions on, the scene file may carry the top-level key
     //     "environment": {"file": "x.pfm" | "x.ppm", "layout": "latlong" | "octahedral", "size": N, "mode": "escape" | "sampled", "scale": x | [r, g, b],
     //                     "rotate_y": degrees, "light_pick": p, "filter": "bilinear" | "nearest", "srgb": true | false}
@@ -165,6 +181,7 @@ private:
     std::string bvhBuilder_ = "sah";
     std::vector<float> spheres;  // extension: 5 floats per sphere {cx, cy, cz, radius, material}
     std::vector<TextureSpec> textures_;  // extension: one per textured diffuse shape, in shape order
+    std::vector<MapSpec> maps_;          // extension: the shapes' normal and roughness maps, in shape order
     EnvironmentSpec environment_;        // extension: the scene file's "environment" block
     int envModeOverride_ = -1;
     bool extensions_ = false, whitted_ = false, hasDielectric_ = false;
@@ -190,6 +207,7 @@ private:
     friend struct SceneMorphSparseProbe;
     friend struct SceneNormalsProbe;
     friend struct SceneTextureProbe;
+    friend struct SceneMapProbe;
     friend struct SceneEnvironmentProbe;
 };
 

@@ -98,7 +98,7 @@ protected:
 
 private:
     void frameParams(struct ::glrtx_params &p) const;
-    void uploadTextures();  // the scene's texture set on every member (glrtx_upload_textures)
+    void uploadTextures();  // the scene's texture set, then its material maps, on every member (glrtx_upload_textures, glrtx_bind_material_maps)
     void uploadEnvironment();  // the scene's environment on every member (glrtx_upload_environment)
     void resizeDefault(int width, int height);
     void resetBuffer();

@@ -178,7 +178,8 @@ EXPORTS = ["glrtx_abi_version", "glrtx_create", "glrtx_destroy", "glrtx_last_err
            "glrtx_upload_morph_targets_sparse", "glrtx_debug_deform_sparse",
            "glrtx_upload_normal_topology", "glrtx_update_positions", "glrtx_update_positions_device", "glrtx_set_pose_normals",
            "glrtx_debug_rebuild_normals", "glrtx_debug_normals_burst", "glrtx_upload_textures", "glrtx_debug_texture_lookup",
-           "glrtx_upload_environment", "glrtx_set_environment_cfg", "glrtx_debug_env_weights", "glrtx_debug_env_sample", "glrtx_debug_env_eval"]
+           "glrtx_upload_environment", "glrtx_set_environment_cfg", "glrtx_debug_env_weights", "glrtx_debug_env_sample", "glrtx_debug_env_eval",
+           "glrtx_bind_material_maps", "glrtx_debug_map_normal"]
 
 SCENE_BUFFERS = ("nodes", "cnodes", "nrms", "lights", "vine", "root")  # glrtx_debug_read_scene's `which`, in order (GLRTX_SCENE_*)
 
@@ -396,6 +397,11 @@ def lib():
             L.glrtx_debug_env_eval.argtypes = [vp, vp, C.c_size_t, vp, fp, C.c_size_t, fp]
         except AttributeError:
             pass
+        try:  # (additive to ABI 10 as well: material maps)
+            L.glrtx_bind_material_maps.argtypes = [vp, vp, C.c_size_t]
+            L.glrtx_debug_map_normal.argtypes = [fp, C.c_size_t, C.c_float, fp]
+        except AttributeError:
+            pass
         _lib = L
     return _lib
 
@@ -474,6 +480,18 @@ def debug_texture_lookup(textures, which, st):
         raise ValueError(f"debug_texture_lookup: {w.size} texture indices, {c.shape[0]} coordinates")
     out = np.zeros((w.size, 3), np.float32)
     rc = L.glrtx_debug_texture_lookup(desc.ctypes.data, desc.size, blob.ctypes.data, blob.size, w.ctypes.data_as(C.POINTER(C.c_int32)), _fp(c), w.size, _fp(out))
+    if rc != 0:
+        raise GlrtxError(rc, L.glrtx_last_error(None).decode())
+    return out
+
+
+def debug_map_normal(records, scale=1.0):
+    """glrtx_debug_map_normal on the current device: the kernels' map_normal (include/glrtx.h "Material maps").  Arguments and result as host.map_normal's."""
+    from .host import MAP_RECORD_FLOATS
+    L = lib()
+    r = np.ascontiguousarray(records, np.float32).reshape(-1, MAP_RECORD_FLOATS)
+    out = np.zeros((r.shape[0], 3), np.float32)
+    rc = L.glrtx_debug_map_normal(_fp(r), r.shape[0], C.c_float(scale), _fp(out))
     if rc != 0:
         raise GlrtxError(rc, L.glrtx_last_error(None).decode())
     return out
@@ -1087,6 +1105,20 @@ class Device:
         desc, blob = pack_textures(textures or [])
         b = np.ascontiguousarray([] if material_texture is None else material_texture, dtype=np.int32).reshape(-1)
         self._ck(self.L.glrtx_upload_textures(self.h, desc.ctypes.data, desc.size, blob.ctypes.data, blob.size, b.ctypes.data_as(C.POINTER(C.c_int32)), b.size))
+
+    def bind_material_maps(self, normal=None, roughness=None, normal_scale=1.0):
+        """Bind material maps on top of the bound texture set (glrtx_bind_material_maps; include/glrtx.h "Material maps"): per-material arrays of texture
+        indices (-1: none) and normal-map scales, or one array of host.MATERIAL_MAP_DTYPE records as `normal`.  A normal map goes on a diffuse or conductor
+        material, a roughness map on a conductor.  Both None unbinds.  upload_textures and upload_scene drop the maps."""
+        from .host import MATERIAL_MAP_DTYPE, material_maps
+        if normal is None and roughness is None:
+            self._ck(self.L.glrtx_bind_material_maps(self.h, None, 0))
+            return
+        if getattr(normal, "dtype", None) == MATERIAL_MAP_DTYPE:
+            rec = np.ascontiguousarray(normal).reshape(-1)
+        else:
+            rec = material_maps(np.size(normal if normal is not None else roughness), normal, roughness, normal_scale)
+        self._ck(self.L.glrtx_bind_material_maps(self.h, rec.ctypes.data, rec.size))
 
     def upload_environment(self, env_map, cfg=None):
         """Bind an environment (glrtx_upload_environment; include/glrtx.h "Environment"): env_map as host.pack_environment takes it -- (array (N, N, 3 or 4),

@@ -77,6 +77,9 @@ def lib():
         L.glrt_env_sample.argtypes = [vp, vp, C.c_size_t, vp, fp, C.c_size_t, fp]
         L.glrt_env_eval.argtypes = [vp, vp, C.c_size_t, vp, fp, C.c_size_t, fp]
         L.glrt_env_from_latlong.argtypes = [fp, C.c_int32, C.c_int32, C.c_int32, fp]
+        L.glrt_map_decode.argtypes = [fp, C.c_size_t, fp]
+        L.glrt_map_normal.argtypes = [fp, C.c_size_t, C.c_float, fp]
+        L.glrt_map_alpha.argtypes = [fp, C.c_size_t, fp]
         L.glrt_look_at.argtypes = [fp, fp, fp, fp]
         L.glrt_perspective.argtypes = [C.c_float, C.c_float, C.c_float, C.c_float, fp]
         L.glrt_mat4_mul.argtypes = [fp, fp, fp]
@@ -659,6 +662,51 @@ def texture_albedo(scene, textures, material_texture, hits):
     if rc != 0:
         raise RuntimeError(f"glrt_texture_albedo failed: {rc}")
     return out.reshape(h.shape[:-1] + (3,))
+
+
+# --------------------------------------------------------------------------- material maps (include/glrtx.h "Material maps")
+MAP_ALPHA_MIN = np.float32(1e-3)  # GLRT_MAP_ALPHA_MIN
+MAP_RECORD_FLOATS = 18  # GLRT_MAP_RECORD_FLOATS: {n, e1, e2, (s0, t0), (s1, t1), (s2, t2), m}
+MATERIAL_MAP_DTYPE = np.dtype([("normal", "<i4"), ("roughness", "<i4"), ("normal_scale", "<f4"), ("reserved", "<i4")])  # glrtx_material_map
+
+
+def material_maps(n_mat, normal=None, roughness=None, normal_scale=1.0):
+    """(n_mat,) MATERIAL_MAP_DTYPE records from per-material arrays (or scalars): texture indices of the bound set, -1 or None for no map."""
+    r = np.zeros(int(n_mat), MATERIAL_MAP_DTYPE)
+    r["normal"] = -1 if normal is None else np.asarray(normal, np.int32)
+    r["roughness"] = -1 if roughness is None else np.asarray(roughness, np.int32)
+    r["normal_scale"] = np.asarray(normal_scale, np.float32)
+    return r
+
+
+def map_records(n, e1, e2, st0, st1, st2, m):
+    """(k, MAP_RECORD_FLOATS) float32 records of glrt_map_normal / glrtx_debug_map_normal from arrays of shape (k, 3) and (k, 2), words moved as they are."""
+    parts = [np.ascontiguousarray(a, np.float32).reshape(-1, w) for a, w in ((n, 3), (e1, 3), (e2, 3), (st0, 2), (st1, 2), (st2, 2), (m, 3))]
+    return np.ascontiguousarray(np.concatenate([p.view(np.uint32) for p in parts], 1)).view(np.float32)
+
+
+def _map_call(name, src, width_in, width_out, *extra):
+    a = np.ascontiguousarray(src, np.float32).reshape(-1, width_in)
+    out = np.zeros((a.shape[0], width_out), np.float32)
+    rc = getattr(lib(), name)(_ptr(a, C.c_float), a.shape[0], *extra, _ptr(out, C.c_float))
+    if rc:
+        raise RuntimeError(f"{name} failed: {rc}")
+    return out
+
+
+def map_decode(rgb):
+    """glrt_map_decode: looked-up texels (k, 3) as tangent-space vectors, m = c * 2 + -1."""
+    return _map_call("glrt_map_decode", rgb, 3, 3)
+
+
+def map_normal(records, scale=1.0):
+    """glrt_map_normal: the CPU statement of the device's tangent-space normal rule; records as map_records makes them, returns n' (k, 3) float32."""
+    return _map_call("glrt_map_normal", records, MAP_RECORD_FLOATS, 3, C.c_float(scale))
+
+
+def map_alpha(rgb):
+    """glrt_map_alpha: (alpha.x, alpha.y) (k, 2) of roughness texels (k, 3): channels r and g, floored at MAP_ALPHA_MIN."""
+    return _map_call("glrt_map_alpha", rgb, 3, 2)
 
 
 REPROJECT_DEFAULTS = dict(max_history=32, depth_tolerance=0.02, normal_tolerance=0.9)

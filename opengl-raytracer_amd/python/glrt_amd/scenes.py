@@ -365,6 +365,61 @@ def config_textured_wall(n=6, width=64, height=48, max_depth=4, n_samples=2, alb
     return scene, make_params(c2w, s2c, width, height, max_depth, n_samples), info
 
 
+def config_mapped_wall(n=6, width=64, height=48, max_depth=4, n_samples=2, wall="conductor", alpha=None, per_cell=False, uv="cell", seed=1, bvh="sah",
+                       normal_map=None, roughness_map=None, lamp=10.0):
+    """config_textured_wall's scene with a CONDUCTOR (copper) or DIFFUSE wall material: the scene material maps are pinned on (include/glrtx.h "Material maps").
+      per_cell False  the wall has ONE material (conductor: alpha 0.2) and texture coordinates.  uv "cell": each cell's centre ((i + 0.5) / n, (j + 0.5) / n) at
+                      all three corners -- a roughness map is then constant over a cell, and a normal map finds det = 0 and keeps the normal; uv "corner": the
+                      wall's own parametrisation, s = x across, t = y up, in [0, 1] -- what a normal map needs; or an array (2 n n, 3, 2).
+      per_cell True   (conductor only) no coordinates, and one conductor material a cell with param2 = (alpha[j, i, 0], alpha[j, i, 1], 0): what a roughness map
+                      constant over each cell must render as.
+    The forms have the same triangles in the same order, so the same tree.  alpha: (n, n, 2) float32, random in [0.05, 0.5] from `seed` by default.
+    normal_map / roughness_map: the blocks export_json_obj writes for the wall's shape.  Returns (scene, params, wall) as config_textured_wall does, with
+    wall["alpha"] in place of the albedo."""
+    if wall not in ("conductor", "diffuse") or (per_cell and wall != "conductor"):
+        raise ValueError("config_mapped_wall: wall is 'conductor' or 'diffuse'; per_cell needs the conductor")
+    rng = np.random.default_rng(seed)
+    al = np.asarray(rng.uniform(0.05, 0.5, (n, n, 2)) if alpha is None else alpha, np.float32).reshape(n, n, 2)
+    b = SceneBuilder()
+    grey = b.add_material(diffuse((0.7, 0.7, 0.7)))
+    cu = b.add_material(conductor(COPPER["eta"], COPPER["kappa"], 0.2))
+    lamp_id = b.add_material(emitter((lamp, lamp, lamp)))
+    b.add_mesh(*quad((-10, 0, 10), (20, 0, 0), (0, 0, -20)), grey)
+    b.add_mesh(*icosphere(1, 1.0, (0.0, 1.0, 0.0)), cu)
+    b.add_mesh(*quad((-1, 5, -1), (2, 0, 0), (0, 0, 2)), lamp_id)
+    first_tri = sum(p.shape[0] for p in b._pos)
+    x0, y0, z0, w, h = -5.0, 0.0, -2.0, 10.0, 6.0
+
+    def cell_material(ax, ay):
+        m = conductor(COPPER["eta"], COPPER["kappa"], 0.2)
+        m["param2"] = (float(ax), float(ay), 0.0)
+        return m
+
+    one = diffuse((0.5, 0.5, 0.5)) if wall == "diffuse" else conductor(COPPER["eta"], COPPER["kappa"], 0.2)
+    for key, block in (("normal_map", normal_map), ("roughness_map", roughness_map)):
+        if block is not None:
+            one[key] = block
+    wall_id = len(b.materials) if per_cell else b.add_material(one)
+    pos, nrm, mid, st = [], [], [], []
+    for j in range(n):
+        for i in range(n):
+            p, q = quad((x0 + w * i / n, y0 + h * j / n, z0), (w / n, 0, 0), (0, h / n, 0))  # normal +z, towards the camera
+            pos.append(p); nrm.append(q)
+            mid += [b.add_material(cell_material(*al[j, i])) if per_cell else wall_id] * 2
+            if isinstance(uv, str) and uv == "corner":
+                c = np.array([[i, j], [i + 1, j], [i + 1, j + 1], [i, j + 1]], np.float32) / np.float32(n)
+                st.append(np.stack([c[[0, 1, 2]], c[[0, 2, 3]]]))  # quad(): triangles (a, b, c), (a, c, d)
+            else:
+                st.append(np.broadcast_to(np.array([(i + 0.5) / n, (j + 0.5) / n], np.float32), (2, 3, 2)))
+    coords = None if per_cell else (np.concatenate(st, 0) if isinstance(uv, str) else uv)
+    b.add_mesh(np.concatenate(pos, 0), np.concatenate(nrm, 0), np.asarray(mid, np.float32), uv=coords)
+    scene = b.build(bvh)
+    c2w, s2c = camera((0, 3, 9), (0, 1, 0), (0, 1, 0), 40.0, width, height)
+    info = dict(n=n, alpha=al, material=wall_id, tri=range(first_tri, first_tri + 2 * n * n), vert=range(3 * first_tri, 3 * (first_tri + 2 * n * n)), builder=b,
+                camera=((0, 3, 9), (0, 1, 0), (0, 1, 0), 40.0))
+    return scene, make_params(c2w, s2c, width, height, max_depth, n_samples), info
+
+
 # --------------------------------------------------------------------------- environment lighting (include/glrtx.h "Environment"; PARITY UNPINNED)
 ENV_QUAD_ALBEDO = (0.5, 0.25, 0.75)
 
@@ -549,6 +604,9 @@ def export_json_obj(builder: SceneBuilder, directory, width, height, origin, tar
                 sh["volume"] = {k: (v if isinstance(v, str) else [float(c) for c in v]) for k, v in m["volume"].items()}
         else:
             raise ValueError("export supports diffuse / conductor / emitter / media shapes")
+        for key in ("normal_map", "roughness_map"):  # (config_mapped_wall; host/scene.h: MapSpec)
+            if m.get(key) is not None:
+                sh[key] = dict(m[key]) if isinstance(m[key], dict) else m[key]
         shapes.append(sh)
     cam = {"type": "perspective", "fov": fov_deg, "nearClip": near, "farClip": far,
            "lookAt": {"origin": list(origin), "target": list(target), "up": list(up)}}
