@@ -1118,7 +1118,8 @@ int glrtx_debug_normals_burst(glrtx_ctx *ctx, int reps, float *ms_per_launch);
 /* ---- Textures: a diffuse material's albedo looked up in an image at the hit's texture coordinates (no reference counterpart -- the reference's Vertex carries
  * uv and its Material ends in texIds, and nothing reads either; off unless called: no other call's behaviour changes).  gfx950 has no image-sampling path: a
  * lookup is address arithmetic and up to four gathers (csrc/texture.hip.h).  Only the extension megakernel shades with textures: while a set is bound, launches
- * run on the persistent megakernel exactly as with analytic spheres uploaded (variant_last 1, GLRTX_FALLBACK_EXTENSIONS).  PINNED through the reference all the
+ * run on the persistent megakernel exactly as with analytic spheres uploaded (variant_last 1, GLRTX_FALLBACK_EXTENSIONS) -- by default: with
+ * glrtx_set_texture_wavefront (below) the wavefront kernel's T form shades them, bit for bit the same.  PINNED through the reference all the
  * same: a texture whose texels are constant over each triangle renders, bit for bit, the image of the same geometry with one diffuse material a triangle.
  *
  * Arithmetic.  Every operation is one correctly rounded fp32 operation in the order written, unfused; denormals are zeros of their sign into and out of every
@@ -1159,7 +1160,20 @@ int glrtx_debug_normals_burst(glrtx_ctx *ctx, int reps, float *ms_per_launch);
  *                     so `demodulate` keeps texture detail out of both denoisers' filters.  glrt_texture_albedo (include/glrt_host.h) states it on plane G.
  *   glrtx_debug_texture_lookup  tex_lookup on caller arrays on the current HIP device, no context: rgb_out[3i..] = lookup(which[i], st[2i], st[2i + 1]).
  *                     Refuses what glrtx_upload_textures refuses of a set, and a `which` out of range.  Errors through glrtx_last_error(NULL).
+ *   glrtx_set_texture_wavefront  1: launches with a set bound run on the wavefront kernel (variant 2) -- its T form, or its TM form while material maps are bound
+ *                     (below) -- instead of the persistent megakernel: variant_last reports 2, fallback_last 0, and the launch is not counted in
+ *                     fallback_launches.  Frames in flight, overlapped and fed launches and the fused present ring then work with the set bound, and so do
+ *                     glrtx_render_adaptive, glrtx_render_adaptive_moments, glrtx_render_moments and glrtx_render_cascades.  TAKEN when the set is all that
+ *                     needs the extension kernel: variant 2 selected, no GLRTX_EXT_* flag, no spheres, no environment, the tree not a vine (the list scan has
+ *                     no textured form), u_maxDepth <= 255 and u_nSamples < 2^20.  ANYTHING ELSE runs exactly as with the switch off -- the textured megakernel,
+ *                     variant_last 1, GLRTX_FALLBACK_EXTENSIONS and the depth / sample bits where they apply -- and the wavefront kernel's calls then refuse
+ *                     as above, the message naming the reason (the switch is off, spheres, an environment, ...).  glrtx_hit_histogram refuses while a set
+ *                     is bound either way.  EQUALS the megakernel's textured kernels bit for bit: images, sample counts, rays, rays_untraced and paths (the
+ *                     shade phase calls the same lookup and shading functions on the hit record the traverse phase left).  A forced GLRTX_PAIR_FETCH=2 is
+ *                     served as 0 (node_fetch_last says what ran).  Default 0; GLRTX_TEXTURE_WAVEFRONT=0/1 in the environment overrides it at every launch.
+ *                     NULL ctx: GLRTX_EINVAL.  Seals an open fed launch, as glrtx_upload_textures and glrtx_bind_material_maps do.
  * Groups: no call; a member is reached through glrtx_group_ctx(grp, i). */
+int glrtx_set_texture_wavefront(glrtx_ctx *ctx, int enable);
 #define GLRTX_TEX_MAX 4096
 #define GLRTX_TEX_MAX_DIM 16384
 enum glrtx_tex_format { GLRTX_TEX_RGBA32F = 0, GLRTX_TEX_RGBA8_UNORM = 1, GLRTX_TEX_RGBA8_SRGB = 2 };
@@ -1285,7 +1299,8 @@ int glrtx_debug_env_eval(const glrtx_texture *map, const void *texels, size_t te
  *                     count; an index outside -1 .. n_tex - 1; a normal map on a material that is neither diffuse nor conductor; a roughness map on a
  *                     material that is not a conductor; a map whose texture has format GLRTX_TEX_RGBA8_SRGB; a scale that is not finite; reserved non-zero.
  *   The wavefront kernel's calls keep refusing with "textures are bound".  glrtx_upload_textures' own refusals are unchanged, the conductor binding included:
- *                     that is why this is a second call.
+ *                     that is why this is a second call.  (With glrtx_set_texture_wavefront -- "Textures" -- launches with maps bound run on the wavefront
+ *                     kernel's TM form, bit for bit the MAPS kernels' images and ray counts, and those calls work.)
  *   Feature pass      with maps bound, plane N of glrtx_render_features carries n' of the primary hit, so the denoisers' normal edge-stop and the
  *                     reprojections' normal test see the detail the image shows.  Albedo, material id, distance and plane G are unchanged.
  *   glrtx_debug_map_normal  the rule on caller arrays on the current HIP device, no context: record i is GLRTX_MAP_RECORD_FLOATS floats {n, e1, e2, (s0, t0),

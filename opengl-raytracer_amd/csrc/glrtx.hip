@@ -122,6 +122,7 @@ struct glrtx_ctx {
     VolArgs vol{};
     bool have_volume = false;
     bool vol_wavefront = false;  // glrtx_set_volume_wavefront: volume launches on the wavefront kernel's V form (GLRTX_VOLUME_WAVEFRONT=0/1 overrides it per launch)
+    bool tex_wavefront = false;  // glrtx_set_texture_wavefront: textured launches on the wavefront kernel's T / TM forms (GLRTX_TEXTURE_WAVEFRONT=0/1 overrides it per launch)
     DevBuf wfState, wfQ;      // wavefront path state (kWfStatePlanes = 6 planes of float4 x ids) + per-workgroup queues (variant 2)
     DevBuf wfSeeds, wfPlanes;       // frames in flight: per-frame seeds, per-sample planes
     // Single-frame launches that overlap (launch_wgwf): pipe_slots (<= kPipeSlots) slots used in turn, each with its own stream, path state, queues, tile
@@ -1019,15 +1020,34 @@ TexSet tex_set(const glrtx_ctx *c) {
 bool vol_wavefront(const glrtx_ctx *c) {
     bool on = c->vol_wavefront;
     if (const char *v = std::getenv("GLRTX_VOLUME_WAVEFRONT")) on = std::atoi(v) != 0;
-    return on && c->ext_flags == GLRTX_EXT_VOLUME && c->have_volume && c->n_spheres == 0 && c->n_tex == 0 && !c->have_env;  // (textures and the environment are shaded by the megakernel only)
+    return on && c->ext_flags == GLRTX_EXT_VOLUME && c->have_volume && c->n_spheres == 0 && c->n_tex == 0 && !c->have_env;  // (beside the volume, textures and the environment are shaded by the megakernel only)
 }
 
 // Whether the wavefront variant's packed path state can represent this launch (meta = depth | sample << 8 | flags << 28; the V form: sample in bits 8-23).
 bool wgwf_can_hold(const glrtx_params *p, bool vol = false) { return p->max_depth <= kWfDepthMax && p->n_samples <= (vol ? kWfVolSampleMax : kWfSampleMax); }
 
-// Whether a launch of this context runs on the wavefront kernel (variant 2): no extensions, or the volume alone with the V form switched on.
+// Textured launches on the wavefront kernel (its T form, kWgwfTextured; TM, kWgwfMaps, while maps are bound): the switch is on (glrtx_set_texture_wavefront;
+// GLRTX_TEXTURE_WAVEFRONT=0/1, read at every launch, overrides it), a set is bound, and nothing else needs the extension megakernel: no extension flag, no
+// spheres, no environment; and the tree is not a vine (the list scan has no T form).  `why_not` (optional): the first of these that does not hold, for a refusal.
+bool tex_wavefront(const glrtx_ctx *c, const char **why_not = nullptr) {
+    bool on = c->tex_wavefront;
+    if (const char *v = std::getenv("GLRTX_TEXTURE_WAVEFRONT")) on = std::atoi(v) != 0;
+    const char *why = c->n_tex == 0 ? "no set is bound"
+                      : !on ? "the texture wavefront switch is off (glrtx_set_texture_wavefront)"
+                      : c->ext_flags != 0 ? "extensions or volume are on"
+                      : c->n_spheres > 0 ? "spheres are uploaded"
+                      : c->have_env ? "an environment is bound"
+                      : c->sc.n_vine > 0 ? "the tree is a vine (the list scan has no textured form)"
+                      : nullptr;
+    if (why_not) *why_not = why;
+    return why == nullptr;
+}
+
+// Whether a launch of this context runs on the wavefront kernel (variant 2): no extensions, or the volume alone with the V form switched on, or a texture set
+// alone with the T / TM forms switched on.
 bool wgwf_routes(const glrtx_ctx *c, const glrtx_params *p) {
-    if (c->variant != 2 || c->n_spheres > 0 || c->n_tex > 0 || c->have_env) return false;
+    if (c->variant != 2 || c->n_spheres > 0 || c->have_env) return false;
+    if (c->n_tex > 0) return tex_wavefront(c) && wgwf_can_hold(p);
     if (c->ext_flags == 0) return wgwf_can_hold(p);
     return vol_wavefront(c) && wgwf_can_hold(p, true);
 }
@@ -1303,7 +1323,7 @@ bool wgwf_compact(const glrtx_ctx *c, bool vine, int fetch) {
 // n_frames > 1 ("frames in flight"): the launch covers n_frames consecutive frames that differ only in u_seed (seeds_xy);
 // the per-sample planes are added to the accumulator in frame order afterwards (accumulate.hip.h), so the result is bit-identical to
 // n_frames separate launches.  launch_wgwf is the steps below, in order; what they work out about the launch is gathered here.
-using WgwfFn = void (*)(const KernelArgs, const WfArgs, unsigned *, float4 *, const int *, const unsigned *, const VolArgs);
+using WgwfFn = void (*)(const KernelArgs, const WfArgs, unsigned *, float4 *, const int *, const unsigned *, const VolArgs, const TexSet);
 struct WgwfLaunch {
     const glrtx_params *p;
     RenderReq req;
@@ -1314,7 +1334,7 @@ struct WgwfLaunch {
     size_t total, plane_f4, plane_bytes, frame_bytes;
     struct Form { bool busy, fed, piped; int fed_cap; } f;  // (wgwf_form)
     size_t ids;
-    struct Kernel { WgwfFn fn; const char *name; bool vol, vine, compact, adapt; int fetch, lds, per_cu; size_t wg_slots; } k;  // (wgwf_kernel)
+    struct Kernel { WgwfFn fn; const char *name; bool vol, tex, maps, vine, compact, adapt; int fetch, lds, per_cu; size_t wg_slots; } k;  // (wgwf_kernel)
     glrtx_ctx::PipeSlot *slot;  // (wgwf_pipe_slot; null: plain)
     int pipe_busy, block_paths, grid;
     bool ctx_state;  // (wgwf_args) the buffers the kernel runs on, its stream, its arguments
@@ -1363,28 +1383,39 @@ WgwfLaunch::Form wgwf_form(glrtx_ctx *c, const WgwfLaunch &L) {
 // The compact node array (pack_compact) has its own four: wgwf_compact.
 // The V form (kWgwfVolume: glrtx_set_volume_wavefront; routed here only with the volume alone, wgwf_routes) has one fetch form only: one record per lane on
 // DevScene::nodes, as in the megakernels (no list scan, no pair fetch, no compact layout).
-// Each of the six has its ADAPT twin (kWgwfAdaptive: glrtx_render_adaptive, glrtx_render_adaptive_moments): 24 instantiations, one table.
-enum WgwfTrav { kTravVine, kTravFetch0, kTravFetch1, kTravFetch2, kTravCompact, kTravVolume, kTravForms };
+// The T and TM forms (kWgwfTextured, kWgwfMaps: glrtx_set_texture_wavefront; routed here only with a texture set alone, wgwf_routes) exist for the fetch forms the
+// host picks for trees by default -- one record per lane, pair-cooperative, the compact array --: a forced GLRTX_PAIR_FETCH=2 is served as 0, a vine never gets here.
+// Each of the twelve has its ADAPT twin (kWgwfAdaptive: glrtx_render_adaptive, glrtx_render_adaptive_moments): 48 instantiations, one table.
+enum WgwfTrav { kTravVine, kTravFetch0, kTravFetch1, kTravFetch2, kTravCompact, kTravVolume, kTravTex0, kTravTex1, kTravTexCompact, kTravMaps0, kTravMaps1, kTravMapsCompact,
+                kTravForms };
 #define GLRTX_WGWF_ROW(VINE, FLAGS) {{pt_render_wgwf<false, VINE, FLAGS>, pt_render_wgwf<true, VINE, FLAGS>}, \
                                      {pt_render_wgwf<false, VINE, (FLAGS) | kWgwfAdaptive>, pt_render_wgwf<true, VINE, (FLAGS) | kWgwfAdaptive>}}
 constexpr WgwfFn kWgwfKernels[kTravForms][2][2] = {  // [traversal][adaptive][count_rays]
-    GLRTX_WGWF_ROW(true, 0), GLRTX_WGWF_ROW(false, 0), GLRTX_WGWF_ROW(false, 1), GLRTX_WGWF_ROW(false, 2), GLRTX_WGWF_ROW(false, kWgwfCompact), GLRTX_WGWF_ROW(false, kWgwfVolume)};
+    GLRTX_WGWF_ROW(true, 0), GLRTX_WGWF_ROW(false, 0), GLRTX_WGWF_ROW(false, 1), GLRTX_WGWF_ROW(false, 2), GLRTX_WGWF_ROW(false, kWgwfCompact), GLRTX_WGWF_ROW(false, kWgwfVolume),
+    GLRTX_WGWF_ROW(false, kWgwfTextured), GLRTX_WGWF_ROW(false, kWgwfTextured | 1), GLRTX_WGWF_ROW(false, kWgwfTextured | kWgwfCompact),
+    GLRTX_WGWF_ROW(false, kWgwfTextured | kWgwfMaps), GLRTX_WGWF_ROW(false, kWgwfTextured | kWgwfMaps | 1), GLRTX_WGWF_ROW(false, kWgwfTextured | kWgwfMaps | kWgwfCompact)};
 #undef GLRTX_WGWF_ROW
-constexpr const char *kWgwfNames[3][2] = {  // [list scan | tree | volume][adaptive] (error reports)
-    {"pt_render_wgwf (list scan)", "pt_render_wgwf (adaptive, list scan)"}, {"pt_render_wgwf", "pt_render_wgwf (adaptive)"}, {"pt_render_wgwf (volume)", "pt_render_wgwf (volume, adaptive)"}};
+constexpr const char *kWgwfNames[5][2] = {  // [list scan | tree | volume | textures | textures and maps][adaptive] (error reports)
+    {"pt_render_wgwf (list scan)", "pt_render_wgwf (adaptive, list scan)"}, {"pt_render_wgwf", "pt_render_wgwf (adaptive)"}, {"pt_render_wgwf (volume)", "pt_render_wgwf (volume, adaptive)"},
+    {"pt_render_wgwf (textures)", "pt_render_wgwf (textures, adaptive)"}, {"pt_render_wgwf (textures, maps)", "pt_render_wgwf (textures, maps, adaptive)"}};
 
 int wgwf_kernel(glrtx_ctx *c, WgwfLaunch &L) {
     WgwfLaunch::Kernel &k = L.k;
     k.vol = c->ext_flags != 0;
+    k.tex = c->n_tex > 0;  // (render_one sends a bound set here only when tex_wavefront() holds: no extension flag, no vine)
+    k.maps = k.tex && c->have_maps;
     k.adapt = L.req.adaptive();
     k.vine = c->sc.n_vine > 0 && !k.vol;
     k.fetch = k.vol ? 0 : wgwf_fetch(c, k.vine);
+    if (k.tex && k.fetch == 2) k.fetch = 0;  // (the alternating fetch has no T form: served as one record per lane, and reported so)
     c->st.node_fetch_last = k.fetch;
     k.compact = !k.vol && wgwf_compact(c, k.vine, k.fetch);
     c->st.node_layout_last = k.compact ? 1 : 0;
-    const int trav = k.vol ? kTravVolume : k.compact ? kTravCompact : k.vine ? kTravVine : kTravFetch0 + k.fetch;
+    if (k.tex && (k.vol || k.vine)) return fail(c, GLRTX_EDEVICE, "internal: a texture set routed to the wavefront kernel beside %s", k.vol ? "the volume" : "a vine tree");
+    const int trav = k.tex ? (k.maps ? kTravMaps0 : kTravTex0) + (k.compact ? 2 : k.fetch)
+                           : k.vol ? kTravVolume : k.compact ? kTravCompact : k.vine ? kTravVine : kTravFetch0 + k.fetch;
     k.fn = kWgwfKernels[trav][k.adapt][L.req.count_rays(c)];
-    k.name = kWgwfNames[k.vol ? 2 : k.vine ? 0 : 1][k.adapt];
+    k.name = kWgwfNames[k.maps ? 4 : k.tex ? 3 : k.vol ? 2 : k.vine ? 0 : 1][k.adapt];
     // (north_star's "primitives staged into LDS": materials, camera block, root box and the per-lane stacks are; the top tree levels were built, measured worth
     // nothing -- profiles/r02_lds_top.json -- and removed.)
     k.lds = wgwf_lds_base(c) + (k.compact ? c->sc.n_crank * (int)sizeof(uint2) : 0);  // | rank table
@@ -1603,6 +1634,8 @@ int wgwf_check(glrtx_ctx *c, const WgwfLaunch &L) {
               p->max_depth <= kWfDepthMax && p->n_samples <= kWfSampleMax && L.workPtr != nullptr;
     if (L.k.vol) ok = ok && p->n_samples <= kWfVolSampleMax && c->ext_flags == GLRTX_EXT_VOLUME && c->have_volume && c->vol.density != nullptr &&
                       c->vol.temperature != nullptr && c->n_spheres == 0 && !L.k.vine && L.k.fetch == 0 && !L.k.compact;
+    if (L.k.tex) ok = ok && c->n_tex > 0 && c->ext_flags == 0 && c->n_spheres == 0 && !c->have_env && !L.k.vine && !L.k.vol && L.k.fetch != 2 && c->texDesc.p != nullptr &&
+                      c->texTexels.p != nullptr && c->texSt.p != nullptr && c->texBind.p != nullptr && (!L.k.maps || c->texMaps.p != nullptr) && L.a.hit_hist == nullptr;
     if (!fed && n_frames > 1) ok = ok && c->wfSeeds.bytes >= (size_t)n_frames * sizeof(float2);
     if (w.planes) ok = ok && L.planeBuf->bytes >= (size_t)std::max(L.n_planes, 1) * L.plane_f4 * sizeof(float4);
     if (L.k.adapt) ok = ok && !fed && !slot && w.planes && c->ad_selected && c->ad_tiles == (int)(total >> 6) && c->adList.bytes >= (total >> 6) * sizeof(int) &&
@@ -1649,8 +1682,9 @@ int wgwf_issue(glrtx_ctx *c, const WgwfLaunch &L) {
     c->last_kernel = L.k.name;
     c->counters_stale = c->counters_stale || L.req.count_rays(c);
     const VolArgs va = vol ? c->vol : VolArgs{};
+    const TexSet ts = L.k.tex ? tex_set(c) : TexSet{};
     hipLaunchKernelGGL(L.k.fn, dim3(L.grid), dim3(kBlockThreads), L.k.lds, rstream, L.a, w, L.workPtr, (float4 *)L.queueBuf->p, adapt ? (const int *)c->adList.p : nullptr,
-                       adapt ? (const unsigned *)c->adCount.p : nullptr, va);
+                       adapt ? (const unsigned *)c->adCount.p : nullptr, va, ts);
     HIP_TRY(c, hipGetLastError());
 #ifdef GLRTX_RAY_LOG
     g_dbg_last = {L.a, w, L.k.lds, L.grid, (float4 *)L.queueBuf->p, L.k.fetch};
@@ -1879,6 +1913,16 @@ int reproject_motion_pass(glrtx_ctx *c, hipStream_t stream, const reproject::Com
 }
 
 
+// What the wavefront-only calls (adaptive, moments, cascades) say while a texture set is bound and the launch would NOT run on the wavefront kernel's T / TM forms
+// (wgwf_routes): "textures are bound", and the reason -- the switch, what else is on, the tree, the variant, the path state's range.  GLRTX_OK: no set, or it routes.
+int tex_refusal(glrtx_ctx *c, const glrtx_params *p, const char *fn, const char *tail) {
+    if (c->n_tex == 0) return GLRTX_OK;
+    const char *why = nullptr;
+    if (tex_wavefront(c, &why)) why = c->variant != 2 ? "the context's variant is not 2" : !wgwf_can_hold(p) ? "max_depth / n_samples beyond the wavefront kernel's path state" : nullptr;
+    if (!why) return GLRTX_OK;
+    return fail(c, GLRTX_EINVAL, "%s: textures are bound and the wavefront kernel does not shade them here: %s (%s)", fn, why, tail);
+}
+
 // ---- adaptive sampling (glrtx_render_adaptive)
 // Everything glrtx_render_adaptive refuses, checked before anything changes.  The megakernels have no tile list and the present ring no adaptive form.
 int adapt_check(glrtx_ctx *c, const glrtx_params *p, const float *seeds_xy, int n_frames, const glrtx_adaptive *cfg) {
@@ -1890,10 +1934,10 @@ int adapt_check(glrtx_ctx *c, const glrtx_params *p, const float *seeds_xy, int 
     if (!c->accum || c->width < 1) return fail(c, GLRTX_EINVAL, "%s: no accumulator (call glrtx_resize)", fn);
     if (p->n_samples < 0 || p->max_depth < 0) return fail(c, GLRTX_EINVAL, "%s: negative n_samples/max_depth", fn);
     if (c->pres.ring > 0) return fail(c, GLRTX_EINVAL, "%s: presentation is enabled (the present ring has no adaptive form)", fn);
+    if (int rc = tex_refusal(c, p, fn, "only the wavefront kernel has a tile list")) return rc;
     const bool vol = vol_wavefront(c);  // the volume alone, with the V form switched on: the wavefront kernel runs it
     if (c->ext_flags != 0 && !vol) return fail(c, GLRTX_EINVAL, "%s: extensions or volume are on (only the wavefront kernel has a tile list)", fn);
     if (c->n_spheres > 0) return fail(c, GLRTX_EINVAL, "%s: spheres are uploaded (only the wavefront kernel has a tile list)", fn);
-    if (c->n_tex > 0) return fail(c, GLRTX_EINVAL, "%s: textures are bound (only the wavefront kernel has a tile list)", fn);
     if (c->have_env) return fail(c, GLRTX_EINVAL, "%s: an environment is bound (only the wavefront kernel has a tile list)", fn);
     if (c->variant != 2) return fail(c, GLRTX_EINVAL, "%s: variant %d (only the wavefront kernel, variant 2, has a tile list)", fn, c->variant);
     if (!wgwf_can_hold(p, vol)) return fail(c, GLRTX_EINVAL, "%s: max_depth %d / n_samples %d beyond the wavefront kernel's path state", fn, p->max_depth, p->n_samples);
@@ -1937,9 +1981,9 @@ int side_plane_check(glrtx_ctx *c, const glrtx_params *p, const float *seeds_xy,
     if (!c->accum || c->width < 1) return fail(c, GLRTX_EINVAL, "%s: no accumulator (call glrtx_resize)", fn);
     if (p->n_samples < 0 || p->max_depth < 0) return fail(c, GLRTX_EINVAL, "%s: negative n_samples/max_depth", fn);
     if (c->pres.ring > 0) return fail(c, GLRTX_EINVAL, "%s: presentation is enabled (the present ring's passes fold neither moments nor cascades)", fn);
+    if (int rc = tex_refusal(c, p, fn, "the megakernel that shades them writes no sample planes")) return rc;
     if (c->ext_flags != 0) return fail(c, GLRTX_EINVAL, "%s: extensions or volume are on", fn);
     if (c->n_spheres > 0) return fail(c, GLRTX_EINVAL, "%s: spheres are uploaded", fn);
-    if (c->n_tex > 0) return fail(c, GLRTX_EINVAL, "%s: textures are bound (the megakernel that shades them writes no sample planes)", fn);
     if (c->have_env) return fail(c, GLRTX_EINVAL, "%s: an environment is bound (the megakernel that shades it writes no sample planes)", fn);
     if (c->variant != 2) return fail(c, GLRTX_EINVAL, "%s: variant %d (only the wavefront kernel, variant 2, writes sample planes)", fn, c->variant);
     if (!wgwf_can_hold(p, false)) return fail(c, GLRTX_EINVAL, "%s: max_depth %d / n_samples %d beyond the wavefront kernel's path state", fn, p->max_depth, p->n_samples);
@@ -3704,6 +3748,13 @@ int glrtx_set_volume_wavefront(glrtx_ctx *c, int enable) {
     return GLRTX_OK;
 }
 
+int glrtx_set_texture_wavefront(glrtx_ctx *c, int enable) {
+    if (!c) return GLRTX_EINVAL;
+    seal_feed(c);  // (nothing is appended to an open launch across this call: glrtx_ctx::OpenFeed)
+    c->tex_wavefront = enable != 0;  // read by the next launch (render_one: tex_wavefront)
+    return GLRTX_OK;
+}
+
 int glrtx_count_rays(glrtx_ctx *c, int enable) {
     if (!c) return GLRTX_EINVAL;
     seal_feed(c);  // (nothing is appended to an open launch across this call: glrtx_ctx::OpenFeed)
@@ -4746,7 +4797,10 @@ static int render_one(glrtx_ctx *c, const glrtx_params *p, const RenderReq &req)
     // The volume alone goes to the wavefront kernel's V form when that is switched on (glrtx_set_volume_wavefront), within its narrower sample range (kWfVolSampleMax).
     const bool tex = c->n_tex > 0;  // a bound texture set: the extension megakernel's textured instantiations (pt_render_persistent_tex)
     const bool envb = c->have_env;  // a bound environment: the extension megakernel's environment instantiations (pt_render_persistent_env)
-    const bool ext = c->n_spheres > 0 || c->ext_flags != 0 || tex || envb;
+    // A texture set alone (material maps included) goes to the wavefront kernel's T / TM forms when those are switched on (glrtx_set_texture_wavefront): such a
+    // launch needs no extension kernel and is no fallback.
+    const bool tex_wf = tex && wavefront;  // (wgwf_routes, above; anything else runs as it did: the textured megakernel, GLRTX_FALLBACK_EXTENSIONS)
+    const bool ext = c->n_spheres > 0 || c->ext_flags != 0 || (tex && !tex_wf) || envb;
     const bool vol_wf = vol_wavefront(c);
     const int variant = ((ext && !vol_wf) || (vol_wf && c->variant != 2) || (c->variant == 2 && !wgwf_can_hold(p, vol_wf))) ? 1 : c->variant;
     c->st.variant_last = variant;

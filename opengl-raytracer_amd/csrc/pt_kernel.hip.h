@@ -608,6 +608,11 @@ constexpr int kWgwfCompact = 8;
 // kWgwfVolume: the V form of pt_render_wgwf -- the volume branch (bounce_volume) as a state machine of the shade phase, one trial ray per trip (wf_vol_trial).
 // Only with the one-record-per-lane fetch on DevScene::nodes (FETCH 0, optionally | kWgwfAdaptive); masked out wherever FETCH selects the node fetch.
 constexpr int kWgwfVolume = 16;
+// kWgwfTextured: the T form of pt_render_wgwf -- the bound texture set's albedo lookups in the shade phase (wf_shade_textured: what bounce_ext<false, true> does
+// between its traversal and its shadow ray).  kWgwfMaps (implies kWgwfTextured): the TM form, normal and roughness maps as well.  With FETCH 0, FETCH 1 or
+// kWgwfCompact, optionally | kWgwfAdaptive; masked out wherever FETCH selects the node fetch -- the traverse phase is the plain kernel's.
+constexpr int kWgwfTextured = 32;
+constexpr int kWgwfMaps = 64;
 template <int FETCH>
 DEV void trav_steps_asm(const DevScene &sc, int *stack, Trav &T, unsigned rk GLRTX_TS_PARAM) {
     unsigned long long s_entry, s_act, s_leaf, s_bl, s_br, s_pop, s_tmp;
@@ -2320,9 +2325,56 @@ DEV int wf_vol_trial(const KernelArgs &a, const WfArgs &w, unsigned sidx, Rng &r
 // st2 / st3 = planes 2 / 3, st4 = plane 4 when has4.
 // VOL (the V form, kWgwfVolume): a media surface hit from the front queues trial 1 instead of being shaded, a trial's hit runs
 // wf_vol_trial, and a surface met after a volume is shaded with passedVolume set (meta bits 24-27, kWfVolShift).
-template <bool VOL = false>
+// TEX / MAPS (the T and TM forms, kWgwfTextured / kWgwfMaps): the hit is shaded by wf_shade_textured instead of shade_hit; nothing else differs.
+DEV const TexSet *wgwf_tex();  // WgwfKernArgs::tex of the running pt_render_wgwf launch (defined below)
+// The T / TM forms' shading of one hit: what bounce_ext<false, true, false, MAPS> does between its traversal and its shadow ray -- surf_tri, the material's binding,
+// the coordinates at the hit, the lookups, shade_core<true, true, false, MAPS> with no extension flag -- on the hit record the traverse phase left.  The same
+// functions, so the same operations in the same order.  The set is read through wgwf_tex(), a pointer into the kernarg segment, where it is used (see wgwf_vol).
+template <bool MAPS>
+DEV void wf_shade_textured(const KernelArgs &a, const float4 *lds_mats, Rng &rng, Path &P, const Hit &h, Shade &sh) {
+    Surf S;
+    S.nx = S.ny = S.nz = 0.f; S.mtrl = 0;
+    bool textured = false, rough = false;
+    float3 alb = make_float3(0.f, 0.f, 0.f);
+    float2 al = make_float2(0.f, 0.f);
+    if (h.tri >= 0) {
+        S = surf_tri(a.sc, h);
+        const TexSet &ts = *wgwf_tex();
+        const int k = ts.mat_tex[S.mtrl];
+        int kn = -1, kr = -1;
+        float scale = 0.f;
+        if constexpr (MAPS) {
+            const MapRec mr = ts.maps[S.mtrl];
+            kn = mr.normal; kr = mr.roughness; scale = mr.scale;
+        }
+        if (k >= 0 || kn >= 0 || kr >= 0) {
+            const float2 st = tex_hit_st(ts, h.tri, h.u, h.v);  // one set of coordinates for the albedo and the maps (bounce_ext forms the same words twice)
+            if (k >= 0) {
+                alb = tex_lookup(ts, k, st.x, st.y);
+                textured = true;
+            }
+            if constexpr (MAPS) {
+                if (kn >= 0) {
+                    const float3 n = map_hit_normal(ts, a.sc.forks, kn, scale, h.tri, st, make_float3(S.nx, S.ny, S.nz));
+                    S.nx = n.x; S.ny = n.y; S.nz = n.z;
+                }
+                if (kr >= 0) {
+                    al = map_alpha(tex_lookup(ts, kr, st.x, st.y));
+                    rough = true;
+                }
+            }
+        }
+    }
+    P.spec = false;  // (shade_core<true> reads it; nothing sets it without an extension flag)
+    if constexpr (MAPS) shade_core<true, true, false, true>(a, lds_mats, rng, P, h.t, h.tri >= 0, S, 0, sh, textured, alb.x, alb.y, alb.z, nullptr, rough, al.x, al.y);
+    else shade_core<true, true>(a, lds_mats, rng, P, h.t, h.tri >= 0, S, 0, sh, textured, alb.x, alb.y, alb.z);
+}
+
+template <bool VOL = false, bool TEX = false, bool MAPS = false>
 DEV void wf_shade_path(const KernelArgs &a, const WfArgs &w, const float4 *lds_mats, const float *cam, unsigned &id, unsigned sidx, bool light_accepted, bool &push_ext,
                        bool &push_sh, bool &requeue, float4 &ray_o, float4 &ray_d, float4 &ray_sd, float4 &st2, float4 &st3, float4 &st4, bool &has4, unsigned long long &rays) {
+    static_assert(!(VOL && TEX), "the volume is not shaded beside textures on the wavefront kernel");
+    static_assert(!MAPS || TEX, "material maps are looked up in the bound texture set");
     const float4 s0 = ld_stream(w.A(0, sidx)), s1 = ld_stream(w.A(1, sidx)), s2 = ld_stream(w.A(2, sidx)), s3 = ld_stream(w.A(3, sidx));
     // the hit record is fetched with the state, not behind the meta word the state delivers: one round trip less per round of the shade loop
     // (-0.9 % per frame, profiles/r03_ab_shade_phase.txt; unused when the path has ended).  Plain load and store for the hit records:
@@ -2415,6 +2467,8 @@ DEV void wf_shade_path(const KernelArgs &a, const WfArgs &w, const float4 *lds_m
             } else {
                 shade_hit(a, lds_mats, rng, P, h, sh);
             }
+        } else if constexpr (TEX) {
+            wf_shade_textured<MAPS>(a, lds_mats, rng, P, h, sh);
         } else {
             shade_hit(a, lds_mats, rng, P, h, sh);
         }
@@ -2745,7 +2799,7 @@ DEV void wg_traverse_phase(const KernelArgs &a, const WfArgs &w, const float4 *r
 // lane that finished the path's shadow ray; the shadow ray pushed here carries the position its path will have in pq_next.
 // Path state: the path at queue position i is read at state index cur_base + i and -- if it goes on -- written at next_base + (its position in pq_next); the next
 // ray's record carries that index (even ray id: where the traversal lane stores the hit), and a ray parked in a traversal lane finds it behind the mark it left.
-template <bool VOL = false>
+template <bool VOL = false, bool TEX = false, bool MAPS = false>
 DEV void wg_shade_phase(const KernelArgs &a, const WfArgs &w, const float4 *lds_mats, const float *cam, const unsigned *light_bits, int n_paths,
                         float4 *rq_next, unsigned *n_rays_next, unsigned *n_paths_next, unsigned cur_base, unsigned next_base, unsigned long long &rays,
                         unsigned *moved) {
@@ -2758,7 +2812,7 @@ DEV void wg_shade_phase(const KernelArgs &a, const WfArgs &w, const float4 *lds_
         float4 ro = make_float4(0.f, 0.f, 0.f, 0.f), rd = ro, rsd = ro, st2 = ro, st3 = ro, st4 = ro;
         const bool light_accepted = i < n_paths && ((light_bits[i >> 5] >> (i & 31)) & 1u) != 0u;
         if (i < n_paths)
-            wf_shade_path<VOL>(a, w, lds_mats, cam, id, cur_base + (unsigned)i, light_accepted, push_ext, push_sh, requeue, ro, rd, rsd, st2, st3, st4, has4, rays);
+            wf_shade_path<VOL, TEX, MAPS>(a, w, lds_mats, cam, id, cur_base + (unsigned)i, light_accepted, push_ext, push_sh, requeue, ro, rd, rsd, st2, st3, st4, has4, rays);
         const unsigned long long me = __ballot(push_ext), ms = __ballot(push_sh), mq = __ballot(requeue), mp = me | ms | mq;
         const unsigned long long mv = __ballot(id != WF_INVALID);
         unsigned br = 0, bp = 0;
@@ -2822,6 +2876,9 @@ struct WgwfKernArgs {
     // the V form (kWgwfVolume): the launch's volume (glrtx_upload_volume).  A trailing kernel argument like the two above (zeros in every other launch), read only
     // under `if constexpr` -- not a __device__ global: two contexts in one process (a group's members on one device) would share that.
     VolArgs vol;
+    // the T / TM forms (kWgwfTextured / kWgwfMaps): the launch's texture set (glrtx_upload_textures, glrtx_bind_material_maps).  Trailing, zeros in every other
+    // launch, read only under `if constexpr`, like the volume.
+    TexSet tex;
 };
 DEV const WgwfKernArgs *wgwf_kernargs() {
     auto p = __builtin_amdgcn_kernarg_segment_ptr();  // constant address space
@@ -2831,6 +2888,7 @@ DEV const WgwfKernArgs *wgwf_kernargs() {
 
 DEV int wgwf_suspend_max() { return wgwf_kernargs()->w.suspend_max; }
 DEV const VolArgs *wgwf_vol() { return &wgwf_kernargs()->vol; }
+DEV const TexSet *wgwf_tex() { return &wgwf_kernargs()->tex; }
 
 // Top-up of a FED launch (FeedHost / FeedDev), run by the workgroup's first wave in place of thread 0's part of pt_render_wgwf's top-up: the tiles known so far are
 // frames_known x tiles_per_frame; when few are left the wave looks at the host's word, copies the seeds and plane chunks of newly published frames into the device
@@ -2954,13 +3012,17 @@ DEV void wg_feed_topup(int kWgPaths, unsigned *ctl, int cur, unsigned *work_coun
 // tile-order pixel), so everything downstream -- wf_pixel, wf_seed, wf_add_sample, WfArgs::split -- is the same code.  The adaptive list and count are trailing
 // kernel arguments (null in every other launch: behind wg_queues no offset of an existing argument moves), read through wgwf_kernargs.
 // kWgwfVolume likewise selects the V form (wf_shade_path<true>), alone or with kWgwfAdaptive.
+// kWgwfTextured / kWgwfMaps select the T / TM form (wf_shade_path<false, true, MAPS>) on top of FETCH 0, FETCH 1 or kWgwfCompact, with or without kWgwfAdaptive.
 constexpr int kWgwfAdaptive = 4;
 template <bool COUNT_RAYS, bool VINE, int FETCH = 0>
 __global__ __launch_bounds__(kBlockThreads, GLRTX_WGWF_WAVES) void pt_render_wgwf(const KernelArgs a, const WfArgs w, unsigned *work_counter, float4 *wg_queues,
-                                                                                  const int * /*adapt_list*/, const unsigned * /*adapt_count*/, const VolArgs /*vol*/) {
+                                                                                  const int * /*adapt_list*/, const unsigned * /*adapt_count*/, const VolArgs /*vol*/,
+                                                                                  const TexSet /*tex*/) {
     constexpr bool ADAPT = (FETCH & kWgwfAdaptive) != 0;
     constexpr bool VOL = (FETCH & kWgwfVolume) != 0;
-    constexpr int NODE_FETCH = FETCH & ~(kWgwfAdaptive | kWgwfVolume);  // what selects the node fetch
+    constexpr bool MAPS = (FETCH & kWgwfMaps) != 0, TEX = MAPS || (FETCH & kWgwfTextured) != 0;
+    constexpr int NODE_FETCH = FETCH & ~(kWgwfAdaptive | kWgwfVolume | kWgwfTextured | kWgwfMaps);  // what selects the node fetch
+    static_assert(!TEX || (!VINE && !VOL && (NODE_FETCH == 0 || NODE_FETCH == 1 || NODE_FETCH == kWgwfCompact)), "the T / TM forms: trees, fetch 0, 1 or the compact array");
     static_assert(!VOL || (!VINE && NODE_FETCH == 0), "the V form has the one-record-per-lane fetch on DevScene::nodes only");
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     // LDS: materials | stack | ctl[16].  The workgroup's ray/path queues live in its private slice of a
@@ -2986,7 +3048,7 @@ __global__ __launch_bounds__(kBlockThreads, GLRTX_WGWF_WAVES) void pt_render_wgw
     float4 *rayQ = wg_queues + (size_t)blockIdx.x * kWgQueueF4;
     if (a.sc.mats_in_lds) stage_mats(a, lds_mats);
     stage_lights(a, lds_mats);
-    if (FETCH & kWgwfCompact) {  // the compact layout's rank table, last in LDS (launch_wgwf sizes it)
+    if (NODE_FETCH & kWgwfCompact) {  // the compact layout's rank table, last in LDS (launch_wgwf sizes it)
         uint2 *lds_ranks = reinterpret_cast<uint2 *>(light_bits + kWgPathsMax / 32);
         for (int i = threadIdx.x; i < a.sc.n_crank; i += kBlockThreads) lds_ranks[i] = a.sc.cranks[i];
     }
@@ -3107,7 +3169,7 @@ __global__ __launch_bounds__(kBlockThreads, GLRTX_WGWF_WAVES) void pt_render_wgw
 
         // ---- shade phase: the live paths; appends go to the other queue pair
         const WgwfKernArgs *ks = wgwf_kernargs();
-        wg_shade_phase<VOL>(ks->a, ks->w, lds_mats, lds_cam, light_bits, n_paths, rayQ + 2 * ((size_t)(cur ^ 1) * 2 * kWgPaths),
+        wg_shade_phase<VOL, TEX, MAPS>(ks->a, ks->w, lds_mats, lds_cam, light_bits, n_paths, rayQ + 2 * ((size_t)(cur ^ 1) * 2 * kWgPaths),
                             &ctl[2 + (cur ^ 1)], &ctl[4 + (cur ^ 1)], ks->w.set_base(cur, (int)blockIdx.x), ks->w.set_base(cur ^ 1, (int)blockIdx.x), rays, &ctl[10]);
         PH_STAMP(ps1);
         __syncthreads();  // everyone has read n_rays/n_paths of `cur` and finished appending

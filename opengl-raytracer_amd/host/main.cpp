@@ -15,7 +15,7 @@
 using namespace glrt;
 
 static void usage(const char *exe) {
-    std::printf("usage: %s -i scene.json [-s N] [--max-depth D] [--spp N] [--frames F] [--frames-in-flight B] [--bvh sah|sah-reinsert|sah-gpu|lbvh|sah-levels-cpu|lbvh-cpu|reference] [--order-by-hits] [--out file.png] [--save-every-frame] [--device G | --gpus N | --devices a,b,..] [--extensions] [--whitted] [--enable-volume] [--volume-wavefront] [--adaptive THRESHOLD | --adaptive-variance THRESHOLD [--min-spp N]] [--denoise | --denoise-variance [--denoise-iters N]] [--tonemap clamp|reinhard|aces [--exposure X] [--auto-exposure]] [--bloom [--bloom-threshold T] [--bloom-strength S] [--bloom-levels N]] [--reweight [--reweight-kappa K] [--reweight-start S]] [--animate FILE [--carry-history]]\n"
+    std::printf("usage: %s -i scene.json [-s N] [--max-depth D] [--spp N] [--frames F] [--frames-in-flight B] [--bvh sah|sah-reinsert|sah-gpu|lbvh|sah-levels-cpu|lbvh-cpu|reference] [--order-by-hits] [--out file.png] [--save-every-frame] [--device G | --gpus N | --devices a,b,..] [--extensions] [--texture-wavefront] [--whitted] [--enable-volume] [--volume-wavefront] [--adaptive THRESHOLD | --adaptive-variance THRESHOLD [--min-spp N]] [--denoise | --denoise-variance [--denoise-iters N]] [--tonemap clamp|reinhard|aces [--exposure X] [--auto-exposure]] [--bloom [--bloom-threshold T] [--bloom-strength S] [--bloom-levels N]] [--reweight [--reweight-kappa K] [--reweight-start S]] [--animate FILE [--carry-history]]\n"
                 "  -i, --input             scene description (JSON; schema: SURVEY.md Appendix C)            [required]\n"
                 "  -s, --sample-per-cycle  accepted for compatibility; like the reference (main.cpp:13) it is not read\n"
                 "      --max-depth D       u_maxDepth (default 16, the reference shader's default)\n"
@@ -40,6 +40,9 @@ static void usage(const char *exe) {
                 "                          their VOL files are read (a missing one is an error only with this flag)\n"
                 "      --volume-wavefront  with --enable-volume: render the media on the wavefront kernel (frames in flight, fed launches; the same image as\n"
                 "                          the persistent megakernel, the default).  --enable-volume --adaptive T turns it on by itself\n"
+                "      --texture-wavefront  with --extensions: render textured shapes (material maps included) on the wavefront kernel (frames in flight, fed\n"
+                "                          launches; the same image as the textured megakernel, the default); scenes with spheres, dielectrics or an environment\n"
+                "                          render as without it\n"
                 "      --adaptive T        adaptive sampling: bursts of --frames-in-flight frames on the 8x8 tiles whose error is above T only, until no tile is\n"
                 "                          active or --frames frames have been issued; an \"Adaptive:\" line per burst (not with --save-every-frame)\n"
                 "      --adaptive-variance T  the same bursts with the tiles selected by the variance of their pixels' mean luminance (the moments plane that\n"
@@ -86,7 +89,7 @@ int main(int argc, char **argv) {
     std::string input, out = "output.png";
     int depth = 16, spp = 1, frames = 16, device = -1, in_flight = 0;
     int env_mode = -1;  // --env-mode: GLRTX_ENV_*, -1 the scene file's
-    bool every_frame = false, extensions = false, whitted = false, order_by_hits = false, volume = false, adaptive = false, adaptive_variance = false, min_spp_given = false, volume_wavefront = false;
+    bool every_frame = false, extensions = false, whitted = false, order_by_hits = false, volume = false, adaptive = false, adaptive_variance = false, min_spp_given = false, volume_wavefront = false, texture_wavefront = false;
     float adapt_threshold = 0.0f;
     int min_spp = 2;
     bool denoise = false, denoise_variance = false;
@@ -128,6 +131,7 @@ int main(int argc, char **argv) {
         }
         else if (a == "--enable-volume") volume = true;
         else if (a == "--volume-wavefront") volume_wavefront = true;
+        else if (a == "--texture-wavefront") texture_wavefront = true;
         else if (a == "--adaptive") { adaptive = true; adapt_threshold = (float)std::atof(next("--adaptive")); }
         else if (a == "--adaptive-variance") { adaptive_variance = true; adapt_threshold = (float)std::atof(next("--adaptive-variance")); }
         else if (a == "--min-spp") { min_spp = std::atoi(next("--min-spp")); min_spp_given = true; }
@@ -225,6 +229,7 @@ int main(int argc, char **argv) {
     if (adaptive) window->setAdaptive(adapt_threshold, min_spp);
     if (adaptive_variance) window->setAdaptiveVariance(adapt_threshold, min_spp);
     window->setVolumeWavefront(volume_wavefront);
+    window->setTextureWavefront(texture_wavefront);
     if (denoise) window->setDenoise(denoise_iters);
     if (denoise_variance) window->setDenoiseVariance(denoise_iters);
     if (tonemap_op >= 0) window->setTonemap(tonemap_op, exposure, auto_exposure);

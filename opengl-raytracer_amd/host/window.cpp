@@ -135,6 +135,11 @@ void Window::mainloop(const std::shared_ptr<Scene> &scene_, double fps) {
                       scene->hasDielectric_ ? ", dielectric" : "", scene->whitted_ ? ", Whitted termination" : "");
     }
     uploadTextures();
+    if (textureWavefront_) {  // the set on the wavefront kernel, on every member (a switch: it takes effect on the launches that can route there)
+        for (int i = 0; i < glrtx_group_size(grp_); i++)
+            if (glrtx_set_texture_wavefront(glrtx_group_ctx(grp_, i), 1) != GLRTX_OK) GLRT_FatalError("glrtx_set_texture_wavefront: %s", glrtx_last_error(glrtx_group_ctx(grp_, i)));
+        GLRT_Info("texture wavefront: textured launches run on the wavefront kernel where they can");
+    }
     uploadEnvironment();
     resize(scene->width, scene->height);
     if (const char *e = std::getenv("GLRT_BVH_ORDER")) orderByHits_ = std::string(e) == "hits";

@@ -57,6 +57,9 @@ public:
     // Volume scenes on the wavefront kernel (glrtx_set_volume_wavefront on every member): frames in flight, fed launches and adaptive sampling with the volume
     // on; same images as the persistent megakernel, the default.  Adaptive sampling of a volume scene turns it on by itself.
     void setVolumeWavefront(bool on) { volumeWavefront_ = on; }
+    // Textured scenes on the wavefront kernel (glrtx_set_texture_wavefront on every member): frames in flight and fed launches with textures and material maps
+    // bound; same images as the textured megakernel, the default.  A scene the wavefront kernel cannot take (spheres, dielectric, an environment) renders as before.
+    void setTextureWavefront(bool on) { textureWavefront_ = on; }
     // Denoising (no reference counterpart; glrtx_render_features / glrtx_denoise, one device only): the feature planes are rendered once before the first frame, and
     // every image that is written is the a-trous filter's result D instead of the raw mean.  iterations < 1: the default.
     void setDenoise(int iterations) { denoise_ = true; if (iterations >= 1) denoiseCfg_.iterations = iterations; }
@@ -119,6 +122,7 @@ private:
     float adaptThreshold_ = 0.0f;
     int adaptMinSamples_ = 2;
     bool volumeWavefront_ = false;
+    bool textureWavefront_ = false;
     bool denoise_ = false, denoiseVar_ = false;
     bool reweight_ = false;
     glrtx_reweight_cfg reweightCfg_ = {4.0f};  // (glrt_amd.host.REWEIGHT_DEFAULTS holds the same)

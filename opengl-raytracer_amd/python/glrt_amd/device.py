@@ -162,7 +162,7 @@ EXPORTS = ["glrtx_abi_version", "glrtx_create", "glrtx_destroy", "glrtx_last_err
            "glrtx_group_present_enable", "glrtx_group_present_acquire", "glrtx_group_present_release", "glrtx_group_present_get_stats",
            "glrtx_upload_volume", "glrtx_group_upload_volume", "glrtx_debug_volume_math", "glrtx_debug_volume_lookup",
            "glrtx_render_adaptive", "glrtx_adaptive_active_tiles", "glrtx_read_tile_mask", "glrtx_read_adaptive_half", "glrtx_debug_adaptive_select",
-           "glrtx_group_render_adaptive", "glrtx_group_adaptive_active_tiles", "glrtx_debug_pack_compact", "glrtx_set_volume_wavefront",
+           "glrtx_group_render_adaptive", "glrtx_group_adaptive_active_tiles", "glrtx_debug_pack_compact", "glrtx_set_volume_wavefront", "glrtx_set_texture_wavefront",
            "glrtx_render_features", "glrtx_read_features", "glrtx_denoise", "glrtx_read_denoised", "glrtx_resolve_denoised_rgba8", "glrtx_debug_denoise",
            "glrtx_update_vertices", "glrtx_update_vertices_device", "glrtx_group_update_vertices", "glrtx_debug_read_scene",
            "glrtx_trace_rays", "glrtx_trace_rays_device", "glrtx_reproject", "glrtx_reproject_last", "glrtx_debug_reproject",
@@ -283,6 +283,7 @@ def lib():
         L.glrtx_debug_read_scene.argtypes = [vp, C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t)]
         try:  # (additive to ABI 10: libraries of earlier rounds, which tools/gpu_abx.py loads, lack it)
             L.glrtx_set_volume_wavefront.argtypes = [vp, C.c_int]
+            L.glrtx_set_texture_wavefront.argtypes = [vp, C.c_int]
         except AttributeError:
             pass
         try:  # (additive to ABI 10 as well: the denoiser)
@@ -1100,7 +1101,7 @@ class Device:
     def upload_textures(self, textures, material_texture):
         """Bind a texture set (glrtx_upload_textures; include/glrtx.h "Textures"): textures as host.pack_textures takes them -- a list of (array, format, wrap,
         filter) --, material_texture one texture index a material of the uploaded scene (-1: untextured; only diffuse materials can be bound).  Launches then run
-        on the extension megakernel.  None or an empty list unbinds.  The triangles' texture coordinates are those of the uploaded scene's vertices, frozen."""
+        on the extension megakernel (or, with set_texture_wavefront, on the wavefront kernel's T form).  None or an empty list unbinds.  The triangles' texture coordinates are those of the uploaded scene's vertices, frozen."""
         from .host import pack_textures
         desc, blob = pack_textures(textures or [])
         b = np.ascontiguousarray([] if material_texture is None else material_texture, dtype=np.int32).reshape(-1)
@@ -1150,6 +1151,12 @@ class Device:
         """True: volume launches (EXT_VOLUME alone) run on the wavefront kernel's V form -- frames in flight, fed launches, the present ring and
         render_adaptive with the volume on; bit-identical to the persistent megakernel (the default).  GLRTX_VOLUME_WAVEFRONT=0/1 overrides it per launch."""
         self._ck(self.L.glrtx_set_volume_wavefront(self.h, int(enable)))
+
+    def set_texture_wavefront(self, enable: bool):
+        """True: launches with a texture set bound (material maps included) and nothing else that needs the extension kernel run on the wavefront
+        kernel's T / TM forms -- frames in flight, fed launches, the present ring, render_adaptive*, render_moments and render_cascades with the set
+        bound; bit-identical to the textured megakernel (the default).  GLRTX_TEXTURE_WAVEFRONT=0/1 overrides it per launch."""
+        self._ck(self.L.glrtx_set_texture_wavefront(self.h, int(enable)))
 
     def set_partition(self, rank, world, stripe_rows=16):
         self._ck(self.L.glrtx_set_partition(self.h, rank, world, stripe_rows))
