@@ -1196,7 +1196,7 @@ int glrtx_debug_texture_lookup(const glrtx_texture *tex, size_t n_tex, const voi
  * the three formats, nearest or bilinear, wrap GLRTX_TEX_CLAMP on both axes.  The layout is OCTAHEDRAL with +y as the fold axis, not lat-long: direction ->
  * (s, t) is three absolute values, one quotient and a few selects on a shading path that is bound by instruction issue; lat-long needs atan2 and acos, which
  * have no bit-exact statement here.  While an environment is bound, launches run on the persistent megakernel exactly as with analytic spheres uploaded
- * (variant_last 1, GLRTX_FALLBACK_EXTENSIONS), in kernels of their own (pt_render_persistent_env); textures, spheres, GLRTX_EXT_DIELECTRIC and
+ * (variant_last 1, GLRTX_FALLBACK_EXTENSIONS), in kernels of their own (pt_render_persistent's ENV forms); textures, spheres, GLRTX_EXT_DIELECTRIC and
  * GLRTX_EXT_WHITTED combine with it, GLRTX_EXT_VOLUME does not.
  *
  * Arithmetic.  Every operation is one correctly rounded fp32 operation in the order written, unfused; denormals are zeros of their sign into and out of every
@@ -1266,7 +1266,7 @@ int glrtx_debug_env_eval(const glrtx_texture *map, const void *texels, size_t te
 /* ---- Material maps: a tangent-space normal map on a diffuse or conductor material, a roughness map on a conductor (no reference counterpart; off unless
  * called: with no maps bound every launch runs the kernels it ran before).  The maps are textures of the set glrtx_upload_textures bound -- that set may bind no
  * albedo at all (all -1) --, looked up by "Textures"' rule at the hit's (s, t).  Shaded by MAPS instantiations of the extension megakernel's textured kernels
- * (pt_render_persistent_tex, pt_render_persistent_env), launched only while maps are bound.  PINNED through the reference all the same: a flat normal map and a
+ * (pt_render_persistent's TEX and ENV forms), launched only while maps are bound.  PINNED through the reference all the same: a flat normal map and a
  * constant roughness map of the material's own alphas render the unmapped image bit for bit, and a roughness map that is constant over each cell renders the
  * image of one conductor material a cell.
  *

@@ -1,7 +1,7 @@
 // environment.hip.h -- environment lighting (include/glrtx.h "Environment"): one square octahedral HDR map, looked up where a path's ray misses (escape mode) or
 // sampled as one more light through an importance grid (sampled mode).  The device statements of the rule: env_dir_to_st / env_st_to_dir (the mapping and its
 // inverse), env_radiance, env_eval, env_sample -- used by the extension megakernel's environment instantiations (pt_kernel.hip.h: shade_core<true, TEX, true>,
-// pt_render_persistent_env) and by the kernels behind the glrtx_debug_env_* hooks -- and env_weights_kernel, which sums the importance grid's cell weights.
+// pt_render_persistent's ENV forms) and by the kernels behind the glrtx_debug_env_* hooks -- and env_weights_kernel, which sums the importance grid's cell weights.
 //
 // Why octahedral and not lat-long: the lookup sits on the shading path of a megakernel that is bound by instruction issue and vector memory.
 // Direction -> (s, t) is three absolute values, one quotient and a few selects; lat-long needs atan2 and acos, neither of which has a bit-exact statement here.

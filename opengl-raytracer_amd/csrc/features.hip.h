@@ -10,14 +10,14 @@
 //
 // Planes (packed rows of `width` float4 over the owned rows):  N {nx, ny, nz, t}, a miss {0, 0, 0, 0};  A {albedo rgb, material id as int32 bits}: param0 of a
 // diffuse material, {1, 1, 1} otherwise and on a miss (id -1).  A NaN normal component is stored as 0x7FC00000.
-// Under glrtx_track_motion the *_geom kernels write a third plane  G {wire triangle as int32 bits, u, v, 0}, a miss {-1, 0, 0, 0}: the traversal's own hit, the
-// triangle mapped through the ray queries' table (query::store_hit's).  They take GeomArgs, whose store() adds the plane, and run the same loops; the kernels without it
-// keep their names and their instructions.
-// With a texture set bound (glrtx_upload_textures) the *_tex kernels run instead: TexArgs / TexGeomArgs add the set, and their store() puts the albedo tex_lookup
-// finds at the hit's coordinates into A for a diffuse material bound to a texture -- what the extension kernel shades with.  The material id is unchanged.  They
-// are further instantiations of the same loops, launched only while a set is bound; the kernels above keep their names and their instructions.
-// With material maps bound as well (glrtx_bind_material_maps) the *_maps kernels run: MapArgs / MapGeomArgs are the textured arguments, and their store() puts
-// the mapped normal n' (maps.hip.h) into N for a hit whose material is bound to a normal map.  Launched only while maps are bound.
+// The tree kernel is a template on its argument type, features_tree<COMPACT, A>, and the vine kernels are features_vine_* by name; A's store() says what is written:
+// Under glrtx_track_motion GeomArgs adds a third plane  G {wire triangle as int32 bits, u, v, 0}, a miss {-1, 0, 0, 0}: the traversal's own hit, the
+// triangle mapped through the ray queries' table (query::store_hit's).
+// With a texture set bound (glrtx_upload_textures) TexArgs / TexGeomArgs add the set, and their store() puts the albedo tex_lookup finds at the hit's
+// coordinates into A for a diffuse material bound to a texture -- what the extension kernel shades with.  The material id is unchanged.
+// With material maps bound as well (glrtx_bind_material_maps) MapArgs / MapGeomArgs are the textured arguments, and their store() puts the mapped normal n'
+// (maps.hip.h) into N for a hit whose material is bound to a normal map.
+// Each form is launched only while what it adds is bound; the instantiations on Args are what is launched otherwise.
 #pragma once
 #include "query.hip.h"
 
@@ -98,7 +98,7 @@ struct GeomArgs : Args {
 };
 
 // (store(const Args &) stays as it is for the kernels without G; the second pixel_of below costs nothing: inlined into one function, the compiler merges the
-// two -- the *_geom kernels hold as many division chains as the kernels they extend)
+// two -- the kernels on GeomArgs hold as many division chains as the kernels they extend)
 DEV void store(const GeomArgs &q, unsigned id, const Hit &h) {
     store(static_cast<const Args &>(q), id, h);
     int lx, lrow;
@@ -156,9 +156,11 @@ DEV void store(const MapGeomArgs &q, unsigned id, const Hit &h) {
     store_mapped_normal(q, q.tex, id, h);
 }
 
-// Trees: query::trace_tree's loop with the ray made here.
-template <bool COMPACT>
-__global__ __launch_bounds__(kBlockThreads) void features_tree(const Args q) {
+// Trees: query::trace_tree's loop with the ray made here.  A: the argument type, which chooses store().  The loop is stated in the kernel template and nowhere
+// else: moved into a body shared by __global__ wrappers, the compiler allocated features_tree<*, Args>' registers differently (the same operations, other
+// register numbers and a slightly different schedule), and that kernel is to keep its instructions (tools/isa_diff.py against a build of the parent shows it).
+template <bool COMPACT, class A = Args>
+__global__ __launch_bounds__(kBlockThreads) void features_tree(const A q) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     int *stack = reinterpret_cast<int *>(lds_raw) + 2 * threadIdx.x;
     uint2 *ranks = reinterpret_cast<uint2 *>(lds_raw + (size_t)2 * q.sc.stack_entries * kBlockThreads * sizeof(int));
@@ -245,108 +247,6 @@ __global__ __launch_bounds__(kBlockThreads) void features_tree(const Args q) {
     }
     if (unsaved) store(q, rid, T.h);
 }
-
-// The same loop for the kernels that also write G (A: GeomArgs; store() is chosen by the argument type).  It is written out a second time on purpose: with
-// the loop moved out of features_tree into a shared body, the compiler allocated that kernel's registers differently (the same operations, other register
-// numbers and a slightly different schedule), and the kernels without G are to keep their instructions.  Keep the two in step.
-template <bool COMPACT, class A>
-DEV void tree_body(const A &q) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-    int *stack = reinterpret_cast<int *>(lds_raw) + 2 * threadIdx.x;
-    uint2 *ranks = reinterpret_cast<uint2 *>(lds_raw + (size_t)2 * q.sc.stack_entries * kBlockThreads * sizeof(int));
-    if (COMPACT) {
-        for (int i = threadIdx.x; i < q.sc.n_crank; i += kBlockThreads) ranks[i] = q.sc.cranks[i];
-        __syncthreads();
-    }
-    const int lane = threadIdx.x & 63;
-    const unsigned long long lt_mask = (1ull << lane) - 1ull;
-    float4 co = make_float4(0.f, 0.f, 0.f, 0.f), cd = co;  // this lane's ray of the wave's current chunk, 1 / direction, and whether it is searched
-    float cix = 0.f, ciy = 0.f, ciz = 0.f;
-    int cgo = 0;
-    unsigned cur_base = 0;  // wave-uniform
-    int cur_pos = 0, cur_cnt = 0;
-    auto fetch = [&]() -> int {  // the next chunk (one 8x8 tile); returns its number of ids (0: none left)
-        unsigned base = 0;
-        if (lane == 0) base = atomicAdd(q.counter, (unsigned)query::kChunk);
-        base = __builtin_amdgcn_readfirstlane(base);
-        const int cnt = base >= q.n ? 0 : query::kChunk;  // (n is a multiple of 64)
-        cur_base = base;
-        if (cnt) {
-            int lx, lrow;
-            bool go = pixel_of(q, base + lane, lx, lrow) && centre_ray(q, lx, lrow, co, cd);
-            cix = frcp(cd.x); ciy = frcp(cd.y); ciz = frcp(cd.z);
-            float t0;
-            if (go && q.sc.root_boxed && !box_pass(q.sc.root_lo, q.sc.root_hi, co.x, co.y, co.z, cix, ciy, ciz, cd.w, t0)) go = false;
-            cgo = go ? 1 : 0;
-        }
-        return cnt;
-    };
-    cur_cnt = fetch();
-    bool exhausted = cur_cnt == 0;
-    bool active = false, unsaved = false;  // a finished ray's planes are written when the lane is refilled
-    unsigned rid = 0;
-    Trav T;
-    T.cur = REF_FIN; T.sp = 0; T.stop_d = -__builtin_inff();
-    T.h.t = 0.f; T.h.tri = -1; T.h.u = 0.f; T.h.v = 0.f;
-    for (;;) {
-        unsigned long long idle = __ballot(!active);
-        if ((int)__popcll(idle) >= query::kRefillMin || idle == ~0ull) {
-            while (idle != 0ull && !exhausted) {
-                if (cur_pos >= cur_cnt) {
-                    cur_cnt = fetch();
-                    cur_pos = 0;
-                    if (cur_cnt == 0) { exhausted = true; break; }
-                }
-                const int n = __popcll(idle);
-                const int avail = cur_cnt - cur_pos;
-                const int take = n < avail ? n : avail;
-                const int rank = __popcll(idle & lt_mask);
-                const int src = (cur_pos + rank) & 63;
-                const float ox = __shfl(co.x, src), oy = __shfl(co.y, src), oz = __shfl(co.z, src);
-                const float dx = __shfl(cd.x, src), dy = __shfl(cd.y, src), dz = __shfl(cd.z, src);
-                const float ix = __shfl(cix, src), iy = __shfl(ciy, src), iz = __shfl(ciz, src);
-                const int go = __shfl(cgo, src);
-                if (!active && rank < take) {
-                    if (unsaved) store(q, rid, T.h);
-                    rid = cur_base + (unsigned)src;
-                    T.ox = ox; T.oy = oy; T.oz = oz; T.dx = dx; T.dy = dy; T.dz = dz; T.ix = ix; T.iy = iy; T.iz = iz;
-                    T.h.t = PT_INFTY; T.h.tri = -1; T.h.u = 0.f; T.h.v = 0.f;  // trav_init's start
-                    T.sp = 0;
-                    T.cur = COMPACT ? 0 : q.sc.root_ref;
-                    active = go != 0;
-                    unsaved = !active;  // not searched, the root box missed, or outside the image (store() drops those)
-                }
-                cur_pos += take;
-                idle = __ballot(!active);
-            }
-        }
-        if (!__any(active)) {
-            if (exhausted) break;
-            continue;
-        }
-        if (active) {
-            bool fin = trav_step<true, COMPACT>(q.sc, stack, T, ranks);
-#pragma unroll
-            for (int k = 1; k < query::kStepsPerTrip; k++)
-                if (!fin) fin = trav_step<true, COMPACT>(q.sc, stack, T, ranks);
-            if (fin) {
-                active = false;
-                unsaved = true;
-            }
-        }
-    }
-    if (unsaved) store(q, rid, T.h);
-}
-template <bool COMPACT>
-__global__ __launch_bounds__(kBlockThreads) void features_tree_geom(const GeomArgs q) { tree_body<COMPACT>(q); }
-template <bool COMPACT>
-__global__ __launch_bounds__(kBlockThreads) void features_tree_tex(const TexArgs q) { tree_body<COMPACT>(q); }
-template <bool COMPACT>
-__global__ __launch_bounds__(kBlockThreads) void features_tree_geom_tex(const TexGeomArgs q) { tree_body<COMPACT>(q); }
-template <bool COMPACT>
-__global__ __launch_bounds__(kBlockThreads) void features_tree_maps(const MapArgs q) { tree_body<COMPACT>(q); }
-template <bool COMPACT>
-__global__ __launch_bounds__(kBlockThreads) void features_tree_geom_maps(const MapGeomArgs q) { tree_body<COMPACT>(q); }
 
 // Vines: the list scan, a wave 64 ids (one tile) at a time.
 template <class A>

@@ -1431,6 +1431,66 @@ int wgwf_kernel(glrtx_ctx *c, WgwfLaunch &L) {
     return GLRTX_OK;
 }
 
+// ---- the persistent megakernel (variant 1: render_one): its instantiation and its grid, then the launch.  The ten forms of pt_render_persistent that exist,
+// each with and without ray counting: one table.
+enum PersistForm { kFormPlain, kFormExt, kFormVol, kFormTex, kFormTexVol, kFormTexMaps, kFormTexVolMaps, kFormEnv, kFormEnvTex, kFormEnvTexMaps, kPersistForms };
+#define GLRTX_PERSIST_ROW(EXT, VOL, TEX, ENV, MAPS) \
+    {(const void *)pt_render_persistent<false, EXT, VOL, TEX, ENV, MAPS>, (const void *)pt_render_persistent<true, EXT, VOL, TEX, ENV, MAPS>}
+const void *const kPersistent[kPersistForms][2] = {  // [form][count_rays]; the fourth argument is a VolArgs, in the kFormEnv* rows an EnvArgs
+    GLRTX_PERSIST_ROW(false, false, false, false, false), GLRTX_PERSIST_ROW(true, false, false, false, false), GLRTX_PERSIST_ROW(true, true, false, false, false),
+    GLRTX_PERSIST_ROW(true, false, true, false, false),   GLRTX_PERSIST_ROW(true, true, true, false, false),   GLRTX_PERSIST_ROW(true, false, true, false, true),
+    GLRTX_PERSIST_ROW(true, true, true, false, true),     GLRTX_PERSIST_ROW(true, false, false, true, false),  GLRTX_PERSIST_ROW(true, false, true, true, false),
+    GLRTX_PERSIST_ROW(true, false, true, true, true)};
+#undef GLRTX_PERSIST_ROW
+constexpr const char *kPersistentNames[kPersistForms] = {  // (error reports)
+    "pt_render_persistent", "pt_render_persistent (extensions)", "pt_render_persistent (volume)", "pt_render_persistent (extensions, textures)",
+    "pt_render_persistent (volume, textures)", "pt_render_persistent (extensions, textures, maps)", "pt_render_persistent (volume, textures, maps)",
+    "pt_render_persistent (extensions, environment)", "pt_render_persistent (extensions, environment, textures)",
+    "pt_render_persistent (extensions, environment, textures, maps)"};
+struct PersistLaunch { const void *fn; const char *name; bool vol, env; int lds, grid; ExtArgs ex; };
+
+// ext: render_one's (spheres, an extension flag, a texture set that is not the wavefront kernel's, an environment); lds: the plain kernel's LDS bytes
+int persist_kernel(glrtx_ctx *c, bool ext, int lds, PersistLaunch &k) {
+    const bool tex = c->n_tex > 0, maps = tex && c->have_maps;  // (maps: bound on top of the set, glrtx_bind_material_maps; without them the TEX forms as ever)
+    k.vol = (c->ext_flags & GLRTX_EXT_VOLUME) != 0;  // (render_one has checked that a volume is uploaded, and that no environment is bound beside it)
+    k.env = c->have_env;
+    const int form = k.env ? (maps ? kFormEnvTexMaps : tex ? kFormEnvTex : kFormEnv)
+                     : tex ? kFormTex + (k.vol ? 1 : 0) + (maps ? 2 : 0)
+                           : k.vol ? kFormVol : ext ? kFormExt : kFormPlain;
+    static_assert(kFormTexVol == kFormTex + 1 && kFormTexMaps == kFormTex + 2 && kFormTexVolMaps == kFormTex + 3, "the TEX rows: [maps][volume]");
+    k.fn = kPersistent[form][c->count_rays];
+    k.name = kPersistentNames[form];
+    k.ex = ExtArgs{};
+    if (tex) k.ex.tex = tex_set(c);
+    k.ex.spheres = (const float4 *)c->spheres.p; k.ex.sphere_mat = (const int *)c->sphereMat.p;
+    k.ex.n_spheres = c->n_spheres; k.ex.flags = c->ext_flags;
+    k.lds = lds + (ext ? c->n_spheres * (int)sizeof(float4) : 0);  // extension kernel: the spheres are staged behind the stacks
+    if (k.lds > 160 * 1024) return fail(c, GLRTX_EDEVICE, "render kernel needs %d B of LDS (> 160 KiB)", k.lds);
+    if (k.lds > 64 * 1024) HIP_TRY(c, hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, k.lds));
+    // grid = what is resident at once (occupancy x CUs), capped by the work available
+    int per_cu = 0;
+    HIP_TRY(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k.fn, kBlockThreads, k.lds));
+    if (per_cu < 1) per_cu = 1;
+    const int tiles8 = ((c->width + 7) / 8) * ((c->owned_rows + 7) / 8);
+    const int n_chunks = (tiles8 * 64 + kChunk - 1) / kChunk;
+    const int waves_per_wg = kBlockThreads / 64;
+    k.grid = std::max(1, std::min(per_cu * c->n_cu, (n_chunks + waves_per_wg - 1) / waves_per_wg));
+    return GLRTX_OK;
+}
+
+int persist_launch(glrtx_ctx *c, const PersistLaunch &k, const KernelArgs &a, hipEvent_t ev0) {
+    HIP_TRY(c, hipMemsetAsync(c->work.p, 0, sizeof(unsigned), c->stream));
+    HIP_TRY(c, hipEventRecord(ev0, c->stream));
+    c->last_kernel = k.name;
+    unsigned *work = (unsigned *)c->work.p;
+    const VolArgs va = k.vol ? c->vol : VolArgs{};  // the fourth argument: the volume's, or (kFormEnv*) the environment's
+    EnvArgs ea = c->env;
+    if (k.env) ea.p_env = c->sc.n_light == 0 ? 1.0f : c->env_cfg.light_pick;  // a scene without lights: the environment is the only light to pick
+    void *args[] = {(void *)&a, &work, (void *)&k.ex, k.env ? (void *)&ea : (void *)&va};
+    HIP_TRY(c, hipLaunchKernel(k.fn, dim3(k.grid), dim3(kBlockThreads), args, k.lds, c->stream));
+    return GLRTX_OK;
+}
+
 // ---- the launch's shape.  plain / fed: every workgroup keeps up to kWgPathsMax paths alive, less when the launch is short (below; a fed launch is sized as if it were to take
 // 16 frames: it may).  overlapped, issued while the context's last launch is still rendering: the frame in ONE helping per workgroup, spread over all the slots (the smallest power of two that holds
 // work / resident paths: 2048 at 1080p; with 1024 the workgroups come back for a second helping, 1.31 instead of 1.24 ms per frame, with 4096 half of them get
@@ -3926,7 +3986,7 @@ int glrtx_render_features(glrtx_ctx *c, const glrtx_params *p) {
     const size_t bytes = (size_t)c->width * (size_t)std::max(c->owned_rows, 1) * sizeof(float4);
     int rc;
     if ((rc = ensure(c, c->ftA, bytes)) || (rc = ensure(c, c->ftCounter, sizeof(unsigned)))) return rc;
-    const bool geom = c->mt_on;  // glrtx_track_motion: the *_geom kernels, which write G as well
+    const bool geom = c->mt_on;  // glrtx_track_motion: the kernels on GeomArgs, which write G as well
     if ((geom && (rc = ensure(c, c->ftG, bytes))) || (rc = plane_packed(c, c->ftN))) return rc;
     const auto planes_written = [&]() {  // (glrtx_track_motion; only once nothing can fail any more) the scene as it stands is what these planes show
         if (geom) { c->mt_g_have = true; c->mt_geom = glrtx_ctx::kMtCurrent; }
@@ -3939,80 +3999,40 @@ int glrtx_render_features(glrtx_ctx *c, const glrtx_params *p) {
     bool compact = wgwf_compact(c, vine, fetch);  // the node layout, chosen as trace_launch chooses it
     if (const char *v = std::getenv("GLRTX_COMPACT_NODES")) compact = std::atoi(v) != 0 && !vine && c->sc.n_crank > 0;
     compact = compact && lds_stack + lds_ranks <= 160 * 1024;
-    using Kernel = void (*)(const features::Args);
-    using KernelG = void (*)(const features::GeomArgs);
-    const Kernel kernel_n = vine ? (Kernel)features::features_vine : compact ? (Kernel)features::features_tree<true> : (Kernel)features::features_tree<false>;
-    const KernelG kernel_g = vine ? (KernelG)features::features_vine_geom
-                                  : compact ? (KernelG)features::features_tree_geom<true> : (KernelG)features::features_tree_geom<false>;
-    // with a texture set bound: the textured instantiations, whose plane A carries the looked-up albedo (the ones above are launched as ever without a set)
-    using KernelT = void (*)(const features::TexArgs);
-    using KernelGT = void (*)(const features::TexGeomArgs);
-    const bool tex = c->n_tex > 0;
-    const KernelT kernel_t = vine ? (KernelT)features::features_vine_tex : compact ? (KernelT)features::features_tree_tex<true> : (KernelT)features::features_tree_tex<false>;
-    const KernelGT kernel_gt = vine ? (KernelGT)features::features_vine_geom_tex
-                                    : compact ? (KernelGT)features::features_tree_geom_tex<true> : (KernelGT)features::features_tree_geom_tex<false>;
-    // with material maps bound on top of the set: the *_maps instantiations, whose plane N carries the mapped normal
-    using KernelM = void (*)(const features::MapArgs);
-    using KernelGM = void (*)(const features::MapGeomArgs);
-    const bool maps = tex && c->have_maps;
-    const KernelM kernel_m = vine ? (KernelM)features::features_vine_maps : compact ? (KernelM)features::features_tree_maps<true> : (KernelM)features::features_tree_maps<false>;
-    const KernelGM kernel_gm = vine ? (KernelGM)features::features_vine_geom_maps
-                                    : compact ? (KernelGM)features::features_tree_geom_maps<true> : (KernelGM)features::features_tree_geom_maps<false>;
-    const void *kernel = maps  ? (geom ? (const void *)kernel_gm : (const void *)kernel_m)
-                         : tex ? (geom ? (const void *)kernel_gt : (const void *)kernel_t)
-                         : geom ? (const void *)kernel_g
-                                : (const void *)kernel_n;
-    const int lds = vine ? 0 : lds_stack + (compact ? lds_ranks : 0);
-    if (lds > 64 * 1024) HIP_TRY(c, hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    int per_cu = 0;
-    HIP_TRY(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kBlockThreads, lds));
-    per_cu = std::max(per_cu, 1);
-    features::Args a;
-    a.sc = c->sc;
-    std::memcpy(a.cam, p->c2w, 16 * sizeof(float));
-    std::memcpy(a.cam + 16, p->s2c, 16 * sizeof(float));
-    a.width = c->width; a.height = c->height;
-    a.owned_rows = c->owned_rows; a.rank = c->rank; a.world = c->world; a.stripe = c->stripe;
-    a.tiles8_x = tiles8_x;
-    a.n = (unsigned)(tiles8_x * tiles8_y) * 64u;
-    a.out_n = (float4 *)c->ftN.buf.p; a.out_a = (float4 *)c->ftA.p;
-    a.counter = (unsigned *)c->ftCounter.p;
-    std::memcpy(c->ft_cam, a.cam, sizeof c->ft_cam);  // (glrtx_reproject: the camera these planes belong to)
-    const size_t needed = (a.n + kBlockThreads - 1) / kBlockThreads;
-    const unsigned grid = (unsigned)std::max<size_t>(1, std::min<size_t>((size_t)per_cu * (size_t)c->n_cu, needed));
-    HIP_TRY(c, hipMemsetAsync(c->ftCounter.p, 0, sizeof(unsigned), c->stream));
-    if (maps && geom) {
-        features::MapGeomArgs ga;
-        static_cast<features::Args &>(ga) = a;
-        ga.out_g = (float4 *)c->ftG.p; ga.wire = (const int *)c->qwire.p;
-        ga.tex = tex_set(c);
-        hipLaunchKernelGGL(kernel_gm, dim3(grid), dim3(kBlockThreads), lds, c->stream, ga);
-    } else if (maps) {
-        features::MapArgs ta;
-        static_cast<features::Args &>(ta) = a;
-        ta.tex = tex_set(c);
-        hipLaunchKernelGGL(kernel_m, dim3(grid), dim3(kBlockThreads), lds, c->stream, ta);
-    } else if (tex && geom) {
-        features::TexGeomArgs ga;
-        static_cast<features::Args &>(ga) = a;
-        ga.out_g = (float4 *)c->ftG.p; ga.wire = (const int *)c->qwire.p;
-        ga.tex = tex_set(c);
-        hipLaunchKernelGGL(kernel_gt, dim3(grid), dim3(kBlockThreads), lds, c->stream, ga);
-    } else if (tex) {
-        features::TexArgs ta;
-        static_cast<features::Args &>(ta) = a;
-        ta.tex = tex_set(c);
-        hipLaunchKernelGGL(kernel_t, dim3(grid), dim3(kBlockThreads), lds, c->stream, ta);
-    } else if (geom) {
-        features::GeomArgs ga;
-        static_cast<features::Args &>(ga) = a;
-        ga.out_g = (float4 *)c->ftG.p; ga.wire = (const int *)c->qwire.p;
-        hipLaunchKernelGGL(kernel_g, dim3(grid), dim3(kBlockThreads), lds, c->stream, ga);
-    } else {
-        hipLaunchKernelGGL(kernel_n, dim3(grid), dim3(kBlockThreads), lds, c->stream, a);
-    }
-    HIP_TRY(c, hipGetLastError());
-    return planes_written();
+    const bool tex = c->n_tex > 0, maps = tex && c->have_maps;
+    // One launch over the argument type: q, one of features.hip.h's six, selects the tree kernel's instantiation (the vine kernel comes by name) and is filled with what its type adds to Args --
+    // G and the wire table (glrtx_track_motion), the texture set (plane A carries the looked-up albedo; as Map*Args, plane N the mapped normal).
+    const auto launch = [&](auto q, void (*vine_kernel)(const decltype(q))) -> int {
+        using A = decltype(q);
+        void (*const kernel)(const A) = vine ? vine_kernel : compact ? features::features_tree<true, A> : features::features_tree<false, A>;
+        const int lds = vine ? 0 : lds_stack + (compact ? lds_ranks : 0);
+        if (lds > 64 * 1024) HIP_TRY(c, hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        int per_cu = 0;
+        HIP_TRY(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kBlockThreads, lds));
+        per_cu = std::max(per_cu, 1);
+        features::Args &a = q;
+        a.sc = c->sc;
+        std::memcpy(a.cam, p->c2w, 16 * sizeof(float));
+        std::memcpy(a.cam + 16, p->s2c, 16 * sizeof(float));
+        a.width = c->width; a.height = c->height;
+        a.owned_rows = c->owned_rows; a.rank = c->rank; a.world = c->world; a.stripe = c->stripe;
+        a.tiles8_x = tiles8_x;
+        a.n = (unsigned)(tiles8_x * tiles8_y) * 64u;
+        a.out_n = (float4 *)c->ftN.buf.p; a.out_a = (float4 *)c->ftA.p;
+        a.counter = (unsigned *)c->ftCounter.p;
+        if constexpr (std::is_base_of_v<features::GeomArgs, A>) { q.out_g = (float4 *)c->ftG.p; q.wire = (const int *)c->qwire.p; }
+        if constexpr (std::is_base_of_v<features::TexArgs, A> || std::is_base_of_v<features::TexGeomArgs, A>) q.tex = tex_set(c);
+        std::memcpy(c->ft_cam, a.cam, sizeof c->ft_cam);  // (glrtx_reproject: the camera these planes belong to)
+        const size_t needed = (a.n + kBlockThreads - 1) / kBlockThreads;
+        const unsigned grid = (unsigned)std::max<size_t>(1, std::min<size_t>((size_t)per_cu * (size_t)c->n_cu, needed));
+        HIP_TRY(c, hipMemsetAsync(c->ftCounter.p, 0, sizeof(unsigned), c->stream));
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlockThreads), lds, c->stream, q);
+        HIP_TRY(c, hipGetLastError());
+        return planes_written();
+    };
+    if (maps) return geom ? launch(features::MapGeomArgs{}, features::features_vine_geom_maps) : launch(features::MapArgs{}, features::features_vine_maps);
+    if (tex) return geom ? launch(features::TexGeomArgs{}, features::features_vine_geom_tex) : launch(features::TexArgs{}, features::features_vine_tex);
+    return geom ? launch(features::GeomArgs{}, features::features_vine_geom) : launch(features::Args{}, features::features_vine);
 }
 
 static int denoise_shape_check(glrtx_ctx *c, const char *fn, bool need_result) {
@@ -4795,8 +4815,8 @@ static int render_one(glrtx_ctx *c, const glrtx_params *p, const RenderReq &req)
     // a launch beyond those ranges runs on the persistent megakernel instead (bit-identical, no packed state).
     // Extensions (analytic spheres, dielectric, Whitted termination) exist only in the persistent megakernel's EXT instantiation.
     // The volume alone goes to the wavefront kernel's V form when that is switched on (glrtx_set_volume_wavefront), within its narrower sample range (kWfVolSampleMax).
-    const bool tex = c->n_tex > 0;  // a bound texture set: the extension megakernel's textured instantiations (pt_render_persistent_tex)
-    const bool envb = c->have_env;  // a bound environment: the extension megakernel's environment instantiations (pt_render_persistent_env)
+    const bool tex = c->n_tex > 0;  // a bound texture set: the extension megakernel's TEX forms
+    const bool envb = c->have_env;  // a bound environment: the extension megakernel's ENV forms
     // A texture set alone (material maps included) goes to the wavefront kernel's T / TM forms when those are switched on (glrtx_set_texture_wavefront): such a
     // launch needs no extension kernel and is no fallback.
     const bool tex_wf = tex && wavefront;  // (wgwf_routes, above; anything else runs as it did: the textured megakernel, GLRTX_FALLBACK_EXTENSIONS)
@@ -4818,57 +4838,9 @@ static int render_one(glrtx_ctx *c, const glrtx_params *p, const RenderReq &req)
     glrtx_ctx::LaunchRec *rec = nullptr;
     if (int rc = next_launch_rec(c, rec)) return rc;
     if (variant == 1) {
-        // persistent kernel: grid = what is resident at once (occupancy x CUs), capped by the work available
-        using PKernel = void (*)(const KernelArgs, unsigned *, const ExtArgs, const VolArgs);
-        static constexpr PKernel kPersistent[3][2] = {  // [plain | extensions | volume][count_rays]
-            {pt_render_persistent<false, false>, pt_render_persistent<true, false>}, {pt_render_persistent<false, true>, pt_render_persistent<true, true>},
-            {pt_render_persistent<false, true, true>, pt_render_persistent<true, true, true>}};
-        static constexpr const char *kPersistentNames[3] = {"pt_render_persistent", "pt_render_persistent (extensions)", "pt_render_persistent (volume)"};
-        static constexpr PKernel kPersistentTex[2][2] = {{pt_render_persistent_tex<false, false>, pt_render_persistent_tex<true, false>},  // [extensions | volume][count_rays]
-                                                         {pt_render_persistent_tex<false, true>, pt_render_persistent_tex<true, true>}};
-        static constexpr const char *kPersistentTexNames[2] = {"pt_render_persistent (extensions, textures)", "pt_render_persistent (volume, textures)"};
-        const bool vol = (c->ext_flags & GLRTX_EXT_VOLUME) != 0;  // (render_one has checked that a volume is uploaded)
-        const int which = vol ? 2 : ext ? 1 : 0;
-        using EKernel = void (*)(const KernelArgs, unsigned *, const ExtArgs, const EnvArgs);
-        static constexpr EKernel kPersistentEnv[2][2] = {{pt_render_persistent_env<false, false>, pt_render_persistent_env<true, false>},  // [textures][count_rays]
-                                                         {pt_render_persistent_env<false, true>, pt_render_persistent_env<true, true>}};
-        static constexpr const char *kPersistentEnvNames[2] = {"pt_render_persistent (extensions, environment)", "pt_render_persistent (extensions, environment, textures)"};
-        // material maps bound on top of the set (glrtx_bind_material_maps): the MAPS instantiations; without them the kernels above are launched as ever
-        static constexpr PKernel kPersistentMaps[2][2] = {{pt_render_persistent_tex<false, false, true>, pt_render_persistent_tex<true, false, true>},  // [extensions | volume][count_rays]
-                                                          {pt_render_persistent_tex<false, true, true>, pt_render_persistent_tex<true, true, true>}};
-        static constexpr EKernel kPersistentEnvMaps[2] = {pt_render_persistent_env<false, true, true>, pt_render_persistent_env<true, true, true>};  // [count_rays]
-        const bool maps = tex && c->have_maps;
-        const EKernel ek = maps ? kPersistentEnvMaps[c->count_rays] : kPersistentEnv[tex][c->count_rays];
-        const PKernel pk = envb ? (PKernel) nullptr : maps ? kPersistentMaps[vol][c->count_rays] : tex ? kPersistentTex[vol][c->count_rays] : kPersistent[which][c->count_rays];
-        const void *kfn = envb ? (const void *)ek : (const void *)pk;
-        ExtArgs ex{};
-        if (tex) ex.tex = tex_set(c);
-        ex.spheres = (const float4 *)c->spheres.p; ex.sphere_mat = (const int *)c->sphereMat.p;
-        ex.n_spheres = c->n_spheres; ex.flags = c->ext_flags;
-        const int lds_p = lds + (ext ? c->n_spheres * (int)sizeof(float4) : 0);  // extension kernel: the spheres are staged behind the stacks
-        if (lds_p > 160 * 1024) return fail(c, GLRTX_EDEVICE, "render kernel needs %d B of LDS (> 160 KiB)", lds_p);
-        if (lds_p > 64 * 1024) HIP_TRY(c, hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_p));
-        int per_cu = 0;
-        HIP_TRY(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kfn, kBlockThreads, lds_p));
-        if (per_cu < 1) per_cu = 1;
-        const int tiles8 = ((c->width + 7) / 8) * ((c->owned_rows + 7) / 8);
-        const int n_chunks = (tiles8 * 64 + kChunk - 1) / kChunk;
-        const int waves_per_wg = kBlockThreads / 64;
-        int grid = std::min(per_cu * c->n_cu, (n_chunks + waves_per_wg - 1) / waves_per_wg);
-        if (grid < 1) grid = 1;
-        HIP_TRY(c, hipMemsetAsync(c->work.p, 0, sizeof(unsigned), c->stream));
-        HIP_TRY(c, hipEventRecord(rec->ev0, c->stream));
-        static constexpr const char *kPersistentMapsNames[3] = {"pt_render_persistent (extensions, textures, maps)", "pt_render_persistent (volume, textures, maps)",
-                                                                "pt_render_persistent (extensions, environment, textures, maps)"};
-        c->last_kernel = maps ? kPersistentMapsNames[envb ? 2 : vol] : envb ? kPersistentEnvNames[tex] : tex ? kPersistentTexNames[vol] : kPersistentNames[which];
-        const VolArgs va = vol ? c->vol : VolArgs{};
-        if (envb) {
-            EnvArgs ea = c->env;
-            ea.p_env = c->sc.n_light == 0 ? 1.0f : c->env_cfg.light_pick;  // a scene without lights: the environment is the only light to pick
-            hipLaunchKernelGGL(ek, dim3(grid), dim3(kBlockThreads), lds_p, c->stream, a, (unsigned *)c->work.p, ex, ea);
-        } else {
-            hipLaunchKernelGGL(pk, dim3(grid), dim3(kBlockThreads), lds_p, c->stream, a, (unsigned *)c->work.p, ex, va);
-        }
+        PersistLaunch k;
+        if (int rc = persist_kernel(c, ext, lds, k)) return rc;
+        if (int rc = persist_launch(c, k, a, rec->ev0)) return rc;
     } else {
         static constexpr void (*kTileKernel[2])(const KernelArgs) = {pt_render_kernel<false>, pt_render_kernel<true>};  // [count_rays]
         const auto tk = kTileKernel[c->count_rays];

@@ -35,6 +35,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
 #include "trav_asm.hip.h"
 #include "scan_asm.hip.h"
 #include "texture.hip.h"
@@ -1702,31 +1703,43 @@ constexpr int kChunk = 256;
 // The kernel's by-value arguments as they lie in the kernarg segment.  The loop below reads its launch constants from there, through a
 // pointer the compiler cannot see through and takes anew in every trip, instead of from the by-value copies: those are loaded once at
 // kernel entry and stay live -- in ~100 scalar registers, most of them spilled to vector lanes -- across the traversal loops.
+// Tail: the volume's arguments, or the environment's in their place (the two do not combine).
+template <class Tail>
 struct PersistKernArgs {
     KernelArgs a;
     unsigned *work_counter;
     ExtArgs ex;
-    VolArgs vol;
+    Tail tail;
 };
-DEV const PersistKernArgs *persist_kernargs() {
+template <class Tail>
+DEV const PersistKernArgs<Tail> *persist_kernargs() {
     auto p = __builtin_amdgcn_kernarg_segment_ptr();  // constant address space
     asm volatile("" : "+s"(p));  // opaque: loads through it stay behind this point
-    return (const PersistKernArgs *)p;
+    return (const PersistKernArgs<Tail> *)p;
 }
 
-// VOL (implies EXT): the extension kernel with the volume branch (bounce_volume).
-template <bool COUNT_RAYS, bool EXT = false, bool VOL = false>
+// The forms (glrtx.hip: kPersistent lists the ten that are launched):
+// EXT: the extension kernel (bounce_ext: analytic spheres, dielectric, Whitted termination).  VOL: with the volume branch (bounce_volume).
+// TEX: textured albedo (include/glrtx.h "Textures"; bounce_ext<VOL, true> looks the albedo up), launched only while a texture set is bound.
+// MAPS: material maps on top of the set (include/glrtx.h "Material maps"), launched only while maps are bound.
+// ENV: an environment is bound (include/glrtx.h "Environment"): bounce_ext<false, TEX, true> adds its radiance where a ray leaves the scene and, in sampled
+// mode, draws it as a light; EnvArgs takes VolArgs' place as the fourth argument.
+// The loop is stated here, in the kernel template, and nowhere else: every instantiation is the syntax tree a kernel written out by hand would be.  Called
+// from a body shared by thin __global__ wrappers, the compiler allocated the registers of every instantiation differently (the same operations, another
+// schedule), and a change of form is to leave the instructions of the forms it does not touch alone: tools/isa_diff.py against a build of the parent shows it.
+template <bool COUNT_RAYS, bool EXT = false, bool VOL = false, bool TEX = false, bool ENV = false, bool MAPS = false>
 __global__ __launch_bounds__(kBlockThreads) void pt_render_persistent(const KernelArgs a_entry, unsigned *work_counter_entry, const ExtArgs ex_entry,
-                                                                      const VolArgs vol_entry) {
+                                                                      const std::conditional_t<ENV, EnvArgs, VolArgs> tail_entry) {
+    using Tail = std::conditional_t<ENV, EnvArgs, VolArgs>;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     float4 *lds_mats;
     int *stack;
-    (void)work_counter_entry; (void)ex_entry; (void)vol_entry;
-    static_assert(!VOL || EXT, "the volume kernel is an extension kernel");
+    (void)work_counter_entry; (void)ex_entry; (void)tail_entry;
+    static_assert((EXT || !(VOL || TEX || ENV)) && (TEX || !MAPS) && !(ENV && VOL), "VOL, TEX and ENV are forms of the extension kernel; MAPS needs TEX; ENV excludes VOL");
     lds_setup(a_entry, lds_raw, lds_mats, stack);
     float4 *lds_spheres = nullptr;
     if (EXT) lds_spheres = ext_stage_spheres(a_entry, ex_entry, lds_raw);
-    const KernelArgs &a = persist_kernargs()->a;  // (re-taken inside the loop)
+    const KernelArgs &a = persist_kernargs<Tail>()->a;  // (re-taken inside the loop)
 
     const int lane = threadIdx.x & 63;
     const unsigned long long lt_mask = (1ull << lane) - 1ull;
@@ -1747,7 +1760,7 @@ __global__ __launch_bounds__(kBlockThreads) void pt_render_persistent(const Kern
     unsigned long long rays = 0;  // low half: reference rays, high half: those resolved without a traversal
 
     for (;;) {
-        const PersistKernArgs *ka = persist_kernargs();
+        const PersistKernArgs<Tail> *ka = persist_kernargs<Tail>();
         const KernelArgs &a = ka->a;
         unsigned *const work_counter = ka->work_counter;
         // ---- regeneration: idle lanes take the next pixels of the wave's chunk
@@ -1797,8 +1810,15 @@ __global__ __launch_bounds__(kBlockThreads) void pt_render_persistent(const Kern
             }
             bool finished = true;
             if (a.max_depth > 0) {
-                if (VOL) finished = bounce_ext<true>(a, ka->ex, lds_spheres, lds_mats, stack, rng, P, rays, &ka->vol);
-                else finished = EXT ? bounce_ext(a, ka->ex, lds_spheres, lds_mats, stack, rng, P, rays) : bounce(a, lds_mats, stack, rng, P, rays);
+                if constexpr (ENV) {
+                    finished = bounce_ext<false, TEX, true, MAPS>(a, ka->ex, lds_spheres, lds_mats, stack, rng, P, rays, nullptr, &ka->tail);
+                } else if constexpr (TEX) {
+                    if (VOL) finished = bounce_ext<true, true, false, MAPS>(a, ka->ex, lds_spheres, lds_mats, stack, rng, P, rays, &ka->tail);
+                    else finished = bounce_ext<false, true, false, MAPS>(a, ka->ex, lds_spheres, lds_mats, stack, rng, P, rays);
+                } else {
+                    if (VOL) finished = bounce_ext<true>(a, ka->ex, lds_spheres, lds_mats, stack, rng, P, rays, &ka->tail);
+                    else finished = EXT ? bounce_ext(a, ka->ex, lds_spheres, lds_mats, stack, rng, P, rays) : bounce(a, lds_mats, stack, rng, P, rays);
+                }
             }
             if (finished) {
                 acc.x = acc.x + fmin_c(P.Lx, 100.0f);  // :558, :608
@@ -1815,226 +1835,7 @@ __global__ __launch_bounds__(kBlockThreads) void pt_render_persistent(const Kern
             }
         }
     }
-    flush_rays<COUNT_RAYS>(persist_kernargs()->a, rays);
-}
-
-// The extension kernel with textured albedo (include/glrtx.h "Textures"): bounce_ext<VOL, true> looks the albedo up, everything else is pt_render_persistent<*, true, VOL>.
-// Launched only while a texture set is bound.  The loop is written out a second time on purpose: called from a body shared by both kernels, the compiler allocated
-// the registers of every pt_render_persistent instantiation differently (the same operations, another schedule), and the kernels without textures are to keep
-// their instructions.  Keep the two in step.
-// MAPS: with material maps bound on top of the set (include/glrtx.h "Material maps"), bounce_ext<VOL, true, false, true>; instantiations of their own, launched only then.
-template <bool COUNT_RAYS, bool VOL, bool MAPS = false>
-__global__ __launch_bounds__(kBlockThreads) void pt_render_persistent_tex(const KernelArgs a_entry, unsigned *work_counter_entry, const ExtArgs ex_entry,
-                                                                          const VolArgs vol_entry) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-    float4 *lds_mats;
-    int *stack;
-    (void)work_counter_entry; (void)ex_entry; (void)vol_entry;
-    lds_setup(a_entry, lds_raw, lds_mats, stack);
-    float4 *lds_spheres = ext_stage_spheres(a_entry, ex_entry, lds_raw);
-    const KernelArgs &a = persist_kernargs()->a;  // (re-taken inside the loop)
-
-    const int lane = threadIdx.x & 63;
-    const unsigned long long lt_mask = (1ull << lane) - 1ull;
-    const int tiles8_x = (a.width + 7) >> 3, tiles8_y = (a.owned_rows + 7) >> 3;
-    const int total = tiles8_x * tiles8_y * 64;
-
-    // wave-uniform work state
-    int chunk_next = 0, chunk_end = 0;
-    bool exhausted = false;
-    // per-lane state
-    bool alive = false, fresh = false;
-    int px_off = 0, sample = 0;
-    float fcx = 0.f, fcy = 0.f;
-    Rng rng = {0.f, 0.f, a.seed_x, a.seed_y};
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    Path P;
-    path_begin(P, 0.f, 0.f, 0.f, 0.f, 0.f, 1.f);
-    unsigned long long rays = 0;  // low half: reference rays, high half: those resolved without a traversal
-
-    for (;;) {
-        const PersistKernArgs *ka = persist_kernargs();
-        const KernelArgs &a = ka->a;
-        unsigned *const work_counter = ka->work_counter;
-        // ---- regeneration: idle lanes take the next pixels of the wave's chunk
-        unsigned long long idle = __ballot(!alive);
-        while (idle != 0ull && !exhausted) {
-            if (chunk_next >= chunk_end) {
-                int base = 0;
-                if (lane == 0) base = (int)atomicAdd(work_counter, (unsigned)kChunk);
-                base = __builtin_amdgcn_readfirstlane(base);
-                if (base >= total) { exhausted = true; break; }
-                chunk_next = base;
-                chunk_end = base + kChunk < total ? base + kChunk : total;
-            }
-            const int n = __popcll(idle);
-            const int avail = chunk_end - chunk_next;
-            const int take = n < avail ? n : avail;
-            const int rank = __popcll(idle & lt_mask);
-            if (!alive && rank < take) {
-                const int id = chunk_next + rank;
-                const int t = id >> 6, w = id & 63;
-                const int lx = (t % tiles8_x) * 8 + (w & 7);
-                const int lrow = (t / tiles8_x) * 8 + (w >> 3);
-                if (lx < a.width && lrow < a.owned_rows && a.n_samples > 0) {
-                    const int gy = local_row_to_y(a, lrow);
-                    fcx = (float)lx + 0.5f; fcy = (float)gy + 0.5f;  // gl_FragCoord.xy
-                    rng.x = fcx / (float)a.width; rng.y = fcy / (float)a.height;  // :567
-                    px_off = lrow * a.pitch_f4 + lx;
-                    acc = a.accum[px_off];  // previous (L, count) (:570-572)
-                    sample = 0;
-                    alive = true; fresh = true;
-                }
-            }
-            chunk_next += take;
-            // still-idle lanes (chunk ran short, or the pixel drawn lies outside the image) go round again;
-            // every round consumes at least one id, so the loop ends when the image is exhausted
-            idle = __ballot(!alive);
-        }
-        if (!__any(alive)) {
-            if (exhausted) break;
-            continue;
-        }
-        // ---- one step for every live lane: (new sample ->) one bounce
-        if (alive) {
-            if (fresh) {
-                camera_ray(a, a.cam, rng, fcx, fcy, P);
-                fresh = false;
-            }
-            bool finished = true;
-            if (a.max_depth > 0) {
-                if (VOL) finished = bounce_ext<true, true, false, MAPS>(a, ka->ex, lds_spheres, lds_mats, stack, rng, P, rays, &ka->vol);
-                else finished = bounce_ext<false, true, false, MAPS>(a, ka->ex, lds_spheres, lds_mats, stack, rng, P, rays);
-            }
-            if (finished) {
-                acc.x = acc.x + fmin_c(P.Lx, 100.0f);  // :558, :608
-                acc.y = acc.y + fmin_c(P.Ly, 100.0f);
-                acc.z = acc.z + fmin_c(P.Lz, 100.0f);
-                acc.w = acc.w + 1.0f;
-                sample++;
-                if (sample >= a.n_samples) {
-                    a.accum[px_off] = acc;
-                    alive = false;
-                } else {
-                    fresh = true;
-                }
-            }
-        }
-    }
-    flush_rays<COUNT_RAYS>(persist_kernargs()->a, rays);
-}
-
-// The extension kernel with an environment bound (include/glrtx.h "Environment"): bounce_ext<false, TEX, true> adds the environment's radiance where a ray leaves
-// the scene and, in sampled mode, draws it as a light; everything else is pt_render_persistent<*, true>.  Launched only while an environment is bound; the
-// environment's arguments take the place of the volume's in the kernarg block (the two do not combine).  The loop is written out once more for the reason
-// pt_render_persistent_tex gives: the existing instantiations are to keep their instructions.  Keep the three in step.
-struct PersistEnvKernArgs {
-    KernelArgs a;
-    unsigned *work_counter;
-    ExtArgs ex;
-    EnvArgs env;
-};
-DEV const PersistEnvKernArgs *persist_env_kernargs() {
-    auto p = __builtin_amdgcn_kernarg_segment_ptr();  // constant address space
-    asm volatile("" : "+s"(p));  // opaque: loads through it stay behind this point
-    return (const PersistEnvKernArgs *)p;
-}
-template <bool COUNT_RAYS, bool TEX, bool MAPS = false>  // (MAPS: as pt_render_persistent_tex's; needs TEX)
-__global__ __launch_bounds__(kBlockThreads) void pt_render_persistent_env(const KernelArgs a_entry, unsigned *work_counter_entry, const ExtArgs ex_entry,
-                                                                          const EnvArgs env_entry) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-    float4 *lds_mats;
-    int *stack;
-    (void)work_counter_entry; (void)ex_entry; (void)env_entry;
-    lds_setup(a_entry, lds_raw, lds_mats, stack);
-    float4 *lds_spheres = ext_stage_spheres(a_entry, ex_entry, lds_raw);
-    const KernelArgs &a = persist_env_kernargs()->a;  // (re-taken inside the loop)
-
-    const int lane = threadIdx.x & 63;
-    const unsigned long long lt_mask = (1ull << lane) - 1ull;
-    const int tiles8_x = (a.width + 7) >> 3, tiles8_y = (a.owned_rows + 7) >> 3;
-    const int total = tiles8_x * tiles8_y * 64;
-
-    // wave-uniform work state
-    int chunk_next = 0, chunk_end = 0;
-    bool exhausted = false;
-    // per-lane state
-    bool alive = false, fresh = false;
-    int px_off = 0, sample = 0;
-    float fcx = 0.f, fcy = 0.f;
-    Rng rng = {0.f, 0.f, a.seed_x, a.seed_y};
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    Path P;
-    path_begin(P, 0.f, 0.f, 0.f, 0.f, 0.f, 1.f);
-    unsigned long long rays = 0;  // low half: reference rays, high half: those resolved without a traversal
-
-    for (;;) {
-        const PersistEnvKernArgs *ka = persist_env_kernargs();
-        const KernelArgs &a = ka->a;
-        unsigned *const work_counter = ka->work_counter;
-        // ---- regeneration: idle lanes take the next pixels of the wave's chunk
-        unsigned long long idle = __ballot(!alive);
-        while (idle != 0ull && !exhausted) {
-            if (chunk_next >= chunk_end) {
-                int base = 0;
-                if (lane == 0) base = (int)atomicAdd(work_counter, (unsigned)kChunk);
-                base = __builtin_amdgcn_readfirstlane(base);
-                if (base >= total) { exhausted = true; break; }
-                chunk_next = base;
-                chunk_end = base + kChunk < total ? base + kChunk : total;
-            }
-            const int n = __popcll(idle);
-            const int avail = chunk_end - chunk_next;
-            const int take = n < avail ? n : avail;
-            const int rank = __popcll(idle & lt_mask);
-            if (!alive && rank < take) {
-                const int id = chunk_next + rank;
-                const int t = id >> 6, w = id & 63;
-                const int lx = (t % tiles8_x) * 8 + (w & 7);
-                const int lrow = (t / tiles8_x) * 8 + (w >> 3);
-                if (lx < a.width && lrow < a.owned_rows && a.n_samples > 0) {
-                    const int gy = local_row_to_y(a, lrow);
-                    fcx = (float)lx + 0.5f; fcy = (float)gy + 0.5f;  // gl_FragCoord.xy
-                    rng.x = fcx / (float)a.width; rng.y = fcy / (float)a.height;  // :567
-                    px_off = lrow * a.pitch_f4 + lx;
-                    acc = a.accum[px_off];  // previous (L, count) (:570-572)
-                    sample = 0;
-                    alive = true; fresh = true;
-                }
-            }
-            chunk_next += take;
-            // still-idle lanes (chunk ran short, or the pixel drawn lies outside the image) go round again;
-            // every round consumes at least one id, so the loop ends when the image is exhausted
-            idle = __ballot(!alive);
-        }
-        if (!__any(alive)) {
-            if (exhausted) break;
-            continue;
-        }
-        // ---- one step for every live lane: (new sample ->) one bounce
-        if (alive) {
-            if (fresh) {
-                camera_ray(a, a.cam, rng, fcx, fcy, P);
-                fresh = false;
-            }
-            bool finished = true;
-            if (a.max_depth > 0) finished = bounce_ext<false, TEX, true, MAPS>(a, ka->ex, lds_spheres, lds_mats, stack, rng, P, rays, nullptr, &ka->env);
-            if (finished) {
-                acc.x = acc.x + fmin_c(P.Lx, 100.0f);  // :558, :608
-                acc.y = acc.y + fmin_c(P.Ly, 100.0f);
-                acc.z = acc.z + fmin_c(P.Lz, 100.0f);
-                acc.w = acc.w + 1.0f;
-                sample++;
-                if (sample >= a.n_samples) {
-                    a.accum[px_off] = acc;
-                    alive = false;
-                } else {
-                    fresh = true;
-                }
-            }
-        }
-    }
-    flush_rays<COUNT_RAYS>(persist_env_kernargs()->a, rays);
+    flush_rays<COUNT_RAYS>(persist_kernargs<Tail>()->a, rays);
 }
 
 // ------------------------------------------------------------------------------------------ wavefront formulation

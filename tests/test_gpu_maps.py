@@ -314,7 +314,7 @@ def test_flat_maps_change_nothing_next_to_the_other_extensions(dev, extras):
         assert st.variant_last == 1
         _same(got, ref, f"albedo + environment + flat maps (extras={extras})")
         assert st.rays == st0.rays
-        # without the environment: pt_render_persistent_tex's MAPS form against its plain form
+        # without the environment: pt_render_persistent's TEX + MAPS form against its TEX form
         dev.upload_environment(None)
         got, st = _frames(dev, params)
         dev.bind_material_maps()

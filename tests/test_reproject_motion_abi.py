@@ -108,7 +108,8 @@ def test_the_new_kernels_spill_no_vector_register_and_use_no_scratch():
         if m:
             rows[m.group(1)] = [int(v) for v in m.group(2).split()]
     for name, lds_free in (("glrtx::motion::reproject_motion_kernel", True), ("glrtx::motion::snapshot_kernel", True), ("glrtx::features::features_vine_geom", True),
-                           ("glrtx::features::features_tree_geom<true>", False), ("glrtx::features::features_tree_geom<false>", False)):
+                           ("glrtx::features::features_tree<true, glrtx::features::GeomArgs>", False),
+                           ("glrtx::features::features_tree<false, glrtx::features::GeomArgs>", False)):
         assert name in rows, (name, sorted(rows))
         vgpr, agpr, sgpr, vspill, sspill, scratch, lds = rows[name]
         assert vspill == 0 and scratch == 0 and agpr == 0 and vgpr <= 64, (name, rows[name])
@@ -116,9 +117,11 @@ def test_the_new_kernels_spill_no_vector_register_and_use_no_scratch():
             assert lds == 0, (name, rows[name])
         if "vine" not in name:
             assert sspill == 0, (name, rows[name])
-    for name in ("glrtx::features::features_vine", "glrtx::features::features_tree<true>", "glrtx::features::features_tree<false>", "glrtx::reproject::reproject_kernel"):
+    for name in ("glrtx::features::features_vine", "glrtx::features::features_tree<true, glrtx::features::Args>",
+                 "glrtx::features::features_tree<false, glrtx::features::Args>", "glrtx::reproject::reproject_kernel"):
         assert name in rows, name
-    assert rows["glrtx::features::features_vine_geom"][4] <= rows["glrtx::features::features_vine"][4] + 8  # (lane spills of scalars, like the kernel it extends)
+    # (lane spills of scalars, like the kernel it extends)
+    assert rows["glrtx::features::features_vine_geom"][4] <= rows["glrtx::features::features_vine"][4] + 8
 
 
 def test_shared_sources():
@@ -131,17 +134,13 @@ def test_shared_sources():
     assert "store(static_cast<const Args &>(q), id, h);" in f
 
 
-def test_the_two_tree_loops_are_one_text():
-    """features_tree keeps its loop in the kernel (its instructions are pinned); tree_body repeats it for the kernels with G.  Apart from the two signature
-    lines the bodies must be the same text, so that a fix to one cannot miss the other."""
+def test_each_persistent_loop_is_stated_once():
+    """The feature pass's tree loop and the megakernel's regeneration and bounce loop each live in one kernel template (their instantiations' instructions are
+    pinned, tools/isa_diff.py): no second copy of either text, and no shared body behind wrappers."""
     f = (PKG / "csrc" / "features.hip.h").read_text()
-
-    def body(start, end):
-        a = f.index(start)
-        a = f.index("\n", a) + 1
-        return f[a:f.index(end, a)]
-
-    kernel = body("__global__ __launch_bounds__(kBlockThreads) void features_tree(const Args q) {", "\n}\n")
-    shared = body("DEV void tree_body(const A &q) {", "\n}\n")
-    assert len(kernel.splitlines()) > 60 and "trav_step<true, COMPACT>" in kernel and "store(q, rid, T.h)" in kernel
-    assert kernel == shared
+    assert "tree_body" not in f
+    loops = f.split("for (;;)")[1:]
+    assert sum("trav_step<true, COMPACT>" in part for part in loops) == 1 and f.count("bool fin = trav_step<true, COMPACT>") == 1
+    k = (PKG / "csrc" / "pt_kernel.hip.h").read_text()
+    assert k.count("atomicAdd(work_counter, (unsigned)kChunk)") == 1
+    assert "pt_render_persistent_" not in k

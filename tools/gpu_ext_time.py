@@ -26,7 +26,7 @@ for (w, h, depth) in ((256, 256, 1), (1920, 1080, 4), (3840, 2160, 8)):
             st = d.stats()
             ms.append((st.kernel_ms_total + st.accumulate_ms_total) / n)
         t = float(np.median(ms[1:]))
-        row = {"size": f"{w}x{h}", "max_depth": depth, "scene": mode, "kernel": "pt_render_wgwf" if st.variant_last == 2 else "pt_render_persistent<*, EXT>",
+        row = {"size": f"{w}x{h}", "max_depth": depth, "scene": mode, "kernel": "pt_render_wgwf" if st.variant_last == 2 else "pt_render_persistent<*, true>",
                "rays_per_frame": rays, "ms_per_frame": round(t, 4), "mrays_per_s": round(rays / t / 1e3, 1)}
         out["rows"].append(row); print(row, flush=True)
         d.set_extensions(0); d.upload_spheres(None)

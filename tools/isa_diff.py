@@ -1,15 +1,25 @@
 #!/usr/bin/env python3
-"""Per-kernel comparison of the gfx950 disassembly of two builds of libglrtx.so: which kernels are new, gone, or changed.
+r"""Per-kernel comparison of the gfx950 disassembly of two builds of libglrtx.so: which kernels are new, gone, or changed.
 
-    python tools/isa_diff.py OTHER/libglrtx.so [THIS/libglrtx.so]      # exit 1 if a kernel present in both differs
+    python tools/isa_diff.py [--rename REGEX=REPLACEMENT ...] OTHER/libglrtx.so [THIS/libglrtx.so]      # exit 1 if a kernel present in both differs
 
 A pull request that adds kernels to the translation unit shows with it that every kernel it did not mean to touch still compiles to the same
-instructions.  Compared per symbol: mnemonics and operands of every instruction in order; addresses and encodings are dropped (a kernel moves when
-another is added in front of it), as are the pc-relative literals that follow s_getpc_b64 (distances to other symbols).
+instructions.  Compared per symbol, by demangled name: mnemonics and operands of every instruction in order; addresses and encodings are dropped (a kernel
+moves when another is added in front of it), as are the pc-relative literals that follow s_getpc_b64 (distances to other symbols).
+--rename (repeatable, applied in order with re.sub to the demangled names of OTHER) compares a renamed kernel against its successor instead of
+listing it as GONE and NEW.  From the commit before pt_render_persistent and features_tree became one template each (9558ec0) to its successor:
+
+    --rename 'pt_render_persistent<(\w+), (\w+), (\w+)>(.*)glrtx::VolArgs\)=pt_render_persistent<\1, \2, \3, false, false, false>\4std::conditional<false, glrtx::EnvArgs, glrtx::VolArgs>::type)'
+    --rename 'pt_render_persistent_tex<(\w+), (\w+), (\w+)>(.*)glrtx::VolArgs\)=pt_render_persistent<\1, true, \2, true, false, \3>\4std::conditional<false, glrtx::EnvArgs, glrtx::VolArgs>::type)'
+    --rename 'pt_render_persistent_env<(\w+), (\w+), (\w+)>(.*)glrtx::EnvArgs\)=pt_render_persistent<\1, true, false, \2, true, \3>\4std::conditional<true, glrtx::EnvArgs, glrtx::VolArgs>::type)'
+    --rename 'features_tree<(\w+)>=features_tree<\1, glrtx::features::Args>'
+    --rename 'features_tree_\w+<(\w+)>\(glrtx::features::(\w+)\)=features_tree<\1, glrtx::features::\2>(glrtx::features::\2)'
+
 Works without a GPU (tools/isa_report.py's extraction, llvm-objdump from /opt/rocm).
 """
 from __future__ import annotations
 
+import argparse
 import pathlib
 import re
 import subprocess
@@ -42,24 +52,38 @@ def functions(lib: pathlib.Path) -> dict[str, list[str]]:
     return out
 
 
+def by_name(lib: pathlib.Path, renames=()) -> dict[str, list[str]]:
+    fs = functions(lib)
+    names = isa_report.demangle(sorted(fs))
+    out = {}
+    for sym, ins in fs.items():
+        n = names[sym]
+        for rx, to in renames:
+            n = re.sub(rx, to, n)
+        assert n not in out, f"{lib}: two symbols named {n}"
+        out[n] = ins
+    return out
+
+
 def main() -> int:
-    if len(sys.argv) < 2:
-        print(__doc__)
-        return 2
-    a = functions(pathlib.Path(sys.argv[1]))
-    b = functions(pathlib.Path(sys.argv[2]) if len(sys.argv) > 2 else isa_report.LIB)
-    names = isa_report.demangle(sorted(set(a) | set(b)))
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("other")
+    ap.add_argument("this", nargs="?", default=str(isa_report.LIB))
+    ap.add_argument("--rename", action="append", default=[], metavar="REGEX=REPLACEMENT")
+    args = ap.parse_args()
+    a = by_name(pathlib.Path(args.other), [r.split("=", 1) for r in args.rename])
+    b = by_name(pathlib.Path(args.this))
     same = changed = 0
     for n in sorted(set(a) & set(b)):
         if a[n] == b[n]:
             same += 1
         else:
             changed += 1
-            print(f"CHANGED  {names[n]}  ({len(a[n])} -> {len(b[n])} instructions)")
+            print(f"CHANGED  {n}  ({len(a[n])} -> {len(b[n])} instructions)")
     for n in sorted(set(a) - set(b)):
-        print(f"GONE     {names[n]}")
+        print(f"GONE     {n}")
     for n in sorted(set(b) - set(a)):
-        print(f"NEW      {names[n]}  ({len(b[n])} instructions)")
+        print(f"NEW      {n}  ({len(b[n])} instructions)")
     print(f"{same} symbols identical, {changed} changed, {len(set(a) - set(b))} gone, {len(set(b) - set(a))} new")
     return 1 if changed else 0
 

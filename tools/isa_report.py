@@ -64,10 +64,11 @@ def kernels(co: pathlib.Path):
 
 
 def table(ks) -> str:
-    hdr = f"{'kernel':58s} {'vgpr':>5s} {'agpr':>5s} {'sgpr':>5s} {'vspill':>6s} {'sspill':>6s} {'scratch':>7s} {'lds':>6s}"
+    w = max([58] + [len(k["pretty"]) for k in ks])  # (no name is cut: template arguments tell the instantiations apart)
+    hdr = f"{'kernel':{w}s} {'vgpr':>5s} {'agpr':>5s} {'sgpr':>5s} {'vspill':>6s} {'sspill':>6s} {'scratch':>7s} {'lds':>6s}"
     rows = [hdr, "-" * len(hdr)]
     for k in ks:
-        rows.append(f"{k['pretty'][:58]:58s} {k['vgpr_count']:5d} {k['agpr_count']:5d} {k['sgpr_count']:5d} {k['vgpr_spill_count']:6d} "
+        rows.append(f"{k['pretty']:{w}s} {k['vgpr_count']:5d} {k['agpr_count']:5d} {k['sgpr_count']:5d} {k['vgpr_spill_count']:6d} "
                     f"{k['sgpr_spill_count']:6d} {k['private_segment_fixed_size']:7d} {k['group_segment_fixed_size']:6d}")
     return "\n".join(rows)
 
