@@ -689,6 +689,66 @@ DEV void trav_steps_asm(const DevScene &sc, int *stack, Trav &T, unsigned rk GLR
         : "vcc", "scc", "memory", GLRTX_ASM_VCLOBBERS GLRTX_TS_CLOBBERS);
 }
 
+// The loop of wg_traverse_phase around the step, as one hand-written asm statement (trav_asm.hip.h: GLRTX_TRAV_LOOP_ASM, where its rules and its invariant are
+// stated).  L is the wave's loop state; returns why the statement left: 0 finished, 1 the chunk is used up, 2 park the running lanes.
+struct TravLoop {
+    unsigned long long act, uns;  // lanes with a running ray / with a finished ray whose record is not written yet (wave-uniform masks)
+    int pos, cnt;                 // the wave's chunk: records taken / held
+    unsigned flags;               // 1 queue exhausted, 2 resume inside the refill, 4 parking may be considered
+    unsigned rid, nr;             // per lane: the ray's id, rays taken
+    float4 co, cd;                // per lane: this lane's record of the chunk ...
+    float ix, iy, iz, lim;        // ... 1 / direction and the search limit, worked out when the chunk arrived
+};
+#define GLRTX_LOOP_OUT \
+    [th] "+&v"(T.h.t), [tri] "+&v"(T.h.tri), [hu] "+&v"(T.h.u), [hv] "+&v"(T.h.v), [cur] "+&v"(T.cur), [sp] "+&v"(T.sp), \
+    [ox] "+&v"(T.ox), [oy] "+&v"(T.oy), [oz] "+&v"(T.oz), [dx] "+&v"(T.dx), [dy] "+&v"(T.dy), [dz] "+&v"(T.dz), [ix] "+&v"(T.ix), [iy] "+&v"(T.iy), [iz] "+&v"(T.iz), \
+    [sd] "+&v"(T.stop_d), [rid] "+&v"(L.rid), [nr] "+&v"(L.nr), [act] "+&s"(L.act), [uns] "+&s"(L.uns), [pos] "+&s"(L.pos), \
+    [entry] "=&s"(s_entry), [was] "=&s"(s_was), [leaf] "=&s"(s_leaf), [bl] "=&s"(s_bl), [br] "=&s"(s_br), [pop] "=&s"(s_pop), [tmp] "=&s"(s_tmp), \
+    [n] "=&s"(s_n), [take] "=&s"(s_take), [why] "=&s"(why)
+#define GLRTX_LOOP_IN \
+    [cox] "v"(L.co.x), [coy] "v"(L.co.y), [coz] "v"(L.co.z), [cow] "v"(L.co.w), [cdx] "v"(L.cd.x), [cdy] "v"(L.cd.y), [cdz] "v"(L.cd.z), [cdw] "v"(L.cd.w), \
+    [cix] "v"(L.ix), [ciy] "v"(L.iy), [ciz] "v"(L.iz), [clim] "v"(L.lim), [stk] "v"(stk), [cnt] "s"(cnt), [flags] "s"(flags), [rmin] "s"(rmin), [smax] "s"(smax), \
+    [hbase] "s"(hbase), [lb] "s"(lb), [eps] "s"(PT_EPS)
+template <int FETCH>
+DEV int trav_loop_asm(const DevScene &sc, int *stack, Trav &T, TravLoop &L, int rmin, int smax, const void *hbase, unsigned lb, unsigned rk) {
+    unsigned long long s_entry, s_was, s_leaf, s_bl, s_br, s_pop, s_tmp;
+    int s_n, s_take, why;
+    const unsigned stk = (unsigned)(uintptr_t)stack;
+    static_assert(kBlockThreads * 8 == 1 << 11 && REF_FIN == INT32_MIN, "see trav_steps_asm");
+    // (wave-uniform by construction; said to the compiler, which would otherwise hand the statement vector registers for them)
+    const int cnt = __builtin_amdgcn_readfirstlane(L.cnt);
+    const unsigned flags = (unsigned)__builtin_amdgcn_readfirstlane((int)L.flags);
+    rmin = __builtin_amdgcn_readfirstlane(rmin);
+    smax = __builtin_amdgcn_readfirstlane(smax);
+    const unsigned par16 = (threadIdx.x & 1u) << 4;  // (see trav_steps_asm)
+    const unsigned bias_e = sc.node_bias + par16, bias_o = sc.node_bias + 16u - par16;
+    if constexpr ((FETCH & kWgwfCompact) != 0) {
+        static_assert((FETCH & ~kWgwfCompact) == 0, "the compact layout has the one-record-per-lane fetch only");
+        asm volatile(GLRTX_TRAV_LOOP_ASM(GLRTX_REP(GLRTX_STEPS_PER_TRIP, GLRTX_TRAV_STEP_ASM_COMPACT), "v[GLRTX_VB+22]", "0")
+                     : GLRTX_LOOP_OUT
+                     : GLRTX_LOOP_IN, [cbase] "s"(sc.cnodes), [rk] "s"(rk)
+                     : "vcc", "scc", "memory", GLRTX_ASM_VCLOBBERS_COMPACT);
+    } else if constexpr (FETCH == 2) {
+        asm volatile(GLRTX_TRAV_LOOP_ASM(GLRTX_REP(GLRTX_STEPS_PER_TRIP_HALF, GLRTX_TRAV_STEP_ASM_PAIR GLRTX_TRAV_STEP_ASM_LANE), "v[GLRTX_VB+11]", "%[root]")
+                     : GLRTX_LOOP_OUT
+                     : GLRTX_LOOP_IN, [root] "s"(sc.root_ref), [base] "s"(sc.nodes0), [bias] "s"(sc.node_bias), [odd] "s"(0xAAAAAAAAAAAAAAAAull), [biase] "v"(bias_e), [biaso] "v"(bias_o)
+                     : "vcc", "scc", "memory", GLRTX_ASM_VCLOBBERS_PAIR);
+    } else if constexpr (FETCH == 1) {
+        asm volatile(GLRTX_TRAV_LOOP_ASM(GLRTX_REP(GLRTX_STEPS_PER_TRIP, GLRTX_TRAV_STEP_ASM_PAIR), "v[GLRTX_VB+11]", "%[root]")
+                     : GLRTX_LOOP_OUT
+                     : GLRTX_LOOP_IN, [root] "s"(sc.root_ref), [base] "s"(sc.nodes0), [odd] "s"(0xAAAAAAAAAAAAAAAAull), [biase] "v"(bias_e), [biaso] "v"(bias_o)
+                     : "vcc", "scc", "memory", GLRTX_ASM_VCLOBBERS_PAIR);
+    } else {
+        static_assert(FETCH == 0, "node fetch: 0 lane, 1 pair, 2 alternating, kWgwfCompact");
+        asm volatile(GLRTX_TRAV_LOOP_ASM(GLRTX_REP(GLRTX_STEPS_PER_TRIP, GLRTX_TRAV_STEP_ASM_LANE), "v[GLRTX_VB+11]", "%[root]")
+                     : GLRTX_LOOP_OUT
+                     : GLRTX_LOOP_IN, [root] "s"(sc.root_ref), [base] "s"(sc.nodes0), [bias] "s"(sc.node_bias)
+                     : "vcc", "scc", "memory", GLRTX_ASM_VCLOBBERS);
+    }
+    (void)rk; (void)bias_e; (void)bias_o;
+    return why;
+}
+
 // intersect(Ray, Triangle) :226-257 against the running closest hit; v0 / e1 = v1-v0 / e2 = v2-v0.  Used by the list scan only (the tree
 // kernels carry the test in their step).  All lanes of a wave test the SAME triangle here, and most triangles are missed by all of
 // them: the test leaves as soon as no lane of the wave can still hit -- after u (22 of the ~60 vector instructions), after v -- which
@@ -2368,6 +2428,10 @@ __device__ unsigned g_ray_log_trips;        // trips appended
 // again in round 2, after the kernel had lost its spills, it bought nothing and its 8 registers were freed; that A/B table was not kept.)
 DEV int wgwf_suspend_max();  // WfArgs::suspend_max of the running pt_render_wgwf launch, from its kernarg segment (defined below)
 
+// The diagnostic builds keep the C++ statement of the loop (as GLRTX_CXX_STEP and GLRTX_TRAV_STATS keep the C++ statement of the step).
+#if defined(GLRTX_CXX_STEP) || defined(GLRTX_TRAV_STATS) || defined(GLRTX_PHASE_STATS) || defined(GLRTX_STEP_TIMING) || defined(GLRTX_RAY_LOG) || defined(GLRTX_CXX_LOOP)
+#define GLRTX_TRAV_LOOP_CXX
+#endif
 template <bool VINE, int FETCH>
 DEV void wg_traverse_phase(const KernelArgs &a, const WfArgs &w, const float4 *root, int *stack, const float4 *rq, int n_rays,
                            unsigned *ray_head, unsigned *light_bits, unsigned long long &rays, float4 *suspend_area) {
@@ -2393,11 +2457,15 @@ DEV void wg_traverse_phase(const KernelArgs &a, const WfArgs &w, const float4 *r
         }
         return;
     }
-    const unsigned long long lt_mask = (1ull << lane) - 1ull;
+    [[maybe_unused]] const unsigned long long lt_mask = (1ull << lane) - 1ull;  // (the C++ statement of the loop)
     const float4 none = make_float4(0.f, 0.f, 0.f, __uint_as_float(WF_INVALID));
     float4 cur_o = none, cur_d = none;  // this lane's record of the wave's current chunk
     float cur_ix = 0.f, cur_iy = 0.f, cur_iz = 0.f;  // ... and 1 / direction (:260), computed when the chunk arrives
-    int cur_pos = 0, cur_cnt = 0;       // wave-uniform
+    [[maybe_unused]] int cur_pos = 0;
+    int cur_cnt = 0;                    // wave-uniform (the hand-written loop keeps the position itself)
+#ifndef GLRTX_TRAV_LOOP_CXX
+    float cur_lim = PT_INFTY;           // ... and the search limit its ray starts with
+#endif
     // What a ray needs before its first step -- the three IEEE reciprocals and the test of the root's own box -- is done HERE, once per
     // record with all 64 lanes busy, not at refill time in the few lanes that take a ray: a refill is then seven instructions of setup
     // behind its cross-lane reads.  A ray that misses the root box is marked in the sign of d.w (the light sample's distance: never negative).
@@ -2415,6 +2483,9 @@ DEV void wg_traverse_phase(const KernelArgs &a, const WfArgs &w, const float4 *r
             float t0;
             if (a.sc.root_boxed && !box_pass(root[0], root[1], o.x, o.y, o.z, cur_ix, cur_iy, cur_iz, shadow ? shadow_limit(d.w, a.sc.shadow_limited) : PT_INFTY, t0))
                 d.w = __uint_as_float(__float_as_uint(d.w) | 0x80000000u);
+#ifndef GLRTX_TRAV_LOOP_CXX
+            cur_lim = shadow ? shadow_limit(__builtin_fabsf(d.w), a.sc.shadow_limited) : PT_INFTY;  // what the refill starts tHit at (the loop statement moves it into place)
+#endif
         }
         return cnt;
     };
@@ -2467,6 +2538,45 @@ DEV void wg_traverse_phase(const KernelArgs &a, const WfArgs &w, const float4 *r
         } else *w.H(id) = make_float4(T.h.t, __int_as_float(T.h.tri), T.h.u, T.h.v);  // plain store: scattered 16-byte writes merge in L2 now and then, non-temporal ones never do (-1.2 %)
         unsaved = false;
     };
+#ifndef GLRTX_TRAV_LOOP_CXX
+    // The loop itself is one hand-written statement (trav_loop_asm; trav_asm.hip.h states its rules).  It comes back for what stays C++: the next chunk, the
+    // parking store, the end.  The C++ statement of the same loop follows behind the diagnostic switches; the two are compared on the device
+    // (tests/test_gpu_traverse_loop.py against the megakernel and the CPU oracle; the diagnostic libraries against this one in tools/).
+    static_assert(WF_INVALID == 0xFFFFFFFFu, "trav_asm.hip.h compares a ray id with the inline constant -1");
+    {
+        TravLoop L;
+        L.act = __ballot(active); L.uns = 0ull;
+        L.pos = 0; L.cnt = cur_cnt;
+        L.flags = exhausted ? 1u : 0u;
+        L.rid = rid; L.nr = 0u;
+        const void *const hbase = w.H(0u);
+        const unsigned lb = (unsigned)(uintptr_t)light_bits;
+        const int smax = wgwf_suspend_max();
+        int why;
+        for (;;) {
+            L.co = cur_o; L.cd = cur_d; L.ix = cur_ix; L.iy = cur_iy; L.iz = cur_iz; L.lim = cur_lim;
+            why = trav_loop_asm<FETCH>(a.sc, stack, T, L, w.refill_min, smax, hbase, lb, (unsigned)(uintptr_t)ranks);
+            if (why != 1) break;
+            cur_cnt = cur_cnt == 64 ? fetch(cur_o, cur_d) : 0;  // chunk used up: the next one; a shorter one was the queue's last
+            L.pos = 0; L.cnt = cur_cnt;
+            L.flags = cur_cnt == 0 ? (1u | 2u | (fetched_any ? 4u : 0u)) : 2u;
+        }
+        rid = L.rid;
+        rays += L.nr;
+        active = ((L.act >> lane) & 1ull) != 0ull;
+        unsaved = ((L.uns >> lane) & 1ull) != 0ull;
+        if (why == 2 && active) {  // park (see the C++ loop below)
+            susp[0] = make_float4(T.ox, T.oy, T.oz, __uint_as_float(rid));
+            susp[1] = make_float4(T.dx, T.dy, T.dz, T.stop_d);
+            susp[2] = make_float4(T.h.t, __int_as_float(T.h.tri), T.h.u, T.h.v);
+            susp[3] = make_float4(__int_as_float(T.cur), __int_as_float(T.sp), 1.0f, 0.f);
+            float mark = kHitSuspended, zero = 0.f;
+            asm volatile("" : "+v"(mark), "+v"(zero));
+            *w.H(rid >> 1) = make_float4(mark, zero, zero, zero);
+            active = false;
+        }
+    }
+#else
 #ifdef GLRTX_PHASE_STATS
     unsigned long long ph_refill = 0ull, ph_refills = 0ull, ph_step = 0ull;
 #endif
@@ -2578,6 +2688,7 @@ DEV void wg_traverse_phase(const KernelArgs &a, const WfArgs &w, const float4 *r
         ph_step += __builtin_amdgcn_s_memtime() - sb0;
 #endif
     }
+#endif  // GLRTX_TRAV_LOOP_CXX
     if (unsaved) save_hit();
 #ifdef GLRTX_PHASE_STATS
     // one set of atomics per phase: per-trip atomics on one address (0.4 M per frame) stretched the kernel threefold

@@ -27,6 +27,8 @@
 //     half as many records -- and exchange what the other one needs with one DPP move per dword: 21 selects / moves and 4 address instructions more per step
 //     for a third less time in the pipe.  The arms below run unchanged on the assembled record.
 // ~147 vector + ~22 scalar + ~8 branch instructions per step (pair fetch; ~122 + ~13 without).
+// The loop AROUND the step -- refill, parking test, finished-lane bookkeeping -- is hand-written too (GLRTX_TRAV_LOOP_ASM at the end of this file, with its own
+// figures): 123 instructions in all where the compiler's had ~410, a third fewer scalar instructions per wave-step over the whole kernel, -3.5 to -4.0 % per headline frame.
 //
 // Register use: 24 scratch registers v[GLRTX_VB .. GLRTX_VB+23] with the pair fetch (v96-v119: +16..+22 the partner's pieces in flight, +23 the second
 // address), 22 without.  Of those: 22 scratch registers v[GLRTX_VB .. GLRTX_VB+21] (GLRTX_ASM_VBASE, default 96; clobbered), written below relative to the
@@ -443,6 +445,166 @@ static_assert(GLRTX_STEPS_PER_TRIP % 2 == 0, "the alternating form of the node f
     GLRTX_TS_END                                                                                                                       \
     "v_cmpx_ne_u32_e64 %[act], %[cur], " FIN "\n\t"                        /* the lanes that go on */                                                     \
     "s_cbranch_execz 99f\n\t"
+
+// ---------------------------------------------------------------------------------------------- the loop around the step
+// GLRTX_TRAV_LOOP_ASM: the loop of wg_traverse_phase (pt_kernel.hip.h) -- idle count, refill from the wave's register-held chunk, parking test, stepping
+// block, finished-lane bookkeeping -- as ONE asm statement around the step macros above (trav_loop_asm).  The C++ statement of the same loop stays in
+// wg_traverse_phase behind the diagnostic switches and is what this one is checked against (tests/test_gpu_traverse_loop.py, tests/test_gpu_parity.py).
+//   * the lane sets live as SGPR masks from start to end: %[act] the lanes with a running ray, %[uns] the lanes whose finished ray's record is not written yet;
+//   * the ray and hit registers are the "+&v" operands of the one statement: nothing is copied in or out between blocks;
+//   * a refill reads the chunk records through ds_bpermute_b32 with every lane enabled (a disabled source lane would read as 0) into v[GLRTX_VB+0..10, +12],
+//     and moves them into place under the takers' exec mask; a finished ray's record is written under (takers & %[uns]) just before;
+//   * the statement leaves with %[why] = 0 (nothing runs, queue exhausted), 1 (the chunk is used up: the caller fetches the next one and comes back with
+//     bit 1 of %[flags] set, which resumes INSIDE the refill) or 2 (park: the caller stores the running lanes' state).
+// %[flags]: bit 0 queue exhausted, bit 1 resume inside the refill, bit 2 parking may be considered (exhausted and something was fetched).
+// INVARIANT (the phase cannot spin): every pass from label 70 either runs the stepping block with at least one lane enabled (80 is reached only with
+// %[act] != 0) or leaves the statement; every pass of the refill (72) either takes at least one record (take = min(idle, left) >= 1, %[pos] grows, and
+// %[pos] >= %[cnt] leaves with why = 1) or goes on to 78; and 78 returns to 70 only with the queue not exhausted and no lane running, where 72 follows.
+// Labels: 70 trip, 72 refill, 73 behind the hit store, 74 behind the record writes, 78 behind the refill, 79 parking test, 80 block, 95-98 exits; 10/20/21/30/99 are the step's.
+// Scratch use outside the step: v[GLRTX_VB+13] permute address, +14 rank / LDS address, +15..+21 temporaries (FIN -- +11, compact +22 -- is left alone).
+// Instruction figures (profiles/r32_traverse_loop.txt).  Static, the whole loop outside the step: 46 vector (21 of them v_mov: the 11 record moves, 5 resets,
+// 4 words staged for the store, -inf), 43 scalar, 18 branches, 2 s_waitcnt, 12 ds_bpermute_b32 + 1 ds_or_b32, 1 store = 123; the compiler's version of the same
+// loop had 171 vector (59 v_mov) and ~240 scalar instructions (35 branches, 29 s_waitcnt among them).  Executed, per refill pass: 12 ds_bpermute_b32, 27 vector,
+// ~20 scalar, 6 branches (+ 12 vector, 1 store and 1 LDS atomic when finished rays are written); per block outside the refill: ~12 scalar, 4 branches, nothing
+// vector.  Measured on the headline, whole kernel, per wave-step: vector 189.2 -> 184.5, scalar 39.4 -> 27.2, branches 11.7 -> 10.7, vector memory unchanged.
+#define GLRTX_TRAV_LOOP_ASM(STEPS, FIN, ROOT) \
+    "s_mov_b64 %[entry], exec\n\t" \
+    "s_mov_b64 exec, -1\n\t" \
+    GLRTX_ASM_SET_VBASE \
+    "v_bfrev_b32 " FIN ", 1\n\t" \
+    "s_bitcmp1_b32 %[flags], 1\n\t"                                     /* back from a chunk fetch: go on inside the refill */ \
+    "s_cbranch_scc1 72f\n\t" \
+    "70:\n\t"                                                           /* ---- a trip: refill once refill_min lanes idle or all do */ \
+    "s_cmp_eq_u64 %[act], 0\n\t" \
+    "s_cbranch_scc1 72f\n\t" \
+    "s_not_b64 %[tmp], %[act]\n\t" \
+    "s_bcnt1_i32_b64 %[n], %[tmp]\n\t" \
+    "s_cmp_ge_i32 %[n], %[rmin]\n\t" \
+    "s_cbranch_scc0 79f\n\t" \
+    "72:\n\t"                                                           /* ---- refill: while lanes idle and the queue is not exhausted */ \
+    "s_not_b64 vcc, %[act]\n\t"                                         /* idle lanes (kept in vcc to the end of the pass) */ \
+    "s_cbranch_scc0 78f\n\t" \
+    "s_bitcmp1_b32 %[flags], 0\n\t" \
+    "s_cbranch_scc1 78f\n\t" \
+    "s_cmp_ge_i32 %[pos], %[cnt]\n\t" \
+    "s_cbranch_scc1 97f\n\t"                                            /* chunk used up: the caller fetches */ \
+    "s_bcnt1_i32_b64 %[n], vcc\n\t" \
+    "s_sub_i32 %[take], %[cnt], %[pos]\n\t" \
+    "s_min_i32 %[take], %[take], %[n]\n\t"                              /* records taken in this pass */ \
+    "v_mbcnt_lo_u32_b32 v[GLRTX_VB+14], vcc_lo, 0\n\t"                  /* rank among the idle lanes */ \
+    "v_mbcnt_hi_u32_b32 v[GLRTX_VB+14], vcc_hi, v[GLRTX_VB+14]\n\t" \
+    "v_add_lshl_u32 v[GLRTX_VB+13], v[GLRTX_VB+14], %[pos], 2\n\t"      /* the idle lane of rank r takes record pos + r: held by lane (pos + r) & 63 */ \
+    "v_and_b32 v[GLRTX_VB+13], 0xfc, v[GLRTX_VB+13]\n\t" \
+    "ds_bpermute_b32 v[GLRTX_VB+3], v[GLRTX_VB+13], %[cow]\n\t"         /* ray id first: it is needed first */ \
+    "ds_bpermute_b32 v[GLRTX_VB+7], v[GLRTX_VB+13], %[cdw]\n\t" \
+    "ds_bpermute_b32 v[GLRTX_VB+0], v[GLRTX_VB+13], %[cox]\n\t" \
+    "ds_bpermute_b32 v[GLRTX_VB+1], v[GLRTX_VB+13], %[coy]\n\t" \
+    "ds_bpermute_b32 v[GLRTX_VB+2], v[GLRTX_VB+13], %[coz]\n\t" \
+    "ds_bpermute_b32 v[GLRTX_VB+4], v[GLRTX_VB+13], %[cdx]\n\t" \
+    "ds_bpermute_b32 v[GLRTX_VB+5], v[GLRTX_VB+13], %[cdy]\n\t" \
+    "ds_bpermute_b32 v[GLRTX_VB+6], v[GLRTX_VB+13], %[cdz]\n\t" \
+    "ds_bpermute_b32 v[GLRTX_VB+8], v[GLRTX_VB+13], %[cix]\n\t" \
+    "ds_bpermute_b32 v[GLRTX_VB+9], v[GLRTX_VB+13], %[ciy]\n\t" \
+    "ds_bpermute_b32 v[GLRTX_VB+10], v[GLRTX_VB+13], %[ciz]\n\t" \
+    "ds_bpermute_b32 v[GLRTX_VB+12], v[GLRTX_VB+13], %[clim]\n\t" \
+    "v_cmp_gt_i32_e64 %[leaf], %[take], v[GLRTX_VB+14]\n\t" \
+    "s_and_b64 %[leaf], %[leaf], vcc\n\t"                               /* the takers: idle and rank < take */ \
+    "s_and_b64 exec, %[leaf], %[uns]\n\t"                               /* ---- takers whose finished ray's record is still to be written */ \
+    "s_cbranch_scc0 74f\n\t" \
+    "s_mov_b64 %[br], exec\n\t" \
+    "v_and_b32 v[GLRTX_VB+15], 1, %[rid]\n\t" \
+    "v_cmp_eq_u32_e64 %[bl], 1, v[GLRTX_VB+15]\n\t"                     /* shadow rays among them */ \
+    "v_lshrrev_b32 v[GLRTX_VB+15], 1, %[rid]\n\t"                       /* path id / position in the path queue */ \
+    "s_andn2_b64 exec, exec, %[bl]\n\t"                                 /* path rays: the hit record, one plain 16-byte store */ \
+    "s_cbranch_execz 73f\n\t"                                           /* (none: no store is issued) */ \
+    "v_lshlrev_b32 v[GLRTX_VB+20], 4, v[GLRTX_VB+15]\n\t" \
+    "v_mov_b32 v[GLRTX_VB+16], %[th]\n\t" \
+    "v_mov_b32 v[GLRTX_VB+17], %[tri]\n\t" \
+    "v_mov_b32 v[GLRTX_VB+18], %[hu]\n\t" \
+    "v_mov_b32 v[GLRTX_VB+19], %[hv]\n\t" \
+    "global_store_dwordx4 v[GLRTX_VB+20], v[GLRTX_VB+16:GLRTX_VB+19], %[hbase]\n\t" \
+    "73:\n\t" \
+    "s_and_b64 exec, %[br], %[bl]\n\t"                                  /* shadow rays: the light test (nee_accepted), one bit in LDS */ \
+    "v_sub_f32 v[GLRTX_VB+21], %[sd], %[th]\n\t" \
+    "v_cmp_lt_f32_e64 %[bl], |v[GLRTX_VB+21]|, %[eps]\n\t" \
+    "v_cmp_le_i32_e64 %[br], 0, %[tri]\n\t" \
+    "s_and_b64 %[bl], %[bl], %[br]\n\t" \
+    "s_and_b64 exec, exec, %[bl]\n\t" \
+    "v_lshlrev_b32_e64 v[GLRTX_VB+21], v[GLRTX_VB+15], 1\n\t"           /* 1 << (id & 31) */ \
+    "v_lshrrev_b32 v[GLRTX_VB+14], 5, v[GLRTX_VB+15]\n\t" \
+    "v_lshl_add_u32 v[GLRTX_VB+14], v[GLRTX_VB+14], 2, %[lb]\n\t" \
+    "ds_or_b32 v[GLRTX_VB+14], v[GLRTX_VB+21]\n\t" \
+    "74:\n\t" \
+    "s_andn2_b64 %[uns], %[uns], %[leaf]\n\t" \
+    "s_mov_b64 exec, %[leaf]\n\t"                                       /* ---- the takers take their rays */ \
+    "s_waitcnt lgkmcnt(0)\n\t" \
+    "v_mov_b32 %[rid], v[GLRTX_VB+3]\n\t" \
+    "v_cmpx_ne_u32_e64 %[bl], -1, v[GLRTX_VB+3]\n\t"                    /* WF_INVALID: an entry to skip (the lane stays idle) */ \
+    "v_add_u32 %[nr], 1, %[nr]\n\t" \
+    "v_mov_b32 %[ox], v[GLRTX_VB+0]\n\t" \
+    "v_mov_b32 %[oy], v[GLRTX_VB+1]\n\t" \
+    "v_mov_b32 %[oz], v[GLRTX_VB+2]\n\t" \
+    "v_mov_b32 %[dx], v[GLRTX_VB+4]\n\t" \
+    "v_mov_b32 %[dy], v[GLRTX_VB+5]\n\t" \
+    "v_mov_b32 %[dz], v[GLRTX_VB+6]\n\t" \
+    "v_mov_b32 %[ix], v[GLRTX_VB+8]\n\t" \
+    "v_mov_b32 %[iy], v[GLRTX_VB+9]\n\t" \
+    "v_mov_b32 %[iz], v[GLRTX_VB+10]\n\t" \
+    "v_mov_b32 %[th], v[GLRTX_VB+12]\n\t"                               /* the search limit, worked out at chunk time */ \
+    "v_mov_b32 %[tri], -1\n\t" \
+    "v_mov_b32 %[hu], 0\n\t" \
+    "v_mov_b32 %[hv], 0\n\t" \
+    "v_mov_b32 %[sp], 0\n\t" \
+    "v_mov_b32 %[cur], " ROOT "\n\t" \
+    "v_and_b32 v[GLRTX_VB+15], 1, %[rid]\n\t" \
+    "v_cmp_eq_u32_e64 %[bl], 1, v[GLRTX_VB+15]\n\t"                     /* shadow ray: stop_d = the light sample's distance, else -inf */ \
+    "v_and_b32 v[GLRTX_VB+16], 0x7fffffff, v[GLRTX_VB+7]\n\t" \
+    "v_mov_b32 v[GLRTX_VB+17], 0xff800000\n\t" \
+    "v_cndmask_b32_e64 %[sd], v[GLRTX_VB+17], v[GLRTX_VB+16], %[bl]\n\t" \
+    "v_cmp_le_i32_e64 %[bl], 0, v[GLRTX_VB+7]\n\t"                      /* sign of d.w clear: the root box is entered, the ray runs */ \
+    "s_or_b64 %[act], %[act], %[bl]\n\t" \
+    "s_andn2_b64 %[bl], exec, %[bl]\n\t"                                /* root box missed: the (miss) record is already final */ \
+    "s_or_b64 %[uns], %[uns], %[bl]\n\t" \
+    "s_add_i32 %[pos], %[pos], %[take]\n\t" \
+    "s_mov_b64 exec, -1\n\t" \
+    "s_branch 72b\n\t" \
+    "78:\n\t"                                                           /* ---- behind the refill */ \
+    "s_cmp_eq_u64 %[act], 0\n\t" \
+    "s_cbranch_scc0 79f\n\t" \
+    "s_bitcmp1_b32 %[flags], 0\n\t" \
+    "s_cbranch_scc1 96f\n\t"                                            /* nothing runs and nothing is left */ \
+    "s_branch 70b\n\t" \
+    "79:\n\t"                                                           /* ---- park the last few path rays?  (queue exhausted, something fetched) */ \
+    "s_bitcmp1_b32 %[flags], 2\n\t" \
+    "s_cbranch_scc0 80f\n\t" \
+    "s_mov_b64 exec, %[act]\n\t" \
+    "v_and_b32 v[GLRTX_VB+15], 1, %[rid]\n\t" \
+    "v_cmp_eq_u32_e64 %[bl], 1, v[GLRTX_VB+15]\n\t" \
+    "s_cmp_eq_u64 %[bl], 0\n\t"                                         /* a shadow ray still runs: no */ \
+    "s_cbranch_scc0 80f\n\t" \
+    "s_bcnt1_i32_b64 %[n], %[act]\n\t" \
+    "s_cmp_le_i32 %[n], %[smax]\n\t" \
+    "s_cbranch_scc1 98f\n\t" \
+    "80:\n\t"                                                           /* ---- the stepping block (%[act] != 0) */ \
+    "s_mov_b64 exec, %[act]\n\t" \
+    "s_mov_b64 %[was], %[act]\n\t" \
+    STEPS \
+    "99:\n\t" \
+    "s_andn2_b64 %[tmp], %[was], %[act]\n\t"                            /* finished in this block: their records wait for the refill */ \
+    "s_or_b64 %[uns], %[uns], %[tmp]\n\t" \
+    "s_mov_b64 exec, -1\n\t" \
+    "s_branch 70b\n\t" \
+    "96:\n\t" \
+    "s_mov_b32 %[why], 0\n\t" \
+    "s_branch 95f\n\t" \
+    "97:\n\t" \
+    "s_mov_b32 %[why], 1\n\t" \
+    "s_branch 95f\n\t" \
+    "98:\n\t" \
+    "s_mov_b32 %[why], 2\n\t" \
+    "95:\n\t" \
+    "s_waitcnt vmcnt(0) lgkmcnt(0)\n\t"                                 /* the compiler does not see this statement's stores */ \
+    "s_mov_b64 exec, %[entry]"
 
 #define GLRTX_REP1(X) X
 #define GLRTX_REP2(X) X X
