@@ -308,6 +308,26 @@ const float *glrt_srgb_table(void);
 int glrt_texture_albedo(const float *vert, size_t n_vert, const float *tri, size_t n_tri, const float *mat, size_t n_mat, const glrt_texture *tex, size_t n_tex,
                         const void *texels, size_t texel_bytes, const int32_t *material_texture, const float *hits, size_t n, float *rgb_out);
 
+/* Cutouts: the CPU statements of the device's alpha test (glrtx_bind_cutouts / glrtx_debug_texture_channel, include/glrtx.h "Cutouts": the rule is there), bit
+ * for bit (host/texture.cpp, host/query.cpp, host/features.cpp; tests/cutout_math.py states the lookup in numpy).  glrt_cutout is glrtx_cutout's layout.
+ *   glrt_texture_channel  value_out[i] = channel channel[i] (0 .. 3) of the lookup in texture which[i] at (st[2i], st[2i+1]): channels 0 .. 2 are
+ *                         glrt_texture_lookup's words; channel 3 is the texel's fourth float, or byte / 255.0f for both 8-bit formats, through the same filter.
+ *   glrt_render_features_geom_cutout   glrt_render_features_geom with the set, the per-material bindings and one cutout record a material: the closest-hit
+ *                         search rejects a candidate that would become the closest hit where its material's record says so (value >= cutoff accepts, a
+ *                         NaN rejects; a record with texture -1 cuts nothing), and plane A carries the looked-up albedo of a bound diffuse material, as the
+ *                         device's textured feature kernels write it.  With every record -1 and every binding -1 it is glrt_render_features_geom.
+ *                         glrt_trace_rays and glrt_render_features_geom themselves are unchanged: queries stay geometric.
+ * GLRT_HOST_EINVAL: a NULL pointer with something to read or write, a set glrtx_upload_textures refuses, a cutoff that is not finite, reserved non-zero, a
+ * cutout on a material that is neither diffuse nor conductor.  GLRT_HOST_EINDEX: a texture or channel index out of range, a binding on a material that is not
+ * diffuse; otherwise glrt_render_features_geom's errors. */
+typedef struct glrt_cutout { int32_t texture, channel; float cutoff; int32_t reserved; } glrt_cutout;
+int glrt_texture_channel(const glrt_texture *tex, size_t n_tex, const void *texels, size_t texel_bytes, const int32_t *which, const int32_t *channel, const float *st,
+                         size_t n, float *value_out);
+int glrt_render_features_geom_cutout(const float *vert, size_t n_vert, const float *tri, size_t n_tri, const float *nodes, size_t n_nodes, const float *mat, size_t n_mat,
+                                     const float *c2w, const float *s2c, int width, int height, int rank, int world, int stripe, const glrt_texture *tex, size_t n_tex,
+                                     const void *texels, size_t texel_bytes, const int32_t *material_texture, const glrt_cutout *cut, float *out_n, float *out_a,
+                                     float *out_g);
+
 /* Environment: the CPU statements of the device's environment lighting (glrtx_upload_environment / glrtx_debug_env_*, include/glrtx.h "Environment": the
  * octahedral mapping, its inverse, the solid-angle factor, the importance grid and the sampling rule are there), bit for bit (host/environment.cpp;
  * tests/env_math.py states them in numpy).  glrt_env_cfg is glrtx_env_cfg's layout.  The arithmetic runs with denormals flushed (MXCSR FTZ | DAZ, restored).

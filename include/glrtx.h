@@ -1131,7 +1131,7 @@ int glrtx_debug_normals_burst(glrtx_ctx *ctx, int reps, float *ms_per_launch);
  * FORMATS.  GLRTX_TEX_RGBA32F: four floats a texel.  GLRTX_TEX_RGBA8_UNORM: four bytes, a channel is (float)b / 255.0f (one IEEE quotient).
  *   GLRTX_TEX_RGBA8_SRGB: four bytes, a channel is entry b of a table of 256 floats -- the piecewise sRGB formula (b / 255 <= 0.04045 ? c / 12.92 :
  *   ((c + 0.055) / 1.055) ^ 2.4) evaluated in float64 and rounded once to fp32; the table is stated as constants on each side (glrt_srgb_table), there is no
- *   pow at run time.  Alpha is never read.
+ *   pow at run time.  Alpha is never read by this lookup (a cutout record that names channel 3 reads it: "Cutouts", below).
  * COORDINATES.  A non-finite s or t is 0.  Per axis with N texels and coordinate s:
  *   GLRTX_TEX_REPEAT  x = s - floor(s).       GLRTX_TEX_CLAMP  x = s > 0 ? s : 0, then x = x < 1 ? x : 1.       a = x * (float)N.
  *   GLRTX_TEX_NEAREST   i = (int)floor(a); under repeat i >= N becomes i - N, under clamp i > N - 1 becomes N - 1.
@@ -1312,6 +1312,60 @@ int glrtx_debug_env_eval(const glrtx_texture *map, const void *texels, size_t te
 typedef struct glrtx_material_map { int32_t normal, roughness; float normal_scale; int32_t reserved; } glrtx_material_map; /* 16 bytes; -1: none; reserved 0 */
 int glrtx_bind_material_maps(glrtx_ctx *ctx, const glrtx_material_map *maps, size_t n_mat);
 int glrtx_debug_map_normal(const float *records, size_t n, float scale, float *normal_out);
+
+/* ---- Cutouts: an alpha test on triangle hits, decided INSIDE the closest-hit search (no reference counterpart; off unless called: with no cutouts bound
+ * every launch runs the kernels it ran before).  Leaves, fences, grates and decals are a few quads whose shape lives in one channel of a texture: a material
+ * may be bound to a cutout record {texture, channel, cutoff}, and a candidate hit on such a material counts only where the texture says so.  The decision
+ * cannot be made above the ABI: it is taken per candidate, before the candidate updates the ray's record, in CUT instantiations of the traversal step
+ * (csrc/pt_kernel.hip.h: trav_step<.., CUT>), launched only while cutouts are bound.  PINNED through the reference all the same: a rejected candidate
+ * leaves the traversal exactly as if that piece of surface did not exist, so a cutout texture that is constant over each triangle renders, bit for bit and
+ * ray for ray, the image of the same tree with the rejected triangles collapsed to a point.
+ *
+ * Arithmetic.  As "Textures".  Three statements agree bit for bit: tex_lookup_channel / cut_accepts (csrc/texture.hip.h), glrt_texture_channel
+ * (include/glrt_host.h), tests/cutout_math.py.
+ *
+ * RECORD.   texture: an index into the bound set, or -1 (the material is not cut).  channel: 0 .. 3.  cutoff: a finite float.  reserved: 0.
+ * VALUE.    At a triangle candidate hit (tri, u, v) on a bound material, (s, t) is "Textures"' AT A HIT expression.  The value is the chosen channel of
+ *   the "Textures" lookup at (s, t): channels 0 .. 2 are what the lookup returns, sRGB decode included; channel 3 is the texel's fourth float for
+ *   GLRTX_TEX_RGBA32F and (float)byte / 255.0f for BOTH 8-bit formats (alpha is never sRGB-decoded), filtered by the same FILTER expression, wrap and filter
+ *   as the other channels.
+ * TEST.     The candidate is accepted iff value >= cutoff.  A NaN value rejects.
+ * WHERE.    The candidate is one that passed the triangle test and lies closer than the ray's closest hit so far.  A rejected candidate changes nothing in
+ *   the ray's state: not t, tri, u, v, nor a shadow ray's stop test -- the search goes on as after a miss.  The rule applies to every ray of a launch: path
+ *   rays, shadow rays to triangle lights (with or without the shadow range limit) and shadow rays to the environment.
+ * Analytic spheres have no coordinates and are never cut.  Only diffuse (type 2) and conductor (type 3) materials may be bound: an emitter may not, because
+ *   the light table that next-event estimation samples carries no coordinates.
+ *
+ *   glrtx_bind_cutouts  binds record m to material m.  cut == NULL or n_mat == 0 unbinds.  Needs a bound texture set, which may bind no albedo at all.
+ *                     glrtx_upload_textures and glrtx_upload_scene DROP the records.  They survive glrtx_update_vertices*, glrtx_pose* and
+ *                     glrtx_update_positions*: topology and the frozen coordinate table do not change.  A per-triangle table (the record index, or -1) is
+ *                     built in this call from the triangles' materials: the traversal pays one 4-byte gather for every would-be-closest candidate, and
+ *                     only a cut triangle goes on to its coordinates and the texels.  Seals an open fed launch.
+ *                     GLRTX_EINVAL, everything unchanged, the offender named in the message: no texture set is bound; n_mat other than the scene's material
+ *                     count; an index outside -1 .. n_tex - 1; a channel outside 0 .. 3; a cutoff that is not finite; a bound material that is neither
+ *                     diffuse nor conductor; reserved non-zero; a vine tree (the list scan has no cutout form).
+ *   ROUTING.          While cutouts are bound, launches run on the persistent megakernel (variant_last 1, GLRTX_FALLBACK_EXTENSIONS), in the CUT forms of its
+ *                     textured kernels; glrtx_set_texture_wavefront does not take them.  glrtx_render_adaptive*, glrtx_render_moments,
+ *                     glrtx_render_cascades and glrtx_hit_histogram refuse with "textures are bound" and the reason "cutouts are bound".  Rendering with
+ *                     GLRTX_EXT_VOLUME set and a volume uploaded refuses with "cutouts are bound".  After unbinding everything routes as before, and images
+ *                     are bit for bit what they were.
+ *   Feature pass      with cutouts bound, the textured feature kernels walk with the same CUT step (both node layouts), so planes N, A and G of
+ *                     glrtx_render_features describe the surface the image shows: the denoisers' edge stops and both reprojections follow the holes.
+ *                     glrt_render_features_geom_cutout (include/glrt_host.h) states it.  Without cutouts bound the pass runs the kernels it ran before.
+ *   glrtx_debug_texture_channel  tex_lookup_channel on caller arrays on the current HIP device, no context: value_out[i] = channel channel[i] of
+ *                     lookup(which[i], st[2i], st[2i + 1]).  Refuses what glrtx_debug_texture_lookup refuses, and a channel outside 0 .. 3.
+ * NOT BUILT: stochastic or blended transparency (this is an alpha test only); cutouts in glrtx_trace_rays (queries stay geometric); cutouts on the wavefront
+ *   kernel, whose traversal step is hand-written assembly; cutouts on spheres, emitters, the dielectric, beside the volume, or on a vine tree; alpha read
+ *   from image files (the facade's readers are three-channel: its "cutout" block names r, g or b); mip levels.  Groups: no call; a member is reached through
+ *   glrtx_group_ctx(grp, i). */
+typedef struct glrtx_cutout { int32_t texture, channel; float cutoff; int32_t reserved; } glrtx_cutout; /* 16 bytes; texture -1: none */
+int glrtx_bind_cutouts(glrtx_ctx *ctx, const glrtx_cutout *cut, size_t n_mat);   /* NULL or 0 unbinds */
+int glrtx_debug_texture_channel(const glrtx_texture *tex, size_t n_tex, const void *texels, size_t texel_bytes,
+                                const int32_t *which, const int32_t *channel, const float *st, size_t n, float *value_out);
+/* The name of the render kernel the context's last launch ran, as error reports give it -- "pt_render_persistent (extensions, textures, cutouts)",
+ * "pt_render_wgwf (textures)", ... --, "" before the first launch or for a NULL context.  Diagnostic: the tests name the launched form with it.  The string
+ * is static. */
+const char *glrtx_debug_last_kernel(const glrtx_ctx *ctx);
 
 /* ---- Groups: the same device layer on several GPUs of one node, behind one handle and one host thread.
  * No reference counterpart (the reference is single-GPU); SURVEY.md 8(b) sketches glrtx_create(ctx**, device_ids, n) with a

@@ -17,6 +17,9 @@
 // coordinates into A for a diffuse material bound to a texture -- what the extension kernel shades with.  The material id is unchanged.
 // With material maps bound as well (glrtx_bind_material_maps) MapArgs / MapGeomArgs are the textured arguments, and their store() puts the mapped normal n'
 // (maps.hip.h) into N for a hit whose material is bound to a normal map.
+// With cutouts bound (glrtx_bind_cutouts; include/glrtx.h "Cutouts") CutArgs<Base> is any of the four textured argument types with the cutout tables behind
+// it: the walk is then trav_step<true, COMPACT, false, true> -- the renderer's CUT step --, so the planes describe the surface the image shows, holes included.
+// store() is Base's.  (A vine never gets here: glrtx_bind_cutouts refuses one.)
 // Each form is launched only while what it adds is bound; the instantiations on Args are what is launched otherwise.
 #pragma once
 #include "query.hip.h"
@@ -156,6 +159,16 @@ DEV void store(const MapGeomArgs &q, unsigned id, const Hit &h) {
     store_mapped_normal(q, q.tex, id, h);
 }
 
+// With cutouts bound: Base's arguments and store(), and the tables the CUT step reads (texture.hip.h)
+template <class Base>
+struct CutArgs : Base {
+    CutSet cut;
+};
+template <class A>
+struct is_cut : std::false_type {};
+template <class Base>
+struct is_cut<CutArgs<Base>> : std::true_type {};
+
 // Trees: query::trace_tree's loop with the ray made here.  A: the argument type, which chooses store().  The loop is stated in the kernel template and nowhere
 // else: moved into a body shared by __global__ wrappers, the compiler allocated features_tree<*, Args>' registers differently (the same operations, other
 // register numbers and a slightly different schedule), and that kernel is to keep its instructions (tools/isa_diff.py against a build of the parent shows it).
@@ -235,13 +248,25 @@ __global__ __launch_bounds__(kBlockThreads) void features_tree(const A q) {
             continue;
         }
         if (active) {
-            bool fin = trav_step<true, COMPACT>(q.sc, stack, T, ranks);
+            if constexpr (is_cut<A>::value) {  // cutouts bound: the same trip with the CUT step, which reads the launch's set and tables
+                const CutRef cr{&q.tex, &q.cut};
+                bool fin_cut = trav_step<true, COMPACT, false, true>(q.sc, stack, T, ranks, PT_EPS, &cr);
 #pragma unroll
-            for (int k = 1; k < query::kStepsPerTrip; k++)
-                if (!fin) fin = trav_step<true, COMPACT>(q.sc, stack, T, ranks);
-            if (fin) {
-                active = false;
-                unsaved = true;
+                for (int k = 1; k < query::kStepsPerTrip; k++)
+                    if (!fin_cut) fin_cut = trav_step<true, COMPACT, false, true>(q.sc, stack, T, ranks, PT_EPS, &cr);
+                if (fin_cut) {
+                    active = false;
+                    unsaved = true;
+                }
+            } else {
+                bool fin = trav_step<true, COMPACT>(q.sc, stack, T, ranks);
+#pragma unroll
+                for (int k = 1; k < query::kStepsPerTrip; k++)
+                    if (!fin) fin = trav_step<true, COMPACT>(q.sc, stack, T, ranks);
+                if (fin) {
+                    active = false;
+                    unsaved = true;
+                }
             }
         }
     }

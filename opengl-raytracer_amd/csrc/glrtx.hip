@@ -112,6 +112,12 @@ struct glrtx_ctx {
     DevBuf texMaps;
     bool have_maps = false;
     std::vector<int> tex_format;
+    // Cutouts (glrtx_bind_cutouts; texture.hip.h), the set's until the next glrtx_upload_textures or glrtx_upload_scene: one CutRec a material and tri_cut, the
+    // record index of every device triangle (-1: not cut); have_cut: the CUT instantiations are launched, on the megakernel only.  scene_mat: the material of
+    // every device triangle (record 0 the never-hit one), taken from the triangles glrtx_upload_scene was given -- tri_cut's source, as scene_st is tri_st's.
+    DevBuf cutRec, cutTri;
+    bool have_cut = false;
+    std::vector<int32_t> scene_mat;
     // Environment (glrtx_upload_environment; environment.hip.h), kept across glrtx_upload_scene: the map's texels, the importance grid's five tables, and what the
     // kernels take of it (env: its pointers are these buffers'; p_env is set at every launch).  env_cfg / env_desc: what it was made from.
     DevBuf envTexels, envRowQ, envRowAlias, envColQ, envColAlias, envCellP;
@@ -1033,6 +1039,7 @@ bool tex_wavefront(const glrtx_ctx *c, const char **why_not = nullptr) {
     bool on = c->tex_wavefront;
     if (const char *v = std::getenv("GLRTX_TEXTURE_WAVEFRONT")) on = std::atoi(v) != 0;
     const char *why = c->n_tex == 0 ? "no set is bound"
+                      : c->have_cut ? "cutouts are bound (the wavefront kernel's traversal step has no cutout form)"
                       : !on ? "the texture wavefront switch is off (glrtx_set_texture_wavefront)"
                       : c->ext_flags != 0 ? "extensions or volume are on"
                       : c->n_spheres > 0 ? "spheres are uploaded"
@@ -1433,31 +1440,42 @@ int wgwf_kernel(glrtx_ctx *c, WgwfLaunch &L) {
 
 // ---- the persistent megakernel (variant 1: render_one): its instantiation and its grid, then the launch.  The ten forms of pt_render_persistent that exist,
 // each with and without ray counting: one table.
-enum PersistForm { kFormPlain, kFormExt, kFormVol, kFormTex, kFormTexVol, kFormTexMaps, kFormTexVolMaps, kFormEnv, kFormEnvTex, kFormEnvTexMaps, kPersistForms };
+enum PersistForm { kFormPlain, kFormExt, kFormVol, kFormTex, kFormTexVol, kFormTexMaps, kFormTexVolMaps, kFormEnv, kFormEnvTex, kFormEnvTexMaps,
+                   kFormTexCut, kFormTexMapsCut, kFormEnvTexCut, kFormEnvTexMapsCut, kPersistForms };
 #define GLRTX_PERSIST_ROW(EXT, VOL, TEX, ENV, MAPS) \
     {(const void *)pt_render_persistent<false, EXT, VOL, TEX, ENV, MAPS>, (const void *)pt_render_persistent<true, EXT, VOL, TEX, ENV, MAPS>}
-const void *const kPersistent[kPersistForms][2] = {  // [form][count_rays]; the fourth argument is a VolArgs, in the kFormEnv* rows an EnvArgs
+#define GLRTX_PERSIST_CUT_ROW(ENV, MAPS) \
+    {(const void *)pt_render_persistent<false, true, false, true, ENV, MAPS, true>, (const void *)pt_render_persistent<true, true, false, true, ENV, MAPS, true>}
+// [form][count_rays]; the fourth argument is a VolArgs, in the kFormEnv* rows an EnvArgs, in the k*Cut rows a CutTail of either (include/glrtx.h "Cutouts")
+const void *const kPersistent[kPersistForms][2] = {
     GLRTX_PERSIST_ROW(false, false, false, false, false), GLRTX_PERSIST_ROW(true, false, false, false, false), GLRTX_PERSIST_ROW(true, true, false, false, false),
     GLRTX_PERSIST_ROW(true, false, true, false, false),   GLRTX_PERSIST_ROW(true, true, true, false, false),   GLRTX_PERSIST_ROW(true, false, true, false, true),
     GLRTX_PERSIST_ROW(true, true, true, false, true),     GLRTX_PERSIST_ROW(true, false, false, true, false),  GLRTX_PERSIST_ROW(true, false, true, true, false),
-    GLRTX_PERSIST_ROW(true, false, true, true, true)};
+    GLRTX_PERSIST_ROW(true, false, true, true, true),
+    GLRTX_PERSIST_CUT_ROW(false, false), GLRTX_PERSIST_CUT_ROW(false, true), GLRTX_PERSIST_CUT_ROW(true, false), GLRTX_PERSIST_CUT_ROW(true, true)};
 #undef GLRTX_PERSIST_ROW
+#undef GLRTX_PERSIST_CUT_ROW
 constexpr const char *kPersistentNames[kPersistForms] = {  // (error reports)
     "pt_render_persistent", "pt_render_persistent (extensions)", "pt_render_persistent (volume)", "pt_render_persistent (extensions, textures)",
     "pt_render_persistent (volume, textures)", "pt_render_persistent (extensions, textures, maps)", "pt_render_persistent (volume, textures, maps)",
     "pt_render_persistent (extensions, environment)", "pt_render_persistent (extensions, environment, textures)",
-    "pt_render_persistent (extensions, environment, textures, maps)"};
-struct PersistLaunch { const void *fn; const char *name; bool vol, env; int lds, grid; ExtArgs ex; };
+    "pt_render_persistent (extensions, environment, textures, maps)",
+    "pt_render_persistent (extensions, textures, cutouts)", "pt_render_persistent (extensions, textures, maps, cutouts)",
+    "pt_render_persistent (extensions, environment, textures, cutouts)", "pt_render_persistent (extensions, environment, textures, maps, cutouts)"};
+struct PersistLaunch { const void *fn; const char *name; bool vol, env, cut; int lds, grid; ExtArgs ex; };
 
 // ext: render_one's (spheres, an extension flag, a texture set that is not the wavefront kernel's, an environment); lds: the plain kernel's LDS bytes
 int persist_kernel(glrtx_ctx *c, bool ext, int lds, PersistLaunch &k) {
     const bool tex = c->n_tex > 0, maps = tex && c->have_maps;  // (maps: bound on top of the set, glrtx_bind_material_maps; without them the TEX forms as ever)
     k.vol = (c->ext_flags & GLRTX_EXT_VOLUME) != 0;  // (render_one has checked that a volume is uploaded, and that no environment is bound beside it)
     k.env = c->have_env;
-    const int form = k.env ? (maps ? kFormEnvTexMaps : tex ? kFormEnvTex : kFormEnv)
+    k.cut = tex && c->have_cut;  // (render_one has refused GLRTX_EXT_VOLUME beside bound cutouts)
+    const int form = k.cut ? (k.env ? kFormEnvTexCut : kFormTexCut) + (maps ? 1 : 0)
+                     : k.env ? (maps ? kFormEnvTexMaps : tex ? kFormEnvTex : kFormEnv)
                      : tex ? kFormTex + (k.vol ? 1 : 0) + (maps ? 2 : 0)
                            : k.vol ? kFormVol : ext ? kFormExt : kFormPlain;
     static_assert(kFormTexVol == kFormTex + 1 && kFormTexMaps == kFormTex + 2 && kFormTexVolMaps == kFormTex + 3, "the TEX rows: [maps][volume]");
+    static_assert(kFormTexMapsCut == kFormTexCut + 1 && kFormEnvTexMapsCut == kFormEnvTexCut + 1, "the CUT rows: [environment][maps]");
     k.fn = kPersistent[form][c->count_rays];
     k.name = kPersistentNames[form];
     k.ex = ExtArgs{};
@@ -1486,7 +1504,12 @@ int persist_launch(glrtx_ctx *c, const PersistLaunch &k, const KernelArgs &a, hi
     const VolArgs va = k.vol ? c->vol : VolArgs{};  // the fourth argument: the volume's, or (kFormEnv*) the environment's
     EnvArgs ea = c->env;
     if (k.env) ea.p_env = c->sc.n_light == 0 ? 1.0f : c->env_cfg.light_pick;  // a scene without lights: the environment is the only light to pick
-    void *args[] = {(void *)&a, &work, (void *)&k.ex, k.env ? (void *)&ea : (void *)&va};
+    // the CUT forms: the same fourth argument with the cutout tables appended behind it (pt_kernel.hip.h: CutTail)
+    const CutSet cs{(const int *)c->cutTri.p, (const CutRec *)c->cutRec.p};
+    const CutTail<VolArgs> va_cut{va, cs};
+    const CutTail<EnvArgs> ea_cut{ea, cs};
+    void *const tail = k.cut ? (k.env ? (void *)&ea_cut : (void *)&va_cut) : (k.env ? (void *)&ea : (void *)&va);
+    void *args[] = {(void *)&a, &work, (void *)&k.ex, tail};
     HIP_TRY(c, hipLaunchKernel(k.fn, dim3(k.grid), dim3(kBlockThreads), args, k.lds, c->stream));
     return GLRTX_OK;
 }
@@ -2342,7 +2365,7 @@ void glrtx_destroy(glrtx_ctx *c) {
         for (auto &ch : sl.chunks) dev_free(ch);
         if (sl.feed_h) (void)hipHostFree(sl.feed_h);
     }
-    dev_free(c->texDesc); dev_free(c->texTexels); dev_free(c->texSt); dev_free(c->texBind); dev_free(c->texMaps);
+    dev_free(c->texDesc); dev_free(c->texTexels); dev_free(c->texSt); dev_free(c->texBind); dev_free(c->texMaps); dev_free(c->cutRec); dev_free(c->cutTri);
     for (DevBuf *b : {&c->envTexels, &c->envRowQ, &c->envRowAlias, &c->envColQ, &c->envColAlias, &c->envCellP}) dev_free(*b);
     dev_free(c->spheres); dev_free(c->sphereMat); dev_free(c->volDensity); dev_free(c->volTemp); dev_free(c->forks); dev_free(c->cnodes); dev_free(c->cranks); dev_free(c->nrms); dev_free(c->mats); dev_free(c->lights); dev_free(c->vine);
     dev_free(c->accum_own); dev_free(c->counter); dev_free(c->rgba8); dev_free(c->work);
@@ -2445,6 +2468,9 @@ int glrtx_upload_scene(glrtx_ctx *c, const float *vert, size_t n_vert, const flo
     c->n_spheres = 0;  // spheres reference this scene's materials: upload them again after a new scene
     c->n_tex = 0;      // ... and so does a texture set's binding (glrtx_upload_textures)
     c->have_maps = false;  // ... and the material maps bound on top of it (glrtx_bind_material_maps)
+    c->have_cut = false;   // ... and the cutout records (glrtx_bind_cutouts)
+    c->scene_mat.assign(c->leaf_tri.size() + 1, -1);  // the material of every device triangle: word 3 of a wire triangle
+    for (size_t k = 0; k < c->leaf_tri.size(); k++) c->scene_mat[k + 1] = (int32_t)tri[4 * (size_t)c->leaf_tri[k] + 3];
     c->scene_st.assign(6 * (c->leaf_tri.size() + 1), 0.0f);  // the corners' (s, t) of every device triangle: words 6 and 7 of a wire vertex
     for (size_t k = 0; k < c->leaf_tri.size(); k++)
         for (int j = 0; j < 3; j++) {
@@ -3278,6 +3304,7 @@ int glrtx_upload_textures(glrtx_ctx *c, const glrtx_texture *tex, size_t n_tex, 
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         c->n_tex = 0;
         c->have_maps = false;
+        c->have_cut = false;
         return GLRTX_OK;
     }
     if (n_mat != (size_t)c->n_mat) return fail(c, GLRTX_EINVAL, "%s: %zu bindings, the scene has %d materials", fn, n_mat, c->n_mat);
@@ -3309,6 +3336,7 @@ int glrtx_upload_textures(glrtx_ctx *c, const glrtx_texture *tex, size_t n_tex, 
     }
     dev_free(c->texDesc); dev_free(c->texTexels); dev_free(c->texSt); dev_free(c->texBind);
     c->have_maps = false;  // (glrtx_bind_material_maps: a new set invalidates the indices)
+    c->have_cut = false;   // (glrtx_bind_cutouts: likewise)
     c->tex_format.resize(n_tex);
     for (size_t k = 0; k < n_tex; k++) c->tex_format[k] = tex[k].format;
     c->texDesc = d; c->texTexels = t; c->texSt = st; c->texBind = b;
@@ -3402,6 +3430,87 @@ int glrtx_debug_map_normal(const float *records, size_t n, float scale, float *n
     }
     s.sync();
     s.download(normal_out, d_out, 3 * n * sizeof(float));
+    return s.result(GLRTX_OK, fn);
+}
+
+// ---- cutouts (include/glrtx.h "Cutouts"; texture.hip.h: cut_accepts, pt_kernel.hip.h: trav_step<.., CUT>)
+static_assert(sizeof(glrtx_cutout) == sizeof(CutRec) && sizeof(CutRec) == 16, "one cutout record on the wire and the device");
+
+int glrtx_bind_cutouts(glrtx_ctx *c, const glrtx_cutout *cut, size_t n_mat) {
+    const char *fn = "glrtx_bind_cutouts";
+    if (!c) return GLRTX_EINVAL;
+    seal_feed(c);  // (nothing is appended to an open launch across this call: glrtx_ctx::OpenFeed)
+    if (!cut || n_mat == 0) {  // unbind: the next launch is routed as before (the buffers stay until the context goes)
+        HIP_TRY(c, hipSetDevice(c->device));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        c->have_cut = false;
+        return GLRTX_OK;
+    }
+    if (!c->have_scene || c->n_tex == 0) return fail(c, GLRTX_EINVAL, "%s: no texture set is bound (call glrtx_upload_textures first)", fn);
+    if (n_mat != (size_t)c->n_mat) return fail(c, GLRTX_EINVAL, "%s: %zu records, the scene has %d materials", fn, n_mat, c->n_mat);
+    if (c->sc.n_vine > 0) return fail(c, GLRTX_EINVAL, "%s: the tree is a vine (the list scan has no cutout form)", fn);
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));  // (also behind every launch that reads the materials or the records bound before)
+    std::vector<float4> m0(3 * n_mat);
+    HIP_TRY(c, hipMemcpy(m0.data(), c->mats.p, m0.size() * sizeof(float4), hipMemcpyDeviceToHost));
+    for (size_t m = 0; m < n_mat; m++) {
+        const glrtx_cutout &r = cut[m];
+        int type;
+        std::memcpy(&type, &m0[3 * m].w, 4);
+        if (r.texture < -1 || r.texture >= c->n_tex) return fail(c, GLRTX_EINVAL, "%s: material %zu: cutout texture %d of %d textures", fn, m, r.texture, c->n_tex);
+        if (r.channel < 0 || r.channel > 3) return fail(c, GLRTX_EINVAL, "%s: material %zu: channel %d is not 0 .. 3", fn, m, r.channel);
+        if (!std::isfinite(r.cutoff)) return fail(c, GLRTX_EINVAL, "%s: material %zu: cutoff is not finite", fn, m);
+        if (r.texture >= 0 && type != 2 && type != 3)
+            return fail(c, GLRTX_EINVAL, "%s: material %zu has a cutout and is neither diffuse nor conductor (type %d)", fn, m, type);
+        if (r.reserved != 0) return fail(c, GLRTX_EINVAL, "%s: material %zu: reserved is %d, not 0", fn, m, r.reserved);
+    }
+    // tri_cut: the record index of every device triangle, -1 where its material is not cut (record 0: the never-hit triangle)
+    std::vector<int32_t> tri_cut(c->scene_mat.size(), -1);
+    for (size_t t = 1; t < tri_cut.size(); t++) {
+        const int32_t m = c->scene_mat[t];
+        if (m >= 0 && (size_t)m < n_mat && cut[m].texture >= 0) tri_cut[t] = m;
+    }
+    DevBuf b, tc;  // fresh buffers first: a failure leaves the bound records as they were
+    int rc;
+    if ((rc = dev_upload(c, b, cut, n_mat * sizeof(glrtx_cutout))) || (rc = dev_upload(c, tc, tri_cut.data(), tri_cut.size() * sizeof(int32_t)))) {
+        dev_free(b); dev_free(tc);
+        return rc;
+    }
+    dev_free(c->cutRec); dev_free(c->cutTri);
+    c->cutRec = b; c->cutTri = tc;
+    c->have_cut = true;
+    return GLRTX_OK;
+}
+
+const char *glrtx_debug_last_kernel(const glrtx_ctx *c) { return c ? c->last_kernel : ""; }
+
+int glrtx_debug_texture_channel(const glrtx_texture *tex, size_t n_tex, const void *texels, size_t texel_bytes, const int32_t *which, const int32_t *channel,
+                                const float *st, size_t n, float *value_out) {
+    const char *fn = "glrtx_debug_texture_channel";
+    if (n_tex == 0 || (n && (!which || !channel || !st || !value_out))) return fail(nullptr, GLRTX_EINVAL, "%s: NULL buffer or no texture", fn);
+    if (n > (size_t)INT32_MAX / 4) return fail(nullptr, GLRTX_EINVAL, "%s: too many lookups", fn);
+    const std::string bad = glrt_detail::texture_set_error(reinterpret_cast<const glrt_detail::TexRecord *>(tex), n_tex, texels, texel_bytes);
+    if (!bad.empty()) return fail(nullptr, GLRTX_EINVAL, "%s: %s", fn, bad.c_str());
+    for (size_t i = 0; i < n; i++) {
+        if (which[i] < 0 || (size_t)which[i] >= n_tex) return fail(nullptr, GLRTX_EINVAL, "%s: lookup %zu names texture %d of %zu", fn, i, which[i], n_tex);
+        if (channel[i] < 0 || channel[i] > 3) return fail(nullptr, GLRTX_EINVAL, "%s: lookup %zu names channel %d, not 0 .. 3", fn, i, channel[i]);
+    }
+    if (n == 0) return GLRTX_OK;
+    DebugScratch s;
+    TexSet ts{};
+    ts.desc = s.alloc<TexDesc>(n_tex * sizeof(glrtx_texture), tex);
+    ts.texels = s.alloc<unsigned char>(texel_bytes, texels);
+    ts.n_tex = (int)n_tex;
+    const int *d_which = s.alloc<int>(n * sizeof(int), which);
+    const int *d_channel = s.alloc<int>(n * sizeof(int), channel);
+    const float *d_st = s.alloc<float>(2 * n * sizeof(float), st);
+    float *d_out = s.alloc<float>(n * sizeof(float));
+    if (s.ok()) {
+        hipLaunchKernelGGL(tex_channel_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, ts, d_which, d_channel, d_st, (unsigned)n, d_out);
+        s.e = hipGetLastError();
+    }
+    s.sync();
+    s.download(value_out, d_out, n * sizeof(float));
     return s.result(GLRTX_OK, fn);
 }
 
@@ -4000,7 +4109,7 @@ int glrtx_render_features(glrtx_ctx *c, const glrtx_params *p) {
     if (const char *v = std::getenv("GLRTX_COMPACT_NODES")) compact = std::atoi(v) != 0 && !vine && c->sc.n_crank > 0;
     compact = compact && lds_stack + lds_ranks <= 160 * 1024;
     const bool tex = c->n_tex > 0, maps = tex && c->have_maps;
-    // One launch over the argument type: q, one of features.hip.h's six, selects the tree kernel's instantiation (the vine kernel comes by name) and is filled with what its type adds to Args --
+    // One launch over the argument type: q, one of features.hip.h's six (or, with cutouts bound, a CutArgs of one of the four textured ones), selects the tree kernel's instantiation (the vine kernel comes by name) and is filled with what its type adds to Args --
     // G and the wire table (glrtx_track_motion), the texture set (plane A carries the looked-up albedo; as Map*Args, plane N the mapped normal).
     const auto launch = [&](auto q, void (*vine_kernel)(const decltype(q))) -> int {
         using A = decltype(q);
@@ -4022,6 +4131,7 @@ int glrtx_render_features(glrtx_ctx *c, const glrtx_params *p) {
         a.counter = (unsigned *)c->ftCounter.p;
         if constexpr (std::is_base_of_v<features::GeomArgs, A>) { q.out_g = (float4 *)c->ftG.p; q.wire = (const int *)c->qwire.p; }
         if constexpr (std::is_base_of_v<features::TexArgs, A> || std::is_base_of_v<features::TexGeomArgs, A>) q.tex = tex_set(c);
+        if constexpr (features::is_cut<A>::value) q.cut = CutSet{(const int *)c->cutTri.p, (const CutRec *)c->cutRec.p};
         std::memcpy(c->ft_cam, a.cam, sizeof c->ft_cam);  // (glrtx_reproject: the camera these planes belong to)
         const size_t needed = (a.n + kBlockThreads - 1) / kBlockThreads;
         const unsigned grid = (unsigned)std::max<size_t>(1, std::min<size_t>((size_t)per_cu * (size_t)c->n_cu, needed));
@@ -4030,6 +4140,11 @@ int glrtx_render_features(glrtx_ctx *c, const glrtx_params *p) {
         HIP_TRY(c, hipGetLastError());
         return planes_written();
     };
+    if (tex && c->have_cut && !vine) {  // cutouts bound (never on a vine: glrtx_bind_cutouts): the same arguments and planes, walked with the CUT step
+        using namespace features;
+        if (maps) return geom ? launch(CutArgs<MapGeomArgs>{}, nullptr) : launch(CutArgs<MapArgs>{}, nullptr);
+        return geom ? launch(CutArgs<TexGeomArgs>{}, nullptr) : launch(CutArgs<TexArgs>{}, nullptr);
+    }
     if (maps) return geom ? launch(features::MapGeomArgs{}, features::features_vine_geom_maps) : launch(features::MapArgs{}, features::features_vine_maps);
     if (tex) return geom ? launch(features::TexGeomArgs{}, features::features_vine_geom_tex) : launch(features::TexArgs{}, features::features_vine_tex);
     return geom ? launch(features::GeomArgs{}, features::features_vine_geom) : launch(features::Args{}, features::features_vine);
@@ -4774,6 +4889,8 @@ static int render_one(glrtx_ctx *c, const glrtx_params *p, const RenderReq &req)
     if ((c->ext_flags & GLRTX_EXT_VOLUME) && !c->have_volume) return fail(c, GLRTX_EINVAL, "glrtx_render: GLRTX_EXT_VOLUME is set and no volume is uploaded (glrtx_upload_volume)");
     if ((c->ext_flags & GLRTX_EXT_VOLUME) && c->have_env)
         return fail(c, GLRTX_EINVAL, "glrtx_render: GLRTX_EXT_VOLUME is set and an environment is bound (the volume branch has its own escape path)");
+    if ((c->ext_flags & GLRTX_EXT_VOLUME) && c->have_volume && c->n_tex > 0 && c->have_cut)
+        return fail(c, GLRTX_EINVAL, "glrtx_render: GLRTX_EXT_VOLUME is set and cutouts are bound (the volume kernels have no cutout form)");
     HIP_TRY(c, hipSetDevice(c->device));
     const bool wavefront = wgwf_routes(c, p);
     if (c->owned_rows > 0 && wavefront && req.kind == RenderReq::Ordinary && req.n_frames == 1 && feed_append(c, p, p->seed, 1) == 1) {  // a launch of the same camera that is still open takes the frame itself
@@ -4945,6 +5062,7 @@ int glrtx_hit_histogram(glrtx_ctx *c, const glrtx_params *p, uint32_t *hist_out,
     if (!c->have_scene) return fail(c, GLRTX_EINVAL, "glrtx_hit_histogram: no scene uploaded");
     if (!c->accum || c->width < 1 || c->owned_rows < 1) return fail(c, GLRTX_EINVAL, "glrtx_hit_histogram: no image size (call glrtx_resize)");
     if (n_tri != (size_t)c->n_tri) return fail(c, GLRTX_EINVAL, "glrtx_hit_histogram: the scene has %d triangles, room for %zu", c->n_tri, n_tri);
+    if (c->n_tex > 0 && c->have_cut) return fail(c, GLRTX_EINVAL, "glrtx_hit_histogram: textures are bound and cutouts are bound (wavefront kernel only)");
     if (c->n_tex > 0) return fail(c, GLRTX_EINVAL, "glrtx_hit_histogram: textures are bound (wavefront kernel only)");
     if (c->have_env) return fail(c, GLRTX_EINVAL, "glrtx_hit_histogram: an environment is bound (wavefront kernel only)");
     if (c->variant != 2 || !wgwf_can_hold(p) || c->n_spheres > 0 || c->ext_flags != 0) return fail(c, GLRTX_EINVAL, "glrtx_hit_histogram: wavefront kernel only");

@@ -453,8 +453,11 @@ DEV bool trav_init(const DevScene &sc, const float4 *root, Trav &T, float ox, fl
 // three 16-byte pieces of the record carry the right child's far corner in their spare words.  Same boxes, same triangles, same order.
 // ANY and tmin serve the ray queries alone (query.hip.h): a hit needs t > tmin instead of t > EPS, and with ANY the ray ends at its first accepted hit.  The
 // renderer's instantiations take the defaults, which are its own constants: the same instructions as before.
-template <bool CLOSEST, bool COMPACT = false, bool ANY = false>
-DEV bool trav_step(const DevScene &sc, int *stack, Trav &T, const uint2 *ranks = nullptr, float tmin = PT_EPS) {
+// CUT (include/glrtx.h "Cutouts"; cut: the launch's texture set and cutout tables): a candidate that would become the ray's closest hit is looked up in its
+// material's cutout texture first (cut_accepts, texture.hip.h), and a rejected one leaves the ray's state as if the triangle had been missed.  Only the CUT
+// forms of the extension megakernel and of the textured feature kernels instantiate it; every other instantiation takes the default and is the code it was.
+template <bool CLOSEST, bool COMPACT = false, bool ANY = false, bool CUT = false>
+DEV bool trav_step(const DevScene &sc, int *stack, Trav &T, const uint2 *ranks = nullptr, float tmin = PT_EPS, const CutRef *cut = nullptr) {
 #ifdef GLRTX_TRAV_STATS
     trav_stats_iter(T.cur, (const void *)(sc.forks + 4 * (ptrdiff_t)T.cur), T.stop_d == -__builtin_inff(), T.sp);
     T.iters++;
@@ -538,7 +541,10 @@ DEV bool trav_step(const DevScene &sc, int *stack, Trav &T, const uint2 *ranks =
         const bool hit = !(-PT_EPS < det && det < PT_EPS) && !(u < 0.0f || 1.0f < u) &&
                          !(v < 0.0f || 1.0f < inv * (U + V)) &&  // u+v>1 is evaluated as inv*(U+V)>1
                          !(tmin >= tt);
-        const bool closer = hit && tt < T.h.t;  // strict: among equal distances the first one visited wins (:325)
+        bool closer = hit && tt < T.h.t;  // strict: among equal distances the first one visited wins (:325)
+        if constexpr (CUT) {  // the step's own u, v: a shadow ray keeps none in its record
+            if (closer) closer = cut_accepts(*cut, t, u, v);
+        }
         T.h.tri = closer ? t : T.h.tri;
         if (CLOSEST) { T.h.u = closer ? u : T.h.u; T.h.v = closer ? v : T.h.v; }
         T.h.t = closer ? tt : T.h.t;  // == hit ? min(tHit, tt) : tHit (a NaN tt is never closer)
@@ -866,12 +872,17 @@ DEV Hit trav_scan(const DevScene &sc, float ox, float oy, float oz, float dx, fl
     return h;
 }
 
-template <bool CLOSEST>
+template <bool CLOSEST, bool CUT = false>
 DEV Hit traverse(const DevScene &sc, int *stack, float ox, float oy, float oz, float dx, float dy, float dz,
-                 float limit = PT_INFTY, float stop_d = -__builtin_inff()) {
+                 float limit = PT_INFTY, float stop_d = -__builtin_inff(), const CutRef *cut = nullptr) {
     Trav T;
-    if (trav_init(sc, &sc.root_lo, T, ox, oy, oz, dx, dy, dz, limit, stop_d))
-        while (!trav_step<CLOSEST>(sc, stack, T)) {}
+    if (trav_init(sc, &sc.root_lo, T, ox, oy, oz, dx, dy, dz, limit, stop_d)) {
+        if constexpr (CUT) {
+            while (!trav_step<CLOSEST, false, false, true>(sc, stack, T, nullptr, PT_EPS, cut)) {}
+        } else {
+            while (!trav_step<CLOSEST>(sc, stack, T)) {}
+        }
+    }
     return T.h;
 }
 
@@ -1390,10 +1401,10 @@ DEV float sphere_t(float4 sp, float ox, float oy, float oz, float dx, float dy, 
 // Closest hit over triangles (the reference traversal) and spheres; Hit::tri >= 0 triangle, -2 - k sphere k, -1 miss.
 // The spheres are staged into LDS at kernel start (ext_stage_spheres): the scan reads them with a wave-uniform ds_read_b128 each --
 // "scene primitives staged into LDS" as BASELINE.json's north_star words it.
-template <bool CLOSEST>
+template <bool CLOSEST, bool CUT = false>
 DEV Hit traverse_ext(const DevScene &sc, const ExtArgs &ex, const float4 *lds_spheres, int *stack, float ox, float oy, float oz, float dx, float dy, float dz,
-                     float limit = PT_INFTY, float stop_d = -__builtin_inff()) {
-    Hit h = traverse<CLOSEST>(sc, stack, ox, oy, oz, dx, dy, dz, limit, stop_d);
+                     float limit = PT_INFTY, float stop_d = -__builtin_inff(), const CutRef *cut = nullptr) {
+    Hit h = traverse<CLOSEST, CUT>(sc, stack, ox, oy, oz, dx, dy, dz, limit, stop_d, cut);  // (spheres have no coordinates and are never cut)
     const lds_cf4 q = (lds_cf4)lds_spheres;
     for (int k = 0; k < ex.n_spheres; k++) {
         const float t = sphere_t(to_f4(q[k]), ox, oy, oz, dx, dy, dz);
@@ -1531,11 +1542,16 @@ DEV bool bounce_volume(const KernelArgs &a, const ExtArgs &ex, const VolArgs &vo
     return P.depth >= a.max_depth;
 }
 
-template <bool VOL = false, bool TEX = false, bool ENV = false, bool MAPS = false>
+// CUT (include/glrtx.h "Cutouts"; cs: the bound cutout tables): all three rays -- the path's, the shadow ray to a triangle light, the shadow ray to the
+// environment -- are traced with the CUT step.  Shading is the TEX forms' as it is: a rejected candidate was never a hit.
+template <bool VOL = false, bool TEX = false, bool ENV = false, bool MAPS = false, bool CUT = false>
 DEV bool bounce_ext(const KernelArgs &a, const ExtArgs &ex, const float4 *lds_spheres, const float4 *lds_mats, int *stack, Rng &rng, Path &P, unsigned long long &rays,
-                    const VolArgs *vo = nullptr, const EnvArgs *env = nullptr) {
+                    const VolArgs *vo = nullptr, const EnvArgs *env = nullptr, const CutSet *cs = nullptr) {
     static_assert(!(ENV && VOL), "the volume branch has its own escape path: no environment beside it");
-    const Hit h = traverse_ext<true>(a.sc, ex, lds_spheres, stack, P.ox, P.oy, P.oz, P.dx, P.dy, P.dz);
+    static_assert(!CUT || (TEX && !VOL), "cutouts read the texture set; none beside the volume");
+    const CutRef cut_ref{&ex.tex, cs};
+    const CutRef *const cut = CUT ? &cut_ref : nullptr;
+    const Hit h = traverse_ext<true, CUT>(a.sc, ex, lds_spheres, stack, P.ox, P.oy, P.oz, P.dx, P.dy, P.dz, PT_INFTY, -__builtin_inff(), cut);
     rays++;
     Surf S;
     S.nx = S.ny = S.nz = 0.f; S.mtrl = 0;
@@ -1594,11 +1610,11 @@ DEV bool bounce_ext(const KernelArgs &a, const ExtArgs &ex, const float4 *lds_sp
     }
     bool ok = false;
     if (ENV && sh.has_shadow && sh.env_shadow) {  // towards the environment: any hit at all (spheres included) occludes -- the inverse of nee_accepted
-        const Hit s = traverse_ext<false>(a.sc, ex, lds_spheres, stack, P.ox, P.oy, P.oz, sh.sdx, sh.sdy, sh.sdz, PT_INFTY, PT_INFTY);
+        const Hit s = traverse_ext<false, CUT>(a.sc, ex, lds_spheres, stack, P.ox, P.oy, P.oz, sh.sdx, sh.sdy, sh.sdz, PT_INFTY, PT_INFTY, cut);
         rays++;
         ok = s.tri == -1;
     } else if (sh.has_shadow) {
-        const Hit s = traverse_ext<false>(a.sc, ex, lds_spheres, stack, P.ox, P.oy, P.oz, sh.sdx, sh.sdy, sh.sdz, shadow_limit(sh.dist, a.sc.shadow_limited), sh.dist);
+        const Hit s = traverse_ext<false, CUT>(a.sc, ex, lds_spheres, stack, P.ox, P.oy, P.oz, sh.sdx, sh.sdy, sh.sdz, shadow_limit(sh.dist, a.sc.shadow_limited), sh.dist, cut);
         rays++;
         ok = nee_accepted(sh.dist, s.t, s.tri != -1);
     } else if (sh.untraced) {
@@ -1763,7 +1779,15 @@ constexpr int kChunk = 256;
 // The kernel's by-value arguments as they lie in the kernarg segment.  The loop below reads its launch constants from there, through a
 // pointer the compiler cannot see through and takes anew in every trip, instead of from the by-value copies: those are loaded once at
 // kernel entry and stay live -- in ~100 scalar registers, most of them spilled to vector lanes -- across the traversal loops.
-// Tail: the volume's arguments, or the environment's in their place (the two do not combine).
+// Tail: the volume's arguments, or the environment's in their place (the two do not combine); in the CUT forms a CutTail of either -- the cutout tables
+// appended BEHIND it, so that nothing the other forms read has moved.
+template <class Base>
+struct CutTail {
+    Base base;
+    CutSet cut;
+};
+template <class Base, bool CUT>
+using PersistTail = std::conditional_t<CUT, CutTail<Base>, Base>;
 template <class Tail>
 struct PersistKernArgs {
     KernelArgs a;
@@ -1784,13 +1808,16 @@ DEV const PersistKernArgs<Tail> *persist_kernargs() {
 // MAPS: material maps on top of the set (include/glrtx.h "Material maps"), launched only while maps are bound.
 // ENV: an environment is bound (include/glrtx.h "Environment"): bounce_ext<false, TEX, true> adds its radiance where a ray leaves the scene and, in sampled
 // mode, draws it as a light; EnvArgs takes VolArgs' place as the fourth argument.
+// CUT (implies TEX, excludes VOL; include/glrtx.h "Cutouts"): alpha cutouts are bound -- bounce_ext<.., true> traces its three rays with the CUT traversal step;
+// the fourth argument is a CutTail.  Launched only while cutouts are bound.
 // The loop is stated here, in the kernel template, and nowhere else: every instantiation is the syntax tree a kernel written out by hand would be.  Called
 // from a body shared by thin __global__ wrappers, the compiler allocated the registers of every instantiation differently (the same operations, another
 // schedule), and a change of form is to leave the instructions of the forms it does not touch alone: tools/isa_diff.py against a build of the parent shows it.
-template <bool COUNT_RAYS, bool EXT = false, bool VOL = false, bool TEX = false, bool ENV = false, bool MAPS = false>
+template <bool COUNT_RAYS, bool EXT = false, bool VOL = false, bool TEX = false, bool ENV = false, bool MAPS = false, bool CUT = false>
 __global__ __launch_bounds__(kBlockThreads) void pt_render_persistent(const KernelArgs a_entry, unsigned *work_counter_entry, const ExtArgs ex_entry,
-                                                                      const std::conditional_t<ENV, EnvArgs, VolArgs> tail_entry) {
-    using Tail = std::conditional_t<ENV, EnvArgs, VolArgs>;
+                                                                      const PersistTail<std::conditional_t<ENV, EnvArgs, VolArgs>, CUT> tail_entry) {
+    using Tail = PersistTail<std::conditional_t<ENV, EnvArgs, VolArgs>, CUT>;
+    static_assert(!CUT || (TEX && !VOL), "CUT is a form of the textured kernels; none beside the volume");
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     float4 *lds_mats;
     int *stack;
@@ -1870,7 +1897,11 @@ __global__ __launch_bounds__(kBlockThreads) void pt_render_persistent(const Kern
             }
             bool finished = true;
             if (a.max_depth > 0) {
-                if constexpr (ENV) {
+                if constexpr (CUT && ENV) {
+                    finished = bounce_ext<false, true, true, MAPS, true>(a, ka->ex, lds_spheres, lds_mats, stack, rng, P, rays, nullptr, &ka->tail.base, &ka->tail.cut);
+                } else if constexpr (CUT) {
+                    finished = bounce_ext<false, true, false, MAPS, true>(a, ka->ex, lds_spheres, lds_mats, stack, rng, P, rays, nullptr, nullptr, &ka->tail.cut);
+                } else if constexpr (ENV) {
                     finished = bounce_ext<false, TEX, true, MAPS>(a, ka->ex, lds_spheres, lds_mats, stack, rng, P, rays, nullptr, &ka->tail);
                 } else if constexpr (TEX) {
                     if (VOL) finished = bounce_ext<true, true, false, MAPS>(a, ka->ex, lds_spheres, lds_mats, stack, rng, P, rays, &ka->tail);

@@ -145,6 +145,65 @@ TEX_DEV float2 tex_hit_st(const TexSet &ts, int tri, float u, float v) {
     return make_float2((w0 * a.x + u * b.x) + v * c.x, (w0 * a.y + u * b.y) + v * c.y);
 }
 
+// One channel of the lookup (include/glrtx.h "Cutouts"): channels 0 to 2 are tex_lookup's x, y, z word for word; channel 3 is the texel's .w (RGBA32F) or
+// byte / 255.0f (both 8-bit formats: alpha is never sRGB-decoded), filtered by the same tex_mix.  Fetches what the channel needs and no more: one 4-byte load a
+// texel in every format (one dword of the RGBA32F texel, or the packed 8-bit texel).
+TEX_DEV float tex_texel_channel(const TexSet &ts, const TexDesc &d, int channel, int ix, int iy) {
+    const size_t k = (size_t)iy * (size_t)d.width + (size_t)ix;
+    const unsigned char *base = ts.texels + d.offset;
+    if (d.format == TEX_RGBA32F) return *reinterpret_cast<const float *>(base + 16 * k + 4 * (size_t)(unsigned)channel);
+    const unsigned w = *reinterpret_cast<const unsigned *>(base + 4 * k);  // bytes r, g, b, a in memory order
+    const unsigned b = (w >> (8u * (unsigned)channel)) & 255u;
+    if (d.format == TEX_RGBA8_SRGB && channel < 3) return __uint_as_float(kSrgbBits[b]);
+    return (float)b / 255.0f;
+}
+// index must lie in [0, set.n_tex), channel in 0 .. 3: the callers' records are checked when they are bound (glrtx_bind_cutouts).
+TEX_DEV float tex_lookup_channel(const TexSet &ts, int index, int channel, float s, float t) {
+    const TexDesc d = ts.desc[index];
+    int x0, x1, y0, y1;
+    float fx, fy;
+    tex_axis(s, d.width, d.wrap_s, d.filter, x0, x1, fx);
+    tex_axis(t, d.height, d.wrap_t, d.filter, y0, y1, fy);
+    const float t00 = tex_texel_channel(ts, d, channel, x0, y0);
+    if (d.filter != TEX_BILINEAR) return t00;
+    const float t10 = tex_texel_channel(ts, d, channel, x1, y0), t01 = tex_texel_channel(ts, d, channel, x0, y1), t11 = tex_texel_channel(ts, d, channel, x1, y1);
+    return tex_mix(fx, fy, t00, t10, t01, t11);
+}
+
+// Cutouts (include/glrtx.h "Cutouts"; glrtx_bind_cutouts).  == glrtx_cutout, 16 bytes: one record a material, texture -1: none.
+struct CutRec {
+    int texture, channel;
+    float cutoff;
+    int reserved;
+};
+// The bound records and tri_cut: the record index of every device triangle (tex_hit_st's index), -1 for a triangle whose material is not cut -- built when the
+// records are bound, from the triangles' materials.  Passed to the CUT kernels behind their last argument; nothing else reads it.
+struct CutSet {
+    const int *tri_cut;
+    const CutRec *rec;
+};
+// What the CUT traversal step takes: the launch's texture set and its cutout tables, both in the kernel's argument segment
+struct CutRef {
+    const TexSet *tex;
+    const CutSet *cut;
+};
+// The rule, at a candidate hit (u, v) of device triangle `tri` that would become the ray's closest: accepted iff value >= cutoff (a NaN rejects).  One 4-byte
+// gather for every candidate; only a cut triangle goes on to its record, tri_st and the texels.
+TEX_DEV bool cut_accepts(const CutRef &cr, int tri, float u, float v) {
+    const int k = cr.cut->tri_cut[tri];
+    if (k < 0) return true;
+    const CutRec r = cr.cut->rec[k];
+    const float2 st = tex_hit_st(*cr.tex, tri, u, v);
+    return tex_lookup_channel(*cr.tex, r.texture, r.channel, st.x, st.y) >= r.cutoff;
+}
+
+// glrtx_debug_texture_channel: out[i] = tex_lookup_channel(which[i], channel[i], st[2i], st[2i + 1])
+__global__ __launch_bounds__(256) void tex_channel_kernel(const TexSet ts, const int *which, const int *channel, const float *st, unsigned n, float *out) {
+    const unsigned i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    out[i] = tex_lookup_channel(ts, which[i], channel[i], st[2 * i], st[2 * i + 1]);
+}
+
 // glrtx_debug_texture_lookup: out[3i..] = tex_lookup(which[i], st[2i], st[2i + 1])
 __global__ __launch_bounds__(256) void tex_lookup_kernel(const TexSet ts, const int *which, const float *st, unsigned n, float *out) {
     const unsigned i = blockIdx.x * 256u + threadIdx.x;

@@ -17,8 +17,10 @@
 #include <limits>
 #include <vector>
 
+#include "cutout_statement.h"
 #include "glrt_host.h"
 #include "statement_math.h"
+#include "texture_statement.h"
 
 namespace {
 
@@ -37,7 +39,18 @@ inline bool finite(float x) { return (bits(x) & 0x7F800000u) != 0x7F800000u; }
 
 struct Tree {
     const float *vert, *tri, *nodes;
+    const glrt_detail::CutoutHook *cut;  // glrt_render_features_geom_cutout's search alone (include/glrtx.h "Cutouts"); null: the geometric query
 };
+
+// The cutout rule at a candidate (u, v) of wire triangle tr with corners v0, v1, v2: accepted iff the channel's value >= cutoff (a NaN rejects)
+bool cut_accepts(const glrt_detail::CutoutHook &h, const float *tr, const float *v0, const float *v1, const float *v2, float u, float v) {
+    const glrt_cutout &r = h.cut[(size_t)tr[3]];
+    if (r.texture < 0) return true;
+    const float w0 = (1.0f - u) - v;
+    const float s = (w0 * v0[6] + u * v1[6]) + v * v2[6];
+    const float t = (w0 * v0[7] + u * v1[7]) + v * v2[7];
+    return glrt_detail::texture_channel_one(h.tex[r.texture], h.texels, r.channel, s, t) >= r.cutoff;
+}
 
 // One ray.  hit: {t, tri (int32 bits), u, v}.
 void trace_one(const Tree &s, const float *r, float *hit, bool any, std::vector<int> &stack) {
@@ -93,6 +106,7 @@ void trace_one(const Tree &s, const float *r, float *hit, bool any, std::vector<
             if (v < 0.0f || 1.0f < inv * (U + V)) continue;  // u + v > 1 evaluated as inv * (U + V) > 1
             const float tt = dot3(e2x, e2y, e2z, qx, qy, qz) * inv;
             if (tmin >= tt || !(tt < tHit)) continue;  // strict: among equal distances the first one visited wins; a NaN t is never a hit
+            if (s.cut && !cut_accepts(*s.cut, tr, v0, v1, v2, u, v)) continue;  // a rejected candidate changes nothing
             tHit = tt; htri = t; hu = u; hv = v;
             if (any) break;
         }
@@ -107,6 +121,11 @@ void trace_one(const Tree &s, const float *r, float *hit, bool any, std::vector<
 
 int glrt_trace_rays(const float *vert, size_t n_vert, const float *tri, size_t n_tri, const float *nodes, size_t n_nodes, const float *rays, size_t n,
                     float *hits_out, int flags) {
+    return glrt_detail::trace_rays_cutout(vert, n_vert, tri, n_tri, nodes, n_nodes, rays, n, hits_out, flags, nullptr);
+}
+
+int glrt_detail::trace_rays_cutout(const float *vert, size_t n_vert, const float *tri, size_t n_tri, const float *nodes, size_t n_nodes, const float *rays, size_t n,
+                                   float *hits_out, int flags, const CutoutHook *hook) {
     if (flags != GLRT_TRACE_CLOSEST && flags != GLRT_TRACE_ANY) return GLRT_HOST_EINVAL;
     if (n == 0) return GLRT_HOST_OK;
     if (!rays || !hits_out) return GLRT_HOST_EINVAL;
@@ -137,7 +156,7 @@ int glrt_trace_rays(const float *vert, size_t n_vert, const float *tri, size_t n
         }
     }
     FlushDenormals ftz;
-    const Tree s{vert, tri, n_nodes > 0 ? nodes : nullptr};
+    const Tree s{vert, tri, n_nodes > 0 ? nodes : nullptr, hook};
     std::vector<int> stack;
     stack.reserve(64);
     for (size_t i = 0; i < n; i++) trace_one(s, rays + 8 * i, hits_out + 4 * i, flags == GLRT_TRACE_ANY, stack);

@@ -50,6 +50,7 @@ void Scene::parse(const std::string &filename) {
     spheres.clear();
     textures_.clear();
     maps_.clear();
+    cutouts_.clear();
     environment_ = EnvironmentSpec{};
     hasDielectric_ = false;
     volumeSpecs_.clear();
@@ -273,6 +274,52 @@ void Scene::parse(const std::string &filename) {
                 GLRT_Info("%s: %s, %d x %d, %s", key, spec.file.c_str(), spec.image.width, spec.image.height, spec.image.isFloat ? "float" : "8-bit linear");
                 maps_.push_back(std::move(spec));
             }
+        }
+        if (extensions_ && !sh["cutout"].is_null()) {  // EXTENSION (scene.h: CutoutSpec); off, the key is one the parser does not know
+            const Json &ct = sh["cutout"];
+            if (!ct.is_object()) GLRT_FatalError("shape %zu: \"cutout\" is not an object", i);
+            if (material != "diffuse" && material != "conductor")
+                GLRT_FatalError("shape %zu: \"cutout\" on a %s shape (a diffuse or conductor shape takes one)", i, material.c_str());
+            CutoutSpec spec;
+            spec.material = materials.size();
+            if (!ct["file"].is_string() || ct["file"].string_value().empty()) GLRT_FatalError("shape %zu: \"cutout\" has no \"file\" string", i);
+            spec.file = baseDir + "/" + ct["file"].string_value();
+            spec.filter = GLRTX_TEX_BILINEAR;
+            if (!ct["filter"].is_null()) {
+                const std::string v = ct["filter"].is_string() ? ct["filter"].string_value() : std::string();
+                if (v == "bilinear") spec.filter = GLRTX_TEX_BILINEAR;
+                else if (v == "nearest") spec.filter = GLRTX_TEX_NEAREST;
+                else GLRT_FatalError("shape %zu: cutout \"filter\" is not \"bilinear\" or \"nearest\"", i);
+            }
+            spec.wrap = GLRTX_TEX_REPEAT;
+            if (!ct["wrap"].is_null()) {
+                const std::string v = ct["wrap"].is_string() ? ct["wrap"].string_value() : std::string();
+                if (v == "repeat") spec.wrap = GLRTX_TEX_REPEAT;
+                else if (v == "clamp") spec.wrap = GLRTX_TEX_CLAMP;
+                else GLRT_FatalError("shape %zu: cutout \"wrap\" is not \"repeat\" or \"clamp\"", i);
+            }
+            if (!ct["srgb"].is_null() && !(ct["srgb"].is_bool() && !ct["srgb"].bool_value()))
+                GLRT_FatalError("shape %zu: cutout \"srgb\": a mask holds coverage, not colour (an sRGB mask is refused)", i);
+            spec.channel = 0;
+            if (!ct["channel"].is_null()) {
+                const std::string v = ct["channel"].is_string() ? ct["channel"].string_value() : std::string();
+                if (v == "r") spec.channel = 0;
+                else if (v == "g") spec.channel = 1;
+                else if (v == "b") spec.channel = 2;
+                else GLRT_FatalError("shape %zu: cutout \"channel\" is not \"r\", \"g\" or \"b\" (the image readers are three-channel)", i);
+            }
+            spec.cutoff = 0.5f;
+            if (!ct["cutoff"].is_null()) {
+                const double v = ct["cutoff"].is_number() ? ct["cutoff"].number_value() : (double)NAN;
+                if (!(std::fabs(v) <= 3.4028234663852886e38)) GLRT_FatalError("shape %zu: cutout \"cutoff\" is not a finite number", i);  // (a float's range; NaN fails too)
+                spec.cutoff = (float)v;
+            }
+            std::string terr;
+            if (!readTextureFile(spec.file, spec.image, terr)) GLRT_FatalError("shape %zu: cutout \"file\": %s", i, terr.c_str());
+            spec.format = spec.image.isFloat ? GLRTX_TEX_RGBA32F : GLRTX_TEX_RGBA8_UNORM;
+            GLRT_Info("cutout: %s, %d x %d, %s, channel %d, cutoff %g", spec.file.c_str(), spec.image.width, spec.image.height, spec.image.isFloat ? "float" : "8-bit linear",
+                      spec.channel, (double)spec.cutoff);
+            cutouts_.push_back(std::move(spec));
         }
         materials.push_back(m);
 
@@ -783,6 +830,29 @@ struct SceneMapProbe {
 
 extern "C" GLRT_API int glrt_scene_map_probe(const char *json, int extensions, int *info, float *scale, int cap) {
     return glrt::SceneMapProbe::run(json, extensions, info, scale, cap);
+}
+
+// Cutout probe: parse with extensions on or off.  Returns the number of cutouts; per cutout info[7k..] = {material, channel, width, height, format, wrap,
+// filter} and cutoff[k].
+namespace glrt {
+struct SceneCutoutProbe {
+    static int run(const char *json, int extensions, int *info, float *cutoff, int cap) {
+        Scene sc;
+        sc.enableExtensions(extensions != 0);
+        sc.parse(json);
+        for (size_t k = 0; k < sc.cutouts_.size() && (int)k < cap; k++) {
+            const Scene::CutoutSpec &t = sc.cutouts_[k];
+            const int row[7] = {(int)t.material, t.channel, t.image.width, t.image.height, t.format, t.wrap, t.filter};
+            if (info) std::memcpy(info + 7 * k, row, sizeof row);
+            if (cutoff) cutoff[k] = t.cutoff;
+        }
+        return (int)sc.cutouts_.size();
+    }
+};
+}  // namespace glrt
+
+extern "C" GLRT_API int glrt_scene_cutout_probe(const char *json, int extensions, int *info, float *cutoff, int cap) {
+    return glrt::SceneCutoutProbe::run(json, extensions, info, cutoff, cap);
 }
 
 // Environment probe: parse with extensions on or off and an optional mode override (-1: none).  info = {present, mode, size, format, filter, latlong, texel

@@ -85,6 +85,22 @@ public:
         TextureImage image;
     };
     const std::vector<MapSpec> &mapSpecs() const { return maps_; }
+    // Cutouts (include/glrtx.h "Cutouts"; no reference counterpart).  With extensions on, a "diffuse" or "conductor" shape may carry
+    //     "cutout": {"file": "mask.ppm" | "mask.pfm", "channel": "r" | "g" | "b", "cutoff": x, "filter": .., "wrap": ..}
+    // "file", "filter" and "wrap" as in "texture".  A PPM is read as GLRTX_TEX_RGBA8_UNORM: a mask holds coverage, not colour, and "srgb": true is a
+    // FatalError.  "channel" defaults to "r" -- the readers are three-channel, so alpha in files is not offered: channel 3 is for callers of the C ABI --,
+    // "cutoff" to 0.5 and must be finite.  The mask is looked up at the OBJ's vt coordinates; a candidate hit counts where the channel's value >= cutoff.  A
+    // cutout on a shape of another material and a value other than those above are FatalErrors that name the shape and the key.  Window uploads the masks'
+    // images behind the textures and maps in the one set and binds them (glrtx_bind_cutouts).  With extensions off the key is ignored, as "texture" is.
+    struct CutoutSpec {
+        size_t material;  // the shape's material
+        std::string file;
+        int format, wrap, filter;  // GLRTX_TEX_*
+        int channel;               // 0 .. 2
+        float cutoff;
+        TextureImage image;
+    };
+    const std::vector<CutoutSpec> &cutoutSpecs() const { return cutouts_; }
     // Environment (include/glrtx.h "Environment"; no reference counterpart).  With extensions on, the scene file may carry the top-level key
     //     "environment": {"file": "x.pfm" | "x.ppm", "layout": "latlong" | "octahedral", "size": N, "mode": "escape" | "sampled", "scale": x | [r, g, b],
     //                     "rotate_y": degrees, "light_pick": p, "filter": "bilinear" | "nearest", "srgb": true | false}
@@ -182,6 +198,7 @@ private:
     std::vector<float> spheres;  // extension: 5 floats per sphere {cx, cy, cz, radius, material}
     std::vector<TextureSpec> textures_;  // extension: one per textured diffuse shape, in shape order
     std::vector<MapSpec> maps_;          // extension: the shapes' normal and roughness maps, in shape order
+    std::vector<CutoutSpec> cutouts_;    // extension: the shapes' cutout masks, in shape order
     EnvironmentSpec environment_;        // extension: the scene file's "environment" block
     int envModeOverride_ = -1;
     bool extensions_ = false, whitted_ = false, hasDielectric_ = false;
@@ -208,6 +225,7 @@ private:
     friend struct SceneNormalsProbe;
     friend struct SceneTextureProbe;
     friend struct SceneMapProbe;
+    friend struct SceneCutoutProbe;
     friend struct SceneEnvironmentProbe;
 };
 

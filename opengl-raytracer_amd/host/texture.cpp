@@ -113,7 +113,43 @@ void lookup(const TexRecord &d, const unsigned char *texels, float s, float t, f
     for (int c = 0; c < 3; c++) rgb[c] = mix(fx, fy, t00[c], t10[c], t01[c], t11[c]);
 }
 
+// One channel (include/glrtx.h "Cutouts"): 0 .. 2 are lookup()'s words; 3 is the texel's fourth float, or byte / 255.0f for both 8-bit formats
+float texel_channel(const TexRecord &d, const unsigned char *texels, int channel, int ix, int iy) {
+    const size_t k = (size_t)iy * (size_t)d.width + (size_t)ix;
+    const unsigned char *p = texels + d.offset;
+    if (d.format == GLRT_TEX_RGBA32F) {
+        float f;
+        std::memcpy(&f, p + 16 * k + 4 * (size_t)channel, 4);
+        return f;
+    }
+    const unsigned b = p[4 * k + (size_t)channel];
+    return d.format == GLRT_TEX_RGBA8_SRGB && channel < 3 ? bits_f(kSrgbBits[b]) : (float)b / 255.0f;
+}
+float lookup_channel(const TexRecord &d, const unsigned char *texels, int channel, float s, float t) {
+    int x0, x1, y0, y1;
+    float fx, fy;
+    axis(s, d.width, d.wrap_s, d.filter, x0, x1, fx);
+    axis(t, d.height, d.wrap_t, d.filter, y0, y1, fy);
+    const float t00 = texel_channel(d, texels, channel, x0, y0);
+    if (d.filter != GLRT_TEX_BILINEAR) return t00;
+    return mix(fx, fy, t00, texel_channel(d, texels, channel, x1, y0), texel_channel(d, texels, channel, x0, y1), texel_channel(d, texels, channel, x1, y1));
+}
+
 }  // namespace
+
+float glrt_detail::texture_channel_one(const TexRecord &d, const unsigned char *texels, int channel, float s, float t) { return lookup_channel(d, texels, channel, s, t); }
+
+int glrt_texture_channel(const glrt_texture *tex, size_t n_tex, const void *texels, size_t texel_bytes, const int32_t *which, const int32_t *channel, const float *st,
+                         size_t n, float *value_out) {
+    if (n && (!which || !channel || !st || !value_out)) return GLRT_HOST_EINVAL;
+    const TexRecord *rec = reinterpret_cast<const TexRecord *>(tex);
+    if (!glrt_detail::texture_set_error(rec, n_tex, texels, texel_bytes).empty()) return GLRT_HOST_EINVAL;
+    for (size_t i = 0; i < n; i++)
+        if (which[i] < 0 || (size_t)which[i] >= n_tex || channel[i] < 0 || channel[i] > 3) return GLRT_HOST_EINDEX;
+    FlushDenormals ftz;
+    for (size_t i = 0; i < n; i++) value_out[i] = lookup_channel(rec[which[i]], (const unsigned char *)texels, channel[i], st[2 * i], st[2 * i + 1]);
+    return GLRT_HOST_OK;
+}
 
 // (texture_statement.h: the same statement for host/environment.cpp)
 void glrt_detail::texture_lookup_one(const TexRecord &d, const unsigned char *texels, float s, float t, float rgb[3]) { lookup(d, texels, s, t, rgb); }

@@ -44,7 +44,7 @@ unsigned long long Window::raysTraced() const {
 
 // The scene's textures (Scene::TextureSpec; extensions only) as one set on every member, after the scene: launches then run on the extension megakernel
 void Window::uploadTextures() {
-    if (scene->textures_.empty() && scene->maps_.empty()) return;
+    if (scene->textures_.empty() && scene->maps_.empty() && scene->cutouts_.empty()) return;
     std::vector<glrtx_texture> desc;
     std::vector<unsigned char> blob;
     std::vector<int32_t> bind(scene->materials.size(), -1);
@@ -63,13 +63,24 @@ void Window::uploadTextures() {
         if (t.roughness) maps[t.material].roughness = (int32_t)desc.size() - 1;
         else { maps[t.material].normal = (int32_t)desc.size() - 1; maps[t.material].normal_scale = t.scale; }
     }
+    // ... and the cutout masks behind those (Scene::CutoutSpec), bound with a third call
+    std::vector<glrtx_cutout> cuts(scene->materials.size(), glrtx_cutout{-1, 0, 0.5f, 0});
+    for (const Scene::CutoutSpec &t : scene->cutouts_) {
+        blob.resize((blob.size() + 15) / 16 * 16, 0);
+        desc.push_back(glrtx_texture{(uint64_t)blob.size(), t.image.width, t.image.height, t.format, t.wrap, t.wrap, t.filter});
+        blob.insert(blob.end(), t.image.texels.begin(), t.image.texels.end());
+        cuts[t.material] = glrtx_cutout{(int32_t)desc.size() - 1, t.channel, t.cutoff, 0};
+    }
     for (int i = 0; i < glrtx_group_size(grp_); i++) {
         glrtx_ctx *c = glrtx_group_ctx(grp_, i);
         if (glrtx_upload_textures(c, desc.data(), desc.size(), blob.data(), blob.size(), bind.data(), bind.size()) != GLRTX_OK)
             GLRT_FatalError("glrtx_upload_textures: %s", glrtx_last_error(c));
         if (!scene->maps_.empty() && glrtx_bind_material_maps(c, maps.data(), maps.size()) != GLRTX_OK)
             GLRT_FatalError("glrtx_bind_material_maps: %s", glrtx_last_error(c));
+        if (!scene->cutouts_.empty() && glrtx_bind_cutouts(c, cuts.data(), cuts.size()) != GLRTX_OK)
+            GLRT_FatalError("glrtx_bind_cutouts: %s", glrtx_last_error(c));
     }
+    if (!scene->cutouts_.empty()) GLRT_Info("cutouts: %zu (not part of the reference)", scene->cutouts_.size());
     if (!scene->maps_.empty()) GLRT_Info("material maps: %zu (not part of the reference)", scene->maps_.size());
     GLRT_Info("textures: %zu, %zu texel bytes (not part of the reference)", desc.size(), blob.size());
 }
@@ -143,7 +154,7 @@ void Window::mainloop(const std::shared_ptr<Scene> &scene_, double fps) {
     uploadEnvironment();
     resize(scene->width, scene->height);
     if (const char *e = std::getenv("GLRT_BVH_ORDER")) orderByHits_ = std::string(e) == "hits";
-    if (orderByHits_ && !scene->nodes.empty() && scene->textures_.empty() && scene->maps_.empty() && !scene->environment_.present && scene->spheres.empty() && !scene->hasDielectric_ && !scene->whitted_ && !scene->hasVolume_) {
+    if (orderByHits_ && !scene->nodes.empty() && scene->textures_.empty() && scene->maps_.empty() && scene->cutouts_.empty() && !scene->environment_.present && scene->spheres.empty() && !scene->hasDielectric_ && !scene->whitted_ && !scene->hasVolume_) {
         // one calibration frame on the first member's share of the rows (interleaved stripes: a fair sample of the image), counted by the render kernel itself
         glrtx_params p;
         frameParams(p);

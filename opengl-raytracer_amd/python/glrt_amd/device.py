@@ -179,7 +179,7 @@ EXPORTS = ["glrtx_abi_version", "glrtx_create", "glrtx_destroy", "glrtx_last_err
            "glrtx_upload_normal_topology", "glrtx_update_positions", "glrtx_update_positions_device", "glrtx_set_pose_normals",
            "glrtx_debug_rebuild_normals", "glrtx_debug_normals_burst", "glrtx_upload_textures", "glrtx_debug_texture_lookup",
            "glrtx_upload_environment", "glrtx_set_environment_cfg", "glrtx_debug_env_weights", "glrtx_debug_env_sample", "glrtx_debug_env_eval",
-           "glrtx_bind_material_maps", "glrtx_debug_map_normal"]
+           "glrtx_bind_material_maps", "glrtx_debug_map_normal", "glrtx_bind_cutouts", "glrtx_debug_texture_channel", "glrtx_debug_last_kernel"]
 
 SCENE_BUFFERS = ("nodes", "cnodes", "nrms", "lights", "vine", "root")  # glrtx_debug_read_scene's `which`, in order (GLRTX_SCENE_*)
 
@@ -403,6 +403,14 @@ def lib():
             L.glrtx_debug_map_normal.argtypes = [fp, C.c_size_t, C.c_float, fp]
         except AttributeError:
             pass
+        try:  # (additive to ABI 10 as well: cutouts)
+            i32p = C.POINTER(C.c_int32)
+            L.glrtx_bind_cutouts.argtypes = [vp, vp, C.c_size_t]
+            L.glrtx_debug_texture_channel.argtypes = [vp, C.c_size_t, vp, C.c_size_t, i32p, i32p, fp, C.c_size_t, fp]
+            L.glrtx_debug_last_kernel.argtypes = [vp]
+            L.glrtx_debug_last_kernel.restype = C.c_char_p
+        except AttributeError:
+            pass
         _lib = L
     return _lib
 
@@ -481,6 +489,26 @@ def debug_texture_lookup(textures, which, st):
         raise ValueError(f"debug_texture_lookup: {w.size} texture indices, {c.shape[0]} coordinates")
     out = np.zeros((w.size, 3), np.float32)
     rc = L.glrtx_debug_texture_lookup(desc.ctypes.data, desc.size, blob.ctypes.data, blob.size, w.ctypes.data_as(C.POINTER(C.c_int32)), _fp(c), w.size, _fp(out))
+    if rc != 0:
+        raise GlrtxError(rc, L.glrtx_last_error(None).decode())
+    return out
+
+
+def debug_texture_channel(textures, which, channel, st):
+    """glrtx_debug_texture_channel on the current device: the kernels' tex_lookup_channel (include/glrtx.h "Cutouts").  Arguments and result as
+    host.texture_channel's."""
+    from .host import pack_textures
+    L = lib()
+    desc, blob = pack_textures(textures)
+    w = np.ascontiguousarray(which, dtype=np.int32).reshape(-1)
+    ch = np.ascontiguousarray(np.broadcast_to(np.asarray(channel, np.int32), w.shape))
+    c = _f32(st).reshape(-1, 2)
+    if c.shape[0] != w.size:
+        raise ValueError(f"debug_texture_channel: {w.size} texture indices, {c.shape[0]} coordinates")
+    out = np.zeros(w.size, np.float32)
+    i32p = C.POINTER(C.c_int32)
+    rc = L.glrtx_debug_texture_channel(desc.ctypes.data, desc.size, blob.ctypes.data, blob.size, w.ctypes.data_as(i32p), ch.ctypes.data_as(i32p), _fp(c), w.size,
+                                       _fp(out))
     if rc != 0:
         raise GlrtxError(rc, L.glrtx_last_error(None).decode())
     return out
@@ -1120,6 +1148,25 @@ class Device:
         else:
             rec = material_maps(np.size(normal if normal is not None else roughness), normal, roughness, normal_scale)
         self._ck(self.L.glrtx_bind_material_maps(self.h, rec.ctypes.data, rec.size))
+
+    def bind_cutouts(self, texture=None, channel=None, cutoff=None):
+        """Bind alpha cutouts on top of the bound texture set (glrtx_bind_cutouts; include/glrtx.h "Cutouts"): per-material arrays of texture indices (-1:
+        not cut), channels (0 .. 3; default 3, alpha) and cutoffs (default 0.5), or one array of host.CUTOUT_DTYPE records as `texture`.  A candidate hit on a
+        bound diffuse or conductor material counts only where the channel's value >= cutoff -- for path and shadow rays alike.  Launches then run on the
+        extension megakernel's CUT forms.  texture None unbinds.  upload_textures and upload_scene drop the records; vertex updates and poses keep them."""
+        from .host import CUTOUT_DTYPE, cutouts
+        if texture is None:
+            self._ck(self.L.glrtx_bind_cutouts(self.h, None, 0))
+            return
+        if getattr(texture, "dtype", None) == CUTOUT_DTYPE:
+            rec = np.ascontiguousarray(texture).reshape(-1)
+        else:
+            rec = cutouts(np.size(texture), texture, channel, cutoff)
+        self._ck(self.L.glrtx_bind_cutouts(self.h, rec.ctypes.data, rec.size))
+
+    def last_kernel(self) -> str:
+        """glrtx_debug_last_kernel: the name of the render kernel the last launch ran, as error reports give it ("" before the first launch)."""
+        return self.L.glrtx_debug_last_kernel(self.h).decode()
 
     def upload_environment(self, env_map, cfg=None):
         """Bind an environment (glrtx_upload_environment; include/glrtx.h "Environment"): env_map as host.pack_environment takes it -- (array (N, N, 3 or 4),

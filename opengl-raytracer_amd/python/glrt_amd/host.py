@@ -71,6 +71,9 @@ def lib():
         L.glrt_srgb_table.restype = fp
         L.glrt_srgb_table.argtypes = []
         L.glrt_texture_albedo.argtypes = [fp, C.c_size_t, fp, C.c_size_t, fp, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, i32p, fp, C.c_size_t, fp]
+        L.glrt_texture_channel.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, i32p, i32p, fp, C.c_size_t, fp]
+        L.glrt_render_features_geom_cutout.argtypes = ([fp, C.c_size_t, fp, C.c_size_t, fp, C.c_size_t, fp, C.c_size_t, fp, fp] + [C.c_int] * 5 +
+                                                       [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, i32p, C.c_void_p, fp, fp, fp])
         vp = C.c_void_p
         L.glrt_env_weights.argtypes = [vp, vp, C.c_size_t, vp, fp, i32p]
         L.glrt_env_alias.argtypes = [fp, C.c_int32, fp, i32p, fp, i32p, fp]
@@ -602,7 +605,7 @@ TEXTURE_DTYPE = np.dtype([("offset", "<u8"), ("width", "<i4"), ("height", "<i4")
 
 def pack_textures(textures):
     """A texture set as the C calls take it.  textures: a list of (array, format, wrap, filter) -- array (height, width, 3 or 4), row 0 at t = 0, float32 for
-    rgba32f and uint8 for the 8-bit formats (three channels get an alpha of 1 / 255, which nothing reads); format, wrap and filter are TEX_* numbers or their
+    rgba32f and uint8 for the 8-bit formats (three channels get an alpha of 1 / 255, which only a cutout on channel 3 reads); format, wrap and filter are TEX_* numbers or their
     names, wrap may be a pair (wrap_s, wrap_t).  A pair (descriptors, blob) already packed passes through.  Returns (descriptors (n,) TEXTURE_DTYPE, blob uint8)."""
     if isinstance(textures, tuple) and len(textures) == 2 and getattr(textures[0], "dtype", None) == TEXTURE_DTYPE:
         return np.ascontiguousarray(textures[0]), np.ascontiguousarray(textures[1], dtype=np.uint8).reshape(-1)
@@ -662,6 +665,60 @@ def texture_albedo(scene, textures, material_texture, hits):
     if rc != 0:
         raise RuntimeError(f"glrt_texture_albedo failed: {rc}")
     return out.reshape(h.shape[:-1] + (3,))
+
+
+# --------------------------------------------------------------------------- cutouts (include/glrtx.h "Cutouts")
+CUTOUT_DTYPE = np.dtype([("texture", "<i4"), ("channel", "<i4"), ("cutoff", "<f4"), ("reserved", "<i4")])  # glrtx_cutout
+
+
+def cutouts(n_mat, texture=None, channel=None, cutoff=None):
+    """(n_mat,) CUTOUT_DTYPE records from per-material arrays (or scalars): texture indices of the bound set (-1 or None: not cut), channels 0 .. 3 (default 3,
+    alpha) and cutoffs (default 0.5)."""
+    r = np.zeros(int(n_mat), CUTOUT_DTYPE)
+    r["texture"] = -1 if texture is None else np.asarray(texture, np.int32)
+    r["channel"] = 3 if channel is None else np.asarray(channel, np.int32)
+    r["cutoff"] = 0.5 if cutoff is None else np.asarray(cutoff, np.float32)
+    return r
+
+
+def texture_channel(textures, which, channel, st):
+    """glrt_texture_channel: the CPU statement of the device's one-channel lookup (include/glrtx.h "Cutouts").  textures as pack_textures takes them; which (n,)
+    texture indices; channel (n,) or one number, 0 .. 3; st (n, 2).  Returns (n,) float32."""
+    desc, blob = pack_textures(textures)
+    w = np.ascontiguousarray(which, dtype=np.int32).reshape(-1)
+    ch = np.ascontiguousarray(np.broadcast_to(np.asarray(channel, np.int32), w.shape))
+    c = _f32(st).reshape(-1, 2)
+    if c.shape[0] != w.size:
+        raise ValueError(f"texture_channel: {w.size} texture indices, {c.shape[0]} coordinates")
+    out = np.zeros(w.size, np.float32)
+    rc = lib().glrt_texture_channel(desc.ctypes.data, desc.size, blob.ctypes.data, blob.size, _ptr(w, C.c_int32), _ptr(ch, C.c_int32), _ptr(c, C.c_float), w.size,
+                                    _ptr(out, C.c_float))
+    if rc != 0:
+        raise RuntimeError(f"glrt_texture_channel failed: {rc}")
+    return out
+
+
+def render_features_geom_cutout(scene, params, textures, material_texture, cut, width=None, height=None, rank=0, world=1, stripe=16):
+    """glrt_render_features_geom_cutout: render_features_geom with the cutout rule inside its closest-hit search -- the CPU statement of the feature pass under
+    Device.track_motion with a set (textures, material_texture: per-material texture indices, -1 none) and cutouts (cut: (n_mat,) CUTOUT_DTYPE) bound.  Returns
+    (normal_depth, albedo_id, geom) as render_features_geom does."""
+    w, h = int(width or params["width"]), int(height or params["height"])
+    vert, tri = _f32(scene["vert"]).reshape(-1, 15), _f32(scene["tri"]).reshape(-1, 4)
+    nodes, mat = _f32(scene["bvh"]).reshape(-1, 9), _f32(scene["mat"]).reshape(-1, 18)
+    c2w, s2c = _f32(params["c2w"]).reshape(16), _f32(params["s2c"]).reshape(16)
+    desc, blob = pack_textures(textures)
+    b = np.ascontiguousarray(material_texture, dtype=np.int32).reshape(-1)
+    rec = np.ascontiguousarray(cut, dtype=CUTOUT_DTYPE).reshape(-1)
+    if b.size != mat.shape[0] or rec.size != mat.shape[0]:
+        raise ValueError(f"render_features_geom_cutout: {mat.shape[0]} materials, {b.size} bindings, {rec.size} cutout records")
+    rows = sum(1 for y in range(h) if (y // stripe) % world == rank)
+    n, a, g = (np.zeros((rows, w, 4), np.float32) for _ in range(3))
+    rc = lib().glrt_render_features_geom_cutout(_fp(vert), vert.shape[0], _fp(tri), tri.shape[0], _fp(nodes), nodes.shape[0], _fp(mat), mat.shape[0], _fp(c2w),
+                                                _fp(s2c), w, h, rank, world, stripe, desc.ctypes.data, desc.size, blob.ctypes.data, blob.size, _ptr(b, C.c_int32),
+                                                rec.ctypes.data, _fp(n), _fp(a), _fp(g))
+    if rc != 0:
+        raise RuntimeError(f"glrt_render_features_geom_cutout failed: {rc}")
+    return n, a, g
 
 
 # --------------------------------------------------------------------------- material maps (include/glrtx.h "Material maps")

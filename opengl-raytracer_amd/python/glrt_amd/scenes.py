@@ -420,6 +420,41 @@ def config_mapped_wall(n=6, width=64, height=48, max_depth=4, n_samples=2, wall=
     return scene, make_params(c2w, s2c, width, height, max_depth, n_samples), info
 
 
+def collapse_triangles(scene, tris):
+    """The scene with vertices 1 and 2 of each wire triangle in `tris` moved onto its vertex 0 (positions only; the triangles' vertices must be unshared, as
+    SceneBuilder makes them) and every other buffer -- the `bvh` array included -- as it is.  A collapsed triangle has det = 0 and is never hit, and the tree
+    still encloses it: the image is the one a traversal that rejects every candidate on those triangles renders (include/glrtx.h "Cutouts")."""
+    s = dict(scene)
+    v = np.array(scene["vert"], np.float32).reshape(-1, 5, 3)
+    t = np.asarray(scene["tri"], np.float32).reshape(-1, 4)
+    for k in np.asarray(list(tris), np.int64):
+        a, b, c = (int(x) for x in t[k, :3])
+        v[b, 0] = v[a, 0]
+        v[c, 0] = v[a, 0]
+    s["vert"] = v.reshape(-1, 3)
+    return s
+
+
+def config_cutout_wall(n=6, cutout=None, **kw):
+    """config_textured_wall's scene as the scene alpha cutouts are pinned on (include/glrtx.h "Cutouts"): the wall's 2 n n triangles have unshared vertices and
+    the cell's centre as their coordinates, so a cutout texture with one texel a cell cuts whole cells.  Returns (scene, params, wall) as config_textured_wall
+    does, with two more entries: wall["cell_tris"](mask) -- the wire triangles of the cells where mask (n, n), indexed [row j, column i] as the texels are, is
+    true -- and wall["collapsed"](tris, moved=None) -- collapse_triangles on the scene (or on `moved`, a moved copy of it): what the reference must be given.
+    cutout: the "cutout" block export_json_obj writes for the wall's shape."""
+    scene, params, wall = config_textured_wall(n=n, **kw)
+    if cutout is not None:
+        wall["builder"].materials[wall["material"]]["cutout"] = cutout
+    first = wall["tri"][0]
+
+    def cell_tris(mask):
+        m = np.asarray(mask, bool).reshape(n, n)
+        return [first + 2 * (j * n + i) + k for j in range(n) for i in range(n) if m[j, i] for k in (0, 1)]
+
+    wall["cell_tris"] = cell_tris
+    wall["collapsed"] = lambda tris, moved=None: collapse_triangles(scene if moved is None else moved, tris)
+    return scene, params, wall
+
+
 # --------------------------------------------------------------------------- environment lighting (include/glrtx.h "Environment"; PARITY UNPINNED)
 ENV_QUAD_ALBEDO = (0.5, 0.25, 0.75)
 
@@ -604,7 +639,7 @@ def export_json_obj(builder: SceneBuilder, directory, width, height, origin, tar
                 sh["volume"] = {k: (v if isinstance(v, str) else [float(c) for c in v]) for k, v in m["volume"].items()}
         else:
             raise ValueError("export supports diffuse / conductor / emitter / media shapes")
-        for key in ("normal_map", "roughness_map"):  # (config_mapped_wall; host/scene.h: MapSpec)
+        for key in ("normal_map", "roughness_map", "cutout"):  # (config_mapped_wall, config_cutout_wall; host/scene.h: MapSpec, CutoutSpec)
             if m.get(key) is not None:
                 sh[key] = dict(m[key]) if isinstance(m[key], dict) else m[key]
         shapes.append(sh)

@@ -15,6 +15,10 @@ listing it as GONE and NEW.  From the commit before pt_render_persistent and fea
     --rename 'features_tree<(\w+)>=features_tree<\1, glrtx::features::Args>'
     --rename 'features_tree_\w+<(\w+)>\(glrtx::features::(\w+)\)=features_tree<\1, glrtx::features::\2>(glrtx::features::\2)'
 
+From the commit before pt_render_persistent gained its CUT argument (66f6c1f) to its successor (608 symbols identical, 9 new):
+
+    --rename 'pt_render_persistent<(\w+), (\w+), (\w+), (\w+), (\w+), (\w+)>(.*)std::conditional<(\w+), glrtx::EnvArgs, glrtx::VolArgs>::type\)=pt_render_persistent<\1, \2, \3, \4, \5, \6, false>\7std::conditional<false, glrtx::CutTail<std::conditional<\8, glrtx::EnvArgs, glrtx::VolArgs>::type>, std::conditional<\8, glrtx::EnvArgs, glrtx::VolArgs>::type>::type)'
+
 Works without a GPU (tools/isa_report.py's extraction, llvm-objdump from /opt/rocm).
 """
 from __future__ import annotations
