@@ -328,6 +328,29 @@ int glrt_render_features_geom_cutout(const float *vert, size_t n_vert, const flo
                                      const void *texels, size_t texel_bytes, const int32_t *material_texture, const glrt_cutout *cut, float *out_n, float *out_a,
                                      float *out_g);
 
+/* Emission maps: the CPU statements of the device's textured emitters (glrtx_bind_emission_maps / glrtx_debug_light_emission, include/glrtx.h "Emission
+ * maps": the rule is there), bit for bit (host/texture.cpp; tests/emission_math.py states the sampled side in numpy).  light: n_light x 4 floats {i0, i1, i2,
+ * material}, the wire's light records.  material_emission: one texture index a material, -1 none.
+ *   glrt_light_st         st_out[6l ..] = {s0, t0, s1, t1, s2, t2}: words 6 and 7 of light l's three vertices in wire order -- the device's light_st table.
+ *   glrt_light_emission   out[5i ..] = {s, t, Le.rgb} of light lid[i] at the RAW uniforms (u[2i], u[2i + 1]): the flip at ua0 + ub0 > 1, w0 = (1 - ua) - ub,
+ *                         s = (w0 * s0 + ua * s1) + ub * s2, t likewise, Le = emission * lookup(s, t) per channel (one rounded product); a light whose material
+ *                         is not bound gives its plain emission.
+ *   glrt_emission_albedo  glrt_texture_albedo, then rgb_out again for a hit on a bound material that is NOT diffuse: the looked-up texel c, without the
+ *                         emission -- plane A of the device's feature pass while emission maps are bound, stated on plane G (hits).
+ *   glrt_emission_bind_check  what glrtx_bind_emission_maps refuses of a scene with n_scene_mat materials and a set of n_tex textures (cutouts_bound: cutouts
+ *                         are bound): GLRT_HOST_EINVAL and the device's message behind its "glrtx_bind_emission_maps: " in msg (cap bytes), or
+ *                         GLRT_HOST_OK and "".
+ * GLRT_HOST_EINVAL: a NULL pointer with something to read or write, a set glrtx_upload_textures refuses.  GLRT_HOST_EINDEX: a texture, vertex, material or
+ * light index out of range, a binding on a material of type 5; otherwise glrt_texture_albedo's errors. */
+int glrt_light_st(const float *vert, size_t n_vert, const float *light, size_t n_light, float *st_out);
+int glrt_light_emission(const float *vert, size_t n_vert, const float *light, size_t n_light, const float *mat, size_t n_mat, const glrt_texture *tex, size_t n_tex,
+                        const void *texels, size_t texel_bytes, const int32_t *material_emission, const int32_t *lid, const float *u, size_t n, float *out);
+int glrt_emission_albedo(const float *vert, size_t n_vert, const float *tri, size_t n_tri, const float *mat, size_t n_mat, const glrt_texture *tex, size_t n_tex,
+                         const void *texels, size_t texel_bytes, const int32_t *material_texture, const int32_t *material_emission, const float *hits, size_t n,
+                         float *rgb_out);
+int glrt_emission_bind_check(const float *mat, size_t n_scene_mat, size_t n_tex, int cutouts_bound, const int32_t *material_emission, size_t n_mat, char *msg,
+                             size_t cap);
+
 /* Environment: the CPU statements of the device's environment lighting (glrtx_upload_environment / glrtx_debug_env_*, include/glrtx.h "Environment": the
  * octahedral mapping, its inverse, the solid-angle factor, the importance grid and the sampling rule are there), bit for bit (host/environment.cpp;
  * tests/env_math.py states them in numpy).  glrt_env_cfg is glrtx_env_cfg's layout.  The arithmetic runs with denormals flushed (MXCSR FTZ | DAZ, restored).

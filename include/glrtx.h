@@ -1367,6 +1367,53 @@ int glrtx_debug_texture_channel(const glrtx_texture *tex, size_t n_tex, const vo
  * is static. */
 const char *glrtx_debug_last_kernel(const glrtx_ctx *ctx);
 
+/* ---- Emission maps: a texture on the emitter, seen directly AND sampled as a light (no reference counterpart; off unless called: with no emission maps
+ * bound every launch runs the kernels it ran before).  A screen, a sign, a stained-glass panel or a light card is one quad whose picture lives in a texture.
+ * This section SUPERSEDES the two remarks above that say emission maps are not built ("Material maps": NOT BUILT; "Cutouts": "an emitter may not"): the light
+ * table still carries no coordinates, and does not need to -- a light's wire record names three vertices, those vertices carry uv, and the binding call
+ * builds a per-light coordinate table from them on the host.  An emitter still cannot be CUT.  PINNED through the reference: an emission map that is constant
+ * over each triangle renders, bit for bit and ray for ray, the image of the same triangles with one emitter material each.
+ *
+ * Arithmetic.  As "Textures".  Three statements of the sampled-side rule agree bit for bit: emit_light_st / emit_radiance (csrc/texture.hip.h, used by
+ * shade_core<.., EMIT> in csrc/pt_kernel.hip.h), glrt_light_emission (include/glrt_host.h), tests/emission_math.py.
+ *
+ * RADIANCE. Le = emission * c, per channel: c is the "Textures" lookup (sRGB decode included), emission is m0.xyz of the material, and the product is ONE
+ *   rounded fp32 product, formed before anything else uses it.  The texture multiplies the emission; it does not replace it, unlike albedo: an 8-bit texel
+ *   lies in [0, 1] and the material carries the intensity.
+ * SEEN.     The renderer adds beta * emission at a triangle hit in two places: the general branch (depth 0, or behind a specular bounce) and the dielectric
+ *   branch.  On a bound material both add beta * Le, c looked up at "Textures"' AT A HIT coordinates, and only where one of those conditions holds.  Both
+ *   faces emit, as in the reference.
+ * SAMPLED.  In next-event estimation's triangle-light branch the sample (ua, ub) -- after the flip at ua0 + ub0 > 1 -- of light lid has
+ *   w0 = (1 - ua) - ub, s = (w0 * s0 + ua * s1) + ub * s2, t likewise, with (s0, t0) .. (s2, t2) the uv words of the light's three vertices in wire order
+ *   (the per-light table light_st, read from global memory).  Where the light's material is bound, Le stands for the emission in the three contribution
+ *   lines.  The lookup happens only for a sample that contributes (both cosines positive).  The random stream, the shadow ray and the ray counts do not
+ *   change; the light pick stays uniform; the environment branch is untouched.
+ * Analytic spheres have no coordinates and emit their plain emission.
+ *
+ *   glrtx_bind_emission_maps  binds material m to texture material_emission[m] of the bound set, -1: none.  NULL or n_mat == 0 unbinds.  Needs a bound
+ *                     texture set, which may bind no albedo at all.  A material of any type except media (type 5) may be bound.  glrtx_upload_textures and
+ *                     glrtx_upload_scene DROP the bindings.  They survive glrtx_update_vertices*, glrtx_pose* and glrtx_update_positions*: light_st is built
+ *                     in this call from the vertices glrtx_upload_scene was given, and frozen, as "Textures" freezes its table.  Seals an open fed launch.
+ *                     GLRTX_EINVAL, everything unchanged, the offender named in the message: a NULL context; no scene, or no texture set; n_mat other than
+ *                     the scene's material count; an index outside -1 .. n_tex - 1; a bound material of type 5; cutouts are bound (the two do not combine
+ *                     yet: glrtx_bind_cutouts likewise refuses while emission maps are bound).
+ *   ROUTING.          While emission maps are bound, launches run on the persistent megakernel (variant_last 1, GLRTX_FALLBACK_EXTENSIONS), in the EMIT forms
+ *                     of its textured kernels ("pt_render_persistent (.., emission maps)"); glrtx_set_texture_wavefront does not take them.
+ *                     glrtx_render_adaptive*, glrtx_render_moments, glrtx_render_cascades and glrtx_hit_histogram refuse with "textures are bound" and the
+ *                     reason "emission maps are bound".  Rendering with GLRTX_EXT_VOLUME set and a volume uploaded refuses with "emission maps are bound".
+ *                     After unbinding everything routes as before, and images are bit for bit what they were.
+ *   Feature pass      with emission maps bound, at a primary hit on a bound material whose type is not diffuse plane A's rgb carries c -- the looked-up
+ *                     texel, without the emission -- where it holds zeros otherwise, so that the denoisers divide the emitter's picture out before they
+ *                     filter and multiply it back afterwards.  A bound diffuse material keeps its albedo rule.  glrt_emission_albedo (include/glrt_host.h)
+ *                     states it on plane G.  Without emission maps bound the pass runs the kernels it ran before.
+ *   glrtx_debug_light_emission  the device statement of SAMPLED on the context's bound scene: out[5i ..] = {s, t, Le.rgb} of light lid[i] at the RAW uniforms
+ *                     (u[2i], u[2i + 1]), the flip included; a light whose material is not bound gives its plain emission.  Refuses a context without
+ *                     emission maps bound and a light index out of range.
+ * NOT BUILT: picking lights by power (the pick stays uniform); emission maps on the wavefront kernel, beside the volume or beside cutouts; emission maps on
+ *   spheres; MIS; mip levels; light_st staged into LDS beside the light records.  Groups: no call; a member is reached through glrtx_group_ctx(grp, i). */
+int glrtx_bind_emission_maps(glrtx_ctx *ctx, const int32_t *material_emission, size_t n_mat);   /* NULL or 0 unbinds */
+int glrtx_debug_light_emission(glrtx_ctx *ctx, const int32_t *lid, const float *u, size_t n, float *out);
+
 /* ---- Groups: the same device layer on several GPUs of one node, behind one handle and one host thread.
  * No reference counterpart (the reference is single-GPU); SURVEY.md 8(b) sketches glrtx_create(ctx**, device_ids, n) with a
  * gathering read_accum -- this is that, kept apart from the single-context calls.  Member i owns the 8-row stripes s with

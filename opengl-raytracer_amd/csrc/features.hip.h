@@ -20,6 +20,9 @@
 // With cutouts bound (glrtx_bind_cutouts; include/glrtx.h "Cutouts") CutArgs<Base> is any of the four textured argument types with the cutout tables behind
 // it: the walk is then trav_step<true, COMPACT, false, true> -- the renderer's CUT step --, so the planes describe the surface the image shows, holes included.
 // store() is Base's.  (A vine never gets here: glrtx_bind_cutouts refuses one.)
+// With emission maps bound (glrtx_bind_emission_maps; include/glrtx.h "Emission maps") EmitArgs<Base> is any of the four textured argument types with the
+// emission table behind it: store() is Base's, then A's rgb again -- the looked-up texel c, without the emission -- for a hit whose material is bound and
+// not diffuse (host/texture.cpp: glrt_emission_albedo states it on plane G).  The walk is Base's; a vine is walked by features_vine_emit<Base>.
 // Each form is launched only while what it adds is bound; the instantiations on Args are what is launched otherwise.
 #pragma once
 #include "query.hip.h"
@@ -169,6 +172,29 @@ struct is_cut : std::false_type {};
 template <class Base>
 struct is_cut<CutArgs<Base>> : std::true_type {};
 
+// With emission maps bound: Base's arguments and store(), then the emitter's picture into A (a bound diffuse material keeps its albedo rule)
+template <class Base>
+struct EmitArgs : Base {
+    EmitSet emit;
+};
+template <class Base>
+DEV void store(const EmitArgs<Base> &q, unsigned id, const Hit &h) {
+    store(static_cast<const Base &>(q), id, h);
+    int lx, lrow;
+    if (h.tri < 0 || !pixel_of(q, id, lx, lrow)) return;
+    const int mtrl = __float_as_int(q.sc.nrms[3 * h.tri].w);
+    const int k = q.emit.mat_emit[mtrl];
+    if (k < 0 || __float_as_int(q.sc.mats[3 * mtrl].w) == 2) return;
+    const float2 st = tex_hit_st(q.tex, h.tri, h.u, h.v);
+    const float3 c = tex_lookup(q.tex, k, st.x, st.y);
+    q.out_a[(size_t)lrow * q.width + lx] = make_float4(c.x, c.y, c.z, __int_as_float(mtrl));
+}
+
+template <class A>
+struct is_emit : std::false_type {};
+template <class Base>
+struct is_emit<EmitArgs<Base>> : std::true_type {};
+
 // Trees: query::trace_tree's loop with the ray made here.  A: the argument type, which chooses store().  The loop is stated in the kernel template and nowhere
 // else: moved into a body shared by __global__ wrappers, the compiler allocated features_tree<*, Args>' registers differently (the same operations, other
 // register numbers and a slightly different schedule), and that kernel is to keep its instructions (tools/isa_diff.py against a build of the parent shows it).
@@ -295,6 +321,8 @@ __global__ __launch_bounds__(kBlockThreads) void features_vine_tex(const TexArgs
 __global__ __launch_bounds__(kBlockThreads) void features_vine_geom_tex(const TexGeomArgs q) { vine_body(q); }
 __global__ __launch_bounds__(kBlockThreads) void features_vine_maps(const MapArgs q) { vine_body(q); }
 __global__ __launch_bounds__(kBlockThreads) void features_vine_geom_maps(const MapGeomArgs q) { vine_body(q); }
+template <class Base>
+__global__ __launch_bounds__(kBlockThreads) void features_vine_emit(const EmitArgs<Base> q) { vine_body(q); }
 
 }  // namespace features
 }  // namespace glrtx

@@ -37,6 +37,7 @@
 #include "../host/morph_sparse.h"
 #include "../host/normal_topology.h"
 #include "../host/texture_set.h"
+#include "../host/emission_statement.h"
 #include "../host/env_tables.h"
 static_assert(glrtx::lbvh::kRotationPasses == GLRT_LBVH_ROTATION_PASSES, "device and CPU LBVH statements must run the same rotation sweeps");
 static_assert(glrtx::lbvh::kRebuildLeaves == GLRT_LBVH_REBUILD_LEAVES, "device and CPU LBVH statements must rebuild the same subtrees");
@@ -118,6 +119,12 @@ struct glrtx_ctx {
     DevBuf cutRec, cutTri;
     bool have_cut = false;
     std::vector<int32_t> scene_mat;
+    // Emission maps (glrtx_bind_emission_maps; texture.hip.h: EmitSet), the set's until the next glrtx_upload_textures or glrtx_upload_scene: the texture index
+    // of every material (-1: none) and light_st, three {s, t} a light; have_emit: the EMIT instantiations are launched, on the megakernel only.
+    // scene_light_st: light_st's source -- words 6 and 7 of the light's three wire vertices, taken from the vertices glrtx_upload_scene was given.
+    DevBuf emitMat, emitSt;
+    bool have_emit = false;
+    std::vector<float> scene_light_st;
     // Environment (glrtx_upload_environment; environment.hip.h), kept across glrtx_upload_scene: the map's texels, the importance grid's five tables, and what the
     // kernels take of it (env: its pointers are these buffers'; p_env is set at every launch).  env_cfg / env_desc: what it was made from.
     DevBuf envTexels, envRowQ, envRowAlias, envColQ, envColAlias, envCellP;
@@ -1040,6 +1047,7 @@ bool tex_wavefront(const glrtx_ctx *c, const char **why_not = nullptr) {
     if (const char *v = std::getenv("GLRTX_TEXTURE_WAVEFRONT")) on = std::atoi(v) != 0;
     const char *why = c->n_tex == 0 ? "no set is bound"
                       : c->have_cut ? "cutouts are bound (the wavefront kernel's traversal step has no cutout form)"
+                      : c->have_emit ? "emission maps are bound (the wavefront kernel's shade phase has no emission-map form)"
                       : !on ? "the texture wavefront switch is off (glrtx_set_texture_wavefront)"
                       : c->ext_flags != 0 ? "extensions or volume are on"
                       : c->n_spheres > 0 ? "spheres are uploaded"
@@ -1441,19 +1449,25 @@ int wgwf_kernel(glrtx_ctx *c, WgwfLaunch &L) {
 // ---- the persistent megakernel (variant 1: render_one): its instantiation and its grid, then the launch.  The ten forms of pt_render_persistent that exist,
 // each with and without ray counting: one table.
 enum PersistForm { kFormPlain, kFormExt, kFormVol, kFormTex, kFormTexVol, kFormTexMaps, kFormTexVolMaps, kFormEnv, kFormEnvTex, kFormEnvTexMaps,
-                   kFormTexCut, kFormTexMapsCut, kFormEnvTexCut, kFormEnvTexMapsCut, kPersistForms };
+                   kFormTexCut, kFormTexMapsCut, kFormEnvTexCut, kFormEnvTexMapsCut, kFormTexEmit, kFormTexMapsEmit, kFormEnvTexEmit, kFormEnvTexMapsEmit,
+                   kPersistForms };
 #define GLRTX_PERSIST_ROW(EXT, VOL, TEX, ENV, MAPS) \
     {(const void *)pt_render_persistent<false, EXT, VOL, TEX, ENV, MAPS>, (const void *)pt_render_persistent<true, EXT, VOL, TEX, ENV, MAPS>}
 #define GLRTX_PERSIST_CUT_ROW(ENV, MAPS) \
     {(const void *)pt_render_persistent<false, true, false, true, ENV, MAPS, true>, (const void *)pt_render_persistent<true, true, false, true, ENV, MAPS, true>}
-// [form][count_rays]; the fourth argument is a VolArgs, in the kFormEnv* rows an EnvArgs, in the k*Cut rows a CutTail of either (include/glrtx.h "Cutouts")
+#define GLRTX_PERSIST_EMIT_ROW(ENV, MAPS) \
+    {(const void *)pt_render_persistent<false, true, false, true, ENV, MAPS, false, Emit>, (const void *)pt_render_persistent<true, true, false, true, ENV, MAPS, false, Emit>}
+// [form][count_rays]; the fourth argument is a VolArgs, in the kFormEnv* rows an EnvArgs, in the k*Cut rows a CutTail of either (include/glrtx.h "Cutouts"),
+// in the k*Emit rows an EmitTail of either (include/glrtx.h "Emission maps")
 const void *const kPersistent[kPersistForms][2] = {
     GLRTX_PERSIST_ROW(false, false, false, false, false), GLRTX_PERSIST_ROW(true, false, false, false, false), GLRTX_PERSIST_ROW(true, true, false, false, false),
     GLRTX_PERSIST_ROW(true, false, true, false, false),   GLRTX_PERSIST_ROW(true, true, true, false, false),   GLRTX_PERSIST_ROW(true, false, true, false, true),
     GLRTX_PERSIST_ROW(true, true, true, false, true),     GLRTX_PERSIST_ROW(true, false, false, true, false),  GLRTX_PERSIST_ROW(true, false, true, true, false),
     GLRTX_PERSIST_ROW(true, false, true, true, true),
-    GLRTX_PERSIST_CUT_ROW(false, false), GLRTX_PERSIST_CUT_ROW(false, true), GLRTX_PERSIST_CUT_ROW(true, false), GLRTX_PERSIST_CUT_ROW(true, true)};
+    GLRTX_PERSIST_CUT_ROW(false, false), GLRTX_PERSIST_CUT_ROW(false, true), GLRTX_PERSIST_CUT_ROW(true, false), GLRTX_PERSIST_CUT_ROW(true, true),
+    GLRTX_PERSIST_EMIT_ROW(false, false), GLRTX_PERSIST_EMIT_ROW(false, true), GLRTX_PERSIST_EMIT_ROW(true, false), GLRTX_PERSIST_EMIT_ROW(true, true)};
 #undef GLRTX_PERSIST_ROW
+#undef GLRTX_PERSIST_EMIT_ROW
 #undef GLRTX_PERSIST_CUT_ROW
 constexpr const char *kPersistentNames[kPersistForms] = {  // (error reports)
     "pt_render_persistent", "pt_render_persistent (extensions)", "pt_render_persistent (volume)", "pt_render_persistent (extensions, textures)",
@@ -1461,8 +1475,10 @@ constexpr const char *kPersistentNames[kPersistForms] = {  // (error reports)
     "pt_render_persistent (extensions, environment)", "pt_render_persistent (extensions, environment, textures)",
     "pt_render_persistent (extensions, environment, textures, maps)",
     "pt_render_persistent (extensions, textures, cutouts)", "pt_render_persistent (extensions, textures, maps, cutouts)",
-    "pt_render_persistent (extensions, environment, textures, cutouts)", "pt_render_persistent (extensions, environment, textures, maps, cutouts)"};
-struct PersistLaunch { const void *fn; const char *name; bool vol, env, cut; int lds, grid; ExtArgs ex; };
+    "pt_render_persistent (extensions, environment, textures, cutouts)", "pt_render_persistent (extensions, environment, textures, maps, cutouts)",
+    "pt_render_persistent (extensions, textures, emission maps)", "pt_render_persistent (extensions, textures, maps, emission maps)",
+    "pt_render_persistent (extensions, environment, textures, emission maps)", "pt_render_persistent (extensions, environment, textures, maps, emission maps)"};
+struct PersistLaunch { const void *fn; const char *name; bool vol, env, cut, emit; int lds, grid; ExtArgs ex; };
 
 // ext: render_one's (spheres, an extension flag, a texture set that is not the wavefront kernel's, an environment); lds: the plain kernel's LDS bytes
 int persist_kernel(glrtx_ctx *c, bool ext, int lds, PersistLaunch &k) {
@@ -1470,12 +1486,15 @@ int persist_kernel(glrtx_ctx *c, bool ext, int lds, PersistLaunch &k) {
     k.vol = (c->ext_flags & GLRTX_EXT_VOLUME) != 0;  // (render_one has checked that a volume is uploaded, and that no environment is bound beside it)
     k.env = c->have_env;
     k.cut = tex && c->have_cut;  // (render_one has refused GLRTX_EXT_VOLUME beside bound cutouts)
-    const int form = k.cut ? (k.env ? kFormEnvTexCut : kFormTexCut) + (maps ? 1 : 0)
+    k.emit = tex && c->have_emit;  // (never beside cutouts: each binding call refuses the other; render_one has refused GLRTX_EXT_VOLUME beside them)
+    const int form = k.emit ? (k.env ? kFormEnvTexEmit : kFormTexEmit) + (maps ? 1 : 0)
+                     : k.cut ? (k.env ? kFormEnvTexCut : kFormTexCut) + (maps ? 1 : 0)
                      : k.env ? (maps ? kFormEnvTexMaps : tex ? kFormEnvTex : kFormEnv)
                      : tex ? kFormTex + (k.vol ? 1 : 0) + (maps ? 2 : 0)
                            : k.vol ? kFormVol : ext ? kFormExt : kFormPlain;
     static_assert(kFormTexVol == kFormTex + 1 && kFormTexMaps == kFormTex + 2 && kFormTexVolMaps == kFormTex + 3, "the TEX rows: [maps][volume]");
     static_assert(kFormTexMapsCut == kFormTexCut + 1 && kFormEnvTexMapsCut == kFormEnvTexCut + 1, "the CUT rows: [environment][maps]");
+    static_assert(kFormTexMapsEmit == kFormTexEmit + 1 && kFormEnvTexMapsEmit == kFormEnvTexEmit + 1, "the EMIT rows: [environment][maps]");
     k.fn = kPersistent[form][c->count_rays];
     k.name = kPersistentNames[form];
     k.ex = ExtArgs{};
@@ -1508,7 +1527,12 @@ int persist_launch(glrtx_ctx *c, const PersistLaunch &k, const KernelArgs &a, hi
     const CutSet cs{(const int *)c->cutTri.p, (const CutRec *)c->cutRec.p};
     const CutTail<VolArgs> va_cut{va, cs};
     const CutTail<EnvArgs> ea_cut{ea, cs};
-    void *const tail = k.cut ? (k.env ? (void *)&ea_cut : (void *)&va_cut) : (k.env ? (void *)&ea : (void *)&va);
+    // the EMIT forms: likewise, with the emission table (pt_kernel.hip.h: EmitTail)
+    const EmitSet es{(const int *)c->emitMat.p, (const float2 *)c->emitSt.p};
+    const EmitTail<VolArgs> va_emit{va, es};
+    const EmitTail<EnvArgs> ea_emit{ea, es};
+    void *const tail = k.emit ? (k.env ? (void *)&ea_emit : (void *)&va_emit)
+                       : k.cut ? (k.env ? (void *)&ea_cut : (void *)&va_cut) : (k.env ? (void *)&ea : (void *)&va);
     void *args[] = {(void *)&a, &work, (void *)&k.ex, tail};
     HIP_TRY(c, hipLaunchKernel(k.fn, dim3(k.grid), dim3(kBlockThreads), args, k.lds, c->stream));
     return GLRTX_OK;
@@ -2366,6 +2390,7 @@ void glrtx_destroy(glrtx_ctx *c) {
         if (sl.feed_h) (void)hipHostFree(sl.feed_h);
     }
     dev_free(c->texDesc); dev_free(c->texTexels); dev_free(c->texSt); dev_free(c->texBind); dev_free(c->texMaps); dev_free(c->cutRec); dev_free(c->cutTri);
+    dev_free(c->emitMat); dev_free(c->emitSt);
     for (DevBuf *b : {&c->envTexels, &c->envRowQ, &c->envRowAlias, &c->envColQ, &c->envColAlias, &c->envCellP}) dev_free(*b);
     dev_free(c->spheres); dev_free(c->sphereMat); dev_free(c->volDensity); dev_free(c->volTemp); dev_free(c->forks); dev_free(c->cnodes); dev_free(c->cranks); dev_free(c->nrms); dev_free(c->mats); dev_free(c->lights); dev_free(c->vine);
     dev_free(c->accum_own); dev_free(c->counter); dev_free(c->rgba8); dev_free(c->work);
@@ -2469,6 +2494,13 @@ int glrtx_upload_scene(glrtx_ctx *c, const float *vert, size_t n_vert, const flo
     c->n_tex = 0;      // ... and so does a texture set's binding (glrtx_upload_textures)
     c->have_maps = false;  // ... and the material maps bound on top of it (glrtx_bind_material_maps)
     c->have_cut = false;   // ... and the cutout records (glrtx_bind_cutouts)
+    c->have_emit = false;  // ... and the emission maps (glrtx_bind_emission_maps)
+    c->scene_light_st.assign(6 * n_light, 0.0f);  // the corners' (s, t) of every light: words 6 and 7 of its three wire vertices, in wire order
+    for (size_t l = 0; l < n_light; l++)
+        for (int j = 0; j < 3; j++) {
+            const float *v = vert + 15 * (size_t)light[4 * l + j];
+            c->scene_light_st[6 * l + 2 * j] = v[6]; c->scene_light_st[6 * l + 2 * j + 1] = v[7];
+        }
     c->scene_mat.assign(c->leaf_tri.size() + 1, -1);  // the material of every device triangle: word 3 of a wire triangle
     for (size_t k = 0; k < c->leaf_tri.size(); k++) c->scene_mat[k + 1] = (int32_t)tri[4 * (size_t)c->leaf_tri[k] + 3];
     c->scene_st.assign(6 * (c->leaf_tri.size() + 1), 0.0f);  // the corners' (s, t) of every device triangle: words 6 and 7 of a wire vertex
@@ -3305,6 +3337,7 @@ int glrtx_upload_textures(glrtx_ctx *c, const glrtx_texture *tex, size_t n_tex, 
         c->n_tex = 0;
         c->have_maps = false;
         c->have_cut = false;
+        c->have_emit = false;
         return GLRTX_OK;
     }
     if (n_mat != (size_t)c->n_mat) return fail(c, GLRTX_EINVAL, "%s: %zu bindings, the scene has %d materials", fn, n_mat, c->n_mat);
@@ -3337,6 +3370,7 @@ int glrtx_upload_textures(glrtx_ctx *c, const glrtx_texture *tex, size_t n_tex, 
     dev_free(c->texDesc); dev_free(c->texTexels); dev_free(c->texSt); dev_free(c->texBind);
     c->have_maps = false;  // (glrtx_bind_material_maps: a new set invalidates the indices)
     c->have_cut = false;   // (glrtx_bind_cutouts: likewise)
+    c->have_emit = false;  // (glrtx_bind_emission_maps: likewise)
     c->tex_format.resize(n_tex);
     for (size_t k = 0; k < n_tex; k++) c->tex_format[k] = tex[k].format;
     c->texDesc = d; c->texTexels = t; c->texSt = st; c->texBind = b;
@@ -3449,6 +3483,7 @@ int glrtx_bind_cutouts(glrtx_ctx *c, const glrtx_cutout *cut, size_t n_mat) {
     if (!c->have_scene || c->n_tex == 0) return fail(c, GLRTX_EINVAL, "%s: no texture set is bound (call glrtx_upload_textures first)", fn);
     if (n_mat != (size_t)c->n_mat) return fail(c, GLRTX_EINVAL, "%s: %zu records, the scene has %d materials", fn, n_mat, c->n_mat);
     if (c->sc.n_vine > 0) return fail(c, GLRTX_EINVAL, "%s: the tree is a vine (the list scan has no cutout form)", fn);
+    if (c->have_emit) return fail(c, GLRTX_EINVAL, "%s: emission maps are bound (glrtx_bind_emission_maps: the two do not combine yet; unbind them first)", fn);
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));  // (also behind every launch that reads the materials or the records bound before)
     std::vector<float4> m0(3 * n_mat);
@@ -3483,6 +3518,70 @@ int glrtx_bind_cutouts(glrtx_ctx *c, const glrtx_cutout *cut, size_t n_mat) {
 }
 
 const char *glrtx_debug_last_kernel(const glrtx_ctx *c) { return c ? c->last_kernel : ""; }
+
+// ---- emission maps (include/glrtx.h "Emission maps"; texture.hip.h: EmitSet, pt_kernel.hip.h: shade_core<.., EMIT>)
+int glrtx_bind_emission_maps(glrtx_ctx *c, const int32_t *material_emission, size_t n_mat) {
+    const char *fn = "glrtx_bind_emission_maps";
+    if (!c) return fail(nullptr, GLRTX_EINVAL, "%s: NULL context", fn);
+    seal_feed(c);  // (nothing is appended to an open launch across this call: glrtx_ctx::OpenFeed)
+    if (!material_emission || n_mat == 0) {  // unbind: the next launch is routed as before (the buffers stay until the context goes)
+        HIP_TRY(c, hipSetDevice(c->device));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        c->have_emit = false;
+        return GLRTX_OK;
+    }
+    std::vector<float4> m0(3 * (size_t)std::max(c->n_mat, 0));
+    if (c->have_scene && !m0.empty()) {
+        HIP_TRY(c, hipSetDevice(c->device));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));  // (also behind every launch that reads the materials or the table bound before)
+        HIP_TRY(c, hipMemcpy(m0.data(), c->mats.p, m0.size() * sizeof(float4), hipMemcpyDeviceToHost));
+    }
+    const std::string bad = glrt_detail::emission_bind_error(c->have_scene, (size_t)c->n_mat, (size_t)c->n_tex, c->have_cut, material_emission, n_mat, [&](size_t m) {
+        int type;
+        std::memcpy(&type, &m0[3 * m].w, 4);
+        return type;
+    });
+    if (!bad.empty()) return fail(c, GLRTX_EINVAL, "%s: %s", fn, bad.c_str());
+    DevBuf b, st;  // fresh buffers first: a failure leaves the bound table as it was
+    int rc;
+    const float no_light[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  // (a scene without lights: the table is never read, the buffer is not empty)
+    const bool lights = !c->scene_light_st.empty();
+    if ((rc = dev_upload(c, b, material_emission, n_mat * sizeof(int32_t))) ||
+        (rc = dev_upload(c, st, lights ? c->scene_light_st.data() : no_light, (lights ? c->scene_light_st.size() : 6) * sizeof(float)))) {
+        dev_free(b); dev_free(st);
+        return rc;
+    }
+    dev_free(c->emitMat); dev_free(c->emitSt);
+    c->emitMat = b; c->emitSt = st;
+    c->have_emit = true;
+    return GLRTX_OK;
+}
+
+int glrtx_debug_light_emission(glrtx_ctx *c, const int32_t *lid, const float *u, size_t n, float *out) {
+    const char *fn = "glrtx_debug_light_emission";
+    if (!c) return fail(nullptr, GLRTX_EINVAL, "%s: NULL context", fn);
+    if (!c->have_scene || c->n_tex == 0 || !c->have_emit) return fail(c, GLRTX_EINVAL, "%s: no emission maps are bound (glrtx_bind_emission_maps)", fn);
+    if (n && (!lid || !u || !out)) return fail(c, GLRTX_EINVAL, "%s: NULL buffer", fn);
+    if (n > (size_t)INT32_MAX / 8) return fail(c, GLRTX_EINVAL, "%s: too many samples", fn);
+    for (size_t i = 0; i < n; i++)
+        if (lid[i] < 0 || lid[i] >= c->n_light) return fail(c, GLRTX_EINVAL, "%s: sample %zu names light %d of %d", fn, i, lid[i], c->n_light);
+    if (n == 0) return GLRTX_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    DebugScratch s;
+    const int *d_lid = s.alloc<int>(n * sizeof(int), lid);
+    const float *d_u = s.alloc<float>(2 * n * sizeof(float), u);
+    float *d_out = s.alloc<float>(5 * n * sizeof(float));
+    if (s.ok()) {
+        const EmitSet es{(const int *)c->emitMat.p, (const float2 *)c->emitSt.p};
+        hipLaunchKernelGGL(emit_light_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, tex_set(c), es, (const float4 *)c->lights.p, (const float4 *)c->mats.p,
+                           d_lid, d_u, (unsigned)n, d_out);
+        s.e = hipGetLastError();
+    }
+    s.sync();
+    s.download(out, d_out, 5 * n * sizeof(float));
+    return s.result(GLRTX_OK, fn);
+}
 
 int glrtx_debug_texture_channel(const glrtx_texture *tex, size_t n_tex, const void *texels, size_t texel_bytes, const int32_t *which, const int32_t *channel,
                                 const float *st, size_t n, float *value_out) {
@@ -4132,6 +4231,7 @@ int glrtx_render_features(glrtx_ctx *c, const glrtx_params *p) {
         if constexpr (std::is_base_of_v<features::GeomArgs, A>) { q.out_g = (float4 *)c->ftG.p; q.wire = (const int *)c->qwire.p; }
         if constexpr (std::is_base_of_v<features::TexArgs, A> || std::is_base_of_v<features::TexGeomArgs, A>) q.tex = tex_set(c);
         if constexpr (features::is_cut<A>::value) q.cut = CutSet{(const int *)c->cutTri.p, (const CutRec *)c->cutRec.p};
+        if constexpr (features::is_emit<A>::value) q.emit = EmitSet{(const int *)c->emitMat.p, (const float2 *)c->emitSt.p};
         std::memcpy(c->ft_cam, a.cam, sizeof c->ft_cam);  // (glrtx_reproject: the camera these planes belong to)
         const size_t needed = (a.n + kBlockThreads - 1) / kBlockThreads;
         const unsigned grid = (unsigned)std::max<size_t>(1, std::min<size_t>((size_t)per_cu * (size_t)c->n_cu, needed));
@@ -4144,6 +4244,11 @@ int glrtx_render_features(glrtx_ctx *c, const glrtx_params *p) {
         using namespace features;
         if (maps) return geom ? launch(CutArgs<MapGeomArgs>{}, nullptr) : launch(CutArgs<MapArgs>{}, nullptr);
         return geom ? launch(CutArgs<TexGeomArgs>{}, nullptr) : launch(CutArgs<TexArgs>{}, nullptr);
+    }
+    if (tex && c->have_emit) {  // emission maps bound (never beside cutouts): the same arguments, walk and planes, then the emitter's picture in A
+        using namespace features;
+        if (maps) return geom ? launch(EmitArgs<MapGeomArgs>{}, features_vine_emit<MapGeomArgs>) : launch(EmitArgs<MapArgs>{}, features_vine_emit<MapArgs>);
+        return geom ? launch(EmitArgs<TexGeomArgs>{}, features_vine_emit<TexGeomArgs>) : launch(EmitArgs<TexArgs>{}, features_vine_emit<TexArgs>);
     }
     if (maps) return geom ? launch(features::MapGeomArgs{}, features::features_vine_geom_maps) : launch(features::MapArgs{}, features::features_vine_maps);
     if (tex) return geom ? launch(features::TexGeomArgs{}, features::features_vine_geom_tex) : launch(features::TexArgs{}, features::features_vine_tex);
@@ -4891,6 +4996,8 @@ static int render_one(glrtx_ctx *c, const glrtx_params *p, const RenderReq &req)
         return fail(c, GLRTX_EINVAL, "glrtx_render: GLRTX_EXT_VOLUME is set and an environment is bound (the volume branch has its own escape path)");
     if ((c->ext_flags & GLRTX_EXT_VOLUME) && c->have_volume && c->n_tex > 0 && c->have_cut)
         return fail(c, GLRTX_EINVAL, "glrtx_render: GLRTX_EXT_VOLUME is set and cutouts are bound (the volume kernels have no cutout form)");
+    if ((c->ext_flags & GLRTX_EXT_VOLUME) && c->have_volume && c->n_tex > 0 && c->have_emit)
+        return fail(c, GLRTX_EINVAL, "glrtx_render: GLRTX_EXT_VOLUME is set and emission maps are bound (the volume kernels have no emission-map form)");
     HIP_TRY(c, hipSetDevice(c->device));
     const bool wavefront = wgwf_routes(c, p);
     if (c->owned_rows > 0 && wavefront && req.kind == RenderReq::Ordinary && req.n_frames == 1 && feed_append(c, p, p->seed, 1) == 1) {  // a launch of the same camera that is still open takes the frame itself
@@ -5063,6 +5170,7 @@ int glrtx_hit_histogram(glrtx_ctx *c, const glrtx_params *p, uint32_t *hist_out,
     if (!c->accum || c->width < 1 || c->owned_rows < 1) return fail(c, GLRTX_EINVAL, "glrtx_hit_histogram: no image size (call glrtx_resize)");
     if (n_tri != (size_t)c->n_tri) return fail(c, GLRTX_EINVAL, "glrtx_hit_histogram: the scene has %d triangles, room for %zu", c->n_tri, n_tri);
     if (c->n_tex > 0 && c->have_cut) return fail(c, GLRTX_EINVAL, "glrtx_hit_histogram: textures are bound and cutouts are bound (wavefront kernel only)");
+    if (c->n_tex > 0 && c->have_emit) return fail(c, GLRTX_EINVAL, "glrtx_hit_histogram: textures are bound and emission maps are bound (wavefront kernel only)");
     if (c->n_tex > 0) return fail(c, GLRTX_EINVAL, "glrtx_hit_histogram: textures are bound (wavefront kernel only)");
     if (c->have_env) return fail(c, GLRTX_EINVAL, "glrtx_hit_histogram: an environment is bound (wavefront kernel only)");
     if (c->variant != 2 || !wgwf_can_hold(p) || c->n_spheres > 0 || c->ext_flags != 0) return fail(c, GLRTX_EINVAL, "glrtx_hit_histogram: wavefront kernel only");

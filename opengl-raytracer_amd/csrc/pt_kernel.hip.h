@@ -994,10 +994,15 @@ constexpr int EXT_WHITTED = 2;     // Whitted-style: a diffuse surface gathers i
 // rule (:490) in sampled mode --, and in sampled mode the environment is one more light of sampleDirect, picked with probability env->p_env.
 // MAPS (implies TEX; include/glrtx.h "Material maps"): S carries the mapped normal n' already (bounce_ext), which then stands wherever the reference reads the
 // shading normal; `rough` says that the hit's conductor is bound to a roughness map and (rax, ray) REPLACE alpha.x / alpha.y at the three places they are read.
-template <bool EXT, bool TEX = false, bool ENV = false, bool MAPS = false>
+// EMIT (implies TEX; include/glrtx.h "Emission maps"): `lit` says that the hit's material is bound to an emission map and (er, eg, eb) is the texel c looked
+// up at the hit, so that the two places that add beta * emission add beta * Le, Le = emission * c; in sampleDirect's triangle-light branch a light whose
+// material is bound (em->mat_emit) has its sample's coordinates mixed from em->light_st and LM.m0 replaced by Le, looked up in *ets only where the sample
+// contributes.  The random stream, the shadow ray and the ray counts are the TEX form's.
+template <bool EXT, bool TEX = false, bool ENV = false, bool MAPS = false, bool EMIT = false>
 DEV void shade_core(const KernelArgs &a, const float4 *lds_mats, Rng &rng, Path &P, float h_t, bool h_hit, const Surf &S, int ext_flags, Shade &out,
                     bool textured = false, float ar = 0.f, float ag = 0.f, float ab = 0.f, const EnvArgs *env = nullptr, bool rough = false, float rax = 0.f,
-                    float ray = 0.f) {
+                    float ray = 0.f, const TexSet *ets = nullptr, const EmitSet *em = nullptr, bool lit = false, float er = 0.f, float eg = 0.f, float eb = 0.f) {
+    static_assert(!EMIT || TEX, "emission maps are looked up in the bound texture set");
     static_assert(!TEX || EXT, "textures are shaded by the extension kernel");
     static_assert(!MAPS || TEX, "material maps are looked up in the bound texture set");
     static_assert(!ENV || EXT, "the environment is shaded by the extension kernel");
@@ -1038,6 +1043,12 @@ DEV void shade_core(const KernelArgs &a, const float4 *lds_mats, Rng &rng, Path 
             // or the refracted direction with the unpolarised Fresnel reflectance as probability (weight = tint either way);
             // delta BSDF: no light sampling; emission met on the next bounce counts (the "specularReflect" the reference
             // declares at :490 and never sets).
+            if (EMIT && lit) {
+                if (depth == 0 || P.spec) {
+                    const float lex = M.m0.x * er, ley = M.m0.y * eg, lez = M.m0.z * eb;
+                    Lx = Lx + bx * lex; Ly = Ly + by * ley; Lz = Lz + bz * lez;
+                }
+            } else
             if (depth == 0 || P.spec) { Lx = Lx + bx * M.m0.x; Ly = Ly + by * M.m0.y; Lz = Lz + bz * M.m0.z; }
             const float rl = rsq(dot3(dx, dy, dz, dx, dy, dz));  // directions are not renormalised along a path (:542)
             const float ux = dx * rl, uy = dy * rl, uz = dz * rl;
@@ -1070,6 +1081,12 @@ DEV void shade_core(const KernelArgs &a, const float4 *lds_mats, Rng &rng, Path 
             bx = bx * M.m1.x; by = by * M.m1.y; bz = bz * M.m1.z;
             spec_out = true;
         } else {
+            if (EMIT && lit) {
+                if (depth == 0 || P.spec) {
+                    const float lex = M.m0.x * er, ley = M.m0.y * eg, lez = M.m0.z * eb;
+                    Lx = Lx + bx * lex; Ly = Ly + by * ley; Lz = Lz + bz * lez;
+                }
+            } else
             if (depth == 0 || (EXT && P.spec)) {  // :490-494 (specularReflect / passedVolume are never set by the reference)
                 Lx = Lx + bx * M.m0.x; Ly = Ly + by * M.m0.y; Lz = Lz + bz * M.m0.z;
             }
@@ -1281,9 +1298,17 @@ DEV void shade_core(const KernelArgs &a, const float4 *lds_mats, Rng &rng, Path 
                         const float area = 0.5f * __builtin_sqrtf((kz * kz + ky * ky) + kx * kx);
                         float lpdf = frcp(area * nLf);
                         if (env_on) lpdf = lpdf * (1.0f - env->p_env);  // (p_env = 0: x * 1 = x)
+                        if (EMIT && lid >= 0 && em->mat_emit[__float_as_int(V0.w)] >= 0) {  // a bound light: Le at the sample's coordinates stands for LM.m0
+                            const float2 lst = emit_light_st(*em, lid, ua, ub);
+                            const float3 le = emit_radiance(*ets, em->mat_emit[__float_as_int(V0.w)], lst.x, lst.y, LM.m0.x, LM.m0.y, LM.m0.z);
+                            cx = fdiv((le.x * gx) * G, lpdf);
+                            cy = fdiv((le.y * gy) * G, lpdf);
+                            cz = fdiv((le.z * gz) * G, lpdf);
+                        } else {
                         cx = fdiv((LM.m0.x * gx) * G, lpdf);
                         cy = fdiv((LM.m0.y * gy) * G, lpdf);
                         cz = fdiv((LM.m0.z * gz) * G, lpdf);
+                        }
                     }
                 }
                 }  // (a triangle light)
@@ -1544,11 +1569,14 @@ DEV bool bounce_volume(const KernelArgs &a, const ExtArgs &ex, const VolArgs &vo
 
 // CUT (include/glrtx.h "Cutouts"; cs: the bound cutout tables): all three rays -- the path's, the shadow ray to a triangle light, the shadow ray to the
 // environment -- are traced with the CUT step.  Shading is the TEX forms' as it is: a rejected candidate was never a hit.
-template <bool VOL = false, bool TEX = false, bool ENV = false, bool MAPS = false, bool CUT = false>
+// EMIT (include/glrtx.h "Emission maps"; em: the bound emission table): the texel c of a hit on a bound material is looked up here, only where the hit's
+// emission counts (depth 0 or behind a specular bounce), and passed down the way alb is; shade_core<.., true> does the rest.
+template <bool VOL = false, bool TEX = false, bool ENV = false, bool MAPS = false, bool CUT = false, bool EMIT = false>
 DEV bool bounce_ext(const KernelArgs &a, const ExtArgs &ex, const float4 *lds_spheres, const float4 *lds_mats, int *stack, Rng &rng, Path &P, unsigned long long &rays,
-                    const VolArgs *vo = nullptr, const EnvArgs *env = nullptr, const CutSet *cs = nullptr) {
+                    const VolArgs *vo = nullptr, const EnvArgs *env = nullptr, const CutSet *cs = nullptr, const EmitSet *em = nullptr) {
     static_assert(!(ENV && VOL), "the volume branch has its own escape path: no environment beside it");
     static_assert(!CUT || (TEX && !VOL), "cutouts read the texture set; none beside the volume");
+    static_assert(!EMIT || (TEX && !VOL && !CUT), "emission maps read the texture set; none beside the volume or cutouts");
     const CutRef cut_ref{&ex.tex, cs};
     const CutRef *const cut = CUT ? &cut_ref : nullptr;
     const Hit h = traverse_ext<true, CUT>(a.sc, ex, lds_spheres, stack, P.ox, P.oy, P.oz, P.dx, P.dy, P.dz, PT_INFTY, -__builtin_inff(), cut);
@@ -1580,6 +1608,18 @@ DEV bool bounce_ext(const KernelArgs &a, const ExtArgs &ex, const float4 *lds_sp
                 textured = true;
             }
         }
+        bool lit = false;
+        float3 ec = make_float3(0.f, 0.f, 0.f);
+        if constexpr (EMIT) {  // a triangle whose material is bound to an emission map, where shade_core will add its emission: the texel at the hit's coordinates
+            if (h.tri >= 0 && (P.depth == 0 || P.spec)) {
+                const int k = em->mat_emit[S.mtrl];
+                if (k >= 0) {
+                    const float2 st = tex_hit_st(ex.tex, h.tri, h.u, h.v);
+                    ec = tex_lookup(ex.tex, k, st.x, st.y);
+                    lit = true;
+                }
+            }
+        }
         if (MAPS) {
             // a triangle whose material is bound to a map (glrtx_bind_material_maps): n' takes the place of surf_tri's normal, a conductor's alphas come from the
             // roughness texel.  The test is wave-uniform wherever a wave's hits lie on one material; spheres have no coordinates and shade unmapped.
@@ -1599,8 +1639,16 @@ DEV bool bounce_ext(const KernelArgs &a, const ExtArgs &ex, const float4 *lds_sp
                     }
                 }
             }
+            if constexpr (EMIT)
+                shade_core<true, true, ENV, true, true>(a, lds_mats, rng, P, h.t, h.tri != -1, S, ex.flags, sh, textured, alb.x, alb.y, alb.z, env, rough, al.x, al.y, &ex.tex,
+                                                        em, lit, ec.x, ec.y, ec.z);
+            else
             shade_core<true, true, ENV, true>(a, lds_mats, rng, P, h.t, h.tri != -1, S, ex.flags, sh, textured, alb.x, alb.y, alb.z, env, rough, al.x, al.y);
         } else {
+            if constexpr (EMIT)
+                shade_core<true, true, ENV, false, true>(a, lds_mats, rng, P, h.t, h.tri != -1, S, ex.flags, sh, textured, alb.x, alb.y, alb.z, env, false, 0.f, 0.f, &ex.tex, em,
+                                                         lit, ec.x, ec.y, ec.z);
+            else
             shade_core<true, true, ENV>(a, lds_mats, rng, P, h.t, h.tri != -1, S, ex.flags, sh, textured, alb.x, alb.y, alb.z, env);
         }
     } else if (ENV) {
@@ -1786,8 +1834,15 @@ struct CutTail {
     Base base;
     CutSet cut;
 };
-template <class Base, bool CUT>
-using PersistTail = std::conditional_t<CUT, CutTail<Base>, Base>;
+// ... and in the EMIT forms an EmitTail: the emission table in the same place (the two do not combine).  Emit: what names an EMIT form of the kernel.
+struct Emit {};
+template <class Base>
+struct EmitTail {
+    Base base;
+    EmitSet emit;
+};
+template <class Base, bool CUT, bool EMIT = false>
+using PersistTail = std::conditional_t<EMIT, EmitTail<Base>, std::conditional_t<CUT, CutTail<Base>, Base>>;
 template <class Tail>
 struct PersistKernArgs {
     KernelArgs a;
@@ -1802,7 +1857,7 @@ DEV const PersistKernArgs<Tail> *persist_kernargs() {
     return (const PersistKernArgs<Tail> *)p;
 }
 
-// The forms (glrtx.hip: kPersistent lists the ten that are launched):
+// The forms (glrtx.hip: kPersistent lists those that are launched):
 // EXT: the extension kernel (bounce_ext: analytic spheres, dielectric, Whitted termination).  VOL: with the volume branch (bounce_volume).
 // TEX: textured albedo (include/glrtx.h "Textures"; bounce_ext<VOL, true> looks the albedo up), launched only while a texture set is bound.
 // MAPS: material maps on top of the set (include/glrtx.h "Material maps"), launched only while maps are bound.
@@ -1813,11 +1868,19 @@ DEV const PersistKernArgs<Tail> *persist_kernargs() {
 // The loop is stated here, in the kernel template, and nowhere else: every instantiation is the syntax tree a kernel written out by hand would be.  Called
 // from a body shared by thin __global__ wrappers, the compiler allocated the registers of every instantiation differently (the same operations, another
 // schedule), and a change of form is to leave the instructions of the forms it does not touch alone: tools/isa_diff.py against a build of the parent shows it.
-template <bool COUNT_RAYS, bool EXT = false, bool VOL = false, bool TEX = false, bool ENV = false, bool MAPS = false, bool CUT = false>
+// EMIT (implies TEX, excludes VOL and CUT; include/glrtx.h "Emission maps"): emission maps are bound -- bounce_ext<.., true> looks a bound emitter's texel up
+// where it is seen, shade_core<.., true> where it is sampled as a light; the fourth argument is an EmitTail.  Launched only while emission maps are bound.
+// EMIT is written as a trailing pack that is empty or the one tag type Emit: the forms without it keep their seven-argument names --
+// pt_render_persistent<.., CUT> --, which tools/isa_report.py, tools/isa_diff.py's rename rules and the tests that list the CUT forms quote; an EMIT form is
+// pt_render_persistent<.., false, glrtx::Emit>.
+template <bool COUNT_RAYS, bool EXT = false, bool VOL = false, bool TEX = false, bool ENV = false, bool MAPS = false, bool CUT = false, class... EMIT_TAG>
 __global__ __launch_bounds__(kBlockThreads) void pt_render_persistent(const KernelArgs a_entry, unsigned *work_counter_entry, const ExtArgs ex_entry,
-                                                                      const PersistTail<std::conditional_t<ENV, EnvArgs, VolArgs>, CUT> tail_entry) {
-    using Tail = PersistTail<std::conditional_t<ENV, EnvArgs, VolArgs>, CUT>;
+                                                                      const PersistTail<std::conditional_t<ENV, EnvArgs, VolArgs>, CUT, (sizeof...(EMIT_TAG) > 0)> tail_entry) {
+    static_assert(sizeof...(EMIT_TAG) == 0 || (sizeof...(EMIT_TAG) == 1 && (std::is_same_v<EMIT_TAG, Emit> && ...)), "EMIT: the tag Emit, or nothing");
+    constexpr bool EMIT = sizeof...(EMIT_TAG) > 0;
+    using Tail = PersistTail<std::conditional_t<ENV, EnvArgs, VolArgs>, CUT, EMIT>;
     static_assert(!CUT || (TEX && !VOL), "CUT is a form of the textured kernels; none beside the volume");
+    static_assert(!EMIT || (TEX && !VOL && !CUT), "EMIT is a form of the textured kernels; none beside the volume or cutouts");
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     float4 *lds_mats;
     int *stack;
@@ -1897,7 +1960,11 @@ __global__ __launch_bounds__(kBlockThreads) void pt_render_persistent(const Kern
             }
             bool finished = true;
             if (a.max_depth > 0) {
-                if constexpr (CUT && ENV) {
+                if constexpr (EMIT && ENV) {
+                    finished = bounce_ext<false, true, true, MAPS, false, true>(a, ka->ex, lds_spheres, lds_mats, stack, rng, P, rays, nullptr, &ka->tail.base, nullptr, &ka->tail.emit);
+                } else if constexpr (EMIT) {
+                    finished = bounce_ext<false, true, false, MAPS, false, true>(a, ka->ex, lds_spheres, lds_mats, stack, rng, P, rays, nullptr, nullptr, nullptr, &ka->tail.emit);
+                } else if constexpr (CUT && ENV) {
                     finished = bounce_ext<false, true, true, MAPS, true>(a, ka->ex, lds_spheres, lds_mats, stack, rng, P, rays, nullptr, &ka->tail.base, &ka->tail.cut);
                 } else if constexpr (CUT) {
                     finished = bounce_ext<false, true, false, MAPS, true>(a, ka->ex, lds_spheres, lds_mats, stack, rng, P, rays, nullptr, nullptr, &ka->tail.cut);

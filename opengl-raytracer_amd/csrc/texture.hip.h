@@ -197,6 +197,45 @@ TEX_DEV bool cut_accepts(const CutRef &cr, int tri, float u, float v) {
     return tex_lookup_channel(*cr.tex, r.texture, r.channel, st.x, st.y) >= r.cutoff;
 }
 
+// Emission maps (include/glrtx.h "Emission maps"; glrtx_bind_emission_maps).  mat_emit: texture index a material, -1 unbound.  light_st: three {s, t} a light
+// (the uv words of the light's three vertices in wire order), frozen when the maps are bound.  Passed to the EMIT kernels behind their last argument, and
+// to the textured feature kernels while emission maps are bound; nothing else reads it.
+struct EmitSet {
+    const int *mat_emit;
+    const float2 *light_st;
+};
+// The sample (ua, ub) -- after the flip -- of light `lid`: the order sampleDirect mixes the light's vertices in
+TEX_DEV float2 emit_light_st(const EmitSet &es, int lid, float ua, float ub) {
+    const float2 a = es.light_st[3 * lid], b = es.light_st[3 * lid + 1], c = es.light_st[3 * lid + 2];
+    const float w0 = (1.0f - ua) - ub;
+    return make_float2((w0 * a.x + ua * b.x) + ub * c.x, (w0 * a.y + ua * b.y) + ub * c.y);
+}
+// Le = emission * c, per channel: one rounded product
+TEX_DEV float3 emit_radiance(const TexSet &ts, int index, float s, float t, float ex, float ey, float ez) {
+    const float3 c = tex_lookup(ts, index, s, t);
+    return make_float3(ex * c.x, ey * c.y, ez * c.z);
+}
+
+// glrtx_debug_light_emission: out[5i..] = {s, t, Le.rgb} of light lid[i] at the raw uniforms u[2i..] (the flip is taken here, as sampleDirect takes it).
+// lights: six float4 a light, {v0, material} first; mats: three float4 a material, {emission, type} first.
+__global__ __launch_bounds__(256) void emit_light_kernel(const TexSet ts, const EmitSet es, const float4 *lights, const float4 *mats, const int *lid, const float *u,
+                                                         unsigned n, float *out) {
+    const unsigned i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const float ua0 = u[2 * i], ub0 = u[2 * i + 1];
+    const bool flip = 1.0f < ua0 + ub0;
+    const float ua = flip ? 1.0f - ua0 : ua0;
+    const float ub = flip ? 1.0f - ub0 : ub0;
+    const int l = lid[i];
+    const int m = __float_as_int(lights[6 * l].w);
+    const float4 m0 = mats[3 * m];
+    const float2 st = emit_light_st(es, l, ua, ub);
+    const int k = es.mat_emit[m];
+    float3 le = make_float3(m0.x, m0.y, m0.z);
+    if (k >= 0) le = emit_radiance(ts, k, st.x, st.y, m0.x, m0.y, m0.z);
+    out[5 * i] = st.x; out[5 * i + 1] = st.y; out[5 * i + 2] = le.x; out[5 * i + 3] = le.y; out[5 * i + 4] = le.z;
+}
+
 // glrtx_debug_texture_channel: out[i] = tex_lookup_channel(which[i], channel[i], st[2i], st[2i + 1])
 __global__ __launch_bounds__(256) void tex_channel_kernel(const TexSet ts, const int *which, const int *channel, const float *st, unsigned n, float *out) {
     const unsigned i = blockIdx.x * 256u + threadIdx.x;

@@ -33,7 +33,9 @@ static void usage(const char *exe) {
                 "                          \"dielectric\" (ior, tint), and a diffuse shape's \"texture\": {\"file\": x.ppm | x.pfm, \"filter\", \"wrap\", \"srgb\"}\n"
                 "                          (looked up at the OBJ's vt coordinates); parity with the reference is not defined for such scenes;\n"
                 "                          a diffuse or conductor shape's \"cutout\": {\"file\": mask.ppm | mask.pfm, \"channel\": \"r\" | \"g\" | \"b\", \"cutoff\",\n"
-                "                          \"filter\", \"wrap\"} (an alpha test inside the ray search: hits count where the mask's channel >= cutoff)\n"
+                "                          \"filter\", \"wrap\"} (an alpha test inside the ray search: hits count where the mask's channel >= cutoff);\n"
+                "                          an emitter shape's \"emission_map\": {\"file\": x.ppm | x.pfm, \"filter\", \"wrap\", \"srgb\"} (multiplies the emission,\n"
+                "                          where the emitter is seen and where it is sampled as a light)\n"
                 "                          and the top-level \"environment\": {\"file\": x.pfm | x.ppm, \"layout\": \"latlong\" | \"octahedral\", \"size\", \"mode\", \"scale\",\n"
                 "                          \"rotate_y\", \"light_pick\", \"filter\", \"srgb\"} (light from an HDR map where a ray leaves the scene; not with --enable-volume)\n"
                 "      --env-mode M        with --extensions: \"escape\" or \"sampled\", overrides the \"environment\" block's \"mode\"\n"

@@ -51,6 +51,7 @@ void Scene::parse(const std::string &filename) {
     textures_.clear();
     maps_.clear();
     cutouts_.clear();
+    emissionMaps_.clear();
     environment_ = EnvironmentSpec{};
     hasDielectric_ = false;
     volumeSpecs_.clear();
@@ -196,6 +197,39 @@ void Scene::parse(const std::string &filename) {
             fill3(m.type, (float)MaterialType::Emitter);
             if (sh["emission"].is_null()) GLRT_Warn("emitter node does not have \"emission\" key!");
             else vec3(sh["emission"], m.emission);
+            if (extensions_ && !sh["emission_map"].is_null()) {  // EXTENSION (scene.h: emissionMapSpecs); off, the key is one the parser does not know
+                const Json &tx = sh["emission_map"];
+                if (!tx.is_object()) GLRT_FatalError("shape %zu: \"emission_map\" is not an object", i);
+                TextureSpec spec;
+                spec.material = materials.size();
+                if (!tx["file"].is_string() || tx["file"].string_value().empty()) GLRT_FatalError("shape %zu: \"emission_map\" has no \"file\" string", i);
+                spec.file = baseDir + "/" + tx["file"].string_value();
+                spec.filter = GLRTX_TEX_BILINEAR;
+                if (!tx["filter"].is_null()) {
+                    const std::string v = tx["filter"].is_string() ? tx["filter"].string_value() : std::string();
+                    if (v == "bilinear") spec.filter = GLRTX_TEX_BILINEAR;
+                    else if (v == "nearest") spec.filter = GLRTX_TEX_NEAREST;
+                    else GLRT_FatalError("shape %zu: emission_map \"filter\" is not \"bilinear\" or \"nearest\"", i);
+                }
+                spec.wrap = GLRTX_TEX_REPEAT;
+                if (!tx["wrap"].is_null()) {
+                    const std::string v = tx["wrap"].is_string() ? tx["wrap"].string_value() : std::string();
+                    if (v == "repeat") spec.wrap = GLRTX_TEX_REPEAT;
+                    else if (v == "clamp") spec.wrap = GLRTX_TEX_CLAMP;
+                    else GLRT_FatalError("shape %zu: emission_map \"wrap\" is not \"repeat\" or \"clamp\"", i);
+                }
+                bool srgb = true;
+                if (!tx["srgb"].is_null()) {
+                    if (!tx["srgb"].is_bool()) GLRT_FatalError("shape %zu: emission_map \"srgb\" is not true or false", i);
+                    srgb = tx["srgb"].bool_value();
+                }
+                std::string terr;
+                if (!readTextureFile(spec.file, spec.image, terr)) GLRT_FatalError("shape %zu: emission_map \"file\": %s", i, terr.c_str());
+                spec.format = spec.image.isFloat ? GLRTX_TEX_RGBA32F : srgb ? GLRTX_TEX_RGBA8_SRGB : GLRTX_TEX_RGBA8_UNORM;
+                GLRT_Info("emission map: %s, %d x %d, %s", spec.file.c_str(), spec.image.width, spec.image.height,
+                          spec.image.isFloat ? "float" : srgb ? "8-bit sRGB" : "8-bit linear");
+                emissionMaps_.push_back(std::move(spec));
+            }
         } else if (material == "media") {
             // The reference uploads two 3D textures here, but its shader's volume branch is compiled
             // out (raytrace.frag:4, :424-487): the material only marks the surface as pass-through -- unless enableVolume(true).
@@ -807,6 +841,27 @@ struct SceneTextureProbe {
 
 extern "C" GLRT_API int glrt_scene_texture_probe(const char *json, int extensions, long long counts[2], int *info, unsigned char *texels, size_t texel_cap) {
     return glrt::SceneTextureProbe::run(json, extensions, counts, info, texels, texel_cap);
+}
+
+// Emission-map probe: parse with extensions on or off.  Returns the number of emission maps; per map info[6k..] = {material, width, height, format, wrap, filter}.
+namespace glrt {
+struct SceneEmissionProbe {
+    static int run(const char *json, int extensions, int *info, int cap) {
+        Scene sc;
+        sc.enableExtensions(extensions != 0);
+        sc.parse(json);
+        for (size_t k = 0; k < sc.emissionMaps_.size() && (int)k < cap; k++) {
+            const Scene::TextureSpec &t = sc.emissionMaps_[k];
+            const int row[6] = {(int)t.material, t.image.width, t.image.height, t.format, t.wrap, t.filter};
+            if (info) std::memcpy(info + 6 * k, row, sizeof row);
+        }
+        return (int)sc.emissionMaps_.size();
+    }
+};
+}  // namespace glrt
+
+extern "C" GLRT_API int glrt_scene_emission_probe(const char *json, int extensions, int *info, int cap) {
+    return glrt::SceneEmissionProbe::run(json, extensions, info, cap);
 }
 
 // Material-map probe: parse with extensions on or off.  Returns the number of maps; per map info[7k..] = {material, roughness (0 / 1), width, height, format,

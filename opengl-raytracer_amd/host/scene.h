@@ -101,6 +101,13 @@ public:
         TextureImage image;
     };
     const std::vector<CutoutSpec> &cutoutSpecs() const { return cutouts_; }
+    // Emission maps (include/glrtx.h "Emission maps"; no reference counterpart).  With extensions on, an "emitter" shape may carry
+    //     "emission_map": {"file": "x.ppm" | "x.pfm", "filter": .., "wrap": .., "srgb": ..}
+    // with the keys of "texture" and their defaults (a PPM is sRGB unless "srgb": false).  The map is looked up at the OBJ's vt coordinates and MULTIPLIES the
+    // shape's "emission", where the emitter is seen and where next-event estimation samples it.  A value other than those above is a FatalError that names
+    // the shape and the key.  Window uploads the images behind the textures, maps and masks in the one set and binds them (glrtx_bind_emission_maps); a scene
+    // that carries both a "cutout" and an "emission_map" is refused there, as the device refuses it.  With extensions off the key is ignored, as "texture" is.
+    const std::vector<TextureSpec> &emissionMapSpecs() const { return emissionMaps_; }
     // Environment (include/glrtx.h "Environment"; no reference counterpart).  With extensions on, the scene file may carry the top-level key
     //     "environment": {"file": "x.pfm" | "x.ppm", "layout": "latlong" | "octahedral", "size": N, "mode": "escape" | "sampled", "scale": x | [r, g, b],
     //                     "rotate_y": degrees, "light_pick": p, "filter": "bilinear" | "nearest", "srgb": true | false}
@@ -199,6 +206,7 @@ private:
     std::vector<TextureSpec> textures_;  // extension: one per textured diffuse shape, in shape order
     std::vector<MapSpec> maps_;          // extension: the shapes' normal and roughness maps, in shape order
     std::vector<CutoutSpec> cutouts_;    // extension: the shapes' cutout masks, in shape order
+    std::vector<TextureSpec> emissionMaps_;  // extension: the emitter shapes' emission maps, in shape order
     EnvironmentSpec environment_;        // extension: the scene file's "environment" block
     int envModeOverride_ = -1;
     bool extensions_ = false, whitted_ = false, hasDielectric_ = false;
@@ -226,6 +234,7 @@ private:
     friend struct SceneTextureProbe;
     friend struct SceneMapProbe;
     friend struct SceneCutoutProbe;
+    friend struct SceneEmissionProbe;
     friend struct SceneEnvironmentProbe;
 };
 

@@ -4,7 +4,9 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <vector>
 
+#include "emission_statement.h"
 #include "glrt_host.h"
 #include "statement_math.h"
 #include "texture_set.h"
@@ -208,6 +210,93 @@ int glrt_texture_albedo(const float *vert, size_t n_vert, const float *tri, size
         const float s = (w0 * a[0] + u * b[0]) + v * c[0];
         const float q = (w0 * a[1] + u * b[1]) + v * c[1];
         lookup(rec[material_texture[id]], (const unsigned char *)texels, s, q, A);
+    }
+    return GLRT_HOST_OK;
+}
+
+// ---- emission maps (include/glrtx.h "Emission maps"): the CPU statements of the sampled-side rule and of the feature pass's plane A
+
+int glrt_light_st(const float *vert, size_t n_vert, const float *light, size_t n_light, float *st_out) {
+    if (n_light && (!vert || !light || !st_out)) return GLRT_HOST_EINVAL;
+    for (size_t l = 0; l < n_light; l++)
+        for (int j = 0; j < 3; j++) {
+            const float i = light[4 * l + j];
+            if (!(i >= 0.0f) || (size_t)i >= n_vert) return GLRT_HOST_EINDEX;
+            const float *v = vert + GLRT_VERTEX_FLOATS * (size_t)i;
+            st_out[6 * l + 2 * j] = v[6];
+            st_out[6 * l + 2 * j + 1] = v[7];
+        }
+    return GLRT_HOST_OK;
+}
+
+int glrt_emission_bind_check(const float *mat, size_t n_scene_mat, size_t n_tex, int cutouts_bound, const int32_t *material_emission, size_t n_mat, char *msg, size_t cap) {
+    if ((n_scene_mat && !mat) || (n_mat && !material_emission)) return GLRT_HOST_EINVAL;
+    const std::string bad = glrt_detail::emission_bind_error(true, n_scene_mat, n_tex, cutouts_bound != 0, material_emission, n_mat,
+                                                             [&](size_t m) { return (int)mat[GLRT_MATERIAL_FLOATS * m]; });
+    if (msg && cap) std::snprintf(msg, cap, "%s", bad.c_str());
+    return bad.empty() ? GLRT_HOST_OK : GLRT_HOST_EINVAL;
+}
+
+int glrt_light_emission(const float *vert, size_t n_vert, const float *light, size_t n_light, const float *mat, size_t n_mat, const glrt_texture *tex, size_t n_tex,
+                        const void *texels, size_t texel_bytes, const int32_t *material_emission, const int32_t *lid, const float *u, size_t n, float *out) {
+    if (n && (!lid || !u || !out)) return GLRT_HOST_EINVAL;
+    if ((n_light && (!vert || !light || !mat)) || (n_mat && !material_emission)) return GLRT_HOST_EINVAL;
+    const TexRecord *rec = reinterpret_cast<const TexRecord *>(tex);
+    if (!glrt_detail::texture_set_error(rec, n_tex, texels, texel_bytes).empty()) return GLRT_HOST_EINVAL;
+    for (size_t m = 0; m < n_mat; m++)
+        if (material_emission[m] < -1 || (material_emission[m] >= 0 && ((size_t)material_emission[m] >= n_tex || (int)mat[GLRT_MATERIAL_FLOATS * m] == 5))) return GLRT_HOST_EINDEX;
+    std::vector<float> st(6 * n_light);
+    if (const int rc = glrt_light_st(vert, n_vert, light, n_light, st.data())) return rc;
+    for (size_t l = 0; l < n_light; l++)
+        if (!(light[4 * l + 3] >= 0.0f) || (size_t)light[4 * l + 3] >= n_mat) return GLRT_HOST_EINDEX;
+    for (size_t i = 0; i < n; i++)
+        if (lid[i] < 0 || (size_t)lid[i] >= n_light) return GLRT_HOST_EINDEX;
+    FlushDenormals ftz;
+    for (size_t i = 0; i < n; i++) {
+        const float ua0 = u[2 * i], ub0 = u[2 * i + 1];
+        const bool flip = 1.0f < ua0 + ub0;  // sampleDirect's flip
+        const float ua = flip ? 1.0f - ua0 : ua0;
+        const float ub = flip ? 1.0f - ub0 : ub0;
+        const float w0 = (1.0f - ua) - ub;
+        const float *q = &st[6 * (size_t)lid[i]];
+        const float s = (w0 * q[0] + ua * q[2]) + ub * q[4];
+        const float t = (w0 * q[1] + ua * q[3]) + ub * q[5];
+        const size_t id = (size_t)light[4 * (size_t)lid[i] + 3];
+        const float *m = mat + GLRT_MATERIAL_FLOATS * id;
+        float *o = out + 5 * i;
+        o[0] = s; o[1] = t;
+        o[2] = m[3]; o[3] = m[4]; o[4] = m[5];  // an unbound light: its plain emission
+        if (material_emission[id] >= 0) {
+            float c[3];
+            lookup(rec[material_emission[id]], (const unsigned char *)texels, s, t, c);
+            o[2] = m[3] * c[0]; o[3] = m[4] * c[1]; o[4] = m[5] * c[2];  // Le = emission * c: one rounded product a channel
+        }
+    }
+    return GLRT_HOST_OK;
+}
+
+int glrt_emission_albedo(const float *vert, size_t n_vert, const float *tri, size_t n_tri, const float *mat, size_t n_mat, const glrt_texture *tex, size_t n_tex,
+                         const void *texels, size_t texel_bytes, const int32_t *material_texture, const int32_t *material_emission, const float *hits, size_t n,
+                         float *rgb_out) {
+    if (n_mat && !material_emission) return GLRT_HOST_EINVAL;
+    if (const int rc = glrt_texture_albedo(vert, n_vert, tri, n_tri, mat, n_mat, tex, n_tex, texels, texel_bytes, material_texture, hits, n, rgb_out)) return rc;
+    const TexRecord *rec = reinterpret_cast<const TexRecord *>(tex);
+    for (size_t m = 0; m < n_mat; m++)
+        if (material_emission[m] < -1 || (material_emission[m] >= 0 && ((size_t)material_emission[m] >= n_tex || (int)mat[GLRT_MATERIAL_FLOATS * m] == 5))) return GLRT_HOST_EINDEX;
+    FlushDenormals ftz;
+    for (size_t i = 0; i < n; i++) {
+        const float *h = hits + 4 * i;
+        int32_t t;
+        std::memcpy(&t, &h[0], 4);
+        if (t < 0) continue;
+        const float *tr = tri + 4 * (size_t)t;
+        const size_t id = (size_t)tr[3];
+        if ((int)mat[GLRT_MATERIAL_FLOATS * id] == 2 || material_emission[id] < 0) continue;  // a diffuse material keeps its albedo rule
+        const float *a = vert + GLRT_VERTEX_FLOATS * (size_t)tr[0] + 6, *b = vert + GLRT_VERTEX_FLOATS * (size_t)tr[1] + 6,
+                    *c = vert + GLRT_VERTEX_FLOATS * (size_t)tr[2] + 6;
+        const float u = h[1], v = h[2];
+        const float w0 = (1.0f - u) - v;
+        lookup(rec[material_emission[id]], (const unsigned char *)texels, (w0 * a[0] + u * b[0]) + v * c[0], (w0 * a[1] + u * b[1]) + v * c[1], rgb_out + 3 * i);
     }
     return GLRT_HOST_OK;
 }

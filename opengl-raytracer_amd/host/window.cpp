@@ -44,7 +44,7 @@ unsigned long long Window::raysTraced() const {
 
 // The scene's textures (Scene::TextureSpec; extensions only) as one set on every member, after the scene: launches then run on the extension megakernel
 void Window::uploadTextures() {
-    if (scene->textures_.empty() && scene->maps_.empty() && scene->cutouts_.empty()) return;
+    if (scene->textures_.empty() && scene->maps_.empty() && scene->cutouts_.empty() && scene->emissionMaps_.empty()) return;
     std::vector<glrtx_texture> desc;
     std::vector<unsigned char> blob;
     std::vector<int32_t> bind(scene->materials.size(), -1);
@@ -71,6 +71,14 @@ void Window::uploadTextures() {
         blob.insert(blob.end(), t.image.texels.begin(), t.image.texels.end());
         cuts[t.material] = glrtx_cutout{(int32_t)desc.size() - 1, t.channel, t.cutoff, 0};
     }
+    // ... and the emitters' emission maps behind those (Scene::emissionMapSpecs), bound with a fourth call
+    std::vector<int32_t> emit(scene->materials.size(), -1);
+    for (const Scene::TextureSpec &t : scene->emissionMaps_) {
+        blob.resize((blob.size() + 15) / 16 * 16, 0);
+        desc.push_back(glrtx_texture{(uint64_t)blob.size(), t.image.width, t.image.height, t.format, t.wrap, t.wrap, t.filter});
+        blob.insert(blob.end(), t.image.texels.begin(), t.image.texels.end());
+        emit[t.material] = (int32_t)desc.size() - 1;
+    }
     for (int i = 0; i < glrtx_group_size(grp_); i++) {
         glrtx_ctx *c = glrtx_group_ctx(grp_, i);
         if (glrtx_upload_textures(c, desc.data(), desc.size(), blob.data(), blob.size(), bind.data(), bind.size()) != GLRTX_OK)
@@ -79,7 +87,10 @@ void Window::uploadTextures() {
             GLRT_FatalError("glrtx_bind_material_maps: %s", glrtx_last_error(c));
         if (!scene->cutouts_.empty() && glrtx_bind_cutouts(c, cuts.data(), cuts.size()) != GLRTX_OK)
             GLRT_FatalError("glrtx_bind_cutouts: %s", glrtx_last_error(c));
+        if (!scene->emissionMaps_.empty() && glrtx_bind_emission_maps(c, emit.data(), emit.size()) != GLRTX_OK)
+            GLRT_FatalError("glrtx_bind_emission_maps: %s", glrtx_last_error(c));
     }
+    if (!scene->emissionMaps_.empty()) GLRT_Info("emission maps: %zu (not part of the reference)", scene->emissionMaps_.size());
     if (!scene->cutouts_.empty()) GLRT_Info("cutouts: %zu (not part of the reference)", scene->cutouts_.size());
     if (!scene->maps_.empty()) GLRT_Info("material maps: %zu (not part of the reference)", scene->maps_.size());
     GLRT_Info("textures: %zu, %zu texel bytes (not part of the reference)", desc.size(), blob.size());
@@ -154,7 +165,7 @@ void Window::mainloop(const std::shared_ptr<Scene> &scene_, double fps) {
     uploadEnvironment();
     resize(scene->width, scene->height);
     if (const char *e = std::getenv("GLRT_BVH_ORDER")) orderByHits_ = std::string(e) == "hits";
-    if (orderByHits_ && !scene->nodes.empty() && scene->textures_.empty() && scene->maps_.empty() && scene->cutouts_.empty() && !scene->environment_.present && scene->spheres.empty() && !scene->hasDielectric_ && !scene->whitted_ && !scene->hasVolume_) {
+    if (orderByHits_ && !scene->nodes.empty() && scene->textures_.empty() && scene->maps_.empty() && scene->cutouts_.empty() && scene->emissionMaps_.empty() && !scene->environment_.present && scene->spheres.empty() && !scene->hasDielectric_ && !scene->whitted_ && !scene->hasVolume_) {
         // one calibration frame on the first member's share of the rows (interleaved stripes: a fair sample of the image), counted by the render kernel itself
         glrtx_params p;
         frameParams(p);

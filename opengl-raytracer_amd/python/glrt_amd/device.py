@@ -179,7 +179,8 @@ EXPORTS = ["glrtx_abi_version", "glrtx_create", "glrtx_destroy", "glrtx_last_err
            "glrtx_upload_normal_topology", "glrtx_update_positions", "glrtx_update_positions_device", "glrtx_set_pose_normals",
            "glrtx_debug_rebuild_normals", "glrtx_debug_normals_burst", "glrtx_upload_textures", "glrtx_debug_texture_lookup",
            "glrtx_upload_environment", "glrtx_set_environment_cfg", "glrtx_debug_env_weights", "glrtx_debug_env_sample", "glrtx_debug_env_eval",
-           "glrtx_bind_material_maps", "glrtx_debug_map_normal", "glrtx_bind_cutouts", "glrtx_debug_texture_channel", "glrtx_debug_last_kernel"]
+           "glrtx_bind_material_maps", "glrtx_debug_map_normal", "glrtx_bind_cutouts", "glrtx_debug_texture_channel", "glrtx_debug_last_kernel",
+           "glrtx_bind_emission_maps", "glrtx_debug_light_emission"]
 
 SCENE_BUFFERS = ("nodes", "cnodes", "nrms", "lights", "vine", "root")  # glrtx_debug_read_scene's `which`, in order (GLRTX_SCENE_*)
 
@@ -411,6 +412,12 @@ def lib():
             L.glrtx_debug_last_kernel.restype = C.c_char_p
         except AttributeError:
             pass
+        try:  # (additive to ABI 10 as well: emission maps)
+            i32p = C.POINTER(C.c_int32)
+            L.glrtx_bind_emission_maps.argtypes = [vp, i32p, C.c_size_t]
+            L.glrtx_debug_light_emission.argtypes = [vp, i32p, fp, C.c_size_t, fp]
+        except AttributeError:
+            pass
         _lib = L
     return _lib
 
@@ -512,6 +519,12 @@ def debug_texture_channel(textures, which, channel, st):
     if rc != 0:
         raise GlrtxError(rc, L.glrtx_last_error(None).decode())
     return out
+
+
+def debug_light_emission(dev, lid, u):
+    """glrtx_debug_light_emission on dev (a Device with emission maps bound): the kernels' sampled-side statement (include/glrtx.h "Emission maps") on the
+    context's own scene, set and bindings.  lid (n,) light indices, u (n, 2) raw uniforms; returns (n, 5) float32 {s, t, Le.rgb}, as host.light_emission."""
+    return dev.debug_light_emission(lid, u)
 
 
 def debug_map_normal(records, scale=1.0):
@@ -1163,6 +1176,27 @@ class Device:
         else:
             rec = cutouts(np.size(texture), texture, channel, cutoff)
         self._ck(self.L.glrtx_bind_cutouts(self.h, rec.ctypes.data, rec.size))
+
+    def bind_emission_maps(self, material_emission=None):
+        """Bind emission maps on top of the bound texture set (glrtx_bind_emission_maps; include/glrtx.h "Emission maps"): one texture index a material (-1:
+        none; any type but media).  A bound emitter's radiance is emission * texel, where it is seen and where next-event estimation samples it.  Launches
+        then run on the extension megakernel's emission-map forms.  None unbinds.  upload_textures and upload_scene drop the bindings; vertex updates and
+        poses keep them."""
+        if material_emission is None:
+            self._ck(self.L.glrtx_bind_emission_maps(self.h, None, 0))
+            return
+        b = np.ascontiguousarray(material_emission, dtype=np.int32).reshape(-1)
+        self._ck(self.L.glrtx_bind_emission_maps(self.h, b.ctypes.data_as(C.POINTER(C.c_int32)), b.size))
+
+    def debug_light_emission(self, lid, u):
+        """glrtx_debug_light_emission: (n, 5) float32 {s, t, Le.rgb} of light lid[i] at the raw uniforms u[i] (see device.debug_light_emission)."""
+        k = np.ascontiguousarray(lid, dtype=np.int32).reshape(-1)
+        uu = _f32(u).reshape(-1, 2)
+        if uu.shape[0] != k.size:
+            raise ValueError(f"debug_light_emission: {k.size} lights, {uu.shape[0]} uniform pairs")
+        out = np.zeros((k.size, 5), np.float32)
+        self._ck(self.L.glrtx_debug_light_emission(self.h, k.ctypes.data_as(C.POINTER(C.c_int32)), _fp(uu), k.size, _fp(out)))
+        return out
 
     def last_kernel(self) -> str:
         """glrtx_debug_last_kernel: the name of the render kernel the last launch ran, as error reports give it ("" before the first launch)."""

@@ -74,6 +74,10 @@ def lib():
         L.glrt_texture_channel.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, i32p, i32p, fp, C.c_size_t, fp]
         L.glrt_render_features_geom_cutout.argtypes = ([fp, C.c_size_t, fp, C.c_size_t, fp, C.c_size_t, fp, C.c_size_t, fp, fp] + [C.c_int] * 5 +
                                                        [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, i32p, C.c_void_p, fp, fp, fp])
+        L.glrt_light_st.argtypes = [fp, C.c_size_t, fp, C.c_size_t, fp]
+        L.glrt_light_emission.argtypes = [fp, C.c_size_t, fp, C.c_size_t, fp, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, i32p, i32p, fp, C.c_size_t, fp]
+        L.glrt_emission_albedo.argtypes = [fp, C.c_size_t, fp, C.c_size_t, fp, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, i32p, i32p, fp, C.c_size_t, fp]
+        L.glrt_emission_bind_check.argtypes = [fp, C.c_size_t, C.c_size_t, C.c_int, i32p, C.c_size_t, C.c_char_p, C.c_size_t]
         vp = C.c_void_p
         L.glrt_env_weights.argtypes = [vp, vp, C.c_size_t, vp, fp, i32p]
         L.glrt_env_alias.argtypes = [fp, C.c_int32, fp, i32p, fp, i32p, fp]
@@ -696,6 +700,70 @@ def texture_channel(textures, which, channel, st):
     if rc != 0:
         raise RuntimeError(f"glrt_texture_channel failed: {rc}")
     return out
+
+
+# --------------------------------------------------------------------------- emission maps (include/glrtx.h "Emission maps")
+def light_st(scene):
+    """glrt_light_st: the device's per-light coordinate table -- (n_light, 3, 2) float32, the uv words of every light's three vertices in wire order."""
+    v, l = _f32(scene["vert"]).reshape(-1, 15), _f32(scene["light"]).reshape(-1, 4)
+    out = np.zeros((l.shape[0], 3, 2), np.float32)
+    rc = lib().glrt_light_st(_ptr(v, C.c_float), v.shape[0], _ptr(l, C.c_float), l.shape[0], _ptr(out, C.c_float))
+    if rc != 0:
+        raise RuntimeError(f"glrt_light_st failed: {rc}")
+    return out
+
+
+def light_emission(scene, textures, material_emission, lid, u):
+    """glrt_light_emission: the CPU statement of next-event estimation's side of an emission map.  scene (vert / light / mat), textures as pack_textures takes
+    them, material_emission one texture index a material (-1: none), lid (n,) light indices, u (n, 2) the RAW uniforms (the flip is taken inside).  Returns
+    (n, 5) float32 {s, t, Le.rgb}."""
+    desc, blob = pack_textures(textures)
+    v, l, m = _f32(scene["vert"]).reshape(-1, 15), _f32(scene["light"]).reshape(-1, 4), _f32(scene["mat"]).reshape(-1, 18)
+    b = np.ascontiguousarray(material_emission, dtype=np.int32).reshape(-1)
+    if b.size != m.shape[0]:
+        raise ValueError(f"light_emission: {m.shape[0]} materials, {b.size} bindings")
+    k = np.ascontiguousarray(lid, dtype=np.int32).reshape(-1)
+    uu = _f32(u).reshape(-1, 2)
+    if uu.shape[0] != k.size:
+        raise ValueError(f"light_emission: {k.size} lights, {uu.shape[0]} uniform pairs")
+    out = np.zeros((k.size, 5), np.float32)
+    rc = lib().glrt_light_emission(_ptr(v, C.c_float), v.shape[0], _ptr(l, C.c_float), l.shape[0], _ptr(m, C.c_float), m.shape[0], desc.ctypes.data, desc.size,
+                                   blob.ctypes.data, blob.size, _ptr(b, C.c_int32), _ptr(k, C.c_int32), _ptr(uu, C.c_float), k.size, _ptr(out, C.c_float))
+    if rc != 0:
+        raise RuntimeError(f"glrt_light_emission failed: {rc}")
+    return out
+
+
+def emission_albedo(scene, textures, material_texture, material_emission, hits):
+    """glrt_emission_albedo: what plane A of the feature pass holds while emission maps are bound, for hit records as plane G stores them: texture_albedo, and
+    the looked-up texel (without the emission) at a hit on a bound material that is not diffuse.  Returns rgb (..., 3) float32."""
+    desc, blob = pack_textures(textures)
+    v, t, m = _f32(scene["vert"]).reshape(-1, 15), _f32(scene["tri"]).reshape(-1, 4), _f32(scene["mat"]).reshape(-1, 18)
+    b = np.ascontiguousarray(material_texture, dtype=np.int32).reshape(-1)
+    e = np.ascontiguousarray(material_emission, dtype=np.int32).reshape(-1)
+    if b.size != m.shape[0] or e.size != m.shape[0]:
+        raise ValueError(f"emission_albedo: {m.shape[0]} materials, {b.size} and {e.size} bindings")
+    h = _f32(hits)
+    flat = h.reshape(-1, 4)
+    out = np.zeros((flat.shape[0], 3), np.float32)
+    rc = lib().glrt_emission_albedo(_ptr(v, C.c_float), v.shape[0], _ptr(t, C.c_float), t.shape[0], _ptr(m, C.c_float), m.shape[0], desc.ctypes.data, desc.size,
+                                    blob.ctypes.data, blob.size, _ptr(b, C.c_int32), _ptr(e, C.c_int32), _ptr(flat, C.c_float), flat.shape[0], _ptr(out, C.c_float))
+    if rc != 0:
+        raise RuntimeError(f"glrt_emission_albedo failed: {rc}")
+    return out.reshape(h.shape[:-1] + (3,))
+
+
+def emission_bind_check(scene, n_tex, material_emission, cutouts_bound=False):
+    """glrt_emission_bind_check: what glrtx_bind_emission_maps would refuse of these bindings on `scene` with a set of n_tex textures bound -- the device's
+    message behind its "glrtx_bind_emission_maps: ", or "" when the bindings may be bound."""
+    m = _f32(scene["mat"]).reshape(-1, 18)
+    b = np.ascontiguousarray(material_emission, dtype=np.int32).reshape(-1)
+    msg = C.create_string_buffer(256)
+    rc = lib().glrt_emission_bind_check(_ptr(m, C.c_float), m.shape[0], int(n_tex), int(bool(cutouts_bound)), _ptr(b, C.c_int32), b.size, msg, 256)
+    text = msg.value.decode()
+    if (rc == 0) != (text == ""):
+        raise RuntimeError(f"glrt_emission_bind_check: {rc} with the message {text!r}")
+    return text
 
 
 def render_features_geom_cutout(scene, params, textures, material_texture, cut, width=None, height=None, rank=0, world=1, stripe=16):

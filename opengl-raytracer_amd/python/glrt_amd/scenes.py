@@ -455,6 +455,83 @@ def config_cutout_wall(n=6, cutout=None, **kw):
     return scene, params, wall
 
 
+def config_emissive_wall(n=6, per_cell=False, emission=(4.0, 3.0, 2.0), texel=None, uv="cell", ball="conductor", width=64, height=48, max_depth=4, n_samples=2, seed=1,
+                         bvh="sah", emission_map=None):
+    """config_textured_wall's scene with the wall as an EMITTER panel in the light table: the scene emission maps are pinned on (include/glrtx.h "Emission
+    maps").  The lamp stays, so the light table holds 2 + 2 n n triangles.
+      per_cell False  the wall has ONE emitter material of `emission` and texture coordinates: uv "cell", each cell's centre at all three corners; uv "corner",
+                      the wall's own parametrisation (s across, t up, in [0, 1]); or an array (2 n n, 3, 2).
+      per_cell True   no coordinates, and one emitter material a cell with emission = float32(emission * texel[j, i]): what an emission map that is constant
+                      over each cell, with the lookup's value texel[j, i], must render as.
+    Both forms use the same triangles in the same order, and the same triangles are lights, so the tree and the light table's order are the same.
+    texel: (n, n, 3) float32, random in [0.1, 0.9] from `seed` by default (never 0: a black cell would leave the light table).  ball: "conductor" (copper) or
+    "glass" (a dielectric icosphere in front of the panel, for GLRTX_EXT_DIELECTRIC).  emission_map: the block export_json_obj writes for the wall's shape.
+    Returns (scene, params, wall) as config_textured_wall does, with wall["texel"] and wall["emission"] in place of the albedo."""
+    if ball not in ("conductor", "glass"):
+        raise ValueError("config_emissive_wall: ball is 'conductor' or 'glass'")
+    rng = np.random.default_rng(seed)
+    c = np.asarray(rng.uniform(0.1, 0.9, (n, n, 3)) if texel is None else texel, np.float32).reshape(n, n, 3)
+    e = np.broadcast_to(np.asarray(emission, np.float32), (3,)).copy()
+    b = SceneBuilder()
+    grey = b.add_material(diffuse((0.7, 0.7, 0.7)))
+    mid_ball = b.add_material(dielectric(1.5) if ball == "glass" else conductor(COPPER["eta"], COPPER["kappa"], 0.2))
+    lamp = b.add_material(emitter((10.0, 10.0, 10.0)))
+    b.add_mesh(*quad((-10, 0, 10), (20, 0, 0), (0, 0, -20)), grey)
+    b.add_mesh(*icosphere(1, 1.0, (0.0, 1.0, 0.0)), mid_ball)
+    b.add_mesh(*quad((-1, 5, -1), (2, 0, 0), (0, 0, 2)), lamp)
+    first_tri = sum(p.shape[0] for p in b._pos)
+    x0, y0, z0, w, h = -5.0, 0.0, -2.0, 10.0, 6.0
+    one = emitter(tuple(float(x) for x in e))
+    if emission_map is not None:
+        one["emission_map"] = emission_map
+    wall_id = len(b.materials) if per_cell else b.add_material(one)
+    pos, nrm, mid, st = [], [], [], []
+    for j in range(n):
+        for i in range(n):
+            p, q = quad((x0 + w * i / n, y0 + h * j / n, z0), (w / n, 0, 0), (0, h / n, 0))  # normal +z, towards the camera
+            pos.append(p); nrm.append(q)
+            mid += [b.add_material(emitter(tuple(float(x) for x in (e * c[j, i]).astype(np.float32)))) if per_cell else wall_id] * 2
+            if isinstance(uv, str) and uv == "corner":
+                k = np.array([[i, j], [i + 1, j], [i + 1, j + 1], [i, j + 1]], np.float32) / np.float32(n)
+                st.append(np.stack([k[[0, 1, 2]], k[[0, 2, 3]]]))  # quad(): triangles (a, b, c), (a, c, d)
+            else:
+                st.append(np.broadcast_to(np.array([(i + 0.5) / n, (j + 0.5) / n], np.float32), (2, 3, 2)))
+    coords = None if per_cell else (np.concatenate(st, 0) if isinstance(uv, str) else uv)
+    b.add_mesh(np.concatenate(pos, 0), np.concatenate(nrm, 0), np.asarray(mid, np.float32), uv=coords)
+    scene = b.build(bvh)
+    c2w, s2c = camera((0, 3, 9), (0, 1, 0), (0, 1, 0), 40.0, width, height)
+    info = dict(n=n, texel=c, emission=e, material=wall_id, tri=range(first_tri, first_tri + 2 * n * n), vert=range(3 * first_tri, 3 * (first_tri + 2 * n * n)),
+                builder=b, camera=((0, 3, 9), (0, 1, 0), (0, 1, 0), 40.0))
+    return scene, make_params(c2w, s2c, width, height, max_depth, n_samples), info
+
+
+def config_emissive_panel(split=False, emission=(6.0, 6.0, 6.0), left=1.0, right=0.1, width=64, height=48, max_depth=4, n_samples=1, bvh="sah"):
+    """A grey floor lit by ONE vertical emitter panel behind it and nothing else: the scene that shows that an emission map varying INSIDE a light triangle is
+    sampled where it is bright (include/glrtx.h "Emission maps").
+      split False  the panel is one quad with corner coordinates (s across, in [0, 1]); under a 2 x 1 nearest texture {left, right} its left half emits
+                   emission * left and its right half emission * right.
+      split True   the same panel as two quads, each with one emitter material of that constant emission.
+    The two are not bit-comparable (other triangles, another tree); their floor irradiance has the same expectation.  Returns (scene, params, panel) with
+    panel = dict(material (the panel's, or the left half's), floor (the floor's material id: plane A of the feature pass says which pixels see it))."""
+    e = np.broadcast_to(np.asarray(emission, np.float32), (3,)).copy()
+    b = SceneBuilder()
+    grey = b.add_material(diffuse((0.7, 0.7, 0.7)))
+    b.add_mesh(*quad((-10, 0, 10), (20, 0, 0), (0, 0, -20)), grey)
+    x0, y0, z0, w, h = -4.0, 0.5, -2.0, 8.0, 3.0
+    if split:
+        ml = b.add_material(emitter(tuple(float(x) for x in (e * np.float32(left)).astype(np.float32))))
+        mr = b.add_material(emitter(tuple(float(x) for x in (e * np.float32(right)).astype(np.float32))))
+        b.add_mesh(*quad((x0, y0, z0), (w / 2, 0, 0), (0, h, 0)), ml)
+        b.add_mesh(*quad((x0 + w / 2, y0, z0), (w / 2, 0, 0), (0, h, 0)), mr)
+    else:
+        ml = b.add_material(emitter(tuple(float(x) for x in e)))
+        k = np.array([[0, 0], [1, 0], [1, 1], [0, 1]], np.float32)
+        b.add_mesh(*quad((x0, y0, z0), (w, 0, 0), (0, h, 0)), ml, uv=np.stack([k[[0, 1, 2]], k[[0, 2, 3]]]))
+    scene = b.build(bvh)
+    c2w, s2c = camera((0, 3, 9), (0, 1, 0), (0, 1, 0), 40.0, width, height)
+    return scene, make_params(c2w, s2c, width, height, max_depth, n_samples), dict(material=ml, floor=grey, builder=b, camera=((0, 3, 9), (0, 1, 0), (0, 1, 0), 40.0))
+
+
 # --------------------------------------------------------------------------- environment lighting (include/glrtx.h "Environment"; PARITY UNPINNED)
 ENV_QUAD_ALBEDO = (0.5, 0.25, 0.75)
 
@@ -633,6 +710,8 @@ def export_json_obj(builder: SceneBuilder, directory, width, height, origin, tar
                       alpha=float(m["param2"][0]))
         elif m["type"] == MTRL_EMITTER:
             sh.update(material="emitter", emission=[float(v) for v in m["emission"]])
+            if m.get("emission_map") is not None:  # (config_emissive_wall; host/scene.h: emissionMapSpecs)
+                sh["emission_map"] = dict(m["emission_map"])
         elif m["type"] == MTRL_MEDIA:
             sh.update(material="media")
             if m.get("volume") is not None:

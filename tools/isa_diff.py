@@ -19,6 +19,11 @@ From the commit before pt_render_persistent gained its CUT argument (66f6c1f) to
 
     --rename 'pt_render_persistent<(\w+), (\w+), (\w+), (\w+), (\w+), (\w+)>(.*)std::conditional<(\w+), glrtx::EnvArgs, glrtx::VolArgs>::type\)=pt_render_persistent<\1, \2, \3, \4, \5, \6, false>\7std::conditional<false, glrtx::CutTail<std::conditional<\8, glrtx::EnvArgs, glrtx::VolArgs>::type>, std::conditional<\8, glrtx::EnvArgs, glrtx::VolArgs>::type>::type)'
 
+From the commit before pt_render_persistent gained its EMIT argument (b9c727a) to its successor (625 symbols identical, 21 new; the kernel's name keeps
+its seven arguments, the type of its last parameter is spelled anew):
+
+    --rename '(pt_render_persistent<.*)std::conditional<(\w+), glrtx::CutTail<std::conditional<(\w+), glrtx::EnvArgs, glrtx::VolArgs>::type>, std::conditional<\w+, glrtx::EnvArgs, glrtx::VolArgs>::type>::type\)=\1std::conditional<((0)>(0)), glrtx::EmitTail<std::conditional<\3, glrtx::EnvArgs, glrtx::VolArgs>::type>, std::conditional<\2, glrtx::CutTail<std::conditional<\3, glrtx::EnvArgs, glrtx::VolArgs>::type>, std::conditional<\3, glrtx::EnvArgs, glrtx::VolArgs>::type>::type>::type)'
+
 Works without a GPU (tools/isa_report.py's extraction, llvm-objdump from /opt/rocm).
 """
 from __future__ import annotations

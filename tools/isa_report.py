@@ -11,6 +11,8 @@ Invariants checked (they protect hand-written inline asm from register-allocatio
     lgkmcnt(0)` that follows it no instruction may read or copy the destination registers.
   * the CUT forms of the persistent megakernel (pt_render_persistent<.., true>: alpha cutouts, a texture lookup inside the traversal loop) are all eight there
     -- TEX, TEX+MAPS, ENV+TEX, ENV+TEX+MAPS, each with and without ray counting -- and none of them spills a register or uses scratch.
+  * the EMIT forms (pt_render_persistent<.., false, glrtx::Emit>: emission maps, a texture lookup where an emitter is seen and where it is sampled as a light) likewise:
+    the same eight, no spills, no scratch.
   * the traversal step's pop loop (trav_step, inline asm) keeps the sentinel REF_FIN and the ref it overwrites in DIFFERENT registers
     (both start out with the same value; sharing them made the loop write back the last culled ref instead of the sentinel).
 Works without a GPU (llvm-objcopy / clang-offload-bundler / llvm-readelf / llvm-objdump from /opt/rocm).
@@ -238,24 +240,35 @@ def check_staged_waits(co: pathlib.Path, ks) -> list:
     return problems
 
 
-def check_cut_forms(ks) -> list:
-    """pt_render_persistent<COUNT_RAYS, EXT, VOL, TEX, ENV, MAPS, CUT> with CUT = true: eight kernels, no spills, no scratch."""
+def check_forms(ks, emit: bool) -> list:
+    """pt_render_persistent<COUNT_RAYS, EXT, VOL, TEX, ENV, MAPS, CUT> with CUT = true, or (emit) pt_render_persistent<.., false, glrtx::Emit>: eight kernels --
+    TEX, TEX+MAPS, ENV+TEX, ENV+TEX+MAPS, each with and without ray counting --, no spills, no scratch."""
+    what = "EMIT" if emit else "CUT"
+    last = ("false", "glrtx::Emit") if emit else ("true",)
     problems, seen = [], set()
     for k in ks:
         m = re.search(r"pt_render_persistent<([^>]*)>", k["pretty"])
         args = [a.strip() for a in m.group(1).split(",")] if m else []
-        if len(args) != 7 or args[6] != "true":
+        if len(args) != 6 + len(last) or args[-1] != last[-1]:
             continue
         seen.add(tuple(args))
         if k["vgpr_spill_count"] or k["sgpr_spill_count"] or k["private_segment_fixed_size"]:
             problems.append(f"{k['pretty']}: {k['vgpr_spill_count']} VGPR spills, {k['sgpr_spill_count']} SGPR spills, {k['private_segment_fixed_size']} B of scratch "
-                            "(the CUT forms are to have none)")
-    want = {(c, "true", "false", "true", e, m, "true") for c in ("false", "true") for e in ("false", "true") for m in ("false", "true")}
+                            f"(the {what} forms are to have none)")
+    want = {(c, "true", "false", "true", e, m) + last for c in ("false", "true") for e in ("false", "true") for m in ("false", "true")}
     for missing in sorted(want - seen):
-        problems.append(f"pt_render_persistent<{', '.join(missing)}>: the CUT form is missing")
+        problems.append(f"pt_render_persistent<{', '.join(missing)}>: the {what} form is missing")
     for extra in sorted(seen - want):
-        problems.append(f"pt_render_persistent<{', '.join(extra)}>: a CUT form nothing launches")
+        problems.append(f"pt_render_persistent<{', '.join(extra)}>: a {what} form nothing launches")
     return problems
+
+
+def check_cut_forms(ks) -> list:
+    return check_forms(ks, False)
+
+
+def check_emit_forms(ks) -> list:
+    return check_forms(ks, True)
 
 
 def main():
@@ -272,7 +285,7 @@ def main():
         if a.out:
             pathlib.Path(a.out).write_text("llvm-readelf --notes of the gfx950 code object in libglrtx.so (tools/isa_report.py)\n\n" + t + "\n")
         if a.check:
-            bad = check_scalar_prefetch(co, ks) + check_pop_loop(co, ks) + check_staged_waits(co, ks) + check_cut_forms(ks)
+            bad = check_scalar_prefetch(co, ks) + check_pop_loop(co, ks) + check_staged_waits(co, ks) + check_cut_forms(ks) + check_emit_forms(ks)
             for b in bad:
                 print("ISA CHECK FAILED:", b)
             sys.exit(1 if bad else 0)
