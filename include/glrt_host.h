@@ -351,6 +351,30 @@ int glrt_emission_albedo(const float *vert, size_t n_vert, const float *tri, siz
 int glrt_emission_bind_check(const float *mat, size_t n_scene_mat, size_t n_tex, int cutouts_bound, const int32_t *material_emission, size_t n_mat, char *msg,
                              size_t cap);
 
+/* Surface context: the three lookups above -- the albedo of "Textures", the acceptance of "Cutouts", the texel of "Emission maps" -- as per-hit calls with C
+ * linkage, for a CPU path tracer that takes them as callbacks (oracle/pt_oracle.c: pt_oracle_set_surface).  The lookups stay stated once: the calls are built
+ * on the statements behind glrt_texture_lookup and glrt_texture_channel and mix the coordinates as glrt_texture_albedo and glrt_light_emission do,
+ * s = (w0 * s0 + u * s1) + v * s2 with w0 = (1 - u) - v.
+ *   glrt_surface_create    checks the wire scene (vert, tri, light, mat), the set and the three kinds of per-material bindings -- material_texture and
+ *                          material_emission one texture index a material (-1: none), cut one record a material; each may be NULL: nothing of that kind is
+ *                          bound -- and copies what the calls read: the coordinates are those of `vert` at this call, as the device's tables are the upload's.
+ *   glrt_surface_free      releases a context (NULL: nothing).
+ *   glrt_surface_albedo    1 and rgb = the lookup at (u, v) of wire triangle tri where its material is bound to a texture; 0, rgb untouched, otherwise.
+ *   glrt_surface_accept    0 where wire triangle tri's material has a cutout record and the channel's value at (u, v) is not >= cutoff (a NaN rejects); else 1.
+ *   glrt_surface_emission  1 and texel = the lookup c (Le = emission * c is the caller's product) where the material is bound to an emission map; 0 otherwise.
+ *                          light == 0: index is a wire triangle and (u, v) the hit's; light != 0: index is a light and (u, v) sampleDirect's flipped uniforms.
+ * The per-hit calls take the context as void *, only read it, and flush denormals for their own duration: any number of threads may call them at once.  An
+ * index outside the scene is unbound (albedo, emission: 0; accept: 1); any float is a valid u or v.
+ * GLRT_HOST_EINVAL / GLRT_HOST_EINDEX: as glrt_texture_albedo, glrt_render_features_geom_cutout and glrt_light_emission refuse the same arguments. */
+typedef struct glrt_surface glrt_surface;
+int glrt_surface_create(const float *vert, size_t n_vert, const float *tri, size_t n_tri, const float *light, size_t n_light, const float *mat, size_t n_mat,
+                        const glrt_texture *tex, size_t n_tex, const void *texels, size_t texel_bytes, const int32_t *material_texture, const glrt_cutout *cut,
+                        const int32_t *material_emission, glrt_surface **surface_out);
+void glrt_surface_free(glrt_surface *surface);
+int glrt_surface_albedo(void *surface, int tri, float u, float v, float rgb[3]);
+int glrt_surface_accept(void *surface, int tri, float u, float v);
+int glrt_surface_emission(void *surface, int index, int light, float u, float v, float texel[3]);
+
 /* Environment: the CPU statements of the device's environment lighting (glrtx_upload_environment / glrtx_debug_env_*, include/glrtx.h "Environment": the
  * octahedral mapping, its inverse, the solid-angle factor, the importance grid and the sampling rule are there), bit for bit (host/environment.cpp;
  * tests/env_math.py states them in numpy).  glrt_env_cfg is glrtx_env_cfg's layout.  The arithmetic runs with denormals flushed (MXCSR FTZ | DAZ, restored).

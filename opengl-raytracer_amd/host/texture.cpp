@@ -300,3 +300,111 @@ int glrt_emission_albedo(const float *vert, size_t n_vert, const float *tri, siz
     }
     return GLRT_HOST_OK;
 }
+
+// ---- surface context (include/glrt_host.h "Surface context"): the three lookups above as per-hit calls, for a path tracer that takes them as callbacks.
+// The context owns copies of everything it reads: the {s, t} of every wire triangle's and every light's corners as they were when it was made, the triangles'
+// and lights' materials, the checked set and the three kinds of per-material bindings.  The calls only read it, so any number of threads may share one.
+struct glrt_surface {
+    std::vector<TexRecord> tex;
+    std::vector<unsigned char> texels;
+    std::vector<float> tri_st, light_st;      // six floats a triangle / a light: {s0, t0, s1, t1, s2, t2}
+    std::vector<int32_t> tri_mat, light_mat;  // the material of every triangle / light
+    std::vector<int32_t> albedo, emission;    // one texture index a material, -1 none
+    std::vector<glrt_cutout> cut;             // one record a material, texture -1: none
+};
+
+namespace {
+// (s, t) at (u, v) of corner coordinates q: the order glrt_texture_albedo and glrt_light_emission mix them in
+inline void mix_st(const float *q, float u, float v, float &s, float &t) {
+    const float w0 = (1.0f - u) - v;
+    s = (w0 * q[0] + u * q[2]) + v * q[4];
+    t = (w0 * q[1] + u * q[3]) + v * q[5];
+}
+}  // namespace
+
+int glrt_surface_create(const float *vert, size_t n_vert, const float *tri, size_t n_tri, const float *light, size_t n_light, const float *mat, size_t n_mat,
+                        const glrt_texture *tex, size_t n_tex, const void *texels, size_t texel_bytes, const int32_t *material_texture, const glrt_cutout *cut,
+                        const int32_t *material_emission, glrt_surface **surface_out) {
+    if (!surface_out) return GLRT_HOST_EINVAL;
+    *surface_out = nullptr;
+    if ((n_tri && (!vert || !tri)) || (n_light && (!vert || !light)) || (n_mat && !mat)) return GLRT_HOST_EINVAL;
+    if (n_tri >= (size_t)INT32_MAX || n_light >= (size_t)INT32_MAX || n_mat >= (size_t)INT32_MAX) return GLRT_HOST_EINVAL;
+    const TexRecord *rec = reinterpret_cast<const TexRecord *>(tex);
+    if (!glrt_detail::texture_set_error(rec, n_tex, texels, texel_bytes).empty()) return GLRT_HOST_EINVAL;
+    for (size_t m = 0; m < n_mat; m++) {  // what glrtx_upload_textures, glrtx_bind_cutouts and glrtx_bind_emission_maps refuse of a material
+        const int type = (int)mat[GLRT_MATERIAL_FLOATS * m];
+        if (material_texture && (material_texture[m] < -1 || (material_texture[m] >= 0 && ((size_t)material_texture[m] >= n_tex || type != 2)))) return GLRT_HOST_EINDEX;
+        if (material_emission && (material_emission[m] < -1 || (material_emission[m] >= 0 && ((size_t)material_emission[m] >= n_tex || type == 5)))) return GLRT_HOST_EINDEX;
+        if (cut) {
+            const glrt_cutout &r = cut[m];
+            if (r.texture < -1 || (r.texture >= 0 && (size_t)r.texture >= n_tex) || r.channel < 0 || r.channel > 3) return GLRT_HOST_EINDEX;
+            if (!std::isfinite(r.cutoff) || r.reserved != 0 || (r.texture >= 0 && type != 2 && type != 3)) return GLRT_HOST_EINVAL;
+        }
+    }
+    glrt_surface *s = new glrt_surface;
+    const auto corners = [&](const float *records, size_t n, std::vector<float> &st, std::vector<int32_t> &material) {
+        st.assign(6 * n, 0.0f);
+        material.assign(n, 0);
+        for (size_t t = 0; t < n; t++) {
+            const float *r = records + 4 * t;
+            for (int k = 0; k < 3; k++) {
+                if (!(r[k] >= 0.0f) || (size_t)r[k] >= n_vert) return false;
+                const float *v = vert + GLRT_VERTEX_FLOATS * (size_t)r[k];
+                st[6 * t + 2 * k] = v[6];
+                st[6 * t + 2 * k + 1] = v[7];
+            }
+            if (!(r[3] >= 0.0f) || (size_t)r[3] >= n_mat) return false;
+            material[t] = (int32_t)r[3];
+        }
+        return true;
+    };
+    if (!corners(tri, n_tri, s->tri_st, s->tri_mat) || !corners(light, n_light, s->light_st, s->light_mat)) { delete s; return GLRT_HOST_EINDEX; }
+    s->tex.assign(rec, rec + n_tex);
+    s->texels.assign((const unsigned char *)texels, (const unsigned char *)texels + (n_tex ? texel_bytes : 0));
+    s->albedo.assign(n_mat, -1);
+    s->emission.assign(n_mat, -1);
+    s->cut.assign(n_mat, glrt_cutout{-1, 3, 0.5f, 0});
+    if (material_texture) s->albedo.assign(material_texture, material_texture + n_mat);
+    if (material_emission) s->emission.assign(material_emission, material_emission + n_mat);
+    if (cut) s->cut.assign(cut, cut + n_mat);
+    *surface_out = s;
+    return GLRT_HOST_OK;
+}
+
+void glrt_surface_free(glrt_surface *surface) { delete surface; }
+
+int glrt_surface_albedo(void *surface, int tri, float u, float v, float rgb[3]) {
+    const glrt_surface &c = *static_cast<const glrt_surface *>(surface);
+    if (tri < 0 || (size_t)tri >= c.tri_mat.size()) return 0;
+    const int32_t k = c.albedo[(size_t)c.tri_mat[(size_t)tri]];
+    if (k < 0) return 0;
+    FlushDenormals ftz;
+    float s, t;
+    mix_st(&c.tri_st[6 * (size_t)tri], u, v, s, t);
+    lookup(c.tex[(size_t)k], c.texels.data(), s, t, rgb);
+    return 1;
+}
+
+int glrt_surface_accept(void *surface, int tri, float u, float v) {
+    const glrt_surface &c = *static_cast<const glrt_surface *>(surface);
+    if (tri < 0 || (size_t)tri >= c.tri_mat.size()) return 1;
+    const glrt_cutout &r = c.cut[(size_t)c.tri_mat[(size_t)tri]];
+    if (r.texture < 0) return 1;
+    FlushDenormals ftz;
+    float s, t;
+    mix_st(&c.tri_st[6 * (size_t)tri], u, v, s, t);
+    return lookup_channel(c.tex[(size_t)r.texture], c.texels.data(), r.channel, s, t) >= r.cutoff ? 1 : 0;  // (a NaN rejects)
+}
+
+int glrt_surface_emission(void *surface, int index, int light, float u, float v, float texel[3]) {
+    const glrt_surface &c = *static_cast<const glrt_surface *>(surface);
+    const std::vector<int32_t> &material = light ? c.light_mat : c.tri_mat;
+    if (index < 0 || (size_t)index >= material.size()) return 0;
+    const int32_t k = c.emission[(size_t)material[(size_t)index]];
+    if (k < 0) return 0;
+    FlushDenormals ftz;
+    float s, t;
+    mix_st(&(light ? c.light_st : c.tri_st)[6 * (size_t)index], u, v, s, t);
+    lookup(c.tex[(size_t)k], c.texels.data(), s, t, texel);
+    return 1;
+}

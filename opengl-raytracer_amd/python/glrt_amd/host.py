@@ -78,6 +78,13 @@ def lib():
         L.glrt_light_emission.argtypes = [fp, C.c_size_t, fp, C.c_size_t, fp, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, i32p, i32p, fp, C.c_size_t, fp]
         L.glrt_emission_albedo.argtypes = [fp, C.c_size_t, fp, C.c_size_t, fp, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, i32p, i32p, fp, C.c_size_t, fp]
         L.glrt_emission_bind_check.argtypes = [fp, C.c_size_t, C.c_size_t, C.c_int, i32p, C.c_size_t, C.c_char_p, C.c_size_t]
+        L.glrt_surface_create.argtypes = [fp, C.c_size_t, fp, C.c_size_t, fp, C.c_size_t, fp, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, i32p, C.c_void_p,
+                                          i32p, C.POINTER(C.c_void_p)]
+        L.glrt_surface_free.restype = None
+        L.glrt_surface_free.argtypes = [C.c_void_p]
+        L.glrt_surface_albedo.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, fp]
+        L.glrt_surface_accept.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float]
+        L.glrt_surface_emission.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, fp]
         vp = C.c_void_p
         L.glrt_env_weights.argtypes = [vp, vp, C.c_size_t, vp, fp, i32p]
         L.glrt_env_alias.argtypes = [fp, C.c_int32, fp, i32p, fp, i32p, fp]
@@ -787,6 +794,76 @@ def render_features_geom_cutout(scene, params, textures, material_texture, cut, 
     if rc != 0:
         raise RuntimeError(f"glrt_render_features_geom_cutout failed: {rc}")
     return n, a, g
+
+
+# --------------------------------------------------------------------------- surface context (include/glrt_host.h "Surface context")
+class Surface:
+    """glrt_surface_create: the albedo, cutout and emission-map lookups of `scene` (vert / tri / light / mat, as uploaded) as per-hit C calls.  textures as
+    pack_textures takes them; material_texture / material_emission one texture index a material (-1 none), cut (n_mat,) CUTOUT_DTYPE records; each may be
+    None.  hooks() is what oracle.pt_oracle.render(..., surface=...) takes: the addresses of the C calls, no Python runs per hit.  albedo / accept /
+    emission call them once from Python, for tests of the statements.  Use as a context manager, or close()."""
+
+    def __init__(self, scene, textures, material_texture=None, cut=None, material_emission=None):
+        desc, blob = pack_textures(textures)
+        v, t, m = _f32(scene["vert"]).reshape(-1, 15), _f32(scene["tri"]).reshape(-1, 4), _f32(scene["mat"]).reshape(-1, 18)
+        l = _f32(scene["light"]).reshape(-1, 4)
+
+        def per_material(a, dtype, what):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=dtype).reshape(-1)
+            if a.size != m.shape[0]:
+                raise ValueError(f"Surface: {m.shape[0]} materials, {a.size} {what}")
+            return a
+
+        b = per_material(material_texture, np.int32, "texture bindings")
+        e = per_material(material_emission, np.int32, "emission bindings")
+        rec = per_material(cut, CUTOUT_DTYPE, "cutout records")
+        self._ctx = C.c_void_p()
+        rc = lib().glrt_surface_create(_fp(v), v.shape[0], _fp(t), t.shape[0], _fp(l), l.shape[0], _fp(m), m.shape[0], desc.ctypes.data, desc.size, blob.ctypes.data,
+                                       blob.size, None if b is None else _ptr(b, C.c_int32), None if rec is None else rec.ctypes.data,
+                                       None if e is None else _ptr(e, C.c_int32), C.byref(self._ctx))
+        if rc != 0:
+            self._ctx = C.c_void_p()
+            raise RuntimeError(f"glrt_surface_create failed: {rc}")
+
+    def hooks(self, albedo=True, accept=True, emission=True):
+        """(user, albedo, accept, emission): the context and the addresses of glrt_surface_albedo / _accept / _emission (None for one switched off)"""
+        if not self._ctx:
+            raise RuntimeError("Surface: closed")
+        L = lib()
+        addr = lambda f, on: C.cast(f, C.c_void_p).value if on else None
+        return self._ctx.value, addr(L.glrt_surface_albedo, albedo), addr(L.glrt_surface_accept, accept), addr(L.glrt_surface_emission, emission)
+
+    def albedo(self, tri, u, v):
+        """(bound, rgb (3,) float32) of glrt_surface_albedo"""
+        out = np.zeros(3, np.float32)
+        return bool(lib().glrt_surface_albedo(self._ctx, int(tri), float(u), float(v), _fp(out))), out
+
+    def accept(self, tri, u, v):
+        return bool(lib().glrt_surface_accept(self._ctx, int(tri), float(u), float(v)))
+
+    def emission(self, index, light, u, v):
+        """(bound, texel (3,) float32) of glrt_surface_emission"""
+        out = np.zeros(3, np.float32)
+        return bool(lib().glrt_surface_emission(self._ctx, int(index), int(bool(light)), float(u), float(v), _fp(out))), out
+
+    def close(self):
+        if self._ctx:
+            lib().glrt_surface_free(self._ctx)
+            self._ctx = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 # --------------------------------------------------------------------------- material maps (include/glrtx.h "Material maps")

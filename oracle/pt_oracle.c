@@ -184,7 +184,7 @@ INL float rsq(float x) { return 1.0f / sqrtf(x); }
 
 /* ------------------------------------------ intersect(Ray, Triangle) :226-257
  * Returns t or INFTY; *n is written only on a hit (callers select on t<tHit). */
-INL float pt_tri(v3 o, v3 d, v3 v0, v3 v1, v3 v2, v3 n0, v3 n1, v3 n2, int want_normal, v3 *n) {
+INL float pt_tri(v3 o, v3 d, v3 v0, v3 v1, v3 v2, v3 n0, v3 n1, v3 n2, int want_normal, v3 *n, const int hooked, float *uv) {
     float e1x = v1.x - v0.x, e1y = v1.y - v0.y, e1z = v1.z - v0.z;
     float e2x = v2.x - v0.x, e2y = v2.y - v0.y, e2z = v2.z - v0.z;
     float px = d.y * e2z - d.z * e2y;
@@ -205,6 +205,7 @@ INL float pt_tri(v3 o, v3 d, v3 v0, v3 v1, v3 v2, v3 n0, v3 n1, v3 n2, int want_
     if (v < 0.0f || 1.0f < inv * (U + V)) return PT_INFTY; /* u+v>1 as inv*(U+V)>1 [order] */
     float t = dot3(e2x, e2y, e2z, qx, qy, qz) * inv;
     if (PT_EPS >= t) return PT_INFTY;
+    if (hooked) { uv[0] = u; uv[1] = v; } /* the hit's own coordinates, for the surface hooks */
     if (want_normal) {
         float w0 = (1.0f - u) - v;
         float nx = (w0 * n0.x + u * n1.x) + v * n2.x;
@@ -217,13 +218,48 @@ INL float pt_tri(v3 o, v3 d, v3 v0, v3 v1, v3 v2, v3 n0, v3 n1, v3 n2, int want_
 }
 
 /* ------------------------------------------- intersect(Ray, Intersection) :276-335 */
-typedef struct { v3 norm; float tHit; int mtrl; int hit; int tri; unsigned visits; } pt_isect;
+typedef struct { v3 norm; float tHit; int mtrl; int hit; int tri; unsigned visits; float u, v; } pt_isect;
 
-INL void pt_traverse(const pt_scene *sc, v3 o, v3 d, int want_normal, pt_isect *is) {
+/* ------------------------------------------------------------------ surface hooks -- PARITY UNPINNED
+ * Nothing of the reference has textures.  The three rules of include/glrtx.h whose whole statement is "a material constant is replaced by a lookup at the
+ * hit" -- "Textures" (param0), "Cutouts" (a candidate's acceptance), "Emission maps" (the emission term) -- enter the restatement as three callbacks, filled
+ * by the host library's own statements of the lookups (host/texture.cpp: glrt_surface_*); no shading is restated for them.  `tri` is the wire index of the
+ * hit triangle and (u, v) its barycentrics as intersect(Ray, Triangle) forms them.  Any pointer may be NULL.
+ *   albedo    returns 1 where the triangle's material is bound, and rgb then stands wherever the diffuse branch reads param0 (:514 and :372);
+ *   accept    asked for a candidate that would become the closest hit; 0: the candidate is a miss and the ray's state stays as it was;
+ *   emission  returns 1 where the material is bound, and c is the looked-up texel: the emission term becomes emission * c, one rounded product a channel.
+ *             light 0: `index` is a hit triangle, seen (:490-494); light 1: `index` is the light sampleDirect picked and (u, v) its flipped uniforms.
+ * "hooked" is a constant argument of every inlined function below, as want_normal is: pt_render_rows is instantiated without the hooks -- the pinned
+ * restatement, the code bench.py times as cpu_baseline -- and with them, and one of the two is chosen per render call. */
+typedef struct {
+    void *user;
+    int (*albedo)(void *user, int tri, float u, float v, float rgb[3]);
+    int (*accept)(void *user, int tri, float u, float v);
+    int (*emission)(void *user, int index, int light, float u, float v, float c[3]);
+} pt_surface;
+static pt_surface g_surf = {0, 0, 0, 0};
+static int g_surf_active = 0;
+void pt_oracle_set_surface(const pt_surface *s) {
+    if (s) g_surf = *s; else memset(&g_surf, 0, sizeof g_surf);
+    g_surf_active = s && (s->albedo || s->accept || s->emission);
+}
+INL v3 pt_hook_albedo(const pt_isect *is, v3 alb) {
+    float c[3];
+    if (g_surf.albedo && is->tri >= 0 && g_surf.albedo(g_surf.user, is->tri, is->u, is->v, c)) { alb.x = c[0]; alb.y = c[1]; alb.z = c[2]; }
+    return alb;
+}
+INL v3 pt_hook_emission(int index, int light, float u, float v, v3 e) {
+    float c[3];
+    if (g_surf.emission && index >= 0 && g_surf.emission(g_surf.user, index, light, u, v, c)) { e.x = e.x * c[0]; e.y = e.y * c[1]; e.z = e.z * c[2]; }
+    return e;
+}
+
+INL void pt_traverse(const pt_scene *sc, v3 o, v3 d, int want_normal, pt_isect *is, const int hooked) {
     int stack[64];
     int pos = 0;
     stack[0] = 0;
     is->tHit = PT_INFTY; is->norm.x = is->norm.y = is->norm.z = 0.f; is->mtrl = 0; is->hit = 0; is->tri = -1; is->visits = 0;
+    if (hooked) { is->u = 0.f; is->v = 0.f; }
     const int n_bvh_texels = sc->n_nodes * 3, n_vert_texels = sc->n_vert * 5;
     float ix = 1.0f / d.x, iy = 1.0f / d.y, iz = 1.0f / d.z; /* :260, recomputed per node there */
     while (pos >= 0) {
@@ -261,8 +297,12 @@ INL void pt_traverse(const pt_scene *sc, v3 o, v3 d, int want_normal, pt_isect *
                 n1 = fetch3(sc->vert, n_vert_texels, i1 + 1);
                 n2 = fetch3(sc->vert, n_vert_texels, i2 + 1);
             }
-            float dist = pt_tri(o, d, v0, v1, v2, n0, n1, n2, want_normal, &n);
+            float uv[2] = {0.f, 0.f};
+            float dist = pt_tri(o, d, v0, v1, v2, n0, n1, n2, want_normal, &n, hooked, uv);
+            /* "Cutouts": a rejected candidate is the miss intersect(Ray, Triangle) would have reported */
+            if (hooked && dist < is->tHit && g_surf.accept && !g_surf.accept(g_surf.user, index, uv[0], uv[1])) dist = PT_INFTY;
             if (dist < is->tHit) {
+                if (hooked) { is->u = uv[0]; is->v = uv[1]; }
                 is->norm = n;
                 is->mtrl = (int)tr[3];
                 is->hit = 1;
@@ -336,7 +376,7 @@ static void exp_ordered(const pt_scene *sc, v3 o, v3 d, float *t_out, int *tri_o
             int index = (int)c[2]; float tr[4]; fetch4(sc->tri, sc->n_tri, index, tr);
             int i0 = (int)tr[0] * 5, i1 = (int)tr[1] * 5, i2 = (int)tr[2] * 5;
             v3 v0 = fetch3(sc->vert, nvt, i0), v1 = fetch3(sc->vert, nvt, i1), v2 = fetch3(sc->vert, nvt, i2), z = {0, 0, 0}, n3;
-            float dist = pt_tri(o, d, v0, v1, v2, z, z, z, 0, &n3);
+            float dist = pt_tri(o, d, v0, v1, v2, z, z, z, 0, &n3, 0, 0);
             if (dist < tHit || (dist == tHit && best >= 0 && dist < PT_INFTY && g_rank[index] < g_rank[best])) best = index;
             tHit = FMIN(tHit, dist);
         }
@@ -397,7 +437,7 @@ static void exp_slot_sim(const pt_scene *sc, v3 o, v3 d) {
                 int index = (int)c[2]; float tr[4]; fetch4(sc->tri, sc->n_tri, index, tr);
                 int i0 = (int)tr[0] * 5, i1 = (int)tr[1] * 5, i2 = (int)tr[2] * 5;
                 v3 v0 = fetch3(sc->vert, nvt, i0), v1 = fetch3(sc->vert, nvt, i1), v2 = fetch3(sc->vert, nvt, i2), z = {0, 0, 0}, n3;
-                float dist = pt_tri(o, d, v0, v1, v2, z, z, z, 0, &n3);
+                float dist = pt_tri(o, d, v0, v1, v2, z, z, z, 0, &n3, 0, 0);
                 tHit = FMIN(tHit, dist);
                 break;
             }
@@ -481,8 +521,8 @@ INL float pt_sphere_t(const float *sp, v3 o, v3 d) {
     return t > PT_EPS ? t : PT_INFTY;
 }
 /* closest hit over the BVH's triangles and the spheres */
-INL void pt_traverse_ext(const pt_scene *sc, v3 o, v3 d, int want_normal, pt_isect *is) {
-    pt_traverse(sc, o, d, want_normal, is);
+INL void pt_traverse_ext(const pt_scene *sc, v3 o, v3 d, int want_normal, pt_isect *is, const int hooked) {
+    pt_traverse(sc, o, d, want_normal, is, hooked);
     for (int k = 0; k < g_ext.n_spheres; k++) {
         const float *sp = g_ext.spheres + 5 * k;
         float t = pt_sphere_t(sp, o, d);
@@ -497,7 +537,7 @@ INL void pt_traverse_ext(const pt_scene *sc, v3 o, v3 d, int want_normal, pt_ise
     }
 }
 
-INL v3 pt_radiance(const pt_scene *sc, const pt_params *pr, pt_rng *rng, v3 o, v3 d, uint64_t *rays) {
+INL v3 pt_radiance(const pt_scene *sc, const pt_params *pr, pt_rng *rng, v3 o, v3 d, uint64_t *rays, const int hooked) {
     v3 L = {0.f, 0.f, 0.f}, beta = {1.f, 1.f, 1.f};
     const int n_mat_texels = sc->n_mat * 6, n_vert_texels = sc->n_vert * 5;
     const int nL = sc->n_light;
@@ -507,7 +547,7 @@ INL v3 pt_radiance(const pt_scene *sc, const pt_params *pr, pt_rng *rng, v3 o, v
     int spec = 0; /* extension: the previous bounce was specular */
     for (int depth = 0; depth < pr->max_depth; depth++) {
         pt_isect is;
-        if (ext) pt_traverse_ext(sc, o, d, 1, &is); else pt_traverse(sc, o, d, 1, &is);
+        if (ext) pt_traverse_ext(sc, o, d, 1, &is, hooked); else pt_traverse(sc, o, d, 1, &is, hooked);
         (*rays)++;
         EXP_CHECK(is, o, d);
         const v3 n = is.norm;
@@ -529,7 +569,10 @@ INL v3 pt_radiance(const pt_scene *sc, const pt_params *pr, pt_rng *rng, v3 o, v
             /* :424-487 volume branch compiled out (ENABLE_VOLUME 0): ray unchanged */
         } else if (ext && is.hit && type == 4 && (g_ext.flags & PT_EXT_DIELECTRIC)) {
             /* extension: smooth dielectric (param0 = tint, param1.x = index of refraction), see shade_core<true> */
-            if (depth == 0 || spec) { L.x = L.x + beta.x * e.x; L.y = L.y + beta.y * e.y; L.z = L.z + beta.z * e.z; }
+            if (depth == 0 || spec) {
+                if (hooked) e = pt_hook_emission(is.tri, 0, is.u, is.v, e);
+                L.x = L.x + beta.x * e.x; L.y = L.y + beta.y * e.y; L.z = L.z + beta.z * e.z;
+            }
             v3 tint = fetch3(sc->mat, n_mat_texels, m6 + 2);
             float ior = fetch3(sc->mat, n_mat_texels, m6 + 3).x;
             float rl = rsq(dot3(d.x, d.y, d.z, d.x, d.y, d.z));
@@ -563,6 +606,7 @@ INL v3 pt_radiance(const pt_scene *sc, const pt_params *pr, pt_rng *rng, v3 o, v
         } else {
             /* :490-499 (specularReflect / passedVolume are never true in the reference; the extension sets the former) */
             if ((depth == 0 || (ext && spec)) && is.hit) {
+                if (hooked) e = pt_hook_emission(is.tri, 0, is.u, is.v, e);
                 L.x = L.x + beta.x * e.x; L.y = L.y + beta.y * e.y; L.z = L.z + beta.z * e.z;
             }
             if (!is.hit) break;
@@ -591,6 +635,7 @@ INL v3 pt_radiance(const pt_scene *sc, const pt_params *pr, pt_rng *rng, v3 o, v
                 wiL.y = pt_sin(r1) * r2s;
                 wiL.z = sqrtf(1.0f - rb);
                 v3 alb = fetch3(sc->mat, n_mat_texels, m6 + 2);
+                if (hooked) alb = pt_hook_albedo(&is, alb);
                 f.x = alb.x / PT_PI; f.y = alb.y / PT_PI; f.z = alb.z / PT_PI;
                 pdf = wiL.z / PT_PI;
             } else if (type == 3) {
@@ -691,7 +736,7 @@ INL v3 pt_radiance(const pt_scene *sc, const pt_params *pr, pt_rng *rng, v3 o, v
                 float rd = rsq(dd);
                 v3 dir = {dvx * rd, dvy * rd, dvz * rd};
                 pt_isect sh;
-                if (ext) pt_traverse_ext(sc, so, dir, 0, &sh); else pt_traverse(sc, so, dir, 0, &sh);
+                if (ext) pt_traverse_ext(sc, so, dir, 0, &sh, hooked); else pt_traverse(sc, so, dir, 0, &sh, hooked);
                 (*rays)++;
                 EXP_CHECK(sh, so, dir);
                 float dist = sqrtf(dd);
@@ -701,6 +746,7 @@ INL v3 pt_radiance(const pt_scene *sc, const pt_params *pr, pt_rng *rng, v3 o, v
                     v3 fb = {0.f, 0.f, 0.f};
                     if (type == 2) {
                         fb = fetch3(sc->mat, n_mat_texels, m6 + 2); /* no 1/PI :372 */
+                        if (hooked) fb = pt_hook_albedo(&is, fb);
                     } else if (type == 3) {
                         v3 alp = fetch3(sc->mat, n_mat_texels, m6 + 4);
                         v3 eta = fetch3(sc->mat, n_mat_texels, m6 + 3);
@@ -731,6 +777,7 @@ INL v3 pt_radiance(const pt_scene *sc, const pt_params *pr, pt_rng *rng, v3 o, v
                     float dot1 = (-(dir.z * nl.z) - (dir.y * nl.y)) - (dir.x * nl.x);
                     TRACE("  dot0 %.9g dot1 %.9g\n", dot0, dot1);
                     if (0.0f < FMIN(dot0, dot1)) {
+                        if (hooked) el = pt_hook_emission(lid, 1, ua, ub, el); /* Le at the sample's coordinates, only where it contributes */
                         float e1x = v1.x - v0.x, e1y = v1.y - v0.y, e1z = v1.z - v0.z;
                         float e2x = v2.x - v0.x, e2y = v2.y - v0.y, e2z = v2.z - v0.z;
                         float cx = e1y * e2z - e1z * e2y;
@@ -777,7 +824,7 @@ INL v3 pt_radiance(const pt_scene *sc, const pt_params *pr, pt_rng *rng, v3 o, v
 
 /* One pixel of main() :565-614.  acc = (L.r, L.g, L.b, count), read-modify-write
  * (replaces the ping-pong FBO pair, window.cpp:214-252). */
-INL void pt_pixel(const pt_scene *sc, const pt_params *pr, int px, int py, float *acc, uint64_t *rays) {
+INL void pt_pixel(const pt_scene *sc, const pt_params *pr, int px, int py, float *acc, uint64_t *rays, const int hooked) {
     const float W = (float)pr->width, H = (float)pr->height;
     const float fcx = (float)px + 0.5f, fcy = (float)py + 0.5f;
     pt_rng rng;
@@ -823,33 +870,43 @@ INL void pt_pixel(const pt_scene *sc, const pt_params *pr, int px, int py, float
         float ez = (C[2] * dx + C[6] * dy) + C[10] * dz;
         float re = rsq((ez * ez + ey * ey) + ex * ex);
         v3 d = {ex * re, ey * re, ez * re};
-        v3 Ls = pt_radiance(sc, pr, &rng, o, d, rays);
+        v3 Ls = pt_radiance(sc, pr, &rng, o, d, rays, hooked);
         Lr = Lr + Ls.x; Lg = Lg + Ls.y; Lb = Lb + Ls.z;
         cnt = cnt + 1.0f;
     }
     acc[0] = Lr; acc[1] = Lg; acc[2] = Lb; acc[3] = cnt;
 }
 
-__attribute__((target_clones("default", "fma")))
-static uint64_t pt_render_rows(const pt_scene *sc, const pt_params *pr, float *accum, size_t pitch_floats,
-                               int y0, int y1, int threads) {
-    uint64_t total = 0;
+/* The row loop, stated once and instantiated twice -- without the surface hooks (the pinned restatement) and with them.  A macro, not an inlined function
+ * with a constant argument: the OpenMP region is outlined into a function of its own before any inlining happens, and a body shared by both instantiations
+ * would read "hooked" at run time and leave the target clones behind. */
 #ifdef _OPENMP
-    if (threads > 0) omp_set_num_threads(threads);
-#pragma omp parallel for schedule(dynamic, 1) reduction(+ : total)
+#define PT_OMP_THREADS(n) do { if ((n) > 0) omp_set_num_threads(n); } while (0)
+#define PT_OMP_ROWS _Pragma("omp parallel for schedule(dynamic, 1) reduction(+ : total)")
+#else
+#define PT_OMP_THREADS(n) ((void)0)
+#define PT_OMP_ROWS
 #endif
-    for (int y = y0; y < y1; y++) {
-        uint64_t rays = 0;
-        /* llvmpipe's rasteriser threads run with denormals flushed (MXCSR FTZ|DAZ); per OpenMP thread */
-        const unsigned csr = _mm_getcsr();
-        _mm_setcsr(csr | 0x8040u);
-        for (int x = 0; x < pr->width; x++) pt_pixel(sc, pr, x, y, accum + (size_t)y * pitch_floats + 4 * (size_t)x, &rays);
-        _mm_setcsr(csr);
-        total += rays;
+#define PT_RENDER_ROWS(NAME, HOOKED)                                                                                                  \
+    __attribute__((target_clones("default", "fma")))                                                                                  \
+    static uint64_t NAME(const pt_scene *sc, const pt_params *pr, float *accum, size_t pitch_floats, int y0, int y1, int threads) {   \
+        uint64_t total = 0;                                                                                                           \
+        PT_OMP_THREADS(threads);                                                                                                      \
+        PT_OMP_ROWS                                                                                                                   \
+        for (int y = y0; y < y1; y++) {                                                                                               \
+            uint64_t rays = 0;                                                                                                        \
+            /* llvmpipe's rasteriser threads run with denormals flushed (MXCSR FTZ|DAZ); per OpenMP thread */                         \
+            const unsigned csr = _mm_getcsr();                                                                                        \
+            _mm_setcsr(csr | 0x8040u);                                                                                                \
+            for (int x = 0; x < pr->width; x++) pt_pixel(sc, pr, x, y, accum + (size_t)y * pitch_floats + 4 * (size_t)x, &rays, HOOKED); \
+            _mm_setcsr(csr);                                                                                                          \
+            total += rays;                                                                                                            \
+        }                                                                                                                             \
+        (void)threads;                                                                                                                \
+        return total;                                                                                                                 \
     }
-    (void)threads;
-    return total;
-}
+PT_RENDER_ROWS(pt_render_rows, 0)
+PT_RENDER_ROWS(pt_render_rows_hooked, 1)
 
 /* ------------------------------------------------------------------ C entry
  * accum: height rows of pitch_bytes, each width float4 (L.rgb, count); row 0 is
@@ -861,6 +918,7 @@ uint64_t pt_oracle_render(const pt_scene *sc, const pt_params *pr, float *accum,
     exp_build_rank(sc);
     exp_build_kind(sc);
 #endif
+    if (g_surf_active) return pt_render_rows_hooked(sc, pr, accum, pitch_bytes / sizeof(float), y0, y1, threads);
     return pt_render_rows(sc, pr, accum, pitch_bytes / sizeof(float), y0, y1, threads);
 }
 
@@ -959,6 +1017,13 @@ void pt_oracle_resolve(const float *accum, size_t pitch_bytes, int width, int he
 #ifdef PT_ORDERED_EXPERIMENT
 void pt_oracle_exp_stats(unsigned long long *out) { for (int i = 0; i < 16; i++) out[i] = g_exp[i]; }
 #endif
+
+/* Which source this library was built from: oracle/Makefile passes the content hash of pt_oracle.c and of itself, and pt_oracle.py refuses to load a
+ * library that carries another one (a library compiled by hand carries "unstamped" and is taken as it is). */
+#ifndef PT_SRC_ID
+#define PT_SRC_ID "unstamped"
+#endif
+const char pt_oracle_src_id[] = "pt_oracle_src_id=" PT_SRC_ID;
 
 int pt_oracle_max_threads(void) {
 #ifdef _OPENMP

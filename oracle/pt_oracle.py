@@ -7,6 +7,7 @@ never as a fallback for the HIP path.
 from __future__ import annotations
 
 import ctypes as C
+import hashlib
 import pathlib
 import subprocess
 
@@ -28,10 +29,29 @@ class _Params(C.Structure):
                 ("height", C.c_int)]
 
 
+class _Surface(C.Structure):  # pt_surface
+    _fields_ = [("user", C.c_void_p), ("albedo", C.c_void_p), ("accept", C.c_void_p), ("emission", C.c_void_p)]
+
+
+def _src_id() -> str:
+    """oracle/Makefile's SRC_ID: the content hash of the source and of the Makefile"""
+    return hashlib.sha256((_HERE / "pt_oracle.c").read_bytes() + (_HERE / "Makefile").read_bytes()).hexdigest()[:16]
+
+
+def _fresh() -> bool:
+    """The library exists and was built from this pt_oracle.c (or by hand: "unstamped").  By content, not by time stamp: _ref/ is outside git and may hold a
+    newer library built from another commit's source."""
+    if not _LIB.exists():
+        return False
+    blob = _LIB.read_bytes()
+    return b"pt_oracle_src_id=" + _src_id().encode() + b"\0" in blob or b"pt_oracle_src_id=unstamped\0" in blob
+
+
 def build(force: bool = False) -> pathlib.Path:
-    src = _HERE / "pt_oracle.c"
-    if force or not _LIB.exists() or _LIB.stat().st_mtime < src.stat().st_mtime:
-        subprocess.run(["make", "-C", str(_HERE), "_ref/libpt_oracle.so"], check=True, capture_output=True)
+    if force or not _fresh():
+        subprocess.run(["make", "-B", "-C", str(_HERE), "_ref/libpt_oracle.so"], check=True, capture_output=True)
+        if not _fresh():
+            raise RuntimeError(f"{_LIB} does not carry the id of {_HERE / 'pt_oracle.c'} after a rebuild")
     return _LIB
 
 
@@ -54,6 +74,8 @@ def lib():
         L.pt_oracle_set_ext.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.pt_oracle_resolve.restype = None
         L.pt_oracle_resolve.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_size_t]
+        L.pt_oracle_set_surface.restype = None
+        L.pt_oracle_set_surface.argtypes = [C.POINTER(_Surface)]
         _lib = L
     return _lib
 
@@ -65,17 +87,23 @@ def _f32(a):
 EXT_DIELECTRIC, EXT_WHITTED = 1, 2
 
 
-def render(scene, params, accum=None, rows=None, threads=0, spheres=None, ext_flags=0):
+def render(scene, params, accum=None, rows=None, threads=0, spheres=None, ext_flags=0, surface=None):
     """Returns (accum (H, W, 4) float32 [L.rgb, count], n_rays).  Row 0 = bottom (gl_FragCoord.y = 0.5).
     spheres (n, 5) [cx, cy, cz, radius, material] / ext_flags: the PARITY-UNPINNED extensions (analytic spheres, EXT_DIELECTRIC,
-    EXT_WHITTED) -- the CPU statement of the device kernel's extension path, nothing of the reference's."""
+    EXT_WHITTED) -- the CPU statement of the device kernel's extension path, nothing of the reference's.
+    surface: (user, albedo, accept, emission) -- a context pointer and the ADDRESSES of three C functions with pt_surface's signatures (pt_oracle.c "surface
+    hooks"; glrt_amd.host.Surface.hooks() makes them), any of them None: PARITY UNPINNED as well.  No Python runs per hit; the caller keeps `user` alive."""
     L = lib()
     sph = None if spheres is None else _f32(np.asarray(spheres, np.float32).reshape(-1, 5))
     L.pt_oracle_set_ext(None if sph is None else sph.ctypes.data, 0 if sph is None else sph.shape[0], int(ext_flags))
     try:
+        if surface is not None:
+            user, albedo, accept, emission = surface
+            L.pt_oracle_set_surface(C.byref(_Surface(user, albedo, accept, emission)))
         return _render(L, scene, params, accum, rows, threads)
     finally:
         L.pt_oracle_set_ext(None, 0, 0)
+        L.pt_oracle_set_surface(None)
 
 
 def _render(L, scene, params, accum, rows, threads):
