@@ -351,6 +351,28 @@ int glrt_emission_albedo(const float *vert, size_t n_vert, const float *tri, siz
 int glrt_emission_bind_check(const float *mat, size_t n_scene_mat, size_t n_tex, int cutouts_bound, const int32_t *material_emission, size_t n_mat, char *msg,
                              size_t cap);
 
+/* A launch's route: which kernel a render call of a device context runs and what glrtx_stats reports about it, or why the call refuses -- the device layer's
+ * own statement (host/route_statement.h; DESIGN.md "A launch's route"), as a function of the context fields and parameters that decide it.
+ *   state   the context as the call finds it: n_spheres, n_tex and n_vine are counts (n_vine > 0: the uploaded tree is a vine), the have_* fields and the
+ *           two switches are 0 or 1 -- vol_switch / tex_switch: glrtx_set_volume_wavefront / glrtx_set_texture_wavefront, or what GLRTX_VOLUME_WAVEFRONT /
+ *           GLRTX_TEXTURE_WAVEFRONT put in their place.
+ *   kind    the call: glrtx_render and glrtx_render_frames, glrtx_render_adaptive, glrtx_render_moments, glrtx_hit_histogram,
+ *           glrtx_render_adaptive_moments, glrtx_render_cascades.
+ * GLRT_HOST_OK: *route_out holds the kernel family (= variant_last), fallback_last, whether the launch counts in fallback_launches, the row of the family's
+ * table of forms and the kernel's name as glrtx_debug_last_kernel gives it; msg is "".  GLRT_HOST_EINVAL: the call refuses, msg (cap bytes) holds the device's
+ * message behind its "<function>: ", *route_out is zeroed.  GLRT_HOST_EINDEX: a NULL state or route_out, or no such kind. */
+#define GLRT_ROUTE_ORDINARY 0
+#define GLRT_ROUTE_ADAPTIVE 1
+#define GLRT_ROUTE_MOMENTS 2
+#define GLRT_ROUTE_CALIBRATION 3
+#define GLRT_ROUTE_ADAPTIVE_MOMENTS 4
+#define GLRT_ROUTE_CASCADES 5
+typedef struct glrt_route_state {
+    int32_t variant, ext_flags, n_spheres, n_tex, n_vine, have_volume, have_maps, have_cut, have_emit, have_env, vol_switch, tex_switch, max_depth, n_samples;
+} glrt_route_state;
+typedef struct glrt_route { int32_t family, variant_last, fallback_last, fallback_counts, form; char kernel[96]; } glrt_route;
+int glrt_launch_route(const glrt_route_state *state, int kind, glrt_route *route_out, char *msg, size_t cap);
+
 /* Surface context: the three lookups above -- the albedo of "Textures", the acceptance of "Cutouts", the texel of "Emission maps" -- as per-hit calls with C
  * linkage, for a CPU path tracer that takes them as callbacks (oracle/pt_oracle.c: pt_oracle_set_surface).  The lookups stay stated once: the calls are built
  * on the statements behind glrt_texture_lookup and glrt_texture_channel and mix the coordinates as glrt_texture_albedo and glrt_light_emission do,

@@ -38,6 +38,7 @@
 #include "../host/normal_topology.h"
 #include "../host/texture_set.h"
 #include "../host/emission_statement.h"
+#include "../host/route_statement.h"
 #include "../host/env_tables.h"
 static_assert(glrtx::lbvh::kRotationPasses == GLRT_LBVH_ROTATION_PASSES, "device and CPU LBVH statements must run the same rotation sweeps");
 static_assert(glrtx::lbvh::kRebuildLeaves == GLRT_LBVH_REBUILD_LEAVES, "device and CPU LBVH statements must rebuild the same subtrees");
@@ -1028,45 +1029,6 @@ TexSet tex_set(const glrtx_ctx *c) {
                   c->have_maps ? (const MapRec *)c->texMaps.p : nullptr};
 }
 
-// Volume launches on the wavefront kernel (its V form, kWgwfVolume): the switch is on (glrtx_set_volume_wavefront; GLRTX_VOLUME_WAVEFRONT=0/1, read at every
-// launch like the other switches, overrides it), the volume is the only extension, a volume is uploaded and no spheres are.
-bool vol_wavefront(const glrtx_ctx *c) {
-    bool on = c->vol_wavefront;
-    if (const char *v = std::getenv("GLRTX_VOLUME_WAVEFRONT")) on = std::atoi(v) != 0;
-    return on && c->ext_flags == GLRTX_EXT_VOLUME && c->have_volume && c->n_spheres == 0 && c->n_tex == 0 && !c->have_env;  // (beside the volume, textures and the environment are shaded by the megakernel only)
-}
-
-// Whether the wavefront variant's packed path state can represent this launch (meta = depth | sample << 8 | flags << 28; the V form: sample in bits 8-23).
-bool wgwf_can_hold(const glrtx_params *p, bool vol = false) { return p->max_depth <= kWfDepthMax && p->n_samples <= (vol ? kWfVolSampleMax : kWfSampleMax); }
-
-// Textured launches on the wavefront kernel (its T form, kWgwfTextured; TM, kWgwfMaps, while maps are bound): the switch is on (glrtx_set_texture_wavefront;
-// GLRTX_TEXTURE_WAVEFRONT=0/1, read at every launch, overrides it), a set is bound, and nothing else needs the extension megakernel: no extension flag, no
-// spheres, no environment; and the tree is not a vine (the list scan has no T form).  `why_not` (optional): the first of these that does not hold, for a refusal.
-bool tex_wavefront(const glrtx_ctx *c, const char **why_not = nullptr) {
-    bool on = c->tex_wavefront;
-    if (const char *v = std::getenv("GLRTX_TEXTURE_WAVEFRONT")) on = std::atoi(v) != 0;
-    const char *why = c->n_tex == 0 ? "no set is bound"
-                      : c->have_cut ? "cutouts are bound (the wavefront kernel's traversal step has no cutout form)"
-                      : c->have_emit ? "emission maps are bound (the wavefront kernel's shade phase has no emission-map form)"
-                      : !on ? "the texture wavefront switch is off (glrtx_set_texture_wavefront)"
-                      : c->ext_flags != 0 ? "extensions or volume are on"
-                      : c->n_spheres > 0 ? "spheres are uploaded"
-                      : c->have_env ? "an environment is bound"
-                      : c->sc.n_vine > 0 ? "the tree is a vine (the list scan has no textured form)"
-                      : nullptr;
-    if (why_not) *why_not = why;
-    return why == nullptr;
-}
-
-// Whether a launch of this context runs on the wavefront kernel (variant 2): no extensions, or the volume alone with the V form switched on, or a texture set
-// alone with the T / TM forms switched on.
-bool wgwf_routes(const glrtx_ctx *c, const glrtx_params *p) {
-    if (c->variant != 2 || c->n_spheres > 0 || c->have_env) return false;
-    if (c->n_tex > 0) return tex_wavefront(c) && wgwf_can_hold(p);
-    if (c->ext_flags == 0) return wgwf_can_hold(p);
-    return vol_wavefront(c) && wgwf_can_hold(p, true);
-}
-
 bool same_camera(const glrtx_params &a, const glrtx_params &b) {
     return std::memcmp(a.c2w, b.c2w, sizeof a.c2w) == 0 && std::memcmp(a.s2c, b.s2c, sizeof a.s2c) == 0 && std::memcmp(&a.aperture, &b.aperture, 4) == 0 &&
            std::memcmp(&a.focal, &b.focal, 4) == 0 && a.n_samples == b.n_samples && a.max_depth == b.max_depth;
@@ -1310,6 +1272,30 @@ struct RenderReq {
     float4 *accum(const glrtx_ctx *c) const { return calibration() ? scratch : c->accum; }
 };
 
+// ---- a launch's route (host/route_statement.h; DESIGN.md "A launch's route"): which kernel a call of `kind` runs on this context with these parameters, in
+// which shading form, what the statistics say about it -- or why the call refuses.  Stated there, once; here the context's fields are handed over.  The two
+// switches are read once a call: glrtx_set_*_wavefront's value, or GLRTX_VOLUME_WAVEFRONT / GLRTX_TEXTURE_WAVEFRONT = 0/1 in its place.
+using glrt_detail::Route;
+static_assert(glrt_detail::kWfDepthMax == kWfDepthMax && glrt_detail::kWfSampleMax == kWfSampleMax && glrt_detail::kWfVolSampleMax == kWfVolSampleMax,
+              "the route statement's ranges are the path state's");
+static_assert(glrt_detail::kRouteExtVolume == GLRTX_EXT_VOLUME && glrt_detail::kRouteFallbackDepth == GLRTX_FALLBACK_DEPTH &&
+              glrt_detail::kRouteFallbackSamples == GLRTX_FALLBACK_SAMPLES && glrt_detail::kRouteFallbackExtensions == GLRTX_FALLBACK_EXTENSIONS, "the route statement's flag values");
+static_assert((int)RenderReq::Ordinary == glrt_detail::kRouteOrdinary && (int)RenderReq::Adaptive == glrt_detail::kRouteAdaptive &&
+              (int)RenderReq::Moments == glrt_detail::kRouteMoments && (int)RenderReq::Calibration == glrt_detail::kRouteCalibration &&
+              (int)RenderReq::AdaptiveMoments == glrt_detail::kRouteAdaptiveMoments && (int)RenderReq::Cascades == glrt_detail::kRouteCascades, "the route statement's request kinds");
+bool wavefront_switch(const char *name, bool set) {
+    const char *v = std::getenv(name);
+    return v ? std::atoi(v) != 0 : set;
+}
+Route route_of(const glrtx_ctx *c, const glrtx_params *p, RenderReq::Kind kind) {
+    const glrt_detail::RouteState s{c->variant,  c->ext_flags, c->n_spheres, c->n_tex,    c->sc.n_vine, c->have_volume, c->have_maps,
+                                    c->have_cut, c->have_emit, c->have_env,  wavefront_switch("GLRTX_VOLUME_WAVEFRONT", c->vol_wavefront),
+                                    wavefront_switch("GLRTX_TEXTURE_WAVEFRONT", c->tex_wavefront), p->max_depth, p->n_samples};
+    return glrt_detail::launch_route(s, (glrt_detail::RouteKind)kind);
+}
+bool on_wavefront(const Route &r) { return r.refusal.empty() && r.family == glrt_detail::kRouteWavefront; }
+int route_refusal(glrtx_ctx *c, const Route &r, const char *fn) { return r.refusal.empty() ? GLRTX_OK : fail(c, GLRTX_EINVAL, "%s: %s", fn, r.refusal.c_str()); }
+
 // The node fetch the wavefront kernel's traversal uses on this scene (vine: the list scan, fetch 0): 0 one record per lane, 1 pair-cooperative, 2 the two
 // in alternate steps.  Picked by the size of the record array; GLRTX_PAIR_FETCH=0/1/2 overrides (read at every launch).  (See wgwf_kernel.)
 int wgwf_fetch(const glrtx_ctx *c, bool vine) {
@@ -1385,7 +1371,8 @@ WgwfLaunch::Form wgwf_form(glrtx_ctx *c, const WgwfLaunch &L) {
     return f;
 }
 
-// ---- the kernel and how many of its workgroups fit the device.  Eight instantiations: ray counting on/off x (list scan of a vine (brute-force) tree | tree traversal
+// ---- the kernel and how many of its workgroups fit the device.  The shading form -- plain, V, T or TM -- is the route's (route_of); the traversal that serves
+// it is chosen here, from the tree and its size.  The plain form has four: ray counting on/off x (list scan of a vine (brute-force) tree | tree traversal
 // with one record per lane | with the pair-cooperative node fetch | with the two in alternate steps).  The pair fetch trades 25 vector-ALU instructions per step for a
 // third less time in the CU's vector-memory pipe (trav_asm.hip.h): it pays where a wave's lanes are spread over many records -- large trees, incoherent rays: config 5
 // (100 k triangles) -9 % per frame -- and costs ~1 % where they share the top of a small tree (headline, 10 k triangles: the step is paced by instruction issue there),
@@ -1396,41 +1383,34 @@ WgwfLaunch::Form wgwf_form(glrtx_ctx *c, const WgwfLaunch &L) {
 // compiled in (GLRTX_PAIR_FETCH=2).  Random triangle soups prefer the pair form from 10 k triangles on (-2 %; 20 k: -4.5 %, 70 k: -7 %): what decides is how
 // far apart a wave's rays are in the tree, which the record count only approximates.
 // The compact node array (pack_compact) has its own four: wgwf_compact.
-// The V form (kWgwfVolume: glrtx_set_volume_wavefront; routed here only with the volume alone, wgwf_routes) has one fetch form only: one record per lane on
+// The V form (kWgwfVolume: glrtx_set_volume_wavefront; routed here only with the volume alone) has one fetch form only: one record per lane on
 // DevScene::nodes, as in the megakernels (no list scan, no pair fetch, no compact layout).
-// The T and TM forms (kWgwfTextured, kWgwfMaps: glrtx_set_texture_wavefront; routed here only with a texture set alone, wgwf_routes) exist for the fetch forms the
+// The T and TM forms (kWgwfTextured, kWgwfMaps: glrtx_set_texture_wavefront; routed here only with a texture set alone) exist for the fetch forms the
 // host picks for trees by default -- one record per lane, pair-cooperative, the compact array --: a forced GLRTX_PAIR_FETCH=2 is served as 0, a vine never gets here.
 // Each of the twelve has its ADAPT twin (kWgwfAdaptive: glrtx_render_adaptive, glrtx_render_adaptive_moments): 48 instantiations, one table.
 enum WgwfTrav { kTravVine, kTravFetch0, kTravFetch1, kTravFetch2, kTravCompact, kTravVolume, kTravTex0, kTravTex1, kTravTexCompact, kTravMaps0, kTravMaps1, kTravMapsCompact,
                 kTravForms };
 #define GLRTX_WGWF_ROW(VINE, FLAGS) {{pt_render_wgwf<false, VINE, FLAGS>, pt_render_wgwf<true, VINE, FLAGS>}, \
                                      {pt_render_wgwf<false, VINE, (FLAGS) | kWgwfAdaptive>, pt_render_wgwf<true, VINE, (FLAGS) | kWgwfAdaptive>}}
-constexpr WgwfFn kWgwfKernels[kTravForms][2][2] = {  // [traversal][adaptive][count_rays]
+constexpr WgwfFn kWgwfKernels[kTravForms][2][2] = {  // [traversal][adaptive][count_rays]; the names of the shading forms: glrt_detail::kWgwfNames
     GLRTX_WGWF_ROW(true, 0), GLRTX_WGWF_ROW(false, 0), GLRTX_WGWF_ROW(false, 1), GLRTX_WGWF_ROW(false, 2), GLRTX_WGWF_ROW(false, kWgwfCompact), GLRTX_WGWF_ROW(false, kWgwfVolume),
     GLRTX_WGWF_ROW(false, kWgwfTextured), GLRTX_WGWF_ROW(false, kWgwfTextured | 1), GLRTX_WGWF_ROW(false, kWgwfTextured | kWgwfCompact),
     GLRTX_WGWF_ROW(false, kWgwfTextured | kWgwfMaps), GLRTX_WGWF_ROW(false, kWgwfTextured | kWgwfMaps | 1), GLRTX_WGWF_ROW(false, kWgwfTextured | kWgwfMaps | kWgwfCompact)};
 #undef GLRTX_WGWF_ROW
-constexpr const char *kWgwfNames[5][2] = {  // [list scan | tree | volume | textures | textures and maps][adaptive] (error reports)
-    {"pt_render_wgwf (list scan)", "pt_render_wgwf (adaptive, list scan)"}, {"pt_render_wgwf", "pt_render_wgwf (adaptive)"}, {"pt_render_wgwf (volume)", "pt_render_wgwf (volume, adaptive)"},
-    {"pt_render_wgwf (textures)", "pt_render_wgwf (textures, adaptive)"}, {"pt_render_wgwf (textures, maps)", "pt_render_wgwf (textures, maps, adaptive)"}};
 
-int wgwf_kernel(glrtx_ctx *c, WgwfLaunch &L) {
+int wgwf_kernel(glrtx_ctx *c, WgwfLaunch &L, const Route &route) {
     WgwfLaunch::Kernel &k = L.k;
-    k.vol = c->ext_flags != 0;
-    k.tex = c->n_tex > 0;  // (render_one sends a bound set here only when tex_wavefront() holds: no extension flag, no vine)
-    k.maps = k.tex && c->have_maps;
+    k.vol = route.vol; k.tex = route.tex; k.maps = route.maps; k.vine = route.vine;  // the shading form: the route's (a set beside the volume or on a vine never gets here)
     k.adapt = L.req.adaptive();
-    k.vine = c->sc.n_vine > 0 && !k.vol;
     k.fetch = k.vol ? 0 : wgwf_fetch(c, k.vine);
     if (k.tex && k.fetch == 2) k.fetch = 0;  // (the alternating fetch has no T form: served as one record per lane, and reported so)
     c->st.node_fetch_last = k.fetch;
     k.compact = !k.vol && wgwf_compact(c, k.vine, k.fetch);
     c->st.node_layout_last = k.compact ? 1 : 0;
-    if (k.tex && (k.vol || k.vine)) return fail(c, GLRTX_EDEVICE, "internal: a texture set routed to the wavefront kernel beside %s", k.vol ? "the volume" : "a vine tree");
     const int trav = k.tex ? (k.maps ? kTravMaps0 : kTravTex0) + (k.compact ? 2 : k.fetch)
                            : k.vol ? kTravVolume : k.compact ? kTravCompact : k.vine ? kTravVine : kTravFetch0 + k.fetch;
     k.fn = kWgwfKernels[trav][k.adapt][L.req.count_rays(c)];
-    k.name = kWgwfNames[k.maps ? 4 : k.tex ? 3 : k.vol ? 2 : k.vine ? 0 : 1][k.adapt];
+    k.name = route.kernel;
     // (north_star's "primitives staged into LDS": materials, camera block, root box and the per-lane stacks are; the top tree levels were built, measured worth
     // nothing -- profiles/r02_lds_top.json -- and removed.)
     k.lds = wgwf_lds_base(c) + (k.compact ? c->sc.n_crank * (int)sizeof(uint2) : 0);  // | rank table
@@ -1446,11 +1426,9 @@ int wgwf_kernel(glrtx_ctx *c, WgwfLaunch &L) {
     return GLRTX_OK;
 }
 
-// ---- the persistent megakernel (variant 1: render_one): its instantiation and its grid, then the launch.  The ten forms of pt_render_persistent that exist,
-// each with and without ray counting: one table.
-enum PersistForm { kFormPlain, kFormExt, kFormVol, kFormTex, kFormTexVol, kFormTexMaps, kFormTexVolMaps, kFormEnv, kFormEnvTex, kFormEnvTexMaps,
-                   kFormTexCut, kFormTexMapsCut, kFormEnvTexCut, kFormEnvTexMapsCut, kFormTexEmit, kFormTexMapsEmit, kFormEnvTexEmit, kFormEnvTexMapsEmit,
-                   kPersistForms };
+// ---- the persistent megakernel (variant 1: render_one): its instantiation and its grid, then the launch.  The eighteen forms of pt_render_persistent that
+// exist, each with and without ray counting: one table, in the order of glrt_detail::PersistForm -- the route picks the row and knows its name.
+using glrt_detail::kPersistForms;
 #define GLRTX_PERSIST_ROW(EXT, VOL, TEX, ENV, MAPS) \
     {(const void *)pt_render_persistent<false, EXT, VOL, TEX, ENV, MAPS>, (const void *)pt_render_persistent<true, EXT, VOL, TEX, ENV, MAPS>}
 #define GLRTX_PERSIST_CUT_ROW(ENV, MAPS) \
@@ -1459,7 +1437,7 @@ enum PersistForm { kFormPlain, kFormExt, kFormVol, kFormTex, kFormTexVol, kFormT
     {(const void *)pt_render_persistent<false, true, false, true, ENV, MAPS, false, Emit>, (const void *)pt_render_persistent<true, true, false, true, ENV, MAPS, false, Emit>}
 // [form][count_rays]; the fourth argument is a VolArgs, in the kFormEnv* rows an EnvArgs, in the k*Cut rows a CutTail of either (include/glrtx.h "Cutouts"),
 // in the k*Emit rows an EmitTail of either (include/glrtx.h "Emission maps")
-const void *const kPersistent[kPersistForms][2] = {
+const void *const kPersistent[kPersistForms][2] = {  // plain, ext, vol | tex, +vol, +maps, +vol +maps | env, +tex, +tex +maps | cut: tex, +maps, env +tex, +maps | emit: likewise
     GLRTX_PERSIST_ROW(false, false, false, false, false), GLRTX_PERSIST_ROW(true, false, false, false, false), GLRTX_PERSIST_ROW(true, true, false, false, false),
     GLRTX_PERSIST_ROW(true, false, true, false, false),   GLRTX_PERSIST_ROW(true, true, true, false, false),   GLRTX_PERSIST_ROW(true, false, true, false, true),
     GLRTX_PERSIST_ROW(true, true, true, false, true),     GLRTX_PERSIST_ROW(true, false, false, true, false),  GLRTX_PERSIST_ROW(true, false, true, true, false),
@@ -1469,39 +1447,16 @@ const void *const kPersistent[kPersistForms][2] = {
 #undef GLRTX_PERSIST_ROW
 #undef GLRTX_PERSIST_EMIT_ROW
 #undef GLRTX_PERSIST_CUT_ROW
-constexpr const char *kPersistentNames[kPersistForms] = {  // (error reports)
-    "pt_render_persistent", "pt_render_persistent (extensions)", "pt_render_persistent (volume)", "pt_render_persistent (extensions, textures)",
-    "pt_render_persistent (volume, textures)", "pt_render_persistent (extensions, textures, maps)", "pt_render_persistent (volume, textures, maps)",
-    "pt_render_persistent (extensions, environment)", "pt_render_persistent (extensions, environment, textures)",
-    "pt_render_persistent (extensions, environment, textures, maps)",
-    "pt_render_persistent (extensions, textures, cutouts)", "pt_render_persistent (extensions, textures, maps, cutouts)",
-    "pt_render_persistent (extensions, environment, textures, cutouts)", "pt_render_persistent (extensions, environment, textures, maps, cutouts)",
-    "pt_render_persistent (extensions, textures, emission maps)", "pt_render_persistent (extensions, textures, maps, emission maps)",
-    "pt_render_persistent (extensions, environment, textures, emission maps)", "pt_render_persistent (extensions, environment, textures, maps, emission maps)"};
-struct PersistLaunch { const void *fn; const char *name; bool vol, env, cut, emit; int lds, grid; ExtArgs ex; };
+struct PersistLaunch { const void *fn; int lds, grid; ExtArgs ex; };
 
-// ext: render_one's (spheres, an extension flag, a texture set that is not the wavefront kernel's, an environment); lds: the plain kernel's LDS bytes
-int persist_kernel(glrtx_ctx *c, bool ext, int lds, PersistLaunch &k) {
-    const bool tex = c->n_tex > 0, maps = tex && c->have_maps;  // (maps: bound on top of the set, glrtx_bind_material_maps; without them the TEX forms as ever)
-    k.vol = (c->ext_flags & GLRTX_EXT_VOLUME) != 0;  // (render_one has checked that a volume is uploaded, and that no environment is bound beside it)
-    k.env = c->have_env;
-    k.cut = tex && c->have_cut;  // (render_one has refused GLRTX_EXT_VOLUME beside bound cutouts)
-    k.emit = tex && c->have_emit;  // (never beside cutouts: each binding call refuses the other; render_one has refused GLRTX_EXT_VOLUME beside them)
-    const int form = k.emit ? (k.env ? kFormEnvTexEmit : kFormTexEmit) + (maps ? 1 : 0)
-                     : k.cut ? (k.env ? kFormEnvTexCut : kFormTexCut) + (maps ? 1 : 0)
-                     : k.env ? (maps ? kFormEnvTexMaps : tex ? kFormEnvTex : kFormEnv)
-                     : tex ? kFormTex + (k.vol ? 1 : 0) + (maps ? 2 : 0)
-                           : k.vol ? kFormVol : ext ? kFormExt : kFormPlain;
-    static_assert(kFormTexVol == kFormTex + 1 && kFormTexMaps == kFormTex + 2 && kFormTexVolMaps == kFormTex + 3, "the TEX rows: [maps][volume]");
-    static_assert(kFormTexMapsCut == kFormTexCut + 1 && kFormEnvTexMapsCut == kFormEnvTexCut + 1, "the CUT rows: [environment][maps]");
-    static_assert(kFormTexMapsEmit == kFormTexEmit + 1 && kFormEnvTexMapsEmit == kFormEnvTexEmit + 1, "the EMIT rows: [environment][maps]");
-    k.fn = kPersistent[form][c->count_rays];
-    k.name = kPersistentNames[form];
+// lds: the plain kernel's LDS bytes
+int persist_kernel(glrtx_ctx *c, const Route &route, int lds, PersistLaunch &k) {
+    k.fn = kPersistent[route.form][c->count_rays];
     k.ex = ExtArgs{};
-    if (tex) k.ex.tex = tex_set(c);
+    if (route.tex) k.ex.tex = tex_set(c);
     k.ex.spheres = (const float4 *)c->spheres.p; k.ex.sphere_mat = (const int *)c->sphereMat.p;
     k.ex.n_spheres = c->n_spheres; k.ex.flags = c->ext_flags;
-    k.lds = lds + (ext ? c->n_spheres * (int)sizeof(float4) : 0);  // extension kernel: the spheres are staged behind the stacks
+    k.lds = lds + (route.ext ? c->n_spheres * (int)sizeof(float4) : 0);  // extension kernel: the spheres are staged behind the stacks
     if (k.lds > 160 * 1024) return fail(c, GLRTX_EDEVICE, "render kernel needs %d B of LDS (> 160 KiB)", k.lds);
     if (k.lds > 64 * 1024) HIP_TRY(c, hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, k.lds));
     // grid = what is resident at once (occupancy x CUs), capped by the work available
@@ -1515,14 +1470,14 @@ int persist_kernel(glrtx_ctx *c, bool ext, int lds, PersistLaunch &k) {
     return GLRTX_OK;
 }
 
-int persist_launch(glrtx_ctx *c, const PersistLaunch &k, const KernelArgs &a, hipEvent_t ev0) {
+int persist_launch(glrtx_ctx *c, const Route &route, const PersistLaunch &k, const KernelArgs &a, hipEvent_t ev0) {
     HIP_TRY(c, hipMemsetAsync(c->work.p, 0, sizeof(unsigned), c->stream));
     HIP_TRY(c, hipEventRecord(ev0, c->stream));
-    c->last_kernel = k.name;
+    c->last_kernel = route.kernel;
     unsigned *work = (unsigned *)c->work.p;
-    const VolArgs va = k.vol ? c->vol : VolArgs{};  // the fourth argument: the volume's, or (kFormEnv*) the environment's
+    const VolArgs va = route.vol ? c->vol : VolArgs{};  // the fourth argument: the volume's, or (kFormEnv*) the environment's
     EnvArgs ea = c->env;
-    if (k.env) ea.p_env = c->sc.n_light == 0 ? 1.0f : c->env_cfg.light_pick;  // a scene without lights: the environment is the only light to pick
+    if (route.env) ea.p_env = c->sc.n_light == 0 ? 1.0f : c->env_cfg.light_pick;  // a scene without lights: the environment is the only light to pick
     // the CUT forms: the same fourth argument with the cutout tables appended behind it (pt_kernel.hip.h: CutTail)
     const CutSet cs{(const int *)c->cutTri.p, (const CutRec *)c->cutRec.p};
     const CutTail<VolArgs> va_cut{va, cs};
@@ -1531,8 +1486,8 @@ int persist_launch(glrtx_ctx *c, const PersistLaunch &k, const KernelArgs &a, hi
     const EmitSet es{(const int *)c->emitMat.p, (const float2 *)c->emitSt.p};
     const EmitTail<VolArgs> va_emit{va, es};
     const EmitTail<EnvArgs> ea_emit{ea, es};
-    void *const tail = k.emit ? (k.env ? (void *)&ea_emit : (void *)&va_emit)
-                       : k.cut ? (k.env ? (void *)&ea_cut : (void *)&va_cut) : (k.env ? (void *)&ea : (void *)&va);
+    void *const tail = route.emit ? (route.env ? (void *)&ea_emit : (void *)&va_emit)
+                       : route.cut ? (route.env ? (void *)&ea_cut : (void *)&va_cut) : (route.env ? (void *)&ea : (void *)&va);
     void *args[] = {(void *)&a, &work, (void *)&k.ex, tail};
     HIP_TRY(c, hipLaunchKernel(k.fn, dim3(k.grid), dim3(kBlockThreads), args, k.lds, c->stream));
     return GLRTX_OK;
@@ -1724,7 +1679,7 @@ int wgwf_args(glrtx_ctx *c, WgwfLaunch &L) {
 // buffers is a GPU memory fault, not an error code): every path id the launch can form indexes inside the state arrays;
 // every workgroup of the grid has its own queue slice; a slice holds both halves of the double-buffered ray queue
 // (2 rays per live path: the next ray and the shadow ray) and of the path-id queue; every (frame, sample) has its plane.
-int wgwf_check(glrtx_ctx *c, const WgwfLaunch &L) {
+int wgwf_check(glrtx_ctx *c, const WgwfLaunch &L, const Route &route) {
     const glrtx_params *p = L.p;
     const glrtx_ctx::PipeSlot *const slot = L.slot;
     const WfArgs &w = L.w;
@@ -1739,10 +1694,11 @@ int wgwf_check(glrtx_ctx *c, const WgwfLaunch &L) {
               block_paths <= kWgPathsMax && slice_f4 <= kWgQueueF4 && L.queueBuf->bytes >= (size_t)grid * kWgQueueF4 * sizeof(float4) &&
               L.stateBuf->bytes >= L.state_bytes && w.ids == state_entries && grid >= 1 && (size_t)grid <= L.k.wg_slots &&
               p->max_depth <= kWfDepthMax && p->n_samples <= kWfSampleMax && L.workPtr != nullptr;
-    if (L.k.vol) ok = ok && p->n_samples <= kWfVolSampleMax && c->ext_flags == GLRTX_EXT_VOLUME && c->have_volume && c->vol.density != nullptr &&
-                      c->vol.temperature != nullptr && c->n_spheres == 0 && !L.k.vine && L.k.fetch == 0 && !L.k.compact;
-    if (L.k.tex) ok = ok && c->n_tex > 0 && c->ext_flags == 0 && c->n_spheres == 0 && !c->have_env && !L.k.vine && !L.k.vol && L.k.fetch != 2 && c->texDesc.p != nullptr &&
-                      c->texTexels.p != nullptr && c->texSt.p != nullptr && c->texBind.p != nullptr && (!L.k.maps || c->texMaps.p != nullptr) && L.a.hit_hist == nullptr;
+    // the kernel that was picked serves the route's form (what may be bound beside a form is the route's business), and what that form reads is there
+    ok = ok && route.family == glrt_detail::kRouteWavefront && L.k.vol == route.vol && L.k.tex == route.tex && L.k.maps == route.maps && L.k.vine == route.vine;
+    if (route.vol) ok = ok && p->n_samples <= kWfVolSampleMax && c->vol.density != nullptr && c->vol.temperature != nullptr && !L.k.vine && L.k.fetch == 0 && !L.k.compact;
+    if (route.tex) ok = ok && !L.k.vine && !route.vol && L.k.fetch != 2 && c->texDesc.p != nullptr && c->texTexels.p != nullptr && c->texSt.p != nullptr &&
+                        c->texBind.p != nullptr && (!route.maps || c->texMaps.p != nullptr) && L.a.hit_hist == nullptr;
     if (!fed && n_frames > 1) ok = ok && c->wfSeeds.bytes >= (size_t)n_frames * sizeof(float2);
     if (w.planes) ok = ok && L.planeBuf->bytes >= (size_t)std::max(L.n_planes, 1) * L.plane_f4 * sizeof(float4);
     if (L.k.adapt) ok = ok && !fed && !slot && w.planes && c->ad_selected && c->ad_tiles == (int)(total >> 6) && c->adList.bytes >= (total >> 6) * sizeof(int) &&
@@ -1846,7 +1802,7 @@ int wgwf_issue(glrtx_ctx *c, const WgwfLaunch &L) {
     return GLRTX_OK;
 }
 
-int launch_wgwf(glrtx_ctx *c, const KernelArgs &a, const glrtx_params *p, const RenderReq &req) {
+int launch_wgwf(glrtx_ctx *c, const KernelArgs &a, const glrtx_params *p, const RenderReq &req, const Route &route) {
     WgwfLaunch L{};
     L.p = p; L.req = req; L.a = a; L.n_frames = req.n_frames;
     L.seeds_xy = req.n_frames == 1 ? p->seed : req.seeds;
@@ -1860,10 +1816,10 @@ int launch_wgwf(glrtx_ctx *c, const KernelArgs &a, const glrtx_params *p, const 
     L.f = wgwf_form(c, L);
     L.ids = L.total * (size_t)(L.f.fed ? L.f.fed_cap : L.n_frames);  // path id = frame * total + pixel
     if (L.ids + 1 >= (size_t)UINT32_MAX) return fail(c, GLRTX_EINVAL, "glrtx_render_frames: %d frames of %zu pixels exceed the 32-bit ray id space", L.n_frames, L.total);
-    if (int rc = wgwf_kernel(c, L)) return rc;
+    if (int rc = wgwf_kernel(c, L, route)) return rc;
     if (int rc = wgwf_pipe_slot(c, L)) return rc;
     if (int rc = wgwf_args(c, L)) return rc;
-    if (int rc = wgwf_check(c, L)) return rc;
+    if (int rc = wgwf_check(c, L, route)) return rc;
     return wgwf_issue(c, L);
 }
 
@@ -2020,16 +1976,6 @@ int reproject_motion_pass(glrtx_ctx *c, hipStream_t stream, const reproject::Com
 }
 
 
-// What the wavefront-only calls (adaptive, moments, cascades) say while a texture set is bound and the launch would NOT run on the wavefront kernel's T / TM forms
-// (wgwf_routes): "textures are bound", and the reason -- the switch, what else is on, the tree, the variant, the path state's range.  GLRTX_OK: no set, or it routes.
-int tex_refusal(glrtx_ctx *c, const glrtx_params *p, const char *fn, const char *tail) {
-    if (c->n_tex == 0) return GLRTX_OK;
-    const char *why = nullptr;
-    if (tex_wavefront(c, &why)) why = c->variant != 2 ? "the context's variant is not 2" : !wgwf_can_hold(p) ? "max_depth / n_samples beyond the wavefront kernel's path state" : nullptr;
-    if (!why) return GLRTX_OK;
-    return fail(c, GLRTX_EINVAL, "%s: textures are bound and the wavefront kernel does not shade them here: %s (%s)", fn, why, tail);
-}
-
 // ---- adaptive sampling (glrtx_render_adaptive)
 // Everything glrtx_render_adaptive refuses, checked before anything changes.  The megakernels have no tile list and the present ring no adaptive form.
 int adapt_check(glrtx_ctx *c, const glrtx_params *p, const float *seeds_xy, int n_frames, const glrtx_adaptive *cfg) {
@@ -2041,14 +1987,7 @@ int adapt_check(glrtx_ctx *c, const glrtx_params *p, const float *seeds_xy, int 
     if (!c->accum || c->width < 1) return fail(c, GLRTX_EINVAL, "%s: no accumulator (call glrtx_resize)", fn);
     if (p->n_samples < 0 || p->max_depth < 0) return fail(c, GLRTX_EINVAL, "%s: negative n_samples/max_depth", fn);
     if (c->pres.ring > 0) return fail(c, GLRTX_EINVAL, "%s: presentation is enabled (the present ring has no adaptive form)", fn);
-    if (int rc = tex_refusal(c, p, fn, "only the wavefront kernel has a tile list")) return rc;
-    const bool vol = vol_wavefront(c);  // the volume alone, with the V form switched on: the wavefront kernel runs it
-    if (c->ext_flags != 0 && !vol) return fail(c, GLRTX_EINVAL, "%s: extensions or volume are on (only the wavefront kernel has a tile list)", fn);
-    if (c->n_spheres > 0) return fail(c, GLRTX_EINVAL, "%s: spheres are uploaded (only the wavefront kernel has a tile list)", fn);
-    if (c->have_env) return fail(c, GLRTX_EINVAL, "%s: an environment is bound (only the wavefront kernel has a tile list)", fn);
-    if (c->variant != 2) return fail(c, GLRTX_EINVAL, "%s: variant %d (only the wavefront kernel, variant 2, has a tile list)", fn, c->variant);
-    if (!wgwf_can_hold(p, vol)) return fail(c, GLRTX_EINVAL, "%s: max_depth %d / n_samples %d beyond the wavefront kernel's path state", fn, p->max_depth, p->n_samples);
-    return GLRTX_OK;
+    return route_refusal(c, route_of(c, p, RenderReq::Adaptive), fn);  // what only the wavefront kernel can do: it has the tile list
 }
 
 // The selection, on the context's stream behind everything issued before: mask, ascending list and count of the active tiles.  from_moments
@@ -2088,13 +2027,7 @@ int side_plane_check(glrtx_ctx *c, const glrtx_params *p, const float *seeds_xy,
     if (!c->accum || c->width < 1) return fail(c, GLRTX_EINVAL, "%s: no accumulator (call glrtx_resize)", fn);
     if (p->n_samples < 0 || p->max_depth < 0) return fail(c, GLRTX_EINVAL, "%s: negative n_samples/max_depth", fn);
     if (c->pres.ring > 0) return fail(c, GLRTX_EINVAL, "%s: presentation is enabled (the present ring's passes fold neither moments nor cascades)", fn);
-    if (int rc = tex_refusal(c, p, fn, "the megakernel that shades them writes no sample planes")) return rc;
-    if (c->ext_flags != 0) return fail(c, GLRTX_EINVAL, "%s: extensions or volume are on", fn);
-    if (c->n_spheres > 0) return fail(c, GLRTX_EINVAL, "%s: spheres are uploaded", fn);
-    if (c->have_env) return fail(c, GLRTX_EINVAL, "%s: an environment is bound (the megakernel that shades it writes no sample planes)", fn);
-    if (c->variant != 2) return fail(c, GLRTX_EINVAL, "%s: variant %d (only the wavefront kernel, variant 2, writes sample planes)", fn, c->variant);
-    if (!wgwf_can_hold(p, false)) return fail(c, GLRTX_EINVAL, "%s: max_depth %d / n_samples %d beyond the wavefront kernel's path state", fn, p->max_depth, p->n_samples);
-    return GLRTX_OK;
+    return route_refusal(c, route_of(c, p, RenderReq::Moments), fn);  // what only the wavefront kernel can do: it writes the sample planes (one list for the three calls)
 }
 
 int moments_check(glrtx_ctx *c, const glrtx_params *p, const float *seeds_xy, int n_frames, const char *fn = "glrtx_render_moments") {
@@ -4012,14 +3945,14 @@ int glrtx_set_shadow_range_limit(glrtx_ctx *c, int enable) {
 int glrtx_set_volume_wavefront(glrtx_ctx *c, int enable) {
     if (!c) return GLRTX_EINVAL;
     seal_feed(c);  // (nothing is appended to an open launch across this call: glrtx_ctx::OpenFeed)
-    c->vol_wavefront = enable != 0;  // read by the next launch (render_one: vol_wavefront)
+    c->vol_wavefront = enable != 0;  // read by the next launch (route_of)
     return GLRTX_OK;
 }
 
 int glrtx_set_texture_wavefront(glrtx_ctx *c, int enable) {
     if (!c) return GLRTX_EINVAL;
     seal_feed(c);  // (nothing is appended to an open launch across this call: glrtx_ctx::OpenFeed)
-    c->tex_wavefront = enable != 0;  // read by the next launch (render_one: tex_wavefront)
+    c->tex_wavefront = enable != 0;  // read by the next launch (route_of)
     return GLRTX_OK;
 }
 
@@ -4053,7 +3986,7 @@ int glrtx_render_frames(glrtx_ctx *c, const glrtx_params *p, const float *seeds_
     if (n_frames < 0 || (n_frames > 0 && !seeds_xy)) return fail(c, GLRTX_EINVAL, "glrtx_render_frames: bad seeds/n_frames");
     if (n_frames == 0) return GLRTX_OK;
     if (int rc = present_prepare(c, n_frames)) return rc;  // (GLRTX_EBUSY: nothing has changed)
-    if (n_frames == 1 || !wgwf_routes(c, p)) return render_helpings(c, p, seeds_xy, n_frames, 1, RenderReq::Ordinary);  // the megakernels have no frames-in-flight form: one launch per frame
+    if (n_frames == 1 || !on_wavefront(route_of(c, p, RenderReq::Ordinary))) return render_helpings(c, p, seeds_xy, n_frames, 1, RenderReq::Ordinary);  // the megakernels have no frames-in-flight form: one launch per frame
     HIP_TRY(c, hipSetDevice(c->device));
     // A launch of the same camera that is still open takes the frames itself (feed_append); otherwise they are issued as launches of at most `most` frames -- what the
     // frames-in-flight memory budget allows (frames_cap) -- of equal size, in order; each of them stays open for the next call.  An allocation that fails is reported,
@@ -4991,15 +4924,10 @@ static int render_one(glrtx_ctx *c, const glrtx_params *p, const RenderReq &req)
     if (!c->have_scene) return fail(c, GLRTX_EINVAL, "glrtx_render: no scene uploaded");
     if (!c->accum || c->width < 1) return fail(c, GLRTX_EINVAL, "glrtx_render: no accumulator (call glrtx_resize)");
     if (p->n_samples < 0 || p->max_depth < 0) return fail(c, GLRTX_EINVAL, "glrtx_render: negative n_samples/max_depth");
-    if ((c->ext_flags & GLRTX_EXT_VOLUME) && !c->have_volume) return fail(c, GLRTX_EINVAL, "glrtx_render: GLRTX_EXT_VOLUME is set and no volume is uploaded (glrtx_upload_volume)");
-    if ((c->ext_flags & GLRTX_EXT_VOLUME) && c->have_env)
-        return fail(c, GLRTX_EINVAL, "glrtx_render: GLRTX_EXT_VOLUME is set and an environment is bound (the volume branch has its own escape path)");
-    if ((c->ext_flags & GLRTX_EXT_VOLUME) && c->have_volume && c->n_tex > 0 && c->have_cut)
-        return fail(c, GLRTX_EINVAL, "glrtx_render: GLRTX_EXT_VOLUME is set and cutouts are bound (the volume kernels have no cutout form)");
-    if ((c->ext_flags & GLRTX_EXT_VOLUME) && c->have_volume && c->n_tex > 0 && c->have_emit)
-        return fail(c, GLRTX_EINVAL, "glrtx_render: GLRTX_EXT_VOLUME is set and emission maps are bound (the volume kernels have no emission-map form)");
+    const Route route = route_of(c, p, req.kind);  // once; everything below reads it
+    if (int rc = route_refusal(c, route, "glrtx_render")) return rc;  // (a call of another kind has asked for its own list before it got here: what is left is the volume's)
     HIP_TRY(c, hipSetDevice(c->device));
-    const bool wavefront = wgwf_routes(c, p);
+    const bool wavefront = on_wavefront(route);
     if (c->owned_rows > 0 && wavefront && req.kind == RenderReq::Ordinary && req.n_frames == 1 && feed_append(c, p, p->seed, 1) == 1) {  // a launch of the same camera that is still open takes the frame itself
         c->last_was_render = true; c->last_p = *p;
         return presenting(c) ? present_issue(c, 1) : GLRTX_OK;
@@ -5035,41 +4963,26 @@ static int render_one(glrtx_ctx *c, const glrtx_params *p, const RenderReq &req)
     if ((size_t)a.pitch_f4 * (size_t)c->owned_rows >= (size_t)INT32_MAX)
         return fail(c, GLRTX_EINVAL, "accumulator too large for 32-bit pixel offsets");
 
-    // The wavefront variant packs depth and sample index into one word of the path state (kWfDepthMax, kWfSampleMax);
-    // a launch beyond those ranges runs on the persistent megakernel instead (bit-identical, no packed state).
-    // Extensions (analytic spheres, dielectric, Whitted termination) exist only in the persistent megakernel's EXT instantiation.
-    // The volume alone goes to the wavefront kernel's V form when that is switched on (glrtx_set_volume_wavefront), within its narrower sample range (kWfVolSampleMax).
-    const bool tex = c->n_tex > 0;  // a bound texture set: the extension megakernel's TEX forms
-    const bool envb = c->have_env;  // a bound environment: the extension megakernel's ENV forms
-    // A texture set alone (material maps included) goes to the wavefront kernel's T / TM forms when those are switched on (glrtx_set_texture_wavefront): such a
-    // launch needs no extension kernel and is no fallback.
-    const bool tex_wf = tex && wavefront;  // (wgwf_routes, above; anything else runs as it did: the textured megakernel, GLRTX_FALLBACK_EXTENSIONS)
-    const bool ext = c->n_spheres > 0 || c->ext_flags != 0 || (tex && !tex_wf) || envb;
-    const bool vol_wf = vol_wavefront(c);
-    const int variant = ((ext && !vol_wf) || (vol_wf && c->variant != 2) || (c->variant == 2 && !wgwf_can_hold(p, vol_wf))) ? 1 : c->variant;
-    c->st.variant_last = variant;
-    c->st.fallback_last = 0;
-    if (c->variant == 2 && variant != 2) {  // not silently: the reason and a count are in the stats
-        c->st.fallback_last = (ext && !vol_wf ? GLRTX_FALLBACK_EXTENSIONS : 0) | (p->max_depth > kWfDepthMax ? GLRTX_FALLBACK_DEPTH : 0) |
-                              (p->n_samples > (vol_wf ? kWfVolSampleMax : kWfSampleMax) ? GLRTX_FALLBACK_SAMPLES : 0);
-        c->st.fallback_launches++;
-    }
-    if (variant == 2) {
-        const int rc = launch_wgwf(c, a, p, req);
+    // The kernel family, and -- not silently -- why variant 2 was left and a count of such launches: the route's
+    c->st.variant_last = route.family;
+    c->st.fallback_last = route.fallback;
+    if (route.fallback_counts) c->st.fallback_launches++;
+    if (wavefront) {
+        const int rc = launch_wgwf(c, a, p, req, route);
         if (rc == GLRTX_OK) { c->last_was_render = true; c->last_p = *p; } else seal_feed(c);
         return rc;
     }
     glrtx_ctx::LaunchRec *rec = nullptr;
     if (int rc = next_launch_rec(c, rec)) return rc;
-    if (variant == 1) {
+    if (route.family == glrt_detail::kRoutePersistent) {
         PersistLaunch k;
-        if (int rc = persist_kernel(c, ext, lds, k)) return rc;
-        if (int rc = persist_launch(c, k, a, rec->ev0)) return rc;
+        if (int rc = persist_kernel(c, route, lds, k)) return rc;
+        if (int rc = persist_launch(c, route, k, a, rec->ev0)) return rc;
     } else {
         static constexpr void (*kTileKernel[2])(const KernelArgs) = {pt_render_kernel<false>, pt_render_kernel<true>};  // [count_rays]
         const auto tk = kTileKernel[c->count_rays];
         HIP_TRY(c, hipEventRecord(rec->ev0, c->stream));
-        c->last_kernel = "pt_render_kernel";
+        c->last_kernel = route.kernel;
         if (lds > 64 * 1024) HIP_TRY(c, hipFuncSetAttribute((const void *)tk, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
         hipLaunchKernelGGL(tk, dim3(a.n_tiles), dim3(kBlockThreads), lds, c->stream, a);
     }
@@ -5169,11 +5082,7 @@ int glrtx_hit_histogram(glrtx_ctx *c, const glrtx_params *p, uint32_t *hist_out,
     if (!c->have_scene) return fail(c, GLRTX_EINVAL, "glrtx_hit_histogram: no scene uploaded");
     if (!c->accum || c->width < 1 || c->owned_rows < 1) return fail(c, GLRTX_EINVAL, "glrtx_hit_histogram: no image size (call glrtx_resize)");
     if (n_tri != (size_t)c->n_tri) return fail(c, GLRTX_EINVAL, "glrtx_hit_histogram: the scene has %d triangles, room for %zu", c->n_tri, n_tri);
-    if (c->n_tex > 0 && c->have_cut) return fail(c, GLRTX_EINVAL, "glrtx_hit_histogram: textures are bound and cutouts are bound (wavefront kernel only)");
-    if (c->n_tex > 0 && c->have_emit) return fail(c, GLRTX_EINVAL, "glrtx_hit_histogram: textures are bound and emission maps are bound (wavefront kernel only)");
-    if (c->n_tex > 0) return fail(c, GLRTX_EINVAL, "glrtx_hit_histogram: textures are bound (wavefront kernel only)");
-    if (c->have_env) return fail(c, GLRTX_EINVAL, "glrtx_hit_histogram: an environment is bound (wavefront kernel only)");
-    if (c->variant != 2 || !wgwf_can_hold(p) || c->n_spheres > 0 || c->ext_flags != 0) return fail(c, GLRTX_EINVAL, "glrtx_hit_histogram: wavefront kernel only");
+    if (int rc = route_refusal(c, route_of(c, p, RenderReq::Calibration), "glrtx_hit_histogram")) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     if (int rc = glrtx_sync(c)) return rc;
     const size_t n_rec = c->leaf_tri.size() + 1;

@@ -78,6 +78,7 @@ def lib():
         L.glrt_light_emission.argtypes = [fp, C.c_size_t, fp, C.c_size_t, fp, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, i32p, i32p, fp, C.c_size_t, fp]
         L.glrt_emission_albedo.argtypes = [fp, C.c_size_t, fp, C.c_size_t, fp, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, i32p, i32p, fp, C.c_size_t, fp]
         L.glrt_emission_bind_check.argtypes = [fp, C.c_size_t, C.c_size_t, C.c_int, i32p, C.c_size_t, C.c_char_p, C.c_size_t]
+        L.glrt_launch_route.argtypes = [C.POINTER(RouteState), C.c_int, C.POINTER(Route), C.c_char_p, C.c_size_t]
         L.glrt_surface_create.argtypes = [fp, C.c_size_t, fp, C.c_size_t, fp, C.c_size_t, fp, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, i32p, C.c_void_p,
                                           i32p, C.POINTER(C.c_void_p)]
         L.glrt_surface_free.restype = None
@@ -771,6 +772,34 @@ def emission_bind_check(scene, n_tex, material_emission, cutouts_bound=False):
     if (rc == 0) != (text == ""):
         raise RuntimeError(f"glrt_emission_bind_check: {rc} with the message {text!r}")
     return text
+
+
+ROUTE_KINDS = ("ordinary", "adaptive", "moments", "calibration", "adaptive_moments", "cascades")  # GLRT_ROUTE_*: the device's render calls
+
+
+class RouteState(C.Structure):
+    """glrt_route_state: the context fields and parameters that decide a launch's route."""
+    _fields_ = [(k, C.c_int32) for k in ("variant", "ext_flags", "n_spheres", "n_tex", "n_vine", "have_volume", "have_maps", "have_cut", "have_emit", "have_env",
+                                         "vol_switch", "tex_switch", "max_depth", "n_samples")]
+
+
+class Route(C.Structure):
+    """glrt_route"""
+    _fields_ = [(k, C.c_int32) for k in ("family", "variant_last", "fallback_last", "fallback_counts", "form")] + [("kernel", C.c_char * 96)]
+
+
+def launch_route(state, kind="ordinary"):
+    """glrt_launch_route: the route of a render call (`kind`: one of ROUTE_KINDS) on a context in `state` -- a RouteState, or a dict of its fields (variant
+    defaults to 2, max_depth to 2, n_samples to 1, the rest to 0).  Returns (route, refusal): the Route and "", or None and the device's message behind its
+    "<function>: " when the call refuses."""
+    if not isinstance(state, RouteState):
+        state = RouteState(**{"variant": 2, "max_depth": 2, "n_samples": 1, **{k: int(v) for k, v in state.items()}})
+    out, msg = Route(), C.create_string_buffer(320)
+    rc = lib().glrt_launch_route(C.byref(state), ROUTE_KINDS.index(kind) if isinstance(kind, str) else int(kind), C.byref(out), msg, 320)
+    text = msg.value.decode()
+    if rc not in (0, -1) or (rc == 0) != (text == ""):
+        raise RuntimeError(f"glrt_launch_route: {rc} with the message {text!r}")
+    return (out, "") if rc == 0 else (None, text)
 
 
 def render_features_geom_cutout(scene, params, textures, material_texture, cut, width=None, height=None, rank=0, world=1, stripe=16):
